@@ -8,6 +8,7 @@ GPU, the rank's own samples already resident in HBM when the timed region starts
 
   python bench.py --gpus 1 --steps 20 --warmup 3            (default: C3, the BASELINE headline)
   python bench.py --config c2|c4|c5|online                  (the other BASELINE.json configs, 1 GPU)
+  python bench.py --dump-outputs DIR                        (also write the last timed step's results as DIR/*.npy)
   python bench.py --gpus N                                  (starts N ranks itself, see below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
@@ -118,7 +119,13 @@ def parse():
                     help="PCIe-inclusive variants (N=1, not the contract number): chunks start in pinned host "
                          "memory every step; 'sync' = vsom_upload_chunk, 'overlap' = prefetch of chunk i+1 "
                          "beside the epoch of chunk i (vsom_prefetch_chunk / vsom_commit_chunk)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (map, sigmaMap, SMap, "
+                         "weightMap, bmuHits, lastBMU, MSE) as DIR/<name>.npy; inputs are seeded, so two builds compare "
+                         "output for output")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = dict(CONFIGS[args.config])
     for k in ("map", "dim", "chunk", "sigma"):
         if getattr(args, k) is not None:
@@ -181,6 +188,32 @@ def make_map(cfg, depth, variant="uint8_sparse"):
         m = gen.random_map(n, depth, seed=42, scale=1.0) * np.float32(100.0) + np.float32(100.0)
         return m if variant == "uint8_sparse" else (m / np.float32(255.0)).astype(np.float32)
     return gen.random_map(n, depth, seed=42)
+
+
+DUMP_MAX_ELEMS = 1 << 22   # per node x depth array (16 MB of float32): three of them + the per-node vectors stay under 64 MB
+DUMP_SEED = 20240601
+
+
+def dump_outputs(out_dir, state, last_bmu, mse):
+    """What a caller of the timed path receives after its last step, as float32 / float64 .npy files.  The
+    node x depth arrays keep every row when they fit DUMP_MAX_ELEMS, else a fixed seeded sample of node rows
+    (the same for every run of the same configuration; `node_index.npy` lists them).  Integer outputs (bmuHits,
+    lastBMU, node indices) go out as float64, exact below 2^53."""
+    os.makedirs(out_dir, exist_ok=True)
+    n, d = state["map"].shape
+    if n * d <= DUMP_MAX_ELEMS:
+        rows = np.arange(n)
+    else:
+        rows = np.sort(np.random.default_rng(DUMP_SEED).choice(n, DUMP_MAX_ELEMS // d, replace=False))
+    arrays = {"node_index": rows.astype(np.float64),
+              "map": state["map"][rows], "sigma_map": state["sigma"][rows], "s_map": state["S"][rows],
+              "weight_map": state["weight"], "bmu_hits": state["hits"].astype(np.float64),
+              "last_bmu": np.asarray(last_bmu).astype(np.float64), "mse": np.array([mse], np.float32)}
+    for name, a in arrays.items():
+        a = np.ascontiguousarray(a)
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(arrays)
 
 
 def cpu_baseline(args, X_host, init_map, online=False):
@@ -422,7 +455,7 @@ def main():
     # per-phase breakdown (`kernel_ms_per_step`)
     dominant = "online" if online else "update"
 
-    def timed(sp, nwarm, nsteps, groups=(dominant,), keep_pending=False):
+    def timed(sp, nwarm, nsteps, groups=(dominant,), keep_pending=False, capture=None):
         if mode["pipelined"]:
             ctx.stage_next_device(sp.own[0].data_ptr(), sp.own[0].shape[0])   # the chunk of step 0
         for i in range(nwarm):
@@ -445,6 +478,8 @@ def main():
         dt = time.perf_counter() - t0
         tm = ctx.get_timing(reset=True)
         ctx.enable_timing(False)
+        if capture is not None:
+            capture()          # before the pending chunk is swapped out below: lastBMU still covers the last step's chunk
         if mode["pipelined"] and not keep_pending:
             # the context still holds step nsteps's chunk as "next" (a pointer into sp.own, possibly staged ahead): swap in
             # an empty one, so that the caller may free sp.own
@@ -461,7 +496,13 @@ def main():
     # the library applies the contracted modes to the chains that have one (vsom_hip.h, vsom_update_mode)
     mode_of = {"contracted": capi.UPDATE_FMA, "strict": capi.UPDATE_STRICT, "sigma": capi.UPDATE_FMA_SIGMA}
     ctx.set_update_mode(mode_of[args.arith])
-    dt, timing = timed(split, args.warmup, args.steps)
+    dumped = {}
+
+    def capture():
+        if args.dump_outputs and rank == 0:
+            dumped["files"] = dump_outputs(args.dump_outputs, ctx.get_state(), ctx.get_last_bmu(), ctx.get_mse())
+
+    dt, timing = timed(split, args.warmup, args.steps, capture=capture)
     mse = float(ctx.get_mse())
     sl_stats = ctx.shortlist_stats() if not online else None
     onl_stats = ctx.online_search_stats() if online else None
@@ -658,6 +699,8 @@ def main():
             "mse_last": mse,
             "bmu_shortlist_last": sl_stats,
         }
+        if dumped:
+            out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped["files"]}
         if onl_stats is not None:
             n_s = max(onl_stats["samples"], 1)
             out["online_search"] = {
@@ -768,6 +811,8 @@ def main_group(args):
 
     dt, tm = timed(args.warmup, args.steps)
     steps = args.steps
+    dumped = (dump_outputs(args.dump_outputs, grp.get_state(), grp.get_last_bmu(), grp.get_mse())
+              if args.dump_outputs else None)
     upd_ms, upd_cnt = tm["update"]
     upd_avg_s = upd_ms / max(upd_cnt, 1) / 1e3
     n_nodes0 = (W * H) // n
@@ -794,6 +839,8 @@ def main_group(args):
         "kernel_ms_per_step_member0": {k: round(v[0] / steps, 4) for k, v in tm.items()},
         "mse_last": float(grp.get_mse()),
     }
+    if dumped:
+        out["dumped_outputs"] = {"dir": args.dump_outputs, "files": dumped}
     print(json.dumps(out), flush=True)
     grp.close()
 

@@ -5,7 +5,7 @@ The reference cannot be built or imported here (C++ needing Eigen/doctest/sqlite
 so these vectors are ORACLE outputs (parity unpinned, see oracle/vsom_oracle.h): they freeze the
 oracle's behaviour (regression) and give the HIP path fixed expected outputs that do not depend on
 the oracle being rebuilt.  Inputs are seeded (tests/gen.py) or the reference's own 20-row SQLite
-fixture (ican_fixture.json, extracted with `--fixture` where /root/reference exists).
+fixture (ican_fixture.json, extracted with `--fixture` from the stored copy tests/golden/testDb.sq3).
 
   python tests/golden/make_goldens.py            # rewrite *.npz
   python tests/golden/make_goldens.py --fixture  # also re-extract ican_fixture.json
@@ -25,7 +25,7 @@ from oracle import pyoracle as po  # noqa: E402
 
 def extract_fixture():
     import sqlite3
-    c = sqlite3.connect("file:/root/reference/tests/performance/data/testDb.sq3?mode=ro", uri=True)
+    c = sqlite3.connect("file:" + os.path.join(HERE, "testDb.sq3") + "?mode=ro", uri=True)
     rows = [list(r[1:]) for r in c.execute("select Id,A,B,C,D,E,F,G,H,I from Ican order by Id")]
     json.dump({"_doc": "Rows of table Ican in the reference's tests/performance/data/testDb.sq3 "
                        "(data fixture) and its column spec (columnSpec.txt, perf_tests.cpp:35-58)",

@@ -78,3 +78,50 @@ def test_group_front_end_line():
 def test_online_line_is_bandwidth_priced():
     d = _run("--config", "online", "--map", "32", "--chunk", "64", "--steps", "2", "--warmup", "1", "--cpu-seconds", "1")
     assert d["roofline"]["bound"] == "hbm" and d["roofline"]["unit"] == "GB/s" and d["value"] > 0
+
+
+def test_dump_outputs_are_the_timed_steps_results(tmp_path):
+    """--dump-outputs DIR: what the timed path computed in its last step, as float32 / float64 .npy files; two runs
+    with the same arguments write the same bytes, and they are what the CPU oracle computes over the same
+    warmup + timed steps (chunk k of the run is chunk k % nchunks, every step a full findBmu + update)"""
+    import importlib.util
+    import numpy as np
+    from oracle import pyoracle as po
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+
+    warmup, steps, nchunks, side, B, sigma = 2, 3, 2, 16, 256, 4.0
+    args = ["--map", str(side), "--chunk", str(B), "--sigma", str(sigma), "--steps", str(steps), "--warmup", str(warmup),
+            "--nchunks", str(nchunks), "--no-cpu", "--no-other-arith", "--no-data-variants"]
+    dumps = []
+    for run in ("a", "b"):
+        out = tmp_path / run
+        d = _run(*args, "--dump-outputs", str(out))
+        assert d["steps"] == steps and d["ms_per_step"] > 0
+        files = sorted(os.listdir(out))
+        assert files == sorted(f + ".npy" for f in d["dumped_outputs"]["files"])
+        assert sum(os.path.getsize(out / f) for f in files) <= 64 << 20
+        arrays = {f[:-4]: np.load(out / f) for f in files}
+        assert all(a.dtype in (np.float32, np.float64) for a in arrays.values())
+        dumps.append(arrays)
+    a, b = dumps
+    assert set(a) == set(b) and all(a[k].tobytes() == b[k].tobytes() for k in a)
+
+    cfg = dict(bench.CONFIGS["c3"], map=side, chunk=B, sigma=sigma)
+    orc = po.OracleSom(side, side, cfg["dim"], po.STANDARD)
+    orc.set_state(map=bench.make_map(cfg, orc.depth))
+    for k in range(warmup + steps):
+        lbo = np.zeros(B, np.uint64)
+        mse = orc.batch_epoch(bench.make_data(cfg, B, 3 + k % nchunks), lbo, sigma, True)
+    assert (a["node_index"] == np.arange(side * side)).all()
+
+    def same(x, ref):
+        x, ref = np.asarray(x, np.float32), np.asarray(ref, np.float32)
+        return bool(((x.view(np.uint32) == ref.view(np.uint32)) | (np.isnan(x) & np.isnan(ref))).all())
+
+    for k, ref in (("map", orc.map), ("sigma_map", orc.sigma), ("s_map", orc.S), ("weight_map", orc.weight)):
+        assert same(a[k], ref), k
+    assert (a["bmu_hits"] == orc.hits.astype(np.float64)).all()
+    assert (a["last_bmu"] == lbo.astype(np.float64)).all()
+    assert same(a["mse"], [mse])

@@ -168,18 +168,16 @@ def test_sqlite_column_spec_file(exe, tmp_path, ican):
     assert (got == rows.astype(np.float32)).all()
 
 
-REF_DATA = "/root/reference/tests/performance/data"
+REF_DATA = os.path.join(ROOT, "tests", "golden")
 
 
-@pytest.mark.skipif(not os.path.exists(os.path.join(REF_DATA, "testDb.sq3")),
-                    reason="the reference tree is not present (GPU box): its fixture files cannot be opened")
 @pytest.mark.parametrize("chunk", [0, 8])
 def test_reference_fixture_db_and_column_spec_opened_directly(exe, chunk):
-    """The ONE reference-held artefact for this path, read where it lies (never copied): the mirror's
-    SqliteDataLoader opens /root/reference/tests/performance/data/testDb.sq3 with the reference's own
-    columnSpec.txt -- the scenario of tests/performance/perf_tests.cpp:35-58,77-84 (table `ican`, columns A..I,
-    all weights 1, column E binary) -- and yields rows, names, weights and the binary flag equal to
-    tests/golden/ican_fixture.json, the data this repo's goldens were generated from."""
+    """The reference's own test data for this path, stored byte for byte under tests/golden
+    (testDb.sq3, columnSpec.txt from its tests/performance/data): the mirror's SqliteDataLoader opens
+    the database with the reference's column spec -- the scenario of tests/performance/perf_tests.cpp:35-58,77-84
+    (table `ican`, columns A..I, all weights 1, column E binary) -- and yields rows, names, weights and the
+    binary flag equal to tests/golden/ican_fixture.json, the data this repo's goldens were generated from."""
     fx = json.load(open(os.path.join(ROOT, "tests", "golden", "ican_fixture.json")))
     want = np.array(fx["rows"], np.float64).astype(np.float32)
     passes, other = parse(run(exe, "spec", os.path.join(REF_DATA, "testDb.sq3"), os.path.join(REF_DATA, "columnSpec.txt"),
