@@ -126,6 +126,35 @@ int vsom_device_count(void);
 int vsom_create(vsom_ctx **out, int device, uint32_t width, uint32_t height,
                 uint32_t in_len, int transform);
 void vsom_destroy(vsom_ctx *ctx);
+
+/* ---- caller-defined Transformation (reference include/Transformation.hpp:10-41; tests/test1.cpp builds one) -------
+ * The caller's Comparer / Stepper arrive as HIP device source that defines two pure functions, each evaluated per
+ * output element with read access to whole rows (J = sample length, D = model depth, R = residual length):
+ *   __device__ float vsom_compare(uint32_t r, const float *x, const float *model, const float *dispersion,
+ *                                 const float *value_weight, uint32_t J, uint32_t D);     element r < R of Comparer
+ *   __device__ float vsom_step(uint32_t d, const float *x, const float *model, const float *value_weight,
+ *                              uint32_t J, uint32_t D);                                   element d < D of Stepper
+ * x has J values, model and dispersion D, value_weight J (all 1: device samples are fully valid, weight 1).  The source
+ * is compiled with hipRTC for gfx950 (-O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt) together with
+ * generic search / batch / online kernels that evaluate the hooks exactly where Som.cpp calls Comparer / Stepper, with
+ * the fp32 operation order of the host path for custom hooks (host/src/vsom_custom.cpp): a device hook that computes
+ * what a host hook computes gives the same bits.  Hooks must be pure (the reference's second Stepper call of an update
+ * is taken to return the first one's values).
+ * vsom_create_custom: a compile error is VSOM_ERR_INVALID with the hipRTC log in vsom_last_error(); depth must be
+ * <= VSOM_CUSTOM_MAX_DEPTH (the batch update keeps a node's model, step and spread in LDS: 3 x D floats).
+ * On a custom context these work: vsom_set_state / vsom_get_state, vsom_upload_chunk(_async), vsom_get_last_bmu /
+ * vsom_set_last_bmu, vsom_get_sqres, vsom_bmu_batch, vsom_bmu_local_batch, vsom_find_bmu, vsom_find_local_bmu,
+ * vsom_dist_single, vsom_distances, vsom_batch_epoch(_async), vsom_get_mse, vsom_train_single,
+ * vsom_train_online_chunk(_acc, _fetch), vsom_residual_len (= R), vsom_prefetch_chunk / vsom_prefetch_wait /
+ * vsom_commit_chunk (the prefetch takes a host copy of the rows; the commit uploads it) and the plumbing (stream,
+ * depth, nodes, pointers, timing).  Everything else -- device-resident chunks, the split batch phases, restricted and raw
+ * distances, compaction, dedupe, shortlist statistics, non-strict update modes -- returns VSOM_ERR_INVALID and leaves
+ * the context usable.  Custom contexts cannot join a group.  vsom_custom_compile_check compiles a hook source the
+ * same way without opening a device. */
+#define VSOM_CUSTOM_MAX_DEPTH 5120
+int vsom_create_custom(vsom_ctx **out, int device, uint32_t width, uint32_t height, uint32_t in_len,
+                       uint32_t depth, uint32_t residual_len, const char *hook_source);
+int vsom_custom_compile_check(const char *hook_source, uint32_t depth, uint32_t residual_len);
 /* adopt an external hipStream_t (NULL = back to the context's own stream) */
 int vsom_set_stream(vsom_ctx *ctx, void *hip_stream);
 int vsom_synchronize(vsom_ctx *ctx);

@@ -4,5 +4,5 @@ The directory name is not a Python identifier; import it through the `vsom_amd` 
 at the repository root (or importlib.import_module("variational-self-organizing-maps_amd")).
 """
 from . import capi  # noqa: F401
-from .capi import (BATCHMAP, CLR, EXPONENTIAL, INVERSE_PROPORTIONAL, MEDIAN, STANDARD,  # noqa: F401
+from .capi import (BATCHMAP, CLR, CUSTOM, EXPONENTIAL, INVERSE_PROPORTIONAL, MEDIAN, STANDARD,  # noqa: F401
                    Context, Group, VsomError)

@@ -17,6 +17,8 @@ _INTREE = os.path.join(_HERE, "libvsom_hip.so")
 LIB_PATH = os.environ.get("VSOM_LIB") or _INTREE
 
 STANDARD, MEDIAN, CLR = 0, 1, 2
+CUSTOM = -1        # a caller-defined transformation from device source (vsom_create_custom)
+CUSTOM_MAX_DEPTH = 5120     # VSOM_CUSTOM_MAX_DEPTH
 EXPONENTIAL, INVERSE_PROPORTIONAL, BATCHMAP = 0, 1, 2
 BMU_AUTO, BMU_EXACT, BMU_SHORTLIST = 0, 1, 2
 UPDATE_STRICT, UPDATE_FMA, UPDATE_FMA_SIGMA = 0, 1, 2
@@ -41,6 +43,7 @@ SYMBOLS = [
     "vsom_group_set_bmu_mode", "vsom_group_upload_chunk", "vsom_group_prefetch_chunk", "vsom_group_prefetch_wait",
     "vsom_group_commit_chunk", "vsom_group_set_chunk_device", "vsom_group_set_last_bmu", "vsom_group_get_last_bmu",
     "vsom_group_batch_epoch_async", "vsom_group_batch_epoch", "vsom_group_get_mse",
+    "vsom_create_custom", "vsom_custom_compile_check",
 ]
 
 
@@ -108,6 +111,9 @@ def lib():
     L.vsom_last_error.restype = C.c_char_p
     L.vsom_device_count.restype = C.c_int
     L.vsom_create.argtypes = [C.POINTER(vp), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_int]
+    L.vsom_create_custom.argtypes = [C.POINTER(vp), C.c_int, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32,
+                                     C.c_char_p]
+    L.vsom_custom_compile_check.argtypes = [C.c_char_p, C.c_uint32, C.c_uint32]
     L.vsom_destroy.argtypes = [vp]
     L.vsom_destroy.restype = None
     L.vsom_set_stream.argtypes = [vp, vp]
@@ -211,6 +217,12 @@ def device_count():
     return int(lib().vsom_device_count())
 
 
+def custom_compile_check(source, depth, residual_len):
+    """compile a hook source (include/vsom_hip.h, vsom_create_custom) for gfx950 without opening a device; raises
+    VsomError with the hipRTC log when it does not compile"""
+    check(lib().vsom_custom_compile_check(source.encode(), int(depth), int(residual_len)))
+
+
 def model_length(transform, in_len):
     """Transformation::Length (Transformation.cpp:33-36,71-74,162-165): J, or J(J-1) for CLR."""
     return int(in_len) * (int(in_len) - 1) if int(transform) == CLR else int(in_len)
@@ -247,12 +259,18 @@ class PinnedBuffer:
 class Context:
     """RAII wrapper of a vsom_ctx (one per GPU)."""
 
-    def __init__(self, width, height, in_len, transform=STANDARD, device=0, _borrowed=None):
+    def __init__(self, width, height, in_len, transform=STANDARD, device=0, _borrowed=None, source=None, depth=None,
+                 residual_len=None):
+        """transform=CUSTOM: `source` defines vsom_compare / vsom_step, `depth` and `residual_len` their lengths"""
         self._owned = _borrowed is None
         if _borrowed is None:
             self._h = C.c_void_p()
-            check(lib().vsom_create(C.byref(self._h), int(device), int(width), int(height), int(in_len),
-                                    int(transform)))
+            if int(transform) == CUSTOM:
+                check(lib().vsom_create_custom(C.byref(self._h), int(device), int(width), int(height), int(in_len),
+                                               int(depth), int(residual_len), source.encode()))
+            else:
+                check(lib().vsom_create(C.byref(self._h), int(device), int(width), int(height), int(in_len),
+                                        int(transform)))
         else:
             self._h = C.c_void_p(_borrowed)       # a member of a Group: the group owns it
         self.width, self.height, self.in_len = int(width), int(height), int(in_len)

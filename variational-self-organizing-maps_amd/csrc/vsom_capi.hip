@@ -155,6 +155,7 @@ int vsom_device_count(void)
 
 static int free_all(vsom_ctx *c)
 {
+    vsom_custom_destroy(c);
     void *ptrs[] = {c->map, c->sigma, c->S, c->weight, c->hits, c->Xs, c->XP, c->YP, c->Xraw,
                     c->lastbmu, c->sqres, c->pair_i, c->pair_j, c->partial, c->nan0,
                     c->cw, c->lut, c->lutd, c->sl_G, c->sl_nrm, c->sl_scal, c->sl_list, c->sl_tmin, c->sl_fs, c->sl_fm, c->v_dev, c->res_dev, c->onl_state, c->onl_f,
@@ -385,6 +386,7 @@ int vsom_set_bmu_mode(vsom_ctx *c, int mode)
 int vsom_get_shortlist_stats(vsom_ctx *c, uint32_t *out)
 {
     CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_get_shortlist_stats");
     if (!out)
         return vsom_fail(VSOM_ERR_INVALID, "null output");
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -397,6 +399,7 @@ int vsom_set_column_compaction(vsom_ctx *c, long min_rows)
 {
     if (!c)
         return vsom_fail(VSOM_ERR_INVALID, "null context");
+    VSOM_CUSTOM_REFUSE(c, "column compaction");
     c->cc_min_rows = min_rows;
     c->cc_skip = 0;
     return VSOM_OK;
@@ -406,6 +409,7 @@ int vsom_set_row_dedupe(vsom_ctx *c, double min_work)
 {
     if (!c)
         return vsom_fail(VSOM_ERR_INVALID, "null context");
+    VSOM_CUSTOM_REFUSE(c, "row dedupe");
     c->dd_min_work = min_work;
     return VSOM_OK;
 }
@@ -414,13 +418,15 @@ int vsom_set_update_mode(vsom_ctx *c, int mode)
 {
     if (!c || (mode != VSOM_UPDATE_STRICT && mode != VSOM_UPDATE_FMA && mode != VSOM_UPDATE_FMA_SIGMA))
         return vsom_fail(VSOM_ERR_INVALID, "bad update mode");
+    if (mode != VSOM_UPDATE_STRICT)
+        VSOM_CUSTOM_REFUSE(c, "a contracted update mode");
     c->update_mode = mode;
     return VSOM_OK;
 }
 
 uint32_t vsom_depth(const vsom_ctx *c) { return c ? c->D : 0; }
 uint32_t vsom_nodes(const vsom_ctx *c) { return c ? c->N : 0; }
-uint32_t vsom_residual_len(const vsom_ctx *c) { return c ? c->part_len : 0; }
+uint32_t vsom_residual_len(const vsom_ctx *c) { return c ? (c->cu ? vsom_custom_residual_len(c) : c->part_len) : 0; }
 size_t vsom_chunk_size(const vsom_ctx *c) { return c ? c->B : 0; }
 
 static bool all_zero_bits(const void *p, size_t bytes)
@@ -504,6 +510,8 @@ int vsom_set_state(vsom_ctx *c, const float *map, const float *sigma, const floa
         else
             VSOM_HIP_CHECK(hipMemcpyAsync(c->hits, bmu_hits, (size_t)c->N * 8, hipMemcpyHostToDevice, c->stream));
     }
+    if (c->cu && sigma)
+        return vsom_custom_after_set_state(c);     // (synchronises)
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
 }
@@ -576,6 +584,7 @@ static int ensure_chunk_capacity(vsom_ctx *c, size_t B)
 int vsom_set_chunk_device(vsom_ctx *c, const float *x_dev, size_t B)
 {
     CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_set_chunk_device");
     if (B > 0 && !x_dev)
         return vsom_fail(VSOM_ERR_INVALID, "x_dev is null");
     if (B > 0x7FFFFFFFull)
@@ -591,6 +600,8 @@ int vsom_set_chunk_device(vsom_ctx *c, const float *x_dev, size_t B)
 static int upload_chunk_impl(vsom_ctx *c, const float *x_host, size_t B, bool wait)
 {
     CHECK_CTX(c);
+    if (c->cu)
+        return vsom_custom_upload(c, x_host, B, wait);
     if (B > 0 && !x_host)
         return vsom_fail(VSOM_ERR_INVALID, "x_host is null");
     size_t need = B * c->J;
@@ -652,6 +663,10 @@ static int stage_ahead_if_possible(vsom_ctx *c, const float *x_dev, size_t B)
 
 int vsom_prefetch_chunk(vsom_ctx *c, const float *x_host, size_t B)
 {
+    if (c && c->cu) {
+        CHECK_CTX(c);
+        return vsom_custom_prefetch(c, x_host, B);
+    }
     int rc = vsom_prefetch_rows(c, x_host, B, 0, B);
     if (rc)
         return rc;
@@ -669,6 +684,7 @@ int vsom_prefetch_chunk(vsom_ctx *c, const float *x_host, size_t B)
 int vsom_stage_next_device(vsom_ctx *c, const float *x_dev, size_t B)
 {
     CHECK_CTX_NOJOIN(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_stage_next_device");
     if (B > 0 && !x_dev)
         return vsom_fail(VSOM_ERR_INVALID, "x_dev is null");
     if (B > 0x7FFFFFFFull)
@@ -683,12 +699,18 @@ int vsom_stage_next_device(vsom_ctx *c, const float *x_dev, size_t B)
 int vsom_prefetch_wait(vsom_ctx *c)
 {
     CHECK_CTX_NOJOIN(c);
+    if (c->cu)
+        return VSOM_OK;             // (the prefetch took a host copy)
     VSOM_HIP_CHECK(hipStreamSynchronize(c->copy_stream));
     return VSOM_OK;
 }
 
 int vsom_commit_chunk(vsom_ctx *c)
 {
+    if (c && c->cu) {
+        CHECK_CTX(c);
+        return vsom_custom_commit(c);
+    }
     if (c && c->next_dev_pending) {       // vsom_stage_next_device: adopt what was staged ahead, or stage it now
         CHECK_CTX(c);
         c->next_dev_pending = false;
@@ -772,6 +794,8 @@ static int copy_search_results(vsom_ctx *c, uint64_t *idx, float *dist)
 int vsom_bmu_batch(vsom_ctx *c, uint64_t *idx_out_host, float *dist_out_host)
 {
     CHECK_CTX(c);
+    if (c->cu)
+        return vsom_custom_bmu_batch(c, 0, idx_out_host, dist_out_host);
     CHECK_ROWS(c);
     int rc = launch_bmu_full(c, 0, c->B);
     if (rc)
@@ -782,6 +806,8 @@ int vsom_bmu_batch(vsom_ctx *c, uint64_t *idx_out_host, float *dist_out_host)
 int vsom_bmu_local_batch(vsom_ctx *c, uint64_t *idx_out_host, float *dist_out_host)
 {
     CHECK_CTX(c);
+    if (c->cu)
+        return vsom_custom_bmu_batch(c, 1, idx_out_host, dist_out_host);
     CHECK_ROWS(c);
     int rc = launch_bmu_local(c, 0, c->B);
     if (rc)
@@ -810,6 +836,8 @@ int vsom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *rows
                    float *dist_out_host)
 {
     CHECK_CTX(c);
+    if (c->cu)
+        return vsom_custom_distances(c, nodes_host, rows_host, count, dist_out_host);
     CHECK_ROWS(c);
     if (count == 0)
         return VSOM_OK;
@@ -838,6 +866,7 @@ int vsom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *rows
 int vsom_bmu_restricted_batch(vsom_ctx *c, uint64_t min_hits, uint64_t *idx_out_host, float *dist_out_host)
 {
     CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_bmu_restricted_batch");
     CHECK_ROWS(c);
     if (c->B == 0)
         return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
@@ -850,6 +879,7 @@ int vsom_bmu_restricted_batch(vsom_ctx *c, uint64_t min_hits, uint64_t *idx_out_
 int vsom_distances_row(vsom_ctx *c, size_t row, float *dist_out_host)
 {
     CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_distances_row");
     CHECK_ROWS(c);
     if (row >= c->B || !dist_out_host)
         return vsom_fail(VSOM_ERR_INVALID, "row out of range or null output");
@@ -868,6 +898,7 @@ int vsom_distances_raw(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *
                        int from_map, float *dist_out_host)
 {
     CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_distances_raw");
     if (!from_map)
         CHECK_ROWS(c);
     if (count == 0)
@@ -895,6 +926,7 @@ int vsom_distances_raw(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *
 int vsom_batch_phase1_async(vsom_ctx *c, size_t s0, size_t s1, int is_first)
 {
     CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_batch_phase1_async");
     CHECK_ROWS(c);
     if (s0 > s1 || s1 > c->B)
         return vsom_fail(VSOM_ERR_INVALID, "sample range out of bounds");
@@ -904,6 +936,7 @@ int vsom_batch_phase1_async(vsom_ctx *c, size_t s0, size_t s1, int is_first)
 int vsom_batch_finish_async(vsom_ctx *c)
 {
     CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_batch_finish_async");
     if (!c->chunk_loaded)   // an EMPTY chunk is legal: the reference's epoch then zeroes the map
         return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
     return launch_finish(c);
@@ -912,6 +945,7 @@ int vsom_batch_finish_async(vsom_ctx *c)
 int vsom_batch_phase2_async(vsom_ctx *c, double sigma, size_t n0, size_t n1)
 {
     CHECK_CTX_NOJOIN(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_batch_phase2_async");
     if (!c->xq_valid)             // (a further node range of the same epoch works on the transposed chunk it already has)
         CHECK_ROWS(c);
     if (n0 > n1 || n1 > c->N)
@@ -924,6 +958,8 @@ int vsom_batch_phase2_async(vsom_ctx *c, double sigma, size_t n0, size_t n1)
 int vsom_batch_epoch_async(vsom_ctx *c, double sigma, int is_first)
 {
     CHECK_CTX(c);
+    if (c->cu)
+        return vsom_custom_batch_epoch_async(c, sigma, is_first);
     CHECK_ROWS(c);
     if (!c->chunk_loaded)   // an EMPTY chunk is legal: the reference's epoch then zeroes the map
         return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");

@@ -1,0 +1,546 @@
+// vsom_custom.hip -- contexts of a caller-defined Transformation (vsom_create_custom): the caller's Comparer / Stepper
+// arrive as device source, are compiled with hipRTC together with the generic kernels of vsom_custom_kernels.inc and
+// run from the module loaded into the context.  The arithmetic is host/src/vsom_custom.cpp's, operation for operation.
+//
+// A custom context is an ordinary vsom_ctx (state, chunk rows, lastBMU, the pinned MSE word, the stream) whose
+// model rows are unpadded (pitch = D) and whose chunk rows are unpadded (xpitch = J); `cu` holds the rest.  The
+// entry points that accept a custom context route here from vsom_capi.hip / vsom_online.hip; all others refuse it.
+#include "vsom_internal.hpp"
+
+#include <hip/hiprtc.h>
+
+#include <cmath>
+#include <cstring>
+#include <new>
+#include <vector>
+
+namespace {
+
+const char *const kKernelText =
+#include "vsom_custom_kernels.inc"
+    ;
+
+// (hipRTC compiles without the HIP headers: the few types the contract names are declared here)
+const char *const kPrelude =
+    "typedef unsigned int uint32_t;\n"
+    "typedef unsigned long long uint64_t;\n"
+    "#line 1 \"hook_source\"\n";
+
+// hook source + generic kernels -> gfx950 code object; false with the hipRTC log in *log on failure
+bool compile_hooks(const char *hook_source, std::vector<char> &code, std::string &log)
+{
+    const std::string src = std::string(kPrelude) + hook_source + "\n#line 1 \"vsom_custom_kernels\"\n" + kKernelText;
+    hiprtcProgram prog;
+    if (hiprtcCreateProgram(&prog, src.c_str(), "vsom_custom.hip", 0, nullptr, nullptr) != HIPRTC_SUCCESS) {
+        log = "hiprtcCreateProgram failed";
+        return false;
+    }
+    const char *opts[] = {"--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off",
+                          "-fhip-fp32-correctly-rounded-divide-sqrt"};
+    const hiprtcResult rc = hiprtcCompileProgram(prog, (int)(sizeof(opts) / sizeof(opts[0])), opts);
+    size_t n = 0;
+    if (hiprtcGetProgramLogSize(prog, &n) == HIPRTC_SUCCESS && n > 1) {
+        std::vector<char> buf(n + 1, 0);
+        if (hiprtcGetProgramLog(prog, buf.data()) == HIPRTC_SUCCESS) {
+            buf[n] = 0;
+            log.assign(buf.data());
+        }
+    }
+    bool ok = rc == HIPRTC_SUCCESS;
+    if (ok) {
+        size_t sz = 0;
+        ok = hiprtcGetCodeSize(prog, &sz) == HIPRTC_SUCCESS && sz > 0;
+        if (ok) {
+            code.resize(sz);
+            ok = hiprtcGetCode(prog, code.data()) == HIPRTC_SUCCESS;
+        }
+    }
+    if (!ok && log.empty())
+        log = hiprtcGetErrorString(rc);
+    (void)hiprtcDestroyProgram(&prog);
+    return ok;
+}
+
+int check_shape(uint32_t depth, uint32_t residual_len, const char *hook_source)
+{
+    if (!hook_source || !*hook_source)
+        return vsom_fail(VSOM_ERR_INVALID, "hook_source is empty");
+    if (depth == 0 || residual_len == 0)
+        return vsom_fail(VSOM_ERR_INVALID, "depth and residual_len must be > 0");
+    if (depth > VSOM_CUSTOM_MAX_DEPTH)
+        return vsom_fail(VSOM_ERR_INVALID, "depth " + std::to_string(depth) + " exceeds VSOM_CUSTOM_MAX_DEPTH (" +
+                                               std::to_string(VSOM_CUSTOM_MAX_DEPTH) + "): the phase-2 model does not fit in LDS");
+    return VSOM_OK;
+}
+
+}   // namespace
+
+struct vsom_custom_state {
+    uint32_t R = 0;
+    hipModule_t mod = nullptr;
+    hipFunction_t k_floor = nullptr, k_full = nullptr, k_local = nullptr, k_pair = nullptr, k_resid = nullptr,
+                  k_finish = nullptr, k_phase2 = nullptr, k_onl_update = nullptr, k_onl_post = nullptr;
+    float *sigf = nullptr;        // [N][D] select(sigma < 1e-5, 1e-5, sigma): the dispersion the distance passes
+    float *ones = nullptr;        // [J] the value weights (valid * weights: every value of a device sample is valid, weight 1)
+    float *vec = nullptr;         // [J] one host vector (find / dist / train_single)
+    float *resid = nullptr;       // [R] train_single's residual
+    u64 *slot = nullptr;          // [2] one BMU index
+    float *fout = nullptr;        // [2] one distance
+    u64 *pairs = nullptr; float *pair_out = nullptr; size_t pair_cap = 0;
+    double *lutd = nullptr; double lutd_sigma = -1.0;   // [H][W] calculateNeighbourhoodWeight(dx, dy, 0, 0, sigma)
+    std::vector<float> next; size_t next_B = 0; bool next_pending = false;   // vsom_prefetch_chunk's rows until the commit
+};
+
+namespace {
+
+int launch(vsom_ctx *c, hipFunction_t f, unsigned grid, unsigned block, unsigned lds, std::vector<void *> args)
+{
+    if (grid == 0)
+        return VSOM_OK;
+    VSOM_HIP_CHECK(hipModuleLaunchKernel(f, grid, 1, 1, block, 1, 1, lds, c->stream, args.data(), nullptr));
+    return VSOM_OK;
+}
+
+int refresh_sigf(vsom_ctx *c)
+{
+    vsom_custom_state *u = c->cu;
+    u64 n = (u64)c->N * c->D;
+    const float *sg = c->sigma;
+    return launch(c, u->k_floor, (unsigned)((n + 255) / 256), 256, 0, {&sg, &u->sigf, &n});
+}
+
+int ensure_chunk(vsom_ctx *c, size_t B)
+{
+    if (B <= c->Bcap)
+        return VSOM_OK;
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    void **ptrs[] = {(void **)&c->Xs, (void **)&c->lastbmu, (void **)&c->sqres};
+    for (void **p : ptrs) {
+        if (*p)
+            (void)hipFree(*p);
+        *p = nullptr;
+    }
+    c->Bcap = 0;
+    c->B = 0;
+    c->chunk_loaded = false;
+    const size_t cap = (B + 63) / 64 * 64;
+    VSOM_HIP_CHECK(hipMalloc(&c->Xs, cap * c->J * 4));
+    VSOM_HIP_CHECK(hipMalloc(&c->lastbmu, cap * 8));
+    VSOM_HIP_CHECK(hipMalloc(&c->sqres, cap * 4));
+    c->Bcap = cap;
+    return VSOM_OK;
+}
+
+int stage_vec(vsom_ctx *c, const float *v_host)
+{
+    if (!v_host)
+        return vsom_fail(VSOM_ERR_INVALID, "null vector");
+    VSOM_HIP_CHECK(hipMemcpyAsync(c->cu->vec, v_host, (size_t)c->J * 4, hipMemcpyHostToDevice, c->stream));
+    return VSOM_OK;
+}
+
+// full search of `rows` sample rows starting at X
+int search_full(vsom_ctx *c, const float *X, unsigned rows, u64 *bmu, float *dist)
+{
+    vsom_custom_state *u = c->cu;
+    u64 xs = c->J;
+    uint32_t N = c->N, J = c->J, D = c->D, R = u->R;
+    return launch(c, u->k_full, rows, 256, 0, {&X, &xs, &c->map, &u->sigf, &u->ones, &N, &J, &D, &R, &bmu, &dist});
+}
+
+int search_local(vsom_ctx *c, const float *X, uint32_t rows, const u64 *start, u64 *bmu, float *dist)
+{
+    vsom_custom_state *u = c->cu;
+    u64 xs = c->J;
+    uint32_t W = c->W, H = c->H, J = c->J, D = c->D, R = u->R;
+    return launch(c, u->k_local, (rows + 63) / 64, 64, 0,
+                  {&X, &xs, &c->map, &u->sigf, &u->ones, &W, &H, &J, &D, &R, &start, &bmu, &dist, &rows});
+}
+
+int ensure_lutd(vsom_ctx *c, double sigma)
+{
+    vsom_custom_state *u = c->cu;
+    if (u->lutd_sigma == sigma)
+        return VSOM_OK;
+    std::vector<double> host((size_t)c->W * c->H);
+    for (uint32_t dy = 0; dy < c->H; ++dy)
+        for (uint32_t dx = 0; dx < c->W; ++dx)
+            host[(size_t)dy * c->W + dx] = vsom_neighbourhood_weight(dx, dy, 0, 0, sigma);
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));    // its previous contents may still be read
+    VSOM_HIP_CHECK(hipMemcpy(u->lutd, host.data(), host.size() * 8, hipMemcpyHostToDevice));
+    u->lutd_sigma = sigma;
+    return VSOM_OK;
+}
+
+// one trainSingle step of the sample at device address x (hostTrainSingle): search, window update, residual / distance;
+// bmu is the sample's lastBMU slot (in / out)
+int online_step(vsom_ctx *c, const float *x, double eta, double sigma, int decay_fn, u64 *bmu, float *resid, float *dist,
+                u64 *hits, float *mse, uint32_t B)
+{
+    vsom_custom_state *u = c->cu;
+    int rc = sigma > 1.0 ? search_full(c, x, 1, bmu, u->fout) : search_local(c, x, 1, bmu, bmu, u->fout);
+    if (rc)
+        return rc;
+    // a box of nx x ny workgroups covers the window: x1 - x0 <= floor(5 sigma) + 1
+    const double ext = std::floor(5.0 * sigma) + 2.0;
+    uint32_t nx = ext >= c->W ? c->W : (uint32_t)ext, ny = ext >= c->H ? c->H : (uint32_t)ext;
+    uint32_t W = c->W, H = c->H, J = c->J, D = c->D, R = u->R;
+    if ((rc = launch(c, u->k_onl_update, nx * ny, 256, 2 * D * 4,
+                     {&x, &c->map, &c->S, &c->sigma, &u->sigf, &c->weight, &bmu, &u->lutd, &W, &H, &u->ones, &J, &D,
+                      &eta, &sigma, &decay_fn, &nx})))
+        return rc;
+    return launch(c, u->k_onl_post, 1, 64, 0,
+                  {&x, &c->map, &c->sigma, &u->sigf, &u->ones, &J, &D, &R, &bmu, &resid, &dist, &hits, &mse, &B});
+}
+
+void free_custom(vsom_custom_state *u)
+{
+    void *ptrs[] = {u->sigf, u->ones, u->vec, u->resid, u->slot, u->fout, u->pairs, u->pair_out, u->lutd};
+    for (void *p : ptrs)
+        if (p)
+            (void)hipFree(p);
+    if (u->mod)
+        (void)hipModuleUnload(u->mod);
+    delete u;
+}
+
+}   // namespace
+
+void vsom_custom_destroy(vsom_ctx *c)
+{
+    if (c->cu)
+        free_custom(c->cu);
+    c->cu = nullptr;
+}
+
+uint32_t vsom_custom_residual_len(const vsom_ctx *c) { return c->cu->R; }
+
+int vsom_custom_refuse(const char *what)
+{
+    return vsom_fail(VSOM_ERR_INVALID, std::string(what) + " is not available on a custom-transformation context");
+}
+
+int vsom_custom_after_set_state(vsom_ctx *c)
+{
+    int rc = refresh_sigf(c);
+    if (rc)
+        return rc;
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VSOM_OK;
+}
+
+int vsom_custom_upload(vsom_ctx *c, const float *x_host, size_t B, bool wait)
+{
+    if (B > 0 && !x_host)
+        return vsom_fail(VSOM_ERR_INVALID, "x_host is null");
+    if (B > 0x7FFFFFFFull)
+        return vsom_fail(VSOM_ERR_INVALID, "chunk too large");
+    int rc = ensure_chunk(c, B);
+    if (rc)
+        return rc;
+    if (B) {
+        VSOM_HIP_CHECK(hipMemcpyAsync(c->Xs, x_host, B * c->J * 4, hipMemcpyHostToDevice, c->stream));
+        VSOM_HIP_CHECK(hipMemsetAsync(c->lastbmu, 0, B * 8, c->stream));     // DataSet.cpp:136-137
+        VSOM_HIP_CHECK(hipMemsetAsync(c->sqres, 0, B * 4, c->stream));
+    }
+    c->B = B;
+    c->chunk_loaded = true;
+    if (wait)
+        VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VSOM_OK;
+}
+
+// double-buffered ingest on a custom context: the prefetch keeps a host copy of the rows, the commit uploads it
+int vsom_custom_prefetch(vsom_ctx *c, const float *x_host, size_t B)
+{
+    if (B > 0 && !x_host)
+        return vsom_fail(VSOM_ERR_INVALID, "x_host is null");
+    vsom_custom_state *u = c->cu;
+    u->next.assign(x_host, x_host + B * c->J);
+    u->next_B = B;
+    u->next_pending = true;
+    return VSOM_OK;
+}
+
+int vsom_custom_commit(vsom_ctx *c)
+{
+    vsom_custom_state *u = c->cu;
+    if (!u->next_pending)
+        return vsom_fail(VSOM_ERR_INVALID, "no prefetched chunk to commit");
+    u->next_pending = false;
+    return vsom_custom_upload(c, u->next.data(), u->next_B, true);
+}
+
+static int copy_results(vsom_ctx *c, uint64_t *idx, float *dist)
+{
+    if (idx && c->B)
+        VSOM_HIP_CHECK(hipMemcpyAsync(idx, c->lastbmu, c->B * 8, hipMemcpyDeviceToHost, c->stream));
+    if (dist && c->B)
+        VSOM_HIP_CHECK(hipMemcpyAsync(dist, c->sqres, c->B * 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VSOM_OK;
+}
+
+int vsom_custom_bmu_batch(vsom_ctx *c, int local, uint64_t *idx_out_host, float *dist_out_host)
+{
+    int rc = local ? search_local(c, c->Xs, (uint32_t)c->B, c->lastbmu, c->lastbmu, c->sqres)
+                   : search_full(c, c->Xs, (unsigned)c->B, c->lastbmu, c->sqres);
+    if (rc)
+        return rc;
+    return copy_results(c, idx_out_host, dist_out_host);
+}
+
+int vsom_custom_find(vsom_ctx *c, const float *v_host, int local, uint64_t start, uint64_t *bmu_out, float *dist_out)
+{
+    vsom_custom_state *u = c->cu;
+    if (local && start >= c->N)
+        return vsom_fail(VSOM_ERR_INVALID, "lastBMU out of range");
+    int rc = stage_vec(c, v_host);
+    if (rc)
+        return rc;
+    u64 s = start;
+    VSOM_HIP_CHECK(hipMemcpyAsync(u->slot, &s, 8, hipMemcpyHostToDevice, c->stream));
+    rc = local ? search_local(c, u->vec, 1, u->slot, u->slot, u->fout) : search_full(c, u->vec, 1, u->slot, u->fout);
+    if (rc)
+        return rc;
+    float d = 0.f;
+    VSOM_HIP_CHECK(hipMemcpyAsync(&s, u->slot, 8, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(&d, u->fout, 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (bmu_out)
+        *bmu_out = s;
+    if (dist_out)
+        *dist_out = d;
+    return VSOM_OK;
+}
+
+static int pair_dist(vsom_ctx *c, const float *X, const uint64_t *nodes_host, const uint64_t *rows_host, size_t count,
+                     float *out_host)
+{
+    vsom_custom_state *u = c->cu;
+    if (count > u->pair_cap) {
+        VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+        if (u->pairs)
+            (void)hipFree(u->pairs);
+        if (u->pair_out)
+            (void)hipFree(u->pair_out);
+        u->pairs = nullptr;
+        u->pair_out = nullptr;
+        u->pair_cap = 0;
+        VSOM_HIP_CHECK(hipMalloc(&u->pairs, count * 16));
+        VSOM_HIP_CHECK(hipMalloc(&u->pair_out, count * 4));
+        u->pair_cap = count;
+    }
+    u64 *dn = u->pairs, *dr = u->pairs + count;
+    VSOM_HIP_CHECK(hipMemcpyAsync(dn, nodes_host, count * 8, hipMemcpyHostToDevice, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(dr, rows_host, count * 8, hipMemcpyHostToDevice, c->stream));
+    u64 xs = c->J, cnt = count;
+    uint32_t J = c->J, D = c->D, R = u->R;
+    int rc = launch(c, u->k_pair, (unsigned)((count + 63) / 64), 64, 0,
+                    {&X, &xs, &c->map, &u->sigf, &u->ones, &J, &D, &R, &dn, &dr, &cnt, &u->pair_out});
+    if (rc)
+        return rc;
+    VSOM_HIP_CHECK(hipMemcpyAsync(out_host, u->pair_out, count * 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VSOM_OK;
+}
+
+int vsom_custom_dist_single(vsom_ctx *c, const float *v_host, uint64_t node, float *dist_out)
+{
+    if (node >= c->N || !dist_out)
+        return vsom_fail(VSOM_ERR_INVALID, "node out of range or null output");
+    int rc = stage_vec(c, v_host);
+    if (rc)
+        return rc;
+    const uint64_t row = 0;
+    return pair_dist(c, c->cu->vec, &node, &row, 1, dist_out);
+}
+
+int vsom_custom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *rows_host, size_t count,
+                          float *dist_out_host)
+{
+    if (count == 0)
+        return VSOM_OK;
+    if (!nodes_host || !rows_host || !dist_out_host)
+        return vsom_fail(VSOM_ERR_INVALID, "null argument");
+    if (count > 0x0FFFFFFFull)
+        return vsom_fail(VSOM_ERR_INVALID, "too many pairs");
+    for (size_t i = 0; i < count; ++i)
+        if (nodes_host[i] >= c->N || rows_host[i] >= c->B)
+            return vsom_fail(VSOM_ERR_INVALID, "pair index out of range");
+    return pair_dist(c, c->Xs, nodes_host, rows_host, count, dist_out_host);
+}
+
+// Som::trainBatchSomEpoch (hostBatchEpoch): phase 1 search + residual, bmuHits / MSE, phase 2 per node
+int vsom_custom_batch_epoch_async(vsom_ctx *c, double sigma, int is_first)
+{
+    if (!c->chunk_loaded)
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    vsom_custom_state *u = c->cu;
+    uint32_t B = (uint32_t)c->B, W = c->W, H = c->H, J = c->J, D = c->D, R = u->R;
+    int rc = is_first ? search_full(c, c->Xs, B, c->lastbmu, c->sqres)
+                      : search_local(c, c->Xs, B, c->lastbmu, c->lastbmu, c->sqres);
+    if (rc)
+        return rc;
+    u64 xs = c->J;
+    if ((rc = launch(c, u->k_resid, (B + 63) / 64, 64, 0,
+                     {&c->Xs, &xs, &c->map, &c->S, &u->ones, &J, &D, &R, &c->lastbmu, &c->sqres, &B})))
+        return rc;
+    float *mse = c->mse;
+    if ((rc = launch(c, u->k_finish, 1, 64, 0, {&c->lastbmu, &c->sqres, &B, &c->hits, &mse})))
+        return rc;
+    if ((rc = ensure_lut(c, sigma)))
+        return rc;
+    uint32_t lutw = c->lut_w;
+    return launch(c, u->k_phase2, c->N, 256, 3 * D * 4,
+                  {&c->Xs, &xs, &c->map, &c->sigma, &u->sigf, &c->weight, &c->lastbmu, &c->lut, &lutw, &W, &H, &B,
+                   &u->ones, &J, &D});
+}
+
+// Som::trainSingle (hostTrainSingle) on one host vector
+int vsom_custom_train_single(vsom_ctx *c, const float *v_host, double eta, double sigma, uint64_t *last_bmu, int decay_fn,
+                             float *residual_out, float *dist_out, uint64_t *bmu_out)
+{
+    vsom_custom_state *u = c->cu;
+    if (!v_host || !last_bmu)
+        return vsom_fail(VSOM_ERR_INVALID, "null argument");
+    if (decay_fn != VSOM_EXPONENTIAL && decay_fn != VSOM_INVERSE_PROPORTIONAL)
+        return vsom_fail(VSOM_ERR_INVALID, "online training needs Exponential or InverseProportional");
+    if (*last_bmu >= c->N)
+        return vsom_fail(VSOM_ERR_INVALID, "lastBMU out of range");
+    int rc = stage_vec(c, v_host);
+    if (rc || (rc = ensure_lutd(c, sigma)))
+        return rc;
+    u64 s = *last_bmu;
+    VSOM_HIP_CHECK(hipMemcpyAsync(u->slot, &s, 8, hipMemcpyHostToDevice, c->stream));
+    if ((rc = online_step(c, u->vec, eta, sigma, decay_fn, u->slot, u->resid, u->fout + 1, nullptr, nullptr, 1)))
+        return rc;
+    float d = 0.f;
+    VSOM_HIP_CHECK(hipMemcpyAsync(&s, u->slot, 8, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(&d, u->fout + 1, 4, hipMemcpyDeviceToHost, c->stream));
+    if (residual_out)
+        VSOM_HIP_CHECK(hipMemcpyAsync(residual_out, u->resid, (size_t)u->R * 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    *last_bmu = s;
+    if (bmu_out)
+        *bmu_out = s;
+    if (dist_out)
+        *dist_out = d;
+    return VSOM_OK;
+}
+
+// the inner loop of Som::trainBasicSom over the staged chunk: one launch sequence per sample, in sample order
+int vsom_custom_train_online_chunk(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk)
+{
+    vsom_custom_state *u = c->cu;
+    if (decay_fn != VSOM_EXPONENTIAL && decay_fn != VSOM_INVERSE_PROPORTIONAL)
+        return vsom_fail(VSOM_ERR_INVALID, "online training needs Exponential or InverseProportional");
+    if (!c->chunk_loaded)
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    int rc = ensure_lutd(c, sigma);
+    if (rc)
+        return rc;
+    if (first_chunk) {
+        VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+        *static_cast<volatile float *>(c->mse) = 0.f;
+    }
+    const uint32_t B = (uint32_t)c->B;
+    for (uint32_t s = 0; s < B; ++s)
+        if ((rc = online_step(c, c->Xs + (size_t)s * c->J, eta, sigma, decay_fn, c->lastbmu + s, nullptr, u->fout + 1,
+                              c->hits, c->mse, B)))
+            return rc;
+    return VSOM_OK;
+}
+
+extern "C" {
+
+int vsom_custom_compile_check(const char *hook_source, uint32_t depth, uint32_t residual_len)
+{
+    int rc = check_shape(depth, residual_len, hook_source);
+    if (rc)
+        return rc;
+    std::vector<char> code;
+    std::string log;
+    if (!compile_hooks(hook_source, code, log))
+        return vsom_fail(VSOM_ERR_INVALID, "hook source does not compile:\n" + log);
+    return VSOM_OK;
+}
+
+int vsom_create_custom(vsom_ctx **out, int device, uint32_t width, uint32_t height, uint32_t in_len, uint32_t depth,
+                       uint32_t residual_len, const char *hook_source)
+{
+    if (!out)
+        return vsom_fail(VSOM_ERR_INVALID, "out is null");
+    *out = nullptr;
+    int rc = check_shape(depth, residual_len, hook_source);
+    if (rc)
+        return rc;
+    std::vector<char> code;
+    std::string log;
+    if (!compile_hooks(hook_source, code, log))
+        return vsom_fail(VSOM_ERR_INVALID, "hook source does not compile:\n" + log);
+    vsom_ctx *c = nullptr;
+    // the context of the built-in Standard transformation carries the state, the stream and the bookkeeping; its
+    // rows are then re-laid out unpadded
+    if ((rc = vsom_create(&c, device, width, height, in_len, VSOM_STANDARD)))
+        return rc;
+    auto fail = [&](int code_, const std::string &msg) {
+        std::string keep = msg;
+        vsom_destroy(c);
+        return vsom_fail(code_, keep);
+    };
+    vsom_custom_state *u = new (std::nothrow) vsom_custom_state();
+    if (!u)
+        return fail(VSOM_ERR_NOMEM, "out of host memory");
+    c->cu = u;
+    c->transform = -1;
+    u->R = residual_len;
+    c->D = depth;
+    c->nparts = 1;
+    c->part_len = depth;
+    c->part_pitch = depth;
+    c->pitch = depth;
+    c->xpitch = in_len;
+    const size_t nd = (size_t)c->N * depth;
+    (void)hipStreamSynchronize(c->stream);
+    void **state[] = {(void **)&c->map, (void **)&c->sigma, (void **)&c->S};
+    for (void **p : state) {
+        (void)hipFree(*p);
+        *p = nullptr;
+    }
+    if (hipMalloc(&c->map, nd * 4) != hipSuccess || hipMalloc(&c->sigma, nd * 4) != hipSuccess ||
+        hipMalloc(&c->S, nd * 4) != hipSuccess || hipMalloc(&u->sigf, nd * 4) != hipSuccess ||
+        hipMalloc(&u->ones, (size_t)in_len * 4) != hipSuccess || hipMalloc(&u->vec, (size_t)in_len * 4) != hipSuccess ||
+        hipMalloc(&u->resid, (size_t)residual_len * 4) != hipSuccess || hipMalloc(&u->slot, 16) != hipSuccess ||
+        hipMalloc(&u->fout, 8) != hipSuccess || hipMalloc(&u->lutd, (size_t)width * height * 8) != hipSuccess) {
+        (void)hipGetLastError();
+        return fail(VSOM_ERR_NOMEM, "hipMalloc of the custom context's state failed");
+    }
+    const std::vector<float> ones(in_len, 1.f);
+    if (hipMemset(c->map, 0, nd * 4) != hipSuccess || hipMemset(c->sigma, 0, nd * 4) != hipSuccess ||
+        hipMemset(c->S, 0, nd * 4) != hipSuccess ||
+        hipMemcpy(u->ones, ones.data(), (size_t)in_len * 4, hipMemcpyHostToDevice) != hipSuccess)
+        return fail(VSOM_ERR_HIP, "initialisation of the custom context failed");
+    if (hipModuleLoadData(&u->mod, code.data()) != hipSuccess) {
+        (void)hipGetLastError();
+        u->mod = nullptr;
+        return fail(VSOM_ERR_HIP, "hipModuleLoadData of the hook module failed");
+    }
+    struct { hipFunction_t *f; const char *name; } fns[] = {
+        {&u->k_floor, "vc_floor_sigma"}, {&u->k_full, "vc_search_full"}, {&u->k_local, "vc_search_local"},
+        {&u->k_pair, "vc_pair_dist"}, {&u->k_resid, "vc_batch_residual"}, {&u->k_finish, "vc_batch_finish"},
+        {&u->k_phase2, "vc_batch_phase2"}, {&u->k_onl_update, "vc_online_update"}, {&u->k_onl_post, "vc_online_post"}};
+    for (auto &f : fns)
+        if (hipModuleGetFunction(f.f, u->mod, f.name) != hipSuccess) {
+            (void)hipGetLastError();
+            return fail(VSOM_ERR_HIP, std::string("hook module lacks ") + f.name);
+        }
+    if ((rc = vsom_custom_after_set_state(c))) {
+        std::string keep = vsom_last_error();
+        return fail(rc, keep);
+    }
+    *out = c;
+    return VSOM_OK;
+}
+
+}   // extern "C"

@@ -37,6 +37,8 @@ constexpr size_t VSOM_ROW_PAD = 32;
 // bytes of vsom_ctx::onl_state (layout: vsom_online.hip)
 constexpr size_t VSOM_ONL_STATE_BYTES = 4352;
 
+struct vsom_custom_state;
+
 struct vsom_ctx {
     int device = 0;
     uint32_t W = 0, H = 0, J = 0, D = 0, N = 0;
@@ -187,6 +189,9 @@ struct vsom_ctx {
     std::vector<Ev> ev_pool;
     float t_ms[VSOM_T_COUNT] = {0};
     uint32_t t_cnt[VSOM_T_COUNT] = {0};
+
+    // caller-defined transformation (vsom_create_custom, vsom_custom.hip); null for the built-in ones
+    vsom_custom_state *cu = nullptr;
 };
 
 // error plumbing -----------------------------------------------------------------------------
@@ -247,3 +252,26 @@ int launch_sl_gather_quant(vsom_ctx *c, size_t B, hipStream_t stream, const int 
 int vsom_xq_ensure(vsom_ctx *c);                                 // vsom_xq.hip
 bool vsom_tiny_applies(const vsom_ctx *c);                        // vsom_tiny.hip
 int launch_tiny_epoch(vsom_ctx *c, double sigma, int is_first);   // whole batch epoch, one workgroup
+
+// custom-transformation contexts (vsom_custom.hip): the entry points that accept one route here, the others refuse it
+#define VSOM_CUSTOM_REFUSE(ctx, what)                                  \
+    do {                                                               \
+        if ((ctx) && (ctx)->cu)                                        \
+            return vsom_custom_refuse(what);                           \
+    } while (0)
+int vsom_custom_refuse(const char *what);
+void vsom_custom_destroy(vsom_ctx *c);
+int vsom_custom_after_set_state(vsom_ctx *c);
+int vsom_custom_upload(vsom_ctx *c, const float *x_host, size_t B, bool wait);
+int vsom_custom_prefetch(vsom_ctx *c, const float *x_host, size_t B);
+int vsom_custom_commit(vsom_ctx *c);
+int vsom_custom_bmu_batch(vsom_ctx *c, int local, uint64_t *idx_out_host, float *dist_out_host);
+int vsom_custom_find(vsom_ctx *c, const float *v_host, int local, uint64_t start, uint64_t *bmu_out, float *dist_out);
+int vsom_custom_dist_single(vsom_ctx *c, const float *v_host, uint64_t node, float *dist_out);
+int vsom_custom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *rows_host, size_t count,
+                          float *dist_out_host);
+int vsom_custom_batch_epoch_async(vsom_ctx *c, double sigma, int is_first);
+int vsom_custom_train_single(vsom_ctx *c, const float *v_host, double eta, double sigma, uint64_t *last_bmu, int decay_fn,
+                             float *residual_out, float *dist_out, uint64_t *bmu_out);
+int vsom_custom_train_online_chunk(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk);
+uint32_t vsom_custom_residual_len(const vsom_ctx *c);

@@ -2082,6 +2082,8 @@ int vsom_find_bmu(vsom_ctx *c, const float *v_host, uint64_t *bmu_out, float *di
     if (!c)
         return vsom_fail(VSOM_ERR_INVALID, "null context");
     VSOM_HIP_CHECK(hipSetDevice(c->device));
+    if (c->cu)
+        return vsom_custom_find(c, v_host, 0, 0, bmu_out, dist_out);
     if (int jrc = vsom_join_aux(c))
         return jrc;
     if (!v_host)
@@ -2266,12 +2268,14 @@ static int single_scan(vsom_ctx *c, const float *v_host, int use_hits, uint64_t 
 // Som::findRestrictedBmu(v, ..., minBmuHits, ...) for ONE host vector (Som.cpp:313-332)
 int vsom_find_restricted_bmu(vsom_ctx *c, const float *v_host, uint64_t min_hits, uint64_t *bmu_out, float *dist_out)
 {
+    VSOM_CUSTOM_REFUSE(c, "vsom_find_restricted_bmu");
     return single_scan(c, v_host, 1, min_hits, bmu_out, dist_out, nullptr);
 }
 
 // euclidianWeightedDist(i, v) of ONE host vector to every node i (what Som::findRestrictedBmd walks, Som.cpp:457-487)
 int vsom_distances_single(vsom_ctx *c, const float *v_host, float *dist_out_host)
 {
+    VSOM_CUSTOM_REFUSE(c, "vsom_distances_single");
     if (!dist_out_host)
         return vsom_fail(VSOM_ERR_INVALID, "null output");
     return single_scan(c, v_host, 0, 0, nullptr, nullptr, dist_out_host);
@@ -2280,12 +2284,16 @@ int vsom_distances_single(vsom_ctx *c, const float *v_host, float *dist_out_host
 // Som::euclidianWeightedDist(pos, v, ...) for ONE host vector (Som.cpp:124-141)
 int vsom_dist_single(vsom_ctx *c, const float *v_host, uint64_t node, float *dist_out)
 {
+    if (c && c->cu && hipSetDevice(c->device) == hipSuccess)
+        return vsom_custom_dist_single(c, v_host, node, dist_out);
     return single_query(c, v_host, node, 0, nullptr, dist_out);
 }
 
 // Som::findLocalBmu(v, ..., lastBMU, ...) for ONE host vector (Som.cpp:335-454)
 int vsom_find_local_bmu(vsom_ctx *c, const float *v_host, uint64_t last_bmu, uint64_t *bmu_out, float *dist_out)
 {
+    if (c && c->cu && hipSetDevice(c->device) == hipSuccess)
+        return vsom_custom_find(c, v_host, 1, last_bmu, bmu_out, dist_out);
     return single_query(c, v_host, last_bmu, 1, bmu_out, dist_out);
 }
 
@@ -2298,6 +2306,15 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
         *lb_in_pinned = false;
     if (!c)
         return vsom_fail(VSOM_ERR_INVALID, "null context");
+    if (c->cu) {
+        VSOM_HIP_CHECK(hipSetDevice(c->device));
+        int rc = vsom_custom_train_online_chunk(c, eta, sigma, decay_fn, first_chunk);
+        if (rc || !mse_out)
+            return rc;
+        VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+        *mse_out = *static_cast<volatile float *>(c->mse);
+        return VSOM_OK;
+    }
     VSOM_HIP_CHECK(hipSetDevice(c->device));
     if (int jrc = vsom_join_aux(c))
         return jrc;
@@ -2421,6 +2438,8 @@ int vsom_train_single(vsom_ctx *c, const float *v_host, double eta, double sigma
     if (!c)
         return vsom_fail(VSOM_ERR_INVALID, "null context");
     VSOM_HIP_CHECK(hipSetDevice(c->device));
+    if (c->cu)
+        return vsom_custom_train_single(c, v_host, eta, sigma, last_bmu, decay_fn, residual_out, dist_out, bmu_out);
     if (int jrc = vsom_join_aux(c))
         return jrc;
     if (!v_host || !last_bmu)

@@ -318,7 +318,8 @@ public:
 // (vsom::*Comparer / vsom::*Stepper below) and run as HIP kernels -- they have no host training path.
 // Any other callable (a caller's own lambdas, tests/test1.cpp:56-84) makes the Som keep its state on the
 // host and run distance / search / batch epoch / online step there with the caller's hooks
-// (src/vsom_custom.cpp); the consumers outside training (U-matrix, evaluate, ...) then throw.  The
+// (src/vsom_custom.cpp).  A custom Transformation that also carries its hooks as device source (DeviceSource,
+// Transformation::Device) trains on the GPU instead (vsom_create_custom, csrc/vsom_custom.hip).  The
 // built-in functors also work on the host, so code that calls transform.Comparer(...) directly keeps working.
 
 #include <functional>
@@ -346,10 +347,21 @@ struct Transformation {
     std::function<std::vector<std::string>(const T &model)> Displayer{[&names = names](const T &) { return names; }};
     std::function<size_t(size_t vectorLength)> Length{vsom::IdentityLength{}};
     std::string Name{"Standard transformation"};
+    // [MI355X build] the caller's hooks as HIP device source (include/vsom_hip.h, vsom_create_custom: vsom_compare /
+    // vsom_step per output element).  Non-empty on a Custom transformation: the Som compiles it with hipRTC and trains
+    // on the device; empty: the host path of src/vsom_custom.cpp.  Comparer / Stepper stay the host hooks for direct calls.
+    std::string DeviceSource{};
+    // residual length of DeviceSource's Comparer for a sample length J (empty: Length(J))
+    std::function<size_t(size_t vectorLength)> ResidualLength{};
 
     static Transformation Standard(const std::vector<std::string> &columnNames);
     static Transformation StandardMedianEstimator(const std::vector<std::string> &columnNames);
     static Transformation CombinatorialLinearRegression(const std::vector<std::string> &columnNames);
+    // [MI355X build] a custom transformation that trains on the device from `source` (see DeviceSource)
+    static Transformation Device(const std::string &name, const std::string &source, std::function<size_t(size_t)> length,
+                                 std::function<size_t(size_t)> residualLength,
+                                 std::function<T(const T &, const T &, const T &, const T &)> comparer,
+                                 std::function<T(const T &, const T &, const T &)> stepper);
 
     // [MI355X build] which device kernels implement this transformation (vsom::Custom = none)
     int kind() const noexcept;

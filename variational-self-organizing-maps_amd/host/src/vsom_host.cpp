@@ -150,6 +150,21 @@ Transformation Transformation::CombinatorialLinearRegression(const std::vector<s
     return t;
 }
 
+Transformation Transformation::Device(const std::string &name, const std::string &source, std::function<size_t(size_t)> length,
+                                      std::function<size_t(size_t)> residualLength,
+                                      std::function<T(const T &, const T &, const T &, const T &)> comparer,
+                                      std::function<T(const T &, const T &, const T &)> stepper)
+{
+    Transformation t;
+    t.Comparer = std::move(comparer);
+    t.Stepper = std::move(stepper);
+    t.Length = std::move(length);
+    t.Name = name;
+    t.DeviceSource = source;
+    t.ResidualLength = std::move(residualLength);
+    return t;
+}
+
 int Transformation::kind() const noexcept
 {
     const bool sc = Comparer.target<vsom::StandardComparer>() != nullptr;
@@ -577,8 +592,16 @@ static void check(int rc, const char *what)
 void Som::createContext()
 {
     const int kind = transform.kind();
+    if (kind == vsom::Custom && !transform.DeviceSource.empty()) {
+        // device source of the hooks: compiled with hipRTC, trained by the generic kernels (one GPU)
+        const size_t R = transform.ResidualLength ? transform.ResidualLength(inLen) : depth;
+        check(vsom_create_custom(&ctx, g_default_device, (uint32_t)width, (uint32_t)height, (uint32_t)inLen, (uint32_t)depth,
+                                 (uint32_t)R, transform.DeviceSource.c_str()),
+              "vsom_create_custom");
+        return;
+    }
     if (kind == vsom::Custom) {
-        ctx = nullptr;   // state-less shell: accessors work on zeros, training throws
+        ctx = nullptr;   // host hooks: the state lives in the host arrays (src/vsom_custom.cpp)
         return;
     }
     const std::vector<int> devs = training_devices(width * height);

@@ -23,10 +23,25 @@ class WeigthDecayFunction(enum.IntEnum):      # SOM.hpp:70-75 (spelling as in th
 
 
 class Transformation:
-    """Transformation.hpp:10-41; only the three built-in factories run on the device."""
+    """Transformation.hpp:10-41: the three built-in factories, or Custom -- the caller's hooks as device source."""
 
-    def __init__(self, kind=capi.STANDARD, names=None, name="Standard transformation"):
+    def __init__(self, kind=capi.STANDARD, names=None, name="Standard transformation", source=None, length=None,
+                 residual_len=None):
         self.kind, self.names, self.Name = kind, list(names or []), name
+        self.DeviceSource, self._length, self._residual_len = source, length, residual_len
+
+    @staticmethod
+    def Custom(source, length=None, residual_len=None, columnNames=(), name="Custom transformation"):
+        """hooks vsom_compare / vsom_step as HIP device source (include/vsom_hip.h, vsom_create_custom); length and
+        residual_len are the model depth and the residual length, each an int or a function of the sample length
+        (default: the sample length)"""
+        return Transformation(capi.CUSTOM, columnNames, name, source, length, residual_len)
+
+    def ResidualLength(self, vectorLength):
+        if self.kind == capi.CUSTOM:
+            r = self._residual_len
+            return vectorLength if r is None else int(r(vectorLength) if callable(r) else r)
+        return vectorLength * (vectorLength - 1) // 2 if self.kind == capi.CLR else vectorLength
 
     @staticmethod
     def Standard(columnNames=()):
@@ -41,6 +56,9 @@ class Transformation:
         return Transformation(capi.CLR, columnNames, "Linear regression")
 
     def Length(self, vectorLength):            # Transformation.cpp:31-35,69-73,162-165
+        if self.kind == capi.CUSTOM:
+            n = self._length
+            return vectorLength if n is None else int(n(vectorLength) if callable(n) else n)
         return vectorLength * (vectorLength - 1) if self.kind == capi.CLR else vectorLength
 
 
@@ -144,7 +162,12 @@ class Som:
             depth = int(depth_or_dataset)
             in_len = self._in_len_from_depth(depth)
         self.width, self.height = int(width), int(height)
-        self.ctx = capi.Context(width, height, in_len, self.transform.kind, device=device)
+        t = self.transform
+        if t.kind == capi.CUSTOM:
+            self.ctx = capi.Context(width, height, in_len, capi.CUSTOM, device=device, source=t.DeviceSource,
+                                    depth=t.Length(in_len), residual_len=t.ResidualLength(in_len))
+        else:
+            self.ctx = capi.Context(width, height, in_len, t.kind, device=device)
         self.depth = self.ctx.depth
         self.in_len = in_len
         self.metrics = Metrics()
