@@ -312,6 +312,33 @@ int vsom_train_online_chunk_fetch(vsom_ctx *ctx, double eta, double sigma, int d
  * bound), out[2] = refinement workgroups that had a candidate, out[3] = 0.  All zero while the exact scan is in use. */
 int vsom_get_online_search_stats(vsom_ctx *ctx, uint64_t *out /*[4]*/, int reset);
 
+/* ---- ensembles: many small maps trained by one call ---------------------------------------
+ * An ensemble is a set of existing contexts on one device; its calls train every member, each with its own parameters,
+ * and have the same effect, bit for bit, as the single-context call made on every member in turn (map, S, sigmaMap,
+ * weightMap, bmuHits, lastBMU, the MSE, the running MSE across chunks).  Members whose single call takes the one-launch
+ * kernel of a tiny map (online: the chunk kernel; batch: the epoch kernel) and whose LDS need fits the device run as one
+ * launch per kernel instantiation, one workgroup per member; every other member (larger maps, CLR online, custom
+ * contexts, VSOM_NO_TINY=1, non-AUTO search modes, sigma = NaN) is trained in the same call through its ordinary path.
+ * Members stay ordinary contexts: upload their chunks, set and read their state and checkpoint them as usual between
+ * ensemble calls.  Each member's work stays ordered on that member's stream.  Give all members ONE stream
+ * (vsom_set_stream) for the fast form; members on different streams are joined with events (the same results).
+ * Every call waits for its launches before it returns.  The one-launch members are not timed: vsom_get_timing of such a
+ * member does not count ensemble calls (members on their ordinary path are timed as in their single call).
+ * create refuses (VSOM_ERR_INVALID): no members, a null or repeated member, members on different devices, members of a
+ * vsom_group.  A train call refuses (VSOM_ERR_INVALID, naming the member index, before anything is enqueued for any
+ * member): a member without a chunk, a member whose next chunk is staged ahead over its rows (vsom_commit_chunk first),
+ * and an online decay_fn other than Exponential / InverseProportional.  A refused call changes nothing.
+ * Lifetime: a member must not be destroyed while an ensemble holds it; destroy the ensemble first.
+ * Arrays are indexed by member (the order given to create).  online: lastbmu_out (NULL: none wanted) holds a pointer per
+ * member, each NULL or room for that member's B values; mse_out (NULL: not wanted) gets each member's running MSE. */
+typedef struct vsom_ensemble vsom_ensemble;
+int vsom_ensemble_create(vsom_ensemble **out, vsom_ctx *const *members, size_t count);
+void vsom_ensemble_destroy(vsom_ensemble *e);
+size_t vsom_ensemble_size(const vsom_ensemble *e);
+int vsom_ensemble_train_online_chunk_fetch(vsom_ensemble *e, const double *eta, const double *sigma, const int *decay_fn,
+                                           int first_chunk, uint64_t *const *lastbmu_out, float *mse_out);
+int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_first, float *mse_out);
+
 /* ---- multi-GPU batch epoch, one process, the GPUs of one node ------------------------
  * Som::trainBatchSomEpoch's two loops shard differently: phase 1 (Som.cpp:764-782 / 786-805) is
  * independent per SAMPLE, phase 2 (Som.cpp:809-876) is independent per NODE but sequential in samples

@@ -44,6 +44,8 @@ SYMBOLS = [
     "vsom_group_commit_chunk", "vsom_group_set_chunk_device", "vsom_group_set_last_bmu", "vsom_group_get_last_bmu",
     "vsom_group_batch_epoch_async", "vsom_group_batch_epoch", "vsom_group_get_mse",
     "vsom_create_custom", "vsom_custom_compile_check",
+    "vsom_ensemble_create", "vsom_ensemble_destroy", "vsom_ensemble_size", "vsom_ensemble_train_online_chunk_fetch",
+    "vsom_ensemble_batch_epoch",
 ]
 
 
@@ -196,6 +198,14 @@ def lib():
     L.vsom_group_batch_epoch_async.argtypes = [vp, C.c_double, C.c_int]
     L.vsom_group_batch_epoch.argtypes = [vp, C.c_double, C.c_int, fp]
     L.vsom_group_get_mse.argtypes = [vp, fp]
+    L.vsom_ensemble_create.argtypes = [C.POINTER(vp), C.POINTER(vp), C.c_size_t]
+    L.vsom_ensemble_destroy.argtypes = [vp]
+    L.vsom_ensemble_destroy.restype = None
+    L.vsom_ensemble_size.argtypes = [vp]
+    L.vsom_ensemble_size.restype = C.c_size_t
+    L.vsom_ensemble_train_online_chunk_fetch.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                         C.POINTER(C.c_int), C.c_int, C.POINTER(u64p), fp]
+    L.vsom_ensemble_batch_epoch.argtypes = [vp, C.POINTER(C.c_double), C.c_int, fp]
     _lib = L
     return L
 
@@ -681,3 +691,56 @@ class Group:
         mse = C.c_float()
         check(lib().vsom_group_get_mse(self._h, C.byref(mse)))
         return np.float32(mse.value)
+
+
+class Ensemble:
+    """A set of Contexts on one device trained by one call (include/vsom_hip.h, vsom_ensemble): the same results, bit for
+    bit, as the single-context call on every member in turn.  Members stay ordinary Contexts (upload, state, checkpoints);
+    close the ensemble before closing a member.  Parameters are scalars (every member) or one value per member."""
+
+    def __init__(self, contexts):
+        self.members = list(contexts)
+        n = len(self.members)
+        arr = (C.c_void_p * max(n, 1))(*[c._h.value if c is not None and c._h else None for c in self.members])
+        self._h = C.c_void_p()
+        check(lib().vsom_ensemble_create(C.byref(self._h), arr, n))
+
+    def __len__(self):
+        return len(self.members)
+
+    def close(self):
+        if self._h:
+            lib().vsom_ensemble_destroy(self._h)
+            self._h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _per_member(self, v, ctype, conv):
+        n = len(self.members)
+        vals = [conv(x) for x in v] if np.ndim(v) else [conv(v)] * n
+        if len(vals) != n:
+            raise ValueError(f"{len(vals)} values for {n} members")
+        return (ctype * n)(*vals)
+
+    def train_online_chunk_fetch(self, eta, sigma, decay_fn, first_chunk=True):
+        """one online chunk on every member: (running MSE per member [float32 array], lastBMU per member [list of
+        uint64 arrays, each of that member's chunk size])"""
+        n = len(self.members)
+        lbs = [np.zeros(c.chunk_size, np.uint64) for c in self.members]
+        ptrs = (C.POINTER(C.c_uint64) * n)(*[_u(a) for a in lbs])
+        mse = np.zeros(n, np.float32)
+        check(lib().vsom_ensemble_train_online_chunk_fetch(
+            self._h, self._per_member(eta, C.c_double, float), self._per_member(sigma, C.c_double, float),
+            self._per_member(decay_fn, C.c_int, int), int(bool(first_chunk)), ptrs, _f(mse)))
+        return mse, lbs
+
+    def batch_epoch(self, sigma, is_first):
+        """one batch epoch on every member: the MSE per member [float32 array]"""
+        mse = np.zeros(len(self.members), np.float32)
+        check(lib().vsom_ensemble_batch_epoch(self._h, self._per_member(sigma, C.c_double, float), int(bool(is_first)),
+                                              _f(mse)))
+        return mse

@@ -249,6 +249,8 @@ int vsom_group_create(vsom_group **out, int ndev, const int *devices, uint32_t w
     for (int r = 0; r < ndev && rc == VSOM_OK; ++r) {
         vsom_ctx *c = nullptr;
         rc = vsom_create(&c, g->dev[r], width, height, in_len, transform);
+        if (c)
+            c->in_group = true;
         g->ctx.push_back(c);
     }
     auto fail = [&](int code) {

@@ -190,6 +190,8 @@ struct vsom_ctx {
     float t_ms[VSOM_T_COUNT] = {0};
     uint32_t t_cnt[VSOM_T_COUNT] = {0};
 
+    bool in_group = false;          // a member of a vsom_group (vsom_group.hip): ensembles refuse it
+
     // caller-defined transformation (vsom_create_custom, vsom_custom.hip); null for the built-in ones
     vsom_custom_state *cu = nullptr;
 };
@@ -252,6 +254,21 @@ int launch_sl_gather_quant(vsom_ctx *c, size_t B, hipStream_t stream, const int 
 int vsom_xq_ensure(vsom_ctx *c);                                 // vsom_xq.hip
 bool vsom_tiny_applies(const vsom_ctx *c);                        // vsom_tiny.hip
 int launch_tiny_epoch(vsom_ctx *c, double sigma, int is_first);   // whole batch epoch, one workgroup
+
+// one workgroup per map forms of the one-launch kernels (vsom_ensemble.hip).  prepare: the member's descriptor into
+// `desc` and its kernel instantiation into *group, or *group = -1 when the member's single call would not take the
+// one-launch kernel or its LDS need exceeds lds_limit (the member takes its ordinary path)
+constexpr int VSOM_ONL_TINY_GROUPS = 12, VSOM_TINY_GROUPS = 3;
+size_t vsom_onl_tiny_desc_bytes();  // (descriptors are packed at exactly this size: the kernels index args[blockIdx.x])
+int vsom_onl_tiny_prepare(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk, bool want_lb,
+                          size_t lds_limit, void *desc, int *group, size_t *smem, int *lut_slot);
+// before any launch of the call: the instantiation's dynamic LDS limit (process-wide, raised only; vsom_online.hip)
+int vsom_onl_tiny_ready(int group, int device, size_t lds_limit);
+int vsom_onl_tiny_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
+void vsom_onl_tiny_done(vsom_ctx *c, int lut_slot);
+size_t vsom_tiny_desc_bytes();       // (descriptors are packed at exactly this size: the kernels index args[blockIdx.x])
+int vsom_tiny_prepare(vsom_ctx *c, double sigma, int is_first, size_t lds_limit, void *desc, int *group, size_t *smem);
+int vsom_tiny_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
 
 // custom-transformation contexts (vsom_custom.hip): the entry points that accept one route here, the others refuse it
 #define VSOM_CUSTOM_REFUSE(ctx, what)                                  \
