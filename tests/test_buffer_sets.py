@@ -1,0 +1,36 @@
+"""The all-or-nothing buffer sets of csrc/vsom_buf.hpp, on the host: a C++ driver replaces the allocate / free seam with
+host memory that fails on the k-th call and checks, for every k, that the set call reports out of memory, that every
+member is left null with capacity 0, and that every allocation that succeeded is freed exactly once.  No device is
+needed (the HIP headers only; the runtime library is linked but never called)."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+CSRC = os.path.join(ROOT, "variational-self-organizing-maps_amd", "csrc")
+ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
+
+
+def _compile(cxx, out, extra):
+    cmd = [cxx, "-std=c++17", "-O1", "-g", "-Wall", "-Werror", "-Wno-unused-result", "-I", CSRC,
+           "-I", os.path.join(ROCM, "include"), "-D__HIP_PLATFORM_AMD__", *extra,
+           os.path.join(ROOT, "tests", "buffer_sets_driver.cpp"), "-o", out,
+           "-L", os.path.join(ROCM, "lib"), "-lamdhip64", "-Wl,-rpath," + os.path.join(ROCM, "lib")]
+    return subprocess.run(cmd, capture_output=True, text=True)
+
+
+def test_sets_are_whole_or_absent(tmp_path):
+    cxx = shutil.which("g++") or shutil.which("c++")
+    if cxx is None or not os.path.isdir(os.path.join(ROCM, "include", "hip")):
+        pytest.skip("needs a host C++ compiler and the HIP headers")
+    exe = str(tmp_path / "buffer_sets_driver")
+    r = _compile(cxx, exe, ["-fsanitize=address", "-fno-omit-frame-pointer"])
+    if r.returncode != 0:                      # a toolchain without AddressSanitizer: the plain build
+        r = _compile(cxx, exe, [])
+    assert r.returncode == 0, r.stderr
+    run = subprocess.run([exe], capture_output=True, text=True, timeout=120,
+                         env=dict(os.environ, ASAN_OPTIONS="detect_leaks=1"))
+    assert run.returncode == 0, run.stdout + run.stderr
+    assert run.stdout.strip().endswith("ok")

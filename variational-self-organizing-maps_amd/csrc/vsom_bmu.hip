@@ -84,18 +84,18 @@ static int stage_chunk_on(vsom_ctx *c, const float *x_dev, size_t B, hipStream_t
     if (int rc = vsom_cc_begin(c, B, &cc))      // does this chunk get the column compaction? (buffers, skip counters)
         return rc;
     if (cc && !idx) {                            // (buffers allocated by vsom_cc_begin just now)
-        idx = c->cc_idx;
-        inv = c->cc_inv;
-        meta = c->cc_meta;
+        idx = c->cc_idx.p;
+        inv = c->cc_inv.p;
+        meta = c->cc_meta.p;
     }
     hipLaunchKernelGGL(stage_rows_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, stream, x_dev, (int)c->J,
-                       (int)B, c->Xs, (int)c->xpitch, lastbmu, cc ? c->cc_flags : (unsigned *)nullptr,
-                       c->sl_scal ? c->sl_scal + 8192 : (unsigned *)nullptr);
+                       (int)B, c->Xs.p, (int)c->xpitch, lastbmu, cc ? c->cc_flags.p : (unsigned *)nullptr,
+                       c->sl_scal.p ? c->sl_scal.p + 8192 : (unsigned *)nullptr);
     if (c->transform == VSOM_CLR) {
         size_t total = B * c->part_pitch;
         hipLaunchKernelGGL(stage_pairs_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0,
-                           stream, x_dev, (int)c->J, (int)B, (int)c->part_len, c->pair_i,
-                           c->pair_j, c->XP, c->YP, (int)c->part_pitch);
+                           stream, x_dev, (int)c->J, (int)B, (int)c->part_len, c->pair_i.p,
+                           c->pair_j.p, c->XP.p, c->YP.p, (int)c->part_pitch);
     }
     VSOM_HIP_CHECK(hipGetLastError());
     if (cc) {                                    // live-column record of this chunk (vsom_compact.hip)
@@ -122,7 +122,7 @@ int launch_stage_chunk(vsom_ctx *c, const float *x_dev, size_t B)
     }
     c->ahead_valid = false;
     bool cc = false, xi = false;
-    int rc = stage_chunk_on(c, x_dev, B, c->stream, c->lastbmu, c->cc_idx, c->cc_inv, c->cc_meta, &cc, &xi);
+    int rc = stage_chunk_on(c, x_dev, B, c->stream, c->lastbmu.p, c->cc_idx.p, c->cc_inv.p, c->cc_meta.p, &cc, &xi);
     c->cc_valid = cc;
     c->xi_valid = xi;
     return rc;
@@ -134,10 +134,10 @@ int launch_stage_chunk(vsom_ctx *c, const float *x_dev, size_t B)
 // rows-are-free event is still the last word on the context (launch_phase2 records it).
 bool vsom_can_stage_ahead(const vsom_ctx *c, size_t B)
 {
-    if (c->transform == VSOM_CLR || !c->rows_free_valid || !c->ev_rows_free || !c->lastbmu_alt || B > c->Bcap)
+    if (c->transform == VSOM_CLR || !c->rows_free_valid || !c->ev_rows_free || !c->lastbmu_alt.p || B > c->Bcap)
         return false;
     if (vsom_cc_applies(c) && B > 0 && c->cc_min_rows >= 0 && (long)B >= c->cc_min_rows &&
-        (!c->cc_meta_alt || (c->Bcap + VSOM_ROW_PAD) * (size_t)c->cpitch > c->Xc_cap))
+        (!c->cc_meta_alt.p || (c->Bcap + VSOM_ROW_PAD) * (size_t)c->cpitch > c->Xc.cap))
         return false;
     return true;
 }
@@ -147,7 +147,7 @@ int launch_stage_chunk_ahead(vsom_ctx *c, const float *x_dev, size_t B)
     // after the epoch's last reader of the staged rows (xq_transpose in launch_phase2) -- NOT after its chains
     VSOM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, c->ev_rows_free, 0));
     bool cc = false, xi = false;
-    int rc = stage_chunk_on(c, x_dev, B, c->copy_stream, c->lastbmu_alt, c->cc_idx_alt, c->cc_inv_alt, c->cc_meta_alt, &cc, &xi);
+    int rc = stage_chunk_on(c, x_dev, B, c->copy_stream, c->lastbmu_alt.p, c->cc_idx_alt.p, c->cc_inv_alt.p, c->cc_meta_alt.p, &cc, &xi);
     if (rc)
         return rc;
     VSOM_HIP_CHECK(hipEventRecord(c->ev_ahead, c->copy_stream));
@@ -182,17 +182,17 @@ static DistArgs make_dist_args(const vsom_ctx *c)
 {
     DistArgs a;
     if (c->transform == VSOM_CLR) {
-        a.xa = c->XP;
-        a.xb = c->YP;
+        a.xa = c->XP.p;
+        a.xb = c->YP.p;
         a.ldx = (int)c->part_pitch;
-        a.ma = c->map;
-        a.mb = c->map + c->part_pitch;
+        a.ma = c->map.p;
+        a.mb = c->map.p + c->part_pitch;
     } else {
-        a.xa = c->Xs;
-        a.xb = c->Xs;
+        a.xa = c->Xs.p;
+        a.xb = c->Xs.p;
         a.ldx = (int)c->xpitch;
-        a.ma = c->map;
-        a.mb = c->map;
+        a.ma = c->map.p;
+        a.mb = c->map.p;
     }
     a.ldm = (int)c->pitch;
     a.L = (int)c->part_len;
@@ -631,19 +631,16 @@ __global__ __launch_bounds__(1024) void bmu_unique_kernel(const int *__restrict_
 // enqueue the three passes; *nlist / *ncount = what bmu_tile_kernel takes (buffers kept with the context)
 static int launch_bmu_dedupe(vsom_ctx *c, const unsigned *scount, unsigned min_list, const int **nlist, const unsigned **ncount)
 {
-    if (!c->dd_hash) {
-        VSOM_HIP_CHECK(hipMalloc(&c->dd_hash, (size_t)c->N * sizeof(u64)));
-        VSOM_HIP_CHECK(hipMalloc(&c->dd_rep, (size_t)c->N * sizeof(int)));
-        VSOM_HIP_CHECK(hipMalloc(&c->dd_list, (size_t)c->N * sizeof(int) + 64));
-    }
-    u64 *hash = reinterpret_cast<u64 *>(c->dd_hash);
-    unsigned *cnt = reinterpret_cast<unsigned *>(c->dd_list + c->N);
-    hipLaunchKernelGGL(bmu_row_hash_kernel, dim3(std::min<unsigned>((unsigned)c->N, 2048u)), dim3(256), 0, c->stream, c->map,
+    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, 0, {vsom_member(c->dd_hash, c->N), vsom_member(c->dd_rep, c->N),
+                                                vsom_member(c->dd_list, (size_t)c->N + 16)}));   // (+ the count)
+    u64 *hash = c->dd_hash.p;
+    unsigned *cnt = reinterpret_cast<unsigned *>(c->dd_list.p + c->N);
+    hipLaunchKernelGGL(bmu_row_hash_kernel, dim3(std::min<unsigned>((unsigned)c->N, 2048u)), dim3(256), 0, c->stream, c->map.p,
                        (int)c->pitch, (int)c->N, hash, scount, min_list);
     hipLaunchKernelGGL(bmu_row_twin_kernel, dim3(std::min<unsigned>((unsigned)((c->N + 3) / 4), 1024u)), dim3(256), 0, c->stream,
-                       c->map, (int)c->pitch, (int)c->N, hash, c->dd_rep, scount, min_list);
-    hipLaunchKernelGGL(bmu_unique_kernel, dim3(1), dim3(1024), 0, c->stream, c->dd_rep, (int)c->N, c->dd_list, cnt, scount, min_list);
-    *nlist = c->dd_list;
+                       c->map.p, (int)c->pitch, (int)c->N, hash, c->dd_rep.p, scount, min_list);
+    hipLaunchKernelGGL(bmu_unique_kernel, dim3(1), dim3(1024), 0, c->stream, c->dd_rep.p, (int)c->N, c->dd_list.p, cnt, scount, min_list);
+    *nlist = c->dd_list.p;
     *ncount = cnt;
     return VSOM_OK;
 }
@@ -660,13 +657,7 @@ int launch_bmu_full_exact_masked(vsom_ctx *c, size_t s0, size_t s1, const int *s
     const int TS = c->transform == VSOM_CLR ? 32 : TILE;      // samples per tile (bmu_tile_kernel<CLR, TI>)
     const int nts = (int)((s1 - s0 + TS - 1) / TS);
     size_t need = (size_t)ntn * c->Bcap;
-    if (need > c->partial_cap) {
-        if (c->partial)
-            VSOM_HIP_CHECK(hipFree(c->partial));
-        c->partial = nullptr;
-        VSOM_HIP_CHECK(hipMalloc(&c->partial, need * sizeof(u64)));
-        c->partial_cap = need;
-    }
+    VSOM_ALLOC_CHECK(vsom_grow(c->partial, need, c->stream));
     DistArgs a = make_dist_args(c);
     // (a redo list is usually empty or short: ~512 workgroups -- the two per CU the kernel's registers allow -- each
     // walking on through the list's tiles; 768 for CLR measured slower: a second, half-empty round)
@@ -695,7 +686,7 @@ int launch_bmu_full_exact_masked(vsom_ctx *c, size_t s0, size_t s1, const int *s
             return rc;
     }
 #define VSOM_TILE_LAUNCH(K)                                                                                             \
-    hipLaunchKernelGGL(K, grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)c->N, c->partial, (int)c->Bcap, c->nan0, \
+    hipLaunchKernelGGL(K, grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)c->N, c->partial.p, (int)c->Bcap, c->nan0.p, \
                        slist, scount, hits, min_hits, fb, nlist, ncount)
     if (c->transform == VSOM_CLR) {
         if (list)
@@ -710,8 +701,8 @@ int launch_bmu_full_exact_masked(vsom_ctx *c, size_t s0, size_t s1, const int *s
     }
 #undef VSOM_TILE_LAUNCH
     hipLaunchKernelGGL(bmu_reduce_kernel, dim3((unsigned)((s1 - s0 + 255) / 256)), dim3(256), 0,
-                       c->stream, c->partial, (int)c->Bcap, ntn, c->nan0, (int)s0, (int)s1, c->lastbmu,
-                       c->sqres, slist, scount, ncount);
+                       c->stream, c->partial.p, (int)c->Bcap, ntn, c->nan0.p, (int)s0, (int)s1, c->lastbmu.p,
+                       c->sqres.p, slist, scount, ncount);
     VSOM_HIP_CHECK(hipGetLastError());
     return VSOM_OK;
 }
@@ -724,7 +715,7 @@ int launch_bmu_full_exact_list(vsom_ctx *c, size_t s0, size_t s1, const int *sli
 int launch_bmu_restricted(vsom_ctx *c, u64 min_hits)
 {
     TimerScope ts(c, VSOM_T_BMU);
-    return launch_bmu_full_exact_masked(c, 0, c->B, nullptr, nullptr, c->hits, min_hits);
+    return launch_bmu_full_exact_masked(c, 0, c->B, nullptr, nullptr, c->hits.p, min_hits);
 }
 
 int launch_bmu_full_shortlist(vsom_ctx *c, size_t s0, size_t s1);
@@ -750,8 +741,8 @@ int launch_bmu_full(vsom_ctx *c, size_t s0, size_t s1)
         // feedback of the previous shortlist call (pinned host words written by the device, read
         // without synchronising: possibly one call stale): when more than a quarter of the samples
         // had to be redone exactly the shortlist does not pay on this map -- skip it for a while
-        if (c->sl_fb) {
-            volatile unsigned *fb = c->sl_fb;
+        if (c->sl_fb.p) {
+            volatile unsigned *fb = c->sl_fb.p;
             unsigned redo = fb[0], rows = fb[2], seq = fb[3];
             if (seq != c->sl_seq_seen) {             // the verdict of a shortlist search not looked at yet
                 c->sl_seq_seen = seq;
@@ -812,10 +803,10 @@ int launch_bmu_local(vsom_ctx *c, size_t s0, size_t s1)
     dim3 grid((unsigned)((waves + 3) / 4));
     if (c->transform == VSOM_CLR)
         hipLaunchKernelGGL(bmu_local_kernel<true>, grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1,
-                           (u64)c->W, (u64)c->H, c->lastbmu, c->sqres);
+                           (u64)c->W, (u64)c->H, c->lastbmu.p, c->sqres.p);
     else
         hipLaunchKernelGGL(bmu_local_kernel<false>, grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1,
-                           (u64)c->W, (u64)c->H, c->lastbmu, c->sqres);
+                           (u64)c->W, (u64)c->H, c->lastbmu.p, c->sqres.p);
     VSOM_HIP_CHECK(hipGetLastError());
     return VSOM_OK;
 }
@@ -927,8 +918,8 @@ int launch_raw_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *vrows_dev, siz
     if (c->transform == VSOM_CLR && !from_map)
         return vsom_fail(VSOM_ERR_UNSUPPORTED, "euclidianWeightedDistRaw against a sample needs depth == sample length");
     dim3 grid((unsigned)((count * 8 + 255) / 256));
-    hipLaunchKernelGGL(raw_dist_kernel, grid, dim3(256), 0, c->stream, c->map, c->sigma, (int)c->pitch,
-                       from_map ? c->map : c->Xs, from_map ? (int)c->pitch : (int)c->xpitch, (int)c->D,
+    hipLaunchKernelGGL(raw_dist_kernel, grid, dim3(256), 0, c->stream, c->map.p, c->sigma.p, (int)c->pitch,
+                       from_map ? c->map.p : c->Xs.p, from_map ? (int)c->pitch : (int)c->xpitch, (int)c->D,
                        (int)c->part_len, (int)c->part_pitch, from_map ? 1 : 0, nodes_dev, vrows_dev, (int)count,
                        out_dev);
     VSOM_HIP_CHECK(hipGetLastError());
@@ -1014,8 +1005,8 @@ int launch_finish(vsom_ctx *c)
     TimerScope ts(c, VSOM_T_FINISH);
     VSOM_HIP_CHECK(hipEventRecord(c->ev_fork, c->stream));
     VSOM_HIP_CHECK(hipStreamWaitEvent(c->aux_stream, c->ev_fork, 0));
-    hipLaunchKernelGGL(finish_kernel, dim3(1u + (unsigned)((c->B + 1023) / 1024)), dim3(1024), 0, c->aux_stream, c->sqres,
-                       (int)c->B, c->mse, c->lastbmu, c->hits);
+    hipLaunchKernelGGL(finish_kernel, dim3(1u + (unsigned)((c->B + 1023) / 1024)), dim3(1024), 0, c->aux_stream, c->sqres.p,
+                       (int)c->B, c->mse.p, c->lastbmu.p, c->hits.p);
     VSOM_HIP_CHECK(hipGetLastError());
     VSOM_HIP_CHECK(hipEventRecord(c->ev_join, c->aux_stream));
     c->aux_pending = true;

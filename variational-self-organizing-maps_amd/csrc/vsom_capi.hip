@@ -89,19 +89,13 @@ int vsom_prefetch_rows(vsom_ctx *c, const float *x_host, size_t B, size_t r0, si
     // the staging kernels of the chunk committed from this slot two prefetches ago must be done
     if (c->staged_valid[k])
         VSOM_HIP_CHECK(hipStreamWaitEvent(c->copy_stream, c->ev_staged[k], 0));
-    if (need > c->Xnext_cap[k]) {
+    if (need > c->Xnext[k].cap) {
         if (c->staged_valid[k])
             VSOM_HIP_CHECK(hipEventSynchronize(c->ev_staged[k]));
-        VSOM_HIP_CHECK(hipStreamSynchronize(c->copy_stream));
-        if (c->Xnext[k])
-            (void)hipFree(c->Xnext[k]);
-        c->Xnext[k] = nullptr;
-        c->Xnext_cap[k] = 0;
-        VSOM_HIP_CHECK(hipMalloc(&c->Xnext[k], need * 4));
-        c->Xnext_cap[k] = need;
+        VSOM_ALLOC_CHECK(vsom_grow(c->Xnext[k], need, c->copy_stream, VSOM_BUF_SYNC));
     }
     if (r1 > r0)
-        VSOM_HIP_CHECK(hipMemcpyAsync(c->Xnext[k] + r0 * c->J, x_host + r0 * c->J, (r1 - r0) * c->J * 4,
+        VSOM_HIP_CHECK(hipMemcpyAsync(c->Xnext[k].p + r0 * c->J, x_host + r0 * c->J, (r1 - r0) * c->J * 4,
                                       hipMemcpyHostToDevice, c->copy_stream));
     VSOM_HIP_CHECK(hipEventRecord(c->ev_copied[k], c->copy_stream));
     c->Bnext = B;
@@ -118,7 +112,7 @@ int vsom_commit_begin(vsom_ctx *c, float **raw, size_t *B)
         return vsom_fail(VSOM_ERR_INVALID, "no prefetched chunk to commit");
     const int k = c->ready_slot;
     VSOM_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_copied[k], 0));
-    *raw = c->Xnext[k];
+    *raw = c->Xnext[k].p;
     *B = c->Bnext;
     return VSOM_OK;
 }
@@ -133,7 +127,7 @@ int vsom_commit_end(vsom_ctx *c)
     c->ready_slot = -1;
     if (c->ahead_valid)           // staged beside the previous epoch (vsom_prefetch_chunk): nothing left to launch
         return vsom_adopt_ahead(c);
-    int rc = vsom_set_chunk_device(c, c->Xnext[k], c->Bnext);
+    int rc = vsom_set_chunk_device(c, c->Xnext[k].p, c->Bnext);
     if (rc)
         return rc;
     VSOM_HIP_CHECK(hipEventRecord(c->ev_staged[k], c->stream));
@@ -153,40 +147,16 @@ int vsom_device_count(void)
     return n;
 }
 
+// streams, events and modules; the buffers are the owners' (vsom_buf.hpp): they go with `delete c`, on c->device
 static int free_all(vsom_ctx *c)
 {
     vsom_custom_destroy(c);
-    void *ptrs[] = {c->map, c->sigma, c->S, c->weight, c->hits, c->Xs, c->XP, c->YP, c->Xraw,
-                    c->lastbmu, c->sqres, c->pair_i, c->pair_j, c->partial, c->nan0,
-                    c->cw, c->lut, c->lutd, c->sl_G, c->sl_nrm, c->sl_scal, c->sl_list, c->sl_tmin, c->sl_fs, c->sl_fm, c->v_dev, c->res_dev, c->onl_state, c->onl_f,
-                    c->cc_flags, c->cc_idx, c->cc_inv, c->cc_meta, c->Xc, c->Mc, c->Uc_map, c->Uc_S, c->Xq, c->zq, c->sl_xi, c->sl_l1, c->sl_q, c->sl_qscale, c->sl_qcorr,
-                    c->lastbmu_alt, c->cc_idx_alt, c->cc_inv_alt, c->cc_meta_alt, c->sl_a2, c->sl_qfast,
-                    c->onl_img, c->onl_nsc, c->onl_lb, c->onl_u, c->onl_xsc, c->q_scratch, c->onl_dirty, c->dd_hash, c->dd_rep, c->dd_list};
-    for (void *p : ptrs)
-        if (p)
-            (void)hipFree(p);
-    if (c->lut_host)
-        (void)hipHostFree(c->lut_host);
-    for (int i = 0; i < 2; ++i)
+    for (int i = 0; i < 2; ++i) {
         if (c->lut_ev[i])
             (void)hipEventDestroy(c->lut_ev[i]);
-    if (c->v_pinned)
-        (void)hipHostFree(c->v_pinned);
-    if (c->st_pinned)
-        (void)hipHostFree(c->st_pinned);
-    if (c->mse)
-        (void)hipHostFree(c->mse);
-    if (c->lutd_host)
-        (void)hipHostFree(c->lutd_host);
-    for (int i = 0; i < 2; ++i)
         if (c->lutd_ev[i])
             (void)hipEventDestroy(c->lutd_ev[i]);
-    if (c->out_pinned)
-        (void)hipHostFree(c->out_pinned);
-    if (c->sl_fb)
-        (void)hipHostFree(c->sl_fb);
-    if (c->cc_fb)
-        (void)hipHostFree(c->cc_fb);
+    }
     for (auto &e : c->ev_live) {
         (void)hipEventDestroy(e.a);
         (void)hipEventDestroy(e.b);
@@ -206,8 +176,6 @@ static int free_all(vsom_ctx *c)
         (void)hipStreamDestroy(c->copy_stream);
     }
     for (int i = 0; i < 2; ++i) {
-        if (c->Xnext[i])
-            (void)hipFree(c->Xnext[i]);
         if (c->ev_copied[i])
             (void)hipEventDestroy(c->ev_copied[i]);
         if (c->ev_staged[i])
@@ -302,19 +270,16 @@ int vsom_create(vsom_ctx **out, int device, uint32_t width, uint32_t height, uin
         }
         c->stream = c->own_stream;
         const size_t nd = (size_t)c->N * c->pitch;
-        if (hipMalloc(&c->map, nd * 4) != hipSuccess || hipMalloc(&c->sigma, nd * 4) != hipSuccess ||
-            hipMalloc(&c->S, nd * 4) != hipSuccess || hipMalloc(&c->weight, (size_t)c->N * 4) != hipSuccess ||
-            hipMalloc(&c->hits, (size_t)c->N * 8) != hipSuccess || hipHostMalloc(&c->mse, 16) != hipSuccess ||
-            hipMalloc(&c->onl_state, VSOM_ONL_STATE_BYTES) != hipSuccess || hipMalloc(&c->onl_f, 64) != hipSuccess) {
+        // (mse: pinned host memory the kernels write through; vsom_get_mse reads it after a stream wait)
+        if (vsom_grow_set(c->stream, 0, {vsom_member(c->map, nd, VSOM_BUF_ZERO), vsom_member(c->sigma, nd, VSOM_BUF_ZERO),
+                                         vsom_member(c->S, nd, VSOM_BUF_ZERO), vsom_member(c->weight, c->N, VSOM_BUF_ZERO),
+                                         vsom_member(c->hits, c->N, VSOM_BUF_ZERO), vsom_member(c->mse, 4, VSOM_BUF_ZERO),
+                                         vsom_member(c->onl_state, VSOM_ONL_STATE_BYTES / sizeof(u64)),
+                                         vsom_member(c->onl_f, 16)}) != hipSuccess) {
+            (void)hipGetLastError();
             rc = vsom_fail(VSOM_ERR_NOMEM, "hipMalloc of model state failed");
             break;
         }
-        (void)hipMemsetAsync(c->map, 0, nd * 4, c->stream);
-        (void)hipMemsetAsync(c->sigma, 0, nd * 4, c->stream);
-        (void)hipMemsetAsync(c->S, 0, nd * 4, c->stream);
-        (void)hipMemsetAsync(c->weight, 0, (size_t)c->N * 4, c->stream);
-        (void)hipMemsetAsync(c->hits, 0, (size_t)c->N * 8, c->stream);
-        std::memset(c->mse, 0, 16);       // (pinned host memory the kernels write through: vsom_get_mse reads it after a stream wait)
         if (transform == VSOM_CLR) {
             // pair tables, i<j lexicographic (Transformation.cpp:94-101; tests/test1.cpp:18-43)
             std::vector<int> pi(c->part_len), pj(c->part_len);
@@ -325,12 +290,13 @@ int vsom_create(vsom_ctx **out, int device, uint32_t width, uint32_t height, uin
                     pj[p] = (int)j;
                     ++p;
                 }
-            if (hipMalloc(&c->pair_i, p * 4) != hipSuccess || hipMalloc(&c->pair_j, p * 4) != hipSuccess) {
+            if (vsom_grow_set(c->stream, 0, {vsom_member(c->pair_i, p), vsom_member(c->pair_j, p)}) != hipSuccess) {
+                (void)hipGetLastError();
                 rc = vsom_fail(VSOM_ERR_NOMEM, "hipMalloc of pair tables failed");
                 break;
             }
-            (void)hipMemcpy(c->pair_i, pi.data(), p * 4, hipMemcpyHostToDevice);
-            (void)hipMemcpy(c->pair_j, pj.data(), p * 4, hipMemcpyHostToDevice);
+            (void)hipMemcpy(c->pair_i.p, pi.data(), p * 4, hipMemcpyHostToDevice);
+            (void)hipMemcpy(c->pair_j.p, pj.data(), p * 4, hipMemcpyHostToDevice);
         }
         if (hipStreamSynchronize(c->stream) != hipSuccess) {
             rc = vsom_fail(VSOM_ERR_HIP, "initialisation failed");
@@ -391,7 +357,7 @@ int vsom_get_shortlist_stats(vsom_ctx *c, uint32_t *out)
         return vsom_fail(VSOM_ERR_INVALID, "null output");
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     for (int i = 0; i < 4; ++i)
-        out[i] = c->sl_fb ? ((volatile unsigned *)c->sl_fb)[i] : 0u;
+        out[i] = c->sl_fb.p ? ((volatile unsigned *)c->sl_fb.p)[i] : 0u;
     return VSOM_OK;
 }
 
@@ -453,21 +419,16 @@ static int copy_rows(vsom_ctx *c, float *dev, const float *host_in, float *host_
         return VSOM_OK;
     }
     if (host_in && bytes <= ((size_t)256 << 20)) {
-        if (bytes > c->st_pinned_cap) {
+        const size_t n = (size_t)c->N * c->D;
+        if (n > c->st_pinned.cap) {
             VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-            if (c->st_pinned)
-                (void)hipHostFree(c->st_pinned);
-            c->st_pinned = nullptr;
-            c->st_pinned_cap = 0;
-            if (hipHostMalloc(&c->st_pinned, bytes) == hipSuccess)
-                c->st_pinned_cap = bytes;
-            else
+            if (vsom_grow(c->st_pinned, n, c->stream) != hipSuccess)
                 (void)hipGetLastError();
         }
-        if (c->st_pinned_cap >= bytes) {
+        if (c->st_pinned.cap >= n) {
             VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));       // the previous array's copy out of the buffer
-            std::memcpy(c->st_pinned, host_in, bytes);
-            host_in = static_cast<const float *>(c->st_pinned);
+            std::memcpy(c->st_pinned.p, host_in, bytes);
+            host_in = c->st_pinned.p;
         }
     }
     for (uint32_t part = 0; part < c->nparts; ++part) {
@@ -492,23 +453,23 @@ int vsom_set_state(vsom_ctx *c, const float *map, const float *sigma, const floa
 {
     CHECK_CTX(c);
     int rc;
-    if (map && (rc = copy_rows(c, c->map, map, nullptr)))
+    if (map && (rc = copy_rows(c, c->map.p, map, nullptr)))
         return rc;
-    if (sigma && (rc = copy_rows(c, c->sigma, sigma, nullptr)))
+    if (sigma && (rc = copy_rows(c, c->sigma.p, sigma, nullptr)))
         return rc;
-    if (S && (rc = copy_rows(c, c->S, S, nullptr)))
+    if (S && (rc = copy_rows(c, c->S.p, S, nullptr)))
         return rc;
     if (weight) {
         if (all_zero_bits(weight, (size_t)c->N * 4))
-            VSOM_HIP_CHECK(hipMemsetAsync(c->weight, 0, (size_t)c->N * 4, c->stream));
+            VSOM_HIP_CHECK(hipMemsetAsync(c->weight.p, 0, (size_t)c->N * 4, c->stream));
         else
-            VSOM_HIP_CHECK(hipMemcpyAsync(c->weight, weight, (size_t)c->N * 4, hipMemcpyHostToDevice, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(c->weight.p, weight, (size_t)c->N * 4, hipMemcpyHostToDevice, c->stream));
     }
     if (bmu_hits) {
         if (all_zero_bits(bmu_hits, (size_t)c->N * 8))
-            VSOM_HIP_CHECK(hipMemsetAsync(c->hits, 0, (size_t)c->N * 8, c->stream));
+            VSOM_HIP_CHECK(hipMemsetAsync(c->hits.p, 0, (size_t)c->N * 8, c->stream));
         else
-            VSOM_HIP_CHECK(hipMemcpyAsync(c->hits, bmu_hits, (size_t)c->N * 8, hipMemcpyHostToDevice, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(c->hits.p, bmu_hits, (size_t)c->N * 8, hipMemcpyHostToDevice, c->stream));
     }
     if (c->cu && sigma)
         return vsom_custom_after_set_state(c);     // (synchronises)
@@ -520,16 +481,16 @@ int vsom_get_state(vsom_ctx *c, float *map, float *sigma, float *S, float *weigh
 {
     CHECK_CTX(c);
     int rc;
-    if (map && (rc = copy_rows(c, c->map, nullptr, map)))
+    if (map && (rc = copy_rows(c, c->map.p, nullptr, map)))
         return rc;
-    if (sigma && (rc = copy_rows(c, c->sigma, nullptr, sigma)))
+    if (sigma && (rc = copy_rows(c, c->sigma.p, nullptr, sigma)))
         return rc;
-    if (S && (rc = copy_rows(c, c->S, nullptr, S)))
+    if (S && (rc = copy_rows(c, c->S.p, nullptr, S)))
         return rc;
     if (weight)
-        VSOM_HIP_CHECK(hipMemcpyAsync(weight, c->weight, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(weight, c->weight.p, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->stream));
     if (bmu_hits)
-        VSOM_HIP_CHECK(hipMemcpyAsync(bmu_hits, c->hits, (size_t)c->N * 8, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(bmu_hits, c->hits.p, (size_t)c->N * 8, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
 }
@@ -541,14 +502,7 @@ static int ensure_chunk_capacity(vsom_ctx *c, size_t B)
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->copy_stream));
     c->ahead_valid = false;       // (a chunk staged ahead into the old buffers is staged anew at its commit)
-    void **ptrs[] = {(void **)&c->Xs, (void **)&c->XP, (void **)&c->YP, (void **)&c->lastbmu, (void **)&c->lastbmu_alt,
-                     (void **)&c->sqres, (void **)&c->nan0, (void **)&c->partial};
-    for (void **p : ptrs) {
-        if (*p)
-            (void)hipFree(*p);
-        *p = nullptr;
-    }
-    c->partial_cap = 0;
+    c->partial.reset();
     c->Bcap = 0;
     // no chunk is staged from here on: should an allocation below fail, later entry points report
     // "no chunk loaded" instead of launching kernels on null buffers
@@ -560,23 +514,13 @@ static int ensure_chunk_capacity(vsom_ctx *c, size_t B)
     // kernel writes next (seen as a few zero sample rows in one search of ~600 random cases)
     // the assembly update kernel reads up to 2 sample rows past the chunk and touches rows up to
     // PF_ROWS + 3 past it (gen_update_asm.py, load_cw)
-    VSOM_HIP_CHECK(hipMalloc(&c->Xs, (cap + VSOM_ROW_PAD) * c->xpitch * 4));
-    VSOM_HIP_CHECK(hipMemsetAsync(c->Xs, 0, (cap + VSOM_ROW_PAD) * c->xpitch * 4, c->stream));
-    if (c->transform == VSOM_CLR) {
-        // like Xs: the pipelined update kernels read one sample pair past the chunk
-        VSOM_HIP_CHECK(hipMalloc(&c->XP, (cap + VSOM_ROW_PAD) * c->part_pitch * 4));
-        VSOM_HIP_CHECK(hipMalloc(&c->YP, (cap + VSOM_ROW_PAD) * c->part_pitch * 4));
-        VSOM_HIP_CHECK(hipMemsetAsync(c->XP, 0, (cap + VSOM_ROW_PAD) * c->part_pitch * 4, c->stream));
-        VSOM_HIP_CHECK(hipMemsetAsync(c->YP, 0, (cap + VSOM_ROW_PAD) * c->part_pitch * 4, c->stream));
-    }
-    VSOM_HIP_CHECK(hipMalloc(&c->lastbmu, cap * 8));
-    VSOM_HIP_CHECK(hipMalloc(&c->lastbmu_alt, cap * 8));
-    VSOM_HIP_CHECK(hipMemsetAsync(c->lastbmu_alt, 0, cap * 8, c->stream));
-    VSOM_HIP_CHECK(hipMalloc(&c->sqres, cap * 4));
-    VSOM_HIP_CHECK(hipMalloc(&c->nan0, cap));
-    VSOM_HIP_CHECK(hipMemsetAsync(c->lastbmu, 0, cap * 8, c->stream));
-    VSOM_HIP_CHECK(hipMemsetAsync(c->sqres, 0, cap * 4, c->stream));
-    VSOM_HIP_CHECK(hipMemsetAsync(c->nan0, 0, cap, c->stream));
+    // XP / YP (CLR) like Xs: the pipelined update kernels read one sample pair past the chunk
+    const size_t pp_rows = c->transform == VSOM_CLR ? (cap + VSOM_ROW_PAD) * c->part_pitch : 0;
+    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_REBUILD,
+                                 {vsom_member(c->Xs, (cap + VSOM_ROW_PAD) * c->xpitch, VSOM_BUF_ZERO),
+                                  vsom_member(c->XP, pp_rows, VSOM_BUF_ZERO), vsom_member(c->YP, pp_rows, VSOM_BUF_ZERO),
+                                  vsom_member(c->lastbmu, cap, VSOM_BUF_ZERO), vsom_member(c->lastbmu_alt, cap, VSOM_BUF_ZERO),
+                                  vsom_member(c->sqres, cap, VSOM_BUF_ZERO), vsom_member(c->nan0, cap, VSOM_BUF_ZERO)}));
     c->Bcap = cap;
     return VSOM_OK;
 }
@@ -605,18 +549,10 @@ static int upload_chunk_impl(vsom_ctx *c, const float *x_host, size_t B, bool wa
     if (B > 0 && !x_host)
         return vsom_fail(VSOM_ERR_INVALID, "x_host is null");
     size_t need = B * c->J;
-    if (need > c->Xraw_cap) {
-        VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (c->Xraw)
-            (void)hipFree(c->Xraw);
-        c->Xraw = nullptr;
-        c->Xraw_cap = 0;
-        VSOM_HIP_CHECK(hipMalloc(&c->Xraw, need * 4));
-        c->Xraw_cap = need;
-    }
+    VSOM_ALLOC_CHECK(vsom_grow(c->Xraw, need, c->stream, VSOM_BUF_SYNC));
     if (need)
-        VSOM_HIP_CHECK(hipMemcpyAsync(c->Xraw, x_host, need * 4, hipMemcpyHostToDevice, c->stream));
-    int rc = vsom_set_chunk_device(c, c->Xraw, B);
+        VSOM_HIP_CHECK(hipMemcpyAsync(c->Xraw.p, x_host, need * 4, hipMemcpyHostToDevice, c->stream));
+    int rc = vsom_set_chunk_device(c, c->Xraw.p, B);
     if (rc)
         return rc;
     if (wait)
@@ -637,7 +573,7 @@ int vsom_host_alloc(void **out, size_t bytes)
     *out = nullptr;
     if (bytes == 0)
         return VSOM_OK;
-    if (hipHostMalloc(out, bytes, hipHostMallocDefault) != hipSuccess) {
+    if (vsom_mem.alloc(out, bytes, true) != hipSuccess) {
         (void)hipGetLastError();
         return vsom_fail(VSOM_ERR_NOMEM, "hipHostMalloc failed");
     }
@@ -647,7 +583,7 @@ int vsom_host_alloc(void **out, size_t bytes)
 int vsom_host_free(void *p)
 {
     if (p)
-        VSOM_HIP_CHECK(hipHostFree(p));
+        VSOM_HIP_CHECK(vsom_mem.release(p, true));
     return VSOM_OK;
 }
 
@@ -672,7 +608,7 @@ int vsom_prefetch_chunk(vsom_ctx *c, const float *x_host, size_t B)
         return rc;
     c->next_dev_pending = false;
     const int k = c->ready_slot;
-    if ((rc = stage_ahead_if_possible(c, c->Xnext[k], B)))
+    if ((rc = stage_ahead_if_possible(c, c->Xnext[k].p, B)))
         return rc;
     if (c->ahead_valid) {         // the slot's raw rows have been read once the ahead staging is through
         VSOM_HIP_CHECK(hipEventRecord(c->ev_staged[k], c->copy_stream));
@@ -741,17 +677,16 @@ int vsom_get_last_bmu(vsom_ctx *c, uint64_t *out_host)
     // short chunks (the reference's own scenarios train 20 rows an epoch): one small kernel stores the indices into pinned
     // host memory -- a device-to-host copy into the caller's pageable buffer was 18 us beyond the wait for the chunk
     if (c->B && c->B <= 8192) {
-        if (!c->out_pinned)
-            VSOM_HIP_CHECK(hipHostMalloc(&c->out_pinned, 8192 * sizeof(uint64_t)));
+        VSOM_ALLOC_CHECK(vsom_grow(c->out_pinned, 8192, c->stream));
         hipLaunchKernelGGL(copy_u64_kernel, dim3((unsigned)((c->B + 255) / 256)), dim3(256), 0, c->stream,
-                           static_cast<u64 *>(c->out_pinned), c->lastbmu, (int)c->B);
+                           c->out_pinned.p, c->lastbmu.p, (int)c->B);
         VSOM_HIP_CHECK(hipGetLastError());
         VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        std::memcpy(out_host, c->out_pinned, c->B * 8);
+        std::memcpy(out_host, c->out_pinned.p, c->B * 8);
         return VSOM_OK;
     }
     if (c->B)
-        VSOM_HIP_CHECK(hipMemcpyAsync(out_host, c->lastbmu, c->B * 8, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(out_host, c->lastbmu.p, c->B * 8, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
 }
@@ -765,7 +700,7 @@ int vsom_set_last_bmu(vsom_ctx *c, const uint64_t *in_host)
         if (in_host[i] >= c->N)
             return vsom_fail(VSOM_ERR_INVALID, "lastBMU index out of range");
     if (c->B)
-        VSOM_HIP_CHECK(hipMemcpyAsync(c->lastbmu, in_host, c->B * 8, hipMemcpyHostToDevice, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(c->lastbmu.p, in_host, c->B * 8, hipMemcpyHostToDevice, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
 }
@@ -776,7 +711,7 @@ int vsom_get_sqres(vsom_ctx *c, float *out_host)
     if (c->B && !out_host)
         return vsom_fail(VSOM_ERR_INVALID, "null output");
     if (c->B)
-        VSOM_HIP_CHECK(hipMemcpyAsync(out_host, c->sqres, c->B * 4, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(out_host, c->sqres.p, c->B * 4, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
 }
@@ -784,9 +719,9 @@ int vsom_get_sqres(vsom_ctx *c, float *out_host)
 static int copy_search_results(vsom_ctx *c, uint64_t *idx, float *dist)
 {
     if (idx && c->B)
-        VSOM_HIP_CHECK(hipMemcpyAsync(idx, c->lastbmu, c->B * 8, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(idx, c->lastbmu.p, c->B * 8, hipMemcpyDeviceToHost, c->stream));
     if (dist && c->B)
-        VSOM_HIP_CHECK(hipMemcpyAsync(dist, c->sqres, c->B * 4, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(dist, c->sqres.p, c->B * 4, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
 }
@@ -816,19 +751,10 @@ int vsom_bmu_local_batch(vsom_ctx *c, uint64_t *idx_out_host, float *dist_out_ho
 }
 
 // device scratch of the distance queries (pair lists in, distances out): grow-only, kept with the context -- a
-// hipMalloc / hipFree pair per call cost more than the queries' kernels (tests/perf/ref_harness.py)
+// device allocation and free per call cost more than the queries' kernels (tests/perf/ref_harness.py)
 static int ensure_query_scratch(vsom_ctx *c, size_t bytes)
 {
-    if (bytes <= c->q_scratch_cap)
-        return VSOM_OK;
-    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    if (c->q_scratch)
-        (void)hipFree(c->q_scratch);
-    c->q_scratch = nullptr;
-    c->q_scratch_cap = 0;
-    const size_t cap = (bytes + 4095) / 4096 * 4096;
-    VSOM_HIP_CHECK(hipMalloc(&c->q_scratch, cap));
-    c->q_scratch_cap = cap;
+    VSOM_ALLOC_CHECK(vsom_grow(c->q_scratch, (bytes + 4095) / 4096 * 4096, c->stream, VSOM_BUF_SYNC));
     return VSOM_OK;
 }
 
@@ -852,8 +778,8 @@ int vsom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *rows
     int rc = ensure_query_scratch(c, 2 * c8 + count * 4);
     if (rc)
         return rc;
-    u64 *dn = reinterpret_cast<u64 *>(c->q_scratch), *dr = reinterpret_cast<u64 *>((char *)c->q_scratch + c8);
-    float *dd = reinterpret_cast<float *>((char *)c->q_scratch + 2 * c8);
+    u64 *dn = reinterpret_cast<u64 *>(c->q_scratch.p), *dr = reinterpret_cast<u64 *>((char *)c->q_scratch.p + c8);
+    float *dd = reinterpret_cast<float *>((char *)c->q_scratch.p + 2 * c8);
     VSOM_HIP_CHECK(hipMemcpyAsync(dn, nodes_host, count * 8, hipMemcpyHostToDevice, c->stream));
     VSOM_HIP_CHECK(hipMemcpyAsync(dr, rows_host, count * 8, hipMemcpyHostToDevice, c->stream));
     if ((rc = launch_pair_dist(c, dn, dr, count, dd)))
@@ -886,7 +812,7 @@ int vsom_distances_row(vsom_ctx *c, size_t row, float *dist_out_host)
     int rc = ensure_query_scratch(c, (size_t)c->N * 4);
     if (rc)
         return rc;
-    float *dd = reinterpret_cast<float *>(c->q_scratch);
+    float *dd = reinterpret_cast<float *>(c->q_scratch.p);
     if ((rc = launch_row_dist(c, row, dd)))
         return rc;
     VSOM_HIP_CHECK(hipMemcpyAsync(dist_out_host, dd, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->stream));
@@ -912,8 +838,8 @@ int vsom_distances_raw(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *
     int rc = ensure_query_scratch(c, 2 * c8 + count * 4);
     if (rc)
         return rc;
-    u64 *dn = reinterpret_cast<u64 *>(c->q_scratch), *dr = reinterpret_cast<u64 *>((char *)c->q_scratch + c8);
-    float *dd = reinterpret_cast<float *>((char *)c->q_scratch + 2 * c8);
+    u64 *dn = reinterpret_cast<u64 *>(c->q_scratch.p), *dr = reinterpret_cast<u64 *>((char *)c->q_scratch.p + c8);
+    float *dd = reinterpret_cast<float *>((char *)c->q_scratch.p + 2 * c8);
     VSOM_HIP_CHECK(hipMemcpyAsync(dn, nodes_host, count * 8, hipMemcpyHostToDevice, c->stream));
     VSOM_HIP_CHECK(hipMemcpyAsync(dr, vrows_host, count * 8, hipMemcpyHostToDevice, c->stream));
     if ((rc = launch_raw_dist(c, dn, dr, count, from_map, dd)))
@@ -979,7 +905,7 @@ int vsom_get_mse(vsom_ctx *c, float *mse_out)
     if (!mse_out)
         return vsom_fail(VSOM_ERR_INVALID, "null output");
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    *mse_out = *static_cast<volatile float *>(c->mse);     // pinned host memory: the kernels' store lands here (22 -> 2 us a call)
+    *mse_out = *static_cast<volatile float *>(c->mse.p);     // pinned host memory: the kernels' store lands here (22 -> 2 us a call)
     return VSOM_OK;
 }
 
@@ -999,14 +925,14 @@ void *vsom_device_ptr(vsom_ctx *c, int which)
     if (!c)
         return nullptr;
     switch (which) {
-    case VSOM_BUF_MAP: return c->map;
-    case VSOM_BUF_SIGMA: return c->sigma;
-    case VSOM_BUF_S: return c->S;
-    case VSOM_BUF_WEIGHT: return c->weight;
-    case VSOM_BUF_HITS: return c->hits;
-    case VSOM_BUF_LASTBMU: return c->lastbmu;
-    case VSOM_BUF_SQRES: return c->sqres;
-    case VSOM_BUF_CHUNK: return c->Xs;
+    case VSOM_BUF_MAP: return c->map.p;
+    case VSOM_BUF_SIGMA: return c->sigma.p;
+    case VSOM_BUF_S: return c->S.p;
+    case VSOM_BUF_WEIGHT: return c->weight.p;
+    case VSOM_BUF_HITS: return c->hits.p;
+    case VSOM_BUF_LASTBMU: return c->lastbmu.p;
+    case VSOM_BUF_SQRES: return c->sqres.p;
+    case VSOM_BUF_CHUNK: return c->Xs.p;
     default: return nullptr;
     }
 }

@@ -154,35 +154,14 @@ static int cc_ensure(vsom_ctx *c)
 {
     if (!c->cpitch)
         c->cpitch = (c->D + 31) / 32 * 32;
-    if (!c->cc_meta) {
-        VSOM_HIP_CHECK(hipMalloc(&c->cc_flags, (size_t)c->xpitch * 4));
-        VSOM_HIP_CHECK(hipMemsetAsync(c->cc_flags, 0, (size_t)c->xpitch * 4, c->stream));
-        VSOM_HIP_CHECK(hipMalloc(&c->cc_idx, (size_t)c->cpitch * 4));
-        VSOM_HIP_CHECK(hipMalloc(&c->cc_inv, (size_t)c->xpitch * 4));
-        VSOM_HIP_CHECK(hipMalloc(&c->cc_idx_alt, (size_t)c->cpitch * 4));      // the record of a chunk staged ahead
-        VSOM_HIP_CHECK(hipMalloc(&c->cc_inv_alt, (size_t)c->xpitch * 4));
-        const size_t meta_bytes = 64;
-        VSOM_HIP_CHECK(hipMalloc(&c->cc_meta, meta_bytes));
-        VSOM_HIP_CHECK(hipMemsetAsync(c->cc_meta, 0, meta_bytes, c->stream));
-        VSOM_HIP_CHECK(hipMalloc(&c->cc_meta_alt, meta_bytes));
-        VSOM_HIP_CHECK(hipMemsetAsync(c->cc_meta_alt, 0, meta_bytes, c->stream));
-        VSOM_HIP_CHECK(hipHostMalloc(&c->cc_fb, 64));
-        c->cc_fb[0] = 0u;
-        c->cc_fb[1] = 0u;
-    }
-    const size_t need = (c->Bcap + VSOM_ROW_PAD) * (size_t)c->cpitch;
-    if (need > c->Xc_cap) {
-        if (c->Xc) {
-            VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-            VSOM_HIP_CHECK(hipFree(c->Xc));
-        }
-        c->Xc = nullptr;
-        c->Xc_cap = 0;
-        VSOM_HIP_CHECK(hipMalloc(&c->Xc, need * 4));
-        // the spare rows behind the chunk are read ahead (never consumed) by the pipelined update kernels
-        VSOM_HIP_CHECK(hipMemsetAsync(c->Xc, 0, need * 4, c->stream));
-        c->Xc_cap = need;
-    }
+    // (the *_alt pair: the record of a chunk staged ahead; meta: 16 words each)
+    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, 0,
+                                 {vsom_member(c->cc_flags, c->xpitch, VSOM_BUF_ZERO), vsom_member(c->cc_idx, c->cpitch),
+                                  vsom_member(c->cc_inv, c->xpitch), vsom_member(c->cc_idx_alt, c->cpitch),
+                                  vsom_member(c->cc_inv_alt, c->xpitch), vsom_member(c->cc_meta, 16, VSOM_BUF_ZERO),
+                                  vsom_member(c->cc_meta_alt, 16, VSOM_BUF_ZERO), vsom_member(c->cc_fb, 16, VSOM_BUF_ZERO)}));
+    // the spare rows behind the chunk are read ahead (never consumed) by the pipelined update kernels
+    VSOM_ALLOC_CHECK(vsom_grow(c->Xc, (c->Bcap + VSOM_ROW_PAD) * (size_t)c->cpitch, c->stream, VSOM_BUF_SYNC | VSOM_BUF_ZERO));
     return VSOM_OK;
 }
 
@@ -195,7 +174,7 @@ int vsom_cc_begin(vsom_ctx *c, size_t B, bool *on)
     if (!vsom_cc_applies(c) || B == 0 || c->cc_min_rows < 0 || (long)B < c->cc_min_rows)
         return VSOM_OK;
     // feedback of earlier chunks (pinned memory, read without synchronising: stale values only delay the decision)
-    volatile unsigned *fb = c->cc_fb;
+    volatile unsigned *fb = c->cc_fb.p;
     if (fb && fb[1] != c->cc_seen) {
         c->cc_seen = fb[1];
         const unsigned kc = fb[0];
@@ -216,8 +195,8 @@ int vsom_cc_begin(vsom_ctx *c, size_t B, bool *on)
 // after the rows are staged (and their live columns flagged): the live-column record, and the chunk gathered onto them
 int vsom_cc_stage(vsom_ctx *c, size_t B, hipStream_t stream, int *idx, int *inv, unsigned *meta, bool *xi_out)
 {
-    hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(1024), 0, stream, c->cc_flags, (int)c->D, (int)c->cpitch, idx, inv, meta,
-                       c->cc_fb);
+    hipLaunchKernelGGL(cc_scan_kernel, dim3(1), dim3(1024), 0, stream, c->cc_flags.p, (int)c->D, (int)c->cpitch, idx, inv, meta,
+                       c->cc_fb.p);
     // the chunk's rows gathered onto the live columns; with the integer shortlist's buffers in place (vsom_sl_i8.hip
     // allocates them at the first search) the same pass writes the chunk's int8 images
     return launch_sl_gather_quant(c, B, stream, idx, xi_out);
@@ -227,11 +206,9 @@ int vsom_cc_stage(vsom_ctx *c, size_t B, hipStream_t stream, int *idx, int *inv,
 int vsom_cc_gather_map(vsom_ctx *c)
 {
     const size_t need = (size_t)c->N * c->cpitch;
-    if (!c->Mc) {
-        VSOM_HIP_CHECK(hipMalloc(&c->Mc, need * 4));
-    }
-    hipLaunchKernelGGL(cc_gather_rows_kernel, dim3((unsigned)c->N), dim3(256), 0, c->stream, c->map, (int)c->pitch, c->Mc,
-                       (int)c->cpitch, c->cc_idx, (int)c->N);
+    VSOM_ALLOC_CHECK(vsom_grow(c->Mc, need, c->stream));
+    hipLaunchKernelGGL(cc_gather_rows_kernel, dim3((unsigned)c->N), dim3(256), 0, c->stream, c->map.p, (int)c->pitch, c->Mc.p,
+                       (int)c->cpitch, c->cc_idx.p, (int)c->N);
     VSOM_HIP_CHECK(hipGetLastError());
     return VSOM_OK;
 }
@@ -239,18 +216,15 @@ int vsom_cc_gather_map(vsom_ctx *c)
 int vsom_cc_ensure_update_scratch(vsom_ctx *c)
 {
     const size_t need = (size_t)c->N * c->cpitch;
-    if (!c->Uc_map) {
-        VSOM_HIP_CHECK(hipMalloc(&c->Uc_map, need * 4));
-        VSOM_HIP_CHECK(hipMalloc(&c->Uc_S, need * 4));
-    }
+    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, 0, {vsom_member(c->Uc_map, need), vsom_member(c->Uc_S, need)}));
     return VSOM_OK;
 }
 
 int vsom_cc_expand(vsom_ctx *c, size_t n0, size_t nloc)
 {
-    hipLaunchKernelGGL(cc_expand_kernel, dim3((unsigned)nloc), dim3(256), 0, c->stream, c->Uc_map, c->Uc_S, (int)c->cpitch,
-                       c->cc_inv, c->map, c->sigma, (int)c->pitch, (int)c->D, (int)n0, (int)nloc, c->weight,
-                       reinterpret_cast<const float4 *>(c->cw));
+    hipLaunchKernelGGL(cc_expand_kernel, dim3((unsigned)nloc), dim3(256), 0, c->stream, c->Uc_map.p, c->Uc_S.p, (int)c->cpitch,
+                       c->cc_inv.p, c->map.p, c->sigma.p, (int)c->pitch, (int)c->D, (int)n0, (int)nloc, c->weight.p,
+                       reinterpret_cast<const float4 *>(c->cw.p));
     VSOM_HIP_CHECK(hipGetLastError());
     return VSOM_OK;
 }

@@ -80,14 +80,14 @@ struct vsom_custom_state {
     hipModule_t mod = nullptr;
     hipFunction_t k_floor = nullptr, k_full = nullptr, k_local = nullptr, k_pair = nullptr, k_resid = nullptr,
                   k_finish = nullptr, k_phase2 = nullptr, k_onl_update = nullptr, k_onl_post = nullptr;
-    float *sigf = nullptr;        // [N][D] select(sigma < 1e-5, 1e-5, sigma): the dispersion the distance passes
-    float *ones = nullptr;        // [J] the value weights (valid * weights: every value of a device sample is valid, weight 1)
-    float *vec = nullptr;         // [J] one host vector (find / dist / train_single)
-    float *resid = nullptr;       // [R] train_single's residual
-    u64 *slot = nullptr;          // [2] one BMU index
-    float *fout = nullptr;        // [2] one distance
-    u64 *pairs = nullptr; float *pair_out = nullptr; size_t pair_cap = 0;
-    double *lutd = nullptr; double lutd_sigma = -1.0;   // [H][W] calculateNeighbourhoodWeight(dx, dy, 0, 0, sigma)
+    DevBuf<float> sigf;           // [N][D] select(sigma < 1e-5, 1e-5, sigma): the dispersion the distance passes
+    DevBuf<float> ones;           // [J] the value weights (valid * weights: every value of a device sample is valid, weight 1)
+    DevBuf<float> vec;            // [J] one host vector (find / dist / train_single)
+    DevBuf<float> resid;          // [R] train_single's residual
+    DevBuf<u64> slot;             // [2] one BMU index
+    DevBuf<float> fout;           // [2] one distance
+    DevBuf<u64> pairs; DevBuf<float> pair_out;    // [2][count] node / row pairs, [count] distances
+    DevBuf<double> lutd; double lutd_sigma = -1.0;   // [H][W] calculateNeighbourhoodWeight(dx, dy, 0, 0, sigma)
     std::vector<float> next; size_t next_B = 0; bool next_pending = false;   // vsom_prefetch_chunk's rows until the commit
 };
 
@@ -105,8 +105,8 @@ int refresh_sigf(vsom_ctx *c)
 {
     vsom_custom_state *u = c->cu;
     u64 n = (u64)c->N * c->D;
-    const float *sg = c->sigma;
-    return launch(c, u->k_floor, (unsigned)((n + 255) / 256), 256, 0, {&sg, &u->sigf, &n});
+    const float *sg = c->sigma.p;
+    return launch(c, u->k_floor, (unsigned)((n + 255) / 256), 256, 0, {&sg, &u->sigf.p, &n});
 }
 
 int ensure_chunk(vsom_ctx *c, size_t B)
@@ -114,19 +114,12 @@ int ensure_chunk(vsom_ctx *c, size_t B)
     if (B <= c->Bcap)
         return VSOM_OK;
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    void **ptrs[] = {(void **)&c->Xs, (void **)&c->lastbmu, (void **)&c->sqres};
-    for (void **p : ptrs) {
-        if (*p)
-            (void)hipFree(*p);
-        *p = nullptr;
-    }
     c->Bcap = 0;
     c->B = 0;
     c->chunk_loaded = false;
     const size_t cap = (B + 63) / 64 * 64;
-    VSOM_HIP_CHECK(hipMalloc(&c->Xs, cap * c->J * 4));
-    VSOM_HIP_CHECK(hipMalloc(&c->lastbmu, cap * 8));
-    VSOM_HIP_CHECK(hipMalloc(&c->sqres, cap * 4));
+    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_REBUILD, {vsom_member(c->Xs, cap * c->J), vsom_member(c->lastbmu, cap),
+                                                               vsom_member(c->sqres, cap)}));
     c->Bcap = cap;
     return VSOM_OK;
 }
@@ -135,7 +128,7 @@ int stage_vec(vsom_ctx *c, const float *v_host)
 {
     if (!v_host)
         return vsom_fail(VSOM_ERR_INVALID, "null vector");
-    VSOM_HIP_CHECK(hipMemcpyAsync(c->cu->vec, v_host, (size_t)c->J * 4, hipMemcpyHostToDevice, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(c->cu->vec.p, v_host, (size_t)c->J * 4, hipMemcpyHostToDevice, c->stream));
     return VSOM_OK;
 }
 
@@ -145,7 +138,7 @@ int search_full(vsom_ctx *c, const float *X, unsigned rows, u64 *bmu, float *dis
     vsom_custom_state *u = c->cu;
     u64 xs = c->J;
     uint32_t N = c->N, J = c->J, D = c->D, R = u->R;
-    return launch(c, u->k_full, rows, 256, 0, {&X, &xs, &c->map, &u->sigf, &u->ones, &N, &J, &D, &R, &bmu, &dist});
+    return launch(c, u->k_full, rows, 256, 0, {&X, &xs, &c->map.p, &u->sigf.p, &u->ones.p, &N, &J, &D, &R, &bmu, &dist});
 }
 
 int search_local(vsom_ctx *c, const float *X, uint32_t rows, const u64 *start, u64 *bmu, float *dist)
@@ -154,7 +147,7 @@ int search_local(vsom_ctx *c, const float *X, uint32_t rows, const u64 *start, u
     u64 xs = c->J;
     uint32_t W = c->W, H = c->H, J = c->J, D = c->D, R = u->R;
     return launch(c, u->k_local, (rows + 63) / 64, 64, 0,
-                  {&X, &xs, &c->map, &u->sigf, &u->ones, &W, &H, &J, &D, &R, &start, &bmu, &dist, &rows});
+                  {&X, &xs, &c->map.p, &u->sigf.p, &u->ones.p, &W, &H, &J, &D, &R, &start, &bmu, &dist, &rows});
 }
 
 int ensure_lutd(vsom_ctx *c, double sigma)
@@ -167,7 +160,7 @@ int ensure_lutd(vsom_ctx *c, double sigma)
         for (uint32_t dx = 0; dx < c->W; ++dx)
             host[(size_t)dy * c->W + dx] = vsom_neighbourhood_weight(dx, dy, 0, 0, sigma);
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));    // its previous contents may still be read
-    VSOM_HIP_CHECK(hipMemcpy(u->lutd, host.data(), host.size() * 8, hipMemcpyHostToDevice));
+    VSOM_HIP_CHECK(hipMemcpy(u->lutd.p, host.data(), host.size() * 8, hipMemcpyHostToDevice));
     u->lutd_sigma = sigma;
     return VSOM_OK;
 }
@@ -178,7 +171,7 @@ int online_step(vsom_ctx *c, const float *x, double eta, double sigma, int decay
                 u64 *hits, float *mse, uint32_t B)
 {
     vsom_custom_state *u = c->cu;
-    int rc = sigma > 1.0 ? search_full(c, x, 1, bmu, u->fout) : search_local(c, x, 1, bmu, bmu, u->fout);
+    int rc = sigma > 1.0 ? search_full(c, x, 1, bmu, u->fout.p) : search_local(c, x, 1, bmu, bmu, u->fout.p);
     if (rc)
         return rc;
     // a box of nx x ny workgroups covers the window: x1 - x0 <= floor(5 sigma) + 1
@@ -186,19 +179,15 @@ int online_step(vsom_ctx *c, const float *x, double eta, double sigma, int decay
     uint32_t nx = ext >= c->W ? c->W : (uint32_t)ext, ny = ext >= c->H ? c->H : (uint32_t)ext;
     uint32_t W = c->W, H = c->H, J = c->J, D = c->D, R = u->R;
     if ((rc = launch(c, u->k_onl_update, nx * ny, 256, 2 * D * 4,
-                     {&x, &c->map, &c->S, &c->sigma, &u->sigf, &c->weight, &bmu, &u->lutd, &W, &H, &u->ones, &J, &D,
+                     {&x, &c->map.p, &c->S.p, &c->sigma.p, &u->sigf.p, &c->weight.p, &bmu, &u->lutd.p, &W, &H, &u->ones.p, &J, &D,
                       &eta, &sigma, &decay_fn, &nx})))
         return rc;
     return launch(c, u->k_onl_post, 1, 64, 0,
-                  {&x, &c->map, &c->sigma, &u->sigf, &u->ones, &J, &D, &R, &bmu, &resid, &dist, &hits, &mse, &B});
+                  {&x, &c->map.p, &c->sigma.p, &u->sigf.p, &u->ones.p, &J, &D, &R, &bmu, &resid, &dist, &hits, &mse, &B});
 }
 
 void free_custom(vsom_custom_state *u)
 {
-    void *ptrs[] = {u->sigf, u->ones, u->vec, u->resid, u->slot, u->fout, u->pairs, u->pair_out, u->lutd};
-    for (void *p : ptrs)
-        if (p)
-            (void)hipFree(p);
     if (u->mod)
         (void)hipModuleUnload(u->mod);
     delete u;
@@ -239,9 +228,9 @@ int vsom_custom_upload(vsom_ctx *c, const float *x_host, size_t B, bool wait)
     if (rc)
         return rc;
     if (B) {
-        VSOM_HIP_CHECK(hipMemcpyAsync(c->Xs, x_host, B * c->J * 4, hipMemcpyHostToDevice, c->stream));
-        VSOM_HIP_CHECK(hipMemsetAsync(c->lastbmu, 0, B * 8, c->stream));     // DataSet.cpp:136-137
-        VSOM_HIP_CHECK(hipMemsetAsync(c->sqres, 0, B * 4, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(c->Xs.p, x_host, B * c->J * 4, hipMemcpyHostToDevice, c->stream));
+        VSOM_HIP_CHECK(hipMemsetAsync(c->lastbmu.p, 0, B * 8, c->stream));     // DataSet.cpp:136-137
+        VSOM_HIP_CHECK(hipMemsetAsync(c->sqres.p, 0, B * 4, c->stream));
     }
     c->B = B;
     c->chunk_loaded = true;
@@ -274,17 +263,17 @@ int vsom_custom_commit(vsom_ctx *c)
 static int copy_results(vsom_ctx *c, uint64_t *idx, float *dist)
 {
     if (idx && c->B)
-        VSOM_HIP_CHECK(hipMemcpyAsync(idx, c->lastbmu, c->B * 8, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(idx, c->lastbmu.p, c->B * 8, hipMemcpyDeviceToHost, c->stream));
     if (dist && c->B)
-        VSOM_HIP_CHECK(hipMemcpyAsync(dist, c->sqres, c->B * 4, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(dist, c->sqres.p, c->B * 4, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
 }
 
 int vsom_custom_bmu_batch(vsom_ctx *c, int local, uint64_t *idx_out_host, float *dist_out_host)
 {
-    int rc = local ? search_local(c, c->Xs, (uint32_t)c->B, c->lastbmu, c->lastbmu, c->sqres)
-                   : search_full(c, c->Xs, (unsigned)c->B, c->lastbmu, c->sqres);
+    int rc = local ? search_local(c, c->Xs.p, (uint32_t)c->B, c->lastbmu.p, c->lastbmu.p, c->sqres.p)
+                   : search_full(c, c->Xs.p, (unsigned)c->B, c->lastbmu.p, c->sqres.p);
     if (rc)
         return rc;
     return copy_results(c, idx_out_host, dist_out_host);
@@ -299,13 +288,13 @@ int vsom_custom_find(vsom_ctx *c, const float *v_host, int local, uint64_t start
     if (rc)
         return rc;
     u64 s = start;
-    VSOM_HIP_CHECK(hipMemcpyAsync(u->slot, &s, 8, hipMemcpyHostToDevice, c->stream));
-    rc = local ? search_local(c, u->vec, 1, u->slot, u->slot, u->fout) : search_full(c, u->vec, 1, u->slot, u->fout);
+    VSOM_HIP_CHECK(hipMemcpyAsync(u->slot.p, &s, 8, hipMemcpyHostToDevice, c->stream));
+    rc = local ? search_local(c, u->vec.p, 1, u->slot.p, u->slot.p, u->fout.p) : search_full(c, u->vec.p, 1, u->slot.p, u->fout.p);
     if (rc)
         return rc;
     float d = 0.f;
-    VSOM_HIP_CHECK(hipMemcpyAsync(&s, u->slot, 8, hipMemcpyDeviceToHost, c->stream));
-    VSOM_HIP_CHECK(hipMemcpyAsync(&d, u->fout, 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(&s, u->slot.p, 8, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(&d, u->fout.p, 4, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     if (bmu_out)
         *bmu_out = s;
@@ -318,29 +307,17 @@ static int pair_dist(vsom_ctx *c, const float *X, const uint64_t *nodes_host, co
                      float *out_host)
 {
     vsom_custom_state *u = c->cu;
-    if (count > u->pair_cap) {
-        VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (u->pairs)
-            (void)hipFree(u->pairs);
-        if (u->pair_out)
-            (void)hipFree(u->pair_out);
-        u->pairs = nullptr;
-        u->pair_out = nullptr;
-        u->pair_cap = 0;
-        VSOM_HIP_CHECK(hipMalloc(&u->pairs, count * 16));
-        VSOM_HIP_CHECK(hipMalloc(&u->pair_out, count * 4));
-        u->pair_cap = count;
-    }
-    u64 *dn = u->pairs, *dr = u->pairs + count;
+    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_SYNC, {vsom_member(u->pairs, 2 * count), vsom_member(u->pair_out, count)}));
+    u64 *dn = u->pairs.p, *dr = u->pairs.p + count;
     VSOM_HIP_CHECK(hipMemcpyAsync(dn, nodes_host, count * 8, hipMemcpyHostToDevice, c->stream));
     VSOM_HIP_CHECK(hipMemcpyAsync(dr, rows_host, count * 8, hipMemcpyHostToDevice, c->stream));
     u64 xs = c->J, cnt = count;
     uint32_t J = c->J, D = c->D, R = u->R;
     int rc = launch(c, u->k_pair, (unsigned)((count + 63) / 64), 64, 0,
-                    {&X, &xs, &c->map, &u->sigf, &u->ones, &J, &D, &R, &dn, &dr, &cnt, &u->pair_out});
+                    {&X, &xs, &c->map.p, &u->sigf.p, &u->ones.p, &J, &D, &R, &dn, &dr, &cnt, &u->pair_out.p});
     if (rc)
         return rc;
-    VSOM_HIP_CHECK(hipMemcpyAsync(out_host, u->pair_out, count * 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(out_host, u->pair_out.p, count * 4, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
 }
@@ -353,7 +330,7 @@ int vsom_custom_dist_single(vsom_ctx *c, const float *v_host, uint64_t node, flo
     if (rc)
         return rc;
     const uint64_t row = 0;
-    return pair_dist(c, c->cu->vec, &node, &row, 1, dist_out);
+    return pair_dist(c, c->cu->vec.p, &node, &row, 1, dist_out);
 }
 
 int vsom_custom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *rows_host, size_t count,
@@ -368,7 +345,7 @@ int vsom_custom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_
     for (size_t i = 0; i < count; ++i)
         if (nodes_host[i] >= c->N || rows_host[i] >= c->B)
             return vsom_fail(VSOM_ERR_INVALID, "pair index out of range");
-    return pair_dist(c, c->Xs, nodes_host, rows_host, count, dist_out_host);
+    return pair_dist(c, c->Xs.p, nodes_host, rows_host, count, dist_out_host);
 }
 
 // Som::trainBatchSomEpoch (hostBatchEpoch): phase 1 search + residual, bmuHits / MSE, phase 2 per node
@@ -378,23 +355,23 @@ int vsom_custom_batch_epoch_async(vsom_ctx *c, double sigma, int is_first)
         return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
     vsom_custom_state *u = c->cu;
     uint32_t B = (uint32_t)c->B, W = c->W, H = c->H, J = c->J, D = c->D, R = u->R;
-    int rc = is_first ? search_full(c, c->Xs, B, c->lastbmu, c->sqres)
-                      : search_local(c, c->Xs, B, c->lastbmu, c->lastbmu, c->sqres);
+    int rc = is_first ? search_full(c, c->Xs.p, B, c->lastbmu.p, c->sqres.p)
+                      : search_local(c, c->Xs.p, B, c->lastbmu.p, c->lastbmu.p, c->sqres.p);
     if (rc)
         return rc;
     u64 xs = c->J;
     if ((rc = launch(c, u->k_resid, (B + 63) / 64, 64, 0,
-                     {&c->Xs, &xs, &c->map, &c->S, &u->ones, &J, &D, &R, &c->lastbmu, &c->sqres, &B})))
+                     {&c->Xs.p, &xs, &c->map.p, &c->S.p, &u->ones.p, &J, &D, &R, &c->lastbmu.p, &c->sqres.p, &B})))
         return rc;
-    float *mse = c->mse;
-    if ((rc = launch(c, u->k_finish, 1, 64, 0, {&c->lastbmu, &c->sqres, &B, &c->hits, &mse})))
+    float *mse = c->mse.p;
+    if ((rc = launch(c, u->k_finish, 1, 64, 0, {&c->lastbmu.p, &c->sqres.p, &B, &c->hits.p, &mse})))
         return rc;
     if ((rc = ensure_lut(c, sigma)))
         return rc;
     uint32_t lutw = c->lut_w;
     return launch(c, u->k_phase2, c->N, 256, 3 * D * 4,
-                  {&c->Xs, &xs, &c->map, &c->sigma, &u->sigf, &c->weight, &c->lastbmu, &c->lut, &lutw, &W, &H, &B,
-                   &u->ones, &J, &D});
+                  {&c->Xs.p, &xs, &c->map.p, &c->sigma.p, &u->sigf.p, &c->weight.p, &c->lastbmu.p, &c->lut.p, &lutw, &W, &H, &B,
+                   &u->ones.p, &J, &D});
 }
 
 // Som::trainSingle (hostTrainSingle) on one host vector
@@ -412,14 +389,14 @@ int vsom_custom_train_single(vsom_ctx *c, const float *v_host, double eta, doubl
     if (rc || (rc = ensure_lutd(c, sigma)))
         return rc;
     u64 s = *last_bmu;
-    VSOM_HIP_CHECK(hipMemcpyAsync(u->slot, &s, 8, hipMemcpyHostToDevice, c->stream));
-    if ((rc = online_step(c, u->vec, eta, sigma, decay_fn, u->slot, u->resid, u->fout + 1, nullptr, nullptr, 1)))
+    VSOM_HIP_CHECK(hipMemcpyAsync(u->slot.p, &s, 8, hipMemcpyHostToDevice, c->stream));
+    if ((rc = online_step(c, u->vec.p, eta, sigma, decay_fn, u->slot.p, u->resid.p, u->fout.p + 1, nullptr, nullptr, 1)))
         return rc;
     float d = 0.f;
-    VSOM_HIP_CHECK(hipMemcpyAsync(&s, u->slot, 8, hipMemcpyDeviceToHost, c->stream));
-    VSOM_HIP_CHECK(hipMemcpyAsync(&d, u->fout + 1, 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(&s, u->slot.p, 8, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(&d, u->fout.p + 1, 4, hipMemcpyDeviceToHost, c->stream));
     if (residual_out)
-        VSOM_HIP_CHECK(hipMemcpyAsync(residual_out, u->resid, (size_t)u->R * 4, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(residual_out, u->resid.p, (size_t)u->R * 4, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     *last_bmu = s;
     if (bmu_out)
@@ -442,12 +419,12 @@ int vsom_custom_train_online_chunk(vsom_ctx *c, double eta, double sigma, int de
         return rc;
     if (first_chunk) {
         VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        *static_cast<volatile float *>(c->mse) = 0.f;
+        *static_cast<volatile float *>(c->mse.p) = 0.f;
     }
     const uint32_t B = (uint32_t)c->B;
     for (uint32_t s = 0; s < B; ++s)
-        if ((rc = online_step(c, c->Xs + (size_t)s * c->J, eta, sigma, decay_fn, c->lastbmu + s, nullptr, u->fout + 1,
-                              c->hits, c->mse, B)))
+        if ((rc = online_step(c, c->Xs.p + (size_t)s * c->J, eta, sigma, decay_fn, c->lastbmu.p + s, nullptr, u->fout.p + 1,
+                              c->hits.p, c->mse.p, B)))
             return rc;
     return VSOM_OK;
 }
@@ -502,24 +479,17 @@ int vsom_create_custom(vsom_ctx **out, int device, uint32_t width, uint32_t heig
     c->pitch = depth;
     c->xpitch = in_len;
     const size_t nd = (size_t)c->N * depth;
-    (void)hipStreamSynchronize(c->stream);
-    void **state[] = {(void **)&c->map, (void **)&c->sigma, (void **)&c->S};
-    for (void **p : state) {
-        (void)hipFree(*p);
-        *p = nullptr;
-    }
-    if (hipMalloc(&c->map, nd * 4) != hipSuccess || hipMalloc(&c->sigma, nd * 4) != hipSuccess ||
-        hipMalloc(&c->S, nd * 4) != hipSuccess || hipMalloc(&u->sigf, nd * 4) != hipSuccess ||
-        hipMalloc(&u->ones, (size_t)in_len * 4) != hipSuccess || hipMalloc(&u->vec, (size_t)in_len * 4) != hipSuccess ||
-        hipMalloc(&u->resid, (size_t)residual_len * 4) != hipSuccess || hipMalloc(&u->slot, 16) != hipSuccess ||
-        hipMalloc(&u->fout, 8) != hipSuccess || hipMalloc(&u->lutd, (size_t)width * height * 8) != hipSuccess) {
+    // the model state at this depth replaces the built-in one (zero-filled on the stream: the first use is on it)
+    if (vsom_grow_set(c->stream, VSOM_BUF_SYNC | VSOM_BUF_REBUILD,
+                      {vsom_member(c->map, nd, VSOM_BUF_ZERO), vsom_member(c->sigma, nd, VSOM_BUF_ZERO),
+                       vsom_member(c->S, nd, VSOM_BUF_ZERO), vsom_member(u->sigf, nd), vsom_member(u->ones, in_len),
+                       vsom_member(u->vec, in_len), vsom_member(u->resid, residual_len), vsom_member(u->slot, 2),
+                       vsom_member(u->fout, 2), vsom_member(u->lutd, (size_t)width * height)}) != hipSuccess) {
         (void)hipGetLastError();
         return fail(VSOM_ERR_NOMEM, "hipMalloc of the custom context's state failed");
     }
     const std::vector<float> ones(in_len, 1.f);
-    if (hipMemset(c->map, 0, nd * 4) != hipSuccess || hipMemset(c->sigma, 0, nd * 4) != hipSuccess ||
-        hipMemset(c->S, 0, nd * 4) != hipSuccess ||
-        hipMemcpy(u->ones, ones.data(), (size_t)in_len * 4, hipMemcpyHostToDevice) != hipSuccess)
+    if (hipMemcpy(u->ones.p, ones.data(), (size_t)in_len * 4, hipMemcpyHostToDevice) != hipSuccess)
         return fail(VSOM_ERR_HIP, "initialisation of the custom context failed");
     if (hipModuleLoadData(&u->mod, code.data()) != hipSuccess) {
         (void)hipGetLastError();

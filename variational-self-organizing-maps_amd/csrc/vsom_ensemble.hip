@@ -19,8 +19,8 @@ struct vsom_ensemble {
     hipStream_t own_stream = nullptr;        // launch stream when the members' streams differ
     std::vector<hipEvent_t> ev_in;           // behind each distinct member stream's pending work
     struct Slot {
-        unsigned char *host = nullptr, *dev = nullptr;
-        size_t cap = 0;
+        PinnedBuf<unsigned char> host;       // descriptors staged here, copied to dev
+        DevBuf<unsigned char> dev;
         hipEvent_t ev = nullptr;
         bool valid = false;
     } slot[2];
@@ -84,10 +84,6 @@ void vsom_ensemble_destroy(vsom_ensemble *e)
             (void)hipEventSynchronize(s.ev);
         if (s.ev)
             (void)hipEventDestroy(s.ev);
-        if (s.host)
-            (void)hipHostFree(s.host);
-        if (s.dev)
-            (void)hipFree(s.dev);
     }
     for (hipEvent_t ev : e->ev_in)
         (void)hipEventDestroy(ev);
@@ -155,22 +151,14 @@ static int launch_groups(vsom_ensemble *e, int ngroups, size_t stride, Ready rea
     if (s.valid)
         VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
     s.valid = false;
-    if (bytes > s.cap) {
-        if (s.host)
-            VSOM_HIP_CHECK(hipHostFree(s.host));
-        if (s.dev)
-            VSOM_HIP_CHECK(hipFree(s.dev));
-        s.host = s.dev = nullptr;
-        s.cap = 0;
+    if (bytes > s.host.cap) {
         const size_t cap = std::max(bytes, (size_t)64 * stride);
-        VSOM_HIP_CHECK(hipHostMalloc(&s.host, cap));
-        VSOM_HIP_CHECK(hipMalloc(&s.dev, cap));
-        s.cap = cap;
+        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, VSOM_BUF_REBUILD, {vsom_member(s.host, cap), vsom_member(s.dev, cap)}));
     }
     std::vector<size_t> at(off.begin(), off.end() - 1);
     for (size_t k = 0; k < n; ++k)
         if (e->grp[k] >= 0)
-            std::memcpy(s.host + (at[e->grp[k]]++) * stride, e->desc.data() + k * stride, stride);
+            std::memcpy(s.host.p + (at[e->grp[k]]++) * stride, e->desc.data() + k * stride, stride);
 
     // the launch stream: the members' one stream, or the ensemble's own behind every member stream's pending work
     hipStream_t ls = shared;
@@ -195,10 +183,10 @@ static int launch_groups(vsom_ensemble *e, int ngroups, size_t stride, Ready rea
         }
     }
     *ls_out = ls;
-    VSOM_HIP_CHECK(hipMemcpyAsync(s.dev, s.host, bytes, hipMemcpyHostToDevice, ls));
+    VSOM_HIP_CHECK(hipMemcpyAsync(s.dev.p, s.host.p, bytes, hipMemcpyHostToDevice, ls));
     for (int g = 0; g < ngroups; ++g)
         if (cnt[g])
-            if (int rc = launch(g, s.dev + off[g] * stride, cnt[g], gsmem[g], ls))
+            if (int rc = launch(g, s.dev.p + off[g] * stride, cnt[g], gsmem[g], ls))
                 return rc;
     VSOM_HIP_CHECK(hipEventRecord(s.ev, ls));
     s.valid = true;
@@ -267,9 +255,9 @@ int vsom_ensemble_train_online_chunk_fetch(vsom_ensemble *e, const double *eta, 
             continue;
         vsom_ctx *c = e->m[k];
         if (lastbmu_out && lastbmu_out[k])
-            std::memcpy(lastbmu_out[k], c->out_pinned, c->B * sizeof(uint64_t));
+            std::memcpy(lastbmu_out[k], c->out_pinned.p, c->B * sizeof(uint64_t));
         if (mse_out)
-            mse_out[k] = *static_cast<volatile float *>(c->mse);
+            mse_out[k] = *static_cast<volatile float *>(c->mse.p);
     }
     return VSOM_OK;
 }
@@ -318,6 +306,6 @@ int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_firs
         return rc;
     for (size_t k = 0; k < n; ++k)
         if (e->grp[k] >= 0 && mse_out)
-            mse_out[k] = *static_cast<volatile float *>(e->m[k]->mse);
+            mse_out[k] = *static_cast<volatile float *>(e->m[k]->mse.p);
     return VSOM_OK;
 }

@@ -441,24 +441,16 @@ int vsom_group_set_chunk_device(vsom_group *g, const void *const *rows_dev, size
         vsom_ctx *c = g->ctx[r];
         VSOM_HIP_CHECK(hipSetDevice(g->dev[r]));
         const size_t need = B * c->J;
-        if (need > c->Xraw_cap) {
-            VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-            if (c->Xraw)
-                (void)hipFree(c->Xraw);
-            c->Xraw = nullptr;
-            c->Xraw_cap = 0;
-            VSOM_HIP_CHECK(hipMalloc(&c->Xraw, need * 4));
-            c->Xraw_cap = need;
-        }
+        VSOM_ALLOC_CHECK(vsom_grow(c->Xraw, need, c->stream, VSOM_BUF_SYNC));
         size_t lo, hi;
         shard(B, n, r, lo, hi);
         if (hi > lo) {
             if (!rows_dev[r])
                 return vsom_fail(VSOM_ERR_INVALID, "rows_dev[r] is null");
-            VSOM_HIP_CHECK(hipMemcpyAsync(c->Xraw + lo * c->J, rows_dev[r], (hi - lo) * (size_t)c->J * 4,
+            VSOM_HIP_CHECK(hipMemcpyAsync(c->Xraw.p + lo * c->J, rows_dev[r], (hi - lo) * (size_t)c->J * 4,
                                           hipMemcpyDeviceToDevice, c->stream));
         }
-        base[r] = (char *)c->Xraw;
+        base[r] = (char *)c->Xraw.p;
     }
     auto st = main_streams(g);
     int rc = gather_rows(g, base, (size_t)g->ctx[0]->J * 4, B, st);   // chunk replication over xGMI
@@ -466,7 +458,7 @@ int vsom_group_set_chunk_device(vsom_group *g, const void *const *rows_dev, size
         return rc;
     for (int r = 0; r < n; ++r) {
         VSOM_HIP_CHECK(hipSetDevice(g->dev[r]));
-        if ((rc = vsom_set_chunk_device(g->ctx[r], g->ctx[r]->Xraw, B)))
+        if ((rc = vsom_set_chunk_device(g->ctx[r], g->ctx[r]->Xraw.p, B)))
             return rc;
     }
     return VSOM_OK;
@@ -525,11 +517,11 @@ int vsom_group_batch_epoch_async(vsom_group *g, double sigma, int is_first)
             return rc;
     }
     for (int r = 0; r < n; ++r)
-        base[r] = (char *)g->ctx[r]->lastbmu;
+        base[r] = (char *)g->ctx[r]->lastbmu.p;
     if ((rc = gather_rows(g, base, 8, B, st)))
         return rc;
     for (int r = 0; r < n; ++r)
-        base[r] = (char *)g->ctx[r]->sqres;
+        base[r] = (char *)g->ctx[r]->sqres.p;
     if ((rc = gather_rows(g, base, 4, B, st)))
         return rc;
     for (int r = 0; r < n; ++r)
@@ -546,7 +538,7 @@ int vsom_group_batch_epoch_async(vsom_group *g, double sigma, int is_first)
     }
     const size_t row = (size_t)c0->pitch * 4;
     for (int r = 0; r < n; ++r)
-        base[r] = (char *)g->ctx[r]->map;
+        base[r] = (char *)g->ctx[r]->map.p;
     if ((rc = gather_rows(g, base, row, N, st)))         // the next search needs the whole map
         return rc;
     if (n > 1 || g->use_rccl) {
@@ -557,11 +549,11 @@ int vsom_group_batch_epoch_async(vsom_group *g, double sigma, int is_first)
             VSOM_HIP_CHECK(hipStreamWaitEvent(g->gstream[r], g->ev_p2[r], 0));
         }
         for (int r = 0; r < n; ++r)
-            base[r] = (char *)g->ctx[r]->sigma;
+            base[r] = (char *)g->ctx[r]->sigma.p;
         if ((rc = gather_rows(g, base, row, N, g->gstream)))
             return rc;
         for (int r = 0; r < n; ++r)
-            base[r] = (char *)g->ctx[r]->weight;
+            base[r] = (char *)g->ctx[r]->weight.p;
         if ((rc = gather_rows(g, base, 4, N, g->gstream)))
             return rc;
         for (int r = 0; r < n; ++r) {

@@ -19,6 +19,7 @@
 #include <vector>
 
 #include "../../include/vsom_hip.h"
+#include "vsom_buf.hpp"
 
 typedef unsigned long long u64;
 
@@ -54,18 +55,16 @@ struct vsom_ctx {
     bool aux_pending = false;
 
     // model state
-    float *map = nullptr, *sigma = nullptr, *S = nullptr, *weight = nullptr;
-    u64 *hits = nullptr;
+    DevBuf<float> map, sigma, S, weight;
+    DevBuf<u64> hits;
 
     // chunk
     size_t B = 0, Bcap = 0;
     bool chunk_loaded = false;      // a chunk (possibly of 0 rows) has been staged
-    float *Xs = nullptr, *XP = nullptr, *YP = nullptr;
-    float *Xraw = nullptr;          // staging for host uploads (B x J, unpadded)
-    size_t Xraw_cap = 0;
+    DevBuf<float> Xs, XP, YP;
+    DevBuf<float> Xraw;             // staging for host uploads (B x J, unpadded)
     // double-buffered ingest: raw chunks land here on copy_stream while the current chunk trains
-    float *Xnext[2] = {nullptr, nullptr};
-    size_t Xnext_cap[2] = {0, 0};
+    DevBuf<float> Xnext[2];
     size_t Bnext = 0;
     int next_slot = 0;              // slot the next prefetch writes
     int ready_slot = -1;            // slot holding a prefetched, not yet committed chunk
@@ -73,16 +72,16 @@ struct vsom_ctx {
     hipEvent_t ev_copied[2] = {nullptr, nullptr};    // H2D copy into slot finished
     hipEvent_t ev_staged[2] = {nullptr, nullptr};    // staging kernels that read slot finished
     bool staged_valid[2] = {false, false};
-    u64 *lastbmu = nullptr;
-    float *sqres = nullptr;
+    DevBuf<u64> lastbmu;
+    DevBuf<float> sqres;
     // The NEXT chunk staged beside the epoch of the current one (vsom_prefetch_chunk / vsom_stage_next_device -> copy
     // stream; vsom_commit_chunk adopts it).  Once a phase 2 has built its transposed chunk nothing of the epoch reads the
     // staged rows (Xs, Xc, the int8 images) any more -- `ev_rows_free` -- so the staging kernels of chunk k+1 may
     // overwrite them while the chains of chunk k run; what phase 2 still reads is double-buffered: lastBMU and the
     // compaction's column record (the *_alt set is what the ahead staging writes, commit swaps the two).
-    u64 *lastbmu_alt = nullptr;
-    int *cc_idx_alt = nullptr, *cc_inv_alt = nullptr;
-    unsigned *cc_meta_alt = nullptr;
+    DevBuf<u64> lastbmu_alt;
+    DevBuf<int> cc_idx_alt, cc_inv_alt;
+    DevBuf<unsigned> cc_meta_alt;
     hipEvent_t ev_rows_free = nullptr, ev_ahead = nullptr;
     bool rows_free_valid = false;   // ev_rows_free belongs to the last enqueued work on this context
     bool ahead_valid = false;       // a chunk is staged ahead (ahead_B rows; its compaction / int8-image state below)
@@ -95,31 +94,30 @@ struct vsom_ctx {
     const float *next_dev = nullptr;   // vsom_stage_next_device: rows in HBM waiting for vsom_commit_chunk
     size_t next_dev_B = 0;
     bool next_dev_pending = false;
-    float *mse = nullptr;           // [1]  pinned HOST memory (device-visible): kernels store, vsom_get_mse reads after a stream wait
-    int *pair_i = nullptr, *pair_j = nullptr;   // CLR pair tables [P]
+    PinnedBuf<float> mse;           // [1]  pinned HOST memory (device-visible): kernels store, vsom_get_mse reads after a stream wait
+    DevBuf<int> pair_i, pair_j;     // CLR pair tables [P]
 
     // BMU tile-search scratch
-    u64 *partial = nullptr; size_t partial_cap = 0;
-    unsigned char *nan0 = nullptr;
+    DevBuf<u64> partial;
+    DevBuf<unsigned char> nan0;
 
     // duplicate-row representatives of the exact search (vsom_bmu.hip, bmu_dedupe_*)
-    void *dd_hash = nullptr; int *dd_rep = nullptr, *dd_list = nullptr;
+    DevBuf<u64> dd_hash; DevBuf<int> dd_rep, dd_list;
     bool dedupe = true;             // VSOM_NO_DEDUPE=1 switches it off (A/B measurements)
     double dd_min_work = 2.0e10;    // exact searches of at least this many (sample, node, value) triples (vsom_set_row_dedupe)
     bool tiny_lds_attr[12] = {};    // online_tiny_chunk_kernel<kind, local, U>: dynamic LDS limit raised (per context: its device, its kind)
 
     // MFMA shortlist scratch
-    float *sl_G = nullptr; size_t sl_cap = 0; float *sl_nrm = nullptr; unsigned *sl_scal = nullptr;
-    float *sl_a2 = nullptr;         // CLR shortlist: per-node max A^2 (the select kernel's per-node bounds)
-    int *sl_list = nullptr; size_t sl_list_cap = 0;
-    float *sl_tmin = nullptr; size_t sl_tmin_cap = 0;
-    unsigned *sl_fb = nullptr;      // pinned host feedback: {redo samples, candidates, rows, seq}
-    float *sl_fs = nullptr, *sl_fm = nullptr;      // CLR shortlist: sample / node feature rows (vsom_shortlist.hip)
-    size_t sl_fs_cap = 0, sl_fm_cap = 0;           // bytes
+    DevBuf<float> sl_G, sl_nrm; DevBuf<unsigned> sl_scal;
+    DevBuf<float> sl_a2;            // CLR shortlist: per-node max A^2 (the select kernel's per-node bounds)
+    DevBuf<int> sl_list;
+    DevBuf<float> sl_tmin;
+    PinnedBuf<unsigned> sl_fb;      // pinned host feedback: {redo samples, candidates, rows, seq}
+    DevBuf<float> sl_fs, sl_fm;     // CLR shortlist: sample / node feature rows (vsom_shortlist.hip)
     // integer contraction of the shortlist (vsom_sl_i8.hip): int8 images of the chunk / the model rows
-    signed char *sl_xi = nullptr; size_t sl_xi_cap = 0; float *sl_l1 = nullptr;
-    signed char *sl_q = nullptr; double *sl_qscale = nullptr, *sl_qcorr = nullptr;
-    void *sl_qfast = nullptr;       // int4 per node: the constants of the uint8 kind's fp32 epilogue (sl_i8_value_fast)
+    DevBuf<signed char> sl_xi; DevBuf<float> sl_l1;
+    DevBuf<signed char> sl_q; DevBuf<double> sl_qscale, sl_qcorr;
+    DevBuf<int4> sl_qfast;          // per node: the constants of the uint8 kind's fp32 epilogue (sl_i8_value_fast)
     uint32_t sl_kp8 = 0;
     bool xi_valid = false;          // sl_xi / sl_l1 describe the staged chunk
     int sl_par = 0;                 // which of the two scal sets the next search uses
@@ -128,14 +126,14 @@ struct vsom_ctx {
     int sl_fail_streak = 0;         // consecutive probes that had to redo most samples exactly
 
     // neighbourhood
-    float2 *cw = nullptr; size_t cw_cap = 0;
-    float *lut = nullptr; size_t lut_cap = 0; float *lut_host = nullptr;   // lut_host: 2 x lut_cap, pinned
+    DevBuf<float2> cw;
+    DevBuf<float> lut; PinnedBuf<float> lut_host;     // lut_host: 2 x lut.cap
     hipEvent_t lut_ev[2] = {nullptr, nullptr}; bool lut_ev_valid[2] = {false, false}; int lut_slot = 0;
     double lut_sigma = -1.0; uint32_t lut_w = 0, lut_h = 0;
-    double *lutd = nullptr; size_t lutd_cap = 0; double lutd_sigma = -1.0;   // online path (double)
+    DevBuf<double> lutd; double lutd_sigma = -1.0;   // online path (double)
     // the table's host image: two pinned slots used alternately (the device copy is enqueued on the stream, one-launch
     // chunks of tiny maps read the slot itself), each guarded by an event recorded behind its last reader
-    double *lutd_host = nullptr; size_t lutd_host_cap = 0; double lutd_host_sigma[2] = {-1.0, -1.0};
+    PinnedBuf<double> lutd_host; double lutd_host_sigma[2] = {-1.0, -1.0};   // 2 slots of W x H
     hipEvent_t lutd_ev[2] = {nullptr, nullptr}; bool lutd_ev_valid[2] = {false, false}; int lutd_slot = 0;
 
     // hand-scheduled update kernel (code object loaded with hipModuleLoadData)
@@ -145,42 +143,42 @@ struct vsom_ctx {
     bool use_tiny = true;           // one-launch epoch for tiny maps (VSOM_NO_TINY=1 disables, debugging)
 
     // column compaction (vsom_compact.hip): columns that are zero in every row of the chunk are retired exactly
-    unsigned *cc_flags = nullptr;   // [xpitch] live flags
-    int *cc_idx = nullptr;          // [cpitch] live column list, -1 beyond the live count
-    int *cc_inv = nullptr;          // [xpitch] column -> compacted position or -1
-    unsigned *cc_meta = nullptr;    // device: {live columns, live 14-dim slices, live columns rounded up to 32, seq}
-    unsigned *cc_fb = nullptr;      // pinned host mirror: {live columns, seq}
+    DevBuf<unsigned> cc_flags;      // [xpitch] live flags
+    DevBuf<int> cc_idx;             // [cpitch] live column list, -1 beyond the live count
+    DevBuf<int> cc_inv;             // [xpitch] column -> compacted position or -1
+    DevBuf<unsigned> cc_meta;       // device: {live columns, live 14-dim slices, live columns rounded up to 32, seq}
+    PinnedBuf<unsigned> cc_fb;      // pinned host mirror: {live columns, seq}
     unsigned cc_seen = 0;
     int cc_skip = 0;
     long cc_min_rows = 1024;        // chunks with fewer rows are not compacted (< 0: never)
     bool cc_valid = false;          // the staged chunk has a compaction (Xc, cc_idx, cc_meta describe it)
     uint32_t cpitch = 0;            // row pitch of the compacted matrices
-    float *Xc = nullptr; size_t Xc_cap = 0;      // (Bcap + VSOM_ROW_PAD) x cpitch
-    float *Mc = nullptr;            // N x cpitch: model rows on the live columns (search)
-    float *Uc_map = nullptr, *Uc_S = nullptr;    // N x cpitch: the chains' M and raw S on the live columns
+    DevBuf<float> Xc;               // (Bcap + VSOM_ROW_PAD) x cpitch
+    DevBuf<float> Mc;               // N x cpitch: model rows on the live columns (search)
+    DevBuf<float> Uc_map, Uc_S;     // N x cpitch: the chains' M and raw S on the live columns
     // the chunk transposed into column quads (vsom_xq.hip) for the lane = node, four-dims-per-wavefront chain kernels
-    float *Xq = nullptr; size_t Xq_cap = 0;      // [quads rounded up to 8][bpad] float4
-    unsigned *zq = nullptr;                      // [quads][bpad / 32] all-zero (sample, quad) bits
+    DevBuf<float4> Xq;              // [quads rounded up to 8][bpad]
+    DevBuf<unsigned> zq;            // [quads][bpad / 32] all-zero (sample, quad) bits
     bool xq_valid = false;
     uint32_t xq_bpad = 0, xq_quads = 0;
 
     // online path scratch
-    float *v_dev = nullptr;         // one sample, padded
-    float *v_pinned = nullptr;      // its pinned host staging (+ 16 floats for results)
-    float *res_dev = nullptr;       // residual
-    u64 *onl_state = nullptr;       // argmin key slots + flags of the online scan (vsom_online.hip)
-    float *onl_f = nullptr;         // [4]: dist, mse
+    DevBuf<float> v_dev;            // one sample, padded
+    PinnedBuf<float> v_pinned;      // its pinned host staging (+ 16 floats for results)
+    DevBuf<float> res_dev;          // residual
+    DevBuf<u64> onl_state;          // argmin key slots + flags of the online scan (vsom_online.hip)
+    DevBuf<float> onl_f;            // [4]: dist, mse
     // image-bounded search of the online chunk loop (vsom_online.hip): one byte per model value + 4 scalars per node,
     // lower bounds of the sample being searched, min-upper-bound slots, per-sample bound terms
-    unsigned char *onl_img = nullptr; void *onl_nsc = nullptr; float *onl_lb = nullptr; unsigned *onl_u = nullptr;
-    void *onl_xsc = nullptr; size_t onl_xsc_cap = 0;
-    unsigned char *onl_dirty = nullptr;      // [N] nodes whose sigmaMap row is written at the end of the chunk
+    DevBuf<unsigned char> onl_img; DevBuf<float4> onl_nsc; DevBuf<float> onl_lb; DevBuf<unsigned> onl_u;
+    DevBuf<float4> onl_xsc;
+    DevBuf<unsigned char> onl_dirty;         // [N] nodes whose sigmaMap row is written at the end of the chunk
 
     // pinned staging of vsom_set_state's host arrays
-    void *st_pinned = nullptr; size_t st_pinned_cap = 0;
-    void *out_pinned = nullptr;     // [8192] u64: vsom_get_last_bmu of short chunks
-    // device scratch of the distance queries (vsom_distances / _row / _raw): grow-only
-    void *q_scratch = nullptr; size_t q_scratch_cap = 0;
+    PinnedBuf<float> st_pinned;
+    PinnedBuf<u64> out_pinned;      // [8192]: vsom_get_last_bmu of short chunks
+    // device scratch of the distance queries (vsom_distances / _row / _raw): grow-only, bytes
+    DevBuf<unsigned char> q_scratch;
 
     // timing
     uint32_t timing = 0;            // bit (1u << VSOM_T_*): that kernel group is timed with HIP events
@@ -199,18 +197,21 @@ struct vsom_ctx {
 // error plumbing -----------------------------------------------------------------------------
 void vsom_set_error(const std::string &msg);
 int vsom_fail(int code, const std::string &msg);
-// (an allocation that does not fit is VSOM_ERR_NOMEM and leaves the context usable: every allocation site drops the old
-// buffer and its capacity first, and the runtime's last-error slot is cleared so that the next hipGetLastError() of a
-// launch sequence does not report it again)
-#define VSOM_HIP_CHECK(expr)                                                             \
+// (an allocation that does not fit is VSOM_ERR_NOMEM and leaves the context usable: every buffer is grown through
+// vsom_buf.hpp, which drops the old buffer first and leaves a set whole or absent, and the runtime's last-error slot is
+// cleared so that the next hipGetLastError() of a launch sequence does not report it again)
+#define VSOM_HIP_CHECK_AS(expr, what)                                                    \
     do {                                                                                 \
         hipError_t _e = (expr);                                                          \
         if (_e != hipSuccess) {                                                          \
             (void)hipGetLastError();                                                     \
             return vsom_fail(_e == hipErrorOutOfMemory ? VSOM_ERR_NOMEM : VSOM_ERR_HIP,  \
-                             std::string(#expr) + ": " + hipGetErrorString(_e));         \
+                             std::string(what) + ": " + hipGetErrorString(_e));          \
         }                                                                                \
     } while (0)
+#define VSOM_HIP_CHECK(expr) VSOM_HIP_CHECK_AS(expr, #expr)
+// vsom_grow / vsom_grow_set: the message names the allocation
+#define VSOM_ALLOC_CHECK(expr) VSOM_HIP_CHECK_AS(expr, "hipMalloc in " #expr)
 
 struct TimerScope {
     vsom_ctx *c; int which; vsom_ctx::Ev ev; bool on;

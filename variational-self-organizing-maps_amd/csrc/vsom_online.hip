@@ -1125,20 +1125,15 @@ static int ensure_lutd_host(vsom_ctx *c, double sigma, const double **out, int *
 {
     const uint32_t lw = c->W, lh = c->H;
     const size_t need = (size_t)lw * lh;
-    if (need > c->lutd_host_cap) {
+    if (2 * need > c->lutd_host.cap) {
         VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (c->lutd_host)
-            VSOM_HIP_CHECK(hipHostFree(c->lutd_host));
-        c->lutd_host = nullptr;
-        c->lutd_host_cap = 0;
-        VSOM_HIP_CHECK(hipHostMalloc(&c->lutd_host, 2 * need * sizeof(double)));
-        c->lutd_host_cap = need;
+        VSOM_ALLOC_CHECK(vsom_grow(c->lutd_host, 2 * need, c->stream));
         c->lutd_host_sigma[0] = c->lutd_host_sigma[1] = -1.0;
         c->lutd_ev_valid[0] = c->lutd_ev_valid[1] = false;
     }
     for (int k = 0; k < 2; ++k)
         if (c->lutd_host_sigma[k] == sigma) {
-            *out = c->lutd_host + (size_t)k * c->lutd_host_cap;
+            *out = c->lutd_host.p + (size_t)k * need;
             *slot_out = k;
             return VSOM_OK;
         }
@@ -1147,7 +1142,7 @@ static int ensure_lutd_host(vsom_ctx *c, double sigma, const double **out, int *
         VSOM_HIP_CHECK(hipEventCreateWithFlags(&c->lutd_ev[k], hipEventDisableTiming));
     if (c->lutd_ev_valid[k])
         VSOM_HIP_CHECK(hipEventSynchronize(c->lutd_ev[k]));      // its last reader (two tables ago): long done
-    double *host = c->lutd_host + (size_t)k * c->lutd_host_cap;
+    double *host = c->lutd_host.p + (size_t)k * need;
     c->lutd_host_sigma[k] = -1.0;
     for (uint32_t dy = 0; dy < lh; ++dy)
         for (uint32_t dx = 0; dx < lw; ++dx)
@@ -1171,29 +1166,21 @@ static int ensure_lutd(vsom_ctx *c, double sigma, const double **out, int *lutw)
     const uint32_t lw = c->W, lh = c->H;
     const size_t need = (size_t)lw * lh;
     *lutw = (int)lw;
-    if (c->lutd && c->lutd_sigma == sigma) {
-        *out = c->lutd;
+    if (c->lutd.p && c->lutd_sigma == sigma) {
+        *out = c->lutd.p;
         return VSOM_OK;
     }
-    if (need > c->lutd_cap) {
-        VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (c->lutd)
-            VSOM_HIP_CHECK(hipFree(c->lutd));
-        c->lutd = nullptr;
-        c->lutd_cap = 0;
-        VSOM_HIP_CHECK(hipMalloc(&c->lutd, need * sizeof(double)));
-        c->lutd_cap = need;
-    }
+    VSOM_ALLOC_CHECK(vsom_grow(c->lutd, need, c->stream, VSOM_BUF_SYNC));
     const double *host = nullptr;
     int k = 0;
     if (int rc = ensure_lutd_host(c, sigma, &host, &k))
         return rc;
     c->lutd_sigma = -1.0;
-    VSOM_HIP_CHECK(hipMemcpyAsync(c->lutd, host, need * sizeof(double), hipMemcpyHostToDevice, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(c->lutd.p, host, need * sizeof(double), hipMemcpyHostToDevice, c->stream));
     if (int rc = lutd_host_used(c, k))
         return rc;
     c->lutd_sigma = sigma;
-    *out = c->lutd;
+    *out = c->lutd.p;
     return VSOM_OK;
 }
 
@@ -1217,12 +1204,12 @@ static int enqueue_single(vsom_ctx *c, const float *xs, const float *xp, const f
     a.d.xa = clr ? xp : xs;
     a.d.xb = clr ? yp : xs;
     a.d.ldx = 0;
-    a.d.ma = c->map;
-    a.d.mb = clr ? c->map + c->part_pitch : c->map;
+    a.d.ma = c->map.p;
+    a.d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
     a.d.ldm = (int)c->pitch;
     a.d.L = (int)c->part_len;
-    a.state = c->onl_state;
-    a.fstate = fstate ? fstate : c->onl_f;   // {distance of the BMU, MSE running sum}
+    a.state = c->onl_state.p;
+    a.fstate = fstate ? fstate : c->onl_f.p;   // {distance of the BMU, MSE running sum}
     a.N = (int)c->N;
     a.W = (int)c->W;
     a.H = (int)c->H;
@@ -1232,21 +1219,21 @@ static int enqueue_single(vsom_ctx *c, const float *xs, const float *xp, const f
         u64 *lb_prev = chunk && lastbmu_dev ? lastbmu_dev - 1 : nullptr;
         if (chunk) {
             if (clr)
-                hipLaunchKernelGGL((online_scan_kernel<true, true>), grid, dim3(256), 0, c->stream, a, c->hits, lb_prev, fB, add_hit);
+                hipLaunchKernelGGL((online_scan_kernel<true, true>), grid, dim3(256), 0, c->stream, a, c->hits.p, lb_prev, fB, add_hit);
             else
-                hipLaunchKernelGGL((online_scan_kernel<false, true>), grid, dim3(256), 0, c->stream, a, c->hits, lb_prev, fB, add_hit);
+                hipLaunchKernelGGL((online_scan_kernel<false, true>), grid, dim3(256), 0, c->stream, a, c->hits.p, lb_prev, fB, add_hit);
         } else {
             if (clr)
-                hipLaunchKernelGGL((online_scan_kernel<true, false>), grid, dim3(256), 0, c->stream, a, c->hits, lb_prev, fB, add_hit);
+                hipLaunchKernelGGL((online_scan_kernel<true, false>), grid, dim3(256), 0, c->stream, a, c->hits.p, lb_prev, fB, add_hit);
             else
-                hipLaunchKernelGGL((online_scan_kernel<false, false>), grid, dim3(256), 0, c->stream, a, c->hits, lb_prev, fB, add_hit);
+                hipLaunchKernelGGL((online_scan_kernel<false, false>), grid, dim3(256), 0, c->stream, a, c->hits.p, lb_prev, fB, add_hit);
         }
     } else {
         // sigma <= 1: one fused launch (local search + <=6x6 window + post)
 #define LAUNCH_SMALL(KIND)                                                                                  \
     hipLaunchKernelGGL(online_small_kernel<KIND>, dim3(1), dim3(1024), 0, c->stream, a, xs, xp, yp, lutd, lutw, \
                        (int)c->D, (int)c->part_len, (int)c->part_pitch, (int)c->pitch, eta, sigma, decay_fn, \
-                       c->map, c->S, c->sigma, c->weight, c->hits, lastbmu_dev, residual_dev, fB, add_hit)
+                       c->map.p, c->S.p, c->sigma.p, c->weight.p, c->hits.p, lastbmu_dev, residual_dev, fB, add_hit)
         if (c->transform == VSOM_CLR)
             LAUNCH_SMALL(VSOM_CLR);
         else if (c->transform == VSOM_MEDIAN)
@@ -1267,7 +1254,7 @@ static int enqueue_single(vsom_ctx *c, const float *xs, const float *xp, const f
 #define LAUNCH_WIN(KIND, POST)                                                                              \
     hipLaunchKernelGGL((online_window_kernel<KIND, POST>), wgrid, dim3(bs), 0, c->stream, a, xs, xp, yp, lutd, lutw, \
                        (int)c->D, (int)c->part_len, (int)c->part_pitch, (int)c->pitch, eta, sigma, decay_fn, \
-                       c->map, c->S, c->sigma, c->weight, c->hits, lastbmu_dev, residual_dev, fB, add_hit)
+                       c->map.p, c->S.p, c->sigma.p, c->weight.p, c->hits.p, lastbmu_dev, residual_dev, fB, add_hit)
     if (chunk) {
         if (c->transform == VSOM_CLR)
             LAUNCH_WIN(VSOM_CLR, false);
@@ -1297,21 +1284,21 @@ static int enqueue_chunk_tail(vsom_ctx *c, const float *pxs, const float *pxp, c
     a.d.xa = a.pxa = clr ? pxp : pxs;
     a.d.xb = a.pxb = clr ? pyp : pxs;
     a.d.ldx = 0;
-    a.d.ma = c->map;
-    a.d.mb = clr ? c->map + c->part_pitch : c->map;
+    a.d.ma = c->map.p;
+    a.d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
     a.d.ldm = (int)c->pitch;
     a.d.L = (int)c->part_len;
-    a.state = c->onl_state;
-    a.fstate = c->onl_f;
+    a.state = c->onl_state.p;
+    a.fstate = c->onl_f.p;
     a.N = (int)c->N;
     a.W = (int)c->W;
     a.H = (int)c->H;
     a.do_scan = 0;
     a.do_post = 1;
     if (clr)
-        hipLaunchKernelGGL((online_scan_kernel<true, true>), dim3(1), dim3(256), 0, c->stream, a, c->hits, lastbmu_last, fB, 1);
+        hipLaunchKernelGGL((online_scan_kernel<true, true>), dim3(1), dim3(256), 0, c->stream, a, c->hits.p, lastbmu_last, fB, 1);
     else
-        hipLaunchKernelGGL((online_scan_kernel<false, true>), dim3(1), dim3(256), 0, c->stream, a, c->hits, lastbmu_last, fB, 1);
+        hipLaunchKernelGGL((online_scan_kernel<false, true>), dim3(1), dim3(256), 0, c->stream, a, c->hits.p, lastbmu_last, fB, 1);
     return VSOM_OK;
 }
 
@@ -1322,17 +1309,13 @@ static int stage_single(vsom_ctx *c, const float *v_host, bool copy = true)
 {
     const size_t xs_n = c->xpitch, pp = c->part_pitch;
     const size_t nstage = xs_n + 2 * pp;
-    if (!c->v_dev) {
-        // device: [xs | xp | yp | residual(pp) | tail(16)]; tail = {u64 lastBMU/bmu, float dist, float mse}
-        VSOM_HIP_CHECK(hipMalloc(&c->v_dev, (xs_n + 3 * pp + 16) * sizeof(float)));
-        VSOM_HIP_CHECK(hipMalloc(&c->res_dev, 64));
-        // pinned: the same rows, 32 floats of tails, and an image of onl_state for vsom_find_bmu
-        VSOM_HIP_CHECK(hipHostMalloc(&c->v_pinned, (xs_n + 3 * pp + 32) * sizeof(float) + ONL_STATE_BYTES));
-    } else {
-        // the previous call's copy out of the pinned buffer has been waited for (every caller
-        // synchronises the stream before returning)
-    }
-    float *host = c->v_pinned;
+    // device: [xs | xp | yp | residual(pp) | tail(16)]; tail = {u64 lastBMU/bmu, float dist, float mse}
+    // pinned: the same rows, 32 floats of tails, and an image of onl_state for vsom_find_bmu
+    // (once allocated, the previous call's copy out of the pinned buffer has been waited for: every caller synchronises
+    // the stream before returning)
+    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, 0, {vsom_member(c->v_dev, xs_n + 3 * pp + 16), vsom_member(c->res_dev, 16),
+                                                vsom_member(c->v_pinned, xs_n + 3 * pp + 32 + ONL_STATE_BYTES / sizeof(float))}));
+    float *host = c->v_pinned.p;
     std::fill(host, host + nstage, 0.f);
     for (uint32_t d = 0; d < c->J; ++d)
         host[d] = v_host[d];
@@ -1346,7 +1329,7 @@ static int stage_single(vsom_ctx *c, const float *v_host, bool copy = true)
             }
     }
     if (copy)
-        VSOM_HIP_CHECK(hipMemcpyAsync(c->v_dev, host, nstage * sizeof(float), hipMemcpyHostToDevice, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(c->v_dev.p, host, nstage * sizeof(float), hipMemcpyHostToDevice, c->stream));
     return VSOM_OK;
 }
 
@@ -1578,7 +1561,7 @@ static bool online_tiny_applies(const vsom_ctx *c, double sigma)
 static void fill_chunk_tiny_args(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw,
                                  int first_chunk, u64 *lastbmu_host, OnlTinyArgs &a)
 {
-    a.X = c->Xs;
+    a.X = c->Xs.p;
     a.ldx = (int)c->xpitch;
     a.B = (int)c->B;
     a.N = (int)c->N;
@@ -1586,13 +1569,13 @@ static void fill_chunk_tiny_args(vsom_ctx *c, double eta, double sigma, int deca
     a.H = (int)c->H;
     a.D = (int)c->part_len;
     a.pitch = (int)c->pitch;
-    a.map = c->map;
-    a.Smap = c->S;
-    a.sigmap = c->sigma;
-    a.weight = c->weight;
-    a.hits = c->hits;
-    a.lastbmu = c->lastbmu;
-    a.fstate = c->onl_f;
+    a.map = c->map.p;
+    a.Smap = c->S.p;
+    a.sigmap = c->sigma.p;
+    a.weight = c->weight.p;
+    a.hits = c->hits.p;
+    a.lastbmu = c->lastbmu.p;
+    a.fstate = c->onl_f.p;
     a.lutd = lutd;
     a.lutw = lutw;
     a.eta = eta;
@@ -1600,7 +1583,7 @@ static void fill_chunk_tiny_args(vsom_ctx *c, double eta, double sigma, int deca
     a.decay_fn = decay_fn;
     a.fB = (float)c->B;
     a.keep_mse = first_chunk ? 0 : 1;
-    a.mse_out = c->mse;
+    a.mse_out = c->mse.p;
     a.lastbmu_host = lastbmu_host;
 }
 
@@ -1673,9 +1656,8 @@ int vsom_onl_tiny_prepare(vsom_ctx *c, double eta, double sigma, int decay_fn, i
         return rc;
     u64 *lbh = nullptr;
     if (want_lb) {                                               // (B <= 4096 here)
-        if (!c->out_pinned)
-            VSOM_HIP_CHECK(hipHostMalloc(&c->out_pinned, 8192 * sizeof(uint64_t)));
-        lbh = static_cast<u64 *>(c->out_pinned);
+        VSOM_ALLOC_CHECK(vsom_grow(c->out_pinned, 8192, c->stream));
+        lbh = c->out_pinned.p;
     }
     OnlTinyArgs a;
     fill_chunk_tiny_args(c, eta, sigma, decay_fn, lutd, (int)c->W, first_chunk, lbh, a);
@@ -1833,32 +1815,27 @@ static bool onl_i8_applies(const vsom_ctx *c, double sigma)
 static int onl_i8_ensure(vsom_ctx *c, OnlI8 *o)
 {
     const uint32_t ipitch = (c->part_len + 15) / 16 * 16;    // rows of 16-byte pieces
-    if (!c->onl_img) {
-        VSOM_HIP_CHECK(hipMalloc(&c->onl_img, (size_t)c->N * ipitch));
-        VSOM_HIP_CHECK(hipMalloc(&c->onl_nsc, (size_t)c->N * sizeof(float4)));
-        VSOM_HIP_CHECK(hipMalloc(&c->onl_lb, (((size_t)c->N + ONL_REF_NODES - 1) / ONL_REF_NODES) * ONL_REF_NODES * sizeof(float)));
-        VSOM_HIP_CHECK(hipMalloc(&c->onl_u, ONL_U_BYTES + 64));
-        VSOM_HIP_CHECK(hipMemsetAsync((char *)c->onl_u + ONL_U_BYTES, 0, 64, c->stream));
-        VSOM_HIP_CHECK(hipMalloc(&c->onl_dirty, (size_t)c->N));
-        VSOM_HIP_CHECK(hipMemsetAsync(c->onl_dirty, 0, (size_t)c->N, c->stream));
+    if (!c->onl_img.p) {
+        // (onl_u: the slots + 64 bytes of stats, which start at zero)
+        VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, 0,
+                                     {vsom_member(c->onl_img, (size_t)c->N * ipitch), vsom_member(c->onl_nsc, c->N),
+                                      vsom_member(c->onl_lb, ((size_t)c->N + ONL_REF_NODES - 1) / ONL_REF_NODES * ONL_REF_NODES),
+                                      vsom_member(c->onl_u, (ONL_U_BYTES + 64) / sizeof(unsigned)),
+                                      vsom_member(c->onl_dirty, c->N, VSOM_BUF_ZERO)}));
+        VSOM_HIP_CHECK(hipMemsetAsync((char *)c->onl_u.p + ONL_U_BYTES, 0, 64, c->stream));
     }
-    if (c->onl_xsc_cap < c->B) {
+    if (c->onl_xsc.cap < c->B) {
         VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (c->onl_xsc)
-            (void)hipFree(c->onl_xsc);
-        c->onl_xsc = nullptr;
-        c->onl_xsc_cap = 0;
-        VSOM_HIP_CHECK(hipMalloc(&c->onl_xsc, c->Bcap * sizeof(float4)));
-        c->onl_xsc_cap = c->Bcap;
+        VSOM_ALLOC_CHECK(vsom_grow(c->onl_xsc, c->Bcap, c->stream));
     }
     const double u = 5.9604644775390625e-8;
-    o->img = c->onl_img;
-    o->nsc = (float4 *)c->onl_nsc;
-    o->lb = c->onl_lb;
-    o->uslots = c->onl_u;
-    o->stats = reinterpret_cast<u64 *>((char *)c->onl_u + ONL_U_BYTES);
-    o->xsc = (const float4 *)c->onl_xsc;
-    o->dirty = c->onl_dirty;
+    o->img = c->onl_img.p;
+    o->nsc = c->onl_nsc.p;
+    o->lb = c->onl_lb.p;
+    o->uslots = c->onl_u.p;
+    o->stats = reinterpret_cast<u64 *>((char *)c->onl_u.p + ONL_U_BYTES);
+    o->xsc = c->onl_xsc.p;
+    o->dirty = c->onl_dirty.p;
     o->ipitch = (int)ipitch;
     o->ni = (int)((ipitch + 127) / 128);
     o->nref = (int)((c->N + ONL_REF_NODES - 1) / ONL_REF_NODES);
@@ -1876,17 +1853,17 @@ static int enqueue_chunk_i8(vsom_ctx *c, double eta, double sigma, int decay_fn,
         return rc;
     const int N = (int)c->N, D = (int)c->part_len;
     const size_t B = c->B;
-    hipLaunchKernelGGL(onl_digit_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, c->map, (int)c->pitch, D, N, o);
-    hipLaunchKernelGGL(onl_prep_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, c->Xs, (int)c->xpitch, D, (int)B,
-                       (float4 *)c->onl_xsc);
-    hipLaunchKernelGGL(onl_uslots_init_kernel, dim3(1), dim3(128), 0, c->stream, c->onl_u);
+    hipLaunchKernelGGL(onl_digit_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, c->map.p, (int)c->pitch, D, N, o);
+    hipLaunchKernelGGL(onl_prep_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, D, (int)B,
+                       c->onl_xsc.p);
+    hipLaunchKernelGGL(onl_uslots_init_kernel, dim3(1), dim3(128), 0, c->stream, c->onl_u.p);
     OnlineArgs a;
     a.d.ldx = 0;
-    a.d.ma = a.d.mb = c->map;
+    a.d.ma = a.d.mb = c->map.p;
     a.d.ldm = (int)c->pitch;
     a.d.L = D;
-    a.state = c->onl_state;
-    a.fstate = c->onl_f;
+    a.state = c->onl_state.p;
+    a.fstate = c->onl_f.p;
     a.N = N;
     a.W = (int)c->W;
     a.H = (int)c->H;
@@ -1927,7 +1904,7 @@ static int enqueue_chunk_i8(vsom_ctx *c, double eta, double sigma, int decay_fn,
         const unsigned grid = (win ? (unsigned)(f.nwin_x * f.nwin_y) : 0u) + (scan ? nscan : 0u);
 #define ONL_FUSED2(KIND, ST, P)                                                                                            \
     hipLaunchKernelGGL((onl_fused_kernel<KIND, ST, P>), dim3(grid), dim3(256), 0, c->stream, f, o, lutd, lutw, D, (int)c->pitch, eta, \
-                       sigma, decay_fn, c->map, c->S, c->sigma, c->weight)
+                       sigma, decay_fn, c->map.p, c->S.p, c->sigma.p, c->weight.p)
 #define ONL_FUSED(KIND, ST) do { if (passes == 2) ONL_FUSED2(KIND, ST, 2); else ONL_FUSED2(KIND, ST, 1); } while (0)
         if (med) {
             if (store_kind == 2) ONL_FUSED(VSOM_MEDIAN, 2); else if (store_kind == 1) ONL_FUSED(VSOM_MEDIAN, 1); else ONL_FUSED(VSOM_MEDIAN, 0);
@@ -1944,22 +1921,22 @@ static int enqueue_chunk_i8(vsom_ctx *c, double eta, double sigma, int decay_fn,
         r.pxa = r.pxb = xs_prev;
         r.do_post = xs_prev != nullptr;
         const dim3 grid((do_refine ? nref : 0u) + 1u);
-        hipLaunchKernelGGL(onl_refine_kernel, grid, dim3(256), 0, c->stream, r, o, do_refine ? 1 : 0, c->hits, lb_prev, fB, 1);
+        hipLaunchKernelGGL(onl_refine_kernel, grid, dim3(256), 0, c->stream, r, o, do_refine ? 1 : 0, c->hits.p, lb_prev, fB, 1);
     };
     // scores of sample 0 (no window yet): the launch works on "sample -1" of parity 1
-    fused(c->Xs, 1, c->Xs, 0, false, true);
+    fused(c->Xs.p, 1, c->Xs.p, 0, false, true);
     const float *prev = nullptr;
     for (size_t j = 0; j < B; ++j) {
-        const float *xs = c->Xs + j * c->xpitch;
-        refine(xs, (int)(j & 1), prev, j ? c->lastbmu + (j - 1) : nullptr, true);
+        const float *xs = c->Xs.p + j * c->xpitch;
+        refine(xs, (int)(j & 1), prev, j ? c->lastbmu.p + (j - 1) : nullptr, true);
         const bool more = j + 1 < B;
         fused(xs, (int)(j & 1), more ? xs + c->xpitch : xs, more ? j + 1 : j, true, more);
         prev = xs;
     }
     // finish the last sample: its post step runs as the "previous sample" of a launch of the other parity
-    refine(prev, (int)(B & 1), prev, c->lastbmu + (B - 1), false);
-    hipLaunchKernelGGL(onl_sigma_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, c->S, c->sigma, c->weight,
-                       c->onl_dirty, D, (int)c->pitch, N);
+    refine(prev, (int)(B & 1), prev, c->lastbmu.p + (B - 1), false);
+    hipLaunchKernelGGL(onl_sigma_kernel, dim3((unsigned)((N + 3) / 4)), dim3(256), 0, c->stream, c->S.p, c->sigma.p, c->weight.p,
+                       c->onl_dirty.p, D, (int)c->pitch, N);
     return VSOM_OK;
 }
 
@@ -1983,22 +1960,22 @@ int vsom_find_bmu(vsom_ctx *c, const float *v_host, uint64_t *bmu_out, float *di
         return rc;
     const bool clr = c->transform == VSOM_CLR;
     const size_t xs_n = c->xpitch, pp = c->part_pitch;
-    float *xs = c->v_dev, *xp = c->v_dev + xs_n, *yp = xp + pp;
+    float *xs = c->v_dev.p, *xp = c->v_dev.p + xs_n, *yp = xp + pp;
     OnlineArgs a;
     a.par = 0;
     a.d.xa = clr ? xp : xs;
     a.d.xb = clr ? yp : xs;
     a.d.ldx = 0;
-    a.d.ma = c->map;
-    a.d.mb = clr ? c->map + c->part_pitch : c->map;
+    a.d.ma = c->map.p;
+    a.d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
     a.d.ldm = (int)c->pitch;
     a.d.L = (int)c->part_len;
-    a.state = c->onl_state;
-    a.fstate = c->onl_f;
+    a.state = c->onl_state.p;
+    a.fstate = c->onl_f.p;
     a.N = (int)c->N;
     a.W = (int)c->W;
     a.H = (int)c->H;
-    VSOM_HIP_CHECK(hipMemsetAsync(c->onl_state, 0xFF, ONL_SLOTS * 16 * sizeof(u64), c->stream));   // arm the keys of parity 0
+    VSOM_HIP_CHECK(hipMemsetAsync(c->onl_state.p, 0xFF, ONL_SLOTS * 16 * sizeof(u64), c->stream));   // arm the keys of parity 0
     dim3 grid((unsigned)(((size_t)c->N * 8 + 255) / 256));
     a.pxa = a.pxb = nullptr;
     a.do_scan = 1;
@@ -2008,8 +1985,8 @@ int vsom_find_bmu(vsom_ctx *c, const float *v_host, uint64_t *bmu_out, float *di
     else
         hipLaunchKernelGGL((online_scan_kernel<false, false>), grid, dim3(256), 0, c->stream, a, (u64 *)nullptr, (u64 *)nullptr, 1.f, 0);
     VSOM_HIP_CHECK(hipGetLastError());
-    u64 *st = reinterpret_cast<u64 *>(c->v_pinned + xs_n + 3 * pp + 32);   // image of onl_state (8-byte aligned: pitches are multiples of 32 floats)
-    VSOM_HIP_CHECK(hipMemcpyAsync(st, c->onl_state, ONL_STATE_BYTES, hipMemcpyDeviceToHost, c->stream));
+    u64 *st = reinterpret_cast<u64 *>(c->v_pinned.p + xs_n + 3 * pp + 32);   // image of onl_state (8-byte aligned: pitches are multiples of 32 floats)
+    VSOM_HIP_CHECK(hipMemcpyAsync(st, c->onl_state.p, ONL_STATE_BYTES, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     uint64_t key = ~0ull;             // minimum over the key slots of parity 0
     for (int sl = 0; sl < ONL_SLOTS; ++sl)
@@ -2049,14 +2026,14 @@ static int single_query(vsom_ctx *c, const float *v_host, uint64_t node, int whi
         return rc;
     const bool clr = c->transform == VSOM_CLR;
     const size_t xs_n = c->xpitch, pp = c->part_pitch;
-    float *rows = zero_copy_in ? c->v_pinned : c->v_dev;
-    float *xs = rows, *xp = rows + xs_n, *yp = xp + pp, *tail = c->v_pinned + xs_n + 3 * pp;
+    float *rows = zero_copy_in ? c->v_pinned.p : c->v_dev.p;
+    float *xs = rows, *xp = rows + xs_n, *yp = xp + pp, *tail = c->v_pinned.p + xs_n + 3 * pp;
     DistArgs d;
     d.xa = clr ? xp : xs;
     d.xb = clr ? yp : xs;
     d.ldx = 0;
-    d.ma = c->map;
-    d.mb = clr ? c->map + c->part_pitch : c->map;
+    d.ma = c->map.p;
+    d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
     d.ldm = (int)c->pitch;
     d.L = (int)c->part_len;
     u64 *oi = reinterpret_cast<u64 *>(tail);
@@ -2098,47 +2075,38 @@ static int single_scan(vsom_ctx *c, const float *v_host, int use_hits, uint64_t 
         return rc;
     float *all_dev = nullptr;
     if (all_out_host) {
-        if ((size_t)c->N * 4 > c->q_scratch_cap) {
-            VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-            if (c->q_scratch)
-                (void)hipFree(c->q_scratch);
-            c->q_scratch = nullptr;
-            c->q_scratch_cap = 0;
-            const size_t cap = ((size_t)c->N * 4 + 4095) / 4096 * 4096;
-            VSOM_HIP_CHECK(hipMalloc(&c->q_scratch, cap));
-            c->q_scratch_cap = cap;
-        }
-        all_dev = reinterpret_cast<float *>(c->q_scratch);
+        VSOM_ALLOC_CHECK(vsom_grow(c->q_scratch, ((size_t)c->N * 4 + 4095) / 4096 * 4096, c->stream, VSOM_BUF_SYNC));
+        all_dev = reinterpret_cast<float *>(c->q_scratch.p);
     }
     const bool clr = c->transform == VSOM_CLR;
     const size_t xs_n = c->xpitch, pp = c->part_pitch;
-    float *xs = c->v_dev, *xp = c->v_dev + xs_n, *yp = xp + pp;
+    float *xs = c->v_dev.p, *xp = c->v_dev.p + xs_n, *yp = xp + pp;
     OnlineArgs a;
     a.par = 0;
     a.d.xa = clr ? xp : xs;
     a.d.xb = clr ? yp : xs;
     a.d.ldx = 0;
-    a.d.ma = c->map;
-    a.d.mb = clr ? c->map + c->part_pitch : c->map;
+    a.d.ma = c->map.p;
+    a.d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
     a.d.ldm = (int)c->pitch;
     a.d.L = (int)c->part_len;
-    a.state = c->onl_state;
-    a.fstate = c->onl_f;
+    a.state = c->onl_state.p;
+    a.fstate = c->onl_f.p;
     a.N = (int)c->N;
     a.W = (int)c->W;
     a.H = (int)c->H;
     a.pxa = a.pxb = nullptr;
     a.do_scan = 1;
     a.do_post = 0;
-    VSOM_HIP_CHECK(hipMemsetAsync(c->onl_state, 0xFF, ONL_SLOTS * 16 * sizeof(u64), c->stream));   // arm the keys of parity 0
+    VSOM_HIP_CHECK(hipMemsetAsync(c->onl_state.p, 0xFF, ONL_SLOTS * 16 * sizeof(u64), c->stream));   // arm the keys of parity 0
     dim3 grid((unsigned)(((size_t)c->N * 8 + 255) / 256));
     if (clr)
-        hipLaunchKernelGGL(single_scan_kernel<true>, grid, dim3(256), 0, c->stream, a, c->hits, (u64)min_hits, use_hits, all_dev);
+        hipLaunchKernelGGL(single_scan_kernel<true>, grid, dim3(256), 0, c->stream, a, c->hits.p, (u64)min_hits, use_hits, all_dev);
     else
-        hipLaunchKernelGGL(single_scan_kernel<false>, grid, dim3(256), 0, c->stream, a, c->hits, (u64)min_hits, use_hits, all_dev);
+        hipLaunchKernelGGL(single_scan_kernel<false>, grid, dim3(256), 0, c->stream, a, c->hits.p, (u64)min_hits, use_hits, all_dev);
     VSOM_HIP_CHECK(hipGetLastError());
-    u64 *st = reinterpret_cast<u64 *>(c->v_pinned + xs_n + 3 * pp + 32);   // image of onl_state (vsom_find_bmu)
-    VSOM_HIP_CHECK(hipMemcpyAsync(st, c->onl_state, ONL_STATE_BYTES, hipMemcpyDeviceToHost, c->stream));
+    u64 *st = reinterpret_cast<u64 *>(c->v_pinned.p + xs_n + 3 * pp + 32);   // image of onl_state (vsom_find_bmu)
+    VSOM_HIP_CHECK(hipMemcpyAsync(st, c->onl_state.p, ONL_STATE_BYTES, hipMemcpyDeviceToHost, c->stream));
     if (all_out_host)
         VSOM_HIP_CHECK(hipMemcpyAsync(all_out_host, all_dev, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -2188,7 +2156,7 @@ int vsom_find_local_bmu(vsom_ctx *c, const float *v_host, uint64_t last_bmu, uin
 }
 
 // lb_host != NULL: the caller wants lastBMU back in this call -- *lb_in_pinned = the one-launch kernel has stored it into
-// c->out_pinned itself (else the caller fetches it with vsom_get_last_bmu)
+// c->out_pinned.p itself (else the caller fetches it with vsom_get_last_bmu)
 static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk, float *mse_out,
                                    bool want_lb, bool *lb_in_pinned)
 {
@@ -2202,7 +2170,7 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
         if (rc || !mse_out)
             return rc;
         VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        *mse_out = *static_cast<volatile float *>(c->mse);
+        *mse_out = *static_cast<volatile float *>(c->mse.p);
         return VSOM_OK;
     }
     VSOM_HIP_CHECK(hipSetDevice(c->device));
@@ -2227,14 +2195,13 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
     {
         TimerScope ts(c, VSOM_T_ONLINE);
         if (!tiny)                            // (the one-launch chunk starts the running MSE itself and uses no key slots)
-            hipLaunchKernelGGL(online_init_kernel, dim3(1), dim3(1), 0, c->stream, c->onl_state, c->onl_f,
+            hipLaunchKernelGGL(online_init_kernel, dim3(1), dim3(1), 0, c->stream, c->onl_state.p, c->onl_f.p,
                                first_chunk ? 0 : 1);
         if (tiny) {
             u64 *lbh = nullptr;
             if (want_lb && c->B <= 8192) {
-                if (!c->out_pinned)
-                    VSOM_HIP_CHECK(hipHostMalloc(&c->out_pinned, 8192 * sizeof(uint64_t)));
-                lbh = static_cast<u64 *>(c->out_pinned);
+                VSOM_ALLOC_CHECK(vsom_grow(c->out_pinned, 8192, c->stream));
+                lbh = c->out_pinned.p;
             }
             if ((rc = enqueue_chunk_tiny(c, eta, sigma, decay_fn, lutd, lutw, first_chunk, lbh)) || (rc = lutd_host_used(c, lslot)))
                 return rc;
@@ -2248,10 +2215,10 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
         const bool pipelined = sigma > 1;     // the search launch of sample j finishes sample j-1 (online_scan_kernel)
         const float *pxs = nullptr, *pxp = nullptr, *pyp = nullptr;
         for (size_t j = 0; j < c->B; ++j) {
-            const float *xs = c->Xs + j * c->xpitch;
-            const float *xp = c->XP ? c->XP + j * c->part_pitch : nullptr;
-            const float *yp = c->YP ? c->YP + j * c->part_pitch : nullptr;
-            rc = enqueue_single(c, xs, xp, yp, eta, sigma, decay_fn, c->lastbmu + j, nullptr, fB, 1,
+            const float *xs = c->Xs.p + j * c->xpitch;
+            const float *xp = c->XP.p ? c->XP.p + j * c->part_pitch : nullptr;
+            const float *yp = c->YP.p ? c->YP.p + j * c->part_pitch : nullptr;
+            rc = enqueue_single(c, xs, xp, yp, eta, sigma, decay_fn, c->lastbmu.p + j, nullptr, fB, 1,
                                 lutd, lutw, (int)(j & 1), nullptr, pipelined, pxs, pxp, pyp);
             if (rc)
                 return rc;
@@ -2260,16 +2227,16 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
             pyp = yp;
         }
         if (pipelined && c->B > 0 &&
-            (rc = enqueue_chunk_tail(c, pxs, pxp, pyp, c->lastbmu + (c->B - 1), fB, (int)((c->B - 1) & 1))))
+            (rc = enqueue_chunk_tail(c, pxs, pxp, pyp, c->lastbmu.p + (c->B - 1), fB, (int)((c->B - 1) & 1))))
             return rc;
         }
         VSOM_HIP_CHECK(hipGetLastError());
     }
     // vsom_get_mse reports the chunk's MSE for callers that passed mse_out = NULL (asynchronous use)
     if (!tiny)
-        VSOM_HIP_CHECK(hipMemcpyAsync(c->mse, c->onl_f + 1, 4, hipMemcpyDefault, c->stream));   // (c->mse: pinned host memory)
+        VSOM_HIP_CHECK(hipMemcpyAsync(c->mse.p, c->onl_f.p + 1, 4, hipMemcpyDefault, c->stream));   // (c->mse.p: pinned host memory)
     if (mse_out) {
-        VSOM_HIP_CHECK(hipMemcpyAsync(mse_out, c->onl_f + 1, 4, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(mse_out, c->onl_f.p + 1, 4, hipMemcpyDeviceToHost, c->stream));
         VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     }
     return VSOM_OK;
@@ -2294,10 +2261,10 @@ int vsom_train_online_chunk_fetch(vsom_ctx *c, double eta, double sigma, int dec
     } else {
         VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
         if (lastbmu_out)
-            std::memcpy(lastbmu_out, c->out_pinned, c->B * sizeof(uint64_t));
+            std::memcpy(lastbmu_out, c->out_pinned.p, c->B * sizeof(uint64_t));
     }
     if (mse_out)
-        *mse_out = *static_cast<volatile float *>(c->mse);  // pinned host memory; written in stream order before the wait above
+        *mse_out = *static_cast<volatile float *>(c->mse.p);  // pinned host memory; written in stream order before the wait above
     return VSOM_OK;
 }
 
@@ -2307,9 +2274,9 @@ int vsom_get_online_search_stats(vsom_ctx *c, uint64_t *out, int reset)
         return vsom_fail(VSOM_ERR_INVALID, "null argument");
     VSOM_HIP_CHECK(hipSetDevice(c->device));
     out[0] = out[1] = out[2] = out[3] = 0;
-    if (!c->onl_u)
+    if (!c->onl_u.p)
         return VSOM_OK;
-    u64 *st = reinterpret_cast<u64 *>((char *)c->onl_u + ONL_U_BYTES);
+    u64 *st = reinterpret_cast<u64 *>((char *)c->onl_u.p + ONL_U_BYTES);
     VSOM_HIP_CHECK(hipMemcpyAsync(out, st, 32, hipMemcpyDeviceToHost, c->stream));
     if (reset)
         VSOM_HIP_CHECK(hipMemsetAsync(st, 0, 32, c->stream));
@@ -2350,8 +2317,8 @@ int vsom_train_single(vsom_ctx *c, const float *v_host, double eta, double sigma
     // The sample's rows are copied into HBM (thousands of wavefronts read them); lastBMU in, residual + {bmu, distance, mse}
     // out go straight through the pinned buffer, which the device addresses: written / read by single wavefronts of the
     // step's kernels -- one copy and one synchronisation per call (three copies before: 36 us per call)
-    float *xs = c->v_dev, *xp = c->v_dev + xs_n, *yp = xp + pp;
-    float *res = c->v_pinned + xs_n + 2 * pp, *tail = res + pp;
+    float *xs = c->v_dev.p, *xp = c->v_dev.p + xs_n, *yp = xp + pp;
+    float *res = c->v_pinned.p + xs_n + 2 * pp, *tail = res + pp;
     u64 *lb = reinterpret_cast<u64 *>(tail);
     float *pout = res;
     std::memcpy(tail, last_bmu, 8);
@@ -2359,7 +2326,7 @@ int vsom_train_single(vsom_ctx *c, const float *v_host, double eta, double sigma
     tail[3] = 0.f;
     {
         TimerScope ts(c, VSOM_T_ONLINE);
-        hipLaunchKernelGGL(online_init_kernel, dim3(1), dim3(1), 0, c->stream, c->onl_state, c->onl_f, 1);
+        hipLaunchKernelGGL(online_init_kernel, dim3(1), dim3(1), 0, c->stream, c->onl_state.p, c->onl_f.p, 1);
         rc = enqueue_single(c, xs, xp, yp, eta, sigma, decay_fn, lb, res, 1.0f, 0, lutd, lutw, 0, tail + 2);
         if (rc)
             return rc;

@@ -753,6 +753,14 @@ int sl_i8_plan(vsom_ctx *c, size_t s0, size_t s1);
 
 static int launch_bmu_full_shortlist_clr(vsom_ctx *c, size_t s0, size_t s1);
 
+// node norms; two alternating sets of {16 words + 3 x 32 line-sized slots} (4096 words each) + the chunk's data-kind
+// flag; the pinned host feedback
+static hipError_t sl_ensure_scalars(vsom_ctx *c)
+{
+    return vsom_grow_set(c->stream, 0, {vsom_member(c->sl_nrm, c->N), vsom_member(c->sl_scal, 3 * 4096, VSOM_BUF_ZERO),
+                                        vsom_member(c->sl_fb, 16, VSOM_BUF_ZERO)});
+}
+
 int launch_bmu_full_shortlist(vsom_ctx *c, size_t s0, size_t s1)
 {
     if (s1 <= s0)
@@ -770,40 +778,15 @@ int launch_bmu_full_shortlist(vsom_ctx *c, size_t s0, size_t s1)
     const bool gless = plan != 0;
     const size_t ldg = ((size_t)c->N + 127) / 128 * 128;
     const size_t need = gless ? 0 : nrows * ldg;
-    if (need > c->sl_cap) {
-        if (c->sl_G)
-            VSOM_HIP_CHECK(hipFree(c->sl_G));
-        c->sl_G = nullptr;
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_G, need * sizeof(float)));
-        c->sl_cap = need;
-    }
     const size_t ntm = gless ? (((size_t)c->N + 31) / 32) * 2 : (((size_t)c->N + GT - 1) / GT) * 2;
-    if (nrows * ntm > c->sl_tmin_cap) {
-        if (c->sl_tmin)
-            VSOM_HIP_CHECK(hipFree(c->sl_tmin));
-        c->sl_tmin = nullptr;
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_tmin, nrows * ntm * sizeof(float)));
-        c->sl_tmin_cap = nrows * ntm;
-    }
-    if (nrows > c->sl_list_cap) {
-        if (c->sl_list)
-            VSOM_HIP_CHECK(hipFree(c->sl_list));
-        c->sl_list = nullptr;
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_list, nrows * sizeof(int)));
-        c->sl_list_cap = nrows;
-    }
-    if (!c->sl_nrm) {
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_nrm, (size_t)c->N * sizeof(float)));
-        // two alternating sets of {16 words + 3 x 32 line-sized slots} (4096 words each) + the chunk's data-kind flag
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_scal, 3 * 16384));
-        VSOM_HIP_CHECK(hipMemsetAsync(c->sl_scal, 0, 3 * 16384, c->stream));
-        VSOM_HIP_CHECK(hipHostMalloc(&c->sl_fb, 64));
-        std::memset(c->sl_fb, 0, 64);
-    }
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_G, need, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_tmin, nrows * ntm, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_list, nrows, c->stream));
+    VSOM_ALLOC_CHECK(sl_ensure_scalars(c));
     // scal: [0] max nrm bits, [1] non-finite flag, [2] redo count, [4] redo samples, [5] candidates
-    unsigned *scal = c->sl_scal + 4096 * c->sl_par, *scal_next = c->sl_scal + 4096 * (c->sl_par ^ 1);
+    unsigned *scal = c->sl_scal.p + 4096 * c->sl_par, *scal_next = c->sl_scal.p + 4096 * (c->sl_par ^ 1);
     c->sl_par ^= 1;
-    unsigned *xflag = c->sl_scal + 8192;
+    unsigned *xflag = c->sl_scal.p + 8192;
     dim3 grid((unsigned)((c->N + GT - 1) / GT), (unsigned)((nrows + GT - 1) / GT));
     const double u = 5.9604644775390625e-08;   // 2^-24
     const double g2 = ((double)c->D / 8.0 + 10.0) * u;
@@ -813,27 +796,27 @@ int launch_bmu_full_shortlist(vsom_ctx *c, size_t s0, size_t s1)
             return rc;
     } else {
     hipLaunchKernelGGL(sl_norm_kernel, dim3((unsigned)(((size_t)c->N * 16 + 255) / 256)), dim3(256), 0, c->stream,
-                       c->map, (int)c->pitch, (int)c->part_pitch, (int)c->N, c->sl_nrm, scal);
+                       c->map.p, (int)c->pitch, (int)c->part_pitch, (int)c->N, c->sl_nrm.p, scal);
     if (c->cc_valid) {
         // columns that are zero in every row of the chunk add exactly 0 to every <x, M>: contract over the live
         // ones (norms, bound and refinement keep the whole rows)
         int rc = vsom_cc_gather_map(c);
         if (rc)
             return rc;
-        hipLaunchKernelGGL(sl_gemm_kernel, grid, dim3(256), 0, c->stream, c->Xc, (int)c->cpitch, (int)s0, (int)s1,
-                           c->Mc, (int)c->cpitch, (int)c->N, (int)c->cpitch, c->sl_nrm, c->sl_G, (int)ldg, c->sl_tmin, (int)ntm,
-                           (const unsigned *)c->cc_meta, (const unsigned *)nullptr);
+        hipLaunchKernelGGL(sl_gemm_kernel, grid, dim3(256), 0, c->stream, c->Xc.p, (int)c->cpitch, (int)s0, (int)s1,
+                           c->Mc.p, (int)c->cpitch, (int)c->N, (int)c->cpitch, c->sl_nrm.p, c->sl_G.p, (int)ldg, c->sl_tmin.p, (int)ntm,
+                           (const unsigned *)c->cc_meta.p, (const unsigned *)nullptr);
     } else
-    hipLaunchKernelGGL(sl_gemm_kernel, grid, dim3(256), 0, c->stream, c->Xs, (int)c->xpitch, (int)s0, (int)s1,
-                       c->map, (int)c->pitch, (int)c->N, (int)c->xpitch, c->sl_nrm, c->sl_G, (int)ldg, c->sl_tmin, (int)ntm,
+    hipLaunchKernelGGL(sl_gemm_kernel, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, (int)s0, (int)s1,
+                       c->map.p, (int)c->pitch, (int)c->N, (int)c->xpitch, c->sl_nrm.p, c->sl_G.p, (int)ldg, c->sl_tmin.p, (int)ntm,
                        (const unsigned *)nullptr, (const unsigned *)nullptr);
     }
     DistArgs a;
-    a.xa = c->Xs;
-    a.xb = c->Xs;
+    a.xa = c->Xs.p;
+    a.xb = c->Xs.p;
     a.ldx = (int)c->xpitch;
-    a.ma = c->map;
-    a.mb = c->map;
+    a.ma = c->map.p;
+    a.mb = c->map.p;
     a.ldm = (int)c->pitch;
     a.L = (int)c->part_len;
     const double K = (double)c->xpitch;
@@ -842,29 +825,29 @@ int launch_bmu_full_shortlist(vsom_ctx *c, size_t s0, size_t s1)
     // (vsom_sl_i8.hip; 3.1u with the fp64 epilogue, 5.1u with the two-rounding fp32 one of the uint8 kind)
     if (gless && c->D <= 64)
         hipLaunchKernelGGL(sl_pick_kernel<1>, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)c->N,
-                           (int)c->D, c->sl_tmin, (int)ntm, scal, (float)(5.5 * u), (float)(2.1 * g2), c->lastbmu, c->sqres, scal + 2,
-                           c->sl_list, scal + 4, 64u, (const float *)c->sl_l1, (unsigned)c->Bcap, 2.0f, (const unsigned *)xflag,
-                           (const float *)c->sl_nrm);
+                           (int)c->D, c->sl_tmin.p, (int)ntm, scal, (float)(5.5 * u), (float)(2.1 * g2), c->lastbmu.p, c->sqres.p, scal + 2,
+                           c->sl_list.p, scal + 4, 64u, (const float *)c->sl_l1.p, (unsigned)c->Bcap, 2.0f, (const unsigned *)xflag,
+                           (const float *)c->sl_nrm.p);
     else if (gless && nrows < 4096)     // few samples (a rank's share of a chunk): a workgroup per sample (0.109 -> 0.089 ms at 512)
         hipLaunchKernelGGL(sl_pick_kernel<4>, dim3((unsigned)nrows), dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)c->N,
-                           (int)c->D, c->sl_tmin, (int)ntm, scal, (float)(5.5 * u), (float)(2.1 * g2), c->lastbmu, c->sqres, scal + 2,
-                           c->sl_list, scal + 4, 64u, (const float *)c->sl_l1, (unsigned)c->Bcap, 2.0f, (const unsigned *)xflag,
-                           (const float *)c->sl_nrm);
+                           (int)c->D, c->sl_tmin.p, (int)ntm, scal, (float)(5.5 * u), (float)(2.1 * g2), c->lastbmu.p, c->sqres.p, scal + 2,
+                           c->sl_list.p, scal + 4, 64u, (const float *)c->sl_l1.p, (unsigned)c->Bcap, 2.0f, (const unsigned *)xflag,
+                           (const float *)c->sl_nrm.p);
     else if (gless)
         hipLaunchKernelGGL(sl_pick_kernel<2>, dim3((unsigned)((nrows + 1) / 2)), dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)c->N,
-                           (int)c->D, c->sl_tmin, (int)ntm, scal, (float)(5.5 * u), (float)(2.1 * g2), c->lastbmu, c->sqres, scal + 2,
-                           c->sl_list, scal + 4, 64u, (const float *)c->sl_l1, (unsigned)c->Bcap, 2.0f, (const unsigned *)xflag,
-                           (const float *)c->sl_nrm);
+                           (int)c->D, c->sl_tmin.p, (int)ntm, scal, (float)(5.5 * u), (float)(2.1 * g2), c->lastbmu.p, c->sqres.p, scal + 2,
+                           c->sl_list.p, scal + 4, 64u, (const float *)c->sl_l1.p, (unsigned)c->Bcap, 2.0f, (const unsigned *)xflag,
+                           (const float *)c->sl_nrm.p);
     else
     hipLaunchKernelGGL(sl_select_kernel<false>, dim3((unsigned)nrows), dim3(256), 0, c->stream, a, (int)s0,
-                       (int)s1, (int)c->N, (int)c->D, c->sl_G, (int)ldg, c->sl_tmin, (int)ntm, scal, (float)(i8 ? 5.5 * u : 2.0 * g1),
-                       (float)(2.1 * g2), c->lastbmu, c->sqres, scal + 2, c->sl_list, scal + 4, (const float *)nullptr, 0, 0, 0.f,
-                       (unsigned)SL_CMAX, (const float *)c->sl_l1, (unsigned)c->Bcap, i8 ? 2.0f : 0.f, (const unsigned *)xflag,
-                       (const float *)nullptr, (const float *)nullptr, (const float *)c->sl_nrm);
+                       (int)s1, (int)c->N, (int)c->D, c->sl_G.p, (int)ldg, c->sl_tmin.p, (int)ntm, scal, (float)(i8 ? 5.5 * u : 2.0 * g1),
+                       (float)(2.1 * g2), c->lastbmu.p, c->sqres.p, scal + 2, c->sl_list.p, scal + 4, (const float *)nullptr, 0, 0, 0.f,
+                       (unsigned)SL_CMAX, (const float *)c->sl_l1.p, (unsigned)c->Bcap, i8 ? 2.0f : 0.f, (const unsigned *)xflag,
+                       (const float *)nullptr, (const float *)nullptr, (const float *)c->sl_nrm.p);
     VSOM_HIP_CHECK(hipGetLastError());
     // exact-order redo of the listed samples (device-side count; its workgroups walk the list) + the feedback words
-    const SlFeedback fb = {scal, c->sl_fb, (unsigned)nrows, i8 ? (const unsigned *)xflag : (const unsigned *)nullptr, scal_next};
-    return launch_bmu_full_exact_list(c, s0, s1, c->sl_list, scal + 2, &fb);
+    const SlFeedback fb = {scal, c->sl_fb.p, (unsigned)nrows, i8 ? (const unsigned *)xflag : (const unsigned *)nullptr, scal_next};
+    return launch_bmu_full_exact_list(c, s0, s1, c->sl_list.p, scal + 2, &fb);
 }
 
 // ==============================================================================================
@@ -1025,54 +1008,30 @@ static int launch_bmu_full_shortlist_clr(vsom_ctx *c, size_t s0, size_t s1)
     const uint32_t P32 = (P + 31) / 32 * 32, Kp = P32 + (3 * J + 31) / 32 * 32;
     const size_t ldg = ((size_t)c->N + 127) / 128 * 128;
     const size_t ntm = (((size_t)c->N + GT - 1) / GT) * 2;
-    auto grow = [](void **buf, size_t *cap, size_t need_bytes) -> int {
-        if (need_bytes <= *cap)
-            return VSOM_OK;
-        if (*buf)
-            VSOM_HIP_CHECK(hipFree(*buf));
-        *buf = nullptr;
-        *cap = 0;
-        VSOM_HIP_CHECK(hipMalloc(buf, need_bytes));
-        *cap = need_bytes;
-        return VSOM_OK;
-    };
-    int rc;
-    size_t capG = c->sl_cap * sizeof(float), capT = c->sl_tmin_cap * sizeof(float), capL = c->sl_list_cap * sizeof(int);
-    if ((rc = grow((void **)&c->sl_G, &capG, nrows * ldg * sizeof(float))) ||
-        (rc = grow((void **)&c->sl_tmin, &capT, nrows * ntm * sizeof(float))) ||
-        (rc = grow((void **)&c->sl_list, &capL, nrows * sizeof(int))) ||
-        (rc = grow((void **)&c->sl_fs, &c->sl_fs_cap, c->B * (size_t)Kp * sizeof(float))) ||
-        (rc = grow((void **)&c->sl_fm, &c->sl_fm_cap, (size_t)c->N * Kp * sizeof(float))))
-        return rc;
-    c->sl_cap = capG / sizeof(float);
-    c->sl_tmin_cap = capT / sizeof(float);
-    c->sl_list_cap = capL / sizeof(int);
-    if (!c->sl_nrm) {
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_nrm, (size_t)c->N * sizeof(float)));
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_scal, 3 * 16384));
-        VSOM_HIP_CHECK(hipMemsetAsync(c->sl_scal, 0, 3 * 16384, c->stream));
-        VSOM_HIP_CHECK(hipHostMalloc(&c->sl_fb, 64));
-        std::memset(c->sl_fb, 0, 64);
-    }
-    if (!c->sl_a2)
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_a2, (size_t)c->N * sizeof(float)));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_G, nrows * ldg, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_tmin, nrows * ntm, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_list, nrows, c->stream));
+    VSOM_ALLOC_CHECK(sl_ensure_scalars(c));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_fs, c->B * (size_t)Kp, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_fm, (size_t)c->N * Kp, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_a2, c->N, c->stream));
     // scal: [0] max nB bits, [1] non-finite flag, [2] redo count, [3] max A^2 bits, [4] redo samples
-    unsigned *scal = c->sl_scal + 4096 * c->sl_par, *scal_next = c->sl_scal + 4096 * (c->sl_par ^ 1);
+    unsigned *scal = c->sl_scal.p + 4096 * c->sl_par, *scal_next = c->sl_scal.p + 4096 * (c->sl_par ^ 1);
     c->sl_par ^= 1;
-    hipLaunchKernelGGL(clr_node_feat_kernel, dim3((unsigned)c->N), dim3(256), 0, c->stream, c->map, (int)c->pitch,
-                       (int)c->part_pitch, (int)P, (int)J, c->sl_fm, (int)Kp, (int)P32, (int)c->N, c->sl_nrm, c->sl_a2, scal);
-    hipLaunchKernelGGL(clr_sample_feat_kernel, dim3((unsigned)nrows), dim3(256), 0, c->stream, c->XP, c->YP, (int)c->part_pitch,
-                       (int)P, c->Xs, (int)c->xpitch, (int)J, c->sl_fs, (int)Kp, (int)P32, (int)s0, (int)s1, (const unsigned *)scal);
+    hipLaunchKernelGGL(clr_node_feat_kernel, dim3((unsigned)c->N), dim3(256), 0, c->stream, c->map.p, (int)c->pitch,
+                       (int)c->part_pitch, (int)P, (int)J, c->sl_fm.p, (int)Kp, (int)P32, (int)c->N, c->sl_nrm.p, c->sl_a2.p, scal);
+    hipLaunchKernelGGL(clr_sample_feat_kernel, dim3((unsigned)nrows), dim3(256), 0, c->stream, c->XP.p, c->YP.p, (int)c->part_pitch,
+                       (int)P, c->Xs.p, (int)c->xpitch, (int)J, c->sl_fs.p, (int)Kp, (int)P32, (int)s0, (int)s1, (const unsigned *)scal);
     dim3 grid((unsigned)((c->N + GT - 1) / GT), (unsigned)((nrows + GT - 1) / GT));
-    hipLaunchKernelGGL(sl_gemm_kernel, grid, dim3(256), 0, c->stream, c->sl_fs, (int)Kp, (int)s0, (int)s1, c->sl_fm, (int)Kp,
-                       (int)c->N, (int)Kp, c->sl_nrm, c->sl_G, (int)ldg, c->sl_tmin, (int)ntm, (const unsigned *)nullptr,
+    hipLaunchKernelGGL(sl_gemm_kernel, grid, dim3(256), 0, c->stream, c->sl_fs.p, (int)Kp, (int)s0, (int)s1, c->sl_fm.p, (int)Kp,
+                       (int)c->N, (int)Kp, c->sl_nrm.p, c->sl_G.p, (int)ldg, c->sl_tmin.p, (int)ntm, (const unsigned *)nullptr,
                        (const unsigned *)scal);
     DistArgs a;
-    a.xa = c->XP;
-    a.xb = c->YP;
+    a.xa = c->XP.p;
+    a.xb = c->YP.p;
     a.ldx = (int)c->part_pitch;
-    a.ma = c->map;
-    a.mb = c->map + c->part_pitch;
+    a.ma = c->map.p;
+    a.mb = c->map.p + c->part_pitch;
     a.ldm = (int)c->pitch;
     a.L = (int)P;
     const double u = 5.9604644775390625e-08;   // 2^-24
@@ -1081,11 +1040,11 @@ static int launch_bmu_full_shortlist_clr(vsom_ctx *c, size_t s0, size_t s1)
     const double g2 = ((double)P / 8.0 + 10.0) * u, e1 = 6.1 * 1.7320508075688773 * u;
     const size_t xy_bytes = (size_t)2 * c->part_pitch * sizeof(float);   // + 8.3 KB static: fits the default 64 KB up to J = 120
     hipLaunchKernelGGL(sl_select_kernel<true>, dim3((unsigned)nrows), dim3(256), xy_bytes, c->stream, a, (int)s0, (int)s1, (int)c->N,
-                       (int)c->D, c->sl_G, (int)ldg, c->sl_tmin, (int)ntm, scal, (float)(1.0001 * ga), (float)(1.0001 * g2),
-                       c->lastbmu, c->sqres, scal + 2, c->sl_list, scal + 4, c->Xs, (int)c->xpitch, (int)J, (float)(1.0001 * e1), 128u,
-                       (const float *)nullptr, 0u, 0.f, (const unsigned *)nullptr, (const float *)c->sl_nrm, (const float *)c->sl_a2,
+                       (int)c->D, c->sl_G.p, (int)ldg, c->sl_tmin.p, (int)ntm, scal, (float)(1.0001 * ga), (float)(1.0001 * g2),
+                       c->lastbmu.p, c->sqres.p, scal + 2, c->sl_list.p, scal + 4, c->Xs.p, (int)c->xpitch, (int)J, (float)(1.0001 * e1), 128u,
+                       (const float *)nullptr, 0u, 0.f, (const unsigned *)nullptr, (const float *)c->sl_nrm.p, (const float *)c->sl_a2.p,
                        (const float *)nullptr);
     VSOM_HIP_CHECK(hipGetLastError());
-    const SlFeedback fb = {scal, c->sl_fb, (unsigned)nrows, (const unsigned *)nullptr, scal_next};
-    return launch_bmu_full_exact_list(c, s0, s1, c->sl_list, scal + 2, &fb);
+    const SlFeedback fb = {scal, c->sl_fb.p, (unsigned)nrows, (const unsigned *)nullptr, scal_next};
+    return launch_bmu_full_exact_list(c, s0, s1, c->sl_list.p, scal + 2, &fb);
 }

@@ -1199,33 +1199,18 @@ __global__ __launch_bounds__(256, 2) void sl_k64_kernel(const signed char *__res
 // buffers of the int8 images: model planes for N rows, sample planes for Bcap rows of kp8 bytes
 static int sl_i8_ensure(vsom_ctx *c, uint32_t kp8)
 {
-    if (!c->sl_q || c->sl_kp8 != kp8) {
-        if (c->sl_q) {
-            VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-            VSOM_HIP_CHECK(hipFree(c->sl_q));
-            VSOM_HIP_CHECK(hipFree(c->sl_qscale));
-            VSOM_HIP_CHECK(hipFree(c->sl_qcorr));
-            VSOM_HIP_CHECK(hipFree(c->sl_qfast));
-        }
-        c->sl_q = nullptr;
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_q, (size_t)3 * c->N * kp8));
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_qscale, (size_t)c->N * sizeof(double)));
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_qcorr, (size_t)c->N * sizeof(double)));
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_qfast, (size_t)c->N * sizeof(int4)));
+    // (the model planes are rebuilt when kp8 changes, and the sample planes with them)
+    const bool rekey = !c->sl_q.p || c->sl_kp8 != kp8;
+    if (rekey) {
+        VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_SYNC | VSOM_BUF_REBUILD,
+                                     {vsom_member(c->sl_q, (size_t)3 * c->N * kp8), vsom_member(c->sl_qscale, c->N),
+                                      vsom_member(c->sl_qcorr, c->N), vsom_member(c->sl_qfast, c->N)}));
         c->sl_kp8 = kp8;
-        c->xi_valid = false;
-        c->sl_xi_cap = 0;
     }
-    if ((size_t)c->Bcap * kp8 > c->sl_xi_cap) {
-        if (c->sl_xi) {
-            VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-            VSOM_HIP_CHECK(hipFree(c->sl_xi));
-            VSOM_HIP_CHECK(hipFree(c->sl_l1));
-        }
-        c->sl_xi = nullptr;
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_xi, (size_t)4 * c->Bcap * kp8));             // [0] x - 128, [1..3] digits
-        VSOM_HIP_CHECK(hipMalloc(&c->sl_l1, (size_t)5 * c->Bcap * sizeof(float)));   // |x|_1, t_s, l1eff_s, e_s, |x|^2 (rows of <= 64 values)
-        c->sl_xi_cap = (size_t)c->Bcap * kp8;
+    if (rekey || (size_t)4 * c->Bcap * kp8 > c->sl_xi.cap) {
+        // sl_xi: [0] x - 128, [1..3] digits; sl_l1: |x|_1, t_s, l1eff_s, e_s, |x|^2 (rows of <= 64 values)
+        VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_SYNC | VSOM_BUF_REBUILD,
+                                     {vsom_member(c->sl_xi, (size_t)4 * c->Bcap * kp8), vsom_member(c->sl_l1, (size_t)5 * c->Bcap)}));
         c->xi_valid = false;
     }
     return VSOM_OK;
@@ -1236,15 +1221,15 @@ static int sl_i8_ensure(vsom_ctx *c, uint32_t kp8)
 int launch_sl_gather_quant(vsom_ctx *c, size_t B, hipStream_t stream, const int *idx, bool *xi_out)
 {
     const uint32_t kp8 = (c->cpitch + 63) / 64 * 64;
-    const bool xi = c->sl_xi && c->sl_kp8 == kp8 && (size_t)c->Bcap * kp8 <= c->sl_xi_cap && c->sl_scal;
+    const bool xi = c->sl_xi.p && c->sl_kp8 == kp8 && (size_t)4 * c->Bcap * kp8 <= c->sl_xi.cap && c->sl_scal.p;
     if (kp8 == 64)
-        hipLaunchKernelGGL(sl_quant_rows64_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, stream, c->Xs, (int)c->xpitch, c->Xc,
-                           (int)c->cpitch, idx, (int)B, xi ? c->sl_xi : (signed char *)nullptr, (size_t)c->Bcap * kp8,
-                           xi ? c->sl_l1 : (float *)nullptr, (size_t)c->Bcap, xi ? c->sl_scal + 8192 : (unsigned *)nullptr);
+        hipLaunchKernelGGL(sl_quant_rows64_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, stream, c->Xs.p, (int)c->xpitch, c->Xc.p,
+                           (int)c->cpitch, idx, (int)B, xi ? c->sl_xi.p : (signed char *)nullptr, (size_t)c->Bcap * kp8,
+                           xi ? c->sl_l1.p : (float *)nullptr, (size_t)c->Bcap, xi ? c->sl_scal.p + 8192 : (unsigned *)nullptr);
     else
-    hipLaunchKernelGGL(sl_quant_rows_kernel, dim3((unsigned)B), dim3(256), 0, stream, c->Xs, (int)c->xpitch, c->Xc,
-                       (int)c->cpitch, idx, (int)B, xi ? c->sl_xi : (signed char *)nullptr, (size_t)c->Bcap * kp8, (int)kp8,
-                       xi ? c->sl_l1 : (float *)nullptr, (size_t)c->Bcap, xi ? c->sl_scal + 8192 : (unsigned *)nullptr);
+    hipLaunchKernelGGL(sl_quant_rows_kernel, dim3((unsigned)B), dim3(256), 0, stream, c->Xs.p, (int)c->xpitch, c->Xc.p,
+                       (int)c->cpitch, idx, (int)B, xi ? c->sl_xi.p : (signed char *)nullptr, (size_t)c->Bcap * kp8, (int)kp8,
+                       xi ? c->sl_l1.p : (float *)nullptr, (size_t)c->Bcap, xi ? c->sl_scal.p + 8192 : (unsigned *)nullptr);
     VSOM_HIP_CHECK(hipGetLastError());
     *xi_out = xi;
     return VSOM_OK;
@@ -1295,40 +1280,40 @@ int launch_sl_i8(vsom_ctx *c, size_t s0, size_t s1, size_t ldg, size_t ntm, unsi
     if (!c->xi_valid) {      // once per staged chunk (the compaction's gather pass does it when the buffers exist)
         if (kp8 == 64)
             hipLaunchKernelGGL(sl_quant_rows64_kernel, dim3((unsigned)((c->B + 15) / 16)), dim3(256), 0, c->stream,
-                               compact ? c->Xc : c->Xs, (int)kmax, (float *)nullptr, (int)kmax, (const int *)nullptr, (int)c->B,
-                               c->sl_xi, xplane, c->sl_l1, (size_t)c->Bcap, xflag);
+                               compact ? c->Xc.p : c->Xs.p, (int)kmax, (float *)nullptr, (int)kmax, (const int *)nullptr, (int)c->B,
+                               c->sl_xi.p, xplane, c->sl_l1.p, (size_t)c->Bcap, xflag);
         else
-        hipLaunchKernelGGL(sl_quant_rows_kernel, dim3((unsigned)c->B), dim3(256), 0, c->stream, compact ? c->Xc : c->Xs, (int)kmax,
-                           (float *)nullptr, (int)kmax, (const int *)nullptr, (int)c->B, c->sl_xi, xplane, (int)kp8, c->sl_l1,
+        hipLaunchKernelGGL(sl_quant_rows_kernel, dim3((unsigned)c->B), dim3(256), 0, c->stream, compact ? c->Xc.p : c->Xs.p, (int)kmax,
+                           (float *)nullptr, (int)kmax, (const int *)nullptr, (int)c->B, c->sl_xi.p, xplane, (int)kp8, c->sl_l1.p,
                            (size_t)c->Bcap, xflag);
         c->xi_valid = true;
     }
-    const float *xscale = c->sl_l1 + c->Bcap;
-    const unsigned *kp_dev = compact ? (const unsigned *)c->cc_meta : nullptr;
+    const float *xscale = c->sl_l1.p + c->Bcap;
+    const unsigned *kp_dev = compact ? (const unsigned *)c->cc_meta.p : nullptr;
     if (kp8 == 64 && c->part_pitch <= 64)
-        hipLaunchKernelGGL(sl_prepare64_kernel, dim3((unsigned)((c->N + 15) / 16)), dim3(256), 0, c->stream, c->map, (int)c->pitch,
-                           (int)c->part_pitch, (int)c->N, compact ? (const int *)c->cc_idx : (const int *)nullptr, (int)kmax, kp_dev,
-                           c->sl_q, c->sl_nrm, c->sl_qscale, c->sl_qcorr, (int4 *)c->sl_qfast, scal, xflag);
+        hipLaunchKernelGGL(sl_prepare64_kernel, dim3((unsigned)((c->N + 15) / 16)), dim3(256), 0, c->stream, c->map.p, (int)c->pitch,
+                           (int)c->part_pitch, (int)c->N, compact ? (const int *)c->cc_idx.p : (const int *)nullptr, (int)kmax, kp_dev,
+                           c->sl_q.p, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, c->sl_qfast.p, scal, xflag);
     else
-    hipLaunchKernelGGL(sl_prepare_i8_kernel, dim3((unsigned)((c->N + 3) / 4)), dim3(256), 0, c->stream, c->map, (int)c->pitch,
-                       (int)c->part_pitch, (int)c->N, compact ? (const int *)c->cc_idx : (const int *)nullptr, (int)kmax, kp_dev,
-                       (int)kp8, c->sl_q, c->sl_nrm, c->sl_qscale, c->sl_qcorr, (int4 *)c->sl_qfast, scal, xflag);
+    hipLaunchKernelGGL(sl_prepare_i8_kernel, dim3((unsigned)((c->N + 3) / 4)), dim3(256), 0, c->stream, c->map.p, (int)c->pitch,
+                       (int)c->part_pitch, (int)c->N, compact ? (const int *)c->cc_idx.p : (const int *)nullptr, (int)kmax, kp_dev,
+                       (int)kp8, c->sl_q.p, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, c->sl_qfast.p, scal, xflag);
     // the fp32 two-fma epilogue of the uint8 kind needs |A| < 2^24: K <= 960 contracted columns (sl_i8_value_fast)
-    const int4 *qfast = kp8 <= 960 ? (const int4 *)c->sl_qfast : (const int4 *)nullptr;
+    const int4 *qfast = kp8 <= 960 ? c->sl_qfast.p : (const int4 *)nullptr;
     if (gless) {             // K <= 64: tile minima only (ntm = 16-node tiles), the refinement is sl_pick_kernel
         if (kp8 != 64)
             return VSOM_ERR_INVALID;
         dim3 grid((unsigned)((c->N + K64_NB * 32 - 1) / (K64_NB * 32)), (unsigned)((s1 - s0 + 128 * K64_SB - 1) / (128 * K64_SB)));
-        hipLaunchKernelGGL(sl_k64_kernel, grid, dim3(256), 0, c->stream, c->sl_xi, xplane, (int)s0, (int)s1, c->sl_q, (int)c->N,
-                           c->sl_nrm, (const int4 *)c->sl_qfast, xscale, c->sl_tmin, (int)ntm, (const unsigned *)xflag, scal);
+        hipLaunchKernelGGL(sl_k64_kernel, grid, dim3(256), 0, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1, c->sl_q.p, (int)c->N,
+                           c->sl_nrm.p, c->sl_qfast.p, xscale, c->sl_tmin.p, (int)ntm, (const unsigned *)xflag, scal);
         VSOM_HIP_CHECK(hipGetLastError());
         return VSOM_OK;
     }
     if (plan == 2) {         // the ring kernel without G (ntm = 16-node tiles)
         dim3 grid((unsigned)((c->N + RT_N - 1) / RT_N), (unsigned)((s1 - s0 + RT_S - 1) / RT_S));
-        hipLaunchKernelGGL(sl_gemm_i8_ring_gless_kernel, grid, dim3(512), RING_BYTES, c->stream, c->sl_xi, xplane, (int)s0, (int)s1,
-                           c->sl_q, (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm, xscale, c->sl_tmin, (int)ntm,
-                           (const unsigned *)xflag, (const int4 *)c->sl_qfast, scal);
+        hipLaunchKernelGGL(sl_gemm_i8_ring_gless_kernel, grid, dim3(512), RING_BYTES, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1,
+                           c->sl_q.p, (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm.p, xscale, c->sl_tmin.p, (int)ntm,
+                           (const unsigned *)xflag, c->sl_qfast.p, scal);
         VSOM_HIP_CHECK(hipGetLastError());
         return VSOM_OK;
     }
@@ -1345,18 +1330,18 @@ int launch_sl_i8(vsom_ctx *c, size_t s0, size_t s1, size_t ldg, size_t ntm, unsi
     }
     if (ring_ok) {
         dim3 grid((unsigned)(ntm / 2), (unsigned)((s1 - s0 + RT_S - 1) / RT_S));   // ntm = 2 ceil(N / 128) 64-node tiles
-        hipLaunchKernelGGL(sl_gemm_i8_ring_kernel, grid, dim3(512), RING_BYTES, c->stream, c->sl_xi, xplane, (int)s0, (int)s1,
-                           c->sl_q, (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm, c->sl_qscale, c->sl_qcorr, xscale, c->sl_G,
-                           (int)ldg, c->sl_tmin, (int)ntm, (const unsigned *)xflag, qfast, scal);
+        hipLaunchKernelGGL(sl_gemm_i8_ring_kernel, grid, dim3(512), RING_BYTES, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1,
+                           c->sl_q.p, (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, xscale, c->sl_G.p,
+                           (int)ldg, c->sl_tmin.p, (int)ntm, (const unsigned *)xflag, qfast, scal);
     } else {
         constexpr int MI = 2;
         dim3 grid((unsigned)ntm, (unsigned)((s1 - s0 + 64 * MI - 1) / (64 * MI)));   // ntm 64-node tiles (the last may lie past N: minima +inf)
-        hipLaunchKernelGGL((sl_gemm_i8_kernel<MI, 1>), grid, dim3(256), 0, c->stream, c->sl_xi, xplane, (int)s0, (int)s1, c->sl_q,
-                           (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm, c->sl_qscale, c->sl_qcorr, xscale, c->sl_G, (int)ldg,
-                           c->sl_tmin, (int)ntm, (const unsigned *)xflag, qfast, scal);
-        hipLaunchKernelGGL((sl_gemm_i8_kernel<MI, 3>), grid, dim3(256), 0, c->stream, c->sl_xi, xplane, (int)s0, (int)s1, c->sl_q,
-                           (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm, c->sl_qscale, c->sl_qcorr, xscale, c->sl_G, (int)ldg,
-                           c->sl_tmin, (int)ntm, (const unsigned *)xflag, qfast, scal);
+        hipLaunchKernelGGL((sl_gemm_i8_kernel<MI, 1>), grid, dim3(256), 0, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1, c->sl_q.p,
+                           (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, xscale, c->sl_G.p, (int)ldg,
+                           c->sl_tmin.p, (int)ntm, (const unsigned *)xflag, qfast, scal);
+        hipLaunchKernelGGL((sl_gemm_i8_kernel<MI, 3>), grid, dim3(256), 0, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1, c->sl_q.p,
+                           (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, xscale, c->sl_G.p, (int)ldg,
+                           c->sl_tmin.p, (int)ntm, (const unsigned *)xflag, qfast, scal);
     }
     VSOM_HIP_CHECK(hipGetLastError());
     return VSOM_OK;

@@ -59,21 +59,21 @@ bool vsom_tiny_applies(const vsom_ctx *c)
 static size_t fill_tiny_args(vsom_ctx *c, int is_first, TinyArgs &a)
 {
     const bool clr = c->transform == VSOM_CLR;
-    a.d.xa = clr ? c->XP : c->Xs;
-    a.d.xb = clr ? c->YP : c->Xs;
+    a.d.xa = clr ? c->XP.p : c->Xs.p;
+    a.d.xb = clr ? c->YP.p : c->Xs.p;
     a.d.ldx = (int)(clr ? c->part_pitch : c->xpitch);
-    a.d.ma = c->map;
-    a.d.mb = clr ? c->map + c->part_pitch : c->map;
+    a.d.ma = c->map.p;
+    a.d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
     a.d.ldm = (int)c->pitch;
     a.d.L = (int)c->part_len;
-    a.map = c->map;
-    a.sigma = c->sigma;
-    a.weight = c->weight;
-    a.hits = c->hits;
-    a.lastbmu = c->lastbmu;
-    a.sqres = c->sqres;
-    a.mse = c->mse;
-    a.lut = c->lut;
+    a.map = c->map.p;
+    a.sigma = c->sigma.p;
+    a.weight = c->weight.p;
+    a.hits = c->hits.p;
+    a.lastbmu = c->lastbmu.p;
+    a.sqres = c->sqres.p;
+    a.mse = c->mse.p;
+    a.lut = c->lut.p;
     a.lutw = (int)c->lut_w;
     a.N = (int)c->N;
     a.W = (int)c->W;

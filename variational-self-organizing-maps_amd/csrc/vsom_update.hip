@@ -523,23 +523,16 @@ double vsom_neighbourhood_weight(size_t cx, size_t cy, size_t bx, size_t by, dou
 
 int ensure_lut(vsom_ctx *c, double sigma)
 {
-    if (c->lut && c->lut_sigma == sigma)
+    if (c->lut.p && c->lut_sigma == sigma)
         return VSOM_OK;
     // largest y that SomIndex(som, idx) can produce is (N-W)/H (Q10)
     uint32_t ymax = c->N ? (c->N - c->W) / c->H : 0;
     uint32_t lh = ymax + 1, lw = c->W;
     size_t need = (size_t)lh * lw;
-    if (need > c->lut_cap) {
+    if (need > c->lut.cap) {
         VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-        if (c->lut)
-            VSOM_HIP_CHECK(hipFree(c->lut));
-        if (c->lut_host)
-            VSOM_HIP_CHECK(hipHostFree(c->lut_host));
-        c->lut = nullptr;
-        c->lut_host = nullptr;
-        VSOM_HIP_CHECK(hipMalloc(&c->lut, need * sizeof(float)));
-        VSOM_HIP_CHECK(hipHostMalloc(&c->lut_host, 2 * need * sizeof(float)));   // two halves used alternately
-        c->lut_cap = need;
+        // (lut_host: two halves used alternately)
+        VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, 0, {vsom_member(c->lut, need), vsom_member(c->lut_host, 2 * need)}));
         c->lut_ev_valid[0] = c->lut_ev_valid[1] = false;
     }
     // the table changes with every epoch's sigma: stage it through the half of the pinned buffer whose
@@ -550,11 +543,11 @@ int ensure_lut(vsom_ctx *c, double sigma)
         VSOM_HIP_CHECK(hipEventCreateWithFlags(&c->lut_ev[k], hipEventDisableTiming));
     if (c->lut_ev_valid[k])
         VSOM_HIP_CHECK(hipEventSynchronize(c->lut_ev[k]));
-    float *host = c->lut_host + (size_t)k * c->lut_cap;
+    float *host = c->lut_host.p + (size_t)k * c->lut.cap;
     for (uint32_t dy = 0; dy < lh; ++dy)
         for (uint32_t dx = 0; dx < lw; ++dx)
             host[(size_t)dy * lw + dx] = (float)vsom_neighbourhood_weight(dx, dy, 0, 0, sigma);
-    VSOM_HIP_CHECK(hipMemcpyAsync(c->lut, host, need * sizeof(float), hipMemcpyHostToDevice, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(c->lut.p, host, need * sizeof(float), hipMemcpyHostToDevice, c->stream));
     VSOM_HIP_CHECK(hipEventRecord(c->lut_ev[k], c->stream));
     c->lut_ev_valid[k] = true;
     c->lut_sigma = sigma;
@@ -605,9 +598,9 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
     if (c->B == 0) {
         TimerScope ts(c, VSOM_T_UPDATE);
         const size_t nloc = n1 - n0, tot = nloc * c->pitch;
-        hipLaunchKernelGGL(empty_epoch_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, c->map,
-                           c->sigma, c->weight, (int)c->pitch, (int)c->part_pitch, (int)c->part_len, (int)n0, (int)nloc);
-        hipLaunchKernelGGL(zero_weight_kernel, dim3((unsigned)((nloc + 255) / 256)), dim3(256), 0, c->stream, c->weight,
+        hipLaunchKernelGGL(empty_epoch_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, c->map.p,
+                           c->sigma.p, c->weight.p, (int)c->pitch, (int)c->part_pitch, (int)c->part_len, (int)n0, (int)nloc);
+        hipLaunchKernelGGL(zero_weight_kernel, dim3((unsigned)((nloc + 255) / 256)), dim3(256), 0, c->stream, c->weight.p,
                            (int)n0, (int)nloc);
         VSOM_HIP_CHECK(hipGetLastError());
         return vsom_join_aux(c);
@@ -620,15 +613,8 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
     // pair rows: ceil(B/2) + what the kernels' staging reads ahead (one block of 16 pair-rows) + slack
     const size_t prow = (c->B + 1) / 2 + 24;
     const size_t need = prow * ldn * 2;   // float2 elements
-    if (need > c->cw_cap) {
-        if (c->cw)
-            VSOM_HIP_CHECK(hipFree(c->cw));
-        c->cw = nullptr;
-        VSOM_HIP_CHECK(hipMalloc(&c->cw, need * sizeof(float2)));
-        // rows beyond B are staged (never used): keep them initialised
-        VSOM_HIP_CHECK(hipMemsetAsync(c->cw, 0, need * sizeof(float2), c->stream));
-        c->cw_cap = need;
-    }
+    // rows beyond B are staged (never used): keep them initialised
+    VSOM_ALLOC_CHECK(vsom_grow(c->cw, need, c->stream, VSOM_BUF_ZERO));
     {
         TimerScope ts(c, VSOM_T_CW);
         // role-split kernel, 16 nodes per workgroup; the table in LDS only while it is small: what counts is how
@@ -642,12 +628,12 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
         const void *fn = lds ? (const void *)cwp_kernel<nw, T, true> : (const void *)cwp_kernel<nw, T, false>;
         if (smem > 64 * 1024)
             VSOM_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        const u64 *bxy = c->lastbmu;
+        const u64 *bxy = c->lastbmu.p;
         int B = (int)c->B, in0 = (int)n0, in1 = (int)n1, iW = (int)c->W, iH = (int)c->H, lw = (int)c->lut_w,
             lh = (int)c->lut_h, ildn = (int)ldn;
-        const float *lut = c->lut;
-        float2 *cwp = c->cw;
-        float *wgt = c->weight;
+        const float *lut = c->lut.p;
+        float2 *cwp = c->cw.p;
+        float *wgt = c->weight.p;
         void *args[] = {&bxy, &B, &in0, &in1, &iW, &iH, &lut, &lw, &lh, &cwp, &ildn, &wgt};
         VSOM_HIP_CHECK(hipLaunchKernel(fn, dim3((unsigned)((nloc + nw - 1) / nw)), dim3(CWP_THREADS), args, smem, c->stream));
     }
@@ -663,10 +649,10 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
             constexpr unsigned RP = 8;
             const unsigned nsl = (c->part_len + RP - 1) / RP;
             UpdAsmArgs a;
-            a.xs = c->XP;
-            a.cw2 = c->cw;
-            a.map = c->map;
-            a.sbuf = c->sigma;
+            a.xs = c->XP.p;
+            a.cw2 = c->cw.p;
+            a.map = c->map.p;
+            a.sbuf = c->sigma.p;
             a.ldx_bytes = c->part_pitch * 4u;
             a.ldn_bytes = (unsigned)(ldn * 16u);
             a.B = (unsigned)c->B;
@@ -675,7 +661,7 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
             a.pitch_bytes = c->pitch * 4u;
             a.n0 = (unsigned)n0;
             a.ppitch_bytes = c->part_pitch * 4u;
-            a.yp = c->YP;
+            a.yp = c->YP.p;
             a.zq = nullptr;
             size_t sz = 72;
             void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
@@ -697,12 +683,12 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
                                : (sfma ? (const void *)update_chain3_kernel<false, 2, P> : (const void *)update_chain3_kernel<false, 0, P>)))
             const void *k3 = pl_log2 == 3 ? VSOM_K3(3) : pl_log2 == 4 ? VSOM_K3(4) : pl_log2 == 5 ? VSOM_K3(5) : VSOM_K3(6);
 #undef VSOM_K3
-            const float *xs_ = c->Xs;
-            const float2 *cw_ = c->cw;
+            const float *xs_ = c->Xs.p;
+            const float2 *cw_ = c->cw.p;
             int ildx = (int)c->xpitch, ildn = (int)ldn, iB = (int)c->B, in0 = (int)n0, inl = (int)nloc, iD = (int)c->D,
                 ipitch = (int)c->pitch;
-            float *map_ = c->map, *sg_ = c->sigma;
-            const float *wt_ = c->weight;
+            float *map_ = c->map.p, *sg_ = c->sigma.p;
+            const float *wt_ = c->weight.p;
             void *args[] = {&xs_, &ildx, &cw_, &ildn, &iB, &in0, &inl, &iD, &map_, &sg_, &ipitch, &wt_};
             VSOM_HIP_CHECK(hipLaunchKernel(k3, grid2, dim3(256), args, 0, c->stream));
         } else {
@@ -734,10 +720,10 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
             const unsigned cols = compact ? c->cpitch : c->pitch;
             const unsigned quads = compact ? c->cpitch / 4 : (c->D + 3) / 4;
             UpdAsmArgs a;
-            a.xs = c->Xq;
-            a.cw2 = c->cw;
-            a.map = compact ? c->Uc_map : c->map;
-            a.sbuf = compact ? c->Uc_S : c->sigma;
+            a.xs = c->Xq.p;
+            a.cw2 = c->cw.p;
+            a.map = compact ? c->Uc_map.p : c->map.p;
+            a.sbuf = compact ? c->Uc_S.p : c->sigma.p;
             a.ldx_bytes = c->xq_bpad * 16u;
             a.ldn_bytes = (unsigned)(ldn * 16u);
             a.B = (unsigned)c->B;
@@ -746,8 +732,8 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
             a.pitch_bytes = cols * 4u;
             a.n0 = (unsigned)n0;
             a.ppitch_bytes = 0;
-            a.yp = compact ? (const void *)c->cc_meta : nullptr;
-            a.zq = c->zq;
+            a.yp = compact ? (const void *)c->cc_meta.p : nullptr;
+            a.zq = c->zq.p;
             size_t sz = 80;
             void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
             void *fn = c->upd_nt[med ? 3 : (fma ? 1 : (sfma ? 2 : 0))];
@@ -767,8 +753,8 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
         // the assembly kernels left raw S in those columns (CLR: in the A part and in the B part)
         for (uint32_t part = 0; part < c->nparts; ++part)
             hipLaunchKernelGGL(sigma_finalize_kernel, dim3((unsigned)nloc), dim3(256), 0, c->stream,
-                               c->sigma, c->map, (int)c->pitch, (int)(part * c->part_pitch), sig_cols,
-                               (int)c->part_len, (int)n0, (int)nloc, c->weight);
+                               c->sigma.p, c->map.p, (int)c->pitch, (int)(part * c->part_pitch), sig_cols,
+                               (int)c->part_len, (int)n0, (int)nloc, c->weight.p);
         VSOM_HIP_CHECK(hipGetLastError());
     }
     return vsom_join_aux(c);   // the MSE sum forked by launch_finish ran beside the kernels above

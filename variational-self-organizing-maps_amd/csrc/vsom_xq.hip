@@ -56,24 +56,12 @@ int vsom_xq_ensure(vsom_ctx *c)
     const uint32_t nq8 = (cols / 4 + 7) / 8 * 8;
     const size_t bpad_cap = (c->Bcap + 31) / 32 * 32 + 32;
     const size_t need = (size_t)nq8 * bpad_cap;                     // float4 elements
-    if (need > c->Xq_cap) {
-        if (c->Xq) {
-            VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-            VSOM_HIP_CHECK(hipFree(c->Xq));
-            VSOM_HIP_CHECK(hipFree(c->zq));
-        }
-        c->Xq = nullptr;
-        c->zq = nullptr;
-        c->Xq_cap = 0;
-        VSOM_HIP_CHECK(hipMalloc(&c->Xq, need * sizeof(float4)));
-        VSOM_HIP_CHECK(hipMalloc(&c->zq, need / 32 * sizeof(unsigned)));
-        c->Xq_cap = need;
-    }
+    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_SYNC, {vsom_member(c->Xq, need), vsom_member(c->zq, need / 32)}));
     const uint32_t bpad = (uint32_t)((c->B + 31) / 32 * 32 + 32);
     hipLaunchKernelGGL(xq_transpose_kernel, dim3((bpad + 63) / 64, nq8 / 16 + (nq8 % 16 ? 1 : 0)), dim3(256), 0, c->stream,
-                       compact ? c->Xc : c->Xs, (int)cols, (int)c->B, (int)bpad, (int)nq8,
-                       c->transform == VSOM_MEDIAN ? 0x1.0p24f : 1.f, reinterpret_cast<float4 *>(c->Xq),
-                       c->zq);
+                       compact ? c->Xc.p : c->Xs.p, (int)cols, (int)c->B, (int)bpad, (int)nq8,
+                       c->transform == VSOM_MEDIAN ? 0x1.0p24f : 1.f, c->Xq.p,
+                       c->zq.p);
     VSOM_HIP_CHECK(hipGetLastError());
     c->xq_bpad = bpad;
     c->xq_quads = nq8;
