@@ -217,7 +217,9 @@ int vsom_prefetch_chunk(vsom_ctx *ctx, const float *x_host, size_t B);
  * epoch from which nothing reads the current chunk's sample rows any more -- so that they run BESIDE the epoch's
  * chains and vsom_commit_chunk launches nothing.  Between such a prefetch and its commit the current chunk's
  * sample rows are gone: lastBMU, the MSE and the model state of the current chunk stay readable, a search or a
- * distance call on it does not (commit first).  In every other situation the staging happens at commit, as before. */
+ * distance call on it does not (commit first), nor does a further vsom_batch_phase2_async range small enough for the
+ * small-map chain kernel (vsom_small_map_chains), which reads the rows themselves.  In every other situation the staging
+ * happens at commit, as before. */
 int vsom_prefetch_wait(vsom_ctx *ctx);
 int vsom_commit_chunk(vsom_ctx *ctx);
 /* the same for a next chunk that ALREADY lives in HBM (x_dev must stay valid until vsom_commit_chunk has been called):

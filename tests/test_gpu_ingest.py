@@ -266,3 +266,120 @@ def test_online_chunk_mse_through_get_mse():
     assert np.float32(got) == np.float32(want)
     a.close()
     b.close()
+
+
+@pytest.mark.parametrize("source", ["pinned", "device"])
+@pytest.mark.parametrize("mode,sigma_online", [(capi.BMU_EXACT, 3.0), (capi.BMU_SHORTLIST, 3.0)])
+def test_prefetch_after_an_unsynchronised_online_chunk_waits_for_it(source, mode, sigma_online):
+    """batch epoch (async) -> online chunk with mse_out = NULL -> prefetch / stage_next_device -> commit -> batch epoch.
+    The online chunk reads the staged rows for every sample (EXACT: the per-sample scan; SHORTLIST with sigma > 1 on
+    uint8-valued rows: the image-bounded search), so the next chunk must not be staged ahead over them while it runs:
+    a 4096-sample chunk runs for tens of milliseconds, its successor's staging takes microseconds."""
+    import ctypes as C
+    W = H = 48
+    J = 196
+    B = 4096
+    xa = gen.mnist_like(B, seed=81, dim=J)
+    xb = gen.mnist_like(B, seed=82, dim=J)
+    init = (gen.random_map(W * H, J, seed=42) * np.float32(100) + np.float32(100)).astype(np.float32)
+    orc = po.OracleSom(W, H, J, po.STANDARD)
+    orc.set_state(map=init)
+    ctx = vsom_amd.Context(W, H, J, po.STANDARD)
+    ctx.set_state(map=init)
+    ctx.set_bmu_mode(mode)
+    ctx.upload_chunk(xa)
+    L = capi.lib()
+    hip = C.CDLL("libamdhip64.so")
+    pb, ptr = None, None
+    if source == "pinned":
+        pb = capi.PinnedBuffer(xb.shape)
+        pb.array[...] = xb
+    else:
+        ptr = C.c_void_p()
+        assert hip.hipMalloc(C.byref(ptr), C.c_size_t(xb.nbytes)) == 0
+        assert hip.hipMemcpy(ptr, xb.ctypes.data_as(C.c_void_p), C.c_size_t(xb.nbytes), C.c_int(1)) == 0
+    ctx.batch_epoch_async(10.0, True)
+    capi.check(L.vsom_train_online_chunk_acc(ctx._h, 0.1, sigma_online, capi.EXPONENTIAL, 1, None))
+    if source == "pinned":
+        ctx.prefetch_chunk(pb.array)
+    else:
+        ctx.stage_next_device(ptr.value, B)
+    ctx.commit_chunk()
+    mse_g = ctx.batch_epoch(9.0, True)
+
+    lb = np.zeros(B, np.uint64)
+    orc.batch_epoch(xa, lb, 10.0, True, nthreads=16)
+    orc.train_online_chunk(xa, lb, 0.1, sigma_online, capi.EXPONENTIAL)
+    lb = np.zeros(B, np.uint64)
+    mse_o = orc.batch_epoch(xb, lb, 9.0, True, nthreads=16)
+    st = ctx.get_state()
+    for k, ref in (("map", orc.map), ("sigma", orc.sigma), ("S", orc.S), ("weight", orc.weight)):
+        same = (_bits(st[k]) == _bits(ref)) | (np.isnan(st[k]) & np.isnan(ref))
+        assert same.all(), (k, int((~same).sum()))
+    assert (st["hits"] == orc.hits).all()
+    assert (ctx.get_last_bmu() == lb).all()
+    assert np.float32(mse_g) == np.float32(mse_o)
+    ctx.close()
+    if pb is not None:
+        pb.free()
+    if ptr is not None:
+        hip.hipFree(ptr)
+
+
+@pytest.mark.parametrize("order", ["chain-range-then-prefetch", "prefetch-then-chain-range"])
+def test_phase2_ranges_around_a_stage_ahead_prefetch(order):
+    """Split phase 2 on a 48 x 48 x 196 map: a range of more than 2048 nodes takes the lane = node kernels, which record the
+    event after which nothing reads the staged rows; a smaller range takes the small-map chain kernel, which reads the rows
+    themselves (include/vsom_hip.h "Staging ahead", vsom_small_map_chains).
+    chain-range-then-prefetch: the chain range comes after the event, so a prefetch behind it must not stage ahead over
+    the rows the chain range reads -- the commit stages the chunk instead.
+    prefetch-then-chain-range: the prefetch stages ahead behind the lane = node range; a chain range is then refused
+    (naming the commit), a lane = node range on the transposed chunk is accepted.  Everything is the oracle's bits."""
+    W = H = 48
+    J = 196
+    N = W * H
+    xa = gen.mnist_like(1100, seed=91, dim=J)
+    xb = gen.mnist_like(77, seed=92, dim=J)
+    init = (gen.random_map(N, J, seed=42) * np.float32(100) + np.float32(100)).astype(np.float32)
+    orc = po.OracleSom(W, H, J, po.STANDARD)
+    orc.set_state(map=init)
+    ctx = vsom_amd.Context(W, H, J, po.STANDARD)
+    assert capi.lib().vsom_small_map_chains(ctx._h, 2048) == 1 and capi.lib().vsom_small_map_chains(ctx._h, 2049) == 0
+    ctx.set_state(map=init)
+    ctx.upload_chunk(xa)
+    pb = capi.PinnedBuffer(xb.shape)
+    pb.array[...] = xb
+    lb = np.zeros(xa.shape[0], np.uint64)
+    sq = np.zeros(xa.shape[0], np.float32)
+    sigma = 8.0
+    orc.batch_phase1_range(xa, 0, xa.shape[0], lb, sq, True, nthreads=16)
+    orc.batch_phase1_finish(lb, sq)
+    if order == "chain-range-then-prefetch":
+        ctx.batch_phase1_async(0, xa.shape[0], True)
+        ctx.batch_finish_async()
+        ctx.batch_phase2_async(sigma, 0, 2100)
+        ctx.batch_phase2_async(sigma, 2100, N)
+        ctx.prefetch_chunk(pb.array)
+        orc.batch_phase2_range(xa, lb, sigma, 0, N, nthreads=16)
+    else:
+        ctx.batch_epoch_async(sigma, True)
+        ctx.prefetch_chunk(pb.array)               # staged ahead behind the epoch's lane = node chains
+        with pytest.raises(capi.VsomError, match="commit"):
+            ctx.batch_phase2_async(sigma * 0.5, 0, 100)
+        ctx.batch_phase2_async(sigma * 0.5, 100, N)   # works on the transposed chunk
+        orc.batch_phase2_range(xa, lb, sigma, 0, N, nthreads=16)
+        orc.batch_phase2_range(xa, lb, sigma * 0.5, 100, N, nthreads=16)
+    assert (ctx.get_last_bmu() == lb).all()
+    ctx.commit_chunk()
+    mse_g = ctx.batch_epoch(6.0, True)
+    lb = np.zeros(xb.shape[0], np.uint64)
+    mse_o = orc.batch_epoch(xb, lb, 6.0, True, nthreads=16)
+    st = ctx.get_state()
+    for k, ref in (("map", orc.map), ("sigma", orc.sigma), ("S", orc.S), ("weight", orc.weight)):
+        same = (_bits(st[k]) == _bits(ref)) | (np.isnan(st[k]) & np.isnan(ref))
+        assert same.all(), (order, k, int((~same).sum()))
+    assert (st["hits"] == orc.hits).all()
+    assert (ctx.get_last_bmu() == lb).all()
+    assert np.float32(mse_g) == np.float32(mse_o)
+    ctx.close()
+    pb.free()

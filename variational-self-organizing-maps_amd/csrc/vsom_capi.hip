@@ -395,15 +395,19 @@ uint32_t vsom_nodes(const vsom_ctx *c) { return c ? c->N : 0; }
 uint32_t vsom_residual_len(const vsom_ctx *c) { return c ? (c->cu ? vsom_custom_residual_len(c) : c->part_len) : 0; }
 size_t vsom_chunk_size(const vsom_ctx *c) { return c ? c->B : 0; }
 
+// (caller arrays may be only 4-byte aligned: the words are loaded with memcpy, not through a uint64_t pointer)
 static bool all_zero_bits(const void *p, size_t bytes)
 {
-    const uint64_t *w = static_cast<const uint64_t *>(p);
+    const unsigned char *b = static_cast<const unsigned char *>(p);
     size_t i = 0;
-    for (; i + 8 <= bytes / 8; i += 8)
-        if (w[i] | w[i + 1] | w[i + 2] | w[i + 3] | w[i + 4] | w[i + 5] | w[i + 6] | w[i + 7])
+    for (; i + 64 <= bytes; i += 64) {
+        uint64_t w[8];
+        std::memcpy(w, b + i, 64);
+        if (w[0] | w[1] | w[2] | w[3] | w[4] | w[5] | w[6] | w[7])
             return false;
-    for (size_t b = i * 8; b < bytes; ++b)
-        if (static_cast<const unsigned char *>(p)[b])
+    }
+    for (; i < bytes; ++i)
+        if (b[i])
             return false;
     return true;
 }
@@ -872,7 +876,9 @@ int vsom_batch_phase2_async(vsom_ctx *c, double sigma, size_t n0, size_t n1)
 {
     CHECK_CTX_NOJOIN(c);
     VSOM_CUSTOM_REFUSE(c, "vsom_batch_phase2_async");
-    if (!c->xq_valid)             // (a further node range of the same epoch works on the transposed chunk it already has)
+    // (a further node range of the same epoch works on the transposed chunk it already has -- unless the range is
+    // small enough for the small-map chain kernel, which reads the staged rows themselves)
+    if (!c->xq_valid || (n1 > n0 && vsom_small_map_chains(c, n1 - n0)))
         CHECK_ROWS(c);
     if (n0 > n1 || n1 > c->N)
         return vsom_fail(VSOM_ERR_INVALID, "node range out of bounds");

@@ -83,7 +83,12 @@ struct vsom_ctx {
     DevBuf<int> cc_idx_alt, cc_inv_alt;
     DevBuf<unsigned> cc_meta_alt;
     hipEvent_t ev_rows_free = nullptr, ev_ahead = nullptr;
-    bool rows_free_valid = false;   // ev_rows_free belongs to the last enqueued work on this context
+    // ev_rows_free belongs to the last enqueued work on this context.  Set only by launch_phase2 behind its last reader of
+    // the staged rows; an entry point may leave it set only if it enqueues no reader of the staged rows (Xs, XP / YP, Xc,
+    // the int8 images) -- the copy-stream calls, a further phase-2 range on the transposed chunk.  Every other entry point
+    // clears it before it enqueues: CHECK_CTX does, and so must those that do without it (the online chunk, the phase-2
+    // chain kernels, the ensemble's train calls).
+    bool rows_free_valid = false;
     bool ahead_valid = false;       // a chunk is staged ahead (ahead_B rows; its compaction / int8-image state below)
     // staging kernels of a chunk staged ahead have been launched over the staged-row buffers and `stream` has neither
     // adopted them nor staged a chunk of its own since (whatever ahead_valid says: the ahead chunk may have been abandoned):

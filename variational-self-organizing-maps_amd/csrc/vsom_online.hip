@@ -2183,6 +2183,7 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
     if (c->ahead_rows)      // (CHECK_ROWS of vsom_capi.hip: the staged rows already belong to the next chunk)
         return vsom_fail(VSOM_ERR_INVALID,
                          "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first");
+    c->rows_free_valid = false;   // (as CHECK_CTX: the chunk below reads the staged rows, a later stage-ahead must not take them)
     const double *lutd = nullptr;
     int lutw = (int)c->W, lslot = 0, rc;
     bool tiny = online_tiny_applies(c, sigma);

@@ -643,6 +643,8 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
         const unsigned gx = (unsigned)((nloc + 63) / 64);
         if ((rc = vsom_load_asm_module(c)))
             return rc;
+        if (c->transform == VSOM_CLR || vsom_use_chain(c, nloc))
+            c->rows_free_valid = false;   // these chain kernels read the staged rows: no stage-ahead behind an earlier range's event
         if (c->transform == VSOM_CLR) {
             // lane = node, 8 parameter pairs per wavefront (gen_update_asm.py); a ragged last slice runs over the
             // parts' zero padding (part_pitch is a multiple of 32)
