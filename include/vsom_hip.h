@@ -314,9 +314,10 @@ int vsom_train_online_chunk_fetch(vsom_ctx *ctx, double eta, double sigma, int d
  * bound), out[2] = refinement workgroups that had a candidate, out[3] = 0.  All zero while the exact scan is in use. */
 int vsom_get_online_search_stats(vsom_ctx *ctx, uint64_t *out /*[4]*/, int reset);
 
-/* ---- ensembles: many small maps trained by one call ---------------------------------------
- * An ensemble is a set of existing contexts on one device; its calls train every member, each with its own parameters,
- * and have the same effect, bit for bit, as the single-context call made on every member in turn (map, S, sigmaMap,
+/* ---- ensembles: many small maps uploaded, trained and scored by one call each ---------------
+ * An ensemble is a set of existing contexts on one device; its calls give every member its rows
+ * (vsom_ensemble_upload_chunks), train every member, each with its own parameters, or score every member's chunk
+ * (vsom_ensemble_bmu_batch), and have the same effect, bit for bit, as the single-context call made on every member in turn (map, S, sigmaMap,
  * weightMap, bmuHits, lastBMU, the MSE, the running MSE across chunks).  Members whose single call takes the one-launch
  * kernel of a tiny map (online: the chunk kernel; batch: the epoch kernel) and whose LDS need fits the device run as one
  * launch per kernel instantiation, one workgroup per member; every other member (larger maps, CLR online, custom
@@ -340,6 +341,27 @@ size_t vsom_ensemble_size(const vsom_ensemble *e);
 int vsom_ensemble_train_online_chunk_fetch(vsom_ensemble *e, const double *eta, const double *sigma, const int *decay_fn,
                                            int first_chunk, uint64_t *const *lastbmu_out, float *mse_out);
 int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_first, float *mse_out);
+/* Every member's chunk from ONE host buffer.  Member k gets B[k] rows of its own row length J_k (the length
+ * vsom_upload_chunk reads for that member), contiguous at x_host + offset[k] (offsets in floats).  Several members may
+ * name the same rows (equal offsets: a sweep over one data set).  n_floats = the extent of x_host.  Afterwards every call
+ * on every member gives, bit for bit, what it gives after vsom_upload_chunk(member, x_host + offset[k], B[k]) (wait = 1)
+ * or vsom_upload_chunk_async (wait = 0).  The union of the members' ranges, gaps between them included, is copied to the
+ * device once; the plain members' rows are staged by one launch, the others (a chunk that gets the column compaction,
+ * CLR, no rows) by their single-context staging from that copy, custom members by their own upload.
+ * wait = 1: returns when x_host may be reused.  wait = 0: x_host must be pinned (vsom_host_alloc) and stay unchanged
+ * until a call that synchronises the members has returned (the contract of vsom_upload_chunk_async); work enqueued on a
+ * member's stream afterwards runs behind the staging.  Refuses (VSOM_ERR_INVALID, naming the member, before anything is
+ * enqueued): a null array, a null x_host with some B[k] > 0, offset[k] + B[k] * J_k > n_floats, B[k] > 0x7FFFFFFF.
+ * Every member state the single upload accepts is accepted (a chunk staged ahead, a prefetched chunk not committed). */
+int vsom_ensemble_upload_chunks(vsom_ensemble *e, const float *x_host, size_t n_floats, const size_t *offset,
+                                const size_t *B, int wait);
+/* Som::findBmu for every row of every member's staged chunk: per member exactly what vsom_bmu_batch returns and leaves
+ * on the device (lastBMU, sqres: a later vsom_get_last_bmu, vsom_get_sqres or batch epoch with is_first = 0 sees the
+ * same values).  Members whose map has N * part_len <= 4096 (part_len: D, or D / 2 for CLR) are searched by one launch
+ * per kind, whatever their chunk size and search settings; larger maps and custom members run vsom_bmu_batch in the same
+ * call.  idx_out / dist_out: NULL, or one pointer per member (NULL or room for that member's B values).  Refuses like
+ * the train calls: a member without a chunk, a member whose next chunk is staged ahead over its rows. */
+int vsom_ensemble_bmu_batch(vsom_ensemble *e, uint64_t *const *idx_out, float *const *dist_out);
 
 /* ---- multi-GPU batch epoch, one process, the GPUs of one node ------------------------
  * Som::trainBatchSomEpoch's two loops shard differently: phase 1 (Som.cpp:764-782 / 786-805) is

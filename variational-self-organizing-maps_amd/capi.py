@@ -45,7 +45,7 @@ SYMBOLS = [
     "vsom_group_batch_epoch_async", "vsom_group_batch_epoch", "vsom_group_get_mse",
     "vsom_create_custom", "vsom_custom_compile_check",
     "vsom_ensemble_create", "vsom_ensemble_destroy", "vsom_ensemble_size", "vsom_ensemble_train_online_chunk_fetch",
-    "vsom_ensemble_batch_epoch",
+    "vsom_ensemble_batch_epoch", "vsom_ensemble_upload_chunks", "vsom_ensemble_bmu_batch",
 ]
 
 
@@ -206,6 +206,8 @@ def lib():
     L.vsom_ensemble_train_online_chunk_fetch.argtypes = [vp, C.POINTER(C.c_double), C.POINTER(C.c_double),
                                                          C.POINTER(C.c_int), C.c_int, C.POINTER(u64p), fp]
     L.vsom_ensemble_batch_epoch.argtypes = [vp, C.POINTER(C.c_double), C.c_int, fp]
+    L.vsom_ensemble_upload_chunks.argtypes = [vp, fp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int]
+    L.vsom_ensemble_bmu_batch.argtypes = [vp, C.POINTER(u64p), C.POINTER(fp)]
     _lib = L
     return L
 
@@ -704,6 +706,7 @@ class Ensemble:
         arr = (C.c_void_p * max(n, 1))(*[c._h.value if c is not None and c._h else None for c in self.members])
         self._h = C.c_void_p()
         check(lib().vsom_ensemble_create(C.byref(self._h), arr, n))
+        self._pinned = None         # upload_chunks' packing buffer (grow-only)
 
     def __len__(self):
         return len(self.members)
@@ -712,6 +715,9 @@ class Ensemble:
         if self._h:
             lib().vsom_ensemble_destroy(self._h)
             self._h = C.c_void_p()
+        if getattr(self, "_pinned", None) is not None:
+            self._pinned.free()
+            self._pinned = None
 
     def __del__(self):
         try:
@@ -744,3 +750,60 @@ class Ensemble:
         check(lib().vsom_ensemble_batch_epoch(self._h, self._per_member(sigma, C.c_double, float), int(bool(is_first)),
                                               _f(mse)))
         return mse
+
+    def upload_chunks(self, rows):
+        """every member's chunk in one call (vsom_ensemble_upload_chunks, wait = 1): `rows` is a list of one 2-D float32
+        array per member, or one 2-D array that every member gets.  The same array object given to several members is
+        packed once and shared.  Bit for bit what Context.upload_chunk on every member gives."""
+        n = len(self.members)
+        if isinstance(rows, np.ndarray):
+            rows = [rows] * n
+        rows = list(rows)
+        if len(rows) != n:
+            raise ValueError(f"{len(rows)} chunks for {n} members")
+        seen, parts, offsets, Bs, total = {}, [], [], [], 0
+        for k, (X, c) in enumerate(zip(rows, self.members)):
+            X = np.asarray(X)
+            if X.ndim != 2 or X.shape[1] != c.in_len:
+                raise ValueError(f"member {k}: rows of shape {X.shape}, the member reads rows of {c.in_len}")
+            key = id(rows[k])
+            if key not in seen:
+                seen[key] = total
+                parts.append((total, X))
+                total += X.size
+            offsets.append(seen[key])
+            Bs.append(X.shape[0])
+        if self._pinned is None or self._pinned.array.size < total:
+            if self._pinned is not None:
+                self._pinned.free()
+            self._pinned = PinnedBuffer((max(total, 1),))
+        buf = self._pinned.array
+        for at, X in parts:
+            buf[at:at + X.size] = X.reshape(-1)
+        self._upload(buf, total, offsets, Bs, 1)
+
+    def upload_chunks_async(self, pinned, offsets, B):
+        """the low-level form (wait = 0): member k gets B[k] rows at pinned.flat[offsets[k]:] (a PinnedBuffer's float32
+        array, which must stay unchanged until a call that synchronises the members has returned)"""
+        a = pinned.array if isinstance(pinned, PinnedBuffer) else pinned
+        assert a.dtype == np.float32 and a.flags.c_contiguous
+        self._upload(a, a.size, offsets, B, 0)
+
+    def _upload(self, a, n_floats, offsets, B, wait):
+        n = len(self.members)
+        if len(offsets) != n or len(B) != n:
+            raise ValueError(f"{len(offsets)} offsets and {len(B)} chunk sizes for {n} members")
+        off = (C.c_size_t * n)(*[int(v) for v in offsets])
+        bs = (C.c_size_t * n)(*[int(v) for v in B])
+        check(lib().vsom_ensemble_upload_chunks(self._h, _f(a), int(n_floats), off, bs, int(wait)))
+
+    def bmu_batch(self):
+        """Som::findBmu for every row of every member's chunk (vsom_ensemble_bmu_batch): (list of uint64 index arrays,
+        list of float32 distance arrays), one array per member"""
+        n = len(self.members)
+        idx = [np.empty(c.chunk_size, np.uint64) for c in self.members]
+        dist = [np.empty(c.chunk_size, np.float32) for c in self.members]
+        ip = (C.POINTER(C.c_uint64) * n)(*[_u(a) for a in idx])
+        dp = (C.POINTER(C.c_float) * n)(*[_f(a) for a in dist])
+        check(lib().vsom_ensemble_bmu_batch(self._h, ip, dp))
+        return idx, dist

@@ -135,6 +135,36 @@ int vsom_commit_end(vsom_ctx *c)
     return VSOM_OK;
 }
 
+int ensure_chunk_capacity(vsom_ctx *c, size_t B)
+{
+    if (B <= c->Bcap)
+        return VSOM_OK;
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->copy_stream));
+    c->ahead_valid = false;       // (a chunk staged ahead into the old buffers is staged anew at its commit)
+    c->partial.reset();
+    c->Bcap = 0;
+    // no chunk is staged from here on: should an allocation below fail, later entry points report
+    // "no chunk loaded" instead of launching kernels on null buffers
+    c->B = 0;
+    c->chunk_loaded = false;
+    size_t cap = (B + 63) / 64 * 64;
+    // the fills below go to the context's stream: hipMemset would run on the null stream, which a
+    // non-blocking stream does not wait for -- the fill could then land on top of the rows the staging
+    // kernel writes next (seen as a few zero sample rows in one search of ~600 random cases)
+    // the assembly update kernel reads up to 2 sample rows past the chunk and touches rows up to
+    // PF_ROWS + 3 past it (gen_update_asm.py, load_cw)
+    // XP / YP (CLR) like Xs: the pipelined update kernels read one sample pair past the chunk
+    const size_t pp_rows = c->transform == VSOM_CLR ? (cap + VSOM_ROW_PAD) * c->part_pitch : 0;
+    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_REBUILD,
+                                 {vsom_member(c->Xs, (cap + VSOM_ROW_PAD) * c->xpitch, VSOM_BUF_ZERO),
+                                  vsom_member(c->XP, pp_rows, VSOM_BUF_ZERO), vsom_member(c->YP, pp_rows, VSOM_BUF_ZERO),
+                                  vsom_member(c->lastbmu, cap, VSOM_BUF_ZERO), vsom_member(c->lastbmu_alt, cap, VSOM_BUF_ZERO),
+                                  vsom_member(c->sqres, cap, VSOM_BUF_ZERO), vsom_member(c->nan0, cap, VSOM_BUF_ZERO)}));
+    c->Bcap = cap;
+    return VSOM_OK;
+}
+
 extern "C" {
 
 const char *vsom_last_error(void) { return g_last_error.c_str(); }
@@ -496,36 +526,6 @@ int vsom_get_state(vsom_ctx *c, float *map, float *sigma, float *S, float *weigh
     if (bmu_hits)
         VSOM_HIP_CHECK(hipMemcpyAsync(bmu_hits, c->hits.p, (size_t)c->N * 8, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return VSOM_OK;
-}
-
-static int ensure_chunk_capacity(vsom_ctx *c, size_t B)
-{
-    if (B <= c->Bcap)
-        return VSOM_OK;
-    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    VSOM_HIP_CHECK(hipStreamSynchronize(c->copy_stream));
-    c->ahead_valid = false;       // (a chunk staged ahead into the old buffers is staged anew at its commit)
-    c->partial.reset();
-    c->Bcap = 0;
-    // no chunk is staged from here on: should an allocation below fail, later entry points report
-    // "no chunk loaded" instead of launching kernels on null buffers
-    c->B = 0;
-    c->chunk_loaded = false;
-    size_t cap = (B + 63) / 64 * 64;
-    // the fills below go to the context's stream: hipMemset would run on the null stream, which a
-    // non-blocking stream does not wait for -- the fill could then land on top of the rows the staging
-    // kernel writes next (seen as a few zero sample rows in one search of ~600 random cases)
-    // the assembly update kernel reads up to 2 sample rows past the chunk and touches rows up to
-    // PF_ROWS + 3 past it (gen_update_asm.py, load_cw)
-    // XP / YP (CLR) like Xs: the pipelined update kernels read one sample pair past the chunk
-    const size_t pp_rows = c->transform == VSOM_CLR ? (cap + VSOM_ROW_PAD) * c->part_pitch : 0;
-    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_REBUILD,
-                                 {vsom_member(c->Xs, (cap + VSOM_ROW_PAD) * c->xpitch, VSOM_BUF_ZERO),
-                                  vsom_member(c->XP, pp_rows, VSOM_BUF_ZERO), vsom_member(c->YP, pp_rows, VSOM_BUF_ZERO),
-                                  vsom_member(c->lastbmu, cap, VSOM_BUF_ZERO), vsom_member(c->lastbmu_alt, cap, VSOM_BUF_ZERO),
-                                  vsom_member(c->sqres, cap, VSOM_BUF_ZERO), vsom_member(c->nan0, cap, VSOM_BUF_ZERO)}));
-    c->Bcap = cap;
     return VSOM_OK;
 }
 

@@ -165,13 +165,19 @@ static int cc_ensure(vsom_ctx *c)
     return VSOM_OK;
 }
 
+// does vsom_cc_begin look at a chunk of B rows at all?  (false: it returns at once and changes nothing)
+bool vsom_cc_considered(const vsom_ctx *c, size_t B)
+{
+    // small chunks: the passes (and the model-row gather / expansion around them) cost more than a few retired
+    // column quads of a short chain save; vsom_set_column_compaction moves the threshold
+    return vsom_cc_applies(c) && B > 0 && c->cc_min_rows >= 0 && (long)B >= c->cc_min_rows;
+}
+
 // before the rows are staged: does this chunk get the compaction?  (then stage_rows_kernel also flags the live columns)
 int vsom_cc_begin(vsom_ctx *c, size_t B, bool *on)
 {
     *on = false;
-    // small chunks: the passes (and the model-row gather / expansion around them) cost more than a few retired
-    // column quads of a short chain save; vsom_set_column_compaction moves the threshold
-    if (!vsom_cc_applies(c) || B == 0 || c->cc_min_rows < 0 || (long)B < c->cc_min_rows)
+    if (!vsom_cc_considered(c, B))
         return VSOM_OK;
     // feedback of earlier chunks (pinned memory, read without synchronising: stale values only delay the decision)
     volatile unsigned *fb = c->cc_fb.p;

@@ -8,7 +8,15 @@
 //
 // The descriptor array lives in two slots (pinned host image + device copy), used alternately: a slot is rewritten only
 // after the event recorded behind its last launch has completed -- the scheme of the pinned neighbourhood-table slots.
-#include "vsom_internal.hpp"
+//
+// The calls around training are batched the same way.  vsom_ensemble_upload_chunks copies the union of the members' row
+// ranges with one H2D copy into the ensemble's raw buffer and stages every plain member's rows with one launch of
+// stage_rows_many_kernel (one workgroup per (member, 16 rows)); members whose chunk gets the column compaction, CLR members
+// and those with no rows are staged by their single-context path from that device copy, custom members by their own
+// upload.  vsom_ensemble_bmu_batch scores every tiny member with one launch of ensemble_bmu_many_kernel<kind> per kind
+// (one workgroup per (member, 64 rows)): the exact search of the one-launch batch epoch's phase 1, whose results the
+// kernel also stores into one pinned buffer for all members; every other member runs vsom_bmu_batch in the same call.
+#include "vsom_device.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -29,6 +37,14 @@ struct vsom_ensemble {
     std::vector<unsigned char> desc;         // one descriptor per member, packed at the kind's own descriptor size
     std::vector<int> grp, lslot;
     std::vector<size_t> smem;
+    // upload: the members' rows as one copy of the host range (grow-only); ev_raw is recorded behind the call's last
+    // reader of it (the staging launch, and -- joined back into the launch stream -- the ordinary stagings)
+    DevBuf<float> raw;
+    hipEvent_t ev_raw = nullptr, ev_stage = nullptr;
+    bool raw_valid = false;
+    // scoring: idx / dist of every launched member, stored by the kernel (pinned host memory, grow-only)
+    PinnedBuf<u64> sc_idx;
+    PinnedBuf<float> sc_dist;
 };
 
 static int ens_fail(size_t k, const char *what)
@@ -85,6 +101,11 @@ void vsom_ensemble_destroy(vsom_ensemble *e)
         if (s.ev)
             (void)hipEventDestroy(s.ev);
     }
+    if (e->raw_valid)
+        (void)hipEventSynchronize(e->ev_raw);
+    for (hipEvent_t ev : {e->ev_raw, e->ev_stage})
+        if (ev)
+            (void)hipEventDestroy(ev);
     for (hipEvent_t ev : e->ev_in)
         (void)hipEventDestroy(ev);
     if (e->own_stream)
@@ -307,5 +328,406 @@ int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_firs
     for (size_t k = 0; k < n; ++k)
         if (e->grp[k] >= 0 && mse_out)
             mse_out[k] = *static_cast<volatile float *>(e->m[k]->mse.p);
+    return VSOM_OK;
+}
+
+// ================================================================================================================
+// upload and scoring
+// ================================================================================================================
+// one member's rows for stage_rows_many_kernel: stage_rows_kernel's arguments without the compaction flags (members whose
+// chunk gets the compaction take the single-context staging)
+struct EnsStageDesc {
+    const float *x;          // B x J raw rows in the ensemble's copy
+    float *xs;
+    u64 *lastbmu;
+    unsigned *xflag;         // the integer shortlist's data-kind word, or null
+    int J, B, xpitch, pad;
+};
+
+// stage_rows_kernel's work for every member in one launch: workgroup (x, y) = rows [16x, 16x + 16) of member y
+__global__ __launch_bounds__(256) void stage_rows_many_kernel(const EnsStageDesc *__restrict__ descs)
+{
+    const EnsStageDesc a = descs[blockIdx.y];
+    const int r0 = blockIdx.x * 16;
+    if (r0 >= a.B)
+        return;                                          // (workgroup-uniform: the grid covers the longest chunk)
+    const int r1 = r0 + 16 < a.B ? r0 + 16 : a.B;
+    if (threadIdx.x < 16 && r0 + (int)threadIdx.x < a.B)
+        a.lastbmu[r0 + threadIdx.x] = 0;                 // DataSet.cpp:136-137
+    if (a.xflag && blockIdx.x == 0 && threadIdx.x < 33)
+        a.xflag[32 * threadIdx.x] = 0u;                  // the word and its 32 write slots (vsom_sl_i8.hip)
+    for (int d = threadIdx.x; d < a.xpitch; d += 256) {
+        float v[16];
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            v[i] = (d < a.J && r0 + i < r1) ? a.x[(size_t)(r0 + i) * a.J + d] : 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i)
+            if (r0 + i < r1)
+                a.xs[(size_t)(r0 + i) * a.xpitch + d] = v[i];
+    }
+}
+
+constexpr int ENS_SCORE_ROWS = 64;   // rows per workgroup of ensemble_bmu_many_kernel
+
+struct EnsScoreDesc {
+    DistArgs d;
+    u64 *lastbmu;
+    float *sqres;
+    u64 *out_idx;            // the member's slice of the ensemble's pinned result buffers
+    float *out_dist;
+    int B, N;
+};
+
+// Som::findBmu (Som.cpp:291-309) for rows [64x, 64x + 64) of member y: the is_first phase 1 of the one-launch batch epoch
+// (vsom_tiny_batch_body.inc) -- every (row, node) distance by an 8-lane group in Eigen's order (vsom_group_dist), the
+// argmin as an LDS atomicMin on the (distance, index) key (strict <, lowest index, NaN never wins), a NaN at node 0 pins
+// the BMU to 0 with sqres = NaN -- on the model rows copied into LDS first (N * part_len <= 4096: at most 32 KB for CLR).
+template <int KIND>
+__global__ __launch_bounds__(256) void ensemble_bmu_many_kernel(const EnsScoreDesc *__restrict__ descs)
+{
+    constexpr bool CLR = KIND == VSOM_CLR;
+    const EnsScoreDesc a = descs[blockIdx.y];
+    const int s0 = blockIdx.x * ENS_SCORE_ROWS;
+    if (s0 >= a.B)
+        return;                                          // (workgroup-uniform)
+    const int T = a.B - s0 < ENS_SCORE_ROWS ? a.B - s0 : ENS_SCORE_ROWS, N = a.N, L = a.d.L;
+    extern __shared__ __attribute__((aligned(16))) unsigned char ens_smem[];
+    u64 *keys = reinterpret_cast<u64 *>(ens_smem);               // [64]
+    int *nan0 = reinterpret_cast<int *>(keys + ENS_SCORE_ROWS);   // [64]
+    float *ml = reinterpret_cast<float *>(nan0 + ENS_SCORE_ROWS); // N rows of L values (CLR: A part, then B part)
+    const int tid = threadIdx.x;
+    const int rl = CLR ? 2 * L : L;
+    for (int i = tid; i < N * rl; i += 256) {
+        const int n = i / rl, e = i - n * rl;
+        ml[i] = e < L ? a.d.ma[(size_t)n * a.d.ldm + e] : a.d.mb[(size_t)n * a.d.ldm + e - L];
+    }
+    for (int s = tid; s < T; s += 256) {
+        keys[s] = ~0ull;
+        nan0[s] = 0;
+    }
+    __syncthreads();
+    const float *ma = ml, *mb = CLR ? ml + L : ml;
+    const int grp = tid >> 3, k = tid & 7;
+    for (int p = grp; p < T * N; p += 32) {
+        const int s = p / N, n = p - s * N;
+        const size_t row = (size_t)(s0 + s) * a.d.ldx;
+        const float dd = vsom_group_dist<CLR>(a.d.xa + row, a.d.xb + row, ma + (size_t)n * rl, mb + (size_t)n * rl, L, k);
+        if (k == 0) {
+            if (n == 0 && dd != dd)
+                nan0[s] = 1;
+            atomicMin(&keys[s], vsom_key(dd, (uint32_t)n));
+        }
+    }
+    __syncthreads();
+    for (int s = tid; s < T; s += 256) {
+        const u64 key = keys[s];
+        const u64 idx = nan0[s] ? 0ull : (key & 0xFFFFFFFFull);
+        const float sq = nan0[s] ? __uint_as_float(0x7FC00000u) : __uint_as_float((uint32_t)(key >> 32));
+        a.lastbmu[s0 + s] = idx;
+        a.sqres[s0 + s] = sq;
+        a.out_idx[s0 + s] = idx;
+        a.out_dist[s0 + s] = sq;
+    }
+}
+
+// the launch stream of a call that enqueues device work for the non-custom members: their one stream, or the ensemble's
+// own behind every member stream's pending work.  *streams: the distinct member streams.
+static int ens_launch_stream(vsom_ensemble *e, std::vector<hipStream_t> *streams, hipStream_t *ls)
+{
+    streams->clear();
+    for (vsom_ctx *c : e->m)
+        if (!c->cu)
+            streams->push_back(c->stream);
+    std::sort(streams->begin(), streams->end());
+    streams->erase(std::unique(streams->begin(), streams->end()), streams->end());
+    *ls = nullptr;
+    if (streams->empty())
+        return VSOM_OK;
+    if (streams->size() == 1) {
+        *ls = (*streams)[0];
+        return VSOM_OK;
+    }
+    if (!e->own_stream)
+        VSOM_HIP_CHECK(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
+    *ls = e->own_stream;
+    while (e->ev_in.size() < streams->size()) {
+        hipEvent_t ev = nullptr;
+        VSOM_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
+        e->ev_in.push_back(ev);
+    }
+    for (size_t i = 0; i < streams->size(); ++i) {
+        VSOM_HIP_CHECK(hipEventRecord(e->ev_in[i], (*streams)[i]));
+        VSOM_HIP_CHECK(hipStreamWaitEvent(*ls, e->ev_in[i], 0));
+    }
+    return VSOM_OK;
+}
+
+// `count` descriptors of `stride` bytes into a free slot and onto the device (on ls); the caller launches from *dev and
+// then calls ens_slot_done
+static int ens_slot_put(vsom_ensemble *e, const void *desc, size_t count, size_t stride, hipStream_t ls,
+                        const unsigned char **dev)
+{
+    auto &s = e->slot[e->next];
+    if (!s.ev)
+        VSOM_HIP_CHECK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    if (s.valid)
+        VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
+    s.valid = false;
+    const size_t bytes = count * stride;
+    if (bytes > s.host.cap) {
+        const size_t cap = std::max(bytes, (size_t)64 * stride);
+        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, VSOM_BUF_REBUILD, {vsom_member(s.host, cap), vsom_member(s.dev, cap)}));
+    }
+    std::memcpy(s.host.p, desc, bytes);
+    VSOM_HIP_CHECK(hipMemcpyAsync(s.dev.p, s.host.p, bytes, hipMemcpyHostToDevice, ls));
+    *dev = s.dev.p;
+    return VSOM_OK;
+}
+
+static int ens_slot_done(vsom_ensemble *e, hipStream_t ls)
+{
+    auto &s = e->slot[e->next];
+    VSOM_HIP_CHECK(hipEventRecord(s.ev, ls));
+    s.valid = true;
+    e->next ^= 1;
+    return VSOM_OK;
+}
+
+// grid.y is at most 65535: more members are launched in slices
+constexpr unsigned ENS_MAX_Y = 65535;
+
+int vsom_ensemble_upload_chunks(vsom_ensemble *e, const float *x_host, size_t n_floats, const size_t *offset,
+                                const size_t *B, int wait)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    if (!offset || !B)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null array");
+    const size_t n = e->m.size();
+    for (size_t k = 0; k < n; ++k) {
+        if (B[k] > 0x7FFFFFFFull)
+            return ens_fail(k, "chunk too large");
+        if (B[k] > 0 && !x_host)
+            return ens_fail(k, "x_host is null");
+        const size_t len = B[k] * e->m[k]->J;   // (< 2^31 * 2^32: no overflow)
+        if (offset[k] > n_floats || len > n_floats - offset[k])
+            return ens_fail(k, "rows beyond n_floats");
+    }
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    if (int rc = join_members(e))
+        return rc;
+    // host bookkeeping first (a capacity that grows synchronises the member and reallocates); which members the one
+    // launch stages (grp 0), and the extent of the rows on the device
+    e->grp.assign(n, -1);
+    size_t lo = SIZE_MAX, hi = 0;
+    for (size_t k = 0; k < n; ++k) {
+        vsom_ctx *c = e->m[k];
+        if (c->cu)
+            continue;
+        if (int rc = ensure_chunk_capacity(c, B[k]))
+            return rc;
+        if (B[k] == 0)
+            continue;
+        lo = std::min(lo, offset[k]);
+        hi = std::max(hi, offset[k] + B[k] * c->J);
+        if (c->transform != VSOM_CLR && !vsom_cc_considered(c, B[k]))
+            e->grp[k] = 0;
+    }
+    std::vector<hipStream_t> streams;
+    hipStream_t ls = nullptr;
+    if (hi > lo) {
+        if (hi - lo > e->raw.cap) {
+            if (e->raw_valid)                    // an earlier call's staging may still read the old buffer
+                VSOM_HIP_CHECK(hipEventSynchronize(e->ev_raw));
+            e->raw_valid = false;
+            VSOM_ALLOC_CHECK(vsom_grow(e->raw, hi - lo, nullptr));
+        }
+        if (!e->ev_raw)
+            VSOM_HIP_CHECK(hipEventCreateWithFlags(&e->ev_raw, hipEventDisableTiming));
+        if (!e->ev_stage)
+            VSOM_HIP_CHECK(hipEventCreateWithFlags(&e->ev_stage, hipEventDisableTiming));
+        if (int rc = ens_launch_stream(e, &streams, &ls))
+            return rc;
+        if (e->raw_valid)                        // (behind the previous call's readers, whichever stream it used)
+            VSOM_HIP_CHECK(hipStreamWaitEvent(ls, e->ev_raw, 0));
+        VSOM_HIP_CHECK(hipMemcpyAsync(e->raw.p, x_host + lo, (hi - lo) * sizeof(float), hipMemcpyHostToDevice, ls));
+        // the one launch: launch_stage_chunk's bookkeeping for each of its members, then the descriptors
+        std::vector<EnsStageDesc> d;
+        unsigned blocks = 0;
+        for (size_t k = 0; k < n; ++k) {
+            if (e->grp[k] != 0)
+                continue;
+            vsom_ctx *c = e->m[k];
+            c->B = B[k];
+            c->chunk_loaded = true;
+            c->cc_valid = false;
+            c->xq_valid = false;
+            c->xi_valid = false;
+            c->rows_free_valid = false;
+            if (c->ahead_rows) {                 // stagings of a chunk staged ahead may still write these buffers
+                VSOM_HIP_CHECK(hipStreamWaitEvent(ls, c->ev_ahead, 0));
+                c->ahead_rows = false;
+            }
+            c->ahead_valid = false;
+            d.push_back({e->raw.p + (offset[k] - lo), c->Xs.p, c->lastbmu.p, c->sl_scal.p ? c->sl_scal.p + 8192 : nullptr,
+                         (int)c->J, (int)B[k], (int)c->xpitch, 0});
+            blocks = std::max(blocks, (unsigned)((B[k] + 15) / 16));
+        }
+        for (size_t i0 = 0; i0 < d.size(); i0 += ENS_MAX_Y) {
+            const size_t cnt = std::min(d.size() - i0, (size_t)ENS_MAX_Y);
+            const unsigned char *dev = nullptr;
+            if (int rc = ens_slot_put(e, d.data() + i0, cnt, sizeof(EnsStageDesc), ls, &dev))
+                return rc;
+            hipLaunchKernelGGL(stage_rows_many_kernel, dim3(blocks, (unsigned)cnt), dim3(256), 0, ls,
+                               reinterpret_cast<const EnsStageDesc *>(dev));
+            VSOM_HIP_CHECK(hipGetLastError());
+            if (int rc = ens_slot_done(e, ls))
+                return rc;
+        }
+        // every member stream behind the copy and the staging: later work on a member, and the ordinary stagings below
+        VSOM_HIP_CHECK(hipEventRecord(e->ev_stage, ls));
+        for (hipStream_t s : streams)
+            if (s != ls)
+                VSOM_HIP_CHECK(hipStreamWaitEvent(s, e->ev_stage, 0));
+    }
+    // the other members: their single-context staging from the device copy (no rows: nothing is read), custom members
+    // from the host range
+    for (size_t k = 0; k < n; ++k) {
+        if (e->grp[k] == 0)
+            continue;
+        vsom_ctx *c = e->m[k];
+        int rc = c->cu ? vsom_custom_upload(c, B[k] ? x_host + offset[k] : nullptr, B[k], wait != 0)
+                       : vsom_set_chunk_device(c, B[k] ? e->raw.p + (offset[k] - lo) : nullptr, B[k]);
+        if (rc)
+            return rc;
+    }
+    if (ls) {
+        // the raw buffer's last readers: the next call (or a growth) waits for ev_raw before it overwrites the buffer
+        for (size_t i = 0; i < streams.size(); ++i)
+            if (streams[i] != ls) {
+                VSOM_HIP_CHECK(hipEventRecord(e->ev_in[i], streams[i]));
+                VSOM_HIP_CHECK(hipStreamWaitEvent(ls, e->ev_in[i], 0));
+            }
+        VSOM_HIP_CHECK(hipEventRecord(e->ev_raw, ls));
+        e->raw_valid = true;
+        if (wait)                                // x_host may be reused by the caller
+            VSOM_HIP_CHECK(hipEventSynchronize(e->ev_raw));
+    }
+    return VSOM_OK;
+}
+
+int vsom_ensemble_bmu_batch(vsom_ensemble *e, uint64_t *const *idx_out, float *const *dist_out)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    const size_t n = e->m.size();
+    for (size_t k = 0; k < n; ++k) {
+        const vsom_ctx *c = e->m[k];
+        if (!c->chunk_loaded)
+            return ens_fail(k, "no chunk loaded");
+        if (c->ahead_rows)
+            return ens_fail(k, "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first");
+    }
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    if (int rc = join_members(e))
+        return rc;
+    // tiny members (the one-launch kernels' bound on the map) with rows: one launch per kind
+    const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);
+    e->grp.assign(n, -1);
+    size_t total = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const vsom_ctx *c = e->m[k];
+        const size_t L = c->part_len, rl = c->transform == VSOM_CLR ? 2 * L : L;
+        const size_t smem = ENS_SCORE_ROWS * (sizeof(u64) + sizeof(int)) + (size_t)c->N * rl * sizeof(float);
+        if (c->cu || c->B == 0 || (size_t)c->N * L > 4096 || smem > lds_cap)
+            continue;
+        e->grp[k] = c->transform;
+        total += c->B;
+    }
+    hipStream_t ls = nullptr;
+    std::vector<hipStream_t> streams;
+    std::vector<size_t> at(n, 0);
+    int rc = VSOM_OK;
+    if (total) {
+        if (total > e->sc_idx.cap)             // (no kernel of an earlier call is running: every call ends in a wait)
+            VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(e->sc_idx, total), vsom_member(e->sc_dist, total)}));
+        if ((rc = ens_launch_stream(e, &streams, &ls)))
+            return rc;
+        for (int kind : {VSOM_STANDARD, VSOM_MEDIAN, VSOM_CLR}) {
+            std::vector<EnsScoreDesc> d;
+            unsigned tiles = 0;
+            size_t smem = 0, pos = 0;
+            for (size_t k = 0; k < n; ++k) {
+                if (e->grp[k] < 0) {
+                    continue;
+                } else if (e->grp[k] != kind) {
+                    pos += e->m[k]->B;
+                    continue;
+                }
+                vsom_ctx *c = e->m[k];
+                const bool clr = kind == VSOM_CLR;
+                EnsScoreDesc a;
+                a.d.xa = clr ? c->XP.p : c->Xs.p;
+                a.d.xb = clr ? c->YP.p : c->Xs.p;
+                a.d.ldx = (int)(clr ? c->part_pitch : c->xpitch);
+                a.d.ma = c->map.p;
+                a.d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
+                a.d.ldm = (int)c->pitch;
+                a.d.L = (int)c->part_len;
+                a.lastbmu = c->lastbmu.p;
+                a.sqres = c->sqres.p;
+                a.out_idx = e->sc_idx.p + pos;
+                a.out_dist = e->sc_dist.p + pos;
+                a.B = (int)c->B;
+                a.N = (int)c->N;
+                at[k] = pos;
+                pos += c->B;
+                d.push_back(a);
+                tiles = std::max(tiles, (unsigned)((c->B + ENS_SCORE_ROWS - 1) / ENS_SCORE_ROWS));
+                smem = std::max(smem, ENS_SCORE_ROWS * (sizeof(u64) + sizeof(int)) +
+                                          (size_t)c->N * c->part_len * (clr ? 2 : 1) * sizeof(float));
+            }
+            for (size_t i0 = 0; i0 < d.size() && !rc; i0 += ENS_MAX_Y) {
+                const size_t cnt = std::min(d.size() - i0, (size_t)ENS_MAX_Y);
+                const unsigned char *dev = nullptr;
+                if ((rc = ens_slot_put(e, d.data() + i0, cnt, sizeof(EnsScoreDesc), ls, &dev)))
+                    break;
+                const EnsScoreDesc *args = reinterpret_cast<const EnsScoreDesc *>(dev);
+                const dim3 grid(tiles, (unsigned)cnt);
+                if (kind == VSOM_CLR)
+                    hipLaunchKernelGGL(ensemble_bmu_many_kernel<VSOM_CLR>, grid, dim3(256), smem, ls, args);
+                else if (kind == VSOM_MEDIAN)
+                    hipLaunchKernelGGL(ensemble_bmu_many_kernel<VSOM_MEDIAN>, grid, dim3(256), smem, ls, args);
+                else
+                    hipLaunchKernelGGL(ensemble_bmu_many_kernel<VSOM_STANDARD>, grid, dim3(256), smem, ls, args);
+                hipError_t err = hipGetLastError();
+                if (err != hipSuccess)
+                    rc = vsom_fail(VSOM_ERR_HIP, std::string("ensemble_bmu_many_kernel: ") + hipGetErrorString(err));
+                else
+                    rc = ens_slot_done(e, ls);
+            }
+            if (rc)
+                break;
+        }
+    }
+    // the other members through vsom_bmu_batch, while the launches run
+    for (size_t k = 0; k < n && !rc; ++k)
+        if (e->grp[k] < 0 && e->m[k]->B > 0)
+            rc = vsom_bmu_batch(e->m[k], idx_out ? idx_out[k] : nullptr, dist_out ? dist_out[k] : nullptr);
+    // (also on an error: what was launched completes before the call returns)
+    if (ls)
+        VSOM_HIP_CHECK(hipStreamSynchronize(ls));
+    if (rc)
+        return rc;
+    for (size_t k = 0; k < n; ++k) {
+        if (e->grp[k] < 0)
+            continue;
+        const size_t b = e->m[k]->B;
+        if (idx_out && idx_out[k])
+            std::memcpy(idx_out[k], e->sc_idx.p + at[k], b * sizeof(uint64_t));
+        if (dist_out && dist_out[k])
+            std::memcpy(dist_out[k], e->sc_dist.p + at[k], b * sizeof(float));
+    }
     return VSOM_OK;
 }

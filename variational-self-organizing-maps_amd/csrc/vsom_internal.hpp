@@ -226,6 +226,8 @@ struct TimerScope {
 
 // kernel launchers (each enqueues on ctx->stream and returns a vsom_status) -------------------
 int launch_stage_chunk(vsom_ctx *c, const float *x_dev, size_t B);
+// the chunk buffers sized for B rows (vsom_capi.hip; synchronises and reallocates only when B exceeds the capacity)
+int ensure_chunk_capacity(vsom_ctx *c, size_t B);
 // the same kernels for the NEXT chunk on the copy stream, beside the running epoch (false: not possible now --
 // the caller stages at commit time instead)
 bool vsom_can_stage_ahead(const vsom_ctx *c, size_t B);
@@ -249,6 +251,7 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1);
 int ensure_lut(vsom_ctx *c, double sigma);
 // column compaction (vsom_compact.hip)
 bool vsom_cc_applies(const vsom_ctx *c);
+bool vsom_cc_considered(const vsom_ctx *c, size_t B);    // side-effect free: false = vsom_cc_begin does nothing for B rows
 int vsom_cc_begin(vsom_ctx *c, size_t B, bool *on);
 // live-column record + gathered rows (+ int8 images) of a chunk of B rows, on `stream`, into the given record
 int vsom_cc_stage(vsom_ctx *c, size_t B, hipStream_t stream, int *idx, int *inv, unsigned *meta, bool *xi_out);
