@@ -263,6 +263,20 @@ int vsom_bmu_restricted_batch(vsom_ctx *ctx, uint64_t min_hits, uint64_t *idx_ou
 /* Som::euclidianWeightedDist of EVERY node for chunk row `row` (input of findRestrictedBmd,
  * Som.cpp:457-487); dist_out_host[N]. */
 int vsom_distances_row(vsom_ctx *ctx, size_t row, float *dist_out_host);
+/* Som::findRestrictedBmd (Som.cpp:457-487) for chunk rows [r0, r1), and optionally one draw per row.
+ * Read-only: lastBMU, sqres, bmuHits and the map are not touched.
+ * norm_out[r1-r0]      C of each row (may be NULL)
+ * prob_out[(r1-r0)*N]  row-major p_i / C, what findRestrictedBmd returns for that row (may be NULL)
+ * u_host[r1-r0]        one uniform in [0,1) per row; required iff draw_out != NULL
+ * draw_out[r1-r0]      drawn node per row, UINT64_MAX when the row has no mass (may be NULL)
+ * p_i = bmuHits[i] >= min_hits ? exp(-(double)d_i * d_i / 2) : 0 with d_i the fp32 distance of vsom_distances_row
+ * (node 0 is not exempt), C = ((0 + p_0) + p_1) + ... in node order, in double.  The draw is the smallest i whose
+ * running sum exceeds u * C -- the largest i with p_i > 0 when rounding leaves none; no draw when C is 0 or not
+ * finite.  exp runs on the device (within an ulp of libm's).  Refuses (VSOM_ERR_INVALID, nothing enqueued) custom
+ * contexts, no chunk, a bad row range, draws without uniforms, a uniform that is NaN or outside [0,1), a chunk staged
+ * ahead.  Device scratch: p of at most max(1, 256 MiB / (8 N)) rows at a time. */
+int vsom_bmd_batch(vsom_ctx *ctx, uint64_t min_hits, size_t r0, size_t r1, const double *u_host,
+                   uint64_t *draw_out, double *norm_out, double *prob_out);
 /* Som::euclidianWeightedDistRaw(pos, v, ones, ones) (Som.cpp:143-157) for `count` pairs; v is
  * chunk row vrows[i] (from_map = 0) or model vector vrows[i] (from_map = 1, the U-matrix case). */
 int vsom_distances_raw(vsom_ctx *ctx, const uint64_t *nodes_host, const uint64_t *vrows_host,

@@ -33,7 +33,7 @@ SYMBOLS = [
     "vsom_get_state", "vsom_upload_chunk", "vsom_set_chunk_device", "vsom_host_alloc", "vsom_host_free",
     "vsom_prefetch_chunk", "vsom_prefetch_wait", "vsom_commit_chunk", "vsom_stage_next_device", "vsom_get_last_bmu",
     "vsom_set_last_bmu", "vsom_get_sqres", "vsom_bmu_batch", "vsom_find_bmu", "vsom_dist_single", "vsom_find_local_bmu", "vsom_find_restricted_bmu", "vsom_distances_single", "vsom_bmu_local_batch",
-    "vsom_distances", "vsom_bmu_restricted_batch", "vsom_distances_row", "vsom_distances_raw", "vsom_batch_phase1_async", "vsom_batch_finish_async",
+    "vsom_distances", "vsom_bmu_restricted_batch", "vsom_distances_row", "vsom_distances_raw", "vsom_bmd_batch", "vsom_batch_phase1_async", "vsom_batch_finish_async",
     "vsom_batch_phase2_async", "vsom_batch_epoch_async", "vsom_batch_epoch", "vsom_get_mse",
     "vsom_residual_len", "vsom_train_single", "vsom_train_online_chunk", "vsom_train_online_chunk_acc", "vsom_train_online_chunk_fetch", "vsom_upload_chunk_async", "vsom_get_online_search_stats",
     "vsom_neighbourhood_weight", "vsom_device_ptr", "vsom_chunk_size", "vsom_pitch",
@@ -153,6 +153,8 @@ def lib():
     L.vsom_distances.argtypes = [vp, u64p, u64p, C.c_size_t, fp]
     L.vsom_bmu_restricted_batch.argtypes = [vp, C.c_uint64, u64p, fp]
     L.vsom_distances_row.argtypes = [vp, C.c_size_t, fp]
+    dp = C.POINTER(C.c_double)
+    L.vsom_bmd_batch.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t, dp, u64p, dp, dp]
     L.vsom_distances_raw.argtypes = [vp, u64p, u64p, C.c_size_t, C.c_int, fp]
     L.vsom_batch_phase1_async.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int]
     L.vsom_batch_finish_async.argtypes = [vp]
@@ -476,6 +478,27 @@ class Context:
         idx, dist = np.empty(B, np.uint64), np.empty(B, np.float32)
         check(lib().vsom_bmu_restricted_batch(self._h, int(min_hits), _u(idx), _f(dist)))
         return idx, dist
+
+    def restricted_bmd(self, min_hits, r0=0, r1=None, u=None, probs=False):
+        """Som::findRestrictedBmd of chunk rows [r0, r1) in one call (vsom_bmd_batch): {"norm": C per row (float64),
+        "draw": the node drawn with uniform u[r] per row (uint64, UINT64_MAX = no mass; None without u), "prob":
+        float64[rows, N] (None unless probs)}.  Reads nothing but the map, the hits and the staged rows."""
+        r1 = self.chunk_size if r1 is None else int(r1)
+        n = max(r1 - int(r0), 0)
+        norm = np.empty(n, np.float64)
+        draw = prob = None
+        up = None
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=np.float64)
+            assert u.shape == (n,), (u.shape, n)
+            up = u.ctypes.data_as(C.POINTER(C.c_double))
+            draw = np.empty(n, np.uint64)
+        if probs:
+            prob = np.empty((n, self.n_nodes), np.float64)
+        dp = C.POINTER(C.c_double)
+        check(lib().vsom_bmd_batch(self._h, int(min_hits), int(r0), r1, up, _u(draw), norm.ctypes.data_as(dp),
+                                   None if prob is None else prob.ctypes.data_as(dp)))
+        return {"norm": norm, "draw": draw, "prob": prob}
 
     def distances_row(self, row):
         out = np.empty(self.n_nodes, np.float32)

@@ -806,6 +806,24 @@ int vsom_bmu_restricted_batch(vsom_ctx *c, uint64_t min_hits, uint64_t *idx_out_
     return copy_search_results(c, idx_out_host, dist_out_host);
 }
 
+int vsom_bmd_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t r1, const double *u_host, uint64_t *draw_out,
+                   double *norm_out, double *prob_out)
+{
+    CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_bmd_batch");
+    CHECK_ROWS(c);
+    if (c->B == 0)
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    if (r0 > r1 || r1 > c->B)
+        return vsom_fail(VSOM_ERR_INVALID, "row range out of bounds");
+    if (draw_out && !u_host)
+        return vsom_fail(VSOM_ERR_INVALID, "draws need one uniform per row");
+    for (size_t i = 0; u_host && i < r1 - r0; ++i)
+        if (!(u_host[i] >= 0.0 && u_host[i] < 1.0))
+            return vsom_fail(VSOM_ERR_INVALID, "uniform " + std::to_string(i) + " is not in [0,1)");
+    return launch_bmd(c, min_hits, r0, r1, u_host, draw_out, norm_out, prob_out);
+}
+
 int vsom_distances_row(vsom_ctx *c, size_t row, float *dist_out_host)
 {
     CHECK_CTX(c);

@@ -184,6 +184,10 @@ struct vsom_ctx {
     PinnedBuf<u64> out_pinned;      // [8192]: vsom_get_last_bmu of short chunks
     // device scratch of the distance queries (vsom_distances / _row / _raw): grow-only, bytes
     DevBuf<unsigned char> q_scratch;
+    // vsom_bmd_batch (vsom_bmd.hip): p of a row slice (node-major), the running sums at chunk boundaries, the slice's
+    // uniforms and norms, its draws, and one copy-out piece of the row-major probabilities; one set, grow-only
+    DevBuf<double> bmd_p, bmd_cum, bmd_vec, bmd_prob;
+    DevBuf<u64> bmd_draw;
 
     // timing
     uint32_t timing = 0;            // bit (1u << VSOM_T_*): that kernel group is timed with HIP events
@@ -245,6 +249,9 @@ int launch_finish(vsom_ctx *c);
 int vsom_join_aux(vsom_ctx *c);      // make ctx->stream wait for the side stream's pending work
 int launch_bmu_restricted(vsom_ctx *c, u64 min_hits);
 int launch_row_dist(vsom_ctx *c, size_t row, float *out_dev);
+// vsom_bmd.hip: findRestrictedBmd + draws for chunk rows [r0,r1) (arguments checked by vsom_bmd_batch); synchronises
+int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_host, uint64_t *draw_out, double *norm_out,
+               double *prob_out);
 int launch_raw_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *vrows_dev, size_t count, int from_map,
                     float *out_dev);
 int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1);

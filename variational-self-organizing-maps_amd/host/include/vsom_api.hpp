@@ -465,6 +465,11 @@ public:
                                const Eigen::VectorXf &weights) const;
     std::vector<double> findRestrictedBmd(const Eigen::VectorXf &v, const Eigen::VectorXf &valid, size_t minBmuHits,
                                           const Eigen::VectorXf &weights) const;
+    // [MI355X build] extension: one model vector per row of `data`, drawn from the row's findRestrictedBmd distribution
+    // with the caller's uniform u[r] in [0,1) (one vsom_bmd_batch call; UINT64_MAX where the row has no mass);
+    // *norm (if given) receives every row's normalising mass C.  Built-in transformations on the device only.
+    std::vector<uint64_t> drawModelVectors(const DataSet *data, size_t minBmuHits, const std::vector<double> &u,
+                                           std::vector<double> *norm = nullptr) const;
     double euclidianWeightedDistRaw(const size_t &pos, const Eigen::VectorXf &v, const Eigen::VectorXf &valid,
                                     const Eigen::VectorXf &weights) const;
     void updateUMatrix(const Eigen::VectorXf &weights);

@@ -1502,13 +1502,26 @@ int Som::measureSimilarity(const DataSet *data, int numOfSigmas, size_t minBmuHi
     return success;
 }
 
-// Som.cpp:525-566: draws a model vector from the restricted distribution of each sample; returns the
-// draw of the LAST sample (as the reference does).  Non-deterministic (std::random_device).
+// Som.cpp:525-566: draws a model vector from the restricted distribution of each sample and returns the draw of the
+// LAST sample; the other draws have no effect.  Built-in transformations: the last row alone, one uniform from the
+// generator the reference builds, one vsom_bmd_batch call; a row without mass gives 0, what libstdc++'s
+// discrete_distribution returns for its all-NaN weights.  Non-deterministic (std::random_device).
 size_t Som::variationalAutoEncoder(const DataSet *data, size_t minBmuHits) const
 {
     std::random_device rd;
     std::mt19937 gen(rd());
     size_t modelVector{0};
+    if (ctx && transform.kind() != vsom::Custom) {
+        const size_t n = data->size();
+        if (n == 0)
+            return modelVector;
+        const double u = std::generate_canonical<double, 53>(gen);
+        uint64_t drawn = 0;
+        joinGroup();
+        check(vsom_upload_chunk(ctx, data->contiguous() + (n - 1) * inLen, 1), "vsom_upload_chunk");
+        check(vsom_bmd_batch(ctx, minBmuHits, 0, 1, &u, &drawn, nullptr, nullptr), "vsom_bmd_batch");
+        return drawn == UINT64_MAX ? 0 : (size_t)drawn;
+    }
     for (size_t i = 0; i < data->size(); ++i) {
         Eigen::VectorXf v = data->getData(i);
         Eigen::VectorXf val = data->getValidity(i).cast<float>();
@@ -1517,6 +1530,25 @@ size_t Som::variationalAutoEncoder(const DataSet *data, size_t minBmuHits) const
         modelVector = d(gen);
     }
     return modelVector;
+}
+
+std::vector<uint64_t> Som::drawModelVectors(const DataSet *data, size_t minBmuHits, const std::vector<double> &u,
+                                            std::vector<double> *norm) const
+{
+    requireDevicePath("drawModelVectors");
+    const size_t n = data->size();
+    if (u.size() != n)
+        throw std::invalid_argument("drawModelVectors: one uniform per row");
+    std::vector<uint64_t> drawn(n);
+    if (norm)
+        norm->assign(n, 0.0);
+    if (n == 0)
+        return drawn;
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data->contiguous(), n), "vsom_upload_chunk");
+    check(vsom_bmd_batch(ctx, minBmuHits, 0, n, u.data(), drawn.data(), norm ? norm->data() : nullptr, nullptr),
+          "vsom_bmd_batch");
+    return drawn;
 }
 
 // Som.cpp:568-623: prints a logit-approximated normal sample per feature around a drawn model vector

@@ -269,6 +269,35 @@ class Som:
         self._stage_one(v)
         return float(self.ctx.distances([self._node(pos)], [0])[0])
 
+    # ---- restricted best matching distribution (Som.cpp:457-487, 525-566) -------------------
+    @staticmethod
+    def _rows(data):
+        """the loaded rows of a DataSet (DataSet::getData(i), i < size()), or a 2-D array as it is"""
+        return data.data if hasattr(data, "data") else np.ascontiguousarray(data, dtype=np.float32)
+
+    def findRestrictedBmd(self, v, valid=None, minBmuHits=0, weights=None):
+        """Som::findRestrictedBmd: float64[N], p_i / C with p_i = exp(-d_i^2 / 2) on the nodes with at least
+        minBmuHits hits (0 elsewhere)"""
+        self._stage_one(v)
+        return self.ctx.restricted_bmd(minBmuHits, 0, 1, probs=True)["prob"][0]
+
+    def drawModelVectors(self, data, minBmuHits, u):
+        """extension: one node per loaded row of `data`, drawn from its restricted distribution with the caller's
+        uniform u[r] in [0, 1) (uint64; UINT64_MAX where the row has no mass)"""
+        X = self._rows(data)
+        self.ctx.upload_chunk(X)
+        return self.ctx.restricted_bmd(minBmuHits, u=u)["draw"]
+
+    def variationalAutoEncoder(self, data, minBmuHits, seed=None):
+        """Som::variationalAutoEncoder: the node drawn for the LAST loaded row (the reference's other draws have no
+        effect); 0 when that row has no mass, as the reference's discrete_distribution returns then"""
+        X = self._rows(data)
+        if X.shape[0] == 0:
+            return 0
+        u = np.random.default_rng(seed).random(1)
+        d = int(self.drawModelVectors(X[-1:], minBmuHits, u)[0])
+        return 0 if d == 0xFFFFFFFFFFFFFFFF else d
+
     # ---- batch training (Som.cpp:716-879) --------------------------------------------------
     def trainBatchSomEpoch(self, dataset, currentSigma, isFirst):
         self.ctx.upload_chunk(dataset.data)
