@@ -277,6 +277,18 @@ int vsom_distances_row(vsom_ctx *ctx, size_t row, float *dist_out_host);
  * ahead.  Device scratch: p of at most max(1, 256 MiB / (8 N)) rows at a time. */
 int vsom_bmd_batch(vsom_ctx *ctx, uint64_t min_hits, size_t r0, size_t r1, const double *u_host,
                    uint64_t *draw_out, double *norm_out, double *prob_out);
+/* The k best matching units of chunk rows [r0, r1): the runner-up for the topographic error, k-nearest-node queries.
+ * idx_out[(r1-r0)*k]   row-major, required
+ * dist_out[(r1-r0)*k]  d of each idx_out entry, bit for bit (may be NULL)
+ * d_i is the fp32 distance of vsom_distances_row; nodes are ordered by the key (d_i, i) with NaN after +inf, so ties go
+ * to the lower index.  Every node is a candidate (bit-identical model rows each appear, in index order).  Entry 0 is
+ * findBmu's BMU, the node vsom_bmu_batch returns (Som.cpp:291-309): node 0 with a NaN distance when d_0 is NaN; entries
+ * 1..k-1 are the other nodes in ascending key order (when d_0 is not NaN the row is the k smallest keys).  A NaN distance
+ * is stored as the quiet NaN 0x7FC00000, as vsom_bmu_batch's sqres.  Read-only: the map, sigma, bmuHits, lastBMU and
+ * sqres are not touched.  Refuses (VSOM_ERR_INVALID, nothing enqueued) custom contexts, no chunk, a bad row range,
+ * k = 0, k > 64, k > N, a null idx_out, a chunk staged ahead; an empty range returns VSOM_OK.  Device scratch: at most
+ * 64 node groups of k keys for a slice of at most 64 MiB / (512 k) rows at a time. */
+int vsom_bmu_topk_batch(vsom_ctx *ctx, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out, float *dist_out);
 /* Som::euclidianWeightedDistRaw(pos, v, ones, ones) (Som.cpp:143-157) for `count` pairs; v is
  * chunk row vrows[i] (from_map = 0) or model vector vrows[i] (from_map = 1, the U-matrix case). */
 int vsom_distances_raw(vsom_ctx *ctx, const uint64_t *nodes_host, const uint64_t *vrows_host,

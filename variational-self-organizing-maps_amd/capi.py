@@ -33,7 +33,7 @@ SYMBOLS = [
     "vsom_get_state", "vsom_upload_chunk", "vsom_set_chunk_device", "vsom_host_alloc", "vsom_host_free",
     "vsom_prefetch_chunk", "vsom_prefetch_wait", "vsom_commit_chunk", "vsom_stage_next_device", "vsom_get_last_bmu",
     "vsom_set_last_bmu", "vsom_get_sqres", "vsom_bmu_batch", "vsom_find_bmu", "vsom_dist_single", "vsom_find_local_bmu", "vsom_find_restricted_bmu", "vsom_distances_single", "vsom_bmu_local_batch",
-    "vsom_distances", "vsom_bmu_restricted_batch", "vsom_distances_row", "vsom_distances_raw", "vsom_bmd_batch", "vsom_batch_phase1_async", "vsom_batch_finish_async",
+    "vsom_distances", "vsom_bmu_restricted_batch", "vsom_distances_row", "vsom_distances_raw", "vsom_bmd_batch", "vsom_bmu_topk_batch", "vsom_batch_phase1_async", "vsom_batch_finish_async",
     "vsom_batch_phase2_async", "vsom_batch_epoch_async", "vsom_batch_epoch", "vsom_get_mse",
     "vsom_residual_len", "vsom_train_single", "vsom_train_online_chunk", "vsom_train_online_chunk_acc", "vsom_train_online_chunk_fetch", "vsom_upload_chunk_async", "vsom_get_online_search_stats",
     "vsom_neighbourhood_weight", "vsom_device_ptr", "vsom_chunk_size", "vsom_pitch",
@@ -155,6 +155,7 @@ def lib():
     L.vsom_distances_row.argtypes = [vp, C.c_size_t, fp]
     dp = C.POINTER(C.c_double)
     L.vsom_bmd_batch.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t, dp, u64p, dp, dp]
+    L.vsom_bmu_topk_batch.argtypes = [vp, C.c_uint32, C.c_size_t, C.c_size_t, u64p, fp]
     L.vsom_distances_raw.argtypes = [vp, u64p, u64p, C.c_size_t, C.c_int, fp]
     L.vsom_batch_phase1_async.argtypes = [vp, C.c_size_t, C.c_size_t, C.c_int]
     L.vsom_batch_finish_async.argtypes = [vp]
@@ -499,6 +500,24 @@ class Context:
         check(lib().vsom_bmd_batch(self._h, int(min_hits), int(r0), r1, up, _u(draw), norm.ctypes.data_as(dp),
                                    None if prob is None else prob.ctypes.data_as(dp)))
         return {"norm": norm, "draw": draw, "prob": prob}
+
+    def bmu_topk(self, k, r0=0, r1=None, dist=True):
+        """The k best matching units of chunk rows [r0, r1) in one call (vsom_bmu_topk_batch): (idx uint64[n, k],
+        dist float32[n, k] or None).  Entry 0 is vsom_bmu_batch's BMU; the others follow in (distance, index) order.
+        Read-only."""
+        k = int(k)
+        B = self.chunk_size
+        r0 = int(r0)
+        r1 = B if r1 is None else int(r1)
+        if not 1 <= k <= min(64, self.n_nodes):
+            raise ValueError(f"k = {k} is not in [1, min(64, N = {self.n_nodes})]")
+        if r0 < 0 or r0 > r1 or r1 > B:
+            raise ValueError(f"row range [{r0}, {r1}) is not within the chunk's {B} rows")
+        n = r1 - r0
+        idx = np.empty((n, k), np.uint64)
+        d = np.empty((n, k), np.float32) if dist else None
+        check(lib().vsom_bmu_topk_batch(self._h, k, r0, r1, _u(idx), None if d is None else _f(d)))
+        return idx, d
 
     def distances_row(self, row):
         out = np.empty(self.n_nodes, np.float32)

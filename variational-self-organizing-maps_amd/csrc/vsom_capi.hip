@@ -824,6 +824,22 @@ int vsom_bmd_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t r1, const d
     return launch_bmd(c, min_hits, r0, r1, u_host, draw_out, norm_out, prob_out);
 }
 
+int vsom_bmu_topk_batch(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out, float *dist_out)
+{
+    CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_bmu_topk_batch");
+    CHECK_ROWS(c);
+    if (c->B == 0)
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    if (r0 > r1 || r1 > c->B)
+        return vsom_fail(VSOM_ERR_INVALID, "row range out of bounds");
+    if (k == 0 || k > 64 || k > c->N)
+        return vsom_fail(VSOM_ERR_INVALID, "k must be in [1, min(64, N)]");
+    if (!idx_out)
+        return vsom_fail(VSOM_ERR_INVALID, "idx_out is null");
+    return launch_topk(c, k, r0, r1, idx_out, dist_out);
+}
+
 int vsom_distances_row(vsom_ctx *c, size_t row, float *dist_out_host)
 {
     CHECK_CTX(c);

@@ -188,6 +188,11 @@ struct vsom_ctx {
     // uniforms and norms, its draws, and one copy-out piece of the row-major probabilities; one set, grow-only
     DevBuf<double> bmd_p, bmd_cum, bmd_vec, bmd_prob;
     DevBuf<u64> bmd_draw;
+    // vsom_bmu_topk_batch (vsom_topk.hip): every node group's k keys per row of a slice, the slice's idx / dist and its
+    // node-0 NaN flags; one set, grow-only
+    DevBuf<u64> topk_part, topk_idx;
+    DevBuf<float> topk_dist;
+    DevBuf<unsigned char> topk_nan0;
 
     // timing
     uint32_t timing = 0;            // bit (1u << VSOM_T_*): that kernel group is timed with HIP events
@@ -252,6 +257,8 @@ int launch_row_dist(vsom_ctx *c, size_t row, float *out_dev);
 // vsom_bmd.hip: findRestrictedBmd + draws for chunk rows [r0,r1) (arguments checked by vsom_bmd_batch); synchronises
 int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_host, uint64_t *draw_out, double *norm_out,
                double *prob_out);
+// vsom_topk.hip: the k best matching units of chunk rows [r0,r1) (arguments checked by vsom_bmu_topk_batch); synchronises
+int launch_topk(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out, float *dist_out);
 int launch_raw_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *vrows_dev, size_t count, int from_map,
                     float *out_dev);
 int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1);

@@ -470,6 +470,14 @@ public:
     // *norm (if given) receives every row's normalising mass C.  Built-in transformations on the device only.
     std::vector<uint64_t> drawModelVectors(const DataSet *data, size_t minBmuHits, const std::vector<double> &u,
                                            std::vector<double> *norm = nullptr) const;
+    // [MI355X build] extension: the k best matching units of every row of `data`, row-major (rows x k; one
+    // vsom_bmu_topk_batch call): entry 0 is findBmu's BMU, the others follow in (distance, index) order; *dist (if given)
+    // receives their distances.  1 <= k <= min(64, N).  Built-in transformations on the device only.
+    std::vector<uint64_t> findBestMatchingUnits(const DataSet *data, size_t k, std::vector<float> *dist = nullptr) const;
+    // [MI355X build] extension: the fraction of rows of `data` whose best and second-best units are not grid neighbours
+    // (node n at row n / width, column n % width; an error when max(|d row|, |d column|) != 1, no wrap); the count is
+    // summed in row order in double and divided by the row count (0 for no rows).  N >= 2.
+    double topographicError(const DataSet *data) const;
     double euclidianWeightedDistRaw(const size_t &pos, const Eigen::VectorXf &v, const Eigen::VectorXf &valid,
                                     const Eigen::VectorXf &weights) const;
     void updateUMatrix(const Eigen::VectorXf &weights);

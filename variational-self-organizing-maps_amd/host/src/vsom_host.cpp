@@ -1551,6 +1551,41 @@ std::vector<uint64_t> Som::drawModelVectors(const DataSet *data, size_t minBmuHi
     return drawn;
 }
 
+std::vector<uint64_t> Som::findBestMatchingUnits(const DataSet *data, size_t k, std::vector<float> *dist) const
+{
+    requireDevicePath("findBestMatchingUnits");
+    if (k == 0 || k > 64 || k > width * height)
+        throw std::invalid_argument("findBestMatchingUnits: k must be in [1, min(64, N)]");
+    const size_t n = data->size();
+    std::vector<uint64_t> idx(n * k);
+    if (dist)
+        dist->assign(n * k, 0.0f);
+    if (n == 0)
+        return idx;
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data->contiguous(), n), "vsom_upload_chunk");
+    check(vsom_bmu_topk_batch(ctx, (uint32_t)k, 0, n, idx.data(), dist ? dist->data() : nullptr), "vsom_bmu_topk_batch");
+    return idx;
+}
+
+double Som::topographicError(const DataSet *data) const
+{
+    if (width * height < 2)
+        throw std::invalid_argument("topographicError: the map needs at least 2 nodes");
+    const std::vector<uint64_t> idx = findBestMatchingUnits(data, 2);
+    const size_t n = idx.size() / 2;
+    if (n == 0)
+        return 0.0;
+    const long long w = (long long)width;
+    double count = 0.0;
+    for (size_t r = 0; r < n; ++r) {
+        const long long a = (long long)idx[2 * r], b = (long long)idx[2 * r + 1];
+        const long long dr = std::llabs(a / w - b / w), dc = std::llabs(a % w - b % w);
+        count += (dr > dc ? dr : dc) != 1 ? 1.0 : 0.0;
+    }
+    return count / (double)n;
+}
+
 // Som.cpp:568-623: prints a logit-approximated normal sample per feature around a drawn model vector
 int Som::autoEncoder(const DataSet *data, size_t minBmuHits) const
 {

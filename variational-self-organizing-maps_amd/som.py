@@ -16,6 +16,27 @@ import numpy as np
 from . import capi
 
 
+def topographic_error(idx2, width):
+    """Topographic error of best / second-best unit pairs idx2 (n x >= 2; columns 0 and 1 are used) on a map `width`
+    nodes wide: node n sits at grid row n // width, column n % width (the storage layout updateUMatrix walks), and a row
+    counts as an error when max(|d row|, |d column|) != 1 between its two units -- no wrap.  The count over n, summed in
+    row order in double; 0.0 for n = 0."""
+    idx2 = np.asarray(idx2)
+    width = int(width)
+    n = idx2.shape[0] if idx2.ndim else 0
+    if n == 0:
+        return 0.0
+    if idx2.ndim != 2 or idx2.shape[1] < 2:
+        raise ValueError("idx2 must be n x k with k >= 2")
+    a = idx2[:, 0].astype(np.int64)
+    b = idx2[:, 1].astype(np.int64)
+    cheb = np.maximum(np.abs(a // width - b // width), np.abs(a % width - b % width))
+    te = 0.0
+    for e in (cheb != 1):
+        te += 1.0 if e else 0.0
+    return te / n
+
+
 class WeigthDecayFunction(enum.IntEnum):      # SOM.hpp:70-75 (spelling as in the reference)
     Exponential = 0
     InverseProportional = 1
@@ -297,6 +318,24 @@ class Som:
         u = np.random.default_rng(seed).random(1)
         d = int(self.drawModelVectors(X[-1:], minBmuHits, u)[0])
         return 0 if d == 0xFFFFFFFFFFFFFFFF else d
+
+    # ---- k best matching units, topographic error (extensions) ---------------------------------
+    def findBestMatchingUnits(self, data, k, dist=False):
+        """extension: the k best matching units of every loaded row of `data` (uint64[rows, k]; entry 0 is findBmu's
+        BMU, the others follow in (distance, index) order); with dist=True also their distances (float32[rows, k])"""
+        X = self._rows(data)
+        self.ctx.upload_chunk(X)
+        if X.shape[0] == 0:
+            return (np.zeros((0, int(k)), np.uint64), np.zeros((0, int(k)), np.float32)) if dist else \
+                np.zeros((0, int(k)), np.uint64)
+        idx, d = self.ctx.bmu_topk(k, dist=dist)
+        return (idx, d) if dist else idx
+
+    def topographicError(self, data):
+        """extension: the fraction of loaded rows of `data` whose best and second-best units are not grid neighbours"""
+        if self.width * self.height < 2:
+            raise ValueError("the topographic error needs a map of at least 2 nodes")
+        return topographic_error(self.findBestMatchingUnits(data, 2), self.width)
 
     # ---- batch training (Som.cpp:716-879) --------------------------------------------------
     def trainBatchSomEpoch(self, dataset, currentSigma, isFirst):
