@@ -102,7 +102,8 @@ typedef enum vsom_buffer {
     VSOM_BUF_HITS = 4,     /* uint64  [N]                                       */
     VSOM_BUF_LASTBMU = 5,  /* uint64  [chunk capacity]                          */
     VSOM_BUF_SQRES = 6,    /* float   [chunk capacity]  ||Comparer(x,M[bmu])||^2 */
-    VSOM_BUF_CHUNK = 7     /* float   [B][J] staged samples                     */
+    VSOM_BUF_CHUNK = 7,    /* float   [B][J] staged samples                     */
+    VSOM_BUF_UMATRIX = 8   /* double  [N] of the last vsom_umatrix (NULL before the first) */
 } vsom_buffer;
 
 typedef enum vsom_timer {
@@ -293,6 +294,19 @@ int vsom_bmu_topk_batch(vsom_ctx *ctx, uint32_t k, size_t r0, size_t r1, uint64_
  * chunk row vrows[i] (from_map = 0) or model vector vrows[i] (from_map = 1, the U-matrix case). */
 int vsom_distances_raw(vsom_ctx *ctx, const uint64_t *nodes_host, const uint64_t *vrows_host,
                        size_t count, int from_map, float *dist_out_host);
+/* Som::updateUMatrix (Som.cpp:999-1111) of the context's current map and sigmaMap, on the context's stream: one stencil
+ * launch, nothing uploaded.  U[n] = the mean of euclidianWeightedDistRaw(n, map[m]) (the fp32 distance of
+ * vsom_distances_raw with from_map = 1) over the 3 / 5 / 8 in-grid neighbours m of node n, diagonals weighted 0.3,
+ * combined in double in the reference's order of additions.
+ * u_out_host[N] doubles; NULL: only enqueue (no wait) -- the result stays in the context's device buffer
+ * (VSOM_BUF_UMATRIX) and vsom_get_umatrix returns it later (the precedent is vsom_train_online_chunk / vsom_get_mse).
+ * vsom_get_umatrix synchronises and returns the matrix of the state at the time of the last vsom_umatrix call (stream
+ * order), not of later state.  Read-only: map, sigma, S, weight, bmuHits, lastBMU, sqres and the chunk are untouched; no
+ * chunk is needed, and a chunk staged ahead does not matter.  Refuses (VSOM_ERR_INVALID, nothing enqueued, the context
+ * stays usable): a null context, custom contexts, width < 2 or height < 2 (the reference indexes outside the map there),
+ * vsom_get_umatrix before any vsom_umatrix on that context, a null u_out_host of vsom_get_umatrix. */
+int vsom_umatrix(vsom_ctx *ctx, double *u_out_host);
+int vsom_get_umatrix(vsom_ctx *ctx, double *u_out_host);
 
 /* ---- batch epoch: Som::trainBatchSomEpoch (Som.cpp:756-879) ----------------------------
  * phase 1 (:762-806) over samples [s0,s1): BMU (findBmu when is_first else findLocalBmu)
@@ -388,6 +402,13 @@ int vsom_ensemble_upload_chunks(vsom_ensemble *e, const float *x_host, size_t n_
  * call.  idx_out / dist_out: NULL, or one pointer per member (NULL or room for that member's B values).  Refuses like
  * the train calls: a member without a chunk, a member whose next chunk is staged ahead over its rows. */
 int vsom_ensemble_bmu_batch(vsom_ensemble *e, uint64_t *const *idx_out, float *const *dist_out);
+/* Som::updateUMatrix of every member: per member exactly what vsom_umatrix gives (also in the member's VSOM_BUF_UMATRIX
+ * buffer: a later vsom_get_umatrix of the member returns it).  u_out: NULL, or one pointer per member (NULL entries
+ * skipped, else room for that member's N doubles).  Members whose map has N * part_len <= 4096 are computed by one launch
+ * per kind (plain / CLR), one workgroup per member; every other member runs vsom_umatrix in the same call.  The call waits
+ * before it returns.  Refuses (VSOM_ERR_INVALID): a null ensemble, or naming the first member that vsom_umatrix would
+ * refuse (a custom context, width < 2 or height < 2) -- before anything is enqueued for any member. */
+int vsom_ensemble_umatrix(vsom_ensemble *e, double *const *u_out);
 
 /* ---- multi-GPU batch epoch, one process, the GPUs of one node ------------------------
  * Som::trainBatchSomEpoch's two loops shard differently: phase 1 (Som.cpp:764-782 / 786-805) is

@@ -22,7 +22,7 @@ CUSTOM_MAX_DEPTH = 5120     # VSOM_CUSTOM_MAX_DEPTH
 EXPONENTIAL, INVERSE_PROPORTIONAL, BATCHMAP = 0, 1, 2
 BMU_AUTO, BMU_EXACT, BMU_SHORTLIST = 0, 1, 2
 UPDATE_STRICT, UPDATE_FMA, UPDATE_FMA_SIGMA = 0, 1, 2
-BUF_MAP, BUF_SIGMA, BUF_S, BUF_WEIGHT, BUF_HITS, BUF_LASTBMU, BUF_SQRES, BUF_CHUNK = range(8)
+BUF_MAP, BUF_SIGMA, BUF_S, BUF_WEIGHT, BUF_HITS, BUF_LASTBMU, BUF_SQRES, BUF_CHUNK, BUF_UMATRIX = range(9)
 T_STAGE, T_BMU, T_FINISH, T_CW, T_UPDATE, T_ONLINE, T_SIGMA, T_COUNT = range(8)
 TIMER_NAMES = ["stage", "bmu", "finish", "cw", "update", "online", "sigma"]
 
@@ -46,6 +46,7 @@ SYMBOLS = [
     "vsom_create_custom", "vsom_custom_compile_check",
     "vsom_ensemble_create", "vsom_ensemble_destroy", "vsom_ensemble_size", "vsom_ensemble_train_online_chunk_fetch",
     "vsom_ensemble_batch_epoch", "vsom_ensemble_upload_chunks", "vsom_ensemble_bmu_batch",
+    "vsom_umatrix", "vsom_get_umatrix", "vsom_ensemble_umatrix",
 ]
 
 
@@ -211,6 +212,9 @@ def lib():
     L.vsom_ensemble_batch_epoch.argtypes = [vp, C.POINTER(C.c_double), C.c_int, fp]
     L.vsom_ensemble_upload_chunks.argtypes = [vp, fp, C.c_size_t, C.POINTER(C.c_size_t), C.POINTER(C.c_size_t), C.c_int]
     L.vsom_ensemble_bmu_batch.argtypes = [vp, C.POINTER(u64p), C.POINTER(fp)]
+    L.vsom_umatrix.argtypes = [vp, dp]
+    L.vsom_get_umatrix.argtypes = [vp, dp]
+    L.vsom_ensemble_umatrix.argtypes = [vp, C.POINTER(dp)]
     _lib = L
     return L
 
@@ -531,6 +535,28 @@ class Context:
         check(lib().vsom_distances_raw(self._h, _u(nodes), _u(vrows), nodes.size, int(bool(from_map)), _f(out)))
         return out
 
+    def _umatrix_shape_check(self):
+        if self.width < 2 or self.height < 2:
+            raise ValueError(f"the U-matrix needs width >= 2 and height >= 2, not {self.width} x {self.height}")
+
+    def umatrix(self, fetch=True):
+        """Som::updateUMatrix of the current map and sigmaMap in one launch (vsom_umatrix): float64[N], or None with
+        fetch=False (only enqueued: get_umatrix() returns it later, as of the state at this call).  Read-only."""
+        self._umatrix_shape_check()
+        if not fetch:
+            check(lib().vsom_umatrix(self._h, None))
+            return None
+        out = np.empty(self.n_nodes, np.float64)
+        check(lib().vsom_umatrix(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
+    def get_umatrix(self):
+        """the matrix of the last umatrix() call (synchronises)"""
+        self._umatrix_shape_check()
+        out = np.empty(self.n_nodes, np.float64)
+        check(lib().vsom_get_umatrix(self._h, out.ctypes.data_as(C.POINTER(C.c_double))))
+        return out
+
     # ---- batch epoch ---------------------------------------------------
     def batch_phase1_async(self, s0, s1, is_first):
         check(lib().vsom_batch_phase1_async(self._h, int(s0), int(s1), int(bool(is_first))))
@@ -849,3 +875,16 @@ class Ensemble:
         dp = (C.POINTER(C.c_float) * n)(*[_f(a) for a in dist])
         check(lib().vsom_ensemble_bmu_batch(self._h, ip, dp))
         return idx, dist
+
+    def umatrix(self):
+        """Som::updateUMatrix of every member (vsom_ensemble_umatrix): a list of float64 arrays, one per member, each
+        what Context.umatrix() of that member gives"""
+        n = len(self.members)
+        for k, c in enumerate(self.members):
+            if c.width < 2 or c.height < 2:
+                raise ValueError(f"member {k}: the U-matrix needs width >= 2 and height >= 2, not {c.width} x {c.height}")
+        out = [np.empty(c.n_nodes, np.float64) for c in self.members]
+        dp = C.POINTER(C.c_double)
+        ptrs = (dp * max(n, 1))(*[a.ctypes.data_as(dp) for a in out])
+        check(lib().vsom_ensemble_umatrix(self._h, ptrs))
+        return out

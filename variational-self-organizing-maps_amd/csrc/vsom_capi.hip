@@ -887,6 +887,37 @@ int vsom_distances_raw(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *
     return VSOM_OK;
 }
 
+// Som::updateUMatrix (vsom_umatrix.hip).  No reader of the staged rows is enqueued, so rows_free_valid stays as it is and
+// a chunk staged ahead does not matter.
+int vsom_umatrix(vsom_ctx *c, double *u_out_host)
+{
+    CHECK_CTX_NOJOIN(c);
+    if (const char *why = vsom_umatrix_refusal(c))
+        return vsom_fail(VSOM_ERR_INVALID, why);
+    int rc = vsom_join_aux(c);
+    if (rc)
+        return rc;
+    if ((rc = launch_umatrix(c)))
+        return rc;
+    if (!u_out_host)
+        return VSOM_OK;
+    VSOM_HIP_CHECK(hipMemcpyAsync(u_out_host, c->umatrix.p, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VSOM_OK;
+}
+
+int vsom_get_umatrix(vsom_ctx *c, double *u_out_host)
+{
+    CHECK_CTX_NOJOIN(c);
+    if (!u_out_host)
+        return vsom_fail(VSOM_ERR_INVALID, "null output");
+    if (!c->um_valid)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_get_umatrix: no vsom_umatrix has run on this context");
+    VSOM_HIP_CHECK(hipMemcpyAsync(u_out_host, c->umatrix.p, (size_t)c->N * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VSOM_OK;
+}
+
 int vsom_batch_phase1_async(vsom_ctx *c, size_t s0, size_t s1, int is_first)
 {
     CHECK_CTX(c);
@@ -973,6 +1004,7 @@ void *vsom_device_ptr(vsom_ctx *c, int which)
     case VSOM_BUF_LASTBMU: return c->lastbmu.p;
     case VSOM_BUF_SQRES: return c->sqres.p;
     case VSOM_BUF_CHUNK: return c->Xs.p;
+    case VSOM_BUF_UMATRIX: return c->um_valid ? c->umatrix.p : nullptr;
     default: return nullptr;
     }
 }

@@ -45,6 +45,8 @@ struct vsom_ensemble {
     // scoring: idx / dist of every launched member, stored by the kernel (pinned host memory, grow-only)
     PinnedBuf<u64> sc_idx;
     PinnedBuf<float> sc_dist;
+    // U-matrices of the launched members, stored by the kernel (pinned host memory, grow-only)
+    PinnedBuf<double> um_out;
 };
 
 static int ens_fail(size_t k, const char *what)
@@ -729,5 +731,92 @@ int vsom_ensemble_bmu_batch(vsom_ensemble *e, uint64_t *const *idx_out, float *c
         if (dist_out && dist_out[k])
             std::memcpy(dist_out[k], e->sc_dist.p + at[k], b * sizeof(float));
     }
+    return VSOM_OK;
+}
+
+// Som::updateUMatrix of every member (vsom_umatrix.hip): members whose model and sigma rows fit LDS in one launch per kind
+// (plain / CLR), one workgroup per member, the results stored into each member's own buffer and into one pinned buffer
+// for all of them; every other member through vsom_umatrix.  Nothing here reads staged rows: rows_free_valid stays.
+int vsom_ensemble_umatrix(vsom_ensemble *e, double *const *u_out)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    const size_t n = e->m.size();
+    for (size_t k = 0; k < n; ++k)
+        if (const char *why = vsom_umatrix_refusal(e->m[k]))
+            return ens_fail(k, why);
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    for (vsom_ctx *c : e->m)
+        if (int rc = vsom_join_aux(c))
+            return rc;
+    const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);
+    e->grp.assign(n, -1);
+    std::vector<size_t> at(n, 0);
+    size_t total = 0;
+    bool any = false;
+    for (size_t k = 0; k < n; ++k) {
+        vsom_ctx *c = e->m[k];
+        if ((size_t)c->N * c->part_len > 4096 || vsom_umatrix_many_smem(c) > lds_cap)
+            continue;
+        if (int rc = vsom_umatrix_ensure(c))
+            return rc;
+        e->grp[k] = c->transform == VSOM_CLR ? 1 : 0;
+        any = true;
+        if (u_out && u_out[k]) {
+            at[k] = total;
+            total += c->N;
+        }
+    }
+    hipStream_t ls = nullptr;
+    std::vector<hipStream_t> streams;
+    int rc = VSOM_OK;
+    if (any) {
+        if (total > e->um_out.cap)             // (no kernel of an earlier call is running: every call ends in a wait)
+            VSOM_ALLOC_CHECK(vsom_grow(e->um_out, total, nullptr));
+        if ((rc = ens_launch_stream(e, &streams, &ls)))
+            return rc;
+        for (int kind = 0; kind < 2 && !rc; ++kind) {
+            std::vector<VsomUmDesc> d;
+            size_t smem = 0;
+            for (size_t k = 0; k < n; ++k) {
+                if (e->grp[k] != kind)
+                    continue;
+                vsom_ctx *c = e->m[k];
+                d.push_back({c->map.p, c->sigma.p, c->umatrix.p, (u_out && u_out[k]) ? e->um_out.p + at[k] : nullptr,
+                             (int)c->pitch, (int)c->D, (int)c->part_len, (int)c->part_pitch, (int)c->W, (int)c->H});
+                smem = std::max(smem, vsom_umatrix_many_smem(c));
+            }
+            if (d.empty())
+                continue;
+            const unsigned char *dev = nullptr;
+            if ((rc = ens_slot_put(e, d.data(), d.size(), sizeof(VsomUmDesc), ls, &dev)))
+                break;
+            if ((rc = vsom_umatrix_launch_many(kind, reinterpret_cast<const VsomUmDesc *>(dev), (unsigned)d.size(), smem, ls)))
+                break;
+            for (size_t k = 0; k < n; ++k)
+                if (e->grp[k] == kind)
+                    e->m[k]->um_valid = true;
+            rc = ens_slot_done(e, ls);
+        }
+    }
+    // the other members: every launch enqueued first, then the copies (or the wait)
+    for (size_t k = 0; k < n && !rc; ++k)
+        if (e->grp[k] < 0)
+            rc = vsom_umatrix(e->m[k], nullptr);
+    for (size_t k = 0; k < n && !rc; ++k)
+        if (e->grp[k] < 0) {
+            if (u_out && u_out[k])
+                rc = vsom_get_umatrix(e->m[k], u_out[k]);
+            else
+                rc = vsom_synchronize(e->m[k]);
+        }
+    // (also on an error: what was launched completes before the call returns)
+    if (ls)
+        VSOM_HIP_CHECK(hipStreamSynchronize(ls));
+    if (rc)
+        return rc;
+    for (size_t k = 0; k < n; ++k)
+        if (e->grp[k] >= 0 && u_out && u_out[k])
+            std::memcpy(u_out[k], e->um_out.p + at[k], (size_t)e->m[k]->N * sizeof(double));
     return VSOM_OK;
 }

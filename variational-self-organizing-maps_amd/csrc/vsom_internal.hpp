@@ -193,6 +193,9 @@ struct vsom_ctx {
     DevBuf<u64> topk_part, topk_idx;
     DevBuf<float> topk_dist;
     DevBuf<unsigned char> topk_nan0;
+    // vsom_umatrix (vsom_umatrix.hip): U[N] of the last call, allocated on first use
+    DevBuf<double> umatrix;
+    bool um_valid = false;          // a vsom_umatrix has been enqueued on this context
 
     // timing
     uint32_t timing = 0;            // bit (1u << VSOM_T_*): that kernel group is timed with HIP events
@@ -261,6 +264,19 @@ int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_
 int launch_topk(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out, float *dist_out);
 int launch_raw_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *vrows_dev, size_t count, int from_map,
                     float *out_dev);
+// vsom_umatrix.hip: Som::updateUMatrix of the current map / sigmaMap into ctx->umatrix; enqueues only.
+// refusal: why vsom_umatrix refuses this context, or null.
+const char *vsom_umatrix_refusal(const vsom_ctx *c);
+int vsom_umatrix_ensure(vsom_ctx *c);
+int launch_umatrix(vsom_ctx *c);
+// the one-workgroup-per-map form for ensembles (maps whose model and sigma rows fit LDS): descriptors, LDS need, launch
+struct VsomUmDesc {
+    const float *map, *sigma;
+    double *u, *out;         // the member's device buffer; its slice of the ensemble's pinned results or null
+    int ldm, D, P, ppitch, W, H;
+};
+size_t vsom_umatrix_many_smem(const vsom_ctx *c);
+int vsom_umatrix_launch_many(int clr, const VsomUmDesc *desc_dev, unsigned count, size_t smem, hipStream_t s);
 int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1);
 int ensure_lut(vsom_ctx *c, double sigma);
 // column compaction (vsom_compact.hip)

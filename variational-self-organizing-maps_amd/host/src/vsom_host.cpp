@@ -1340,7 +1340,13 @@ double Som::euclidianWeightedDistRaw(const size_t &pos, const Eigen::VectorXf &v
 void Som::updateUMatrix(const Eigen::VectorXf &)
 {
     if (ctx)
-        joinGroup();   // raw_dist_kernel reads sigma of every node: the deferred sigmaMap gather must have landed
+        joinGroup();   // the kernels read sigma of every node: the deferred sigmaMap gather must have landed
+    // built-in transformation on the device: one stencil launch, the combination included (csrc/vsom_umatrix.hip);
+    // host hooks, custom device contexts and maps narrower than 2 keep the pair-list route below
+    if (ctx && transform.kind() != vsom::Custom && width >= 2 && height >= 2) {
+        check(vsom_umatrix(ctx, uMatrix.data()), "vsom_umatrix");
+        return;
+    }
     // neighbour offsets in the order the reference adds them for an interior node (:1017-1024):
     // W, E, S(i+1), N(i-1), NW(i-1,j-1), SW(i+1,j-1), NE(i-1,j+1), SE(i+1,j+1)
     static const int DI[8] = {0, 0, 1, -1, -1, 1, -1, 1};

@@ -349,9 +349,13 @@ class Som:
     # ---- U-matrix (Som.cpp:143-157, 999-1111) -------------------------------------------------
     def updateUMatrix(self, weights=None):
         """Mean sigma-normalised raw distance of every node to its 3/5/8 neighbours, diagonals weighted 0.3;
-        the distances on the device (vsom_distances_raw), their combination in double on the host in the
-        reference's order of additions."""
+        one stencil launch on the device (vsom_umatrix).  Custom contexts and maps with width < 2 or height < 2 keep
+        the earlier route: the distances on the device (vsom_distances_raw), their combination in double on the host
+        in the reference's order of additions."""
         W, H = self.width, self.height
+        if W >= 2 and H >= 2 and self.ctx.transform != capi.CUSTOM:
+            self.uMatrix = self.ctx.umatrix()
+            return self.uMatrix
         DI = (0, 0, 1, -1, -1, 1, -1, 1)       # W, E, S(i+1), N(i-1), NW, SW, NE, SE  (:1017-1024)
         DJ = (-1, 1, 0, 0, -1, -1, 1, 1)
         nodes, nbrs, slot = [], [], {}
