@@ -109,7 +109,7 @@ typedef enum vsom_buffer {
 typedef enum vsom_timer {
     VSOM_T_STAGE = 0,      /* chunk re-layout kernels                           */
     VSOM_T_BMU = 1,        /* full / local BMU search kernels                   */
-    VSOM_T_FINISH = 2,     /* bmuHits + MSE                                     */
+    VSOM_T_FINISH = 2,     /* bmuHits + MSE; vsom_similarity_batch's scoring kernel */
     VSOM_T_CW = 3,         /* neighbourhood weight chain (w, w/W) kernel        */
     VSOM_T_UPDATE = 4,     /* mean / sigma^2 chain kernel                       */
     VSOM_T_ONLINE = 5,     /* online (trainSingle) kernels                      */
@@ -290,6 +290,52 @@ int vsom_bmd_batch(vsom_ctx *ctx, uint64_t min_hits, size_t r0, size_t r1, const
  * k = 0, k > 64, k > N, a null idx_out, a chunk staged ahead; an empty range returns VSOM_OK.  Device scratch: at most
  * 64 node groups of k keys for a slice of at most 64 MiB / (512 k) rows at a time. */
 int vsom_bmu_topk_batch(vsom_ctx *ctx, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out, float *dist_out);
+/* Som::measureSimilarity's per-record report (Som.cpp:631-714) for chunk rows [r0, r1): every row is searched and then
+ * scored against its best matching unit, column by column, in units of that unit's sigma -- one call, one stream wait.
+ * Search: b = Som::findRestrictedBmu(x_r, min_hits) for EVERY row of the chunk, exactly as vsom_bmu_restricted_batch (node 0
+ * seeds the search whatever its hits); it overwrites the chunk's lastBMU / sqres for the whole chunk like that call.  With
+ * min_hits = 0 every node qualifies, the search is findBmu's and takes vsom_bmu_batch's path (the shortlist included; every
+ * vsom_set_bmu_mode gives the same indices).
+ * Per column d < C = min(J, D), in fp32 with one rounding per operation and nothing contracted: m = map[b][d],
+ * s = sigmaMap[b][d], k = (float)num_sigmas,
+ *   sM    = s > 1e-5f ? 1e-5f : s   VSOM_SIGMA_AS_WRITTEN: the select of Som.cpp:658 as the reference wrote it, a cap (NaN stays)
+ *           s > 1e-5f ? s : 1e-5f   VSOM_SIGMA_FLOOR: the evident intent, a floor (a NaN sigma becomes 1e-5f)
+ *   delta = (x - m) / sM / k (:671),  lo = m - sM * k,  hi = m + sM * k (:675-677);
+ * column d of row r is valid iff valid_host == NULL or valid_host[(r - r0) * J + d] != 0.
+ * Outputs (host pointers, each may be NULL; entry r - r0 belongs to row r; lowest column on ties; columns d < C only):
+ *   bmu, dist          b and the stored sqres of the row, as the search calls return them (a NaN distance is 0x7FC00000)
+ *   dmax, dmax_col     the largest delta (signed) over the columns whose delta is not NaN; -inf, UINT32_MAX when none
+ *   first              delta of the lowest column with delta > -99999999.f; NaN (0x7FC00000) when none
+ *   amax, amax_col     the largest |delta| over the VALID columns whose delta is finite: the row's anomaly score and the
+ *                      column that causes it; 0, UINT32_MAX when none
+ *   outside            the number of valid columns with x < lo || x > hi (a NaN compares false, as in :702)
+ *   delta              dense report, delta[(r - r0) * C + d], NaN and +-inf replaced by 0 (:693)
+ * first and dmax carry the reference's running maximum (:684-690 compares the signed delta and stores its fabs): start at
+ * the first row whose `first` is not NaN with maxValue = |first|; for that row and every later one, dmax > maxValue makes
+ * maxValue = dmax and that row the reported one; measureSimilarity returns outside[reported row] == 0.
+ * Read-only apart from lastBMU / sqres: map, sigmaMap, S, weightMap, bmuHits and the chunk are untouched.  Refuses
+ * (VSOM_ERR_INVALID, nothing enqueued, the context stays usable): a null context or out, custom contexts, no chunk, a chunk
+ * staged ahead, r0 > r1 or r1 > B, an unknown sigma_rule.  An empty range returns VSOM_OK and enqueues nothing (no search).
+ * Device scratch: 36 bytes per row, the validity bytes when given, and for the dense report a slice of at most
+ * max(1, 64 MiB / (4 C)) rows at a time; without delta nothing of size rows x C is allocated.  delta and valid_host travel
+ * straight from / to the caller's memory, the per-row results through pinned memory of the context. */
+typedef enum vsom_sigma_rule {
+    VSOM_SIGMA_AS_WRITTEN = 0,
+    VSOM_SIGMA_FLOOR = 1
+} vsom_sigma_rule;
+typedef struct vsom_similarity_out {
+    uint64_t *bmu;
+    float *dist;
+    float *dmax;
+    uint32_t *dmax_col;
+    float *first;
+    float *amax;
+    uint32_t *amax_col;
+    uint32_t *outside;
+    float *delta;
+} vsom_similarity_out;
+int vsom_similarity_batch(vsom_ctx *ctx, uint64_t min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
+                          const uint8_t *valid_host, vsom_similarity_out *out);
 /* Som::euclidianWeightedDistRaw(pos, v, ones, ones) (Som.cpp:143-157) for `count` pairs; v is
  * chunk row vrows[i] (from_map = 0) or model vector vrows[i] (from_map = 1, the U-matrix case). */
 int vsom_distances_raw(vsom_ctx *ctx, const uint64_t *nodes_host, const uint64_t *vrows_host,

@@ -25,6 +25,7 @@ UPDATE_STRICT, UPDATE_FMA, UPDATE_FMA_SIGMA = 0, 1, 2
 BUF_MAP, BUF_SIGMA, BUF_S, BUF_WEIGHT, BUF_HITS, BUF_LASTBMU, BUF_SQRES, BUF_CHUNK, BUF_UMATRIX = range(9)
 T_STAGE, T_BMU, T_FINISH, T_CW, T_UPDATE, T_ONLINE, T_SIGMA, T_COUNT = range(8)
 TIMER_NAMES = ["stage", "bmu", "finish", "cw", "update", "online", "sigma"]
+SIGMA_AS_WRITTEN, SIGMA_FLOOR = 0, 1       # vsom_sigma_rule
 
 # every symbol include/vsom_hip.h declares (tests/test_capi_symbols.py checks the header too)
 SYMBOLS = [
@@ -46,8 +47,15 @@ SYMBOLS = [
     "vsom_create_custom", "vsom_custom_compile_check",
     "vsom_ensemble_create", "vsom_ensemble_destroy", "vsom_ensemble_size", "vsom_ensemble_train_online_chunk_fetch",
     "vsom_ensemble_batch_epoch", "vsom_ensemble_upload_chunks", "vsom_ensemble_bmu_batch",
-    "vsom_umatrix", "vsom_get_umatrix", "vsom_ensemble_umatrix",
+    "vsom_umatrix", "vsom_get_umatrix", "vsom_ensemble_umatrix", "vsom_similarity_batch",
 ]
+
+
+class SimilarityOut(C.Structure):
+    """vsom_similarity_out: host pointers, each may be NULL"""
+    _fields_ = [("bmu", C.POINTER(C.c_uint64)), ("dist", C.POINTER(C.c_float)), ("dmax", C.POINTER(C.c_float)),
+                ("dmax_col", C.POINTER(C.c_uint32)), ("first", C.POINTER(C.c_float)), ("amax", C.POINTER(C.c_float)),
+                ("amax_col", C.POINTER(C.c_uint32)), ("outside", C.POINTER(C.c_uint32)), ("delta", C.POINTER(C.c_float))]
 
 
 class VsomError(RuntimeError):
@@ -215,6 +223,9 @@ def lib():
     L.vsom_umatrix.argtypes = [vp, dp]
     L.vsom_get_umatrix.argtypes = [vp, dp]
     L.vsom_ensemble_umatrix.argtypes = [vp, C.POINTER(dp)]
+    if hasattr(L, "vsom_similarity_batch"):     # (VSOM_LIB may name an older build: tools/similarity_bench.py --route parent)
+        L.vsom_similarity_batch.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
+                                            C.POINTER(C.c_uint8), C.POINTER(SimilarityOut)]
     _lib = L
     return L
 
@@ -522,6 +533,42 @@ class Context:
         d = np.empty((n, k), np.float32) if dist else None
         check(lib().vsom_bmu_topk_batch(self._h, k, r0, r1, _u(idx), None if d is None else _f(d)))
         return idx, d
+
+    def similarity(self, min_hits, num_sigmas, sigma_rule=SIGMA_FLOOR, r0=0, r1=None, valid=None, delta=False):
+        """Som::measureSimilarity's per-row report of chunk rows [r0, r1) in one call (vsom_similarity_batch): every row
+        searched (findRestrictedBmu; findBmu's path when min_hits is 0) and scored against its BMU.  A dict of arrays
+        with one entry per row: bmu (uint64), dist, dmax, first, amax (float32), dmax_col, amax_col, outside (uint32),
+        and delta (float32[rows, min(J, D)], None unless delta=True).  valid: None, or rows x J, nonzero = the column
+        counts for amax / outside.  Overwrites the chunk's lastBMU / sqres like bmu_restricted_batch."""
+        B = self.chunk_size
+        r0 = int(r0)
+        r1 = B if r1 is None else int(r1)
+        if int(sigma_rule) not in (SIGMA_AS_WRITTEN, SIGMA_FLOOR):
+            raise ValueError(f"sigma_rule = {sigma_rule} is neither SIGMA_AS_WRITTEN nor SIGMA_FLOOR")
+        if int(min_hits) < 0:
+            raise ValueError("min_hits must be >= 0")
+        if not -2 ** 31 <= int(num_sigmas) < 2 ** 31:
+            raise ValueError("num_sigmas must fit an int")
+        if r0 < 0 or r0 > r1 or r1 > B:
+            raise ValueError(f"row range [{r0}, {r1}) is not within the chunk's {B} rows")
+        n = r1 - r0
+        vb = None
+        if valid is not None:
+            vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+            if vb.shape != (n, self.in_len):
+                raise ValueError(f"valid has shape {vb.shape}, not ({n}, {self.in_len})")
+        cols = min(self.in_len, self.depth)
+        res = {"bmu": np.empty(n, np.uint64), "dist": np.empty(n, np.float32), "dmax": np.empty(n, np.float32),
+               "dmax_col": np.empty(n, np.uint32), "first": np.empty(n, np.float32), "amax": np.empty(n, np.float32),
+               "amax_col": np.empty(n, np.uint32), "outside": np.empty(n, np.uint32),
+               "delta": np.empty((n, cols), np.float32) if delta else None}
+        out = SimilarityOut()
+        for name, ctype in SimilarityOut._fields_:
+            if res[name] is not None:
+                setattr(out, name, res[name].ctypes.data_as(ctype))
+        check(lib().vsom_similarity_batch(self._h, int(min_hits), int(num_sigmas), int(sigma_rule), r0, r1,
+                                          None if vb is None else vb.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(out)))
+        return res
 
     def distances_row(self, row):
         out = np.empty(self.n_nodes, np.float32)

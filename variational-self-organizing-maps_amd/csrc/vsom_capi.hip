@@ -840,6 +840,23 @@ int vsom_bmu_topk_batch(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t 
     return launch_topk(c, k, r0, r1, idx_out, dist_out);
 }
 
+int vsom_similarity_batch(vsom_ctx *c, uint64_t min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
+                          const uint8_t *valid_host, vsom_similarity_out *out)
+{
+    CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_similarity_batch");
+    CHECK_ROWS(c);
+    if (!out)
+        return vsom_fail(VSOM_ERR_INVALID, "out is null");
+    if (c->B == 0)
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    if (r0 > r1 || r1 > c->B)
+        return vsom_fail(VSOM_ERR_INVALID, "row range out of bounds");
+    if (sigma_rule != VSOM_SIGMA_AS_WRITTEN && sigma_rule != VSOM_SIGMA_FLOOR)
+        return vsom_fail(VSOM_ERR_INVALID, "unknown sigma_rule");
+    return launch_similarity(c, min_hits, num_sigmas, sigma_rule, r0, r1, valid_host, out);
+}
+
 int vsom_distances_row(vsom_ctx *c, size_t row, float *dist_out_host)
 {
     CHECK_CTX(c);

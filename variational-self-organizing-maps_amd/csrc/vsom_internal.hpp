@@ -193,6 +193,12 @@ struct vsom_ctx {
     DevBuf<u64> topk_part, topk_idx;
     DevBuf<float> topk_dist;
     DevBuf<unsigned char> topk_nan0;
+    // vsom_similarity_batch (vsom_similarity.hip): the per-row results of a call and their pinned host image, the validity
+    // bytes when given, the dense report of a row slice; one set, grow-only
+    DevBuf<unsigned> sim_rows;
+    PinnedBuf<unsigned> sim_pinned;
+    DevBuf<unsigned char> sim_valid;
+    DevBuf<float> sim_delta;
     // vsom_umatrix (vsom_umatrix.hip): U[N] of the last call, allocated on first use
     DevBuf<double> umatrix;
     bool um_valid = false;          // a vsom_umatrix has been enqueued on this context
@@ -262,6 +268,9 @@ int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_
                double *prob_out);
 // vsom_topk.hip: the k best matching units of chunk rows [r0,r1) (arguments checked by vsom_bmu_topk_batch); synchronises
 int launch_topk(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out, float *dist_out);
+// vsom_similarity.hip: search + scoring of chunk rows [r0,r1) (arguments checked by vsom_similarity_batch); synchronises
+int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
+                      const uint8_t *valid_host, const vsom_similarity_out *out);
 int launch_raw_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *vrows_dev, size_t count, int from_map,
                     float *out_dev);
 // vsom_umatrix.hip: Som::updateUMatrix of the current map / sigmaMap into ctx->umatrix; enqueues only.

@@ -1,0 +1,274 @@
+// vsom_similarity.hip -- Som::measureSimilarity's per-record report (Som.cpp:631-714) for chunk rows [r0, r1): the search of
+// the staged chunk, then one launch that scores every row against its BMU (gfx950).
+//
+//  similarity_kernel : one wavefront per row.  The row's lastBMU entry (wavefront-uniform) names the map and sigmaMap rows
+//                      to gather; lanes stride the C = min(J, D) columns, four consecutive columns per lane and step
+//                      (16-byte loads) where the model row is one part (Standard / Median), one column per lane for CLR's
+//                      two-part rows.  Two steps' loads are issued before the first value is used.  Per column, in fp32
+//                      with one rounding per operation: sM (the select of Som.cpp:658 as written, or a floor),
+//                      delta = (x - m) / sM / k (:671), lo = m - sM k, hi = m + sM k (:675-677).  Every lane keeps its own
+//                      candidates in column order; the row's results are reductions over the 64 lanes with cross-lane
+//                      moves -- a packed (ordered value, ~column) key for the two maxima, the lowest column for `first`, a
+//                      sum for `outside` -- and the winning value itself comes from the lane that owns the winning column.
+//                      No LDS, no atomics; lane 0 stores the row's nine words.
+// The memory traffic is 12 C bytes per row (three gathered rows) plus C bytes of validity and 4 C of the dense report when
+// those are asked for: the kernel is bound by the latency of the dependent gather (lastBMU -> model rows), not arithmetic.
+#include "vsom_device.hpp"
+#include <algorithm>
+#include <cstring>
+
+#define SIM_NONE 0xFFFFFFFFu
+#define SIM_ROWS_PER_WG 4
+#define SIM_ROW_WORDS 9     // bmu (2), dist, dmax, dmax_col, first, amax, amax_col, outside
+
+struct SimArgs {
+    const float *x;             // staged rows (Xs), pitch ldx
+    const float *map, *sigma;   // model rows, pitch ldm
+    const u64 *lastbmu;
+    const float *sqres;
+    const unsigned char *valid; // rows [r0, r1) x J, or null: every column valid
+    float *delta;               // the slice's dense report, rows x C, or null
+    unsigned *rows;             // per-row results of [r0, r1): SIM_ROW_WORDS arrays of R entries
+    int ldx, ldm, part_len, part_pitch;
+    int J, C, N, R;
+    float k;
+    int floor_rule;
+};
+
+// order-preserving image of a float that is not NaN (-0 taken as +0: the two compare equal)
+__device__ __forceinline__ uint32_t sim_ord(float v)
+{
+    const uint32_t u = __float_as_uint(v == 0.f ? 0.f : v);
+    return (u >> 31) ? ~u : (u | 0x80000000u);
+}
+
+__device__ __forceinline__ u64 sim_wave_max(u64 v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const u64 o = __shfl_xor(v, m);
+        v = o > v ? o : v;
+    }
+    return v;
+}
+
+struct SimLane {
+    float dmax_v, first_v, amax_v;
+    uint32_t dmax_c, first_c, amax_c, outside;
+};
+
+__device__ __forceinline__ float sim_column(SimLane &l, const SimArgs &a, uint32_t d, float x, float m, float s, bool valid)
+{
+    const float eps = 0.00001f;
+    const float sM = a.floor_rule ? (s > eps ? s : eps) : (s > eps ? eps : s);
+    const float t = x - m;
+    const float q = t / sM;
+    const float delta = q / a.k;
+    const float sk = sM * a.k;
+    const float lo = m - sk, hi = m + sk;
+    if (delta == delta && (l.dmax_c == SIM_NONE || delta > l.dmax_v)) {
+        l.dmax_v = delta;
+        l.dmax_c = d;
+    }
+    if (l.first_c == SIM_NONE && delta > -99999999.f) {
+        l.first_v = delta;
+        l.first_c = d;
+    }
+    const float ad = fabsf(delta);
+    const bool finite = ad < __builtin_inff();     // (false for NaN)
+    if (valid && finite && (l.amax_c == SIM_NONE || ad > l.amax_v)) {
+        l.amax_v = ad;
+        l.amax_c = d;
+    }
+    if (valid && (x < lo || x > hi))
+        ++l.outside;
+    return finite ? delta : 0.f;
+}
+
+// VEC: the model row is one part and lanes take four consecutive columns per step (pitches are multiples of 32 floats and
+// C <= J, D: a 16-byte load of a row's last, partial quad stays inside the padded row).  Otherwise one column per lane and
+// step, logical column d of a model row at (d / part_len) * part_pitch + d % part_len.
+template <bool VEC>
+__global__ __launch_bounds__(64 * SIM_ROWS_PER_WG) void similarity_kernel(SimArgs a, int r0, int s0, int s1)
+{
+    constexpr int W = VEC ? 4 : 1;
+    constexpr int U = 2;                        // steps whose loads are in flight together
+    const int lane = threadIdx.x & 63;
+    const int r = s0 + (int)blockIdx.x * SIM_ROWS_PER_WG + (int)(threadIdx.x >> 6);
+    if (r >= s1)
+        return;                                 // (wavefront-uniform)
+    u64 b = a.lastbmu[r];
+    b = b < (u64)a.N ? b : 0;                   // (the searches store indices below N)
+    const float *xr = a.x + (size_t)r * a.ldx;
+    const float *mr = a.map + (size_t)b * a.ldm;
+    const float *sr = a.sigma + (size_t)b * a.ldm;
+    const unsigned char *vr = a.valid ? a.valid + (size_t)(r - r0) * a.J : nullptr;
+    float *dr = a.delta ? a.delta + (size_t)(r - s0) * a.C : nullptr;
+    const int C = a.C;
+    const bool quad_store = VEC && (C & 3) == 0;
+
+    SimLane l;
+    l.dmax_v = -__builtin_inff();
+    l.first_v = __uint_as_float(0x7FC00000u);
+    l.amax_v = 0.f;
+    l.dmax_c = l.first_c = l.amax_c = SIM_NONE;
+    l.outside = 0;
+
+    for (int g0 = lane; g0 * W < C; g0 += 64 * U) {
+        float xv[U][W], mv[U][W], sv[U][W];
+        unsigned char vv[U][W];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int g = g0 + 64 * u;
+            if (g * W < C) {
+                if constexpr (VEC) {
+                    const float4 x4 = *reinterpret_cast<const float4 *>(xr + 4 * g);
+                    const float4 m4 = *reinterpret_cast<const float4 *>(mr + 4 * g);
+                    const float4 s4 = *reinterpret_cast<const float4 *>(sr + 4 * g);
+                    xv[u][0] = x4.x, xv[u][1] = x4.y, xv[u][2] = x4.z, xv[u][3] = x4.w;
+                    mv[u][0] = m4.x, mv[u][1] = m4.y, mv[u][2] = m4.z, mv[u][3] = m4.w;
+                    sv[u][0] = s4.x, sv[u][1] = s4.y, sv[u][2] = s4.z, sv[u][3] = s4.w;
+                } else {
+                    const int part = g / a.part_len;
+                    const int off = part * a.part_pitch + (g - part * a.part_len);
+                    xv[u][0] = xr[g];
+                    mv[u][0] = mr[off];
+                    sv[u][0] = sr[off];
+                }
+#pragma unroll
+                for (int e = 0; e < W; ++e)
+                    vv[u][e] = (vr && g * W + e < C) ? vr[g * W + e] : (unsigned char)1;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const int g = g0 + 64 * u;
+            if (g * W < C) {
+                float out[W];
+#pragma unroll
+                for (int e = 0; e < W; ++e) {
+                    const int d = g * W + e;
+                    out[e] = 0.f;
+                    if (d < C)
+                        out[e] = sim_column(l, a, (uint32_t)d, xv[u][e], mv[u][e], sv[u][e], vv[u][e] != 0);
+                }
+                if (dr) {
+                    bool stored = false;
+                    if constexpr (VEC) {
+                        if (quad_store) {
+                            *reinterpret_cast<float4 *>(dr + 4 * g) = make_float4(out[0], out[1], out[2], out[3]);
+                            stored = true;
+                        }
+                    }
+                    if (!stored) {
+#pragma unroll
+                        for (int e = 0; e < W; ++e)
+                            if (g * W + e < C)
+                                dr[g * W + e] = out[e];
+                    }
+                }
+            }
+        }
+    }
+
+    // the row's results over the 64 lanes; the lane that owns column c is (c / W) % 64
+    const u64 kd = sim_wave_max(l.dmax_c == SIM_NONE ? 0ull : ((u64)sim_ord(l.dmax_v) << 32) | (u64)(~l.dmax_c));
+    const u64 ka = sim_wave_max(l.amax_c == SIM_NONE ? 0ull : ((u64)sim_ord(l.amax_v) << 32) | (u64)(~l.amax_c));
+    uint32_t fc = l.first_c, cnt = l.outside;
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const uint32_t o = __shfl_xor(fc, m);
+        fc = o < fc ? o : fc;
+        cnt += __shfl_xor(cnt, m);
+    }
+    const uint32_t dc = kd ? ~(uint32_t)kd : SIM_NONE, ac = ka ? ~(uint32_t)ka : SIM_NONE;
+    const float dmax = __shfl(l.dmax_v, dc == SIM_NONE ? 0 : (int)((dc / W) & 63));     // (no column: every lane holds -inf)
+    const float amax = __shfl(l.amax_v, ac == SIM_NONE ? 0 : (int)((ac / W) & 63));     // (... 0)
+    const float first = __shfl(l.first_v, fc == SIM_NONE ? 0 : (int)((fc / W) & 63));   // (... NaN)
+    if (lane == 0) {
+        const size_t i = (size_t)(r - r0), R = (size_t)a.R;
+        reinterpret_cast<u64 *>(a.rows)[i] = a.lastbmu[r];
+        a.rows[2 * R + i] = __float_as_uint(a.sqres[r]);
+        a.rows[3 * R + i] = __float_as_uint(dmax);
+        a.rows[4 * R + i] = dc;
+        a.rows[5 * R + i] = __float_as_uint(first);
+        a.rows[6 * R + i] = __float_as_uint(amax);
+        a.rows[7 * R + i] = ac;
+        a.rows[8 * R + i] = cnt;
+    }
+}
+
+// rows per slice of the dense report: its device scratch stays within 64 MiB
+static size_t vsom_similarity_slice_rows(size_t C)
+{
+    return std::max<size_t>(1, ((size_t)64 << 20) / (4 * C));
+}
+
+int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
+                      const uint8_t *valid_host, const vsom_similarity_out *out)
+{
+    const size_t rows = r1 - r0;
+    if (rows == 0)
+        return VSOM_OK;
+    const size_t C = std::min<size_t>(c->J, c->D);
+    const size_t slice = out->delta ? std::min(vsom_similarity_slice_rows(C), rows) : rows;
+    // grow-only: a member keeps what it has when this call needs less
+    const size_t words = rows * SIM_ROW_WORDS;
+    VSOM_ALLOC_CHECK(vsom_grow_set(
+        c->stream, VSOM_BUF_SYNC,
+        {vsom_member(c->sim_rows, std::max(c->sim_rows.cap, words)), vsom_member(c->sim_pinned, std::max(c->sim_pinned.cap, words)),
+         vsom_member(c->sim_valid, std::max(c->sim_valid.cap, valid_host ? rows * c->J : 0)),
+         vsom_member(c->sim_delta, std::max(c->sim_delta.cap, out->delta ? slice * C : 0))}));
+
+    // findRestrictedBmu of the whole chunk; with min_hits = 0 every node qualifies and the search is findBmu's
+    int rc = min_hits == 0 ? launch_bmu_full(c, 0, c->B) : launch_bmu_restricted(c, min_hits);
+    if (rc)
+        return rc;
+    if (valid_host)
+        VSOM_HIP_CHECK(hipMemcpyAsync(c->sim_valid.p, valid_host, rows * c->J, hipMemcpyHostToDevice, c->stream));
+
+    SimArgs a;
+    a.x = c->Xs.p;
+    a.map = c->map.p;
+    a.sigma = c->sigma.p;
+    a.lastbmu = c->lastbmu.p;
+    a.sqres = c->sqres.p;
+    a.valid = valid_host ? c->sim_valid.p : nullptr;
+    a.delta = out->delta ? c->sim_delta.p : nullptr;
+    a.rows = c->sim_rows.p;
+    a.ldx = (int)c->xpitch;
+    a.ldm = (int)c->pitch;
+    a.part_len = (int)c->part_len;
+    a.part_pitch = (int)c->part_pitch;
+    a.J = (int)c->J;
+    a.C = (int)C;
+    a.N = (int)c->N;
+    a.R = (int)rows;
+    a.k = (float)num_sigmas;
+    a.floor_rule = sigma_rule == VSOM_SIGMA_FLOOR;
+    for (size_t s0 = r0; s0 < r1; s0 += slice) {
+        const size_t s1 = std::min(r1, s0 + slice), n = s1 - s0;
+        {
+            TimerScope ts(c, VSOM_T_FINISH);
+            const dim3 grid((unsigned)((n + SIM_ROWS_PER_WG - 1) / SIM_ROWS_PER_WG)), block(64 * SIM_ROWS_PER_WG);
+            if (c->nparts == 1)
+                hipLaunchKernelGGL(similarity_kernel<true>, grid, block, 0, c->stream, a, (int)r0, (int)s0, (int)s1);
+            else
+                hipLaunchKernelGGL(similarity_kernel<false>, grid, block, 0, c->stream, a, (int)r0, (int)s0, (int)s1);
+            VSOM_HIP_CHECK(hipGetLastError());
+        }
+        if (out->delta)
+            VSOM_HIP_CHECK(hipMemcpyAsync(out->delta + (s0 - r0) * C, c->sim_delta.p, n * C * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    VSOM_HIP_CHECK(hipMemcpyAsync(c->sim_pinned.p, c->sim_rows.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+
+    const unsigned *p = c->sim_pinned.p;
+    void *dst[SIM_ROW_WORDS - 1] = {out->bmu, out->dist, out->dmax, out->dmax_col, out->first, out->amax, out->amax_col, out->outside};
+    for (int i = 0; i < SIM_ROW_WORDS - 1; ++i) {
+        const size_t at = i == 0 ? 0 : (size_t)(i + 1) * rows, len = i == 0 ? 2 * rows : rows;
+        if (dst[i])
+            std::memcpy(dst[i], p + at, len * 4);
+    }
+    return VSOM_OK;
+}

@@ -478,6 +478,28 @@ public:
     // (node n at row n / width, column n % width; an error when max(|d row|, |d column|) != 1, no wrap); the count is
     // summed in row order in double and divided by the row count (0 for no rows).  N >= 2.
     double topographicError(const DataSet *data) const;
+    // [MI355X build] extension: the per-row report measureSimilarity computes and throws away, for every row of `data`
+    // (one vsom_similarity_batch call, include/vsom_hip.h): the row's restricted BMU and its distance, dmax / first (what
+    // the reference's running maximum needs), the anomaly score amax = the largest |x - m| / sM / numberOfSigmas over
+    // the valid columns with the column that causes it, the number of valid columns outside m +- sM * numberOfSigmas,
+    // and with wantDelta the dense rows x columns matrix.  floor: sM = max(sigma, 1e-5) (what a user wants); otherwise
+    // the reference's select as written (a cap at 1e-5).  useValidity: the data set's validity flags decide which columns
+    // count (otherwise all do).  Built-in transformations on the device only.
+    struct SimilarityRows {
+        size_t columns = 0;                       // min(sample length, depth)
+        std::vector<uint64_t> bmu;
+        std::vector<float> dist, dmax, first, amax;
+        std::vector<uint32_t> dmaxCol, amaxCol, outside;
+        std::vector<float> delta;                 // rows x columns, empty unless asked for
+    };
+    SimilarityRows similarityRows(const DataSet *data, int numberOfSigmas, size_t minBmuHits, bool floor = true,
+                                  bool useValidity = true, bool wantDelta = false) const;
+    // the finish of measureSimilarity from such a report: the row the reference reports (Som.cpp:684-690: one running
+    // maximum over every delta of every row, compared signed, stored as fabs); 0 when no delta exceeds the start value
+    static size_t measureSimilarityRow(const std::vector<float> &first, const std::vector<float> &dmax);
+    // how often this Som has downloaded the model state into its host mirror (refreshHost): for tests that a call runs
+    // on the device state
+    size_t stateDownloads() const noexcept { return nDownloads; }
     double euclidianWeightedDistRaw(const size_t &pos, const Eigen::VectorXf &v, const Eigen::VectorXf &valid,
                                     const Eigen::VectorXf &weights) const;
     void updateUMatrix(const Eigen::VectorXf &weights);
@@ -543,6 +565,7 @@ private:
     void syncReplicas();
     size_t inLen = 0;                 // J: sample length (depth = transform.Length(J))
     mutable bool hostStale = true;    // host mirrors below are out of date
+    mutable size_t nDownloads = 0;    // vsom_get_state calls of refreshHost
     mutable std::vector<float> hMap, hSigma, hWeight;
     mutable std::vector<uint64_t> hHits;
     // host execution for user-supplied hooks (kind() == vsom::Custom; src/vsom_custom.cpp): the state then

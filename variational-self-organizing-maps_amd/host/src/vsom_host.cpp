@@ -812,6 +812,7 @@ void Som::refreshHost() const
     if (ctx) {
         joinGroup();
         check(vsom_get_state(ctx, hMap.data(), hSigma.data(), nullptr, hWeight.data(), hHits.data()), "vsom_get_state");
+        ++nDownloads;
     }
     hostStale = false;
 }
@@ -1455,15 +1456,78 @@ double Som::evaluate(const DataSet &data) const
     return error;
 }
 
+// The per-row report of Som.cpp:631-714 on the device: upload, one vsom_similarity_batch call.
+Som::SimilarityRows Som::similarityRows(const DataSet *data, int numOfSigmas, size_t minBmuHits, bool floor, bool useValidity,
+                                        bool wantDelta) const
+{
+    requireDevicePath("similarityRows");
+    const size_t n = data->size();
+    SimilarityRows r;
+    r.columns = std::min(inLen, depth);
+    r.bmu.assign(n, 0);
+    r.dist.assign(n, 0.f);
+    r.dmax.assign(n, 0.f);
+    r.first.assign(n, 0.f);
+    r.amax.assign(n, 0.f);
+    r.dmaxCol.assign(n, 0);
+    r.amaxCol.assign(n, 0);
+    r.outside.assign(n, 0);
+    if (wantDelta)
+        r.delta.assign(n * r.columns, 0.f);
+    if (n == 0)
+        return r;
+    std::vector<uint8_t> valid;
+    if (useValidity) {   // (the data set hands its flags over row by row; a column it has no flag for does not count)
+        valid.assign(n * inLen, 0);
+        for (size_t i = 0; i < n; ++i) {
+            const Eigen::VectorXi v = data->getValidity(i);
+            const size_t m = std::min<size_t>((size_t)v.size(), inLen);
+            for (size_t d = 0; d < m; ++d)
+                valid[i * inLen + d] = v[(Eigen::Index)d] != 0;
+        }
+    }
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data->contiguous(), n), "vsom_upload_chunk");
+    vsom_similarity_out out = {r.bmu.data(),   r.dist.data(),    r.dmax.data(),    r.dmaxCol.data(), r.first.data(),
+                               r.amax.data(),  r.amaxCol.data(), r.outside.data(), wantDelta ? r.delta.data() : nullptr};
+    check(vsom_similarity_batch(ctx, minBmuHits, numOfSigmas, floor ? VSOM_SIGMA_FLOOR : VSOM_SIGMA_AS_WRITTEN, 0, n,
+                                useValidity ? valid.data() : nullptr, &out),
+          "vsom_similarity_batch");
+    return r;
+}
+
+size_t Som::measureSimilarityRow(const std::vector<float> &first, const std::vector<float> &dmax)
+{
+    const size_t n = std::min(first.size(), dmax.size());
+    size_t r = 0;
+    while (r < n && std::isnan(first[r]))
+        ++r;
+    if (r == n)
+        return 0;
+    size_t row = r;
+    float maxValue = std::fabs(first[r]);
+    for (; r < n; ++r)
+        if (dmax[r] > maxValue) {
+            maxValue = dmax[r];
+            row = r;
+        }
+    return row;
+}
+
 // Som.cpp:631-714
 int Som::measureSimilarity(const DataSet *data, int numOfSigmas, size_t minBmuHits) const
 {
     const size_t n = data->size();
     if (n == 0)
         return true;
+    if (ctx) {   // search and scoring on the device state; the finish walks one value per row
+        const SimilarityRows r = similarityRows(data, numOfSigmas, minBmuHits, false, true, false);
+        return r.outside[measureSimilarityRow(r.first, r.dmax)] == 0;
+    }
+    // caller's hooks: findRestrictedBmu per sample on the host (:652)
     std::vector<uint64_t> bmus(n);
-    if (!ctx) {   // caller's hooks: findRestrictedBmu per sample on the host (:652)
-        hostEnsure();
+    hostEnsure();
+    {
         const Eigen::VectorXf w = data->getWeights();
         for (size_t i = 0; i < n; ++i) {
             const Eigen::VectorXi validity = data->getValidity(i);
@@ -1472,10 +1536,6 @@ int Som::measureSimilarity(const DataSet *data, int numOfSigmas, size_t minBmuHi
                 val[d] = (float)validity[d];
             bmus[i] = hostFindRestrictedBmu(data->getData(i), val, minBmuHits, w);
         }
-    } else {
-        refreshHost();
-        check(vsom_upload_chunk(ctx, data->contiguous(), n), "vsom_upload_chunk");
-        check(vsom_bmu_restricted_batch(ctx, minBmuHits, bmus.data(), nullptr), "vsom_bmu_restricted_batch");
     }
     bool success = true;
     float maxValue{-99999999.f};

@@ -37,6 +37,36 @@ def topographic_error(idx2, width):
     return te / n
 
 
+def measure_similarity_from_rows(first, dmax, outside):
+    """The finish of Som::measureSimilarity (Som.cpp:631-714) from the per-row report of vsom_similarity_batch: (the row
+    the reference reports, its return value).  The reference walks every delta of every row with one running maximum that
+    starts at -99999999.f, compares the SIGNED delta with it and stores the delta's fabs (:684-690); `first[r]` is the
+    delta of row r's lowest column above that start value (NaN: none) and `dmax[r]` the row's largest signed delta (NaN
+    deltas excluded).  The walk equals: start at the first row whose `first` is not NaN with maxValue = |first|; for that
+    row and every later one, dmax > maxValue makes maxValue = dmax and that row the reported one.  Row 0 is reported when
+    no delta ever exceeds the start value (or there are no rows: then the result is True, as the mirrors return).  The
+    return value is outside[row] == 0: no valid column of the reported row lies outside its approved interval."""
+    first = np.asarray(first, dtype=np.float32)
+    dmax = np.asarray(dmax, dtype=np.float32)
+    outside = np.asarray(outside)
+    n = first.shape[0]
+    if dmax.shape[0] != n or outside.shape[0] != n:
+        raise ValueError("first, dmax and outside must have one entry per row")
+    if n == 0:
+        return 0, True
+    row = 0
+    started = np.flatnonzero(~np.isnan(first))
+    if started.size:
+        r = int(started[0])
+        row = r
+        maxValue = np.float32(abs(first[r]))
+        for i in range(r, n):
+            if dmax[i] > maxValue:
+                maxValue = dmax[i]
+                row = i
+    return row, bool(outside[row] == 0)
+
+
 class WeigthDecayFunction(enum.IntEnum):      # SOM.hpp:70-75 (spelling as in the reference)
     Exponential = 0
     InverseProportional = 1
@@ -318,6 +348,28 @@ class Som:
         u = np.random.default_rng(seed).random(1)
         d = int(self.drawModelVectors(X[-1:], minBmuHits, u)[0])
         return 0 if d == 0xFFFFFFFFFFFFFFFF else d
+
+    # ---- similarity of records to their best matching units (Som.cpp:631-714) -----------------
+    def similarityRows(self, data, numOfSigmas, minBmuHits, floor=True, valid=None, delta=False):
+        """extension: the per-row report measureSimilarity computes and throws away, for every loaded row of `data`
+        (capi.Context.similarity): the row's BMU among the nodes with at least minBmuHits hits, its anomaly score amax
+        (the largest |x - m| / sM / numOfSigmas over the valid columns) with the column that causes it, the number of
+        valid columns outside m +- sM * numOfSigmas, and with delta=True the dense matrix.  floor=True takes
+        sM = max(sigma, 1e-5) (what a user wants), floor=False the reference's select as written (a cap at 1e-5)."""
+        X = self._rows(data)
+        self.ctx.upload_chunk(X)
+        rule = capi.SIGMA_FLOOR if floor else capi.SIGMA_AS_WRITTEN
+        return self.ctx.similarity(minBmuHits, numOfSigmas, sigma_rule=rule, valid=valid, delta=delta)
+
+    def measureSimilarity(self, data, numOfSigmas, minBmuHits):
+        """Som::measureSimilarity: whether the record with the largest relative distance to its BMU in any column lies
+        inside the approved interval in all its valid columns (reference semantics, its sigma select as written).  The
+        validity comes from the data set when it has one (an attribute `validity`, rows x J)."""
+        X = self._rows(data)
+        if X.shape[0] == 0:
+            return True
+        rep = self.similarityRows(X, numOfSigmas, minBmuHits, floor=False, valid=getattr(data, "validity", None))
+        return measure_similarity_from_rows(rep["first"], rep["dmax"], rep["outside"])[1]
 
     # ---- k best matching units, topographic error (extensions) ---------------------------------
     def findBestMatchingUnits(self, data, k, dist=False):
