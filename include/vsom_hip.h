@@ -336,6 +336,39 @@ typedef struct vsom_similarity_out {
 } vsom_similarity_out;
 int vsom_similarity_batch(vsom_ctx *ctx, uint64_t min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
                           const uint8_t *valid_host, vsom_similarity_out *out);
+/* The best matching unit of chunk rows [r0, r1) over their VALID columns only -- partial-vector search, the SOM's way
+ * of handling missing data -- and the record imputed from it.  Every other search treats every value as present, as the
+ * reference's built-in Comparers do (Transformation.cpp:7-8,45-46 drop valueWeight); this one computes what
+ * Som::euclidianWeightedDist documents ("Considers only dimensions where valid is true", Som.cpp:112-141, the form of the
+ * commented-out :139) -- the evident intent next to "as written", as VSOM_SIGMA_FLOOR is.  Standard and Median (D = J).
+ * Mask: valid_host is (r1-r0) x J bytes, row-major, when one_mask == 0, and J bytes applied to every row (a column mask:
+ * "which unit matches these columns, and what do its others say?") when one_mask != 0; a non-zero byte means valid.
+ * Distance of row x to node m: r_d = valid[d] ? (m_d - x_d) : +0.0f -- a select, not a multiply: a NaN or inf stored at
+ * an invalid position of x or m has no effect -- and d = r.dot(r) over all J positions in the Eigen packet order of the
+ * unmasked distance (8 class accumulators, the same reduction tree).  With an all-valid mask every (bmu, dist) is
+ * bit-identical to vsom_bmu_restricted_batch with the same min_hits (min_hits = 0: to vsom_bmu_batch, every mode).
+ * Argmin: Som::findRestrictedBmu (Som.cpp:313-332): node 0 seeds the search whatever its hits, then strict `<` over the
+ * nodes with bmuHits >= min_hits, so the lowest index wins ties; NaN never wins and a NaN d_0 keeps node 0.  A NaN
+ * distance is stored as 0x7FC00000.  A row without a valid column has every distance +0: node 0, distance 0, nvalid 0.
+ * Outputs (host pointers, each may be NULL; entry r - r0 belongs to row r):
+ *   bmu, dist   the unit and the masked distance of the row to it, bit for bit
+ *   nvalid      the number of valid columns of the row
+ *   fill        [(r1-r0) * J] row-major: the bits of x at valid positions, of map[bmu][d] at invalid ones
+ * Read-only: lastBMU, sqres, the map, sigmaMap, S, weightMap, bmuHits and the chunk are untouched.  One call makes one
+ * stream wait; validity bytes and results travel from / to the caller's memory.  Refuses (VSOM_ERR_INVALID, nothing
+ * enqueued, the context stays usable): a null context, out or valid_host, custom and CLR contexts (the CLR residual runs
+ * over column pairs), no chunk, a chunk staged ahead, r0 > r1 or r1 > B.  An empty range returns VSOM_OK and enqueues
+ * nothing.  Device scratch: the rows are searched in slices whose scratch stays within 64 MiB (one row where a single
+ * row needs more): per row of a slice J + roundup(J, 32) validity bytes, at most 64 keys of 8 bytes, 17 bytes of results
+ * and, with fill, 4 J bytes. */
+typedef struct vsom_masked_out {
+    uint64_t *bmu;
+    float *dist;
+    uint32_t *nvalid;
+    float *fill;
+} vsom_masked_out;
+int vsom_bmu_masked_batch(vsom_ctx *ctx, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
+                          vsom_masked_out *out);
 /* Som::euclidianWeightedDistRaw(pos, v, ones, ones) (Som.cpp:143-157) for `count` pairs; v is
  * chunk row vrows[i] (from_map = 0) or model vector vrows[i] (from_map = 1, the U-matrix case). */
 int vsom_distances_raw(vsom_ctx *ctx, const uint64_t *nodes_host, const uint64_t *vrows_host,

@@ -48,6 +48,7 @@ SYMBOLS = [
     "vsom_ensemble_create", "vsom_ensemble_destroy", "vsom_ensemble_size", "vsom_ensemble_train_online_chunk_fetch",
     "vsom_ensemble_batch_epoch", "vsom_ensemble_upload_chunks", "vsom_ensemble_bmu_batch",
     "vsom_umatrix", "vsom_get_umatrix", "vsom_ensemble_umatrix", "vsom_similarity_batch",
+    "vsom_bmu_masked_batch",
 ]
 
 
@@ -56,6 +57,12 @@ class SimilarityOut(C.Structure):
     _fields_ = [("bmu", C.POINTER(C.c_uint64)), ("dist", C.POINTER(C.c_float)), ("dmax", C.POINTER(C.c_float)),
                 ("dmax_col", C.POINTER(C.c_uint32)), ("first", C.POINTER(C.c_float)), ("amax", C.POINTER(C.c_float)),
                 ("amax_col", C.POINTER(C.c_uint32)), ("outside", C.POINTER(C.c_uint32)), ("delta", C.POINTER(C.c_float))]
+
+
+class MaskedOut(C.Structure):
+    """vsom_masked_out: host pointers, each may be NULL"""
+    _fields_ = [("bmu", C.POINTER(C.c_uint64)), ("dist", C.POINTER(C.c_float)), ("nvalid", C.POINTER(C.c_uint32)),
+                ("fill", C.POINTER(C.c_float))]
 
 
 class VsomError(RuntimeError):
@@ -226,6 +233,8 @@ def lib():
     if hasattr(L, "vsom_similarity_batch"):     # (VSOM_LIB may name an older build: tools/similarity_bench.py --route parent)
         L.vsom_similarity_batch.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
                                             C.POINTER(C.c_uint8), C.POINTER(SimilarityOut)]
+    L.vsom_bmu_masked_batch.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8), C.c_int,
+                                        C.POINTER(MaskedOut)]
     _lib = L
     return L
 
@@ -568,6 +577,34 @@ class Context:
                 setattr(out, name, res[name].ctypes.data_as(ctype))
         check(lib().vsom_similarity_batch(self._h, int(min_hits), int(num_sigmas), int(sigma_rule), r0, r1,
                                           None if vb is None else vb.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(out)))
+        return res
+
+    def bmu_masked(self, valid, r0=0, r1=None, min_hits=0, fill=False):
+        """The best matching unit of chunk rows [r0, r1) over their valid columns only (vsom_bmu_masked_batch; Standard /
+        Median): findRestrictedBmu on the distance whose residual is +0 at invalid columns.  valid: rows x J (nonzero =
+        valid), or a 1-D column mask of J entries applied to every row.  A dict of arrays with one entry per row: bmu
+        (uint64), dist (float32), nvalid (uint32), and fill (float32[rows, J]: x where valid, the unit's value where not;
+        None unless fill=True).  Read-only."""
+        B = self.chunk_size
+        r0 = int(r0)
+        r1 = B if r1 is None else int(r1)
+        if int(min_hits) < 0:
+            raise ValueError("min_hits must be >= 0")
+        if r0 < 0 or r0 > r1 or r1 > B:
+            raise ValueError(f"row range [{r0}, {r1}) is not within the chunk's {B} rows")
+        n = r1 - r0
+        vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        one = vb.ndim == 1
+        if vb.shape != ((self.in_len,) if one else (n, self.in_len)):
+            raise ValueError(f"valid has shape {vb.shape}, neither ({self.in_len},) nor ({n}, {self.in_len})")
+        res = {"bmu": np.empty(n, np.uint64), "dist": np.empty(n, np.float32), "nvalid": np.empty(n, np.uint32),
+               "fill": np.empty((n, self.in_len), np.float32) if fill else None}
+        out = MaskedOut()
+        for name, ctype in MaskedOut._fields_:
+            if res[name] is not None:
+                setattr(out, name, res[name].ctypes.data_as(ctype))
+        check(lib().vsom_bmu_masked_batch(self._h, int(min_hits), r0, r1, vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one),
+                                          C.byref(out)))
         return res
 
     def distances_row(self, row):

@@ -857,6 +857,25 @@ int vsom_similarity_batch(vsom_ctx *c, uint64_t min_hits, int num_sigmas, int si
     return launch_similarity(c, min_hits, num_sigmas, sigma_rule, r0, r1, valid_host, out);
 }
 
+int vsom_bmu_masked_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
+                          vsom_masked_out *out)
+{
+    CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_bmu_masked_batch");
+    if (c->transform == VSOM_CLR)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_bmu_masked_batch: CLR contexts are not supported (the residual runs over column pairs)");
+    CHECK_ROWS(c);
+    if (!out)
+        return vsom_fail(VSOM_ERR_INVALID, "out is null");
+    if (!valid_host)
+        return vsom_fail(VSOM_ERR_INVALID, "valid_host is null");
+    if (c->B == 0)
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    if (r0 > r1 || r1 > c->B)
+        return vsom_fail(VSOM_ERR_INVALID, "row range out of bounds");
+    return launch_masked(c, min_hits, r0, r1, valid_host, one_mask, out);
+}
+
 int vsom_distances_row(vsom_ctx *c, size_t row, float *dist_out_host)
 {
     CHECK_CTX(c);

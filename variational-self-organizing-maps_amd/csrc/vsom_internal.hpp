@@ -199,6 +199,12 @@ struct vsom_ctx {
     PinnedBuf<unsigned> sim_pinned;
     DevBuf<unsigned char> sim_valid;
     DevBuf<float> sim_delta;
+    // vsom_bmu_masked_batch (vsom_masked.hip): a row slice's validity bytes as given and packed (0xFF / 0x00, xpitch per row),
+    // its node groups' keys, its results and node-0 NaN flags, its imputed rows; one set, grow-only
+    DevBuf<unsigned char> msk_raw, msk_valid, msk_nan0;
+    DevBuf<u64> msk_part, msk_bmu;
+    DevBuf<float> msk_dist, msk_fill;
+    DevBuf<unsigned> msk_nvalid;
     // vsom_umatrix (vsom_umatrix.hip): U[N] of the last call, allocated on first use
     DevBuf<double> umatrix;
     bool um_valid = false;          // a vsom_umatrix has been enqueued on this context
@@ -271,6 +277,9 @@ int launch_topk(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out
 // vsom_similarity.hip: search + scoring of chunk rows [r0,r1) (arguments checked by vsom_similarity_batch); synchronises
 int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
                       const uint8_t *valid_host, const vsom_similarity_out *out);
+// vsom_masked.hip: the search over valid columns of chunk rows [r0,r1) (arguments checked by vsom_bmu_masked_batch); synchronises
+int launch_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
+                  const vsom_masked_out *out);
 int launch_raw_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *vrows_dev, size_t count, int from_map,
                     float *out_dev);
 // vsom_umatrix.hip: Som::updateUMatrix of the current map / sigmaMap into ctx->umatrix; enqueues only.

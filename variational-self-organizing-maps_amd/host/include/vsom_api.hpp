@@ -494,6 +494,15 @@ public:
     };
     SimilarityRows similarityRows(const DataSet *data, int numberOfSigmas, size_t minBmuHits, bool floor = true,
                                   bool useValidity = true, bool wantDelta = false) const;
+    // [MI355X build] extension: the best matching unit of every row of `data` over its VALID columns only (the data set's
+    // validity flags; one vsom_bmu_masked_batch call, include/vsom_hip.h): Som::findRestrictedBmu on the distance whose
+    // residual is +0 at invalid columns, so a missing field no longer counts as a measured zero.  *dist (if given)
+    // receives the masked distances.  With every column valid the result is findRestrictedBmu's.  Standard / Median on the
+    // device only.
+    std::vector<uint64_t> findMaskedBmus(const DataSet *data, size_t minBmuHits, std::vector<float> *dist = nullptr) const;
+    // [MI355X build] extension: rows x sample length, row-major: every row of `data` with its invalid columns filled from
+    // the model vector of its findMaskedBmus unit (the same call).
+    std::vector<float> impute(const DataSet *data, size_t minBmuHits) const;
     // the finish of measureSimilarity from such a report: the row the reference reports (Som.cpp:684-690: one running
     // maximum over every delta of every row, compared signed, stored as fabs); 0 when no delta exceeds the start value
     static size_t measureSimilarityRow(const std::vector<float> &first, const std::vector<float> &dmax);
@@ -585,6 +594,7 @@ private:
                            WeigthDecayFunction fn, bool updateUMatrixAfterEpoch);
     void createContext();
     void requireDevicePath(const char *what) const;
+    void maskedRows(const DataSet *data, size_t minBmuHits, uint64_t *bmu, float *dist, float *fill) const;
     void refreshHost() const;
     void stageOne(const Eigen::VectorXf &v) const;
 };

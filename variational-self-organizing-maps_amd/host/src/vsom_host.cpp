@@ -1496,6 +1496,44 @@ Som::SimilarityRows Som::similarityRows(const DataSet *data, int numOfSigmas, si
     return r;
 }
 
+// upload, one vsom_bmu_masked_batch call with the data set's validity flags (collected row by row, as similarityRows does)
+void Som::maskedRows(const DataSet *data, size_t minBmuHits, uint64_t *bmu, float *dist, float *fill) const
+{
+    const size_t n = data->size();
+    if (n == 0)
+        return;
+    std::vector<uint8_t> valid(n * inLen, 0);   // (a column the data set has no flag for does not count)
+    for (size_t i = 0; i < n; ++i) {
+        const Eigen::VectorXi v = data->getValidity(i);
+        const size_t m = std::min<size_t>((size_t)v.size(), inLen);
+        for (size_t d = 0; d < m; ++d)
+            valid[i * inLen + d] = v[(Eigen::Index)d] != 0;
+    }
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data->contiguous(), n), "vsom_upload_chunk");
+    vsom_masked_out out = {bmu, dist, nullptr, fill};
+    check(vsom_bmu_masked_batch(ctx, minBmuHits, 0, n, valid.data(), 0, &out), "vsom_bmu_masked_batch");
+}
+
+std::vector<uint64_t> Som::findMaskedBmus(const DataSet *data, size_t minBmuHits, std::vector<float> *dist) const
+{
+    requireDevicePath("findMaskedBmus");
+    const size_t n = data->size();
+    std::vector<uint64_t> bmu(n, 0);
+    if (dist)
+        dist->assign(n, 0.0f);
+    maskedRows(data, minBmuHits, bmu.data(), dist ? dist->data() : nullptr, nullptr);
+    return bmu;
+}
+
+std::vector<float> Som::impute(const DataSet *data, size_t minBmuHits) const
+{
+    requireDevicePath("impute");
+    std::vector<float> fill(data->size() * inLen, 0.0f);
+    maskedRows(data, minBmuHits, nullptr, nullptr, fill.data());
+    return fill;
+}
+
 size_t Som::measureSimilarityRow(const std::vector<float> &first, const std::vector<float> &dmax)
 {
     const size_t n = std::min(first.size(), dmax.size());

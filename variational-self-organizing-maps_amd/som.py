@@ -371,6 +371,44 @@ class Som:
         rep = self.similarityRows(X, numOfSigmas, minBmuHits, floor=False, valid=getattr(data, "validity", None))
         return measure_similarity_from_rows(rep["first"], rep["dmax"], rep["outside"])[1]
 
+    # ---- search over the valid columns, imputation, classification (extensions) ----------------
+    def _masked(self, data, valid, minBmuHits, fill):
+        X = self._rows(data)
+        self.ctx.upload_chunk(X)
+        if X.shape[0] == 0:
+            return {"bmu": np.zeros(0, np.uint64), "dist": np.zeros(0, np.float32), "nvalid": np.zeros(0, np.uint32),
+                    "fill": np.zeros((0, self.ctx.in_len), np.float32) if fill else None}
+        if valid is None:
+            valid = np.ones(self.ctx.in_len, np.uint8)
+        return self.ctx.bmu_masked(valid, min_hits=minBmuHits, fill=fill)
+
+    def findBmuMasked(self, data, minBmuHits=0):
+        """extension: the best matching unit of every loaded row of `data` over its valid columns only, among node 0 and
+        the nodes with at least minBmuHits hits (capi.Context.bmu_masked): {"bmu", "dist", "nvalid"}.  The validity comes
+        from the data set when it has one (an attribute `validity`, rows x J, nonzero = valid), as in measureSimilarity;
+        without one every column is valid."""
+        rep = self._masked(data, getattr(data, "validity", None), minBmuHits, False)
+        return {k: rep[k] for k in ("bmu", "dist", "nvalid")}
+
+    def impute(self, data, minBmuHits=0):
+        """extension: float32[rows, J], every loaded row of `data` with its invalid columns filled from its best matching
+        unit over the valid ones (validity as in findBmuMasked)"""
+        return self._masked(data, getattr(data, "validity", None), minBmuHits, True)["fill"]
+
+    def classify(self, data, label_columns, minBmuHits=0):
+        """extension: a trained map with label columns used as a classifier.  Every loaded row of `data` is matched on the
+        columns outside `label_columns` (a column mask; what the rows hold in the label columns is ignored), and its
+        label is the argmax over its unit's values in the label columns, the lowest column on ties (numpy's argmax: a NaN
+        counts as the largest).  Returns (label int64[rows], an index into label_columns; bmu uint64[rows])."""
+        cols = np.asarray(label_columns, dtype=np.int64).ravel()
+        J = self.ctx.in_len
+        if cols.size == 0 or cols.min() < 0 or cols.max() >= J:
+            raise ValueError(f"label_columns must name at least one column in [0, {J})")
+        valid = np.ones(J, np.uint8)
+        valid[cols] = 0
+        rep = self._masked(data, valid, minBmuHits, True)
+        return np.argmax(rep["fill"][:, cols], axis=1).astype(np.int64), rep["bmu"]
+
     # ---- k best matching units, topographic error (extensions) ---------------------------------
     def findBestMatchingUnits(self, data, k, dist=False):
         """extension: the k best matching units of every loaded row of `data` (uint64[rows, k]; entry 0 is findBmu's
