@@ -1,19 +1,16 @@
 // vsom_bmd.hip -- Som::findRestrictedBmd (Som.cpp:457-487) for a range of chunk rows, and one draw per row (gfx950).
 //
-//  bmd_tile_kernel : the distance tile of bmu_tile_kernel (vsom_bmu.hip: 64 (CLR: 32) rows x 64 nodes per workgroup,
-//                    8 class accumulators + Eigen's reduction tree, the same operations in the same order) with a
+//  bmd_tile_kernel : the shared distance tile (vsom_dist_tile.hpp: 64 (CLR: 32) rows x 64 nodes per workgroup, 8 class
+//                    accumulators + Eigen's reduction tree, the exact search's operations in its order) with a
 //                    distribution epilogue: p = hits >= min_hits ? exp(-(double)d * d / 2) : 0 (Som.cpp:468-479),
 //                    stored node-major inside the row slice, P[node * ppitch + row]
 //  bmd_sum_kernel  : one lane per row walks the nodes in ascending order, C = ((0 + p_0) + p_1) + ... (Som.cpp:463-476),
 //                    keeping the running sum at every BMD_NC-node boundary; the draw re-walks the one BMD_NC-node chunk
 //                    that holds the first running sum above t = u * C with the same adds
 //  bmd_prob_kernel : p_i / C (Som.cpp:483-484), transposed to row-major for the copy-out
-// The body of the tile is a copy of bmu_tile_body without its row / node lists: no existing kernel changes.
-#include "vsom_device.hpp"
+#include "vsom_dist_tile.hpp"
 #include <algorithm>
 
-#define TILE 64
-#define LDT 36
 #define BMD_R 8        // rows per workgroup of the row pass
 #define BMD_NC 256     // nodes per chunk of the row pass (one per thread)
 
@@ -22,156 +19,19 @@ __global__ __launch_bounds__(256, 2) void bmd_tile_kernel(DistArgs a, int s0, in
                                                           int ppitch, const u64 *__restrict__ hits, u64 min_hits)
 {
     constexpr int TS = 16 * TI;                 // samples per tile
-    constexpr int NX = TS * 8 / 256;            // float4 of a sample operand per thread and K-chunk (1 or 2)
-    __shared__ __attribute__((aligned(16))) float sx[TILE * LDT];
-    __shared__ __attribute__((aligned(16))) float sm[TILE * LDT];
-    __shared__ __attribute__((aligned(16))) float sy[CLR ? TS * LDT : 4];
-    __shared__ __attribute__((aligned(16))) float sb[CLR ? TILE * LDT : 4];
     __shared__ double sp[TILE][TS + 1];         // the tile's p, node-major, for coalesced stores
 
     const int tid = threadIdx.x, tx = tid & 15, ty = tid >> 4;
     const int nbase = blockIdx.x * TILE;
     const int sbase = s0 + blockIdx.y * TS;
-    const int L = a.L, L8 = L & ~7;
-    const int nchunks = (L + VSOM_TK - 1) / VSOM_TK;
 
-    float acc[TI][4][8];
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j)
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-                acc[i][j][k] = 0.f;
-
-    float4 gx[NX], gm[2], gy[NX], gb[2];
-    auto gload = [&](int k0) {
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            int f = tid + 256 * i;
-            int row = f >> 3, c4 = (f & 7) * 4;
-            int s = sbase + row;
-            gx[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            gy[i] = gx[i];
-            if (s < s1) {
-                gx[i] = *reinterpret_cast<const float4 *>(a.xa + (size_t)s * a.ldx + k0 + c4);
-                if (CLR)
-                    gy[i] = *reinterpret_cast<const float4 *>(a.xb + (size_t)s * a.ldx + k0 + c4);
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            int f = tid + 256 * i;
-            int row = f >> 3, c4 = (f & 7) * 4;
-            int n = nbase + row;
-            gm[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-            gb[i] = gm[i];
-            if (n < N) {
-                gm[i] = *reinterpret_cast<const float4 *>(a.ma + (size_t)n * a.ldm + k0 + c4);
-                if (CLR)
-                    gb[i] = *reinterpret_cast<const float4 *>(a.mb + (size_t)n * a.ldm + k0 + c4);
-            }
-        }
-    };
-    gload(0);
-    int dk = 0;
-    for (int ch = 0; ch < nchunks; ++ch, dk += VSOM_TK) {
-        if (ch > 0)
-            __syncthreads();
-#pragma unroll
-        for (int i = 0; i < NX; ++i) {
-            int f = tid + 256 * i;
-            int row = f >> 3, c4 = (f & 7) * 4;
-            *reinterpret_cast<float4 *>(&sx[row * LDT + c4]) = gx[i];
-            if (CLR)
-                *reinterpret_cast<float4 *>(&sy[row * LDT + c4]) = gy[i];
-        }
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-            int f = tid + 256 * i;
-            int row = f >> 3, c4 = (f & 7) * 4;
-            *reinterpret_cast<float4 *>(&sm[row * LDT + c4]) = gm[i];
-            if (CLR)
-                *reinterpret_cast<float4 *>(&sb[row * LDT + c4]) = gb[i];
-        }
-        __syncthreads();
-        if (ch + 1 < nchunks)
-            gload(dk + VSOM_TK);
-#pragma unroll
-        for (int kk = 0; kk < VSOM_TK; kk += 8) {
-            if (dk + kk < L8) {   // whole 8-blocks only; the remainder is handled in Eigen's order below
-#pragma unroll
-                for (int h = 0; h < 2; ++h) {
-                    float4 xv[TI], mv[4], yv[TI], bv[4];
-#pragma unroll
-                    for (int j = 0; j < 4; ++j) {
-                        mv[j] = *reinterpret_cast<const float4 *>(&sm[(tx + 16 * j) * LDT + kk + 4 * h]);
-                        if (CLR)
-                            bv[j] = *reinterpret_cast<const float4 *>(&sb[(tx + 16 * j) * LDT + kk + 4 * h]);
-                    }
-#pragma unroll
-                    for (int i = 0; i < TI; ++i) {
-                        xv[i] = *reinterpret_cast<const float4 *>(&sx[(ty + 16 * i) * LDT + kk + 4 * h]);
-                        if (CLR)
-                            yv[i] = *reinterpret_cast<const float4 *>(&sy[(ty + 16 * i) * LDT + kk + 4 * h]);
-                    }
-#pragma unroll
-                    for (int i = 0; i < TI; ++i) {
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            float r0 = vsom_resid<CLR>(xv[i].x, CLR ? yv[i].x : 0.f, mv[j].x, CLR ? bv[j].x : 0.f);
-                            float r1 = vsom_resid<CLR>(xv[i].y, CLR ? yv[i].y : 0.f, mv[j].y, CLR ? bv[j].y : 0.f);
-                            float r2 = vsom_resid<CLR>(xv[i].z, CLR ? yv[i].z : 0.f, mv[j].z, CLR ? bv[j].z : 0.f);
-                            float r3 = vsom_resid<CLR>(xv[i].w, CLR ? yv[i].w : 0.f, mv[j].w, CLR ? bv[j].w : 0.f);
-                            float p0 = r0 * r0, p1 = r1 * r1, p2 = r2 * r2, p3 = r3 * r3;
-                            acc[i][j][4 * h + 0] = acc[i][j][4 * h + 0] + p0;
-                            acc[i][j][4 * h + 1] = acc[i][j][4 * h + 1] + p1;
-                            acc[i][j][4 * h + 2] = acc[i][j][4 * h + 2] + p2;
-                            acc[i][j][4 * h + 3] = acc[i][j][4 * h + 3] + p3;
-                        }
-                    }
-                }
-            }
-        }
-    }
-
-    // reduction tree + remainder (the last chunk is still in LDS)
-    const int rem = L - L8;
-    const int roff = L8 - (nchunks - 1) * VSOM_TK;   // column of element L8 inside the last chunk
-#pragma unroll
-    for (int i = 0; i < TI; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float q0 = acc[i][j][0] + acc[i][j][4];
-            float q1 = acc[i][j][1] + acc[i][j][5];
-            float q2 = acc[i][j][2] + acc[i][j][6];
-            float q3 = acc[i][j][3] + acc[i][j][7];
-            const int xr = (ty + 16 * i) * LDT + roff, mr = (tx + 16 * j) * LDT + roff;
-            int t = 0;
-            if (rem >= 4) {
-                float r0 = vsom_resid<CLR>(sx[xr + 0], CLR ? sy[xr + 0] : 0.f, sm[mr + 0], CLR ? sb[mr + 0] : 0.f);
-                float r1 = vsom_resid<CLR>(sx[xr + 1], CLR ? sy[xr + 1] : 0.f, sm[mr + 1], CLR ? sb[mr + 1] : 0.f);
-                float r2 = vsom_resid<CLR>(sx[xr + 2], CLR ? sy[xr + 2] : 0.f, sm[mr + 2], CLR ? sb[mr + 2] : 0.f);
-                float r3 = vsom_resid<CLR>(sx[xr + 3], CLR ? sy[xr + 3] : 0.f, sm[mr + 3], CLR ? sb[mr + 3] : 0.f);
-                float p0 = r0 * r0, p1 = r1 * r1, p2 = r2 * r2, p3 = r3 * r3;
-                q0 = q0 + p0;
-                q1 = q1 + p1;
-                q2 = q2 + p2;
-                q3 = q3 + p3;
-                t = 4;
-            }
-            float t02 = q0 + q2, t13 = q1 + q3;
-            float res = t02 + t13;
-            for (; t < rem; ++t) {
-                float r = vsom_resid<CLR>(sx[xr + t], CLR ? sy[xr + t] : 0.f, sm[mr + t], CLR ? sb[mr + t] : 0.f);
-                float p = r * r;
-                res = res + p;
-            }
-            // Som.cpp:468-479: the distance as a double, exp(-d * d / 2) for the nodes with enough hits, 0 for the others
-            const int n = nbase + tx + 16 * j;
-            const double d = (double)res;
-            sp[tx + 16 * j][ty + 16 * i] = (n < N && hits[n] >= min_hits) ? exp(-d * d / 2) : 0.0;
-        }
+    // Som.cpp:468-479: the distance as a double, exp(-d * d / 2) for the nodes with enough hits, 0 for the others
+    vsom_dist_tile<CLR, TI>(a, tid, sbase, s1, nbase, N, VsomMaskNone(),
+                            [&](int i, int j, float res) {
+                                const int n = nbase + tx + 16 * j;
+                                const double d = (double)res;
+                                sp[tx + 16 * j][ty + 16 * i] = (n < N && hits[n] >= min_hits) ? exp(-d * d / 2) : 0.0;
+                            });
     __syncthreads();
     // node-major stores: consecutive lanes write consecutive rows of one node
 #pragma unroll
@@ -308,27 +168,6 @@ __global__ __launch_bounds__(256) void bmd_prob_kernel(const double *__restrict_
     }
 }
 
-static DistArgs bmd_dist_args(const vsom_ctx *c)
-{
-    DistArgs a;
-    if (c->transform == VSOM_CLR) {
-        a.xa = c->XP.p;
-        a.xb = c->YP.p;
-        a.ldx = (int)c->part_pitch;
-        a.ma = c->map.p;
-        a.mb = c->map.p + c->part_pitch;
-    } else {
-        a.xa = c->Xs.p;
-        a.xb = c->Xs.p;
-        a.ldx = (int)c->xpitch;
-        a.ma = c->map.p;
-        a.mb = c->map.p;
-    }
-    a.ldm = (int)c->pitch;
-    a.L = (int)c->part_len;
-    return a;
-}
-
 // rows per slice: the node-major p of a slice stays within 256 MiB
 static size_t vsom_bmd_slice_rows(size_t N)
 {
@@ -353,7 +192,7 @@ int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_
                                     vsom_member(c->bmd_prob, prob_out ? prow * N : 0)}));
     double *P = c->bmd_p.p, *u_dev = c->bmd_vec.p, *norm_dev = c->bmd_vec.p + ppitch;
     u64 *draw_dev = draw_out ? c->bmd_draw.p : nullptr;
-    const DistArgs a = bmd_dist_args(c);
+    const DistArgs a = vsom_dist_args(c);
     const int TS = c->transform == VSOM_CLR ? 32 : TILE;
     for (size_t s0 = r0; s0 < r1; s0 += slice) {
         const size_t s1 = std::min(r1, s0 + slice), n = s1 - s0, off = s0 - r0;

@@ -3,6 +3,8 @@
 //  bmu_tile_kernel   : Som::findBmu (Som.cpp:291-309) for a 64-sample x 64-node tile per
 //                      workgroup; every distance is evaluated in the reference's fp32 order
 //                      (8 class accumulators + Eigen's reduction tree) on the VALU.
+//                      The distance part is the twin of vsom_dist_tile (vsom_dist_tile.hpp), with row
+//                      and node lists: see bmu_tile_body.
 //  bmu_reduce_kernel : per-sample argmin over the node tiles (strict <, lowest index, NaN
 //                      rules of Som.cpp:293-304).
 //  bmu_local_kernel  : Som::findLocalBmu (Som.cpp:335-454), one wavefront per sample,
@@ -11,7 +13,7 @@
 //  finish_kernel     : bmuHits[idx] += 1 and the fp32 MSE running sum in sample order
 //                      (Som.cpp:777-781).
 //  stage kernels     : chunk re-layout (zero-padded rows; CLR x'/y' expansion).
-#include "vsom_device.hpp"
+#include "vsom_dist_tile.hpp"
 #include "vsom_digits.hpp"
 #include <algorithm>
 #include <utility>
@@ -178,7 +180,7 @@ int vsom_adopt_ahead(vsom_ctx *c)
     return VSOM_OK;
 }
 
-static DistArgs make_dist_args(const vsom_ctx *c)
+DistArgs vsom_dist_args(const vsom_ctx *c)
 {
     DistArgs a;
     if (c->transform == VSOM_CLR) {
@@ -202,14 +204,12 @@ static DistArgs make_dist_args(const vsom_ctx *c)
 // ------------------------------------------------------------------------------------------
 // full search: 64 x 64 tile per workgroup, 4 x 4 pairs x 8 class accumulators per thread
 // ------------------------------------------------------------------------------------------
-#define TILE 64
-#define LDT 36   // LDS row stride in floats: 16-B aligned, lane rows land on distinct 4-bank slots
-
-// TI = sample rows per thread: 4 for Standard / Median (64 x 64 tile, 128 accumulators per thread).  The CLR
-// residual needs two more operand arrays (y', B): with 4 x 4 pairs the kernel sat at 256 VGPRs with 46 spilled
-// dwords in the hot loop and no room to prefetch (r2: VALU 54 % busy, 2.3 ms at C5).  CLR therefore takes
-// TI = 2 -- a 32-sample x 64-node tile, 64 accumulators -- which leaves registers for the next K-chunk's loads
-// in flight while the current one is consumed and lets three workgroups share a CU.
+// The distance part of this body (from the accumulators to `dist[i][j] = res`) is the twin of vsom_dist_tile
+// (vsom_dist_tile.hpp: TILE, LDT, TI and the tile the other chunk queries call) with the sample rows read through slist
+// and the model rows through nlist.  It stays a copy: calling the shared tile gave the same optimised IR up to the order
+// of hoisted address computations, but the LIST Standard kernel -- at 256 VGPRs already -- then spilled one register more
+// (profiles/EXPERIMENTS.md, "One distance tile").  A change to either is made to both, and tests/test_gpu_tile_consumers.py
+// holds them to the same bits.
 template <bool CLR, int TI>
 __device__ __forceinline__ void bmu_tile_body(const DistArgs &a, int s0, int s1, int N,
                                               u64 *__restrict__ partial, int pstride,
@@ -658,7 +658,7 @@ int launch_bmu_full_exact_masked(vsom_ctx *c, size_t s0, size_t s1, const int *s
     const int nts = (int)((s1 - s0 + TS - 1) / TS);
     size_t need = (size_t)ntn * c->Bcap;
     VSOM_ALLOC_CHECK(vsom_grow(c->partial, need, c->stream));
-    DistArgs a = make_dist_args(c);
+    DistArgs a = vsom_dist_args(c);
     // (a redo list is usually empty or short: ~512 workgroups -- the two per CU the kernel's registers allow -- each
     // walking on through the list's tiles; 768 for CLR measured slower: a second, half-empty round)
     const bool list = slist != nullptr && scount != nullptr;
@@ -798,7 +798,7 @@ int launch_bmu_local(vsom_ctx *c, size_t s0, size_t s1)
     TimerScope ts(c, VSOM_T_BMU);
     if (s1 <= s0)
         return VSOM_OK;
-    DistArgs a = make_dist_args(c);
+    DistArgs a = vsom_dist_args(c);
     size_t waves = s1 - s0;
     dim3 grid((unsigned)((waves + 3) / 4));
     if (c->transform == VSOM_CLR)
@@ -834,7 +834,7 @@ int launch_pair_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *rows_dev, siz
 {
     if (count == 0)
         return VSOM_OK;
-    DistArgs a = make_dist_args(c);
+    DistArgs a = vsom_dist_args(c);
     dim3 grid((unsigned)((count * 8 + 255) / 256));
     if (c->transform == VSOM_CLR)
         hipLaunchKernelGGL(pair_dist_kernel<true>, grid, dim3(256), 0, c->stream, a, nodes_dev,
@@ -861,7 +861,7 @@ __global__ __launch_bounds__(256) void row_dist_kernel(DistArgs a, int row, int 
 
 int launch_row_dist(vsom_ctx *c, size_t row, float *out_dev)
 {
-    DistArgs a = make_dist_args(c);
+    DistArgs a = vsom_dist_args(c);
     dim3 grid((unsigned)(((size_t)c->N * 8 + 255) / 256));
     if (c->transform == VSOM_CLR)
         hipLaunchKernelGGL(row_dist_kernel<true>, grid, dim3(256), 0, c->stream, a, (int)row, (int)c->N, out_dev);

@@ -39,6 +39,17 @@ __device__ __forceinline__ u64 vsom_key(float d, uint32_t node)
     return ((u64)bits << 32) | (u64)node;
 }
 
+// the smallest v of the wavefront's 64 lanes, in every lane
+__device__ __forceinline__ u64 vsom_wave_min(u64 v)
+{
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        const u64 o = __shfl_xor(v, m);
+        v = o < v ? o : v;
+    }
+    return v;
+}
+
 // Distance of one (sample,node) pair computed by a group of 8 consecutive lanes, lane k
 // owning Eigen's accumulator class k (elements d = k mod 8), followed by the reduction tree
 // of Eigen's SSE linear-vectorised redux:

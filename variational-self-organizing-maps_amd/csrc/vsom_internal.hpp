@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stddef.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 
@@ -249,6 +250,21 @@ struct TimerScope {
 };
 
 // kernel launchers (each enqueues on ctx->stream and returns a vsom_status) -------------------
+// the operands of the context's distance evaluations (vsom_device.hpp; defined in vsom_bmu.hip)
+struct DistArgs;
+DistArgs vsom_dist_args(const vsom_ctx *c);
+// The node groups of a tile walk (vsom_topk.hip, vsom_masked.hip): a workgroup walks G consecutive node tiles, ng groups
+// cover the ntiles node tiles.  Enough workgroups to fill the chip (2048: four rounds of two per CU) over the rtiles row
+// tiles of a slice, and at most maxg groups (one result per row and group is merged afterwards).
+struct VsomNodeGroups {
+    size_t G, ng;
+};
+inline VsomNodeGroups vsom_node_groups(size_t ntiles, size_t rtiles, size_t maxg)
+{
+    const size_t want = std::min<size_t>({maxg, ntiles, std::max<size_t>(1, (2048 + rtiles - 1) / rtiles)});
+    const size_t G = (ntiles + want - 1) / want;
+    return {G, (ntiles + G - 1) / G};
+}
 int launch_stage_chunk(vsom_ctx *c, const float *x_dev, size_t B);
 // the chunk buffers sized for B rows (vsom_capi.hip; synchronises and reallocates only when B exceeds the capacity)
 int ensure_chunk_capacity(vsom_ctx *c, size_t B);

@@ -1,8 +1,8 @@
 // vsom_topk.hip -- the k best matching units of every chunk row in [r0, r1): the k smallest keys vsom_key(d_i, i) over
 // every node, with findBmu's node-0 rule in front (Som.cpp:291-309) (gfx950).
 //
-//  topk_tile_kernel  : the distance tile of bmd_tile_kernel (vsom_bmd.hip: 64 (CLR: 32) rows x 64 nodes per tile, 8 class
-//                      accumulators + Eigen's reduction tree, the same operations in the same order), walked over G
+//  topk_tile_kernel  : the shared distance tile (vsom_dist_tile.hpp: 64 (CLR: 32) rows x 64 nodes per tile, 8 class
+//                      accumulators + Eigen's reduction tree, the exact search's operations in its order), walked over G
 //                      consecutive node tiles per workgroup.  Every row keeps a sorted list of its k smallest keys in LDS;
 //                      after each tile the keys below the row's k-th key are merged into it by rank (position = rank in
 //                      the list + rank among the accepted keys: keys are unique, so positions are), and at the end the
@@ -10,12 +10,9 @@
 //  topk_merge_kernel : one wavefront per row selects the k smallest keys of the node groups' sorted lists (staged in LDS;
 //                      lane g holds the head of list g), applies the node-0 rule and stores idx (u64) and the distance
 //                      row-major.
-// The distance body is a copy of bmd_tile_kernel's: no existing kernel changes.
-#include "vsom_device.hpp"
+#include "vsom_dist_tile.hpp"
 #include <algorithm>
 
-#define TILE 64
-#define LDT 36
 #define TOPK_KMAX 64       // largest k (vsom_bmu_topk_batch refuses more)
 #define TOPK_MAXG 64       // node groups per row at most: one merge lane each
 #define TOPK_NONE (~0ull)  // above every key (a key's node is < 2^32 - 1)
@@ -93,12 +90,7 @@ __global__ __launch_bounds__(256, 2) void topk_tile_kernel(DistArgs a, int s0, i
                                                            u64 *__restrict__ part, unsigned char *__restrict__ nan0)
 {
     constexpr int TS = 16 * TI;                 // samples per tile
-    constexpr int NX = TS * 8 / 256;            // float4 of a sample operand per thread and K-chunk (1 or 2)
     constexpr int Q = 256 / TS;                 // threads per row in the list passes
-    __shared__ __attribute__((aligned(16))) float sx[TILE * LDT];
-    __shared__ __attribute__((aligned(16))) float sm[TILE * LDT];
-    __shared__ __attribute__((aligned(16))) float sy[CLR ? TS * LDT : 4];
-    __shared__ __attribute__((aligned(16))) float sb[CLR ? TILE * LDT : 4];
     __shared__ float sd[TS][TILE + 1];          // the tile's distances
     __shared__ u64 top[TS][TOPK_KMAX + 1];      // each row's k smallest keys so far, ascending (padded against bank aliasing)
     __shared__ unsigned char cpos[TS][TILE];    // merged position of an accepted key (255: out of the list)
@@ -107,8 +99,6 @@ __global__ __launch_bounds__(256, 2) void topk_tile_kernel(DistArgs a, int s0, i
     const int tid0 = threadIdx.x;
     const int lr = tid0 % TS, q = tid0 / TS;      // list passes: row lr, share q of Q
     const int sbase0 = s0 + blockIdx.y * TS;
-    const int L = a.L, L8 = L & ~7;
-    const int nchunks = (L + VSOM_TK - 1) / VSOM_TK;
 
     for (int j = q; j < k; j += Q)
         top[lr][j] = TOPK_NONE;
@@ -127,140 +117,8 @@ __global__ __launch_bounds__(256, 2) void topk_tile_kernel(DistArgs a, int s0, i
         asm volatile("" : "+s"(sbase));
         const int tx = tid & 15, ty = tid >> 4;
 
-        float acc[TI][4][8];
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j)
-#pragma unroll
-                for (int e = 0; e < 8; ++e)
-                    acc[i][j][e] = 0.f;
-
-        float4 gx[NX], gm[2], gy[NX], gb[2];
-        auto gload = [&](int k0) {
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-                int f = tid + 256 * i;
-                int row = f >> 3, c4 = (f & 7) * 4;
-                int s = sbase + row;
-                gx[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                gy[i] = gx[i];
-                if (s < s1) {
-                    gx[i] = *reinterpret_cast<const float4 *>(a.xa + (size_t)s * a.ldx + k0 + c4);
-                    if (CLR)
-                        gy[i] = *reinterpret_cast<const float4 *>(a.xb + (size_t)s * a.ldx + k0 + c4);
-                }
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                int f = tid + 256 * i;
-                int row = f >> 3, c4 = (f & 7) * 4;
-                int n = nbase + row;
-                gm[i] = make_float4(0.f, 0.f, 0.f, 0.f);
-                gb[i] = gm[i];
-                if (n < N) {
-                    gm[i] = *reinterpret_cast<const float4 *>(a.ma + (size_t)n * a.ldm + k0 + c4);
-                    if (CLR)
-                        gb[i] = *reinterpret_cast<const float4 *>(a.mb + (size_t)n * a.ldm + k0 + c4);
-                }
-            }
-        };
-        gload(0);
-        int dk = 0;
-        for (int ch = 0; ch < nchunks; ++ch, dk += VSOM_TK) {
-            if (ch > 0)
-                __syncthreads();
-#pragma unroll
-            for (int i = 0; i < NX; ++i) {
-                int f = tid + 256 * i;
-                int row = f >> 3, c4 = (f & 7) * 4;
-                *reinterpret_cast<float4 *>(&sx[row * LDT + c4]) = gx[i];
-                if (CLR)
-                    *reinterpret_cast<float4 *>(&sy[row * LDT + c4]) = gy[i];
-            }
-#pragma unroll
-            for (int i = 0; i < 2; ++i) {
-                int f = tid + 256 * i;
-                int row = f >> 3, c4 = (f & 7) * 4;
-                *reinterpret_cast<float4 *>(&sm[row * LDT + c4]) = gm[i];
-                if (CLR)
-                    *reinterpret_cast<float4 *>(&sb[row * LDT + c4]) = gb[i];
-            }
-            __syncthreads();
-            if (ch + 1 < nchunks)
-                gload(dk + VSOM_TK);
-#pragma unroll
-            for (int kk = 0; kk < VSOM_TK; kk += 8) {
-                if (dk + kk < L8) {   // whole 8-blocks only; the remainder is handled in Eigen's order below
-#pragma unroll
-                    for (int h = 0; h < 2; ++h) {
-                        float4 xv[TI], mv[4], yv[TI], bv[4];
-#pragma unroll
-                        for (int j = 0; j < 4; ++j) {
-                            mv[j] = *reinterpret_cast<const float4 *>(&sm[(tx + 16 * j) * LDT + kk + 4 * h]);
-                            if (CLR)
-                                bv[j] = *reinterpret_cast<const float4 *>(&sb[(tx + 16 * j) * LDT + kk + 4 * h]);
-                        }
-#pragma unroll
-                        for (int i = 0; i < TI; ++i) {
-                            xv[i] = *reinterpret_cast<const float4 *>(&sx[(ty + 16 * i) * LDT + kk + 4 * h]);
-                            if (CLR)
-                                yv[i] = *reinterpret_cast<const float4 *>(&sy[(ty + 16 * i) * LDT + kk + 4 * h]);
-                        }
-#pragma unroll
-                        for (int i = 0; i < TI; ++i) {
-#pragma unroll
-                            for (int j = 0; j < 4; ++j) {
-                                float r0 = vsom_resid<CLR>(xv[i].x, CLR ? yv[i].x : 0.f, mv[j].x, CLR ? bv[j].x : 0.f);
-                                float r1 = vsom_resid<CLR>(xv[i].y, CLR ? yv[i].y : 0.f, mv[j].y, CLR ? bv[j].y : 0.f);
-                                float r2 = vsom_resid<CLR>(xv[i].z, CLR ? yv[i].z : 0.f, mv[j].z, CLR ? bv[j].z : 0.f);
-                                float r3 = vsom_resid<CLR>(xv[i].w, CLR ? yv[i].w : 0.f, mv[j].w, CLR ? bv[j].w : 0.f);
-                                float p0 = r0 * r0, p1 = r1 * r1, p2 = r2 * r2, p3 = r3 * r3;
-                                acc[i][j][4 * h + 0] = acc[i][j][4 * h + 0] + p0;
-                                acc[i][j][4 * h + 1] = acc[i][j][4 * h + 1] + p1;
-                                acc[i][j][4 * h + 2] = acc[i][j][4 * h + 2] + p2;
-                                acc[i][j][4 * h + 3] = acc[i][j][4 * h + 3] + p3;
-                            }
-                        }
-                    }
-                }
-            }
-        }
-
-        // reduction tree + remainder (the last chunk is still in LDS); keys below the row's current k-th key are accepted
-        const int rem = L - L8;
-        const int roff = L8 - (nchunks - 1) * VSOM_TK;   // column of element L8 inside the last chunk
-#pragma unroll
-        for (int i = 0; i < TI; ++i)
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float q0 = acc[i][j][0] + acc[i][j][4];
-                float q1 = acc[i][j][1] + acc[i][j][5];
-                float q2 = acc[i][j][2] + acc[i][j][6];
-                float q3 = acc[i][j][3] + acc[i][j][7];
-                const int xr = (ty + 16 * i) * LDT + roff, mr = (tx + 16 * j) * LDT + roff;
-                int e = 0;
-                if (rem >= 4) {
-                    float r0 = vsom_resid<CLR>(sx[xr + 0], CLR ? sy[xr + 0] : 0.f, sm[mr + 0], CLR ? sb[mr + 0] : 0.f);
-                    float r1 = vsom_resid<CLR>(sx[xr + 1], CLR ? sy[xr + 1] : 0.f, sm[mr + 1], CLR ? sb[mr + 1] : 0.f);
-                    float r2 = vsom_resid<CLR>(sx[xr + 2], CLR ? sy[xr + 2] : 0.f, sm[mr + 2], CLR ? sb[mr + 2] : 0.f);
-                    float r3 = vsom_resid<CLR>(sx[xr + 3], CLR ? sy[xr + 3] : 0.f, sm[mr + 3], CLR ? sb[mr + 3] : 0.f);
-                    float p0 = r0 * r0, p1 = r1 * r1, p2 = r2 * r2, p3 = r3 * r3;
-                    q0 = q0 + p0;
-                    q1 = q1 + p1;
-                    q2 = q2 + p2;
-                    q3 = q3 + p3;
-                    e = 4;
-                }
-                float t02 = q0 + q2, t13 = q1 + q3;
-                float res = t02 + t13;
-                for (; e < rem; ++e) {
-                    float r = vsom_resid<CLR>(sx[xr + e], CLR ? sy[xr + e] : 0.f, sm[mr + e], CLR ? sb[mr + e] : 0.f);
-                    float p = r * r;
-                    res = res + p;
-                }
-                sd[ty + 16 * i][tx + 16 * j] = res;
-            }
+        vsom_dist_tile<CLR, TI>(a, tid, sbase, s1, nbase, N, VsomMaskNone(),
+                                [&](int i, int j, float res) { sd[ty + 16 * i][tx + 16 * j] = res; });
         __syncthreads();
 
         // accept: the keys below the row's current k-th key (this thread's share of the row: nodes q, q + Q, ...)
@@ -290,16 +148,6 @@ __global__ __launch_bounds__(256, 2) void topk_tile_kernel(DistArgs a, int s0, i
     }
 }
 
-__device__ __forceinline__ u64 topk_wave_min(u64 v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const u64 o = __shfl_xor(v, m);
-        v = o < v ? o : v;
-    }
-    return v;
-}
-
 // One wavefront per row of the slice: the row's ng sorted lists of k keys are staged in LDS (ng * k <= 4096 keys), lane g
 // holds the head of list g, and every round takes the wavefront's smallest head.  The node-0 rule: when d_0 is NaN, node 0
 // comes first and is skipped where the lists hold it.  dist: NULL = not wanted; a NaN distance is stored as 0x7FC00000,
@@ -326,7 +174,7 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const u64 *__restrict__ 
     }
     // (k <= N: the lists hold the k smallest keys, so every counted round takes a real key; every round consumes one key)
     while (cnt < k) {
-        const u64 m = topk_wave_min(head);
+        const u64 m = vsom_wave_min(head);
         if (head == m) {                        // keys are unique: one lane
             ++ptr;
             head = ptr < k ? lists[lane * k + ptr] : TOPK_NONE;
@@ -345,27 +193,6 @@ __global__ __launch_bounds__(64) void topk_merge_kernel(const u64 *__restrict__ 
     }
 }
 
-static DistArgs topk_dist_args(const vsom_ctx *c)
-{
-    DistArgs a;
-    if (c->transform == VSOM_CLR) {
-        a.xa = c->XP.p;
-        a.xb = c->YP.p;
-        a.ldx = (int)c->part_pitch;
-        a.ma = c->map.p;
-        a.mb = c->map.p + c->part_pitch;
-    } else {
-        a.xa = c->Xs.p;
-        a.xb = c->Xs.p;
-        a.ldx = (int)c->xpitch;
-        a.ma = c->map.p;
-        a.mb = c->map.p;
-    }
-    a.ldm = (int)c->pitch;
-    a.L = (int)c->part_len;
-    return a;
-}
-
 // rows per slice: the partial lists of a slice (at most TOPK_MAXG groups of k keys per row) stay within 64 MiB
 static size_t vsom_topk_slice_rows(uint32_t k)
 {
@@ -380,17 +207,14 @@ int launch_topk(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out
         return VSOM_OK;
     const size_t slice = std::min(vsom_topk_slice_rows(k), rows);
     const int TS = c->transform == VSOM_CLR ? 32 : TILE;
-    const size_t ntiles = (N + TILE - 1) / TILE;
-    // node groups: enough workgroups to fill the chip (2048: four rounds of two per CU) and at most TOPK_MAXG lists per
-    // row to merge; G consecutive node tiles per group
-    const size_t rtiles = (slice + TS - 1) / TS;
-    const size_t want = std::min<size_t>({(size_t)TOPK_MAXG, ntiles, std::max<size_t>(1, (2048 + rtiles - 1) / rtiles)});
-    const size_t G = (ntiles + want - 1) / want, ng = (ntiles + G - 1) / G;
+    // node groups: at most TOPK_MAXG lists per row to merge
+    const VsomNodeGroups grp = vsom_node_groups((N + TILE - 1) / TILE, (slice + TS - 1) / TS, TOPK_MAXG);
+    const size_t G = grp.G, ng = grp.ng;
     VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_SYNC,
                                    {vsom_member(c->topk_part, slice * ng * k), vsom_member(c->topk_idx, slice * k),
                                     vsom_member(c->topk_dist, dist_out ? slice * k : 0),
                                     vsom_member(c->topk_nan0, slice)}));
-    const DistArgs a = topk_dist_args(c);
+    const DistArgs a = vsom_dist_args(c);
     for (size_t s0 = r0; s0 < r1; s0 += slice) {
         const size_t s1 = std::min(r1, s0 + slice), n = s1 - s0, off = s0 - r0;
         dim3 grid((unsigned)ng, (unsigned)((n + TS - 1) / TS));
