@@ -109,7 +109,7 @@ typedef enum vsom_buffer {
 typedef enum vsom_timer {
     VSOM_T_STAGE = 0,      /* chunk re-layout kernels                           */
     VSOM_T_BMU = 1,        /* full / local BMU search kernels                   */
-    VSOM_T_FINISH = 2,     /* bmuHits + MSE; vsom_similarity_batch's scoring kernel */
+    VSOM_T_FINISH = 2,     /* bmuHits + MSE; vsom_similarity_batch's / vsom_evaluate_batch's scoring kernel */
     VSOM_T_CW = 3,         /* neighbourhood weight chain (w, w/W) kernel        */
     VSOM_T_UPDATE = 4,     /* mean / sigma^2 chain kernel                       */
     VSOM_T_ONLINE = 5,     /* online (trainSingle) kernels                      */
@@ -369,6 +369,50 @@ typedef struct vsom_masked_out {
 } vsom_masked_out;
 int vsom_bmu_masked_batch(vsom_ctx *ctx, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
                           vsom_masked_out *out);
+/* Som::evaluate (Som.cpp:490-523), the validation loss of a map, for chunk rows [r0, r1): every row is searched, scored
+ * against its best matching unit, and the running mean of :519 is taken -- one call, one stream wait, nothing of size
+ * N x D moves.
+ * Search: b = Som::findBmu(x_r) for EVERY row of the chunk, exactly as vsom_bmu_batch (the same path, the shortlist
+ * included; every vsom_set_bmu_mode gives the same indices); it overwrites the chunk's lastBMU / sqres like that call.  The
+ * built-in comparers ignore `valid`, so the distance is unmasked ("as written").
+ * Per column d < C = min(J, D), in fp32 with one rounding per operation, nothing contracted, no fast-math log:
+ * m = map[b][d], x = x_r[d],
+ *   be   = log(m) * x + log(1.0f - m) * (1.0f - x)              (:509; the reference's never-filled `ones` taken as ones)
+ *   be   = (isnan(be) || isinf(be)) ? -99999.0f : be            (:512)
+ *   val  = valid ? continuous_host[d] : 0.0f                    (:505; column d of row r is valid iff valid_host == NULL
+ *                                                                or valid_host[(r - r0) * J + d] != 0)
+ *   t    = (be * binary_host[d]) * val                          (:514, in that order)
+ *   bsum = t.dot(t) over d = 0..C-1 in Eigen's packet order (two 4-wide accumulators over the multiples of 8,
+ *          p0 += p1, the packet tail, (p0[0] + p0[2]) + (p0[1] + p0[3]), the scalar tail) -- the order of every other
+ *          r.dot(r) of this library.
+ * Outputs (host pointers, each may be NULL; entry r - r0 belongs to row r):
+ *   bmu, dist   b and euclidianWeightedDist(b, x_r): what vsom_bmu_batch returns, bit for bit (a NaN distance is 0x7FC00000)
+ *   bsum        binaryError.dot(binaryError) of the row, before the sqrt of :519
+ *   nrepl       the number of columns d < C whose term was replaced by -99999 and whose factor is non-zero
+ *               (binary_host[d] != 0 and val != 0)
+ *   error[1]    error += 1.0 / (i + 1.0) * ((double)dist + sqrt((double)bsum) - error) in row order, i counted from 0 at r0,
+ *               evaluated on the host from the returned dist / bsum
+ * Accuracy: only log can differ from a CPU restatement.  For x in [0,1] and m in (0,1) both products of be have the same
+ * sign, nothing cancels, and with L the device log's error bound in ulps bsum lies within (C + 2 L + 4) * 2^-24 relative of
+ * the float64 value computed from the fp32 operands (1.0f - m and 1.0f - x formed in fp32 first); the sqrt halves it.
+ * L = 1 is taken (csrc/vsom_evaluate.hip names the source and labels the assumption).  A zero factor, a replaced term,
+ * the search outputs and the running mean of the returned values carry no tolerance.  With binary_host all 0 every t
+ * is +-0, bsum is 0 and error is the running mean of vsom_bmu_batch's distances.
+ * Read-only apart from lastBMU / sqres: map, sigmaMap, S, weightMap, bmuHits and the chunk are untouched.  Refuses
+ * (VSOM_ERR_INVALID, nothing enqueued, the context stays usable): a null context, out, binary_host or continuous_host,
+ * custom contexts, no chunk, a chunk staged ahead, r0 > r1 or r1 > B.  An empty range returns VSOM_OK, enqueues nothing
+ * (no search) and writes *error = 0.  Device scratch: 20 bytes per row, the validity bytes when given, 8 J bytes of column
+ * arrays; one grow-only set.  valid_host travels straight from the caller's memory, the column arrays and the per-row
+ * results through pinned memory of the context; the scoring launch is timed under VSOM_T_FINISH. */
+typedef struct vsom_evaluate_out {
+    uint64_t *bmu;
+    float *dist;
+    float *bsum;
+    uint32_t *nrepl;
+    double *error;
+} vsom_evaluate_out;
+int vsom_evaluate_batch(vsom_ctx *ctx, size_t r0, size_t r1, const float *binary_host, const float *continuous_host,
+                        const uint8_t *valid_host, vsom_evaluate_out *out);
 /* Som::euclidianWeightedDistRaw(pos, v, ones, ones) (Som.cpp:143-157) for `count` pairs; v is
  * chunk row vrows[i] (from_map = 0) or model vector vrows[i] (from_map = 1, the U-matrix case). */
 int vsom_distances_raw(vsom_ctx *ctx, const uint64_t *nodes_host, const uint64_t *vrows_host,

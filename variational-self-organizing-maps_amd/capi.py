@@ -48,7 +48,7 @@ SYMBOLS = [
     "vsom_ensemble_create", "vsom_ensemble_destroy", "vsom_ensemble_size", "vsom_ensemble_train_online_chunk_fetch",
     "vsom_ensemble_batch_epoch", "vsom_ensemble_upload_chunks", "vsom_ensemble_bmu_batch",
     "vsom_umatrix", "vsom_get_umatrix", "vsom_ensemble_umatrix", "vsom_similarity_batch",
-    "vsom_bmu_masked_batch",
+    "vsom_bmu_masked_batch", "vsom_evaluate_batch",
 ]
 
 
@@ -63,6 +63,12 @@ class MaskedOut(C.Structure):
     """vsom_masked_out: host pointers, each may be NULL"""
     _fields_ = [("bmu", C.POINTER(C.c_uint64)), ("dist", C.POINTER(C.c_float)), ("nvalid", C.POINTER(C.c_uint32)),
                 ("fill", C.POINTER(C.c_float))]
+
+
+class EvaluateOut(C.Structure):
+    """vsom_evaluate_out: host pointers, each may be NULL"""
+    _fields_ = [("bmu", C.POINTER(C.c_uint64)), ("dist", C.POINTER(C.c_float)), ("bsum", C.POINTER(C.c_float)),
+                ("nrepl", C.POINTER(C.c_uint32)), ("error", C.POINTER(C.c_double))]
 
 
 class VsomError(RuntimeError):
@@ -235,6 +241,7 @@ def lib():
                                             C.POINTER(C.c_uint8), C.POINTER(SimilarityOut)]
     L.vsom_bmu_masked_batch.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8), C.c_int,
                                         C.POINTER(MaskedOut)]
+    L.vsom_evaluate_batch.argtypes = [vp, C.c_size_t, C.c_size_t, fp, fp, C.POINTER(C.c_uint8), C.POINTER(EvaluateOut)]
     _lib = L
     return L
 
@@ -577,6 +584,39 @@ class Context:
                 setattr(out, name, res[name].ctypes.data_as(ctype))
         check(lib().vsom_similarity_batch(self._h, int(min_hits), int(num_sigmas), int(sigma_rule), r0, r1,
                                           None if vb is None else vb.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(out)))
+        return res
+
+    def evaluate(self, binary, continuous, valid=None, r0=0, r1=None):
+        """Som::evaluate of chunk rows [r0, r1) in one call (vsom_evaluate_batch): every row searched (findBmu, as
+        bmu_batch) and its binary error scored against its BMU.  binary, continuous: J column factors each.  valid: None,
+        or rows x J, nonzero = valid.  A dict: bmu (uint64), dist, bsum (float32), nrepl (uint32) with one entry per row,
+        and error (float), the running mean of dist + sqrt(bsum) over the rows.  Overwrites the chunk's lastBMU / sqres
+        like bmu_batch."""
+        B = self.chunk_size
+        r0 = int(r0)
+        r1 = B if r1 is None else int(r1)
+        if r0 < 0 or r0 > r1 or r1 > B:
+            raise ValueError(f"row range [{r0}, {r1}) is not within the chunk's {B} rows")
+        n = r1 - r0
+        cols = []
+        for name, a in (("binary", binary), ("continuous", continuous)):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (self.in_len,):
+                raise ValueError(f"{name} has shape {a.shape}, not ({self.in_len},)")
+            cols.append(a)
+        vb = None
+        if valid is not None:
+            vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+            if vb.shape != (n, self.in_len):
+                raise ValueError(f"valid has shape {vb.shape}, not ({n}, {self.in_len})")
+        res = {"bmu": np.empty(n, np.uint64), "dist": np.empty(n, np.float32), "bsum": np.empty(n, np.float32),
+               "nrepl": np.empty(n, np.uint32), "error": np.zeros(1, np.float64)}
+        out = EvaluateOut()
+        for name, ctype in EvaluateOut._fields_:
+            setattr(out, name, res[name].ctypes.data_as(ctype))
+        check(lib().vsom_evaluate_batch(self._h, r0, r1, _f(cols[0]), _f(cols[1]),
+                                        None if vb is None else vb.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(out)))
+        res["error"] = float(res["error"][0])
         return res
 
     def bmu_masked(self, valid, r0=0, r1=None, min_hits=0, fill=False):

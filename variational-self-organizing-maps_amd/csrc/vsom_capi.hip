@@ -857,6 +857,23 @@ int vsom_similarity_batch(vsom_ctx *c, uint64_t min_hits, int num_sigmas, int si
     return launch_similarity(c, min_hits, num_sigmas, sigma_rule, r0, r1, valid_host, out);
 }
 
+int vsom_evaluate_batch(vsom_ctx *c, size_t r0, size_t r1, const float *binary_host, const float *continuous_host,
+                        const uint8_t *valid_host, vsom_evaluate_out *out)
+{
+    CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_evaluate_batch");
+    CHECK_ROWS(c);
+    if (!out)
+        return vsom_fail(VSOM_ERR_INVALID, "out is null");
+    if (!binary_host || !continuous_host)
+        return vsom_fail(VSOM_ERR_INVALID, "binary_host or continuous_host is null");
+    if (c->B == 0)
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    if (r0 > r1 || r1 > c->B)
+        return vsom_fail(VSOM_ERR_INVALID, "row range out of bounds");
+    return launch_evaluate(c, r0, r1, binary_host, continuous_host, valid_host, out);
+}
+
 int vsom_bmu_masked_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
                           vsom_masked_out *out)
 {

@@ -1,0 +1,238 @@
+// vsom_evaluate.hip -- Som::evaluate (Som.cpp:490-523), the validation loss of a map, for chunk rows [r0, r1): findBmu of the
+// staged chunk (vsom_bmu_batch's path), one launch that scores every row against its BMU, the running mean on the host (gfx950).
+//
+//  evaluate_kernel : eight lanes per row, eight rows per wavefront.  A row's lastBMU entry names the model row to gather.
+//                    Per logical column d < C = min(J, D), in fp32 with one rounding per operation, nothing contracted:
+//                      be = log(m) * x + log(1.0f - m) * (1.0f - x) (:509), NaN / inf -> -99999.0f (:512),
+//                      val = valid ? continuous[d] : 0.0f (:505), t = (be * binary[d]) * val (:514), bsum = t.dot(t) (:519).
+//                    The sum takes Eigen's packet order (tests/pyref.py:dot_self), which the contract fixes, so
+//                    the row is NOT reduced by a 64-lane tree: lane c of a row's eight owns element c of the two 4-wide
+//                    packet accumulators and walks the columns 8k + c < a2 = C / 8 * 8 in order; lane c also squares the
+//                    one column a2 + c behind them.  Then, with cross-lane moves inside the eight: p0 += p1 (lane c takes
+//                    lane c + 4), the packet tail when C - a2 >= 4 (lanes 0..3 add their own column), (p0[0] + p0[2]) +
+//                    (p0[1] + p0[3]), and the at most three scalar-tail columns added one by one.  Accumulators start at +0:
+//                    +0 + p = p exactly for a square p, so every branch of Eigen's redux (C < 4, 4 <= C < 8, C >= 8) is this
+//                    one sequence.  No LDS, no atomics; lane 0 of the eight stores the row's five words.
+//                    A column whose factor is an exact zero -- binary[d] == 0 with a finite val, or val == 0 with a finite
+//                    binary[d] -- has t = +-0 whatever m and x hold (be is finite after :512), and adding its +0 changes no
+//                    accumulator: such a column is skipped before anything of the row is gathered.  With the usual few
+//                    binary columns the kernel reads the column arrays and the validity bytes and little else.
+// What bounds it: the dependent gather lastBMU -> model row (as similarity_kernel), then for the columns that count two
+// logs each; a row's eight lanes read 32 consecutive bytes per step, four steps in flight.  Memory traffic per row: J validity
+// bytes when given, 8 bytes (x and m) per counting column; the two column arrays stay in cache.
+// log is the device math library's single-precision logf (-fno-fast-math: the accurate form, denormals kept).  No statement
+// of its error bound ships with the ROCm installation this was written against; HIP's published table of device math
+// functions gives 1 ulp for logf, and the project already relies on the same library's "within an ulp" for exp in
+// vsom_bmd_batch.  The tolerance of include/vsom_hip.h therefore takes L = 1 AS AN ASSUMPTION.
+// Against the host loop this call replaces in the C++ mirror (libm logf, a sequential sum) the value of a data set with
+// binary columns moves within that tolerance; with no binary column every t is +-0, bsum is 0 and the value is the same bits.
+#include "vsom_device.hpp"
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#define EV_LANES 8          // lanes per row: one per element of the two Packet4f accumulators
+#define EV_ROWS_PER_WG 32   // four wavefronts of eight rows
+#define EV_ROW_WORDS 5      // bmu (2), dist, bsum, nrepl
+#define EV_STEPS 4          // steps whose loads are in flight together
+
+struct EvArgs {
+    const float *x;             // staged rows (Xs), pitch ldx
+    const float *map;           // model rows, pitch ldm
+    const u64 *lastbmu;
+    const float *sqres;
+    const unsigned char *valid; // rows [r0, r1) x J, or null: every column valid
+    const float *binary, *continuous;   // [J]
+    unsigned *rows;             // per-row results of [r0, r1): EV_ROW_WORDS arrays of R entries
+    int ldx, ldm, part_len, part_pitch;
+    int J, C, N, R;
+};
+
+// the factor of a column is an exact zero: t = +-0 for every finite be
+__device__ __forceinline__ bool ev_zero(float fb, float val)
+{
+    const float inf = __builtin_inff();
+    return (fb == 0.f && fabsf(val) < inf) || (val == 0.f && fabsf(fb) < inf);
+}
+
+// t * t of one column; counts a replaced term whose factor is non-zero
+__device__ __forceinline__ float ev_square(float x, float m, float fb, float val, uint32_t &nrepl)
+{
+    const float lm = logf(m);
+    const float om = 1.0f - m;
+    const float l1 = logf(om);
+    const float ox = 1.0f - x;
+    const float a = lm * x;
+    const float b = l1 * ox;
+    float be = a + b;
+    const bool repl = !(fabsf(be) < __builtin_inff());      // NaN or +-inf
+    be = repl ? -99999.0f : be;
+    const float tb = be * fb;
+    const float t = tb * val;
+    nrepl += (repl && fb != 0.f && val != 0.f) ? 1u : 0u;
+    return t * t;
+}
+
+// CLR: the model row has two parts, logical column d at (d / part_len) * part_pitch + d % part_len (as similarity_kernel<false>)
+template <bool CLR>
+__global__ __launch_bounds__(EV_LANES * EV_ROWS_PER_WG) void evaluate_kernel(EvArgs a, int r0, int r1)
+{
+    const int c = threadIdx.x & (EV_LANES - 1);
+    const int row = r0 + (int)blockIdx.x * EV_ROWS_PER_WG + (int)(threadIdx.x / EV_LANES);
+    const bool live = row < r1;
+    const int r = live ? row : r1 - 1;              // (a dead eight repeats the last row and stores nothing)
+    u64 b = a.lastbmu[r];
+    b = b < (u64)a.N ? b : 0;                       // (the searches store indices below N)
+    const float *xr = a.x + (size_t)r * a.ldx;
+    const float *mr = a.map + (size_t)b * a.ldm;
+    const unsigned char *vr = a.valid ? a.valid + (size_t)(r - r0) * a.J : nullptr;
+    const int C = a.C, a2 = C / 8 * 8;
+
+    auto factor = [&](int d, float &fb, float &val) -> bool {      // false: the column adds +0
+        fb = a.binary[d];
+        const float fc = a.continuous[d];
+        val = (vr && vr[d] == 0) ? 0.0f : fc;
+        return !ev_zero(fb, val);
+    };
+    auto model = [&](int d) -> float {
+        if constexpr (CLR) {
+            const int part = d / a.part_len;
+            return mr[part * a.part_pitch + (d - part * a.part_len)];
+        } else {
+            return mr[d];
+        }
+    };
+
+    float acc = 0.f;
+    uint32_t nrepl = 0;
+    for (int d0 = c; d0 < a2; d0 += 8 * EV_STEPS) {
+        float fb[EV_STEPS], val[EV_STEPS], xv[EV_STEPS], mv[EV_STEPS];
+        bool on[EV_STEPS];
+#pragma unroll
+        for (int u = 0; u < EV_STEPS; ++u) {
+            const int d = d0 + 8 * u;
+            on[u] = d < a2 && factor(d, fb[u], val[u]);
+        }
+#pragma unroll
+        for (int u = 0; u < EV_STEPS; ++u) {
+            const int d = d0 + 8 * u;
+            if (on[u]) {
+                xv[u] = xr[d];
+                mv[u] = model(d);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < EV_STEPS; ++u)
+            if (on[u])
+                acc += ev_square(xv[u], mv[u], fb[u], val[u], nrepl);
+    }
+    // the one column behind the multiples of 8 that this lane owns: packet tail (C - a2 >= 4: lanes 0..3) or scalar tail
+    float q = 0.f;
+    {
+        const int d = a2 + c;
+        float fb, val;
+        if (d < C && factor(d, fb, val))
+            q = ev_square(xr[d], model(d), fb, val, nrepl);
+    }
+    const int rest = C - a2;                        // 0..7
+    const bool ptail = rest >= 4;
+    float s = acc + __shfl_xor(acc, 4);             // p0 += p1 (lanes 0..3)
+    if (ptail)
+        s += q;                                     // p0 += the packet tail (lanes 0..3)
+    s = s + __shfl_xor(s, 2);                       // lane 0: p0[0] + p0[2], lane 1: p0[1] + p0[3]
+    s = s + __shfl_xor(s, 1);                       // lane 0: (p0[0] + p0[2]) + (p0[1] + p0[3])
+    const int t0 = ptail ? 4 : 0, nt = rest - t0;   // the scalar tail: lanes t0 .. t0 + nt - 1, nt <= 3
+    const int base = (int)(threadIdx.x & 63) & ~(EV_LANES - 1);
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+        const float qj = __shfl(q, base + t0 + j);
+        if (j < nt)
+            s += qj;
+    }
+#pragma unroll
+    for (int m = 4; m >= 1; m >>= 1)
+        nrepl += __shfl_xor(nrepl, m);
+    if (live && c == 0) {
+        const size_t i = (size_t)(r - r0), R = (size_t)a.R;
+        reinterpret_cast<u64 *>(a.rows)[i] = a.lastbmu[r];
+        a.rows[2 * R + i] = __float_as_uint(a.sqres[r]);
+        a.rows[3 * R + i] = __float_as_uint(s);
+        a.rows[4 * R + i] = nrepl;
+    }
+}
+
+int launch_evaluate(vsom_ctx *c, size_t r0, size_t r1, const float *binary_host, const float *continuous_host,
+                    const uint8_t *valid_host, const vsom_evaluate_out *out)
+{
+    const size_t rows = r1 - r0;
+    if (rows == 0) {
+        if (out->error)
+            *out->error = 0.0;
+        return VSOM_OK;
+    }
+    const size_t J = c->J, C = std::min<size_t>(c->J, c->D);
+    // grow-only: a member keeps what it has when this call needs less.  The pinned image holds the two column arrays on
+    // their way in (behind the rows' words) and the rows' words on their way out.
+    const size_t words = rows * EV_ROW_WORDS;
+    VSOM_ALLOC_CHECK(vsom_grow_set(
+        c->stream, VSOM_BUF_SYNC,
+        {vsom_member(c->ev_rows, std::max(c->ev_rows.cap, words)), vsom_member(c->ev_pinned, std::max(c->ev_pinned.cap, words + 2 * J)),
+         vsom_member(c->ev_valid, std::max(c->ev_valid.cap, valid_host ? rows * J : 0)),
+         vsom_member(c->ev_cols, std::max(c->ev_cols.cap, 2 * J))}));
+
+    int rc = launch_bmu_full(c, 0, c->B);           // findBmu of the whole chunk, as vsom_bmu_batch
+    if (rc)
+        return rc;
+    float *cols = reinterpret_cast<float *>(c->ev_pinned.p + words);
+    std::memcpy(cols, binary_host, J * 4);
+    std::memcpy(cols + J, continuous_host, J * 4);
+    VSOM_HIP_CHECK(hipMemcpyAsync(c->ev_cols.p, cols, 2 * J * 4, hipMemcpyHostToDevice, c->stream));
+    if (valid_host)
+        VSOM_HIP_CHECK(hipMemcpyAsync(c->ev_valid.p, valid_host, rows * J, hipMemcpyHostToDevice, c->stream));
+
+    EvArgs a;
+    a.x = c->Xs.p;
+    a.map = c->map.p;
+    a.lastbmu = c->lastbmu.p;
+    a.sqres = c->sqres.p;
+    a.valid = valid_host ? c->ev_valid.p : nullptr;
+    a.binary = c->ev_cols.p;
+    a.continuous = c->ev_cols.p + J;
+    a.rows = c->ev_rows.p;
+    a.ldx = (int)c->xpitch;
+    a.ldm = (int)c->pitch;
+    a.part_len = (int)c->part_len;
+    a.part_pitch = (int)c->part_pitch;
+    a.J = (int)J;
+    a.C = (int)C;
+    a.N = (int)c->N;
+    a.R = (int)rows;
+    {
+        TimerScope ts(c, VSOM_T_FINISH);
+        const dim3 grid((unsigned)((rows + EV_ROWS_PER_WG - 1) / EV_ROWS_PER_WG)), block(EV_LANES * EV_ROWS_PER_WG);
+        if (c->nparts == 1)
+            hipLaunchKernelGGL(evaluate_kernel<false>, grid, block, 0, c->stream, a, (int)r0, (int)r1);
+        else
+            hipLaunchKernelGGL(evaluate_kernel<true>, grid, block, 0, c->stream, a, (int)r0, (int)r1);
+        VSOM_HIP_CHECK(hipGetLastError());
+    }
+    VSOM_HIP_CHECK(hipMemcpyAsync(c->ev_pinned.p, c->ev_rows.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+
+    const unsigned *p = c->ev_pinned.p;
+    if (out->bmu)
+        std::memcpy(out->bmu, p, rows * 8);
+    void *dst[3] = {out->dist, out->bsum, out->nrepl};
+    for (int i = 0; i < 3; ++i)
+        if (dst[i])
+            std::memcpy(dst[i], p + (size_t)(i + 2) * rows, rows * 4);
+    if (out->error) {
+        // Som.cpp:519, the running mean in row order
+        const float *dist = reinterpret_cast<const float *>(p + 2 * rows), *bsum = reinterpret_cast<const float *>(p + 3 * rows);
+        double error = 0;
+        for (size_t i = 0; i < rows; ++i)
+            error += 1.0 / ((double)i + 1.0) * ((double)dist[i] + std::sqrt((double)bsum[i]) - error);
+        *out->error = error;
+    }
+    return VSOM_OK;
+}

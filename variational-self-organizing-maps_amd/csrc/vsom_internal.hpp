@@ -200,6 +200,12 @@ struct vsom_ctx {
     PinnedBuf<unsigned> sim_pinned;
     DevBuf<unsigned char> sim_valid;
     DevBuf<float> sim_delta;
+    // vsom_evaluate_batch (vsom_evaluate.hip): the per-row results of a call and their pinned host image (which also stages
+    // the two column arrays on their way in), the validity bytes when given, the column arrays; one set, grow-only
+    DevBuf<unsigned> ev_rows;
+    PinnedBuf<unsigned> ev_pinned;
+    DevBuf<unsigned char> ev_valid;
+    DevBuf<float> ev_cols;
     // vsom_bmu_masked_batch (vsom_masked.hip): a row slice's validity bytes as given and packed (0xFF / 0x00, xpitch per row),
     // its node groups' keys, its results and node-0 NaN flags, its imputed rows; one set, grow-only
     DevBuf<unsigned char> msk_raw, msk_valid, msk_nan0;
@@ -293,6 +299,10 @@ int launch_topk(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out
 // vsom_similarity.hip: search + scoring of chunk rows [r0,r1) (arguments checked by vsom_similarity_batch); synchronises
 int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
                       const uint8_t *valid_host, const vsom_similarity_out *out);
+// vsom_evaluate.hip: search + scoring of chunk rows [r0,r1) and the running mean (arguments checked by vsom_evaluate_batch);
+// synchronises
+int launch_evaluate(vsom_ctx *c, size_t r0, size_t r1, const float *binary_host, const float *continuous_host,
+                    const uint8_t *valid_host, const vsom_evaluate_out *out);
 // vsom_masked.hip: the search over valid columns of chunk rows [r0,r1) (arguments checked by vsom_bmu_masked_batch); synchronises
 int launch_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
                   const vsom_masked_out *out);

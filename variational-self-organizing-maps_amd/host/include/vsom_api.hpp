@@ -503,6 +503,18 @@ public:
     // [MI355X build] extension: rows x sample length, row-major: every row of `data` with its invalid columns filled from
     // the model vector of its findMaskedBmus unit (the same call).
     std::vector<float> impute(const DataSet *data, size_t minBmuHits) const;
+    // [MI355X build] extension: what evaluate sums, for every row of `data` (one vsom_evaluate_batch call, include/vsom_hip.h):
+    // the row's BMU and its distance, bsum = binaryError.dot(binaryError) (Som.cpp:509-514, before the sqrt of :519), the
+    // number of terms replaced by -99999 that count, and the running mean `error` evaluate returns.  The data set's
+    // getBinary / getContinuous are the column factors, its validity flags the mask.  Built-in transformations on the
+    // device only; throws when the data set holds a validity flag outside {0, 1} (the byte mask cannot carry it).
+    struct EvaluateRows {
+        std::vector<uint64_t> bmu;
+        std::vector<float> dist, bsum;
+        std::vector<uint32_t> nrepl;
+        double error = 0;
+    };
+    EvaluateRows evaluateRows(const DataSet &data) const;
     // the finish of measureSimilarity from such a report: the row the reference reports (Som.cpp:684-690: one running
     // maximum over every delta of every row, compared signed, stored as fabs); 0 when no delta exceeds the start value
     static size_t measureSimilarityRow(const std::vector<float> &first, const std::vector<float> &dmax);
@@ -594,6 +606,7 @@ private:
                            WeigthDecayFunction fn, bool updateUMatrixAfterEpoch);
     void createContext();
     void requireDevicePath(const char *what) const;
+    bool evaluateOnDevice(const DataSet &data, EvaluateRows &r) const;   // false: a validity flag outside {0, 1}
     void maskedRows(const DataSet *data, size_t minBmuHits, uint64_t *bmu, float *dist, float *fill) const;
     void refreshHost() const;
     void stageOne(const Eigen::VectorXf &v) const;

@@ -1406,14 +1406,69 @@ void Som::updateUMatrix(const Eigen::VectorXf &)
         }
 }
 
+// upload, one vsom_evaluate_batch call: the search, the binary error of every row and the running mean on the device
+// state, no refreshHost().  The validity flags are collected row by row, as similarityRows does; a flag outside {0, 1}
+// (the reference multiplies the integer, :505; no loader produces one) does not fit the byte mask: false, nothing done.
+bool Som::evaluateOnDevice(const DataSet &data, EvaluateRows &r) const
+{
+    const size_t n = data.size();
+    r.bmu.assign(n, 0);
+    r.dist.assign(n, 0.f);
+    r.bsum.assign(n, 0.f);
+    r.nrepl.assign(n, 0);
+    r.error = 0;
+    if (n == 0)
+        return true;
+    std::vector<uint8_t> valid(n * inLen, 0);   // (a column the data set has no flag for does not count)
+    for (size_t i = 0; i < n; ++i) {
+        const Eigen::VectorXi v = data.getValidity(i);
+        const size_t m = std::min<size_t>((size_t)v.size(), inLen);
+        for (size_t d = 0; d < m; ++d) {
+            if (v[(Eigen::Index)d] != 0 && v[(Eigen::Index)d] != 1)
+                return false;
+            valid[i * inLen + d] = (uint8_t)v[(Eigen::Index)d];
+        }
+    }
+    const Eigen::ArrayXi continuous = data.getContinuous(), binary = data.getBinary();
+    std::vector<float> fb(inLen, 0.f), fc(inLen, 0.f);
+    for (size_t d = 0; d < inLen; ++d) {
+        fb[d] = d < (size_t)binary.size() ? (float)binary[(Eigen::Index)d] : 0.f;
+        fc[d] = d < (size_t)continuous.size() ? (float)continuous[(Eigen::Index)d] : 0.f;
+    }
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data.contiguous(), n), "vsom_upload_chunk");
+    vsom_evaluate_out out = {r.bmu.data(), r.dist.data(), r.bsum.data(), r.nrepl.data(), &r.error};
+    check(vsom_evaluate_batch(ctx, 0, n, fb.data(), fc.data(), valid.data(), &out), "vsom_evaluate_batch");
+    return true;
+}
+
+Som::EvaluateRows Som::evaluateRows(const DataSet &data) const
+{
+    requireDevicePath("evaluateRows");
+    if (transform.kind() == vsom::Custom)
+        throw std::runtime_error("evaluateRows: a Transformation::Device Som has no per-row report: vsom_evaluate_batch "
+                                 "scores the built-in transformations only; Som::evaluate serves it through the host loop");
+    EvaluateRows r;
+    if (!evaluateOnDevice(data, r))
+        throw std::runtime_error("evaluateRows: the data set holds a validity flag outside {0, 1}");
+    return r;
+}
+
 // Som.cpp:490-523.  The reference's `ones` array is constructed but never filled (ArrayXf(rows,1),
-// :495); it is taken to be all ones here.  log is libm's logf (Eigen's vectorised plog may differ
-// in the last bits).
+// :495); it is taken to be all ones here.  On a context of a built-in transformation: one vsom_evaluate_batch call (the
+// device's log, Eigen's order of the sum).  The host loop below stays for the caller's hooks, host or device source, and
+// for a data set with a validity flag outside {0, 1}; its log is libm's logf and its sum sequential, so with binary
+// columns the two differ within the tolerance of include/vsom_hip.h; with none both give the same bits.
 double Som::evaluate(const DataSet &data) const
 {
     const size_t n = data.size();
     if (n == 0)
         return 0.0;
+    if (ctx && transform.kind() != vsom::Custom) {
+        EvaluateRows r;
+        if (evaluateOnDevice(data, r))
+            return r.error;
+    }
     std::vector<uint64_t> bmu(n);
     std::vector<float> dist(n);
     const Eigen::ArrayXi continuous = data.getContinuous(), binary = data.getBinary();
@@ -1429,7 +1484,7 @@ double Som::evaluate(const DataSet &data) const
             bmu[i] = hostFindBmu(x, val, w);
             dist[i] = (float)hostDist((size_t)bmu[i], x, val, w);
         }
-    } else {
+    } else {   // a Transformation::Device Som (vsom_evaluate_batch refuses custom contexts), or a validity flag outside {0, 1}
         refreshHost();
         check(vsom_upload_chunk(ctx, data.contiguous(), n), "vsom_upload_chunk");
         check(vsom_bmu_batch(ctx, bmu.data(), dist.data()), "vsom_bmu_batch");   // findBmu + euclidianWeightedDist(bmu)

@@ -371,6 +371,30 @@ class Som:
         rep = self.similarityRows(X, numOfSigmas, minBmuHits, floor=False, valid=getattr(data, "validity", None))
         return measure_similarity_from_rows(rep["first"], rep["dmax"], rep["outside"])[1]
 
+    # ---- validation loss (Som.cpp:490-523) -------------------------------------------------------
+    def evaluateRows(self, data, binary=None, continuous=None, valid=None):
+        """extension: what Som::evaluate sums, for every loaded row of `data` (capi.Context.evaluate): the row's BMU and
+        its distance, bsum (binaryError.dot(binaryError)), nrepl (terms replaced by -99999 that count), and the running
+        mean `error`.  binary defaults to all 0, continuous to all 1 (DataSet::getBinary / getContinuous of a data set
+        that flags nothing binary); valid: rows x J, nonzero = valid -- when None it comes from the data set if that has
+        one (an attribute `validity`), as in measureSimilarity, and otherwise every column is valid."""
+        if valid is None:
+            valid = getattr(data, "validity", None)
+        X = self._rows(data)
+        J = self.ctx.in_len
+        binary = np.zeros(J, np.float32) if binary is None else binary
+        continuous = np.ones(J, np.float32) if continuous is None else continuous
+        self.ctx.upload_chunk(X)
+        if X.shape[0] == 0:
+            return {"bmu": np.zeros(0, np.uint64), "dist": np.zeros(0, np.float32), "bsum": np.zeros(0, np.float32),
+                    "nrepl": np.zeros(0, np.uint32), "error": 0.0}
+        return self.ctx.evaluate(binary, continuous, valid=valid)
+
+    def evaluate(self, data, binary=None, continuous=None, valid=None):
+        """Som::evaluate: the mean over the loaded rows of `data` of the distance to the BMU plus the norm of the binary
+        error (arguments as evaluateRows)."""
+        return self.evaluateRows(data, binary, continuous, valid)["error"]
+
     # ---- search over the valid columns, imputation, classification (extensions) ----------------
     def _masked(self, data, valid, minBmuHits, fill):
         X = self._rows(data)
