@@ -9,9 +9,11 @@
 
 static std::set<void *> g_live;        // allocations not yet freed
 static long g_calls = 0, g_fail_at = -1, g_errors = 0;
+static long g_releases = 0, g_pinned_allocs = 0, g_pinned_releases = 0;
 
-static hipError_t fake_alloc(void **p, size_t bytes, bool)
+static hipError_t fake_alloc(void **p, size_t bytes, bool pinned)
 {
+    g_pinned_allocs += pinned;
     if (g_calls++ == g_fail_at) {
         *p = nullptr;
         return hipErrorOutOfMemory;
@@ -22,13 +24,24 @@ static hipError_t fake_alloc(void **p, size_t bytes, bool)
     return hipSuccess;
 }
 
-static hipError_t fake_release(void *p, bool)
+static hipError_t fake_release(void *p, bool pinned)
 {
+    ++g_releases;
+    g_pinned_releases += pinned;
     if (!g_live.erase(p)) {
         std::printf("freed a pointer that is not live (double free or foreign)\n");
         ++g_errors;
     }
     std::free(p);
+    return hipSuccess;
+}
+
+// The arena grows with VSOM_BUF_SYNC.  The program's own definition takes the place of the runtime's, so that no device is
+// needed, and counts the calls: a synchronise comes before every drop of an allocated arena.
+static long g_syncs = 0;
+extern "C" hipError_t hipStreamSynchronize(hipStream_t)
+{
+    ++g_syncs;
     return hipSuccess;
 }
 
@@ -128,6 +141,73 @@ int main()
         EXPECT(!y.p && z.p && g_live.size() == 1);
     }
     EXPECT(g_live.empty());
+
+    // the scratch arena: a layout of mixed types and counts carves at multiples of 256 bytes, in request order, without
+    // overlap; a zero count takes no bytes; no pointer before the arena is there
+    g_calls = 0, g_fail_at = -1;
+    {
+        DevBuf<unsigned char> arena;
+        vsom_layout lay;
+        const auto a = lay.add<unsigned long long>(3);
+        const auto b = lay.add<unsigned char>(5);
+        const auto z = lay.add<double>(0);
+        const auto f = lay.add<float>(7);
+        EXPECT(a.off == 0 && b.off == 256 && z.off == 512 && f.off == 512 && lay.bytes == 768);
+        EXPECT(a.off + 3 * 8 <= b.off && b.off + 5 <= z.off && f.off + 7 * 4 <= lay.bytes);
+        EXPECT(!lay.at(a) && !lay.at(f));
+        EXPECT(vsom_arena_ensure(arena, lay, nullptr) == hipSuccess && arena.p && arena.cap == 4096 && g_calls == 1);
+        EXPECT((unsigned char *)lay.at(a) == arena.p && lay.at(b) == arena.p + 256 && (unsigned char *)lay.at(f) == arena.p + 512);
+        EXPECT((unsigned char *)lay.at(z) == arena.p + 512);
+        for (int i = 0; i < 3; ++i)        // (every carved element is writable: the sanitizer build checks the bounds)
+            lay.at(a)[i] = 1;
+        for (int i = 0; i < 7; ++i)
+            lay.at(f)[i] = 1.f;
+        std::memset(lay.at(b), 1, 5);
+
+        // grow-only: a smaller layout after a larger one allocates nothing and is bound to the same arena
+        vsom_layout big;
+        (void)big.add<float>(5000);
+        const auto tail = big.add<unsigned char>(1);
+        EXPECT(tail.off == 20224 && big.bytes == 20480);
+        g_releases = 0;
+        EXPECT(vsom_arena_ensure(arena, big, nullptr) == hipSuccess && arena.cap == 20480);
+        EXPECT(g_calls == 2 && g_releases == 1 && g_live.size() == 1);   // exactly one buffer released, one allocated
+        EXPECT(g_syncs == 1);                                            // (behind a synchronise; none on first use)
+        unsigned char *held = arena.p;
+        vsom_layout small;
+        const auto s0 = small.add<unsigned>(9);
+        EXPECT(vsom_arena_ensure(arena, small, nullptr) == hipSuccess && g_calls == 2 && g_releases == 1);
+        EXPECT(arena.p == held && arena.cap == 20480 && (unsigned char *)small.at(s0) == held);
+        vsom_layout none;                   // an empty layout asks for nothing
+        EXPECT(vsom_arena_ensure(arena, none, nullptr) == hipSuccess && g_calls == 2 && arena.p == held);
+
+        // a failing allocator: the error, the arena absent, no pointer; the next, smaller request succeeds
+        vsom_layout huge;
+        const auto h = huge.add<double>(1 << 20);
+        g_fail_at = g_calls;
+        EXPECT(vsom_arena_ensure(arena, huge, nullptr) == hipErrorOutOfMemory);
+        EXPECT(!arena.p && arena.cap == 0 && !huge.at(h) && g_live.empty());
+        g_fail_at = -1;
+        EXPECT(vsom_arena_ensure(arena, lay, nullptr) == hipSuccess && arena.p && arena.cap == 4096);
+        EXPECT((unsigned char *)lay.at(f) == arena.p + 512 && g_live.size() == 1);
+    }
+    EXPECT(g_live.empty());
+
+    // the pinned arena passes pinned = true to both allocator functions, the device arena to neither
+    {
+        g_pinned_allocs = g_pinned_releases = g_releases = 0;
+        g_calls = 0;
+        PinnedBuf<unsigned char> pinned;
+        DevBuf<unsigned char> dev;
+        vsom_layout one, two;
+        (void)one.add<unsigned>(10);
+        (void)two.add<unsigned>(2000);
+        EXPECT(vsom_arena_ensure(dev, one, nullptr) == hipSuccess && vsom_arena_ensure(dev, two, nullptr) == hipSuccess);
+        EXPECT(g_calls == 2 && g_releases == 1 && g_pinned_allocs == 0 && g_pinned_releases == 0);
+        EXPECT(vsom_arena_ensure(pinned, one, nullptr) == hipSuccess && vsom_arena_ensure(pinned, two, nullptr) == hipSuccess);
+        EXPECT(g_calls == 4 && g_releases == 2 && g_pinned_allocs == 2 && g_pinned_releases == 1);
+    }
+    EXPECT(g_live.empty() && g_pinned_releases == 2);
 
     if (g_errors) {
         std::printf("%ld failure(s)\n", g_errors);

@@ -1,6 +1,8 @@
 """The all-or-nothing buffer sets of csrc/vsom_buf.hpp, on the host: a C++ driver replaces the allocate / free seam with
 host memory that fails on the k-th call and checks, for every k, that the set call reports out of memory, that every
-member is left null with capacity 0, and that every allocation that succeeded is freed exactly once.  No device is
+member is left null with capacity 0, and that every allocation that succeeded is freed exactly once.  The same driver
+checks the scratch arena (vsom_layout / vsom_arena_ensure): carves at multiples of 256 bytes in request order, grow-only
+capacity, absence after a failed growth, and the pinned flag on both allocator functions.  No device is
 needed (the HIP headers only; the runtime library is linked but never called)."""
 import os
 import shutil

@@ -186,12 +186,14 @@ int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_
     const size_t ppitch = (slice + BMD_R - 1) / BMD_R * BMD_R;
     const size_t nch = (N + BMD_NC - 1) / BMD_NC;
     const size_t prow = std::min(slice, std::max<size_t>(1, ((size_t)32 << 20) / (8 * N)));   // rows per prob copy-out
-    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_SYNC,
-                                   {vsom_member(c->bmd_p, ppitch * N), vsom_member(c->bmd_cum, nch * ppitch),
-                                    vsom_member(c->bmd_vec, 2 * ppitch), vsom_member(c->bmd_draw, ppitch),
-                                    vsom_member(c->bmd_prob, prob_out ? prow * N : 0)}));
-    double *P = c->bmd_p.p, *u_dev = c->bmd_vec.p, *norm_dev = c->bmd_vec.p + ppitch;
-    u64 *draw_dev = draw_out ? c->bmd_draw.p : nullptr;
+    // the slice's p (node-major), running sums at chunk boundaries, uniforms | norms and draws; one copy-out piece of prob
+    vsom_layout lay;
+    const auto p = lay.add<double>(ppitch * N), cum = lay.add<double>(nch * ppitch), vec = lay.add<double>(2 * ppitch),
+               prob = lay.add<double>(prob_out ? prow * N : 0);
+    const auto draw = lay.add<u64>(ppitch);
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+    double *P = lay.at(p), *u_dev = lay.at(vec), *norm_dev = lay.at(vec) + ppitch;
+    u64 *draw_dev = draw_out ? lay.at(draw) : nullptr;
     const DistArgs a = vsom_dist_args(c);
     const int TS = c->transform == VSOM_CLR ? 32 : TILE;
     for (size_t s0 = r0; s0 < r1; s0 += slice) {
@@ -206,7 +208,7 @@ int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_
             hipLaunchKernelGGL((bmd_tile_kernel<false, 4>), grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)N, P,
                                (int)ppitch, c->hits.p, min_hits);
         hipLaunchKernelGGL(bmd_sum_kernel, dim3((unsigned)((n + BMD_R - 1) / BMD_R)), dim3(256), 0, c->stream, P, (int)ppitch,
-                           (int)n, (int)N, c->bmd_cum.p, u_dev, norm_dev, draw_dev);
+                           (int)n, (int)N, lay.at(cum), u_dev, norm_dev, draw_dev);
         VSOM_HIP_CHECK(hipGetLastError());
         if (norm_out)
             VSOM_HIP_CHECK(hipMemcpyAsync(norm_out + off, norm_dev, n * 8, hipMemcpyDeviceToHost, c->stream));
@@ -215,9 +217,9 @@ int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_
         for (size_t q0 = 0; prob_out && q0 < n; q0 += prow) {
             const size_t m = std::min(prow, n - q0);
             hipLaunchKernelGGL(bmd_prob_kernel, dim3((unsigned)((N + 31) / 32), (unsigned)((m + 31) / 32)), dim3(256), 0,
-                               c->stream, P, (int)ppitch, (int)q0, (int)m, (int)N, norm_dev, c->bmd_prob.p);
+                               c->stream, P, (int)ppitch, (int)q0, (int)m, (int)N, norm_dev, lay.at(prob));
             VSOM_HIP_CHECK(hipGetLastError());
-            VSOM_HIP_CHECK(hipMemcpyAsync(prob_out + (off + q0) * N, c->bmd_prob.p, m * N * 8, hipMemcpyDeviceToHost,
+            VSOM_HIP_CHECK(hipMemcpyAsync(prob_out + (off + q0) * N, lay.at(prob), m * N * 8, hipMemcpyDeviceToHost,
                                           c->stream));
         }
     }

@@ -12,6 +12,12 @@
 // of 0 leaves that member null.  The result is a hipError_t for VSOM_HIP_CHECK (out of memory -> VSOM_ERR_NOMEM).
 // vsom_grow(buf, count, stream, flags) is the set of one.
 //
+// vsom_layout / vsom_arena_ensure: the scratch of one call, carved out of one grow-only byte arena (device or pinned).
+// The call collects its pieces first, h = lay.add<T>(count), each at a multiple of 256 bytes as hipMalloc would place it
+// (a count of 0 takes no bytes); vsom_arena_ensure(arena, lay, stream) then grows the arena to the layout's total rounded
+// up to 4 KiB (VSOM_BUF_SYNC; on failure the arena is absent) and binds the layout to it.  lay.at(h), the piece's typed
+// pointer, is null until that has succeeded.  An arena's contents belong to the running call.
+//
 // The allocate / free functions are reached through `vsom_mem`, so a host-only test can substitute failing ones.
 #pragma once
 
@@ -145,4 +151,25 @@ template <typename T, bool Pinned>
 hipError_t vsom_grow(vsom_buf<T, Pinned> &b, size_t count, hipStream_t stream, unsigned flags = 0)
 {
     return vsom_grow_set(stream, flags & ~VSOM_BUF_ZERO, {vsom_member(b, count, flags)});
+}
+
+struct vsom_layout {
+    template <typename T> struct piece { size_t off; };
+    size_t bytes = 0;
+    unsigned char *base = nullptr;      // the arena this layout is bound to (vsom_arena_ensure)
+    template <typename T> piece<T> add(size_t count)
+    {
+        const piece<T> h{bytes};
+        bytes += (count * sizeof(T) + 255) / 256 * 256;
+        return h;
+    }
+    template <typename T> T *at(piece<T> h) const { return base ? reinterpret_cast<T *>(base + h.off) : nullptr; }
+};
+
+template <bool Pinned>
+hipError_t vsom_arena_ensure(vsom_buf<unsigned char, Pinned> &arena, vsom_layout &lay, hipStream_t stream)
+{
+    const hipError_t e = vsom_grow(arena, (lay.bytes + 4095) / 4096 * 4096, stream, VSOM_BUF_SYNC);
+    lay.base = arena.p;     // (null after a failure)
+    return e;
 }

@@ -754,11 +754,23 @@ int vsom_bmu_local_batch(vsom_ctx *c, uint64_t *idx_out_host, float *dist_out_ho
     return copy_search_results(c, idx_out_host, dist_out_host);
 }
 
-// device scratch of the distance queries (pair lists in, distances out): grow-only, kept with the context -- a
-// device allocation and free per call cost more than the queries' kernels (tests/perf/ref_harness.py)
-static int ensure_query_scratch(vsom_ctx *c, size_t bytes)
+// The checked pair lists of vsom_distances (from_map < 0) / vsom_distances_raw in, their distances out.  The scratch is the
+// context's arena: a device allocation and free per call cost more than the queries' kernels (tests/perf/ref_harness.py).
+static int pair_query(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *rows_host, size_t count, int from_map,
+                      float *dist_out_host)
 {
-    VSOM_ALLOC_CHECK(vsom_grow(c->q_scratch, (bytes + 4095) / 4096 * 4096, c->stream, VSOM_BUF_SYNC));
+    vsom_layout lay;
+    const auto hn = lay.add<u64>(count), hr = lay.add<u64>(count);
+    const auto hd = lay.add<float>(count);
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+    u64 *dn = lay.at(hn), *dr = lay.at(hr);
+    float *dd = lay.at(hd);
+    VSOM_HIP_CHECK(hipMemcpyAsync(dn, nodes_host, count * 8, hipMemcpyHostToDevice, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(dr, rows_host, count * 8, hipMemcpyHostToDevice, c->stream));
+    if (int rc = from_map < 0 ? launch_pair_dist(c, dn, dr, count, dd) : launch_raw_dist(c, dn, dr, count, from_map, dd))
+        return rc;
+    VSOM_HIP_CHECK(hipMemcpyAsync(dist_out_host, dd, count * 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
 }
 
@@ -778,19 +790,7 @@ int vsom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *rows
     for (size_t i = 0; i < count; ++i)
         if (nodes_host[i] >= c->N || rows_host[i] >= c->B)
             return vsom_fail(VSOM_ERR_INVALID, "pair index out of range");
-    const size_t c8 = (count * 8 + 255) / 256 * 256;
-    int rc = ensure_query_scratch(c, 2 * c8 + count * 4);
-    if (rc)
-        return rc;
-    u64 *dn = reinterpret_cast<u64 *>(c->q_scratch.p), *dr = reinterpret_cast<u64 *>((char *)c->q_scratch.p + c8);
-    float *dd = reinterpret_cast<float *>((char *)c->q_scratch.p + 2 * c8);
-    VSOM_HIP_CHECK(hipMemcpyAsync(dn, nodes_host, count * 8, hipMemcpyHostToDevice, c->stream));
-    VSOM_HIP_CHECK(hipMemcpyAsync(dr, rows_host, count * 8, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_pair_dist(c, dn, dr, count, dd)))
-        return rc;
-    VSOM_HIP_CHECK(hipMemcpyAsync(dist_out_host, dd, count * 4, hipMemcpyDeviceToHost, c->stream));
-    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return VSOM_OK;
+    return pair_query(c, nodes_host, rows_host, count, -1, dist_out_host);
 }
 
 int vsom_bmu_restricted_batch(vsom_ctx *c, uint64_t min_hits, uint64_t *idx_out_host, float *dist_out_host)
@@ -900,11 +900,11 @@ int vsom_distances_row(vsom_ctx *c, size_t row, float *dist_out_host)
     CHECK_ROWS(c);
     if (row >= c->B || !dist_out_host)
         return vsom_fail(VSOM_ERR_INVALID, "row out of range or null output");
-    int rc = ensure_query_scratch(c, (size_t)c->N * 4);
-    if (rc)
-        return rc;
-    float *dd = reinterpret_cast<float *>(c->q_scratch.p);
-    if ((rc = launch_row_dist(c, row, dd)))
+    vsom_layout lay;
+    const auto hd = lay.add<float>(c->N);
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+    float *dd = lay.at(hd);
+    if (int rc = launch_row_dist(c, row, dd))
         return rc;
     VSOM_HIP_CHECK(hipMemcpyAsync(dist_out_host, dd, (size_t)c->N * 4, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -925,19 +925,7 @@ int vsom_distances_raw(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *
     for (size_t i = 0; i < count; ++i)
         if (nodes_host[i] >= c->N || vrows_host[i] >= (from_map ? (uint64_t)c->N : (uint64_t)c->B))
             return vsom_fail(VSOM_ERR_INVALID, "pair index out of range");
-    const size_t c8 = (count * 8 + 255) / 256 * 256;
-    int rc = ensure_query_scratch(c, 2 * c8 + count * 4);
-    if (rc)
-        return rc;
-    u64 *dn = reinterpret_cast<u64 *>(c->q_scratch.p), *dr = reinterpret_cast<u64 *>((char *)c->q_scratch.p + c8);
-    float *dd = reinterpret_cast<float *>((char *)c->q_scratch.p + 2 * c8);
-    VSOM_HIP_CHECK(hipMemcpyAsync(dn, nodes_host, count * 8, hipMemcpyHostToDevice, c->stream));
-    VSOM_HIP_CHECK(hipMemcpyAsync(dr, vrows_host, count * 8, hipMemcpyHostToDevice, c->stream));
-    if ((rc = launch_raw_dist(c, dn, dr, count, from_map, dd)))
-        return rc;
-    VSOM_HIP_CHECK(hipMemcpyAsync(dist_out_host, dd, count * 4, hipMemcpyDeviceToHost, c->stream));
-    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    return VSOM_OK;
+    return pair_query(c, nodes_host, vrows_host, count, from_map != 0, dist_out_host);
 }
 
 // Som::updateUMatrix (vsom_umatrix.hip).  No reader of the staged rows is enqueued, so rows_free_valid stays as it is and

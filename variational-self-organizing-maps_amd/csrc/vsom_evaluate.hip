@@ -171,34 +171,35 @@ int launch_evaluate(vsom_ctx *c, size_t r0, size_t r1, const float *binary_host,
         return VSOM_OK;
     }
     const size_t J = c->J, C = std::min<size_t>(c->J, c->D);
-    // grow-only: a member keeps what it has when this call needs less.  The pinned image holds the two column arrays on
-    // their way in (behind the rows' words) and the rows' words on their way out.
+    // the per-row results of the call, the validity bytes when given, the column arrays.  The pinned image holds the two
+    // column arrays on their way in (behind the rows' words) and the rows' words on their way out.
     const size_t words = rows * EV_ROW_WORDS;
-    VSOM_ALLOC_CHECK(vsom_grow_set(
-        c->stream, VSOM_BUF_SYNC,
-        {vsom_member(c->ev_rows, std::max(c->ev_rows.cap, words)), vsom_member(c->ev_pinned, std::max(c->ev_pinned.cap, words + 2 * J)),
-         vsom_member(c->ev_valid, std::max(c->ev_valid.cap, valid_host ? rows * J : 0)),
-         vsom_member(c->ev_cols, std::max(c->ev_cols.cap, 2 * J))}));
+    vsom_layout lay, pin;
+    const auto erows = lay.add<unsigned>(words), pinned = pin.add<unsigned>(words + 2 * J);
+    const auto valid = lay.add<unsigned char>(valid_host ? rows * J : 0);
+    const auto ecols = lay.add<float>(2 * J);
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_pinned, pin, c->stream));
 
     int rc = launch_bmu_full(c, 0, c->B);           // findBmu of the whole chunk, as vsom_bmu_batch
     if (rc)
         return rc;
-    float *cols = reinterpret_cast<float *>(c->ev_pinned.p + words);
+    float *cols = reinterpret_cast<float *>(pin.at(pinned) + words);
     std::memcpy(cols, binary_host, J * 4);
     std::memcpy(cols + J, continuous_host, J * 4);
-    VSOM_HIP_CHECK(hipMemcpyAsync(c->ev_cols.p, cols, 2 * J * 4, hipMemcpyHostToDevice, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(ecols), cols, 2 * J * 4, hipMemcpyHostToDevice, c->stream));
     if (valid_host)
-        VSOM_HIP_CHECK(hipMemcpyAsync(c->ev_valid.p, valid_host, rows * J, hipMemcpyHostToDevice, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(valid), valid_host, rows * J, hipMemcpyHostToDevice, c->stream));
 
     EvArgs a;
     a.x = c->Xs.p;
     a.map = c->map.p;
     a.lastbmu = c->lastbmu.p;
     a.sqres = c->sqres.p;
-    a.valid = valid_host ? c->ev_valid.p : nullptr;
-    a.binary = c->ev_cols.p;
-    a.continuous = c->ev_cols.p + J;
-    a.rows = c->ev_rows.p;
+    a.valid = valid_host ? lay.at(valid) : nullptr;
+    a.binary = lay.at(ecols);
+    a.continuous = lay.at(ecols) + J;
+    a.rows = lay.at(erows);
     a.ldx = (int)c->xpitch;
     a.ldm = (int)c->pitch;
     a.part_len = (int)c->part_len;
@@ -216,10 +217,10 @@ int launch_evaluate(vsom_ctx *c, size_t r0, size_t r1, const float *binary_host,
             hipLaunchKernelGGL(evaluate_kernel<true>, grid, block, 0, c->stream, a, (int)r0, (int)r1);
         VSOM_HIP_CHECK(hipGetLastError());
     }
-    VSOM_HIP_CHECK(hipMemcpyAsync(c->ev_pinned.p, c->ev_rows.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(pin.at(pinned), lay.at(erows), words * 4, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
 
-    const unsigned *p = c->ev_pinned.p;
+    const unsigned *p = pin.at(pinned);
     if (out->bmu)
         std::memcpy(out->bmu, p, rows * 8);
     void *dst[3] = {out->dist, out->bsum, out->nrepl};

@@ -183,35 +183,11 @@ struct vsom_ctx {
     // pinned staging of vsom_set_state's host arrays
     PinnedBuf<float> st_pinned;
     PinnedBuf<u64> out_pinned;      // [8192]: vsom_get_last_bmu of short chunks
-    // device scratch of the distance queries (vsom_distances / _row / _raw): grow-only, bytes
+    // scratch arenas of the chunk and distance queries (vsom_layout, vsom_buf.hpp): every call lays out what it needs and
+    // the arena grows to the largest layout asked for.  The contents belong to the running call: nothing in them may be
+    // expected to survive into the next entry point.
     DevBuf<unsigned char> q_scratch;
-    // vsom_bmd_batch (vsom_bmd.hip): p of a row slice (node-major), the running sums at chunk boundaries, the slice's
-    // uniforms and norms, its draws, and one copy-out piece of the row-major probabilities; one set, grow-only
-    DevBuf<double> bmd_p, bmd_cum, bmd_vec, bmd_prob;
-    DevBuf<u64> bmd_draw;
-    // vsom_bmu_topk_batch (vsom_topk.hip): every node group's k keys per row of a slice, the slice's idx / dist and its
-    // node-0 NaN flags; one set, grow-only
-    DevBuf<u64> topk_part, topk_idx;
-    DevBuf<float> topk_dist;
-    DevBuf<unsigned char> topk_nan0;
-    // vsom_similarity_batch (vsom_similarity.hip): the per-row results of a call and their pinned host image, the validity
-    // bytes when given, the dense report of a row slice; one set, grow-only
-    DevBuf<unsigned> sim_rows;
-    PinnedBuf<unsigned> sim_pinned;
-    DevBuf<unsigned char> sim_valid;
-    DevBuf<float> sim_delta;
-    // vsom_evaluate_batch (vsom_evaluate.hip): the per-row results of a call and their pinned host image (which also stages
-    // the two column arrays on their way in), the validity bytes when given, the column arrays; one set, grow-only
-    DevBuf<unsigned> ev_rows;
-    PinnedBuf<unsigned> ev_pinned;
-    DevBuf<unsigned char> ev_valid;
-    DevBuf<float> ev_cols;
-    // vsom_bmu_masked_batch (vsom_masked.hip): a row slice's validity bytes as given and packed (0xFF / 0x00, xpitch per row),
-    // its node groups' keys, its results and node-0 NaN flags, its imputed rows; one set, grow-only
-    DevBuf<unsigned char> msk_raw, msk_valid, msk_nan0;
-    DevBuf<u64> msk_part, msk_bmu;
-    DevBuf<float> msk_dist, msk_fill;
-    DevBuf<unsigned> msk_nvalid;
+    PinnedBuf<unsigned char> q_pinned;
     // vsom_umatrix (vsom_umatrix.hip): U[N] of the last call, allocated on first use
     DevBuf<double> umatrix;
     bool um_valid = false;          // a vsom_umatrix has been enqueued on this context

@@ -195,48 +195,48 @@ int launch_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const uint8_t
     const VsomNodeGroups grp = vsom_node_groups((N + TILE - 1) / TILE, (slice + TILE - 1) / TILE, MSK_MAXG);
     const size_t G = grp.G, ng = grp.ng;
     const size_t vrows = one ? 1 : slice;
-    // grow-only: a member keeps what it has when this call needs less
-    VSOM_ALLOC_CHECK(vsom_grow_set(
-        c->stream, VSOM_BUF_SYNC,
-        {vsom_member(c->msk_raw, std::max(c->msk_raw.cap, vrows * J)), vsom_member(c->msk_valid, std::max(c->msk_valid.cap, vrows * vld)),
-         vsom_member(c->msk_part, std::max(c->msk_part.cap, slice * ng)), vsom_member(c->msk_bmu, std::max(c->msk_bmu.cap, slice)),
-         vsom_member(c->msk_dist, std::max(c->msk_dist.cap, slice)), vsom_member(c->msk_nvalid, std::max(c->msk_nvalid.cap, slice)),
-         vsom_member(c->msk_nan0, std::max(c->msk_nan0.cap, slice)),
-         vsom_member(c->msk_fill, std::max(c->msk_fill.cap, out->fill ? slice * J : 0))}));
+    // a slice's validity bytes as given and packed (0xFF / 0x00, xpitch per row), node-group keys, results and imputed rows
+    vsom_layout lay;
+    const auto raw = lay.add<unsigned char>(vrows * J), valid = lay.add<unsigned char>(vrows * vld),
+               nan0 = lay.add<unsigned char>(slice);
+    const auto part = lay.add<u64>(slice * ng), bmu = lay.add<u64>(slice);
+    const auto dist = lay.add<float>(slice), fill = lay.add<float>(out->fill ? slice * J : 0);
+    const auto nvalid = lay.add<unsigned>(slice);
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
 
     const DistArgs a = vsom_dist_args(c);     // (Standard / Median: the rows themselves)
-    unsigned *packed = reinterpret_cast<unsigned *>(c->msk_valid.p);
+    unsigned *packed = reinterpret_cast<unsigned *>(lay.at(valid));
     for (size_t s0 = r0; s0 < r1; s0 += slice) {
         const size_t s1 = std::min(r1, s0 + slice), n = s1 - s0, off = s0 - r0;
         if (!one || s0 == r0) {     // (a column mask is packed once)
             const size_t vr = one ? 1 : n;
-            VSOM_HIP_CHECK(hipMemcpyAsync(c->msk_raw.p, valid_host + (one ? 0 : off * J), vr * J, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(masked_pack_kernel, dim3((unsigned)vr), dim3(256), 0, c->stream, c->msk_raw.p, (int)J, (int)vld,
+            VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(raw), valid_host + (one ? 0 : off * J), vr * J, hipMemcpyHostToDevice, c->stream));
+            hipLaunchKernelGGL(masked_pack_kernel, dim3((unsigned)vr), dim3(256), 0, c->stream, lay.at(raw), (int)J, (int)vld,
                                packed);
         }
         dim3 grid((unsigned)ng, (unsigned)((n + TILE - 1) / TILE));
         if (one)
-            hipLaunchKernelGGL(masked_tile_kernel<true>, grid, dim3(256), 0, c->stream, a, c->msk_valid.p, (int)vld, (int)s0,
-                               (int)s1, (int)N, (int)G, c->hits.p, min_hits, c->msk_part.p, c->msk_nan0.p);
+            hipLaunchKernelGGL(masked_tile_kernel<true>, grid, dim3(256), 0, c->stream, a, lay.at(valid), (int)vld, (int)s0,
+                               (int)s1, (int)N, (int)G, c->hits.p, min_hits, lay.at(part), lay.at(nan0));
         else
-            hipLaunchKernelGGL(masked_tile_kernel<false>, grid, dim3(256), 0, c->stream, a, c->msk_valid.p, (int)vld, (int)s0,
-                               (int)s1, (int)N, (int)G, c->hits.p, min_hits, c->msk_part.p, c->msk_nan0.p);
-        hipLaunchKernelGGL(masked_reduce_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, c->msk_part.p, (int)ng,
-                           c->msk_nan0.p, packed, (int)vld, (int)one, (int)n, c->msk_bmu.p, c->msk_dist.p, c->msk_nvalid.p);
+            hipLaunchKernelGGL(masked_tile_kernel<false>, grid, dim3(256), 0, c->stream, a, lay.at(valid), (int)vld, (int)s0,
+                               (int)s1, (int)N, (int)G, c->hits.p, min_hits, lay.at(part), lay.at(nan0));
+        hipLaunchKernelGGL(masked_reduce_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, lay.at(part), (int)ng,
+                           lay.at(nan0), packed, (int)vld, (int)one, (int)n, lay.at(bmu), lay.at(dist), lay.at(nvalid));
         if (out->fill)
             hipLaunchKernelGGL(masked_fill_kernel, dim3((unsigned)n, (unsigned)((J + 255) / 256)), dim3(256), 0, c->stream,
                                reinterpret_cast<const unsigned *>(c->Xs.p), (int)c->xpitch,
-                               reinterpret_cast<const unsigned *>(c->map.p), (int)c->pitch, c->msk_bmu.p, c->msk_valid.p, (int)vld,
-                               (int)one, (int)s0, (int)J, reinterpret_cast<unsigned *>(c->msk_fill.p));
+                               reinterpret_cast<const unsigned *>(c->map.p), (int)c->pitch, lay.at(bmu), lay.at(valid), (int)vld,
+                               (int)one, (int)s0, (int)J, reinterpret_cast<unsigned *>(lay.at(fill)));
         VSOM_HIP_CHECK(hipGetLastError());
         if (out->bmu)
-            VSOM_HIP_CHECK(hipMemcpyAsync(out->bmu + off, c->msk_bmu.p, n * 8, hipMemcpyDeviceToHost, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(out->bmu + off, lay.at(bmu), n * 8, hipMemcpyDeviceToHost, c->stream));
         if (out->dist)
-            VSOM_HIP_CHECK(hipMemcpyAsync(out->dist + off, c->msk_dist.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(out->dist + off, lay.at(dist), n * 4, hipMemcpyDeviceToHost, c->stream));
         if (out->nvalid)
-            VSOM_HIP_CHECK(hipMemcpyAsync(out->nvalid + off, c->msk_nvalid.p, n * 4, hipMemcpyDeviceToHost, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(out->nvalid + off, lay.at(nvalid), n * 4, hipMemcpyDeviceToHost, c->stream));
         if (out->fill)
-            VSOM_HIP_CHECK(hipMemcpyAsync(out->fill + off * J, c->msk_fill.p, n * J * 4, hipMemcpyDeviceToHost, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(out->fill + off * J, lay.at(fill), n * J * 4, hipMemcpyDeviceToHost, c->stream));
     }
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;

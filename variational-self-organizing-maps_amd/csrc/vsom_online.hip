@@ -2075,8 +2075,10 @@ static int single_scan(vsom_ctx *c, const float *v_host, int use_hits, uint64_t 
         return rc;
     float *all_dev = nullptr;
     if (all_out_host) {
-        VSOM_ALLOC_CHECK(vsom_grow(c->q_scratch, ((size_t)c->N * 4 + 4095) / 4096 * 4096, c->stream, VSOM_BUF_SYNC));
-        all_dev = reinterpret_cast<float *>(c->q_scratch.p);
+        vsom_layout lay;
+        const auto hall = lay.add<float>(c->N);
+        VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+        all_dev = lay.at(hall);
     }
     const bool clr = c->transform == VSOM_CLR;
     const size_t xs_n = c->xpitch, pp = c->part_pitch;

@@ -212,20 +212,21 @@ int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule,
         return VSOM_OK;
     const size_t C = std::min<size_t>(c->J, c->D);
     const size_t slice = out->delta ? std::min(vsom_similarity_slice_rows(C), rows) : rows;
-    // grow-only: a member keeps what it has when this call needs less
+    // the per-row results of the call and their pinned host image, the validity bytes when given, a slice's dense report
     const size_t words = rows * SIM_ROW_WORDS;
-    VSOM_ALLOC_CHECK(vsom_grow_set(
-        c->stream, VSOM_BUF_SYNC,
-        {vsom_member(c->sim_rows, std::max(c->sim_rows.cap, words)), vsom_member(c->sim_pinned, std::max(c->sim_pinned.cap, words)),
-         vsom_member(c->sim_valid, std::max(c->sim_valid.cap, valid_host ? rows * c->J : 0)),
-         vsom_member(c->sim_delta, std::max(c->sim_delta.cap, out->delta ? slice * C : 0))}));
+    vsom_layout lay, pin;
+    const auto srows = lay.add<unsigned>(words), pinned = pin.add<unsigned>(words);
+    const auto valid = lay.add<unsigned char>(valid_host ? rows * c->J : 0);
+    const auto delta = lay.add<float>(out->delta ? slice * C : 0);
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_pinned, pin, c->stream));
 
     // findRestrictedBmu of the whole chunk; with min_hits = 0 every node qualifies and the search is findBmu's
     int rc = min_hits == 0 ? launch_bmu_full(c, 0, c->B) : launch_bmu_restricted(c, min_hits);
     if (rc)
         return rc;
     if (valid_host)
-        VSOM_HIP_CHECK(hipMemcpyAsync(c->sim_valid.p, valid_host, rows * c->J, hipMemcpyHostToDevice, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(valid), valid_host, rows * c->J, hipMemcpyHostToDevice, c->stream));
 
     SimArgs a;
     a.x = c->Xs.p;
@@ -233,9 +234,9 @@ int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule,
     a.sigma = c->sigma.p;
     a.lastbmu = c->lastbmu.p;
     a.sqres = c->sqres.p;
-    a.valid = valid_host ? c->sim_valid.p : nullptr;
-    a.delta = out->delta ? c->sim_delta.p : nullptr;
-    a.rows = c->sim_rows.p;
+    a.valid = valid_host ? lay.at(valid) : nullptr;
+    a.delta = out->delta ? lay.at(delta) : nullptr;
+    a.rows = lay.at(srows);
     a.ldx = (int)c->xpitch;
     a.ldm = (int)c->pitch;
     a.part_len = (int)c->part_len;
@@ -258,12 +259,12 @@ int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule,
             VSOM_HIP_CHECK(hipGetLastError());
         }
         if (out->delta)
-            VSOM_HIP_CHECK(hipMemcpyAsync(out->delta + (s0 - r0) * C, c->sim_delta.p, n * C * 4, hipMemcpyDeviceToHost, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(out->delta + (s0 - r0) * C, lay.at(delta), n * C * 4, hipMemcpyDeviceToHost, c->stream));
     }
-    VSOM_HIP_CHECK(hipMemcpyAsync(c->sim_pinned.p, c->sim_rows.p, words * 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipMemcpyAsync(pin.at(pinned), lay.at(srows), words * 4, hipMemcpyDeviceToHost, c->stream));
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
 
-    const unsigned *p = c->sim_pinned.p;
+    const unsigned *p = pin.at(pinned);
     void *dst[SIM_ROW_WORDS - 1] = {out->bmu, out->dist, out->dmax, out->dmax_col, out->first, out->amax, out->amax_col, out->outside};
     for (int i = 0; i < SIM_ROW_WORDS - 1; ++i) {
         const size_t at = i == 0 ? 0 : (size_t)(i + 1) * rows, len = i == 0 ? 2 * rows : rows;

@@ -210,26 +210,28 @@ int launch_topk(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out
     // node groups: at most TOPK_MAXG lists per row to merge
     const VsomNodeGroups grp = vsom_node_groups((N + TILE - 1) / TILE, (slice + TS - 1) / TS, TOPK_MAXG);
     const size_t G = grp.G, ng = grp.ng;
-    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_SYNC,
-                                   {vsom_member(c->topk_part, slice * ng * k), vsom_member(c->topk_idx, slice * k),
-                                    vsom_member(c->topk_dist, dist_out ? slice * k : 0),
-                                    vsom_member(c->topk_nan0, slice)}));
+    // every node group's k keys per row of a slice, the slice's idx / dist and its node-0 NaN flags
+    vsom_layout lay;
+    const auto part = lay.add<u64>(slice * ng * k), idx = lay.add<u64>(slice * k);
+    const auto dist = lay.add<float>(dist_out ? slice * k : 0);
+    const auto nan0 = lay.add<unsigned char>(slice);
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
     const DistArgs a = vsom_dist_args(c);
     for (size_t s0 = r0; s0 < r1; s0 += slice) {
         const size_t s1 = std::min(r1, s0 + slice), n = s1 - s0, off = s0 - r0;
         dim3 grid((unsigned)ng, (unsigned)((n + TS - 1) / TS));
         if (c->transform == VSOM_CLR)
             hipLaunchKernelGGL((topk_tile_kernel<true, 2>), grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)N,
-                               (int)k, (int)G, c->topk_part.p, c->topk_nan0.p);
+                               (int)k, (int)G, lay.at(part), lay.at(nan0));
         else
             hipLaunchKernelGGL((topk_tile_kernel<false, 4>), grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)N,
-                               (int)k, (int)G, c->topk_part.p, c->topk_nan0.p);
-        hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)n), dim3(64), ng * k * 8, c->stream, c->topk_part.p,
-                           c->topk_nan0.p, (int)ng, (int)k, c->topk_idx.p, dist_out ? c->topk_dist.p : nullptr);
+                               (int)k, (int)G, lay.at(part), lay.at(nan0));
+        hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)n), dim3(64), ng * k * 8, c->stream, lay.at(part),
+                           lay.at(nan0), (int)ng, (int)k, lay.at(idx), dist_out ? lay.at(dist) : nullptr);
         VSOM_HIP_CHECK(hipGetLastError());
-        VSOM_HIP_CHECK(hipMemcpyAsync(idx_out + off * k, c->topk_idx.p, n * k * 8, hipMemcpyDeviceToHost, c->stream));
+        VSOM_HIP_CHECK(hipMemcpyAsync(idx_out + off * k, lay.at(idx), n * k * 8, hipMemcpyDeviceToHost, c->stream));
         if (dist_out)
-            VSOM_HIP_CHECK(hipMemcpyAsync(dist_out + off * k, c->topk_dist.p, n * k * 4, hipMemcpyDeviceToHost, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(dist_out + off * k, lay.at(dist), n * k * 4, hipMemcpyDeviceToHost, c->stream));
     }
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
