@@ -109,7 +109,7 @@ typedef enum vsom_buffer {
 typedef enum vsom_timer {
     VSOM_T_STAGE = 0,      /* chunk re-layout kernels                           */
     VSOM_T_BMU = 1,        /* full / local BMU search kernels                   */
-    VSOM_T_FINISH = 2,     /* bmuHits + MSE; vsom_similarity_batch's / vsom_evaluate_batch's scoring kernel */
+    VSOM_T_FINISH = 2,     /* bmuHits + MSE; the scoring kernels of vsom_similarity_batch / vsom_evaluate_batch, vsom_generate_batch's decode */
     VSOM_T_CW = 3,         /* neighbourhood weight chain (w, w/W) kernel        */
     VSOM_T_UPDATE = 4,     /* mean / sigma^2 chain kernel                       */
     VSOM_T_ONLINE = 5,     /* online (trainSingle) kernels                      */
@@ -413,6 +413,53 @@ typedef struct vsom_evaluate_out {
 } vsom_evaluate_out;
 int vsom_evaluate_batch(vsom_ctx *ctx, size_t r0, size_t r1, const float *binary_host, const float *continuous_host,
                         const uint8_t *valid_host, vsom_evaluate_out *out);
+/* Som::autoEncoder's records (Som.cpp:568-623) for chunk rows [r0, r1): a model vector per row drawn from a restricted best
+ * matching distribution (Som::findRestrictedBmd, vsom_bmd_batch), and every column of the record sampled from a
+ * logit-approximated normal around that unit's map / sigmaMap values -- one call, one stream wait, nothing of size N x D moves.
+ * rule (vsom_generate_rule):
+ *   VSOM_GENERATE_AS_WRITTEN  the reference calls variationalAutoEncoder(data) afresh for every row, and that walks the whole
+ *                             data set and returns the draw of its LAST row (:532-565): every row's unit is an independent
+ *                             draw, with the row's own uniform, from the distribution of chunk row B - 1 (whatever r0, r1)
+ *   VSOM_GENERATE_PER_ROW     row r's unit is drawn from row r's own distribution, the evident intent (:584-589)
+ * The draw is vsom_bmd_batch's, word for word: p_i = bmuHits[i] >= min_hits ? exp(-(double)d_i * d_i / 2) : 0,
+ * C = ((0 + p_0) + p_1) + ... in node order in double, the unit is the smallest i whose running sum exceeds u * C, the
+ * largest i with p_i > 0 when rounding leaves none, UINT64_MAX when C is 0 or not finite.  PER_ROW returns the bits
+ * vsom_bmd_batch returns for the same rows and uniforms; AS_WRITTEN those of vsom_bmd_batch on [B - 1, B) with each uniform.
+ *   u_host[r1-r0]        one uniform in [0,1) per row, required
+ *   l_host[(r1-r0)*C]    row-major, C = min(J, D): the reference's L of :608, one per value.  Not validated; the arithmetic
+ *                        is IEEE: L = 0 gives -inf, L = 1 gives +inf, L outside [0,1] gives NaN
+ * Decode, per row with unit b and logical column d < C (the column vsom_get_state returns), m = map[b][d], s = sigmaMap[b][d],
+ * in double with one rounding per operation, nothing contracted, in the order of :609:
+ *   q = L / (1 - L);  g = log(q);  z = g / 1.6;  t = z * (double)s;  rec = t + (double)m
+ * A row without mass has unit = UINT64_MAX and the quiet NaN 0x7FF8000000000000 in every column of its record.
+ * Outputs (host pointers, each may be NULL; entry r - r0 belongs to row r): unit[r1-r0], record[(r1-r0)*C] row-major.
+ * Accuracy: only log can differ from a CPU restatement (q is one IEEE division on both sides).  With Ld, Lh the error
+ * bounds in ulps of the device's and of the host's double log, and ulp(x) <= 2^-52 |x|: the two g differ by at most
+ * (Ld + Lh) 2^-52 |g|; the division by 1.6 rounds once on each side (2 * 2^-53), the product with s likewise, so the two t
+ * differ by at most (Ld + Lh + 2) 2^-52 |z s|; the final sum rounds once on each side, 2^-53 (|rec_dev| + |rec_ref|).  To
+ * first order in 2^-52:
+ *   |rec_dev - rec_ref| <= (Ld + Lh + 2) * 2^-52 * |z * s| + 2^-52 * |rec_ref|
+ * Ld = Lh = 1 are taken AS ASSUMPTIONS (csrc/vsom_generate.hip names the sources).  No tolerance: unit; L = 0.5 (q = 1,
+ * g = +0, rec = m); s = 0 with a finite g (rec = m); NaN and inf propagation; the row without mass.
+ * Read-only: map, sigmaMap, S, weightMap, bmuHits, lastBMU, sqres and the chunk are untouched.  Refuses (VSOM_ERR_INVALID,
+ * nothing enqueued, the context stays usable): a null context, out, u_host or l_host, custom contexts, C = 0, an unknown
+ * rule, no chunk, a chunk staged ahead, r0 > r1 or r1 > B, a uniform that is NaN or outside [0,1).  An empty range returns
+ * VSOM_OK and enqueues nothing.  Device scratch, in the query arena: the distribution of a slice (PER_ROW: at most 256 MiB
+ * of p) or of row B - 1 (AS_WRITTEN: 8 N doubles), and a slice's L and record, at most 64 MiB each; VSOM_GENERATE_SLICE_ROWS
+ * (read at every call) caps the rows of a slice.  l_host and record travel straight from and to the caller's memory, u_host
+ * and unit as vsom_bmd_batch moves them.  The draw launches are timed under VSOM_T_BMU, the decode under VSOM_T_FINISH. */
+typedef enum vsom_generate_rule {
+    VSOM_GENERATE_AS_WRITTEN = 0, /* every row's unit is drawn from the BMD of the chunk's LAST row (row B-1) */
+    VSOM_GENERATE_PER_ROW = 1     /* row r's unit is drawn from row r's own BMD: the evident intent (Som.cpp:584-589) */
+} vsom_generate_rule;
+typedef struct vsom_generate_out { uint64_t *unit; double *record; } vsom_generate_out;
+int vsom_generate_batch(vsom_ctx *ctx, uint64_t min_hits, int rule, size_t r0, size_t r1,
+                        const double *u_host, const double *l_host, vsom_generate_out *out);
+/* The decode of vsom_generate_batch for `count` units the caller names: record_out[i*C + d] from nodes_host[i] and
+ * l_host[i*C + d], the same kernel, the same arithmetic and accuracy.  Needs no chunk and makes no search; read-only.
+ * Refuses (VSOM_ERR_INVALID, nothing enqueued): a null context, l_host or record_out, a null nodes_host with count > 0,
+ * custom contexts, C = 0, a node >= N.  count = 0 returns VSOM_OK and enqueues nothing. */
+int vsom_decode_nodes(vsom_ctx *ctx, const uint64_t *nodes_host, size_t count, const double *l_host, double *record_out);
 /* Som::euclidianWeightedDistRaw(pos, v, ones, ones) (Som.cpp:143-157) for `count` pairs; v is
  * chunk row vrows[i] (from_map = 0) or model vector vrows[i] (from_map = 1, the U-matrix case). */
 int vsom_distances_raw(vsom_ctx *ctx, const uint64_t *nodes_host, const uint64_t *vrows_host,

@@ -26,6 +26,8 @@ BUF_MAP, BUF_SIGMA, BUF_S, BUF_WEIGHT, BUF_HITS, BUF_LASTBMU, BUF_SQRES, BUF_CHU
 T_STAGE, T_BMU, T_FINISH, T_CW, T_UPDATE, T_ONLINE, T_SIGMA, T_COUNT = range(8)
 TIMER_NAMES = ["stage", "bmu", "finish", "cw", "update", "online", "sigma"]
 SIGMA_AS_WRITTEN, SIGMA_FLOOR = 0, 1       # vsom_sigma_rule
+GENERATE_AS_WRITTEN, GENERATE_PER_ROW = 0, 1   # vsom_generate_rule
+NO_UNIT = 2 ** 64 - 1      # the unit of a row without mass (UINT64_MAX)
 
 # every symbol include/vsom_hip.h declares (tests/test_capi_symbols.py checks the header too)
 SYMBOLS = [
@@ -48,7 +50,7 @@ SYMBOLS = [
     "vsom_ensemble_create", "vsom_ensemble_destroy", "vsom_ensemble_size", "vsom_ensemble_train_online_chunk_fetch",
     "vsom_ensemble_batch_epoch", "vsom_ensemble_upload_chunks", "vsom_ensemble_bmu_batch",
     "vsom_umatrix", "vsom_get_umatrix", "vsom_ensemble_umatrix", "vsom_similarity_batch",
-    "vsom_bmu_masked_batch", "vsom_evaluate_batch",
+    "vsom_bmu_masked_batch", "vsom_evaluate_batch", "vsom_generate_batch", "vsom_decode_nodes",
 ]
 
 
@@ -69,6 +71,11 @@ class EvaluateOut(C.Structure):
     """vsom_evaluate_out: host pointers, each may be NULL"""
     _fields_ = [("bmu", C.POINTER(C.c_uint64)), ("dist", C.POINTER(C.c_float)), ("bsum", C.POINTER(C.c_float)),
                 ("nrepl", C.POINTER(C.c_uint32)), ("error", C.POINTER(C.c_double))]
+
+
+class GenerateOut(C.Structure):
+    """vsom_generate_out: host pointers, each may be NULL"""
+    _fields_ = [("unit", C.POINTER(C.c_uint64)), ("record", C.POINTER(C.c_double))]
 
 
 class VsomError(RuntimeError):
@@ -242,6 +249,9 @@ def lib():
     L.vsom_bmu_masked_batch.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8), C.c_int,
                                         C.POINTER(MaskedOut)]
     L.vsom_evaluate_batch.argtypes = [vp, C.c_size_t, C.c_size_t, fp, fp, C.POINTER(C.c_uint8), C.POINTER(EvaluateOut)]
+    if hasattr(L, "vsom_generate_batch"):       # (VSOM_LIB may name an older build: tools/generate_bench.py --route parent)
+        L.vsom_generate_batch.argtypes = [vp, C.c_uint64, C.c_int, C.c_size_t, C.c_size_t, dp, dp, C.POINTER(GenerateOut)]
+        L.vsom_decode_nodes.argtypes = [vp, u64p, C.c_size_t, dp, dp]
     _lib = L
     return L
 
@@ -618,6 +628,61 @@ class Context:
                                         None if vb is None else vb.ctypes.data_as(C.POINTER(C.c_uint8)), C.byref(out)))
         res["error"] = float(res["error"][0])
         return res
+
+    def _logits(self, l, n):
+        cols = min(self.in_len, self.depth)
+        if cols == 0:
+            raise ValueError("the records have no columns")
+        l = np.ascontiguousarray(l, dtype=np.float64)
+        if l.shape != (n, cols):
+            raise ValueError(f"l has shape {l.shape}, not ({n}, {cols})")
+        return l, cols
+
+    def generate(self, min_hits, u, l, rule=GENERATE_PER_ROW, r0=0, r1=None):
+        """Som::autoEncoder's records of chunk rows [r0, r1) in one call (vsom_generate_batch): a unit per row drawn from a
+        restricted best matching distribution with the uniform u[r] in [0, 1) -- the row's own (GENERATE_PER_ROW:
+        restricted_bmd's draw) or that of the chunk's last row (GENERATE_AS_WRITTEN, what the reference does) -- and every
+        column sampled as log(l / (1 - l)) / 1.6 * sigma + mean around that unit, l: float64[rows, min(J, D)].  A dict:
+        unit (uint64, NO_UNIT = no mass) and record (float64[rows, min(J, D)], NaN in a row without mass).  Read-only."""
+        B = self.chunk_size
+        r0 = int(r0)
+        r1 = B if r1 is None else int(r1)
+        if int(rule) not in (GENERATE_AS_WRITTEN, GENERATE_PER_ROW):
+            raise ValueError(f"rule = {rule} is neither GENERATE_AS_WRITTEN nor GENERATE_PER_ROW")
+        if int(min_hits) < 0:
+            raise ValueError("min_hits must be >= 0")
+        if r0 < 0 or r0 > r1 or r1 > B:
+            raise ValueError(f"row range [{r0}, {r1}) is not within the chunk's {B} rows")
+        n = r1 - r0
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.shape != (n,):
+            raise ValueError(f"u has shape {u.shape}, not ({n},)")
+        if not ((u >= 0.0) & (u < 1.0)).all():
+            raise ValueError("every uniform must lie in [0, 1)")
+        l, cols = self._logits(l, n)
+        res = {"unit": np.empty(n, np.uint64), "record": np.empty((n, cols), np.float64)}
+        out = GenerateOut()
+        for name, ctype in GenerateOut._fields_:
+            setattr(out, name, res[name].ctypes.data_as(ctype))
+        dp = C.POINTER(C.c_double)
+        check(lib().vsom_generate_batch(self._h, int(min_hits), int(rule), r0, r1, u.ctypes.data_as(dp), l.ctypes.data_as(dp),
+                                        C.byref(out)))
+        return res
+
+    def decode_nodes(self, nodes, l):
+        """generate's decode for given units (vsom_decode_nodes): float64[len(nodes), min(J, D)], row i sampled around unit
+        nodes[i] with l[i].  Needs no chunk.  Read-only."""
+        a = np.asarray(nodes)
+        if a.ndim != 1:
+            raise ValueError(f"nodes has shape {a.shape}, not one dimension")
+        if a.size and (a.dtype.kind not in "iu" or int(a.min()) < 0 or int(a.max()) >= self.n_nodes):
+            raise ValueError(f"every node must be an integer in [0, {self.n_nodes})")
+        a = np.ascontiguousarray(a, dtype=np.uint64)
+        l, cols = self._logits(l, a.size)
+        rec = np.empty((a.size, cols), np.float64)
+        dp = C.POINTER(C.c_double)
+        check(lib().vsom_decode_nodes(self._h, _u(a), a.size, l.ctypes.data_as(dp), rec.ctypes.data_as(dp)))
+        return rec
 
     def bmu_masked(self, valid, r0=0, r1=None, min_hits=0, fill=False):
         """The best matching unit of chunk rows [r0, r1) over their valid columns only (vsom_bmu_masked_batch; Standard /

@@ -8,6 +8,8 @@
 //                    keeping the running sum at every BMD_NC-node boundary; the draw re-walks the one BMD_NC-node chunk
 //                    that holds the first running sum above t = u * C with the same adds
 //  bmd_prob_kernel : p_i / C (Som.cpp:483-484), transposed to row-major for the copy-out
+//  bmd_draws_kernel: many draws from ONE row's distribution (vsom_generate_batch, VSOM_GENERATE_AS_WRITTEN): one thread per
+//                    uniform, the chunk search and the re-walk of bmd_sum_kernel's draw (bmd_find_chunk / bmd_walk_chunk)
 #include "vsom_dist_tile.hpp"
 #include <algorithm>
 
@@ -41,6 +43,27 @@ __global__ __launch_bounds__(256, 2) void bmd_tile_kernel(DistArgs a, int s0, in
         if (n < N && s < s1)
             P[(size_t)n * ppitch + (s - s0)] = sp[nl][rl];
     }
+}
+
+// The two steps of a draw, shared by bmd_sum_kernel and bmd_draws_kernel.
+// The first chunk whose closing running sum exceeds t, or -1; cum(k) = the running sum after chunk k.
+template <class F> __device__ __forceinline__ int bmd_find_chunk(F cum, int nch, double t)
+{
+    for (int k = 0; k < nch; ++k)
+        if (cum(k) > t)
+            return k;
+    return -1;
+}
+// The walk of that chunk from the running sum s in front of it, with the adds of the row pass: the first node whose running
+// sum exceeds t, or `none`; p(j) = the chunk's j-th value.
+template <class F> __device__ __forceinline__ u64 bmd_walk_chunk(F p, double s, int n0, int cnt, double t, u64 none)
+{
+    for (int j = 0; j < cnt; ++j) {
+        s = s + p(j);                           // the same adds as the row pass
+        if (s > t)
+            return (u64)(n0 + j);
+    }
+    return none;
 }
 
 // BMD_R rows per workgroup: the 256 threads stage BMD_NC nodes x BMD_R rows of P per step (the next step's loads in
@@ -109,11 +132,7 @@ __global__ __launch_bounds__(256) void bmd_sum_kernel(const double *__restrict__
     u64 result = ~0ull;
     if (mine && C > 0.0 && __builtin_isfinite(C)) {
         t = u[row] * C;
-        for (int k = 0; k < nch; ++k)
-            if (cum[(size_t)k * ppitch + row] > t) {
-                kc = k;
-                break;
-            }
+        kc = bmd_find_chunk([&](int k) { return cum[(size_t)k * ppitch + row]; }, nch, t);
         if (kc < 0)
             result = (u64)lastpos;
     }
@@ -134,18 +153,44 @@ __global__ __launch_bounds__(256) void bmd_sum_kernel(const double *__restrict__
     }
     __syncthreads();
     if (mine && kc >= 0) {
-        double s = kc > 0 ? cum[(size_t)(kc - 1) * ppitch + row] : 0.0;
+        const double s = kc > 0 ? cum[(size_t)(kc - 1) * ppitch + row] : 0.0;
         const int n0 = kc * BMD_NC, cnt = N - n0 < BMD_NC ? N - n0 : BMD_NC;
-        for (int j = 0; j < cnt; ++j) {
-            s = s + sp[tid][j];                 // the same adds as the walk above
-            if (s > t) {
-                result = (u64)(n0 + j);
-                break;
-            }
-        }
+        result = bmd_walk_chunk([&](int j) { return sp[tid][j]; }, s, n0, cnt, t, result);
     }
     if (mine)
         draw[row] = result;
+}
+
+// ndraws draws from the distribution of slice row `row`, whose P column, running sums (cum) and mass (norm) a
+// bmd_sum_kernel launch with draws has left: draw[i] is what that launch would have drawn for the row with uniform u[i].
+// One thread per draw; the BMD_NC values of a chunk are read straight from P (every thread reads the same few lines).
+__global__ __launch_bounds__(256) void bmd_draws_kernel(const double *__restrict__ P, int ppitch, int row, int N,
+                                                        const double *__restrict__ cum, const double *__restrict__ norm,
+                                                        const double *__restrict__ u, int ndraws, u64 *__restrict__ draw)
+{
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= ndraws)
+        return;
+    const int nch = (N + BMD_NC - 1) / BMD_NC;
+    const double C = norm[row];
+    u64 result = ~0ull;
+    if (C > 0.0 && __builtin_isfinite(C)) {
+        const double t = u[i] * C;
+        const int kc = bmd_find_chunk([&](int k) { return cum[(size_t)k * ppitch + row]; }, nch, t);
+        if (kc < 0) {
+            // no running sum above t (u close to 1): the last node with mass (C > 0: there is one)
+            for (int n = N - 1; n >= 0; --n)
+                if (P[(size_t)n * ppitch + row] > 0.0) {
+                    result = (u64)n;
+                    break;
+                }
+        } else {
+            const double s = kc > 0 ? cum[(size_t)(kc - 1) * ppitch + row] : 0.0;
+            const int n0 = kc * BMD_NC, cnt = N - n0 < BMD_NC ? N - n0 : BMD_NC;
+            result = bmd_walk_chunk([&](int j) { return P[(size_t)(n0 + j) * ppitch + row]; }, s, n0, cnt, t, result);
+        }
+    }
+    draw[i] = result;
 }
 
 // rows [q0, q0 + nrows) of the slice: out[r * N + n] = P[n * ppitch + q0 + r] / C (Som.cpp:483-484), 32 x 32 per workgroup
@@ -175,6 +220,38 @@ static size_t vsom_bmd_slice_rows(size_t N)
     return s > 0 ? s : 1;
 }
 
+size_t vsom_bmd_pitch(size_t rows) { return (rows + BMD_R - 1) / BMD_R * BMD_R; }
+size_t vsom_bmd_chunks(size_t N) { return (N + BMD_NC - 1) / BMD_NC; }
+
+// the tile and the row pass of slice rows [s0, s1) on the context's stream (vsom_internal.hpp)
+int vsom_bmd_enqueue(vsom_ctx *c, u64 min_hits, size_t s0, size_t s1, double *P, size_t ppitch, double *cum,
+                     const double *u_dev, double *norm_dev, u64 *draw_dev)
+{
+    const size_t N = c->N, n = s1 - s0;
+    const DistArgs a = vsom_dist_args(c);
+    const int TS = c->transform == VSOM_CLR ? 32 : TILE;
+    dim3 grid((unsigned)((N + TILE - 1) / TILE), (unsigned)((n + TS - 1) / TS));
+    if (c->transform == VSOM_CLR)
+        hipLaunchKernelGGL((bmd_tile_kernel<true, 2>), grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)N, P,
+                           (int)ppitch, c->hits.p, min_hits);
+    else
+        hipLaunchKernelGGL((bmd_tile_kernel<false, 4>), grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)N, P,
+                           (int)ppitch, c->hits.p, min_hits);
+    hipLaunchKernelGGL(bmd_sum_kernel, dim3((unsigned)((n + BMD_R - 1) / BMD_R)), dim3(256), 0, c->stream, P, (int)ppitch,
+                       (int)n, (int)N, cum, u_dev, norm_dev, draw_dev);
+    VSOM_HIP_CHECK(hipGetLastError());
+    return VSOM_OK;
+}
+
+int vsom_bmd_enqueue_draws(vsom_ctx *c, const double *P, size_t ppitch, size_t row, const double *cum, const double *norm_dev,
+                           const double *u_dev, size_t ndraws, u64 *draw_dev)
+{
+    hipLaunchKernelGGL(bmd_draws_kernel, dim3((unsigned)((ndraws + 255) / 256)), dim3(256), 0, c->stream, P, (int)ppitch,
+                       (int)row, (int)c->N, cum, norm_dev, u_dev, (int)ndraws, draw_dev);
+    VSOM_HIP_CHECK(hipGetLastError());
+    return VSOM_OK;
+}
+
 int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_host, uint64_t *draw_out, double *norm_out,
                double *prob_out)
 {
@@ -194,22 +271,12 @@ int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_
     VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
     double *P = lay.at(p), *u_dev = lay.at(vec), *norm_dev = lay.at(vec) + ppitch;
     u64 *draw_dev = draw_out ? lay.at(draw) : nullptr;
-    const DistArgs a = vsom_dist_args(c);
-    const int TS = c->transform == VSOM_CLR ? 32 : TILE;
     for (size_t s0 = r0; s0 < r1; s0 += slice) {
         const size_t s1 = std::min(r1, s0 + slice), n = s1 - s0, off = s0 - r0;
         if (draw_out)
             VSOM_HIP_CHECK(hipMemcpyAsync(u_dev, u_host + off, n * 8, hipMemcpyHostToDevice, c->stream));
-        dim3 grid((unsigned)((N + TILE - 1) / TILE), (unsigned)((n + TS - 1) / TS));
-        if (c->transform == VSOM_CLR)
-            hipLaunchKernelGGL((bmd_tile_kernel<true, 2>), grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)N, P,
-                               (int)ppitch, c->hits.p, min_hits);
-        else
-            hipLaunchKernelGGL((bmd_tile_kernel<false, 4>), grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)N, P,
-                               (int)ppitch, c->hits.p, min_hits);
-        hipLaunchKernelGGL(bmd_sum_kernel, dim3((unsigned)((n + BMD_R - 1) / BMD_R)), dim3(256), 0, c->stream, P, (int)ppitch,
-                           (int)n, (int)N, lay.at(cum), u_dev, norm_dev, draw_dev);
-        VSOM_HIP_CHECK(hipGetLastError());
+        if (int rc = vsom_bmd_enqueue(c, min_hits, s0, s1, P, ppitch, lay.at(cum), u_dev, norm_dev, draw_dev))
+            return rc;
         if (norm_out)
             VSOM_HIP_CHECK(hipMemcpyAsync(norm_out + off, norm_dev, n * 8, hipMemcpyDeviceToHost, c->stream));
         if (draw_out)

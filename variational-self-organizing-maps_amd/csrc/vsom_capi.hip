@@ -874,6 +874,47 @@ int vsom_evaluate_batch(vsom_ctx *c, size_t r0, size_t r1, const float *binary_h
     return launch_evaluate(c, r0, r1, binary_host, continuous_host, valid_host, out);
 }
 
+int vsom_generate_batch(vsom_ctx *c, uint64_t min_hits, int rule, size_t r0, size_t r1, const double *u_host,
+                        const double *l_host, vsom_generate_out *out)
+{
+    CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_generate_batch");
+    CHECK_ROWS(c);
+    if (!out)
+        return vsom_fail(VSOM_ERR_INVALID, "out is null");
+    if (!u_host || !l_host)
+        return vsom_fail(VSOM_ERR_INVALID, "u_host or l_host is null");
+    if (rule != VSOM_GENERATE_AS_WRITTEN && rule != VSOM_GENERATE_PER_ROW)
+        return vsom_fail(VSOM_ERR_INVALID, "unknown rule");
+    if (c->J == 0 || c->D == 0)
+        return vsom_fail(VSOM_ERR_INVALID, "the records have no columns");
+    if (c->B == 0)
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    if (r0 > r1 || r1 > c->B)
+        return vsom_fail(VSOM_ERR_INVALID, "row range out of bounds");
+    for (size_t i = 0; i < r1 - r0; ++i)
+        if (!(u_host[i] >= 0.0 && u_host[i] < 1.0))
+            return vsom_fail(VSOM_ERR_INVALID, "uniform " + std::to_string(i) + " is not in [0,1)");
+    return launch_generate(c, min_hits, rule, r0, r1, u_host, l_host, out);
+}
+
+// Reads the model state only: a chunk staged ahead does not matter.
+int vsom_decode_nodes(vsom_ctx *c, const uint64_t *nodes_host, size_t count, const double *l_host, double *record_out)
+{
+    CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_decode_nodes");
+    if (!l_host || !record_out)
+        return vsom_fail(VSOM_ERR_INVALID, "l_host or record_out is null");
+    if (count > 0 && !nodes_host)
+        return vsom_fail(VSOM_ERR_INVALID, "nodes_host is null");
+    if (c->J == 0 || c->D == 0)
+        return vsom_fail(VSOM_ERR_INVALID, "the records have no columns");
+    for (size_t i = 0; i < count; ++i)
+        if (nodes_host[i] >= c->N)
+            return vsom_fail(VSOM_ERR_INVALID, "node " + std::to_string(i) + " is out of range");
+    return launch_decode_nodes(c, nodes_host, count, l_host, record_out);
+}
+
 int vsom_bmu_masked_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
                           vsom_masked_out *out)
 {

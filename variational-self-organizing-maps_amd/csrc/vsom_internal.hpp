@@ -270,6 +270,21 @@ int launch_row_dist(vsom_ctx *c, size_t row, float *out_dev);
 // vsom_bmd.hip: findRestrictedBmd + draws for chunk rows [r0,r1) (arguments checked by vsom_bmd_batch); synchronises
 int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_host, uint64_t *draw_out, double *norm_out,
                double *prob_out);
+// pieces of launch_bmd for callers that lay the scratch out themselves (vsom_generate.hip); they enqueue only.
+// P: ppitch x N doubles, node-major, ppitch = vsom_bmd_pitch(rows of the slice); cum: vsom_bmd_chunks(N) x ppitch (written
+// only with draws); u_dev, norm_dev, draw_dev: one entry per slice row, draw_dev null = no draws.
+size_t vsom_bmd_pitch(size_t rows);
+size_t vsom_bmd_chunks(size_t N);
+int vsom_bmd_enqueue(vsom_ctx *c, u64 min_hits, size_t s0, size_t s1, double *P, size_t ppitch, double *cum,
+                     const double *u_dev, double *norm_dev, u64 *draw_dev);
+// ndraws draws from the distribution of slice row `row` after a vsom_bmd_enqueue WITH draws: draw_dev[i] from u_dev[i]
+int vsom_bmd_enqueue_draws(vsom_ctx *c, const double *P, size_t ppitch, size_t row, const double *cum, const double *norm_dev,
+                           const double *u_dev, size_t ndraws, u64 *draw_dev);
+// vsom_generate.hip: draws + decode of chunk rows [r0,r1) (arguments checked by vsom_generate_batch), the decode alone for
+// given units (arguments checked by vsom_decode_nodes); both synchronise
+int launch_generate(vsom_ctx *c, u64 min_hits, int rule, size_t r0, size_t r1, const double *u_host, const double *l_host,
+                    const vsom_generate_out *out);
+int launch_decode_nodes(vsom_ctx *c, const uint64_t *nodes_host, size_t count, const double *l_host, double *record_out);
 // vsom_topk.hip: the k best matching units of chunk rows [r0,r1) (arguments checked by vsom_bmu_topk_batch); synchronises
 int launch_topk(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out, float *dist_out);
 // vsom_similarity.hip: search + scoring of chunk rows [r0,r1) (arguments checked by vsom_similarity_batch); synchronises

@@ -515,6 +515,20 @@ public:
         double error = 0;
     };
     EvaluateRows evaluateRows(const DataSet &data) const;
+    // [MI355X build] extension: autoEncoder's records with the caller's random numbers, for every row of `data` (one
+    // vsom_generate_batch call, include/vsom_hip.h): a unit per row drawn with the uniform u[r] in [0,1) from the row's own
+    // restricted distribution (perRow) or from that of the LAST row (the reference as written), and every column sampled as
+    // log(l / (1 - l)) / 1.6 * sigma + mean around that unit; l is rows x columns, row-major, columns = min(sample length,
+    // depth).  A row without mass has unit UINT64_MAX and a record of NaN.  Built-in transformations on the device only.
+    struct GeneratedRows {
+        std::vector<uint64_t> unit;
+        std::vector<double> record;               // rows x columns
+        size_t columns = 0;
+    };
+    GeneratedRows generateRows(const DataSet &data, size_t minBmuHits, const std::vector<double> &u,
+                               const std::vector<double> &l, bool perRow = true) const;
+    // [MI355X build] extension: the same sampling around given units (one vsom_decode_nodes call): units.size() x columns
+    std::vector<double> decodeUnits(const std::vector<uint64_t> &units, const std::vector<double> &l) const;
     // the finish of measureSimilarity from such a report: the row the reference reports (Som.cpp:684-690: one running
     // maximum over every delta of every row, compared signed, stored as fabs); 0 when no delta exceeds the start value
     static size_t measureSimilarityRow(const std::vector<float> &first, const std::vector<float> &dmax);

@@ -1745,10 +1745,91 @@ double Som::topographicError(const DataSet *data) const
     return count / (double)n;
 }
 
-// Som.cpp:568-623: prints a logit-approximated normal sample per feature around a drawn model vector
+Som::GeneratedRows Som::generateRows(const DataSet &data, size_t minBmuHits, const std::vector<double> &u,
+                                     const std::vector<double> &l, bool perRow) const
+{
+    requireDevicePath("generateRows");
+    if (transform.kind() == vsom::Custom)
+        throw std::runtime_error("generateRows: vsom_generate_batch serves the built-in transformations only");
+    GeneratedRows r;
+    r.columns = std::min(inLen, depth);
+    const size_t n = data.size();
+    if (u.size() != n)
+        throw std::invalid_argument("generateRows: one uniform per row");
+    if (l.size() != n * r.columns)
+        throw std::invalid_argument("generateRows: l must hold rows x min(sample length, depth) values");
+    r.unit.assign(n, 0);
+    r.record.assign(n * r.columns, 0.0);
+    if (n == 0)
+        return r;
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data.contiguous(), n), "vsom_upload_chunk");
+    vsom_generate_out out = {r.unit.data(), r.record.data()};
+    check(vsom_generate_batch(ctx, minBmuHits, perRow ? VSOM_GENERATE_PER_ROW : VSOM_GENERATE_AS_WRITTEN, 0, n, u.data(),
+                              l.data(), &out),
+          "vsom_generate_batch");
+    return r;
+}
+
+std::vector<double> Som::decodeUnits(const std::vector<uint64_t> &units, const std::vector<double> &l) const
+{
+    requireDevicePath("decodeUnits");
+    if (transform.kind() == vsom::Custom)
+        throw std::runtime_error("decodeUnits: vsom_decode_nodes serves the built-in transformations only");
+    const size_t columns = std::min(inLen, depth);
+    if (l.size() != units.size() * columns)
+        throw std::invalid_argument("decodeUnits: l must hold units x min(sample length, depth) values");
+    std::vector<double> record(units.size() * columns, 0.0);
+    if (units.empty())
+        return record;
+    joinGroup();
+    check(vsom_decode_nodes(ctx, units.data(), units.size(), l.data(), record.data()), "vsom_decode_nodes");
+    return record;
+}
+
+// Som.cpp:568-623: prints a logit-approximated normal sample per feature around a drawn model vector.
+// Built-in transformations: the random numbers are drawn first, from the generators the reference uses and in its order --
+// L = (rand() % 1000) / 1000 per value after srand(time + clock), and per row one uniform from a fresh random_device-seeded
+// mt19937, as each variationalAutoEncoder call builds one --, then one upload, one vsom_generate_batch call
+// (VSOM_GENERATE_AS_WRITTEN: every row's unit comes from the LAST row's distribution, as the reference's does) and, for the
+// rows without mass, one vsom_decode_nodes call with node 0, what libstdc++'s discrete_distribution returns for its all-NaN
+// weights.  No refreshHost().  The printed values come from the device's double log, not libm's: they lie within the
+// tolerance of include/vsom_hip.h of what the host loop below prints for the same random numbers.  The loop stays for the
+// caller's hooks.
 int Som::autoEncoder(const DataSet *data, size_t minBmuHits) const
 {
     std::srand((unsigned)(time(NULL) + clock()));
+    const size_t n = data->size(), columns = std::min(inLen, depth);
+    if (ctx && transform.kind() != vsom::Custom && n > 0 && columns > 0 && columns == inLen) {
+        std::vector<double> l(n * columns), u(n);
+        for (size_t i = 0; i < n; ++i) {
+            std::random_device rd;
+            std::mt19937 gen(rd());
+            u[i] = std::generate_canonical<double, 53>(gen);
+            for (size_t k = 0; k < columns; ++k)
+                l[i * columns + k] = (double)(std::rand() % (int)(1000)) / 1000;
+        }
+        GeneratedRows r = generateRows(*data, minBmuHits, u, l, false);
+        std::vector<uint64_t> zeros;
+        std::vector<double> lz;
+        for (size_t i = 0; i < n; ++i)
+            if (r.unit[i] == UINT64_MAX) {
+                zeros.push_back(0);
+                lz.insert(lz.end(), l.begin() + (std::ptrdiff_t)(i * columns), l.begin() + (std::ptrdiff_t)((i + 1) * columns));
+            }
+        const std::vector<double> rz = decodeUnits(zeros, lz);
+        size_t z = 0;
+        for (size_t i = 0; i < n; i++) {
+            const double *rec = r.unit[i] == UINT64_MAX ? rz.data() + (z++) * columns : r.record.data() + i * columns;
+            Eigen::VectorXf v = data->getData(i);
+            for (Eigen::Index k = 0; k < v.size(); k++) {
+                std::cout << v(k) << "\n";
+                std::cout << data->getName((size_t)k) << "\t" << rec[k] << "\t\n";
+            }
+            std::cout << "\n";
+        }
+        return true;
+    }
     for (size_t i = 0; i < data->size(); i++) {
         Eigen::VectorXf v = data->getData(i);
         auto bmuInt = variationalAutoEncoder(data, minBmuHits);

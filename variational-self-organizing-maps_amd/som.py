@@ -349,6 +349,43 @@ class Som:
         d = int(self.drawModelVectors(X[-1:], minBmuHits, u)[0])
         return 0 if d == 0xFFFFFFFFFFFFFFFF else d
 
+    # ---- generated records (Som.cpp:568-623) ----------------------------------------------------
+    def generateRows(self, data, minBmuHits, u, l, perRow=True):
+        """extension: Som::autoEncoder's records for every loaded row of `data` with the caller's random numbers
+        (capi.Context.generate): a unit per row drawn with the uniform u[r] in [0, 1) from the row's own restricted
+        distribution (perRow=True) or from that of the last row (perRow=False, the reference as written), and every column
+        sampled as log(l / (1 - l)) / 1.6 * sigma + mean around it, l: float64[rows, min(J, D)].  {"unit", "record"};
+        a row without mass has the unit capi.NO_UNIT and a record of NaN."""
+        X = self._rows(data)
+        self.ctx.upload_chunk(X)
+        if X.shape[0] == 0:
+            return {"unit": np.zeros(0, np.uint64), "record": np.zeros((0, min(self.ctx.in_len, self.ctx.depth)), np.float64)}
+        return self.ctx.generate(minBmuHits, u, l, capi.GENERATE_PER_ROW if perRow else capi.GENERATE_AS_WRITTEN)
+
+    def decodeUnits(self, units, l):
+        """extension: the records of given units (capi.Context.decode_nodes): float64[len(units), min(J, D)], row i sampled
+        around unit units[i] with l[i]"""
+        return self.ctx.decode_nodes(units, l)
+
+    def autoEncoder(self, data, minBmuHits, seed=None):
+        """Som::autoEncoder as written: every loaded row gets a unit drawn from the LAST row's restricted distribution and a
+        record sampled around it; the uniforms and the reference's L = (rand() % 1000) / 1000 come from
+        numpy.random.default_rng(seed).  Returns (unit uint64[rows], record float64[rows, min(J, D)]); a row without mass
+        takes node 0, what the reference's discrete_distribution returns then.  (The reference prints; the text output is
+        the C++ mirror's.)"""
+        X = self._rows(data)
+        n, cols = X.shape[0], min(self.ctx.in_len, self.ctx.depth)
+        rng = np.random.default_rng(seed)
+        u = rng.random(n)
+        l = rng.integers(0, 1000, (n, cols)).astype(np.float64) / 1000.0
+        rep = self.generateRows(X, minBmuHits, u, l, perRow=False)
+        unit, record = rep["unit"], rep["record"]
+        none = unit == np.uint64(capi.NO_UNIT)
+        if none.any():
+            unit[none] = 0
+            record[none] = self.ctx.decode_nodes(np.zeros(int(none.sum()), np.uint64), l[none])
+        return unit, record
+
     # ---- similarity of records to their best matching units (Som.cpp:631-714) -----------------
     def similarityRows(self, data, numOfSigmas, minBmuHits, floor=True, valid=None, delta=False):
         """extension: the per-row report measureSimilarity computes and throws away, for every loaded row of `data`
