@@ -489,6 +489,32 @@ int vsom_batch_finish_async(vsom_ctx *ctx);
 int vsom_batch_phase2_async(vsom_ctx *ctx, double sigma, size_t n0, size_t n1);
 int vsom_batch_epoch_async(vsom_ctx *ctx, double sigma, int is_first);
 int vsom_batch_epoch(vsom_ctx *ctx, double sigma, int is_first, float *mse_out);
+/* Som::trainBatchSomEpoch over the VALID entries of the chunk only: the loaders store a missing field as 0.0f with
+ * valid = 0 and the built-in Steppers drop valueWeight (Transformation.cpp:11-12,49-50), so vsom_batch_epoch takes every
+ * missing field as a measured zero.  This call is the evident intent beside "as written", as vsom_bmu_masked_batch is for
+ * the search.  Blocking, on the context's stream; Standard and Median (D = J), strict update mode only.
+ * valid_host: B x J bytes row-major, or J bytes applied to every row when one_mask != 0; a non-zero byte means valid.  The
+ * bytes travel with the call, nothing is kept between calls.  For the chunk's rows x_0 .. x_{B-1} in load order:
+ *   phase 1 (:762-806) on the distance of vsom_bmu_masked_batch (r_d = valid[d] ? m_d - x_d : +0.0f, r.dot(r) over all J
+ *     positions in the exact search's order): is_first != 0 the argmin of findBmu over all nodes (vsom_bmu_masked_batch
+ *     with min_hits = 0), else findLocalBmu's walk (Som.cpp:335-454) from lastBMU[r], every distance the masked one.
+ *     lastBMU[r] = the unit, sqres[r] = its masked distance; bmuHits and the MSE come from the unchanged finish step.
+ *   phase 2 (:809-876) column by column: for node i and column d the rows are walked in load order and every row that
+ *     is invalid at d is skipped; for a valid row w = (float)h(i, lastBMU[j], sigma), W_d += w, delta = Stepper(x_jd, M_d),
+ *     M_d = M_d + (w / W_d) * delta, S_d = S_d + (w * delta) * delta -- the float operations of the unmasked chain, unfused,
+ *     the division correctly rounded; map[i][d] = M_d, sigmaMap[i][d] = sqrt(S_d / W_d).  Column d of the result is column
+ *     d of the unmasked phase 2 run over the rows valid at d with those rows' units.  What x holds at an invalid position
+ *     (NaN, inf, anything) has no effect; a column without a valid row gives map = +0, sigmaMap = NaN (sqrt(0/0), literally);
+ *     weightMap[i] is the sum of w over all B rows, as in vsom_batch_epoch; S is untouched.
+ * With an all-valid mask (per row or one_mask) map, sigmaMap, weightMap, bmuHits, lastBMU, sqres and the MSE are
+ * bit-identical to vsom_batch_epoch on the same state, chunk and lastBMU.  An empty chunk behaves as in vsom_batch_epoch.
+ * Refuses (VSOM_ERR_INVALID, nothing enqueued, the state untouched, the context stays usable): a null context, valid_host
+ * or mse_out, custom and CLR contexts, no chunk, a chunk staged ahead, an update mode other than VSOM_UPDATE_STRICT.
+ * Timed under VSOM_T_STAGE (validity packing), VSOM_T_BMU, VSOM_T_FINISH, VSOM_T_CW, VSOM_T_UPDATE (the masked chains too)
+ * and VSOM_T_SIGMA.  Device scratch: B (J + roundup(J, 32)) validity bytes (one row of each with one_mask), J ceil(B/32)
+ * words of (column, row) bits, 8 B bytes of BMU coordinates, 4 J bytes of column list and the search's slice scratch. */
+int vsom_batch_epoch_masked(vsom_ctx *ctx, double sigma, int is_first, const uint8_t *valid_host, int one_mask,
+                            float *mse_out);
 /* MSE of the last finish / online chunk (synchronises) */
 int vsom_get_mse(vsom_ctx *ctx, float *mse_out);
 

@@ -51,6 +51,7 @@ SYMBOLS = [
     "vsom_ensemble_batch_epoch", "vsom_ensemble_upload_chunks", "vsom_ensemble_bmu_batch",
     "vsom_umatrix", "vsom_get_umatrix", "vsom_ensemble_umatrix", "vsom_similarity_batch",
     "vsom_bmu_masked_batch", "vsom_evaluate_batch", "vsom_generate_batch", "vsom_decode_nodes",
+    "vsom_batch_epoch_masked",
 ]
 
 
@@ -252,6 +253,8 @@ def lib():
     if hasattr(L, "vsom_generate_batch"):       # (VSOM_LIB may name an older build: tools/generate_bench.py --route parent)
         L.vsom_generate_batch.argtypes = [vp, C.c_uint64, C.c_int, C.c_size_t, C.c_size_t, dp, dp, C.POINTER(GenerateOut)]
         L.vsom_decode_nodes.argtypes = [vp, u64p, C.c_size_t, dp, dp]
+    if hasattr(L, "vsom_batch_epoch_masked"):   # (VSOM_LIB may name an older build)
+        L.vsom_batch_epoch_masked.argtypes = [vp, C.c_double, C.c_int, C.POINTER(C.c_uint8), C.c_int, fp]
     _lib = L
     return L
 
@@ -767,6 +770,20 @@ class Context:
     def get_mse(self):
         mse = C.c_float()
         check(lib().vsom_get_mse(self._h, C.byref(mse)))
+        return np.float32(mse.value)
+
+    def batch_epoch_masked(self, sigma, is_first, valid):
+        """One batch epoch over the valid entries of the chunk only (vsom_batch_epoch_masked; Standard / Median, strict
+        update mode): the search on the masked distance, and per column the chain over the rows valid at that column.
+        valid: B x J (nonzero = valid), or a 1-D column mask of J entries applied to every row.  Returns the MSE."""
+        B = self.chunk_size
+        vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        one = vb.ndim == 1
+        if vb.shape != ((self.in_len,) if one else (B, self.in_len)):
+            raise ValueError(f"valid has shape {vb.shape}, neither ({self.in_len},) nor ({B}, {self.in_len})")
+        mse = C.c_float()
+        check(lib().vsom_batch_epoch_masked(self._h, float(sigma), int(bool(is_first)),
+                                            vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one), C.byref(mse)))
         return np.float32(mse.value)
 
     # ---- online --------------------------------------------------------

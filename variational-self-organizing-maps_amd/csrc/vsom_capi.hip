@@ -1073,6 +1073,26 @@ int vsom_batch_epoch(vsom_ctx *c, double sigma, int is_first, float *mse_out)
     return VSOM_OK;
 }
 
+int vsom_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uint8_t *valid_host, int one_mask, float *mse_out)
+{
+    CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_batch_epoch_masked");
+    if (c->transform == VSOM_CLR)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_epoch_masked: CLR contexts are not supported (residual and step run over column pairs)");
+    CHECK_ROWS(c);
+    if (!valid_host)
+        return vsom_fail(VSOM_ERR_INVALID, "valid_host is null");
+    if (!mse_out)
+        return vsom_fail(VSOM_ERR_INVALID, "mse_out is null");
+    if (!c->chunk_loaded)   // an EMPTY chunk is legal, as for vsom_batch_epoch
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    if (c->update_mode != VSOM_UPDATE_STRICT)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_epoch_masked: the masked chains exist in the strict update mode only");
+    if (int rc = launch_batch_epoch_masked(c, sigma, is_first, valid_host, one_mask))
+        return rc;
+    return vsom_get_mse(c, mse_out);
+}
+
 void *vsom_device_ptr(vsom_ctx *c, int which)
 {
     if (!c)

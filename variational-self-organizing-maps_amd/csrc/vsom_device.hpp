@@ -164,9 +164,11 @@ __device__ __forceinline__ float vsom_group_dist_lat(const float *xa, const floa
 // Som::findLocalBmu (Som.cpp:335-454) for one sample by one wavefront: 8 candidates x 8 accumulator
 // classes across the 64 lanes, unsigned (size_t) arithmetic kept literal.  Every lane
 // returns the same (minIndex, minDist); minDist == ||Comparer(x, M[minIndex])||^2.
-template <bool CLR>
-__device__ __forceinline__ void vsom_local_walk(const DistArgs &a, const float *xa, const float *xb, u64 width,
-                                                u64 height, u64 start, int lane, u64 &minIndexOut, float &minDistOut)
+// dist(node, k): the distance of the sample to `node`, computed by the 8 lanes k = 0..7 of a group (vsom_group_dist's
+// contract); vsom_local_walk below is the walk on the unmasked distance.
+template <class DistFn>
+__device__ __forceinline__ void vsom_local_walk_with(DistFn dist, u64 width, u64 height, u64 start, int lane,
+                                                     u64 &minIndexOut, float &minDistOut)
 {
     const int g = lane >> 3, k = lane & 7;
     const u64 m1 = ~0ull;   // -1uz
@@ -175,8 +177,7 @@ __device__ __forceinline__ void vsom_local_walk(const DistArgs &a, const float *
     const u64 fsy = (g <= 2) ? 1ull : ((g == 3 || g == 7) ? 0ull : m1);
 
     u64 lastBMU = start;
-    float minDist = vsom_group_dist<CLR>(xa, xb, a.ma + (size_t)lastBMU * a.ldm,
-                                         a.mb + (size_t)lastBMU * a.ldm, a.L, k);
+    float minDist = dist(lastBMU, k);
     minDist = __shfl(minDist, 0);
     u64 minIndex = lastBMU;
     u64 lastMeasured = lastBMU;
@@ -190,8 +191,7 @@ __device__ __forceinline__ void vsom_local_walk(const DistArgs &a, const float *
             u64 cy = lmY + fsy;
             cy = cy < height - 1 ? cy : height - 1;
             u64 node = cy * width + cx;
-            float d = vsom_group_dist<CLR>(xa, xb, a.ma + (size_t)node * a.ldm,
-                                           a.mb + (size_t)node * a.ldm, a.L, k);
+            float d = dist(node, k);
 #pragma unroll
             for (int i = 0; i < 8; ++i) {
                 float di = __shfl(d, i * 8);
@@ -212,8 +212,7 @@ __device__ __forceinline__ void vsom_local_walk(const DistArgs &a, const float *
                 u64 cy = lmY + off;
                 cy = cy < height - 1 ? cy : height - 1;
                 u64 node = cy * width + cx;
-                float d = vsom_group_dist<CLR>(xa, xb, a.ma + (size_t)node * a.ldm,
-                                               a.mb + (size_t)node * a.ldm, a.L, k);
+                float d = dist(node, k);
 #pragma unroll
                 for (int i = 0; i < 3; ++i) {
                     float di = __shfl(d, i * 8);
@@ -235,6 +234,17 @@ __device__ __forceinline__ void vsom_local_walk(const DistArgs &a, const float *
     }
     minIndexOut = minIndex;
     minDistOut = minDist;
+}
+
+template <bool CLR>
+__device__ __forceinline__ void vsom_local_walk(const DistArgs &a, const float *xa, const float *xb, u64 width,
+                                                u64 height, u64 start, int lane, u64 &minIndexOut, float &minDistOut)
+{
+    vsom_local_walk_with(
+        [&](u64 node, int k) {
+            return vsom_group_dist<CLR>(xa, xb, a.ma + (size_t)node * a.ldm, a.mb + (size_t)node * a.ldm, a.L, k);
+        },
+        width, height, start, lane, minIndexOut, minDistOut);
 }
 
 // SomIndex(const Som&, size_t) (SomIndex.cpp:13-18): y divides by HEIGHT (Q10)

@@ -297,6 +297,19 @@ int launch_evaluate(vsom_ctx *c, size_t r0, size_t r1, const float *binary_host,
 // vsom_masked.hip: the search over valid columns of chunk rows [r0,r1) (arguments checked by vsom_bmu_masked_batch); synchronises
 int launch_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
                   const vsom_masked_out *out);
+// pieces of launch_masked for callers that lay the scratch out themselves (vsom_masked_train.hip); they enqueue only.
+// pack: rows x J validity bytes as given -> rows x xpitch bytes of 0xFF / 0x00.  search: chunk rows [s0,s1) over the packed
+// rows vp (row s - s0 at vp + (s - s0) * xpitch; one: the row every sample shares) with the node groups of
+// vsom_masked_groups(rows of the slice); part: (s1 - s0) * grp.ng keys, nan0: s1 - s0 bytes; entry s - s0 of bmu / dist /
+// nvalid (device) belongs to row s.  slice_rows: the rows per slice that keep the search scratch within its bound.
+void vsom_masked_pack_enqueue(vsom_ctx *c, const unsigned char *raw_dev, size_t rows, unsigned char *packed_dev);
+size_t vsom_masked_search_slice_rows(const vsom_ctx *c);
+VsomNodeGroups vsom_masked_groups(const vsom_ctx *c, size_t slice);
+int vsom_masked_search_enqueue(vsom_ctx *c, u64 min_hits, size_t s0, size_t s1, const unsigned char *vp, bool one,
+                               const VsomNodeGroups &grp, u64 *part, unsigned char *nan0, u64 *bmu, float *dist,
+                               unsigned *nvalid);
+// vsom_masked_train.hip: the batch epoch over valid columns only (arguments checked by vsom_batch_epoch_masked); synchronises
+int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uint8_t *valid_host, int one_mask);
 int launch_raw_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *vrows_dev, size_t count, int from_map,
                     float *out_dev);
 // vsom_umatrix.hip: Som::updateUMatrix of the current map / sigmaMap into ctx->umatrix; enqueues only.

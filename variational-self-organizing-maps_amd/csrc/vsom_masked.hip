@@ -182,18 +182,54 @@ static size_t vsom_masked_slice_rows(const vsom_ctx *c, bool fill)
     return s;
 }
 
+// Rows of J validity bytes as the caller gives them -> rows of xpitch packed bytes (enqueues only)
+void vsom_masked_pack_enqueue(vsom_ctx *c, const unsigned char *raw_dev, size_t rows, unsigned char *packed_dev)
+{
+    hipLaunchKernelGGL(masked_pack_kernel, dim3((unsigned)rows), dim3(256), 0, c->stream, raw_dev, (int)c->J, (int)c->xpitch,
+                       reinterpret_cast<unsigned *>(packed_dev));
+}
+
+size_t vsom_masked_search_slice_rows(const vsom_ctx *c) { return vsom_masked_slice_rows(c, false); }
+
+// node groups of a slice's tile walk: at most MSK_MAXG keys per row to reduce
+VsomNodeGroups vsom_masked_groups(const vsom_ctx *c, size_t slice)
+{
+    return vsom_node_groups(((size_t)c->N + TILE - 1) / TILE, (slice + TILE - 1) / TILE, MSK_MAXG);
+}
+
+// The search of chunk rows [s0, s1) over the packed validity rows vp (row s - s0 at vp + (s - s0) * xpitch; one: the row
+// every sample shares): tile walk and reduction, entry s - s0 of bmu / dist / nvalid (device) belongs to row s.  part holds
+// (s1 - s0) * grp.ng keys, nan0 s1 - s0 bytes.  Enqueues only.
+int vsom_masked_search_enqueue(vsom_ctx *c, u64 min_hits, size_t s0, size_t s1, const unsigned char *vp, bool one,
+                               const VsomNodeGroups &grp, u64 *part, unsigned char *nan0, u64 *bmu, float *dist,
+                               unsigned *nvalid)
+{
+    const size_t N = c->N, vld = c->xpitch, n = s1 - s0;
+    const DistArgs a = vsom_dist_args(c);     // (Standard / Median: the rows themselves)
+    dim3 grid((unsigned)grp.ng, (unsigned)((n + TILE - 1) / TILE));
+    if (one)
+        hipLaunchKernelGGL(masked_tile_kernel<true>, grid, dim3(256), 0, c->stream, a, vp, (int)vld, (int)s0, (int)s1, (int)N,
+                           (int)grp.G, c->hits.p, min_hits, part, nan0);
+    else
+        hipLaunchKernelGGL(masked_tile_kernel<false>, grid, dim3(256), 0, c->stream, a, vp, (int)vld, (int)s0, (int)s1, (int)N,
+                           (int)grp.G, c->hits.p, min_hits, part, nan0);
+    hipLaunchKernelGGL(masked_reduce_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, part, (int)grp.ng, nan0,
+                       reinterpret_cast<const unsigned *>(vp), (int)vld, (int)one, (int)n, bmu, dist, nvalid);
+    VSOM_HIP_CHECK(hipGetLastError());
+    return VSOM_OK;
+}
+
 int launch_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
                   const vsom_masked_out *out)
 {
     TimerScope ts(c, VSOM_T_BMU);
-    const size_t N = c->N, J = c->J, vld = c->xpitch, rows = r1 - r0;
+    const size_t J = c->J, vld = c->xpitch, rows = r1 - r0;
     if (rows == 0)
         return VSOM_OK;
     const bool one = one_mask != 0;
     const size_t slice = std::min(vsom_masked_slice_rows(c, out->fill != nullptr), rows);
-    // node groups: at most MSK_MAXG keys per row to reduce
-    const VsomNodeGroups grp = vsom_node_groups((N + TILE - 1) / TILE, (slice + TILE - 1) / TILE, MSK_MAXG);
-    const size_t G = grp.G, ng = grp.ng;
+    const VsomNodeGroups grp = vsom_masked_groups(c, slice);
+    const size_t ng = grp.ng;
     const size_t vrows = one ? 1 : slice;
     // a slice's validity bytes as given and packed (0xFF / 0x00, xpitch per row), node-group keys, results and imputed rows
     vsom_layout lay;
@@ -204,25 +240,16 @@ int launch_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const uint8_t
     const auto nvalid = lay.add<unsigned>(slice);
     VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
 
-    const DistArgs a = vsom_dist_args(c);     // (Standard / Median: the rows themselves)
-    unsigned *packed = reinterpret_cast<unsigned *>(lay.at(valid));
     for (size_t s0 = r0; s0 < r1; s0 += slice) {
         const size_t s1 = std::min(r1, s0 + slice), n = s1 - s0, off = s0 - r0;
         if (!one || s0 == r0) {     // (a column mask is packed once)
             const size_t vr = one ? 1 : n;
             VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(raw), valid_host + (one ? 0 : off * J), vr * J, hipMemcpyHostToDevice, c->stream));
-            hipLaunchKernelGGL(masked_pack_kernel, dim3((unsigned)vr), dim3(256), 0, c->stream, lay.at(raw), (int)J, (int)vld,
-                               packed);
+            vsom_masked_pack_enqueue(c, lay.at(raw), vr, lay.at(valid));
         }
-        dim3 grid((unsigned)ng, (unsigned)((n + TILE - 1) / TILE));
-        if (one)
-            hipLaunchKernelGGL(masked_tile_kernel<true>, grid, dim3(256), 0, c->stream, a, lay.at(valid), (int)vld, (int)s0,
-                               (int)s1, (int)N, (int)G, c->hits.p, min_hits, lay.at(part), lay.at(nan0));
-        else
-            hipLaunchKernelGGL(masked_tile_kernel<false>, grid, dim3(256), 0, c->stream, a, lay.at(valid), (int)vld, (int)s0,
-                               (int)s1, (int)N, (int)G, c->hits.p, min_hits, lay.at(part), lay.at(nan0));
-        hipLaunchKernelGGL(masked_reduce_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, c->stream, lay.at(part), (int)ng,
-                           lay.at(nan0), packed, (int)vld, (int)one, (int)n, lay.at(bmu), lay.at(dist), lay.at(nvalid));
+        if (int rc = vsom_masked_search_enqueue(c, min_hits, s0, s1, lay.at(valid), one, grp, lay.at(part), lay.at(nan0),
+                                                lay.at(bmu), lay.at(dist), lay.at(nvalid)))
+            return rc;
         if (out->fill)
             hipLaunchKernelGGL(masked_fill_kernel, dim3((unsigned)n, (unsigned)((J + 255) / 256)), dim3(256), 0, c->stream,
                                reinterpret_cast<const unsigned *>(c->Xs.p), (int)c->xpitch,

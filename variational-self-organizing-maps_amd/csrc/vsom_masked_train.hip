@@ -1,0 +1,305 @@
+// vsom_masked_train.hip -- Som::trainBatchSomEpoch (Som.cpp:756-879) over the VALID entries of the chunk only (gfx950;
+// Standard / Median, strict arithmetic): vsom_batch_epoch_masked.
+//
+// Phase 1 is the search on the distance of vsom_masked.hip (r_d = valid ? m_d - x_d : +0): the masked tile walk for the
+// first epoch, findLocalBmu's walk (vsom_local_walk_with) on the same distance afterwards, both straight into lastBMU and
+// sqres; the finish step is the unmasked one.  Phase 2 runs the unmasked phase 2 over the whole map first -- it yields
+// weightMap (the sum of w over ALL rows) and, bit for bit, every column that has no invalid entry in the chunk -- and then
+// recomputes the "dirty" columns, those with at least one invalid entry, with a per-column weight sum:
+//
+//  masked_bxy_kernel    : SomIndex(lastBMU[j]) of every row, once (the chains read it as a scalar pair)
+//  masked_bits_kernel   : packed validity bytes (rows x xpitch, or the one shared row) -> bits[column][row / 32], 32 rows
+//                         to a word, rows past the chunk read as invalid
+//  masked_dirty_kernel  : one workgroup: the columns with an invalid entry among the chunk's rows, in ascending order, and
+//                         their count (ballot compaction; no host round trip)
+//  masked_chain_kernel  : lane = node, one wavefront per block of MT_CB dirty columns, M, S and W_d of every column in
+//                         registers.  The rows are walked in load order in groups of MT_U: the group's BMU coordinates,
+//                         sample values and validity word are wave-uniform (scalar loads), w comes from the neighbourhood
+//                         table the unmasked path built for this sigma.  For a valid (row, column):
+//                             W_d += w ; delta = Stepper(x, M) ; M = M + (w / W_d) * delta ; S = S + (w * delta) * delta
+//                         (one rounding per operation, a correctly rounded division: this translation unit is built with
+//                         the strict flags), an invalid one is skipped: what x holds there is loaded and never used.  At
+//                         the end map = M, sigmaMap = sqrt(S / W_d): a column without a valid row is +0 / NaN.  No atomics,
+//                         no LDS; workgroups past the dirty count leave at once.
+#include "vsom_device.hpp"
+#include <algorithm>
+
+#define MT_CB 4     // columns per wavefront
+#define MT_U 8      // rows per group (operands fetched together before the dependent steps)
+
+__global__ __launch_bounds__(256) void masked_bxy_kernel(const u64 *__restrict__ lastbmu, int B, u64 W, u64 H,
+                                                         int2 *__restrict__ bxy)
+{
+    const int j = blockIdx.x * 256 + threadIdx.x;
+    if (j >= B)
+        return;
+    int bx, by;
+    vsom_somindex(lastbmu[j], W, H, bx, by);        // SomIndex(*this, lastBMU[j]) (Som.cpp:847-849)
+    bxy[j] = make_int2(bx, by);
+}
+
+// thread = (column, word): consecutive lanes read consecutive bytes of a packed row
+__global__ __launch_bounds__(256) void masked_bits_kernel(const unsigned char *__restrict__ packed, int vld, int one, int J,
+                                                          int B, int nwords, unsigned *__restrict__ bits)
+{
+    const int d = blockIdx.y * 256 + threadIdx.x, w = blockIdx.x;
+    if (d >= J)
+        return;
+    unsigned v = 0;
+    const int nt = B - 32 * w < 32 ? B - 32 * w : 32;
+    for (int t = 0; t < nt; ++t)
+        if (packed[(one ? 0 : (size_t)(32 * w + t) * vld) + d])
+            v |= 1u << t;
+    bits[(size_t)d * nwords + w] = v;
+}
+
+// dcols[0 .. *ndirty): the columns with an invalid entry in rows [0, B), ascending
+__global__ __launch_bounds__(256) void masked_dirty_kernel(const unsigned *__restrict__ bits, int J, int B, int nwords,
+                                                           int *__restrict__ dcols, unsigned *__restrict__ ndirty)
+{
+    __shared__ unsigned wcnt[4];
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    unsigned base = 0;
+    for (int d0 = 0; d0 < J; d0 += 256) {
+        const int d = d0 + (int)threadIdx.x;
+        bool dirty = false;
+        if (d < J)
+            for (int w = 0; w < nwords; ++w) {
+                const int nt = B - 32 * w < 32 ? B - 32 * w : 32;
+                const unsigned full = nt == 32 ? ~0u : (1u << nt) - 1u;
+                dirty = dirty || bits[(size_t)d * nwords + w] != full;
+            }
+        const u64 m = __ballot(dirty);
+        if (lane == 0)
+            wcnt[wv] = (unsigned)__popcll(m);
+        __syncthreads();
+        unsigned at = base;
+        for (int i = 0; i < wv; ++i)
+            at += wcnt[i];
+        if (dirty)
+            dcols[at + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = d;
+        base += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0)
+        *ndirty = base;
+}
+
+// vsom_group_dist (vsom_device.hpp) with the residual +0 at invalid columns: the same operations in the same order per
+// accumulator class, the same reduction tree.  v: the row's packed validity bytes.
+__device__ __forceinline__ float masked_resid(float x, unsigned char v, float m) { return v ? m - x : 0.f; }
+
+__device__ __forceinline__ float masked_group_dist(const float *x, const unsigned char *v, const float *m, int L, int k)
+{
+    const int L8 = L & ~7;
+    float acc = 0.f;
+#pragma unroll 14
+    for (int d = k; d < L8; d += 8) {
+        const float r = masked_resid(x[d], v[d], m[d]);
+        const float p = r * r;
+        acc = acc + p;
+    }
+    float q = acc + __shfl_xor(acc, 4);
+    const int rem = L - L8;
+    if (rem >= 4) {
+        const int d = L8 + (k & 3);
+        const float r = masked_resid(x[d], v[d], m[d]);
+        const float p = r * r;
+        q = q + p;
+    }
+    const float t = q + __shfl_xor(q, 2);
+    float res = t + __shfl_xor(t, 1);
+    for (int tt = (rem >= 4 ? 4 : 0); tt < rem; ++tt) {
+        const int d = L8 + tt;
+        const float r = masked_resid(x[d], v[d], m[d]);
+        const float p = r * r;
+        res = res + p;
+    }
+    return res;
+}
+
+// bmu_local_kernel (vsom_bmu.hip) on the masked distance: one wavefront per row
+__global__ __launch_bounds__(256) void masked_local_kernel(DistArgs a, const unsigned char *__restrict__ vp, int vld, int one,
+                                                           int B, u64 width, u64 height, u64 *__restrict__ lastbmu,
+                                                           float *__restrict__ sqres)
+{
+    const int s = (int)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    const int lane = threadIdx.x & 63;
+    if (s >= B)
+        return;   // wave-uniform
+    const float *x = a.xa + (size_t)s * a.ldx;
+    const unsigned char *v = vp + (one ? 0 : (size_t)s * vld);
+    u64 minIndex;
+    float minDist;
+    vsom_local_walk_with([&](u64 node, int k) { return masked_group_dist(x, v, a.ma + (size_t)node * a.ldm, a.L, k); },
+                         width, height, lastbmu[s], lane, minIndex, minDist);
+    if (lane == 0) {
+        lastbmu[s] = minIndex;
+        sqres[s] = minDist;
+    }
+}
+
+// Transformation::Stepper (Transformation.cpp:11-12, 49-50); sign(): NaN -> NaN, else (a > 0) - (a < 0)
+template <bool MEDIAN>
+__device__ __forceinline__ float masked_stepper(float x, float M)
+{
+    const float dl = x - M;
+    if (!MEDIAN)
+        return dl;
+    return dl != dl ? dl : (float)((dl > 0.f) - (dl < 0.f));
+}
+
+template <bool MEDIAN>
+__global__ __launch_bounds__(256) void masked_chain_kernel(const float *__restrict__ Xs, int ldx, const int2 *__restrict__ bxy,
+                                                           int B, const unsigned *__restrict__ bits, int nwords,
+                                                           const int *__restrict__ dcols,
+                                                           const unsigned *__restrict__ ndirty,
+                                                           const float *__restrict__ lut, int lutw, int luth, int W, int H,
+                                                           int N, float *__restrict__ map, float *__restrict__ sigma,
+                                                           int pitch)
+{
+    static_assert(32 % MT_U == 0, "a group of rows lies within one validity word");
+    const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+    const int first = ((int)blockIdx.y * 4 + wv) * MT_CB;     // position of the wavefront's first column in the dirty list
+    const int nd = (int)*ndirty;
+    if (first >= nd)
+        return;                                                // (wavefront-uniform; the kernel has no barrier)
+    const int lane = threadIdx.x & 63;
+    const int node = (int)blockIdx.x * 64 + lane;
+    int cx, cy;
+    vsom_somindex((u64)(node < N ? node : 0), (u64)W, (u64)H, cx, cy);     // SomIndex(*this, index) (Som.cpp:816)
+
+    int col[MT_CB];                                            // (uniform) -1: no column
+#pragma unroll
+    for (int c = 0; c < MT_CB; ++c)
+        col[c] = first + c < nd ? dcols[first + c] : -1;
+    float M[MT_CB], S[MT_CB], Wd[MT_CB];
+#pragma unroll
+    for (int c = 0; c < MT_CB; ++c)
+        M[c] = S[c] = Wd[c] = 0.f;                             // :840, :843-844
+
+    const int last = B - 1;
+    for (int j0 = 0; j0 < B; j0 += MT_U) {
+        // the group's operands first: rows past the chunk are clamped re-reads of the last row, never consumed
+        float w[MT_U], x[MT_U][MT_CB];
+        unsigned vb[MT_CB];
+#pragma unroll
+        for (int c = 0; c < MT_CB; ++c)
+            vb[c] = col[c] >= 0 ? bits[(size_t)col[c] * nwords + (j0 >> 5)] >> (j0 & 31) : 0u;
+#pragma unroll
+        for (int u = 0; u < MT_U; ++u) {
+            const int j = j0 + u < last ? j0 + u : last;
+            const int2 b = bxy[j];
+            int dx = cx - b.x, dy = cy - b.y;
+            dx = dx < 0 ? -dx : dx;
+            dy = dy < 0 ? -dy : dy;
+            dx = dx < lutw ? dx : lutw - 1;
+            dy = dy < luth ? dy : luth - 1;
+            w[u] = lut[dy * lutw + dx];                        // (float)calculateNeighbourhoodWeight(...) :851
+#pragma unroll
+            for (int c = 0; c < MT_CB; ++c)
+                x[u][c] = Xs[(size_t)j * ldx + (col[c] >= 0 ? col[c] : 0)];
+        }
+#pragma unroll
+        for (int u = 0; u < MT_U; ++u) {
+#pragma unroll
+            for (int c = 0; c < MT_CB; ++c) {
+                if (j0 + u < B && ((vb[c] >> u) & 1u)) {       // (uniform) a row invalid at the column is skipped
+                    Wd[c] = Wd[c] + w[u];                      // :857
+                    const float cc = w[u] / Wd[c];             // :864 (0/0 -> NaN, Q7)
+                    const float dl = masked_stepper<MEDIAN>(x[u][c], M[c]);   // :861
+                    const float t = cc * dl;
+                    M[c] = M[c] + t;                           // :864
+                    float q = w[u] * dl;                       // :867
+                    q = q * dl;
+                    S[c] = S[c] + q;
+                }
+            }
+        }
+    }
+    if (node < N) {
+#pragma unroll
+        for (int c = 0; c < MT_CB; ++c)
+            if (col[c] >= 0) {
+                map[(size_t)node * pitch + col[c]] = M[c];                      // :870
+                sigma[(size_t)node * pitch + col[c]] = sqrtf(S[c] / Wd[c]);     // :873
+            }
+    }
+}
+
+int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uint8_t *valid_host, int one_mask)
+{
+    const size_t B = c->B, N = c->N, J = c->J, vld = c->xpitch;
+    int rc;
+    if (B == 0) {       // the epoch of an empty chunk reads no validity
+        if ((rc = launch_finish(c)) || (rc = launch_phase2(c, sigma, 0, N)))
+            return rc;
+        VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+        return VSOM_OK;
+    }
+    const bool one = one_mask != 0;
+    const size_t vrows = one ? 1 : B, nwords = (B + 31) / 32;
+    const size_t slice = std::min(vsom_masked_search_slice_rows(c), B);
+    const VsomNodeGroups grp = vsom_masked_groups(c, slice);
+    // the chunk's validity bytes as given and packed, the (column, row) bits, BMU coordinates, dirty columns and their count,
+    // and a search slice's node-group keys and flags (the valid-column counts of the reduction are not used)
+    vsom_layout lay;
+    const auto raw = lay.add<unsigned char>(vrows * J), packed = lay.add<unsigned char>(vrows * vld);
+    const auto bits = lay.add<unsigned>(J * nwords);
+    const auto dcols = lay.add<int>(J);
+    const auto ndirty = lay.add<unsigned>(1);
+    const auto bxy = lay.add<int2>(B);
+    const auto part = lay.add<u64>(is_first ? slice * grp.ng : 0);
+    const auto nan0 = lay.add<unsigned char>(is_first ? slice : 0);
+    const auto nvalid = lay.add<unsigned>(is_first ? slice : 0);
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+
+    {
+        TimerScope ts(c, VSOM_T_STAGE);
+        VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(raw), valid_host, vrows * J, hipMemcpyHostToDevice, c->stream));
+        vsom_masked_pack_enqueue(c, lay.at(raw), vrows, lay.at(packed));
+        hipLaunchKernelGGL(masked_bits_kernel, dim3((unsigned)nwords, (unsigned)((J + 255) / 256)), dim3(256), 0, c->stream,
+                           lay.at(packed), (int)vld, (int)one, (int)J, (int)B, (int)nwords, lay.at(bits));
+        hipLaunchKernelGGL(masked_dirty_kernel, dim3(1), dim3(256), 0, c->stream, lay.at(bits), (int)J, (int)B, (int)nwords,
+                           lay.at(dcols), lay.at(ndirty));
+        VSOM_HIP_CHECK(hipGetLastError());
+    }
+    {   // phase 1 (:762-806) on the masked distance, results where phase 1 stores them
+        TimerScope ts(c, VSOM_T_BMU);
+        if (is_first) {
+            for (size_t s0 = 0; s0 < B; s0 += slice) {
+                const size_t s1 = std::min(B, s0 + slice);
+                if ((rc = vsom_masked_search_enqueue(c, 0, s0, s1, lay.at(packed) + (one ? 0 : s0 * vld), one, grp, lay.at(part),
+                                                     lay.at(nan0), c->lastbmu.p + s0, c->sqres.p + s0, lay.at(nvalid))))
+                    return rc;
+            }
+        } else {
+            hipLaunchKernelGGL(masked_local_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, vsom_dist_args(c),
+                               lay.at(packed), (int)vld, (int)one, (int)B, (u64)c->W, (u64)c->H, c->lastbmu.p, c->sqres.p);
+            VSOM_HIP_CHECK(hipGetLastError());
+        }
+    }
+    if ((rc = launch_finish(c)))
+        return rc;
+    // phase 2 (:809-876) as it is: weightMap and every clean column; it builds the neighbourhood table of this sigma
+    if ((rc = launch_phase2(c, sigma, 0, N)))
+        return rc;
+    c->rows_free_valid = false;     // the chains below read the staged rows
+    {
+        TimerScope ts(c, VSOM_T_UPDATE);
+        hipLaunchKernelGGL(masked_bxy_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, c->lastbmu.p, (int)B,
+                           (u64)c->W, (u64)c->H, lay.at(bxy));
+        const dim3 grid((unsigned)((N + 63) / 64), (unsigned)(((J + MT_CB - 1) / MT_CB + 3) / 4));
+        if (c->transform == VSOM_MEDIAN)
+            hipLaunchKernelGGL(masked_chain_kernel<true>, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, lay.at(bxy),
+                               (int)B, lay.at(bits), (int)nwords, lay.at(dcols), lay.at(ndirty), c->lut.p, (int)c->lut_w,
+                               (int)c->lut_h, (int)c->W, (int)c->H, (int)N, c->map.p, c->sigma.p, (int)c->pitch);
+        else
+            hipLaunchKernelGGL(masked_chain_kernel<false>, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, lay.at(bxy),
+                               (int)B, lay.at(bits), (int)nwords, lay.at(dcols), lay.at(ndirty), c->lut.p, (int)c->lut_w,
+                               (int)c->lut_h, (int)c->W, (int)c->H, (int)N, c->map.p, c->sigma.p, (int)c->pitch);
+        VSOM_HIP_CHECK(hipGetLastError());
+    }
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VSOM_OK;
+}

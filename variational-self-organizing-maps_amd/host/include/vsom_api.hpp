@@ -441,6 +441,14 @@ public:
     void trainBatchSom(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
                        bool updateUMatrixAfterEpoch = false);
     float trainBatchSomEpoch(DataSet &data, double currentSigma, bool isFirst);
+    // [MI355X build] extension: trainBatchSomEpoch / trainBatchSom over the VALID entries of the rows only (the data set's
+    // validity flags; one vsom_batch_epoch_masked call per chunk, include/vsom_hip.h): a missing field neither attracts the
+    // search nor enters the means and sigmas of its column.  The driver is trainBatchSom's: the sigma schedule, the stop at
+    // sigma < 1, the chunk loop and the metrics.  With every column valid the result is trainBatchSom's bit for bit.
+    // Standard / Median on one device only.
+    float trainBatchSomEpochMasked(DataSet &data, double currentSigma, bool isFirst);
+    void trainBatchSomMasked(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
+                             bool updateUMatrixAfterEpoch = false);
     TrainingReturnValue trainSingle(const Eigen::VectorXf &v, const Eigen::VectorXf &valid,
                                     const Eigen::VectorXf &weights, const double eta, const double sigma,
                                     size_t &lastBMU, const WeigthDecayFunction weightDecayFunction);

@@ -1004,6 +1004,20 @@ double Som::euclidianWeightedDist(const size_t &pos, const Eigen::VectorXf &v, c
     return (double)d;
 }
 
+// the validity flags of the loaded rows as the byte mask of the masked calls (collected row by row, as similarityRows does)
+static std::vector<uint8_t> validity_bytes(const DataSet &data, size_t inLen)
+{
+    const size_t n = data.size();
+    std::vector<uint8_t> valid(n * inLen, 0);   // (a column the data set has no flag for does not count)
+    for (size_t i = 0; i < n; ++i) {
+        const Eigen::VectorXi v = data.getValidity(i);
+        const size_t m = std::min<size_t>((size_t)v.size(), inLen);
+        for (size_t d = 0; d < m; ++d)
+            valid[i * inLen + d] = v[(Eigen::Index)d] != 0;
+    }
+    return valid;
+}
+
 // ---- batch training ----------------------------------------------------------------------------
 float Som::trainBatchSomEpoch(DataSet &dataset, double currentSigma, bool isFirst)
 {
@@ -1142,6 +1156,66 @@ void Som::trainBatchSom(DataSet &data, size_t numberOfEpochs, double sigma0, dou
             have = true;              // chunk 0 of epoch i+1 is already loaded and on its way
         else
             data.resetStreamLoadPosition();   // :749
+        if (updateUMatrixAfterEpoch)
+            updateUMatrix(data.getWeights());   // :751-752
+    }
+}
+
+// upload, lastBMU in, one vsom_batch_epoch_masked call with the data set's validity flags, lastBMU out; no refreshHost()
+float Som::trainBatchSomEpochMasked(DataSet &dataset, double currentSigma, bool isFirst)
+{
+    requireDevicePath("trainBatchSomEpochMasked");
+    if (grp)
+        throw std::runtime_error("trainBatchSomEpochMasked: a multi-GPU Som has no masked epoch (vsom_batch_epoch_masked "
+                                 "runs on one context)");
+    const size_t B = dataset.size();
+    std::vector<uint64_t> lb(B);
+    if (!isFirst)
+        for (size_t s = 0; s < B; ++s)
+            lb[s] = dataset.getLastBMU(s);
+    std::vector<uint8_t> valid = validity_bytes(dataset, inLen);
+    if (valid.empty())
+        valid.assign(1, 0);       // (an empty chunk reads no flag; the call wants a pointer)
+    float mse = 0.f;
+    check(vsom_upload_chunk(ctx, dataset.contiguous(), B), "vsom_upload_chunk");
+    if (!isFirst)
+        check(vsom_set_last_bmu(ctx, lb.data()), "vsom_set_last_bmu");
+    check(vsom_batch_epoch_masked(ctx, currentSigma, isFirst ? 1 : 0, valid.data(), 0, &mse), "vsom_batch_epoch_masked");
+    check(vsom_get_last_bmu(ctx, lb.data()), "vsom_get_last_bmu");
+    for (size_t s = 0; s < B; ++s)
+        dataset.getLastBMU(s) = (size_t)lb[s];
+    hostStale = true;
+    return mse;
+}
+
+// Som.cpp:716-754 with the masked epoch.  The call is blocking (the flags travel with it), so the chunk loop is the
+// reference's own, without trainBatchSom's software pipeline.
+void Som::trainBatchSomMasked(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
+                              bool updateUMatrixAfterEpoch)
+{
+    requireDevicePath("trainBatchSomMasked");
+    {
+        const std::lock_guard<std::mutex> lock(metricsMutex);   // (the reference resets without it: trainBatchSom)
+        metrics = Som::Metrics(numberOfEpochs);
+    }
+    for (size_t i = 0; i < numberOfEpochs; ++i) {
+        std::cout << "Training VSOM epoch " << i << "/" << numberOfEpochs << '\n';
+        const auto sigma = sigma0 * std::exp(-sigmaDecay * static_cast<double>(i));   // :727
+        if (sigma < 1.0)
+            return;   // :729-730
+        auto meanSquareError = float{0.0f};
+        auto countDataChunks = size_t{0};
+        while (!data.hasReadWholeDataStream()) {   // :735
+            data.loadNextDataFromStream();
+            meanSquareError += trainBatchSomEpochMasked(data, sigma, i == 0);
+            ++countDataChunks;
+        }
+        meanSquareError /= static_cast<float>(countDataChunks);   // :743
+        {
+            const std::lock_guard<std::mutex> lock(metricsMutex);
+            metrics.MeanSquaredError[i] = meanSquareError;
+        }
+        data.resetStreamLoadPosition();   // :749
         if (updateUMatrixAfterEpoch)
             updateUMatrix(data.getWeights());   // :751-752
     }
@@ -1551,19 +1625,13 @@ Som::SimilarityRows Som::similarityRows(const DataSet *data, int numOfSigmas, si
     return r;
 }
 
-// upload, one vsom_bmu_masked_batch call with the data set's validity flags (collected row by row, as similarityRows does)
+// upload, one vsom_bmu_masked_batch call with the data set's validity flags
 void Som::maskedRows(const DataSet *data, size_t minBmuHits, uint64_t *bmu, float *dist, float *fill) const
 {
     const size_t n = data->size();
     if (n == 0)
         return;
-    std::vector<uint8_t> valid(n * inLen, 0);   // (a column the data set has no flag for does not count)
-    for (size_t i = 0; i < n; ++i) {
-        const Eigen::VectorXi v = data->getValidity(i);
-        const size_t m = std::min<size_t>((size_t)v.size(), inLen);
-        for (size_t d = 0; d < m; ++d)
-            valid[i * inLen + d] = v[(Eigen::Index)d] != 0;
-    }
+    const std::vector<uint8_t> valid = validity_bytes(*data, inLen);
     joinGroup();
     check(vsom_upload_chunk(ctx, data->contiguous(), n), "vsom_upload_chunk");
     vsom_masked_out out = {bmu, dist, nullptr, fill};

@@ -497,6 +497,21 @@ class Som:
         dataset.lastBMU[...] = self.ctx.get_last_bmu()
         return mse
 
+    def trainBatchSomEpochMasked(self, dataset, currentSigma, isFirst):
+        """extension: trainBatchSomEpoch over the valid entries of the loaded rows only (capi.Context.batch_epoch_masked): a
+        missing field neither attracts the search nor enters the means and sigmas.  The validity comes from the data set
+        when it has one (an attribute `validity`, loaded rows x J, nonzero = valid), as in findBmuMasked; without one every
+        column is valid."""
+        self.ctx.upload_chunk(dataset.data)
+        if not isFirst:
+            self.ctx.set_last_bmu(dataset.lastBMU)
+        valid = getattr(dataset, "validity", None)
+        if valid is None:
+            valid = np.ones(self.ctx.in_len, np.uint8)
+        mse = self.ctx.batch_epoch_masked(currentSigma, isFirst, valid)
+        dataset.lastBMU[...] = self.ctx.get_last_bmu()
+        return mse
+
     # ---- U-matrix (Som.cpp:143-157, 999-1111) -------------------------------------------------
     def updateUMatrix(self, weights=None):
         """Mean sigma-normalised raw distance of every node to its 3/5/8 neighbours, diagonals weighted 0.3;
@@ -554,6 +569,14 @@ class Som:
         return getattr(self, "uMatrix", np.zeros(self.width * self.height, np.float64))
 
     def trainBatchSom(self, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch=False):
+        self._trainBatchSom(self.trainBatchSomEpoch, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch)
+
+    def trainBatchSomMasked(self, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch=False):
+        """extension: trainBatchSom with trainBatchSomEpochMasked as its epoch -- the same sigma schedule, stop at
+        sigma < 1, chunk loop and metrics"""
+        self._trainBatchSom(self.trainBatchSomEpochMasked, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch)
+
+    def _trainBatchSom(self, epoch, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch):
         self.metrics = Metrics(numberOfEpochs)                    # :719
         for i in range(numberOfEpochs):
             if self._verbose:
@@ -565,7 +588,7 @@ class Som:
             count = 0
             while not data.hasReadWholeDataStream():              # :735
                 data.loadNextDataFromStream()
-                mse = np.float32(mse + self.trainBatchSomEpoch(data, sigma, i == 0))
+                mse = np.float32(mse + epoch(data, sigma, i == 0))
                 count += 1
             mse = np.float32(mse / np.float32(count))             # :743
             self.metrics.MeanSquaredError[i] = mse
