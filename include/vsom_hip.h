@@ -517,6 +517,24 @@ int vsom_batch_epoch_masked(vsom_ctx *ctx, double sigma, int is_first, const uin
                             float *mse_out);
 /* MSE of the last finish / online chunk (synchronises) */
 int vsom_get_mse(vsom_ctx *ctx, float *mse_out);
+/* A whole batch schedule on the chunk currently loaded, in one call.  The result is, bit for bit,
+ * that of
+ *     for ep in 0 .. epochs-1:
+ *         if ep > 0 and reset_bmu: lastBMU := 0            (the reference's per-epoch reload, DataSet.cpp:136-137)
+ *         batch_epoch(ctx, sigma[ep], ep == 0, &mse_out[ep])
+ * so epoch 0 runs findBmu and the later ones findLocalBmu from lastBMU; reset_bmu = 1 is trainBatchSom on a one-chunk data
+ * set, reset_bmu = 0 carries every row's BMU into the next epoch's walk.  The caller supplies every sigma (the stop rule
+ * sigma < 1 of Som.cpp:729-730 belongs to the mirrors); sigma <= 1 is legal (the 1/0 table).  Map, sigmaMap, weightMap,
+ * bmuHits (accumulated over all epochs), lastBMU, sqres, the MSE word and the context's bookkeeping end as after the last
+ * call of that sequence; S is untouched; the neighbourhood table cached by the single-epoch calls is left alone.
+ * Where the single epoch takes the one-launch kernel of a tiny map (not custom, not VSOM_NO_TINY=1) and every sigma is
+ * finite, one launch runs up to VSOM_SCHEDULE_MAX_EPOCHS epochs (longer schedules: successive launches, each with the
+ * tables of its own epochs); every other
+ * context runs the sequence above inside the library.  epochs = 0: nothing is done (VSOM_OK).  The call blocks.
+ * Refuses (VSOM_ERR_INVALID, nothing enqueued, state untouched): a null context; with epochs > 0 a null sigma or mse_out,
+ * no chunk loaded, the next chunk staged ahead over the current chunk's rows (custom contexts included). */
+#define VSOM_SCHEDULE_MAX_EPOCHS 1024
+int vsom_batch_schedule(vsom_ctx *ctx, const double *sigma, size_t epochs, int reset_bmu, float *mse_out /*[epochs]*/);
 
 /* ---- online path -----------------------------------------------------------------------
  * Som::trainSingle (Som.cpp:885-947) on one host vector; residual_out has
@@ -577,6 +595,15 @@ size_t vsom_ensemble_size(const vsom_ensemble *e);
 int vsom_ensemble_train_online_chunk_fetch(vsom_ensemble *e, const double *eta, const double *sigma, const int *decay_fn,
                                            int first_chunk, uint64_t *const *lastbmu_out, float *mse_out);
 int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_first, float *mse_out);
+/* vsom_batch_schedule for every member, each with its own schedule: sigma[k] / mse_out[k] hold epochs[k] values.  Per
+ * member the result of vsom_batch_schedule(member k, sigma[k], epochs[k], reset_bmu, mse_out[k]).  Members on the fast
+ * path of that call run as one launch per kind, one workgroup per member looping its own epochs; members whose schedules
+ * name the same sigma on the same table shape share one table.  Every other member runs its sequence in the same call;
+ * a member with epochs[k] = 0 is not touched.  Refuses (VSOM_ERR_INVALID, naming the member, before anything is enqueued
+ * for any member): a null ensemble; a null epochs array; for a member with epochs[k] > 0 a null sigma, mse_out, sigma[k]
+ * or mse_out[k], no chunk loaded, the next chunk staged ahead over its rows. */
+int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma /*[K][epochs[k]]*/, const size_t *epochs /*[K]*/,
+                                 int reset_bmu, float *const *mse_out /*[K][epochs[k]]*/);
 /* Every member's chunk from ONE host buffer.  Member k gets B[k] rows of its own row length J_k (the length
  * vsom_upload_chunk reads for that member), contiguous at x_host + offset[k] (offsets in floats).  Several members may
  * name the same rows (equal offsets: a sweep over one data set).  n_floats = the extent of x_host.  Afterwards every call

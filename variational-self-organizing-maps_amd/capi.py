@@ -51,8 +51,9 @@ SYMBOLS = [
     "vsom_ensemble_batch_epoch", "vsom_ensemble_upload_chunks", "vsom_ensemble_bmu_batch",
     "vsom_umatrix", "vsom_get_umatrix", "vsom_ensemble_umatrix", "vsom_similarity_batch",
     "vsom_bmu_masked_batch", "vsom_evaluate_batch", "vsom_generate_batch", "vsom_decode_nodes",
-    "vsom_batch_epoch_masked",
+    "vsom_batch_epoch_masked", "vsom_batch_schedule", "vsom_ensemble_batch_schedule",
 ]
+SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
 
 class SimilarityOut(C.Structure):
@@ -255,6 +256,9 @@ def lib():
         L.vsom_decode_nodes.argtypes = [vp, u64p, C.c_size_t, dp, dp]
     if hasattr(L, "vsom_batch_epoch_masked"):   # (VSOM_LIB may name an older build)
         L.vsom_batch_epoch_masked.argtypes = [vp, C.c_double, C.c_int, C.POINTER(C.c_uint8), C.c_int, fp]
+    if hasattr(L, "vsom_batch_schedule"):
+        L.vsom_batch_schedule.argtypes = [vp, dp, C.c_size_t, C.c_int, fp]
+        L.vsom_ensemble_batch_schedule.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_size_t), C.c_int, C.POINTER(fp)]
     _lib = L
     return L
 
@@ -772,6 +776,16 @@ class Context:
         check(lib().vsom_get_mse(self._h, C.byref(mse)))
         return np.float32(mse.value)
 
+    def batch_schedule(self, sigmas, reset_bmu=True):
+        """A whole batch schedule on the loaded chunk in one call (vsom_batch_schedule): epoch 0 with the exact search,
+        the later ones with the local walk -- from unit 0 (reset_bmu, the reference's per-epoch reload) or from the
+        previous epoch's BMU.  sigmas: one value per epoch.  Returns every epoch's MSE [float32 array]."""
+        sg = _schedule(sigmas)
+        mse = np.zeros(sg.size, np.float32)
+        check(lib().vsom_batch_schedule(self._h, sg.ctypes.data_as(C.POINTER(C.c_double)), sg.size, int(bool(reset_bmu)),
+                                        _f(mse)))
+        return mse
+
     def batch_epoch_masked(self, sigma, is_first, valid):
         """One batch epoch over the valid entries of the chunk only (vsom_batch_epoch_masked; Standard / Median, strict
         update mode): the search on the masked distance, and per column the chain over the rows valid at that column.
@@ -969,6 +983,21 @@ class Group:
         return np.float32(mse.value)
 
 
+def _schedule(sigmas):
+    """a schedule's sigma values as a contiguous 1-D float64 array (ValueError for any other shape)"""
+    sg = np.asarray(sigmas, dtype=np.float64)
+    if sg.ndim != 1:
+        raise ValueError(f"a schedule is a 1-D sequence of sigma values, got shape {sg.shape}")
+    return np.ascontiguousarray(sg)
+
+
+def _is_nested(sigmas):
+    """one schedule per member (a sequence of sequences) rather than one schedule of scalars"""
+    if isinstance(sigmas, np.ndarray):
+        return sigmas.ndim == 2 or sigmas.dtype == object
+    return hasattr(sigmas, "__len__") and len(sigmas) > 0 and all(hasattr(v, "__len__") for v in sigmas)
+
+
 class Ensemble:
     """A set of Contexts on one device trained by one call (include/vsom_hip.h, vsom_ensemble): the same results, bit for
     bit, as the single-context call on every member in turn.  Members stay ordinary Contexts (upload, state, checkpoints);
@@ -1024,6 +1053,25 @@ class Ensemble:
         check(lib().vsom_ensemble_batch_epoch(self._h, self._per_member(sigma, C.c_double, float), int(bool(is_first)),
                                               _f(mse)))
         return mse
+
+    def batch_schedule(self, sigmas, reset_bmu=True):
+        """a whole batch schedule on every member in one call (vsom_ensemble_batch_schedule).  sigmas: one sequence of
+        values that every member runs, or one sequence per member (their lengths may differ, 0 included).  Returns each
+        member's per-epoch MSE [list of float32 arrays]."""
+        n = len(self.members)
+        if _is_nested(sigmas):
+            per = [_schedule(v) for v in sigmas]
+            if len(per) != n:
+                raise ValueError(f"{len(per)} schedules for {n} members")
+        else:
+            per = [_schedule(sigmas)] * n
+        mses = [np.zeros(sg.size, np.float32) for sg in per]
+        dp = C.POINTER(C.c_double)
+        sig = (dp * max(n, 1))(*[sg.ctypes.data_as(dp) for sg in per])
+        out = (C.POINTER(C.c_float) * max(n, 1))(*[_f(m) for m in mses])
+        cnt = (C.c_size_t * max(n, 1))(*[sg.size for sg in per])
+        check(lib().vsom_ensemble_batch_schedule(self._h, sig, cnt, int(bool(reset_bmu)), out))
+        return mses
 
     def upload_chunks(self, rows):
         """every member's chunk in one call (vsom_ensemble_upload_chunks, wait = 1): `rows` is a list of one 2-D float32

@@ -47,6 +47,9 @@ struct vsom_ensemble {
     PinnedBuf<float> sc_dist;
     // U-matrices of the launched members, stored by the kernel (pinned host memory, grow-only)
     PinnedBuf<double> um_out;
+    // schedules: every launched member's tables (shared where shape and sigma agree) and per-epoch table offsets
+    PinnedBuf<unsigned char> sch_host;
+    DevBuf<unsigned char> sch_dev;
 };
 
 static int ens_fail(size_t k, const char *what)
@@ -330,6 +333,128 @@ int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_firs
     for (size_t k = 0; k < n; ++k)
         if (e->grp[k] >= 0 && mse_out)
             mse_out[k] = *static_cast<volatile float *>(e->m[k]->mse.p);
+    return VSOM_OK;
+}
+
+// vsom_batch_schedule for every member.  The members on the fast path of that call go as rounds of
+// at most VSOM_SCHEDULE_MAX_EPOCHS epochs: per round one table copy and one launch per kind, each workgroup looping its own
+// count.  A call within the cap is one round and one wait; a further round waits for the one before it.
+int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma, const size_t *epochs, int reset_bmu,
+                                 float *const *mse_out)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    if (!epochs)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null epochs array");
+    const size_t n = e->m.size();
+    for (size_t k = 0; k < n; ++k) {
+        if (!epochs[k])
+            continue;                        // not touched
+        if (!sigma || !mse_out || !sigma[k] || !mse_out[k])
+            return ens_fail(k, "null sigma or mse_out with epochs > 0");
+        if (const char *why = vsom_schedule_refusal(e->m[k]))
+            return ens_fail(k, why);
+    }
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    for (size_t k = 0; k < n; ++k) {         // join_members, but a member without epochs is not touched
+        if (!epochs[k])
+            continue;
+        if (int rc = vsom_join_aux(e->m[k]))
+            return rc;
+        e->m[k]->rows_free_valid = false;
+    }
+    // who is launched
+    const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);
+    std::vector<int> kind(n, -1);
+    size_t longest = 0;
+    vsom_ctx *first_launched = nullptr;
+    for (size_t k = 0; k < n; ++k) {
+        vsom_ctx *c = e->m[k];
+        if (!epochs[k] || !vsom_tiny_schedule_applies(c, sigma[k], epochs[k], lds_cap))
+            continue;
+        kind[k] = c->transform;
+        longest = std::max(longest, epochs[k]);
+        if (!first_launched)
+            first_launched = c;
+    }
+    hipStream_t ls = nullptr;
+    int rc = VSOM_OK;
+    if (first_launched) {
+        for (size_t k = 0; k < n; ++k)
+            if (kind[k] >= 0)
+                VSOM_ALLOC_CHECK(vsom_grow(e->m[k]->sch_mse, epochs[k], e->m[k]->stream, VSOM_BUF_SYNC));
+        const size_t stride = vsom_tiny_sched_desc_bytes();
+        e->desc.resize(n * stride);
+        e->smem.assign(n, 0);
+        std::vector<size_t> tab_at(n, 0);    // the member's first offset word of the round
+        std::vector<unsigned> tab;
+        for (size_t e0 = 0; e0 < longest && !rc; e0 += VSOM_SCHEDULE_MAX_EPOCHS) {
+            // the round's tables: one per distinct (shape, sigma) over all launched members
+            VsomSchedTables tabs;
+            tab.clear();
+            for (size_t k = 0; k < n; ++k) {
+                if (kind[k] < 0 || epochs[k] <= e0)
+                    continue;
+                uint32_t lw, lh;
+                vsom_lut_dims(e->m[k], &lw, &lh);
+                tab_at[k] = tab.size();
+                const size_t cnt = std::min(epochs[k] - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS);
+                for (size_t ep = 0; ep < cnt; ++ep)
+                    tab.push_back((unsigned)tabs.add(lw, lh, sigma[k][e0 + ep]));
+            }
+            if (tabs.floats > 0xFFFFFFFFull) {
+                rc = vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble_batch_schedule: the tables of one round exceed 2^32 values");
+                break;
+            }
+            if (e0) {                        // the previous round has read the image and the device buffer
+                VSOM_HIP_CHECK(hipStreamSynchronize(first_launched->stream));
+                VSOM_HIP_CHECK(hipStreamSynchronize(ls));
+            }
+            // (no kernel of an earlier call or round is running now)
+            const size_t bytes = (tabs.floats + tab.size()) * sizeof(float);
+            VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(e->sch_host, bytes), vsom_member(e->sch_dev, bytes)}));
+            tabs.tabulate(reinterpret_cast<float *>(e->sch_host.p));
+            std::memcpy(e->sch_host.p + tabs.floats * sizeof(float), tab.data(), tab.size() * sizeof(unsigned));
+            // on a launched member's stream: the launch stream is that stream, or waits for an event recorded behind this copy
+            VSOM_HIP_CHECK(hipMemcpyAsync(e->sch_dev.p, e->sch_host.p, bytes, hipMemcpyHostToDevice, first_launched->stream));
+            const float *lut_dev = reinterpret_cast<const float *>(e->sch_dev.p);
+            const unsigned *tab_dev = reinterpret_cast<const unsigned *>(e->sch_dev.p + tabs.floats * sizeof(float));
+            e->grp.assign(n, -1);
+            for (size_t k = 0; k < n; ++k) {
+                if (kind[k] < 0)
+                    continue;
+                // (a member whose schedule has ended stays in the launches with no epochs: every round then has the
+                //  same launch stream, and the rounds stay ordered)
+                vsom_ctx *c = e->m[k];
+                const size_t cnt = epochs[k] > e0 ? std::min(epochs[k] - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS) : 0;
+                e->grp[k] = vsom_tiny_sched_fill(c, lut_dev, tab_dev + (cnt ? tab_at[k] : 0), c->sch_mse.p + (cnt ? e0 : 0), cnt,
+                                                 e0 == 0, reset_bmu, e->desc.data() + k * stride, &e->smem[k]);
+            }
+            hipStream_t rs = nullptr;
+            rc = launch_groups(
+                e, VSOM_TINY_GROUPS, stride, [](int) { return VSOM_OK; },
+                [&](int g, const void *d, unsigned cnt, size_t smem, hipStream_t s) {
+                    return vsom_tiny_sched_launch_many(g, d, cnt, smem, s);
+                },
+                &rs);
+            if (rs)
+                ls = rs;
+        }
+    }
+    // the other members through the sequence of single epochs, while the launches run
+    for (size_t k = 0; k < n && !rc; ++k)
+        if (kind[k] < 0 && epochs[k])
+            rc = vsom_schedule_loop(e->m[k], sigma[k], epochs[k], reset_bmu, mse_out[k]);
+    // (also on an error: what was enqueued completes before the call returns)
+    if (first_launched)
+        VSOM_HIP_CHECK(hipStreamSynchronize(first_launched->stream));
+    if (ls)
+        VSOM_HIP_CHECK(hipStreamSynchronize(ls));
+    if (rc)
+        return rc;
+    for (size_t k = 0; k < n; ++k)
+        if (kind[k] >= 0)
+            vsom_schedule_results(e->m[k], epochs[k], mse_out[k]);
     return VSOM_OK;
 }
 

@@ -16,7 +16,9 @@
 #include <stdint.h>
 #include <stddef.h>
 #include <algorithm>
+#include <map>
 #include <string>
+#include <tuple>
 #include <vector>
 
 #include "../../include/vsom_hip.h"
@@ -101,6 +103,11 @@ struct vsom_ctx {
     size_t next_dev_B = 0;
     bool next_dev_pending = false;
     PinnedBuf<float> mse;           // [1]  pinned HOST memory (device-visible): kernels store, vsom_get_mse reads after a stream wait
+    // vsom_batch_schedule (vsom_tiny.hip): the schedule's neighbourhood tables followed by each epoch's table offset --
+    // pinned image and device copy, one set -- and the per-epoch MSE words the kernel stores (pinned, as `mse`).  The
+    // call blocks, so nothing reads them between calls.
+    PinnedBuf<unsigned char> sch_host; DevBuf<unsigned char> sch_dev;
+    PinnedBuf<float> sch_mse;
     DevBuf<int> pair_i, pair_j;     // CLR pair tables [P]
 
     // BMU tile-search scratch
@@ -356,6 +363,29 @@ void vsom_onl_tiny_done(vsom_ctx *c, int lut_slot);
 size_t vsom_tiny_desc_bytes();       // (descriptors are packed at exactly this size: the kernels index args[blockIdx.x])
 int vsom_tiny_prepare(vsom_ctx *c, double sigma, int is_first, size_t lds_limit, void *desc, int *group, size_t *smem);
 int vsom_tiny_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
+
+// whole schedules in one launch (vsom_batch_schedule, vsom_ensemble_batch_schedule; vsom_tiny.hip)
+void vsom_lut_dims(const vsom_ctx *c, uint32_t *lw, uint32_t *lh);   // the shape of the context's neighbourhood table
+// the tables of a call: one per distinct (lut_w, lut_h, sigma), packed in the order of first use
+struct VsomSchedTables {
+    std::map<std::tuple<uint32_t, uint32_t, uint64_t>, size_t> at;   // (shape, sigma's bits) -> the table's first float
+    size_t floats = 0;
+    size_t add(uint32_t w, uint32_t h, double sigma);                // the table's first float
+    void tabulate(float *host) const;                                // every table, as ensure_lut fills one
+};
+const char *vsom_schedule_refusal(const vsom_ctx *c);                // why a schedule call refuses this context, or null
+// the fast path applies: the single epoch would take the one-launch kernel within lds_limit, and every sigma is finite
+bool vsom_tiny_schedule_applies(const vsom_ctx *c, const double *sigma, size_t epochs, size_t lds_limit);
+size_t vsom_tiny_sched_desc_bytes();
+// the descriptor of `epochs` epochs (first: they start the schedule) reading tables lut_dev + tab_dev[ep] and storing the
+// MSE of epoch ep to mse[ep]; returns the kernel instantiation (the transform), *smem = its LDS need
+int vsom_tiny_sched_fill(vsom_ctx *c, const float *lut_dev, const unsigned *tab_dev, float *mse, size_t epochs, int first,
+                         int reset_bmu, void *desc, size_t *smem);
+int vsom_tiny_sched_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
+// the schedule as the sequence of single epochs (contexts off the fast path)
+int vsom_schedule_loop(vsom_ctx *c, const double *sigma, size_t epochs, int reset_bmu, float *mse_out);
+// after the wait behind the launches: sch_mse[0 .. epochs) into mse_out, the last one into the word vsom_get_mse reads
+void vsom_schedule_results(vsom_ctx *c, size_t epochs, float *mse_out);
 
 // custom-transformation contexts (vsom_custom.hip): the entry points that accept one route here, the others refuse it
 #define VSOM_CUSTOM_REFUSE(ctx, what)                                  \

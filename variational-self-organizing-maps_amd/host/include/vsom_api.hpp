@@ -449,6 +449,11 @@ public:
     float trainBatchSomEpochMasked(DataSet &data, double currentSigma, bool isFirst);
     void trainBatchSomMasked(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
                              bool updateUMatrixAfterEpoch = false);
+    // [MI355X build] extension: trainBatchSom for a data set that is ONE chunk -- the chunk is uploaded once and the whole
+    // sigma schedule (the epochs before the first sigma < 1) runs as one vsom_batch_schedule call (include/vsom_hip.h).  The
+    // state, the metrics and the rows' lastBMU are trainBatchSom's bit for bit.  Throws std::invalid_argument before it
+    // trains when the first load does not read the whole stream.  One device only.
+    void trainBatchSomResident(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay);
     TrainingReturnValue trainSingle(const Eigen::VectorXf &v, const Eigen::VectorXf &valid,
                                     const Eigen::VectorXf &weights, const double eta, const double sigma,
                                     size_t &lastBMU, const WeigthDecayFunction weightDecayFunction);

@@ -1221,6 +1221,53 @@ void Som::trainBatchSomMasked(DataSet &data, size_t numberOfEpochs, double sigma
     }
 }
 
+// Som.cpp:716-754 for a one-chunk data set: the chunk stays on the device and one vsom_batch_schedule call runs every
+// epoch (reset_bmu: each epoch's walk starts from unit 0, as after the reference's per-epoch reload, DataSet.cpp:136-137)
+void Som::trainBatchSomResident(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay)
+{
+    requireDevicePath("trainBatchSomResident");
+    if (grp)
+        throw std::runtime_error("trainBatchSomResident: a multi-GPU Som has no resident schedule (vsom_batch_schedule "
+                                 "runs on one context)");
+    {
+        const std::lock_guard<std::mutex> lock(metricsMutex);   // (the reference resets without it: trainBatchSom)
+        metrics = Som::Metrics(numberOfEpochs);
+    }
+    std::vector<double> sigmas;
+    for (size_t i = 0; i < numberOfEpochs; ++i) {
+        const auto sigma = sigma0 * std::exp(-sigmaDecay * static_cast<double>(i));   // :727
+        if (sigma < 1.0)
+            break;   // :729-730
+        sigmas.push_back(sigma);
+    }
+    if (sigmas.empty())
+        return;
+    data.loadNextDataFromStream();
+    if (!data.hasReadWholeDataStream()) {
+        data.resetStreamLoadPosition();   // (a caller that falls back to trainBatchSom starts from a clean stream)
+        throw std::invalid_argument("trainBatchSomResident: the data set does not load as one chunk; use trainBatchSom");
+    }
+    const size_t B = data.size();
+    std::vector<float> mse(sigmas.size(), 0.f);
+    std::vector<uint64_t> lb(B);
+    check(vsom_upload_chunk(ctx, data.contiguous(), B), "vsom_upload_chunk");
+    check(vsom_batch_schedule(ctx, sigmas.data(), sigmas.size(), 1, mse.data()), "vsom_batch_schedule");
+    check(vsom_get_last_bmu(ctx, lb.data()), "vsom_get_last_bmu");
+    for (size_t s = 0; s < B; ++s)
+        data.getLastBMU(s) = (size_t)lb[s];
+    hostStale = true;
+    {
+        const std::lock_guard<std::mutex> lock(metricsMutex);
+        for (size_t i = 0; i < mse.size(); ++i) {
+            auto meanSquareError = float{0.0f};
+            meanSquareError += mse[i];
+            meanSquareError /= static_cast<float>(size_t{1});   // :743, one chunk
+            metrics.MeanSquaredError[i] = meanSquareError;
+        }
+    }
+    data.resetStreamLoadPosition();   // :749
+}
+
 // ---- online training ---------------------------------------------------------------------------
 static int decay_code(Som::WeigthDecayFunction f)
 {

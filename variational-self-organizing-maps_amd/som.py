@@ -193,6 +193,18 @@ class ArrayDataSet:
         return self.lastBMU
 
 
+def batch_sigma_schedule(numberOfEpochs, sigma0, sigmaDecay):
+    """The sigma of every epoch that trainBatchSom runs (Som.cpp:727-730): sigma0 * exp(-sigmaDecay * i) for
+    i = 0, 1, ..., ending before the first value below 1 (sigma = 1.0 exactly still trains)."""
+    out = []
+    for i in range(numberOfEpochs):
+        sigma = sigma0 * math.exp(-sigmaDecay * float(i))         # :727
+        if sigma < 1.0:                                           # :729-730
+            break
+        out.append(sigma)
+    return out
+
+
 class Metrics:
     def __init__(self, n=0):
         self.MeanSquaredError = [0.0] * n
@@ -595,6 +607,26 @@ class Som:
             data.resetStreamLoadPosition()
             if updateUMatrixAfterEpoch:
                 self.updateUMatrix(data.getWeights())             # :751-752 / :1183-1184
+
+    def trainBatchSomResident(self, data, numberOfEpochs, sigma0, sigmaDecay):
+        """extension: trainBatchSom for a data set that is ONE chunk, with the chunk uploaded once and the whole sigma
+        schedule run by one call (capi.Context.batch_schedule) -- the same map, metrics and lastBMU as trainBatchSom,
+        which reloads the chunk (lastBMU := 0) and calls the device once per epoch.  Raises ValueError before it trains
+        when the first load does not read the whole stream."""
+        self.metrics = Metrics(numberOfEpochs)                    # :719
+        sigmas = batch_sigma_schedule(numberOfEpochs, sigma0, sigmaDecay)
+        if not sigmas:
+            return
+        data.loadNextDataFromStream()
+        if not data.hasReadWholeDataStream():
+            data.resetStreamLoadPosition()      # (a caller that falls back to trainBatchSom starts from a clean stream)
+            raise ValueError("trainBatchSomResident needs a data set that loads as one chunk; use trainBatchSom")
+        self.ctx.upload_chunk(data.data)
+        mses = self.ctx.batch_schedule(sigmas, reset_bmu=True)
+        for i, mse in enumerate(mses):
+            self.metrics.MeanSquaredError[i] = np.float32(np.float32(np.float32(0.0) + mse) / np.float32(1))   # :743
+        data.lastBMU[...] = self.ctx.get_last_bmu()
+        data.resetStreamLoadPosition()
 
     # ---- online training (Som.cpp:885-947, 1135-1187) ---------------------------------------
     def trainSingle(self, v, valid, weights, eta, sigma, lastBMU, weightDecayFunction):
