@@ -93,6 +93,14 @@ typedef enum vsom_update_mode {
                                rounding differences beyond the tolerance.                                    */
 } vsom_update_mode;
 
+/* when a batch epoch writes sigmaMap (vsom_set_sigma_mode) */
+typedef enum vsom_sigma_mode {
+    VSOM_SIGMA_AUTO = 0,    /* default: an epoch leaves its sigmaMap pending when the two epochs before it ended without
+                               anybody reading theirs; a new context, and every context after a read, is eager again */
+    VSOM_SIGMA_EAGER = 1,   /* every epoch writes sigmaMap, as the reference does */
+    VSOM_SIGMA_LAZY = 2     /* every epoch that can leaves it pending (tests) */
+} vsom_sigma_mode;
+
 /* selectors for vsom_device_ptr / vsom_get_timing */
 typedef enum vsom_buffer {
     VSOM_BUF_MAP = 0,      /* float   [N][D]                                    */
@@ -161,6 +169,34 @@ int vsom_set_stream(vsom_ctx *ctx, void *hip_stream);
 int vsom_synchronize(vsom_ctx *ctx);
 int vsom_set_bmu_mode(vsom_ctx *ctx, int mode);
 int vsom_set_update_mode(vsom_ctx *ctx, int mode);
+/* [MI355X build; the reference computes sigmaMap in every epoch, Som.cpp:867-873, and reads it in none: the next epoch
+ * rebuilds every row from zero and the built-in Comparers ignore the dispersion]
+ * Pending sigmaMap.  A whole-map batch epoch (vsom_batch_epoch(_async), vsom_batch_phase2_async over [0, N)) of a Standard
+ * or Median context on the lane = node chain kernels may run the mean chains alone -- half the arithmetic -- and keep what
+ * the full kernel needs to produce that epoch's sigmaMap later.  The next whole-map epoch drops the record (it overwrites
+ * every row); every other entry point materialises it first, on the context's stream: the full chain kernel of that
+ * epoch, bit-identical to what the eager epoch would have written.  So results never depend on the mode; only where
+ * the time goes does.  The calls that leave it pending, and no others:
+ *   chunk staging     vsom_upload_chunk(_async), vsom_set_chunk_device, vsom_prefetch_chunk, vsom_prefetch_wait,
+ *                     vsom_stage_next_device, vsom_commit_chunk
+ *   batch epochs      vsom_batch_phase1_async, vsom_batch_finish_async, vsom_batch_phase2_async (a partial node range
+ *                     materialises), vsom_batch_epoch_async, vsom_batch_epoch
+ *   read-backs        vsom_get_mse, vsom_get_last_bmu, vsom_set_last_bmu, vsom_get_sqres, vsom_get_umatrix,
+ *                     vsom_get_shortlist_stats, vsom_get_online_search_stats, vsom_get_timing, vsom_sigma_stats
+ *   plumbing          vsom_synchronize, vsom_set_bmu_mode, vsom_set_update_mode, vsom_set_sigma_mode,
+ *                     vsom_set_column_compaction, vsom_set_row_dedupe, vsom_enable_timing(_of), vsom_depth, vsom_nodes,
+ *                     vsom_residual_len, vsom_chunk_size, vsom_pitch, vsom_chunk_pitch, vsom_small_map_chains,
+ *                     vsom_device_ptr of every buffer but VSOM_BUF_SIGMA
+ * (vsom_set_stream materialises.)  Partial node ranges, CLR, small maps (vsom_small_map_chains), group members, the masked
+ * and custom epochs are always eager, and so is a context from the moment it joins an ensemble -- also after that
+ * ensemble is destroyed.
+ * The environment variable VSOM_SIGMA_MODE (auto / eager / lazy) sets the initial mode at vsom_create; any other value
+ * makes vsom_create fail with VSOM_ERR_INVALID.
+ * vsom_sigma_flush enqueues the materialisation (a no-op when nothing is pending) and counts as a read.
+ * vsom_sigma_stats: out[0..3] = epochs deferred, records dropped, records materialised, 1 if one is pending now. */
+int vsom_set_sigma_mode(vsom_ctx *ctx, int mode);
+int vsom_sigma_flush(vsom_ctx *ctx);
+int vsom_sigma_stats(vsom_ctx *ctx, uint64_t *out /*[4]*/);
 /* [MI355X build; no counterpart in the reference, whose phase 2 walks every column: Som.cpp:840-875]
  * Exact retirement of the sample columns that are zero in every row of a chunk (csrc/vsom_compact.hip: their
  * chains stay 0 -- or NaN for a node whose first weight is 0/0 -- and they add nothing to the search's
@@ -682,7 +718,9 @@ int vsom_group_get_mse(vsom_group *g, float *mse_out);
 double vsom_neighbourhood_weight(size_t cx, size_t cy, size_t bx, size_t by, double sigma);
 
 /* ---- interop / measurement -------------------------------------------------------------*/
-/* raw device pointer of a context buffer (for RCCL / torch.distributed collectives) */
+/* raw device pointer of a context buffer (for RCCL / torch.distributed collectives).  VSOM_BUF_SIGMA materialises a
+ * pending sigmaMap, so the rows are current for work enqueued behind this call; a pointer KEPT across later whole-map
+ * epochs is current again only after vsom_sigma_flush (or any call that materialises). */
 void *vsom_device_ptr(vsom_ctx *ctx, int which);
 size_t vsom_chunk_size(const vsom_ctx *ctx);
 /* row pitch in floats of the MAP/SIGMA/S device buffers (>= D; CLR: [A | pad | B | pad]) and

@@ -22,6 +22,7 @@ CUSTOM_MAX_DEPTH = 5120     # VSOM_CUSTOM_MAX_DEPTH
 EXPONENTIAL, INVERSE_PROPORTIONAL, BATCHMAP = 0, 1, 2
 BMU_AUTO, BMU_EXACT, BMU_SHORTLIST = 0, 1, 2
 UPDATE_STRICT, UPDATE_FMA, UPDATE_FMA_SIGMA = 0, 1, 2
+SIGMA_AUTO, SIGMA_EAGER, SIGMA_LAZY = 0, 1, 2
 BUF_MAP, BUF_SIGMA, BUF_S, BUF_WEIGHT, BUF_HITS, BUF_LASTBMU, BUF_SQRES, BUF_CHUNK, BUF_UMATRIX = range(9)
 T_STAGE, T_BMU, T_FINISH, T_CW, T_UPDATE, T_ONLINE, T_SIGMA, T_COUNT = range(8)
 TIMER_NAMES = ["stage", "bmu", "finish", "cw", "update", "online", "sigma"]
@@ -52,6 +53,7 @@ SYMBOLS = [
     "vsom_umatrix", "vsom_get_umatrix", "vsom_ensemble_umatrix", "vsom_similarity_batch",
     "vsom_bmu_masked_batch", "vsom_evaluate_batch", "vsom_generate_batch", "vsom_decode_nodes",
     "vsom_batch_epoch_masked", "vsom_batch_schedule", "vsom_ensemble_batch_schedule",
+    "vsom_set_sigma_mode", "vsom_sigma_flush", "vsom_sigma_stats",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -153,6 +155,9 @@ def lib():
     L.vsom_synchronize.argtypes = [vp]
     L.vsom_set_bmu_mode.argtypes = [vp, C.c_int]
     L.vsom_set_update_mode.argtypes = [vp, C.c_int]
+    L.vsom_set_sigma_mode.argtypes = [vp, C.c_int]
+    L.vsom_sigma_flush.argtypes = [vp]
+    L.vsom_sigma_stats.argtypes = [vp, C.POINTER(C.c_uint64)]
     L.vsom_set_column_compaction.argtypes = [vp, C.c_long]
     L.vsom_set_row_dedupe.argtypes = [vp, C.c_double]
     L.vsom_get_shortlist_stats.argtypes = [vp, C.POINTER(C.c_uint32)]
@@ -367,6 +372,18 @@ class Context:
 
     def set_update_mode(self, mode):
         check(lib().vsom_set_update_mode(self._h, int(mode)))
+
+    def set_sigma_mode(self, mode):
+        """SIGMA_AUTO / SIGMA_EAGER / SIGMA_LAZY: when a whole-map batch epoch writes sigmaMap (vsom_set_sigma_mode)"""
+        check(lib().vsom_set_sigma_mode(self._h, int(mode)))
+
+    def sigma_flush(self):
+        check(lib().vsom_sigma_flush(self._h))
+
+    def sigma_stats(self):
+        out = (C.c_uint64 * 4)()
+        check(lib().vsom_sigma_stats(self._h, out))
+        return {"deferred": int(out[0]), "dropped": int(out[1]), "materialised": int(out[2]), "pending": bool(out[3])}
 
     def set_row_dedupe(self, min_work):
         """exact searches of at least min_work (sample, node, value) triples evaluate one representative per class of

@@ -25,6 +25,9 @@ Scalar loads return out of order, so every wait is lgkmcnt(0): at the top of eac
 wavefront waits for everything it issued one group earlier (x of this group, (c, w) of this group's two pairs),
 issues the next group's loads and computes 40-48 packed operations.
 
+Mean-only forms (MEAN below): the same text without the S instructions and the second store, for epochs whose sigmaMap is
+produced later by the full kernel (vsom_update.hip, "pending sigma"): 6 packed operations per sample and quad, 4 for a zero quad.
+
 XCD-aware grid: grid.x = 8 * column blocks, grid.y = ceil(node groups / 8) (gen_update_asm.py).
 
 Kernarg (UpdAsmArgs, 80 bytes): Xq, cw2, map, sbuf, Xq row pitch in bytes (16 * padded samples; zq rows are
@@ -70,8 +73,9 @@ def compute(o, mode, xs, cwb):
     """one sample: x in s[xs:xs+3], {c, w} in v[cwb:cwb+1] (Som.cpp:861-867, Transformation.cpp:12,50)"""
     cw = f"v[{cwb}:{cwb + 1}]"
     P = (0, 1)
-    if mode == "med":
-        # StandardMedianEstimator, 7 operations per pair (vsom_update.hip, VSOM_MED_STEP): the transposed chunk holds
+    if mode in MED:
+        # StandardMedianEstimator, 7 operations per pair -- medmean: the 5 of them that M needs -- (vsom_update.hip,
+        # VSOM_MED_STEP): the transposed chunk holds
         # x * 2^24 for a Median context (vsom_xq.hip), and t = fma(M, -2^24, x * 2^24) has exactly the sign of x - M
         # (the scaling is exact, the fused difference rounds once and never to zero; NaN stays NaN);
         # p = clamp(t * 2^127) = [t > 0], n = clamp(-t * 2^127) = [t < 0] (DX10_CLAMP off: NaN passes); the four
@@ -84,21 +88,29 @@ def compute(o, mode, xs, cwb):
             o.append(f"\tv_pk_mul_f32 {vp(V_U, p)}, {vp(V_D, p)}, {S_BIG} neg_lo:[1,0] neg_hi:[1,0] clamp")
         for p in P:   # M = M + c*p
             o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {cw}, {vp(V_T, p)}, {vp(V_M, p)} op_sel_hi:[0,1,1]")
-        for p in P:   # S = S + w*p
-            o.append(f"\tv_pk_fma_f32 {vp(V_S, p)}, {cw}, {vp(V_T, p)}, {vp(V_S, p)} op_sel:[1,0,0]")
+        if mode == "med":
+            for p in P:   # S = S + w*p
+                o.append(f"\tv_pk_fma_f32 {vp(V_S, p)}, {cw}, {vp(V_T, p)}, {vp(V_S, p)} op_sel:[1,0,0]")
         for p in P:   # M = M - c*n
             o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {cw}, {vp(V_U, p)}, {vp(V_M, p)} op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]")
-        for p in P:   # S = S + w*n
-            o.append(f"\tv_pk_fma_f32 {vp(V_S, p)}, {cw}, {vp(V_U, p)}, {vp(V_S, p)} op_sel:[1,0,0]")
+        if mode == "med":
+            for p in P:   # S = S + w*n
+                o.append(f"\tv_pk_fma_f32 {vp(V_S, p)}, {cw}, {vp(V_U, p)}, {vp(V_S, p)} op_sel:[1,0,0]")
         return
     for p in P:   # delta = x - M
         o.append(f"\tv_pk_add_f32 {vp(V_D, p)}, {sp(xs, p)}, {vp(V_M, p)} neg_lo:[0,1] neg_hi:[0,1]")
-    if mode == "fma":
+    if mode in ("fma", "meanfma"):
         for p in P:   # M = c*delta + M
             o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {cw}, {vp(V_D, p)}, {vp(V_M, p)} op_sel_hi:[0,1,1]")
     else:
         for p in P:   # t = c*delta
             o.append(f"\tv_pk_mul_f32 {vp(V_T, p)}, {cw}, {vp(V_D, p)} op_sel_hi:[0,1]")
+    if mode == "meanfma":
+        return
+    if mode == "mean":
+        for p in P:   # M = M + t                               (Som.cpp:864)
+            o.append(f"\tv_pk_add_f32 {vp(V_M, p)}, {vp(V_M, p)}, {vp(V_T, p)}")
+        return
     for p in P:       # u = w*delta
         o.append(f"\tv_pk_mul_f32 {vp(V_U, p)}, {cw}, {vp(V_D, p)} op_sel:[1,0]")
     if mode != "fma":
@@ -119,6 +131,16 @@ def compute_zero(o, mode, cwb):
     (gen_update_asm.py, compute_zero_x)"""
     cw = f"v[{cwb}:{cwb + 1}]"
     P = (0, 1)
+    if mode == "mean":
+        for p in P:   # t = c*M ; M = M - t
+            o.append(f"\tv_pk_mul_f32 {vp(V_T, p)}, {cw}, {vp(V_M, p)} op_sel_hi:[0,1]")
+        for p in P:
+            o.append(f"\tv_pk_add_f32 {vp(V_M, p)}, {vp(V_M, p)}, {vp(V_T, p)} neg_lo:[0,1] neg_hi:[0,1]")
+        return
+    if mode == "meanfma":
+        for p in P:   # M = (-c)*M + M
+            o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {cw}, {vp(V_M, p)}, {vp(V_M, p)} op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]")
+        return
     for p in P:       # u = w*M (M before the step)
         o.append(f"\tv_pk_mul_f32 {vp(V_U, p)}, {cw}, {vp(V_M, p)} op_sel:[1,0]")
     if mode == "std":
@@ -143,12 +165,17 @@ def compute_zero(o, mode, cwb):
             o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {cw}, {vp(V_M, p)}, {vp(V_M, p)} op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]")
 
 
+MED = ("med", "medmean")
+# the chains without their S half (a deferred sigmaMap, vsom_update.hip): M's own operation sequence -- "mean" is the M
+# chain of "std" and of "sfma", "meanfma" that of "fma", "medmean" that of "med" -- the same staging, loads, zero-quad
+# branch and barriers, and the sigma buffer never written
+MEAN = ("mean", "meanfma", "medmean")
 _lab = [0]
 
 
 def step(o, mode, xs, cwb, bit):
     """one sample, the zero form when bit `bit` of the block's mask word is set"""
-    if mode == "med" or os.environ.get("VSOM_GEN_NT_NOZ"):
+    if mode in MED or os.environ.get("VSOM_GEN_NT_NOZ"):
         return compute(o, mode, xs, cwb)
     _lab[0] += 1
     n = _lab[0]
@@ -197,7 +224,7 @@ def kernel(name, mode):
     E(f"\ts_cbranch_scc1 .L_end_{name}")
     E(f"\ts_cmp_ge_u32 {S_Q}, {S_NQ}")                         # a dead quad inside a live block: takes part in the
     E(f"\ts_cselect_b32 {S_DEAD}, 1, 0")                       # staging and the barriers, stores nothing
-    if mode == "med":
+    if mode in MED:
         E(f"\ts_mov_b32 s30, 0x7f000000")                         # 2^127
         E(f"\ts_mov_b32 s31, 0x7f000000")
         E(f"\tv_mov_b32_e32 v{V_K}, 0xcb800000")                  # -2^24
@@ -355,7 +382,7 @@ def kernel(name, mode):
     E(f"\ts_cbranch_execz .L_end_{name}")
     E(f"\tv_add_u32_e32 {VN}, {S_N0}, {VN}")                    # global node index
     E(f"\ts_lshl_b32 {S_TMP}, {S_Q}, 4")                       # quad * 16 B
-    for base, tag in ((S_MAP, V_M), (S_SBUF, V_S)):
+    for base, tag in ((S_MAP, V_M), (S_SBUF, V_S))[:1 if mode in MEAN else 2]:   # the mean-only kernels store M alone
         E(f"\ts_add_u32 {S_TMP2}, s{base[0]}, {S_TMP}")
         E(f"\ts_addc_u32 s34, s{base[1]}, 0")
         E(f"\tv_mov_b32_e32 v{V_A}, {S_TMP2}")
@@ -369,7 +396,7 @@ def kernel(name, mode):
     return "\n".join(o)
 
 
-MODES = ("std", "fma", "sfma", "med")
+MODES = ("std", "fma", "sfma", "med", "mean", "meanfma", "medmean")
 
 
 def emit():
@@ -377,5 +404,5 @@ def emit():
     out = []
     for m in MODES:
         name = f"vsom_update_{m}_nt4_gfx950"
-        out.append((name, kernel(name, m), NVGPR, 80, LDS_BYTES, 0 if m == "med" else 1, WG))
+        out.append((name, kernel(name, m), NVGPR, 80, LDS_BYTES, 0 if m in MED else 1, WG))
     return out

@@ -1013,11 +1013,19 @@ int launch_finish(vsom_ctx *c)
     return VSOM_OK;
 }
 
-int vsom_join_aux(vsom_ctx *c)
+int vsom_join_aux_keep(vsom_ctx *c)
 {
     if (c->aux_pending) {
         VSOM_HIP_CHECK(hipStreamWaitEvent(c->stream, c->ev_join, 0));
         c->aux_pending = false;
     }
     return VSOM_OK;
+}
+
+// the default of every entry point: whatever follows may read sigmaMap (or overwrite what a pending one is made from)
+int vsom_join_aux(vsom_ctx *c)
+{
+    if (int rc = vsom_join_aux_keep(c))
+        return rc;
+    return vsom_sigma_flush_pending(c);
 }

@@ -52,6 +52,21 @@ static inline uint32_t roundup(uint32_t v, uint32_t m) { return (v + m - 1) / m 
             return _rc;                                                \
         (ctx)->rows_free_valid = false;   /* whatever follows may read the staged rows again */ \
     } while (0)
+// The same for the entry points that provably never read sigmaMap and overwrite nothing a pending one is made from (chunk
+// staging, the batch phases, the MSE and lastBMU read-backs, timing, statistics, synchronisation): a pending sigmaMap stays
+// pending (vsom_internal.hpp, vsom_ctx::sg).  CHECK_CTX is the default and materialises it -- an entry point missing
+// here costs time, one wrongly listed here would cost correctness.
+#define CHECK_CTX_KEEP(ctx)                                            \
+    do {                                                               \
+        if (!(ctx))                                                    \
+            return vsom_fail(VSOM_ERR_INVALID, "null context");        \
+        hipError_t _e = hipSetDevice((ctx)->device);                   \
+        if (_e != hipSuccess)                                          \
+            return vsom_fail(VSOM_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_e)); \
+        if (int _rc = vsom_join_aux_keep(ctx))                         \
+            return _rc;                                                \
+        (ctx)->rows_free_valid = false;                                \
+    } while (0)
 // Entry points that READ the staged rows (Xs / XP / YP, the gathered rows, the int8 images): once the NEXT chunk has been
 // staged ahead (vsom_prefetch_chunk / vsom_stage_next_device beside a running epoch) those buffers hold the next chunk's
 // rows while B, lastBMU and the compaction record still describe the current one -- a search would silently mix the two.
@@ -62,7 +77,8 @@ static inline uint32_t roundup(uint32_t v, uint32_t m) { return (v + m - 1) / m 
             return vsom_fail(VSOM_ERR_INVALID,                         \
                              "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first"); \
     } while (0)
-// phase 2 runs beside the side stream's work and joins it at its end
+// phase 2 runs beside the side stream's work and joins it at its end (a pending sigmaMap is its own business); the
+// copy-stream calls touch neither
 #define CHECK_CTX_NOJOIN(ctx)                                          \
     do {                                                               \
         if (!(ctx))                                                    \
@@ -107,7 +123,7 @@ int vsom_prefetch_rows(vsom_ctx *c, const float *x_host, size_t B, size_t r0, si
 // first half of vsom_commit_chunk: the compute stream waits for the copy; *raw = the B x J rows
 int vsom_commit_begin(vsom_ctx *c, float **raw, size_t *B)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     if (c->ready_slot < 0)
         return vsom_fail(VSOM_ERR_INVALID, "no prefetched chunk to commit");
     const int k = c->ready_slot;
@@ -120,7 +136,7 @@ int vsom_commit_begin(vsom_ctx *c, float **raw, size_t *B)
 // second half: stage the rows (lastBMU := 0) and mark the slot reusable once staging has read it
 int vsom_commit_end(vsom_ctx *c)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     if (c->ready_slot < 0)
         return vsom_fail(VSOM_ERR_INVALID, "no prefetched chunk to commit");
     const int k = c->ready_slot;
@@ -238,6 +254,16 @@ int vsom_create(vsom_ctx **out, int device, uint32_t width, uint32_t height, uin
         return vsom_fail(VSOM_ERR_INVALID, "CombinatorialLinearRegression needs in_len >= 2");
     if ((uint64_t)width * height > 0x7FFFFFFFull)
         return vsom_fail(VSOM_ERR_INVALID, "map too large");
+    int sigma_mode = VSOM_SIGMA_AUTO;
+    if (const char *e = std::getenv("VSOM_SIGMA_MODE")) {  // initial vsom_set_sigma_mode: auto / eager / lazy, nothing else
+        const std::string v(e);
+        if (v == "eager")
+            sigma_mode = VSOM_SIGMA_EAGER;
+        else if (v == "lazy")
+            sigma_mode = VSOM_SIGMA_LAZY;
+        else if (v != "auto")
+            return vsom_fail(VSOM_ERR_INVALID, "VSOM_SIGMA_MODE is '" + v + "': auto, eager or lazy");
+    }
     int ndev = 0;
     hipError_t e = hipGetDeviceCount(&ndev);
     if (e != hipSuccess || ndev <= 0)
@@ -273,6 +299,7 @@ int vsom_create(vsom_ctx **out, int device, uint32_t width, uint32_t height, uin
         c->cc_min_rows = std::atol(e);
     if (const char *e = std::getenv("VSOM_NO_DEDUPE"))
         c->dedupe = !(e[0] == '1');     // A/B measurements of the duplicate-row pass of the exact search
+    c->sigma_mode = sigma_mode;
     if (const char *e = std::getenv("VSOM_NO_CHAIN"))
         c->use_chain = !(e[0] == '1');  // debugging aid: lane = node update kernel on small maps too
 
@@ -366,7 +393,7 @@ int vsom_set_stream(vsom_ctx *c, void *hip_stream)
 
 int vsom_synchronize(vsom_ctx *c)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     return VSOM_OK;
 }
@@ -381,7 +408,7 @@ int vsom_set_bmu_mode(vsom_ctx *c, int mode)
 
 int vsom_get_shortlist_stats(vsom_ctx *c, uint32_t *out)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     VSOM_CUSTOM_REFUSE(c, "vsom_get_shortlist_stats");
     if (!out)
         return vsom_fail(VSOM_ERR_INVALID, "null output");
@@ -407,6 +434,30 @@ int vsom_set_row_dedupe(vsom_ctx *c, double min_work)
         return vsom_fail(VSOM_ERR_INVALID, "null context");
     VSOM_CUSTOM_REFUSE(c, "row dedupe");
     c->dd_min_work = min_work;
+    return VSOM_OK;
+}
+
+int vsom_set_sigma_mode(vsom_ctx *c, int mode)
+{
+    if (!c || mode < VSOM_SIGMA_AUTO || mode > VSOM_SIGMA_LAZY)
+        return vsom_fail(VSOM_ERR_INVALID, "bad sigma mode");
+    c->sigma_mode = mode;        // (a sigmaMap already pending stays pending: every reader materialises it in any mode)
+    return VSOM_OK;
+}
+
+int vsom_sigma_flush(vsom_ctx *c)
+{
+    CHECK_CTX(c);                // (materialises)
+    return VSOM_OK;
+}
+
+int vsom_sigma_stats(vsom_ctx *c, uint64_t *out)
+{
+    if (!c || !out)
+        return vsom_fail(VSOM_ERR_INVALID, "null context or output");
+    for (int i = 0; i < 3; ++i)
+        out[i] = c->sg_stats[i];
+    out[3] = c->sg.on ? 1 : 0;
     return VSOM_OK;
 }
 
@@ -531,7 +582,7 @@ int vsom_get_state(vsom_ctx *c, float *map, float *sigma, float *S, float *weigh
 
 int vsom_set_chunk_device(vsom_ctx *c, const float *x_dev, size_t B)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     VSOM_CUSTOM_REFUSE(c, "vsom_set_chunk_device");
     if (B > 0 && !x_dev)
         return vsom_fail(VSOM_ERR_INVALID, "x_dev is null");
@@ -547,7 +598,7 @@ int vsom_set_chunk_device(vsom_ctx *c, const float *x_dev, size_t B)
 
 static int upload_chunk_impl(vsom_ctx *c, const float *x_host, size_t B, bool wait)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     if (c->cu)
         return vsom_custom_upload(c, x_host, B, wait);
     if (B > 0 && !x_host)
@@ -604,7 +655,7 @@ static int stage_ahead_if_possible(vsom_ctx *c, const float *x_dev, size_t B)
 int vsom_prefetch_chunk(vsom_ctx *c, const float *x_host, size_t B)
 {
     if (c && c->cu) {
-        CHECK_CTX(c);
+        CHECK_CTX_KEEP(c);
         return vsom_custom_prefetch(c, x_host, B);
     }
     int rc = vsom_prefetch_rows(c, x_host, B, 0, B);
@@ -648,11 +699,11 @@ int vsom_prefetch_wait(vsom_ctx *c)
 int vsom_commit_chunk(vsom_ctx *c)
 {
     if (c && c->cu) {
-        CHECK_CTX(c);
+        CHECK_CTX_KEEP(c);
         return vsom_custom_commit(c);
     }
     if (c && c->next_dev_pending) {       // vsom_stage_next_device: adopt what was staged ahead, or stage it now
-        CHECK_CTX(c);
+        CHECK_CTX_KEEP(c);
         c->next_dev_pending = false;
         if (c->ahead_valid)
             return vsom_adopt_ahead(c);
@@ -675,7 +726,7 @@ __global__ void copy_u64_kernel(u64 *dst, const u64 *src, int n)
 
 int vsom_get_last_bmu(vsom_ctx *c, uint64_t *out_host)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     if (c->B && !out_host)
         return vsom_fail(VSOM_ERR_INVALID, "null output");
     // short chunks (the reference's own scenarios train 20 rows an epoch): one small kernel stores the indices into pinned
@@ -697,7 +748,7 @@ int vsom_get_last_bmu(vsom_ctx *c, uint64_t *out_host)
 
 int vsom_set_last_bmu(vsom_ctx *c, const uint64_t *in_host)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     if (c->B && !in_host)
         return vsom_fail(VSOM_ERR_INVALID, "null input");
     for (size_t i = 0; i < c->B; ++i)
@@ -711,7 +762,7 @@ int vsom_set_last_bmu(vsom_ctx *c, const uint64_t *in_host)
 
 int vsom_get_sqres(vsom_ctx *c, float *out_host)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     if (c->B && !out_host)
         return vsom_fail(VSOM_ERR_INVALID, "null output");
     if (c->B)
@@ -1002,7 +1053,7 @@ int vsom_get_umatrix(vsom_ctx *c, double *u_out_host)
 
 int vsom_batch_phase1_async(vsom_ctx *c, size_t s0, size_t s1, int is_first)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     VSOM_CUSTOM_REFUSE(c, "vsom_batch_phase1_async");
     CHECK_ROWS(c);
     if (s0 > s1 || s1 > c->B)
@@ -1012,7 +1063,7 @@ int vsom_batch_phase1_async(vsom_ctx *c, size_t s0, size_t s1, int is_first)
 
 int vsom_batch_finish_async(vsom_ctx *c)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     VSOM_CUSTOM_REFUSE(c, "vsom_batch_finish_async");
     if (!c->chunk_loaded)   // an EMPTY chunk is legal: the reference's epoch then zeroes the map
         return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
@@ -1031,30 +1082,32 @@ int vsom_batch_phase2_async(vsom_ctx *c, double sigma, size_t n0, size_t n1)
         return vsom_fail(VSOM_ERR_INVALID, "node range out of bounds");
     if (!c->chunk_loaded)   // an EMPTY chunk is legal: the reference's epoch then zeroes the map
         return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
-    return launch_phase2(c, sigma, n0, n1);
+    return launch_phase2(c, sigma, n0, n1, true);
 }
 
 int vsom_batch_epoch_async(vsom_ctx *c, double sigma, int is_first)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     if (c->cu)
         return vsom_custom_batch_epoch_async(c, sigma, is_first);
     CHECK_ROWS(c);
     if (!c->chunk_loaded)   // an EMPTY chunk is legal: the reference's epoch then zeroes the map
         return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
-    if (vsom_tiny_applies(c))
+    if (vsom_tiny_applies(c)) {
+        vsom_sigma_drop(c);                             // (every sigmaMap row is rewritten)
         return launch_tiny_epoch(c, sigma, is_first);   // tiny map: the whole epoch in one launch
+    }
     int rc = vsom_batch_phase1_async(c, 0, c->B, is_first);
     if (rc)
         return rc;
     if ((rc = launch_finish(c)))
         return rc;
-    return launch_phase2(c, sigma, 0, c->N);
+    return launch_phase2(c, sigma, 0, c->N, true);
 }
 
 int vsom_get_mse(vsom_ctx *c, float *mse_out)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     if (!mse_out)
         return vsom_fail(VSOM_ERR_INVALID, "null output");
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
@@ -1099,7 +1152,12 @@ void *vsom_device_ptr(vsom_ctx *c, int which)
         return nullptr;
     switch (which) {
     case VSOM_BUF_MAP: return c->map.p;
-    case VSOM_BUF_SIGMA: return c->sigma.p;
+    case VSOM_BUF_SIGMA:
+        // the caller is about to read it: current as of this call; a pointer kept across later epochs is current again
+        // after vsom_sigma_flush (include/vsom_hip.h)
+        if (hipSetDevice(c->device) != hipSuccess || vsom_sigma_flush_pending(c) != VSOM_OK)
+            return nullptr;
+        return c->sigma.p;
     case VSOM_BUF_S: return c->S.p;
     case VSOM_BUF_WEIGHT: return c->weight.p;
     case VSOM_BUF_HITS: return c->hits.p;
@@ -1132,7 +1190,7 @@ int vsom_enable_timing_of(vsom_ctx *c, uint32_t group_mask)
 
 int vsom_get_timing(vsom_ctx *c, float *ms_out, uint32_t *count_out, int reset)
 {
-    CHECK_CTX(c);
+    CHECK_CTX_KEEP(c);
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     for (auto &e : c->ev_live) {
         float ms = 0.f;

@@ -93,7 +93,9 @@ __global__ __launch_bounds__(256) void cc_gather_rows_kernel(const float *__rest
 
 // model rows back in the reference's layout: live column d <- compacted column inv[d] (map: the chain's M;
 // sigmaMap: sqrt(S / W), Som.cpp:873), dead column <- +0, or NaN when the node's first coefficient is 0/0
-// (header); the padding columns of the rows are put to zero as sigma_finalize_kernel does
+// (header); the padding columns of the rows are put to zero as sigma_finalize_kernel does.  WHAT: 3 = both, 1 = the map rows
+// only (an epoch whose sigmaMap stays pending, vsom_update.hip), 2 = the sigmaMap rows only (its materialisation)
+template <int WHAT>
 __global__ __launch_bounds__(256) void cc_expand_kernel(const float *__restrict__ um, const float *__restrict__ us, int ldc,
                                                         const int *__restrict__ inv, float *__restrict__ map,
                                                         float *__restrict__ sigma, int pitch, int D, int n0, int nloc,
@@ -113,15 +115,19 @@ __global__ __launch_bounds__(256) void cc_expand_kernel(const float *__restrict_
         if (d < D) {
             const int k = inv[d];
             if (k >= 0) {
-                m = pm[k];
-                s = sqrtf(ps[k] / Wf);
+                if (WHAT & 1)
+                    m = pm[k];
+                if (WHAT & 2)
+                    s = sqrtf(ps[k] / Wf);
             } else {
                 m = dead_m;
                 s = dead_s;
             }
         }
-        map[node * pitch + d] = m;
-        sigma[node * pitch + d] = s;
+        if (WHAT & 1)
+            map[node * pitch + d] = m;
+        if (WHAT & 2)
+            sigma[node * pitch + d] = s;
     }
 }
 
@@ -226,10 +232,11 @@ int vsom_cc_ensure_update_scratch(vsom_ctx *c)
     return VSOM_OK;
 }
 
-int vsom_cc_expand(vsom_ctx *c, size_t n0, size_t nloc)
+int vsom_cc_expand(vsom_ctx *c, size_t n0, size_t nloc, int what, const int *inv)
 {
-    hipLaunchKernelGGL(cc_expand_kernel, dim3((unsigned)nloc), dim3(256), 0, c->stream, c->Uc_map.p, c->Uc_S.p, (int)c->cpitch,
-                       c->cc_inv.p, c->map.p, c->sigma.p, (int)c->pitch, (int)c->D, (int)n0, (int)nloc, c->weight.p,
+    const auto fn = what == 1 ? cc_expand_kernel<1> : (what == 2 ? cc_expand_kernel<2> : cc_expand_kernel<3>);
+    hipLaunchKernelGGL(fn, dim3((unsigned)nloc), dim3(256), 0, c->stream, c->Uc_map.p, c->Uc_S.p, (int)c->cpitch,
+                       inv ? inv : c->cc_inv.p, c->map.p, c->sigma.p, (int)c->pitch, (int)c->D, (int)n0, (int)nloc, c->weight.p,
                        reinterpret_cast<const float4 *>(c->cw.p));
     VSOM_HIP_CHECK(hipGetLastError());
     return VSOM_OK;

@@ -85,10 +85,18 @@ int vsom_ensemble_create(vsom_ensemble **out, vsom_ctx *const *members, size_t c
     VSOM_HIP_CHECK(hipSetDevice(members[0]->device));
     int lds = 0;
     VSOM_HIP_CHECK(hipDeviceGetAttribute(&lds, hipDeviceAttributeMaxSharedMemoryPerBlock, members[0]->device));
+    for (size_t k = 0; k < count; ++k)
+        if (int rc = vsom_sigma_flush_pending(members[k]))
+            return rc;
     vsom_ensemble *e = new vsom_ensemble;
     e->device = members[0]->device;
     e->m.assign(members, members + count);
     e->lds_limit = (size_t)lds;
+    // The ensemble's calls read the members' sigmaMap rows directly, so from here on (nothing above is left to fail) a
+    // member's epochs keep sigmaMap current.  The flag outlives the ensemble: vsom_ensemble_destroy may run after its
+    // members are gone and cannot touch them (include/vsom_hip.h, vsom_set_sigma_mode, says so).
+    for (vsom_ctx *c : e->m)
+        c->sigma_shared = true;
     *out = e;
     return VSOM_OK;
 }

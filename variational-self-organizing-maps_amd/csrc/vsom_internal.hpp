@@ -151,6 +151,7 @@ struct vsom_ctx {
 
     // hand-scheduled update kernel (code object loaded with hipModuleLoadData)
     void *upd_module = nullptr, *upd_clr8 = nullptr, *upd_nt[4] = {nullptr, nullptr, nullptr, nullptr};   // nt: std, fma, sfma, med
+    void *upd_nt_mean[4] = {nullptr, nullptr, nullptr, nullptr};   // their M-only forms: mean, meanfma, mean, medmean
     int update_mode = VSOM_UPDATE_STRICT;
     bool use_chain = true;
     bool use_tiny = true;           // one-launch epoch for tiny maps (VSOM_NO_TINY=1 disables, debugging)
@@ -174,6 +175,26 @@ struct vsom_ctx {
     DevBuf<unsigned> zq;            // [quads][bpad / 32] all-zero (sample, quad) bits
     bool xq_valid = false;
     uint32_t xq_bpad = 0, xq_quads = 0;
+
+    // Deferred sigmaMap (vsom_update.hip, "pending sigma"): a full-range phase 2 of the lane = node Standard / Median path
+    // may run the M-only chain kernel and leave sigmaMap unwritten; `sg` then records what the full kernel needs to
+    // produce that epoch's sigmaMap later.  Its inputs are the context's own buffers -- Xq / zq, cw, weight and the
+    // compaction's scratch rows are written by launch_phase2 alone, which drops or materialises the record first -- except
+    // the live-column record, which the staging of the next chunk overwrites: sg_inv / sg_meta are owned copies.
+    // Every entry point materialises it (vsom_sigma_flush_pending via vsom_join_aux) but the listed ones that never
+    // read sigmaMap (vsom_capi.hip, CHECK_CTX_KEEP); the next full-range epoch, which overwrites every row, drops it.
+    struct PendingSigma {
+        bool on = false;
+        size_t B = 0, ldn = 0;
+        uint32_t bpad = 0;
+        bool compact = false;
+        int kernel = 0;             // index into upd_nt: the update mode and transformation in force at that epoch
+    } sg;
+    DevBuf<int> sg_inv; DevBuf<unsigned> sg_meta;
+    int sigma_mode = VSOM_SIGMA_AUTO;
+    unsigned sigma_unread = 0;      // full-range epochs since the last entry point that may have read sigmaMap (AUTO)
+    bool sigma_shared = false;      // a group or an ensemble reads this context's buffers directly: never deferred
+    uint64_t sg_stats[3] = {0, 0, 0};   // epochs deferred, dropped, materialised
 
     // online path scratch
     DevBuf<float> v_dev;            // one sample, padded
@@ -271,7 +292,13 @@ int launch_bmu_local(vsom_ctx *c, size_t s0, size_t s1);          // findLocalBm
 int launch_pair_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *rows_dev, size_t count,
                      float *out_dev);
 int launch_finish(vsom_ctx *c);
-int vsom_join_aux(vsom_ctx *c);      // make ctx->stream wait for the side stream's pending work
+// make ctx->stream wait for the side stream's pending work, and materialise a pending sigmaMap: what every entry point
+// does first, unless it is one of those that never read sigmaMap (vsom_join_aux_keep)
+int vsom_join_aux(vsom_ctx *c);
+int vsom_join_aux_keep(vsom_ctx *c); // the join alone
+// pending sigmaMap (vsom_update.hip): enqueue its materialisation, if there is one; the caller may have read sigmaMap
+int vsom_sigma_flush_pending(vsom_ctx *c);
+void vsom_sigma_drop(vsom_ctx *c);   // the next full-range epoch overwrites every row: nothing runs
 int launch_bmu_restricted(vsom_ctx *c, u64 min_hits);
 int launch_row_dist(vsom_ctx *c, size_t row, float *out_dev);
 // vsom_bmd.hip: findRestrictedBmd + draws for chunk rows [r0,r1) (arguments checked by vsom_bmd_batch); synchronises
@@ -332,7 +359,8 @@ struct VsomUmDesc {
 };
 size_t vsom_umatrix_many_smem(const vsom_ctx *c);
 int vsom_umatrix_launch_many(int clr, const VsomUmDesc *desc_dev, unsigned count, size_t smem, hipStream_t s);
-int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1);
+// may_defer: the caller is a plain batch epoch (vsom_batch_phase2_async / _epoch_async), whose sigmaMap may stay pending
+int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1, bool may_defer = false);
 int ensure_lut(vsom_ctx *c, double sigma);
 // column compaction (vsom_compact.hip)
 bool vsom_cc_applies(const vsom_ctx *c);
@@ -342,7 +370,8 @@ int vsom_cc_begin(vsom_ctx *c, size_t B, bool *on);
 int vsom_cc_stage(vsom_ctx *c, size_t B, hipStream_t stream, int *idx, int *inv, unsigned *meta, bool *xi_out);
 int vsom_cc_gather_map(vsom_ctx *c);
 int vsom_cc_ensure_update_scratch(vsom_ctx *c);
-int vsom_cc_expand(vsom_ctx *c, size_t n0, size_t nloc);
+// what: 3 = map and sigmaMap from the scratch rows, 1 = map only, 2 = sigmaMap only (inv: the live-column record to use)
+int vsom_cc_expand(vsom_ctx *c, size_t n0, size_t nloc, int what = 3, const int *inv = nullptr);
 // vsom_sl_i8.hip: rows onto the live columns (+ int8 images)
 int launch_sl_gather_quant(vsom_ctx *c, size_t B, hipStream_t stream, const int *idx, bool *xi_out);
 int vsom_xq_ensure(vsom_ctx *c);                                 // vsom_xq.hip

@@ -17,6 +17,8 @@
 //                    one column quad per wavefront, x from scalar loads of the transposed chunk (vsom_xq.hip)
 //                    as SGPR operands of v_pk_*, (c,w) staged once per workgroup through LDS, the 5-operation
 //                    step for all-zero quads.
+//                  - vsom_update_{mean,meanfma,medmean}_nt4_gfx950: the same kernels without the S chain, for full-range
+//                    epochs whose sigmaMap stays pending ("pending sigma" below, vsom_internal.hpp)
 //                  - vsom_update_clr_rp8_gfx950 (gen_update_asm.py): CLR, lane = node, 8 parameter pairs per lane.
 //                  - update_chain3_kernel (HIP, below): maps too small to fill the chip with lane = node
 //                    (C4: 64x64x32): one lane per (node, dim pair) chain, operands staged through LDS.
@@ -502,6 +504,12 @@ int vsom_load_asm_module(vsom_ctx *c)
         VSOM_HIP_CHECK(hipModuleGetFunction(&f, mod, n.c_str()));
         c->upd_nt[i] = f;
     }
+    static const char *const mean_names[4] = {"mean", "meanfma", "mean", "medmean"};   // (sfma's M chain is the strict one)
+    for (int i = 0; i < 4; ++i) {
+        const std::string n = std::string("vsom_update_") + mean_names[i] + "_nt4_gfx950";
+        VSOM_HIP_CHECK(hipModuleGetFunction(&f, mod, n.c_str()));
+        c->upd_nt_mean[i] = f;
+    }
     c->upd_module = mod;
     return VSOM_OK;
 }
@@ -591,10 +599,115 @@ static bool vsom_use_chain(const vsom_ctx *c, size_t nloc)
 
 extern "C" int vsom_small_map_chains(const vsom_ctx *c, size_t nodes) { return c && vsom_use_chain(c, nodes) ? 1 : 0; }
 
-int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
+// ---- pending sigma (vsom_internal.hpp, vsom_ctx::sg) ------------------------------------------------------------
+// one launch of a lane = node Standard / Median chain kernel over the nodes [n0, n0 + nloc), from the operands of a chunk of
+// B rows: the one place that fills the kernarg, for the eager epoch, the mean-only epoch and the materialisation
+static int launch_nt_chains(vsom_ctx *c, void *fn, size_t n0, size_t nloc, size_t B, size_t ldn, uint32_t bpad, bool compact,
+                            const unsigned *meta)
+{
+    const unsigned gx = (unsigned)((nloc + 63) / 64);
+    const unsigned cols = compact ? c->cpitch : c->pitch;
+    const unsigned quads = compact ? c->cpitch / 4 : (c->D + 3) / 4;
+    UpdAsmArgs a;
+    a.xs = c->Xq.p;
+    a.cw2 = c->cw.p;
+    a.map = compact ? c->Uc_map.p : c->map.p;
+    a.sbuf = compact ? c->Uc_S.p : c->sigma.p;
+    a.ldx_bytes = bpad * 16u;
+    a.ldn_bytes = (unsigned)(ldn * 16u);
+    a.B = (unsigned)B;
+    a.nloc = (unsigned)nloc;
+    a.nslices = quads;
+    a.pitch_bytes = cols * 4u;
+    a.n0 = (unsigned)n0;
+    a.ppitch_bytes = 0;
+    a.yp = compact ? (const void *)meta : nullptr;
+    a.zq = c->zq.p;
+    size_t sz = 80;
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+    VSOM_HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)fn, 8 * ((quads + 7) / 8), (gx + 7) / 8, 1, 512, 1, 1, 0, c->stream,
+                                         nullptr, extra));
+    return VSOM_OK;
+}
+
+// the owned copy of the live-column record: inv [ninv], meta [16]
+__global__ __launch_bounds__(256) void sg_keep_record_kernel(const int *__restrict__ inv, int ninv, const unsigned *__restrict__ meta,
+                                                             int *__restrict__ inv_out, unsigned *__restrict__ meta_out)
+{
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < ninv)
+        inv_out[i] = inv[i];
+    if (i < 16)
+        meta_out[i] = meta[i];
+}
+
+void vsom_sigma_drop(vsom_ctx *c)
+{
+    if (c->sg.on) {
+        c->sg.on = false;
+        ++c->sg_stats[1];
+    }
+}
+
+// The full chain kernel of the pending epoch from the operands that epoch left in place: its M goes where the M-only
+// kernel put the same values (the compaction's scratch rows, or the map rows themselves: no epoch has run since, and
+// every call that writes the map materialises first), its raw S becomes sigmaMap as in an eager epoch.
+static int sigma_materialise(vsom_ctx *c)
+{
+    const vsom_ctx::PendingSigma p = c->sg;
+    c->sg.on = false;
+    ++c->sg_stats[2];
+    int rc;
+    {
+        TimerScope ts(c, VSOM_T_UPDATE);
+        if ((rc = launch_nt_chains(c, c->upd_nt[p.kernel], 0, c->N, p.B, p.ldn, p.bpad, p.compact, c->sg_meta.p)))
+            return rc;
+    }
+    TimerScope ts(c, VSOM_T_SIGMA);
+    if (p.compact)
+        return vsom_cc_expand(c, 0, c->N, 2, c->sg_inv.p);
+    hipLaunchKernelGGL(sigma_finalize_kernel, dim3((unsigned)c->N), dim3(256), 0, c->stream, c->sigma.p, c->map.p, (int)c->pitch, 0,
+                       (int)((c->D + 3) / 4 * 4), (int)c->part_len, 0, (int)c->N, c->weight.p);
+    VSOM_HIP_CHECK(hipGetLastError());
+    return VSOM_OK;
+}
+
+int vsom_sigma_flush_pending(vsom_ctx *c)
+{
+    c->sigma_unread = 0;
+    return c->sg.on ? sigma_materialise(c) : VSOM_OK;
+}
+
+// does this full-range epoch leave its sigmaMap pending?  (dense rows of a ragged depth stay eager: their last quad runs
+// into the rows' padding, which sigma_finalize_kernel re-zeroes in map and sigmaMap at once)
+static bool sigma_defers(const vsom_ctx *c, bool compact)
+{
+    if (c->sigma_shared || c->in_group || c->sigma_mode == VSOM_SIGMA_EAGER)
+        return false;
+    if (!compact && c->D % 4 != 0)
+        return false;
+    return c->sigma_mode == VSOM_SIGMA_LAZY || c->sigma_unread >= 2;
+}
+
+int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1, bool may_defer)
 {
     if (n1 <= n0)
-        return vsom_join_aux(c);
+        return vsom_join_aux_keep(c);
+    const bool full = n0 == 0 && n1 == c->N;
+    // A partial range must find the other sigmaMap rows as an eager epoch would have left them (and is about to overwrite
+    // the record's operands): materialise.  A full range overwrites every row, so the pending one is never seen: the record
+    // is dropped -- at the last moment before this epoch overwrites its operands (the (c,w) array), behind what can fail
+    // without having touched anything (the table, the code object).  An epoch that fails later (an allocation) leaves map,
+    // sigmaMap and weightMap unspecified, as a failed epoch always did: the neighbourhood pass has rewritten weightMap.
+    if (c->sg.on && !full)
+        if (int prc = sigma_materialise(c))
+            return prc;
+    // a completed epoch counts as unread from its end on: AUTO looks at the epochs BEFORE the one it decides
+    auto done = [&]() {
+        if (may_defer && full && c->sigma_unread < 1000u)
+            ++c->sigma_unread;
+        return vsom_join_aux_keep(c);
+    };
     if (c->B == 0) {
         TimerScope ts(c, VSOM_T_UPDATE);
         const size_t nloc = n1 - n0, tot = nloc * c->pitch;
@@ -603,11 +716,15 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
         hipLaunchKernelGGL(zero_weight_kernel, dim3((unsigned)((nloc + 255) / 256)), dim3(256), 0, c->stream, c->weight.p,
                            (int)n0, (int)nloc);
         VSOM_HIP_CHECK(hipGetLastError());
-        return vsom_join_aux(c);
+        vsom_sigma_drop(c);
+        return done();
     }
     int rc = ensure_lut(c, sigma);
     if (rc)
         return rc;
+    if ((rc = vsom_load_asm_module(c)))
+        return rc;
+    vsom_sigma_drop(c);
     const size_t nloc = n1 - n0;
     const size_t ldn = (nloc + 63) / 64 * 64;
     // pair rows: ceil(B/2) + what the kernels' staging reads ahead (one block of 16 pair-rows) + slack
@@ -638,11 +755,10 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
         VSOM_HIP_CHECK(hipLaunchKernel(fn, dim3((unsigned)((nloc + nw - 1) / nw)), dim3(CWP_THREADS), args, smem, c->stream));
     }
     int sig_cols = 0;   // > 0: columns left as raw S by the kernel; < 0: the compaction's scratch rows hold M and raw S
+    bool deferred = false;
     {
         TimerScope ts(c, VSOM_T_UPDATE);
         const unsigned gx = (unsigned)((nloc + 63) / 64);
-        if ((rc = vsom_load_asm_module(c)))
-            return rc;
         if (c->transform == VSOM_CLR || vsom_use_chain(c, nloc))
             c->rows_free_valid = false;   // these chain kernels read the staged rows: no stage-ahead behind an earlier range's event
         if (c->transform == VSOM_CLR) {
@@ -719,38 +835,38 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
                 return rc;
             const bool fma = c->update_mode == VSOM_UPDATE_FMA, sfma = c->update_mode == VSOM_UPDATE_FMA_SIGMA;
             const bool med = c->transform == VSOM_MEDIAN;     // its FMAs are exact: one kernel for all modes
-            const unsigned cols = compact ? c->cpitch : c->pitch;
             const unsigned quads = compact ? c->cpitch / 4 : (c->D + 3) / 4;
-            UpdAsmArgs a;
-            a.xs = c->Xq.p;
-            a.cw2 = c->cw.p;
-            a.map = compact ? c->Uc_map.p : c->map.p;
-            a.sbuf = compact ? c->Uc_S.p : c->sigma.p;
-            a.ldx_bytes = c->xq_bpad * 16u;
-            a.ldn_bytes = (unsigned)(ldn * 16u);
-            a.B = (unsigned)c->B;
-            a.nloc = (unsigned)nloc;
-            a.nslices = quads;
-            a.pitch_bytes = cols * 4u;
-            a.n0 = (unsigned)n0;
-            a.ppitch_bytes = 0;
-            a.yp = compact ? (const void *)c->cc_meta.p : nullptr;
-            a.zq = c->zq.p;
-            size_t sz = 80;
-            void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-            void *fn = c->upd_nt[med ? 3 : (fma ? 1 : (sfma ? 2 : 0))];
-            VSOM_HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)fn, 8 * ((quads + 7) / 8), (gx + 7) / 8, 1, 512, 1, 1, 0,
-                                                 c->stream, nullptr, extra));
+            const int kernel = med ? 3 : (fma ? 1 : (sfma ? 2 : 0));
+            deferred = may_defer && full && sigma_defers(c, compact);
+            if (deferred) {
+                // the M chains alone; sigmaMap stays what it was until somebody may read it (vsom_internal.hpp, `sg`)
+                if (compact) {
+                    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, 0, {vsom_member(c->sg_inv, c->xpitch), vsom_member(c->sg_meta, 16)}));
+                    hipLaunchKernelGGL(sg_keep_record_kernel, dim3((c->xpitch + 255) / 256), dim3(256), 0, c->stream, c->cc_inv.p,
+                                       (int)c->xpitch, c->cc_meta.p, c->sg_inv.p, c->sg_meta.p);
+                }
+                if ((rc = launch_nt_chains(c, c->upd_nt_mean[kernel], 0, c->N, c->B, ldn, c->xq_bpad, compact, c->cc_meta.p)))
+                    return rc;
+                c->sg.on = true;
+                c->sg.B = c->B;
+                c->sg.ldn = ldn;
+                c->sg.bpad = c->xq_bpad;
+                c->sg.compact = compact;
+                c->sg.kernel = kernel;
+                ++c->sg_stats[0];
+            } else if ((rc = launch_nt_chains(c, c->upd_nt[kernel], n0, nloc, c->B, ldn, c->xq_bpad, compact, c->cc_meta.p))) {
+                return rc;
+            }
             sig_cols = compact ? -1 : (int)(quads * 4);
         }
         VSOM_HIP_CHECK(hipGetLastError());
     }
     if (sig_cols < 0) {
         TimerScope ts(c, VSOM_T_SIGMA);
-        if ((rc = vsom_cc_expand(c, n0, nloc)))
+        if ((rc = vsom_cc_expand(c, n0, nloc, deferred ? 1 : 3)))
             return rc;
     }
-    if (sig_cols > 0) {
+    if (sig_cols > 0 && !deferred) {
         TimerScope ts(c, VSOM_T_SIGMA);
         // the assembly kernels left raw S in those columns (CLR: in the A part and in the B part)
         for (uint32_t part = 0; part < c->nparts; ++part)
@@ -759,5 +875,5 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1)
                                (int)c->part_len, (int)n0, (int)nloc, c->weight.p);
         VSOM_HIP_CHECK(hipGetLastError());
     }
-    return vsom_join_aux(c);   // the MSE sum forked by launch_finish ran beside the kernels above
+    return done();   // (joins the side stream: the MSE sum forked by launch_finish ran beside the kernels above)
 }

@@ -64,8 +64,15 @@ class HipEngine:
     def _bind_state(self):
         c, n, p, dev = self.ctx, self.N, self.pitch, self.device
         self.map_rows = device_tensor(c.device_ptr(capi.BUF_MAP), (n, p), torch.float32, dev)
+        # sigma_rows is a KEPT pointer: current as of this call and after every partial-range phase 2 (world > 1, always
+        # eager).  At world == 1 the epochs are whole-map ones and may leave sigmaMap pending (vsom_set_sigma_mode): call
+        # sigma_flush() before reading the tensor.
         self.sigma_rows = device_tensor(c.device_ptr(capi.BUF_SIGMA), (n, p), torch.float32, dev)
         self.weight = device_tensor(c.device_ptr(capi.BUF_WEIGHT), (n,), torch.float32, dev)
+
+    def sigma_flush(self):
+        """make sigma_rows current: enqueues the materialisation of a pending sigmaMap on the context's stream"""
+        self.ctx.sigma_flush()
 
     def load_chunk_device(self, x_tensor):
         """x_tensor: [B, J] fp32 on this GPU; staged on the context's stream."""

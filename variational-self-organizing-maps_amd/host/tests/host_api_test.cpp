@@ -514,8 +514,67 @@ static int mnist(const std::string &folder, const std::string &out)
     return 0;
 }
 
+// `host_api_test sigma <rows.f32> <nrows> <depth> <chunk> <width> <height> <epochs> <outdir>`: the mirror as a reader of a
+// pending sigmaMap (include/vsom_hip.h, vsom_set_sigma_mode; VSOM_SIGMA_MODE picks the mode at vsom_create).
+// Som::train(BatchMap) of one epoch, a read of sigmaMap through the host mirror (which caches the state it downloads),
+// Som::train(BatchMap) of <epochs> more epochs -- they never read sigmaMap -- and the read again: the cached copy must be
+// replaced by the last epoch's sigmaMap, materialised by that read.  Dumps after either read (sigma_a.bin, sigma_b.bin:
+// tests/test_gpu_sigma_readers.py and tools/e2e_bench.sh compare them with the oracle) and one JSON line with the wall
+// times of the second train() and of the read behind it, the downloads and vsom_sigma_stats.
+static int sigma_mode(int argc, char **argv)
+{
+    if (argc < 10) {
+        std::fprintf(stderr, "usage: sigma <rows.f32> <nrows> <depth> <chunk> <width> <height> <epochs> <outdir>\n");
+        return 2;
+    }
+    const size_t nrows = std::stoul(argv[3]), depth = std::stoul(argv[4]), chunk = std::stoul(argv[5]);
+    const size_t W = std::stoul(argv[6]), H = std::stoul(argv[7]), epochs = std::stoul(argv[8]);
+    const std::string out = argv[9];
+    std::vector<float> rows(nrows * depth);
+    {
+        std::ifstream f(argv[2], std::ios::binary);
+        f.read((char *)rows.data(), (std::streamsize)(rows.size() * 4));
+        if (!f) {
+            std::fprintf(stderr, "cannot read %s\n", argv[2]);
+            return 2;
+        }
+    }
+    ArrayDataLoader loader(rows.data(), nrows, depth, chunk);
+    DataSet ds(loader);
+    Som som{W, H, depth};
+    som.randomInitialize(5, 1);
+    using clk = std::chrono::steady_clock;
+    auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+    std::cout.setstate(std::ios_base::failbit);          // the drivers print per epoch
+    som.train(ds, 1, 0.0, 0.0, 8.0, 0.2, Som::WeigthDecayFunction::BatchMap);
+    (void)som.getMaxSigmaOfFeature(0);                   // downloads and caches the state
+    dump(out + "/sigma_a.bin", som, som.getMetrics().MeanSquaredError);
+    const size_t downloads_a = som.stateDownloads();
+    auto t0 = clk::now();
+    som.train(ds, epochs, 0.0, 0.0, 8.0, 0.2, Som::WeigthDecayFunction::BatchMap);
+    const double train_ms = ms_since(t0);
+    uint64_t before[4] = {0, 0, 0, 0}, after[4] = {0, 0, 0, 0};
+    vsom_sigma_stats(som.context(), before);
+    t0 = clk::now();
+    (void)som.getMaxSigmaOfFeature(0);                   // the cached copy is stale: downloads again, materialising first
+    const double read_ms = ms_since(t0);
+    vsom_sigma_stats(som.context(), after);
+    dump(out + "/sigma_b.bin", som, som.getMetrics().MeanSquaredError);
+    std::cout.clear();
+    std::printf("{\"sigma_reader\": \"%zux%zux%zu, %zu rows in chunks of %zu, 1 + %zu epochs\", \"train_ms_per_epoch\": %.3f, "
+                "\"read_ms\": %.3f, \"downloads_first\": %zu, "
+                "\"downloads_last\": %zu, \"pending_before_read\": %llu, \"deferred\": %llu, \"dropped\": %llu, "
+                "\"materialised_before_read\": %llu, \"materialised\": %llu}\n",
+                W, H, depth, nrows, chunk, epochs, train_ms / (double)epochs, read_ms, downloads_a,
+                som.stateDownloads(), (unsigned long long)before[3], (unsigned long long)after[0], (unsigned long long)after[1],
+                (unsigned long long)before[2], (unsigned long long)after[2]);
+    return 0;
+}
+
 int main(int argc, char **argv)
 {
+    if (argc > 1 && std::string(argv[1]) == "sigma")
+        return sigma_mode(argc, argv);
     if (argc > 1 && std::string(argv[1]) == "perf")
         return perf();
     if (argc > 1 && std::string(argv[1]) == "perf_tiny")
