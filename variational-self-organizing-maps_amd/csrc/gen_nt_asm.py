@@ -25,8 +25,12 @@ Scalar loads return out of order, so every wait is lgkmcnt(0): at the top of eac
 wavefront waits for everything it issued one group earlier (x of this group, (c, w) of this group's two pairs),
 issues the next group's loads and computes 40-48 packed operations.
 
-Mean-only forms (MEAN below): the same text without the S instructions and the second store, for epochs whose sigmaMap is
+Mean-only forms (MEAN below): the chains without the S instructions and the second store, for epochs whose sigmaMap is
 produced later by the full kernel (vsom_update.hip, "pending sigma"): 6 packed operations per sample and quad, 4 for a zero quad.
+They never read w, so they take the c-only operand array (vsom_update.hip, cwp_kernel<.., true>): one float4
+{c_j, c_j+1, c_j+2, c_j+3} per node and sample QUAD at [(j>>2)][node].  Per block of 32 samples the workgroup stages 8 quad-rows
+x 64 nodes = 8 KB (ONE 16-byte global load per thread) into one of two 8-KB LDS slots, and a wavefront gets the four c of a
+group of 4 samples with ONE ds_read_b128; sample i of the group takes c from half i&1 of register pair i>>1 (op_sel).
 
 XCD-aware grid: grid.x = 8 * column blocks, grid.y = ceil(node groups / 8) (gen_update_asm.py).
 
@@ -38,6 +42,8 @@ import os
 CT = 32                                   # samples per staged (c, w) block
 SLOT_XOR = 0x4000                         # (c, w) slots of 16 KB at 0x0000 / 0x4000
 LDS_BYTES = 0x8000
+SLOT_XOR_C = 0x2000                       # c-only slots of 8 KB at 0x0000 / 0x2000 (the mean-only kernels)
+LDS_BYTES_C = 0x4000
 WG = 512
 
 S_KARG = "s[0:1]"
@@ -53,8 +59,8 @@ S_REC = (38, 39)
 XSET = (40, 56)                           # two sets of 16 SGPRs: 4 samples x 4 values
 V_TID = 0
 V_M, V_S, V_D, V_T, V_U = 2, 6, 10, 14, 18
-V_RING = 22                               # 2 sets x 2 pairs x {c, w, c, w}
-V_G = 38                                  # staging: two 16-byte pieces
+V_RING = 22                               # 2 sets x 2 pairs x {c, w, c, w}; c-only: 2 sets x {c, c, c, c}
+V_G = 38                                  # staging: two 16-byte pieces (c-only: one)
 V_CR, V_CW, V_OC, V_OC2 = 46, 47, 48, 49
 V_K = 50                                  # Median: both halves -2^24
 V_A = V_D
@@ -69,9 +75,22 @@ def sp(base, p):
     return f"s[{base + 2 * p}:{base + 2 * p + 1}]"
 
 
+def csrc(mode, cwb, nsrc):
+    """(register pair, modifiers) that broadcast c as source 0 of a packed operation of nsrc sources: the low half of
+    {c, w} in v[cwb:cwb+1] -- or, for the mean-only kernels, c alone in v[cwb]: either half of the aligned pair it lies in"""
+    lo = "op_sel_hi:[0,1,1]" if nsrc == 3 else "op_sel_hi:[0,1]"
+    if mode not in MEAN:
+        return f"v[{cwb}:{cwb + 1}]", lo
+    hi = "op_sel:[1,0,0]" if nsrc == 3 else "op_sel:[1,0]"
+    return f"v[{cwb & ~1}:{(cwb & ~1) + 1}]", hi if cwb & 1 else lo
+
+
 def compute(o, mode, xs, cwb):
-    """one sample: x in s[xs:xs+3], {c, w} in v[cwb:cwb+1] (Som.cpp:861-867, Transformation.cpp:12,50)"""
+    """one sample: x in s[xs:xs+3], {c, w} in v[cwb:cwb+1] -- mean-only: c in v[cwb] -- (Som.cpp:861-867,
+    Transformation.cpp:12,50)"""
     cw = f"v[{cwb}:{cwb + 1}]"
+    c3, sel3 = csrc(mode, cwb, 3)
+    c2, sel2 = csrc(mode, cwb, 2)
     P = (0, 1)
     if mode in MED:
         # StandardMedianEstimator, 7 operations per pair -- medmean: the 5 of them that M needs -- (vsom_update.hip,
@@ -87,12 +106,12 @@ def compute(o, mode, xs, cwb):
         for p in P:   # n = [t < 0]
             o.append(f"\tv_pk_mul_f32 {vp(V_U, p)}, {vp(V_D, p)}, {S_BIG} neg_lo:[1,0] neg_hi:[1,0] clamp")
         for p in P:   # M = M + c*p
-            o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {cw}, {vp(V_T, p)}, {vp(V_M, p)} op_sel_hi:[0,1,1]")
+            o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {c3}, {vp(V_T, p)}, {vp(V_M, p)} {sel3}")
         if mode == "med":
             for p in P:   # S = S + w*p
                 o.append(f"\tv_pk_fma_f32 {vp(V_S, p)}, {cw}, {vp(V_T, p)}, {vp(V_S, p)} op_sel:[1,0,0]")
         for p in P:   # M = M - c*n
-            o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {cw}, {vp(V_U, p)}, {vp(V_M, p)} op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]")
+            o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {c3}, {vp(V_U, p)}, {vp(V_M, p)} {sel3} neg_lo:[1,0,0] neg_hi:[1,0,0]")
         if mode == "med":
             for p in P:   # S = S + w*n
                 o.append(f"\tv_pk_fma_f32 {vp(V_S, p)}, {cw}, {vp(V_U, p)}, {vp(V_S, p)} op_sel:[1,0,0]")
@@ -101,10 +120,10 @@ def compute(o, mode, xs, cwb):
         o.append(f"\tv_pk_add_f32 {vp(V_D, p)}, {sp(xs, p)}, {vp(V_M, p)} neg_lo:[0,1] neg_hi:[0,1]")
     if mode in ("fma", "meanfma"):
         for p in P:   # M = c*delta + M
-            o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {cw}, {vp(V_D, p)}, {vp(V_M, p)} op_sel_hi:[0,1,1]")
+            o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {c3}, {vp(V_D, p)}, {vp(V_M, p)} {sel3}")
     else:
         for p in P:   # t = c*delta
-            o.append(f"\tv_pk_mul_f32 {vp(V_T, p)}, {cw}, {vp(V_D, p)} op_sel_hi:[0,1]")
+            o.append(f"\tv_pk_mul_f32 {vp(V_T, p)}, {c2}, {vp(V_D, p)} {sel2}")
     if mode == "meanfma":
         return
     if mode == "mean":
@@ -132,14 +151,16 @@ def compute_zero(o, mode, cwb):
     cw = f"v[{cwb}:{cwb + 1}]"
     P = (0, 1)
     if mode == "mean":
+        c2, sel2 = csrc(mode, cwb, 2)
         for p in P:   # t = c*M ; M = M - t
-            o.append(f"\tv_pk_mul_f32 {vp(V_T, p)}, {cw}, {vp(V_M, p)} op_sel_hi:[0,1]")
+            o.append(f"\tv_pk_mul_f32 {vp(V_T, p)}, {c2}, {vp(V_M, p)} {sel2}")
         for p in P:
             o.append(f"\tv_pk_add_f32 {vp(V_M, p)}, {vp(V_M, p)}, {vp(V_T, p)} neg_lo:[0,1] neg_hi:[0,1]")
         return
     if mode == "meanfma":
+        c3, sel3 = csrc(mode, cwb, 3)
         for p in P:   # M = (-c)*M + M
-            o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {cw}, {vp(V_M, p)}, {vp(V_M, p)} op_sel_hi:[0,1,1] neg_lo:[1,0,0] neg_hi:[1,0,0]")
+            o.append(f"\tv_pk_fma_f32 {vp(V_M, p)}, {c3}, {vp(V_M, p)}, {vp(V_M, p)} {sel3} neg_lo:[1,0,0] neg_hi:[1,0,0]")
         return
     for p in P:       # u = w*M (M before the step)
         o.append(f"\tv_pk_mul_f32 {vp(V_U, p)}, {cw}, {vp(V_M, p)} op_sel:[1,0]")
@@ -167,8 +188,8 @@ def compute_zero(o, mode, cwb):
 
 MED = ("med", "medmean")
 # the chains without their S half (a deferred sigmaMap, vsom_update.hip): M's own operation sequence -- "mean" is the M
-# chain of "std" and of "sfma", "meanfma" that of "fma", "medmean" that of "med" -- the same staging, loads, zero-quad
-# branch and barriers, and the sigma buffer never written
+# chain of "std" and of "sfma", "meanfma" that of "fma", "medmean" that of "med" -- the same x loads, zero-quad branch and
+# barriers, the c-only operand array staged in half the bytes, and the sigma buffer never written
 MEAN = ("mean", "meanfma", "medmean")
 _lab = [0]
 
@@ -191,6 +212,8 @@ def step(o, mode, xs, cwb, bit):
 def kernel(name, mode):
     o = []
     E = o.append
+    conly = mode in MEAN                                        # the c-only operand array: 8 quad-rows of 16 B per block
+    slot_xor = SLOT_XOR_C if conly else SLOT_XOR
     E(f"\t.text\n\t.globl {name}\n\t.p2align 8\n\t.type {name},@function\n{name}:")
     E(f"\ts_load_dwordx8 s[4:11], {S_KARG}, 0x0")              # Xq, cw2, map, sbuf
     E(f"\ts_load_dwordx4 s[12:15], {S_KARG}, 0x20")            # xq row pitch, ldn_bytes, B, nloc
@@ -238,21 +261,22 @@ def kernel(name, mode):
     E(f"\ts_mul_i32 {S_TMP}, {S_TMP}, {S_Q}")
     E(f"\ts_add_u32 s{S_ZP[0]}, s{S_ZP[0]}, {S_TMP}")
     E(f"\ts_addc_u32 s{S_ZP[1]}, s{S_ZP[1]}, 0")
-    # (c, w): staging piece of thread t = pair-row t>>6 (+8), node t&63
+    # (c, w): staging piece of thread t = pair-row t>>6 (+8), node t&63; c-only: quad-row t>>6, node t&63
     E(f"\tv_and_b32_e32 v{V_CR}, 63, v{V_TID}")
     E(f"\tv_lshlrev_b32_e32 v{V_CR}, 4, v{V_CR}")              # lane*16: read base (slot 0)
     E(f"\tv_lshlrev_b32_e32 v{V_CW}, 4, v{V_TID}")             # write: tid*16 (+8192)
     E(f"\tv_lshrrev_b32_e32 v{V_OC}, 6, v{V_TID}")
     E(f"\tv_mul_lo_u32 v{V_OC}, v{V_OC}, {S_LDN}")
     E(f"\tv_add_u32_e32 v{V_OC}, v{V_OC}, v{V_CR}")
-    E(f"\ts_lshl_b32 {S_TMP}, {S_LDN}, 3")
-    E(f"\tv_add_u32_e32 v{V_OC2}, {S_TMP}, v{V_OC}")
+    if not conly:
+        E(f"\ts_lshl_b32 {S_TMP}, {S_LDN}, 3")
+        E(f"\tv_add_u32_e32 v{V_OC2}, {S_TMP}, v{V_OC}")
     E(f"\ts_lshl_b32 {S_TMP}, {S_WGX}, 10")                    # node group * 64 nodes * 16 B
     if os.environ.get("VSOM_GEN_NT_CWL2"):                      # development, timing only (WRONG results): every workgroup
         E(f"\ts_and_b32 {S_TMP}, {S_TMP}, 0x400")                # stages node group 0 / 1's (c, w): 8 MB, L2-resident
     E(f"\ts_add_u32 s{S_CP[0]}, s{S_CP[0]}, {S_TMP}")
     E(f"\ts_addc_u32 s{S_CP[1]}, s{S_CP[1]}, 0")
-    E(f"\ts_lshl_b32 {S_CSTEP}, {S_LDN}, 4")                   # 16 pair-rows
+    E(f"\ts_lshl_b32 {S_CSTEP}, {S_LDN}, {3 if conly else 4}")  # 16 pair-rows / 8 quad-rows
     for r in range(V_M, V_M + 8):                               # currentModel / currentModelSigma .setZero() :843-844
         E(f"\tv_mov_b32_e32 v{r}, 0")
     E(f"\ts_cmp_eq_u32 {S_B}, 0")
@@ -265,13 +289,15 @@ def kernel(name, mode):
 
     def gload():
         E(f"\tglobal_load_dwordx4 v[{V_G}:{V_G + 3}], v{V_OC}, s[{S_CP[0]}:{S_CP[1]}]")
-        E(f"\tglobal_load_dwordx4 v[{V_G + 4}:{V_G + 7}], v{V_OC2}, s[{S_CP[0]}:{S_CP[1]}]")
+        if not conly:
+            E(f"\tglobal_load_dwordx4 v[{V_G + 4}:{V_G + 7}], v{V_OC2}, s[{S_CP[0]}:{S_CP[1]}]")
         E(f"\ts_add_u32 s{S_CP[0]}, s{S_CP[0]}, {S_CSTEP}")
         E(f"\ts_addc_u32 s{S_CP[1]}, s{S_CP[1]}, 0")
 
     def lwrite():
         E(f"\tds_write_b128 v{V_CW}, v[{V_G}:{V_G + 3}]")
-        E(f"\tds_write_b128 v{V_CW}, v[{V_G + 4}:{V_G + 7}] offset:8192")
+        if not conly:
+            E(f"\tds_write_b128 v{V_CW}, v[{V_G + 4}:{V_G + 7}] offset:8192")
 
     def xload(st):
         E(f"\ts_load_dwordx16 s[{st}:{st + 15}], s[{S_XP[0]}:{S_XP[1]}], 0x0")
@@ -279,7 +305,11 @@ def kernel(name, mode):
         E(f"\ts_addc_u32 s{S_XP[1]}, s{S_XP[1]}, 0")
 
     def cread(ring, g):
-        """{c, w} of the two sample pairs of group g -> ring set `ring`"""
+        """{c, w} of the two sample pairs of group g -> ring set `ring`; c-only: the four c of group g"""
+        if conly:
+            r = V_RING + 4 * ring
+            E(f"\tds_read_b128 v[{r}:{r + 3}], v{V_CR} offset:{1024 * g}")
+            return
         r = V_RING + 8 * ring
         E(f"\tds_read_b128 v[{r}:{r + 3}], v{V_CR} offset:{1024 * (2 * g)}")
         E(f"\tds_read_b128 v[{r + 4}:{r + 7}], v{V_CR} offset:{1024 * (2 * g + 1)}")
@@ -293,7 +323,7 @@ def kernel(name, mode):
     E(f"\ts_mov_b32 {S_ZN}, 0")
     E(f"\ts_waitcnt vmcnt(0)")
     lwrite()
-    E(f"\tv_xor_b32_e32 v{V_CW}, {SLOT_XOR}, v{V_CW}")
+    E(f"\tv_xor_b32_e32 v{V_CW}, {slot_xor}, v{V_CW}")
     E(f"\ts_waitcnt lgkmcnt(0)")
     E(f"\ts_cmp_eq_u32 {S_CNT}, 0")
     E(f"\ts_cbranch_scc1 .L_p1_{name}")
@@ -324,11 +354,11 @@ def kernel(name, mode):
         xload(XSET[(g + 1) % 2])                                # next group's x (the next block's at g = 7)
         if g + 1 < CT // 4:
             cread((g + 1) % 2, g + 1)
-        xs, r = XSET[g % 2], V_RING + 8 * (g % 2)
+        xs, r = XSET[g % 2], V_RING + (4 if conly else 8) * (g % 2)
         for i in range(4):
-            step(o, mode, xs + 4 * i, r + 2 * i, 4 * g + i)
-    E(f"\tv_xor_b32_e32 v{V_CW}, {SLOT_XOR}, v{V_CW}")
-    E(f"\tv_xor_b32_e32 v{V_CR}, {SLOT_XOR}, v{V_CR}")
+            step(o, mode, xs + 4 * i, r + (1 if conly else 2) * i, 4 * g + i)
+    E(f"\tv_xor_b32_e32 v{V_CW}, {slot_xor}, v{V_CW}")
+    E(f"\tv_xor_b32_e32 v{V_CR}, {slot_xor}, v{V_CR}")
     E(f"\ts_waitcnt lgkmcnt(0)")
     E(f"\ts_mov_b32 {S_Z}, {S_ZN}")
     E(f"\ts_barrier")                                          # slot b+1 written by all, slot b read by all
@@ -343,7 +373,7 @@ def kernel(name, mode):
     E(f"\ts_cbranch_scc1 .L_dnl_{name}")
     gload()
     E(f".L_dnl_{name}:")
-    E(f"\tv_xor_b32_e32 v{V_CW}, {SLOT_XOR}, v{V_CW}")
+    E(f"\tv_xor_b32_e32 v{V_CW}, {slot_xor}, v{V_CW}")
     E(f"\ts_waitcnt lgkmcnt(0)")
     E(f"\ts_barrier")
     E(f"\ts_sub_u32 {S_CNT}, {S_CNT}, 1")
@@ -361,12 +391,12 @@ def kernel(name, mode):
         if g + 1 < CT // 4:
             xload(XSET[(g + 1) % 2])                            # (rows past the chunk: padded, never consumed)
             cread((g + 1) % 2, g + 1)
-        xs, r = XSET[g % 2], V_RING + 8 * (g % 2)
+        xs, r = XSET[g % 2], V_RING + (4 if conly else 8) * (g % 2)
         for i in range(4):
             if i > 0:
                 E(f"\ts_cmp_le_u32 {S_TAIL}, {4 * g + i}")
                 E(f"\ts_cbranch_scc1 .L_store_{name}")
-            step(o, mode, xs + 4 * i, r + 2 * i, 4 * g + i)
+            step(o, mode, xs + 4 * i, r + (1 if conly else 2) * i, 4 * g + i)
     # ---- epilogue: map row <- M (Som.cpp:870), sigma buffer <- raw S --------------------------------
     E(f".L_store_{name}:")
     E(f"\ts_waitcnt vmcnt(0) lgkmcnt(0)")
@@ -404,5 +434,5 @@ def emit():
     out = []
     for m in MODES:
         name = f"vsom_update_{m}_nt4_gfx950"
-        out.append((name, kernel(name, m), NVGPR, 80, LDS_BYTES, 0 if m in MED else 1, WG))
+        out.append((name, kernel(name, m), NVGPR, 80, LDS_BYTES_C if m in MEAN else LDS_BYTES, 0 if m in MED else 1, WG))
     return out

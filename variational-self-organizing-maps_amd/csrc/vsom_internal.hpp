@@ -180,7 +180,9 @@ struct vsom_ctx {
     // may run the M-only chain kernel and leave sigmaMap unwritten; `sg` then records what the full kernel needs to
     // produce that epoch's sigmaMap later.  Its inputs are the context's own buffers -- Xq / zq, cw, weight and the
     // compaction's scratch rows are written by launch_phase2 alone, which drops or materialises the record first -- except
-    // the live-column record, which the staging of the next chunk overwrites: sg_inv / sg_meta are owned copies.
+    // the live-column record and lastBMU, which the staging and the search of the next chunk overwrite: sg_inv / sg_meta /
+    // sg_bmu are owned copies.  The mean-only kernel takes the c-only form of the (c,w) array (half the bytes), so the
+    // record also keeps the epoch's sigma: the materialisation runs the neighbourhood pass again in its full form.
     // Every entry point materialises it (vsom_sigma_flush_pending via vsom_join_aux) but the listed ones that never
     // read sigmaMap (vsom_capi.hip, CHECK_CTX_KEEP); the next full-range epoch, which overwrites every row, drops it.
     struct PendingSigma {
@@ -189,8 +191,12 @@ struct vsom_ctx {
         uint32_t bpad = 0;
         bool compact = false;
         int kernel = 0;             // index into upd_nt: the update mode and transformation in force at that epoch
+        double sigma = 0.0;         // the epoch's sigma: the table of its neighbourhood pass.  (Today every call that
+                                    // retabulates -- another phase 2, the tiny and custom paths -- materialises or drops the
+                                    // record first, so the table in place is still this one; the record does not rely on it.)
     } sg;
     DevBuf<int> sg_inv; DevBuf<unsigned> sg_meta;
+    DevBuf<u64> sg_bmu;             // [B] the epoch's lastBMU
     int sigma_mode = VSOM_SIGMA_AUTO;
     unsigned sigma_unread = 0;      // full-range epochs since the last entry point that may have read sigmaMap (AUTO)
     bool sigma_shared = false;      // a group or an ensemble reads this context's buffers directly: never deferred

@@ -17,20 +17,26 @@
 //                    one column quad per wavefront, x from scalar loads of the transposed chunk (vsom_xq.hip)
 //                    as SGPR operands of v_pk_*, (c,w) staged once per workgroup through LDS, the 5-operation
 //                    step for all-zero quads.
-//                  - vsom_update_{mean,meanfma,medmean}_nt4_gfx950: the same kernels without the S chain, for full-range
-//                    epochs whose sigmaMap stays pending ("pending sigma" below, vsom_internal.hpp)
+//                  - vsom_update_{mean,meanfma,medmean}_nt4_gfx950: the same chains without S, for full-range
+//                    epochs whose sigmaMap stays pending ("pending sigma" below, vsom_internal.hpp); they never read w and
+//                    take the c-only form of the (c,w) array, which cwp_kernel writes for such an epoch
 //                  - vsom_update_clr_rp8_gfx950 (gen_update_asm.py): CLR, lane = node, 8 parameter pairs per lane.
 //                  - update_chain3_kernel (HIP, below): maps too small to fill the chip with lane = node
 //                    (C4: 64x64x32): one lane per (node, dim pair) chain, operands staged through LDS.
 //   sigma_finalize_kernel : sigmaMap = sqrt(S / W) for the columns the assembly kernels left as S
 //                  (+ zeroes of the padding columns a ragged last slice wrote).
 #include "vsom_device.hpp"
+#include <algorithm>
 #include <cmath>
 #include <cstdlib>
 #include <mutex>
 
 // (c,w) layout: pair-interleaved, one float4 {c_j, w_j, c_j+1, w_j+1} per node and sample pair at
 // [(j>>1)][node] -- the chain kernels stage it with 16-byte loads.
+// c-only layout (CONLY, in the same buffer): one float4 {c_j, c_j+1, c_j+2, c_j+3} per node and sample QUAD at
+// [(j>>2)][node], for the mean-only chain kernels, which never read w: half the bytes written, staged and read back.
+// In BOTH forms element [0][node].x is c of sample 0: cc_expand_kernel (vsom_compact.hip) reads it for its NaN-row decision,
+// after an eager and after a deferred epoch alike.
 
 // Role-split neighbourhood chain: one workgroup (9 wavefronts) serves NW nodes and walks the chunk
 // in tiles of T samples (NW*T = 2048) through LDS.  Wavefront 0 does nothing but the serial part --
@@ -40,15 +46,17 @@
 // workgroup is the chain's own ~B dependent adds instead of B x (lookup + division + chain).
 #define CWP_WT 512                               // worker threads
 #define CWP_THREADS (64 + CWP_WT)
-template <int NW, int T, bool LUT_LDS>
+template <int NW, int T, bool LUT_LDS, bool CONLY>
 __global__ __launch_bounds__(CWP_THREADS) void cwp_kernel(const u64 *__restrict__ lastbmu, int B, int n0, int n1,
                                                           int W, int H, const float *__restrict__ lut,
                                                           int lutw, int luth, float2 *__restrict__ cw, int ldn,
                                                           float *__restrict__ weight)
 {
-    static_assert(NW * T == 2048 && CWP_WT % NW == 0 && T % 2 == 0 && T <= CWP_WT, "worker mapping");
+    static_assert(NW * T == 2048 && CWP_WT % NW == 0 && T % 4 == 0 && T <= CWP_WT, "worker mapping");
     constexpr int LK = NW * T / CWP_WT;          // lookups per worker thread and tile (4)
     constexpr int PK = LK / 2;                   // sample pairs per worker thread and tile (2)
+    constexpr int QK = LK / 4;                   // sample quads per worker thread and tile (1), c-only form
+    static_assert(LK % 4 == 0, "whole sample quads per worker thread");
     constexpr int SS = CWP_WT / NW;              // sample stride between a thread's elements
     extern __shared__ __attribute__((aligned(16))) unsigned char cwp_smem[];
     float *wL = (float *)cwp_smem;               // [3][T][NW]  w of tiles t-1, t, t+1
@@ -110,6 +118,30 @@ __global__ __launch_bounds__(CWP_THREADS) void cwp_kernel(const u64 *__restrict_
         const float *ws = wL + (t % 3) * T * NW;
         const float *Ws = WL + (t & 1) * T * NW;
         const int nt = B - t * T < T ? B - t * T : T;
+        if (CONLY) {                             // the same divisions in the same order, c alone: one float4 per sample quad
+            float w[QK][4], Wp[QK][4];
+#pragma unroll
+            for (int k = 0; k < QK; ++k) {
+                const int s = (s0 + k * SS) * 4;
+#pragma unroll
+                for (int i = 0; i < 4; ++i) {
+                    w[k][i] = ws[(s + i) * NW + lnode];
+                    Wp[k][i] = Ws[(s + i) * NW + lnode];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < QK; ++k) {
+                const int s = (s0 + k * SS) * 4;
+                float4 o;                        // slots past the chunk's end hold 0.f and are never consumed
+                o.x = w[k][0] / Wp[k][0];        // c = w/W :864 (0/0 -> NaN, Q7)
+                o.y = s + 1 < nt ? w[k][1] / Wp[k][1] : 0.f;
+                o.z = s + 2 < nt ? w[k][2] / Wp[k][2] : 0.f;
+                o.w = s + 3 < nt ? w[k][3] / Wp[k][3] : 0.f;
+                if (valid && s < nt)
+                    ((float4 *)cw)[(size_t)((t * T + s) >> 2) * ldn + nl] = o;
+            }
+            return;
+        }
         float w0[PK], w1[PK], W0[PK], W1[PK];
 #pragma unroll
         for (int k = 0; k < PK; ++k) {
@@ -181,8 +213,8 @@ __global__ __launch_bounds__(CWP_THREADS) void cwp_kernel(const u64 *__restrict_
     }
     if (wt >= 0)
         emit(ntiles - 1);
-    else if (tid < NW && valid)
-        weight[n0 + nl] = run;                   // :875
+    else if (tid < NW && valid && weight)
+        weight[n0 + nl] = run;                   // :875 (null: a materialisation, whose epoch wrote it)
 }
 
 typedef float vsom_f2 __attribute__((ext_vector_type(2)));
@@ -599,6 +631,32 @@ static bool vsom_use_chain(const vsom_ctx *c, size_t nloc)
 
 extern "C" int vsom_small_map_chains(const vsom_ctx *c, size_t nodes) { return c && vsom_use_chain(c, nodes) ? 1 : 0; }
 
+// The neighbourhood pass over the nodes [n0, n1) for the B rows whose BMUs are `bmu`, from the table ensure_lut left:
+// the (c,w) array, or its c-only form for an epoch that runs the mean-only chains; weightMap unless `weight` is null.
+static int launch_cwp(vsom_ctx *c, const u64 *bmu, size_t B_, size_t n0, size_t n1, size_t ldn, bool conly, float *weight)
+{
+    // role-split kernel, 16 nodes per workgroup; the table in LDS only while it is small: what counts is how
+    // many workgroups (worker wavefronts) a CU holds -- 40 KB of tiles each; a 64-KB table (128x128 map) would
+    // leave one per CU.  Measured at C3: 64 nodes + LDS table 0.153 ms, 32 + global 0.142, 16 + global 0.121,
+    // 16 + LDS 0.20.
+    const size_t nloc = n1 - n0;
+    const size_t lut_bytes = (size_t)c->lut_w * c->lut_h * sizeof(float);
+    const bool lds = lut_bytes <= 24 * 1024;
+    constexpr int nw = 16, T = 2048 / nw;
+    const size_t smem = (size_t)5 * 2048 * sizeof(float) + (size_t)3 * T * sizeof(int2) + (lds ? lut_bytes : 0);
+    const void *fn = conly ? (lds ? (const void *)cwp_kernel<nw, T, true, true> : (const void *)cwp_kernel<nw, T, false, true>)
+                           : (lds ? (const void *)cwp_kernel<nw, T, true, false> : (const void *)cwp_kernel<nw, T, false, false>);
+    if (smem > 64 * 1024)
+        VSOM_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
+    int B = (int)B_, in0 = (int)n0, in1 = (int)n1, iW = (int)c->W, iH = (int)c->H, lw = (int)c->lut_w, lh = (int)c->lut_h,
+        ildn = (int)ldn;
+    const float *lut = c->lut.p;
+    float2 *cwp = c->cw.p;
+    void *args[] = {&bmu, &B, &in0, &in1, &iW, &iH, &lut, &lw, &lh, &cwp, &ildn, &weight};
+    VSOM_HIP_CHECK(hipLaunchKernel(fn, dim3((unsigned)((nloc + nw - 1) / nw)), dim3(CWP_THREADS), args, smem, c->stream));
+    return VSOM_OK;
+}
+
 // ---- pending sigma (vsom_internal.hpp, vsom_ctx::sg) ------------------------------------------------------------
 // one launch of a lane = node Standard / Median chain kernel over the nodes [n0, n0 + nloc), from the operands of a chunk of
 // B rows: the one place that fills the kernarg, for the eager epoch, the mean-only epoch and the materialisation
@@ -630,15 +688,19 @@ static int launch_nt_chains(vsom_ctx *c, void *fn, size_t n0, size_t nloc, size_
     return VSOM_OK;
 }
 
-// the owned copy of the live-column record: inv [ninv], meta [16]
+// the owned copies of the live-column record -- inv [ninv], meta [16]; ninv = 0: no compaction, neither is touched -- and
+// of the epoch's lastBMU [nb]
 __global__ __launch_bounds__(256) void sg_keep_record_kernel(const int *__restrict__ inv, int ninv, const unsigned *__restrict__ meta,
-                                                             int *__restrict__ inv_out, unsigned *__restrict__ meta_out)
+                                                             int *__restrict__ inv_out, unsigned *__restrict__ meta_out,
+                                                             const u64 *__restrict__ bmu, int nb, u64 *__restrict__ bmu_out)
 {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < ninv)
         inv_out[i] = inv[i];
-    if (i < 16)
+    if (i < 16 && ninv > 0)
         meta_out[i] = meta[i];
+    if (i < nb)
+        bmu_out[i] = bmu[i];
 }
 
 void vsom_sigma_drop(vsom_ctx *c)
@@ -649,15 +711,24 @@ void vsom_sigma_drop(vsom_ctx *c)
     }
 }
 
-// The full chain kernel of the pending epoch from the operands that epoch left in place: its M goes where the M-only
+// The full chain kernel of the pending epoch from the operands that epoch left in place -- but (c,w), of which the epoch
+// wrote the c-only form: the neighbourhood pass runs again in its full form, from the epoch's sigma and its owned lastBMU
+// (the same table, additions and divisions: the same c, and the w beside it).  The kernel's M goes where the M-only
 // kernel put the same values (the compaction's scratch rows, or the map rows themselves: no epoch has run since, and
 // every call that writes the map materialises first), its raw S becomes sigmaMap as in an eager epoch.
 static int sigma_materialise(vsom_ctx *c)
 {
     const vsom_ctx::PendingSigma p = c->sg;
+    int rc = ensure_lut(c, p.sigma);       // (may fail: the record stays)
+    if (rc)
+        return rc;
     c->sg.on = false;
     ++c->sg_stats[2];
-    int rc;
+    {
+        TimerScope ts(c, VSOM_T_CW);
+        if ((rc = launch_cwp(c, c->sg_bmu.p, p.B, 0, c->N, p.ldn, false, nullptr)))
+            return rc;
+    }
     {
         TimerScope ts(c, VSOM_T_UPDATE);
         if ((rc = launch_nt_chains(c, c->upd_nt[p.kernel], 0, c->N, p.B, p.ldn, p.bpad, p.compact, c->sg_meta.p)))
@@ -724,9 +795,19 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1, bool may_defe
         return rc;
     if ((rc = vsom_load_asm_module(c)))
         return rc;
-    vsom_sigma_drop(c);
     const size_t nloc = n1 - n0;
     const size_t ldn = (nloc + 63) / 64 * 64;
+    // does this epoch run the mean-only chains (the lane = node Standard / Median path alone)?  Decided here because the
+    // neighbourhood pass then writes the c-only operand array.  The old record goes BEFORE its owned buffers may be
+    // reallocated for the new one: a failed growth leaves them null, and no record may point at them then.
+    const bool compact = c->cc_valid;
+    const bool deferred = may_defer && full && c->transform != VSOM_CLR && !vsom_use_chain(c, nloc) && sigma_defers(c, compact);
+    vsom_sigma_drop(c);
+    if (deferred) {
+        if (compact)
+            VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, 0, {vsom_member(c->sg_inv, c->xpitch), vsom_member(c->sg_meta, 16)}));
+        VSOM_ALLOC_CHECK(vsom_grow(c->sg_bmu, c->B, c->stream));
+    }
     // pair rows: ceil(B/2) + what the kernels' staging reads ahead (one block of 16 pair-rows) + slack
     const size_t prow = (c->B + 1) / 2 + 24;
     const size_t need = prow * ldn * 2;   // float2 elements
@@ -734,28 +815,10 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1, bool may_defe
     VSOM_ALLOC_CHECK(vsom_grow(c->cw, need, c->stream, VSOM_BUF_ZERO));
     {
         TimerScope ts(c, VSOM_T_CW);
-        // role-split kernel, 16 nodes per workgroup; the table in LDS only while it is small: what counts is how
-        // many workgroups (worker wavefronts) a CU holds -- 40 KB of tiles each; a 64-KB table (128x128 map) would
-        // leave one per CU.  Measured at C3: 64 nodes + LDS table 0.153 ms, 32 + global 0.142, 16 + global 0.121,
-        // 16 + LDS 0.20.
-        const size_t lut_bytes = (size_t)c->lut_w * c->lut_h * sizeof(float);
-        const bool lds = lut_bytes <= 24 * 1024;
-        constexpr int nw = 16, T = 2048 / nw;
-        const size_t smem = (size_t)5 * 2048 * sizeof(float) + (size_t)3 * T * sizeof(int2) + (lds ? lut_bytes : 0);
-        const void *fn = lds ? (const void *)cwp_kernel<nw, T, true> : (const void *)cwp_kernel<nw, T, false>;
-        if (smem > 64 * 1024)
-            VSOM_HIP_CHECK(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)smem));
-        const u64 *bxy = c->lastbmu.p;
-        int B = (int)c->B, in0 = (int)n0, in1 = (int)n1, iW = (int)c->W, iH = (int)c->H, lw = (int)c->lut_w,
-            lh = (int)c->lut_h, ildn = (int)ldn;
-        const float *lut = c->lut.p;
-        float2 *cwp = c->cw.p;
-        float *wgt = c->weight.p;
-        void *args[] = {&bxy, &B, &in0, &in1, &iW, &iH, &lut, &lw, &lh, &cwp, &ildn, &wgt};
-        VSOM_HIP_CHECK(hipLaunchKernel(fn, dim3((unsigned)((nloc + nw - 1) / nw)), dim3(CWP_THREADS), args, smem, c->stream));
+        if ((rc = launch_cwp(c, c->lastbmu.p, c->B, n0, n1, ldn, deferred, c->weight.p)))
+            return rc;
     }
     int sig_cols = 0;   // > 0: columns left as raw S by the kernel; < 0: the compaction's scratch rows hold M and raw S
-    bool deferred = false;
     {
         TimerScope ts(c, VSOM_T_UPDATE);
         const unsigned gx = (unsigned)((nloc + 63) / 64);
@@ -830,21 +893,19 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1, bool may_defe
                 VSOM_HIP_CHECK(hipEventRecord(c->ev_rows_free, c->stream));
                 c->rows_free_valid = true;
             }
-            const bool compact = c->cc_valid;
             if (compact && (rc = vsom_cc_ensure_update_scratch(c)))
                 return rc;
             const bool fma = c->update_mode == VSOM_UPDATE_FMA, sfma = c->update_mode == VSOM_UPDATE_FMA_SIGMA;
             const bool med = c->transform == VSOM_MEDIAN;     // its FMAs are exact: one kernel for all modes
             const unsigned quads = compact ? c->cpitch / 4 : (c->D + 3) / 4;
             const int kernel = med ? 3 : (fma ? 1 : (sfma ? 2 : 0));
-            deferred = may_defer && full && sigma_defers(c, compact);
             if (deferred) {
-                // the M chains alone; sigmaMap stays what it was until somebody may read it (vsom_internal.hpp, `sg`)
-                if (compact) {
-                    VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, 0, {vsom_member(c->sg_inv, c->xpitch), vsom_member(c->sg_meta, 16)}));
-                    hipLaunchKernelGGL(sg_keep_record_kernel, dim3((c->xpitch + 255) / 256), dim3(256), 0, c->stream, c->cc_inv.p,
-                                       (int)c->xpitch, c->cc_meta.p, c->sg_inv.p, c->sg_meta.p);
-                }
+                // the M chains alone, from the c-only array; sigmaMap stays what it was until somebody may read it
+                // (vsom_internal.hpp, `sg`).  First the owned copies of what the materialisation needs and the staging and
+                // the search of the next chunk overwrite: the live-column record, lastBMU
+                hipLaunchKernelGGL(sg_keep_record_kernel, dim3((unsigned)((std::max<size_t>(compact ? c->xpitch : 0, c->B) + 255) / 256)),
+                                   dim3(256), 0, c->stream, c->cc_inv.p, compact ? (int)c->xpitch : 0, c->cc_meta.p, c->sg_inv.p,
+                                   c->sg_meta.p, c->lastbmu.p, (int)c->B, c->sg_bmu.p);
                 if ((rc = launch_nt_chains(c, c->upd_nt_mean[kernel], 0, c->N, c->B, ldn, c->xq_bpad, compact, c->cc_meta.p)))
                     return rc;
                 c->sg.on = true;
@@ -853,6 +914,7 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1, bool may_defe
                 c->sg.bpad = c->xq_bpad;
                 c->sg.compact = compact;
                 c->sg.kernel = kernel;
+                c->sg.sigma = sigma;
                 ++c->sg_stats[0];
             } else if ((rc = launch_nt_chains(c, c->upd_nt[kernel], n0, nloc, c->B, ldn, c->xq_bpad, compact, c->cc_meta.p))) {
                 return rc;
