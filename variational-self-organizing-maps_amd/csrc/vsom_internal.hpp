@@ -152,6 +152,8 @@ struct vsom_ctx {
     // hand-scheduled update kernel (code object loaded with hipModuleLoadData)
     void *upd_module = nullptr, *upd_clr8 = nullptr, *upd_nt[4] = {nullptr, nullptr, nullptr, nullptr};   // nt: std, fma, sfma, med
     void *upd_nt_mean[4] = {nullptr, nullptr, nullptr, nullptr};   // their M-only forms: mean, meanfma, mean, medmean
+    void *upd_nt_mean8[4] = {nullptr, nullptr, nullptr, nullptr};  // the same with two column quads per wavefront (`_nt8`)
+    bool mean_nt4 = false;          // development builds only (VSOM_MEAN_NT4): deferred epochs launch the `_nt4` forms at every size
     int update_mode = VSOM_UPDATE_STRICT;
     bool use_chain = true;
     bool use_tiny = true;           // one-launch epoch for tiny maps (VSOM_NO_TINY=1 disables, debugging)

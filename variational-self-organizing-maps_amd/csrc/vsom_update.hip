@@ -20,6 +20,10 @@
 //                  - vsom_update_{mean,meanfma,medmean}_nt4_gfx950: the same chains without S, for full-range
 //                    epochs whose sigmaMap stays pending ("pending sigma" below, vsom_internal.hpp); they never read w and
 //                    take the c-only form of the (c,w) array, which cwp_kernel writes for such an epoch
+//                  - vsom_update_{mean,meanfma,medmean}_nt8_gfx950: those with two column quads per wavefront (workgroup = 4
+//                    wavefronts over the same 64 nodes x 8 quads); what a deferred epoch launches unless the launch is small
+//                    (launch_phase2: at most two thirds of a 1024-workgroup round take the `_nt4` forms); development builds
+//                    force `_nt4` with VSOM_MEAN_NT4 for A/B runs.
 //                  - vsom_update_clr_rp8_gfx950 (gen_update_asm.py): CLR, lane = node, 8 parameter pairs per lane.
 //                  - update_chain3_kernel (HIP, below): maps too small to fill the chip with lane = node
 //                    (C4: 64x64x32): one lane per (node, dim pair) chain, operands staged through LDS.
@@ -541,7 +545,13 @@ int vsom_load_asm_module(vsom_ctx *c)
         const std::string n = std::string("vsom_update_") + mean_names[i] + "_nt4_gfx950";
         VSOM_HIP_CHECK(hipModuleGetFunction(&f, mod, n.c_str()));
         c->upd_nt_mean[i] = f;
+        const std::string n8 = std::string("vsom_update_") + mean_names[i] + "_nt8_gfx950";   // two column quads per wavefront
+        VSOM_HIP_CHECK(hipModuleGetFunction(&f, mod, n8.c_str()));
+        c->upd_nt_mean8[i] = f;
     }
+#ifdef VSOM_DEVELOPMENT
+    c->mean_nt4 = std::getenv("VSOM_MEAN_NT4") != nullptr;   // A/B: the deferred epochs on the one-quad mean-only kernels
+#endif
     c->upd_module = mod;
     return VSOM_OK;
 }
@@ -660,8 +670,10 @@ static int launch_cwp(vsom_ctx *c, const u64 *bmu, size_t B_, size_t n0, size_t 
 // ---- pending sigma (vsom_internal.hpp, vsom_ctx::sg) ------------------------------------------------------------
 // one launch of a lane = node Standard / Median chain kernel over the nodes [n0, n0 + nloc), from the operands of a chunk of
 // B rows: the one place that fills the kernarg, for the eager epoch, the mean-only epoch and the materialisation
+// (block: 512 threads = one column quad per wavefront, the `_nt4` kernels; 256 = two, the mean-only `_nt8` kernels: the same
+// 64 nodes x 8 quads per workgroup, so the same grid)
 static int launch_nt_chains(vsom_ctx *c, void *fn, size_t n0, size_t nloc, size_t B, size_t ldn, uint32_t bpad, bool compact,
-                            const unsigned *meta)
+                            const unsigned *meta, unsigned block = 512)
 {
     const unsigned gx = (unsigned)((nloc + 63) / 64);
     const unsigned cols = compact ? c->cpitch : c->pitch;
@@ -683,7 +695,7 @@ static int launch_nt_chains(vsom_ctx *c, void *fn, size_t n0, size_t nloc, size_
     a.zq = c->zq.p;
     size_t sz = 80;
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-    VSOM_HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)fn, 8 * ((quads + 7) / 8), (gx + 7) / 8, 1, 512, 1, 1, 0, c->stream,
+    VSOM_HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)fn, 8 * ((quads + 7) / 8), (gx + 7) / 8, 1, block, 1, 1, 0, c->stream,
                                          nullptr, extra));
     return VSOM_OK;
 }
@@ -906,7 +918,14 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1, bool may_defe
                 hipLaunchKernelGGL(sg_keep_record_kernel, dim3((unsigned)((std::max<size_t>(compact ? c->xpitch : 0, c->B) + 255) / 256)),
                                    dim3(256), 0, c->stream, c->cc_inv.p, compact ? (int)c->xpitch : 0, c->cc_meta.p, c->sg_inv.p,
                                    c->sg_meta.p, c->lastbmu.p, (int)c->B, c->sg_bmu.p);
-                if ((rc = launch_nt_chains(c, c->upd_nt_mean[kernel], 0, c->N, c->B, ldn, c->xq_bpad, compact, c->cc_meta.p)))
+                // Two column quads per wavefront (gen_nt_asm.py, K2) where the launch is more than two thirds of a round of
+                // 1024 workgroups; below, the one-quad form: a small launch leaves SIMDs short of wavefronts, and the two-quad
+                // form has half as many, each twice as long.  Measured (B = 4096 x 784 sparse, 21 column blocks, launch time
+                // one-quad -> two-quad, profiles/mean_nt8_small_launches.txt): 525 workgroups 0.310 -> 0.344 ms, 672 0.340 ->
+                // 0.343 (the step 0.488 -> 0.503), 756 0.590 -> 0.405, 1008 0.592 -> 0.491, 5376 (C3) 2.28 -> 1.86.
+                const bool two = !c->mean_nt4 && 3 * chain_wgs > 2 * 1024;
+                void *const fn = two ? c->upd_nt_mean8[kernel] : c->upd_nt_mean[kernel];
+                if ((rc = launch_nt_chains(c, fn, 0, c->N, c->B, ldn, c->xq_bpad, compact, c->cc_meta.p, two ? 256 : 512)))
                     return rc;
                 c->sg.on = true;
                 c->sg.B = c->B;
