@@ -193,6 +193,9 @@ int vsom_set_update_mode(vsom_ctx *ctx, int mode);
  * The environment variable VSOM_SIGMA_MODE (auto / eager / lazy) sets the initial mode at vsom_create; any other value
  * makes vsom_create fail with VSOM_ERR_INVALID.
  * vsom_sigma_flush enqueues the materialisation (a no-op when nothing is pending) and counts as a read.
+ * A call that is refused (VSOM_ERR_INVALID) changes no result; if it is not on the list above it may already have
+ * materialised a pending sigmaMap and counted as a read (its arguments and the staged rows are checked behind the entry
+ * check that materialises).
  * vsom_sigma_stats: out[0..3] = epochs deferred, records dropped, records materialised, 1 if one is pending now. */
 int vsom_set_sigma_mode(vsom_ctx *ctx, int mode);
 int vsom_sigma_flush(vsom_ctx *ctx);

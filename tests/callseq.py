@@ -8,17 +8,33 @@ The model is an oracle.pyoracle.OracleSom plus a record of what the header promi
 current chunk and its lastBMU, the pending (prefetched / device-staged) chunk, the last MSE and the online running
 accumulator.  Every accepted call must return the model's values bit for bit (NaN == NaN); a call that reads the staged
 rows while a chunk is pending may instead be refused (VSOM_ERR_INVALID naming the commit), which changes nothing.
+
+Two profiles.  "ingest" is the walk over the chunk pipeline (uploads, prefetches, commits, epochs whole and split, online
+chunks, searches).  "sigma" walks the pending sigmaMap (include/vsom_hip.h, vsom_set_sigma_mode): it sets a sigma mode,
+adds the flush, the column compaction, whole-map phase-2 ranges, empty chunks, the masked epoch, partial vsom_set_state
+calls, the sigmaMap readers and the arena queries, and holds by construction the runs in which a record stays pending
+across a stage-ahead and its commit, a lastBMU write, a reallocating upload, an empty chunk, an online chunk enqueued
+without a wait and a weight-only state write.  The model (SigmaRecord) restates the header's contract -- which calls leave
+a record pending, when AUTO defers, what vsom_sigma_stats counts -- and the walk compares all four numbers of
+vsom_sigma_stats after every accepted call; a refused call may have materialised the record or not, nothing else.  The
+oracle state never depends on the mode.  The real backend drives a second context fixed at VSOM_SIGMA_EAGER through the
+same calls: what the readers, the arena queries and the masked epoch return must equal that twin's output bit for bit
+(doubles on 64 bits), and the twin's own state is compared with the oracle at the end.  The masked epoch's model is
+tests/masked_train_ref.py (its phase 1 and phase 2) applied to the model's oracle state.
 """
 import ctypes as C
 
 import numpy as np
 
 import gen
+import masked_train_ref
 from oracle import pyoracle as po
 
 VSOM_ERR_INVALID = -1
 EXPONENTIAL, INVERSE_PROPORTIONAL = 0, 1
 BMU_AUTO, BMU_EXACT, BMU_SHORTLIST = 0, 1, 2
+SIGMA_AUTO, SIGMA_EAGER, SIGMA_LAZY = 0, 1, 2
+SIGMA_MODES = {"auto": SIGMA_AUTO, "eager": SIGMA_EAGER, "lazy": SIGMA_LAZY}
 NTHREADS = 16
 VSOM_CHAIN_MAX_WAVES = 448           # csrc/vsom_internal.hpp
 
@@ -27,22 +43,42 @@ VSOM_CHAIN_MAX_WAVES = 448           # csrc/vsom_internal.hpp
 CONFIGS = {
     "std48": dict(W=48, H=48, J=196, tr=po.STANDARD, custom=False,
                   chunks=[(1100, "u8"), (1280, "f"), (77, "u8"), (1500, "dense"), (4500, "u8"), (1024, "f")]),
+    # (sigma_weights: the sigma profile's draws alone.  Median's online scan and its masked search -- Python, a row of the
+    # 300-row shortest chunk at a time -- are the model's dearest ops: drawn less often there)
     "med48": dict(W=48, H=48, J=196, tr=po.MEDIAN, custom=False,
-                  chunks=[(1100, "u8"), (300, "dense"), (1536, "f"), (4500, "u8"), (1024, "u8")]),
+                  chunks=[(1100, "u8"), (300, "dense"), (1536, "f"), (4500, "u8"), (1024, "u8")],
+                  sigma_weights={"online": 1, "single": 1, "epoch_masked": 0.5}),
     "std12": dict(W=12, H=12, J=24, tr=po.STANDARD, custom=False,
                   chunks=[(300, "dense"), (128, "dense"), (77, "dense"), (1500, "dense")]),
     "clr12": dict(W=12, H=12, J=6, tr=po.CLR, custom=False,
                   chunks=[(300, "clr"), (128, "clr"), (77, "clr"), (700, "clr")]),
     "custom12": dict(W=12, H=12, J=24, tr=po.STANDARD, custom=True,
                      chunks=[(200, "dense"), (64, "dense"), (301, "dense")]),
+    # 100 node groups x 7 column blocks = 700 workgroups: a deferred whole-map launch takes the two-quad mean-only chains
+    # (two_quad_launch below).  The online scan and the single step cost N x D per sample on the oracle: drawn less often.
+    "std80": dict(W=80, H=80, J=196, tr=po.STANDARD, custom=False,
+                  chunks=[(320, "u8"), (77, "u8"), (512, "f"), (200, "dense")], weights={"online": 2, "single": 1}),
 }
 
 # ops that read the staged rows of the current chunk: the ones a pending chunk staged ahead may refuse
 READS_ROWS = {"bmu", "bmu_local", "bmu_restricted", "distances", "distances_row", "p1", "p2", "epoch", "epoch_async",
-              "online"}
+              "online", "epoch_masked", "similarity", "generate", "evaluate", "topk", "bmd", "bmu_masked",
+              "distances_raw"}       # (distances_raw: against chunk rows, not from_map)
 OBSERVE = {"get_state", "get_last_bmu", "get_sqres", "get_mse"}
 # what a custom context refuses (include/vsom_hip.h, vsom_create_custom)
-CUSTOM_REFUSED = {"stage", "p1", "finish", "p2", "bmu_restricted", "distances_row"}
+CUSTOM_REFUSED = {"stage", "p1", "finish", "p2", "bmu_restricted", "distances_row", "epoch_masked", "similarity",
+                  "generate", "decode_nodes", "distances_raw", "umatrix", "evaluate", "topk", "bmd", "bmu_masked",
+                  "compaction"}
+# what a CLR context refuses (vsom_bmu_masked_batch, vsom_batch_epoch_masked: Standard / Median only)
+CLR_REFUSED = {"bmu_masked", "epoch_masked"}
+# the calls that leave a pending sigmaMap pending, "and no others" (include/vsom_hip.h, vsom_set_sigma_mode); a whole-map
+# epoch drops it, a partial phase-2 range materialises it
+SIGMA_KEEP = {"upload", "upload_empty", "prefetch", "stage", "commit", "p1", "finish", "p2", "epoch", "epoch_async",
+              "get_mse", "get_last_bmu", "set_last_bmu", "get_sqres", "bmu_mode", "sigma_mode", "compaction"}
+READERS = ("similarity", "generate", "decode_nodes", "distances_raw", "umatrix", "evaluate")
+ARENA = ("topk", "bmd", "bmu_masked")
+# what the real backend checks against its EAGER twin, bit for bit
+TWIN_COMPARED = set(READERS) | set(ARENA) | {"epoch_masked"}
 
 
 def chunk_data(cfg_name, seed, scale=1):
@@ -80,6 +116,21 @@ def stages_ahead(cfg):
     return c is not None and cfg["W"] * cfg["H"] > c
 
 
+def defers(cfg):
+    """whether a whole-map epoch of this configuration may leave its sigmaMap pending: Standard / Median on the lane = node
+    kernels, at a depth that is a multiple of 4 (so that it does not matter whether the column compaction applied)"""
+    return stages_ahead(cfg) and po.length(cfg["tr"], cfg["J"]) % 4 == 0
+
+
+def two_quad_launch(cfg):
+    """mirror of the launch rule of the mean-only chains (csrc/vsom_update.hip, launch_phase2): workgroups = node groups of
+    64 x blocks of 8 column quads; the two-quad kernels where 3 * workgroups > 2 * 1024.  (With the compaction the quads
+    come from the compacted pitch, which is fixed per context: the depth rounded up to 32 columns.)"""
+    D = po.length(cfg["tr"], cfg["J"])
+    wgs = ((cfg["W"] * cfg["H"] + 63) // 64) * (((D + 3) // 4 + 7) // 8)
+    return wgs, 3 * wgs > 2 * 1024
+
+
 def initial_map(cfg_name, seed):
     cfg = CONFIGS[cfg_name]
     D = po.length(cfg["tr"], cfg["J"])
@@ -93,8 +144,11 @@ def initial_map(cfg_name, seed):
 
 # ---- generator ---------------------------------------------------------------------------------------------------------
 class _Gen:
-    def __init__(self, cfg_name, seed, scale):
+    def __init__(self, cfg_name, seed, scale, profile="ingest", mode="lazy"):
         self.cfg = CONFIGS[cfg_name]
+        self.profile = profile
+        self.walk_mode = self.mode = mode  # sigma profile: the mode the required runs need, the mode in force
+        self.last_sigma = None
         self.rs = np.random.RandomState(seed)
         self.sizes = [max(8, b // scale) for b, _ in self.cfg["chunks"]]
         self.N = self.cfg["W"] * self.cfg["H"]
@@ -113,6 +167,10 @@ class _Gen:
         self.ops.append((name, p))
         if name == "upload":
             self.B = self.sizes[p["chunk"]]
+        elif name == "upload_empty":
+            self.B = 0
+        elif name == "sigma_mode":
+            self.mode = p["mode"]
         elif name in ("prefetch", "stage"):
             self.pending = p["chunk"]
         elif name == "commit" and self.pending is not None:
@@ -120,8 +178,10 @@ class _Gen:
             self.pending = None
         if name == "online":
             self.chain = self.pending is None       # (with a chunk pending the call may be refused)
-        elif name in ("single", "epoch", "epoch_async", "p1", "finish", "p2"):
+        elif name in ("single", "epoch", "epoch_async", "p1", "finish", "p2", "epoch_masked"):
             self.chain = False
+        if "sigma" in p and name != "online":
+            self.last_sigma = p["sigma"]
 
     def next_chunk(self):
         return self.r(len(self.sizes))
@@ -141,8 +201,9 @@ class _Gen:
         self.emit("online", eta=float(self.rs.choice([0.05, 0.2])), sigma=self.sigma(),
                   decay=self.r(2), first=first, mode=mode)
 
-    def split(self, interleave=False, end_with_commit=False):
-        """phase 1 over a random partition of the rows, finish, phase 2 over a random partition of the nodes"""
+    def split(self, interleave=False, end_with_commit=False, whole=False):
+        """phase 1 over a random partition of the rows, finish, phase 2 over a random partition of the nodes (whole: over
+        exactly [0, N), which the header counts as a whole-map epoch)"""
         if interleave and stages_ahead(self.cfg):
             self.emit("upload", chunk=0, asynchronous=False)     # (not the short chunk staged ahead below)
         first = bool(self.r(2))
@@ -153,11 +214,14 @@ class _Gen:
             self.emit("p1", s0=int(s0), s1=int(s1), first=first)
         self.emit("finish")
         sg = self.sigma()
-        if interleave and stages_ahead(self.cfg):
+        if whole:
+            self.emit("p2", sigma=sg, n0=0, n1=self.N)
+        elif interleave and stages_ahead(self.cfg):
             # a range large enough for the lane = node kernels, a short next chunk staged ahead behind it, then ranges
             # small enough for the chain kernel, which must not read the rows that staging overwrote
             c = chain_max_nodes(self.cfg)
-            big = c + 1 + self.r(min(64, self.N - c - 1))
+            # (on a map of more than 2 c nodes the first range is longer, so that what is left fits the chain kernel)
+            big = max(c + 1, self.N - c) + self.r(min(64, self.N - c - 1))
             sg = 12.0                       # (a wide neighbourhood: every node of the chain ranges feels every sample)
             cuts = sorted(set([big, self.N] + [big + self.r(self.N - big) for _ in range(self.r(3))]))
             rest = list(zip(cuts[:-1], cuts[1:]))
@@ -183,8 +247,22 @@ class _Gen:
                    "bmu_restricted", "distances", "distances_row", "set_last_bmu", "get_last_bmu", "get_sqres",
                    "get_mse", "bmu_mode", "set_state", "get_state"]
         w = np.array([3, 4, 4, 4, 3, 2, 5, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 2, 1, 1], np.float64)
+        if self.profile == "sigma":
+            w[choices.index("epoch_async")], w[choices.index("epoch")] = 6, 5
+            w[choices.index("online")] = 2         # (the oracle's serial scan: the ingest profile's subject, not this one's)
+            more = ["sigma_mode", "sigma_flush", "compaction", "whole_p2", "upload_empty", "epoch_masked", "topk", "bmd",
+                    "bmu_masked"] + list(READERS)
+            choices = choices + more
+            w = np.concatenate([w, [2, 1, 1, 3, 1, 1, 1, 1, 1] + [1] * len(READERS)])
+        for k, v in cfg.get("weights", {}).items():
+            w[choices.index(k)] = v
+        if self.profile == "sigma":
+            for k, v in cfg.get("sigma_weights", {}).items():
+                w[choices.index(k)] = v
         if cfg["custom"]:
             w[choices.index("bmu_mode")] = 0
+            if "compaction" in choices:
+                w[choices.index("compaction")] = 0     # (refused: the custom path has no compaction)
         what = choices[int(self.rs.choice(len(choices), p=w / w.sum()))]
         if what == "upload":
             self.emit("upload", chunk=self.next_chunk(), asynchronous=bool(self.r(2)))
@@ -198,7 +276,8 @@ class _Gen:
             if self.pending is None:       # (a refusal inside phase 1 would leave a half-searched chunk to the finish)
                 self.split()
         elif what == "online":
-            self.online()
+            if self.profile == "ingest" or self.B <= 512:      # (Median's scan of 1024 rows: 5 s on the oracle)
+                self.online()
         elif what == "single":
             self.emit("single", seed=self.r(1 << 30), eta=0.1, sigma=self.sigma(), decay=self.r(2),
                       last=self.r(self.N))
@@ -214,17 +293,183 @@ class _Gen:
         elif what == "bmu_mode":
             self.emit(what, mode=self.r(3))
         elif what == "set_state":
-            self.emit(what, seed=self.r(1 << 30), parts=["map", "msw", "all"][self.r(3)])
+            parts = ["map", "msw", "all"] + (["map_only", "weight_only"] if self.profile == "sigma" else [])
+            self.emit(what, seed=self.r(1 << 30), parts=parts[self.r(len(parts))])
+        elif what == "sigma_mode":
+            self.emit(what, mode=["auto", "eager", "lazy"][self.r(3)])
+        elif what == "compaction":
+            self.emit(what, min_rows=int(self.rs.choice([1, -1, 1024])))
+        elif what == "whole_p2":
+            if self.pending is None:
+                self.split(whole=True)
+        elif what == "upload_empty":
+            self.empty_chunk_epoch()
+            self.emit("upload", chunk=self.next_chunk(), asynchronous=False)
+        elif what == "epoch_masked":
+            self.masked_epoch()
+        elif what in READERS or what in ARENA:
+            self.query(what)
         else:
             self.emit(what)
 
+    # ---- the sigma profile ----
+    def window(self):
+        """a row window of at most 64 rows"""
+        n = 1 + self.r(min(64, self.B))
+        r0 = self.r(self.B - n + 1)
+        return dict(r0=r0, r1=r0 + n)
 
-def generate(cfg_name, seed, n_ops=40, scale=1):
-    """A walk of about n_ops ops.  By construction it holds each of these runs with no synchronising call inside:
+    def query(self, what):
+        seed = self.r(1 << 30)
+        if what == "similarity":
+            # (the model's restricted search is a Python loop over the chunk's rows, as for bmu_restricted)
+            self.emit(what, min_hits=self.r(2) if self.B <= 1100 else 0, rule=self.r(2), **self.window())
+        elif what in ("generate", "bmd", "bmu_masked"):
+            self.emit(what, min_hits=self.r(2), rule=self.r(2), seed=seed, **self.window())
+        elif what == "evaluate":
+            self.emit(what, seed=seed, **self.window())
+        elif what == "topk":
+            self.emit(what, k=1 + self.r(8), **self.window())
+        elif what == "decode_nodes":
+            self.emit(what, count=1 + self.r(64), seed=seed)
+        elif what == "distances_raw":
+            self.emit(what, count=1 + self.r(64), seed=seed, from_map=bool(self.r(2)))
+        else:
+            self.emit(what)
+
+    def reader(self):
+        self.query(READERS[self.r(len(READERS))])
+
+    def small(self):
+        """one of the shorter chunks (never the largest)"""
+        order = np.argsort(self.sizes, kind="stable")
+        return int(order[self.r(max(1, len(order) // 2))])
+
+    def masked_epoch(self):
+        # the masked search of the model is pure Python, a row at a time: on the shortest chunk
+        if self.pending is not None:
+            self.emit("commit")
+        self.emit("upload", chunk=int(np.argmin(self.sizes)), asynchronous=False)
+        self.emit("epoch_masked", sigma=self.sigma(), first=bool(self.r(2)), seed=self.r(1 << 30))
+
+    def empty_chunk_epoch(self):
+        if self.pending is not None:
+            self.emit("commit")
+        self.emit("upload_empty")
+        self.emit(["epoch", "epoch_async"][self.r(2)], sigma=self.sigma(), first=bool(self.r(2)))
+
+    def whole_epoch(self, kinds=("epoch_async", "epoch", "p2")):
+        kind = kinds[self.r(len(kinds))]
+        if kind == "p2" and not self.cfg["custom"]:        # (a custom context refuses the split phases)
+            self.split(whole=True)
+        else:
+            self.emit("epoch" if kind == "epoch" else "epoch_async", sigma=self.sigma(), first=bool(self.r(2)))
+
+    def pending_epoch(self, kinds=("epoch_async", "epoch", "p2")):
+        """a whole-map epoch that leaves its sigmaMap pending where the configuration defers: in the walk's mode -- under
+        AUTO behind two whole-map epochs with nothing between them"""
+        if self.mode != self.walk_mode:
+            self.emit("sigma_mode", mode=self.walk_mode)
+        if self.walk_mode == "auto":
+            self.whole_epoch(("epoch_async",))
+            self.whole_epoch(("epoch_async",))
+        self.whole_epoch(kinds)
+
+    def sigma_run(self, run):
+        if self.pending is not None:
+            self.emit("commit")
+        short = int(np.argmin(self.sizes))
+        self.emit("upload", chunk=short if run == 4 else self.small(), asynchronous=False)
+        if run == 0:
+            # (an asynchronous epoch or a whole-map range: what a prefetch right behind it stages ahead of)
+            self.pending_epoch(("epoch_async", "p2"))
+            self.give(chunk=short)
+            self.emit("commit")
+            self.reader()
+        elif run == 1:
+            self.pending_epoch()
+            self.emit("set_last_bmu", seed=self.r(1 << 30))
+            sg = self.sigma()
+            while sg == self.last_sigma:
+                sg = self.sigma()
+            n0 = 1 + self.r(self.N - 1)
+            self.emit("p2", sigma=sg, n0=n0, n1=n0 + 1 + self.r(self.N - n0))
+        elif run == 2:
+            self.pending_epoch()
+            self.emit("upload", chunk=int(np.argmax(self.sizes)), asynchronous=bool(self.r(2)))
+            self.emit("sigma_flush")
+        elif run == 3:
+            self.pending_epoch()
+            self.empty_chunk_epoch()
+            self.emit("get_state")
+            self.emit("upload", chunk=self.small(), asynchronous=False)
+        elif run == 4:
+            self.pending_epoch()
+            self.online(mode="null")
+        elif run == 5:
+            self.pending_epoch()
+            self.emit("set_state", seed=self.r(1 << 30), parts="weight_only")
+        else:
+            if self.mode != self.walk_mode:
+                self.emit("sigma_mode", mode=self.walk_mode)
+            for _ in range(3):
+                self.whole_epoch()
+                keep = self.r(4)
+                if keep == 0:
+                    self.emit("get_mse")
+                elif keep == 1:
+                    self.emit("get_last_bmu")
+                elif keep == 2:
+                    self.emit("upload", chunk=self.small(), asynchronous=bool(self.r(2)))
+                else:
+                    self.give(chunk=self.small())
+                    self.emit("commit")
+            self.reader()
+        self.emit("get_state")
+
+
+def generate_sigma(cfg_name, seed, n_ops, scale, mode):
+    """The sigma profile.  By construction the walk holds each of these runs, with no materialising call before its end
+    (E: a whole-map epoch that leaves its sigmaMap pending where the configuration defers -- under AUTO the third of three):
+    E -> prefetch / stage_next_device (staged ahead where the configuration stages ahead) -> commit -> reader;
+    E -> set_last_bmu -> partial phase-2 range at another sigma;
+    E -> upload of the largest chunk -> sigma_flush;
+    E -> upload_empty -> epoch -> get_state;
+    E -> online chunk (mse NULL) -> get_state;
+    E -> weight-only set_state -> get_state;
+    three whole-map epochs with a call that keeps the record behind each (get_mse, get_last_bmu, an upload, a prefetch and
+    its commit) -> reader."""
+    assert mode in ("lazy", "auto"), mode
+    g = _Gen(cfg_name, seed, scale, "sigma", mode)
+    g.ops.append(("config", {"name": cfg_name, "seed": seed, "scale": scale, "profile": "sigma", "mode": mode}))
+    g.emit("sigma_mode", mode=mode)
+    g.emit("set_state", seed=seed, parts="init")
+    g.emit("upload", chunk=0, asynchronous=False)
+    slots = sorted(g.rs.choice(np.arange(3, n_ops - 4), 7, replace=False))
+    runs = list(g.rs.permutation(7))
+    k = 3
+    while k < n_ops:
+        if slots and k >= slots[0]:
+            slots.pop(0)
+            g.sigma_run(runs.pop(0))
+            k += 2
+            continue
+        g.random_op()
+        k += 1
+    g.emit("get_state")
+    return g.ops
+
+
+def generate(cfg_name, seed, n_ops=40, scale=1, profile="ingest", mode="lazy"):
+    """A walk of about n_ops ops.  profile="sigma": generate_sigma, in `mode` ("lazy" / "auto").  profile="ingest": by
+    construction it holds each of these runs with no synchronising call inside:
     async epoch -> online chunk (mse NULL) -> prefetch / stage_next_device -> commit;
     phase-2 range -> prefetch -> phase-2 range(s) -> commit (where a prefetch stages ahead: a lane = node range, a short
     chunk staged behind it, chain-kernel ranges);
     async epoch -> prefetch -> prefetch (an abandoned stage-ahead) -> search -> commit."""
+    if profile == "sigma":
+        return generate_sigma(cfg_name, seed, n_ops, scale, mode)
+    assert profile == "ingest", profile
     g = _Gen(cfg_name, seed, scale)
     g.ops.append(("config", {"name": cfg_name, "seed": seed, "scale": scale}))
     g.emit("set_state", seed=seed, parts="init")
@@ -276,7 +521,9 @@ class Refused(Exception):
 
 def _rand_state(cfg_name, seed, parts, N, D):
     rs = np.random.RandomState(seed)
-    st = {"map": initial_map(cfg_name, seed)}
+    if parts == "weight_only":
+        return {"weight": (rs.rand(N) * 10 + 0.5).astype(np.float32)}
+    st = {"map": initial_map(cfg_name, seed)}      # ("map", "map_only": the map alone)
     if parts in ("msw", "all"):
         st["sigma"] = (rs.rand(N, D) * 0.5).astype(np.float32)
         st["S"] = (rs.rand(N, D) * 2).astype(np.float32)
@@ -308,15 +555,98 @@ def materialize(op, model):
         return {"idx": np.random.RandomState(p["seed"]).randint(0, N, size=B).astype(np.uint64)}
     if name == "set_state":
         return _rand_state(model.cfg_name, p["seed"], p["parts"], N, po.length(cfg["tr"], cfg["J"]))
+    J = cfg["J"]
+    cols = min(J, po.length(cfg["tr"], J))
+    rs = np.random.RandomState(p.get("seed", 0))
+    n = p.get("r1", 0) - p.get("r0", 0)
+    if name == "upload_empty":
+        return {"X": np.zeros((0, J), np.float32)}
+    if name == "epoch_masked":
+        return {"valid": (rs.rand(B, J) < 0.8).astype(np.uint8)}
+    if name == "bmu_masked":
+        return {"valid": (rs.rand(n, J) < 0.8).astype(np.uint8)}
+    if name == "generate":
+        return {"u": rs.rand(n), "l": 0.05 + 0.9 * rs.rand(n, cols)}
+    if name == "bmd":
+        return {"u": rs.rand(n)}
+    if name == "decode_nodes":
+        return {"nodes": rs.randint(0, N, size=p["count"]).astype(np.uint64), "l": 0.05 + 0.9 * rs.rand(p["count"], cols)}
+    if name == "distances_raw":
+        return {"nodes": rs.randint(0, N, size=p["count"]).astype(np.uint64),
+                "vrows": rs.randint(0, N if p["from_map"] else max(B, 1), size=p["count"]).astype(np.uint64)}
+    if name == "evaluate":
+        binary = (rs.rand(J) < 0.3).astype(np.float32)
+        return {"binary": binary, "continuous": (1 - binary).astype(np.float32)}
     return {}
+
+
+class SigmaRecord:
+    """The pending sigmaMap as include/vsom_hip.h states it (vsom_sigma_mode, vsom_set_sigma_mode): the mode, the whole-map
+    epochs since the last call that may have read sigmaMap, whether a record is pending, and vsom_sigma_stats' counters.
+    Two points the header leaves open are pinned to what csrc/vsom_capi.hip and launch_phase2 do: a partial phase-2 range
+    materialises without counting as a read (the header lists it among the calls that never read sigmaMap), and a refused
+    call that is not on the keep list counts as a read (the header: it "may")."""
+
+    def __init__(self, cfg):
+        self.can_defer = defers(cfg) and not cfg["custom"] and cfg["tr"] != po.CLR
+        self.mode = SIGMA_AUTO
+        self.unread = 0
+        self.pending = False
+        self.deferred = self.dropped = self.materialised = 0
+
+    def stats(self):
+        return (self.deferred, self.dropped, self.materialised, int(self.pending))
+
+    def read(self):
+        """an entry point that is not on the header's list: materialises, and counts as a read"""
+        self.unread = 0
+        if self.pending:
+            self.pending = False
+            self.materialised += 1
+
+    def accepted(self, op, B, N):
+        name, p = op
+        if name == "sigma_mode":
+            self.mode = SIGMA_MODES[p["mode"]]
+        whole = name in ("epoch", "epoch_async") or (name == "p2" and p["n0"] == 0 and p["n1"] == N)
+        if whole:
+            if self.pending:                 # the epoch overwrites every row
+                self.pending = False
+                self.dropped += 1
+            if self.can_defer and B > 0 and (self.mode == SIGMA_LAZY or (self.mode == SIGMA_AUTO and self.unread >= 2)):
+                self.pending = True
+                self.deferred += 1
+            self.unread += 1
+        elif name == "p2":
+            if self.pending and p["n1"] > p["n0"]:     # a partial range materialises (and is no read)
+                self.pending = False
+                self.materialised += 1
+        elif name not in SIGMA_KEEP:
+            self.read()
+
+    def refused(self, op, got):
+        """A refused call may have materialised the record before it was refused, or not: the header does not say.  Returns
+        whether `got` (vsom_sigma_stats after the call) is one of the two, and adopts it.  Whether such a call counted as a
+        read the counters cannot show when nothing was pending: the model takes it as one, as the library's entry check
+        does (include/vsom_hip.h allows both); were that to change, the AUTO walks would report a deferral one epoch off."""
+        before = self.stats()
+        if op[0] not in SIGMA_KEEP:
+            self.unread = 0
+        if tuple(got) == before:
+            return True
+        if self.pending and tuple(got) == (before[0], before[1], before[2] + 1, 0):
+            self.pending = False
+            self.materialised += 1
+            return True
+        return False
 
 
 class Model:
     """what the header says the context holds after each call"""
 
-    def __init__(self, cfg_name, seed, scale=1):
+    def __init__(self, cfg_name, seed, scale=1, profile="ingest"):
         cfg = CONFIGS[cfg_name]
-        self.cfg_name, self.cfg = cfg_name, cfg
+        self.cfg_name, self.cfg, self.profile = cfg_name, cfg, profile
         self.som = po.OracleSom(cfg["W"], cfg["H"], cfg["J"], cfg["tr"])
         self.N = cfg["W"] * cfg["H"]
         self.chunks = chunk_data(cfg_name, seed, scale)
@@ -327,6 +657,7 @@ class Model:
         self.pending = None
         self.mse = None                        # last MSE (None: nothing has written one yet)
         self.run = None                        # online running accumulator after the last online chunk
+        self.sig = SigmaRecord(cfg)
 
     @property
     def B(self):
@@ -344,15 +675,45 @@ class Model:
     def _dist(self, nodes, rows):
         return np.array([self.som.dist(int(n), self.X[int(r)]) for n, r in zip(nodes, rows)], np.float32)
 
-    def refusal_allowed(self, name):
+    def refusal_allowed(self, name, p=None):
+        if name == "distances_raw" and p["from_map"]:
+            return False
         return name in READS_ROWS and self.pending is not None
+
+    def _search_chunk(self, min_hits):
+        """what vsom_similarity_batch / vsom_evaluate_batch leave behind: they search the WHOLE chunk, as vsom_bmu_batch
+        (min_hits 0) or vsom_bmu_restricted_batch does, and score the rows of the window"""
+        if min_hits:
+            self.lb[:] = [self.som.find_restricted_bmu(x, min_hits) for x in self.X]
+        else:
+            self.som.batch_phase1_range(self.X, 0, self.B, self.lb, self.sq, True, nthreads=NTHREADS)
+        self.sqres = self._dist(self.lb, np.arange(self.B))
+
+    def _epoch_masked(self, p, valid):
+        """tests/masked_train_ref.py (MaskedOracle.epoch) on this model's state"""
+        s, cfg = self.som, self.cfg
+        valid = valid != 0
+        lb, sq = masked_train_ref.phase1(cfg["tr"], cfg["W"], cfg["H"], s.map, self.X, valid, self.lb, p["first"])
+        mse = s.batch_phase1_finish(lb, sq) if self.B else np.float32(0)
+        newmap, newsig, weight = masked_train_ref.phase2(cfg["tr"], cfg["W"], cfg["H"], self.X, valid, lb, p["sigma"])
+        s.set_state(map=newmap, sigma=newsig, weight=weight)
+        self.lb[...] = lb
+        self.sqres = None
+        return mse
 
     def apply(self, op, a):
         """the op's effect; returns the outputs the call must give"""
         name, p = op
         s = self.som
-        if name == "upload":
+        if name in ("upload", "upload_empty"):
             self._load(a["X"])
+        elif name == "epoch_masked":
+            self.mse = self._epoch_masked(p, a["valid"])
+            return {"mse": self.mse}
+        elif name == "similarity":
+            self._search_chunk(p["min_hits"])
+        elif name == "evaluate":
+            self._search_chunk(0)
         elif name in ("prefetch", "stage"):
             self.pending = a["X"]
         elif name == "commit":
@@ -434,6 +795,24 @@ def first_difference(got, exp):
     return f"element {tuple(int(i) for i in at)}: got {g[at]!r}, expected {e[at]!r} ({int((~same).sum())} differ)"
 
 
+def first_difference_exact(got, exp):
+    """the same on the values' own width (doubles on 64 bits); None values must be None on both sides"""
+    if got is None or exp is None:
+        return None if got is exp else f"got {type(got).__name__}, expected {type(exp).__name__}"
+    g, e = np.asarray(got), np.asarray(exp)
+    if g.shape != e.shape or g.dtype != e.dtype:
+        return f"shape / type {g.shape} {g.dtype} != {e.shape} {e.dtype}"
+    same = g == e
+    if e.dtype.kind == "f":
+        same = same & (np.signbit(g) == np.signbit(e)) | (np.isnan(g) & np.isnan(e))
+    if np.all(same):
+        return None
+    same = np.atleast_1d(same)
+    at = np.unravel_index(int(np.argmin(same.reshape(-1))), same.shape)
+    return (f"element {tuple(int(i) for i in at)}: got {np.atleast_1d(g)[at]!r}, expected {np.atleast_1d(e)[at]!r} "
+            f"({int((~same).sum())} differ)")
+
+
 class WalkFailure(AssertionError):
     pass
 
@@ -443,7 +822,8 @@ def run_walk(ops, make_backend):
     the ops up to the failing one and the first differing element.  Returns counts of what happened."""
     name0, cfg = ops[0]
     assert name0 == "config", ops[0]
-    model = Model(cfg["name"], cfg["seed"], cfg.get("scale", 1))
+    sigma = cfg.get("profile", "ingest") == "sigma"
+    model = Model(cfg["name"], cfg["seed"], cfg.get("scale", 1), cfg.get("profile", "ingest"))
     be = make_backend(cfg["name"], model)
     stats = {"ops": 0, "refused": 0}
     done = [ops[0]]
@@ -458,11 +838,26 @@ def run_walk(ops, make_backend):
             if d:
                 fail(f"{what}: output {k!r} differs from the oracle at {d}")
 
-    def check_all(what):
-        got = be.observe()
+    def check_all(what, observe=None):
+        got = (observe or be.observe)()
         exp = model.state()
         exp.update(lb=model.lb, mse=model.mse)
         check_outputs(f"{what} (full state)", got, exp)
+
+    def check_sigma(op, out, refused):
+        """vsom_sigma_stats after the call against the header's contract (SigmaRecord)"""
+        if not sigma:
+            return
+        got = tuple(int(v) for v in out["sigma_stats"])
+        stats["sigma"] = got
+        if refused:
+            before = model.sig.stats()
+            if not model.sig.refused(op, got):
+                fail(f"{op[0]} was refused and left vsom_sigma_stats = {got}: neither unchanged from {before} nor one more "
+                     f"record materialised and none pending")
+        elif got != model.sig.stats():
+            fail(f"{op[0]}: vsom_sigma_stats = {got}, the header's contract gives {model.sig.stats()} "
+                 f"(deferred, dropped, materialised, pending)")
 
     try:
         for op in ops[1:]:
@@ -471,24 +866,40 @@ def run_walk(ops, make_backend):
             a = materialize(op, model)
             rc, msg, out = be.call(op, a)
             stats["ops"] += 1
+            if out.get("twin_diff"):
+                fail(f"{name}: {out['twin_diff']}")
             if model.cfg["custom"] and name in CUSTOM_REFUSED:
                 if rc != VSOM_ERR_INVALID:
                     fail(f"{name} on a custom context returned {rc}, not VSOM_ERR_INVALID")
+                check_sigma(op, out, True)
+                continue
+            if model.cfg["tr"] == po.CLR and name in CLR_REFUSED:
+                if rc != VSOM_ERR_INVALID:
+                    fail(f"{name} on a CLR context returned {rc}, not VSOM_ERR_INVALID")
+                check_sigma(op, out, True)
                 continue
             if name == "commit" and model.pending is None:
                 if rc != VSOM_ERR_INVALID:
                     fail(f"commit with nothing pending returned {rc}")
+                check_sigma(op, out, True)
                 continue
             if rc != 0:
-                if rc == VSOM_ERR_INVALID and "commit" in msg and model.refusal_allowed(name):
+                if rc == VSOM_ERR_INVALID and "commit" in msg and model.refusal_allowed(name, p):
                     stats["refused"] += 1
+                    check_sigma(op, out, True)
                     continue
                 fail(f"{name} failed: {rc} {msg}")
+            model.sig.accepted(op, model.B, model.N)
             exp = model.apply(op, a)
             check_outputs(name, out, exp)
-            if name in OBSERVE:
+            check_sigma(op, out, False)
+            # (the full state is read through vsom_get_state, which materialises: in the sigma profile only where the
+            # op itself has just done so)
+            if name in OBSERVE and (not sigma or name == "get_state"):
                 check_all(name)
         check_all("end of walk")
+        if sigma and hasattr(be, "observe_twin"):
+            check_all("end of walk, the EAGER twin", be.observe_twin)
     finally:
         be.close()
         model.close()
@@ -508,11 +919,17 @@ class GpuBackend:
         cfg = CONFIGS[cfg_name]
         if cfg["custom"]:
             depth, rlen = custom_hooks.shape("standard", cfg["J"])
-            self.ctx = capi.Context(cfg["W"], cfg["H"], cfg["J"], capi.CUSTOM, source=custom_hooks.STANDARD,
-                                    depth=depth, residual_len=rlen)
+            make = lambda: capi.Context(cfg["W"], cfg["H"], cfg["J"], capi.CUSTOM, source=custom_hooks.STANDARD,
+                                        depth=depth, residual_len=rlen)
         else:
-            self.ctx = vsom_amd.Context(cfg["W"], cfg["H"], cfg["J"], cfg["tr"])
-        self.h = self.ctx._h
+            make = lambda: vsom_amd.Context(cfg["W"], cfg["H"], cfg["J"], cfg["tr"])
+        self.ctx = make()
+        # sigma profile: a second context fixed at VSOM_SIGMA_EAGER that receives every call of the walk
+        self.sigma = model.profile == "sigma"
+        self.twin = None
+        if self.sigma:
+            self.twin = make()
+            self.twin.set_sigma_mode(SIGMA_EAGER)
         self.N, self.D = self.ctx.n_nodes, self.ctx.depth
         # pinned and device copies of every chunk, made up front: an allocation inside the walk (hipHostMalloc,
         # hipMalloc + hipMemcpy) would synchronise the device and hide the asynchrony the walk is about
@@ -529,20 +946,81 @@ class GpuBackend:
 
     def close(self):
         self.ctx.close()
+        if self.twin is not None:
+            self.twin.close()
         for pb in self.pinned:
             pb.free()
         for p in self.dev:
             self.hip.hipFree(p)
 
-    def B(self):
-        return int(self.L.vsom_chunk_size(self.h))
-
     def call(self, op, a):
-        L, h, capi = self.L, self.h, self.capi
+        rc, msg, out = self._call(self.ctx, op, a)
+        if self.sigma:
+            name = op[0]
+            trc, _, tout = self._call(self.twin, op, a)
+            if name == "sigma_mode":                   # (the twin stays eager)
+                self.twin.set_sigma_mode(SIGMA_EAGER)
+            if trc != rc:
+                out["twin_diff"] = f"returned {rc}, the EAGER twin {trc}"
+            elif rc == 0 and name in TWIN_COMPARED:
+                for k in tout:
+                    d = first_difference_exact(out.get(k), tout[k])
+                    if d:
+                        out["twin_diff"] = f"output {k!r} differs from the EAGER twin's at {d}"
+                        break
+            out["sigma_stats"] = tuple(self.ctx.sigma_stats()[k] for k in ("deferred", "dropped", "materialised", "pending"))
+        return rc, msg, out
+
+    def _wrapped(self, fn, *args, **kw):
+        """a call through the Python wrapper: (rc, what it returned as a dict)"""
+        try:
+            res = fn(*args, **kw)
+        except self.capi.VsomError as e:
+            return int(str(e).split("error ", 1)[1].split(":", 1)[0]), {}
+        if isinstance(res, tuple):
+            res = {f"r{i}": v for i, v in enumerate(res)}
+        elif not isinstance(res, dict):
+            res = {"r0": res}
+        return 0, res
+
+    def _call(self, ctx, op, a):
+        L, h, capi = self.L, ctx._h, self.capi
         f, u = capi._f, capi._u
         name, p = op
         out = {}
-        if name == "upload":
+        B = int(L.vsom_chunk_size(h))
+        if name in ("similarity", "generate", "evaluate", "topk", "bmd", "bmu_masked"):
+            w = dict(r0=p["r0"], r1=p["r1"])
+        if name == "sigma_mode":
+            rc = L.vsom_set_sigma_mode(h, SIGMA_MODES[p["mode"]])
+        elif name == "sigma_flush":
+            rc = L.vsom_sigma_flush(h)
+        elif name == "compaction":
+            rc = L.vsom_set_column_compaction(h, C.c_long(p["min_rows"]))
+        elif name == "upload_empty":
+            rc = L.vsom_upload_chunk(h, f(a["X"]), 0)
+        elif name == "epoch_masked":
+            rc, out = self._wrapped(ctx.batch_epoch_masked, p["sigma"], p["first"], a["valid"])
+            out = {"mse": out.get("r0")}
+        elif name == "similarity":
+            rc, out = self._wrapped(ctx.similarity, p["min_hits"], 2, p["rule"], delta=True, **w)
+        elif name == "generate":
+            rc, out = self._wrapped(ctx.generate, p["min_hits"], a["u"], a["l"], p["rule"], **w)
+        elif name == "decode_nodes":
+            rc, out = self._wrapped(ctx.decode_nodes, a["nodes"], a["l"])
+        elif name == "distances_raw":
+            rc, out = self._wrapped(ctx.distances_raw, a["nodes"], a["vrows"], p["from_map"])
+        elif name == "umatrix":
+            rc, out = self._wrapped(ctx.umatrix)
+        elif name == "evaluate":
+            rc, out = self._wrapped(ctx.evaluate, a["binary"], a["continuous"], **w)
+        elif name == "topk":
+            rc, out = self._wrapped(ctx.bmu_topk, p["k"], **w)
+        elif name == "bmd":
+            rc, out = self._wrapped(ctx.restricted_bmd, p["min_hits"], u=a["u"], **w)
+        elif name == "bmu_masked":
+            rc, out = self._wrapped(ctx.bmu_masked, a["valid"], min_hits=p["min_hits"], fill=True, **w)
+        elif name == "upload":
             X = a["X"]
             if p["asynchronous"]:
                 X = self.pinned[p["chunk"]].array
@@ -571,7 +1049,7 @@ class GpuBackend:
         elif name == "online":
             m = C.c_float()
             if p["mode"] == "fetch":
-                lb = np.zeros(self.B(), np.uint64)
+                lb = np.zeros(B, np.uint64)
                 rc = L.vsom_train_online_chunk_fetch(h, p["eta"], p["sigma"], p["decay"], int(p["first"]), u(lb),
                                                      C.byref(m))
                 out["lb"] = lb
@@ -586,7 +1064,6 @@ class GpuBackend:
                                      C.byref(dist), C.byref(bmu))
             out.update(bmu=int(bmu.value), res=res, dist=np.float32(dist.value), last=int(lb.value))
         elif name in ("bmu", "bmu_local", "bmu_restricted"):
-            B = self.B()
             idx, dist = np.empty(B, np.uint64), np.empty(B, np.float32)
             if name == "bmu":
                 rc = L.vsom_bmu_batch(h, u(idx), f(dist))
@@ -606,11 +1083,11 @@ class GpuBackend:
         elif name == "set_last_bmu":
             rc = L.vsom_set_last_bmu(h, u(a["idx"]))
         elif name == "get_last_bmu":
-            lb = np.empty(self.B(), np.uint64)
+            lb = np.empty(B, np.uint64)
             rc = L.vsom_get_last_bmu(h, u(lb))
             out["lb"] = lb
         elif name == "get_sqres":
-            sq = np.empty(self.B(), np.float32)
+            sq = np.empty(B, np.float32)
             rc = L.vsom_get_sqres(h, f(sq))
             out["sq"] = sq
         elif name == "get_mse":
@@ -623,28 +1100,33 @@ class GpuBackend:
             g = lambda k: a.get(k)
             rc = L.vsom_set_state(h, f(g("map")), f(g("sigma")), f(g("S")), f(g("weight")), u(g("hits")))
         elif name == "get_state":
-            out = self._state()
+            out = self._state(ctx)
             rc = 0 if out is not None else -1
         else:
             raise ValueError(name)
         msg = "" if rc == 0 else L.vsom_last_error().decode(errors="replace")
         return rc, msg, out
 
-    def _state(self):
+    def _state(self, ctx=None):
+        h = (ctx or self.ctx)._h
         N, D = self.N, self.D
         st = {"map": np.empty((N, D), np.float32), "sigma": np.empty((N, D), np.float32),
               "S": np.empty((N, D), np.float32), "weight": np.empty(N, np.float32), "hits": np.empty(N, np.uint64)}
         f, u = self.capi._f, self.capi._u
-        self.capi.check(self.L.vsom_get_state(self.h, f(st["map"]), f(st["sigma"]), f(st["S"]), f(st["weight"]),
+        self.capi.check(self.L.vsom_get_state(h, f(st["map"]), f(st["sigma"]), f(st["S"]), f(st["weight"]),
                                               u(st["hits"])))
         return st
 
-    def observe(self):
-        st = self._state()
-        lb = np.empty(self.B(), np.uint64)
-        self.capi.check(self.L.vsom_get_last_bmu(self.h, self.capi._u(lb)))
+    def observe_twin(self):
+        return self.observe(self.twin)
+
+    def observe(self, ctx=None):
+        ctx = ctx or self.ctx
+        st = self._state(ctx)
+        lb = np.empty(int(self.L.vsom_chunk_size(ctx._h)), np.uint64)
+        self.capi.check(self.L.vsom_get_last_bmu(ctx._h, self.capi._u(lb)))
         m = C.c_float()
-        self.capi.check(self.L.vsom_get_mse(self.h, C.byref(m)))
+        self.capi.check(self.L.vsom_get_mse(ctx._h, C.byref(m)))
         st.update(lb=lb, mse=np.float32(m.value))
         return st
 
