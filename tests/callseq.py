@@ -101,7 +101,7 @@ def chunk_data(cfg_name, seed, scale=1):
 
 def chain_max_nodes(cfg):
     """The largest phase-2 node range that takes the small-map chain kernel, which reads the staged rows themselves
-    (csrc/vsom_update.hip, vsom_use_chain: ceil(n / 64) * ceil(D / 14) <= VSOM_CHAIN_MAX_WAVES); a larger range takes
+    (csrc/vsom_phase2_plan.hpp, vsom_use_chain: ceil(n / 64) * ceil(D / 14) <= VSOM_CHAIN_MAX_WAVES); a larger range takes
     the lane = node kernels, which record the rows-are-free event a later prefetch may stage ahead behind.  None where
     nothing is staged ahead (CLR, custom contexts)."""
     if cfg["custom"] or cfg["tr"] == po.CLR:
@@ -123,7 +123,7 @@ def defers(cfg):
 
 
 def two_quad_launch(cfg):
-    """mirror of the launch rule of the mean-only chains (csrc/vsom_update.hip, launch_phase2): workgroups = node groups of
+    """mirror of the launch rule of the mean-only chains (csrc/vsom_phase2_plan.hpp, vsom_phase2_plan): workgroups = node groups of
     64 x blocks of 8 column quads; the two-quad kernels where 3 * workgroups > 2 * 1024.  (With the compaction the quads
     come from the compacted pitch, which is fixed per context: the depth rounded up to 32 columns.)"""
     D = po.length(cfg["tr"], cfg["J"])

@@ -3,7 +3,7 @@ that vsom_update.hip launches for a deferred epoch) -- LAZY against a VSOM_SIGMA
 bit (NaN == NaN), after one epoch and after a schedule of three, get_state after vsom_sigma_flush.
 
 Every test runs on two maps.
-  * 41x39 (1599 nodes = 24 full node groups and one of 63), depth 300 for the sparse rows.  launch_phase2 chooses the kernel by
+  * 41x39 (1599 nodes = 24 full node groups and one of 63), depth 300 for the sparse rows.  vsom_phase2_plan chooses the kernel by
     launch size (`_nt8` above two thirds of a round of 1024 workgroups): this map's launches are at most 25 x 10 workgroups
     and take the one-quad `_nt4` kernels.
   * 210x209 (43890 nodes = 685 full node groups and one of 50), depth 96 for the sparse rows: 686 workgroups per column
@@ -50,7 +50,7 @@ SCHEDULE = (10.0, 6.0, 3.0)
 
 
 def two_quad_form(workgroups):
-    """csrc/vsom_update.hip, launch_phase2: more than two thirds of a round of 1024 workgroups"""
+    """csrc/vsom_phase2_plan.hpp, vsom_phase2_plan (pinned by tests/test_phase2_plan.py): more than two thirds of a round of 1024 workgroups"""
     return 3 * workgroups > 2 * 1024
 
 

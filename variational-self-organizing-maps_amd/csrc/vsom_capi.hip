@@ -1,5 +1,6 @@
 // vsom_capi.hip -- the extern "C" entry points declared in include/vsom_hip.h.
 #include "vsom_internal.hpp"
+#include "vsom_phase2_plan.hpp"
 
 #include <cstring>
 #include <cstdlib>
@@ -1074,9 +1075,9 @@ int vsom_batch_phase2_async(vsom_ctx *c, double sigma, size_t n0, size_t n1)
 {
     CHECK_CTX_NOJOIN(c);
     VSOM_CUSTOM_REFUSE(c, "vsom_batch_phase2_async");
-    // (a further node range of the same epoch works on the transposed chunk it already has -- unless the range is
-    // small enough for the small-map chain kernel, which reads the staged rows themselves)
-    if (!c->xq_valid || (n1 > n0 && vsom_small_map_chains(c, n1 - n0)))
+    // (a further node range of the same epoch works on the transposed chunk it already has -- unless its plan takes a
+    // path that reads the staged rows themselves: a range small enough for the small-map chain kernel)
+    if (!c->xq_valid || (n1 > n0 && vsom_phase2_plan(*c, n0, n1, true).reads_staged_rows))
         CHECK_ROWS(c);
     if (n0 > n1 || n1 > c->N)
         return vsom_fail(VSOM_ERR_INVALID, "node range out of bounds");

@@ -20,6 +20,7 @@
 // MNIST (BASELINE configs 2-3): 67 of the 784 pixels are zero in every training image and ~120 in a
 // 4096-image chunk (tests/gen.py reproduces 661 live); the exact results are unchanged bit for bit.
 #include "vsom_device.hpp"
+#include "vsom_phase2_plan.hpp"
 
 #include <cstdlib>
 
@@ -93,8 +94,8 @@ __global__ __launch_bounds__(256) void cc_gather_rows_kernel(const float *__rest
 
 // model rows back in the reference's layout: live column d <- compacted column inv[d] (map: the chain's M;
 // sigmaMap: sqrt(S / W), Som.cpp:873), dead column <- +0, or NaN when the node's first coefficient is 0/0
-// (header); the padding columns of the rows are put to zero as sigma_finalize_kernel does.  WHAT: 3 = both, 1 = the map rows
-// only (an epoch whose sigmaMap stays pending, vsom_update.hip), 2 = the sigmaMap rows only (its materialisation)
+// (header); the padding columns of the rows are put to zero as sigma_finalize_kernel does.  WHAT (VsomExpand): both, the map rows
+// only (an epoch whose sigmaMap stays pending, vsom_update.hip), or the sigmaMap rows only (its materialisation)
 template <int WHAT>
 __global__ __launch_bounds__(256) void cc_expand_kernel(const float *__restrict__ um, const float *__restrict__ us, int ldc,
                                                         const int *__restrict__ inv, float *__restrict__ map,
@@ -151,9 +152,8 @@ bool vsom_cc_applies(const vsom_ctx *c)
     if (c->D < 64)           // the chain / tiny kernels, and nothing worth retiring
         return false;
     // only the lane = node chain kernels and the MFMA shortlist consume the compaction: maps below their
-    // thresholds (launch_phase2: VSOM_CHAIN_MAX_WAVES; launch_bmu_full: 1024 nodes) skip the passes
-    const size_t waves = ((size_t)c->N + 63) / 64 * ((c->D + 13) / 14);
-    return waves > VSOM_CHAIN_MAX_WAVES || c->N >= 1024;
+    // thresholds (vsom_phase2_plan: VSOM_CHAIN_MAX_WAVES; launch_bmu_full: 1024 nodes) skip the passes
+    return vsom_lane_node_waves(*c, c->N) > VSOM_CHAIN_MAX_WAVES || c->N >= 1024;
 }
 
 static int cc_ensure(vsom_ctx *c)
@@ -232,9 +232,10 @@ int vsom_cc_ensure_update_scratch(vsom_ctx *c)
     return VSOM_OK;
 }
 
-int vsom_cc_expand(vsom_ctx *c, size_t n0, size_t nloc, int what, const int *inv)
+int vsom_cc_expand(vsom_ctx *c, size_t n0, size_t nloc, VsomExpand what, const int *inv)
 {
-    const auto fn = what == 1 ? cc_expand_kernel<1> : (what == 2 ? cc_expand_kernel<2> : cc_expand_kernel<3>);
+    const auto fn = what == VSOM_EXPAND_MAP ? cc_expand_kernel<VSOM_EXPAND_MAP>
+                    : (what == VSOM_EXPAND_SIGMA ? cc_expand_kernel<VSOM_EXPAND_SIGMA> : cc_expand_kernel<VSOM_EXPAND_BOTH>);
     hipLaunchKernelGGL(fn, dim3((unsigned)nloc), dim3(256), 0, c->stream, c->Uc_map.p, c->Uc_S.p, (int)c->cpitch,
                        inv ? inv : c->cc_inv.p, c->map.p, c->sigma.p, (int)c->pitch, (int)c->D, (int)n0, (int)nloc, c->weight.p,
                        reinterpret_cast<const float4 *>(c->cw.p));

@@ -43,6 +43,13 @@ constexpr size_t VSOM_ONL_STATE_BYTES = 4352;
 
 struct vsom_custom_state;
 
+// The lane = node column-quad chain kernels of the hand-scheduled code object (gen_nt_asm.py), by arithmetic and by form:
+// FULL runs the M and S chains with one column quad per wavefront (`_nt4`); the MEAN forms run the M chain alone, for
+// epochs whose sigmaMap stays pending, with one quad per wavefront (`_nt4`) or two (`_nt8`).  Which one an epoch launches:
+// vsom_phase2_plan.hpp.
+enum VsomQuadVariant { VSOM_QV_STD, VSOM_QV_FMA, VSOM_QV_SFMA, VSOM_QV_MED, VSOM_QV_COUNT };
+enum VsomQuadForm { VSOM_QF_FULL, VSOM_QF_MEAN_ONE_QUAD, VSOM_QF_MEAN_TWO_QUADS, VSOM_QF_COUNT };
+
 struct vsom_ctx {
     int device = 0;
     uint32_t W = 0, H = 0, J = 0, D = 0, N = 0;
@@ -150,9 +157,8 @@ struct vsom_ctx {
     hipEvent_t lutd_ev[2] = {nullptr, nullptr}; bool lutd_ev_valid[2] = {false, false}; int lutd_slot = 0;
 
     // hand-scheduled update kernel (code object loaded with hipModuleLoadData)
-    void *upd_module = nullptr, *upd_clr8 = nullptr, *upd_nt[4] = {nullptr, nullptr, nullptr, nullptr};   // nt: std, fma, sfma, med
-    void *upd_nt_mean[4] = {nullptr, nullptr, nullptr, nullptr};   // their M-only forms: mean, meanfma, mean, medmean
-    void *upd_nt_mean8[4] = {nullptr, nullptr, nullptr, nullptr};  // the same with two column quads per wavefront (`_nt8`)
+    void *upd_module = nullptr, *upd_clr8 = nullptr;
+    void *upd_quad[VSOM_QF_COUNT][VSOM_QV_COUNT] = {};   // the lane = node quad kernels (vsom_load_asm_module names them)
     bool mean_nt4 = false;          // development builds only (VSOM_MEAN_NT4): deferred epochs launch the `_nt4` forms at every size
     int update_mode = VSOM_UPDATE_STRICT;
     bool use_chain = true;
@@ -178,9 +184,9 @@ struct vsom_ctx {
     bool xq_valid = false;
     uint32_t xq_bpad = 0, xq_quads = 0;
 
-    // Deferred sigmaMap (vsom_update.hip, "pending sigma"): a full-range phase 2 of the lane = node Standard / Median path
-    // may run the M-only chain kernel and leave sigmaMap unwritten; `sg` then records what the full kernel needs to
-    // produce that epoch's sigmaMap later.  Its inputs are the context's own buffers -- Xq / zq, cw, weight and the
+    // Deferred sigmaMap (vsom_update.hip, "pending sigma"): a full-range phase 2 on the QUADS path whose plan says `deferred`
+    // (vsom_phase2_plan.hpp) runs a MEAN form of the quad kernels and leaves sigmaMap unwritten; `sg` then records what the
+    // FULL form of the same variant needs to produce that epoch's sigmaMap later (vsom_phase2_replay plans that launch).  Its inputs are the context's own buffers -- Xq / zq, cw, weight and the
     // compaction's scratch rows are written by launch_phase2 alone, which drops or materialises the record first -- except
     // the live-column record and lastBMU, which the staging and the search of the next chunk overwrite: sg_inv / sg_meta /
     // sg_bmu are owned copies.  The mean-only kernel takes the c-only form of the (c,w) array (half the bytes), so the
@@ -189,10 +195,10 @@ struct vsom_ctx {
     // read sigmaMap (vsom_capi.hip, CHECK_CTX_KEEP); the next full-range epoch, which overwrites every row, drops it.
     struct PendingSigma {
         bool on = false;
-        size_t B = 0, ldn = 0;
+        size_t B = 0;
         uint32_t bpad = 0;
         bool compact = false;
-        int kernel = 0;             // index into upd_nt: the update mode and transformation in force at that epoch
+        VsomQuadVariant variant = VSOM_QV_STD;   // the update mode and transformation in force at that epoch
         double sigma = 0.0;         // the epoch's sigma: the table of its neighbourhood pass.  (Today every call that
                                     // retabulates -- another phase 2, the tiny and custom paths -- materialises or drops the
                                     // record first, so the table in place is still this one; the record does not rely on it.)
@@ -378,8 +384,9 @@ int vsom_cc_begin(vsom_ctx *c, size_t B, bool *on);
 int vsom_cc_stage(vsom_ctx *c, size_t B, hipStream_t stream, int *idx, int *inv, unsigned *meta, bool *xi_out);
 int vsom_cc_gather_map(vsom_ctx *c);
 int vsom_cc_ensure_update_scratch(vsom_ctx *c);
-// what: 3 = map and sigmaMap from the scratch rows, 1 = map only, 2 = sigmaMap only (inv: the live-column record to use)
-int vsom_cc_expand(vsom_ctx *c, size_t n0, size_t nloc, int what = 3, const int *inv = nullptr);
+// which rows the expansion writes from the scratch rows (bit 0: map, bit 1: sigmaMap); inv: the live-column record to use
+enum VsomExpand { VSOM_EXPAND_MAP = 1, VSOM_EXPAND_SIGMA = 2, VSOM_EXPAND_BOTH = 3 };
+int vsom_cc_expand(vsom_ctx *c, size_t n0, size_t nloc, VsomExpand what, const int *inv = nullptr);
 // vsom_sl_i8.hip: rows onto the live columns (+ int8 images)
 int launch_sl_gather_quant(vsom_ctx *c, size_t B, hipStream_t stream, const int *idx, bool *xi_out);
 int vsom_xq_ensure(vsom_ctx *c);                                 // vsom_xq.hip

@@ -22,14 +22,19 @@
 //                    take the c-only form of the (c,w) array, which cwp_kernel writes for such an epoch
 //                  - vsom_update_{mean,meanfma,medmean}_nt8_gfx950: those with two column quads per wavefront (workgroup = 4
 //                    wavefronts over the same 64 nodes x 8 quads); what a deferred epoch launches unless the launch is small
-//                    (launch_phase2: at most two thirds of a 1024-workgroup round take the `_nt4` forms); development builds
+//                    (vsom_phase2_plan: at most two thirds of a 1024-workgroup round take the `_nt4` forms); development builds
 //                    force `_nt4` with VSOM_MEAN_NT4 for A/B runs.
+//                    The three groups are the forms FULL, MEAN_ONE_QUAD and MEAN_TWO_QUADS of vsom_ctx::upd_quad[form][variant].
 //                  - vsom_update_clr_rp8_gfx950 (gen_update_asm.py): CLR, lane = node, 8 parameter pairs per lane.
 //                  - update_chain3_kernel (HIP, below): maps too small to fill the chip with lane = node
 //                    (C4: 64x64x32): one lane per (node, dim pair) chain, operands staged through LDS.
 //   sigma_finalize_kernel : sigmaMap = sqrt(S / W) for the columns the assembly kernels left as S
 //                  (+ zeroes of the padding columns a ragged last slice wrote).
+// Host side: vsom_phase2_plan (vsom_phase2_plan.hpp) decides everything about an epoch -- its path (EMPTY, CLR, SMALL_MAP, QUADS),
+// kernel, launch shape, whether sigmaMap stays pending, what follows the chains -- and launch_phase2 executes that plan
+// through run_clr / run_small_map / run_quads and run_after; sigma_materialise executes vsom_phase2_replay's.
 #include "vsom_device.hpp"
+#include "vsom_phase2_plan.hpp"
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -534,21 +539,16 @@ int vsom_load_asm_module(vsom_ctx *c)
     hipFunction_t f;
     VSOM_HIP_CHECK(hipModuleGetFunction(&f, mod, "vsom_update_clr_rp8_gfx950"));
     c->upd_clr8 = f;
-    static const char *const nt_names[4] = {"std", "fma", "sfma", "med"};
-    for (int i = 0; i < 4; ++i) {
-        const std::string n = std::string("vsom_update_") + nt_names[i] + "_nt4_gfx950";
-        VSOM_HIP_CHECK(hipModuleGetFunction(&f, mod, n.c_str()));
-        c->upd_nt[i] = f;
-    }
-    static const char *const mean_names[4] = {"mean", "meanfma", "mean", "medmean"};   // (sfma's M chain is the strict one)
-    for (int i = 0; i < 4; ++i) {
-        const std::string n = std::string("vsom_update_") + mean_names[i] + "_nt4_gfx950";
-        VSOM_HIP_CHECK(hipModuleGetFunction(&f, mod, n.c_str()));
-        c->upd_nt_mean[i] = f;
-        const std::string n8 = std::string("vsom_update_") + mean_names[i] + "_nt8_gfx950";   // two column quads per wavefront
-        VSOM_HIP_CHECK(hipModuleGetFunction(&f, mod, n8.c_str()));
-        c->upd_nt_mean8[i] = f;
-    }
+    static const char *const quad_names[VSOM_QF_COUNT][VSOM_QV_COUNT] = {
+        {"std_nt4", "fma_nt4", "sfma_nt4", "med_nt4"},               // by VsomQuadVariant: STD, FMA, SFMA, MED
+        {"mean_nt4", "meanfma_nt4", "mean_nt4", "medmean_nt4"},      // (sfma's M chain is the strict one)
+        {"mean_nt8", "meanfma_nt8", "mean_nt8", "medmean_nt8"}};     // two column quads per wavefront
+    for (int form = 0; form < VSOM_QF_COUNT; ++form)
+        for (int v = 0; v < VSOM_QV_COUNT; ++v) {
+            const std::string n = std::string("vsom_update_") + quad_names[form][v] + "_gfx950";
+            VSOM_HIP_CHECK(hipModuleGetFunction(&f, mod, n.c_str()));
+            c->upd_quad[form][v] = f;
+        }
 #ifdef VSOM_DEVELOPMENT
     c->mean_nt4 = std::getenv("VSOM_MEAN_NT4") != nullptr;   // A/B: the deferred epochs on the one-quad mean-only kernels
 #endif
@@ -629,17 +629,7 @@ __global__ void zero_weight_kernel(float *__restrict__ weight, int n0, int nloc)
         weight[n0 + i] = 0.f;
 }
 
-// Maps whose node shard times depth is small (ceil(nodes/64) * ceil(D/14) <= VSOM_CHAIN_MAX_WAVES, the measured
-// crossover against lane = node kernels, vsom_internal.hpp) take the small-map chain kernel, lane = (node, dim
-// pair): C4's 64x64x32 map would give the quad kernels half a wavefront per SIMD.
-static bool vsom_use_chain(const vsom_ctx *c, size_t nloc)
-{
-    if (!c->use_chain || c->transform == VSOM_CLR)
-        return false;
-    return ((nloc + 63) / 64) * ((c->D + 13) / 14) <= VSOM_CHAIN_MAX_WAVES;
-}
-
-extern "C" int vsom_small_map_chains(const vsom_ctx *c, size_t nodes) { return c && vsom_use_chain(c, nodes) ? 1 : 0; }
+extern "C" int vsom_small_map_chains(const vsom_ctx *c, size_t nodes) { return c && vsom_use_chain(*c, nodes) ? 1 : 0; }
 
 // The neighbourhood pass over the nodes [n0, n1) for the B rows whose BMUs are `bmu`, from the table ensure_lut left:
 // the (c,w) array, or its c-only form for an epoch that runs the mean-only chains; weightMap unless `weight` is null.
@@ -668,35 +658,50 @@ static int launch_cwp(vsom_ctx *c, const u64 *bmu, size_t B_, size_t n0, size_t 
 }
 
 // ---- pending sigma (vsom_internal.hpp, vsom_ctx::sg) ------------------------------------------------------------
-// one launch of a lane = node Standard / Median chain kernel over the nodes [n0, n0 + nloc), from the operands of a chunk of
-// B rows: the one place that fills the kernarg, for the eager epoch, the mean-only epoch and the materialisation
-// (block: 512 threads = one column quad per wavefront, the `_nt4` kernels; 256 = two, the mean-only `_nt8` kernels: the same
-// 64 nodes x 8 quads per workgroup, so the same grid)
-static int launch_nt_chains(vsom_ctx *c, void *fn, size_t n0, size_t nloc, size_t B, size_t ldn, uint32_t bpad, bool compact,
-                            const unsigned *meta, unsigned block = 512)
+// one launch of a lane = node Standard / Median chain kernel, the plan's upd_quad[form][variant] in the plan's shape, over the
+// nodes [n0, n0 + nloc), from the operands of a chunk of B rows: the one place that fills the kernarg, for the eager epoch, the
+// mean-only epoch and the materialisation
+static int launch_nt_chains(vsom_ctx *c, const Phase2Plan &p, size_t n0, size_t B, uint32_t bpad, const unsigned *meta)
 {
-    const unsigned gx = (unsigned)((nloc + 63) / 64);
-    const unsigned cols = compact ? c->cpitch : c->pitch;
-    const unsigned quads = compact ? c->cpitch / 4 : (c->D + 3) / 4;
+    const unsigned cols = p.compact ? c->cpitch : c->pitch;
     UpdAsmArgs a;
     a.xs = c->Xq.p;
     a.cw2 = c->cw.p;
-    a.map = compact ? c->Uc_map.p : c->map.p;
-    a.sbuf = compact ? c->Uc_S.p : c->sigma.p;
+    a.map = p.compact ? c->Uc_map.p : c->map.p;
+    a.sbuf = p.compact ? c->Uc_S.p : c->sigma.p;
     a.ldx_bytes = bpad * 16u;
-    a.ldn_bytes = (unsigned)(ldn * 16u);
+    a.ldn_bytes = (unsigned)(p.ldn * 16u);
     a.B = (unsigned)B;
-    a.nloc = (unsigned)nloc;
-    a.nslices = quads;
+    a.nloc = (unsigned)p.nloc;
+    a.nslices = p.quads;
     a.pitch_bytes = cols * 4u;
     a.n0 = (unsigned)n0;
     a.ppitch_bytes = 0;
-    a.yp = compact ? (const void *)meta : nullptr;
+    a.yp = p.compact ? (const void *)meta : nullptr;
     a.zq = c->zq.p;
     size_t sz = 80;
     void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-    VSOM_HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)fn, 8 * ((quads + 7) / 8), (gx + 7) / 8, 1, block, 1, 1, 0, c->stream,
-                                         nullptr, extra));
+    VSOM_HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)c->upd_quad[p.form][p.variant], p.grid_x, p.grid_y, 1, p.block, 1, 1, 0,
+                                         c->stream, nullptr, extra));
+    return VSOM_OK;
+}
+
+// What follows the chains (Phase2After): the compaction's scratch rows expanded into map / sigmaMap rows (inv: the
+// live-column record to use), or raw S turned into sigmaMap in the columns the assembly kernels left so, part by part
+static int run_after(vsom_ctx *c, const Phase2Plan &p, size_t n0, const int *inv = nullptr)
+{
+    if (p.after == VSOM_P2_NOTHING)
+        return VSOM_OK;
+    TimerScope ts(c, VSOM_T_SIGMA);
+    if (p.after != VSOM_P2_FINALIZE_COLUMNS)
+        return vsom_cc_expand(c, n0, p.nloc,
+                              p.after == VSOM_P2_EXPAND_MAP_ONLY ? VSOM_EXPAND_MAP
+                              : p.after == VSOM_P2_EXPAND_SIGMA_ONLY ? VSOM_EXPAND_SIGMA : VSOM_EXPAND_BOTH, inv);
+    for (uint32_t part = 0; part < c->nparts; ++part)
+        hipLaunchKernelGGL(sigma_finalize_kernel, dim3((unsigned)p.nloc), dim3(256), 0, c->stream, c->sigma.p, c->map.p,
+                           (int)c->pitch, (int)(part * c->part_pitch), (int)p.after_cols, (int)c->part_len, (int)n0, (int)p.nloc,
+                           c->weight.p);
+    VSOM_HIP_CHECK(hipGetLastError());
     return VSOM_OK;
 }
 
@@ -736,23 +741,18 @@ static int sigma_materialise(vsom_ctx *c)
         return rc;
     c->sg.on = false;
     ++c->sg_stats[2];
+    const Phase2Plan plan = vsom_phase2_replay(*c, p.B, p.variant, p.compact);
     {
         TimerScope ts(c, VSOM_T_CW);
-        if ((rc = launch_cwp(c, c->sg_bmu.p, p.B, 0, c->N, p.ldn, false, nullptr)))
+        if ((rc = launch_cwp(c, c->sg_bmu.p, p.B, 0, c->N, plan.ldn, false, nullptr)))
             return rc;
     }
     {
         TimerScope ts(c, VSOM_T_UPDATE);
-        if ((rc = launch_nt_chains(c, c->upd_nt[p.kernel], 0, c->N, p.B, p.ldn, p.bpad, p.compact, c->sg_meta.p)))
+        if ((rc = launch_nt_chains(c, plan, 0, p.B, p.bpad, c->sg_meta.p)))
             return rc;
     }
-    TimerScope ts(c, VSOM_T_SIGMA);
-    if (p.compact)
-        return vsom_cc_expand(c, 0, c->N, 2, c->sg_inv.p);
-    hipLaunchKernelGGL(sigma_finalize_kernel, dim3((unsigned)c->N), dim3(256), 0, c->stream, c->sigma.p, c->map.p, (int)c->pitch, 0,
-                       (int)((c->D + 3) / 4 * 4), (int)c->part_len, 0, (int)c->N, c->weight.p);
-    VSOM_HIP_CHECK(hipGetLastError());
-    return VSOM_OK;
+    return run_after(c, plan, 0, c->sg_inv.p);
 }
 
 int vsom_sigma_flush_pending(vsom_ctx *c)
@@ -761,15 +761,87 @@ int vsom_sigma_flush_pending(vsom_ctx *c)
     return c->sg.on ? sigma_materialise(c) : VSOM_OK;
 }
 
-// does this full-range epoch leave its sigmaMap pending?  (dense rows of a ragged depth stay eager: their last quad runs
-// into the rows' padding, which sigma_finalize_kernel re-zeroes in map and sigmaMap at once)
-static bool sigma_defers(const vsom_ctx *c, bool compact)
+// ---- the paths of an epoch: each runs its chain kernel as the plan says -------------------------------------------
+// CLR: lane = node, 8 parameter pairs per wavefront (gen_update_asm.py)
+static int run_clr(vsom_ctx *c, const Phase2Plan &p, size_t n0)
 {
-    if (c->sigma_shared || c->in_group || c->sigma_mode == VSOM_SIGMA_EAGER)
-        return false;
-    if (!compact && c->D % 4 != 0)
-        return false;
-    return c->sigma_mode == VSOM_SIGMA_LAZY || c->sigma_unread >= 2;
+    UpdAsmArgs a;
+    a.xs = c->XP.p;
+    a.cw2 = c->cw.p;
+    a.map = c->map.p;
+    a.sbuf = c->sigma.p;
+    a.ldx_bytes = c->part_pitch * 4u;
+    a.ldn_bytes = (unsigned)(p.ldn * 16u);
+    a.B = (unsigned)c->B;
+    a.nloc = (unsigned)p.nloc;
+    a.nslices = p.nslices;
+    a.pitch_bytes = c->pitch * 4u;
+    a.n0 = (unsigned)n0;
+    a.ppitch_bytes = c->part_pitch * 4u;
+    a.yp = c->YP.p;
+    a.zq = nullptr;
+    size_t sz = 72;
+    void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
+    VSOM_HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)c->upd_clr8, p.grid_x, p.grid_y, 1, p.block, 1, 1, 0, c->stream, nullptr,
+                                         extra));
+    return VSOM_OK;
+}
+
+// small maps: one lane per (node, dim pair) chain, operands staged through LDS (update_chain3_kernel)
+static int run_small_map(vsom_ctx *c, const Phase2Plan &p, size_t n0)
+{
+    using K3 = void (*)(const float *, int, const float2 *, int, int, int, int, int, float *, float *, int, const float *);
+    static constexpr K3 k3[VSOM_QV_COUNT][4] = {   // [variant][pl_log2 - 3]
+        {update_chain3_kernel<false, 0, 3>, update_chain3_kernel<false, 0, 4>, update_chain3_kernel<false, 0, 5>, update_chain3_kernel<false, 0, 6>},
+        {update_chain3_kernel<false, 1, 3>, update_chain3_kernel<false, 1, 4>, update_chain3_kernel<false, 1, 5>, update_chain3_kernel<false, 1, 6>},
+        {update_chain3_kernel<false, 2, 3>, update_chain3_kernel<false, 2, 4>, update_chain3_kernel<false, 2, 5>, update_chain3_kernel<false, 2, 6>},
+        {update_chain3_kernel<true, 0, 3>, update_chain3_kernel<true, 0, 4>, update_chain3_kernel<true, 0, 5>, update_chain3_kernel<true, 0, 6>}};
+    const float *xs_ = c->Xs.p;
+    const float2 *cw_ = c->cw.p;
+    int ildx = (int)c->xpitch, ildn = (int)p.ldn, iB = (int)c->B, in0 = (int)n0, inl = (int)p.nloc, iD = (int)c->D,
+        ipitch = (int)c->pitch;
+    float *map_ = c->map.p, *sg_ = c->sigma.p;
+    const float *wt_ = c->weight.p;
+    void *args[] = {&xs_, &ildx, &cw_, &ildn, &iB, &in0, &inl, &iD, &map_, &sg_, &ipitch, &wt_};
+    VSOM_HIP_CHECK(hipLaunchKernel((const void *)k3[p.variant][p.pl_log2 - 3], dim3(p.grid_x, p.grid_y), dim3(p.block), args, 0,
+                                   c->stream));
+    return VSOM_OK;
+}
+
+// Standard / Median: lane = node, workgroup = 64 nodes x 8 column quads, x from scalar loads of the transposed chunk
+// (gen_nt_asm.py, vsom_xq.hip); with the column compaction (vsom_compact.hip) on the gathered live columns, into dense
+// scratch rows
+static int run_quads(vsom_ctx *c, const Phase2Plan &p, double sigma, size_t n0)
+{
+    int rc = vsom_xq_ensure(c);
+    if (rc)
+        return rc;
+    // nothing below reads the staged rows (Xs / Xc / int8 images) of this chunk any more: the next chunk's staging kernels
+    // may overwrite them beside the chains (vsom_prefetch_chunk / vsom_stage_next_device), where the plan finds that it pays
+    if (p.offer_rows_free) {
+        VSOM_HIP_CHECK(hipEventRecord(c->ev_rows_free, c->stream));
+        c->rows_free_valid = true;
+    }
+    if (p.compact && (rc = vsom_cc_ensure_update_scratch(c)))
+        return rc;
+    if (!p.deferred)
+        return launch_nt_chains(c, p, n0, c->B, c->xq_bpad, c->cc_meta.p);
+    // the M chains alone, from the c-only array; sigmaMap stays what it was until somebody may read it
+    // (vsom_internal.hpp, `sg`).  First the owned copies of what the materialisation needs and the staging and
+    // the search of the next chunk overwrite: the live-column record, lastBMU
+    hipLaunchKernelGGL(sg_keep_record_kernel, dim3((unsigned)((std::max<size_t>(p.compact ? c->xpitch : 0, c->B) + 255) / 256)),
+                       dim3(256), 0, c->stream, c->cc_inv.p, p.compact ? (int)c->xpitch : 0, c->cc_meta.p, c->sg_inv.p,
+                       c->sg_meta.p, c->lastbmu.p, (int)c->B, c->sg_bmu.p);
+    if ((rc = launch_nt_chains(c, p, n0, c->B, c->xq_bpad, c->cc_meta.p)))
+        return rc;
+    c->sg.on = true;
+    c->sg.B = c->B;
+    c->sg.bpad = c->xq_bpad;
+    c->sg.compact = p.compact;
+    c->sg.variant = p.variant;
+    c->sg.sigma = sigma;
+    ++c->sg_stats[0];
+    return VSOM_OK;
 }
 
 int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1, bool may_defer)
@@ -791,7 +863,7 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1, bool may_defe
             ++c->sigma_unread;
         return vsom_join_aux_keep(c);
     };
-    if (c->B == 0) {
+    if (c->B == 0) {   // (the plan's EMPTY path, taken before anything that can fail)
         TimerScope ts(c, VSOM_T_UPDATE);
         const size_t nloc = n1 - n0, tot = nloc * c->pitch;
         hipLaunchKernelGGL(empty_epoch_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, c->stream, c->map.p,
@@ -807,154 +879,34 @@ int launch_phase2(vsom_ctx *c, double sigma, size_t n0, size_t n1, bool may_defe
         return rc;
     if ((rc = vsom_load_asm_module(c)))
         return rc;
-    const size_t nloc = n1 - n0;
-    const size_t ldn = (nloc + 63) / 64 * 64;
-    // does this epoch run the mean-only chains (the lane = node Standard / Median path alone)?  Decided here because the
-    // neighbourhood pass then writes the c-only operand array.  The old record goes BEFORE its owned buffers may be
-    // reallocated for the new one: a failed growth leaves them null, and no record may point at them then.
-    const bool compact = c->cc_valid;
-    const bool deferred = may_defer && full && c->transform != VSOM_CLR && !vsom_use_chain(c, nloc) && sigma_defers(c, compact);
+    // Everything the epoch decides, decided here: among it whether it runs the mean-only chains, because the neighbourhood
+    // pass then writes the c-only operand array.  The old record goes BEFORE its owned buffers may be reallocated for the
+    // new one: a failed growth leaves them null, and no record may point at them then.
+    const Phase2Plan plan = vsom_phase2_plan(*c, n0, n1, may_defer);
     vsom_sigma_drop(c);
-    if (deferred) {
-        if (compact)
+    if (plan.deferred) {
+        if (plan.compact)
             VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, 0, {vsom_member(c->sg_inv, c->xpitch), vsom_member(c->sg_meta, 16)}));
         VSOM_ALLOC_CHECK(vsom_grow(c->sg_bmu, c->B, c->stream));
     }
-    // pair rows: ceil(B/2) + what the kernels' staging reads ahead (one block of 16 pair-rows) + slack
-    const size_t prow = (c->B + 1) / 2 + 24;
-    const size_t need = prow * ldn * 2;   // float2 elements
     // rows beyond B are staged (never used): keep them initialised
-    VSOM_ALLOC_CHECK(vsom_grow(c->cw, need, c->stream, VSOM_BUF_ZERO));
+    VSOM_ALLOC_CHECK(vsom_grow(c->cw, plan.cw_elems, c->stream, VSOM_BUF_ZERO));
     {
         TimerScope ts(c, VSOM_T_CW);
-        if ((rc = launch_cwp(c, c->lastbmu.p, c->B, n0, n1, ldn, deferred, c->weight.p)))
+        if ((rc = launch_cwp(c, c->lastbmu.p, c->B, n0, n1, plan.ldn, plan.deferred, c->weight.p)))
             return rc;
     }
-    int sig_cols = 0;   // > 0: columns left as raw S by the kernel; < 0: the compaction's scratch rows hold M and raw S
     {
         TimerScope ts(c, VSOM_T_UPDATE);
-        const unsigned gx = (unsigned)((nloc + 63) / 64);
-        if (c->transform == VSOM_CLR || vsom_use_chain(c, nloc))
-            c->rows_free_valid = false;   // these chain kernels read the staged rows: no stage-ahead behind an earlier range's event
-        if (c->transform == VSOM_CLR) {
-            // lane = node, 8 parameter pairs per wavefront (gen_update_asm.py); a ragged last slice runs over the
-            // parts' zero padding (part_pitch is a multiple of 32)
-            constexpr unsigned RP = 8;
-            const unsigned nsl = (c->part_len + RP - 1) / RP;
-            UpdAsmArgs a;
-            a.xs = c->XP.p;
-            a.cw2 = c->cw.p;
-            a.map = c->map.p;
-            a.sbuf = c->sigma.p;
-            a.ldx_bytes = c->part_pitch * 4u;
-            a.ldn_bytes = (unsigned)(ldn * 16u);
-            a.B = (unsigned)c->B;
-            a.nloc = (unsigned)nloc;
-            a.nslices = nsl;
-            a.pitch_bytes = c->pitch * 4u;
-            a.n0 = (unsigned)n0;
-            a.ppitch_bytes = c->part_pitch * 4u;
-            a.yp = c->YP.p;
-            a.zq = nullptr;
-            size_t sz = 72;
-            void *extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &a, HIP_LAUNCH_PARAM_BUFFER_SIZE, &sz, HIP_LAUNCH_PARAM_END};
-            VSOM_HIP_CHECK(hipModuleLaunchKernel((hipFunction_t)c->upd_clr8, 8 * ((nsl + 3) / 4), (gx + 7) / 8, 1, 256, 1, 1, 0,
-                                                 c->stream, nullptr, extra));
-            sig_cols = (int)(nsl * RP);
-        } else if (vsom_use_chain(c, nloc)) {
-            // small maps: one lane per (node, dim pair) chain, operands staged through LDS (update_chain3_kernel);
-            // at least 8 dim pairs per node row (lanes past the depth idle)
-            int pl_log2 = 3;
-            while ((2u << pl_log2) < c->D && pl_log2 < 6)
-                ++pl_log2;
-            const unsigned PL = 1u << pl_log2, npairs = (c->D + 1) / 2;
-            dim3 grid2((unsigned)((nloc + (256 / PL) - 1) / (256 / PL)), (npairs + PL - 1) / PL);
-            const bool med = c->transform == VSOM_MEDIAN, fma = c->update_mode == VSOM_UPDATE_FMA,
-                       sfma = c->update_mode == VSOM_UPDATE_FMA_SIGMA;
-#define VSOM_K3(P) (med ? (const void *)update_chain3_kernel<true, 0, P> \
-                        : (fma ? (const void *)update_chain3_kernel<false, 1, P>                    \
-                               : (sfma ? (const void *)update_chain3_kernel<false, 2, P> : (const void *)update_chain3_kernel<false, 0, P>)))
-            const void *k3 = pl_log2 == 3 ? VSOM_K3(3) : pl_log2 == 4 ? VSOM_K3(4) : pl_log2 == 5 ? VSOM_K3(5) : VSOM_K3(6);
-#undef VSOM_K3
-            const float *xs_ = c->Xs.p;
-            const float2 *cw_ = c->cw.p;
-            int ildx = (int)c->xpitch, ildn = (int)ldn, iB = (int)c->B, in0 = (int)n0, inl = (int)nloc, iD = (int)c->D,
-                ipitch = (int)c->pitch;
-            float *map_ = c->map.p, *sg_ = c->sigma.p;
-            const float *wt_ = c->weight.p;
-            void *args[] = {&xs_, &ildx, &cw_, &ildn, &iB, &in0, &inl, &iD, &map_, &sg_, &ipitch, &wt_};
-            VSOM_HIP_CHECK(hipLaunchKernel(k3, grid2, dim3(256), args, 0, c->stream));
-        } else {
-            // Standard / Median: lane = node, one column quad per wavefront, workgroup = 64 nodes x 8 quads, x from
-            // scalar loads of the transposed chunk (gen_nt_asm.py, vsom_xq.hip); grid.x = 8 * column blocks
-            // (XCD-aware).  With the column compaction (vsom_compact.hip) the kernel runs on the gathered live
-            // columns -- their count is a device value the kernel reads from the record -- into dense scratch rows
-            // that cc_expand_kernel writes back; otherwise a last quad of a ragged depth runs into the rows' zero
-            // padding and sigma_finalize_kernel re-zeroes it.
-            if ((rc = vsom_xq_ensure(c)))
-                return rc;
-            // nothing below reads the staged rows (Xs / Xc / int8 images) of this chunk any more: the next chunk's
-            // staging kernels may overwrite them beside the chains (vsom_prefetch_chunk / vsom_stage_next_device)
-            // -- where that pays: kernels running beside the chain kernel take slots and clock from it, and measured
-            // (tools/exp/ab_stage.py, interleaved A/B, strict, B = 4096 x 784) the step gains 2.7 % / 2.3 % on 48x48 /
-            // 64x64 maps (the chain launch leaves slots idle: 1.3 rounds of the 1024 resident workgroups), nothing
-            // at 80x80 / 96x96 and LOSES 1 % at 112x112 / 128x128 (six full rounds: 0.05 ms of staging kernels cost the
-            // chains 0.09 ms).  So the event is offered only when the chain launch is at most two rounds.
-            const size_t chain_wgs = (size_t)gx * (((c->cc_valid ? c->cpitch / 4 : (c->D + 3) / 4) + 7) / 8);
-            if (chain_wgs <= 2048) {
-                VSOM_HIP_CHECK(hipEventRecord(c->ev_rows_free, c->stream));
-                c->rows_free_valid = true;
-            }
-            if (compact && (rc = vsom_cc_ensure_update_scratch(c)))
-                return rc;
-            const bool fma = c->update_mode == VSOM_UPDATE_FMA, sfma = c->update_mode == VSOM_UPDATE_FMA_SIGMA;
-            const bool med = c->transform == VSOM_MEDIAN;     // its FMAs are exact: one kernel for all modes
-            const unsigned quads = compact ? c->cpitch / 4 : (c->D + 3) / 4;
-            const int kernel = med ? 3 : (fma ? 1 : (sfma ? 2 : 0));
-            if (deferred) {
-                // the M chains alone, from the c-only array; sigmaMap stays what it was until somebody may read it
-                // (vsom_internal.hpp, `sg`).  First the owned copies of what the materialisation needs and the staging and
-                // the search of the next chunk overwrite: the live-column record, lastBMU
-                hipLaunchKernelGGL(sg_keep_record_kernel, dim3((unsigned)((std::max<size_t>(compact ? c->xpitch : 0, c->B) + 255) / 256)),
-                                   dim3(256), 0, c->stream, c->cc_inv.p, compact ? (int)c->xpitch : 0, c->cc_meta.p, c->sg_inv.p,
-                                   c->sg_meta.p, c->lastbmu.p, (int)c->B, c->sg_bmu.p);
-                // Two column quads per wavefront (gen_nt_asm.py, K2) where the launch is more than two thirds of a round of
-                // 1024 workgroups; below, the one-quad form: a small launch leaves SIMDs short of wavefronts, and the two-quad
-                // form has half as many, each twice as long.  Measured (B = 4096 x 784 sparse, 21 column blocks, launch time
-                // one-quad -> two-quad, profiles/mean_nt8_small_launches.txt): 525 workgroups 0.310 -> 0.344 ms, 672 0.340 ->
-                // 0.343 (the step 0.488 -> 0.503), 756 0.590 -> 0.405, 1008 0.592 -> 0.491, 5376 (C3) 2.28 -> 1.86.
-                const bool two = !c->mean_nt4 && 3 * chain_wgs > 2 * 1024;
-                void *const fn = two ? c->upd_nt_mean8[kernel] : c->upd_nt_mean[kernel];
-                if ((rc = launch_nt_chains(c, fn, 0, c->N, c->B, ldn, c->xq_bpad, compact, c->cc_meta.p, two ? 256 : 512)))
-                    return rc;
-                c->sg.on = true;
-                c->sg.B = c->B;
-                c->sg.ldn = ldn;
-                c->sg.bpad = c->xq_bpad;
-                c->sg.compact = compact;
-                c->sg.kernel = kernel;
-                c->sg.sigma = sigma;
-                ++c->sg_stats[0];
-            } else if ((rc = launch_nt_chains(c, c->upd_nt[kernel], n0, nloc, c->B, ldn, c->xq_bpad, compact, c->cc_meta.p))) {
-                return rc;
-            }
-            sig_cols = compact ? -1 : (int)(quads * 4);
-        }
-        VSOM_HIP_CHECK(hipGetLastError());
-    }
-    if (sig_cols < 0) {
-        TimerScope ts(c, VSOM_T_SIGMA);
-        if ((rc = vsom_cc_expand(c, n0, nloc, deferred ? 1 : 3)))
+        if (plan.reads_staged_rows)
+            c->rows_free_valid = false;   // no stage-ahead behind an earlier range's event
+        rc = plan.path == VSOM_P2_CLR ? run_clr(c, plan, n0)
+             : plan.path == VSOM_P2_SMALL_MAP ? run_small_map(c, plan, n0) : run_quads(c, plan, sigma, n0);
+        if (rc)
             return rc;
-    }
-    if (sig_cols > 0 && !deferred) {
-        TimerScope ts(c, VSOM_T_SIGMA);
-        // the assembly kernels left raw S in those columns (CLR: in the A part and in the B part)
-        for (uint32_t part = 0; part < c->nparts; ++part)
-            hipLaunchKernelGGL(sigma_finalize_kernel, dim3((unsigned)nloc), dim3(256), 0, c->stream,
-                               c->sigma.p, c->map.p, (int)c->pitch, (int)(part * c->part_pitch), sig_cols,
-                               (int)c->part_len, (int)n0, (int)nloc, c->weight.p);
         VSOM_HIP_CHECK(hipGetLastError());
     }
+    if ((rc = run_after(c, plan, n0)))
+        return rc;
     return done();   // (joins the side stream: the MSE sum forked by launch_finish ran beside the kernels above)
 }
