@@ -187,7 +187,9 @@ int vsom_set_update_mode(vsom_ctx *ctx, int mode);
  *                     vsom_set_column_compaction, vsom_set_row_dedupe, vsom_enable_timing(_of), vsom_depth, vsom_nodes,
  *                     vsom_residual_len, vsom_chunk_size, vsom_pitch, vsom_chunk_pitch, vsom_small_map_chains,
  *                     vsom_device_ptr of every buffer but VSOM_BUF_SIGMA
- * (vsom_set_stream materialises.)  Partial node ranges, CLR, small maps (vsom_small_map_chains), group members, the masked
+ * (vsom_set_stream materialises.  So do the four vsom_batch_accum_* calls: the first of them materialises a pending record,
+ * vsom_batch_accum_end writes its sigmaMap eagerly, none of them defers or counts towards VSOM_SIGMA_AUTO's rule.)
+ * Partial node ranges, CLR, small maps (vsom_small_map_chains), group members, the masked
  * and custom epochs are always eager, and so is a context from the moment it joins an ensemble -- also after that
  * ensemble is destroyed.
  * The environment variable VSOM_SIGMA_MODE (auto / eager / lazy) sets the initial mode at vsom_create; any other value
@@ -554,6 +556,49 @@ int vsom_batch_epoch(vsom_ctx *ctx, double sigma, int is_first, float *mse_out);
  * words of (column, row) bits, 8 B bytes of BMU coordinates, 4 J bytes of column list and the search's slice scratch. */
 int vsom_batch_epoch_masked(vsom_ctx *ctx, double sigma, int is_first, const uint8_t *valid_host, int one_mask,
                             float *mse_out);
+/* [MI355X build; Som::trainBatchSom restarts every node's chain with every chunk (Som.cpp:843,870), so after a pass over a
+ * data set that loads in K chunks the map is the batch map of the LAST chunk alone]
+ * A batch epoch over ALL rows of a data set that loads in several chunks.  Call order:
+ *     vsom_batch_accum_begin(ctx, sigma, is_first, total_rows)
+ *     for every chunk k = 0 .. K-1 of B_k rows, sum B_k = total_rows:
+ *         load it (any staging call), optionally vsom_set_last_bmu (a load zeroes lastBMU), vsom_batch_accum_chunk(ctx)
+ *     vsom_batch_accum_end(ctx, &mse)
+ * The result equals, bit for bit, vsom_batch_epoch on the state at begin with the concatenated rows as ONE chunk and the
+ * concatenated lastBMU: per node the reference's chain is a sequential walk over the rows in load order that carries W, M_d
+ * and S_d; the walk is cut at the chunk borders and the three values are carried in buffers of the context.
+ *   begin   opens the epoch; the accumulators (2 N pitch + N floats, allocated once and kept) start at zero.  map, sigmaMap,
+ *           weightMap and S are untouched until end.
+ *   chunk   enqueues and does not block, like vsom_batch_epoch_async.  Phase 1 as vsom_batch_phase1_async(0, B, is_first)
+ *           against map, which still holds the epoch-start values: lastBMU and sqres of the chunk as phase 1 leaves them,
+ *           bmuHits incremented per row; the MSE word continues in sample order, mse = mse + sqres[s] / (float)total_rows.
+ *           Phase 2 for every node i and the chunk's rows j in load order: w = (float)h(i, lastBMU[j], sigma),
+ *           accW = accW + w, c = w / accW (correctly rounded, 0/0 -> NaN), and for every column d
+ *           delta = Stepper(x_jd, accM_d), accM_d = accM_d + c * delta, accS_d = accS_d + (w * delta) * delta -- the float
+ *           operations of the epoch's chain, unfused.  Standard and Median (D = J).  A chunk of 0 rows changes nothing.  The
+ *           chains read the staged rows: a vsom_prefetch_chunk behind it copies beside it and stages at vsom_commit_chunk.
+ *   end     blocks.  map = accM, sigmaMap = sqrt(accS / accW), weightMap = accW, pad columns as every epoch leaves them; S
+ *           is untouched; vsom_device_ptr values stay the same.  mse_out (may be NULL) and vsom_get_mse afterwards: the
+ *           running MSE.  With total_rows = 0 the state is that of vsom_batch_epoch on an empty chunk (map +0, sigmaMap NaN,
+ *           weightMap 0).  Closes the epoch.
+ *   abort   closes the epoch: map, sigmaMap, weightMap and S are what they were at begin.  bmuHits, lastBMU, sqres and the
+ *           MSE word keep what the chunk calls did to them.
+ * Between begin and end the staging calls (upload, _async, set_chunk_device, prefetch, commit, set / get_last_bmu, get_sqres)
+ * and read-only queries are legal; the queries see the epoch-start map.  A call that rewrites the model state in between
+ * (vsom_set_state, any other training call) is not refused, but the epoch is then no epoch of the reference: each chunk
+ * searches the map current at its call and end overwrites the state.  The accumulators are not reachable by other calls.
+ * Refuses (VSOM_ERR_INVALID, nothing enqueued, the state untouched, the context stays usable): every call a null context;
+ * begin while an epoch is open, custom and CLR contexts, an update mode other than VSOM_UPDATE_STRICT, a context that has
+ * joined a group or an ensemble; chunk, end and abort when no epoch is open; chunk when no chunk is loaded, with a chunk
+ * staged ahead over the current rows, or when the rows so far plus B exceed total_rows; end while the rows accumulated
+ * differ from total_rows (the epoch stays open: add the missing chunk or abort).
+ * Timed under VSOM_T_BMU (phase 1), VSOM_T_FINISH (MSE and hits), VSOM_T_CW (carried neighbourhood pass), VSOM_T_UPDATE
+ * (carried chains) and VSOM_T_SIGMA (end).  Device scratch per chunk: 8 B roundup(N, 64) bytes of (c, w) and 8 B bytes of
+ * BMU coordinates in the query arena.  Out of scope: CLR and custom contexts, the contracted update modes, groups and
+ * ensembles, a masked accumulating epoch, a deferred sigmaMap. */
+int vsom_batch_accum_begin(vsom_ctx *ctx, double sigma, int is_first, size_t total_rows);
+int vsom_batch_accum_chunk(vsom_ctx *ctx);
+int vsom_batch_accum_end(vsom_ctx *ctx, float *mse_out);
+int vsom_batch_accum_abort(vsom_ctx *ctx);
 /* MSE of the last finish / online chunk (synchronises) */
 int vsom_get_mse(vsom_ctx *ctx, float *mse_out);
 /* A whole batch schedule on the chunk currently loaded, in one call.  The result is, bit for bit,

@@ -54,6 +54,7 @@ SYMBOLS = [
     "vsom_bmu_masked_batch", "vsom_evaluate_batch", "vsom_generate_batch", "vsom_decode_nodes",
     "vsom_batch_epoch_masked", "vsom_batch_schedule", "vsom_ensemble_batch_schedule",
     "vsom_set_sigma_mode", "vsom_sigma_flush", "vsom_sigma_stats",
+    "vsom_batch_accum_begin", "vsom_batch_accum_chunk", "vsom_batch_accum_end", "vsom_batch_accum_abort",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -264,6 +265,11 @@ def lib():
     if hasattr(L, "vsom_batch_schedule"):
         L.vsom_batch_schedule.argtypes = [vp, dp, C.c_size_t, C.c_int, fp]
         L.vsom_ensemble_batch_schedule.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_size_t), C.c_int, C.POINTER(fp)]
+    if hasattr(L, "vsom_batch_accum_begin"):    # (VSOM_LIB may name an older build: tools/accum_bench.py --lib)
+        L.vsom_batch_accum_begin.argtypes = [vp, C.c_double, C.c_int, C.c_size_t]
+        L.vsom_batch_accum_chunk.argtypes = [vp]
+        L.vsom_batch_accum_end.argtypes = [vp, fp]
+        L.vsom_batch_accum_abort.argtypes = [vp]
     _lib = L
     return L
 
@@ -802,6 +808,34 @@ class Context:
         check(lib().vsom_batch_schedule(self._h, sg.ctypes.data_as(C.POINTER(C.c_double)), sg.size, int(bool(reset_bmu)),
                                         _f(mse)))
         return mse
+
+    def batch_accum_begin(self, sigma, is_first, total_rows):
+        """Open a batch epoch over a data set that loads in several chunks (vsom_batch_accum_begin): total_rows is the sum
+        of the rows of the chunks that batch_accum_chunk will be called on.  ValueError for a negative or non-integral
+        total_rows or a non-finite sigma, before any call into the library."""
+        sigma = float(sigma)
+        if not np.isfinite(sigma):
+            raise ValueError(f"sigma must be finite, got {sigma}")
+        if isinstance(total_rows, (bool, np.bool_)) or int(total_rows) != total_rows:
+            raise ValueError(f"total_rows must be a whole number, got {total_rows!r}")
+        if int(total_rows) < 0:
+            raise ValueError(f"total_rows must be >= 0, got {total_rows}")
+        check(lib().vsom_batch_accum_begin(self._h, sigma, int(bool(is_first)), int(total_rows)))
+
+    def batch_accum_chunk(self):
+        """the chunk currently loaded into the open epoch: search against the epoch-start map, then every node's chains
+        continue over its rows (enqueues, does not block)"""
+        check(lib().vsom_batch_accum_chunk(self._h))
+
+    def batch_accum_end(self):
+        """map, sigmaMap and weightMap of the whole epoch; returns its MSE (blocks)"""
+        mse = C.c_float()
+        check(lib().vsom_batch_accum_end(self._h, C.byref(mse)))
+        return np.float32(mse.value)
+
+    def batch_accum_abort(self):
+        """close the open epoch: map, sigmaMap, weightMap and S stay what they were at batch_accum_begin"""
+        check(lib().vsom_batch_accum_abort(self._h))
 
     def batch_epoch_masked(self, sigma, is_first, valid):
         """One batch epoch over the valid entries of the chunk only (vsom_batch_epoch_masked; Standard / Median, strict

@@ -1147,6 +1147,77 @@ int vsom_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uint8
     return vsom_get_mse(c, mse_out);
 }
 
+// ---- the accumulated epoch (vsom_accum.hip): ordinary entry points, a pending sigmaMap is materialised by the first ----
+
+int vsom_batch_accum_begin(vsom_ctx *c, double sigma, int is_first, size_t total_rows)
+{
+    CHECK_CTX(c);
+    VSOM_CUSTOM_REFUSE(c, "vsom_batch_accum_begin");
+    if (c->transform == VSOM_CLR)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_begin: CLR contexts are not supported (the chains run over column pairs)");
+    if (c->update_mode != VSOM_UPDATE_STRICT)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_begin: the carried chains exist in the strict update mode only");
+    if (c->in_group || c->sigma_shared)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_begin: the context has joined a group or an ensemble");
+    if (c->ac.open)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_begin: an accumulated epoch is already open");
+    if (total_rows > 0x7FFFFFFFull)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_begin: total_rows too large");
+    if (int rc = launch_accum_begin(c))
+        return rc;
+    c->ac.open = true;
+    c->ac.sigma = sigma;
+    c->ac.is_first = is_first;
+    c->ac.total = total_rows;
+    c->ac.rows = 0;
+    return VSOM_OK;
+}
+
+int vsom_batch_accum_chunk(vsom_ctx *c)
+{
+    CHECK_CTX(c);
+    if (!c->ac.open)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_chunk: no accumulated epoch is open");
+    CHECK_ROWS(c);
+    if (!c->chunk_loaded)   // an EMPTY chunk is legal and changes nothing
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    if (c->ac.rows + c->B > c->ac.total)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_chunk: the chunk's " + std::to_string(c->B) + " rows exceed total_rows (" +
+                                               std::to_string(c->ac.rows) + " of " + std::to_string(c->ac.total) + " accumulated)");
+    if (c->B == 0)
+        return VSOM_OK;
+    if (int rc = launch_accum_chunk(c))
+        return rc;
+    c->ac.rows += c->B;
+    return VSOM_OK;
+}
+
+int vsom_batch_accum_end(vsom_ctx *c, float *mse_out)
+{
+    CHECK_CTX(c);
+    if (!c->ac.open)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_end: no accumulated epoch is open");
+    if (c->ac.rows != c->ac.total)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_end: " + std::to_string(c->ac.rows) + " of total_rows = " +
+                                               std::to_string(c->ac.total) + " rows accumulated (the epoch stays open)");
+    if (int rc = launch_accum_end(c))
+        return rc;
+    c->ac.open = false;
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    if (mse_out)
+        *mse_out = *static_cast<volatile float *>(c->mse.p);
+    return VSOM_OK;
+}
+
+int vsom_batch_accum_abort(vsom_ctx *c)
+{
+    CHECK_CTX(c);
+    if (!c->ac.open)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_abort: no accumulated epoch is open");
+    c->ac.open = false;     // (chunks still running write the accumulators only)
+    return VSOM_OK;
+}
+
 void *vsom_device_ptr(vsom_ctx *c, int which)
 {
     if (!c)

@@ -244,6 +244,17 @@ struct vsom_ctx {
 
     bool in_group = false;          // a member of a vsom_group (vsom_group.hip): ensembles refuse it
 
+    // Accumulated epoch (vsom_accum.hip): between vsom_batch_accum_begin and _end / _abort the chains of every node continue
+    // in acc_M / acc_S (N x pitch) and acc_W (N) from where the previous chunk left them, acc_mse is the running MSE word
+    // and `rows` counts what has been accumulated.  The buffers are the feature's own: allocated by the first begin, kept.
+    struct AccumEpoch {
+        bool open = false;
+        double sigma = 0.0;
+        int is_first = 0;
+        size_t total = 0, rows = 0;
+    } ac;
+    DevBuf<float> acc_M, acc_S, acc_W, acc_mse;
+
     // caller-defined transformation (vsom_create_custom, vsom_custom.hip); null for the built-in ones
     vsom_custom_state *cu = nullptr;
 };
@@ -358,6 +369,12 @@ int vsom_masked_search_enqueue(vsom_ctx *c, u64 min_hits, size_t s0, size_t s1, 
                                unsigned *nvalid);
 // vsom_masked_train.hip: the batch epoch over valid columns only (arguments checked by vsom_batch_epoch_masked); synchronises
 int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uint8_t *valid_host, int one_mask);
+// vsom_accum.hip: the accumulated epoch (state and arguments checked by vsom_batch_accum_*); they enqueue only.  begin:
+// the accumulators allocated and zeroed; chunk: phase 1, MSE / hits and the carried phase 2 of the loaded chunk (B > 0),
+// with the sigma and is_first of c->ac; end: map, sigmaMap, weightMap and the MSE word from the accumulators
+int launch_accum_begin(vsom_ctx *c);
+int launch_accum_chunk(vsom_ctx *c);
+int launch_accum_end(vsom_ctx *c);
 int launch_raw_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *vrows_dev, size_t count, int from_map,
                     float *out_dev);
 // vsom_umatrix.hip: Som::updateUMatrix of the current map / sigmaMap into ctx->umatrix; enqueues only.

@@ -454,6 +454,16 @@ public:
     // state, the metrics and the rows' lastBMU are trainBatchSom's bit for bit.  Throws std::invalid_argument before it
     // trains when the first load does not read the whole stream.  One device only.
     void trainBatchSomResident(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay);
+    // [MI355X build] extension: trainBatchSom's driver with ONE batch epoch per pass over the stream -- the chunks of a
+    // pass accumulate into one epoch over all rows (vsom_batch_accum_begin / _chunk / _end, include/vsom_hip.h), where
+    // trainBatchSom runs an epoch per chunk and ends a pass with the batch map of its last chunk alone.  The same sigma
+    // schedule and stop at sigma < 1; MeanSquaredError[i] is the MSE of epoch i over all rows; updateUMatrix runs after
+    // the epoch's end.  A DataSet cannot tell how many rows its stream holds, so the stream is read once before the first
+    // epoch to count them.  resetBmu = true is the reference's behaviour (a load zeroes lastBMU: the epochs after the
+    // first walk from unit 0); with false every row's BMU of the previous epoch starts that row's walk.  Chunk k+1 is
+    // loaded and copied while chunk k accumulates.  Standard / Median on one device only.
+    void trainBatchSomWhole(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
+                            bool updateUMatrixAfterEpoch = false, bool resetBmu = true);
     TrainingReturnValue trainSingle(const Eigen::VectorXf &v, const Eigen::VectorXf &valid,
                                     const Eigen::VectorXf &weights, const double eta, const double sigma,
                                     size_t &lastBMU, const WeigthDecayFunction weightDecayFunction);

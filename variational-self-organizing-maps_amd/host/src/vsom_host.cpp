@@ -1221,6 +1221,88 @@ void Som::trainBatchSomMasked(DataSet &data, size_t numberOfEpochs, double sigma
     }
 }
 
+// Som.cpp:716-754 with one epoch per pass: every chunk of the pass continues the chains of the one before it
+// (vsom_batch_accum_*).  No refreshHost() inside the loop.
+void Som::trainBatchSomWhole(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
+                             bool updateUMatrixAfterEpoch, bool resetBmu)
+{
+    requireDevicePath("trainBatchSomWhole");
+    if (grp)
+        throw std::runtime_error("trainBatchSomWhole: a multi-GPU Som has no accumulated epoch (vsom_batch_accum_* "
+                                 "run on one context)");
+    {
+        const std::lock_guard<std::mutex> lock(metricsMutex);   // (the reference resets without it: trainBatchSom)
+        metrics = Som::Metrics(numberOfEpochs);
+    }
+    if (numberOfEpochs == 0 || sigma0 < 1.0)
+        return;   // :729-730 at the first epoch
+    size_t total = 0;             // the counting pass
+    while (!data.hasReadWholeDataStream()) {
+        data.loadNextDataFromStream();
+        total += data.size();
+    }
+    data.resetStreamLoadPosition();
+    std::vector<uint64_t> prev(resetBmu ? 0 : total), lb;
+    struct Guard {                // an exception between begin and end leaves no epoch open
+        vsom_ctx *c;
+        bool open = false;
+        ~Guard()
+        {
+            if (open)
+                (void)vsom_batch_accum_abort(c);
+        }
+    } guard{ctx};
+    for (size_t i = 0; i < numberOfEpochs; ++i) {
+        std::cout << "Training VSOM epoch " << i << "/" << numberOfEpochs << '\n';
+        const auto sigma = sigma0 * std::exp(-sigmaDecay * static_cast<double>(i));   // :727
+        if (sigma < 1.0)
+            return;   // :729-730
+        check(vsom_batch_accum_begin(ctx, sigma, i == 0 ? 1 : 0, total), "vsom_batch_accum_begin");
+        guard.open = true;
+        size_t off = 0, B = 0;
+        bool have = !data.hasReadWholeDataStream();   // :735
+        if (have) {
+            data.loadNextDataFromStream();
+            B = data.size();
+            check(vsom_prefetch_chunk(ctx, data.contiguous(), B), "vsom_prefetch_chunk");
+        }
+        while (have) {
+            const size_t Bcur = B;
+            check(vsom_commit_chunk(ctx), "vsom_commit_chunk");   // lastBMU := 0 (DataSet.cpp:136-137)
+            if (!resetBmu && i > 0 && Bcur > 0)
+                check(vsom_set_last_bmu(ctx, prev.data() + off), "vsom_set_last_bmu");
+            check(vsom_batch_accum_chunk(ctx), "vsom_batch_accum_chunk");
+            have = !data.hasReadWholeDataStream();
+            if (have) {           // host work and the copy beside the device's chains
+                data.loadNextDataFromStream();
+                B = data.size();
+                check(vsom_prefetch_chunk(ctx, data.contiguous(), B), "vsom_prefetch_chunk");
+            }
+            if ((!resetBmu || !have) && Bcur > 0) {
+                lb.resize(Bcur);
+                check(vsom_get_last_bmu(ctx, lb.data()), "vsom_get_last_bmu");
+                if (!resetBmu)
+                    std::copy(lb.begin(), lb.end(), prev.begin() + (std::ptrdiff_t)off);
+                if (!have)        // the chunk the data set still holds keeps its BMUs (Som.cpp:777,800)
+                    for (size_t s = 0; s < Bcur; ++s)
+                        data.getLastBMU(s) = (size_t)lb[s];
+            }
+            off += Bcur;
+        }
+        float mse = 0.f;
+        check(vsom_batch_accum_end(ctx, &mse), "vsom_batch_accum_end");
+        guard.open = false;
+        hostStale = true;
+        {
+            const std::lock_guard<std::mutex> lock(metricsMutex);
+            metrics.MeanSquaredError[i] = mse;
+        }
+        data.resetStreamLoadPosition();   // :749
+        if (updateUMatrixAfterEpoch)
+            updateUMatrix(data.getWeights());   // :751-752
+    }
+}
+
 // Som.cpp:716-754 for a one-chunk data set: the chunk stays on the device and one vsom_batch_schedule call runs every
 // epoch (reset_bmu: each epoch's walk starts from unit 0, as after the reference's per-epoch reload, DataSet.cpp:136-137)
 void Som::trainBatchSomResident(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay)

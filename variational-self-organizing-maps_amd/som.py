@@ -168,6 +168,10 @@ class ArrayDataSet:
     def size(self):
         return self.data.shape[0]
 
+    def totalRows(self):
+        """extension: the rows of the whole stream (trainBatchSomWhole asks for it)"""
+        return self.X.shape[0]
+
     def isAtStartOfDataStream(self):
         return self._pos == 0
 
@@ -607,6 +611,80 @@ class Som:
             data.resetStreamLoadPosition()
             if updateUMatrixAfterEpoch:
                 self.updateUMatrix(data.getWeights())             # :751-752 / :1183-1184
+
+    @staticmethod
+    def _streamRows(data):
+        """the rows of the whole stream: the data set's totalRows() or len(), else one counting pass over the stream"""
+        if hasattr(data, "totalRows"):
+            return int(data.totalRows())
+        if hasattr(data, "__len__"):
+            return len(data)
+        total = 0
+        while not data.hasReadWholeDataStream():
+            data.loadNextDataFromStream()
+            total += data.size()
+        data.resetStreamLoadPosition()
+        return total
+
+    def trainBatchSomWhole(self, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch=False, reset_bmu=True):
+        """extension: trainBatchSom's driver with ONE batch epoch per pass over the stream -- the chunks of a pass
+        accumulate into one epoch over all rows (capi.Context.batch_accum_begin / _chunk / _end), where trainBatchSom runs
+        an epoch per chunk and ends a pass with the batch map of its last chunk alone.  The same sigma schedule and stop
+        at sigma < 1; metrics.MeanSquaredError[i] is the MSE of epoch i over all rows; updateUMatrix runs after the
+        epoch's end.  The row count of the stream comes from data.totalRows() or len(data); a data set with neither is
+        streamed once before the first epoch to count its rows.
+        reset_bmu=True is the reference's behaviour: a load zeroes lastBMU, so the epochs after the first walk from unit
+        0.  With reset_bmu=False every row's BMU of the previous epoch is kept (a host array of one entry per row) and
+        starts that row's walk.  Chunk k+1 is copied to the device (prefetch / commit) while chunk k accumulates.
+        Standard and Median on one device, strict update mode."""
+        self.metrics = Metrics(numberOfEpochs)                    # :719
+        sigmas = batch_sigma_schedule(numberOfEpochs, sigma0, sigmaDecay)
+        if not sigmas:
+            return
+        total = self._streamRows(data)
+        prev = None if reset_bmu else np.zeros(total, np.uint64)
+        ctx = self.ctx
+        for i, sigma in enumerate(sigmas):
+            if self._verbose:
+                print(f"Training VSOM epoch {i}/{numberOfEpochs}")
+            ctx.batch_accum_begin(sigma, i == 0, total)
+            try:
+                off = 0
+                rows = None                                       # the rows on their way to the device: kept alive
+                have = not data.hasReadWholeDataStream()          # :735
+                if have:
+                    data.loadNextDataFromStream()
+                    rows = np.ascontiguousarray(data.data, dtype=np.float32)
+                    ctx.prefetch_chunk(rows)
+                while have:
+                    ctx.commit_chunk()                            # lastBMU := 0 (DataSet.cpp:136-137)
+                    B, lb_ref = rows.shape[0], data.lastBMU
+                    if prev is not None and i > 0:
+                        ctx.set_last_bmu(prev[off:off + B])
+                    ctx.batch_accum_chunk()
+                    have = not data.hasReadWholeDataStream()
+                    if have:                                      # the next chunk's load and copy beside this one's chains
+                        data.loadNextDataFromStream()
+                        rows = np.ascontiguousarray(data.data, dtype=np.float32)
+                        ctx.prefetch_chunk(rows)
+                    if prev is not None or not have:
+                        lb = ctx.get_last_bmu()
+                        if prev is not None:
+                            prev[off:off + B] = lb
+                        if not have:
+                            lb_ref[...] = lb                      # the chunk the data set still holds keeps its BMUs
+                    off += B
+                mse = ctx.batch_accum_end()
+            except BaseException:
+                try:
+                    ctx.batch_accum_abort()
+                except capi.VsomError:
+                    pass
+                raise
+            self.metrics.MeanSquaredError[i] = mse
+            data.resetStreamLoadPosition()                        # :749
+            if updateUMatrixAfterEpoch:
+                self.updateUMatrix(data.getWeights())             # :751-752
 
     def trainBatchSomResident(self, data, numberOfEpochs, sigma0, sigmaDecay):
         """extension: trainBatchSom for a data set that is ONE chunk, with the chunk uploaded once and the whole sigma
