@@ -647,7 +647,7 @@ int vsom_train_online_chunk_acc(vsom_ctx *ctx, double eta, double sigma, int dec
  * stores into -- one launch and one stream wait per chunk (the reference's own 10 x 10 x 9 scenario). */
 int vsom_train_online_chunk_fetch(vsom_ctx *ctx, double eta, double sigma, int decay_fn, int first_chunk,
                                   uint64_t *lastbmu_out, float *mse_out);
-/* diagnostics of the chunk loop's image-bounded search (csrc/vsom_online.hip; synchronises): out[0] = samples searched
+/* diagnostics of the chunk loop's image-bounded search (csrc/vsom_online_i8.hip; synchronises): out[0] = samples searched
  * through the image since the last reset, out[1] = nodes evaluated exactly for them (the candidates that survived the
  * bound), out[2] = refinement workgroups that had a candidate, out[3] = 0.  All zero while the exact scan is in use. */
 int vsom_get_online_search_stats(vsom_ctx *ctx, uint64_t *out /*[4]*/, int reset);

@@ -68,7 +68,7 @@ def _run_online_case(W, H, J, tr, fn, B, sigma, X, init, eta, mode=None, reps=2)
     ctx.close()
 
 
-# The chunk loop's image-bounded search (csrc/vsom_online.hip, "Image-bounded search": sigma > 1, Standard / Median):
+# The chunk loop's image-bounded search (csrc/vsom_online_i8.hip: sigma > 1, Standard / Median):
 # VSOM_BMU_SHORTLIST forces it on every map size, so every case of the table above that it covers runs through it too --
 # ragged node counts, depths with every remainder class of Eigen's reduction, windows larger than the map
 I8_CASES = [c for c in CASES if c[4] != 2 and c[7] > 1]

@@ -94,7 +94,7 @@ def test_random_shape(name, tr, W, H, J, B, sigma, seed):
             for k, ref in (("map", orc.map), ("sigma", orc.sigma), ("S", orc.S), ("weight", orc.weight), ("hits", orc.hits)):
                 assert _same(st[k], ref), (name, sg, mode, "online " + k)
     ctx.set_bmu_mode(capi.BMU_AUTO)
-    # and the same chunk once more through the image-bounded search of the chunk loop (csrc/vsom_online.hip; forced: these
+    # and the same chunk once more through the image-bounded search of the chunk loop (csrc/vsom_online_i8.hip; forced: these
     # maps are far below the size VSOM_BMU_AUTO takes it for): random shapes, scales 0.1 / 1 / 50, exact zeros
     if tr != capi.CLR and D <= 1024:
         ctx.set_bmu_mode(capi.BMU_SHORTLIST)

@@ -180,6 +180,8 @@ int vsom_adopt_ahead(vsom_ctx *c)
     return VSOM_OK;
 }
 
+// the staged chunk against the map.  (One row that is not part of the chunk -- the online step's sample, a single-vector
+// query: vsom_onl_args, vsom_online.hip, which takes the model half from here.)
 DistArgs vsom_dist_args(const vsom_ctx *c)
 {
     DistArgs a;

@@ -42,53 +42,6 @@ TimerScope::~TimerScope()
 
 static inline uint32_t roundup(uint32_t v, uint32_t m) { return (v + m - 1) / m * m; }
 
-#define CHECK_CTX(ctx)                                                 \
-    do {                                                               \
-        if (!(ctx))                                                    \
-            return vsom_fail(VSOM_ERR_INVALID, "null context");        \
-        hipError_t _e = hipSetDevice((ctx)->device);                   \
-        if (_e != hipSuccess)                                          \
-            return vsom_fail(VSOM_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_e)); \
-        if (int _rc = vsom_join_aux(ctx))                              \
-            return _rc;                                                \
-        (ctx)->rows_free_valid = false;   /* whatever follows may read the staged rows again */ \
-    } while (0)
-// The same for the entry points that provably never read sigmaMap and overwrite nothing a pending one is made from (chunk
-// staging, the batch phases, the MSE and lastBMU read-backs, timing, statistics, synchronisation): a pending sigmaMap stays
-// pending (vsom_internal.hpp, vsom_ctx::sg).  CHECK_CTX is the default and materialises it -- an entry point missing
-// here costs time, one wrongly listed here would cost correctness.
-#define CHECK_CTX_KEEP(ctx)                                            \
-    do {                                                               \
-        if (!(ctx))                                                    \
-            return vsom_fail(VSOM_ERR_INVALID, "null context");        \
-        hipError_t _e = hipSetDevice((ctx)->device);                   \
-        if (_e != hipSuccess)                                          \
-            return vsom_fail(VSOM_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_e)); \
-        if (int _rc = vsom_join_aux_keep(ctx))                         \
-            return _rc;                                                \
-        (ctx)->rows_free_valid = false;                                \
-    } while (0)
-// Entry points that READ the staged rows (Xs / XP / YP, the gathered rows, the int8 images): once the NEXT chunk has been
-// staged ahead (vsom_prefetch_chunk / vsom_stage_next_device beside a running epoch) those buffers hold the next chunk's
-// rows while B, lastBMU and the compaction record still describe the current one -- a search would silently mix the two.
-// (ahead_rows, not ahead_valid: a staged-ahead chunk that was abandoned for another one has overwritten the rows all the same.)
-#define CHECK_ROWS(ctx)                                                \
-    do {                                                               \
-        if ((ctx)->ahead_rows)                                         \
-            return vsom_fail(VSOM_ERR_INVALID,                         \
-                             "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first"); \
-    } while (0)
-// phase 2 runs beside the side stream's work and joins it at its end (a pending sigmaMap is its own business); the
-// copy-stream calls touch neither
-#define CHECK_CTX_NOJOIN(ctx)                                          \
-    do {                                                               \
-        if (!(ctx))                                                    \
-            return vsom_fail(VSOM_ERR_INVALID, "null context");        \
-        hipError_t _e = hipSetDevice((ctx)->device);                   \
-        if (_e != hipSuccess)                                          \
-            return vsom_fail(VSOM_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_e)); \
-    } while (0)
-
 // ---- pieces of the double-buffered ingest shared with the multi-GPU group (vsom_group.hip) -------------
 // Rows [r0,r1) of a B-row host chunk -> the same rows of the context's NEXT raw device buffer, on the
 // copy stream (a group copies each device's shard only and all-gathers the rest over xGMI).

@@ -4,7 +4,7 @@
 //
 // A custom context is an ordinary vsom_ctx (state, chunk rows, lastBMU, the pinned MSE word, the stream) whose
 // model rows are unpadded (pitch = D) and whose chunk rows are unpadded (xpitch = J); `cu` holds the rest.  The
-// entry points that accept a custom context route here from vsom_capi.hip / vsom_online.hip; all others refuse it.
+// entry points that accept a custom context route here from vsom_capi.hip / vsom_online.hip / vsom_single.hip; all others refuse it.
 #include "vsom_internal.hpp"
 
 #include <hip/hiprtc.h>

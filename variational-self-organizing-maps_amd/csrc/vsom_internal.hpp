@@ -38,7 +38,7 @@ typedef unsigned long long u64;
 // spare rows behind the staged sample matrices (readable, contents unspecified: zero at allocation, stale
 // samples after a larger chunk): the pipelined update kernels read ahead into them and never consume them
 constexpr size_t VSOM_ROW_PAD = 32;
-// bytes of vsom_ctx::onl_state (layout: vsom_online.hip)
+// bytes of vsom_ctx::onl_state (layout: vsom_online.hpp)
 constexpr size_t VSOM_ONL_STATE_BYTES = 4352;
 
 struct vsom_custom_state;
@@ -214,9 +214,9 @@ struct vsom_ctx {
     DevBuf<float> v_dev;            // one sample, padded
     PinnedBuf<float> v_pinned;      // its pinned host staging (+ 16 floats for results)
     DevBuf<float> res_dev;          // residual
-    DevBuf<u64> onl_state;          // argmin key slots + flags of the online scan (vsom_online.hip)
+    DevBuf<u64> onl_state;          // argmin key slots + flags of the online scan (vsom_online.hpp)
     DevBuf<float> onl_f;            // [4]: dist, mse
-    // image-bounded search of the online chunk loop (vsom_online.hip): one byte per model value + 4 scalars per node,
+    // image-bounded search of the online chunk loop (vsom_online_i8.hip): one byte per model value + 4 scalars per node,
     // lower bounds of the sample being searched, min-upper-bound slots, per-sample bound terms
     DevBuf<unsigned char> onl_img; DevBuf<float4> onl_nsc; DevBuf<float> onl_lb; DevBuf<unsigned> onl_u;
     DevBuf<float4> onl_xsc;
@@ -277,6 +277,54 @@ int vsom_fail(int code, const std::string &msg);
 #define VSOM_HIP_CHECK(expr) VSOM_HIP_CHECK_AS(expr, #expr)
 // vsom_grow / vsom_grow_set: the message names the allocation
 #define VSOM_ALLOC_CHECK(expr) VSOM_HIP_CHECK_AS(expr, "hipMalloc in " #expr)
+
+// the gate of the entry points (vsom_capi.hip and the files that define entry points of their own) ------------------
+#define CHECK_CTX(ctx)                                                 \
+    do {                                                               \
+        if (!(ctx))                                                    \
+            return vsom_fail(VSOM_ERR_INVALID, "null context");        \
+        hipError_t _e = hipSetDevice((ctx)->device);                   \
+        if (_e != hipSuccess)                                          \
+            return vsom_fail(VSOM_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_e)); \
+        if (int _rc = vsom_join_aux(ctx))                              \
+            return _rc;                                                \
+        (ctx)->rows_free_valid = false;   /* whatever follows may read the staged rows again */ \
+    } while (0)
+// The same for the entry points that provably never read sigmaMap and overwrite nothing a pending one is made from (chunk
+// staging, the batch phases, the MSE and lastBMU read-backs, timing, statistics, synchronisation): a pending sigmaMap stays
+// pending (vsom_internal.hpp, vsom_ctx::sg).  CHECK_CTX is the default and materialises it -- an entry point missing
+// here costs time, one wrongly listed here would cost correctness.
+#define CHECK_CTX_KEEP(ctx)                                            \
+    do {                                                               \
+        if (!(ctx))                                                    \
+            return vsom_fail(VSOM_ERR_INVALID, "null context");        \
+        hipError_t _e = hipSetDevice((ctx)->device);                   \
+        if (_e != hipSuccess)                                          \
+            return vsom_fail(VSOM_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_e)); \
+        if (int _rc = vsom_join_aux_keep(ctx))                         \
+            return _rc;                                                \
+        (ctx)->rows_free_valid = false;                                \
+    } while (0)
+// Entry points that READ the staged rows (Xs / XP / YP, the gathered rows, the int8 images): once the NEXT chunk has been
+// staged ahead (vsom_prefetch_chunk / vsom_stage_next_device beside a running epoch) those buffers hold the next chunk's
+// rows while B, lastBMU and the compaction record still describe the current one -- a search would silently mix the two.
+// (ahead_rows, not ahead_valid: a staged-ahead chunk that was abandoned for another one has overwritten the rows all the same.)
+#define CHECK_ROWS(ctx)                                                \
+    do {                                                               \
+        if ((ctx)->ahead_rows)                                         \
+            return vsom_fail(VSOM_ERR_INVALID,                         \
+                             "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first"); \
+    } while (0)
+// phase 2 runs beside the side stream's work and joins it at its end (a pending sigmaMap is its own business); the
+// copy-stream calls touch neither
+#define CHECK_CTX_NOJOIN(ctx)                                          \
+    do {                                                               \
+        if (!(ctx))                                                    \
+            return vsom_fail(VSOM_ERR_INVALID, "null context");        \
+        hipError_t _e = hipSetDevice((ctx)->device);                   \
+        if (_e != hipSuccess)                                          \
+            return vsom_fail(VSOM_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(_e)); \
+    } while (0)
 
 struct TimerScope {
     vsom_ctx *c; int which; vsom_ctx::Ev ev; bool on;
@@ -417,7 +465,7 @@ constexpr int VSOM_ONL_TINY_GROUPS = 12, VSOM_TINY_GROUPS = 3;
 size_t vsom_onl_tiny_desc_bytes();  // (descriptors are packed at exactly this size: the kernels index args[blockIdx.x])
 int vsom_onl_tiny_prepare(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk, bool want_lb,
                           size_t lds_limit, void *desc, int *group, size_t *smem, int *lut_slot);
-// before any launch of the call: the instantiation's dynamic LDS limit (process-wide, raised only; vsom_online.hip)
+// before any launch of the call: the instantiation's dynamic LDS limit (process-wide, raised only; vsom_online_tiny.hip)
 int vsom_onl_tiny_ready(int group, int device, size_t lds_limit);
 int vsom_onl_tiny_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
 void vsom_onl_tiny_done(vsom_ctx *c, int lut_slot);

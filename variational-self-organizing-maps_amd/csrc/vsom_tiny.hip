@@ -25,8 +25,8 @@ struct TinyArgs {
     int luth;                                       // table rows (the table is copied into LDS)
 };
 
-__device__ __forceinline__ float tiny_sign(float a)   // as vsom_update.hip's vsom_sign (see there)
-{
+__device__ __forceinline__ float tiny_sign(float a)   // Transformation::Stepper's sign (Transformation.cpp:49-50):
+{                                                     // +-1; a zero or a NaN comes back as it is
     const float one = __builtin_copysignf(1.f, a);
     return (a < 0.f || a > 0.f) ? one : a;
 }
