@@ -594,11 +594,35 @@ int vsom_batch_epoch_masked(vsom_ctx *ctx, double sigma, int is_first, const uin
  * Timed under VSOM_T_BMU (phase 1), VSOM_T_FINISH (MSE and hits), VSOM_T_CW (carried neighbourhood pass), VSOM_T_UPDATE
  * (carried chains) and VSOM_T_SIGMA (end).  Device scratch per chunk: 8 B roundup(N, 64) bytes of (c, w) and 8 B bytes of
  * BMU coordinates in the query arena.  Out of scope: CLR and custom contexts, the contracted update modes, groups and
- * ensembles, a masked accumulating epoch, a deferred sigmaMap. */
+ * ensembles, a deferred sigmaMap. */
 int vsom_batch_accum_begin(vsom_ctx *ctx, double sigma, int is_first, size_t total_rows);
 int vsom_batch_accum_chunk(vsom_ctx *ctx);
 int vsom_batch_accum_end(vsom_ctx *ctx, float *mse_out);
 int vsom_batch_accum_abort(vsom_ctx *ctx);
+/* The chunk call of an accumulated epoch over the VALID entries of the chunk only: legal wherever
+ * vsom_batch_accum_chunk is, in any mix with it, refused for the same reasons and for a null valid_host.  valid_host and
+ * one_mask as in vsom_batch_epoch_masked: B x J bytes, nonzero = valid, or with one_mask one row of J bytes applied to every
+ * row of the chunk.  It is not read after the call returns (it is copied into pinned memory of the context); the call
+ * enqueues and does not wait for the stream.
+ * begin, K chunk calls (masked or plain; a plain chunk counts as all valid) and end leave, bit for bit (NaN == NaN), what
+ * vsom_batch_epoch_masked leaves on the state at begin with the concatenated rows as ONE chunk, the concatenated validity
+ * and the concatenated lastBMU: map, sigmaMap, weightMap, bmuHits, every chunk's lastBMU and sqres, the MSE.
+ *   Phase 1 as in vsom_batch_epoch_masked (the masked tile walk when is_first, the masked local walk from lastBMU otherwise)
+ *   against map, which keeps its epoch-start values; hits and the running MSE as for vsom_batch_accum_chunk.
+ *   Phase 2: for node i and column d the rows are walked in load order across all chunks; a row invalid at d is skipped, a
+ *   valid one does  w = (float)h(i, lastBMU[j], sigma), W_d = W_d + w, delta = Stepper(x, M_d), M_d = M_d + (w / W_d) * delta,
+ *   S_d = S_d + (w * delta) * delta  (unfused, a correctly rounded division).  A column that had an invalid entry in some
+ *   chunk of the epoch carries M_d, S_d and W_d in side buffers of the context (3 J roundup(N, 64) floats, allocated by the
+ *   first masked chunk and kept); every other column is the unmasked epoch's.  What x holds at an invalid position (NaN,
+ *   inf) has no effect on any output.
+ *   end: map = M_d, sigmaMap = sqrt(S_d / W_d), weightMap = the sum of w over ALL rows; a column without a valid row in the
+ *   whole epoch is +0 / NaN.  abort restores as it does for plain chunks.
+ * A plain vsom_batch_accum_chunk in an epoch that has had a masked chunk also walks the columns that were dirty so far, with
+ * every entry valid; in an epoch without a masked chunk its launches and results are unchanged.
+ * Timed under VSOM_T_STAGE (validity staging, bits, dirty columns), VSOM_T_BMU, VSOM_T_FINISH, VSOM_T_CW, VSOM_T_UPDATE (the
+ * masked chains too) and VSOM_T_SIGMA.  Device scratch per masked chunk in the query arena: that of vsom_batch_accum_chunk
+ * and of vsom_batch_epoch_masked; pinned: 2 B J validity bytes (two halves used alternately). */
+int vsom_batch_accum_chunk_masked(vsom_ctx *ctx, const uint8_t *valid_host, int one_mask);
 /* MSE of the last finish / online chunk (synchronises) */
 int vsom_get_mse(vsom_ctx *ctx, float *mse_out);
 /* A whole batch schedule on the chunk currently loaded, in one call.  The result is, bit for bit,

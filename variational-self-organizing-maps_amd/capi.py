@@ -55,6 +55,7 @@ SYMBOLS = [
     "vsom_batch_epoch_masked", "vsom_batch_schedule", "vsom_ensemble_batch_schedule",
     "vsom_set_sigma_mode", "vsom_sigma_flush", "vsom_sigma_stats",
     "vsom_batch_accum_begin", "vsom_batch_accum_chunk", "vsom_batch_accum_end", "vsom_batch_accum_abort",
+    "vsom_batch_accum_chunk_masked",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -270,6 +271,8 @@ def lib():
         L.vsom_batch_accum_chunk.argtypes = [vp]
         L.vsom_batch_accum_end.argtypes = [vp, fp]
         L.vsom_batch_accum_abort.argtypes = [vp]
+    if hasattr(L, "vsom_batch_accum_chunk_masked"):     # (VSOM_LIB may name an older build: tools/accum_masked_bench.py --lib)
+        L.vsom_batch_accum_chunk_masked.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int]
     _lib = L
     return L
 
@@ -826,6 +829,18 @@ class Context:
         """the chunk currently loaded into the open epoch: search against the epoch-start map, then every node's chains
         continue over its rows (enqueues, does not block)"""
         check(lib().vsom_batch_accum_chunk(self._h))
+
+    def batch_accum_chunk_masked(self, valid):
+        """batch_accum_chunk over the valid entries of the chunk only (vsom_batch_accum_chunk_masked): the search on the
+        masked distance, and per column the carried chain over the rows valid at that column.  valid: B x J (nonzero =
+        valid), or a 1-D column mask of J entries applied to every row; ValueError for another shape, before any call
+        into the library.  The array is not read after the call returns (enqueues, does not block)."""
+        B = self.chunk_size
+        vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        one = vb.ndim == 1
+        if vb.shape != ((self.in_len,) if one else (B, self.in_len)):
+            raise ValueError(f"valid has shape {vb.shape}, neither ({self.in_len},) nor ({B}, {self.in_len})")
+        check(lib().vsom_batch_accum_chunk_masked(self._h, vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one)))
 
     def batch_accum_end(self):
         """map, sigmaMap and weightMap of the whole epoch; returns its MSE (blocks)"""

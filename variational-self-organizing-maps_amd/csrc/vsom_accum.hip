@@ -23,6 +23,9 @@
 //                          no LDS, no scratch.
 // and at the end of the epoch
 //  accum_end_kernel      : map = accM, sigmaMap = sqrt(accS / accW), weightMap = accW; pad columns zero
+// A chunk may come with validity bytes (vsom_batch_accum_chunk_masked): the columns that had an invalid entry in some chunk
+// of the epoch are carried beside these accumulators by vsom_accum_masked.hip; the kernels here run
+// over all columns either way.
 #include "vsom_device.hpp"
 #include <algorithm>
 
@@ -248,22 +251,58 @@ int launch_accum_begin(vsom_ctx *c)
     VSOM_HIP_CHECK(hipMemsetAsync(c->acc_S.p, 0, nd * sizeof(float), c->stream));       // :844
     VSOM_HIP_CHECK(hipMemsetAsync(c->acc_W.p, 0, (size_t)c->N * sizeof(float), c->stream));   // :840
     VSOM_HIP_CHECK(hipMemsetAsync(c->acc_mse.p, 0, sizeof(float), c->stream));
-    return VSOM_OK;
+    c->ac.masked = false;
+    return vsom_accum_masked_reset(c);      // no ever-dirty column (nothing to do before the first masked chunk)
 }
 
-// the loaded chunk (B > 0 rows) into the open epoch; enqueues only
-int launch_accum_chunk(vsom_ctx *c)
+// the loaded chunk (B > 0 rows) into the open epoch; enqueues only.  valid_host: the masked call --
+// the search runs on the masked distance, and the columns that are dirty in this chunk join the ever-dirty columns, whose
+// chains (vsom_accum_masked.hip) run before the carried pass below touches the accumulators.  Without a mask the launches
+// are the ones listed at the top of this file, plus -- once the epoch has had a masked chunk -- the ever-dirty columns'
+// chains with every entry valid (the unmasked search equals the masked one on an all-valid mask bit for bit).
+int launch_accum_chunk(vsom_ctx *c, const uint8_t *valid_host, int one_mask)
 {
-    const size_t B = c->B, N = c->N, J = c->J, ldn = (N + 63) / 64 * 64;
+    const size_t B = c->B, N = c->N, J = c->J, ldn = (N + 63) / 64 * 64, vld = c->xpitch;
+    const bool masked = valid_host != nullptr, one = one_mask != 0;
+    const size_t vrows = one ? 1 : B, nwords = (B + 31) / 32;
+    const size_t slice = masked ? std::min(vsom_masked_search_slice_rows(c), B) : 0;
+    const VsomNodeGroups grp = masked ? vsom_masked_groups(c, slice) : VsomNodeGroups{0, 0};
+    const bool walk = masked && c->ac.is_first;
     int rc;
-    if ((rc = c->ac.is_first ? launch_bmu_full(c, 0, B) : launch_bmu_local(c, 0, B)))   // phase 1 (:762-806)
-        return rc;
-    if ((rc = ensure_lut(c, c->ac.sigma)))
-        return rc;
     vsom_layout lay;
     const auto bxy = lay.add<int2>(B);
     const auto cw = lay.add<float2>(B * ldn);
+    // the masked call's own: validity bytes as given and packed, the (column, row) bits, the chunk's dirty columns and their
+    // count, a search slice's node-group keys and flags
+    const auto raw = lay.add<unsigned char>(masked ? vrows * J : 0), packed = lay.add<unsigned char>(masked ? vrows * vld : 0);
+    const auto bits = lay.add<unsigned>(masked ? J * nwords : 0);
+    const auto dcols = lay.add<int>(masked ? J : 0);
+    const auto ndirty = lay.add<unsigned>(masked ? 1 : 0);
+    const auto part = lay.add<u64>(walk ? slice * grp.ng : 0);
+    const auto nan0 = lay.add<unsigned char>(walk ? slice : 0);
+    const auto nvalid = lay.add<unsigned>(walk ? slice : 0);
     VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+    if (masked) {
+        if ((rc = vsom_accum_masked_ensure(c, vrows * J)))
+            return rc;
+        {
+            TimerScope ts(c, VSOM_T_STAGE);
+            if ((rc = vsom_accum_masked_stage(c, valid_host, vrows * J, lay.at(raw))))
+                return rc;
+            vsom_masked_pack_enqueue(c, lay.at(raw), vrows, lay.at(packed));
+            vsom_masked_bits_enqueue(c, lay.at(packed), one, lay.at(bits), lay.at(dcols), lay.at(ndirty));
+            c->ac.masked = true;
+            if ((rc = vsom_accum_masked_fold(c, lay.at(dcols), lay.at(ndirty))))
+                return rc;
+        }
+        TimerScope ts(c, VSOM_T_BMU);      // phase 1 on the masked distance, as vsom_batch_epoch_masked runs it
+        if ((rc = vsom_masked_phase1_enqueue(c, c->ac.is_first, lay.at(packed), one, slice, grp, lay.at(part), lay.at(nan0),
+                                             lay.at(nvalid))))
+            return rc;
+    } else if ((rc = c->ac.is_first ? launch_bmu_full(c, 0, B) : launch_bmu_local(c, 0, B)))   // phase 1 (:762-806)
+        return rc;
+    if ((rc = ensure_lut(c, c->ac.sigma)))
+        return rc;
     {
         TimerScope ts(c, VSOM_T_FINISH);
         hipLaunchKernelGGL(accum_finish_kernel, dim3(1u + (unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, c->sqres.p,
@@ -274,6 +313,15 @@ int launch_accum_chunk(vsom_ctx *c)
         TimerScope ts(c, VSOM_T_CW);
         hipLaunchKernelGGL(accum_bxy_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, c->lastbmu.p, (int)B,
                            (u64)c->W, (u64)c->H, lay.at(bxy));
+        VSOM_HIP_CHECK(hipGetLastError());
+    }
+    if (c->ac.masked) {     // the ever-dirty columns first: a fresh one starts from the accumulators as they stand
+        TimerScope ts(c, VSOM_T_UPDATE);
+        if ((rc = vsom_accum_masked_chains(c, lay.at(bxy), masked ? lay.at(bits) : nullptr, nwords)))
+            return rc;
+    }
+    {
+        TimerScope ts(c, VSOM_T_CW);
         hipLaunchKernelGGL(accum_cw_kernel, dim3((unsigned)(ldn / 64)), dim3(64), 0, c->stream, lay.at(bxy), (int)B,
                            (int)c->W, (int)c->H, (int)N, c->lut.p, (int)c->lut_w, (int)c->lut_h, c->acc_W.p, lay.at(cw),
                            (int)ldn);
@@ -301,5 +349,7 @@ int launch_accum_end(vsom_ctx *c)
                        c->acc_W.p, (int)c->N, (int)c->J, (int)c->pitch, c->map.p, c->sigma.p, c->weight.p, c->acc_mse.p,
                        c->mse.p);
     VSOM_HIP_CHECK(hipGetLastError());
+    if (c->ac.masked)       // the ever-dirty columns from their own state
+        return vsom_accum_masked_end(c);
     return VSOM_OK;
 }

@@ -156,6 +156,8 @@ static int free_all(vsom_ctx *c)
             (void)hipEventDestroy(c->lut_ev[i]);
         if (c->lutd_ev[i])
             (void)hipEventDestroy(c->lutd_ev[i]);
+        if (c->acm_ev[i])
+            (void)hipEventDestroy(c->acm_ev[i]);
     }
     for (auto &e : c->ev_live) {
         (void)hipEventDestroy(e.a);
@@ -1126,23 +1128,38 @@ int vsom_batch_accum_begin(vsom_ctx *c, double sigma, int is_first, size_t total
     return VSOM_OK;
 }
 
-int vsom_batch_accum_chunk(vsom_ctx *c)
+// valid_host null: the plain call
+static int accum_chunk(vsom_ctx *c, const char *name, const uint8_t *valid_host, int one_mask)
 {
-    CHECK_CTX(c);
+    const std::string who(name);
     if (!c->ac.open)
-        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_chunk: no accumulated epoch is open");
+        return vsom_fail(VSOM_ERR_INVALID, who + ": no accumulated epoch is open");
     CHECK_ROWS(c);
     if (!c->chunk_loaded)   // an EMPTY chunk is legal and changes nothing
         return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
     if (c->ac.rows + c->B > c->ac.total)
-        return vsom_fail(VSOM_ERR_INVALID, "vsom_batch_accum_chunk: the chunk's " + std::to_string(c->B) + " rows exceed total_rows (" +
+        return vsom_fail(VSOM_ERR_INVALID, who + ": the chunk's " + std::to_string(c->B) + " rows exceed total_rows (" +
                                                std::to_string(c->ac.rows) + " of " + std::to_string(c->ac.total) + " accumulated)");
     if (c->B == 0)
         return VSOM_OK;
-    if (int rc = launch_accum_chunk(c))
+    if (int rc = launch_accum_chunk(c, valid_host, one_mask))
         return rc;
     c->ac.rows += c->B;
     return VSOM_OK;
+}
+
+int vsom_batch_accum_chunk(vsom_ctx *c)
+{
+    CHECK_CTX(c);
+    return accum_chunk(c, "vsom_batch_accum_chunk", nullptr, 0);
+}
+
+int vsom_batch_accum_chunk_masked(vsom_ctx *c, const uint8_t *valid_host, int one_mask)
+{
+    CHECK_CTX(c);
+    if (!valid_host)
+        return vsom_fail(VSOM_ERR_INVALID, "valid_host is null");
+    return accum_chunk(c, "vsom_batch_accum_chunk_masked", valid_host, one_mask);
 }
 
 int vsom_batch_accum_end(vsom_ctx *c, float *mse_out)

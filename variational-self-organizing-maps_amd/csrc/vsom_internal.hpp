@@ -252,8 +252,22 @@ struct vsom_ctx {
         double sigma = 0.0;
         int is_first = 0;
         size_t total = 0, rows = 0;
+        bool masked = false;        // a masked chunk has been accumulated: the ever-dirty list below may hold columns
     } ac;
     DevBuf<float> acc_M, acc_S, acc_W, acc_mse;
+    // Masked chunks of an accumulated epoch (vsom_accum_masked.hip): a column that had an invalid entry in some chunk of the
+    // epoch ("ever dirty") carries M_d, S_d and its own weight sum W_d in acm_M / acm_S / acm_W ([column][node], rows of
+    // N rounded up to 64), and acc_M / acc_S hold dead values there.  acm_ever / acm_fresh: per column, ever dirty / became
+    // dirty in the chunk being accumulated; acm_cols: the ever-dirty columns in ascending order, acm_meta[0] their count.
+    // All on the device (no host round trip), allocated by the first masked chunk and kept; begin clears ever and count.
+    // acm_valid: the pinned staging of the caller's validity bytes, two halves used alternately, each guarded by an event
+    // recorded behind its copy.
+    DevBuf<float> acm_M, acm_S, acm_W;
+    DevBuf<unsigned char> acm_ever, acm_fresh;
+    DevBuf<int> acm_cols;
+    DevBuf<unsigned> acm_meta;
+    PinnedBuf<unsigned char> acm_valid;
+    hipEvent_t acm_ev[2] = {nullptr, nullptr}; bool acm_ev_valid[2] = {false, false}; int acm_slot = 0;
 
     // caller-defined transformation (vsom_create_custom, vsom_custom.hip); null for the built-in ones
     vsom_custom_state *cu = nullptr;
@@ -420,9 +434,31 @@ int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uin
 // vsom_accum.hip: the accumulated epoch (state and arguments checked by vsom_batch_accum_*); they enqueue only.  begin:
 // the accumulators allocated and zeroed; chunk: phase 1, MSE / hits and the carried phase 2 of the loaded chunk (B > 0),
 // with the sigma and is_first of c->ac; end: map, sigmaMap, weightMap and the MSE word from the accumulators
+// valid_host: the chunk's validity bytes (vsom_batch_accum_chunk_masked) or null (every entry valid)
 int launch_accum_begin(vsom_ctx *c);
-int launch_accum_chunk(vsom_ctx *c);
+int launch_accum_chunk(vsom_ctx *c, const uint8_t *valid_host = nullptr, int one_mask = 0);
 int launch_accum_end(vsom_ctx *c);
+// pieces of launch_batch_epoch_masked for callers that lay the scratch out themselves (vsom_accum.hip); they enqueue only.
+// bits: packed validity rows (B x xpitch, or the one shared row) -> bits[column][row / 32] (J x (B + 31) / 32 words), the
+// chunk's dirty columns in ascending order (J entries) and their count.  phase1: the masked search of the whole chunk
+// straight into lastBMU and sqres -- the tile walk in slices of `slice` rows (part, nan0, nvalid: one slice's scratch, as
+// for vsom_masked_search_enqueue) when is_first, findLocalBmu's walk from lastBMU otherwise.
+void vsom_masked_bits_enqueue(vsom_ctx *c, const unsigned char *packed_dev, bool one, unsigned *bits, int *dcols,
+                              unsigned *ndirty);
+int vsom_masked_phase1_enqueue(vsom_ctx *c, int is_first, const unsigned char *packed_dev, bool one, size_t slice,
+                               const VsomNodeGroups &grp, u64 *part, unsigned char *nan0, unsigned *nvalid);
+// vsom_accum_masked.hip: the ever-dirty columns of an accumulated epoch (vsom_ctx::acm_*).  ensure: the side buffers and the
+// pinned staging for vbytes validity bytes (may synchronise when it allocates).  stage: the caller's bytes through the
+// pinned staging into raw_dev.  fold: the chunk's dirty columns into the ever-dirty list, marking the fresh ones.  chains:
+// the chunk's rows into the side state of every ever-dirty column (bits null: every entry valid, no fresh column); it
+// must run before the carried neighbourhood pass and chains of the chunk touch acc_W / acc_M / acc_S.  end: map and
+// sigmaMap of the ever-dirty columns from the side state, after accum_end_kernel.  All but ensure enqueue only.
+int vsom_accum_masked_ensure(vsom_ctx *c, size_t vbytes);
+int vsom_accum_masked_reset(vsom_ctx *c);
+int vsom_accum_masked_stage(vsom_ctx *c, const uint8_t *valid_host, size_t vbytes, unsigned char *raw_dev);
+int vsom_accum_masked_fold(vsom_ctx *c, const int *dcols, const unsigned *ndirty);
+int vsom_accum_masked_chains(vsom_ctx *c, const int2 *bxy, const unsigned *bits, size_t nwords);
+int vsom_accum_masked_end(vsom_ctx *c);
 int launch_raw_dist(vsom_ctx *c, const u64 *nodes_dev, const u64 *vrows_dev, size_t count, int from_map,
                     float *out_dev);
 // vsom_umatrix.hip: Som::updateUMatrix of the current map / sigmaMap into ctx->umatrix; enqueues only.

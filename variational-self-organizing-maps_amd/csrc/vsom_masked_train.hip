@@ -227,6 +227,34 @@ __global__ __launch_bounds__(256) void masked_chain_kernel(const float *__restri
     }
 }
 
+void vsom_masked_bits_enqueue(vsom_ctx *c, const unsigned char *packed_dev, bool one, unsigned *bits, int *dcols,
+                              unsigned *ndirty)
+{
+    const size_t B = c->B, J = c->J, nwords = (B + 31) / 32;
+    hipLaunchKernelGGL(masked_bits_kernel, dim3((unsigned)nwords, (unsigned)((J + 255) / 256)), dim3(256), 0, c->stream,
+                       packed_dev, (int)c->xpitch, (int)one, (int)J, (int)B, (int)nwords, bits);
+    hipLaunchKernelGGL(masked_dirty_kernel, dim3(1), dim3(256), 0, c->stream, bits, (int)J, (int)B, (int)nwords, dcols, ndirty);
+}
+
+int vsom_masked_phase1_enqueue(vsom_ctx *c, int is_first, const unsigned char *packed_dev, bool one, size_t slice,
+                               const VsomNodeGroups &grp, u64 *part, unsigned char *nan0, unsigned *nvalid)
+{
+    const size_t B = c->B, vld = c->xpitch;
+    if (is_first) {
+        for (size_t s0 = 0; s0 < B; s0 += slice) {
+            const size_t s1 = std::min(B, s0 + slice);
+            if (int rc = vsom_masked_search_enqueue(c, 0, s0, s1, packed_dev + (one ? 0 : s0 * vld), one, grp, part, nan0,
+                                                    c->lastbmu.p + s0, c->sqres.p + s0, nvalid))
+                return rc;
+        }
+    } else {
+        hipLaunchKernelGGL(masked_local_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, vsom_dist_args(c),
+                           packed_dev, (int)vld, (int)one, (int)B, (u64)c->W, (u64)c->H, c->lastbmu.p, c->sqres.p);
+        VSOM_HIP_CHECK(hipGetLastError());
+    }
+    return VSOM_OK;
+}
+
 int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uint8_t *valid_host, int one_mask)
 {
     const size_t B = c->B, N = c->N, J = c->J, vld = c->xpitch;
@@ -258,26 +286,14 @@ int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uin
         TimerScope ts(c, VSOM_T_STAGE);
         VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(raw), valid_host, vrows * J, hipMemcpyHostToDevice, c->stream));
         vsom_masked_pack_enqueue(c, lay.at(raw), vrows, lay.at(packed));
-        hipLaunchKernelGGL(masked_bits_kernel, dim3((unsigned)nwords, (unsigned)((J + 255) / 256)), dim3(256), 0, c->stream,
-                           lay.at(packed), (int)vld, (int)one, (int)J, (int)B, (int)nwords, lay.at(bits));
-        hipLaunchKernelGGL(masked_dirty_kernel, dim3(1), dim3(256), 0, c->stream, lay.at(bits), (int)J, (int)B, (int)nwords,
-                           lay.at(dcols), lay.at(ndirty));
+        vsom_masked_bits_enqueue(c, lay.at(packed), one, lay.at(bits), lay.at(dcols), lay.at(ndirty));
         VSOM_HIP_CHECK(hipGetLastError());
     }
     {   // phase 1 (:762-806) on the masked distance, results where phase 1 stores them
         TimerScope ts(c, VSOM_T_BMU);
-        if (is_first) {
-            for (size_t s0 = 0; s0 < B; s0 += slice) {
-                const size_t s1 = std::min(B, s0 + slice);
-                if ((rc = vsom_masked_search_enqueue(c, 0, s0, s1, lay.at(packed) + (one ? 0 : s0 * vld), one, grp, lay.at(part),
-                                                     lay.at(nan0), c->lastbmu.p + s0, c->sqres.p + s0, lay.at(nvalid))))
-                    return rc;
-            }
-        } else {
-            hipLaunchKernelGGL(masked_local_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, vsom_dist_args(c),
-                               lay.at(packed), (int)vld, (int)one, (int)B, (u64)c->W, (u64)c->H, c->lastbmu.p, c->sqres.p);
-            VSOM_HIP_CHECK(hipGetLastError());
-        }
+        if ((rc = vsom_masked_phase1_enqueue(c, is_first, lay.at(packed), one, slice, grp, lay.at(part), lay.at(nan0),
+                                             lay.at(nvalid))))
+            return rc;
     }
     if ((rc = launch_finish(c)))
         return rc;

@@ -464,6 +464,12 @@ public:
     // loaded and copied while chunk k accumulates.  Standard / Median on one device only.
     void trainBatchSomWhole(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
                             bool updateUMatrixAfterEpoch = false, bool resetBmu = true);
+    // [MI355X build] extension: trainBatchSomWhole over the VALID entries of the rows only -- every chunk goes into the epoch
+    // with its validity flags (vsom_batch_accum_chunk_masked, include/vsom_hip.h), so that a missing field neither attracts
+    // the search nor enters the means and sigmas of its column, and the epoch still covers all rows of the stream (the
+    // SqliteDataLoader's case: NULLs and maxLoadCount rows per load).  Driver, metrics and resetBmu are trainBatchSomWhole's.
+    void trainBatchSomWholeMasked(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
+                                  bool updateUMatrixAfterEpoch = false, bool resetBmu = true);
     TrainingReturnValue trainSingle(const Eigen::VectorXf &v, const Eigen::VectorXf &valid,
                                     const Eigen::VectorXf &weights, const double eta, const double sigma,
                                     size_t &lastBMU, const WeigthDecayFunction weightDecayFunction);
@@ -643,6 +649,8 @@ private:
                            WeigthDecayFunction fn, bool updateUMatrixAfterEpoch);
     void createContext();
     void requireDevicePath(const char *what) const;
+    void trainWhole(const char *what, bool masked, DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
+                    bool updateUMatrixAfterEpoch, bool resetBmu);
     bool evaluateOnDevice(const DataSet &data, EvaluateRows &r) const;   // false: a validity flag outside {0, 1}
     void maskedRows(const DataSet *data, size_t minBmuHits, uint64_t *bmu, float *dist, float *fill) const;
     void refreshHost() const;

@@ -1226,10 +1226,23 @@ void Som::trainBatchSomMasked(DataSet &data, size_t numberOfEpochs, double sigma
 void Som::trainBatchSomWhole(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
                              bool updateUMatrixAfterEpoch, bool resetBmu)
 {
-    requireDevicePath("trainBatchSomWhole");
+    trainWhole("trainBatchSomWhole", false, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch, resetBmu);
+}
+
+// the same with every chunk's validity flags (vsom_batch_accum_chunk_masked copies them before it returns)
+void Som::trainBatchSomWholeMasked(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
+                                   bool updateUMatrixAfterEpoch, bool resetBmu)
+{
+    trainWhole("trainBatchSomWholeMasked", true, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch, resetBmu);
+}
+
+void Som::trainWhole(const char *what, bool masked, DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
+                     bool updateUMatrixAfterEpoch, bool resetBmu)
+{
+    requireDevicePath(what);
     if (grp)
-        throw std::runtime_error("trainBatchSomWhole: a multi-GPU Som has no accumulated epoch (vsom_batch_accum_* "
-                                 "run on one context)");
+        throw std::runtime_error(std::string(what) + ": a multi-GPU Som has no accumulated epoch (vsom_batch_accum_* "
+                                                     "run on one context)");
     {
         const std::lock_guard<std::mutex> lock(metricsMutex);   // (the reference resets without it: trainBatchSom)
         metrics = Som::Metrics(numberOfEpochs);
@@ -1243,6 +1256,14 @@ void Som::trainBatchSomWhole(DataSet &data, size_t numberOfEpochs, double sigma0
     }
     data.resetStreamLoadPosition();
     std::vector<uint64_t> prev(resetBmu ? 0 : total), lb;
+    std::vector<uint8_t> valid;   // the loaded chunk's flags (masked)
+    const auto chunkValidity = [&] {
+        if (!masked)
+            return;
+        valid = validity_bytes(data, inLen);
+        if (valid.empty())
+            valid.assign(1, 0);   // (an empty chunk reads no flag; the call wants a pointer)
+    };
     struct Guard {                // an exception between begin and end leaves no epoch open
         vsom_ctx *c;
         bool open = false;
@@ -1264,6 +1285,7 @@ void Som::trainBatchSomWhole(DataSet &data, size_t numberOfEpochs, double sigma0
         if (have) {
             data.loadNextDataFromStream();
             B = data.size();
+            chunkValidity();
             check(vsom_prefetch_chunk(ctx, data.contiguous(), B), "vsom_prefetch_chunk");
         }
         while (have) {
@@ -1271,11 +1293,15 @@ void Som::trainBatchSomWhole(DataSet &data, size_t numberOfEpochs, double sigma0
             check(vsom_commit_chunk(ctx), "vsom_commit_chunk");   // lastBMU := 0 (DataSet.cpp:136-137)
             if (!resetBmu && i > 0 && Bcur > 0)
                 check(vsom_set_last_bmu(ctx, prev.data() + off), "vsom_set_last_bmu");
-            check(vsom_batch_accum_chunk(ctx), "vsom_batch_accum_chunk");
+            if (masked)
+                check(vsom_batch_accum_chunk_masked(ctx, valid.data(), 0), "vsom_batch_accum_chunk_masked");
+            else
+                check(vsom_batch_accum_chunk(ctx), "vsom_batch_accum_chunk");
             have = !data.hasReadWholeDataStream();
             if (have) {           // host work and the copy beside the device's chains
                 data.loadNextDataFromStream();
                 B = data.size();
+                chunkValidity();
                 check(vsom_prefetch_chunk(ctx, data.contiguous(), B), "vsom_prefetch_chunk");
             }
             if ((!resetBmu || !have) && Bcur > 0) {

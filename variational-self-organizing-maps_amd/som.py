@@ -637,6 +637,26 @@ class Som:
         0.  With reset_bmu=False every row's BMU of the previous epoch is kept (a host array of one entry per row) and
         starts that row's walk.  Chunk k+1 is copied to the device (prefetch / commit) while chunk k accumulates.
         Standard and Median on one device, strict update mode."""
+        self._trainBatchSomWhole(False, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch, reset_bmu)
+
+    def trainBatchSomWholeMasked(self, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch=False,
+                                 reset_bmu=True):
+        """extension: trainBatchSomWhole over the valid entries of the rows only -- every chunk goes into the epoch with
+        capi.Context.batch_accum_chunk_masked, so that a missing field neither attracts the search nor enters the means
+        and sigmas of its column, and the epoch still covers all rows of the stream.  The validity of a chunk comes from
+        the data set when it has one (an attribute `validity`, loaded rows x J, nonzero = valid), as in
+        trainBatchSomEpochMasked; without one every column is valid.  Driver, schedule, metrics and reset_bmu are
+        trainBatchSomWhole's, the prefetch / commit pipeline included."""
+        self._trainBatchSomWhole(True, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch, reset_bmu)
+
+    def _chunkValidity(self, data):
+        """the loaded chunk's validity as the masked calls take it (a copy: the next load replaces the data set's)"""
+        valid = getattr(data, "validity", None)
+        if valid is None:
+            return np.ones(self.ctx.in_len, np.uint8)
+        return np.array(valid)
+
+    def _trainBatchSomWhole(self, masked, data, numberOfEpochs, sigma0, sigmaDecay, updateUMatrixAfterEpoch, reset_bmu):
         self.metrics = Metrics(numberOfEpochs)                    # :719
         sigmas = batch_sigma_schedule(numberOfEpochs, sigma0, sigmaDecay)
         if not sigmas:
@@ -655,17 +675,22 @@ class Som:
                 if have:
                     data.loadNextDataFromStream()
                     rows = np.ascontiguousarray(data.data, dtype=np.float32)
+                    valid = self._chunkValidity(data) if masked else None
                     ctx.prefetch_chunk(rows)
                 while have:
                     ctx.commit_chunk()                            # lastBMU := 0 (DataSet.cpp:136-137)
                     B, lb_ref = rows.shape[0], data.lastBMU
                     if prev is not None and i > 0:
                         ctx.set_last_bmu(prev[off:off + B])
-                    ctx.batch_accum_chunk()
+                    if masked:
+                        ctx.batch_accum_chunk_masked(valid)
+                    else:
+                        ctx.batch_accum_chunk()
                     have = not data.hasReadWholeDataStream()
                     if have:                                      # the next chunk's load and copy beside this one's chains
                         data.loadNextDataFromStream()
                         rows = np.ascontiguousarray(data.data, dtype=np.float32)
+                        valid = self._chunkValidity(data) if masked else None
                         ctx.prefetch_chunk(rows)
                     if prev is not None or not have:
                         lb = ctx.get_last_bmu()
