@@ -6,7 +6,9 @@ VSOM_NO_CHAIN); general masks against tests/masked_train_ref.py, which restates 
 Shapes: 7x5x9 with 70 rows (base), 12x11x33 with 257 rows (132 nodes: a second, partly filled wavefront; 33 columns cross
 the 32-byte packing; 257 rows cross the 32- and 64-row words), J = 1, B in {1, 63, 65} (row-word edges), 10x10x9 with 20 rows
 (the tiny route).  Every random mask carries a never-invalid column, a never-valid one, one valid in exactly one row and one
-valid in the last row only (J = 1: the single column takes each of the four roles in turn)."""
+valid in the last row only (J = 1: the single column takes each of the four roles in turn).  13x5x13 with B in {1, 7, 8, 9, 31,
+32, 33, 40} drives the chains' row walk across its group of 8 rows and its 32-row validity word, against the helper and
+against masked accumulated epochs on the same rows (section 2b)."""
 import ctypes
 import functools
 import math
@@ -175,6 +177,83 @@ def test_random_masks_against_the_helper(monkeypatch, tr, W, H, J, B, role0, env
         assert beq(snap["S"], np.zeros_like(snap["S"]))            # SMap is untouched in batch mode
         dead = ~valid.any(axis=0)
         assert (snap["map"][:, dead].view(np.uint32) == 0).all() and np.isnan(snap["sigma"][:, dead]).all()
+
+
+# ---- 2b. the borders of the chains' row walk: the group of 8 rows and the 32-row validity word ------------------------------
+# 13x5 (65 nodes: a second node group with one live lane), J = 13.  Column 0 is clean, column 1 has no valid row, column 2 is
+# invalid in the last row only, column 3 in row 0 only; the other columns are 80 % valid from BORDER_SEED, which was picked
+# so that one of them stays valid through all 40 rows: the dirty columns (7, 10, then 11) never fill their last block of 4.
+BORDER_ROWS = (1, 7, 8, 9, 31, 32, 33, 40)
+BORDER_SCHEDULE = ((3.0, True), (2.5, False))
+BORDER_SEED = 1793
+BORDER_KEYS = ("map", "sigma", "weight", "hits", "lastbmu", "sqres", "mse")
+
+
+def border_mask(B, J):
+    valid = np.random.default_rng(BORDER_SEED).random((B, J)) < 0.8
+    valid[:, 0] = True
+    valid[:, 1] = False
+    valid[:, 2] = True
+    valid[B - 1, 2] = False
+    valid[:, 3] = True
+    valid[0, 3] = False
+    return valid
+
+
+@functools.lru_cache(maxsize=None)
+def border_reference(tr, W, H, J, B):
+    """the helper's snapshots (computed once per case; callers do not modify them)"""
+    X, init = rows_and_map(W, H, J, B)
+    valid = border_mask(B, J)
+    ref = mref.MaskedOracle(W, H, J, tr, init)
+    lb = np.zeros(B, np.uint64)
+    out = []
+    for sigma, first in BORDER_SCHEDULE:
+        mse, sq = ref.epoch(np.where(valid, X, np.float32(0)), valid, lb, sigma, first)
+        out.append({"map": ref.map, "sigma": ref.sigma, "weight": ref.weight, "hits": ref.hits, "lastbmu": lb.copy(),
+                    "sqres": sq, "mse": np.array([mse], np.float32)})
+    return out
+
+
+def run_accum_masked(tr, W, H, J, init, X, valid, splits):
+    """BORDER_SCHEDULE as masked accumulated epochs over the rows cut into `splits`; lastBMU and sqres concatenated"""
+    ctx = vsom_amd.Context(W, H, J, tr)
+    ctx.set_state(map=init)
+    lb = np.zeros(X.shape[0], np.uint64)
+    out = []
+    for sigma, first in BORDER_SCHEDULE:
+        ctx.batch_accum_begin(sigma, first, X.shape[0])
+        lbs, sqs, off = [], [], 0
+        for n in splits:
+            ctx.upload_chunk(X[off:off + n])
+            ctx.set_last_bmu(lb[off:off + n])
+            ctx.batch_accum_chunk_masked(valid[off:off + n])
+            lbs.append(ctx.get_last_bmu())
+            sqs.append(ctx.get_sqres())
+            off += n
+        mse = ctx.batch_accum_end()
+        lb = np.concatenate(lbs)
+        out.append(dict(snapshot(ctx, mse), lastbmu=lb, sqres=np.concatenate(sqs)))
+    ctx.close()
+    return out
+
+
+@pytest.mark.parametrize("tr", KINDS)
+@pytest.mark.parametrize("B", BORDER_ROWS)
+def test_row_group_and_validity_word_borders(tr, B):
+    W, H, J = 13, 5, 13
+    X, init = rows_and_map(W, H, J, B)
+    valid = border_mask(B, J)
+    assert valid[:, 0].all() and not valid[:, 1].any()
+    assert (~valid).any(axis=0).sum() % 4 != 0                  # a ragged last block of dirty columns
+    X = poisoned(X, valid)
+    want = border_reference(tr, W, H, J, B)
+    got = run_gpu(tr, W, H, J, init, X, valid, BORDER_SCHEDULE)
+    same_runs(got, want, "helper", keys=BORDER_KEYS)
+    for snap in got:
+        assert (snap["map"][:, 1].view(np.uint32) == 0).all() and np.isnan(snap["sigma"][:, 1]).all()
+    for splits in ((B,), (B // 2, B - B // 2))[:1 if B < 2 else 2]:
+        same_runs(run_accum_masked(tr, W, H, J, init, X, valid, splits), got, ("accumulated", splits), keys=BORDER_KEYS)
 
 
 # ---- 3. winner takes all ---------------------------------------------------------------------------------------------------

@@ -23,7 +23,11 @@ fi
 objs=()
 for f in vsom_capi vsom_bmu vsom_shortlist vsom_update vsom_online vsom_online_i8 vsom_online_tiny vsom_single vsom_tiny vsom_group vsom_compact vsom_xq vsom_sl_i8 vsom_custom vsom_ensemble vsom_bmd vsom_topk vsom_umatrix vsom_similarity vsom_masked vsom_masked_train vsom_accum vsom_accum_masked vsom_evaluate vsom_generate; do
   o="$here/$f.o"
-  if [ ! -f "$o" ] || [ "$here/$f.hip" -nt "$o" ] || [ "$here/vsom_internal.hpp" -nt "$o" ] || [ "$here/vsom_phase2_plan.hpp" -nt "$o" ] || [ "$here/vsom_buf.hpp" -nt "$o" ] || [ "$here/vsom_device.hpp" -nt "$o" ] || [ "$here/vsom_online.hpp" -nt "$o" ] ||[ "$here/vsom_dist_tile.hpp" -nt "$o" ] || [ "$here/vsom_digits.hpp" -nt "$o" ] || [ "$here/vsom_custom_kernels.inc" -nt "$o" ] || [ "$here/vsom_tiny_batch_body.inc" -nt "$o" ] || [ "$here/vsom_tiny_online_body.inc" -nt "$o" ] || [ "$here/../../include/vsom_hip.h" -nt "$o" ]; then
+  stale=0
+  for d in "$here/$f.hip" "$here"/*.hpp "$here"/*.inc "$here/../../include/vsom_hip.h"; do   # any header may reach any object
+    if [ ! -f "$o" ] || [ "$d" -nt "$o" ]; then stale=1; fi
+  done
+  if [ $stale = 1 ]; then
     $HIPCC $FLAGS -c "$here/$f.hip" -o "$o" &
   fi
   objs+=("$o")

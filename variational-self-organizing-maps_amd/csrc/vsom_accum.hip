@@ -9,7 +9,7 @@
 //  phase 1               : launch_bmu_full / launch_bmu_local, unchanged, into lastBMU and sqres
 //  accum_finish_kernel   : bmuHits[lastBMU[s]] += 1; the MSE word continues in sample order with the divisor of the whole
 //                          epoch, mse = mse + sqres[s] / (float)total_rows
-//  accum_bxy_kernel      : SomIndex(lastBMU[j]) of every row, once
+//  vsom_bxy_kernel       : SomIndex(lastBMU[j]) of every row, once (vsom_masked_train.hip's)
 //  accum_cw_kernel       : the carried neighbourhood pass.  Thread = node: W = accW[i], then the rows in groups of AC_PU --
 //                          the group's w from the table ensure_lut built (independent loads), the fp32 prefix W += w (the
 //                          only dependent part), c = w / W (correctly rounded, 0/0 -> NaN; off the chain) -> cw[j][i] =
@@ -25,27 +25,16 @@
 //  accum_end_kernel      : map = accM, sigmaMap = sqrt(accS / accW), weightMap = accW; pad columns zero
 // A chunk may come with validity bytes (vsom_batch_accum_chunk_masked): the columns that had an invalid entry in some chunk
 // of the epoch are carried beside these accumulators by vsom_accum_masked.hip; the kernels here run
-// over all columns either way.
-#include "vsom_device.hpp"
+// over all columns either way.  The Stepper and the table lookup are vsom_chain.hpp's.
+#include "vsom_chain.hpp"
 #include <algorithm>
 
 #define AC_CB 8     // columns per wavefront: one s_load_dwordx8 of a staged row (rows are 128-byte aligned)
 #define AC_U 8      // rows per group of the chains
 #define AC_PU 16    // rows per group of the neighbourhood pass
 
-typedef float ac_f2 __attribute__((ext_vector_type(2)));
+typedef vsom_f2 ac_f2;
 typedef float ac_f8 __attribute__((ext_vector_type(8)));
-
-__global__ __launch_bounds__(256) void accum_bxy_kernel(const u64 *__restrict__ lastbmu, int B, u64 W, u64 H,
-                                                        int2 *__restrict__ bxy)
-{
-    const int j = blockIdx.x * 256 + threadIdx.x;
-    if (j >= B)
-        return;
-    int bx, by;
-    vsom_somindex(lastbmu[j], W, H, bx, by);        // SomIndex(*this, lastBMU[j]) (Som.cpp:847-849)
-    bxy[j] = make_int2(bx, by);
-}
 
 // workgroup 0: the running MSE; workgroups 1..: bmuHits of 256 rows each (integer atomics: any order gives the same sum)
 #define AC_FIN_TILE 4096
@@ -92,15 +81,8 @@ __global__ __launch_bounds__(64) void accum_cw_kernel(const int2 *__restrict__ b
     for (int j0 = 0; j0 < B; j0 += AC_PU) {
         float w[AC_PU], Wp[AC_PU];
 #pragma unroll
-        for (int u = 0; u < AC_PU; ++u) {                       // rows past the chunk: clamped re-reads, never consumed
-            const int2 b = bxy[j0 + u < last ? j0 + u : last];
-            int dx = cx - b.x, dy = cy - b.y;
-            dx = dx < 0 ? -dx : dx;
-            dy = dy < 0 ? -dy : dy;
-            dx = dx < lutw ? dx : lutw - 1;
-            dy = dy < luth ? dy : luth - 1;
-            w[u] = lut[dy * lutw + dx];                         // (float)calculateNeighbourhoodWeight(...) :851
-        }
+        for (int u = 0; u < AC_PU; ++u)                         // rows past the chunk: clamped re-reads, never consumed
+            w[u] = vsom_nbh_weight(lut, lutw, luth, cx, cy, bxy[j0 + u < last ? j0 + u : last]);
 #pragma unroll
         for (int u = 0; u < AC_PU; ++u) {
             if (j0 + u < B)                                     // (uniform)
@@ -115,9 +97,6 @@ __global__ __launch_bounds__(64) void accum_cw_kernel(const int2 *__restrict__ b
     accW[node] = Wr;
 }
 
-// Transformation::Stepper (Transformation.cpp:11-12, 49-50); sign(): NaN -> NaN, else (a > 0) - (a < 0)
-__device__ __forceinline__ float accum_sign(float dl) { return dl != dl ? dl : (float)((dl > 0.f) - (dl < 0.f)); }
-
 // rows [j0, j0 + n) of one group, n = AC_U when FULL: M and S of the wavefront's AC_CB columns, as column pairs
 template <bool MEDIAN, bool FULL>
 __device__ __forceinline__ void accum_steps(const float2 (&q)[AC_U], const ac_f8 (&x)[AC_U], int n, ac_f2 (&M)[AC_CB / 2],
@@ -130,11 +109,7 @@ __device__ __forceinline__ void accum_steps(const float2 (&q)[AC_U], const ac_f8
 #pragma unroll
             for (int p = 0; p < AC_CB / 2; ++p) {
                 const ac_f2 xv = {x[u][2 * p], x[u][2 * p + 1]};
-                ac_f2 dl = xv - M[p];                           // :861
-                if (MEDIAN) {
-                    dl.x = accum_sign(dl.x);
-                    dl.y = accum_sign(dl.y);
-                }
+                const ac_f2 dl = vsom_stepper<MEDIAN>(xv, M[p]);    // :861
                 const ac_f2 t = c2 * dl;
                 M[p] = M[p] + t;                                // :864
                 ac_f2 v = w2 * dl;                              // :867
@@ -262,42 +237,30 @@ int launch_accum_begin(vsom_ctx *c)
 // chains with every entry valid (the unmasked search equals the masked one on an all-valid mask bit for bit).
 int launch_accum_chunk(vsom_ctx *c, const uint8_t *valid_host, int one_mask)
 {
-    const size_t B = c->B, N = c->N, J = c->J, ldn = (N + 63) / 64 * 64, vld = c->xpitch;
-    const bool masked = valid_host != nullptr, one = one_mask != 0;
-    const size_t vrows = one ? 1 : B, nwords = (B + 31) / 32;
-    const size_t slice = masked ? std::min(vsom_masked_search_slice_rows(c), B) : 0;
-    const VsomNodeGroups grp = masked ? vsom_masked_groups(c, slice) : VsomNodeGroups{0, 0};
-    const bool walk = masked && c->ac.is_first;
+    const size_t B = c->B, N = c->N, J = c->J, ldn = vsom_node_pitch(N);
+    const bool masked = valid_host != nullptr;
     int rc;
     vsom_layout lay;
     const auto bxy = lay.add<int2>(B);
     const auto cw = lay.add<float2>(B * ldn);
-    // the masked call's own: validity bytes as given and packed, the (column, row) bits, the chunk's dirty columns and their
-    // count, a search slice's node-group keys and flags
-    const auto raw = lay.add<unsigned char>(masked ? vrows * J : 0), packed = lay.add<unsigned char>(masked ? vrows * vld : 0);
-    const auto bits = lay.add<unsigned>(masked ? J * nwords : 0);
-    const auto dcols = lay.add<int>(masked ? J : 0);
-    const auto ndirty = lay.add<unsigned>(masked ? 1 : 0);
-    const auto part = lay.add<u64>(walk ? slice * grp.ng : 0);
-    const auto nan0 = lay.add<unsigned char>(walk ? slice : 0);
-    const auto nvalid = lay.add<unsigned>(walk ? slice : 0);
+    VsomMaskedScratch ms{};     // the masked call's own
+    if (masked)
+        ms = vsom_masked_scratch_add(c, lay, one_mask != 0, c->ac.is_first);
     VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
     if (masked) {
-        if ((rc = vsom_accum_masked_ensure(c, vrows * J)))
+        if ((rc = vsom_accum_masked_ensure(c, ms.vrows * J)))
             return rc;
         {
             TimerScope ts(c, VSOM_T_STAGE);
-            if ((rc = vsom_accum_masked_stage(c, valid_host, vrows * J, lay.at(raw))))
+            if ((rc = vsom_accum_masked_stage(c, valid_host, ms.vrows * J, lay.at(ms.raw))))
                 return rc;
-            vsom_masked_pack_enqueue(c, lay.at(raw), vrows, lay.at(packed));
-            vsom_masked_bits_enqueue(c, lay.at(packed), one, lay.at(bits), lay.at(dcols), lay.at(ndirty));
+            vsom_masked_prepare_enqueue(c, lay, ms);
             c->ac.masked = true;
-            if ((rc = vsom_accum_masked_fold(c, lay.at(dcols), lay.at(ndirty))))
+            if ((rc = vsom_accum_masked_fold(c, lay.at(ms.dcols), lay.at(ms.ndirty))))
                 return rc;
         }
         TimerScope ts(c, VSOM_T_BMU);      // phase 1 on the masked distance, as vsom_batch_epoch_masked runs it
-        if ((rc = vsom_masked_phase1_enqueue(c, c->ac.is_first, lay.at(packed), one, slice, grp, lay.at(part), lay.at(nan0),
-                                             lay.at(nvalid))))
+        if ((rc = vsom_masked_phase1_enqueue(c, lay, ms)))
             return rc;
     } else if ((rc = c->ac.is_first ? launch_bmu_full(c, 0, B) : launch_bmu_local(c, 0, B)))   // phase 1 (:762-806)
         return rc;
@@ -311,13 +274,12 @@ int launch_accum_chunk(vsom_ctx *c, const uint8_t *valid_host, int one_mask)
     }
     {
         TimerScope ts(c, VSOM_T_CW);
-        hipLaunchKernelGGL(accum_bxy_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, c->lastbmu.p, (int)B,
-                           (u64)c->W, (u64)c->H, lay.at(bxy));
+        vsom_bxy_enqueue(c, lay.at(bxy));
         VSOM_HIP_CHECK(hipGetLastError());
     }
     if (c->ac.masked) {     // the ever-dirty columns first: a fresh one starts from the accumulators as they stand
         TimerScope ts(c, VSOM_T_UPDATE);
-        if ((rc = vsom_accum_masked_chains(c, lay.at(bxy), masked ? lay.at(bits) : nullptr, nwords)))
+        if ((rc = vsom_accum_masked_chains(c, lay.at(bxy), masked ? lay.at(ms.bits) : nullptr, (B + 31) / 32)))
             return rc;
     }
     {
@@ -329,13 +291,10 @@ int launch_accum_chunk(vsom_ctx *c, const uint8_t *valid_host, int one_mask)
     }
     {
         TimerScope ts(c, VSOM_T_UPDATE);
-        const dim3 grid((unsigned)(ldn / 64), (unsigned)(((J + AC_CB - 1) / AC_CB + 3) / 4));
-        if (c->transform == VSOM_MEDIAN)
-            hipLaunchKernelGGL(accum_chain_kernel<true>, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, (int)B,
-                               lay.at(cw), (int)ldn, (int)N, (int)J, c->acc_M.p, c->acc_S.p, (int)c->pitch);
-        else
-            hipLaunchKernelGGL(accum_chain_kernel<false>, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, (int)B,
-                               lay.at(cw), (int)ldn, (int)N, (int)J, c->acc_M.p, c->acc_S.p, (int)c->pitch);
+        const auto k = c->transform == VSOM_MEDIAN ? accum_chain_kernel<true> : accum_chain_kernel<false>;
+        hipLaunchKernelGGL(k, dim3((unsigned)(ldn / 64), (unsigned)(((J + AC_CB - 1) / AC_CB + 3) / 4)), dim3(256), 0,
+                           c->stream, c->Xs.p, (int)c->xpitch, (int)B, lay.at(cw), (int)ldn, (int)N, (int)J, c->acc_M.p,
+                           c->acc_S.p, (int)c->pitch);
         VSOM_HIP_CHECK(hipGetLastError());
     }
     return VSOM_OK;

@@ -12,8 +12,9 @@
 //  accum_masked_fold_kernel  : one workgroup: the chunk's dirty columns into the ever-dirty flags, the fresh flags of this
 //                              chunk, and the ever-dirty columns in ascending order with their count (ballot compaction; no
 //                              host round trip)
-//  accum_masked_chain_kernel : masked_chain_kernel's body between a load and a store of the carried state.  lane = node,
-//                              one wavefront per block of AM_CB ever-dirty columns; rows in load order in groups of AM_U:
+//  accum_masked_chain_kernel : masked_chain_kernel's walk (vsom_masked_walk, vsom_chain.hpp) between a load and a store
+//                              of the carried state.  lane = node, one wavefront per block of CH_CB ever-dirty columns;
+//                              rows in load order in groups of CH_U:
 //                              BMU coordinates, sample values and the validity word are wave-uniform, w comes from the
 //                              neighbourhood table of the epoch's sigma.  For a valid (row, column):
 //                                  W_d += w ; delta = Stepper(x, M) ; M = M + (w / W_d) * delta ; S = S + (w * delta) * delta
@@ -23,12 +24,9 @@
 //                              past the ever-dirty count leave at once.
 // and at the end of the epoch, after accum_end_kernel,
 //  accum_masked_end_kernel   : map = M_d, sigmaMap = sqrt(S_d / W_d) at the ever-dirty columns (no valid row: +0 / NaN)
-#include "vsom_device.hpp"
+#include "vsom_chain.hpp"
 #include <algorithm>
 #include <string.h>
-
-#define AM_CB 4     // columns per wavefront
-#define AM_U 8      // rows per group (operands fetched together before the dependent steps)
 
 __global__ __launch_bounds__(256) void accum_masked_fold_kernel(const int *__restrict__ dcols,
                                                                 const unsigned *__restrict__ ndirty, int J,
@@ -36,7 +34,6 @@ __global__ __launch_bounds__(256) void accum_masked_fold_kernel(const int *__res
                                                                 int *__restrict__ ecols, unsigned *__restrict__ ecount)
 {
     __shared__ unsigned wcnt[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     for (int d = (int)threadIdx.x; d < J; d += 256)
         fresh[d] = 0;
     __syncthreads();
@@ -52,31 +49,10 @@ __global__ __launch_bounds__(256) void accum_masked_fold_kernel(const int *__res
     unsigned base = 0;
     for (int d0 = 0; d0 < J; d0 += 256) {
         const int d = d0 + (int)threadIdx.x;
-        const bool on = d < J && ever[d];
-        const u64 m = __ballot(on);
-        if (lane == 0)
-            wcnt[wv] = (unsigned)__popcll(m);
-        __syncthreads();
-        unsigned at = base;
-        for (int i = 0; i < wv; ++i)
-            at += wcnt[i];
-        if (on)
-            ecols[at + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = d;
-        base += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
+        vsom_compact_round(d < J && ever[d], d, ecols, wcnt, base);
     }
     if (threadIdx.x == 0)
         *ecount = base;
-}
-
-// Transformation::Stepper (Transformation.cpp:11-12, 49-50); sign(): NaN -> NaN, else (a > 0) - (a < 0)
-template <bool MEDIAN>
-__device__ __forceinline__ float accum_masked_stepper(float x, float M)
-{
-    const float dl = x - M;
-    if (!MEDIAN)
-        return dl;
-    return dl != dl ? dl : (float)((dl > 0.f) - (dl < 0.f));
 }
 
 // sM / sS / sW: [column][ldn], ldn = N rounded up to 64.  bits null: every entry of the chunk valid (and fresh null)
@@ -88,9 +64,8 @@ __global__ __launch_bounds__(256) void accum_masked_chain_kernel(
     const float *__restrict__ accS, const float *__restrict__ accW, int pitch, float *__restrict__ sM, float *__restrict__ sS,
     float *__restrict__ sW, int ldn)
 {
-    static_assert(32 % AM_U == 0, "a group of rows lies within one validity word");
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int first = ((int)blockIdx.y * 4 + wv) * AM_CB;     // position of the wavefront's first column in the ever-dirty list
+    const int first = ((int)blockIdx.y * 4 + wv) * CH_CB;     // position of the wavefront's first column in the ever-dirty list
     const int ne = (int)*ecount;
     if (first >= ne || B <= 0)
         return;                                                // (wavefront-uniform; the kernel has no barrier)
@@ -101,10 +76,10 @@ __global__ __launch_bounds__(256) void accum_masked_chain_kernel(
     int cx, cy;
     vsom_somindex((u64)ln, (u64)W, (u64)H, cx, cy);            // SomIndex(*this, index) (Som.cpp:816)
 
-    int col[AM_CB];                                            // (uniform) -1: no column
-    float M[AM_CB], S[AM_CB], Wd[AM_CB];
+    int col[CH_CB];                                            // (uniform) -1: no column
+    float M[CH_CB], S[CH_CB], Wd[CH_CB];
 #pragma unroll
-    for (int c = 0; c < AM_CB; ++c) {
+    for (int c = 0; c < CH_CB; ++c) {
         col[c] = first + c < ne ? ecols[first + c] : -1;
         M[c] = S[c] = Wd[c] = 0.f;
         if (col[c] >= 0) {
@@ -121,49 +96,10 @@ __global__ __launch_bounds__(256) void accum_masked_chain_kernel(
         }
     }
 
-    const int last = B - 1;
-    for (int j0 = 0; j0 < B; j0 += AM_U) {
-        // the group's operands first: rows past the chunk are clamped re-reads of the last row, never consumed.  The words
-        // are the chunk's own (row 0 of the chunk is bit 0): j0 is a multiple of AM_U, so the group stays within one word
-        float w[AM_U], x[AM_U][AM_CB];
-        unsigned vb[AM_CB];
-#pragma unroll
-        for (int c = 0; c < AM_CB; ++c)
-            vb[c] = col[c] < 0 ? 0u : bits ? bits[(size_t)col[c] * nwords + (j0 >> 5)] >> (j0 & 31) : ~0u;
-#pragma unroll
-        for (int u = 0; u < AM_U; ++u) {
-            const int j = j0 + u < last ? j0 + u : last;
-            const int2 b = bxy[j];
-            int dx = cx - b.x, dy = cy - b.y;
-            dx = dx < 0 ? -dx : dx;
-            dy = dy < 0 ? -dy : dy;
-            dx = dx < lutw ? dx : lutw - 1;
-            dy = dy < luth ? dy : luth - 1;
-            w[u] = lut[dy * lutw + dx];                        // (float)calculateNeighbourhoodWeight(...) :851
-#pragma unroll
-            for (int c = 0; c < AM_CB; ++c)
-                x[u][c] = Xs[(size_t)j * ldx + (col[c] >= 0 ? col[c] : 0)];
-        }
-#pragma unroll
-        for (int u = 0; u < AM_U; ++u) {
-#pragma unroll
-            for (int c = 0; c < AM_CB; ++c) {
-                if (j0 + u < B && ((vb[c] >> u) & 1u)) {       // (uniform) a row invalid at the column is skipped
-                    Wd[c] = Wd[c] + w[u];                      // :857
-                    const float cc = w[u] / Wd[c];             // :864 (0/0 -> NaN, Q7)
-                    const float dl = accum_masked_stepper<MEDIAN>(x[u][c], M[c]);   // :861
-                    const float t = cc * dl;
-                    M[c] = M[c] + t;                           // :864
-                    float q = w[u] * dl;                       // :867
-                    q = q * dl;
-                    S[c] = S[c] + q;
-                }
-            }
-        }
-    }
+    vsom_masked_walk<MEDIAN, true, CH_CB, CH_U>(Xs, ldx, bxy, B, bits, nwords, lut, lutw, luth, cx, cy, col, M, S, Wd);
     if (live) {
 #pragma unroll
-        for (int c = 0; c < AM_CB; ++c)
+        for (int c = 0; c < CH_CB; ++c)
             if (col[c] >= 0) {
                 const size_t at = (size_t)col[c] * ldn + node;
                 sM[at] = M[c];
@@ -196,7 +132,7 @@ __global__ __launch_bounds__(256) void accum_masked_end_kernel(const int *__rest
 
 int vsom_accum_masked_ensure(vsom_ctx *c, size_t vbytes)
 {
-    const size_t J = c->J, ldn = ((size_t)c->N + 63) / 64 * 64;
+    const size_t J = c->J, ldn = vsom_node_pitch(c->N);
     const bool had = c->acm_ever.p != nullptr;
     VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_SYNC,
                                    {vsom_member(c->acm_M, J * ldn), vsom_member(c->acm_S, J * ldn), vsom_member(c->acm_W, J * ldn),
@@ -250,26 +186,21 @@ int vsom_accum_masked_fold(vsom_ctx *c, const int *dcols, const unsigned *ndirty
 
 int vsom_accum_masked_chains(vsom_ctx *c, const int2 *bxy, const unsigned *bits, size_t nwords)
 {
-    const size_t N = c->N, J = c->J, ldn = (N + 63) / 64 * 64;
+    const size_t N = c->N, J = c->J, ldn = vsom_node_pitch(N);
     const unsigned char *fresh = bits ? c->acm_fresh.p : nullptr;
-    const dim3 grid((unsigned)(ldn / 64), (unsigned)(((J + AM_CB - 1) / AM_CB + 3) / 4));
-    if (c->transform == VSOM_MEDIAN)
-        hipLaunchKernelGGL(accum_masked_chain_kernel<true>, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, bxy, (int)c->B,
-                           bits, (int)nwords, c->acm_cols.p, c->acm_meta.p, fresh, c->lut.p, (int)c->lut_w, (int)c->lut_h,
-                           (int)c->W, (int)c->H, (int)N, c->acc_M.p, c->acc_S.p, c->acc_W.p, (int)c->pitch, c->acm_M.p,
-                           c->acm_S.p, c->acm_W.p, (int)ldn);
-    else
-        hipLaunchKernelGGL(accum_masked_chain_kernel<false>, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, bxy, (int)c->B,
-                           bits, (int)nwords, c->acm_cols.p, c->acm_meta.p, fresh, c->lut.p, (int)c->lut_w, (int)c->lut_h,
-                           (int)c->W, (int)c->H, (int)N, c->acc_M.p, c->acc_S.p, c->acc_W.p, (int)c->pitch, c->acm_M.p,
-                           c->acm_S.p, c->acm_W.p, (int)ldn);
+    const dim3 grid((unsigned)(ldn / 64), (unsigned)(((J + CH_CB - 1) / CH_CB + 3) / 4));
+    const auto k = c->transform == VSOM_MEDIAN ? accum_masked_chain_kernel<true> : accum_masked_chain_kernel<false>;
+    hipLaunchKernelGGL(k, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, bxy, (int)c->B, bits, (int)nwords,
+                       c->acm_cols.p, c->acm_meta.p, fresh, c->lut.p, (int)c->lut_w, (int)c->lut_h, (int)c->W, (int)c->H,
+                       (int)N, c->acc_M.p, c->acc_S.p, c->acc_W.p, (int)c->pitch, c->acm_M.p, c->acm_S.p, c->acm_W.p,
+                       (int)ldn);
     VSOM_HIP_CHECK(hipGetLastError());
     return VSOM_OK;
 }
 
 int vsom_accum_masked_end(vsom_ctx *c)
 {
-    const size_t N = c->N, ldn = (N + 63) / 64 * 64;
+    const size_t N = c->N, ldn = vsom_node_pitch(N);
     hipLaunchKernelGGL(accum_masked_end_kernel, dim3((unsigned)((N + 255) / 256), (unsigned)std::min<size_t>(c->J, 65535)), dim3(256), 0, c->stream,
                        c->acm_cols.p, c->acm_meta.p, c->acm_M.p, c->acm_S.p, c->acm_W.p, (int)ldn, (int)N, (int)c->pitch,
                        c->map.p, c->sigma.p);

@@ -438,15 +438,30 @@ int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uin
 int launch_accum_begin(vsom_ctx *c);
 int launch_accum_chunk(vsom_ctx *c, const uint8_t *valid_host = nullptr, int one_mask = 0);
 int launch_accum_end(vsom_ctx *c);
-// pieces of launch_batch_epoch_masked for callers that lay the scratch out themselves (vsom_accum.hip); they enqueue only.
-// bits: packed validity rows (B x xpitch, or the one shared row) -> bits[column][row / 32] (J x (B + 31) / 32 words), the
-// chunk's dirty columns in ascending order (J entries) and their count.  phase1: the masked search of the whole chunk
-// straight into lastBMU and sqres -- the tile walk in slices of `slice` rows (part, nan0, nvalid: one slice's scratch, as
-// for vsom_masked_search_enqueue) when is_first, findLocalBmu's walk from lastBMU otherwise.
-void vsom_masked_bits_enqueue(vsom_ctx *c, const unsigned char *packed_dev, bool one, unsigned *bits, int *dcols,
-                              unsigned *ndirty);
-int vsom_masked_phase1_enqueue(vsom_ctx *c, int is_first, const unsigned char *packed_dev, bool one, size_t slice,
-                               const VsomNodeGroups &grp, u64 *part, unsigned char *nan0, unsigned *nvalid);
+// Pieces of launch_batch_epoch_masked shared with the accumulated epoch (vsom_accum.hip); they enqueue only.
+// VsomMaskedScratch: the scratch of a masked chunk of c->B > 0 rows -- the validity bytes as given (vrows x J; one: the
+// row every sample shares) and packed (vrows x xpitch), bits[column][row / 32] (J x nwords words), the chunk's dirty
+// columns in ascending order (J entries) and their count, and, for the first epoch's tile walk, one search slice's
+// node-group keys and flags (first; part, nan0, nvalid as for vsom_masked_search_enqueue; empty otherwise).  scratch_add: its
+// members added to a layout.  How the caller's bytes reach `raw` is the caller's.  prepare: raw -> packed -> bits -> dirty
+// columns.  phase1: the masked search of the whole chunk straight into lastBMU and sqres -- the tile walk in slices when
+// first, findLocalBmu's walk from lastBMU otherwise.
+struct VsomMaskedScratch {
+    bool one, first;
+    size_t vrows, nwords, slice;
+    VsomNodeGroups grp;
+    vsom_layout::piece<unsigned char> raw, packed, nan0;
+    vsom_layout::piece<unsigned> bits, ndirty, nvalid;
+    vsom_layout::piece<int> dcols;
+    vsom_layout::piece<u64> part;
+};
+VsomMaskedScratch vsom_masked_scratch_add(const vsom_ctx *c, vsom_layout &lay, bool one, bool first);
+void vsom_masked_prepare_enqueue(vsom_ctx *c, const vsom_layout &lay, const VsomMaskedScratch &ms);
+int vsom_masked_phase1_enqueue(vsom_ctx *c, const vsom_layout &lay, const VsomMaskedScratch &ms);
+// SomIndex(lastBMU[j]) of the chunk's rows into bxy (c->B entries), for the chains of both epoch paths
+void vsom_bxy_enqueue(vsom_ctx *c, int2 *bxy);
+// node rows padded to whole wavefronts: the pitch of the (c,w) rows and of the masked side state
+inline size_t vsom_node_pitch(size_t N) { return (N + 63) / 64 * 64; }
 // vsom_accum_masked.hip: the ever-dirty columns of an accumulated epoch (vsom_ctx::acm_*).  ensure: the side buffers and the
 // pinned staging for vbytes validity bytes (may synchronise when it allocates).  stage: the caller's bytes through the
 // pinned staging into raw_dev.  fold: the chunk's dirty columns into the ever-dirty list, marking the fresh ones.  chains:

@@ -7,13 +7,14 @@
 // weightMap (the sum of w over ALL rows) and, bit for bit, every column that has no invalid entry in the chunk -- and then
 // recomputes the "dirty" columns, those with at least one invalid entry, with a per-column weight sum:
 //
-//  masked_bxy_kernel    : SomIndex(lastBMU[j]) of every row, once (the chains read it as a scalar pair)
+//  vsom_bxy_kernel      : SomIndex(lastBMU[j]) of every row, once (the chains read it as a scalar pair); the accumulated
+//                         epoch (vsom_accum.hip) runs it too
 //  masked_bits_kernel   : packed validity bytes (rows x xpitch, or the one shared row) -> bits[column][row / 32], 32 rows
 //                         to a word, rows past the chunk read as invalid
 //  masked_dirty_kernel  : one workgroup: the columns with an invalid entry among the chunk's rows, in ascending order, and
 //                         their count (ballot compaction; no host round trip)
-//  masked_chain_kernel  : lane = node, one wavefront per block of MT_CB dirty columns, M, S and W_d of every column in
-//                         registers.  The rows are walked in load order in groups of MT_U: the group's BMU coordinates,
+//  masked_chain_kernel  : lane = node, one wavefront per block of CH_CB dirty columns, M, S and W_d of every column in
+//                         registers.  The rows are walked in load order in groups of CH_U: the group's BMU coordinates,
 //                         sample values and validity word are wave-uniform (scalar loads), w comes from the neighbourhood
 //                         table the unmasked path built for this sigma.  For a valid (row, column):
 //                             W_d += w ; delta = Stepper(x, M) ; M = M + (w / W_d) * delta ; S = S + (w * delta) * delta
@@ -21,14 +22,13 @@
 //                         the strict flags), an invalid one is skipped: what x holds there is loaded and never used.  At
 //                         the end map = M, sigmaMap = sqrt(S / W_d): a column without a valid row is +0 / NaN.  No atomics,
 //                         no LDS; workgroups past the dirty count leave at once.
-#include "vsom_device.hpp"
+// The walk, its step, the Stepper, the table lookup and the compaction round are vsom_chain.hpp's, shared with
+// vsom_accum.hip and vsom_accum_masked.hip.
+#include "vsom_chain.hpp"
 #include <algorithm>
 
-#define MT_CB 4     // columns per wavefront
-#define MT_U 8      // rows per group (operands fetched together before the dependent steps)
-
-__global__ __launch_bounds__(256) void masked_bxy_kernel(const u64 *__restrict__ lastbmu, int B, u64 W, u64 H,
-                                                         int2 *__restrict__ bxy)
+__global__ __launch_bounds__(256) void vsom_bxy_kernel(const u64 *__restrict__ lastbmu, int B, u64 W, u64 H,
+                                                       int2 *__restrict__ bxy)
 {
     const int j = blockIdx.x * 256 + threadIdx.x;
     if (j >= B)
@@ -58,7 +58,6 @@ __global__ __launch_bounds__(256) void masked_dirty_kernel(const unsigned *__res
                                                            int *__restrict__ dcols, unsigned *__restrict__ ndirty)
 {
     __shared__ unsigned wcnt[4];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     unsigned base = 0;
     for (int d0 = 0; d0 < J; d0 += 256) {
         const int d = d0 + (int)threadIdx.x;
@@ -69,17 +68,7 @@ __global__ __launch_bounds__(256) void masked_dirty_kernel(const unsigned *__res
                 const unsigned full = nt == 32 ? ~0u : (1u << nt) - 1u;
                 dirty = dirty || bits[(size_t)d * nwords + w] != full;
             }
-        const u64 m = __ballot(dirty);
-        if (lane == 0)
-            wcnt[wv] = (unsigned)__popcll(m);
-        __syncthreads();
-        unsigned at = base;
-        for (int i = 0; i < wv; ++i)
-            at += wcnt[i];
-        if (dirty)
-            dcols[at + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = d;
-        base += wcnt[0] + wcnt[1] + wcnt[2] + wcnt[3];
-        __syncthreads();
+        vsom_compact_round(dirty, d, dcols, wcnt, base);
     }
     if (threadIdx.x == 0)
         *ndirty = base;
@@ -139,16 +128,6 @@ __global__ __launch_bounds__(256) void masked_local_kernel(DistArgs a, const uns
     }
 }
 
-// Transformation::Stepper (Transformation.cpp:11-12, 49-50); sign(): NaN -> NaN, else (a > 0) - (a < 0)
-template <bool MEDIAN>
-__device__ __forceinline__ float masked_stepper(float x, float M)
-{
-    const float dl = x - M;
-    if (!MEDIAN)
-        return dl;
-    return dl != dl ? dl : (float)((dl > 0.f) - (dl < 0.f));
-}
-
 template <bool MEDIAN>
 __global__ __launch_bounds__(256) void masked_chain_kernel(const float *__restrict__ Xs, int ldx, const int2 *__restrict__ bxy,
                                                            int B, const unsigned *__restrict__ bits, int nwords,
@@ -158,9 +137,8 @@ __global__ __launch_bounds__(256) void masked_chain_kernel(const float *__restri
                                                            int N, float *__restrict__ map, float *__restrict__ sigma,
                                                            int pitch)
 {
-    static_assert(32 % MT_U == 0, "a group of rows lies within one validity word");
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int first = ((int)blockIdx.y * 4 + wv) * MT_CB;     // position of the wavefront's first column in the dirty list
+    const int first = ((int)blockIdx.y * 4 + wv) * CH_CB;     // position of the wavefront's first column in the dirty list
     const int nd = (int)*ndirty;
     if (first >= nd)
         return;                                                // (wavefront-uniform; the kernel has no barrier)
@@ -169,57 +147,19 @@ __global__ __launch_bounds__(256) void masked_chain_kernel(const float *__restri
     int cx, cy;
     vsom_somindex((u64)(node < N ? node : 0), (u64)W, (u64)H, cx, cy);     // SomIndex(*this, index) (Som.cpp:816)
 
-    int col[MT_CB];                                            // (uniform) -1: no column
+    int col[CH_CB];                                            // (uniform) -1: no column
 #pragma unroll
-    for (int c = 0; c < MT_CB; ++c)
+    for (int c = 0; c < CH_CB; ++c)
         col[c] = first + c < nd ? dcols[first + c] : -1;
-    float M[MT_CB], S[MT_CB], Wd[MT_CB];
+    float M[CH_CB], S[CH_CB], Wd[CH_CB];
 #pragma unroll
-    for (int c = 0; c < MT_CB; ++c)
+    for (int c = 0; c < CH_CB; ++c)
         M[c] = S[c] = Wd[c] = 0.f;                             // :840, :843-844
 
-    const int last = B - 1;
-    for (int j0 = 0; j0 < B; j0 += MT_U) {
-        // the group's operands first: rows past the chunk are clamped re-reads of the last row, never consumed
-        float w[MT_U], x[MT_U][MT_CB];
-        unsigned vb[MT_CB];
-#pragma unroll
-        for (int c = 0; c < MT_CB; ++c)
-            vb[c] = col[c] >= 0 ? bits[(size_t)col[c] * nwords + (j0 >> 5)] >> (j0 & 31) : 0u;
-#pragma unroll
-        for (int u = 0; u < MT_U; ++u) {
-            const int j = j0 + u < last ? j0 + u : last;
-            const int2 b = bxy[j];
-            int dx = cx - b.x, dy = cy - b.y;
-            dx = dx < 0 ? -dx : dx;
-            dy = dy < 0 ? -dy : dy;
-            dx = dx < lutw ? dx : lutw - 1;
-            dy = dy < luth ? dy : luth - 1;
-            w[u] = lut[dy * lutw + dx];                        // (float)calculateNeighbourhoodWeight(...) :851
-#pragma unroll
-            for (int c = 0; c < MT_CB; ++c)
-                x[u][c] = Xs[(size_t)j * ldx + (col[c] >= 0 ? col[c] : 0)];
-        }
-#pragma unroll
-        for (int u = 0; u < MT_U; ++u) {
-#pragma unroll
-            for (int c = 0; c < MT_CB; ++c) {
-                if (j0 + u < B && ((vb[c] >> u) & 1u)) {       // (uniform) a row invalid at the column is skipped
-                    Wd[c] = Wd[c] + w[u];                      // :857
-                    const float cc = w[u] / Wd[c];             // :864 (0/0 -> NaN, Q7)
-                    const float dl = masked_stepper<MEDIAN>(x[u][c], M[c]);   // :861
-                    const float t = cc * dl;
-                    M[c] = M[c] + t;                           // :864
-                    float q = w[u] * dl;                       // :867
-                    q = q * dl;
-                    S[c] = S[c] + q;
-                }
-            }
-        }
-    }
+    vsom_masked_walk<MEDIAN, false, CH_CB, CH_U>(Xs, ldx, bxy, B, bits, nwords, lut, lutw, luth, cx, cy, col, M, S, Wd);
     if (node < N) {
 #pragma unroll
-        for (int c = 0; c < MT_CB; ++c)
+        for (int c = 0; c < CH_CB; ++c)
             if (col[c] >= 0) {
                 map[(size_t)node * pitch + col[c]] = M[c];                      // :870
                 sigma[(size_t)node * pitch + col[c]] = sqrtf(S[c] / Wd[c]);     // :873
@@ -227,29 +167,59 @@ __global__ __launch_bounds__(256) void masked_chain_kernel(const float *__restri
     }
 }
 
-void vsom_masked_bits_enqueue(vsom_ctx *c, const unsigned char *packed_dev, bool one, unsigned *bits, int *dcols,
-                              unsigned *ndirty)
+void vsom_bxy_enqueue(vsom_ctx *c, int2 *bxy)
 {
-    const size_t B = c->B, J = c->J, nwords = (B + 31) / 32;
-    hipLaunchKernelGGL(masked_bits_kernel, dim3((unsigned)nwords, (unsigned)((J + 255) / 256)), dim3(256), 0, c->stream,
-                       packed_dev, (int)c->xpitch, (int)one, (int)J, (int)B, (int)nwords, bits);
-    hipLaunchKernelGGL(masked_dirty_kernel, dim3(1), dim3(256), 0, c->stream, bits, (int)J, (int)B, (int)nwords, dcols, ndirty);
+    hipLaunchKernelGGL(vsom_bxy_kernel, dim3((unsigned)((c->B + 255) / 256)), dim3(256), 0, c->stream, c->lastbmu.p, (int)c->B,
+                       (u64)c->W, (u64)c->H, bxy);
 }
 
-int vsom_masked_phase1_enqueue(vsom_ctx *c, int is_first, const unsigned char *packed_dev, bool one, size_t slice,
-                               const VsomNodeGroups &grp, u64 *part, unsigned char *nan0, unsigned *nvalid)
+VsomMaskedScratch vsom_masked_scratch_add(const vsom_ctx *c, vsom_layout &lay, bool one, bool first)
+{
+    const size_t B = c->B, J = c->J;
+    VsomMaskedScratch ms;
+    ms.one = one;
+    ms.first = first;
+    ms.vrows = one ? 1 : B;
+    ms.nwords = (B + 31) / 32;
+    ms.slice = std::min(vsom_masked_search_slice_rows(c), B);
+    ms.grp = vsom_masked_groups(c, ms.slice);
+    ms.raw = lay.add<unsigned char>(ms.vrows * J);
+    ms.packed = lay.add<unsigned char>(ms.vrows * c->xpitch);
+    ms.bits = lay.add<unsigned>(J * ms.nwords);
+    ms.dcols = lay.add<int>(J);
+    ms.ndirty = lay.add<unsigned>(1);
+    // (the valid-column counts of the search's reduction are not used)
+    ms.part = lay.add<u64>(first ? ms.slice * ms.grp.ng : 0);
+    ms.nan0 = lay.add<unsigned char>(first ? ms.slice : 0);
+    ms.nvalid = lay.add<unsigned>(first ? ms.slice : 0);
+    return ms;
+}
+
+void vsom_masked_prepare_enqueue(vsom_ctx *c, const vsom_layout &lay, const VsomMaskedScratch &ms)
+{
+    const size_t B = c->B, J = c->J;
+    vsom_masked_pack_enqueue(c, lay.at(ms.raw), ms.vrows, lay.at(ms.packed));
+    hipLaunchKernelGGL(masked_bits_kernel, dim3((unsigned)ms.nwords, (unsigned)((J + 255) / 256)), dim3(256), 0, c->stream,
+                       lay.at(ms.packed), (int)c->xpitch, (int)ms.one, (int)J, (int)B, (int)ms.nwords, lay.at(ms.bits));
+    hipLaunchKernelGGL(masked_dirty_kernel, dim3(1), dim3(256), 0, c->stream, lay.at(ms.bits), (int)J, (int)B, (int)ms.nwords,
+                       lay.at(ms.dcols), lay.at(ms.ndirty));
+}
+
+int vsom_masked_phase1_enqueue(vsom_ctx *c, const vsom_layout &lay, const VsomMaskedScratch &ms)
 {
     const size_t B = c->B, vld = c->xpitch;
-    if (is_first) {
-        for (size_t s0 = 0; s0 < B; s0 += slice) {
-            const size_t s1 = std::min(B, s0 + slice);
-            if (int rc = vsom_masked_search_enqueue(c, 0, s0, s1, packed_dev + (one ? 0 : s0 * vld), one, grp, part, nan0,
-                                                    c->lastbmu.p + s0, c->sqres.p + s0, nvalid))
+    const unsigned char *packed = lay.at(ms.packed);
+    if (ms.first) {
+        for (size_t s0 = 0; s0 < B; s0 += ms.slice) {
+            const size_t s1 = std::min(B, s0 + ms.slice);
+            if (int rc = vsom_masked_search_enqueue(c, 0, s0, s1, packed + (ms.one ? 0 : s0 * vld), ms.one, ms.grp,
+                                                    lay.at(ms.part), lay.at(ms.nan0), c->lastbmu.p + s0, c->sqres.p + s0,
+                                                    lay.at(ms.nvalid)))
                 return rc;
         }
     } else {
         hipLaunchKernelGGL(masked_local_kernel, dim3((unsigned)((B + 3) / 4)), dim3(256), 0, c->stream, vsom_dist_args(c),
-                           packed_dev, (int)vld, (int)one, (int)B, (u64)c->W, (u64)c->H, c->lastbmu.p, c->sqres.p);
+                           packed, (int)vld, (int)ms.one, (int)B, (u64)c->W, (u64)c->H, c->lastbmu.p, c->sqres.p);
         VSOM_HIP_CHECK(hipGetLastError());
     }
     return VSOM_OK;
@@ -257,7 +227,7 @@ int vsom_masked_phase1_enqueue(vsom_ctx *c, int is_first, const unsigned char *p
 
 int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uint8_t *valid_host, int one_mask)
 {
-    const size_t B = c->B, N = c->N, J = c->J, vld = c->xpitch;
+    const size_t B = c->B, N = c->N, J = c->J;
     int rc;
     if (B == 0) {       // the epoch of an empty chunk reads no validity
         if ((rc = launch_finish(c)) || (rc = launch_phase2(c, sigma, 0, N)))
@@ -265,34 +235,20 @@ int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uin
         VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
         return VSOM_OK;
     }
-    const bool one = one_mask != 0;
-    const size_t vrows = one ? 1 : B, nwords = (B + 31) / 32;
-    const size_t slice = std::min(vsom_masked_search_slice_rows(c), B);
-    const VsomNodeGroups grp = vsom_masked_groups(c, slice);
-    // the chunk's validity bytes as given and packed, the (column, row) bits, BMU coordinates, dirty columns and their count,
-    // and a search slice's node-group keys and flags (the valid-column counts of the reduction are not used)
     vsom_layout lay;
-    const auto raw = lay.add<unsigned char>(vrows * J), packed = lay.add<unsigned char>(vrows * vld);
-    const auto bits = lay.add<unsigned>(J * nwords);
-    const auto dcols = lay.add<int>(J);
-    const auto ndirty = lay.add<unsigned>(1);
-    const auto bxy = lay.add<int2>(B);
-    const auto part = lay.add<u64>(is_first ? slice * grp.ng : 0);
-    const auto nan0 = lay.add<unsigned char>(is_first ? slice : 0);
-    const auto nvalid = lay.add<unsigned>(is_first ? slice : 0);
+    const VsomMaskedScratch ms = vsom_masked_scratch_add(c, lay, one_mask != 0, is_first != 0);
+    const auto bxy = lay.add<int2>(B);      // BMU coordinates
     VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
 
     {
         TimerScope ts(c, VSOM_T_STAGE);
-        VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(raw), valid_host, vrows * J, hipMemcpyHostToDevice, c->stream));
-        vsom_masked_pack_enqueue(c, lay.at(raw), vrows, lay.at(packed));
-        vsom_masked_bits_enqueue(c, lay.at(packed), one, lay.at(bits), lay.at(dcols), lay.at(ndirty));
+        VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(ms.raw), valid_host, ms.vrows * J, hipMemcpyHostToDevice, c->stream));
+        vsom_masked_prepare_enqueue(c, lay, ms);
         VSOM_HIP_CHECK(hipGetLastError());
     }
     {   // phase 1 (:762-806) on the masked distance, results where phase 1 stores them
         TimerScope ts(c, VSOM_T_BMU);
-        if ((rc = vsom_masked_phase1_enqueue(c, is_first, lay.at(packed), one, slice, grp, lay.at(part), lay.at(nan0),
-                                             lay.at(nvalid))))
+        if ((rc = vsom_masked_phase1_enqueue(c, lay, ms)))
             return rc;
     }
     if ((rc = launch_finish(c)))
@@ -303,17 +259,12 @@ int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uin
     c->rows_free_valid = false;     // the chains below read the staged rows
     {
         TimerScope ts(c, VSOM_T_UPDATE);
-        hipLaunchKernelGGL(masked_bxy_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, c->stream, c->lastbmu.p, (int)B,
-                           (u64)c->W, (u64)c->H, lay.at(bxy));
-        const dim3 grid((unsigned)((N + 63) / 64), (unsigned)(((J + MT_CB - 1) / MT_CB + 3) / 4));
-        if (c->transform == VSOM_MEDIAN)
-            hipLaunchKernelGGL(masked_chain_kernel<true>, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, lay.at(bxy),
-                               (int)B, lay.at(bits), (int)nwords, lay.at(dcols), lay.at(ndirty), c->lut.p, (int)c->lut_w,
-                               (int)c->lut_h, (int)c->W, (int)c->H, (int)N, c->map.p, c->sigma.p, (int)c->pitch);
-        else
-            hipLaunchKernelGGL(masked_chain_kernel<false>, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, lay.at(bxy),
-                               (int)B, lay.at(bits), (int)nwords, lay.at(dcols), lay.at(ndirty), c->lut.p, (int)c->lut_w,
-                               (int)c->lut_h, (int)c->W, (int)c->H, (int)N, c->map.p, c->sigma.p, (int)c->pitch);
+        vsom_bxy_enqueue(c, lay.at(bxy));
+        const auto k = c->transform == VSOM_MEDIAN ? masked_chain_kernel<true> : masked_chain_kernel<false>;
+        hipLaunchKernelGGL(k, dim3((unsigned)((N + 63) / 64), (unsigned)(((J + CH_CB - 1) / CH_CB + 3) / 4)), dim3(256), 0,
+                           c->stream, c->Xs.p, (int)c->xpitch, lay.at(bxy), (int)B, lay.at(ms.bits), (int)ms.nwords,
+                           lay.at(ms.dcols), lay.at(ms.ndirty), c->lut.p, (int)c->lut_w, (int)c->lut_h, (int)c->W, (int)c->H,
+                           (int)N, c->map.p, c->sigma.p, (int)c->pitch);
         VSOM_HIP_CHECK(hipGetLastError());
     }
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
