@@ -4,7 +4,7 @@ contexts driven one call at a time (vsom_upload_chunk, vsom_bmu_batch), and agai
 (tiny maps of the three kinds, maps above the tiny bound, a chunk that gets the column compaction, a custom member, no
 rows, shared and distinct offsets with gaps), the asynchronous form on both stream layouts, a member with a chunk staged
 ahead, the search's NaN / tie rules at chunk sizes around the tile and at the tiny bound, more members than the chip has
-CUs, and the refusals."""
+CUs, all six ensemble calls back to back on one ensemble, and the refusals."""
 import ctypes as C
 
 import numpy as np
@@ -213,6 +213,69 @@ def test_async_upload_then_train_at_once(layout):
         p.m.synchronize()
         p.close()
     for pin, _, _ in bufs:
+        pin.free()
+
+
+@pytest.mark.parametrize("layout", ["shared", "one_apart", "each_own"])
+def test_all_calls_back_to_back_on_one_ensemble(layout):
+    """the six calls share the ensemble's two descriptor slots and its launch stream, each with a descriptor size of its
+    own: two rounds of upload (wait = 0), schedule, batch epoch, online chunk, scoring, U-matrix on one ensemble of tiny
+    maps of the three kinds, a map just above the tiny bound and a member without rows in the first round -- every returned
+    array and every member's state after each call equal the twins' driven one single-context call at a time"""
+    import torch
+    specs = [(10, 10, 9, po.STANDARD), (12, 9, 20, po.MEDIAN), (7, 7, 6, po.CLR),
+             (33, 32, 4, po.STANDARD),                        # N * D = 4224: the ordinary way in every call
+             (8, 8, 12, po.MEDIAN)]                           # no rows in the first round
+    pairs = [Pair(W, H, J, tr, 160 + i) for i, (W, H, J, tr) in enumerate(specs)]
+    n = len(pairs)
+    dev = torch.device("cuda", 0)
+    streams = [torch.cuda.Stream(device=dev) for _ in range(n)]
+    for k, p in enumerate(pairs):
+        own = layout == "each_own" or (layout == "one_apart" and k == 3)
+        p.m.set_stream(streams[k if own else 0].cuda_stream)
+    ens = vsom_amd.Ensemble([p.m for p in pairs])
+    eta, fn = [0.05] * n, [EXP] * n
+    pins = []
+    for rnd, Bs in enumerate(([20, 37, 40, 500, 0], [20, 37, 40, 500, 50])):
+        # (the NaN and inf rows only in the last round: no state is compared as NaN against NaN before it)
+        chunks = [gen.correlated(B, p.J, 170 + 10 * rnd + k) if p.tr == po.CLR
+                  else rows(B, p.J, 170 + 10 * rnd + k, special=rnd == 1) for k, (p, B) in enumerate(zip(pairs, Bs))]
+        flat, offs = pack(chunks, [None] * n, seed=rnd)
+        pin = capi.PinnedBuffer(flat.shape)
+        pin.array[:] = flat
+        pins.append(pin)
+        what = (layout, rnd)
+        ens.upload_chunks_async(pin, offs, Bs)
+        for k, p in enumerate(pairs):
+            p.t.upload_chunk(chunks[k])
+        sched = [[3.0 - 0.5 * ep + 0.1 * k for ep in range(3)] for k in range(n)]
+        mses = ens.batch_schedule(sched)
+        for k, p in enumerate(pairs):
+            assert beq(mses[k], p.t.batch_schedule(sched[k])), (what, "schedule mse", k)
+            p.same((what, "schedule", k))
+        sigma = [2.0 + 0.25 * k for k in range(n)]
+        mse = ens.batch_epoch(sigma, False)
+        for k, p in enumerate(pairs):
+            p.same((what, "batch", k), mse[k], p.t.batch_epoch(sigma[k], False))
+        mse, lbs = ens.train_online_chunk_fetch(eta, sigma, fn, first_chunk=rnd == 0)
+        for k, p in enumerate(pairs):
+            mse_t, lb_t = p.t.train_online_chunk_fetch(eta[k], sigma[k], fn[k], first_chunk=rnd == 0)
+            assert beq(lbs[k], lb_t), (what, "online lastBMU", k)
+            p.same((what, "online", k), mse[k], mse_t)
+        score_twins(pairs, ens.bmu_batch())
+        for k, p in enumerate(pairs):
+            p.same((what, "score", k))
+        um = ens.umatrix()
+        for k, p in enumerate(pairs):
+            um_t = p.t.umatrix()
+            assert um[k].dtype == um_t.dtype == np.float64, (what, "umatrix", k)
+            assert ((um[k].view(np.uint64) == um_t.view(np.uint64)) | (np.isnan(um[k]) & np.isnan(um_t))).all(), (what, "umatrix", k)
+            p.same((what, "umatrix", k))
+    ens.close()
+    for p in pairs:
+        p.m.synchronize()
+        p.close()
+    for pin in pins:
         pin.free()
 
 

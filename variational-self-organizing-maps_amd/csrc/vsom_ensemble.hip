@@ -37,6 +37,7 @@ struct vsom_ensemble {
     std::vector<unsigned char> desc;         // one descriptor per member, packed at the kind's own descriptor size
     std::vector<int> grp, lslot;
     std::vector<size_t> smem;
+    std::vector<unsigned> ext;               // the grid's other dimension: 16-row blocks (staging), 64-row tiles (scoring)
     // upload: the members' rows as one copy of the host range (grow-only); ev_raw is recorded behind the call's last
     // reader of it (the staging launch, and -- joined back into the launch stream -- the ordinary stagings)
     DevBuf<float> raw;
@@ -128,84 +129,86 @@ void vsom_ensemble_destroy(vsom_ensemble *e)
 
 size_t vsom_ensemble_size(const vsom_ensemble *e) { return e ? e->m.size() : 0; }
 
-// what every train call does for each member first: the bookkeeping of CHECK_CTX (join the side stream; whatever follows
-// reads the staged rows, so a later stage-ahead must not take them)
-static int join_members(vsom_ensemble *e)
+// why a call that reads the staged rows refuses a member, or null
+static const char *ens_rows_refusal(const vsom_ctx *c)
 {
-    for (vsom_ctx *c : e->m) {
-        if (int rc = vsom_join_aux(c))
+    if (!c->chunk_loaded)
+        return "no chunk loaded";
+    if (c->ahead_rows)
+        return "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first";
+    return nullptr;
+}
+
+// what every call does first for each member (`only`: for those with only[k] != 0): the bookkeeping of CHECK_CTX -- join
+// the side stream and, where the call reads the staged rows, keep a later stage-ahead from taking them
+static int join_members(vsom_ensemble *e, const size_t *only, bool reads_rows)
+{
+    for (size_t k = 0; k < e->m.size(); ++k) {
+        if (only && !only[k])
+            continue;
+        if (int rc = vsom_join_aux(e->m[k]))
             return rc;
-        c->rows_free_valid = false;
+        if (reads_rows)
+            e->m[k]->rows_free_valid = false;
     }
     return VSOM_OK;
 }
 
-// the launches of the members whose e->grp[k] >= 0: ready(group) for every group first (nothing is launched unless all
-// of them can be), descriptors -- `stride` bytes each, the size the kernel indexes its array by -- into a free slot, the
-// launch stream joined to every such member's stream, one launch(group, desc_dev, count, smem) per group.
-// *ls_out: the launch stream (null: no launch).  The caller waits for it before it returns, on every path: that wait
-// orders whatever is enqueued on a member's stream afterwards behind the launches (so no event joins the member streams
-// back), and it is what releases the members' table slots.
-template <typename Ready, typename Launch>
-static int launch_groups(vsom_ensemble *e, int ngroups, size_t stride, Ready ready, Launch launch, hipStream_t *ls_out)
+// the per-member inputs of ens_launch, cleared: no member is launched
+static void ens_scratch(vsom_ensemble *e, size_t stride)
 {
-    *ls_out = nullptr;
     const size_t n = e->m.size();
-    std::vector<unsigned> cnt(ngroups, 0);
-    std::vector<size_t> gsmem(ngroups, 0);
-    hipStream_t shared = nullptr;
-    bool first = true, same = true;
-    for (size_t k = 0; k < n; ++k) {
-        const int g = e->grp[k];
-        if (g < 0)
-            continue;
-        ++cnt[g];
-        gsmem[g] = std::max(gsmem[g], e->smem[k]);
-        if (first)
-            shared = e->m[k]->stream;
-        else if (e->m[k]->stream != shared)
-            same = false;
-        first = false;
-    }
-    if (first)
-        return VSOM_OK;                      // no member takes the one-launch kernel
-    for (int g = 0; g < ngroups; ++g)
-        if (cnt[g])
-            if (int rc = ready(g))
-                return rc;
-    std::vector<size_t> off(ngroups + 1, 0);
-    for (int g = 0; g < ngroups; ++g)
-        off[g + 1] = off[g] + cnt[g];
-    const size_t bytes = off[ngroups] * stride;
+    e->desc.resize(n * stride);
+    e->grp.assign(n, -1);
+    e->lslot.assign(n, 0);
+    e->smem.assign(n, 0);
+    e->ext.assign(n, 0);
+}
 
-    // a free slot: its last launch has completed
-    auto &s = e->slot[e->next];
-    if (!s.ev)
-        VSOM_HIP_CHECK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    if (s.valid)
-        VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
-    s.valid = false;
-    if (bytes > s.host.cap) {
-        const size_t cap = std::max(bytes, (size_t)64 * stride);
-        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, VSOM_BUF_REBUILD, {vsom_member(s.host, cap), vsom_member(s.dev, cap)}));
-    }
-    std::vector<size_t> at(off.begin(), off.end() - 1);
-    for (size_t k = 0; k < n; ++k)
-        if (e->grp[k] >= 0)
-            std::memcpy(s.host.p + (at[e->grp[k]]++) * stride, e->desc.data() + k * stride, stride);
+// whose streams the launch stream runs behind: the members of the call's launches, or every member but the custom ones
+// (an event record per distinct stream: the smaller set where it is enough); ENS_JOINED: the caller has joined already
+enum EnsSet { ENS_LAUNCHED, ENS_PLAIN, ENS_JOINED };
 
-    // the launch stream: the members' one stream, or the ensemble's own behind every member stream's pending work
-    hipStream_t ls = shared;
-    std::vector<hipStream_t> streams;
-    if (!same) {
+// What one call enqueues for the ensemble, and the one way out of that call.  Declared before the call's first enqueue:
+// whichever return leaves the scope -- a failed HIP call or allocation, a member's rc -- waits for the launch stream
+// first (end() on the ordinary way and reports the wait's status; the destructor on every other, where the status that
+// is returned is the first failure's).  That wait orders whatever is enqueued on a member's stream afterwards behind the
+// launches (so no event joins the member streams back), and it is what releases the members' table slots.
+struct EnsCall {
+    vsom_ensemble *e;
+    hipStream_t ls = nullptr;                // the launch stream (null: nothing joined or launched yet)
+    hipStream_t also = nullptr;              // the schedule's table copies: a launched member's stream
+    std::vector<hipStream_t> streams;        // the distinct streams of the last join
+    bool onl_slots = false;                  // online training: e->lslot[] of the launched members is released
+    bool open = true;
+    explicit EnsCall(vsom_ensemble *ens) : e(ens) {}
+    EnsCall(const EnsCall &) = delete;
+    ~EnsCall()
+    {
+        if (open)
+            (void)wait(true);
+    }
+    // the launch stream: the set's one stream (the fast form: no events), or the ensemble's own behind the pending work
+    // of every stream of the set.  May be repeated: new work on the member streams is joined in.
+    int join(EnsSet set)
+    {
+        streams.clear();
+        for (size_t k = 0; k < e->m.size(); ++k)
+            if ((set == ENS_LAUNCHED ? e->grp[k] >= 0 : !e->m[k]->cu) &&
+                (streams.empty() || streams.back() != e->m[k]->stream))
+                streams.push_back(e->m[k]->stream);
+        if (streams.size() > 1) {            // (one stream, or runs of a few, need no sort)
+            std::sort(streams.begin(), streams.end());
+            streams.erase(std::unique(streams.begin(), streams.end()), streams.end());
+        }
+        if (streams.size() <= 1) {
+            if (!streams.empty())
+                ls = streams[0];
+            return VSOM_OK;
+        }
         if (!e->own_stream)
             VSOM_HIP_CHECK(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
         ls = e->own_stream;
-        for (size_t k = 0; k < n; ++k)
-            if (e->grp[k] >= 0)
-                streams.push_back(e->m[k]->stream);
-        std::sort(streams.begin(), streams.end());
-        streams.erase(std::unique(streams.begin(), streams.end()), streams.end());
         while (e->ev_in.size() < streams.size()) {
             hipEvent_t ev = nullptr;
             VSOM_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -215,13 +218,101 @@ static int launch_groups(vsom_ensemble *e, int ngroups, size_t stride, Ready rea
             VSOM_HIP_CHECK(hipEventRecord(e->ev_in[i], streams[i]));
             VSOM_HIP_CHECK(hipStreamWaitEvent(ls, e->ev_in[i], 0));
         }
+        return VSOM_OK;
     }
-    *ls_out = ls;
+    // the host wait that ends the call.  failed: something may be left on the joined member streams as well (an upload's
+    // ordinary stagings read e->raw there), so they are drained too and e->raw has no reader that ev_raw does not cover.
+    hipError_t wait(bool failed)
+    {
+        open = false;
+        hipError_t err = hipSuccess;
+        auto sync = [&err](hipStream_t s) {
+            const hipError_t x = s ? hipStreamSynchronize(s) : hipSuccess;
+            if (err == hipSuccess)
+                err = x;
+        };
+        sync(also);
+        if (failed)
+            for (hipStream_t s : streams)
+                sync(s);
+        sync(ls);
+        // (also on an error: a launched member's table slot is released only once its reader has completed)
+        for (size_t k = 0; k < e->m.size() && onl_slots && ls; ++k)
+            if (e->grp[k] >= 0)
+                vsom_onl_tiny_done(e->m[k], e->lslot[k]);
+        return err;
+    }
+    int end(int rc)
+    {
+        const hipError_t err = wait(rc != VSOM_OK);
+        if (rc)
+            return rc;                       // (the first failure is the one reported)
+        VSOM_HIP_CHECK_AS(err, "hipStreamSynchronize(ls)");
+        return VSOM_OK;
+    }
+    void detach() { open = false; }          // (the asynchronous upload: its success returns without a host wait)
+};
+
+// The launches of the members whose e->grp[k] >= 0, from the per-member inputs the caller has filled: e->grp (the group),
+// e->desc (`stride` bytes each, the size the kernel indexes its array by), e->smem (the LDS need) and e->ext (the extent
+// on the grid's other dimension, where the kernel has one).  ready(group) for every group first (nothing is launched
+// unless all of them can be), the launch stream joined to the streams of `set`, the descriptors sorted by group into a
+// free slot and sent, then launch(group, desc_dev, count, smem, ext, ls) per group with the group's largest smem and
+// ext -- in slices of at most `cap` members, the bound of the grid dimension the members sit on.
+constexpr unsigned ENS_NO_CAP = ~0u;         // members on grid.x
+static int ens_always_ready(int) { return VSOM_OK; }
+
+template <typename Ready, typename Launch>
+static int ens_launch(EnsCall &call, EnsSet set, int ngroups, size_t stride, unsigned cap, Ready ready, Launch launch)
+{
+    vsom_ensemble *e = call.e;
+    const size_t n = e->m.size();
+    std::vector<size_t> off(ngroups + 1, 0), gsmem(ngroups, 0);
+    std::vector<unsigned> gext(ngroups, 0);
+    for (size_t k = 0; k < n; ++k) {
+        const int g = e->grp[k];
+        if (g < 0)
+            continue;
+        ++off[g + 1];
+        gsmem[g] = std::max(gsmem[g], e->smem[k]);
+        gext[g] = std::max(gext[g], e->ext[k]);
+    }
+    for (int g = 0; g < ngroups; ++g) {
+        if (off[g + 1])
+            if (int rc = ready(g))
+                return rc;
+        off[g + 1] += off[g];
+    }
+    if (off[ngroups] == 0)
+        return VSOM_OK;                      // no member is launched
+    if (set != ENS_JOINED)
+        if (int rc = call.join(set))
+            return rc;
+    hipStream_t ls = call.ls;
+
+    // a free slot: its last launch has completed
+    auto &s = e->slot[e->next];
+    if (!s.ev)
+        VSOM_HIP_CHECK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
+    if (s.valid)
+        VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
+    s.valid = false;
+    const size_t bytes = off[ngroups] * stride;
+    if (bytes > s.host.cap) {
+        const size_t grown = std::max(bytes, (size_t)64 * stride);
+        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, VSOM_BUF_REBUILD, {vsom_member(s.host, grown), vsom_member(s.dev, grown)}));
+    }
+    std::vector<size_t> at(off.begin(), off.end() - 1);
+    for (size_t k = 0; k < n; ++k)
+        if (e->grp[k] >= 0)
+            std::memcpy(s.host.p + (at[e->grp[k]]++) * stride, e->desc.data() + k * stride, stride);
     VSOM_HIP_CHECK(hipMemcpyAsync(s.dev.p, s.host.p, bytes, hipMemcpyHostToDevice, ls));
     for (int g = 0; g < ngroups; ++g)
-        if (cnt[g])
-            if (int rc = launch(g, s.dev.p + off[g] * stride, cnt[g], gsmem[g], ls))
+        for (size_t i = off[g]; i < off[g + 1]; i += cap) {
+            const unsigned cnt = (unsigned)std::min(off[g + 1] - i, (size_t)cap);
+            if (int rc = launch(g, s.dev.p + i * stride, cnt, gsmem[g], gext[g], ls))
                 return rc;
+        }
     VSOM_HIP_CHECK(hipEventRecord(s.ev, ls));
     s.valid = true;
     e->next ^= 1;
@@ -241,19 +332,16 @@ int vsom_ensemble_train_online_chunk_fetch(vsom_ensemble *e, const double *eta, 
         const vsom_ctx *c = e->m[k];
         if (decay_fn[k] != VSOM_EXPONENTIAL && decay_fn[k] != VSOM_INVERSE_PROPORTIONAL)
             return ens_fail(k, "online training needs Exponential or InverseProportional");
-        if (!c->chunk_loaded)
-            return ens_fail(k, "no chunk loaded");
-        if (c->ahead_rows)
-            return ens_fail(k, "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first");
+        if (const char *why = ens_rows_refusal(c))
+            return ens_fail(k, why);
     }
     VSOM_HIP_CHECK(hipSetDevice(e->device));
-    if (int rc = join_members(e))
+    EnsCall call(e);
+    call.onl_slots = true;
+    if (int rc = join_members(e, nullptr, true))
         return rc;
     const size_t stride = vsom_onl_tiny_desc_bytes();
-    e->desc.resize(n * stride);
-    e->grp.assign(n, -1);
-    e->lslot.assign(n, 0);
-    e->smem.assign(n, 0);
+    ens_scratch(e, stride);
     for (size_t k = 0; k < n; ++k) {
         vsom_ctx *c = e->m[k];
         if (c->cu)
@@ -263,25 +351,18 @@ int vsom_ensemble_train_online_chunk_fetch(vsom_ensemble *e, const double *eta, 
                                            e->desc.data() + k * stride, &e->grp[k], &e->smem[k], &e->lslot[k]))
             return rc;
     }
-    hipStream_t ls = nullptr;
-    int rc = launch_groups(
-        e, VSOM_ONL_TINY_GROUPS, stride, [&](int g) { return vsom_onl_tiny_ready(g, e->device, e->lds_limit); },
-        [&](int g, const void *d, unsigned cnt, size_t smem, hipStream_t s) {
+    int rc = ens_launch(
+        call, ENS_LAUNCHED, VSOM_ONL_TINY_GROUPS, stride, ENS_NO_CAP,
+        [&](int g) { return vsom_onl_tiny_ready(g, e->device, e->lds_limit); },
+        [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t s) {
             return vsom_onl_tiny_launch_many(g, d, cnt, smem, s);
-        },
-        &ls);
+        });
     // the other members through their ordinary path, while the launches run
     for (size_t k = 0; k < n && !rc; ++k)
         if (e->grp[k] < 0)
             rc = vsom_train_online_chunk_fetch(e->m[k], eta[k], sigma[k], decay_fn[k], first_chunk,
                                                lastbmu_out ? lastbmu_out[k] : nullptr, mse_out ? mse_out + k : nullptr);
-    // (also on an error: a launched member's table slot is released only once its reader has completed)
-    if (ls)
-        VSOM_HIP_CHECK(hipStreamSynchronize(ls));
-    for (size_t k = 0; k < n; ++k)
-        if (e->grp[k] >= 0 && ls)
-            vsom_onl_tiny_done(e->m[k], e->lslot[k]);
-    if (rc)
+    if ((rc = call.end(rc)))
         return rc;
     // results of the launched members: the kernels stored them into each member's pinned words
     for (size_t k = 0; k < n; ++k) {
@@ -303,20 +384,15 @@ int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_firs
     if (!sigma)
         return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null parameter array");
     const size_t n = e->m.size();
-    for (size_t k = 0; k < n; ++k) {
-        const vsom_ctx *c = e->m[k];
-        if (!c->chunk_loaded)
-            return ens_fail(k, "no chunk loaded");
-        if (c->ahead_rows)
-            return ens_fail(k, "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first");
-    }
+    for (size_t k = 0; k < n; ++k)
+        if (const char *why = ens_rows_refusal(e->m[k]))
+            return ens_fail(k, why);
     VSOM_HIP_CHECK(hipSetDevice(e->device));
-    if (int rc = join_members(e))
+    EnsCall call(e);
+    if (int rc = join_members(e, nullptr, true))
         return rc;
     const size_t stride = vsom_tiny_desc_bytes();
-    e->desc.resize(n * stride);
-    e->grp.assign(n, -1);
-    e->smem.assign(n, 0);
+    ens_scratch(e, stride);
     for (size_t k = 0; k < n; ++k) {
         vsom_ctx *c = e->m[k];
         if (c->cu)
@@ -326,17 +402,14 @@ int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_firs
                                        e->desc.data() + k * stride, &e->grp[k], &e->smem[k]))
             return rc;
     }
-    hipStream_t ls = nullptr;
-    int rc = launch_groups(
-        e, VSOM_TINY_GROUPS, stride, [](int) { return VSOM_OK; },
-        [&](int g, const void *d, unsigned cnt, size_t smem, hipStream_t s) { return vsom_tiny_launch_many(g, d, cnt, smem, s); },
-        &ls);
+    int rc = ens_launch(call, ENS_LAUNCHED, VSOM_TINY_GROUPS, stride, ENS_NO_CAP, ens_always_ready,
+                        [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t s) {
+                            return vsom_tiny_launch_many(g, d, cnt, smem, s);
+                        });
     for (size_t k = 0; k < n && !rc; ++k)
         if (e->grp[k] < 0)
             rc = vsom_batch_epoch(e->m[k], sigma[k], is_first, mse_out ? mse_out + k : nullptr);
-    if (ls)
-        VSOM_HIP_CHECK(hipStreamSynchronize(ls));
-    if (rc)
+    if ((rc = call.end(rc)))
         return rc;
     for (size_t k = 0; k < n; ++k)
         if (e->grp[k] >= 0 && mse_out)
@@ -364,13 +437,9 @@ int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma, c
             return ens_fail(k, why);
     }
     VSOM_HIP_CHECK(hipSetDevice(e->device));
-    for (size_t k = 0; k < n; ++k) {         // join_members, but a member without epochs is not touched
-        if (!epochs[k])
-            continue;
-        if (int rc = vsom_join_aux(e->m[k]))
-            return rc;
-        e->m[k]->rows_free_valid = false;
-    }
+    EnsCall call(e);
+    if (int rc = join_members(e, epochs, true))   // (a member without epochs is not touched)
+        return rc;
     // who is launched
     const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);
     std::vector<int> kind(n, -1);
@@ -385,15 +454,13 @@ int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma, c
         if (!first_launched)
             first_launched = c;
     }
-    hipStream_t ls = nullptr;
     int rc = VSOM_OK;
     if (first_launched) {
         for (size_t k = 0; k < n; ++k)
             if (kind[k] >= 0)
                 VSOM_ALLOC_CHECK(vsom_grow(e->m[k]->sch_mse, epochs[k], e->m[k]->stream, VSOM_BUF_SYNC));
+        call.also = first_launched->stream;  // the table copies below
         const size_t stride = vsom_tiny_sched_desc_bytes();
-        e->desc.resize(n * stride);
-        e->smem.assign(n, 0);
         std::vector<size_t> tab_at(n, 0);    // the member's first offset word of the round
         std::vector<unsigned> tab;
         for (size_t e0 = 0; e0 < longest && !rc; e0 += VSOM_SCHEDULE_MAX_EPOCHS) {
@@ -416,7 +483,7 @@ int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma, c
             }
             if (e0) {                        // the previous round has read the image and the device buffer
                 VSOM_HIP_CHECK(hipStreamSynchronize(first_launched->stream));
-                VSOM_HIP_CHECK(hipStreamSynchronize(ls));
+                VSOM_HIP_CHECK(hipStreamSynchronize(call.ls));
             }
             // (no kernel of an earlier call or round is running now)
             const size_t bytes = (tabs.floats + tab.size()) * sizeof(float);
@@ -427,7 +494,7 @@ int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma, c
             VSOM_HIP_CHECK(hipMemcpyAsync(e->sch_dev.p, e->sch_host.p, bytes, hipMemcpyHostToDevice, first_launched->stream));
             const float *lut_dev = reinterpret_cast<const float *>(e->sch_dev.p);
             const unsigned *tab_dev = reinterpret_cast<const unsigned *>(e->sch_dev.p + tabs.floats * sizeof(float));
-            e->grp.assign(n, -1);
+            ens_scratch(e, stride);
             for (size_t k = 0; k < n; ++k) {
                 if (kind[k] < 0)
                     continue;
@@ -438,27 +505,17 @@ int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma, c
                 e->grp[k] = vsom_tiny_sched_fill(c, lut_dev, tab_dev + (cnt ? tab_at[k] : 0), c->sch_mse.p + (cnt ? e0 : 0), cnt,
                                                  e0 == 0, reset_bmu, e->desc.data() + k * stride, &e->smem[k]);
             }
-            hipStream_t rs = nullptr;
-            rc = launch_groups(
-                e, VSOM_TINY_GROUPS, stride, [](int) { return VSOM_OK; },
-                [&](int g, const void *d, unsigned cnt, size_t smem, hipStream_t s) {
-                    return vsom_tiny_sched_launch_many(g, d, cnt, smem, s);
-                },
-                &rs);
-            if (rs)
-                ls = rs;
+            rc = ens_launch(call, ENS_LAUNCHED, VSOM_TINY_GROUPS, stride, ENS_NO_CAP, ens_always_ready,
+                            [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t s) {
+                                return vsom_tiny_sched_launch_many(g, d, cnt, smem, s);
+                            });
         }
     }
     // the other members through the sequence of single epochs, while the launches run
     for (size_t k = 0; k < n && !rc; ++k)
         if (kind[k] < 0 && epochs[k])
             rc = vsom_schedule_loop(e->m[k], sigma[k], epochs[k], reset_bmu, mse_out[k]);
-    // (also on an error: what was enqueued completes before the call returns)
-    if (first_launched)
-        VSOM_HIP_CHECK(hipStreamSynchronize(first_launched->stream));
-    if (ls)
-        VSOM_HIP_CHECK(hipStreamSynchronize(ls));
-    if (rc)
+    if ((rc = call.end(rc)))
         return rc;
     for (size_t k = 0; k < n; ++k)
         if (kind[k] >= 0)
@@ -566,69 +623,6 @@ __global__ __launch_bounds__(256) void ensemble_bmu_many_kernel(const EnsScoreDe
     }
 }
 
-// the launch stream of a call that enqueues device work for the non-custom members: their one stream, or the ensemble's
-// own behind every member stream's pending work.  *streams: the distinct member streams.
-static int ens_launch_stream(vsom_ensemble *e, std::vector<hipStream_t> *streams, hipStream_t *ls)
-{
-    streams->clear();
-    for (vsom_ctx *c : e->m)
-        if (!c->cu)
-            streams->push_back(c->stream);
-    std::sort(streams->begin(), streams->end());
-    streams->erase(std::unique(streams->begin(), streams->end()), streams->end());
-    *ls = nullptr;
-    if (streams->empty())
-        return VSOM_OK;
-    if (streams->size() == 1) {
-        *ls = (*streams)[0];
-        return VSOM_OK;
-    }
-    if (!e->own_stream)
-        VSOM_HIP_CHECK(hipStreamCreateWithFlags(&e->own_stream, hipStreamNonBlocking));
-    *ls = e->own_stream;
-    while (e->ev_in.size() < streams->size()) {
-        hipEvent_t ev = nullptr;
-        VSOM_HIP_CHECK(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-        e->ev_in.push_back(ev);
-    }
-    for (size_t i = 0; i < streams->size(); ++i) {
-        VSOM_HIP_CHECK(hipEventRecord(e->ev_in[i], (*streams)[i]));
-        VSOM_HIP_CHECK(hipStreamWaitEvent(*ls, e->ev_in[i], 0));
-    }
-    return VSOM_OK;
-}
-
-// `count` descriptors of `stride` bytes into a free slot and onto the device (on ls); the caller launches from *dev and
-// then calls ens_slot_done
-static int ens_slot_put(vsom_ensemble *e, const void *desc, size_t count, size_t stride, hipStream_t ls,
-                        const unsigned char **dev)
-{
-    auto &s = e->slot[e->next];
-    if (!s.ev)
-        VSOM_HIP_CHECK(hipEventCreateWithFlags(&s.ev, hipEventDisableTiming));
-    if (s.valid)
-        VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
-    s.valid = false;
-    const size_t bytes = count * stride;
-    if (bytes > s.host.cap) {
-        const size_t cap = std::max(bytes, (size_t)64 * stride);
-        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, VSOM_BUF_REBUILD, {vsom_member(s.host, cap), vsom_member(s.dev, cap)}));
-    }
-    std::memcpy(s.host.p, desc, bytes);
-    VSOM_HIP_CHECK(hipMemcpyAsync(s.dev.p, s.host.p, bytes, hipMemcpyHostToDevice, ls));
-    *dev = s.dev.p;
-    return VSOM_OK;
-}
-
-static int ens_slot_done(vsom_ensemble *e, hipStream_t ls)
-{
-    auto &s = e->slot[e->next];
-    VSOM_HIP_CHECK(hipEventRecord(s.ev, ls));
-    s.valid = true;
-    e->next ^= 1;
-    return VSOM_OK;
-}
-
 // grid.y is at most 65535: more members are launched in slices
 constexpr unsigned ENS_MAX_Y = 65535;
 
@@ -650,11 +644,12 @@ int vsom_ensemble_upload_chunks(vsom_ensemble *e, const float *x_host, size_t n_
             return ens_fail(k, "rows beyond n_floats");
     }
     VSOM_HIP_CHECK(hipSetDevice(e->device));
-    if (int rc = join_members(e))
+    EnsCall call(e);
+    if (int rc = join_members(e, nullptr, true))
         return rc;
     // host bookkeeping first (a capacity that grows synchronises the member and reallocates); which members the one
     // launch stages (grp 0), and the extent of the rows on the device
-    e->grp.assign(n, -1);
+    ens_scratch(e, sizeof(EnsStageDesc));
     size_t lo = SIZE_MAX, hi = 0;
     for (size_t k = 0; k < n; ++k) {
         vsom_ctx *c = e->m[k];
@@ -669,8 +664,6 @@ int vsom_ensemble_upload_chunks(vsom_ensemble *e, const float *x_host, size_t n_
         if (c->transform != VSOM_CLR && !vsom_cc_considered(c, B[k]))
             e->grp[k] = 0;
     }
-    std::vector<hipStream_t> streams;
-    hipStream_t ls = nullptr;
     if (hi > lo) {
         if (hi - lo > e->raw.cap) {
             if (e->raw_valid)                    // an earlier call's staging may still read the old buffer
@@ -682,14 +675,14 @@ int vsom_ensemble_upload_chunks(vsom_ensemble *e, const float *x_host, size_t n_
             VSOM_HIP_CHECK(hipEventCreateWithFlags(&e->ev_raw, hipEventDisableTiming));
         if (!e->ev_stage)
             VSOM_HIP_CHECK(hipEventCreateWithFlags(&e->ev_stage, hipEventDisableTiming));
-        if (int rc = ens_launch_stream(e, &streams, &ls))
+        // (joined here, not by ens_launch: the copy goes first, and it is made whether or not a member is launched)
+        if (int rc = call.join(ENS_PLAIN))
             return rc;
+        hipStream_t ls = call.ls;
         if (e->raw_valid)                        // (behind the previous call's readers, whichever stream it used)
             VSOM_HIP_CHECK(hipStreamWaitEvent(ls, e->ev_raw, 0));
         VSOM_HIP_CHECK(hipMemcpyAsync(e->raw.p, x_host + lo, (hi - lo) * sizeof(float), hipMemcpyHostToDevice, ls));
         // the one launch: launch_stage_chunk's bookkeeping for each of its members, then the descriptors
-        std::vector<EnsStageDesc> d;
-        unsigned blocks = 0;
         for (size_t k = 0; k < n; ++k) {
             if (e->grp[k] != 0)
                 continue;
@@ -705,24 +698,22 @@ int vsom_ensemble_upload_chunks(vsom_ensemble *e, const float *x_host, size_t n_
                 c->ahead_rows = false;
             }
             c->ahead_valid = false;
-            d.push_back({e->raw.p + (offset[k] - lo), c->Xs.p, c->lastbmu.p, c->sl_scal.p ? c->sl_scal.p + 8192 : nullptr,
-                         (int)c->J, (int)B[k], (int)c->xpitch, 0});
-            blocks = std::max(blocks, (unsigned)((B[k] + 15) / 16));
+            const EnsStageDesc d = {e->raw.p + (offset[k] - lo), c->Xs.p, c->lastbmu.p,
+                                    c->sl_scal.p ? c->sl_scal.p + 8192 : nullptr, (int)c->J, (int)B[k], (int)c->xpitch, 0};
+            std::memcpy(e->desc.data() + k * sizeof(d), &d, sizeof(d));
+            e->ext[k] = (unsigned)((B[k] + 15) / 16);
         }
-        for (size_t i0 = 0; i0 < d.size(); i0 += ENS_MAX_Y) {
-            const size_t cnt = std::min(d.size() - i0, (size_t)ENS_MAX_Y);
-            const unsigned char *dev = nullptr;
-            if (int rc = ens_slot_put(e, d.data() + i0, cnt, sizeof(EnsStageDesc), ls, &dev))
-                return rc;
-            hipLaunchKernelGGL(stage_rows_many_kernel, dim3(blocks, (unsigned)cnt), dim3(256), 0, ls,
-                               reinterpret_cast<const EnsStageDesc *>(dev));
-            VSOM_HIP_CHECK(hipGetLastError());
-            if (int rc = ens_slot_done(e, ls))
-                return rc;
-        }
+        if (int rc = ens_launch(call, ENS_JOINED, 1, sizeof(EnsStageDesc), ENS_MAX_Y, ens_always_ready,
+                                [](int, const void *d, unsigned cnt, size_t, unsigned blocks, hipStream_t s) -> int {
+                                    hipLaunchKernelGGL(stage_rows_many_kernel, dim3(blocks, cnt), dim3(256), 0, s,
+                                                       static_cast<const EnsStageDesc *>(d));
+                                    VSOM_HIP_CHECK(hipGetLastError());
+                                    return VSOM_OK;
+                                }))
+            return rc;
         // every member stream behind the copy and the staging: later work on a member, and the ordinary stagings below
         VSOM_HIP_CHECK(hipEventRecord(e->ev_stage, ls));
-        for (hipStream_t s : streams)
+        for (hipStream_t s : call.streams)
             if (s != ls)
                 VSOM_HIP_CHECK(hipStreamWaitEvent(s, e->ev_stage, 0));
     }
@@ -737,18 +728,17 @@ int vsom_ensemble_upload_chunks(vsom_ensemble *e, const float *x_host, size_t n_
         if (rc)
             return rc;
     }
-    if (ls) {
-        // the raw buffer's last readers: the next call (or a growth) waits for ev_raw before it overwrites the buffer
-        for (size_t i = 0; i < streams.size(); ++i)
-            if (streams[i] != ls) {
-                VSOM_HIP_CHECK(hipEventRecord(e->ev_in[i], streams[i]));
-                VSOM_HIP_CHECK(hipStreamWaitEvent(ls, e->ev_in[i], 0));
-            }
-        VSOM_HIP_CHECK(hipEventRecord(e->ev_raw, ls));
+    if (call.ls) {
+        // the raw buffer's last readers, joined back into the launch stream: the next call (or a growth) waits for ev_raw
+        // before it overwrites the buffer
+        if (int rc = call.join(ENS_PLAIN))
+            return rc;
+        VSOM_HIP_CHECK(hipEventRecord(e->ev_raw, call.ls));
         e->raw_valid = true;
         if (wait)                                // x_host may be reused by the caller
             VSOM_HIP_CHECK(hipEventSynchronize(e->ev_raw));
     }
+    call.detach();                               // (wait = 0 returns without a host wait; ev_raw covers what is in flight)
     return VSOM_OK;
 }
 
@@ -757,19 +747,17 @@ int vsom_ensemble_bmu_batch(vsom_ensemble *e, uint64_t *const *idx_out, float *c
     if (!e)
         return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
     const size_t n = e->m.size();
-    for (size_t k = 0; k < n; ++k) {
-        const vsom_ctx *c = e->m[k];
-        if (!c->chunk_loaded)
-            return ens_fail(k, "no chunk loaded");
-        if (c->ahead_rows)
-            return ens_fail(k, "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first");
-    }
+    for (size_t k = 0; k < n; ++k)
+        if (const char *why = ens_rows_refusal(e->m[k]))
+            return ens_fail(k, why);
     VSOM_HIP_CHECK(hipSetDevice(e->device));
-    if (int rc = join_members(e))
+    EnsCall call(e);
+    if (int rc = join_members(e, nullptr, true))
         return rc;
     // tiny members (the one-launch kernels' bound on the map) with rows: one launch per kind
     const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);
-    e->grp.assign(n, -1);
+    ens_scratch(e, sizeof(EnsScoreDesc));
+    std::vector<size_t> at(n, 0);                // the member's place in the pinned result buffers
     size_t total = 0;
     for (size_t k = 0; k < n; ++k) {
         const vsom_ctx *c = e->m[k];
@@ -778,82 +766,54 @@ int vsom_ensemble_bmu_batch(vsom_ensemble *e, uint64_t *const *idx_out, float *c
         if (c->cu || c->B == 0 || (size_t)c->N * L > 4096 || smem > lds_cap)
             continue;
         e->grp[k] = c->transform;
+        e->smem[k] = smem;
+        e->ext[k] = (unsigned)((c->B + ENS_SCORE_ROWS - 1) / ENS_SCORE_ROWS);
+        at[k] = total;
         total += c->B;
     }
-    hipStream_t ls = nullptr;
-    std::vector<hipStream_t> streams;
-    std::vector<size_t> at(n, 0);
     int rc = VSOM_OK;
     if (total) {
         if (total > e->sc_idx.cap)             // (no kernel of an earlier call is running: every call ends in a wait)
             VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(e->sc_idx, total), vsom_member(e->sc_dist, total)}));
-        if ((rc = ens_launch_stream(e, &streams, &ls)))
-            return rc;
-        for (int kind : {VSOM_STANDARD, VSOM_MEDIAN, VSOM_CLR}) {
-            std::vector<EnsScoreDesc> d;
-            unsigned tiles = 0;
-            size_t smem = 0, pos = 0;
-            for (size_t k = 0; k < n; ++k) {
-                if (e->grp[k] < 0) {
-                    continue;
-                } else if (e->grp[k] != kind) {
-                    pos += e->m[k]->B;
-                    continue;
-                }
-                vsom_ctx *c = e->m[k];
-                const bool clr = kind == VSOM_CLR;
-                EnsScoreDesc a;
-                a.d.xa = clr ? c->XP.p : c->Xs.p;
-                a.d.xb = clr ? c->YP.p : c->Xs.p;
-                a.d.ldx = (int)(clr ? c->part_pitch : c->xpitch);
-                a.d.ma = c->map.p;
-                a.d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
-                a.d.ldm = (int)c->pitch;
-                a.d.L = (int)c->part_len;
-                a.lastbmu = c->lastbmu.p;
-                a.sqres = c->sqres.p;
-                a.out_idx = e->sc_idx.p + pos;
-                a.out_dist = e->sc_dist.p + pos;
-                a.B = (int)c->B;
-                a.N = (int)c->N;
-                at[k] = pos;
-                pos += c->B;
-                d.push_back(a);
-                tiles = std::max(tiles, (unsigned)((c->B + ENS_SCORE_ROWS - 1) / ENS_SCORE_ROWS));
-                smem = std::max(smem, ENS_SCORE_ROWS * (sizeof(u64) + sizeof(int)) +
-                                          (size_t)c->N * c->part_len * (clr ? 2 : 1) * sizeof(float));
-            }
-            for (size_t i0 = 0; i0 < d.size() && !rc; i0 += ENS_MAX_Y) {
-                const size_t cnt = std::min(d.size() - i0, (size_t)ENS_MAX_Y);
-                const unsigned char *dev = nullptr;
-                if ((rc = ens_slot_put(e, d.data() + i0, cnt, sizeof(EnsScoreDesc), ls, &dev)))
-                    break;
-                const EnsScoreDesc *args = reinterpret_cast<const EnsScoreDesc *>(dev);
-                const dim3 grid(tiles, (unsigned)cnt);
-                if (kind == VSOM_CLR)
-                    hipLaunchKernelGGL(ensemble_bmu_many_kernel<VSOM_CLR>, grid, dim3(256), smem, ls, args);
-                else if (kind == VSOM_MEDIAN)
-                    hipLaunchKernelGGL(ensemble_bmu_many_kernel<VSOM_MEDIAN>, grid, dim3(256), smem, ls, args);
-                else
-                    hipLaunchKernelGGL(ensemble_bmu_many_kernel<VSOM_STANDARD>, grid, dim3(256), smem, ls, args);
-                hipError_t err = hipGetLastError();
-                if (err != hipSuccess)
-                    rc = vsom_fail(VSOM_ERR_HIP, std::string("ensemble_bmu_many_kernel: ") + hipGetErrorString(err));
-                else
-                    rc = ens_slot_done(e, ls);
-            }
-            if (rc)
-                break;
+        for (size_t k = 0; k < n; ++k) {
+            if (e->grp[k] < 0)
+                continue;
+            vsom_ctx *c = e->m[k];
+            const bool clr = c->transform == VSOM_CLR;
+            EnsScoreDesc a;
+            a.d.xa = clr ? c->XP.p : c->Xs.p;
+            a.d.xb = clr ? c->YP.p : c->Xs.p;
+            a.d.ldx = (int)(clr ? c->part_pitch : c->xpitch);
+            a.d.ma = c->map.p;
+            a.d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
+            a.d.ldm = (int)c->pitch;
+            a.d.L = (int)c->part_len;
+            a.lastbmu = c->lastbmu.p;
+            a.sqres = c->sqres.p;
+            a.out_idx = e->sc_idx.p + at[k];
+            a.out_dist = e->sc_dist.p + at[k];
+            a.B = (int)c->B;
+            a.N = (int)c->N;
+            std::memcpy(e->desc.data() + k * sizeof(a), &a, sizeof(a));
         }
+        // by VSOM_CLR - kind: named in the order they always were, which is the order the compiler emits them in (the
+        // device object stays what it was, byte for byte)
+        static void (*const kernel[])(const EnsScoreDesc *) = {ensemble_bmu_many_kernel<VSOM_CLR>,
+                                                               ensemble_bmu_many_kernel<VSOM_MEDIAN>,
+                                                               ensemble_bmu_many_kernel<VSOM_STANDARD>};
+        rc = ens_launch(call, ENS_PLAIN, 3, sizeof(EnsScoreDesc), ENS_MAX_Y, ens_always_ready,
+                        [](int kind, const void *d, unsigned cnt, size_t smem, unsigned tiles, hipStream_t s) -> int {
+                            hipLaunchKernelGGL(kernel[VSOM_CLR - kind], dim3(tiles, cnt), dim3(256), smem, s,
+                                               static_cast<const EnsScoreDesc *>(d));
+                            VSOM_HIP_CHECK_AS(hipGetLastError(), "ensemble_bmu_many_kernel");
+                            return VSOM_OK;
+                        });
     }
     // the other members through vsom_bmu_batch, while the launches run
     for (size_t k = 0; k < n && !rc; ++k)
         if (e->grp[k] < 0 && e->m[k]->B > 0)
             rc = vsom_bmu_batch(e->m[k], idx_out ? idx_out[k] : nullptr, dist_out ? dist_out[k] : nullptr);
-    // (also on an error: what was launched completes before the call returns)
-    if (ls)
-        VSOM_HIP_CHECK(hipStreamSynchronize(ls));
-    if (rc)
+    if ((rc = call.end(rc)))
         return rc;
     for (size_t k = 0; k < n; ++k) {
         if (e->grp[k] < 0)
@@ -879,14 +839,13 @@ int vsom_ensemble_umatrix(vsom_ensemble *e, double *const *u_out)
         if (const char *why = vsom_umatrix_refusal(e->m[k]))
             return ens_fail(k, why);
     VSOM_HIP_CHECK(hipSetDevice(e->device));
-    for (vsom_ctx *c : e->m)
-        if (int rc = vsom_join_aux(c))
-            return rc;
+    EnsCall call(e);
+    if (int rc = join_members(e, nullptr, false))
+        return rc;
     const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);
-    e->grp.assign(n, -1);
-    std::vector<size_t> at(n, 0);
+    ens_scratch(e, sizeof(VsomUmDesc));
+    std::vector<size_t> at(n, 0);                // the member's place in the pinned result buffer
     size_t total = 0;
-    bool any = false;
     for (size_t k = 0; k < n; ++k) {
         vsom_ctx *c = e->m[k];
         if ((size_t)c->N * c->part_len > 4096 || vsom_umatrix_many_smem(c) > lds_cap)
@@ -894,44 +853,31 @@ int vsom_ensemble_umatrix(vsom_ensemble *e, double *const *u_out)
         if (int rc = vsom_umatrix_ensure(c))
             return rc;
         e->grp[k] = c->transform == VSOM_CLR ? 1 : 0;
-        any = true;
+        e->smem[k] = vsom_umatrix_many_smem(c);
         if (u_out && u_out[k]) {
             at[k] = total;
             total += c->N;
         }
     }
-    hipStream_t ls = nullptr;
-    std::vector<hipStream_t> streams;
-    int rc = VSOM_OK;
-    if (any) {
-        if (total > e->um_out.cap)             // (no kernel of an earlier call is running: every call ends in a wait)
-            VSOM_ALLOC_CHECK(vsom_grow(e->um_out, total, nullptr));
-        if ((rc = ens_launch_stream(e, &streams, &ls)))
-            return rc;
-        for (int kind = 0; kind < 2 && !rc; ++kind) {
-            std::vector<VsomUmDesc> d;
-            size_t smem = 0;
-            for (size_t k = 0; k < n; ++k) {
-                if (e->grp[k] != kind)
-                    continue;
-                vsom_ctx *c = e->m[k];
-                d.push_back({c->map.p, c->sigma.p, c->umatrix.p, (u_out && u_out[k]) ? e->um_out.p + at[k] : nullptr,
-                             (int)c->pitch, (int)c->D, (int)c->part_len, (int)c->part_pitch, (int)c->W, (int)c->H});
-                smem = std::max(smem, vsom_umatrix_many_smem(c));
-            }
-            if (d.empty())
-                continue;
-            const unsigned char *dev = nullptr;
-            if ((rc = ens_slot_put(e, d.data(), d.size(), sizeof(VsomUmDesc), ls, &dev)))
-                break;
-            if ((rc = vsom_umatrix_launch_many(kind, reinterpret_cast<const VsomUmDesc *>(dev), (unsigned)d.size(), smem, ls)))
-                break;
-            for (size_t k = 0; k < n; ++k)
-                if (e->grp[k] == kind)
-                    e->m[k]->um_valid = true;
-            rc = ens_slot_done(e, ls);
-        }
+    if (total > e->um_out.cap)                 // (no kernel of an earlier call is running: every call ends in a wait)
+        VSOM_ALLOC_CHECK(vsom_grow(e->um_out, total, nullptr));
+    for (size_t k = 0; k < n; ++k) {
+        if (e->grp[k] < 0)
+            continue;
+        vsom_ctx *c = e->m[k];
+        const VsomUmDesc d = {c->map.p, c->sigma.p, c->umatrix.p, (u_out && u_out[k]) ? e->um_out.p + at[k] : nullptr,
+                              (int)c->pitch, (int)c->D, (int)c->part_len, (int)c->part_pitch, (int)c->W, (int)c->H};
+        std::memcpy(e->desc.data() + k * sizeof(d), &d, sizeof(d));
     }
+    int rc = ens_launch(call, ENS_PLAIN, 2, sizeof(VsomUmDesc), ENS_NO_CAP, ens_always_ready,
+                        [e](int clr, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t s) {
+                            if (int rc = vsom_umatrix_launch_many(clr, static_cast<const VsomUmDesc *>(d), cnt, smem, s))
+                                return rc;
+                            for (size_t k = 0; k < e->m.size(); ++k)
+                                if (e->grp[k] == clr)
+                                    e->m[k]->um_valid = true;
+                            return (int)VSOM_OK;
+                        });
     // the other members: every launch enqueued first, then the copies (or the wait)
     for (size_t k = 0; k < n && !rc; ++k)
         if (e->grp[k] < 0)
@@ -943,10 +889,7 @@ int vsom_ensemble_umatrix(vsom_ensemble *e, double *const *u_out)
             else
                 rc = vsom_synchronize(e->m[k]);
         }
-    // (also on an error: what was launched completes before the call returns)
-    if (ls)
-        VSOM_HIP_CHECK(hipStreamSynchronize(ls));
-    if (rc)
+    if ((rc = call.end(rc)))
         return rc;
     for (size_t k = 0; k < n; ++k)
         if (e->grp[k] >= 0 && u_out && u_out[k])
