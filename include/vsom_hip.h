@@ -671,6 +671,39 @@ int vsom_train_online_chunk_acc(vsom_ctx *ctx, double eta, double sigma, int dec
  * stores into -- one launch and one stream wait per chunk (the reference's own 10 x 10 x 9 scenario). */
 int vsom_train_online_chunk_fetch(vsom_ctx *ctx, double eta, double sigma, int decay_fn, int first_chunk,
                                   uint64_t *lastbmu_out, float *mse_out);
+/* vsom_train_online_chunk_fetch over the VALID entries of the rows only: blocking, one stream wait,
+ * on the context's stream.  valid_host and one_mask as in vsom_batch_epoch_masked: B x J bytes row-major, nonzero = valid, or
+ * with one_mask one row of J bytes applied to every row.  The bytes travel with the call; nothing is kept between calls.
+ * Standard and Median only (D = J).  For the staged rows x_0 .. x_{B-1} in load order, each with its validity row v_j, B
+ * sequential steps, each on the state the previous one left:
+ *   Search: the distance of vsom_bmu_masked_batch, r_d = v_j[d] ? m_d - x_d : +0, r.dot(r) over all J positions in the Eigen
+ *   packet order of the unmasked distance.  sigma > 1: findBmu's argmin over all nodes, strict < from node 0 (the lowest
+ *   index wins a tie, a NaN d_0 keeps node 0); sigma <= 1: findLocalBmu's walk from lastBMU[j] (Som.cpp:335-454) with every
+ *   distance the masked one.  lastBMU[j] = bmu.
+ *   Window (Som.cpp:899-944): for every window node n, weightMap[n] and the scalars of the step (scM, tw, twf) are exactly
+ *   the unmasked step's -- the node's weight counts the sample whatever its columns.  A valid column d gets the unmasked
+ *   step's float operations on map, SMap and sigmaMap (unfused); at an invalid column none of the three is written: the
+ *   bits there, NaN included, stay as they were.
+ *   Post (:946, :1165-1167): dist = the masked distance of x_j to the updated BMU row, mse = mse + dist / (float)B,
+ *   bmuHits[bmu] += 1.  first_chunk starts or continues the running MSE as in vsom_train_online_chunk_acc.
+ * Guarantees:
+ *   With an all-valid mask (per row or one_mask) map, SMap, sigmaMap, weightMap, bmuHits, lastBMU and the MSE are
+ *   bit-identical to vsom_train_online_chunk_fetch on the same state and chunk.
+ *   What x holds at an invalid position (NaN, inf, anything) has no effect on any output.
+ *   A row without a valid column has every distance +0: its BMU is node 0 (sigma > 1) or lastBMU[j] (sigma <= 1), its
+ *   distance 0, and only weightMap and bmuHits move.
+ *   Known bias, not solved here: weightMap is per node, so InverseProportional's step h / weightMap[n] and the denominator
+ *   of sigmaMap count samples that were invalid at column d (per-column online weights would be a new N x D state array).
+ * Refuses (VSOM_ERR_INVALID, nothing enqueued, state untouched, the context stays usable): a null context or valid_host;
+ * custom and CLR contexts; a decay_fn other than the two online ones; no chunk loaded; a chunk staged ahead over the
+ * current rows; a context that has joined a group or an ensemble.  A pending sigmaMap is materialised first, as for the
+ * unmasked chunk calls.  Masked chunks always take the exact scan, for every vsom_set_bmu_mode: neither the image-bounded
+ * search nor the one-launch tiny-map chunk is used, and vsom_get_online_search_stats does not count their samples.
+ * Timed under VSOM_T_STAGE (validity staging) and VSOM_T_ONLINE (the kernels).  Device scratch in the query arena:
+ * B (J + chunk pitch) validity bytes, or one row of each with one_mask; VSOM_ERR_NOMEM leaves the state untouched. */
+int vsom_train_online_chunk_masked(vsom_ctx *ctx, double eta, double sigma, int decay_fn, int first_chunk,
+                                   const uint8_t *valid_host, int one_mask,
+                                   uint64_t *lastbmu_out /*[B], may be NULL*/, float *mse_out /*may be NULL*/);
 /* diagnostics of the chunk loop's image-bounded search (csrc/vsom_online_i8.hip; synchronises): out[0] = samples searched
  * through the image since the last reset, out[1] = nodes evaluated exactly for them (the candidates that survived the
  * bound), out[2] = refinement workgroups that had a candidate, out[3] = 0.  All zero while the exact scan is in use. */

@@ -55,7 +55,7 @@ SYMBOLS = [
     "vsom_batch_epoch_masked", "vsom_batch_schedule", "vsom_ensemble_batch_schedule",
     "vsom_set_sigma_mode", "vsom_sigma_flush", "vsom_sigma_stats",
     "vsom_batch_accum_begin", "vsom_batch_accum_chunk", "vsom_batch_accum_end", "vsom_batch_accum_abort",
-    "vsom_batch_accum_chunk_masked",
+    "vsom_batch_accum_chunk_masked", "vsom_train_online_chunk_masked",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -271,6 +271,9 @@ def lib():
         L.vsom_batch_accum_chunk.argtypes = [vp]
         L.vsom_batch_accum_end.argtypes = [vp, fp]
         L.vsom_batch_accum_abort.argtypes = [vp]
+    if hasattr(L, "vsom_train_online_chunk_masked"):    # (VSOM_LIB may name an older build: tools/online_masked_bench.py --lib)
+        L.vsom_train_online_chunk_masked.argtypes = [vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int,
+                                                     C.POINTER(C.c_uint64), fp]
     if hasattr(L, "vsom_batch_accum_chunk_masked"):     # (VSOM_LIB may name an older build: tools/accum_masked_bench.py --lib)
         L.vsom_batch_accum_chunk_masked.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int]
     _lib = L
@@ -890,6 +893,22 @@ class Context:
         lb = np.zeros(self.chunk_size, np.uint64)
         check(lib().vsom_train_online_chunk_fetch(self._h, float(eta), float(sigma), int(decay_fn), int(bool(first_chunk)),
                                                   _u(lb), C.byref(mse)))
+        return np.float32(mse.value), lb
+
+    def train_online_chunk_masked(self, eta, sigma, decay_fn, valid, first_chunk=True):
+        """train_online_chunk_fetch over the valid entries of the rows only (vsom_train_online_chunk_masked; Standard /
+        Median): the search on the masked distance, and in every window node only the valid columns of map, SMap and
+        sigmaMap are stepped.  valid: B x J (nonzero = valid), or a 1-D column mask of J entries applied to every row;
+        ValueError for another shape, before any call into the library.  Returns (running MSE, lastBMU)."""
+        B = self.chunk_size
+        vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        one = vb.ndim == 1
+        if vb.shape != ((self.in_len,) if one else (B, self.in_len)):
+            raise ValueError(f"valid has shape {vb.shape}, neither ({self.in_len},) nor ({B}, {self.in_len})")
+        mse = C.c_float()
+        lb = np.zeros(B, np.uint64)
+        check(lib().vsom_train_online_chunk_masked(self._h, float(eta), float(sigma), int(decay_fn), int(bool(first_chunk)),
+                                                   vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one), _u(lb), C.byref(mse)))
         return np.float32(mse.value), lb
 
     def online_search_stats(self, reset=False):

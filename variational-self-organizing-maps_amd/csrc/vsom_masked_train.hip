@@ -25,6 +25,7 @@
 // The walk, its step, the Stepper, the table lookup and the compaction round are vsom_chain.hpp's, shared with
 // vsom_accum.hip and vsom_accum_masked.hip.
 #include "vsom_chain.hpp"
+#include "vsom_masked_dist.hpp"
 #include <algorithm>
 
 __global__ __launch_bounds__(256) void vsom_bxy_kernel(const u64 *__restrict__ lastbmu, int B, u64 W, u64 H,
@@ -74,40 +75,7 @@ __global__ __launch_bounds__(256) void masked_dirty_kernel(const unsigned *__res
         *ndirty = base;
 }
 
-// vsom_group_dist (vsom_device.hpp) with the residual +0 at invalid columns: the same operations in the same order per
-// accumulator class, the same reduction tree.  v: the row's packed validity bytes.
-__device__ __forceinline__ float masked_resid(float x, unsigned char v, float m) { return v ? m - x : 0.f; }
-
-__device__ __forceinline__ float masked_group_dist(const float *x, const unsigned char *v, const float *m, int L, int k)
-{
-    const int L8 = L & ~7;
-    float acc = 0.f;
-#pragma unroll 14
-    for (int d = k; d < L8; d += 8) {
-        const float r = masked_resid(x[d], v[d], m[d]);
-        const float p = r * r;
-        acc = acc + p;
-    }
-    float q = acc + __shfl_xor(acc, 4);
-    const int rem = L - L8;
-    if (rem >= 4) {
-        const int d = L8 + (k & 3);
-        const float r = masked_resid(x[d], v[d], m[d]);
-        const float p = r * r;
-        q = q + p;
-    }
-    const float t = q + __shfl_xor(q, 2);
-    float res = t + __shfl_xor(t, 1);
-    for (int tt = (rem >= 4 ? 4 : 0); tt < rem; ++tt) {
-        const int d = L8 + tt;
-        const float r = masked_resid(x[d], v[d], m[d]);
-        const float p = r * r;
-        res = res + p;
-    }
-    return res;
-}
-
-// bmu_local_kernel (vsom_bmu.hip) on the masked distance: one wavefront per row
+// bmu_local_kernel (vsom_bmu.hip) on the masked distance (masked_group_dist, vsom_masked_dist.hpp): one wavefront per row
 __global__ __launch_bounds__(256) void masked_local_kernel(DistArgs a, const unsigned char *__restrict__ vp, int vld, int one,
                                                            int B, u64 width, u64 height, u64 *__restrict__ lastbmu,
                                                            float *__restrict__ sqres)

@@ -5,6 +5,8 @@
 //                         onl_refine_kernel and their per-chunk passes, enqueue_chunk_i8, vsom_get_online_search_stats
 //   vsom_online_tiny.hip  tiny maps: the whole chunk loop in one launch of one workgroup (online_tiny_chunk_kernel), and
 //                         one workgroup per map for ensembles (vsom_onl_tiny_*)
+//   vsom_online_masked.hip the chunk loop over the valid entries of the rows only (Standard / Median): the masked scan,
+//                         window and one-launch step of vsom_train_online_chunk_masked, enqueue_chunk_masked
 //   vsom_single.hip       single-vector queries: vsom_find_bmu, vsom_find_restricted_bmu, vsom_distances_single,
 //                         vsom_dist_single, vsom_find_local_bmu; stage_single
 // Here: the per-sample kernels, the neighbourhood tables (lutd), and the entry points vsom_train_online_chunk* (which pick
@@ -30,19 +32,6 @@
 #include <cmath>
 #include <algorithm>
 #include <cstring>
-
-// BMU of the sample from its scan results; a NaN distance at node 0 pins it to 0 (Som.cpp:293-299)
-// (whole wavefronts call this: the slots are read by 16 lanes and folded with shuffles)
-__device__ __forceinline__ u64 online_resolve(const u64 *state, int par)
-{
-    u64 key = state[(par * ONL_SLOTS + ((int)threadIdx.x & (ONL_SLOTS - 1))) * 16];
-#pragma unroll
-    for (int off = ONL_SLOTS / 2; off >= 1; off >>= 1) {
-        const u64 o = __shfl_xor(key, off);
-        key = o < key ? o : key;
-    }
-    return state[ONL_FLAG + par] ? 0ull : (key & 0xFFFFFFFFull);
-}
 
 template <bool CLR>
 __device__ __forceinline__ void online_post(const OnlineArgs &a, const float *xa, const float *xb, u64 bmu, int lane, u64 *hits,
@@ -491,12 +480,24 @@ extern "C" {
 
 // lb_host != NULL: the caller wants lastBMU back in this call -- *lb_in_pinned = the one-launch kernel has stored it into
 // c->out_pinned.p itself (else the caller fetches it with vsom_get_last_bmu)
+// masked: vsom_train_online_chunk_masked -- the same preamble, then always the exact-scan loop of vsom_online_masked.hip
+// with the validity bytes valid_host (B x J, or J with one_mask) staged into the query arena
 static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk, float *mse_out,
-                                   bool want_lb, bool *lb_in_pinned)
+                                   bool want_lb, bool *lb_in_pinned, bool masked = false, const uint8_t *valid_host = nullptr,
+                                   int one_mask = 0)
 {
     if (lb_in_pinned)
         *lb_in_pinned = false;
     CHECK_CTX_NOJOIN(c);
+    if (masked) {
+        VSOM_CUSTOM_REFUSE(c, "vsom_train_online_chunk_masked");
+        if (c->transform == VSOM_CLR)
+            return vsom_fail(VSOM_ERR_INVALID, "vsom_train_online_chunk_masked: CLR contexts are not supported (residual and step run over column pairs)");
+        if (c->in_group || c->sigma_shared)
+            return vsom_fail(VSOM_ERR_INVALID, "vsom_train_online_chunk_masked: the context has joined a group or an ensemble");
+        if (!valid_host)
+            return vsom_fail(VSOM_ERR_INVALID, "valid_host is null");
+    }
     if (c->cu) {
         int rc = vsom_custom_train_online_chunk(c, eta, sigma, decay_fn, first_chunk);
         if (rc || !mse_out)
@@ -517,13 +518,26 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
     c->rows_free_valid = false;   // (the chunk below reads the staged rows, a later stage-ahead must not take them)
     const double *lutd = nullptr;
     int lutw = (int)c->W, lslot = 0, rc;
-    bool tiny = online_tiny_applies(c, sigma);
+    bool tiny = !masked && online_tiny_applies(c, sigma);
     if (tiny)                                 // one launch reads the table once, into LDS: straight from the pinned slot
         rc = ensure_lutd_host(c, sigma, &lutd, &lslot);
     else
         rc = ensure_lutd(c, sigma, &lutd, &lutw);
     if (rc)
         return rc;
+    const bool one = one_mask != 0;
+    const unsigned char *packed = nullptr;
+    if (masked && c->B > 0) {     // the validity bytes as given and packed (0xFF / 0x00, xpitch a row), before any kernel
+        const size_t vrows = one ? 1 : c->B;
+        vsom_layout lay;
+        const auto raw = lay.add<unsigned char>(vrows * c->J), pk = lay.add<unsigned char>(vrows * c->xpitch);
+        VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+        TimerScope ts(c, VSOM_T_STAGE);
+        VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(raw), valid_host, vrows * c->J, hipMemcpyHostToDevice, c->stream));
+        vsom_masked_pack_enqueue(c, lay.at(raw), vrows, lay.at(pk));
+        VSOM_HIP_CHECK(hipGetLastError());
+        packed = lay.at(pk);
+    }
     {
         TimerScope ts(c, VSOM_T_ONLINE);
         if (!tiny)                            // (the one-launch chunk starts the running MSE itself and uses no key slots)
@@ -539,6 +553,9 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
                 return rc;
             if (lbh && lb_in_pinned)
                 *lb_in_pinned = true;
+        } else if (masked) {
+            if ((rc = enqueue_chunk_masked(c, eta, sigma, decay_fn, lutd, lutw, packed, one)))
+                return rc;
         } else if (onl_i8_applies(c, sigma)) {
             if ((rc = enqueue_chunk_i8(c, eta, sigma, decay_fn, lutd, lutw)))
                 return rc;
@@ -580,13 +597,10 @@ int vsom_train_online_chunk_acc(vsom_ctx *c, double eta, double sigma, int decay
     return train_online_chunk_impl(c, eta, sigma, decay_fn, first_chunk, mse_out, false, nullptr);
 }
 
-int vsom_train_online_chunk_fetch(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk,
-                                  uint64_t *lastbmu_out, float *mse_out)
+// the chunk is enqueued: one stream wait, lastBMU (in_pinned: the one-launch kernel stored it into c->out_pinned) and the MSE
+static int online_chunk_fetch(vsom_ctx *c, bool in_pinned, uint64_t *lastbmu_out, float *mse_out)
 {
-    bool in_pinned = false;
-    int rc = train_online_chunk_impl(c, eta, sigma, decay_fn, first_chunk, nullptr, lastbmu_out != nullptr, &in_pinned);
-    if (rc)
-        return rc;
+    int rc;
     if (lastbmu_out && !in_pinned) {
         if ((rc = vsom_get_last_bmu(c, lastbmu_out)))      // (synchronises)
             return rc;
@@ -598,6 +612,24 @@ int vsom_train_online_chunk_fetch(vsom_ctx *c, double eta, double sigma, int dec
     if (mse_out)
         *mse_out = *static_cast<volatile float *>(c->mse.p);  // pinned host memory; written in stream order before the wait above
     return VSOM_OK;
+}
+
+int vsom_train_online_chunk_fetch(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk,
+                                  uint64_t *lastbmu_out, float *mse_out)
+{
+    bool in_pinned = false;
+    if (int rc = train_online_chunk_impl(c, eta, sigma, decay_fn, first_chunk, nullptr, lastbmu_out != nullptr, &in_pinned))
+        return rc;
+    return online_chunk_fetch(c, in_pinned, lastbmu_out, mse_out);
+}
+
+int vsom_train_online_chunk_masked(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk,
+                                   const uint8_t *valid_host, int one_mask, uint64_t *lastbmu_out, float *mse_out)
+{
+    if (int rc = train_online_chunk_impl(c, eta, sigma, decay_fn, first_chunk, nullptr, lastbmu_out != nullptr, nullptr, true,
+                                         valid_host, one_mask))
+        return rc;
+    return online_chunk_fetch(c, false, lastbmu_out, mse_out);
 }
 
 int vsom_train_online_chunk(vsom_ctx *c, double eta, double sigma, int decay_fn, float *mse_out)

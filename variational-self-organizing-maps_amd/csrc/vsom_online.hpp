@@ -1,5 +1,5 @@
 // vsom_online.hpp -- what the files of the online family share (private to them): vsom_online.hip (the index of the
-// family), vsom_online_i8.hip, vsom_online_tiny.hip and vsom_single.hip.
+// family), vsom_online_i8.hip, vsom_online_tiny.hip, vsom_online_masked.hip and vsom_single.hip.
 //
 // The layout of onl_state and the kernel arguments built on it, the window update of one node with the helpers it is made
 // of, and the host functions that cross those files.  What only one of the files uses stays in that file.  Every
@@ -20,6 +20,19 @@ constexpr int ONL_FLAG = 2 * ONL_SLOTS * 16;
 constexpr size_t ONL_STATE_BYTES = (ONL_FLAG + 16) * sizeof(u64);
 static_assert(ONL_STATE_BYTES <= VSOM_ONL_STATE_BYTES, "vsom_create allocates VSOM_ONL_STATE_BYTES");
 __device__ __forceinline__ u64 *online_slot(u64 *state, int par, int s) { return state + (par * ONL_SLOTS + s) * 16; }
+// BMU of the sample from its scan results; a NaN distance at node 0 pins it to 0 (Som.cpp:293-299)
+// (whole wavefronts call this: the slots are read by 16 lanes and folded with shuffles)
+__device__ __forceinline__ u64 online_resolve(const u64 *state, int par)
+{
+    u64 key = state[(par * ONL_SLOTS + ((int)threadIdx.x & (ONL_SLOTS - 1))) * 16];
+#pragma unroll
+    for (int off = ONL_SLOTS / 2; off >= 1; off >>= 1) {
+        const u64 o = __shfl_xor(key, off);
+        key = o < key ? o : key;
+    }
+    return state[ONL_FLAG + par] ? 0ull : (key & 0xFFFFFFFFull);
+}
+
 struct OnlineArgs {
     DistArgs d;          // xa/xb point at the sample's row(s)
     u64 *state;
@@ -178,5 +191,8 @@ int enqueue_chunk_i8(vsom_ctx *c, double eta, double sigma, int decay_fn, const 
 bool online_tiny_applies(const vsom_ctx *c, double sigma);
 int enqueue_chunk_tiny(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw, int first_chunk,
                        u64 *lastbmu_host);
+// vsom_online_masked.hip: the exact-scan chunk loop over valid entries (Standard / Median), vp: the packed validity rows
+int enqueue_chunk_masked(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw,
+                         const unsigned char *vp, bool one);
 // vsom_single.hip
 int stage_single(vsom_ctx *c, const float *v_host, bool copy = true);

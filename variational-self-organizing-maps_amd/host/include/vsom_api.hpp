@@ -470,6 +470,13 @@ public:
     // SqliteDataLoader's case: NULLs and maxLoadCount rows per load).  Driver, metrics and resetBmu are trainBatchSomWhole's.
     void trainBatchSomWholeMasked(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
                                   bool updateUMatrixAfterEpoch = false, bool resetBmu = true);
+    // [MI355X build] extension: trainBasicSom over the VALID entries of the rows only (the data set's validity flags; one
+    // vsom_train_online_chunk_masked call per chunk, include/vsom_hip.h): a missing field neither attracts the search nor
+    // steps its column of the window's nodes.  Schedule, sigma clamp at 1.0, running MSE and metrics are trainBasicSom's;
+    // the chunk loop is the plain one (upload, then the blocking call).  With every column valid the result is
+    // trainBasicSom's bit for bit.  Standard / Median on one device only.
+    void trainBasicSomMasked(DataSet &data, size_t numberOfEpochs, double eta0, double etaDecay, double sigma0,
+                             double sigmaDecay, WeigthDecayFunction weightDecayFunction, bool updateUMatrixAfterEpoch = false);
     TrainingReturnValue trainSingle(const Eigen::VectorXf &v, const Eigen::VectorXf &valid,
                                     const Eigen::VectorXf &weights, const double eta, const double sigma,
                                     size_t &lastBMU, const WeigthDecayFunction weightDecayFunction);

@@ -1483,6 +1483,56 @@ void Som::trainBasicSom(DataSet &data, size_t numberOfEpochs, double eta0, doubl
     std::cout << "\rTraining SOM:100%\n";
 }
 
+// Som.cpp:1135-1187 with every chunk through vsom_train_online_chunk_masked and the data set's validity flags.  The call is
+// blocking (the flags travel with it), so the chunk loop is the reference's own: plain upload, no hand-over pipeline.
+void Som::trainBasicSomMasked(DataSet &data, size_t numberOfEpochs, double eta0, double etaDecay, double sigma0,
+                              double sigmaDecay, WeigthDecayFunction weightDecayFunction, bool updateUMatrixAfterEpoch)
+{
+    requireDevicePath("trainBasicSomMasked");
+    if (grp)
+        throw std::runtime_error("trainBasicSomMasked: a multi-GPU Som has no masked online chunk "
+                                 "(vsom_train_online_chunk_masked runs on one context)");
+    {
+        const std::lock_guard<std::mutex> lock(metricsMutex);
+        metrics = Som::Metrics(numberOfEpochs);   // :1139
+    }
+    std::vector<uint64_t> lb;
+    for (size_t i = 0; i < numberOfEpochs; ++i) {
+        auto eta = eta0 * std::exp(-etaDecay * static_cast<double>(i));         // :1145
+        auto sigma = sigma0 * std::exp(-sigmaDecay * static_cast<double>(i));   // :1146
+        if (sigma < 1.0)
+            sigma = 1.0;   // :1148-1149
+        std::cout << "Epoch: " << i + 1 << "/" << numberOfEpochs << "\teta: " << eta << "\tsigma: " << sigma << "\n";
+        float meanSquareError{0.0};   // ONE running float over all chunks of the epoch (:1153,1167)
+        size_t countDataChunks{0};
+        while (!data.hasReadWholeDataStream()) {
+            data.loadNextDataFromStream();
+            const size_t B = data.size();
+            std::vector<uint8_t> valid = validity_bytes(data, inLen);
+            if (valid.empty())
+                valid.assign(1, 0);       // (an empty chunk reads no flag; the call wants a pointer)
+            lb.resize(B);
+            check(vsom_upload_chunk(ctx, data.contiguous(), B), "vsom_upload_chunk");   // lastBMU zeroed by the load
+            check(vsom_train_online_chunk_masked(ctx, eta, sigma, decay_code(weightDecayFunction), countDataChunks == 0 ? 1 : 0,
+                                                 valid.data(), 0, B ? lb.data() : nullptr, &meanSquareError),
+                  "vsom_train_online_chunk_masked");
+            for (size_t s = 0; s < B; ++s)
+                data.getLastBMU(s) = (size_t)lb[s];
+            ++countDataChunks;
+        }
+        meanSquareError /= static_cast<float>(countDataChunks);   // :1175
+        {
+            const std::lock_guard<std::mutex> lock(metricsMutex);
+            metrics.MeanSquaredError[i] = meanSquareError;
+        }
+        data.resetStreamLoadPosition();
+        hostStale = true;
+        if (updateUMatrixAfterEpoch)
+            updateUMatrix(data.getWeights());   // :1183-1184
+    }
+    std::cout << "\rTraining SOM:100%\n";
+}
+
 // Som.cpp:1113-1132: dispatch; exceptions are printed, not propagated
 void Som::train(DataSet &data, size_t numberOfEpochs, double eta0, double etaDecay, double sigma0, double sigmaDecay,
                 WeigthDecayFunction weightDecayFunction, bool updateUMatrixAfterEpoch)

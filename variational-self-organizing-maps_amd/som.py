@@ -738,6 +738,21 @@ class Som:
 
     def trainBasicSom(self, data, numberOfEpochs, eta0, etaDecay, sigma0, sigmaDecay,
                       weightDecayFunction, updateUMatrixAfterEpoch=False):
+        self._trainBasicSom(False, data, numberOfEpochs, eta0, etaDecay, sigma0, sigmaDecay, weightDecayFunction,
+                            updateUMatrixAfterEpoch)
+
+    def trainBasicSomMasked(self, data, numberOfEpochs, eta0, etaDecay, sigma0, sigmaDecay,
+                            weightDecayFunction, updateUMatrixAfterEpoch=False):
+        """extension: trainBasicSom over the valid entries of the rows only -- every chunk goes through
+        capi.Context.train_online_chunk_masked, so that a missing field neither attracts the search nor steps its column
+        of the window's nodes.  The validity of a chunk comes from the data set when it has one (an attribute `validity`,
+        loaded rows x J, nonzero = valid), as in trainBatchSomEpochMasked; without one every column is valid.  Driver,
+        schedule, sigma clamp at 1.0, running MSE and metrics are trainBasicSom's.  Standard and Median."""
+        self._trainBasicSom(True, data, numberOfEpochs, eta0, etaDecay, sigma0, sigmaDecay, weightDecayFunction,
+                            updateUMatrixAfterEpoch)
+
+    def _trainBasicSom(self, masked, data, numberOfEpochs, eta0, etaDecay, sigma0, sigmaDecay, weightDecayFunction,
+                       updateUMatrixAfterEpoch):
         self.metrics = Metrics(numberOfEpochs)
         for i in range(numberOfEpochs):
             eta = eta0 * math.exp(-etaDecay * float(i))           # :1145
@@ -750,8 +765,13 @@ class Som:
                 data.loadNextDataFromStream()
                 self.ctx.upload_chunk(data.data)                  # lastBMU zeroed by the load
                 # ONE running accumulator over the epoch's chunks (Som.cpp:1153,1167)
-                mse = self.ctx.train_online_chunk(eta, sigma, int(weightDecayFunction), first_chunk=(count == 0))
-                data.lastBMU[...] = self.ctx.get_last_bmu()
+                if masked:
+                    mse, lb = self.ctx.train_online_chunk_masked(eta, sigma, int(weightDecayFunction),
+                                                                 self._chunkValidity(data), first_chunk=(count == 0))
+                    data.lastBMU[...] = lb
+                else:
+                    mse = self.ctx.train_online_chunk(eta, sigma, int(weightDecayFunction), first_chunk=(count == 0))
+                    data.lastBMU[...] = self.ctx.get_last_bmu()
                 count += 1
             mse = np.float32(mse / np.float32(count))             # :1175
             self.metrics.MeanSquaredError[i] = mse
