@@ -117,7 +117,7 @@ typedef enum vsom_buffer {
 typedef enum vsom_timer {
     VSOM_T_STAGE = 0,      /* chunk re-layout kernels                           */
     VSOM_T_BMU = 1,        /* full / local BMU search kernels                   */
-    VSOM_T_FINISH = 2,     /* bmuHits + MSE; the scoring kernels of vsom_similarity_batch / vsom_evaluate_batch, vsom_generate_batch's decode */
+    VSOM_T_FINISH = 2,     /* bmuHits + MSE; the scoring kernels of vsom_similarity_batch / vsom_evaluate_batch and their masked forms, vsom_generate_batch's decode */
     VSOM_T_CW = 3,         /* neighbourhood weight chain (w, w/W) kernel        */
     VSOM_T_UPDATE = 4,     /* mean / sigma^2 chain kernel                       */
     VSOM_T_ONLINE = 5,     /* online (trainSingle) kernels                      */
@@ -454,6 +454,72 @@ typedef struct vsom_evaluate_out {
 } vsom_evaluate_out;
 int vsom_evaluate_batch(vsom_ctx *ctx, size_t r0, size_t r1, const float *binary_host, const float *continuous_host,
                         const uint8_t *valid_host, vsom_evaluate_out *out);
+/* vsom_similarity_batch and vsom_evaluate_batch for records with missing fields: the search runs over the VALID columns of
+ * every row, as vsom_bmu_masked_batch, and the row is scored against that unit in its valid columns only -- one call, one
+ * stream wait, nothing of size N x D moves.  (The valid_host of the two unmasked calls only gates which columns count AFTER
+ * a search that took a missing field for a measured zero.)  Standard and Median (D = J, C = J).
+ * Mask: as vsom_bmu_masked_batch -- valid_host is (r1-r0) x J bytes, row-major (entry (r - r0) * J + d belongs to chunk row r),
+ * when one_mask == 0, and J bytes applied to every row when one_mask != 0; a non-zero byte means valid; required.
+ * Search: for rows [r0, r1) ONLY, the search of vsom_bmu_masked_batch(min_hits, mask) word for word: r_d = valid ?
+ * (m_d - x_d) : +0.0f as a select on the bits, the Eigen packet order of the exact tile, findRestrictedBmu's argmin (node 0
+ * seeds, strict `<` over the nodes with bmuHits >= min_hits, NaN never wins, a NaN d_0 keeps node 0 and stores 0x7FC00000).
+ * bmu, dist and nvalid are bit-identical to that call's outputs for the same arguments; a row without a valid column gets
+ * node 0, distance +0, nvalid 0.
+ * vsom_similarity_masked_batch scores as vsom_similarity_batch does (the same fp32 operations, both sigma rules) with one
+ * addition: at an invalid column delta is the quiet NaN, by select, before anything is reduced.  So dmax / dmax_col and
+ * first range over the valid columns only, amax / amax_col and outside are as there (they always ranged over the valid
+ * columns), and the dense delta stores 0 at an invalid column.  A row without a valid column reports dmax = -inf,
+ * dmax_col = UINT32_MAX, first = NaN (0x7FC00000), amax = 0, amax_col = UINT32_MAX, outside = 0 and a zero delta row.  first
+ * and dmax feed the same running maximum as those of vsom_similarity_batch.
+ * vsom_evaluate_masked_batch scores as vsom_evaluate_batch does, except
+ *   t = valid ? (be * binary_host[d]) * continuous_host[d] : +0.0f
+ * -- a select, not the multiplication by a zero val: an inf product at an invalid column cannot become NaN.  nrepl counts
+ * valid columns only; error is the running mean of (double)dist + sqrt((double)bsum) in row order from r0, on the host, with
+ * the masked dist; an empty range writes *error = 0.  The accuracy statement of vsom_evaluate_batch holds for bsum.
+ * Outputs: the fields of vsom_similarity_out / vsom_evaluate_out, and nvalid, the number of valid columns of the row (host
+ * pointers, each may be NULL; entry r - r0 belongs to row r).
+ *  - With an all-valid mask every output of vsom_similarity_masked_batch is bit-identical to vsom_similarity_batch(min_hits,
+ *    ..., valid_host = NULL), with nvalid = J; every output of vsom_evaluate_masked_batch(min_hits = 0) to
+ *    vsom_evaluate_batch(valid_host = NULL) in every vsom_set_bmu_mode, bsum included (the same kernel arithmetic).
+ *  - What a row of the chunk holds at an invalid position (NaN, +-inf, 1e30, values outside [0,1]) reaches no output, nor
+ *    does what the unit's map / sigmaMap rows hold there.
+ *  - Read-only: lastBMU and sqres (unlike the unmasked scorers: only [r0, r1) is searched, into scratch), map, sigmaMap, S,
+ *    weightMap, bmuHits and the chunk are untouched.
+ *  - A pending sigmaMap is materialised by both calls.
+ * Refuses (VSOM_ERR_INVALID, nothing enqueued, the context stays usable): a null context, out or valid_host, a null
+ * binary_host or continuous_host (evaluate), custom and CLR contexts (the CLR residual runs over column pairs), no chunk, a
+ * chunk staged ahead, r0 > r1 or r1 > B, an unknown sigma_rule.  An empty range returns VSOM_OK and enqueues nothing.
+ * Device scratch: the rows are searched and scored in slices that follow vsom_bmu_masked_batch's rule (64 MiB; with the dense
+ * delta at most max(1, 64 MiB / (4 J)) rows, 4 J bytes each); per row of a slice J + roundup(J, 32) validity bytes, at most
+ * 64 keys of 8 bytes and 17 bytes of search results; per row of the call 40 (similarity) or 24 (evaluate) bytes of results,
+ * which return through pinned memory of the context; evaluate: 8 J bytes of column arrays.  A slice's validity bytes go up
+ * once and are packed once; the packed bytes serve the search and the scoring.  The search is timed under VSOM_T_BMU, the
+ * scoring under VSOM_T_FINISH. */
+typedef struct vsom_similarity_masked_out {
+    uint64_t *bmu;
+    float *dist;
+    float *dmax;
+    uint32_t *dmax_col;
+    float *first;
+    float *amax;
+    uint32_t *amax_col;
+    uint32_t *outside;
+    float *delta;
+    uint32_t *nvalid;
+} vsom_similarity_masked_out;
+typedef struct vsom_evaluate_masked_out {
+    uint64_t *bmu;
+    float *dist;
+    float *bsum;
+    uint32_t *nrepl;
+    double *error;
+    uint32_t *nvalid;
+} vsom_evaluate_masked_out;
+int vsom_similarity_masked_batch(vsom_ctx *ctx, uint64_t min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
+                                 const uint8_t *valid_host, int one_mask, vsom_similarity_masked_out *out);
+int vsom_evaluate_masked_batch(vsom_ctx *ctx, uint64_t min_hits, size_t r0, size_t r1, const float *binary_host,
+                               const float *continuous_host, const uint8_t *valid_host, int one_mask,
+                               vsom_evaluate_masked_out *out);
 /* Som::autoEncoder's records (Som.cpp:568-623) for chunk rows [r0, r1): a model vector per row drawn from a restricted best
  * matching distribution (Som::findRestrictedBmd, vsom_bmd_batch), and every column of the record sampled from a
  * logit-approximated normal around that unit's map / sigmaMap values -- one call, one stream wait, nothing of size N x D moves.

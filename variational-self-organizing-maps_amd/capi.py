@@ -56,6 +56,7 @@ SYMBOLS = [
     "vsom_set_sigma_mode", "vsom_sigma_flush", "vsom_sigma_stats",
     "vsom_batch_accum_begin", "vsom_batch_accum_chunk", "vsom_batch_accum_end", "vsom_batch_accum_abort",
     "vsom_batch_accum_chunk_masked", "vsom_train_online_chunk_masked",
+    "vsom_similarity_masked_batch", "vsom_evaluate_masked_batch",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -77,6 +78,16 @@ class EvaluateOut(C.Structure):
     """vsom_evaluate_out: host pointers, each may be NULL"""
     _fields_ = [("bmu", C.POINTER(C.c_uint64)), ("dist", C.POINTER(C.c_float)), ("bsum", C.POINTER(C.c_float)),
                 ("nrepl", C.POINTER(C.c_uint32)), ("error", C.POINTER(C.c_double))]
+
+
+class SimilarityMaskedOut(C.Structure):
+    """vsom_similarity_masked_out: vsom_similarity_out's fields and nvalid; host pointers, each may be NULL"""
+    _fields_ = SimilarityOut._fields_ + [("nvalid", C.POINTER(C.c_uint32))]
+
+
+class EvaluateMaskedOut(C.Structure):
+    """vsom_evaluate_masked_out: vsom_evaluate_out's fields and nvalid; host pointers, each may be NULL"""
+    _fields_ = EvaluateOut._fields_ + [("nvalid", C.POINTER(C.c_uint32))]
 
 
 class GenerateOut(C.Structure):
@@ -276,6 +287,11 @@ def lib():
                                                      C.POINTER(C.c_uint64), fp]
     if hasattr(L, "vsom_batch_accum_chunk_masked"):     # (VSOM_LIB may name an older build: tools/accum_masked_bench.py --lib)
         L.vsom_batch_accum_chunk_masked.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int]
+    if hasattr(L, "vsom_similarity_masked_batch"):      # (VSOM_LIB may name an older build: tools/masked_score_bench.py --lib)
+        L.vsom_similarity_masked_batch.argtypes = [vp, C.c_uint64, C.c_int, C.c_int, C.c_size_t, C.c_size_t,
+                                                   C.POINTER(C.c_uint8), C.c_int, C.POINTER(SimilarityMaskedOut)]
+        L.vsom_evaluate_masked_batch.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t, fp, fp, C.POINTER(C.c_uint8), C.c_int,
+                                                 C.POINTER(EvaluateMaskedOut)]
     _lib = L
     return L
 
@@ -746,6 +762,75 @@ class Context:
                 setattr(out, name, res[name].ctypes.data_as(ctype))
         check(lib().vsom_bmu_masked_batch(self._h, int(min_hits), r0, r1, vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one),
                                           C.byref(out)))
+        return res
+
+    def _mask_bytes(self, valid, n):
+        """valid as the masked calls take it: (bytes, one_mask) from rows x J (nonzero = valid) or a 1-D column mask"""
+        vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        one = vb.ndim == 1
+        if vb.shape != ((self.in_len,) if one else (n, self.in_len)):
+            raise ValueError(f"valid has shape {vb.shape}, neither ({self.in_len},) nor ({n}, {self.in_len})")
+        return vb, one
+
+    def similarity_masked(self, valid, min_hits, num_sigmas, sigma_rule=SIGMA_FLOOR, r0=0, r1=None, delta=False):
+        """similarity for records with missing fields (vsom_similarity_masked_batch; Standard / Median): chunk rows
+        [r0, r1) searched over their valid columns only, as bmu_masked, and scored against that unit in those columns.
+        valid: rows x J (nonzero = valid), or a 1-D column mask of J entries applied to every row.  similarity's dict
+        (dmax / first over the valid columns only, delta 0 at invalid ones) and nvalid (uint32).  Read-only: lastBMU and
+        sqres stay."""
+        B = self.chunk_size
+        r0 = int(r0)
+        r1 = B if r1 is None else int(r1)
+        if int(sigma_rule) not in (SIGMA_AS_WRITTEN, SIGMA_FLOOR):
+            raise ValueError(f"sigma_rule = {sigma_rule} is neither SIGMA_AS_WRITTEN nor SIGMA_FLOOR")
+        if int(min_hits) < 0:
+            raise ValueError("min_hits must be >= 0")
+        if not -2 ** 31 <= int(num_sigmas) < 2 ** 31:
+            raise ValueError("num_sigmas must fit an int")
+        if r0 < 0 or r0 > r1 or r1 > B:
+            raise ValueError(f"row range [{r0}, {r1}) is not within the chunk's {B} rows")
+        n = r1 - r0
+        vb, one = self._mask_bytes(valid, n)
+        res = {"bmu": np.empty(n, np.uint64), "dist": np.empty(n, np.float32), "dmax": np.empty(n, np.float32),
+               "dmax_col": np.empty(n, np.uint32), "first": np.empty(n, np.float32), "amax": np.empty(n, np.float32),
+               "amax_col": np.empty(n, np.uint32), "outside": np.empty(n, np.uint32),
+               "delta": np.empty((n, self.in_len), np.float32) if delta else None, "nvalid": np.empty(n, np.uint32)}
+        out = SimilarityMaskedOut()
+        for name, ctype in SimilarityMaskedOut._fields_:
+            if res[name] is not None:
+                setattr(out, name, res[name].ctypes.data_as(ctype))
+        check(lib().vsom_similarity_masked_batch(self._h, int(min_hits), int(num_sigmas), int(sigma_rule), r0, r1,
+                                                 vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one), C.byref(out)))
+        return res
+
+    def evaluate_masked(self, valid, binary, continuous, min_hits=0, r0=0, r1=None):
+        """evaluate for records with missing fields (vsom_evaluate_masked_batch; Standard / Median): chunk rows [r0, r1)
+        searched over their valid columns only, as bmu_masked, and the binary error summed over those columns (an invalid
+        column's term is +0 by select).  valid as in similarity_masked.  evaluate's dict, error the running mean of the
+        masked dist + sqrt(bsum), and nvalid (uint32).  Read-only: lastBMU and sqres stay."""
+        B = self.chunk_size
+        r0 = int(r0)
+        r1 = B if r1 is None else int(r1)
+        if int(min_hits) < 0:
+            raise ValueError("min_hits must be >= 0")
+        if r0 < 0 or r0 > r1 or r1 > B:
+            raise ValueError(f"row range [{r0}, {r1}) is not within the chunk's {B} rows")
+        n = r1 - r0
+        cols = []
+        for name, a in (("binary", binary), ("continuous", continuous)):
+            a = np.ascontiguousarray(a, dtype=np.float32)
+            if a.shape != (self.in_len,):
+                raise ValueError(f"{name} has shape {a.shape}, not ({self.in_len},)")
+            cols.append(a)
+        vb, one = self._mask_bytes(valid, n)
+        res = {"bmu": np.empty(n, np.uint64), "dist": np.empty(n, np.float32), "bsum": np.empty(n, np.float32),
+               "nrepl": np.empty(n, np.uint32), "error": np.zeros(1, np.float64), "nvalid": np.empty(n, np.uint32)}
+        out = EvaluateMaskedOut()
+        for name, ctype in EvaluateMaskedOut._fields_:
+            setattr(out, name, res[name].ctypes.data_as(ctype))
+        check(lib().vsom_evaluate_masked_batch(self._h, int(min_hits), r0, r1, _f(cols[0]), _f(cols[1]),
+                                               vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one), C.byref(out)))
+        res["error"] = float(res["error"][0])
         return res
 
     def distances_row(self, row):

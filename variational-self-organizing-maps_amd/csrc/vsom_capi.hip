@@ -941,6 +941,47 @@ int vsom_bmu_masked_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t r1, 
     return launch_masked(c, min_hits, r0, r1, valid_host, one_mask, out);
 }
 
+// the gate the two masked scorers share behind CHECK_CTX (`what`: the entry point's name)
+static int vsom_masked_score_gate(vsom_ctx *c, const char *what, size_t r0, size_t r1, const void *valid_host, const void *out)
+{
+    VSOM_CUSTOM_REFUSE(c, what);
+    if (c->transform == VSOM_CLR)
+        return vsom_fail(VSOM_ERR_INVALID, std::string(what) + ": CLR contexts are not supported (the residual runs over column pairs)");
+    CHECK_ROWS(c);
+    if (!out)
+        return vsom_fail(VSOM_ERR_INVALID, "out is null");
+    if (!valid_host)
+        return vsom_fail(VSOM_ERR_INVALID, "valid_host is null");
+    if (c->B == 0)
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    if (r0 > r1 || r1 > c->B)
+        return vsom_fail(VSOM_ERR_INVALID, "row range out of bounds");
+    return VSOM_OK;
+}
+
+int vsom_similarity_masked_batch(vsom_ctx *c, uint64_t min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
+                                 const uint8_t *valid_host, int one_mask, vsom_similarity_masked_out *out)
+{
+    CHECK_CTX(c);                // (reads sigmaMap: a pending one is materialised)
+    if (int rc = vsom_masked_score_gate(c, "vsom_similarity_masked_batch", r0, r1, valid_host, out))
+        return rc;
+    if (sigma_rule != VSOM_SIGMA_AS_WRITTEN && sigma_rule != VSOM_SIGMA_FLOOR)
+        return vsom_fail(VSOM_ERR_INVALID, "unknown sigma_rule");
+    return launch_similarity_masked(c, min_hits, num_sigmas, sigma_rule, r0, r1, valid_host, one_mask, out);
+}
+
+int vsom_evaluate_masked_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t r1, const float *binary_host,
+                               const float *continuous_host, const uint8_t *valid_host, int one_mask,
+                               vsom_evaluate_masked_out *out)
+{
+    CHECK_CTX(c);                // (reads the map only; the safe default all the same, as vsom_evaluate_batch)
+    if (int rc = vsom_masked_score_gate(c, "vsom_evaluate_masked_batch", r0, r1, valid_host, out))
+        return rc;
+    if (!binary_host || !continuous_host)
+        return vsom_fail(VSOM_ERR_INVALID, "binary_host or continuous_host is null");
+    return launch_evaluate_masked(c, min_hits, r0, r1, binary_host, continuous_host, valid_host, one_mask, out);
+}
+
 int vsom_distances_row(vsom_ctx *c, size_t row, float *dist_out_host)
 {
     CHECK_CTX(c);

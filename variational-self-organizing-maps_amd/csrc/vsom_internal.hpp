@@ -429,6 +429,29 @@ VsomNodeGroups vsom_masked_groups(const vsom_ctx *c, size_t slice);
 int vsom_masked_search_enqueue(vsom_ctx *c, u64 min_hits, size_t s0, size_t s1, const unsigned char *vp, bool one,
                                const VsomNodeGroups &grp, u64 *part, unsigned char *nan0, u64 *bmu, float *dist,
                                unsigned *nvalid);
+// The same pieces for the callers that keep a slice's units on the device and work on them (the imputed rows of
+// launch_masked, the masked scorers): the scratch of one slice of `slice` rows added to a layout -- the validity bytes as
+// given and packed, the search's keys and flags, its results -- and slice [s0, s1) of a call over rows from r0: the slice's
+// validity bytes up and packed (a column mask once, with the first slice), then the search.  Enqueues only.
+struct VsomMaskedSearch {
+    bool one;
+    size_t slice;
+    VsomNodeGroups grp;
+    vsom_layout::piece<unsigned char> raw, packed, nan0;
+    vsom_layout::piece<u64> part, bmu;
+    vsom_layout::piece<float> dist;
+    vsom_layout::piece<unsigned> nvalid;
+};
+VsomMaskedSearch vsom_masked_search_add(const vsom_ctx *c, vsom_layout &lay, bool one, size_t slice);
+int vsom_masked_slice_enqueue(vsom_ctx *c, const vsom_layout &lay, const VsomMaskedSearch &ms, u64 min_hits, size_t r0,
+                              size_t s0, size_t s1, const uint8_t *valid_host);
+// vsom_similarity.hip / vsom_evaluate.hip: the masked search of chunk rows [r0,r1) in slices, each slice scored from its own
+// results and packed validity (arguments checked by vsom_similarity_masked_batch / vsom_evaluate_masked_batch); synchronise
+int launch_similarity_masked(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
+                             const uint8_t *valid_host, int one_mask, const vsom_similarity_masked_out *out);
+int launch_evaluate_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const float *binary_host,
+                           const float *continuous_host, const uint8_t *valid_host, int one_mask,
+                           const vsom_evaluate_masked_out *out);
 // vsom_masked_train.hip: the batch epoch over valid columns only (arguments checked by vsom_batch_epoch_masked); synchronises
 int launch_batch_epoch_masked(vsom_ctx *c, double sigma, int is_first, const uint8_t *valid_host, int one_mask);
 // vsom_accum.hip: the accumulated epoch (state and arguments checked by vsom_batch_accum_*); they enqueue only.  begin:

@@ -219,6 +219,40 @@ int vsom_masked_search_enqueue(vsom_ctx *c, u64 min_hits, size_t s0, size_t s1, 
     return VSOM_OK;
 }
 
+// The search scratch of one slice, for the callers that keep a slice's units on the device (launch_masked, the masked scorers)
+VsomMaskedSearch vsom_masked_search_add(const vsom_ctx *c, vsom_layout &lay, bool one, size_t slice)
+{
+    VsomMaskedSearch ms;
+    ms.one = one;
+    ms.slice = slice;
+    ms.grp = vsom_masked_groups(c, slice);
+    const size_t vrows = one ? 1 : slice;
+    ms.raw = lay.add<unsigned char>(vrows * c->J);
+    ms.packed = lay.add<unsigned char>(vrows * c->xpitch);
+    ms.nan0 = lay.add<unsigned char>(slice);
+    ms.part = lay.add<u64>(slice * ms.grp.ng);
+    ms.bmu = lay.add<u64>(slice);
+    ms.dist = lay.add<float>(slice);
+    ms.nvalid = lay.add<unsigned>(slice);
+    return ms;
+}
+
+// Slice [s0, s1) of a call over [r0, ...): its validity bytes up and packed (a column mask once, with the first slice), then
+// the search into ms.bmu / ms.dist / ms.nvalid.  Enqueues only.
+int vsom_masked_slice_enqueue(vsom_ctx *c, const vsom_layout &lay, const VsomMaskedSearch &ms, u64 min_hits, size_t r0,
+                              size_t s0, size_t s1, const uint8_t *valid_host)
+{
+    const size_t J = c->J;
+    if (!ms.one || s0 == r0) {
+        const size_t vr = ms.one ? 1 : s1 - s0;
+        VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(ms.raw), valid_host + (ms.one ? 0 : (s0 - r0) * J), vr * J, hipMemcpyHostToDevice,
+                                      c->stream));
+        vsom_masked_pack_enqueue(c, lay.at(ms.raw), vr, lay.at(ms.packed));
+    }
+    return vsom_masked_search_enqueue(c, min_hits, s0, s1, lay.at(ms.packed), ms.one, ms.grp, lay.at(ms.part), lay.at(ms.nan0),
+                                      lay.at(ms.bmu), lay.at(ms.dist), lay.at(ms.nvalid));
+}
+
 int launch_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
                   const vsom_masked_out *out)
 {
@@ -226,42 +260,29 @@ int launch_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const uint8_t
     const size_t J = c->J, vld = c->xpitch, rows = r1 - r0;
     if (rows == 0)
         return VSOM_OK;
-    const bool one = one_mask != 0;
     const size_t slice = std::min(vsom_masked_slice_rows(c, out->fill != nullptr), rows);
-    const VsomNodeGroups grp = vsom_masked_groups(c, slice);
-    const size_t ng = grp.ng;
-    const size_t vrows = one ? 1 : slice;
     // a slice's validity bytes as given and packed (0xFF / 0x00, xpitch per row), node-group keys, results and imputed rows
     vsom_layout lay;
-    const auto raw = lay.add<unsigned char>(vrows * J), valid = lay.add<unsigned char>(vrows * vld),
-               nan0 = lay.add<unsigned char>(slice);
-    const auto part = lay.add<u64>(slice * ng), bmu = lay.add<u64>(slice);
-    const auto dist = lay.add<float>(slice), fill = lay.add<float>(out->fill ? slice * J : 0);
-    const auto nvalid = lay.add<unsigned>(slice);
+    const VsomMaskedSearch ms = vsom_masked_search_add(c, lay, one_mask != 0, slice);
+    const auto fill = lay.add<float>(out->fill ? slice * J : 0);
     VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
 
     for (size_t s0 = r0; s0 < r1; s0 += slice) {
         const size_t s1 = std::min(r1, s0 + slice), n = s1 - s0, off = s0 - r0;
-        if (!one || s0 == r0) {     // (a column mask is packed once)
-            const size_t vr = one ? 1 : n;
-            VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(raw), valid_host + (one ? 0 : off * J), vr * J, hipMemcpyHostToDevice, c->stream));
-            vsom_masked_pack_enqueue(c, lay.at(raw), vr, lay.at(valid));
-        }
-        if (int rc = vsom_masked_search_enqueue(c, min_hits, s0, s1, lay.at(valid), one, grp, lay.at(part), lay.at(nan0),
-                                                lay.at(bmu), lay.at(dist), lay.at(nvalid)))
+        if (int rc = vsom_masked_slice_enqueue(c, lay, ms, min_hits, r0, s0, s1, valid_host))
             return rc;
         if (out->fill)
             hipLaunchKernelGGL(masked_fill_kernel, dim3((unsigned)n, (unsigned)((J + 255) / 256)), dim3(256), 0, c->stream,
                                reinterpret_cast<const unsigned *>(c->Xs.p), (int)c->xpitch,
-                               reinterpret_cast<const unsigned *>(c->map.p), (int)c->pitch, lay.at(bmu), lay.at(valid), (int)vld,
-                               (int)one, (int)s0, (int)J, reinterpret_cast<unsigned *>(lay.at(fill)));
+                               reinterpret_cast<const unsigned *>(c->map.p), (int)c->pitch, lay.at(ms.bmu), lay.at(ms.packed),
+                               (int)vld, (int)ms.one, (int)s0, (int)J, reinterpret_cast<unsigned *>(lay.at(fill)));
         VSOM_HIP_CHECK(hipGetLastError());
         if (out->bmu)
-            VSOM_HIP_CHECK(hipMemcpyAsync(out->bmu + off, lay.at(bmu), n * 8, hipMemcpyDeviceToHost, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(out->bmu + off, lay.at(ms.bmu), n * 8, hipMemcpyDeviceToHost, c->stream));
         if (out->dist)
-            VSOM_HIP_CHECK(hipMemcpyAsync(out->dist + off, lay.at(dist), n * 4, hipMemcpyDeviceToHost, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(out->dist + off, lay.at(ms.dist), n * 4, hipMemcpyDeviceToHost, c->stream));
         if (out->nvalid)
-            VSOM_HIP_CHECK(hipMemcpyAsync(out->nvalid + off, lay.at(nvalid), n * 4, hipMemcpyDeviceToHost, c->stream));
+            VSOM_HIP_CHECK(hipMemcpyAsync(out->nvalid + off, lay.at(ms.nvalid), n * 4, hipMemcpyDeviceToHost, c->stream));
         if (out->fill)
             VSOM_HIP_CHECK(hipMemcpyAsync(out->fill + off * J, lay.at(fill), n * J * 4, hipMemcpyDeviceToHost, c->stream));
     }

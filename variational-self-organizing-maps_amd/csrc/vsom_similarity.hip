@@ -13,6 +13,13 @@
 //                      No LDS, no atomics; lane 0 stores the row's nine words.
 // The memory traffic is 12 C bytes per row (three gathered rows) plus C bytes of validity and 4 C of the dense report when
 // those are asked for: the kernel is bound by the latency of the dependent gather (lastBMU -> model rows), not arithmetic.
+//
+//  similarity_kernel<true, true> : the same wavefront for vsom_similarity_masked_batch.  The row's unit and distance come
+//                      from the results of the slice's masked search (vsom_masked_search_enqueue) instead of lastBMU / sqres,
+//                      the validity from the packed bytes that search read (0xFF / 0x00, xpitch per row, or the one shared
+//                      row), and delta of an invalid column is the quiet NaN by select before anything is reduced: such a
+//                      column can be neither dmax nor first nor amax, is not counted outside, and stores 0 in the dense
+//                      report, whatever x, map and sigmaMap hold there.  Lane 0 stores a tenth word, the row's nvalid.
 #include "vsom_device.hpp"
 #include <algorithm>
 #include <cstring>
@@ -20,17 +27,20 @@
 #define SIM_NONE 0xFFFFFFFFu
 #define SIM_ROWS_PER_WG 4
 #define SIM_ROW_WORDS 9     // bmu (2), dist, dmax, dmax_col, first, amax, amax_col, outside
+#define SIM_MROW_WORDS 10   // ... and nvalid (vsom_similarity_masked_batch)
 
 struct SimArgs {
     const float *x;             // staged rows (Xs), pitch ldx
     const float *map, *sigma;   // model rows, pitch ldm
-    const u64 *lastbmu;
+    const u64 *lastbmu;         // per chunk row; MASKED: the slice's search results, entry r - s0 for row r
     const float *sqres;
-    const unsigned char *valid; // rows [r0, r1) x J, or null: every column valid
+    const unsigned *nvalid;     // MASKED only: the slice's counts of valid columns
+    const unsigned char *valid; // rows [r0, r1) x J, or null: every column valid; MASKED: the slice's packed rows, vstride
+                                // bytes apart (0: the one row every sample shares)
     float *delta;               // the slice's dense report, rows x C, or null
     unsigned *rows;             // per-row results of [r0, r1): SIM_ROW_WORDS arrays of R entries
     int ldx, ldm, part_len, part_pitch;
-    int J, C, N, R;
+    int J, C, N, R, vstride;
     float k;
     int floor_rule;
 };
@@ -57,13 +67,16 @@ struct SimLane {
     uint32_t dmax_c, first_c, amax_c, outside;
 };
 
+template <bool MASKED>
 __device__ __forceinline__ float sim_column(SimLane &l, const SimArgs &a, uint32_t d, float x, float m, float s, bool valid)
 {
     const float eps = 0.00001f;
     const float sM = a.floor_rule ? (s > eps ? s : eps) : (s > eps ? eps : s);
     const float t = x - m;
     const float q = t / sM;
-    const float delta = q / a.k;
+    float delta = q / a.k;
+    if constexpr (MASKED)
+        delta = valid ? delta : __uint_as_float(0x7FC00000u);
     const float sk = sM * a.k;
     const float lo = m - sk, hi = m + sk;
     if (delta == delta && (l.dmax_c == SIM_NONE || delta > l.dmax_v)) {
@@ -88,7 +101,9 @@ __device__ __forceinline__ float sim_column(SimLane &l, const SimArgs &a, uint32
 // VEC: the model row is one part and lanes take four consecutive columns per step (pitches are multiples of 32 floats and
 // C <= J, D: a 16-byte load of a row's last, partial quad stays inside the padded row).  Otherwise one column per lane and
 // step, logical column d of a model row at (d / part_len) * part_pitch + d % part_len.
-template <bool VEC>
+// MASKED (with VEC): unit, distance and nvalid of row r at entry r - s0 of the slice's search results, validity row r - s0
+// of the packed rows (C <= J <= xpitch: the bytes of a partial quad are padding zeros).
+template <bool VEC, bool MASKED = false>
 __global__ __launch_bounds__(64 * SIM_ROWS_PER_WG) void similarity_kernel(SimArgs a, int r0, int s0, int s1)
 {
     constexpr int W = VEC ? 4 : 1;
@@ -97,12 +112,14 @@ __global__ __launch_bounds__(64 * SIM_ROWS_PER_WG) void similarity_kernel(SimArg
     const int r = s0 + (int)blockIdx.x * SIM_ROWS_PER_WG + (int)(threadIdx.x >> 6);
     if (r >= s1)
         return;                                 // (wavefront-uniform)
-    u64 b = a.lastbmu[r];
+    const size_t ri = MASKED ? (size_t)(r - s0) : (size_t)r;    // the row's entry of lastbmu / sqres / nvalid
+    u64 b = a.lastbmu[ri];
     b = b < (u64)a.N ? b : 0;                   // (the searches store indices below N)
     const float *xr = a.x + (size_t)r * a.ldx;
     const float *mr = a.map + (size_t)b * a.ldm;
     const float *sr = a.sigma + (size_t)b * a.ldm;
-    const unsigned char *vr = a.valid ? a.valid + (size_t)(r - r0) * a.J : nullptr;
+    const unsigned char *vr = MASKED ? a.valid + ri * (size_t)a.vstride
+                                     : (a.valid ? a.valid + (size_t)(r - r0) * a.J : nullptr);
     float *dr = a.delta ? a.delta + (size_t)(r - s0) * a.C : nullptr;
     const int C = a.C;
     const bool quad_store = VEC && (C & 3) == 0;
@@ -150,7 +167,7 @@ __global__ __launch_bounds__(64 * SIM_ROWS_PER_WG) void similarity_kernel(SimArg
                     const int d = g * W + e;
                     out[e] = 0.f;
                     if (d < C)
-                        out[e] = sim_column(l, a, (uint32_t)d, xv[u][e], mv[u][e], sv[u][e], vv[u][e] != 0);
+                        out[e] = sim_column<MASKED>(l, a, (uint32_t)d, xv[u][e], mv[u][e], sv[u][e], vv[u][e] != 0);
                 }
                 if (dr) {
                     bool stored = false;
@@ -187,14 +204,16 @@ __global__ __launch_bounds__(64 * SIM_ROWS_PER_WG) void similarity_kernel(SimArg
     const float first = __shfl(l.first_v, fc == SIM_NONE ? 0 : (int)((fc / W) & 63));   // (... NaN)
     if (lane == 0) {
         const size_t i = (size_t)(r - r0), R = (size_t)a.R;
-        reinterpret_cast<u64 *>(a.rows)[i] = a.lastbmu[r];
-        a.rows[2 * R + i] = __float_as_uint(a.sqres[r]);
+        reinterpret_cast<u64 *>(a.rows)[i] = a.lastbmu[ri];
+        a.rows[2 * R + i] = __float_as_uint(a.sqres[ri]);
         a.rows[3 * R + i] = __float_as_uint(dmax);
         a.rows[4 * R + i] = dc;
         a.rows[5 * R + i] = __float_as_uint(first);
         a.rows[6 * R + i] = __float_as_uint(amax);
         a.rows[7 * R + i] = ac;
         a.rows[8 * R + i] = cnt;
+        if constexpr (MASKED)
+            a.rows[9 * R + i] = a.nvalid[ri];
     }
 }
 
@@ -202,6 +221,26 @@ __global__ __launch_bounds__(64 * SIM_ROWS_PER_WG) void similarity_kernel(SimArg
 static size_t vsom_similarity_slice_rows(size_t C)
 {
     return std::max<size_t>(1, ((size_t)64 << 20) / (4 * C));
+}
+
+// what the two launchers share: the operands of the context and the call's constants
+static SimArgs sim_args(const vsom_ctx *c, size_t C, size_t rows, int num_sigmas, int sigma_rule)
+{
+    SimArgs a{};
+    a.x = c->Xs.p;
+    a.map = c->map.p;
+    a.sigma = c->sigma.p;
+    a.ldx = (int)c->xpitch;
+    a.ldm = (int)c->pitch;
+    a.part_len = (int)c->part_len;
+    a.part_pitch = (int)c->part_pitch;
+    a.J = (int)c->J;
+    a.C = (int)C;
+    a.N = (int)c->N;
+    a.R = (int)rows;
+    a.k = (float)num_sigmas;
+    a.floor_rule = sigma_rule == VSOM_SIGMA_FLOOR;
+    return a;
 }
 
 int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
@@ -228,25 +267,14 @@ int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule,
     if (valid_host)
         VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(valid), valid_host, rows * c->J, hipMemcpyHostToDevice, c->stream));
 
-    SimArgs a;
-    a.x = c->Xs.p;
-    a.map = c->map.p;
-    a.sigma = c->sigma.p;
+    SimArgs a = sim_args(c, C, rows, num_sigmas, sigma_rule);
     a.lastbmu = c->lastbmu.p;
     a.sqres = c->sqres.p;
+    a.nvalid = nullptr;
     a.valid = valid_host ? lay.at(valid) : nullptr;
+    a.vstride = (int)c->J;
     a.delta = out->delta ? lay.at(delta) : nullptr;
     a.rows = lay.at(srows);
-    a.ldx = (int)c->xpitch;
-    a.ldm = (int)c->pitch;
-    a.part_len = (int)c->part_len;
-    a.part_pitch = (int)c->part_pitch;
-    a.J = (int)c->J;
-    a.C = (int)C;
-    a.N = (int)c->N;
-    a.R = (int)rows;
-    a.k = (float)num_sigmas;
-    a.floor_rule = sigma_rule == VSOM_SIGMA_FLOOR;
     for (size_t s0 = r0; s0 < r1; s0 += slice) {
         const size_t s1 = std::min(r1, s0 + slice), n = s1 - s0;
         {
@@ -267,6 +295,65 @@ int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule,
     const unsigned *p = pin.at(pinned);
     void *dst[SIM_ROW_WORDS - 1] = {out->bmu, out->dist, out->dmax, out->dmax_col, out->first, out->amax, out->amax_col, out->outside};
     for (int i = 0; i < SIM_ROW_WORDS - 1; ++i) {
+        const size_t at = i == 0 ? 0 : (size_t)(i + 1) * rows, len = i == 0 ? 2 * rows : rows;
+        if (dst[i])
+            std::memcpy(dst[i], p + at, len * 4);
+    }
+    return VSOM_OK;
+}
+
+// vsom_similarity_masked_batch: per slice the validity bytes up and packed once, the masked search (VSOM_T_BMU), and the
+// scoring of the slice's rows from the search's own results and packed bytes (VSOM_T_FINISH).  The slice follows the masked
+// search's rule with the dense report's cap on top.
+int launch_similarity_masked(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
+                             const uint8_t *valid_host, int one_mask, const vsom_similarity_masked_out *out)
+{
+    const size_t rows = r1 - r0;
+    if (rows == 0)
+        return VSOM_OK;
+    const size_t C = c->J;                      // (Standard / Median: D = J)
+    size_t slice = std::min(vsom_masked_search_slice_rows(c), rows);
+    if (out->delta)
+        slice = std::min(slice, vsom_similarity_slice_rows(C));
+    const size_t words = rows * SIM_MROW_WORDS;
+    vsom_layout lay, pin;
+    const VsomMaskedSearch ms = vsom_masked_search_add(c, lay, one_mask != 0, slice);
+    const auto srows = lay.add<unsigned>(words), pinned = pin.add<unsigned>(words);
+    const auto delta = lay.add<float>(out->delta ? slice * C : 0);
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_pinned, pin, c->stream));
+
+    SimArgs a = sim_args(c, C, rows, num_sigmas, sigma_rule);
+    a.lastbmu = lay.at(ms.bmu);
+    a.sqres = lay.at(ms.dist);
+    a.nvalid = lay.at(ms.nvalid);
+    a.valid = lay.at(ms.packed);
+    a.vstride = ms.one ? 0 : (int)c->xpitch;
+    a.delta = out->delta ? lay.at(delta) : nullptr;
+    a.rows = lay.at(srows);
+    for (size_t s0 = r0; s0 < r1; s0 += slice) {
+        const size_t s1 = std::min(r1, s0 + slice), n = s1 - s0;
+        {
+            TimerScope ts(c, VSOM_T_BMU);
+            if (int rc = vsom_masked_slice_enqueue(c, lay, ms, min_hits, r0, s0, s1, valid_host))
+                return rc;
+        }
+        {
+            TimerScope ts(c, VSOM_T_FINISH);
+            const dim3 grid((unsigned)((n + SIM_ROWS_PER_WG - 1) / SIM_ROWS_PER_WG)), block(64 * SIM_ROWS_PER_WG);
+            hipLaunchKernelGGL((similarity_kernel<true, true>), grid, block, 0, c->stream, a, (int)r0, (int)s0, (int)s1);
+            VSOM_HIP_CHECK(hipGetLastError());
+        }
+        if (out->delta)
+            VSOM_HIP_CHECK(hipMemcpyAsync(out->delta + (s0 - r0) * C, lay.at(delta), n * C * 4, hipMemcpyDeviceToHost, c->stream));
+    }
+    VSOM_HIP_CHECK(hipMemcpyAsync(pin.at(pinned), lay.at(srows), words * 4, hipMemcpyDeviceToHost, c->stream));
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+
+    const unsigned *p = pin.at(pinned);
+    void *dst[SIM_MROW_WORDS - 1] = {out->bmu,  out->dist,     out->dmax,    out->dmax_col, out->first,
+                                     out->amax, out->amax_col, out->outside, out->nvalid};
+    for (int i = 0; i < SIM_MROW_WORDS - 1; ++i) {
         const size_t at = i == 0 ? 0 : (size_t)(i + 1) * rows, len = i == 0 ? 2 * rows : rows;
         if (dst[i])
             std::memcpy(dst[i], p + at, len * 4);

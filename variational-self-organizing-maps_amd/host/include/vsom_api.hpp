@@ -551,6 +551,25 @@ public:
         double error = 0;
     };
     EvaluateRows evaluateRows(const DataSet &data) const;
+    // [MI355X build] extensions: similarityRows / measureSimilarity / evaluateRows / evaluate for records with missing fields
+    // (one vsom_similarity_masked_batch / vsom_evaluate_masked_batch call, include/vsom_hip.h): every row of `data` is
+    // searched over its VALID columns only, as findMaskedBmus, and scored against that unit in those columns -- dmax / first
+    // range over the valid columns, delta is 0 at invalid ones, an invalid column's binary error term is +0 -- and nvalid
+    // counts the row's valid columns.  The data set's validity flags are the mask (any non-zero flag is valid), its
+    // getBinary / getContinuous the column factors.  measureSimilarityMasked takes the reference's sigma select as written
+    // and measureSimilarity's finish; evaluateMasked returns the running mean.  Standard / Median on the device only; no
+    // state is downloaded.
+    struct SimilarityRowsMasked : SimilarityRows {
+        std::vector<uint32_t> nvalid;
+    };
+    struct EvaluateRowsMasked : EvaluateRows {
+        std::vector<uint32_t> nvalid;
+    };
+    SimilarityRowsMasked similarityRowsMasked(const DataSet *data, int numberOfSigmas, size_t minBmuHits, bool floor = true,
+                                              bool wantDelta = false) const;
+    int measureSimilarityMasked(const DataSet *data, int numberOfSigmas, size_t minBmuHits) const;
+    EvaluateRowsMasked evaluateRowsMasked(const DataSet &data, size_t minBmuHits = 0) const;
+    double evaluateMasked(const DataSet &data, size_t minBmuHits = 0) const;
     // [MI355X build] extension: autoEncoder's records with the caller's random numbers, for every row of `data` (one
     // vsom_generate_batch call, include/vsom_hip.h): a unit per row drawn with the uniform u[r] in [0,1) from the row's own
     // restricted distribution (perRow) or from that of the LAST row (the reference as written), and every column sampled as

@@ -1862,6 +1862,81 @@ std::vector<float> Som::impute(const DataSet *data, size_t minBmuHits) const
     return fill;
 }
 
+// upload, one vsom_similarity_masked_batch call with the data set's validity flags
+Som::SimilarityRowsMasked Som::similarityRowsMasked(const DataSet *data, int numOfSigmas, size_t minBmuHits, bool floor,
+                                                    bool wantDelta) const
+{
+    requireDevicePath("similarityRowsMasked");
+    const size_t n = data->size();
+    SimilarityRowsMasked r;
+    r.columns = inLen;
+    r.bmu.assign(n, 0);
+    r.dist.assign(n, 0.f);
+    r.dmax.assign(n, 0.f);
+    r.first.assign(n, 0.f);
+    r.amax.assign(n, 0.f);
+    r.dmaxCol.assign(n, 0);
+    r.amaxCol.assign(n, 0);
+    r.outside.assign(n, 0);
+    r.nvalid.assign(n, 0);
+    if (wantDelta)
+        r.delta.assign(n * r.columns, 0.f);
+    if (n == 0)
+        return r;
+    const std::vector<uint8_t> valid = validity_bytes(*data, inLen);
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data->contiguous(), n), "vsom_upload_chunk");
+    vsom_similarity_masked_out out = {r.bmu.data(),  r.dist.data(),    r.dmax.data(),    r.dmaxCol.data(),
+                                      r.first.data(), r.amax.data(),   r.amaxCol.data(), r.outside.data(),
+                                      wantDelta ? r.delta.data() : nullptr, r.nvalid.data()};
+    check(vsom_similarity_masked_batch(ctx, minBmuHits, numOfSigmas, floor ? VSOM_SIGMA_FLOOR : VSOM_SIGMA_AS_WRITTEN, 0, n,
+                                       valid.data(), 0, &out),
+          "vsom_similarity_masked_batch");
+    return r;
+}
+
+int Som::measureSimilarityMasked(const DataSet *data, int numOfSigmas, size_t minBmuHits) const
+{
+    requireDevicePath("measureSimilarityMasked");
+    if (data->size() == 0)
+        return true;
+    const SimilarityRowsMasked r = similarityRowsMasked(data, numOfSigmas, minBmuHits, false, false);
+    return r.outside[measureSimilarityRow(r.first, r.dmax)] == 0;
+}
+
+// upload, one vsom_evaluate_masked_batch call with the data set's validity flags and column factors
+Som::EvaluateRowsMasked Som::evaluateRowsMasked(const DataSet &data, size_t minBmuHits) const
+{
+    requireDevicePath("evaluateRowsMasked");
+    const size_t n = data.size();
+    EvaluateRowsMasked r;
+    r.bmu.assign(n, 0);
+    r.dist.assign(n, 0.f);
+    r.bsum.assign(n, 0.f);
+    r.nrepl.assign(n, 0);
+    r.nvalid.assign(n, 0);
+    if (n == 0)
+        return r;
+    const std::vector<uint8_t> valid = validity_bytes(data, inLen);
+    const Eigen::ArrayXi continuous = data.getContinuous(), binary = data.getBinary();
+    std::vector<float> fb(inLen, 0.f), fc(inLen, 0.f);
+    for (size_t d = 0; d < inLen; ++d) {
+        fb[d] = d < (size_t)binary.size() ? (float)binary[(Eigen::Index)d] : 0.f;
+        fc[d] = d < (size_t)continuous.size() ? (float)continuous[(Eigen::Index)d] : 0.f;
+    }
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data.contiguous(), n), "vsom_upload_chunk");
+    vsom_evaluate_masked_out out = {r.bmu.data(), r.dist.data(), r.bsum.data(), r.nrepl.data(), &r.error, r.nvalid.data()};
+    check(vsom_evaluate_masked_batch(ctx, minBmuHits, 0, n, fb.data(), fc.data(), valid.data(), 0, &out),
+          "vsom_evaluate_masked_batch");
+    return r;
+}
+
+double Som::evaluateMasked(const DataSet &data, size_t minBmuHits) const
+{
+    return evaluateRowsMasked(data, minBmuHits).error;
+}
+
 size_t Som::measureSimilarityRow(const std::vector<float> &first, const std::vector<float> &dmax)
 {
     const size_t n = std::min(first.size(), dmax.size());

@@ -472,6 +472,58 @@ class Som:
         unit over the valid ones (validity as in findBmuMasked)"""
         return self._masked(data, getattr(data, "validity", None), minBmuHits, True)["fill"]
 
+    # ---- the two scorers over the valid columns only (extensions) --------------------------------
+    def _validity(self, data):
+        valid = getattr(data, "validity", None)
+        return np.ones(self.ctx.in_len, np.uint8) if valid is None else valid
+
+    def similarityRowsMasked(self, data, numOfSigmas, minBmuHits, floor=True, delta=False):
+        """extension: similarityRows for records with missing fields (capi.Context.similarity_masked): every loaded row of
+        `data` searched over its valid columns only, as findBmuMasked, and scored against that unit in those columns;
+        similarityRows' report (dmax / first over the valid columns, delta 0 at invalid ones) and nvalid.  The validity
+        comes from the data set when it has one (an attribute `validity`, rows x J, nonzero = valid); without one every
+        column is valid."""
+        X = self._rows(data)
+        self.ctx.upload_chunk(X)
+        n, J = X.shape[0], self.ctx.in_len
+        if n == 0:
+            rep = {k: np.zeros(0, np.float32) for k in ("dist", "dmax", "first", "amax")}
+            rep.update({k: np.zeros(0, np.uint32) for k in ("dmax_col", "amax_col", "outside", "nvalid")})
+            rep.update(bmu=np.zeros(0, np.uint64), delta=np.zeros((0, J), np.float32) if delta else None)
+            return rep
+        rule = capi.SIGMA_FLOOR if floor else capi.SIGMA_AS_WRITTEN
+        return self.ctx.similarity_masked(self._validity(data), minBmuHits, numOfSigmas, sigma_rule=rule, delta=delta)
+
+    def measureSimilarityMasked(self, data, numOfSigmas, minBmuHits):
+        """extension: measureSimilarity for records with missing fields: the same finish (the reference's sigma select as
+        written) over the report of similarityRowsMasked -- the record with the largest relative distance to its masked
+        BMU in any VALID column, and whether it lies inside the approved interval in all its valid columns."""
+        X = self._rows(data)
+        if X.shape[0] == 0:
+            return True
+        rep = self.similarityRowsMasked(data, numOfSigmas, minBmuHits, floor=False)
+        return measure_similarity_from_rows(rep["first"], rep["dmax"], rep["outside"])[1]
+
+    def evaluateRowsMasked(self, data, binary=None, continuous=None, minBmuHits=0):
+        """extension: evaluateRows for records with missing fields (capi.Context.evaluate_masked): every loaded row of
+        `data` searched over its valid columns only and its binary error summed over those columns; evaluateRows' report
+        and nvalid.  binary / continuous default as in evaluateRows, the validity as in similarityRowsMasked."""
+        X = self._rows(data)
+        J = self.ctx.in_len
+        binary = np.zeros(J, np.float32) if binary is None else binary
+        continuous = np.ones(J, np.float32) if continuous is None else continuous
+        self.ctx.upload_chunk(X)
+        if X.shape[0] == 0:
+            return {"bmu": np.zeros(0, np.uint64), "dist": np.zeros(0, np.float32), "bsum": np.zeros(0, np.float32),
+                    "nrepl": np.zeros(0, np.uint32), "error": 0.0, "nvalid": np.zeros(0, np.uint32)}
+        return self.ctx.evaluate_masked(self._validity(data), binary, continuous, min_hits=minBmuHits)
+
+    def evaluateMasked(self, data, binary=None, continuous=None, minBmuHits=0):
+        """extension: evaluate for records with missing fields: the mean over the loaded rows of `data` of the masked
+        distance to the masked BMU plus the norm of the binary error over the valid columns (arguments as
+        evaluateRowsMasked)."""
+        return self.evaluateRowsMasked(data, binary, continuous, minBmuHits)["error"]
+
     def classify(self, data, label_columns, minBmuHits=0):
         """extension: a trained map with label columns used as a classifier.  Every loaded row of `data` is matched on the
         columns outside `label_columns` (a column mask; what the rows hold in the label columns is ignored), and its
