@@ -21,7 +21,46 @@ oracle state never depends on the mode.  The real backend drives a second contex
 same calls: what the readers, the arena queries and the masked epoch return must equal that twin's output bit for bit
 (doubles on 64 bits), and the twin's own state is compared with the oracle at the end.  The masked epoch's model is
 tests/masked_train_ref.py (its phase 1 and phase 2) applied to the model's oracle state.
+
+A third profile, "accum", walks the accumulated batch epoch (include/vsom_hip.h, vsom_batch_accum_begin / _chunk /
+_chunk_masked / _end / _abort; DESIGN.md sections 4n, 4o): the one protocol of the C ABI whose state lives across calls
+that do not block.  It keeps every op of the sigma profile, under a sigma mode, and adds the five calls, the two masked
+scoring calls as row-window queries and an update-mode switch.  Epochs are generated whole (generate_accum); each walk holds,
+between ("run", id) / ("run_end", id) markers the backends never see, these runs:
+  1  no wait: begin(first), three masked chunks, each behind a load that does not synchronise and never the same rows
+     twice in a row, end -- the third reuses the first pinned validity half; this epoch has a row without a valid column
+     and a column without a valid row
+  2  no wait: plain chunks of growing size, the configuration's largest last, one top-8 query between two of them -- the
+     chunk buffers and the query arena grow behind enqueued work
+  3  plain, masked, plain in a non-first epoch, vsom_set_last_bmu between each load and its chunk call
+  4  abort behind two chunks or more, one masked; get_state; a plain epoch on the same context (the ever-dirty list is gone)
+  5  epoch_async, prefetch, begin, a chunk call, commit, a chunk call, abort: where stages_ahead(cfg) the prefetch is
+     staged ahead and the first chunk call MUST be refused, naming the commit (elsewhere it takes the old chunk)
+  6  every refusal the header lists, each followed by a comparison of the whole state; the empty epoch; an empty chunk
+  7  an epoch that leaves its sigmaMap pending (where the configuration defers), then begin
+  8  vsom_set_state(map) and a single step at another sigma between two chunks; ended with end
+  9  the masked scoring calls, the masked search, the BMD and a reader between two chunks
+In runs 1-4 and 6-9 a call is refused only where the header says it must be; every refusal of one of the five calls,
+run 5's included, is followed at once by a comparison of the whole state, lastBMU and the MSE word.  The model (Model._accum_*) keeps the epoch's
+rows, validity and lastBMU and restates begin / chunk / end / abort from the oracle: phase 1 per chunk on the model's
+current map (batch_phase1_range, or masked_train_ref.phase1), the running MSE in sample order over total_rows, phase 2 at end
+over the concatenation -- the clean columns from one batch_phase2_range, every column that had an invalid entry from
+masked_train_ref.phase2.  Masks are engineered (materialize): at most 16 dirty columns per epoch -- column 0, column J - 1,
+columns 31 and 32, one column invalid in every masked chunk, and columns that turn dirty only in the epoch's second or
+third masked chunk -- except in run 1, whose row without a valid column makes every column dirty.  The rows loaded for a
+masked chunk call are made for that call (poisoned_rows; the load op carries the call's parameters): NaN / +-inf under
+every invalid entry of its mask -- the border columns, the column invalid throughout, the columns that have just turned
+dirty, the empty row -- and nowhere else.  The real backend drives a second context through the same calls, fed from
+pageable memory, fixed at VSOM_SIGMA_EAGER and synchronised after every call: what the twin-compared calls return must equal
+that sequential twin's output bit for bit.  Between two calls of a walk the twin makes its call and waits, and the model
+runs its own (a Python masked search takes a second), so the first context's stream is as good as idle at every call:
+call by call the walk tests the state logic, not the ordering.  The no-wait runs 1 and 2 are therefore issued back to back
+on the first context (run_walk, back_to_back), with nothing between two calls but the calls' own host work, and only then
+replayed on the twin and the model, each return held against them: there the third masked chunk does meet a busy stream,
+and the buffers and the arena do grow behind enqueued work.  (Not on clr12 / custom12, where begin is refused, and not on
+the CPU fake, which is sequential by nature.)
 """
+import copy
 import ctypes as C
 
 import numpy as np
@@ -31,6 +70,7 @@ import masked_train_ref
 from oracle import pyoracle as po
 
 VSOM_ERR_INVALID = -1
+VSOM_ERR_UNSUPPORTED = -4
 EXPONENTIAL, INVERSE_PROPORTIONAL = 0, 1
 BMU_AUTO, BMU_EXACT, BMU_SHORTLIST = 0, 1, 2
 SIGMA_AUTO, SIGMA_EAGER, SIGMA_LAZY = 0, 1, 2
@@ -41,13 +81,16 @@ VSOM_CHAIN_MAX_WAVES = 448           # csrc/vsom_internal.hpp
 # configuration: map, transformation, chunks (size, kind); kinds: "u8" uint8-valued, "f" the same / 255, "dense" blobs,
 # "clr" correlated columns
 CONFIGS = {
+    # (accum_chunks: further chunks of the accum profile alone, two of them short enough for the model's masked full
+    # search, so that the masked chunks of run 1 follow each other with different rows)
     "std48": dict(W=48, H=48, J=196, tr=po.STANDARD, custom=False,
-                  chunks=[(1100, "u8"), (1280, "f"), (77, "u8"), (1500, "dense"), (4500, "u8"), (1024, "f")]),
+                  chunks=[(1100, "u8"), (1280, "f"), (77, "u8"), (1500, "dense"), (4500, "u8"), (1024, "f")],
+                  accum_chunks=[(33, "u8"), (23, "f")]),
     # (sigma_weights: the sigma profile's draws alone.  Median's online scan and its masked search -- Python, a row of the
     # 300-row shortest chunk at a time -- are the model's dearest ops: drawn less often there)
     "med48": dict(W=48, H=48, J=196, tr=po.MEDIAN, custom=False,
                   chunks=[(1100, "u8"), (300, "dense"), (1536, "f"), (4500, "u8"), (1024, "u8")],
-                  sigma_weights={"online": 1, "single": 1, "epoch_masked": 0.5}),
+                  sigma_weights={"online": 1, "single": 1, "epoch_masked": 0.5}, accum_chunks=[(33, "dense"), (23, "u8")]),
     "std12": dict(W=12, H=12, J=24, tr=po.STANDARD, custom=False,
                   chunks=[(300, "dense"), (128, "dense"), (77, "dense"), (1500, "dense")]),
     "clr12": dict(W=12, H=12, J=6, tr=po.CLR, custom=False,
@@ -57,7 +100,8 @@ CONFIGS = {
     # 100 node groups x 7 column blocks = 700 workgroups: a deferred whole-map launch takes the two-quad mean-only chains
     # (two_quad_launch below).  The online scan and the single step cost N x D per sample on the oracle: drawn less often.
     "std80": dict(W=80, H=80, J=196, tr=po.STANDARD, custom=False,
-                  chunks=[(320, "u8"), (77, "u8"), (512, "f"), (200, "dense")], weights={"online": 2, "single": 1}),
+                  chunks=[(320, "u8"), (77, "u8"), (512, "f"), (200, "dense")], weights={"online": 2, "single": 1},
+                  accum_chunks=[(40, "u8"), (12, "dense"), (11, "u8")]),
 }
 
 # ops that read the staged rows of the current chunk: the ones a pending chunk staged ahead may refuse
@@ -79,12 +123,37 @@ READERS = ("similarity", "generate", "decode_nodes", "distances_raw", "umatrix",
 ARENA = ("topk", "bmd", "bmu_masked")
 # what the real backend checks against its EAGER twin, bit for bit
 TWIN_COMPARED = set(READERS) | set(ARENA) | {"epoch_masked"}
+# ---- the accum profile ----
+ACCUM_OPS = ("accum_begin", "accum_chunk", "accum_chunk_masked", "accum_end", "accum_abort")
+MASKED_SCORES = ("similarity_masked", "evaluate_masked")
+READS_ROWS |= {"accum_chunk", "accum_chunk_masked"} | set(MASKED_SCORES)
+CUSTOM_REFUSED |= set(MASKED_SCORES)
+CLR_REFUSED |= set(MASKED_SCORES)
+ACCUM_TWIN_COMPARED = TWIN_COMPARED | set(MASKED_SCORES)
+# vsom_set_update_mode touches neither the stream nor the pending record
+ACCUM_KEEP = {"update_mode"}
+ACCUM_DRAWS = 12                     # random draws of an accum walk, around its runs (about 120 ops)
+UPDATE_STRICT, UPDATE_FMA = 0, 1
+MASK_ROWS = 300                      # masked chunks on chunks of at most this many rows (at scale 1): the model's masked
+#                                      search is pure Python, a row at a time
+MASK_DISTANCES = 80000               # ... at about 9 us a distance
+MAX_DIRTY = 16                       # dirty columns of an epoch (but for run 1's row without a valid column)
+RUNS = tuple(range(1, 10))
+NO_WAIT_RUNS = (1, 2)
+# what may stand inside a no-wait run: none of these waits for the stream (an upload only with asynchronous=True, a
+# prefetch only from pinned memory); run 2's top-k query, its subject, is the one exception
+NO_WAIT_OPS = {"upload", "prefetch", "stage", "commit", "accum_begin", "accum_chunk", "accum_chunk_masked"}
 
 
-def chunk_data(cfg_name, seed, scale=1):
+def chunk_list(cfg, profile="ingest"):
+    """the configuration's chunks (size, kind) as the profile sees them"""
+    return cfg["chunks"] + (cfg.get("accum_chunks", []) if profile == "accum" else [])
+
+
+def chunk_data(cfg_name, seed, scale=1, profile="ingest"):
     cfg = CONFIGS[cfg_name]
     out = []
-    for i, (b, kind) in enumerate(cfg["chunks"]):
+    for i, (b, kind) in enumerate(chunk_list(cfg, profile)):
         b = max(8, b // scale)
         s = 1000 * seed + 17 * i + 3
         if kind == "u8":
@@ -97,6 +166,66 @@ def chunk_data(cfg_name, seed, scale=1):
             x = gen.blobs(b, cfg["J"], 5, s, s + 1, sigma=0.4)
         out.append(np.ascontiguousarray(x, np.float32))
     return out
+
+
+def maskable(cfg, first=False):
+    """The chunks a masked chunk call may run on: at most MASK_ROWS rows at scale 1, and at most MASK_DISTANCES masked
+    distances of the model's -- rows x nodes in an epoch that searches the whole map (is_first), an eighth of that or less
+    for the local walk from lastBMU.  (Only run 1 puts masked chunks into a first epoch: generate_accum.)"""
+    cap = (1 if first else 8) * MASK_DISTANCES // (cfg["W"] * cfg["H"])
+    return [i for i, (b, _) in enumerate(chunk_list(cfg, "accum")) if b <= min(cap, MASK_ROWS)]
+
+
+def accepts_accum(cfg):
+    """whether vsom_batch_accum_begin opens an epoch on this configuration (Standard / Median, no custom hooks)"""
+    return not cfg["custom"] and cfg["tr"] != po.CLR
+
+
+def border_columns(J):
+    """the columns every masked chunk has invalid entries in: the first, the last, one each side of the 32-column word
+    border of the (column, row) bits (where the map is that deep)"""
+    return sorted({0, J - 1} | ({31, 32} if J > 33 else set()))
+
+
+def poisoned_rows(X, seed, k, form, full):
+    """X with NaN / +inf / -inf under every invalid entry of accum_mask(seed, k, form, full, X): what the masked chunk call
+    with these parameters is given.  None of it may reach an output."""
+    valid = np.broadcast_to(accum_mask(seed, k, form, full, X) != 0, X.shape)
+    bad = np.array([np.nan, np.inf, -np.inf], np.float32)
+    rs = np.random.RandomState([seed, k, 1])
+    return np.where(valid, X, bad[rs.randint(3, size=X.shape)]).astype(np.float32)
+
+
+def accum_mask(seed, k, form, full, X):
+    """The validity bytes of the k-th masked chunk (from 0) of the epoch whose draws `seed` names, for the rows X: uint8
+    [B, J] (form "rows") or [J] ("one_mask").  The epoch's dirty columns are the border columns, one column invalid in every
+    masked chunk (with masked chunks only: no valid row in the whole epoch) and columns that turn dirty in the epoch's
+    second or third masked chunk, MAX_DIRTY at the most; `full` adds a row without a valid column, which makes every
+    column dirty.  Whatever is not finite in X is invalid."""
+    B, J = X.shape
+    rs = np.random.RandomState(seed)
+    base = border_columns(J)
+    others = [int(d) for d in rs.permutation(J) if d not in base]
+    dead, late = others[0], others[1:MAX_DIRTY - len(base)]
+    active = base + [d for i, d in enumerate(late) if 1 + i % 2 <= k]
+    rk = np.random.RandomState([seed, k])
+    if form == "one_mask":
+        valid = np.ones(J, np.uint8)
+        valid[base] = 0
+        valid[dead] = 0
+        for d in active[len(base):]:
+            valid[d] = rk.rand() < 0.5
+        return valid & np.isfinite(X).all(axis=0)
+    valid = np.ones((B, J), np.uint8)
+    valid[:, dead] = 0
+    if B:
+        for d in active:
+            bad = rk.rand(B) < 0.3
+            bad[rk.randint(B)] = True
+            valid[bad, d] = 0
+        if full:
+            valid[rk.randint(B), :] = 0
+    return valid & np.isfinite(X)
 
 
 def chain_max_nodes(cfg):
@@ -150,7 +279,7 @@ class _Gen:
         self.walk_mode = self.mode = mode  # sigma profile: the mode the required runs need, the mode in force
         self.last_sigma = None
         self.rs = np.random.RandomState(seed)
-        self.sizes = [max(8, b // scale) for b, _ in self.cfg["chunks"]]
+        self.sizes = [max(8, b // scale) for b, _ in chunk_list(self.cfg, profile)]
         self.N = self.cfg["W"] * self.cfg["H"]
         self.B = self.sizes[0]
         self.pending = None                # index of the pending chunk
@@ -171,6 +300,8 @@ class _Gen:
             self.B = 0
         elif name == "sigma_mode":
             self.mode = p["mode"]
+        elif name == "stage" and self.cfg["custom"] and self.profile == "accum":
+            pass                           # (refused: a custom context takes no chunk in HBM; nothing becomes pending)
         elif name in ("prefetch", "stage"):
             self.pending = p["chunk"]
         elif name == "commit" and self.pending is not None:
@@ -178,7 +309,7 @@ class _Gen:
             self.pending = None
         if name == "online":
             self.chain = self.pending is None       # (with a chunk pending the call may be refused)
-        elif name in ("single", "epoch", "epoch_async", "p1", "finish", "p2", "epoch_masked"):
+        elif name in ("single", "epoch", "epoch_async", "p1", "finish", "p2", "epoch_masked") or name in ACCUM_OPS:
             self.chain = False
         if "sigma" in p and name != "online":
             self.last_sigma = p["sigma"]
@@ -247,17 +378,24 @@ class _Gen:
                    "bmu_restricted", "distances", "distances_row", "set_last_bmu", "get_last_bmu", "get_sqres",
                    "get_mse", "bmu_mode", "set_state", "get_state"]
         w = np.array([3, 4, 4, 4, 3, 2, 5, 2, 2, 2, 1, 1, 1, 1, 1, 1, 1, 2, 1, 1], np.float64)
-        if self.profile == "sigma":
+        sigma_ops = self.profile in ("sigma", "accum")       # (the accum profile keeps every op of the sigma profile)
+        if sigma_ops:
             w[choices.index("epoch_async")], w[choices.index("epoch")] = 6, 5
             w[choices.index("online")] = 2         # (the oracle's serial scan: the ingest profile's subject, not this one's)
             more = ["sigma_mode", "sigma_flush", "compaction", "whole_p2", "upload_empty", "epoch_masked", "topk", "bmd",
                     "bmu_masked"] + list(READERS)
             choices = choices + more
             w = np.concatenate([w, [2, 1, 1, 3, 1, 1, 1, 1, 1] + [1] * len(READERS)])
+        if self.profile == "accum":
+            choices = choices + ["accum_epoch", "accum_stray"] + list(MASKED_SCORES)
+            w = np.concatenate([w, [3, 1, 1, 1]])
         for k, v in cfg.get("weights", {}).items():
             w[choices.index(k)] = v
-        if self.profile == "sigma":
+        if sigma_ops:
             for k, v in cfg.get("sigma_weights", {}).items():
+                w[choices.index(k)] = v
+        if self.profile == "accum":
+            for k, v in cfg.get("accum_weights", {}).items():
                 w[choices.index(k)] = v
         if cfg["custom"]:
             w[choices.index("bmu_mode")] = 0
@@ -293,7 +431,7 @@ class _Gen:
         elif what == "bmu_mode":
             self.emit(what, mode=self.r(3))
         elif what == "set_state":
-            parts = ["map", "msw", "all"] + (["map_only", "weight_only"] if self.profile == "sigma" else [])
+            parts = ["map", "msw", "all"] + (["map_only", "weight_only"] if sigma_ops else [])
             self.emit(what, seed=self.r(1 << 30), parts=parts[self.r(len(parts))])
         elif what == "sigma_mode":
             self.emit(what, mode=["auto", "eager", "lazy"][self.r(3)])
@@ -307,10 +445,188 @@ class _Gen:
             self.emit("upload", chunk=self.next_chunk(), asynchronous=False)
         elif what == "epoch_masked":
             self.masked_epoch()
-        elif what in READERS or what in ARENA:
+        elif what in READERS or what in ARENA or what in MASKED_SCORES:
             self.query(what)
+        elif what == "accum_epoch":
+            self.random_epoch()
+        elif what == "accum_stray":
+            self.emit(["accum_chunk", "accum_end", "accum_abort"][self.r(3)])      # (no epoch is open: refused)
         else:
             self.emit(what)
+
+    # ---- the accum profile: epochs are generated whole, so that total_rows is known at the begin ----
+    def load(self, chunk, nowait=False, poisoned=False):
+        """make `chunk` the current chunk; nowait: by calls that do not wait for the stream (an asynchronous upload from
+        pinned memory, a prefetch from pinned memory or a chunk handed over in HBM, and the commit)"""
+        p = dict(chunk=int(chunk))
+        if poisoned and accepts_accum(self.cfg):       # (elsewhere the call is refused and the rows reach the other ops)
+            p["poisoned"] = poisoned
+        how = self.r(3 if nowait else 5)
+        if how == 2 and self.cfg["custom"]:    # (a custom context refuses the hand-over in HBM)
+            how = 1
+        if how == 0:
+            self.emit("upload", asynchronous=True, **p)
+        elif how == 1:
+            self.emit("prefetch", src="pinned", **p)
+            self.emit("commit")
+        elif how == 2:
+            self.emit("stage", **p)
+            self.emit("commit")
+        elif how == 3:
+            self.emit("prefetch", src="pageable", **p)
+            self.emit("commit")
+        else:
+            self.emit("upload", asynchronous=False, **p)
+
+    def accum_epoch(self, plan, first, nowait=False, finish="end", set_lb=False, full=False, between=None, sigma=None):
+        """begin, one load and one chunk call per entry of plan -- (chunk, "plain" / "rows" / "one_mask") --, between[i]()
+        behind chunk call i, then end / abort.  The masked chunks of an epoch share its seed and count up k (accum_mask);
+        their rows are the poisoned ones."""
+        seed = self.r(1 << 30)
+        self.emit("accum_begin", sigma=self.sigma() if sigma is None else sigma, first=bool(first),
+                  total=int(sum(self.sizes[c] for c, _ in plan)))
+        k = 0
+        for i, (chunk, kind) in enumerate(plan):
+            p = None
+            if kind != "plain":
+                p = dict(seed=seed, form=kind, k=k)
+                if full and kind == "rows" and not any(kd == "rows" for _, kd in plan[:i]):
+                    p["full"] = True
+            self.load(chunk, nowait, poisoned=p)
+            if set_lb:
+                self.emit("set_last_bmu", seed=self.r(1 << 30))
+            if kind == "plain":
+                self.emit("accum_chunk")
+            else:
+                self.emit("accum_chunk_masked", **p)
+                k += 1
+            if between and i in between:
+                between[i]()
+        if finish:
+            self.emit("accum_" + finish)
+
+    def first_for(self, plan):
+        """is_first of an epoch with this plan: drawn, but 0 where it has a masked chunk (the model's full masked search
+        is its dearest op: run 1 alone pays for it)"""
+        return bool(self.r(2)) and all(kind == "plain" for _, kind in plan)
+
+    def masked_kind(self):
+        return ["rows", "one_mask"][self.r(2)]
+
+    def any_maskable(self, first=False):
+        m = maskable(self.cfg, first)
+        return m[self.r(len(m))]
+
+    def clean_chunk(self):
+        """(a poisoned chunk must not stay current: the other ops would read its NaN)"""
+        self.emit("upload", chunk=self.small(), asynchronous=False)
+
+    def random_epoch(self):
+        if self.pending is not None:
+            self.emit("commit")
+        plan = []
+        for _ in range(1 + self.r(3)):
+            if self.r(10) < 3:
+                plan.append((self.any_maskable(), self.masked_kind()))
+            else:
+                plan.append((self.small(), "plain"))
+        first = self.first_for(plan)
+        self.accum_epoch(plan, first, set_lb=not first and bool(self.r(2)), finish="end" if self.r(4) else "abort")
+        self.clean_chunk()
+
+    def accum_run(self, run):
+        cfg = self.cfg
+        if self.pending is not None:
+            self.emit("commit")
+        if self.mode != self.walk_mode:
+            self.emit("sigma_mode", mode=self.walk_mode)
+        self.emit("upload", chunk=self.small(), asynchronous=False)
+        self.emit("run", id=run)
+        order = [int(i) for i in np.argsort(self.sizes, kind="stable")]
+        if run == 1:
+            short = [int(c) for c in self.rs.permutation(maskable(cfg, True))]      # no chunk twice in a row
+            kinds = ["rows", self.masked_kind(), self.masked_kind()]
+            self.rs.shuffle(kinds)
+            plan = [(short[i % len(short)], kinds[i]) for i in range(3)]
+            self.accum_epoch(plan, True, nowait=True, full=True)
+        elif run == 2:
+            a, b = sorted(self.rs.choice(len(order) - 1, 2, replace=False))
+            plan = [(order[a], "plain"), (order[b], "plain"), (order[-1], "plain")]
+
+            def topk():
+                n = min(64, self.B)
+                r0 = self.r(self.B - n + 1)
+                self.emit("topk", k=8, r0=r0, r1=r0 + n)
+            self.accum_epoch(plan, True, nowait=True, between={1: topk})
+        elif run == 3:
+            plan = [(self.small(), "plain"), (self.any_maskable(), self.masked_kind()), (self.small(), "plain")]
+            self.accum_epoch(plan, False, set_lb=True)
+        elif run == 4:
+            plan = [(self.small(), "plain") for _ in range(2 + self.r(2))]
+            plan[self.r(len(plan))] = (self.any_maskable(), self.masked_kind())
+            self.accum_epoch(plan, False, finish="abort")
+            self.emit("get_state")
+            self.accum_epoch([(self.small(), "plain") for _ in range(1 + self.r(2))], bool(self.r(2)))
+        elif run == 5:
+            short = order[0]
+            total = self.B + self.sizes[short]
+            self.emit("epoch_async", sigma=self.sigma(), first=bool(self.r(2)))
+            self.emit("prefetch", chunk=short, src=["pinned", "pageable"][self.r(2)])
+            self.emit("accum_begin", sigma=self.sigma(), first=True, total=total)
+            self.emit("accum_chunk")           # refused where the prefetch was staged ahead; else it takes the old chunk
+            self.emit("commit")
+            self.emit("accum_chunk")
+            self.emit("accum_abort")           # (rows are missing where the first chunk call was refused)
+        elif run == 6:
+            for name in ("accum_chunk", "accum_end", "accum_abort"):
+                self.emit(name)                # no epoch is open
+            self.emit("accum_chunk_masked", seed=0, form="rows", k=0, null=True)
+            if not cfg["custom"]:              # (a custom context refuses the contracted modes themselves)
+                self.emit("update_mode", mode=UPDATE_FMA)
+                self.emit("accum_begin", sigma=self.sigma(), first=True, total=self.B)
+                self.emit("update_mode", mode=UPDATE_STRICT)
+            self.emit("accum_begin", sigma=self.sigma(), first=True, total=0)       # the empty epoch
+            self.emit("accum_end")
+            self.emit("get_state")
+            self.emit("set_state", seed=self.r(1 << 30), parts="msw")
+            c1, c2, big = self.small(), order[0], order[-1]
+            self.emit("accum_begin", sigma=self.sigma(), first=True, total=self.sizes[c1] + self.sizes[c2])
+            self.emit("accum_begin", sigma=self.sigma(), first=True, total=7)       # an epoch is open
+            self.load(c1)
+            self.emit("accum_chunk")
+            self.emit("accum_chunk_masked", seed=0, form="rows", k=0, null=True)
+            self.emit("upload_empty")
+            self.emit("accum_chunk")           # an empty chunk: accepted, changes nothing
+            self.load(big)
+            self.emit("accum_chunk")           # more rows than are missing
+            self.emit("accum_end")             # rows are missing: refused, the epoch stays open
+            self.load(c2)
+            self.emit("accum_chunk")
+            self.emit("accum_end")
+        elif run == 7:
+            self.pending_epoch(("epoch_async",))
+            plan = [(self.small(), "plain") for _ in range(1 + self.r(2))]
+            self.accum_epoch(plan, bool(self.r(2)))
+        elif run == 8:
+            sg = self.sigma()
+            other = self.sigma()
+            while other == sg:
+                other = self.sigma()
+
+            def rewrite():
+                self.emit("set_state", seed=self.r(1 << 30), parts="map")
+                self.emit("single", seed=self.r(1 << 30), eta=0.1, sigma=other, decay=self.r(2), last=self.r(self.N))
+            plan = [(self.small(), "plain"), (self.any_maskable(), self.masked_kind()) if self.r(2) else (self.small(), "plain")]
+            self.accum_epoch(plan, self.first_for(plan), between={0: rewrite}, sigma=sg)
+        elif run == 9:
+            def queries():
+                for what in MASKED_SCORES + ("bmu_masked", "bmd", READERS[self.r(len(READERS))]):
+                    self.query(what)
+            plan = [(self.small(), "plain"), (self.any_maskable(), self.masked_kind()) if self.r(2) else (self.small(), "plain")]
+            self.accum_epoch(plan, self.first_for(plan), between={0: queries})
+        self.emit("run_end", id=run)
+        self.clean_chunk()
+        self.emit("get_state")
 
     # ---- the sigma profile ----
     def window(self):
@@ -328,6 +644,10 @@ class _Gen:
             self.emit(what, min_hits=self.r(2), rule=self.r(2), seed=seed, **self.window())
         elif what == "evaluate":
             self.emit(what, seed=seed, **self.window())
+        elif what == "similarity_masked":
+            self.emit(what, min_hits=self.r(2), rule=self.r(2), seed=seed, form=self.masked_kind(), **self.window())
+        elif what == "evaluate_masked":
+            self.emit(what, min_hits=self.r(2), seed=seed, form=self.masked_kind(), **self.window())
         elif what == "topk":
             self.emit(what, k=1 + self.r(8), **self.window())
         elif what == "decode_nodes":
@@ -460,8 +780,35 @@ def generate_sigma(cfg_name, seed, n_ops, scale, mode):
     return g.ops
 
 
+def generate_accum(cfg_name, seed, n_ops, scale, mode):
+    """The accum profile: n_ops random draws (the sigma profile's ops, whole accumulated epochs, stray accum calls, the
+    masked scoring calls) around the nine runs of the module docstring, each between its markers.  The walk opens with the
+    one refusal that needs a context without a chunk."""
+    assert mode in ("lazy", "auto"), mode
+    g = _Gen(cfg_name, seed, scale, "accum", mode)
+    g.ops.append(("config", {"name": cfg_name, "seed": seed, "scale": scale, "profile": "accum", "mode": mode}))
+    g.emit("sigma_mode", mode=mode)
+    g.emit("set_state", seed=seed, parts="init")
+    g.emit("run", id=6)
+    g.emit("accum_begin", sigma=g.sigma(), first=True, total=g.sizes[0])
+    g.emit("accum_chunk")                  # no chunk loaded
+    g.emit("accum_abort")
+    g.emit("run_end", id=6)
+    g.emit("upload", chunk=0, asynchronous=False)
+    slots = sorted(g.rs.choice(np.arange(1, n_ops), len(RUNS), replace=False))
+    runs = [int(r) for r in g.rs.permutation(RUNS)]
+    for k in range(n_ops):
+        if slots and k >= slots[0]:
+            slots.pop(0)
+            g.accum_run(runs.pop(0))
+        g.random_op()
+    g.emit("get_state")
+    return g.ops
+
+
 def generate(cfg_name, seed, n_ops=40, scale=1, profile="ingest", mode="lazy"):
-    """A walk of about n_ops ops.  profile="sigma": generate_sigma, in `mode` ("lazy" / "auto").  profile="ingest": by
+    """A walk of about n_ops ops.  profile="sigma": generate_sigma, in `mode` ("lazy" / "auto").  profile="accum":
+    generate_accum, with n_ops random draws around its runs.  profile="ingest": by
     construction it holds each of these runs with no synchronising call inside:
     async epoch -> online chunk (mse NULL) -> prefetch / stage_next_device -> commit;
     phase-2 range -> prefetch -> phase-2 range(s) -> commit (where a prefetch stages ahead: a lane = node range, a short
@@ -469,6 +816,8 @@ def generate(cfg_name, seed, n_ops=40, scale=1, profile="ingest", mode="lazy"):
     async epoch -> prefetch -> prefetch (an abandoned stage-ahead) -> search -> commit."""
     if profile == "sigma":
         return generate_sigma(cfg_name, seed, n_ops, scale, mode)
+    if profile == "accum":
+        return generate_accum(cfg_name, seed, n_ops, scale, mode)
     assert profile == "ingest", profile
     g = _Gen(cfg_name, seed, scale)
     g.ops.append(("config", {"name": cfg_name, "seed": seed, "scale": scale}))
@@ -542,7 +891,21 @@ def materialize(op, model):
     cfg = CONFIGS[model.cfg_name]
     N, B = model.N, model.B
     if name in ("upload", "prefetch", "stage"):
-        return {"X": model.chunks[p["chunk"]]}
+        return {"X": model.rows(p)}
+    if name == "accum_chunk_masked":
+        if p.get("null"):
+            return {"valid": None}
+        X = model.X if model.X is not None else np.zeros((0, cfg["J"]), np.float32)
+        return {"valid": np.ascontiguousarray(accum_mask(p["seed"], p["k"], p["form"], p.get("full", False), X), np.uint8)}
+    if name in MASKED_SCORES:
+        rs = np.random.RandomState(p["seed"])
+        Xw = model.X[p["r0"]:p["r1"]]
+        if p["form"] == "one_mask":
+            valid = (rs.rand(cfg["J"]) < 0.8) & np.isfinite(Xw).all(axis=0)
+        else:
+            valid = (rs.rand(*Xw.shape) < 0.8) & np.isfinite(Xw)
+        binary = (rs.rand(cfg["J"]) < 0.3).astype(np.float32)
+        return {"valid": valid.astype(np.uint8), "binary": binary, "continuous": (1 - binary).astype(np.float32)}
     if name == "single":
         rs = np.random.RandomState(p["seed"])
         X = model.chunks[rs.randint(len(model.chunks))]
@@ -585,7 +948,10 @@ class SigmaRecord:
     epochs since the last call that may have read sigmaMap, whether a record is pending, and vsom_sigma_stats' counters.
     Two points the header leaves open are pinned to what csrc/vsom_capi.hip and launch_phase2 do: a partial phase-2 range
     materialises without counting as a read (the header lists it among the calls that never read sigmaMap), and a refused
-    call that is not on the keep list counts as a read (the header: it "may")."""
+    call that is not on the keep list counts as a read (the header: it "may").  The vsom_batch_accum_* calls are ordinary
+    entry points here, as the header says of them: none is on the keep list, so the first materialises a pending record
+    (and resets AUTO's count, like every such call); none is a whole-map epoch, so none defers, drops or counts towards
+    AUTO's rule; vsom_batch_accum_end writes sigmaMap eagerly (Model._accum_end)."""
 
     def __init__(self, cfg):
         self.can_defer = defers(cfg) and not cfg["custom"] and cfg["tr"] != po.CLR
@@ -621,7 +987,7 @@ class SigmaRecord:
             if self.pending and p["n1"] > p["n0"]:     # a partial range materialises (and is no read)
                 self.pending = False
                 self.materialised += 1
-        elif name not in SIGMA_KEEP:
+        elif name not in SIGMA_KEEP and name not in ACCUM_KEEP:
             self.read()
 
     def refused(self, op, got):
@@ -630,7 +996,7 @@ class SigmaRecord:
         read the counters cannot show when nothing was pending: the model takes it as one, as the library's entry check
         does (include/vsom_hip.h allows both); were that to change, the AUTO walks would report a deferral one epoch off."""
         before = self.stats()
-        if op[0] not in SIGMA_KEEP:
+        if op[0] not in SIGMA_KEEP and op[0] not in ACCUM_KEEP:
             self.unread = 0
         if tuple(got) == before:
             return True
@@ -649,7 +1015,10 @@ class Model:
         self.cfg_name, self.cfg, self.profile = cfg_name, cfg, profile
         self.som = po.OracleSom(cfg["W"], cfg["H"], cfg["J"], cfg["tr"])
         self.N = cfg["W"] * cfg["H"]
-        self.chunks = chunk_data(cfg_name, seed, scale)
+        self.chunks = chunk_data(cfg_name, seed, scale, profile)
+        self.poisoned = {}                     # rows(): the poisoned copies made so far
+        self.acc = None                        # the open accumulated epoch (_accum_begin)
+        self.update_mode = UPDATE_STRICT
         self.X = None
         self.lb = np.zeros(0, np.uint64)
         self.sq = np.zeros(0, np.float32)      # the oracle's per-sample residuals of the last phase 1 (the finish sums them)
@@ -665,6 +1034,17 @@ class Model:
 
     def close(self):
         self.som.close()
+
+    def rows(self, p):
+        """the rows a load op names: the chunk, or (p["poisoned"]: the masked chunk call they are loaded for) that chunk
+        with NaN / +-inf under every invalid entry of that call's mask"""
+        if "poisoned" not in p:
+            return self.chunks[p["chunk"]]
+        q = p["poisoned"]
+        key = (p["chunk"], q["seed"], q["k"], q["form"], q.get("full", False))
+        if key not in self.poisoned:
+            self.poisoned[key] = poisoned_rows(self.chunks[p["chunk"]], *key[1:])
+        return self.poisoned[key]
 
     def _load(self, X):
         self.X = X
@@ -701,11 +1081,108 @@ class Model:
         self.sqres = None
         return mse
 
+    # ---- the accumulated epoch (include/vsom_hip.h, vsom_batch_accum_begin / vsom_batch_accum_chunk_masked) ----
+    def accum_refusal(self, op, staged=False):
+        """None where the header accepts the call, else words of the refusal it must get, in the order csrc/vsom_capi.hip
+        checks; staged: the backend has the next chunk staged ahead over the current rows (the model cannot know)"""
+        name, p = op
+        acc = self.acc
+        if name == "accum_begin":
+            if self.cfg["custom"]:
+                return "vsom_batch_accum_begin is not available on a custom-transformation context"
+            if self.cfg["tr"] == po.CLR:
+                return "CLR"
+            if self.update_mode != UPDATE_STRICT:
+                return "strict update mode"
+            return "already open" if acc is not None else None
+        if name == "accum_chunk_masked" and p.get("null"):
+            return "valid_host is null"
+        if acc is None:
+            return "no accumulated epoch is open"
+        if name in ("accum_chunk", "accum_chunk_masked"):
+            if staged:
+                return "vsom_commit_chunk first"
+            if self.X is None:
+                return "no chunk loaded"
+            if acc["rows"] + self.B > acc["total"]:
+                return "exceed total_rows"
+        elif name == "accum_end" and acc["rows"] != acc["total"]:
+            return "rows accumulated"
+        return None
+
+    def _accum_chunk(self, valid):
+        """phase 1 of the current chunk against the current map, hits, the running MSE over total_rows; the chunk's rows,
+        validity (None: a plain chunk, all valid) and lastBMU join the epoch's record"""
+        acc, s, cfg, B = self.acc, self.som, self.cfg, self.B
+        if B == 0:
+            return
+        if valid is None:
+            v = np.ones(self.X.shape, bool)
+            s.batch_phase1_range(self.X, 0, B, self.lb, self.sq, acc["first"], nthreads=NTHREADS)
+        else:
+            v = np.broadcast_to(np.asarray(valid) != 0, self.X.shape).copy()
+            lb, sq = masked_train_ref.phase1(cfg["tr"], cfg["W"], cfg["H"], s.map, self.X, v, self.lb, acc["first"])
+            self.lb[...] = lb
+            self.sq[...] = sq
+        s.batch_phase1_finish(self.lb, self.sq)        # bmuHits (its MSE is the chunk's own, not the epoch's)
+        run, div = acc["run"], np.float32(acc.get("divisor", acc["total"]))
+        with np.errstate(all="ignore"):
+            for q in self.sq:
+                run = np.float32(run + np.float32(q / div))
+        acc["run"] = self.mse = run
+        self.sqres = self.sq.copy()
+        acc["parts"].append((self.X, v, self.lb.copy()))
+        acc["rows"] += B
+
+    def accum_phase2(self, acc):
+        """(map, sigmaMap, weightMap) of vsom_batch_accum_end: the oracle's phase 2 over the concatenated rows; every column
+        that had an invalid entry from the per-column restatement (tests/masked_train_ref.py, phase2).  What the rows hold
+        at an invalid position is replaced by 0 first: it may reach no output."""
+        cfg, J = self.cfg, self.cfg["J"]
+        parts = acc["parts"]
+        X = np.concatenate([x for x, _, _ in parts]) if parts else np.zeros((0, J), np.float32)
+        valid = np.concatenate([v for _, v, _ in parts]) if parts else np.zeros((0, J), bool)
+        lb = np.ascontiguousarray(np.concatenate([b for _, _, b in parts]) if parts else np.zeros(0), np.uint64)
+        X = np.ascontiguousarray(np.where(valid, X, np.float32(0)), np.float32)
+        t = po.OracleSom(cfg["W"], cfg["H"], J, cfg["tr"])
+        t.batch_phase2_range(X, lb, acc["sigma"], 0, self.N, nthreads=NTHREADS)
+        newmap, newsig, weight = t.map.copy(), t.sigma.copy(), t.weight.copy()
+        t.close()
+        dirty = np.flatnonzero(~valid.all(axis=0))
+        if dirty.size:
+            m, sg, _ = masked_train_ref.phase2(cfg["tr"], cfg["W"], cfg["H"], X[:, dirty], valid[:, dirty], lb, acc["sigma"])
+            newmap[:, dirty] = m
+            newsig[:, dirty] = sg
+        return newmap, newsig, weight
+
+    def _accum(self, op, a):
+        name, p = op
+        if name == "accum_begin":
+            # (phase 2 never reads the map and abort writes nothing: the state at begin need not be kept)
+            self.acc = dict(sigma=p["sigma"], first=p["first"], total=p["total"], rows=0, run=np.float32(0), parts=[])
+        elif name == "accum_chunk":
+            self._accum_chunk(None)
+        elif name == "accum_chunk_masked":
+            self._accum_chunk(a["valid"])
+        elif name == "accum_end":
+            newmap, newsig, weight = self.accum_phase2(self.acc)
+            self.som.set_state(map=newmap, sigma=newsig, weight=weight)       # S is untouched
+            self.mse = self.acc["run"]
+            self.acc = None
+            return {"mse": self.mse}
+        else:                                  # abort: the model state stays; hits, lastBMU, sqres, the MSE word too
+            self.acc = None
+        return {}
+
     def apply(self, op, a):
         """the op's effect; returns the outputs the call must give"""
         name, p = op
         s = self.som
-        if name in ("upload", "upload_empty"):
+        if name in ACCUM_OPS:
+            return self._accum(op, a)
+        if name == "update_mode":
+            self.update_mode = p["mode"]
+        elif name in ("upload", "upload_empty"):
             self._load(a["X"])
         elif name == "epoch_masked":
             self.mse = self._epoch_masked(p, a["valid"])
@@ -822,10 +1299,14 @@ def run_walk(ops, make_backend):
     the ops up to the failing one and the first differing element.  Returns counts of what happened."""
     name0, cfg = ops[0]
     assert name0 == "config", ops[0]
-    sigma = cfg.get("profile", "ingest") == "sigma"
+    sigma = cfg.get("profile", "ingest") in ("sigma", "accum")
     model = Model(cfg["name"], cfg["seed"], cfg.get("scale", 1), cfg.get("profile", "ingest"))
+    model.ops = ops                        # (the real backend makes its pinned and device copies of the rows up front)
     be = make_backend(cfg["name"], model)
     stats = {"ops": 0, "refused": 0}
+    if model.profile == "accum":
+        stats["accum"] = {"chunks": 0, "masked": 0, "ends": 0, "aborts": 0, "staged": 0}
+    run = None                             # the run of generate_accum the walk is in
     done = [ops[0]]
 
     def fail(msg):
@@ -859,47 +1340,111 @@ def run_walk(ops, make_backend):
             fail(f"{op[0]}: vsom_sigma_stats = {got}, the header's contract gives {model.sig.stats()} "
                  f"(deferred, dropped, materialised, pending)")
 
-    try:
-        for op in ops[1:]:
+    def check(op, a, rc, msg, out):
+        """one call's return against the model; the model then makes the call"""
+        name, p = op
+        stats["ops"] += 1
+        if out.get("twin_diff"):
+            fail(f"{name}: {out['twin_diff']}")
+        if model.cfg["custom"] and name in CUSTOM_REFUSED:
+            if rc != VSOM_ERR_INVALID:
+                fail(f"{name} on a custom context returned {rc}, not VSOM_ERR_INVALID")
+            return check_sigma(op, out, True)
+        if model.cfg["tr"] == po.CLR and name in CLR_REFUSED:
+            if rc != VSOM_ERR_INVALID:
+                fail(f"{name} on a CLR context returned {rc}, not VSOM_ERR_INVALID")
+            return check_sigma(op, out, True)
+        if model.cfg["tr"] == po.CLR and name == "distances_raw" and not p["from_map"]:
+            # (Som::euclidianWeightedDistRaw against a sample needs depth == sample length: csrc/vsom_bmu.hip)
+            if rc != VSOM_ERR_UNSUPPORTED:
+                fail(f"{name} against chunk rows on a CLR context returned {rc}, not VSOM_ERR_UNSUPPORTED")
+            return check_sigma(op, out, True)
+        if name == "commit" and model.pending is None:
+            if rc != VSOM_ERR_INVALID:
+                fail(f"commit with nothing pending returned {rc}")
+            return check_sigma(op, out, True)
+        staged = rc == VSOM_ERR_INVALID and "commit" in msg and model.refusal_allowed(name, p)
+        if name in ACCUM_OPS:
+            why = model.accum_refusal(op)
+            # (a chunk staged ahead is checked before the chunk and its rows)
+            if why is not None and not (staged and why in ("no chunk loaded", "exceed total_rows")):
+                if rc != VSOM_ERR_INVALID or why not in msg:
+                    fail(f"{name} returned {rc} {msg!r}: the header refuses it ({why})")
+                check_sigma(op, out, True)
+                check_all(f"{name} refused ({why})")      # a refused call leaves everything as it was
+                model.sig.read()                          # (vsom_get_state)
+                return
+            # run 5: where a prefetch right behind an asynchronous epoch stages ahead, the first chunk call of the epoch
+            # opened behind it must be refused for the chunk staged ahead
+            if run == 5 and stages_ahead(model.cfg) and name == "accum_chunk" and model.pending is not None and \
+                    not (staged and "vsom_commit_chunk first" in msg):
+                fail(f"{name} behind epoch_async, prefetch, begin returned {rc} {msg!r}: the next chunk is staged ahead over "
+                     f"the current rows, the header refuses it (vsom_commit_chunk first)")
+        if rc != 0:
+            if staged:
+                if run is not None and run != 5:
+                    fail(f"{name} was refused inside run {run}, whose calls the header accepts: {msg}")
+                stats["refused"] += 1
+                check_sigma(op, out, True)
+                if name in ACCUM_OPS:                     # as after every refusal of these calls
+                    stats["accum"]["staged"] += 1
+                    check_all(f"{name} refused (a chunk staged ahead)")
+                    model.sig.read()
+                return
+            fail(f"{name} failed: {rc} {msg}")
+        model.sig.accepted(op, model.B, model.N)
+        exp = model.apply(op, a)
+        check_outputs(name, out, exp)
+        check_sigma(op, out, False)
+        if name in ("accum_chunk", "accum_chunk_masked") and model.B:
+            stats["accum"]["chunks"] += 1
+            stats["accum"]["masked"] += name == "accum_chunk_masked"
+        elif name in ("accum_end", "accum_abort"):
+            stats["accum"][name[6:] + "s"] += 1
+        # (the full state is read through vsom_get_state, which materialises: in the sigma profile only where the
+        # op itself has just done so)
+        if name in OBSERVE and (not sigma or name == "get_state"):
+            check_all(name)
+
+    def back_to_back(batch):
+        """A no-wait run on a backend that can separate its first context from the twin (call_first / call_twin): every
+        call of the run goes to the first context before the twin or the model sees one of them, so nothing but the
+        calls' own host work stands between them.  The arguments come from a shadow of the model that follows the loads
+        alone (a mask depends on the chunk's rows, not on the model's state); then the twin and the model replay the run,
+        each call's return held against them."""
+        shadow = copy.copy(model)
+        made = []
+        for op in batch:
+            a = materialize(op, shadow)
+            made.append((op, a) + tuple(be.call_first(op, a)))
+            if made[-1][2] == 0 and op[0] in ("upload", "prefetch", "stage", "commit"):
+                shadow.apply(op, a)
+        for op, a, rc, msg, out in made:
             done.append(op)
+            be.call_twin(op, a, rc, msg, out)
+            check(op, a, rc, msg, out)
+
+    try:
+        todo = list(ops[1:])
+        while todo:
+            op = todo.pop(0)
             name, p = op
+            if name in ("run", "run_end"):     # markers of generate_accum: no call
+                done.append(op)
+                run = p["id"] if name == "run" else None
+                # (not where begin is refused: the whole-state comparison behind a refusal must follow its call at once)
+                if run in NO_WAIT_RUNS and hasattr(be, "call_first") and accepts_accum(model.cfg):
+                    n = [o[0] for o in todo].index("run_end")
+                    back_to_back(todo[:n])
+                    del todo[:n]
+                continue
+            done.append(op)
             a = materialize(op, model)
             rc, msg, out = be.call(op, a)
-            stats["ops"] += 1
-            if out.get("twin_diff"):
-                fail(f"{name}: {out['twin_diff']}")
-            if model.cfg["custom"] and name in CUSTOM_REFUSED:
-                if rc != VSOM_ERR_INVALID:
-                    fail(f"{name} on a custom context returned {rc}, not VSOM_ERR_INVALID")
-                check_sigma(op, out, True)
-                continue
-            if model.cfg["tr"] == po.CLR and name in CLR_REFUSED:
-                if rc != VSOM_ERR_INVALID:
-                    fail(f"{name} on a CLR context returned {rc}, not VSOM_ERR_INVALID")
-                check_sigma(op, out, True)
-                continue
-            if name == "commit" and model.pending is None:
-                if rc != VSOM_ERR_INVALID:
-                    fail(f"commit with nothing pending returned {rc}")
-                check_sigma(op, out, True)
-                continue
-            if rc != 0:
-                if rc == VSOM_ERR_INVALID and "commit" in msg and model.refusal_allowed(name, p):
-                    stats["refused"] += 1
-                    check_sigma(op, out, True)
-                    continue
-                fail(f"{name} failed: {rc} {msg}")
-            model.sig.accepted(op, model.B, model.N)
-            exp = model.apply(op, a)
-            check_outputs(name, out, exp)
-            check_sigma(op, out, False)
-            # (the full state is read through vsom_get_state, which materialises: in the sigma profile only where the
-            # op itself has just done so)
-            if name in OBSERVE and (not sigma or name == "get_state"):
-                check_all(name)
+            check(op, a, rc, msg, out)
         check_all("end of walk")
         if sigma and hasattr(be, "observe_twin"):
-            check_all("end of walk, the EAGER twin", be.observe_twin)
+            check_all("end of walk, the EAGER twin", be.observe_twin)     # (accum profile: EAGER and sequential)
     finally:
         be.close()
         model.close()
@@ -925,7 +1470,10 @@ class GpuBackend:
             make = lambda: vsom_amd.Context(cfg["W"], cfg["H"], cfg["J"], cfg["tr"])
         self.ctx = make()
         # sigma profile: a second context fixed at VSOM_SIGMA_EAGER that receives every call of the walk
-        self.sigma = model.profile == "sigma"
+        # accum profile: that twin is also the sequential one -- fed from pageable memory, synchronised after every call
+        self.sigma = model.profile in ("sigma", "accum")
+        self.accum = model.profile == "accum"
+        self.custom = cfg["custom"]
         self.twin = None
         if self.sigma:
             self.twin = make()
@@ -935,41 +1483,67 @@ class GpuBackend:
         # hipMalloc + hipMemcpy) would synchronise the device and hide the asynchrony the walk is about
         self.hip = C.CDLL("libamdhip64.so")
         self.pinned, self.dev = [], []
+        self.pinned_poisoned, self.dev_poisoned = {}, {}
         for X in model.chunks:
-            pb = capi.PinnedBuffer(X.shape)
-            pb.array[...] = X
+            pb, ptr = self._copies(X)
             self.pinned.append(pb)
-            ptr = C.c_void_p()
-            assert self.hip.hipMalloc(C.byref(ptr), C.c_size_t(max(X.nbytes, 4))) == 0
-            assert self.hip.hipMemcpy(ptr, X.ctypes.data_as(C.c_void_p), C.c_size_t(X.nbytes), C.c_int(1)) == 0
             self.dev.append(ptr)
+        for name, p in getattr(model, "ops", ()):      # the poisoned rows of every masked chunk call of the walk
+            if "poisoned" in p and self._key(p) not in self.pinned_poisoned:
+                self.pinned_poisoned[self._key(p)], self.dev_poisoned[self._key(p)] = self._copies(model.rows(p))
+
+    @staticmethod
+    def _key(p):
+        return (p["chunk"],) + tuple(sorted(p["poisoned"].items()))
+
+    def _copies(self, X):
+        pb = self.capi.PinnedBuffer(X.shape)
+        pb.array[...] = X
+        ptr = C.c_void_p()
+        assert self.hip.hipMalloc(C.byref(ptr), C.c_size_t(max(X.nbytes, 4))) == 0
+        assert self.hip.hipMemcpy(ptr, X.ctypes.data_as(C.c_void_p), C.c_size_t(X.nbytes), C.c_int(1)) == 0
+        return pb, ptr
 
     def close(self):
         self.ctx.close()
         if self.twin is not None:
             self.twin.close()
-        for pb in self.pinned:
+        for pb in self.pinned + list(self.pinned_poisoned.values()):
             pb.free()
-        for p in self.dev:
+        for p in self.dev + list(self.dev_poisoned.values()):
             self.hip.hipFree(p)
 
     def call(self, op, a):
+        rc, msg, out = self.call_first(op, a)
+        self.call_twin(op, a, rc, msg, out)
+        return rc, msg, out
+
+    def call_first(self, op, a):
+        """the call on the first context alone (and vsom_sigma_stats, which reads host counters)"""
         rc, msg, out = self._call(self.ctx, op, a)
         if self.sigma:
-            name = op[0]
-            trc, _, tout = self._call(self.twin, op, a)
+            out["sigma_stats"] = tuple(self.ctx.sigma_stats()[k] for k in ("deferred", "dropped", "materialised", "pending"))
+        return rc, msg, out
+
+    def call_twin(self, op, a, rc, msg, out):
+        """the same call on the twin, compared with what the first context returned (out["twin_diff"])"""
+        name = op[0]
+        # The sequential twin never has a chunk staged ahead (vsom_synchronize ends the window in which a prefetch stages
+        # ahead), so a call the first context refuses for one is not made on the twin: it changes nothing on either.
+        if self.accum and rc == VSOM_ERR_INVALID and name in READS_ROWS and "vsom_commit_chunk first" in msg:
+            return
+        if self.sigma:
+            trc, _, tout = self._call(self.twin, op, a, twin=self.accum)
             if name == "sigma_mode":                   # (the twin stays eager)
                 self.twin.set_sigma_mode(SIGMA_EAGER)
             if trc != rc:
                 out["twin_diff"] = f"returned {rc}, the EAGER twin {trc}"
-            elif rc == 0 and name in TWIN_COMPARED:
+            elif rc == 0 and name in (ACCUM_TWIN_COMPARED if self.accum else TWIN_COMPARED):
                 for k in tout:
                     d = first_difference_exact(out.get(k), tout[k])
                     if d:
                         out["twin_diff"] = f"output {k!r} differs from the EAGER twin's at {d}"
                         break
-            out["sigma_stats"] = tuple(self.ctx.sigma_stats()[k] for k in ("deferred", "dropped", "materialised", "pending"))
-        return rc, msg, out
 
     def _wrapped(self, fn, *args, **kw):
         """a call through the Python wrapper: (rc, what it returned as a dict)"""
@@ -983,15 +1557,52 @@ class GpuBackend:
             res = {"r0": res}
         return 0, res
 
-    def _call(self, ctx, op, a):
+    def _call(self, ctx, op, a, twin=False):
+        """the call on ctx; twin: as the sequential twin makes it -- rows from pageable memory only (a blocking upload, a
+        prefetch from pageable memory, also for a chunk the walk hands over in HBM), vsom_synchronize behind the call"""
+        rc, msg, out = self._call1(ctx, op, a, twin)
+        if twin:
+            self.capi.check(self.L.vsom_synchronize(ctx._h))
+        return rc, msg, out
+
+    def _call1(self, ctx, op, a, twin):
         L, h, capi = self.L, ctx._h, self.capi
         f, u = capi._f, capi._u
         name, p = op
         out = {}
         B = int(L.vsom_chunk_size(h))
-        if name in ("similarity", "generate", "evaluate", "topk", "bmd", "bmu_masked"):
+        if name in ("similarity", "generate", "evaluate", "topk", "bmd", "bmu_masked") or name in MASKED_SCORES:
             w = dict(r0=p["r0"], r1=p["r1"])
-        if name == "sigma_mode":
+        if "poisoned" in p:                    # (one entry, under the chunk's index)
+            pinned = {p["chunk"]: self.pinned_poisoned[self._key(p)]}
+            dev = {p["chunk"]: self.dev_poisoned[self._key(p)]}
+        else:
+            pinned, dev = self.pinned, self.dev
+        # the five calls of the accumulated epoch go to the C ABI as they are: the wrapper copies and converts
+        if name == "accum_begin":
+            rc = L.vsom_batch_accum_begin(h, p["sigma"], int(p["first"]), p["total"])
+        elif name == "accum_chunk":
+            rc = L.vsom_batch_accum_chunk(h)
+        elif name == "accum_chunk_masked":
+            if a["valid"] is None:
+                rc = L.vsom_batch_accum_chunk_masked(h, None, 0)
+            else:
+                vb = a["valid"].copy()
+                rc = L.vsom_batch_accum_chunk_masked(h, vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(vb.ndim == 1))
+                vb[...] = 0                    # "not read after the call returns": the chunk is still in flight
+        elif name == "accum_end":
+            m = C.c_float()
+            rc = L.vsom_batch_accum_end(h, C.byref(m))
+            out["mse"] = np.float32(m.value)
+        elif name == "accum_abort":
+            rc = L.vsom_batch_accum_abort(h)
+        elif name == "update_mode":
+            rc = L.vsom_set_update_mode(h, p["mode"])
+        elif name == "similarity_masked":
+            rc, out = self._wrapped(ctx.similarity_masked, a["valid"], p["min_hits"], 2, p["rule"], delta=True, **w)
+        elif name == "evaluate_masked":
+            rc, out = self._wrapped(ctx.evaluate_masked, a["valid"], a["binary"], a["continuous"], p["min_hits"], **w)
+        elif name == "sigma_mode":
             rc = L.vsom_set_sigma_mode(h, SIGMA_MODES[p["mode"]])
         elif name == "sigma_flush":
             rc = L.vsom_sigma_flush(h)
@@ -1022,16 +1633,18 @@ class GpuBackend:
             rc, out = self._wrapped(ctx.bmu_masked, a["valid"], min_hits=p["min_hits"], fill=True, **w)
         elif name == "upload":
             X = a["X"]
-            if p["asynchronous"]:
-                X = self.pinned[p["chunk"]].array
+            if p["asynchronous"] and not twin:
+                X = pinned[p["chunk"]].array
                 rc = L.vsom_upload_chunk_async(h, f(X), X.shape[0])
             else:
                 rc = L.vsom_upload_chunk(h, f(X), X.shape[0])
         elif name == "prefetch":
-            X = a["X"] if p["src"] == "pageable" else self.pinned[p["chunk"]].array
+            X = a["X"] if p["src"] == "pageable" or twin else pinned[p["chunk"]].array
             rc = L.vsom_prefetch_chunk(h, f(X), X.shape[0])
+        elif name == "stage" and twin and not self.custom:        # (a custom context refuses the hand-over: the twin too)
+            rc = L.vsom_prefetch_chunk(h, f(a["X"]), a["X"].shape[0])
         elif name == "stage":
-            rc = L.vsom_stage_next_device(h, C.c_void_p(self.dev[p["chunk"]].value), a["X"].shape[0])
+            rc = L.vsom_stage_next_device(h, C.c_void_p(dev[p["chunk"]].value), a["X"].shape[0])
         elif name == "commit":
             rc = L.vsom_commit_chunk(h)
         elif name == "epoch_async":

@@ -7,7 +7,12 @@ The sigma profile's walks run against the same fake, which then also models the 
 the whole epoch and withholds the new sigmaMap / S rows, keeping what the library's record keeps (the epoch's rows, its
 lastBMU, its sigma); a materialisation computes them from that record, a drop discards it.  Mutants e-k break that
 bookkeeping the ways an entry point wrongly listed as keeping the record -- or a record made from the wrong operands --
-would.  The ingest walks themselves are pinned by digest: the generator's new ops must never enter their draws."""
+would.  The ingest walks themselves are pinned by digest: the generator's new ops must never enter their draws.
+
+The accum profile's walks (the accumulated batch epoch) run against the same fake, which keeps what the model keeps -- the
+open epoch's rows, validity and lastBMU -- on its own oracle.  Mutants l-r break it the ways hand-kept host state can be
+wrong between calls that do not block.  The sigma walks are pinned by digest too, and what the GPU test asserts of its
+walks' counts is checked here as a condition on the inputs."""
 import ast
 import copy
 import functools
@@ -39,7 +44,17 @@ class FakeBackend:
       h  a weight-only vsom_set_state is treated as keeping the record (the materialisation then divides by the new weight)
       i  AUTO defers after one unread epoch
       j  an empty-chunk epoch forgets the drop
-      k  vsom_set_last_bmu / vsom_get_mse count as a read"""
+      k  vsom_set_last_bmu / vsom_get_mse count as a read
+    and, in the accum profile (the accumulated epoch):
+      l  the accumulators restart with every chunk, so end gives the last chunk's batch map (what the reference does)
+      m  abort writes the partial accumulators as end would
+      n  the running MSE divides by the chunk's rows, not by total_rows
+      o  a plain chunk behind a masked one does not walk the columns dirty so far: those columns drop its rows
+      p  a refused end (rows missing) closes the epoch
+      q  the masked chunk reads its validity after the call returned, and sees the zeros the caller wrote there
+      r  begin does not clear the ever-dirty list: the next end writes those columns from the previous epoch's side
+         buffers
+      s  a chunk call does not look whether the next chunk is staged ahead over the current rows"""
 
     def __init__(self, cfg_name, model, mutant=None):
         self.m = cs.Model(model.cfg_name, 0)
@@ -52,7 +67,8 @@ class FakeBackend:
         self.ahead_rows = False
         self.deferred = None
         # the pending sigmaMap (sigma profile only: the ingest walks run the fake they always ran)
-        self.sigma_profile = model.profile == "sigma"
+        self.sigma_profile = model.profile in ("sigma", "accum")
+        self.stale = None                   # mutant r: (columns, their map and sigmaMap values) the last epoch left
         self.can_defer = cs.stages_ahead(self.cfg) and po.length(self.cfg["tr"], self.cfg["J"]) % 4 == 0
         self.mode = cs.SIGMA_AUTO
         self.unread = 0
@@ -95,7 +111,7 @@ class FakeBackend:
             return False
         if self.mutant == "h" and name == "set_state" and p["parts"] == "weight_only":
             return True
-        return name in cs.SIGMA_KEEP
+        return name in cs.SIGMA_KEEP or name in cs.ACCUM_KEEP
 
     def _whole(self, op):
         name, p = op
@@ -174,8 +190,12 @@ class FakeBackend:
             return cs.VSOM_ERR_INVALID, "not for a custom context", {}
         if self.cfg["tr"] == po.CLR and name in cs.CLR_REFUSED:
             return cs.VSOM_ERR_INVALID, "CLR contexts are not supported", {}
+        if self.cfg["tr"] == po.CLR and name == "distances_raw" and not p["from_map"]:
+            return cs.VSOM_ERR_UNSUPPORTED, "needs depth == sample length", {}
         if name == "commit" and m.pending is None:
             return cs.VSOM_ERR_INVALID, "no prefetched chunk to commit", {}
+        if name in cs.ACCUM_OPS:
+            return self._accum(op, a)
         keep_free = False
         if name in ("prefetch", "stage"):
             if self.rows_free and self.stage_ok:
@@ -219,6 +239,56 @@ class FakeBackend:
             self.rows_free = True
         elif not keep_free:
             self.rows_free = False
+        return 0, "", {k: v for k, v in out.items() if v is not None}
+
+    # ---- the accumulated epoch ----
+    @staticmethod
+    def _dirty(parts):
+        """the columns that had an invalid entry in these chunks"""
+        if not parts:
+            return np.zeros(0, np.int64)
+        return np.flatnonzero(~np.concatenate([v for _, v, _ in parts]).all(axis=0))
+
+    def _accum(self, op, a):
+        name, p = op
+        m = self.m
+        self.rows_free = False
+        why = m.accum_refusal(op, staged=self.ahead_rows and self.mutant != "s")
+        if why is not None:
+            if self.mutant == "p" and why == "rows accumulated":
+                m.acc = None
+            if self.mutant == "d":
+                m.som.train_single(m.chunks[0][0], 0.1, 1.0, 0, 0)
+            return cs.VSOM_ERR_INVALID, f"{name}: {why}", {}
+        chunk = name in ("accum_chunk", "accum_chunk_masked") and m.B > 0
+        if chunk and self.mutant == "l":
+            m.acc["parts"].clear()
+        if chunk and self.mutant == "n":
+            m.acc["divisor"] = m.B
+        if name == "accum_chunk_masked" and self.mutant == "q":
+            a = {"valid": np.zeros_like(a["valid"])}
+        if name == "accum_abort" and self.mutant == "m":
+            newmap, newsig, weight = m.accum_phase2(m.acc)
+            m.som.set_state(map=newmap, sigma=newsig, weight=weight)
+        stale = self.stale
+        if name in ("accum_end", "accum_abort") and self.mutant == "r":
+            dirty = self._dirty(m.acc["parts"])
+            if dirty.size:
+                newmap, newsig, _ = m.accum_phase2(m.acc)
+                self.stale = (dirty, newmap[:, dirty], newsig[:, dirty])
+        dirty_so_far = self._dirty(m.acc["parts"]) if name == "accum_chunk" and chunk else ()
+        out = self._apply(op, a)
+        if len(dirty_so_far) and self.mutant == "o":
+            X, v, lb = m.acc["parts"][-1]
+            v = v.copy()
+            v[:, dirty_so_far] = False
+            m.acc["parts"][-1] = (X, v, lb)
+        if name == "accum_end" and self.mutant == "r" and stale is not None:
+            cols, oldmap, oldsig = stale
+            newmap, newsig = m.som.map.copy(), m.som.sigma.copy()
+            newmap[:, cols] = oldmap
+            newsig[:, cols] = oldsig
+            m.som.set_state(map=newmap, sigma=newsig)
         return 0, "", {k: v for k, v in out.items() if v is not None}
 
     def observe(self):
@@ -532,3 +602,382 @@ class _NoStats(FakeBackend):
         else:
             out["sigma_stats"] = self.model.sig.stats()
         return rc, msg, out
+
+
+# sha256(repr(generate(cfg, seed, scale=scale, profile="sigma", mode=mode))) of the sigma walks, recorded before the accum
+# profile existed
+SIGMA_DIGESTS = {
+    ("std48", "lazy", 1, 1): "c5d42f13acfaa377e9a00984095e92b18d819da7c647f5aa00ca06983bdaa68a",
+    ("std48", "lazy", 2, 1): "ea71f358828c84e15a4d9b5341edc720c2d76f0378a050237ed218032b74f9be",
+    ("std48", "lazy", 3, 1): "1ccde8ea17863066e4ab9a5c0f3586bd3ab7e458f89cb2c55f37528dd69c7427",
+    ("std48", "auto", 1, 1): "e0e5337a98450315b41ad3d72c9bcd71cb33e78c5cb8fa64ac2beff89f27be20",
+    ("std48", "auto", 2, 1): "c3730d82aaeddf32ec4365cf329fc666de31f970619feae9be3a617f9c124833",
+    ("std48", "auto", 3, 1): "31a06209350fd0267dfc189d5d19d07e75ee5a4b3c7b297038a1b466f0907049",
+    ("med48", "lazy", 1, 1): "0fd7f96979deda441dfa30c2377f8bb595cf67f1f8d0d183bd3238f86c8e734c",
+    ("med48", "lazy", 2, 1): "cb77a5a918cf54ea98ec33e2be24ce9665c4bd1e054e6d337ce8bc020af198b8",
+    ("med48", "lazy", 3, 1): "6c0f26f12eb51ad190d1e0f65c956def18307ba29381c895a09ddd2762d96515",
+    ("med48", "auto", 1, 1): "50a3777947103fd31af40384e98b0ea80da40d1bea6affa9d8fe3a5604969ca1",
+    ("med48", "auto", 2, 1): "fe0ff1532e6c0971b455cde7c1210678acaa0def22ffdb02339280d5983c9621",
+    ("med48", "auto", 3, 1): "cb9e2718f31d71f97eb71733401b11a3254e6293aa3b2f35d9f5ac751af85233",
+    ("std12", "lazy", 1, 1): "e79b7998e40fef4abdabf5bb565543cba1add9a363be4f631a1a3a0a7da76dea",
+    ("std12", "lazy", 2, 1): "bf695fe6a6a200827bdcc24a7651d3b3970373da0e22547206d4658057b11796",
+    ("std12", "lazy", 3, 1): "f3f8a84e17f71de310a4be0cfd604ac223d654e2975419bb05b6205369b6aaaf",
+    ("std12", "auto", 1, 1): "d5ab1d2b06dc19ee822d372ccba86a663ede8d4fd0b1b421cc78ef8596632586",
+    ("std12", "auto", 2, 1): "bf2c36a846c1b75e90b36839bd0eb53ba14f75bfab45fd3acdc1f785b5a35108",
+    ("std12", "auto", 3, 1): "55d7bc9909abc4b1731abcf9c58fa8ddb4b2c8cbd754d6f23975c843502249f7",
+    ("clr12", "lazy", 1, 1): "7a73cee9ee7dc9991a49ba175e426e45467fa35127075abe80da3948ae5e61c5",
+    ("clr12", "lazy", 2, 1): "14d58a998c0a51fa7a1e1d174f47e1a3f3671e5226239ae580bfb691678ae272",
+    ("clr12", "lazy", 3, 1): "af7e7a6650b7f1c7cb5a2bcbd342965f3b7988a31e7886373a405b2ec514bf00",
+    ("clr12", "auto", 1, 1): "bb309f4ff1f46d00185f81ba17b8be00072ee35a786e290632aa7bcb3b6a72e7",
+    ("clr12", "auto", 2, 1): "61e0de3314664fa986a7840b444ef1b1134b47470fab32a0a8f26f5f71a37b79",
+    ("clr12", "auto", 3, 1): "6add8b6cc01fa270aa7e3dfb214571aa98396b9f07f86523d8296bd9e19e9268",
+    ("custom12", "lazy", 1, 1): "c92941cdfbf9ae526955ffc4f2605c527743a7b35d8b754e5e87ca87aa9c3a08",
+    ("custom12", "lazy", 2, 1): "72404b69a0cf314834a623a5d009044b1f2451a745512d47723c7939c1ba2935",
+    ("custom12", "lazy", 3, 1): "b4b49d838bd8b871f7bcf70f3e924ad6514040e4ee881dc7e6170a09afe20809",
+    ("custom12", "auto", 1, 1): "22f7d472a19eac7e8bc05ee8c8f8351c4df5ed7f3c0503445a51a8adf4cde2e0",
+    ("custom12", "auto", 2, 1): "7f1214e8de384dc553f607c1314fdbd36e2a1aff932095e27be549c0f04b5729",
+    ("custom12", "auto", 3, 1): "7f54bf87fedbc02899b01c53972a02bef30feebf0ec746da7277287aeec135b2",
+    ("std80", "lazy", 1, 1): "6fac3739f21ee8cb3042fe2f658abd93078516948206f36f4b4ceb51ac3e2add",
+    ("std80", "lazy", 2, 1): "3e06621520f90e42250498c2f84e336cce7e0ffe0dfe83245ec8ceb5bd1757dc",
+    ("std80", "lazy", 3, 1): "f40f03372042af2e257fff3487998b2b59d2d1cd9fb2aa4b0a90e8f0e6df5d2f",
+    ("std80", "auto", 1, 1): "f8e553a73eb237063893cf637604015de970033f7ad797d35b858f96a288f2a3",
+    ("std80", "auto", 2, 1): "62b58734f611bc4fd8c2b7332411772074dc41ccbd8689badd260e7f52f2d54c",
+    ("std80", "auto", 3, 1): "4cd4987e5df6cc9dccbd6b8ae05b168bf7e65fb9c65a38052fcc4734884c8099",
+    ("std48", "lazy", 1, 8): "4d1e67c0d9331b5a4a4912559b4d5390962e2d2261b39f818d5870037f82bd10",
+    ("std48", "lazy", 2, 8): "beed7556ae63a06765ea284c442c0d62de054547fda9523ea3371f165f3b01d7",
+    ("std48", "lazy", 3, 8): "c1883f718f9169ad2d7706c4e13922b75c455ec1144f6f6bd4e73e1a4735cfe7",
+    ("std48", "auto", 1, 8): "32c839b5e80197420026b9904a34bca4051b10d6f04c05e3e935242b4bd8eb19",
+    ("std48", "auto", 2, 8): "1893bd421666801dce7043b8edeb269f597a0b1d6ab5fea5b17b92317d2dfaea",
+    ("std48", "auto", 3, 8): "dd7cdd3d76d61bf97b853501c6fbc881b5ac074b5c2cc2c89e0452598d5c61b6",
+    ("med48", "lazy", 1, 8): "877b53ddfa12fe2d194abb72ba7ef8284930f0454117d7a1e9afaaccb221b743",
+    ("med48", "lazy", 2, 8): "94d8507d697f6f6256863695e1fa3fff7d454d4a72df4132c2871b4020211074",
+    ("med48", "lazy", 3, 8): "664d3048c088e6327eae565d8811418a48882d11506221d5628d5c6143662275",
+    ("med48", "auto", 1, 8): "2fb5f35ec9253348c278fb403538910eda92629ad4635a4543bc61a99e1a0512",
+    ("med48", "auto", 2, 8): "04a344ecf3106df6b28fd4a3088fea3fd8e474e708866a0c30a5b44ac5534c8f",
+    ("med48", "auto", 3, 8): "a9a3f96926c0c36aa47251b94ba58a9726ddbcff204a17d2b052c273d0228953",
+    ("std12", "lazy", 1, 8): "f0c293f1324528b3b3859bbb6297d4c8f040204a5aae416e9123eefd0714c863",
+    ("std12", "lazy", 2, 8): "d1b8ba5b4a8bb5b867889ad597824d3cd32ca8a76469ee3b5f46f65d5d68f16d",
+    ("std12", "lazy", 3, 8): "f46001258a5711f51bf5c47b885f43dba0127a44f64496fa597cc531de3cdadf",
+    ("std12", "auto", 1, 8): "20d5f2075fe390cac02722d18ecfaabda15f475fdc9de7b6a4f2109636b56b46",
+    ("std12", "auto", 2, 8): "066b9bf144407ca2aec606b3ac5e905beeb5014ca2ef1a6a8c69ffd49e807dbd",
+    ("std12", "auto", 3, 8): "9fe814b87dca5fab6e80aec50cdf22b9bff17360922bced04cc6ec1d058d6a81",
+    ("clr12", "lazy", 1, 8): "ddae8768dc02e25ac5234548a091b8e5439596913cecb570f5ab87091ffe3227",
+    ("clr12", "lazy", 2, 8): "102af3e7560bb5f565baacf293f2208a4d7c6417ab0e49130897de4ca8551e69",
+    ("clr12", "lazy", 3, 8): "08da026274d34e4d74103b7e8ace0ead83c6d9e54d490a874784c345a77ab351",
+    ("clr12", "auto", 1, 8): "d8bbb9d02aff7f9c1324e96db733558281f3baa263907781e39dbbb3872334de",
+    ("clr12", "auto", 2, 8): "9825488746e0fca08e4e2a6ac32dc3f55489428ebb71de1e9deb47c739ace3ba",
+    ("clr12", "auto", 3, 8): "486ba7cfdfd16b78fca9b4ea984fbf641bff17710c72a699483b5b93de887f61",
+    ("custom12", "lazy", 1, 8): "b3ab6acc4389b989354440cb79eb3c6f7b537a91a60477af6323a24105cd5c24",
+    ("custom12", "lazy", 2, 8): "0660e92a63bd85bfc8ee25140b2bb3e23d2fac8da1626c618f059712f4f18408",
+    ("custom12", "lazy", 3, 8): "e285fb11f71c5489611f967fe9a50008e1a05388edecb1293c2595a5e0ad379d",
+    ("custom12", "auto", 1, 8): "7ead2a3e3a1078e3c50f4fbe238ae4704bce2f28b3dddfdb52dd3ddc13840e2b",
+    ("custom12", "auto", 2, 8): "c18235d562556e06f63b27c011c9b09ec088898acff7ada87e457a2034c78216",
+    ("custom12", "auto", 3, 8): "98a224fdc6b772f882e301086feb74dfbd6ab1d763114ba6abe669f0c9f0d6c6",
+    ("std80", "lazy", 1, 8): "395c930a1b25129cc2a54269c6e447a334c0cf6e9ff181f7737772b216f5f6eb",
+    ("std80", "lazy", 2, 8): "cdada319d51a04ed3f648d516ffcf83eb7a5d0949914a18c37b07e4e64f3b589",
+    ("std80", "lazy", 3, 8): "bf15a30cf2a1902e93ef70c09b912dfcbd3fbbd93010109bfdea15cc8d740440",
+    ("std80", "auto", 1, 8): "de13e40c160d2a878e772728f55a41175c1e8d8d80f2a839c127547c3f4c4928",
+    ("std80", "auto", 2, 8): "cdb7d458d2db53a806cbc1fe99b2b21ac3ec1da7b9c6f2a51ca83fe39a30cc43",
+    ("std80", "auto", 3, 8): "05a51c6c39ed06afd99c719280721d8c30df8a5c1e6318368efed2f96ed2b736",
+}
+
+
+@pytest.mark.parametrize("key", list(SIGMA_DIGESTS), ids=lambda k: "-".join(str(v) for v in k))
+def test_sigma_walks_are_unchanged(key):
+    cfg, mode, seed, scale = key
+    ops = cs.generate(cfg, seed, scale=scale, profile="sigma", mode=mode)
+    assert hashlib.sha256(repr(ops).encode()).hexdigest() == SIGMA_DIGESTS[key]
+
+
+# ---- the accum profile -------------------------------------------------------------------------------------------------
+ACCUM_NEW_OPS = set(cs.ACCUM_OPS) | set(cs.MASKED_SCORES) | {"update_mode", "run", "run_end"}
+ACCEPTING = ("std48", "med48", "std12", "std80")       # vsom_batch_accum_begin opens an epoch (callseq.accepts_accum)
+
+
+def test_accum_ops_stay_out_of_the_other_walks():
+    assert ACCEPTING == tuple(c for c in cs.CONFIGS if cs.accepts_accum(cs.CONFIGS[c]))
+    for cfg in cs.CONFIGS:
+        for seed in SEEDS:
+            for scale in (1, SCALE):
+                walks = [cs.generate(cfg, seed, scale=scale)]
+                walks += [cs.generate(cfg, seed, scale=scale, profile="sigma", mode=mode) for mode in MODES]
+                for ops in walks:
+                    assert not ACCUM_NEW_OPS & {op[0] for op in ops}
+                    assert not any("poisoned" in op[1] for op in ops)
+                    assert all(op[1]["chunk"] < len(cs.CONFIGS[cfg]["chunks"]) for op in ops if "chunk" in op[1])
+
+
+def _accum_walks():
+    return [(c, m, s) for c in cs.CONFIGS for m in MODES for s in GPU_SEEDS]
+
+
+def _accum_ops(cfg, mode, seed, scale=SCALE):
+    return cs.generate(cfg, seed, n_ops=cs.ACCUM_DRAWS, scale=scale, profile="accum", mode=mode)
+
+
+def _run_accum(cfg, mode, seed, mutant=None, scale=SCALE):
+    return cs.run_walk(_accum_ops(cfg, mode, seed, scale), lambda name, model: FakeBackend(name, model, mutant))
+
+
+@functools.lru_cache(maxsize=None)
+def _faithful_accum(cfg, mode, seed, scale=SCALE):
+    return _run_accum(cfg, mode, seed, scale=scale)
+
+
+def _gpu_conditions(cfg, stats):
+    """what tests/test_gpu_call_sequences.py, test_accum_walk_matches_oracle, asserts of a walk's counts"""
+    a = stats["accum"]
+    assert stats["ops"] >= 50
+    if cfg in ACCEPTING:
+        assert a["chunks"] >= 8 and a["masked"] >= 3 and a["ends"] >= 2 and a["aborts"] >= 1, a
+        assert a["staged"] == (1 if cs.stages_ahead(cs.CONFIGS[cfg]) else 0), a
+    else:
+        assert not any(a.values()), a               # every begin refused, so every other call too
+
+
+@pytest.mark.parametrize("cfg,mode,seed", _accum_walks())
+def test_faithful_fake_passes_accum_walks(cfg, mode, seed):
+    stats = _faithful_accum(cfg, mode, seed)
+    _gpu_conditions(cfg, stats)
+    if cfg not in DEFERRING:
+        assert stats["sigma"] == (0, 0, 0, 0)
+    # run 5: refused where a prefetch behind an asynchronous epoch stages ahead (run_walk requires it there), nowhere else
+    assert stats["accum"]["staged"] == (1 if cs.stages_ahead(cs.CONFIGS[cfg]) else 0), stats
+
+
+def _accum_trace(cfg, ops):
+    """[(run, op, refusal, a sigmaMap record is pending at the call)] along an accum walk, from the contract alone (no
+    oracle): callseq.Model.accum_refusal on a stand-in that knows the open epoch's rows and the chunk's size, and
+    callseq.SigmaRecord.  A call that only a chunk staged ahead could refuse counts as accepted."""
+    import types
+    conf = cs.CONFIGS[cfg]
+    rec = cs.SigmaRecord(conf)
+    g = cs._Gen(cfg, 0, ops[0][1]["scale"], "accum", ops[0][1]["mode"])
+    m = types.SimpleNamespace(cfg=conf, acc=None, update_mode=cs.UPDATE_STRICT, X=None, B=0)
+    out, run = [], None
+    for op in ops[1:]:
+        name, p = op
+        if name in ("run", "run_end"):
+            run = p["id"] if name == "run" else None
+            continue
+        why = cs.Model.accum_refusal(m, op) if name in cs.ACCUM_OPS else None
+        if why is None and ((conf["custom"] and name in cs.CUSTOM_REFUSED) or (conf["tr"] == po.CLR and name in cs.CLR_REFUSED)):
+            why = "custom / CLR"
+        out.append((run, op, why, rec.pending))
+        g.emit(name, **p)
+        if name in ("upload", "upload_empty", "commit"):
+            m.X = True
+        m.B = g.B
+        if why is not None:
+            rec.read()
+            continue
+        rec.accepted(op, g.B, g.N)
+        if name == "accum_begin":
+            m.acc = {"rows": 0, "total": p["total"]}
+        elif name in ("accum_chunk", "accum_chunk_masked"):
+            m.acc["rows"] += g.B
+        elif name in ("accum_end", "accum_abort"):
+            m.acc = None
+        elif name == "update_mode":
+            m.update_mode = p["mode"]
+    return out
+
+
+def _trace_counts(trace):
+    """the counts of callseq.run_walk's stats["accum"], run 5's calls left out (its first chunk call may be refused)"""
+    n = {"chunks": 0, "masked": 0, "ends": 0, "aborts": 0}
+    for run, (name, p), why, _ in trace:
+        if why is None and run != 5 and name in cs.ACCUM_OPS[1:]:
+            if name in ("accum_chunk", "accum_chunk_masked"):
+                n["chunks"] += 1                    # (an empty chunk is counted here and not there: see the caller)
+                n["masked"] += name == "accum_chunk_masked"
+            else:
+                n[name[6:] + "s"] += 1
+    return n
+
+
+@pytest.mark.parametrize("cfg", list(cs.CONFIGS))
+def test_gpu_accum_walks_meet_their_conditions(cfg):
+    """What test_accum_walk_matches_oracle asserts of its walks' counts is a condition on the inputs: here it is checked at
+    that test's own scale -- against the faithful fake where the model can afford it (the 12 x 12 maps), from the contract
+    alone for the others (_accum_trace: no refusal but the ones the header names, so the GPU test cannot pass by having
+    everything refused)."""
+    for mode in MODES:
+        for seed in GPU_SEEDS:
+            ops = _accum_ops(cfg, mode, seed, scale=1)
+            trace = _accum_trace(cfg, ops)
+            n = _trace_counts(trace)
+            empty = sum(1 for run, op, why, _ in trace if run == 6 and why is None and op[0] == "accum_chunk") - 2
+            if cfg in ACCEPTING:
+                assert empty == 1                   # run 6: two chunks and the empty one
+                assert n["chunks"] - empty >= 8 and n["masked"] >= 3 and n["ends"] >= 2 and n["aborts"] >= 1, (mode, seed, n)
+            else:
+                assert not any(n.values())
+            assert len(trace) >= 50
+            if cfg in ("std12", "clr12", "custom12"):
+                stats = _faithful_accum(cfg, mode, seed, 1)
+                _gpu_conditions(cfg, stats)
+                if cfg in ACCEPTING:                # the trace is the walk: run 5 adds its two chunks and its abort
+                    a = stats["accum"]
+                    assert (a["chunks"], a["masked"], a["ends"], a["aborts"], a["staged"]) == \
+                        (n["chunks"] - empty + 2, n["masked"], n["ends"], n["aborts"] + 1, 0)
+
+
+RUN6_REFUSALS = ["no chunk loaded"] + ["no accumulated epoch is open"] * 3 + \
+    ["valid_host is null", "strict update mode", "already open", "valid_host is null", "exceed total_rows", "rows accumulated"]
+
+
+def test_accum_walks_hold_the_required_runs():
+    """from the op lists alone: every accum walk holds runs 1-9 of callseq's module docstring, no call of a no-wait run
+    waits for the stream, and by the contract no call of runs 1-4 and 6-9 is refused but the refusals run 6 is made of"""
+    loads = ("upload", "prefetch", "stage", "commit")
+    for scale in (SCALE, 1):
+        for cfg, mode, seed in _accum_walks():
+            where = (cfg, mode, seed, scale)
+            conf = cs.CONFIGS[cfg]
+            ops = _accum_ops(cfg, mode, seed, scale)
+            assert ops[1] == ("sigma_mode", {"mode": mode})
+            trace = _accum_trace(cfg, ops)
+            runs = {r: [t for t in trace if t[0] == r] for r in cs.RUNS}
+            names = {r: [t[1][0] for t in runs[r]] for r in cs.RUNS}
+            chunks = {r: [t[1] for t in runs[r] if t[1][0] in ("accum_chunk", "accum_chunk_masked")] for r in cs.RUNS}
+            sizes = cs._Gen(cfg, 0, scale, "accum", mode).sizes
+            assert all(names[r] for r in cs.RUNS), where
+
+            def between_chunks(r, wanted):
+                """the names of `wanted` that stand between the first and the last chunk call of run r, in order"""
+                at = [i for i, n in enumerate(names[r]) if n in ("accum_chunk", "accum_chunk_masked")]
+                return [n for n in names[r][at[0]:at[-1]] if n in wanted]
+
+            # no refusal by the contract, but run 6's (and everything behind a refused begin)
+            for r in cs.RUNS:
+                why = [t[2] for t in runs[r] if t[2] is not None]
+                if cfg not in ACCEPTING:
+                    assert all(t[2] is not None for t in runs[r] if t[1][0] in cs.ACCUM_OPS), where
+                elif r == 6:
+                    assert why == RUN6_REFUSALS, (where, why)
+                else:
+                    assert not why, (where, r, why)
+            # the no-wait runs
+            for r in cs.NO_WAIT_RUNS:
+                assert names[r][0] == "accum_begin" and names[r][-1] == "accum_end", where
+                assert runs[r][0][1][1]["first"] is True, where
+                for _, (name, p), _, _ in runs[r][1:-1]:
+                    if r == 2 and name == "topk":
+                        continue
+                    assert name in cs.NO_WAIT_OPS, (where, r, name)
+                    assert name != "upload" or p["asynchronous"], (where, r)
+                    assert name != "prefetch" or p["src"] == "pinned", (where, r)
+            # 1: three masked chunks or more and nothing else; a row without a valid column
+            assert len(chunks[1]) >= 3 and all(c[0] == "accum_chunk_masked" for c in chunks[1]), where
+            assert [c[1]["k"] for c in chunks[1]] == list(range(len(chunks[1]))), where
+            assert len({c[1]["seed"] for c in chunks[1]}) == 1, where
+            assert any(c[1].get("full") and c[1]["form"] == "rows" for c in chunks[1]), where
+            rows1 = [t[1][1]["chunk"] for t in runs[1] if t[1][0] in ("upload", "prefetch", "stage")]
+            if len(cs.maskable(conf, True)) > 1:       # different rows behind each other: a late reader would see them
+                assert all(x != y for x, y in zip(rows1, rows1[1:])), (where, rows1)
+            # 2: growing chunks, the largest last, one top-8 query on a 64-row window between two chunk calls
+            up = [sizes[t[1][1]["chunk"]] for t in runs[2] if t[1][0] in ("upload", "prefetch", "stage")]
+            assert len(up) >= 3 and up == sorted(up) and up[-1] == max(sizes) and up[0] < up[-1], (where, up)
+            assert all(c[0] == "accum_chunk" for c in chunks[2]) and len(chunks[2]) == len(up), where
+            assert between_chunks(2, ("topk",)) == ["topk"] and names[2].count("topk") == 1, where
+            q = [t[1][1] for t in runs[2] if t[1][0] == "topk"][0]
+            assert q["k"] == 8 and q["r1"] - q["r0"] == min(64, up[-2]), (where, q)
+            # 3: plain, masked, plain in a non-first epoch, set_last_bmu between each load and its chunk call
+            assert [c[0] for c in chunks[3]] == ["accum_chunk", "accum_chunk_masked", "accum_chunk"], where
+            assert runs[3][0][1][0] == "accum_begin" and runs[3][0][1][1]["first"] is False, where
+            for i, n in enumerate(names[3]):
+                if n in ("accum_chunk", "accum_chunk_masked"):
+                    assert names[3][i - 1] == "set_last_bmu" and names[3][i - 2] in loads, where
+            assert names[3][-1] == "accum_end", where
+            # 4: an abort behind two chunks or more, one masked; get_state; a plain epoch
+            a = names[4].index("accum_abort")
+            first = [n for n in names[4][:a] if n in ("accum_chunk", "accum_chunk_masked")]
+            assert len(first) >= 2 and "accum_chunk_masked" in first, where
+            assert names[4][a + 1] == "get_state" and names[4][a + 2] == "accum_begin", where
+            rest = names[4][a + 2:]
+            assert "accum_chunk" in rest and "accum_chunk_masked" not in rest and rest[-1] == "accum_end", where
+            # 5: the stage-ahead refusal
+            assert names[5] == ["epoch_async", "prefetch", "accum_begin", "accum_chunk", "commit", "accum_chunk",
+                                "accum_abort"], where
+            # 6: the empty epoch, the empty chunk (the refusals: above)
+            assert any(names[6][i:i + 2] == ["accum_begin", "accum_end"] and runs[6][i][1][1]["total"] == 0
+                       for i in range(len(names[6]))), where
+            assert any(names[6][i:i + 2] == ["upload_empty", "accum_chunk"] and (runs[6][i + 1][2] is None or
+                                                                                 cfg not in ACCEPTING)
+                       for i in range(len(names[6]))), where
+            # 7: a pending record meets begin
+            b = names[7].index("accum_begin")
+            assert names[7][b - 1] == "epoch_async" and names[7][-1] == "accum_end", where
+            if cfg in DEFERRING:
+                assert runs[7][b][3] and not any(t[3] for t in runs[7][b + 1:]), where
+            # 8: a map write and a single step at another sigma between two chunks; ended with end
+            assert between_chunks(8, ("set_state", "single")) == ["set_state", "single"], where
+            st = [t[1][1] for t in runs[8] if t[1][0] in ("set_state", "single")]
+            assert st[0]["parts"] == "map" and st[1]["sigma"] != runs[8][0][1][1]["sigma"], where
+            assert names[8][-1] == "accum_end" and "accum_abort" not in names[8], where
+            # 9: the queries between two chunks
+            got = between_chunks(9, cs.MASKED_SCORES + cs.ARENA + cs.READERS)
+            assert got[:4] == ["similarity_masked", "evaluate_masked", "bmu_masked", "bmd"] and got[4] in cs.READERS, where
+            assert len(got) == 5 and names[9][-1] == "accum_end", where
+
+
+def test_accum_masks_are_engineered():
+    """the dirty columns of an epoch's masked chunks: the border columns, a column invalid throughout, columns that turn
+    dirty in the second and in the third masked chunk, MAX_DIRTY at the most; the rows a masked chunk call is given hold
+    NaN / inf under every invalid entry of its mask and nowhere else, and every walk loads exactly those rows for it"""
+    for cfg in ACCEPTING:
+        conf = cs.CONFIGS[cfg]
+        J = conf["J"]
+        chunks = cs.chunk_data(cfg, 1, 1, "accum")
+        assert len(cs.maskable(conf, True)) >= 2 or conf["W"] * conf["H"] * 300 <= cs.MASK_DISTANCES
+        for i in cs.maskable(conf):
+            X = chunks[i]
+            assert np.isfinite(X).all()
+            dirty = []
+            for form in ("rows", "one_mask"):
+                for k in range(3):
+                    v = np.broadcast_to(cs.accum_mask(77, k, form, False, X) != 0, X.shape)
+                    P = cs.poisoned_rows(X, 77, k, form, False)
+                    assert (np.isfinite(P) == v).all() and (P[v] == X[v]).all()
+                    assert (np.broadcast_to(cs.accum_mask(77, k, form, False, P) != 0, X.shape) == v).all()
+                    dirty.append(set(np.flatnonzero(~v.all(axis=0))))
+                    if form == "rows":
+                        assert v.any(axis=1).all()
+            assert len(set.union(*dirty[:3])) <= cs.MAX_DIRTY and len(set.union(*dirty[3:])) <= cs.MAX_DIRTY
+            assert set(cs.border_columns(J)) <= dirty[0]
+            assert dirty[0] < dirty[1] < dirty[2]           # the dirty set grows: the fold kernel's fresh path
+            dead = [d for d in range(J) if all(not np.broadcast_to(cs.accum_mask(77, k, f, False, X), X.shape)[:, d].any()
+                                               for k in range(3) for f in ("rows", "one_mask"))]
+            assert len(dead) == 1 and dead[0] not in cs.border_columns(J)
+            full = cs.accum_mask(77, 0, "rows", True, X) != 0
+            assert (~full.any(axis=1)).sum() == 1
+            P = cs.poisoned_rows(X, 77, 0, "rows", True)
+            assert (np.isfinite(P) == full).all() and (~np.isfinite(P)).all(axis=1).sum() == 1
+    # every masked chunk call of a walk stands behind the load of its own poisoned rows
+    for cfg, mode, seed in _accum_walks():
+        ops = [op for op in _accum_ops(cfg, mode, seed) if op[0] not in ("set_last_bmu", "commit", "run", "run_end")]
+        masked = [i for i, op in enumerate(ops) if op[0] == "accum_chunk_masked" and not op[1].get("null")]
+        assert masked
+        for i in masked:
+            load = ops[i - 1]
+            assert load[0] in ("upload", "prefetch", "stage"), (cfg, mode, seed, load)
+            if cfg in ACCEPTING:
+                assert load[1]["poisoned"] == ops[i][1], (cfg, mode, seed, load)
+            else:
+                assert "poisoned" not in load[1]
+        assert sum("poisoned" in op[1] for op in ops) == (len(masked) if cfg in ACCEPTING else 0)
+
+
+@pytest.mark.parametrize("mutant", ["l", "m", "n", "o", "p", "q", "r", "s"])
+def test_accum_mutants_are_caught(mutant):
+    caught = []
+    for cfg, mode, seed in _accum_walks():
+        if cfg not in ("std12", "std48"):
+            continue
+        try:
+            _run_accum(cfg, mode, seed, mutant)
+        except cs.WalkFailure as e:
+            caught.append((cfg, mode, seed, str(e).splitlines()[0]))
+            break
+    assert caught, f"mutant {mutant} was not caught by any walk"

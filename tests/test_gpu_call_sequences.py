@@ -24,7 +24,38 @@ The fake runs the oracle a second time, so the model's share -- what this test p
 of each figure.  Seeds 1 and 2, lazy / auto, in seconds: std48 4.1, 3.5 / 4.0, 3.9; med48 4.7, 4.6 / 7.7, 4.4; std80 2.2,
 2.8 / 2.2, 2.9; std12, clr12, custom12 at most 0.1 each.  (The ingest walks measure 0.03 to 15 the same way.)  The oracle's
 serial online scan is what a walk can spend most on: the sigma profile draws it less often, on chunks of at most 512 rows,
-and less often still for med48 and std80 (callseq.CONFIGS, "sigma_weights" / "weights")."""
+and less often still for med48 and std80 (callseq.CONFIGS, "sigma_weights" / "weights").
+
+The accum walks (callseq.generate_accum) do the same for the accumulated batch epoch (include/vsom_hip.h,
+vsom_batch_accum_begin / _chunk / _chunk_masked / _end / _abort), the one protocol whose state lives across calls that do not
+block: the pinned validity halves used alternately, chunk scratch in the query arena shared with the queries, staged rows
+overwritten behind enqueued chains, the neighbourhood table, the ever-dirty column list, a pending sigmaMap.  Under
+VSOM_SIGMA_LAZY and VSOM_SIGMA_AUTO a walk makes callseq.ACCUM_DRAWS random draws -- the sigma profile's ops, whole epochs
+of plain and masked chunks ended or aborted, stray calls, the masked scoring calls -- around nine runs it holds by
+construction (callseq's module docstring): three masked chunks with no wait between them, growing chunks with an arena query
+between, plain / masked / plain in a non-first epoch, an abort and a plain epoch behind it, the stage-ahead refusal, every
+refusal of the header (each followed by a comparison of the whole state) with the empty epoch and the empty chunk, a pending
+sigmaMap meeting begin, a model rewritten in mid-epoch, and queries in mid-epoch.  The five calls go to the C ABI directly;
+the validity bytes are zeroed as soon as a masked chunk call returns; a masked chunk call is given rows with NaN / inf under
+every invalid entry of its mask.  The two no-wait runs go to the first context back to back, before the twin or the model
+sees a call of them; everywhere else the twin's wait and the model's work stand between two calls, so there the walk tests
+the state logic and not the ordering.  Where a prefetch behind an asynchronous epoch stages ahead (callseq.stages_ahead)
+the chunk call of run 5 must be refused, and the whole state is compared behind that refusal as behind every other.  Every call returns the oracle's values bit for bit (callseq.Model: phase 1 per chunk, the running MSE
+over total_rows, phase 2 over the concatenation at end, dirty columns from tests/masked_train_ref.py), vsom_sigma_stats
+follows the header's contract, and a second context -- VSOM_SIGMA_EAGER, fed from pageable memory, synchronised after every
+call -- returns the same bits from the readers, the arena queries, the masked epoch and the masked scoring calls, and ends
+in the oracle's state.  On clr12 and custom12 begin is refused, every other accum call with it, and the rest of the walk
+matches the oracle.
+
+Cost of an accum walk, measured the same way (against the CPU fake, at this test's scale; the model's share is about half).
+Seeds 1 and 2, lazy / auto, in seconds: std48 7.3, 5.9 / 6.9, 6.6; med48 7.2, 8.9 / 7.3, 8.8; std80 7.7, 7.9 / 7.8, 8.6;
+std12 1.8, 1.5 / 1.8, 2.0; clr12, custom12 at most 0.1.  On an MI355X the tests themselves took 1.7 to 2.6 s (std48), 2.0 s
+(med48), 2.0 to 2.2 s (std80), 0.4 to 0.5 s (std12) and under 0.8 s.  The dearest op is the model's full masked search
+(tests/masked_train_ref.py, pure Python, 12 us a distance): only run 1 puts masked chunks into a first epoch, three of
+them, on chunks of the accum profile alone that are short enough (callseq.CONFIGS, "accum_chunks"; callseq.maskable caps
+rows x nodes at callseq.MASK_DISTANCES, 8 times that for the local walk), and a walk makes 12 random draws around its runs
+(callseq.ACCUM_DRAWS; with 24 the large maps measured 9 to 17 s); the rest is the phase 2 at end -- run 2 ends on the
+configuration's largest chunk by design, and every dirty column costs one single-column oracle run."""
 import pytest
 
 import callseq as cs
@@ -56,3 +87,27 @@ def test_sigma_walk_matches_oracle(cfg, mode, seed):
         assert deferred >= 1 and dropped >= 1 and materialised >= 1, stats
     else:
         assert (deferred, dropped, materialised) == (0, 0, 0), stats     # "always eager"
+
+
+ACCEPTING = ("std48", "med48", "std12", "std80")
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+@pytest.mark.parametrize("mode", ["lazy", "auto"])
+@pytest.mark.parametrize("cfg", list(cs.CONFIGS))
+def test_accum_walk_matches_oracle(cfg, mode, seed):
+    ops = cs.generate(cfg, seed, n_ops=cs.ACCUM_DRAWS, profile="accum", mode=mode)
+    # (run_walk itself fails a walk in which a call of runs 1-4 or 6-9 is refused where the header accepts it, or accepted
+    # where the header refuses it)
+    stats = cs.run_walk(ops, cs.GpuBackend)
+    assert stats["ops"] >= 50
+    a = stats["accum"]
+    if cfg in ACCEPTING:
+        # (tests/test_call_sequences_model.py, test_gpu_accum_walks_meet_their_conditions: these walks do)
+        assert a["chunks"] >= 8 and a["masked"] >= 3 and a["ends"] >= 2 and a["aborts"] >= 1, stats
+        # run 5: the chunk call behind a chunk staged ahead was refused (run_walk fails the walk where it is not)
+        assert a["staged"] >= (1 if cs.stages_ahead(cs.CONFIGS[cfg]) else 0), stats
+    else:
+        assert not any(a.values()), stats            # vsom_batch_accum_begin is refused, and so every call behind it
+    if cfg not in DEFERRING:
+        assert stats["sigma"][:3] == (0, 0, 0), stats
