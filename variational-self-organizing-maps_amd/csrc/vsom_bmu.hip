@@ -15,6 +15,7 @@
 //  stage kernels     : chunk re-layout (zero-padded rows; CLR x'/y' expansion).
 #include "vsom_dist_tile.hpp"
 #include "vsom_digits.hpp"
+#include "vsom_search_plan.hpp"
 #include <algorithm>
 #include <utility>
 
@@ -655,55 +656,33 @@ int launch_bmu_full_exact_masked(vsom_ctx *c, size_t s0, size_t s1, const int *s
         fb = *fbp;
     if (s1 <= s0)
         return VSOM_OK;
-    const int ntn = (int)((c->N + TILE - 1) / TILE);
-    const int TS = c->transform == VSOM_CLR ? 32 : TILE;      // samples per tile (bmu_tile_kernel<CLR, TI>)
-    const int nts = (int)((s1 - s0 + TS - 1) / TS);
-    size_t need = (size_t)ntn * c->Bcap;
-    VSOM_ALLOC_CHECK(vsom_grow(c->partial, need, c->stream));
+    const ExactPlan e = vsom_exact_plan(*c, s0, s1, slist != nullptr && scount != nullptr, hits != nullptr);
+    VSOM_ALLOC_CHECK(vsom_grow(c->partial, e.partial_elems, c->stream));
     DistArgs a = vsom_dist_args(c);
-    // (a redo list is usually empty or short: ~512 workgroups -- the two per CU the kernel's registers allow -- each
-    // walking on through the list's tiles; 768 for CLR measured slower: a second, half-empty round)
-    const bool list = slist != nullptr && scount != nullptr;
-    const int gy = list ? std::min(nts, std::max(1, 512 / ntn)) : nts;
-    dim3 grid((unsigned)ntn, (unsigned)gy);
-    // Representatives of the duplicate rows only -- where the search is large enough to repay three passes over the map
-    // (C3's size: hash 15 + twins 5 + list 17 us): 2e10 (sample, node, value) triples = ~0.5 ms of this kernel
-    // (vsom_set_row_dedupe moves the threshold; 0 = always).  With a redo list the passes look at its device-side length
-    // first and leave when it is short.  Not for restricted searches: bit-identical rows may differ in their hit counts.
+    dim3 grid((unsigned)e.ntn, (unsigned)e.gy);
     const int *nlist = nullptr;
     const unsigned *ncount = nullptr;
-    const double work = (double)(s1 - s0) * (double)c->N * (double)c->D;
-    bool dd = !hits && c->N >= 256 && c->dedupe && c->dd_min_work >= 0 && work >= c->dd_min_work;
-    if (dd && list && c->dd_min_work > 0 && c->transform != VSOM_CLR) {
-        // A redo list is usually empty or a handful of non-finite samples (C3: always empty), and then even three launches
-        // that look at its length and leave are ~8 us of a step for nothing.  Whole-chunk redo lists are what the CLR
-        // shortlist produces when it recognises a collapsed map on the device (vsom_shortlist.hip, sl_clr_degenerate): the
-        // passes are enqueued behind CLR searches (8 us of a 5.4 ms step when the list is short) and, for the other
-        // transformations, only when vsom_set_row_dedupe(ctx, 0) asks for them always.  (A hint from the previous search's
-        // feedback words was tried: the host enqueues whole steps ahead of the device, the words are stale when it matters.)
-        dd = false;
-    }
-    if (dd) {
-        if (int rc = launch_bmu_dedupe(c, list ? scount : nullptr, 256u, &nlist, &ncount))
+    if (e.dedupe) {
+        if (int rc = launch_bmu_dedupe(c, e.list ? scount : nullptr, 256u, &nlist, &ncount))
             return rc;
     }
 #define VSOM_TILE_LAUNCH(K)                                                                                             \
     hipLaunchKernelGGL(K, grid, dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)c->N, c->partial.p, (int)c->Bcap, c->nan0.p, \
                        slist, scount, hits, min_hits, fb, nlist, ncount)
-    if (c->transform == VSOM_CLR) {
-        if (list)
+    if (e.clr) {
+        if (e.list)
             VSOM_TILE_LAUNCH((bmu_tile_kernel<true, 2, true>));
         else
             VSOM_TILE_LAUNCH((bmu_tile_kernel<true, 2, false>));
     } else {
-        if (list)
+        if (e.list)
             VSOM_TILE_LAUNCH((bmu_tile_kernel<false, 4, true>));
         else
             VSOM_TILE_LAUNCH((bmu_tile_kernel<false, 4, false>));
     }
 #undef VSOM_TILE_LAUNCH
     hipLaunchKernelGGL(bmu_reduce_kernel, dim3((unsigned)((s1 - s0 + 255) / 256)), dim3(256), 0,
-                       c->stream, c->partial.p, (int)c->Bcap, ntn, c->nan0.p, (int)s0, (int)s1, c->lastbmu.p,
+                       c->stream, c->partial.p, (int)c->Bcap, e.ntn, c->nan0.p, (int)s0, (int)s1, c->lastbmu.p,
                        c->sqres.p, slist, scount, ncount);
     VSOM_HIP_CHECK(hipGetLastError());
     return VSOM_OK;
@@ -720,55 +699,30 @@ int launch_bmu_restricted(vsom_ctx *c, u64 min_hits)
     return launch_bmu_full_exact_masked(c, 0, c->B, nullptr, nullptr, c->hits.p, min_hits);
 }
 
-int launch_bmu_full_shortlist(vsom_ctx *c, size_t s0, size_t s1);
-
+// findBmu for samples [s0, s1): what it does is vsom_search_plan's (vsom_search_plan.hpp); here the plan's two inputs that
+// are not the context's -- the verdict of the back-off on the previous shortlist search's feedback, consulted exactly where
+// AUTO's size rule wants the shortlist, and whether the ring kernels' LDS limit could be raised -- and its execution
 int launch_bmu_full(vsom_ctx *c, size_t s0, size_t s1)
 {
     TimerScope ts(c, VSOM_T_BMU);
-    // the MFMA shortlist covers the plain squared-distance comparer (Standard / Median);
-    // it pays once the map is large enough to fill the matrix pipes and the vectors are long enough
-    // for the contraction to outweigh writing and re-reading the B x N approximation matrix
-    // (measured on 64x64 maps, B = 16384: D = 32 exact 0.22 vs 0.36 ms, D = 64 0.34 vs 0.39, D = 128
-    // 0.61 vs 0.47)
-    // (CLR: one contraction of length P + 3J over derived features, vsom_shortlist.hip "CLR shortlist")
-    const bool can = true;
-    bool want = c->bmu_mode == VSOM_BMU_SHORTLIST;
-    // Rows of at most 64 values (Standard / Median): the contraction keeps tile minima only, nothing of size B x N is
-    // written (sl_k64_kernel, vsom_sl_i8.hip) -- it beats the exact kernel once that has ~0.1 ms of work
-    // (C4, 16384 x 4096 x 32: exact 0.21 ms)
-    const bool short_rows = c->transform != VSOM_CLR && c->D <= 64 && c->D >= 16 &&
-                            (double)(s1 - s0) * (double)c->N * (double)c->D >= 1.0e9;
-    if (c->bmu_mode == VSOM_BMU_AUTO && c->N >= 1024 && (s1 - s0) >= 64 && (c->D > 64 || short_rows)) {
-        want = true;
-        // feedback of the previous shortlist call (pinned host words written by the device, read
-        // without synchronising: possibly one call stale): when more than a quarter of the samples
-        // had to be redone exactly the shortlist does not pay on this map -- skip it for a while
-        if (c->sl_fb.p) {
-            volatile unsigned *fb = c->sl_fb.p;
-            unsigned redo = fb[0], rows = fb[2], seq = fb[3];
-            if (seq != c->sl_seq_seen) {             // the verdict of a shortlist search not looked at yet
-                c->sl_seq_seen = seq;
-                if (rows > 0 && redo * 4u > rows) {
-                    // A failed probe costs a fraction of the exact search it falls back to (Standard C3: 0.35 of
-                    // 2.9 ms; CLR: a collapsed map is recognised on the device before the contraction runs, vsom_shortlist.hip)
-                    // and a wrongly skipped one several times its own cost, and every chunk rebuilds the map from zero
-                    // (Som.cpp:843,870) -- one bad map says little about the next: no pause after a first failure,
-                    // 4 searches after a second in a row, doubling up to 32
-                    c->sl_skip = c->sl_fail_streak == 0 ? 0 : (2 << (c->sl_fail_streak < 4 ? c->sl_fail_streak : 4));
-                    ++c->sl_fail_streak;
-                } else {
-                    c->sl_fail_streak = 0;
-                }
-            }
-            if (c->sl_skip > 0) {
-                --c->sl_skip;
-                want = false;
-            }
-        }
+    bool skips = false;
+    if (c->bmu_mode == VSOM_BMU_AUTO && s1 > s0 && vsom_search_auto_shortlist(*c, s1 - s0) && c->sl_fb.p) {
+        volatile unsigned *fb = c->sl_fb.p;   // pinned host words written by the device, read without synchronising
+        const unsigned redo = fb[0], rows = fb[2], seq = fb[3];
+        skips = vsom_sl_backoff_step(c->sl_skip, c->sl_fail_streak, c->sl_seq_seen, redo, rows, seq);
     }
-    if (can && want)
-        return launch_bmu_full_shortlist(c, s0, s1);
-    return launch_bmu_full_exact_list(c, s0, s1, nullptr, nullptr, nullptr);
+    SearchPlan p = vsom_search_plan(*c, s0, s1, skips, true);
+    if (p.ring() && !sl_i8_raise_ring_lds(p.contraction))
+        p = vsom_search_plan(*c, s0, s1, skips, false);
+    switch (p.path) {
+    case VSOM_SEARCH_SL_CLR:
+        return launch_bmu_full_shortlist_clr(c, s0, s1, p);
+    case VSOM_SEARCH_SL_FP32:
+    case VSOM_SEARCH_SL_I8:
+        return launch_bmu_full_shortlist(c, s0, s1, p);
+    default:
+        return launch_bmu_full_exact_list(c, s0, s1, nullptr, nullptr, nullptr);
+    }
 }
 
 // ------------------------------------------------------------------------------------------

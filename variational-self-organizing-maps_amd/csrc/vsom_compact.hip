@@ -152,7 +152,7 @@ bool vsom_cc_applies(const vsom_ctx *c)
     if (c->D < 64)           // the chain / tiny kernels, and nothing worth retiring
         return false;
     // only the lane = node chain kernels and the MFMA shortlist consume the compaction: maps below their
-    // thresholds (vsom_phase2_plan: VSOM_CHAIN_MAX_WAVES; launch_bmu_full: 1024 nodes) skip the passes
+    // thresholds (vsom_phase2_plan: VSOM_CHAIN_MAX_WAVES; vsom_search_auto_shortlist: 1024 nodes) skip the passes
     return vsom_lane_node_waves(*c, c->N) > VSOM_CHAIN_MAX_WAVES || c->N >= 1024;
 }
 

@@ -10,8 +10,7 @@
 #include "vsom_device.hpp"
 #include <type_traits>
 
-#define TILE 64
-#define LDT 36   // LDS row stride in floats: 16-B aligned, lane rows land on distinct 4-bank slots
+#define LDT 36  // LDS row stride in floats: 16-B aligned, lane rows land on distinct 4-bank slots
 #define MSK_LDV (VSOM_TK / 4)   // dwords per row of the validity tile
 
 // r where the column is valid (m = ~0), +0 where it is not (m = 0): whatever r holds, a NaN included

@@ -34,6 +34,7 @@ typedef unsigned long long u64;
 #define VSOM_CHAIN_MAX_WAVES 448
 
 #define VSOM_TK 32          // K-chunk of the tile kernels; row pitches are multiples of it
+#define TILE 64             // nodes (and, but for CLR, samples) of a distance tile (vsom_dist_tile.hpp; vsom_exact_plan sizes grids by it)
 
 // spare rows behind the staged sample matrices (readable, contents unspecified: zero at allocation, stale
 // samples after a larger chunk): the pipelined update kernels read ahead into them and never consume them

@@ -31,11 +31,10 @@
 // is fed back to the host through pinned memory so that AUTO mode can stop using the shortlist on
 // maps where it does not prune (very smooth maps early in training).
 #include "vsom_digits.hpp"
+#include "vsom_search_plan.hpp"
 #include <cstring>
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-
-#define SL_CMAX 2048
 
 __global__ __launch_bounds__(256) void sl_norm_kernel(const float *__restrict__ map, int ldm, int Dp, int N,
                                                       float *__restrict__ nrm, unsigned *__restrict__ scal)
@@ -121,8 +120,6 @@ __device__ __forceinline__ bool sl_clr_degenerate(const unsigned *__restrict__ s
     return (nbmax - nbmin) <= 1.0e-3f * nbmax && (a2max - a2min) <= 1.0e-3f * a2max;
 }
 
-#define GT 128     // block tile (samples x nodes)
-#define GK 32      // K chunk
 #define GLD 36     // LDS row stride (floats)
 
 __global__ __launch_bounds__(256, 2) void sl_gemm_kernel(const float *__restrict__ X, int ldx, int s0, int s1,
@@ -746,13 +743,7 @@ __global__ __launch_bounds__(256) void sl_pick_kernel(DistArgs a, int s0, int s1
     }
 }
 
-// host side ------------------------------------------------------------------------------------
-int launch_bmu_full_exact_list(vsom_ctx *c, size_t s0, size_t s1, const int *slist, const unsigned *scount, const SlFeedback *fb);
-int launch_sl_i8(vsom_ctx *c, size_t s0, size_t s1, size_t ldg, size_t ntm, unsigned *scal, unsigned *xflag, int plan);   // vsom_sl_i8.hip
-int sl_i8_plan(vsom_ctx *c, size_t s0, size_t s1);
-
-static int launch_bmu_full_shortlist_clr(vsom_ctx *c, size_t s0, size_t s1);
-
+// host side: the executors of a shortlist plan (vsom_search_plan.hpp) ----------------------------
 // node norms; two alternating sets of {16 words + 3 x 32 line-sized slots} (4096 words each) + the chunk's data-kind
 // flag; the pinned host feedback
 static hipError_t sl_ensure_scalars(vsom_ctx *c)
@@ -761,55 +752,30 @@ static hipError_t sl_ensure_scalars(vsom_ctx *c)
                                         vsom_member(c->sl_fb, 16, VSOM_BUF_ZERO)});
 }
 
-int launch_bmu_full_shortlist(vsom_ctx *c, size_t s0, size_t s1)
+int launch_bmu_full_shortlist(vsom_ctx *c, size_t s0, size_t s1, const SearchPlan &p)
 {
-    if (s1 <= s0)
-        return VSOM_OK;
-    if (c->transform == VSOM_CLR)
-        return launch_bmu_full_shortlist_clr(c, s0, s1);
-    const size_t nrows = s1 - s0;
-    // the contraction in exact integer arithmetic on the int8 matrix pipe (vsom_sl_i8.hip): one digit per sample value
-    // for chunks of small non-negative integers (MNIST pixels), three for any other data -- which of the two is a
-    // device-side fact of the staged chunk (`xflag`) that the kernels read; nothing is decided here
-    const bool i8 = c->xpitch <= 4096;
-    // no B x N matrix where the contraction kernels keep 16-node tile minima only (rows of at most 64 values; big
-    // problems of at most 960 contracted columns): sl_pick_kernel refines
-    const int plan = i8 ? sl_i8_plan(c, s0, s1) : 0;
-    const bool gless = plan != 0;
-    const size_t ldg = ((size_t)c->N + 127) / 128 * 128;
-    const size_t need = gless ? 0 : nrows * ldg;
-    const size_t ntm = gless ? (((size_t)c->N + 31) / 32) * 2 : (((size_t)c->N + GT - 1) / GT) * 2;
-    VSOM_ALLOC_CHECK(vsom_grow(c->sl_G, need, c->stream));
-    VSOM_ALLOC_CHECK(vsom_grow(c->sl_tmin, nrows * ntm, c->stream));
-    VSOM_ALLOC_CHECK(vsom_grow(c->sl_list, nrows, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_G, p.g_elems, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_tmin, p.tmin_elems, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_list, p.rows, c->stream));
     VSOM_ALLOC_CHECK(sl_ensure_scalars(c));
     // scal: [0] max nrm bits, [1] non-finite flag, [2] redo count, [4] redo samples, [5] candidates
     unsigned *scal = c->sl_scal.p + 4096 * c->sl_par, *scal_next = c->sl_scal.p + 4096 * (c->sl_par ^ 1);
     c->sl_par ^= 1;
     unsigned *xflag = c->sl_scal.p + 8192;
-    dim3 grid((unsigned)((c->N + GT - 1) / GT), (unsigned)((nrows + GT - 1) / GT));
-    const double u = 5.9604644775390625e-08;   // 2^-24
-    const double g2 = ((double)c->D / 8.0 + 10.0) * u;
-    if (i8) {
-        int rc = launch_sl_i8(c, s0, s1, ldg, ntm, scal, xflag, plan);
-        if (rc)
+    const int N = (int)c->N, ldg = (int)p.ldg, ntm = (int)p.ntm;
+    if (p.path == VSOM_SEARCH_SL_I8) {
+        if (int rc = launch_sl_i8(c, s0, s1, p, scal, xflag))
             return rc;
     } else {
-    hipLaunchKernelGGL(sl_norm_kernel, dim3((unsigned)(((size_t)c->N * 16 + 255) / 256)), dim3(256), 0, c->stream,
-                       c->map.p, (int)c->pitch, (int)c->part_pitch, (int)c->N, c->sl_nrm.p, scal);
-    if (c->cc_valid) {
-        // columns that are zero in every row of the chunk add exactly 0 to every <x, M>: contract over the live
-        // ones (norms, bound and refinement keep the whole rows)
-        int rc = vsom_cc_gather_map(c);
-        if (rc)
-            return rc;
-        hipLaunchKernelGGL(sl_gemm_kernel, grid, dim3(256), 0, c->stream, c->Xc.p, (int)c->cpitch, (int)s0, (int)s1,
-                           c->Mc.p, (int)c->cpitch, (int)c->N, (int)c->cpitch, c->sl_nrm.p, c->sl_G.p, (int)ldg, c->sl_tmin.p, (int)ntm,
-                           (const unsigned *)c->cc_meta.p, (const unsigned *)nullptr);
-    } else
-    hipLaunchKernelGGL(sl_gemm_kernel, grid, dim3(256), 0, c->stream, c->Xs.p, (int)c->xpitch, (int)s0, (int)s1,
-                       c->map.p, (int)c->pitch, (int)c->N, (int)c->xpitch, c->sl_nrm.p, c->sl_G.p, (int)ldg, c->sl_tmin.p, (int)ntm,
-                       (const unsigned *)nullptr, (const unsigned *)nullptr);
+        VSOM_PLAN_LAUNCH(sl_norm_kernel, p.norm, c->stream, c->map.p, (int)c->pitch, (int)c->part_pitch, N, c->sl_nrm.p, scal);
+        if (p.compact) {
+            if (int rc = vsom_cc_gather_map(c))
+                return rc;
+        }
+        const float *X = p.compact ? c->Xc.p : c->Xs.p, *M = p.compact ? c->Mc.p : c->map.p;
+        const unsigned *kp_dev = p.compact ? (const unsigned *)c->cc_meta.p : nullptr;
+        VSOM_PLAN_LAUNCH(sl_gemm_kernel, p.contract, c->stream, X, (int)p.kmax, (int)s0, (int)s1, M, (int)(p.compact ? c->cpitch : c->pitch),
+                         N, (int)p.kmax, c->sl_nrm.p, c->sl_G.p, ldg, c->sl_tmin.p, ntm, kp_dev, (const unsigned *)nullptr);
     }
     DistArgs a;
     a.xa = c->Xs.p;
@@ -819,34 +785,30 @@ int launch_bmu_full_shortlist(vsom_ctx *c, size_t s0, size_t s1)
     a.mb = c->map.p;
     a.ldm = (int)c->pitch;
     a.L = (int)c->part_len;
-    const double K = (double)c->xpitch;
-    const double g1 = ((double)GK + K / GK + 3.0) * u;
-    // integer contraction: |G - (|M|^2 - 2<x,M>)| <= 2 (e_s L1Mmax + l1eff_s eps_max) + 5.1u (nMmax + |x|^2) + 2^-7 eps_max
-    // (vsom_sl_i8.hip; 3.1u with the fp64 epilogue, 5.1u with the two-rounding fp32 one of the uint8 kind)
-    if (gless && c->D <= 64)
-        hipLaunchKernelGGL(sl_pick_kernel<1>, dim3((unsigned)((nrows + 3) / 4)), dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)c->N,
-                           (int)c->D, c->sl_tmin.p, (int)ntm, scal, (float)(5.5 * u), (float)(2.1 * g2), c->lastbmu.p, c->sqres.p, scal + 2,
-                           c->sl_list.p, scal + 4, 64u, (const float *)c->sl_l1.p, (unsigned)c->Bcap, 2.0f, (const unsigned *)xflag,
-                           (const float *)c->sl_nrm.p);
-    else if (gless && nrows < 4096)     // few samples (a rank's share of a chunk): a workgroup per sample (0.109 -> 0.089 ms at 512)
-        hipLaunchKernelGGL(sl_pick_kernel<4>, dim3((unsigned)nrows), dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)c->N,
-                           (int)c->D, c->sl_tmin.p, (int)ntm, scal, (float)(5.5 * u), (float)(2.1 * g2), c->lastbmu.p, c->sqres.p, scal + 2,
-                           c->sl_list.p, scal + 4, 64u, (const float *)c->sl_l1.p, (unsigned)c->Bcap, 2.0f, (const unsigned *)xflag,
-                           (const float *)c->sl_nrm.p);
-    else if (gless)
-        hipLaunchKernelGGL(sl_pick_kernel<2>, dim3((unsigned)((nrows + 1) / 2)), dim3(256), 0, c->stream, a, (int)s0, (int)s1, (int)c->N,
-                           (int)c->D, c->sl_tmin.p, (int)ntm, scal, (float)(5.5 * u), (float)(2.1 * g2), c->lastbmu.p, c->sqres.p, scal + 2,
-                           c->sl_list.p, scal + 4, 64u, (const float *)c->sl_l1.p, (unsigned)c->Bcap, 2.0f, (const unsigned *)xflag,
-                           (const float *)c->sl_nrm.p);
-    else
-    hipLaunchKernelGGL(sl_select_kernel<false>, dim3((unsigned)nrows), dim3(256), 0, c->stream, a, (int)s0,
-                       (int)s1, (int)c->N, (int)c->D, c->sl_G.p, (int)ldg, c->sl_tmin.p, (int)ntm, scal, (float)(i8 ? 5.5 * u : 2.0 * g1),
-                       (float)(2.1 * g2), c->lastbmu.p, c->sqres.p, scal + 2, c->sl_list.p, scal + 4, (const float *)nullptr, 0, 0, 0.f,
-                       (unsigned)SL_CMAX, (const float *)c->sl_l1.p, (unsigned)c->Bcap, i8 ? 2.0f : 0.f, (const unsigned *)xflag,
-                       (const float *)nullptr, (const float *)nullptr, (const float *)c->sl_nrm.p);
+#define SL_PICK_LAUNCH(WPS)                                                                                                      \
+    VSOM_PLAN_LAUNCH(sl_pick_kernel<WPS>, p.refine, c->stream, a, (int)s0, (int)s1, N, (int)c->D, c->sl_tmin.p, ntm, scal, p.thr_approx, \
+                     p.thr_exact, c->lastbmu.p, c->sqres.p, scal + 2, c->sl_list.p, scal + 4, p.cand_cap, (const float *)c->sl_l1.p, \
+                     (unsigned)c->Bcap, p.digit_slack, (const unsigned *)xflag, (const float *)c->sl_nrm.p)
+    switch (p.refine_kind == VSOM_SLR_PICK ? p.wps : 0) {
+    case 1:
+        SL_PICK_LAUNCH(1);
+        break;
+    case 4:
+        SL_PICK_LAUNCH(4);
+        break;
+    case 2:
+        SL_PICK_LAUNCH(2);
+        break;
+    default:
+        VSOM_PLAN_LAUNCH(sl_select_kernel<false>, p.refine, c->stream, a, (int)s0, (int)s1, N, (int)c->D, c->sl_G.p, ldg, c->sl_tmin.p, ntm,
+                         scal, p.thr_approx, p.thr_exact, c->lastbmu.p, c->sqres.p, scal + 2, c->sl_list.p, scal + 4, (const float *)nullptr,
+                         0, 0, 0.f, p.cand_cap, (const float *)c->sl_l1.p, (unsigned)c->Bcap, p.digit_slack, (const unsigned *)xflag,
+                         (const float *)nullptr, (const float *)nullptr, (const float *)c->sl_nrm.p);
+    }
+#undef SL_PICK_LAUNCH
     VSOM_HIP_CHECK(hipGetLastError());
     // exact-order redo of the listed samples (device-side count; its workgroups walk the list) + the feedback words
-    const SlFeedback fb = {scal, c->sl_fb.p, (unsigned)nrows, i8 ? (const unsigned *)xflag : (const unsigned *)nullptr, scal_next};
+    const SlFeedback fb = {scal, c->sl_fb.p, (unsigned)p.rows, p.fb_xflag ? (const unsigned *)xflag : (const unsigned *)nullptr, scal_next};
     return launch_bmu_full_exact_list(c, s0, s1, c->sl_list.p, scal + 2, &fb);
 }
 
@@ -997,35 +959,25 @@ __global__ __launch_bounds__(256) void clr_node_feat_kernel(const float *__restr
     }
 }
 
-static int launch_bmu_full_shortlist_clr(vsom_ctx *c, size_t s0, size_t s1)
+int launch_bmu_full_shortlist_clr(vsom_ctx *c, size_t s0, size_t s1, const SearchPlan &p)
 {
-    // the select kernel keeps the sample's x' / y' rows in LDS (2 * part_pitch floats beside 8.3 KB of
-    // static storage): beyond 48 KB (J > 110) the exact-order kernel searches instead
-    if ((size_t)2 * c->part_pitch * sizeof(float) > 48 * 1024)
-        return launch_bmu_full_exact_list(c, s0, s1, nullptr, nullptr, nullptr);
-    const size_t nrows = s1 - s0;
-    const uint32_t P = c->part_len, J = c->J;
-    const uint32_t P32 = (P + 31) / 32 * 32, Kp = P32 + (3 * J + 31) / 32 * 32;
-    const size_t ldg = ((size_t)c->N + 127) / 128 * 128;
-    const size_t ntm = (((size_t)c->N + GT - 1) / GT) * 2;
-    VSOM_ALLOC_CHECK(vsom_grow(c->sl_G, nrows * ldg, c->stream));
-    VSOM_ALLOC_CHECK(vsom_grow(c->sl_tmin, nrows * ntm, c->stream));
-    VSOM_ALLOC_CHECK(vsom_grow(c->sl_list, nrows, c->stream));
+    const int P = (int)c->part_len, J = (int)c->J, Kp = (int)p.Kp, P32 = (int)p.P32, N = (int)c->N, ldg = (int)p.ldg, ntm = (int)p.ntm;
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_G, p.g_elems, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_tmin, p.tmin_elems, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_list, p.rows, c->stream));
     VSOM_ALLOC_CHECK(sl_ensure_scalars(c));
-    VSOM_ALLOC_CHECK(vsom_grow(c->sl_fs, c->B * (size_t)Kp, c->stream));
-    VSOM_ALLOC_CHECK(vsom_grow(c->sl_fm, (size_t)c->N * Kp, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_fs, p.fs_elems, c->stream));
+    VSOM_ALLOC_CHECK(vsom_grow(c->sl_fm, p.fm_elems, c->stream));
     VSOM_ALLOC_CHECK(vsom_grow(c->sl_a2, c->N, c->stream));
     // scal: [0] max nB bits, [1] non-finite flag, [2] redo count, [3] max A^2 bits, [4] redo samples
     unsigned *scal = c->sl_scal.p + 4096 * c->sl_par, *scal_next = c->sl_scal.p + 4096 * (c->sl_par ^ 1);
     c->sl_par ^= 1;
-    hipLaunchKernelGGL(clr_node_feat_kernel, dim3((unsigned)c->N), dim3(256), 0, c->stream, c->map.p, (int)c->pitch,
-                       (int)c->part_pitch, (int)P, (int)J, c->sl_fm.p, (int)Kp, (int)P32, (int)c->N, c->sl_nrm.p, c->sl_a2.p, scal);
-    hipLaunchKernelGGL(clr_sample_feat_kernel, dim3((unsigned)nrows), dim3(256), 0, c->stream, c->XP.p, c->YP.p, (int)c->part_pitch,
-                       (int)P, c->Xs.p, (int)c->xpitch, (int)J, c->sl_fs.p, (int)Kp, (int)P32, (int)s0, (int)s1, (const unsigned *)scal);
-    dim3 grid((unsigned)((c->N + GT - 1) / GT), (unsigned)((nrows + GT - 1) / GT));
-    hipLaunchKernelGGL(sl_gemm_kernel, grid, dim3(256), 0, c->stream, c->sl_fs.p, (int)Kp, (int)s0, (int)s1, c->sl_fm.p, (int)Kp,
-                       (int)c->N, (int)Kp, c->sl_nrm.p, c->sl_G.p, (int)ldg, c->sl_tmin.p, (int)ntm, (const unsigned *)nullptr,
-                       (const unsigned *)scal);
+    VSOM_PLAN_LAUNCH(clr_node_feat_kernel, p.norm, c->stream, c->map.p, (int)c->pitch, (int)c->part_pitch, P, J, c->sl_fm.p, Kp, P32, N,
+                     c->sl_nrm.p, c->sl_a2.p, scal);
+    VSOM_PLAN_LAUNCH(clr_sample_feat_kernel, p.sample_feat, c->stream, c->XP.p, c->YP.p, (int)c->part_pitch, P, c->Xs.p, (int)c->xpitch, J,
+                     c->sl_fs.p, Kp, P32, (int)s0, (int)s1, (const unsigned *)scal);
+    VSOM_PLAN_LAUNCH(sl_gemm_kernel, p.contract, c->stream, c->sl_fs.p, Kp, (int)s0, (int)s1, c->sl_fm.p, Kp, N, Kp, c->sl_nrm.p, c->sl_G.p,
+                     ldg, c->sl_tmin.p, ntm, (const unsigned *)nullptr, (const unsigned *)scal);
     DistArgs a;
     a.xa = c->XP.p;
     a.xb = c->YP.p;
@@ -1033,18 +985,13 @@ static int launch_bmu_full_shortlist_clr(vsom_ctx *c, size_t s0, size_t s1)
     a.ma = c->map.p;
     a.mb = c->map.p + c->part_pitch;
     a.ldm = (int)c->pitch;
-    a.L = (int)P;
-    const double u = 5.9604644775390625e-08;   // 2^-24
-    const double g1 = ((double)GK + (double)Kp / GK + 3.0) * u, gf = ((double)J + 3.0) * u;
-    const double ga = 3.01 * (g1 + gf) + ((double)P / 256.0 + 12.0 + 7.0) * u;   // + the final nB - 2*dot rounding
-    const double g2 = ((double)P / 8.0 + 10.0) * u, e1 = 6.1 * 1.7320508075688773 * u;
-    const size_t xy_bytes = (size_t)2 * c->part_pitch * sizeof(float);   // + 8.3 KB static: fits the default 64 KB up to J = 120
-    hipLaunchKernelGGL(sl_select_kernel<true>, dim3((unsigned)nrows), dim3(256), xy_bytes, c->stream, a, (int)s0, (int)s1, (int)c->N,
-                       (int)c->D, c->sl_G.p, (int)ldg, c->sl_tmin.p, (int)ntm, scal, (float)(1.0001 * ga), (float)(1.0001 * g2),
-                       c->lastbmu.p, c->sqres.p, scal + 2, c->sl_list.p, scal + 4, c->Xs.p, (int)c->xpitch, (int)J, (float)(1.0001 * e1), 128u,
-                       (const float *)nullptr, 0u, 0.f, (const unsigned *)nullptr, (const float *)c->sl_nrm.p, (const float *)c->sl_a2.p,
-                       (const float *)nullptr);
+    a.L = P;
+    // (the x' / y' rows in dynamic LDS + 8.3 KB static: within the default 64 KB limit)
+    VSOM_PLAN_LAUNCH(sl_select_kernel<true>, p.refine, c->stream, a, (int)s0, (int)s1, N, (int)c->D, c->sl_G.p, ldg, c->sl_tmin.p, ntm, scal,
+                     p.thr_approx, p.thr_exact, c->lastbmu.p, c->sqres.p, scal + 2, c->sl_list.p, scal + 4, c->Xs.p, (int)c->xpitch, J,
+                     p.thr_e1, p.cand_cap, (const float *)nullptr, 0u, 0.f, (const unsigned *)nullptr, (const float *)c->sl_nrm.p,
+                     (const float *)c->sl_a2.p, (const float *)nullptr);
     VSOM_HIP_CHECK(hipGetLastError());
-    const SlFeedback fb = {scal, c->sl_fb.p, (unsigned)nrows, (const unsigned *)nullptr, scal_next};
+    const SlFeedback fb = {scal, c->sl_fb.p, (unsigned)p.rows, (const unsigned *)nullptr, scal_next};
     return launch_bmu_full_exact_list(c, s0, s1, c->sl_list.p, scal + 2, &fb);
 }

@@ -26,6 +26,7 @@
 // 2 g1 (nMmax + |x|^2), g1 = (32 + K/32 + 3) u.
 // Samples holding NaN / inf / overflowing values are redone exactly through the |x|^2 test of the select kernel.
 #include "vsom_digits.hpp"
+#include "vsom_search_plan.hpp"
 #include <cstdlib>
 
 typedef int v4i __attribute__((ext_vector_type(4)));
@@ -783,9 +784,6 @@ __global__ __launch_bounds__(256, XD == 1 ? 3 : 2) void sl_gemm_i8_kernel(const 
 // A wave-instruction deposits 1 KB contiguously (16 rows x 64 B); the 16-byte pieces of a row are stored XOR-swizzled
 // (slot = piece ^ ((row >> 2) & 3), applied on the GLOBAL side: each lane picks the piece that belongs into its slot),
 // which makes the 16-byte fragment reads of 32 consecutive rows conflict-free without row padding.
-#define RT_S 256
-#define RT_N 128
-#define RING_BYTES 147456      // max(3 x 40960, 2 x 73728)
 template <int XD, int WM, int NS, bool FAST, bool GLESS = false>
 __device__ __forceinline__ void sl_gemm_i8_ring_body(const signed char *__restrict__ xi, size_t xplane, int s0, int s1,
                                                      const signed char *__restrict__ q, int N, int kp, int kp8,
@@ -1084,8 +1082,6 @@ __global__ __launch_bounds__(512, 1) void sl_gemm_i8_ring_gless_kernel(const sig
 // matrix pipe: accumulators start from the MFMA's zero operand instead of 48 moves.  (Two digits per value instead of three -- half the MFMAs, 6
 // instructions per value, bound terms x 128 -- measured at C4: kernel 30 instead of 34 us, but 4.7 instead of 1.0
 // candidate tiles per sample on the trained map: refinement 45 instead of 22 us.  Dropped.)
-#define K64_NB 16         // node blocks of 32 per workgroup (its 256 threads stage the constants of these 512 nodes)
-#define K64_SB 2          // sample blocks of 32 per wavefront: every model fragment feeds two MFMAs (see below)
 template <int XD>         // sample planes: 1 (uint8 image) or 3 (digits)
 __device__ __forceinline__ void sl_k64_body(const signed char *__restrict__ xi, size_t xplane, int s0, int s1,
                                             const signed char *__restrict__ q, int N, const float *__restrict__ xscale,
@@ -1216,54 +1212,46 @@ static int sl_i8_ensure(vsom_ctx *c, uint32_t kp8)
     return VSOM_OK;
 }
 
+// the sample images of B rows (src, or its columns idx gathered into dst as well) on `stream`; xi / l1 / xflag null: the
+// gather alone
+static void sl_quant_launch(const vsom_ctx *c, bool quant64, size_t B, hipStream_t stream, const float *src, uint32_t lds, float *dst,
+                            uint32_t ldd, const int *idx, uint32_t kp8, signed char *xi, float *l1, unsigned *xflag)
+{
+    const SearchLaunch l = {vsom_sl_quant_grid(quant64, B)};
+    const size_t xplane = (size_t)c->Bcap * kp8;
+    if (quant64)
+        VSOM_PLAN_LAUNCH(sl_quant_rows64_kernel, l, stream, src, (int)lds, dst, (int)ldd, idx, (int)B, xi, xplane, l1, (size_t)c->Bcap, xflag);
+    else
+        VSOM_PLAN_LAUNCH(sl_quant_rows_kernel, l, stream, src, (int)lds, dst, (int)ldd, idx, (int)B, xi, xplane, (int)kp8, l1,
+                         (size_t)c->Bcap, xflag);
+}
+
 // the compaction's gather pass (vsom_compact.hip): the staged rows onto the live columns and -- once the integer
 // shortlist's buffers exist (the first search of a context allocates them) -- their int8 images in the same pass
 int launch_sl_gather_quant(vsom_ctx *c, size_t B, hipStream_t stream, const int *idx, bool *xi_out)
 {
     const uint32_t kp8 = (c->cpitch + 63) / 64 * 64;
     const bool xi = c->sl_xi.p && c->sl_kp8 == kp8 && (size_t)4 * c->Bcap * kp8 <= c->sl_xi.cap && c->sl_scal.p;
-    if (kp8 == 64)
-        hipLaunchKernelGGL(sl_quant_rows64_kernel, dim3((unsigned)((B + 15) / 16)), dim3(256), 0, stream, c->Xs.p, (int)c->xpitch, c->Xc.p,
-                           (int)c->cpitch, idx, (int)B, xi ? c->sl_xi.p : (signed char *)nullptr, (size_t)c->Bcap * kp8,
-                           xi ? c->sl_l1.p : (float *)nullptr, (size_t)c->Bcap, xi ? c->sl_scal.p + 8192 : (unsigned *)nullptr);
-    else
-    hipLaunchKernelGGL(sl_quant_rows_kernel, dim3((unsigned)B), dim3(256), 0, stream, c->Xs.p, (int)c->xpitch, c->Xc.p,
-                       (int)c->cpitch, idx, (int)B, xi ? c->sl_xi.p : (signed char *)nullptr, (size_t)c->Bcap * kp8, (int)kp8,
-                       xi ? c->sl_l1.p : (float *)nullptr, (size_t)c->Bcap, xi ? c->sl_scal.p + 8192 : (unsigned *)nullptr);
+    sl_quant_launch(c, vsom_sl_quant64(kp8), B, stream, c->Xs.p, c->xpitch, c->Xc.p, c->cpitch, idx, kp8,
+                    xi ? c->sl_xi.p : (signed char *)nullptr, xi ? c->sl_l1.p : (float *)nullptr,
+                    xi ? c->sl_scal.p + 8192 : (unsigned *)nullptr);
     VSOM_HIP_CHECK(hipGetLastError());
     *xi_out = xi;
     return VSOM_OK;
 }
 
-// prepares the int8 images and computes G / tmin for samples [s0, s1) (ldg, ntm as the fp32 path lays them out: 64-node
-// tile minima); scal = the counter set THIS search's select / feedback kernels read (the two sets alternate,
-// vsom_shortlist.hip), already reset
-// Which form a search of samples [s0, s1) takes: 0 = G and 64-node tile minima (sl_select_kernel refines), 1 = no G, 16-node
-// tile minima from sl_k64_kernel (at most 64 contracted columns), 2 = no G, from the ring kernel (big problems, K <= 960);
-// 1 and 2 are refined by sl_pick_kernel.  (The attribute is per DEVICE -- a group drives several from one process -- so it
-// is raised on every call, as launch_phase2 does.)
-int sl_i8_plan(vsom_ctx *c, size_t s0, size_t s1)
+bool sl_i8_raise_ring_lds(SlContraction ring)
 {
-    const uint32_t kp8 = ((c->cc_valid ? c->cpitch : c->xpitch) + 63) / 64 * 64;
-    if (kp8 == 64)
-        return 1;
-    const size_t big_tiles = ((size_t)c->N + RT_N - 1) / RT_N * ((s1 - s0 + RT_S - 1) / RT_S);
-    if (kp8 <= 960 && big_tiles >= 256) {
-        if (hipFuncSetAttribute((const void *)sl_gemm_i8_ring_gless_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                RING_BYTES) == hipSuccess)
-            return 2;
-        (void)hipGetLastError();
-    }
-    return 0;
+    const void *k = ring == VSOM_SLC_RING_GLESS ? (const void *)sl_gemm_i8_ring_gless_kernel : (const void *)sl_gemm_i8_ring_kernel;
+    if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, RING_BYTES) == hipSuccess)
+        return true;
+    (void)hipGetLastError();
+    return false;
 }
 
-int launch_sl_i8(vsom_ctx *c, size_t s0, size_t s1, size_t ldg, size_t ntm, unsigned *scal, unsigned *xflag, int plan)
+int launch_sl_i8(vsom_ctx *c, size_t s0, size_t s1, const SearchPlan &p, unsigned *scal, unsigned *xflag)
 {
-    const bool gless = plan == 1;
-    const bool compact = c->cc_valid;
-    const uint32_t kmax = compact ? c->cpitch : c->xpitch;
-    const uint32_t kp8 = (kmax + 63) / 64 * 64;
-    if (int rc = sl_i8_ensure(c, kp8))
+    if (int rc = sl_i8_ensure(c, p.kp8))
         return rc;
 #ifdef VSOM_DEVELOPMENT
     {
@@ -1276,73 +1264,47 @@ int launch_sl_i8(vsom_ctx *c, size_t s0, size_t s1, size_t ldg, size_t ntm, unsi
         }
     }
 #endif
-    const size_t xplane = (size_t)c->Bcap * kp8;
+    const int kmax = (int)p.kmax, kp8 = (int)p.kp8, N = (int)c->N, ldg = (int)p.ldg, ntm = (int)p.ntm;
+    const size_t xplane = (size_t)c->Bcap * p.kp8;
     if (!c->xi_valid) {      // once per staged chunk (the compaction's gather pass does it when the buffers exist)
-        if (kp8 == 64)
-            hipLaunchKernelGGL(sl_quant_rows64_kernel, dim3((unsigned)((c->B + 15) / 16)), dim3(256), 0, c->stream,
-                               compact ? c->Xc.p : c->Xs.p, (int)kmax, (float *)nullptr, (int)kmax, (const int *)nullptr, (int)c->B,
-                               c->sl_xi.p, xplane, c->sl_l1.p, (size_t)c->Bcap, xflag);
-        else
-        hipLaunchKernelGGL(sl_quant_rows_kernel, dim3((unsigned)c->B), dim3(256), 0, c->stream, compact ? c->Xc.p : c->Xs.p, (int)kmax,
-                           (float *)nullptr, (int)kmax, (const int *)nullptr, (int)c->B, c->sl_xi.p, xplane, (int)kp8, c->sl_l1.p,
-                           (size_t)c->Bcap, xflag);
+        sl_quant_launch(c, p.quant64, c->B, c->stream, p.compact ? c->Xc.p : c->Xs.p, p.kmax, nullptr, p.kmax, nullptr, p.kp8,
+                        c->sl_xi.p, c->sl_l1.p, xflag);
         c->xi_valid = true;
     }
     const float *xscale = c->sl_l1.p + c->Bcap;
-    const unsigned *kp_dev = compact ? (const unsigned *)c->cc_meta.p : nullptr;
-    if (kp8 == 64 && c->part_pitch <= 64)
-        hipLaunchKernelGGL(sl_prepare64_kernel, dim3((unsigned)((c->N + 15) / 16)), dim3(256), 0, c->stream, c->map.p, (int)c->pitch,
-                           (int)c->part_pitch, (int)c->N, compact ? (const int *)c->cc_idx.p : (const int *)nullptr, (int)kmax, kp_dev,
-                           c->sl_q.p, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, c->sl_qfast.p, scal, xflag);
+    const int *cc_idx = p.compact ? (const int *)c->cc_idx.p : nullptr;
+    const unsigned *kp_dev = p.compact ? (const unsigned *)c->cc_meta.p : nullptr;
+    if (p.prepare64)
+        VSOM_PLAN_LAUNCH(sl_prepare64_kernel, p.prepare, c->stream, c->map.p, (int)c->pitch, (int)c->part_pitch, N, cc_idx, kmax, kp_dev,
+                         c->sl_q.p, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, c->sl_qfast.p, scal, xflag);
     else
-    hipLaunchKernelGGL(sl_prepare_i8_kernel, dim3((unsigned)((c->N + 3) / 4)), dim3(256), 0, c->stream, c->map.p, (int)c->pitch,
-                       (int)c->part_pitch, (int)c->N, compact ? (const int *)c->cc_idx.p : (const int *)nullptr, (int)kmax, kp_dev,
-                       (int)kp8, c->sl_q.p, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, c->sl_qfast.p, scal, xflag);
-    // the fp32 two-fma epilogue of the uint8 kind needs |A| < 2^24: K <= 960 contracted columns (sl_i8_value_fast)
-    const int4 *qfast = kp8 <= 960 ? c->sl_qfast.p : (const int4 *)nullptr;
-    if (gless) {             // K <= 64: tile minima only (ntm = 16-node tiles), the refinement is sl_pick_kernel
-        if (kp8 != 64)
-            return VSOM_ERR_INVALID;
-        dim3 grid((unsigned)((c->N + K64_NB * 32 - 1) / (K64_NB * 32)), (unsigned)((s1 - s0 + 128 * K64_SB - 1) / (128 * K64_SB)));
-        hipLaunchKernelGGL(sl_k64_kernel, grid, dim3(256), 0, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1, c->sl_q.p, (int)c->N,
-                           c->sl_nrm.p, c->sl_qfast.p, xscale, c->sl_tmin.p, (int)ntm, (const unsigned *)xflag, scal);
-        VSOM_HIP_CHECK(hipGetLastError());
-        return VSOM_OK;
+        VSOM_PLAN_LAUNCH(sl_prepare_i8_kernel, p.prepare, c->stream, c->map.p, (int)c->pitch, (int)c->part_pitch, N, cc_idx, kmax, kp_dev,
+                         kp8, c->sl_q.p, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, c->sl_qfast.p, scal, xflag);
+    const int4 *qfast = p.qfast ? c->sl_qfast.p : (const int4 *)nullptr;
+    // the G kernels share one argument list
+#define SL_I8_G_LAUNCH(K)                                                                                                        \
+    VSOM_PLAN_LAUNCH(K, p.contract, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1, c->sl_q.p, N, kmax, kp_dev, kp8, c->sl_nrm.p, \
+                     c->sl_qscale.p, c->sl_qcorr.p, xscale, c->sl_G.p, ldg, c->sl_tmin.p, ntm, (const unsigned *)xflag, qfast, scal)
+    switch (p.contraction) {
+    case VSOM_SLC_K64:
+        VSOM_PLAN_LAUNCH(sl_k64_kernel, p.contract, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1, c->sl_q.p, N, c->sl_nrm.p, qfast,
+                         xscale, c->sl_tmin.p, ntm, (const unsigned *)xflag, scal);
+        break;
+    case VSOM_SLC_RING_GLESS:
+        VSOM_PLAN_LAUNCH(sl_gemm_i8_ring_gless_kernel, p.contract, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1, c->sl_q.p, N, kmax,
+                         kp_dev, kp8, c->sl_nrm.p, xscale, c->sl_tmin.p, ntm, (const unsigned *)xflag, qfast, scal);
+        break;
+    case VSOM_SLC_RING_G:
+        SL_I8_G_LAUNCH(sl_gemm_i8_ring_kernel);
+        break;
+    case VSOM_SLC_SMALL_TILES:
+        SL_I8_G_LAUNCH((sl_gemm_i8_kernel<2, 1>));
+        SL_I8_G_LAUNCH((sl_gemm_i8_kernel<2, 3>));
+        break;
+    default:
+        return VSOM_ERR_INVALID;
     }
-    if (plan == 2) {         // the ring kernel without G (ntm = 16-node tiles)
-        dim3 grid((unsigned)((c->N + RT_N - 1) / RT_N), (unsigned)((s1 - s0 + RT_S - 1) / RT_S));
-        hipLaunchKernelGGL(sl_gemm_i8_ring_gless_kernel, grid, dim3(512), RING_BYTES, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1,
-                           c->sl_q.p, (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm.p, xscale, c->sl_tmin.p, (int)ntm,
-                           (const unsigned *)xflag, c->sl_qfast.p, scal);
-        VSOM_HIP_CHECK(hipGetLastError());
-        return VSOM_OK;
-    }
-    // big maps and chunks: 256 x 128 tiles through the LDS-DMA ring; otherwise (few tiles: they would not fill the
-    // chip) 128 x 64 tiles staged through registers
-    const size_t big_tiles = ((size_t)c->N + RT_N - 1) / RT_N * ((s1 - s0 + RT_S - 1) / RT_S);
-    // the attribute is per DEVICE (a group drives several from one process): raised on every launch, as launch_phase2 does
-    bool ring_ok = false;
-    if (big_tiles >= 1024) {
-        ring_ok = hipFuncSetAttribute((const void *)sl_gemm_i8_ring_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                      RING_BYTES) == hipSuccess;
-        if (!ring_ok)
-            (void)hipGetLastError();
-    }
-    if (ring_ok) {
-        dim3 grid((unsigned)(ntm / 2), (unsigned)((s1 - s0 + RT_S - 1) / RT_S));   // ntm = 2 ceil(N / 128) 64-node tiles
-        hipLaunchKernelGGL(sl_gemm_i8_ring_kernel, grid, dim3(512), RING_BYTES, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1,
-                           c->sl_q.p, (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, xscale, c->sl_G.p,
-                           (int)ldg, c->sl_tmin.p, (int)ntm, (const unsigned *)xflag, qfast, scal);
-    } else {
-        constexpr int MI = 2;
-        dim3 grid((unsigned)ntm, (unsigned)((s1 - s0 + 64 * MI - 1) / (64 * MI)));   // ntm 64-node tiles (the last may lie past N: minima +inf)
-        hipLaunchKernelGGL((sl_gemm_i8_kernel<MI, 1>), grid, dim3(256), 0, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1, c->sl_q.p,
-                           (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, xscale, c->sl_G.p, (int)ldg,
-                           c->sl_tmin.p, (int)ntm, (const unsigned *)xflag, qfast, scal);
-        hipLaunchKernelGGL((sl_gemm_i8_kernel<MI, 3>), grid, dim3(256), 0, c->stream, c->sl_xi.p, xplane, (int)s0, (int)s1, c->sl_q.p,
-                           (int)c->N, (int)kmax, kp_dev, (int)kp8, c->sl_nrm.p, c->sl_qscale.p, c->sl_qcorr.p, xscale, c->sl_G.p, (int)ldg,
-                           c->sl_tmin.p, (int)ntm, (const unsigned *)xflag, qfast, scal);
-    }
+#undef SL_I8_G_LAUNCH
     VSOM_HIP_CHECK(hipGetLastError());
     return VSOM_OK;
 }
