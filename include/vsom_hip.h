@@ -567,6 +567,56 @@ int vsom_generate_batch(vsom_ctx *ctx, uint64_t min_hits, int rule, size_t r0, s
  * Refuses (VSOM_ERR_INVALID, nothing enqueued): a null context, l_host or record_out, a null nodes_host with count > 0,
  * custom contexts, C = 0, a node >= N.  count = 0 returns VSOM_OK and enqueues nothing. */
 int vsom_decode_nodes(vsom_ctx *ctx, const uint64_t *nodes_host, size_t count, const double *l_host, double *record_out);
+/* vsom_bmd_batch and vsom_generate_batch for records with missing fields: the distribution over the units is taken over the
+ * VALID columns of every row, and the records sampled from it keep what was observed -- the sampled (multiple) imputation next
+ * to the point imputation of vsom_bmu_masked_batch's fill.  (The unmasked calls take a missing field for a measured zero: the
+ * mass moves towards units near 0 there, and one wild placeholder, d > ~38.6, leaves the row without mass.)  Standard and
+ * Median (D = J).  One call, one stream wait, nothing of size N x D moves.
+ * Mask: as vsom_bmu_masked_batch -- valid_host is (r1-r0) x J bytes, row-major (entry (r - r0) * J + d belongs to chunk row r),
+ * when one_mask == 0, and J bytes applied to every row when one_mask != 0; a non-zero byte means valid; required.
+ *
+ * vsom_bmd_masked_batch is vsom_bmd_batch, word for word, on the masked distance of vsom_bmu_masked_batch: r_d = valid ?
+ * (m_d - x_d) : +0.0f as a select on the bits, d_i = r.dot(r) in the Eigen packet order of the exact tile;
+ * p_i = bmuHits[i] >= min_hits ? exp(-(double)d_i * d_i / 2) : 0 (node 0 is not exempt), C = ((0 + p_0) + p_1) + ... in node
+ * order, in double; the draw is the smallest i whose running sum exceeds u * C, the largest i with p_i > 0 when rounding
+ * leaves none, UINT64_MAX when C is 0 or not finite; prob is p_i / C.
+ *   u_host[r1-r0], draw_out[r1-r0], norm_out[r1-r0], prob_out[(r1-r0)*N]   as vsom_bmd_batch's (each output may be NULL;
+ *                                                                          u_host is required iff draw_out != NULL)
+ *  - With an all-valid mask norm, prob and draw are bit-identical to vsom_bmd_batch's (the same operations on the same
+ *    operands: derived, not measured).
+ *  - What a row of the chunk or a model row holds at an invalid position (NaN, +-inf, 1e30) reaches no output.
+ *  - A row without a valid column has d_i = +0 for every node: p_i = 1 on the nodes with enough hits, norm is their count,
+ *    prob exactly 1 / count, and the draw is the floor(u * count)-th of them (counted from 0).
+ *
+ * vsom_generate_masked_batch produces draws = K >= 1 records per row:
+ *   u_host[(r1-r0)*K]      uniforms in [0,1), entry (r - r0) * K + k belongs to draw k of row r, required
+ *   l_host[(r1-r0)*K*J]    the L of vsom_generate_batch, entry ((r - r0) * K + k) * J + d, required; not validated
+ *   out->unit[(r1-r0)*K], out->record[(r1-r0)*K*J]   row-major, the draw index inside the row index (each may be NULL)
+ * Unit k of row r is what vsom_bmd_masked_batch draws for row r with the uniform u[(r - r0) * K + k] (the same device
+ * functions on the same distribution: the same bits); only the row's own distribution is used (no "as written" last-row rule).
+ * Column d of that record: with keep_observed != 0 and the column valid for row r it is (double)x[r][d], the staged value
+ * -- a select: L there has no effect, a NaN included --; otherwise vsom_generate_batch's decode around the unit, operation for
+ * operation (q = L / (1 - L); g = log(q); z = g / 1.6; t = z * (double)s; rec = t + (double)m), with that call's accuracy
+ * statement.  A draw without mass has unit UINT64_MAX and the quiet NaN 0x7FF8000000000000 in EVERY column of its record, the
+ * observed ones included.  With keep_observed = 0, draws = 1 and an all-valid mask unit and record are bit-identical to
+ * vsom_generate_batch(VSOM_GENERATE_PER_ROW).
+ *
+ * Read-only: map, sigmaMap, S, weightMap, bmuHits, lastBMU, sqres and the chunk are untouched; vsom_generate_masked_batch
+ * reads sigmaMap, so a pending one is materialised.  Both refuse (VSOM_ERR_INVALID, nothing enqueued, the context stays
+ * usable): a null context or valid_host, custom and CLR contexts (the CLR residual runs over column pairs), no chunk, a chunk
+ * staged ahead, r0 > r1 or r1 > B, a uniform that is NaN or outside [0,1); vsom_bmd_masked_batch: draw_out without u_host;
+ * vsom_generate_masked_batch: a null out, u_host or l_host, draws = 0, draws > 65535.  An empty range returns VSOM_OK and
+ * enqueues nothing.  Device scratch, in the query arena: the rows are taken in slices that respect three budgets (one row
+ * where a single row needs more) -- the node-major p of a slice within 256 MiB (8 N bytes per row), vsom_bmu_masked_batch's
+ * 64 MiB rule for the validity bytes (J + roundup(J, 32) per row; one row of each with one_mask, uploaded and packed once), and
+ * for generate the slice's L and record within 64 MiB each (8 K J bytes per row) plus 16 K bytes of uniforms and units per
+ * row.  VSOM_MASKED_SLICE_ROWS and (generate) VSOM_GENERATE_SLICE_ROWS, read at every call, cap the rows of a slice.  The tile,
+ * the row pass and the draws are timed under VSOM_T_BMU, the decode under VSOM_T_FINISH. */
+int vsom_bmd_masked_batch(vsom_ctx *ctx, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
+                          const double *u_host, uint64_t *draw_out, double *norm_out, double *prob_out);
+int vsom_generate_masked_batch(vsom_ctx *ctx, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
+                               uint32_t draws, int keep_observed, const double *u_host, const double *l_host,
+                               vsom_generate_out *out);
 /* Som::euclidianWeightedDistRaw(pos, v, ones, ones) (Som.cpp:143-157) for `count` pairs; v is
  * chunk row vrows[i] (from_map = 0) or model vector vrows[i] (from_map = 1, the U-matrix case). */
 int vsom_distances_raw(vsom_ctx *ctx, const uint64_t *nodes_host, const uint64_t *vrows_host,

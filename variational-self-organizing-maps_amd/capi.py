@@ -57,6 +57,7 @@ SYMBOLS = [
     "vsom_batch_accum_begin", "vsom_batch_accum_chunk", "vsom_batch_accum_end", "vsom_batch_accum_abort",
     "vsom_batch_accum_chunk_masked", "vsom_train_online_chunk_masked",
     "vsom_similarity_masked_batch", "vsom_evaluate_masked_batch",
+    "vsom_bmd_masked_batch", "vsom_generate_masked_batch",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -292,6 +293,11 @@ def lib():
                                                    C.POINTER(C.c_uint8), C.c_int, C.POINTER(SimilarityMaskedOut)]
         L.vsom_evaluate_masked_batch.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t, fp, fp, C.POINTER(C.c_uint8), C.c_int,
                                                  C.POINTER(EvaluateMaskedOut)]
+    if hasattr(L, "vsom_bmd_masked_batch"):             # (VSOM_LIB may name an older build: tools/bmd_masked_bench.py --lib)
+        L.vsom_bmd_masked_batch.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8), C.c_int, dp, u64p,
+                                            dp, dp]
+        L.vsom_generate_masked_batch.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8), C.c_int,
+                                                 C.c_uint32, C.c_int, dp, dp, C.POINTER(GenerateOut)]
     _lib = L
     return L
 
@@ -831,6 +837,81 @@ class Context:
         check(lib().vsom_evaluate_masked_batch(self._h, int(min_hits), r0, r1, _f(cols[0]), _f(cols[1]),
                                                vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one), C.byref(out)))
         res["error"] = float(res["error"][0])
+        return res
+
+    def restricted_bmd_masked(self, valid, min_hits, r0=0, r1=None, u=None, probs=False):
+        """restricted_bmd for records with missing fields (vsom_bmd_masked_batch; Standard / Median): the distribution of
+        chunk rows [r0, r1) over the units from the distance over their valid columns only, as bmu_masked's.  valid: rows x J
+        (nonzero = valid), or a 1-D column mask of J entries applied to every row.  restricted_bmd's dict.  Read-only."""
+        B = self.chunk_size
+        r0 = int(r0)
+        r1 = B if r1 is None else int(r1)
+        if int(min_hits) < 0:
+            raise ValueError("min_hits must be >= 0")
+        if r0 < 0 or r0 > r1 or r1 > B:
+            raise ValueError(f"row range [{r0}, {r1}) is not within the chunk's {B} rows")
+        n = r1 - r0
+        vb, one = self._mask_bytes(valid, n)
+        dp = C.POINTER(C.c_double)
+        norm = np.empty(n, np.float64)
+        draw = prob = up = None
+        if u is not None:
+            u = self._uniforms(u, (n,))
+            up = u.ctypes.data_as(dp)
+            draw = np.empty(n, np.uint64)
+        if probs:
+            prob = np.empty((n, self.n_nodes), np.float64)
+        check(lib().vsom_bmd_masked_batch(self._h, int(min_hits), r0, r1, vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one), up,
+                                          _u(draw), norm.ctypes.data_as(dp), None if prob is None else prob.ctypes.data_as(dp)))
+        return {"norm": norm, "draw": draw, "prob": prob}
+
+    @staticmethod
+    def _uniforms(u, shape):
+        u = np.ascontiguousarray(u, dtype=np.float64)
+        if u.shape != shape:
+            raise ValueError(f"u has shape {u.shape}, not {shape}")
+        if not ((u >= 0.0) & (u < 1.0)).all():
+            raise ValueError("every uniform must lie in [0, 1)")
+        return u
+
+    def generate_masked(self, valid, min_hits, u, l, draws=1, keep_observed=True, r0=0, r1=None):
+        """Sampled imputation of chunk rows [r0, r1) in one call (vsom_generate_masked_batch; Standard / Median): draws = K
+        units per row, drawn with the uniforms u[r, k] from the row's distribution over its valid columns
+        (restricted_bmd_masked's draw), and around each unit a record whose valid columns are the row's own values
+        (keep_observed) and whose other columns are sampled as generate does, l: float64[rows, K, J].  valid as in
+        restricted_bmd_masked.  A dict: unit (uint64[rows, K], NO_UNIT = no mass) and record (float64[rows, K, J], NaN
+        throughout for a draw without mass).  u and l may also come as [rows] and [rows, J] when draws is 1.  Read-only."""
+        B = self.chunk_size
+        r0 = int(r0)
+        r1 = B if r1 is None else int(r1)
+        K = int(draws)
+        if not 1 <= K <= 65535:
+            raise ValueError(f"draws = {draws} is not in [1, 65535]")
+        if int(min_hits) < 0:
+            raise ValueError("min_hits must be >= 0")
+        if r0 < 0 or r0 > r1 or r1 > B:
+            raise ValueError(f"row range [{r0}, {r1}) is not within the chunk's {B} rows")
+        n = r1 - r0
+        J = self.in_len
+        vb, one = self._mask_bytes(valid, n)
+        u = np.asarray(u, dtype=np.float64)
+        l = np.asarray(l, dtype=np.float64)
+        if K == 1 and u.shape == (n,):
+            u = u.reshape(n, 1)
+        if K == 1 and l.shape == (n, J):
+            l = l.reshape(n, 1, J)
+        u = self._uniforms(u, (n, K))
+        l = np.ascontiguousarray(l)
+        if l.shape != (n, K, J):
+            raise ValueError(f"l has shape {l.shape}, not ({n}, {K}, {J})")
+        res = {"unit": np.empty((n, K), np.uint64), "record": np.empty((n, K, J), np.float64)}
+        out = GenerateOut()
+        for name, ctype in GenerateOut._fields_:
+            setattr(out, name, res[name].ctypes.data_as(ctype))
+        dp = C.POINTER(C.c_double)
+        check(lib().vsom_generate_masked_batch(self._h, int(min_hits), r0, r1, vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one),
+                                               K, int(bool(keep_observed)), u.ctypes.data_as(dp), l.ctypes.data_as(dp),
+                                               C.byref(out)))
         return res
 
     def distances_row(self, row):

@@ -941,14 +941,16 @@ int vsom_bmu_masked_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t r1, 
     return launch_masked(c, min_hits, r0, r1, valid_host, one_mask, out);
 }
 
-// the gate the two masked scorers share behind CHECK_CTX (`what`: the entry point's name)
-static int vsom_masked_score_gate(vsom_ctx *c, const char *what, size_t r0, size_t r1, const void *valid_host, const void *out)
+// the gate the masked chunk queries share behind CHECK_CTX (`what`: the entry point's name; has_out: the call takes an
+// `out` structure, which must not be null)
+static int vsom_masked_score_gate(vsom_ctx *c, const char *what, size_t r0, size_t r1, const void *valid_host, const void *out,
+                                  bool has_out = true)
 {
     VSOM_CUSTOM_REFUSE(c, what);
     if (c->transform == VSOM_CLR)
         return vsom_fail(VSOM_ERR_INVALID, std::string(what) + ": CLR contexts are not supported (the residual runs over column pairs)");
     CHECK_ROWS(c);
-    if (!out)
+    if (has_out && !out)
         return vsom_fail(VSOM_ERR_INVALID, "out is null");
     if (!valid_host)
         return vsom_fail(VSOM_ERR_INVALID, "valid_host is null");
@@ -980,6 +982,43 @@ int vsom_evaluate_masked_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t
     if (!binary_host || !continuous_host)
         return vsom_fail(VSOM_ERR_INVALID, "binary_host or continuous_host is null");
     return launch_evaluate_masked(c, min_hits, r0, r1, binary_host, continuous_host, valid_host, one_mask, out);
+}
+
+// the same gate for the masked distribution and its records, and per_row uniforms per row, each in [0,1)
+static int vsom_masked_draw_gate(vsom_ctx *c, const char *what, size_t r0, size_t r1, const void *valid_host, const void *out,
+                                 bool has_out, const double *u_host, size_t per_row)
+{
+    if (int rc = vsom_masked_score_gate(c, what, r0, r1, valid_host, out, has_out))
+        return rc;
+    for (size_t i = 0; u_host && i < (r1 - r0) * per_row; ++i)
+        if (!(u_host[i] >= 0.0 && u_host[i] < 1.0))
+            return vsom_fail(VSOM_ERR_INVALID, "uniform " + std::to_string(i) + " is not in [0,1)");
+    return VSOM_OK;
+}
+
+int vsom_bmd_masked_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
+                          const double *u_host, uint64_t *draw_out, double *norm_out, double *prob_out)
+{
+    CHECK_CTX(c);
+    if (draw_out && !u_host)
+        return vsom_fail(VSOM_ERR_INVALID, "draws need one uniform per row");
+    if (int rc = vsom_masked_draw_gate(c, "vsom_bmd_masked_batch", r0, r1, valid_host, nullptr, false, u_host, 1))
+        return rc;
+    return launch_bmd(c, min_hits, r0, r1, u_host, draw_out, norm_out, prob_out, valid_host, one_mask);
+}
+
+int vsom_generate_masked_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
+                               uint32_t draws, int keep_observed, const double *u_host, const double *l_host,
+                               vsom_generate_out *out)
+{
+    CHECK_CTX(c);                // (reads sigmaMap: a pending one is materialised)
+    if (!u_host || !l_host)
+        return vsom_fail(VSOM_ERR_INVALID, "u_host or l_host is null");
+    if (draws == 0 || draws > 65535)
+        return vsom_fail(VSOM_ERR_INVALID, "draws must be in [1, 65535]");
+    if (int rc = vsom_masked_draw_gate(c, "vsom_generate_masked_batch", r0, r1, valid_host, out, true, u_host, draws))
+        return rc;
+    return launch_generate_masked(c, min_hits, r0, r1, valid_host, one_mask, draws, keep_observed, u_host, l_host, out);
 }
 
 int vsom_distances_row(vsom_ctx *c, size_t row, float *dist_out_host)

@@ -389,24 +389,43 @@ int vsom_sigma_flush_pending(vsom_ctx *c);
 void vsom_sigma_drop(vsom_ctx *c);   // the next full-range epoch overwrites every row: nothing runs
 int launch_bmu_restricted(vsom_ctx *c, u64 min_hits);
 int launch_row_dist(vsom_ctx *c, size_t row, float *out_dev);
-// vsom_bmd.hip: findRestrictedBmd + draws for chunk rows [r0,r1) (arguments checked by vsom_bmd_batch); synchronises
+// vsom_bmd.hip: findRestrictedBmd + draws for chunk rows [r0,r1) (arguments checked by vsom_bmd_batch / vsom_bmd_masked_batch);
+// valid_host: null, or the validity bytes of the masked call (one_mask: J bytes for every row); synchronises
 int launch_bmd(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const double *u_host, uint64_t *draw_out, double *norm_out,
-               double *prob_out);
+               double *prob_out, const uint8_t *valid_host = nullptr, int one_mask = 0);
 // pieces of launch_bmd for callers that lay the scratch out themselves (vsom_generate.hip); they enqueue only.
 // P: ppitch x N doubles, node-major, ppitch = vsom_bmd_pitch(rows of the slice); cum: vsom_bmd_chunks(N) x ppitch (written
-// only with draws); u_dev, norm_dev, draw_dev: one entry per slice row, draw_dev null = no draws.
+// only with draws); u_dev, norm_dev, draw_dev: one entry per slice row, draw_dev null = no draws.  vp: the slice's packed
+// validity rows (row s - s0 at vp + (s - s0) * xpitch; one: the row every sample shares), null = every column counts.
 size_t vsom_bmd_pitch(size_t rows);
 size_t vsom_bmd_chunks(size_t N);
 int vsom_bmd_enqueue(vsom_ctx *c, u64 min_hits, size_t s0, size_t s1, double *P, size_t ppitch, double *cum,
-                     const double *u_dev, double *norm_dev, u64 *draw_dev);
+                     const double *u_dev, double *norm_dev, u64 *draw_dev, const unsigned char *vp = nullptr, bool one = false);
 // ndraws draws from the distribution of slice row `row` after a vsom_bmd_enqueue WITH draws: draw_dev[i] from u_dev[i]
 int vsom_bmd_enqueue_draws(vsom_ctx *c, const double *P, size_t ppitch, size_t row, const double *cum, const double *norm_dev,
                            const double *u_dev, size_t ndraws, u64 *draw_dev);
+// K draws from the distribution of each of the slice's `rows` rows after a vsom_bmd_enqueue WITH draws: draw_dev[r * K + k]
+// from u_dev[r * K + k]
+int vsom_bmd_enqueue_row_draws(vsom_ctx *c, const double *P, size_t ppitch, size_t rows, size_t K, const double *cum,
+                               const double *norm_dev, const double *u_dev, u64 *draw_dev);
+// The validity scratch of one slice of a masked distribution, added to a layout (valid_host null: nothing, on = false), and
+// slice [s0, s1) of a call over rows from r0: its validity bytes up and packed (a column mask once, with the first slice).
+struct VsomBmdMask {
+    bool on, one;
+    vsom_layout::piece<unsigned char> raw, packed;
+};
+VsomBmdMask vsom_bmd_mask_add(const vsom_ctx *c, vsom_layout &lay, const uint8_t *valid_host, bool one, size_t slice);
+int vsom_bmd_mask_slice_enqueue(vsom_ctx *c, const vsom_layout &lay, const VsomBmdMask &m, size_t r0, size_t s0, size_t s1,
+                                const uint8_t *valid_host);
 // vsom_generate.hip: draws + decode of chunk rows [r0,r1) (arguments checked by vsom_generate_batch), the decode alone for
 // given units (arguments checked by vsom_decode_nodes); both synchronise
 int launch_generate(vsom_ctx *c, u64 min_hits, int rule, size_t r0, size_t r1, const double *u_host, const double *l_host,
                     const vsom_generate_out *out);
 int launch_decode_nodes(vsom_ctx *c, const uint64_t *nodes_host, size_t count, const double *l_host, double *record_out);
+// K draws per row from the row's masked distribution + decode with the observed columns kept (arguments checked by
+// vsom_generate_masked_batch); synchronises
+int launch_generate_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask, size_t K,
+                           int keep_observed, const double *u_host, const double *l_host, const vsom_generate_out *out);
 // vsom_topk.hip: the k best matching units of chunk rows [r0,r1) (arguments checked by vsom_bmu_topk_batch); synchronises
 int launch_topk(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out, float *dist_out);
 // vsom_similarity.hip: search + scoring of chunk rows [r0,r1) (arguments checked by vsom_similarity_batch); synchronises

@@ -22,4 +22,5 @@ $CXX $FLAGS "$here/tests/host_accum_test.cpp" -o "$here/host_accum_test" -L"$her
 $CXX $FLAGS "$here/tests/host_accum_masked_test.cpp" -o "$here/host_accum_masked_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_online_masked_test.cpp" -o "$here/host_online_masked_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_masked_score_test.cpp" -o "$here/host_masked_score_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
+$CXX $FLAGS "$here/tests/host_bmd_masked_test.cpp" -o "$here/host_bmd_masked_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 echo "built $here/libsom_hip.so and host_api_test"

@@ -582,6 +582,20 @@ public:
     };
     GeneratedRows generateRows(const DataSet &data, size_t minBmuHits, const std::vector<double> &u,
                                const std::vector<double> &l, bool perRow = true) const;
+    // [MI355X build] extensions: findRestrictedBmd / drawModelVectors / generateRows for records with missing fields (one
+    // vsom_bmd_masked_batch / vsom_generate_masked_batch call, include/vsom_hip.h): the distribution over the units is taken
+    // over the VALID columns only -- `valid` for the one vector (any non-zero entry is valid), the data set's validity flags
+    // for its rows -- so a missing field no longer counts as a measured zero.  generateRowsMasked draws `draws` units per row
+    // with the uniforms u[r * draws + k] and samples a record around each, l being rows x draws x sample length; with
+    // keepObserved a valid column of the record is the row's own value: sampled (multiple) imputation next to impute.  unit
+    // is rows x draws, record rows x draws x columns; a draw without mass has unit UINT64_MAX and a record of NaN.
+    // Standard / Median on the device only; no state is downloaded.
+    std::vector<double> findRestrictedBmdMasked(const Eigen::VectorXf &v, const Eigen::VectorXf &valid,
+                                                size_t minBmuHits = 0) const;
+    std::vector<uint64_t> drawModelVectorsMasked(const DataSet *data, size_t minBmuHits, const std::vector<double> &u,
+                                                 std::vector<double> *norm = nullptr) const;
+    GeneratedRows generateRowsMasked(const DataSet &data, size_t minBmuHits, const std::vector<double> &u,
+                                     const std::vector<double> &l, size_t draws = 1, bool keepObserved = true) const;
     // [MI355X build] extension: the same sampling around given units (one vsom_decode_nodes call): units.size() x columns
     std::vector<double> decodeUnits(const std::vector<uint64_t> &units, const std::vector<double> &l) const;
     // the finish of measureSimilarity from such a report: the row the reference reports (Som.cpp:684-690: one running

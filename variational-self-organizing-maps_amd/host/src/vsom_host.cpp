@@ -2119,6 +2119,73 @@ Som::GeneratedRows Som::generateRows(const DataSet &data, size_t minBmuHits, con
     return r;
 }
 
+// the vector staged as a chunk of one row, one vsom_bmd_masked_batch call with its validity as the column mask
+std::vector<double> Som::findRestrictedBmdMasked(const Eigen::VectorXf &v, const Eigen::VectorXf &valid, size_t minBmuHits) const
+{
+    requireDevicePath("findRestrictedBmdMasked");
+    if ((size_t)v.size() != inLen || (size_t)valid.size() != inLen)
+        throw std::invalid_argument("findRestrictedBmdMasked: sample or validity length does not match the map");
+    std::vector<uint8_t> vb(inLen);
+    for (size_t d = 0; d < inLen; ++d)
+        vb[d] = valid[(Eigen::Index)d] != 0.f;
+    std::vector<double> prob(width * height, 0.0);
+    joinGroup();
+    check(vsom_upload_chunk(ctx, v.data(), 1), "vsom_upload_chunk");
+    check(vsom_bmd_masked_batch(ctx, minBmuHits, 0, 1, vb.data(), 1, nullptr, nullptr, nullptr, prob.data()),
+          "vsom_bmd_masked_batch");
+    return prob;
+}
+
+// upload, one vsom_bmd_masked_batch call with the data set's validity flags
+std::vector<uint64_t> Som::drawModelVectorsMasked(const DataSet *data, size_t minBmuHits, const std::vector<double> &u,
+                                                  std::vector<double> *norm) const
+{
+    requireDevicePath("drawModelVectorsMasked");
+    const size_t n = data->size();
+    if (u.size() != n)
+        throw std::invalid_argument("drawModelVectorsMasked: one uniform per row");
+    std::vector<uint64_t> drawn(n);
+    if (norm)
+        norm->assign(n, 0.0);
+    if (n == 0)
+        return drawn;
+    const std::vector<uint8_t> valid = validity_bytes(*data, inLen);
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data->contiguous(), n), "vsom_upload_chunk");
+    check(vsom_bmd_masked_batch(ctx, minBmuHits, 0, n, valid.data(), 0, u.data(), drawn.data(), norm ? norm->data() : nullptr,
+                                nullptr),
+          "vsom_bmd_masked_batch");
+    return drawn;
+}
+
+// upload, one vsom_generate_masked_batch call with the data set's validity flags
+Som::GeneratedRows Som::generateRowsMasked(const DataSet &data, size_t minBmuHits, const std::vector<double> &u,
+                                           const std::vector<double> &l, size_t draws, bool keepObserved) const
+{
+    requireDevicePath("generateRowsMasked");
+    if (draws == 0 || draws > 65535)
+        throw std::invalid_argument("generateRowsMasked: draws must be in [1, 65535]");
+    GeneratedRows r;
+    r.columns = inLen;
+    const size_t n = data.size();
+    if (u.size() != n * draws)
+        throw std::invalid_argument("generateRowsMasked: `draws` uniforms per row");
+    if (l.size() != n * draws * r.columns)
+        throw std::invalid_argument("generateRowsMasked: l must hold rows x draws x sample length values");
+    r.unit.assign(n * draws, 0);
+    r.record.assign(n * draws * r.columns, 0.0);
+    if (n == 0)
+        return r;
+    const std::vector<uint8_t> valid = validity_bytes(data, inLen);
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data.contiguous(), n), "vsom_upload_chunk");
+    vsom_generate_out out = {r.unit.data(), r.record.data()};
+    check(vsom_generate_masked_batch(ctx, minBmuHits, 0, n, valid.data(), 0, (uint32_t)draws, keepObserved ? 1 : 0, u.data(),
+                                     l.data(), &out),
+          "vsom_generate_masked_batch");
+    return r;
+}
+
 std::vector<double> Som::decodeUnits(const std::vector<uint64_t> &units, const std::vector<double> &l) const
 {
     requireDevicePath("decodeUnits");

@@ -524,6 +524,47 @@ class Som:
         evaluateRowsMasked)."""
         return self.evaluateRowsMasked(data, binary, continuous, minBmuHits)["error"]
 
+    # ---- the distribution over the units and sampled records, over the valid columns only (extensions) ----
+    def findRestrictedBmdMasked(self, v, valid, minBmuHits=0):
+        """extension: findRestrictedBmd over the valid columns of v only (capi.Context.restricted_bmd_masked): float64[N];
+        valid: J entries, nonzero = valid"""
+        self._stage_one(v)
+        return self.ctx.restricted_bmd_masked(np.asarray(valid).reshape(-1), minBmuHits, 0, 1, probs=True)["prob"][0]
+
+    def drawModelVectorsMasked(self, data, minBmuHits, u):
+        """extension: drawModelVectors for records with missing fields: one node per loaded row of `data`, drawn with the
+        uniform u[r] from the row's restricted distribution over its valid columns (validity as in findBmuMasked)"""
+        X = self._rows(data)
+        self.ctx.upload_chunk(X)
+        if X.shape[0] == 0:
+            return np.zeros(0, np.uint64)
+        return self.ctx.restricted_bmd_masked(self._validity(data), minBmuHits, u=u)["draw"]
+
+    def generateRowsMasked(self, data, minBmuHits, u, l, draws=1, keepObserved=True):
+        """extension: sampled imputation with the caller's random numbers (capi.Context.generate_masked): for every loaded
+        row of `data`, `draws` units drawn with the uniforms u[r, k] from the row's restricted distribution over its valid
+        columns, and around each a record that keeps the row's valid columns (keepObserved) and samples the others as
+        generateRows does, l: float64[rows, draws, J].  {"unit": uint64[rows, draws], "record": float64[rows, draws, J]};
+        a draw without mass has the unit capi.NO_UNIT and a record of NaN.  Validity as in findBmuMasked."""
+        X = self._rows(data)
+        self.ctx.upload_chunk(X)
+        if X.shape[0] == 0:
+            return {"unit": np.zeros((0, int(draws)), np.uint64),
+                    "record": np.zeros((0, int(draws), self.ctx.in_len), np.float64)}
+        return self.ctx.generate_masked(self._validity(data), minBmuHits, u, l, draws=draws, keep_observed=keepObserved)
+
+    def imputeSampled(self, data, minBmuHits=0, draws=1, seed=None):
+        """extension: multiple imputation next to impute: float64[rows, draws, J], `draws` completions of every loaded row
+        of `data` -- its valid columns as they are, the others sampled around units drawn from the row's distribution over
+        the valid ones (generateRowsMasked).  The uniforms and L = integers(1, 1000) / 1000 (never 0 or 1: no +-inf) come
+        from numpy.random.default_rng(seed)."""
+        X = self._rows(data)
+        n, K, J = X.shape[0], int(draws), self.ctx.in_len
+        rng = np.random.default_rng(seed)
+        u = rng.random((n, K))
+        l = rng.integers(1, 1000, (n, K, J)).astype(np.float64) / 1000.0
+        return self.generateRowsMasked(data, minBmuHits, u, l, draws=K, keepObserved=True)["record"]
+
     def classify(self, data, label_columns, minBmuHits=0):
         """extension: a trained map with label columns used as a classifier.  Every loaded row of `data` is matched on the
         columns outside `label_columns` (a column mask; what the rows hold in the label columns is ignored), and its
