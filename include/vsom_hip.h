@@ -143,7 +143,8 @@ void vsom_destroy(vsom_ctx *ctx);
  *                                 const float *value_weight, uint32_t J, uint32_t D);     element r < R of Comparer
  *   __device__ float vsom_step(uint32_t d, const float *x, const float *model, const float *value_weight,
  *                              uint32_t J, uint32_t D);                                   element d < D of Stepper
- * x has J values, model and dispersion D, value_weight J (all 1: device samples are fully valid, weight 1).  The source
+ * x has J values, model and dispersion D, value_weight J: what Som.cpp builds at that call from the chunk's validity
+ * (0.0f / 1.0f) and the column weights, see "value_weight" below; all 1 while neither has been set.  The source
  * is compiled with hipRTC for gfx950 (-O3 -ffp-contract=off -fhip-fp32-correctly-rounded-divide-sqrt) together with
  * generic search / batch / online kernels that evaluate the hooks exactly where Som.cpp calls Comparer / Stepper, with
  * the fp32 operation order of the host path for custom hooks (host/src/vsom_custom.cpp): a device hook that computes
@@ -155,7 +156,8 @@ void vsom_destroy(vsom_ctx *ctx);
  * vsom_set_last_bmu, vsom_get_sqres, vsom_bmu_batch, vsom_bmu_local_batch, vsom_find_bmu, vsom_find_local_bmu,
  * vsom_dist_single, vsom_distances, vsom_batch_epoch(_async), vsom_get_mse, vsom_train_single,
  * vsom_train_online_chunk(_acc, _fetch), vsom_residual_len (= R), vsom_prefetch_chunk / vsom_prefetch_wait /
- * vsom_commit_chunk (the prefetch takes a host copy of the rows; the commit uploads it) and the plumbing (stream,
+ * vsom_commit_chunk (the prefetch takes a host copy of the rows; the commit uploads it), vsom_set_column_weights,
+ * vsom_set_chunk_validity and the four _valid calls (below) and the plumbing (stream,
  * depth, nodes, pointers, timing).  Everything else -- device-resident chunks, the split batch phases, restricted and raw
  * distances, compaction, dedupe, shortlist statistics, non-strict update modes -- returns VSOM_ERR_INVALID and leaves
  * the context usable.  Custom contexts cannot join a group.  vsom_custom_compile_check compiles a hook source the
@@ -164,6 +166,45 @@ void vsom_destroy(vsom_ctx *ctx);
 int vsom_create_custom(vsom_ctx **out, int device, uint32_t width, uint32_t height, uint32_t in_len,
                        uint32_t depth, uint32_t residual_len, const char *hook_source);
 int vsom_custom_compile_check(const char *hook_source, uint32_t depth, uint32_t residual_len);
+/* ---- value_weight: missing fields and column weights of a custom context -------------------------------------------------
+ * The reference lets missing fields and column weights matter through the valueWeight argument of Comparer / Stepper
+ * alone (the built-in transformations drop it, Transformation.cpp:7-12,45-50), and Som builds it from the data set at
+ * every call.  A custom context does the same from two settings, with valid as 0.0f / 1.0f and vw = valid * weights,
+ * one fp32 product per element:
+ *   vsom_bmu_batch, vsom_bmu_local_batch, vsom_distances    search / distance of a row with the row's vw   Som.cpp:134
+ *   vsom_batch_epoch(_async)                                search with vw; the residual against SMap[bmu] and the
+ *                                                           phase-2 Stepper with valid alone    :774,:780,:797,:803,:861,:867
+ *   vsom_train_online_chunk(_acc, _fetch)                   row s: search, window Steppers, residual and BMU distance, all
+ *                                                           with the vw of row s                              :891,:905-946
+ *   the four _valid calls                                   one vw from valid_host (NULL = all valid) and the column
+ *                                                           weights, where trainSingle / findBmu / findLocalBmu /
+ *                                                           euclidianWeightedDist use totalWeight             :889-946
+ * vsom_find_bmu, vsom_find_local_bmu, vsom_dist_single and vsom_train_single on a custom context keep an all-valid
+ * vector and still apply the column weights, as findBmu(v) with a default `valid` would.
+ * vsom_set_column_weights: the weights belong to the context, as getWeights() belongs to the loader, and hold until set
+ * again (NULL = all 1).  Values pass through as given: a zero, a negative value or a NaN is the caller's business.
+ * vsom_set_chunk_validity: the validity belongs to the loaded chunk -- one_mask == 0: B x J bytes row-major, != 0: J bytes
+ * for every row; non-zero = valid; NULL = all valid.  Every call that makes a new chunk current (vsom_upload_chunk(_async),
+ * vsom_commit_chunk, vsom_ensemble_upload_chunks for a custom member) resets it to all valid; it survives everything
+ * else (epochs, vsom_set_last_bmu, vsom_set_state).  Both setters expand their input once, on the context's stream, into
+ * the fp32 arrays the kernels read ([B][J] for a per-row mask, else [J]) and return when the caller's memory has been
+ * read.  While neither is set every launch is the one of a context that never called them: same kernels, grid and bits.
+ * Refused (VSOM_ERR_INVALID, nothing enqueued, the context stays usable): a null context; a built-in context for any
+ * of the six (its hooks ignore valueWeight: use the masked calls, vsom_bmu_masked_batch, vsom_batch_epoch_masked,
+ * vsom_train_online_chunk_masked ...); vsom_set_chunk_validity with no chunk loaded.  (It also checks for a chunk staged
+ * ahead over the current rows, as the masked calls do; a custom context never stages ahead today -- its prefetch keeps
+ * a host copy until the commit -- so that refusal cannot occur yet.)
+ * Out of scope: validity for the consumers that refuse custom contexts (restricted, top-k, BMD, similarity, evaluate,
+ * generate, U-matrix), groups, checkpoints of custom maps. */
+int vsom_set_column_weights(vsom_ctx *ctx, const float *weights_host /*[J]; NULL = all 1*/);
+int vsom_set_chunk_validity(vsom_ctx *ctx, const uint8_t *valid_host, int one_mask);
+int vsom_find_bmu_valid(vsom_ctx *ctx, const float *v_host, const uint8_t *valid_host /*[J]*/, uint64_t *bmu_out,
+                        float *dist_out);
+int vsom_find_local_bmu_valid(vsom_ctx *ctx, const float *v_host, const uint8_t *valid_host, uint64_t last_bmu,
+                              uint64_t *bmu_out, float *dist_out);
+int vsom_dist_single_valid(vsom_ctx *ctx, const float *v_host, const uint8_t *valid_host, uint64_t node, float *dist_out);
+int vsom_train_single_valid(vsom_ctx *ctx, const float *v_host, const uint8_t *valid_host, double eta, double sigma,
+                            uint64_t *last_bmu, int decay_fn, float *residual_out, float *dist_out, uint64_t *bmu_out);
 /* adopt an external hipStream_t (NULL = back to the context's own stream) */
 int vsom_set_stream(vsom_ctx *ctx, void *hip_stream);
 int vsom_synchronize(vsom_ctx *ctx);

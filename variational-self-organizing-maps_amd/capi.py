@@ -58,6 +58,8 @@ SYMBOLS = [
     "vsom_batch_accum_chunk_masked", "vsom_train_online_chunk_masked",
     "vsom_similarity_masked_batch", "vsom_evaluate_masked_batch",
     "vsom_bmd_masked_batch", "vsom_generate_masked_batch",
+    "vsom_set_column_weights", "vsom_set_chunk_validity", "vsom_find_bmu_valid", "vsom_find_local_bmu_valid",
+    "vsom_dist_single_valid", "vsom_train_single_valid",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -298,6 +300,14 @@ def lib():
                                             dp, dp]
         L.vsom_generate_masked_batch.argtypes = [vp, C.c_uint64, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8), C.c_int,
                                                  C.c_uint32, C.c_int, dp, dp, C.POINTER(GenerateOut)]
+    if hasattr(L, "vsom_set_chunk_validity"):           # (VSOM_LIB may name an older build: tools/custom_validity_bench.py --lib)
+        u8p = C.POINTER(C.c_uint8)
+        L.vsom_set_column_weights.argtypes = [vp, fp]
+        L.vsom_set_chunk_validity.argtypes = [vp, u8p, C.c_int]
+        L.vsom_find_bmu_valid.argtypes = [vp, fp, u8p, u64p, fp]
+        L.vsom_find_local_bmu_valid.argtypes = [vp, fp, u8p, C.c_uint64, u64p, fp]
+        L.vsom_dist_single_valid.argtypes = [vp, fp, u8p, C.c_uint64, fp]
+        L.vsom_train_single_valid.argtypes = [vp, fp, u8p, C.c_double, C.c_double, u64p, C.c_int, fp, fp, u64p]
     _lib = L
     return L
 
@@ -519,20 +529,55 @@ class Context:
         check(lib().vsom_bmu_batch(self._h, _u(idx), _f(dist)))
         return idx, dist
 
-    def dist_single(self, v, node):
-        """Som::euclidianWeightedDist(node, v) of one host vector (does not disturb the staged chunk)."""
+    def set_column_weights(self, w):
+        """custom contexts: the column weights of the hooks' value_weight (None = all 1); they hold until set again"""
+        if w is not None:
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.shape != (self.in_len,):
+                raise ValueError(f"weights have shape {w.shape}, not ({self.in_len},)")
+        check(lib().vsom_set_column_weights(self._h, _f(w)))
+
+    def set_chunk_validity(self, valid, one_mask=False):
+        """custom contexts: the loaded chunk's validity for the hooks' value_weight -- B x J (nonzero = valid), or J values
+        for every row with one_mask; None = all valid.  The next chunk resets it."""
+        if valid is None:
+            check(lib().vsom_set_chunk_validity(self._h, None, 0))
+            return
+        vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        want = (self.in_len,) if one_mask else (self.chunk_size, self.in_len)
+        if vb.shape != want:
+            raise ValueError(f"valid has shape {vb.shape}, not {want}")
+        check(lib().vsom_set_chunk_validity(self._h, vb.ctypes.data_as(C.POINTER(C.c_uint8)), 1 if one_mask else 0))
+
+    def _vector_valid(self, valid):
+        vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        if vb.shape != (self.in_len,):
+            raise ValueError(f"valid has shape {vb.shape}, not ({self.in_len},)")
+        return vb, vb.ctypes.data_as(C.POINTER(C.c_uint8))
+
+    def dist_single(self, v, node, valid=None):
+        """Som::euclidianWeightedDist(node, v) of one host vector (does not disturb the staged chunk); valid= (custom
+        contexts): the vector's validity for the hooks' value_weight."""
         v = np.ascontiguousarray(v, dtype=np.float32)
         assert v.shape == (self.in_len,)
         d = C.c_float()
-        check(lib().vsom_dist_single(self._h, _f(v), int(node), C.byref(d)))
+        if valid is not None:
+            vb, vp = self._vector_valid(valid)
+            check(lib().vsom_dist_single_valid(self._h, _f(v), vp, int(node), C.byref(d)))
+        else:
+            check(lib().vsom_dist_single(self._h, _f(v), int(node), C.byref(d)))
         return np.float32(d.value)
 
-    def find_local_bmu(self, v, last_bmu):
-        """Som::findLocalBmu of one host vector from `last_bmu`: (index, distance)."""
+    def find_local_bmu(self, v, last_bmu, valid=None):
+        """Som::findLocalBmu of one host vector from `last_bmu`: (index, distance); valid= as in dist_single."""
         v = np.ascontiguousarray(v, dtype=np.float32)
         assert v.shape == (self.in_len,)
         idx, d = C.c_uint64(), C.c_float()
-        check(lib().vsom_find_local_bmu(self._h, _f(v), int(last_bmu), C.byref(idx), C.byref(d)))
+        if valid is not None:
+            vb, vp = self._vector_valid(valid)
+            check(lib().vsom_find_local_bmu_valid(self._h, _f(v), vp, int(last_bmu), C.byref(idx), C.byref(d)))
+        else:
+            check(lib().vsom_find_local_bmu(self._h, _f(v), int(last_bmu), C.byref(idx), C.byref(d)))
         return int(idx.value), np.float32(d.value)
 
     def find_restricted_bmu(self, v, min_hits):
@@ -551,12 +596,16 @@ class Context:
         check(lib().vsom_distances_single(self._h, _f(v), _f(out)))
         return out
 
-    def find_bmu(self, v):
-        """Som::findBmu of one host vector (does not disturb the staged chunk)."""
+    def find_bmu(self, v, valid=None):
+        """Som::findBmu of one host vector (does not disturb the staged chunk); valid= as in dist_single."""
         v = np.ascontiguousarray(v, dtype=np.float32)
         assert v.size == self.in_len
         idx, dist = C.c_uint64(), C.c_float()
-        check(lib().vsom_find_bmu(self._h, _f(v), C.byref(idx), C.byref(dist)))
+        if valid is not None:
+            vb, vp = self._vector_valid(valid)
+            check(lib().vsom_find_bmu_valid(self._h, _f(v), vp, C.byref(idx), C.byref(dist)))
+        else:
+            check(lib().vsom_find_bmu(self._h, _f(v), C.byref(idx), C.byref(dist)))
         return int(idx.value), np.float32(dist.value)
 
     def bmu_local_batch(self):
@@ -1036,13 +1085,19 @@ class Context:
         return np.float32(mse.value)
 
     # ---- online --------------------------------------------------------
-    def train_single(self, v, eta, sigma, last_bmu, decay_fn):
+    def train_single(self, v, eta, sigma, last_bmu, decay_fn, valid=None):
+        """Som::trainSingle of one host vector; valid= (custom contexts): the vector's validity for the hooks' value_weight"""
         v = np.ascontiguousarray(v, dtype=np.float32)
         assert v.size == self.in_len
         res = np.empty(self.residual_len, np.float32)
         lb, bmu, dist = C.c_uint64(int(last_bmu)), C.c_uint64(), C.c_float()
-        check(lib().vsom_train_single(self._h, _f(v), float(eta), float(sigma), C.byref(lb),
-                                      int(decay_fn), _f(res), C.byref(dist), C.byref(bmu)))
+        if valid is not None:
+            vb, vp = self._vector_valid(valid)
+            check(lib().vsom_train_single_valid(self._h, _f(v), vp, float(eta), float(sigma), C.byref(lb),
+                                                int(decay_fn), _f(res), C.byref(dist), C.byref(bmu)))
+        else:
+            check(lib().vsom_train_single(self._h, _f(v), float(eta), float(sigma), C.byref(lb),
+                                          int(decay_fn), _f(res), C.byref(dist), C.byref(bmu)))
         return int(bmu.value), res, np.float32(dist.value), int(lb.value)
 
     def train_online_chunk(self, eta, sigma, decay_fn, first_chunk=True):

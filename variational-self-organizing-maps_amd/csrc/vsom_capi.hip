@@ -573,6 +573,22 @@ static int upload_chunk_impl(vsom_ctx *c, const float *x_host, size_t B, bool wa
 
 int vsom_upload_chunk(vsom_ctx *c, const float *x_host, size_t B) { return upload_chunk_impl(c, x_host, B, true); }
 
+// the hooks' value_weight on a custom context: the loader's column weights (they belong to the context) and the loaded
+// chunk's validity (it belongs to the chunk: every call that makes a new chunk current resets it)
+int vsom_set_column_weights(vsom_ctx *c, const float *weights_host)
+{
+    VSOM_CUSTOM_ONLY(c, "vsom_set_column_weights");
+    CHECK_CTX_KEEP(c);
+    return vsom_custom_set_weights(c, weights_host);
+}
+
+int vsom_set_chunk_validity(vsom_ctx *c, const uint8_t *valid_host, int one_mask)
+{
+    VSOM_CUSTOM_ONLY(c, "vsom_set_chunk_validity");
+    CHECK_CTX_KEEP(c);
+    return vsom_custom_set_validity(c, valid_host, one_mask);
+}
+
 // copy and staging enqueued on the context's stream, no wait: x_host (pinned: vsom_host_alloc) stays the caller's to keep
 // unchanged until a call that synchronises the context has returned
 int vsom_upload_chunk_async(vsom_ctx *c, const float *x_host, size_t B) { return upload_chunk_impl(c, x_host, B, false); }

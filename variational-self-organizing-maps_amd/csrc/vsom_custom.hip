@@ -78,10 +78,18 @@ int check_shape(uint32_t depth, uint32_t residual_len, const char *hook_source)
 struct vsom_custom_state {
     uint32_t R = 0;
     hipModule_t mod = nullptr;
-    hipFunction_t k_floor = nullptr, k_full = nullptr, k_local = nullptr, k_pair = nullptr, k_resid = nullptr,
-                  k_finish = nullptr, k_phase2 = nullptr, k_onl_update = nullptr, k_onl_post = nullptr;
+    hipFunction_t k_floor = nullptr, k_expand = nullptr, k_full = nullptr, k_local = nullptr, k_pair = nullptr,
+                  k_resid = nullptr, k_finish = nullptr, k_phase2 = nullptr, k_onl_update = nullptr, k_onl_post = nullptr;
     DevBuf<float> sigf;           // [N][D] select(sigma < 1e-5, 1e-5, sigma): the dispersion the distance passes
-    DevBuf<float> ones;           // [J] the value weights (valid * weights: every value of a device sample is valid, weight 1)
+    DevBuf<float> ones;           // [J] the value weights while neither validity nor column weights are set: all 1
+    // value_weight (vsom_set_chunk_validity, vsom_set_column_weights): expanded once per setter call by vc_expand_validity,
+    // read by every launch.  mask: 0 = the chunk is all valid, 1 = one [J] mask for every row, 2 = [B][J].
+    int mask = 0;
+    bool weighted = false;
+    DevBuf<unsigned char> vbytes; // the current chunk's validity bytes as given ([J] or [B][J]; kept for a change of the weights)
+    DevBuf<float> wts;            // [J] the column weights
+    DevBuf<float> cvalid, cvw;    // [J] or [B][J]: valid as 0 / 1, valid * weights
+    DevBuf<unsigned char> vec_bytes; DevBuf<float> vec_valid, vec_vw;   // [J] the same for one host vector (the _valid calls)
     DevBuf<float> vec;            // [J] one host vector (find / dist / train_single)
     DevBuf<float> resid;          // [R] train_single's residual
     DevBuf<u64> slot;             // [2] one BMU index
@@ -92,6 +100,12 @@ struct vsom_custom_state {
 };
 
 namespace {
+
+// the value_weight rows of a launch: row s is p + s * stride (stride 0: one [J] vector for every row)
+struct VwRef {
+    const float *p;
+    u64 stride;
+};
 
 int launch(vsom_ctx *c, hipFunction_t f, unsigned grid, unsigned block, unsigned lds, std::vector<void *> args)
 {
@@ -107,6 +121,63 @@ int refresh_sigf(vsom_ctx *c)
     u64 n = (u64)c->N * c->D;
     const float *sg = c->sigma.p;
     return launch(c, u->k_floor, (unsigned)((n + 255) / 256), 256, 0, {&sg, &u->sigf.p, &n});
+}
+
+// valid .* weights of the chunk rows (Som.cpp:134, :905): `ones` while nothing is set -- the launches of an untouched
+// context -- and the weights themselves while every entry is valid (1.0f * w is w)
+VwRef chunk_vw(const vsom_ctx *c)
+{
+    const vsom_custom_state *u = c->cu;
+    if (!u->mask)
+        return {u->weighted ? u->wts.p : u->ones.p, 0};
+    return {u->cvw.p, u->mask == 2 ? (u64)c->J : 0};
+}
+
+// valid alone (the batch residual and phase 2, Som.cpp:780,:803,:861,:867)
+VwRef chunk_valid(const vsom_ctx *c)
+{
+    const vsom_custom_state *u = c->cu;
+    if (!u->mask)
+        return {u->ones.p, 0};
+    return {u->cvalid.p, u->mask == 2 ? (u64)c->J : 0};
+}
+
+int expand_validity(vsom_ctx *c, const unsigned char *bytes, float *valid, float *vw, u64 rows)
+{
+    vsom_custom_state *u = c->cu;
+    const float *w = u->weighted ? u->wts.p : nullptr;
+    u64 n = rows * c->J;
+    uint32_t J = c->J;
+    return launch(c, u->k_expand, (unsigned)((n + 255) / 256), 256, 0, {&bytes, &w, &valid, &vw, &n, &J});
+}
+
+// cvalid / cvw of the current chunk from vbytes and wts, after either changed (nothing to do while the chunk is all valid).
+// A failed allocation leaves the chunk all valid: the set is absent then.
+int refresh_chunk_vw(vsom_ctx *c)
+{
+    vsom_custom_state *u = c->cu;
+    if (!u->mask)
+        return VSOM_OK;
+    const size_t rows = u->mask == 2 ? c->B : 1, cap = (u->mask == 2 ? c->Bcap : 1) * (size_t)c->J;
+    if (vsom_grow_set(c->stream, VSOM_BUF_SYNC, {vsom_member(u->cvalid, cap), vsom_member(u->cvw, cap)}) != hipSuccess) {
+        (void)hipGetLastError();
+        u->mask = 0;
+        return vsom_fail(VSOM_ERR_NOMEM, "hipMalloc of the chunk's value weights failed");
+    }
+    return expand_validity(c, u->vbytes.p, u->cvalid.p, u->cvw.p, rows);
+}
+
+// the one value_weight vector of a host vector: valid_host (null: all valid) .* the column weights
+int vector_vw(vsom_ctx *c, const uint8_t *valid_host, VwRef *out)
+{
+    vsom_custom_state *u = c->cu;
+    if (!valid_host) {
+        *out = {u->weighted ? u->wts.p : u->ones.p, 0};
+        return VSOM_OK;
+    }
+    VSOM_HIP_CHECK(hipMemcpyAsync(u->vec_bytes.p, valid_host, c->J, hipMemcpyHostToDevice, c->stream));
+    *out = {u->vec_vw.p, 0};
+    return expand_validity(c, u->vec_bytes.p, u->vec_valid.p, u->vec_vw.p, 1);
 }
 
 int ensure_chunk(vsom_ctx *c, size_t B)
@@ -133,21 +204,22 @@ int stage_vec(vsom_ctx *c, const float *v_host)
 }
 
 // full search of `rows` sample rows starting at X
-int search_full(vsom_ctx *c, const float *X, unsigned rows, u64 *bmu, float *dist)
+int search_full(vsom_ctx *c, const float *X, VwRef vw, unsigned rows, u64 *bmu, float *dist)
 {
     vsom_custom_state *u = c->cu;
     u64 xs = c->J;
     uint32_t N = c->N, J = c->J, D = c->D, R = u->R;
-    return launch(c, u->k_full, rows, 256, 0, {&X, &xs, &c->map.p, &u->sigf.p, &u->ones.p, &N, &J, &D, &R, &bmu, &dist});
+    return launch(c, u->k_full, rows, 256, 0,
+                  {&X, &xs, &c->map.p, &u->sigf.p, &vw.p, &vw.stride, &N, &J, &D, &R, &bmu, &dist});
 }
 
-int search_local(vsom_ctx *c, const float *X, uint32_t rows, const u64 *start, u64 *bmu, float *dist)
+int search_local(vsom_ctx *c, const float *X, VwRef vw, uint32_t rows, const u64 *start, u64 *bmu, float *dist)
 {
     vsom_custom_state *u = c->cu;
     u64 xs = c->J;
     uint32_t W = c->W, H = c->H, J = c->J, D = c->D, R = u->R;
     return launch(c, u->k_local, (rows + 63) / 64, 64, 0,
-                  {&X, &xs, &c->map.p, &u->sigf.p, &u->ones.p, &W, &H, &J, &D, &R, &start, &bmu, &dist, &rows});
+                  {&X, &xs, &c->map.p, &u->sigf.p, &vw.p, &vw.stride, &W, &H, &J, &D, &R, &start, &bmu, &dist, &rows});
 }
 
 int ensure_lutd(vsom_ctx *c, double sigma)
@@ -166,12 +238,13 @@ int ensure_lutd(vsom_ctx *c, double sigma)
 }
 
 // one trainSingle step of the sample at device address x (hostTrainSingle): search, window update, residual / distance;
-// bmu is the sample's lastBMU slot (in / out)
-int online_step(vsom_ctx *c, const float *x, double eta, double sigma, int decay_fn, u64 *bmu, float *resid, float *dist,
-                u64 *hits, float *mse, uint32_t B)
+// bmu is the sample's lastBMU slot (in / out); every hook call takes row `row` of vw (Som.cpp:891,:905-946)
+int online_step(vsom_ctx *c, const float *x, VwRef vw, u64 row, double eta, double sigma, int decay_fn, u64 *bmu, float *resid,
+                float *dist, u64 *hits, float *mse, uint32_t B)
 {
     vsom_custom_state *u = c->cu;
-    int rc = sigma > 1.0 ? search_full(c, x, 1, bmu, u->fout.p) : search_local(c, x, 1, bmu, bmu, u->fout.p);
+    const VwRef mine{vw.p + row * vw.stride, 0};
+    int rc = sigma > 1.0 ? search_full(c, x, mine, 1, bmu, u->fout.p) : search_local(c, x, mine, 1, bmu, bmu, u->fout.p);
     if (rc)
         return rc;
     // a box of nx x ny workgroups covers the window: x1 - x0 <= floor(5 sigma) + 1
@@ -179,11 +252,12 @@ int online_step(vsom_ctx *c, const float *x, double eta, double sigma, int decay
     uint32_t nx = ext >= c->W ? c->W : (uint32_t)ext, ny = ext >= c->H ? c->H : (uint32_t)ext;
     uint32_t W = c->W, H = c->H, J = c->J, D = c->D, R = u->R;
     if ((rc = launch(c, u->k_onl_update, nx * ny, 256, 2 * D * 4,
-                     {&x, &c->map.p, &c->S.p, &c->sigma.p, &u->sigf.p, &c->weight.p, &bmu, &u->lutd.p, &W, &H, &u->ones.p, &J, &D,
-                      &eta, &sigma, &decay_fn, &nx})))
+                     {&x, &c->map.p, &c->S.p, &c->sigma.p, &u->sigf.p, &c->weight.p, &bmu, &u->lutd.p, &W, &H, &vw.p, &vw.stride,
+                      &row, &J, &D, &eta, &sigma, &decay_fn, &nx})))
         return rc;
     return launch(c, u->k_onl_post, 1, 64, 0,
-                  {&x, &c->map.p, &c->sigma.p, &u->sigf.p, &u->ones.p, &J, &D, &R, &bmu, &resid, &dist, &hits, &mse, &B});
+                  {&x, &c->map.p, &c->sigma.p, &u->sigf.p, &vw.p, &vw.stride, &row, &J, &D, &R, &bmu, &resid, &dist, &hits, &mse,
+                   &B});
 }
 
 void free_custom(vsom_custom_state *u)
@@ -207,6 +281,13 @@ uint32_t vsom_custom_residual_len(const vsom_ctx *c) { return c->cu->R; }
 int vsom_custom_refuse(const char *what)
 {
     return vsom_fail(VSOM_ERR_INVALID, std::string(what) + " is not available on a custom-transformation context");
+}
+
+int vsom_custom_only(const char *what)
+{
+    return vsom_fail(VSOM_ERR_INVALID, std::string(what) + " needs a custom-transformation context: the built-in Comparer / "
+                                       "Stepper ignore valueWeight; for missing values on a built-in context use the masked "
+                                       "calls (vsom_bmu_masked_batch, vsom_batch_epoch_masked, vsom_train_online_chunk_masked)");
 }
 
 int vsom_custom_after_set_state(vsom_ctx *c)
@@ -234,8 +315,43 @@ int vsom_custom_upload(vsom_ctx *c, const float *x_host, size_t B, bool wait)
     }
     c->B = B;
     c->chunk_loaded = true;
+    c->cu->mask = 0;                // a new chunk is all valid; the column weights stay
     if (wait)
         VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
+    return VSOM_OK;
+}
+
+// Som.cpp's valueWeight on the device: the column weights of the context (DataSet::getWeights) ...
+int vsom_custom_set_weights(vsom_ctx *c, const float *weights_host)
+{
+    vsom_custom_state *u = c->cu;
+    u->weighted = weights_host != nullptr;
+    if (weights_host)
+        VSOM_HIP_CHECK(hipMemcpyAsync(u->wts.p, weights_host, (size_t)c->J * 4, hipMemcpyHostToDevice, c->stream));
+    if (int rc = refresh_chunk_vw(c))
+        return rc;
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));    // weights_host is the caller's again
+    return VSOM_OK;
+}
+
+// ... and the validity of the loaded chunk (DataSet::getValidity); the bytes go up from the caller's memory as they are
+int vsom_custom_set_validity(vsom_ctx *c, const uint8_t *valid_host, int one_mask)
+{
+    vsom_custom_state *u = c->cu;
+    if (!c->chunk_loaded)
+        return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
+    CHECK_ROWS(c);
+    const size_t n = (one_mask ? 1 : c->B) * (size_t)c->J;
+    const int mask = !valid_host || n == 0 ? 0 : one_mask ? 1 : 2;
+    if (mask) {
+        u->mask = 0;                // (until the bytes are up: a failure below leaves the chunk all valid)
+        VSOM_ALLOC_CHECK(vsom_grow(u->vbytes, (one_mask ? 1 : c->Bcap) * (size_t)c->J, c->stream, VSOM_BUF_SYNC));
+        VSOM_HIP_CHECK(hipMemcpyAsync(u->vbytes.p, valid_host, n, hipMemcpyHostToDevice, c->stream));
+    }
+    u->mask = mask;
+    if (int rc = refresh_chunk_vw(c))
+        return rc;
+    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));    // valid_host is the caller's again
     return VSOM_OK;
 }
 
@@ -272,24 +388,28 @@ static int copy_results(vsom_ctx *c, uint64_t *idx, float *dist)
 
 int vsom_custom_bmu_batch(vsom_ctx *c, int local, uint64_t *idx_out_host, float *dist_out_host)
 {
-    int rc = local ? search_local(c, c->Xs.p, (uint32_t)c->B, c->lastbmu.p, c->lastbmu.p, c->sqres.p)
-                   : search_full(c, c->Xs.p, (unsigned)c->B, c->lastbmu.p, c->sqres.p);
+    const VwRef vw = chunk_vw(c);
+    int rc = local ? search_local(c, c->Xs.p, vw, (uint32_t)c->B, c->lastbmu.p, c->lastbmu.p, c->sqres.p)
+                   : search_full(c, c->Xs.p, vw, (unsigned)c->B, c->lastbmu.p, c->sqres.p);
     if (rc)
         return rc;
     return copy_results(c, idx_out_host, dist_out_host);
 }
 
-int vsom_custom_find(vsom_ctx *c, const float *v_host, int local, uint64_t start, uint64_t *bmu_out, float *dist_out)
+int vsom_custom_find(vsom_ctx *c, const float *v_host, const uint8_t *valid_host, int local, uint64_t start, uint64_t *bmu_out,
+                     float *dist_out)
 {
     vsom_custom_state *u = c->cu;
     if (local && start >= c->N)
         return vsom_fail(VSOM_ERR_INVALID, "lastBMU out of range");
+    VwRef vw;
     int rc = stage_vec(c, v_host);
-    if (rc)
+    if (rc || (rc = vector_vw(c, valid_host, &vw)))
         return rc;
     u64 s = start;
     VSOM_HIP_CHECK(hipMemcpyAsync(u->slot.p, &s, 8, hipMemcpyHostToDevice, c->stream));
-    rc = local ? search_local(c, u->vec.p, 1, u->slot.p, u->slot.p, u->fout.p) : search_full(c, u->vec.p, 1, u->slot.p, u->fout.p);
+    rc = local ? search_local(c, u->vec.p, vw, 1, u->slot.p, u->slot.p, u->fout.p)
+               : search_full(c, u->vec.p, vw, 1, u->slot.p, u->fout.p);
     if (rc)
         return rc;
     float d = 0.f;
@@ -303,7 +423,7 @@ int vsom_custom_find(vsom_ctx *c, const float *v_host, int local, uint64_t start
     return VSOM_OK;
 }
 
-static int pair_dist(vsom_ctx *c, const float *X, const uint64_t *nodes_host, const uint64_t *rows_host, size_t count,
+static int pair_dist(vsom_ctx *c, const float *X, VwRef vw, const uint64_t *nodes_host, const uint64_t *rows_host, size_t count,
                      float *out_host)
 {
     vsom_custom_state *u = c->cu;
@@ -314,7 +434,7 @@ static int pair_dist(vsom_ctx *c, const float *X, const uint64_t *nodes_host, co
     u64 xs = c->J, cnt = count;
     uint32_t J = c->J, D = c->D, R = u->R;
     int rc = launch(c, u->k_pair, (unsigned)((count + 63) / 64), 64, 0,
-                    {&X, &xs, &c->map.p, &u->sigf.p, &u->ones.p, &J, &D, &R, &dn, &dr, &cnt, &u->pair_out.p});
+                    {&X, &xs, &c->map.p, &u->sigf.p, &vw.p, &vw.stride, &J, &D, &R, &dn, &dr, &cnt, &u->pair_out.p});
     if (rc)
         return rc;
     VSOM_HIP_CHECK(hipMemcpyAsync(out_host, u->pair_out.p, count * 4, hipMemcpyDeviceToHost, c->stream));
@@ -322,15 +442,16 @@ static int pair_dist(vsom_ctx *c, const float *X, const uint64_t *nodes_host, co
     return VSOM_OK;
 }
 
-int vsom_custom_dist_single(vsom_ctx *c, const float *v_host, uint64_t node, float *dist_out)
+int vsom_custom_dist_single(vsom_ctx *c, const float *v_host, const uint8_t *valid_host, uint64_t node, float *dist_out)
 {
     if (node >= c->N || !dist_out)
         return vsom_fail(VSOM_ERR_INVALID, "node out of range or null output");
+    VwRef vw;
     int rc = stage_vec(c, v_host);
-    if (rc)
+    if (rc || (rc = vector_vw(c, valid_host, &vw)))
         return rc;
     const uint64_t row = 0;
-    return pair_dist(c, c->cu->vec.p, &node, &row, 1, dist_out);
+    return pair_dist(c, c->cu->vec.p, vw, &node, &row, 1, dist_out);
 }
 
 int vsom_custom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *rows_host, size_t count,
@@ -345,7 +466,7 @@ int vsom_custom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_
     for (size_t i = 0; i < count; ++i)
         if (nodes_host[i] >= c->N || rows_host[i] >= c->B)
             return vsom_fail(VSOM_ERR_INVALID, "pair index out of range");
-    return pair_dist(c, c->Xs.p, nodes_host, rows_host, count, dist_out_host);
+    return pair_dist(c, c->Xs.p, chunk_vw(c), nodes_host, rows_host, count, dist_out_host);
 }
 
 // Som::trainBatchSomEpoch (hostBatchEpoch): phase 1 search + residual, bmuHits / MSE, phase 2 per node
@@ -355,13 +476,14 @@ int vsom_custom_batch_epoch_async(vsom_ctx *c, double sigma, int is_first)
         return vsom_fail(VSOM_ERR_INVALID, "no chunk loaded");
     vsom_custom_state *u = c->cu;
     uint32_t B = (uint32_t)c->B, W = c->W, H = c->H, J = c->J, D = c->D, R = u->R;
-    int rc = is_first ? search_full(c, c->Xs.p, B, c->lastbmu.p, c->sqres.p)
-                      : search_local(c, c->Xs.p, B, c->lastbmu.p, c->lastbmu.p, c->sqres.p);
+    VwRef vw = chunk_vw(c), valid = chunk_valid(c);    // search: valid .* weights; residual and phase 2: valid alone
+    int rc = is_first ? search_full(c, c->Xs.p, vw, B, c->lastbmu.p, c->sqres.p)
+                      : search_local(c, c->Xs.p, vw, B, c->lastbmu.p, c->lastbmu.p, c->sqres.p);
     if (rc)
         return rc;
     u64 xs = c->J;
     if ((rc = launch(c, u->k_resid, (B + 63) / 64, 64, 0,
-                     {&c->Xs.p, &xs, &c->map.p, &c->S.p, &u->ones.p, &J, &D, &R, &c->lastbmu.p, &c->sqres.p, &B})))
+                     {&c->Xs.p, &xs, &c->map.p, &c->S.p, &valid.p, &valid.stride, &J, &D, &R, &c->lastbmu.p, &c->sqres.p, &B})))
         return rc;
     float *mse = c->mse.p;
     if ((rc = launch(c, u->k_finish, 1, 64, 0, {&c->lastbmu.p, &c->sqres.p, &B, &c->hits.p, &mse})))
@@ -371,12 +493,12 @@ int vsom_custom_batch_epoch_async(vsom_ctx *c, double sigma, int is_first)
     uint32_t lutw = c->lut_w;
     return launch(c, u->k_phase2, c->N, 256, 3 * D * 4,
                   {&c->Xs.p, &xs, &c->map.p, &c->sigma.p, &u->sigf.p, &c->weight.p, &c->lastbmu.p, &c->lut.p, &lutw, &W, &H, &B,
-                   &u->ones.p, &J, &D});
+                   &valid.p, &valid.stride, &J, &D});
 }
 
 // Som::trainSingle (hostTrainSingle) on one host vector
-int vsom_custom_train_single(vsom_ctx *c, const float *v_host, double eta, double sigma, uint64_t *last_bmu, int decay_fn,
-                             float *residual_out, float *dist_out, uint64_t *bmu_out)
+int vsom_custom_train_single(vsom_ctx *c, const float *v_host, const uint8_t *valid_host, double eta, double sigma,
+                             uint64_t *last_bmu, int decay_fn, float *residual_out, float *dist_out, uint64_t *bmu_out)
 {
     vsom_custom_state *u = c->cu;
     if (!v_host || !last_bmu)
@@ -385,12 +507,13 @@ int vsom_custom_train_single(vsom_ctx *c, const float *v_host, double eta, doubl
         return vsom_fail(VSOM_ERR_INVALID, "online training needs Exponential or InverseProportional");
     if (*last_bmu >= c->N)
         return vsom_fail(VSOM_ERR_INVALID, "lastBMU out of range");
+    VwRef vw;
     int rc = stage_vec(c, v_host);
-    if (rc || (rc = ensure_lutd(c, sigma)))
+    if (rc || (rc = vector_vw(c, valid_host, &vw)) || (rc = ensure_lutd(c, sigma)))
         return rc;
     u64 s = *last_bmu;
     VSOM_HIP_CHECK(hipMemcpyAsync(u->slot.p, &s, 8, hipMemcpyHostToDevice, c->stream));
-    if ((rc = online_step(c, u->vec.p, eta, sigma, decay_fn, u->slot.p, u->resid.p, u->fout.p + 1, nullptr, nullptr, 1)))
+    if ((rc = online_step(c, u->vec.p, vw, 0, eta, sigma, decay_fn, u->slot.p, u->resid.p, u->fout.p + 1, nullptr, nullptr, 1)))
         return rc;
     float d = 0.f;
     VSOM_HIP_CHECK(hipMemcpyAsync(&s, u->slot.p, 8, hipMemcpyDeviceToHost, c->stream));
@@ -422,8 +545,9 @@ int vsom_custom_train_online_chunk(vsom_ctx *c, double eta, double sigma, int de
         *static_cast<volatile float *>(c->mse.p) = 0.f;
     }
     const uint32_t B = (uint32_t)c->B;
+    const VwRef vw = chunk_vw(c);
     for (uint32_t s = 0; s < B; ++s)
-        if ((rc = online_step(c, c->Xs.p + (size_t)s * c->J, eta, sigma, decay_fn, c->lastbmu.p + s, nullptr, u->fout.p + 1,
+        if ((rc = online_step(c, c->Xs.p + (size_t)s * c->J, vw, s, eta, sigma, decay_fn, c->lastbmu.p + s, nullptr, u->fout.p + 1,
                               c->hits.p, c->mse.p, B)))
             return rc;
     return VSOM_OK;
@@ -484,7 +608,9 @@ int vsom_create_custom(vsom_ctx **out, int device, uint32_t width, uint32_t heig
                       {vsom_member(c->map, nd, VSOM_BUF_ZERO), vsom_member(c->sigma, nd, VSOM_BUF_ZERO),
                        vsom_member(c->S, nd, VSOM_BUF_ZERO), vsom_member(u->sigf, nd), vsom_member(u->ones, in_len),
                        vsom_member(u->vec, in_len), vsom_member(u->resid, residual_len), vsom_member(u->slot, 2),
-                       vsom_member(u->fout, 2), vsom_member(u->lutd, (size_t)width * height)}) != hipSuccess) {
+                       vsom_member(u->fout, 2), vsom_member(u->lutd, (size_t)width * height), vsom_member(u->wts, in_len),
+                       vsom_member(u->vec_bytes, in_len), vsom_member(u->vec_valid, in_len),
+                       vsom_member(u->vec_vw, in_len)}) != hipSuccess) {
         (void)hipGetLastError();
         return fail(VSOM_ERR_NOMEM, "hipMalloc of the custom context's state failed");
     }
@@ -497,8 +623,8 @@ int vsom_create_custom(vsom_ctx **out, int device, uint32_t width, uint32_t heig
         return fail(VSOM_ERR_HIP, "hipModuleLoadData of the hook module failed");
     }
     struct { hipFunction_t *f; const char *name; } fns[] = {
-        {&u->k_floor, "vc_floor_sigma"}, {&u->k_full, "vc_search_full"}, {&u->k_local, "vc_search_local"},
-        {&u->k_pair, "vc_pair_dist"}, {&u->k_resid, "vc_batch_residual"}, {&u->k_finish, "vc_batch_finish"},
+        {&u->k_floor, "vc_floor_sigma"}, {&u->k_expand, "vc_expand_validity"}, {&u->k_full, "vc_search_full"},
+        {&u->k_local, "vc_search_local"}, {&u->k_pair, "vc_pair_dist"}, {&u->k_resid, "vc_batch_residual"}, {&u->k_finish, "vc_batch_finish"},
         {&u->k_phase2, "vc_batch_phase2"}, {&u->k_onl_update, "vc_online_update"}, {&u->k_onl_post, "vc_online_post"}};
     for (auto &f : fns)
         if (hipModuleGetFunction(f.f, u->mod, f.name) != hipSuccess) {

@@ -8,6 +8,12 @@
 // Every kernel reproduces one loop of host/src/vsom_custom.cpp with the same fp32 operations (the module is built
 // with -ffp-contract=off and correctly rounded division / square root), so a hook that computes what a host hook
 // computes gives the same bits.  Neighbourhood weights come from host-built tables (glibc's exp, like the host).
+//
+// value_weight: every kernel that hands the hooks a value_weight row takes `vw` with a row stride `vws` (in floats); the
+// row of sample s is vw + s * vws, and stride 0 is one shared [J] vector.  vsom_custom.hip passes what Som.cpp builds at
+// that call: valid .* weights for the searches and the online step, valid alone for the batch residual and phase 2.
+// The kernels with one thread per sample branch on the stride once: with stride 0 the pointer stays uniform over the
+// wavefront, so the hooks' reads of value_weight stay scalar loads, as they were before the stride existed.
 R"VSOMRTC(
 typedef unsigned long long vc_u64;
 
@@ -60,13 +66,28 @@ __device__ float vc_sqnorm(const float *x, const float *model, const float *disp
 
 // Som::euclidianWeightedDist (hostDist): sigf holds the floored sigmaMap, select(sigma < 1e-5, 1e-5, sigma)
 struct VcDist {
-    const float *map, *sigf, *vw;
+    const float *map, *sigf, *vw;      // vw: the value_weight row of the sample the distances are taken for
     uint32_t J, D, R;
     __device__ float operator()(vc_u64 node, const float *x) const
     {
         return vc_sqnorm(x, map + node * D, sigf + node * D, vw, J, D, R);
     }
 };
+
+// validity bytes and column weights -> the two value_weight arrays: valid as 0.0f / 1.0f, and valid * weights (one fp32
+// product per element).  bytes == null: all valid; weights == null: all 1.  n = rows * J elements; the column of element
+// i is i % J (a column mask or weights alone are one row).
+extern "C" __global__ void vc_expand_validity(const unsigned char *__restrict__ bytes, const float *__restrict__ weights,
+    float *__restrict__ valid, float *__restrict__ vw, vc_u64 n, uint32_t J)
+{
+    const vc_u64 i = (vc_u64)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n)
+        return;
+    const float v = (bytes == nullptr || bytes[i] != 0) ? 1.f : 0.f;
+    const float w = weights ? weights[i % J] : 1.f;
+    valid[i] = v;
+    vw[i] = v * w;
+}
 
 extern "C" __global__ void vc_floor_sigma(const float *__restrict__ sigma, float *__restrict__ sigf, vc_u64 n)
 {
@@ -80,12 +101,13 @@ extern "C" __global__ void vc_floor_sigma(const float *__restrict__ sigma, float
 // hostFindBmu for sample row blockIdx.x: node 0 first, strict '<', lowest index wins ties, NaN never wins (and a NaN
 // distance of node 0 keeps node 0).  One workgroup of 256 per sample; dist_out = the BMU's distance.
 extern "C" __global__ __launch_bounds__(256) void vc_search_full(const float *X, vc_u64 xstride, const float *map,
-    const float *sigf, const float *vw, uint32_t N, uint32_t J, uint32_t D, uint32_t R, vc_u64 *bmu_out, float *dist_out)
+    const float *sigf, const float *vw, vc_u64 vws, uint32_t N, uint32_t J, uint32_t D, uint32_t R, vc_u64 *bmu_out,
+    float *dist_out)
 {
     __shared__ float sd[256];
     __shared__ uint32_t si[256];
     __shared__ float d0s;
-    const VcDist dist{map, sigf, vw, J, D, R};
+    const VcDist dist{map, sigf, vw + (vc_u64)blockIdx.x * vws, J, D, R};
     const float *x = X + (vc_u64)blockIdx.x * xstride;
     const uint32_t t = threadIdx.x;
     float best = __builtin_inff();
@@ -164,40 +186,43 @@ __device__ vc_u64 vc_local_walk(const VcDist &dist, const float *x, vc_u64 width
 
 // one thread per sample: start[s] -> bmu_out[s] (may be the same array), dist_out[s] = the BMU's distance
 extern "C" __global__ void vc_search_local(const float *X, vc_u64 xstride, const float *map, const float *sigf,
-    const float *vw, uint32_t W, uint32_t H, uint32_t J, uint32_t D, uint32_t R, const vc_u64 *start, vc_u64 *bmu_out,
-    float *dist_out, uint32_t B)
+    const float *vw, vc_u64 vws, uint32_t W, uint32_t H, uint32_t J, uint32_t D, uint32_t R, const vc_u64 *start,
+    vc_u64 *bmu_out, float *dist_out, uint32_t B)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= B)
         return;
-    const VcDist dist{map, sigf, vw, J, D, R};
+    const float *x = X + (vc_u64)s * xstride;
     float d = 0.f;
-    const vc_u64 b = vc_local_walk(dist, X + (vc_u64)s * xstride, W, H, start[s], d);
+    const vc_u64 b = vws == 0 ? vc_local_walk(VcDist{map, sigf, vw, J, D, R}, x, W, H, start[s], d)
+                              : vc_local_walk(VcDist{map, sigf, vw + (vc_u64)s * vws, J, D, R}, x, W, H, start[s], d);
     bmu_out[s] = b;
     dist_out[s] = d;
 }
 
 // euclidianWeightedDist for `count` (node, row) pairs
 extern "C" __global__ void vc_pair_dist(const float *X, vc_u64 xstride, const float *map, const float *sigf,
-    const float *vw, uint32_t J, uint32_t D, uint32_t R, const vc_u64 *nodes, const vc_u64 *rows, vc_u64 count,
-    float *out)
+    const float *vw, vc_u64 vws, uint32_t J, uint32_t D, uint32_t R, const vc_u64 *nodes, const vc_u64 *rows,
+    vc_u64 count, float *out)
 {
     const vc_u64 i = (vc_u64)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= count)
         return;
-    const VcDist dist{map, sigf, vw, J, D, R};
-    out[i] = dist(nodes[i], X + rows[i] * xstride);
+    const float *x = X + rows[i] * xstride;
+    out[i] = vws == 0 ? VcDist{map, sigf, vw, J, D, R}(nodes[i], x) : VcDist{map, sigf, vw + rows[i] * vws, J, D, R}(nodes[i], x);
 }
 
 // hostBatchEpoch phase 1 tail: ||Comparer(x, M[bmu], S[bmu], valid)||^2 per sample (the residual takes SMap rows)
 extern "C" __global__ void vc_batch_residual(const float *X, vc_u64 xstride, const float *map, const float *S,
-    const float *vw, uint32_t J, uint32_t D, uint32_t R, const vc_u64 *bmu, float *sq, uint32_t B)
+    const float *vw, vc_u64 vws, uint32_t J, uint32_t D, uint32_t R, const vc_u64 *bmu, float *sq, uint32_t B)
 {
     const uint32_t s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= B)
         return;
     const vc_u64 b = bmu[s];
-    sq[s] = vc_sqnorm(X + (vc_u64)s * xstride, map + b * D, S + b * D, vw, J, D, R);
+    const float *x = X + (vc_u64)s * xstride;
+    sq[s] = vws == 0 ? vc_sqnorm(x, map + b * D, S + b * D, vw, J, D, R)
+                     : vc_sqnorm(x, map + b * D, S + b * D, vw + (vc_u64)s * vws, J, D, R);
 }
 
 // bmuHits += 1 and the fp32 MSE summed in sample order (one thread: the order is the result)
@@ -217,7 +242,7 @@ extern "C" __global__ void vc_batch_finish(const vc_u64 *bmu, const float *sq, u
 // lut[dy * lutw + dx] = (float)calculateNeighbourhoodWeight(dx, dy, 0, 0, sigma); SomIndex's y divides by HEIGHT.
 extern "C" __global__ __launch_bounds__(256) void vc_batch_phase2(const float *X, vc_u64 xstride, float *map,
     float *sigma, float *sigf, float *weight, const vc_u64 *bmu, const float *lut, uint32_t lutw, uint32_t W, uint32_t H,
-    uint32_t B, const float *vw, uint32_t J, uint32_t D)
+    uint32_t B, const float *vw, vc_u64 vws, uint32_t J, uint32_t D)
 {
     extern __shared__ float lds[];
     float *model = lds, *delta = lds + D, *spread = lds + 2 * D;
@@ -237,7 +262,7 @@ extern "C" __global__ __launch_bounds__(256) void vc_batch_phase2(const float *X
         total += w;
         const float *x = X + (vc_u64)j * xstride;
         for (uint32_t d = t; d < D; d += blockDim.x)
-            delta[d] = vsom_step(d, x, model, vw, J, D);
+            delta[d] = vsom_step(d, x, model, vw + (vc_u64)j * vws, J, D);
         __syncthreads();
         const float c = w / total;
         for (uint32_t d = t; d < D; d += blockDim.x) {
@@ -262,10 +287,11 @@ extern "C" __global__ __launch_bounds__(256) void vc_batch_phase2(const float *X
 // *bmu; nodes outside the window leave at once.  lutd[dy * W + dx] = calculateNeighbourhoodWeight(dx, dy, 0, 0, sigma).
 extern "C" __global__ __launch_bounds__(256) void vc_online_update(const float *v, float *map, float *S, float *sigma,
     float *sigf, float *weight, const vc_u64 *bmu, const double *lutd, uint32_t W, uint32_t H, const float *vw,
-    uint32_t J, uint32_t D, double eta, double sig, int decay_fn, uint32_t nx)
+    vc_u64 vws, vc_u64 row, uint32_t J, uint32_t D, double eta, double sig, int decay_fn, uint32_t nx)
 {
     extern __shared__ float lds[];
     float *model = lds, *delta = lds + D;
+    vw += row * vws;                      // the value_weight row of sample `row`
     const vc_u64 b = *bmu, bx = b % W, by = b / W;
     const vc_u64 x0 = (vc_u64)fmax((double)bx - 2.5 * sig, 0.), y0 = (vc_u64)fmax((double)by - 2.5 * sig, 0.);
     const vc_u64 x1 = (vc_u64)fmin((double)bx + 2.5 * sig, (double)W), y1 = (vc_u64)fmin((double)by + 2.5 * sig, (double)H);
@@ -314,11 +340,12 @@ extern "C" __global__ __launch_bounds__(256) void vc_online_update(const float *
 // hostTrainSingle's tail: the residual Comparer(v, M[bmu], sigmaMap[bmu], vw) (into resid when given), the distance of
 // the BMU; hits[bmu] += 1 and mse += ||residual||^2 / B when given (trainBasicSom's loop body)
 extern "C" __global__ void vc_online_post(const float *v, const float *map, const float *sigma, const float *sigf,
-    const float *vw, uint32_t J, uint32_t D, uint32_t R, const vc_u64 *bmu, float *resid, float *dist_out, vc_u64 *hits,
-    float *mse, uint32_t B)
+    const float *vw, vc_u64 vws, vc_u64 row, uint32_t J, uint32_t D, uint32_t R, const vc_u64 *bmu, float *resid,
+    float *dist_out, vc_u64 *hits, float *mse, uint32_t B)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0)
         return;
+    vw += row * vws;                      // the value_weight row of sample `row`
     const vc_u64 b = *bmu;
     const float *M = map + b * D;
     const float sq = vc_packet_sum(R, [&](uint32_t r) {

@@ -603,12 +603,26 @@ int vsom_custom_upload(vsom_ctx *c, const float *x_host, size_t B, bool wait);
 int vsom_custom_prefetch(vsom_ctx *c, const float *x_host, size_t B);
 int vsom_custom_commit(vsom_ctx *c);
 int vsom_custom_bmu_batch(vsom_ctx *c, int local, uint64_t *idx_out_host, float *dist_out_host);
-int vsom_custom_find(vsom_ctx *c, const float *v_host, int local, uint64_t start, uint64_t *bmu_out, float *dist_out);
-int vsom_custom_dist_single(vsom_ctx *c, const float *v_host, uint64_t node, float *dist_out);
+// (valid_host: the vector's validity bytes for the _valid entry points, null = all valid; the column weights always apply)
+int vsom_custom_find(vsom_ctx *c, const float *v_host, const uint8_t *valid_host, int local, uint64_t start, uint64_t *bmu_out,
+                     float *dist_out);
+int vsom_custom_dist_single(vsom_ctx *c, const float *v_host, const uint8_t *valid_host, uint64_t node, float *dist_out);
 int vsom_custom_distances(vsom_ctx *c, const uint64_t *nodes_host, const uint64_t *rows_host, size_t count,
                           float *dist_out_host);
 int vsom_custom_batch_epoch_async(vsom_ctx *c, double sigma, int is_first);
-int vsom_custom_train_single(vsom_ctx *c, const float *v_host, double eta, double sigma, uint64_t *last_bmu, int decay_fn,
-                             float *residual_out, float *dist_out, uint64_t *bmu_out);
+int vsom_custom_train_single(vsom_ctx *c, const float *v_host, const uint8_t *valid_host, double eta, double sigma,
+                             uint64_t *last_bmu, int decay_fn, float *residual_out, float *dist_out, uint64_t *bmu_out);
+// vsom_set_column_weights / vsom_set_chunk_validity and the four _valid calls exist on custom contexts only: the gate of
+// those six entry points (a null context, then a built-in one, are VSOM_ERR_INVALID)
+#define VSOM_CUSTOM_ONLY(ctx, what)                                    \
+    do {                                                               \
+        if (!(ctx))                                                    \
+            return vsom_fail(VSOM_ERR_INVALID, "null context");        \
+        if (!(ctx)->cu)                                                \
+            return vsom_custom_only(what);                             \
+    } while (0)
+int vsom_custom_only(const char *what);
+int vsom_custom_set_weights(vsom_ctx *c, const float *weights_host);
+int vsom_custom_set_validity(vsom_ctx *c, const uint8_t *valid_host, int one_mask);
 int vsom_custom_train_online_chunk(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk);
 uint32_t vsom_custom_residual_len(const vsom_ctx *c);

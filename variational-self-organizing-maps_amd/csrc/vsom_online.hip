@@ -637,12 +637,21 @@ int vsom_train_online_chunk(vsom_ctx *c, double eta, double sigma, int decay_fn,
     return vsom_train_online_chunk_acc(c, eta, sigma, decay_fn, 1, mse_out);
 }
 
+// vsom_train_single with the vector's validity bytes (custom contexts only): value_weight = valid .* column weights
+int vsom_train_single_valid(vsom_ctx *c, const float *v_host, const uint8_t *valid_host, double eta, double sigma,
+                            uint64_t *last_bmu, int decay_fn, float *residual_out, float *dist_out, uint64_t *bmu_out)
+{
+    VSOM_CUSTOM_ONLY(c, "vsom_train_single_valid");
+    CHECK_CTX_NOJOIN(c);
+    return vsom_custom_train_single(c, v_host, valid_host, eta, sigma, last_bmu, decay_fn, residual_out, dist_out, bmu_out);
+}
+
 int vsom_train_single(vsom_ctx *c, const float *v_host, double eta, double sigma, uint64_t *last_bmu,
                       int decay_fn, float *residual_out, float *dist_out, uint64_t *bmu_out)
 {
     CHECK_CTX_NOJOIN(c);
     if (c->cu)
-        return vsom_custom_train_single(c, v_host, eta, sigma, last_bmu, decay_fn, residual_out, dist_out, bmu_out);
+        return vsom_custom_train_single(c, v_host, nullptr, eta, sigma, last_bmu, decay_fn, residual_out, dist_out, bmu_out);
     // not CHECK_CTX: a custom context leaves before the join, and the step reads its own copy of the vector, not the staged
     // rows, so rows_free_valid stays as it is
     if (int jrc = vsom_join_aux(c))

@@ -132,7 +132,7 @@ int vsom_find_bmu(vsom_ctx *c, const float *v_host, uint64_t *bmu_out, float *di
 {
     CHECK_CTX_NOJOIN(c);
     if (c->cu)
-        return vsom_custom_find(c, v_host, 0, 0, bmu_out, dist_out);
+        return vsom_custom_find(c, v_host, nullptr, 0, 0, bmu_out, dist_out);
     if (int jrc = vsom_join_aux(c))
         return jrc;
     if (!v_host)
@@ -258,7 +258,7 @@ int vsom_distances_single(vsom_ctx *c, const float *v_host, float *dist_out_host
 int vsom_dist_single(vsom_ctx *c, const float *v_host, uint64_t node, float *dist_out)
 {
     if (c && c->cu && hipSetDevice(c->device) == hipSuccess)
-        return vsom_custom_dist_single(c, v_host, node, dist_out);
+        return vsom_custom_dist_single(c, v_host, nullptr, node, dist_out);
     return single_query(c, v_host, node, 0, nullptr, dist_out);
 }
 
@@ -266,8 +266,31 @@ int vsom_dist_single(vsom_ctx *c, const float *v_host, uint64_t node, float *dis
 int vsom_find_local_bmu(vsom_ctx *c, const float *v_host, uint64_t last_bmu, uint64_t *bmu_out, float *dist_out)
 {
     if (c && c->cu && hipSetDevice(c->device) == hipSuccess)
-        return vsom_custom_find(c, v_host, 1, last_bmu, bmu_out, dist_out);
+        return vsom_custom_find(c, v_host, nullptr, 1, last_bmu, bmu_out, dist_out);
     return single_query(c, v_host, last_bmu, 1, bmu_out, dist_out);
+}
+
+// the three searches above with the vector's validity bytes (custom contexts only): value_weight = valid .* column weights
+int vsom_find_bmu_valid(vsom_ctx *c, const float *v_host, const uint8_t *valid_host, uint64_t *bmu_out, float *dist_out)
+{
+    VSOM_CUSTOM_ONLY(c, "vsom_find_bmu_valid");
+    CHECK_CTX_NOJOIN(c);
+    return vsom_custom_find(c, v_host, valid_host, 0, 0, bmu_out, dist_out);
+}
+
+int vsom_find_local_bmu_valid(vsom_ctx *c, const float *v_host, const uint8_t *valid_host, uint64_t last_bmu, uint64_t *bmu_out,
+                              float *dist_out)
+{
+    VSOM_CUSTOM_ONLY(c, "vsom_find_local_bmu_valid");
+    CHECK_CTX_NOJOIN(c);
+    return vsom_custom_find(c, v_host, valid_host, 1, last_bmu, bmu_out, dist_out);
+}
+
+int vsom_dist_single_valid(vsom_ctx *c, const float *v_host, const uint8_t *valid_host, uint64_t node, float *dist_out)
+{
+    VSOM_CUSTOM_ONLY(c, "vsom_dist_single_valid");
+    CHECK_CTX_NOJOIN(c);
+    return vsom_custom_dist_single(c, v_host, valid_host, node, dist_out);
 }
 
 }   // extern "C"

@@ -9,6 +9,7 @@ $CXX $FLAGS "$here/tests/host_api_test.cpp" -o "$here/host_api_test" -L"$here" -
 $CXX $FLAGS "$here/tests/host_loader_test.cpp" -o "$here/host_loader_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_custom_test.cpp" -o "$here/host_custom_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_custom_device_test.cpp" -o "$here/host_custom_device_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
+$CXX $FLAGS "$here/tests/host_custom_validity_test.cpp" -o "$here/host_custom_validity_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_bmd_test.cpp" -o "$here/host_bmd_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_topk_test.cpp" -o "$here/host_topk_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_umatrix_test.cpp" -o "$here/host_umatrix_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'

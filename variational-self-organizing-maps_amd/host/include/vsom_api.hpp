@@ -350,6 +350,9 @@ struct Transformation {
     // [MI355X build] the caller's hooks as HIP device source (include/vsom_hip.h, vsom_create_custom: vsom_compare /
     // vsom_step per output element).  Non-empty on a Custom transformation: the Som compiles it with hipRTC and trains
     // on the device; empty: the host path of src/vsom_custom.cpp.  Comparer / Stepper stay the host hooks for direct calls.
+    // The device hooks get the valueWeight the host hooks get: the Som sets the loaded chunk's validity
+    // (DataSet::getValidity) and the loader's column weights (DataSet::getWeights) on the context after every chunk it
+    // uploads, and findBmu / findLocalBmu / euclidianWeightedDist / trainSingle pass their valid and weights along.
     std::string DeviceSource{};
     // residual length of DeviceSource's Comparer for a sample length J (empty: Length(J))
     std::function<size_t(size_t vectorLength)> ResidualLength{};
@@ -688,6 +691,12 @@ private:
     void hostTrainBasicSom(DataSet &data, size_t numberOfEpochs, double eta0, double etaDecay, double sigma0, double sigmaDecay,
                            WeigthDecayFunction fn, bool updateUMatrixAfterEpoch);
     void createContext();
+    // device hooks (Transformation::Device): the hooks' valueWeight comes from the context's column weights and the loaded
+    // chunk's validity (include/vsom_hip.h, "value_weight"); devWeights is what the context holds (empty: all 1)
+    bool deviceHooks() const noexcept;
+    mutable std::vector<float> devWeights;
+    void applyDeviceWeights(const Eigen::VectorXf &weights) const;
+    void applyChunkValidity(const DataSet &data) const;
     void requireDevicePath(const char *what) const;
     void trainWhole(const char *what, bool masked, DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
                     bool updateUMatrixAfterEpoch, bool resetBmu);

@@ -619,6 +619,7 @@ void Som::createContext()
 
 void Som::destroyContext()
 {
+    devWeights.clear();           // (a context created after this one holds no column weights)
     if (grp)
         vsom_group_destroy(grp);   // owns its members, ctx included
     else if (ctx)
@@ -953,6 +954,31 @@ void Som::stageOne(const Eigen::VectorXf &v) const
     check(vsom_upload_chunk(ctx, v.data(), 1), "vsom_upload_chunk");
 }
 
+// one vector's validity as the bytes of the _valid calls (a column the vector has no flag for does not count)
+static std::vector<uint8_t> vector_validity(const Eigen::VectorXf &valid, size_t inLen)
+{
+    std::vector<uint8_t> vb(inLen, 0);
+    for (size_t d = 0; d < std::min<size_t>((size_t)valid.size(), inLen); ++d)
+        vb[d] = valid[(Eigen::Index)d] != 0.f;
+    return vb;
+}
+
+bool Som::deviceHooks() const noexcept { return ctx && transform.kind() == vsom::Custom; }
+
+// the context's column weights := weights, when they are not what it holds already (all 1: unset)
+void Som::applyDeviceWeights(const Eigen::VectorXf &weights) const
+{
+    if ((size_t)weights.size() != inLen)
+        throw std::invalid_argument("the weights' length does not match the map");
+    std::vector<float> w(weights.data(), weights.data() + weights.size());
+    if (std::all_of(w.begin(), w.end(), [](float x) { return x == 1.f; }))
+        w.clear();
+    if (w.size() == devWeights.size() && (w.empty() || std::memcmp(w.data(), devWeights.data(), w.size() * sizeof(float)) == 0))
+        return;
+    check(vsom_set_column_weights(ctx, w.empty() ? nullptr : w.data()), "vsom_set_column_weights");
+    devWeights = w;
+}
+
 SomIndex Som::findBmu(const Eigen::VectorXf &v) const
 {
     Eigen::VectorXf ones = Eigen::VectorXf::Ones(v.size());
@@ -968,6 +994,12 @@ SomIndex Som::findBmu(const Eigen::VectorXf &v, const Eigen::VectorXf &valid, co
     if ((size_t)v.size() != inLen)
         throw std::invalid_argument("sample length does not match the map");
     uint64_t idx = 0;
+    if (deviceHooks()) {          // the hooks take valid .* weights (Som.cpp:134)
+        applyDeviceWeights(weights);
+        const std::vector<uint8_t> vb = vector_validity(valid, inLen);
+        check(vsom_find_bmu_valid(ctx, v.data(), vb.data(), &idx, nullptr), "vsom_find_bmu_valid");
+        return SomIndex((size_t)idx % width, (size_t)idx / width);
+    }
     check(vsom_find_bmu(ctx, v.data(), &idx, nullptr), "vsom_find_bmu");
     return SomIndex((size_t)idx % width, (size_t)idx / width);   // Som.cpp:306
 }
@@ -982,6 +1014,12 @@ SomIndex Som::findLocalBmu(const Eigen::VectorXf &v, const Eigen::VectorXf &vali
     if ((size_t)v.size() != inLen)
         throw std::invalid_argument("sample length does not match the map");
     uint64_t idx = lastBMUref;
+    if (deviceHooks()) {
+        applyDeviceWeights(weights);
+        const std::vector<uint8_t> vb = vector_validity(valid, inLen);
+        check(vsom_find_local_bmu_valid(ctx, v.data(), vb.data(), lastBMUref, &idx, nullptr), "vsom_find_local_bmu_valid");
+        return SomIndex((size_t)idx % width, (size_t)idx / width);
+    }
     check(vsom_find_local_bmu(ctx, v.data(), lastBMUref, &idx, nullptr), "vsom_find_local_bmu");
     return SomIndex((size_t)idx % width, (size_t)idx / width);
 }
@@ -1000,6 +1038,12 @@ double Som::euclidianWeightedDist(const size_t &pos, const Eigen::VectorXf &v, c
     if ((size_t)v.size() != inLen)
         throw std::invalid_argument("sample length does not match the map");
     float d = 0.f;
+    if (deviceHooks()) {
+        applyDeviceWeights(weights);
+        const std::vector<uint8_t> vb = vector_validity(valid, inLen);
+        check(vsom_dist_single_valid(ctx, v.data(), vb.data(), pos, &d), "vsom_dist_single_valid");
+        return (double)d;
+    }
     check(vsom_dist_single(ctx, v.data(), pos, &d), "vsom_dist_single");
     return (double)d;
 }
@@ -1016,6 +1060,18 @@ static std::vector<uint8_t> validity_bytes(const DataSet &data, size_t inLen)
             valid[i * inLen + d] = v[(Eigen::Index)d] != 0;
     }
     return valid;
+}
+
+// after a chunk of `data` became the context's current one (device hooks): the loader's column weights and, when any
+// entry is invalid, the chunk's validity (the upload itself left it all valid)
+void Som::applyChunkValidity(const DataSet &data) const
+{
+    if (!deviceHooks())
+        return;
+    applyDeviceWeights(data.getWeights());
+    const std::vector<uint8_t> valid = validity_bytes(data, inLen);
+    if (std::find(valid.begin(), valid.end(), (uint8_t)0) != valid.end())
+        check(vsom_set_chunk_validity(ctx, valid.data(), 0), "vsom_set_chunk_validity");
 }
 
 // ---- batch training ----------------------------------------------------------------------------
@@ -1041,6 +1097,7 @@ float Som::trainBatchSomEpoch(DataSet &dataset, double currentSigma, bool isFirs
         check(vsom_group_get_last_bmu(grp, lb.data()), "vsom_group_get_last_bmu");
     } else {
         check(vsom_upload_chunk(ctx, dataset.contiguous(), B), "vsom_upload_chunk");
+        applyChunkValidity(dataset);
         if (!isFirst)
             check(vsom_set_last_bmu(ctx, lb.data()), "vsom_set_last_bmu");
         check(vsom_batch_epoch(ctx, currentSigma, isFirst ? 1 : 0, &mse), "vsom_batch_epoch");
@@ -1114,6 +1171,7 @@ void Som::trainBatchSom(DataSet &data, size_t numberOfEpochs, double sigma0, dou
             const size_t Bcur = B;
             // (also for an empty chunk: the reference's epoch then zeroes the map, see trainBatchSomEpoch)
             commit();   // lastBMU := 0 (DataSet.cpp:136-137)
+            applyChunkValidity(data);   // (`data` still holds the committed chunk: the next load comes below)
             epochAsync(sigma, i == 0 ? 1 : 0);
             have = false;
             const bool last = data.hasReadWholeDataStream();
@@ -1394,8 +1452,15 @@ Som::TrainingReturnValue Som::trainSingle(const Eigen::VectorXf &v, const Eigen:
     Eigen::VectorXf residual((Eigen::Index)vsom_residual_len(ctx));
     uint64_t lb = lastBMU, bmu = 0;
     float dist = 0.f;
-    check(vsom_train_single(ctx, v.data(), eta, sigma, &lb, decay_code(weightDecayFunction), residual.data(), &dist, &bmu),
-          "vsom_train_single");
+    if (deviceHooks()) {          // the hooks take valid .* weights (Som.cpp:905)
+        applyDeviceWeights(weights);
+        const std::vector<uint8_t> vb = vector_validity(valid, inLen);
+        check(vsom_train_single_valid(ctx, v.data(), vb.data(), eta, sigma, &lb, decay_code(weightDecayFunction), residual.data(),
+                                      &dist, &bmu),
+              "vsom_train_single_valid");
+    } else
+        check(vsom_train_single(ctx, v.data(), eta, sigma, &lb, decay_code(weightDecayFunction), residual.data(), &dist, &bmu),
+              "vsom_train_single");
     lastBMU = (size_t)lb;
     hostStale = true;
     replicasStale = grp != nullptr;
@@ -1435,6 +1500,7 @@ void Som::trainBasicSom(DataSet &data, size_t numberOfEpochs, double eta0, doubl
             // stream could overlap with -- copy and staging go straight onto the context's stream, no events, no wait (the
             // DataSet's pinned buffer is not rewritten before the chunk after next is loaded)
             check(vsom_upload_chunk_async(ctx, data.contiguous(), B), "vsom_upload_chunk_async");
+            applyChunkValidity(data);
             have = true;
             staged = true;
         }
@@ -1442,8 +1508,10 @@ void Som::trainBasicSom(DataSet &data, size_t numberOfEpochs, double eta0, doubl
             const size_t Bcur = B;
             // meanSquareError is ONE running float over all chunks of the epoch (:1153,1167): the device
             // keeps it across chunks (first chunk starts at 0); an empty chunk adds nothing
-            if (!staged)
+            if (!staged) {
                 check(vsom_commit_chunk(ctx), "vsom_commit_chunk");
+                applyChunkValidity(data);   // (`data` still holds the committed chunk: the next load comes below)
+            }
             staged = false;
             have = false;
             const bool last = data.hasReadWholeDataStream();
@@ -1766,6 +1834,15 @@ double Som::evaluate(const DataSet &data) const
     } else {   // a Transformation::Device Som (vsom_evaluate_batch refuses custom contexts), or a validity flag outside {0, 1}
         refreshHost();
         check(vsom_upload_chunk(ctx, data.contiguous(), n), "vsom_upload_chunk");
+        if (deviceHooks()) {      // the hooks get what the host branch above hands them: val = validity * continuous, these weights
+            applyDeviceWeights(data.getWeights());
+            std::vector<uint8_t> val = validity_bytes(data, inLen);
+            for (size_t i = 0; i < n; ++i)
+                for (size_t d = 0; d < inLen; ++d)
+                    val[i * inLen + d] = val[i * inLen + d] && d < (size_t)continuous.size() && continuous[(Eigen::Index)d] != 0;
+            if (std::find(val.begin(), val.end(), (uint8_t)0) != val.end())
+                check(vsom_set_chunk_validity(ctx, val.data(), 0), "vsom_set_chunk_validity");
+        }
         check(vsom_bmu_batch(ctx, bmu.data(), dist.data()), "vsom_bmu_batch");   // findBmu + euclidianWeightedDist(bmu)
     }
     double error = 0;

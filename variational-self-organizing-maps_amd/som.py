@@ -322,17 +322,55 @@ class Som:
         v = np.ascontiguousarray(v, dtype=np.float32).reshape(1, -1)
         self.ctx.upload_chunk(v)
 
+    # Transformation.Custom: the hooks' valueWeight is real on the device (capi.Context.set_column_weights /
+    # set_chunk_validity and the valid= keyword); the built-in transformations ignore valid and weights, as the reference's do
+    def _custom(self):
+        return self.ctx.transform == capi.CUSTOM
+
+    def _setWeights(self, weights):
+        """the context's column weights := weights (None: all 1), when they are not what it holds already"""
+        w = None if weights is None else np.ascontiguousarray(weights, dtype=np.float32)
+        if w is not None and (w == 1).all():
+            w = None
+        held = getattr(self, "_devWeights", None)
+        if (w is None) != (held is None) or (w is not None and w.tobytes() != held.tobytes()):
+            self.ctx.set_column_weights(w)
+            self._devWeights = None if w is None else w.copy()
+
+    def _chunkToDevice(self, data):
+        """upload the data set's loaded rows; with custom hooks also its column weights and -- when it has an attribute
+        `validity` (loaded rows x J, nonzero = valid) with an invalid entry -- the chunk's validity"""
+        self.ctx.upload_chunk(data.data)
+        if not self._custom():
+            return
+        self._setWeights(data.getWeights() if hasattr(data, "getWeights") else None)
+        valid = getattr(data, "validity", None)
+        if valid is not None and not np.asarray(valid).all():
+            self.ctx.set_chunk_validity(np.asarray(valid))
+
+    def _vectorValid(self, valid, weights):
+        """valid= of the single-vector calls of a custom context (None elsewhere), after setting the weights"""
+        if not self._custom():
+            return None
+        self._setWeights(weights)
+        return None if valid is None else np.asarray(valid)
+
     def findBmu(self, v, valid=None, weights=None):
-        idx, _ = self.ctx.find_bmu(v)
+        idx, _ = self.ctx.find_bmu(v, valid=self._vectorValid(valid, weights))
         return SomIndex(idx % self.width, idx // self.width)
 
     def findLocalBmu(self, v, valid, lastBMUref, weights=None):
+        if self._custom():
+            idx, _ = self.ctx.find_local_bmu(v, lastBMUref, valid=self._vectorValid(valid, weights))
+            return SomIndex(idx % self.width, idx // self.width)
         self._stage_one(v)
         self.ctx.set_last_bmu(np.array([lastBMUref], np.uint64))
         idx, _ = self.ctx.bmu_local_batch()
         return SomIndex(int(idx[0]) % self.width, int(idx[0]) // self.width)
 
     def euclidianWeightedDist(self, pos, v, valid=None, weights=None):
+        if self._custom():
+            return float(self.ctx.dist_single(v, self._node(pos), valid=self._vectorValid(valid, weights)))
         self._stage_one(v)
         return float(self.ctx.distances([self._node(pos)], [0])[0])
 
@@ -599,7 +637,7 @@ class Som:
 
     # ---- batch training (Som.cpp:716-879) --------------------------------------------------
     def trainBatchSomEpoch(self, dataset, currentSigma, isFirst):
-        self.ctx.upload_chunk(dataset.data)
+        self._chunkToDevice(dataset)
         if not isFirst:
             self.ctx.set_last_bmu(dataset.lastBMU)
         mse = self.ctx.batch_epoch(currentSigma, isFirst)
@@ -826,7 +864,8 @@ class Som:
 
     # ---- online training (Som.cpp:885-947, 1135-1187) ---------------------------------------
     def trainSingle(self, v, valid, weights, eta, sigma, lastBMU, weightDecayFunction):
-        bmu, residual, dist, last = self.ctx.train_single(v, eta, sigma, lastBMU, int(weightDecayFunction))
+        bmu, residual, dist, last = self.ctx.train_single(v, eta, sigma, lastBMU, int(weightDecayFunction),
+                                                          valid=self._vectorValid(valid, weights))
         return SomIndex(bmu % self.width, bmu // self.width), residual, dist, last
 
     def trainBasicSom(self, data, numberOfEpochs, eta0, etaDecay, sigma0, sigmaDecay,
@@ -856,7 +895,10 @@ class Som:
             count = 0
             while not data.hasReadWholeDataStream():
                 data.loadNextDataFromStream()
-                self.ctx.upload_chunk(data.data)                  # lastBMU zeroed by the load
+                if masked:
+                    self.ctx.upload_chunk(data.data)              # lastBMU zeroed by the load
+                else:
+                    self._chunkToDevice(data)                     # (custom hooks: with the chunk's validity and the weights)
                 # ONE running accumulator over the epoch's chunks (Som.cpp:1153,1167)
                 if masked:
                     mse, lb = self.ctx.train_online_chunk_masked(eta, sigma, int(weightDecayFunction),
