@@ -658,6 +658,53 @@ int vsom_bmd_masked_batch(vsom_ctx *ctx, uint64_t min_hits, size_t r0, size_t r1
 int vsom_generate_masked_batch(vsom_ctx *ctx, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
                                uint32_t draws, int keep_observed, const double *u_host, const double *l_host,
                                vsom_generate_out *out);
+/* The k best matching units of chunk rows [r0, r1) over their VALID columns only -- vsom_bmu_topk_batch for records with
+ * missing fields: the runner-up for the topographic error of a map trained on such records, and an imputation blended
+ * from k units.  Standard and Median (D = J).  One call, one stream wait.
+ * Mask: exactly vsom_bmu_masked_batch's -- valid_host is (r1-r0) x J bytes, row-major, when one_mask == 0, and J bytes
+ * applied to every row when one_mask != 0; a non-zero byte means valid; required.
+ * Distance: r_d = valid ? (m_d - x_d) : +0.0f as a select on the bits, d_i = r.dot(r) in the Eigen packet order of the exact
+ * tile: what a row or a model row holds at an invalid position (NaN, +-inf, 1e30) reaches no idx, dist, count or nvalid.
+ * Candidates: node 0 always (it seeds Som::findRestrictedBmu whatever its hits) and every node with bmuHits >= min_hits;
+ * bit-identical model rows each appear, in index order.
+ * Order: the key (d_i, i) with NaN after +inf, so ties go to the lower index, and vsom_bmu_topk_batch's node-0 rule: when
+ * d_0 is NaN, node 0 is entry 0 and the others follow in key order.  Entry 0 is therefore, bit for bit, the (bmu, dist) of
+ * vsom_bmu_masked_batch for the same min_hits and mask.  A NaN distance is stored as 0x7FC00000.  With an all-valid mask
+ * and min_hits = 0, idx and dist are bit-identical to vsom_bmu_topk_batch's.
+ * Padding: a row with fewer than k candidates has count < k, and idx = UINT64_MAX, dist = 0x7FC00000 from entry count on
+ * (k itself is only checked against N).  A row without a valid column has every distance +0: its list is the first count
+ * candidates in index order and nvalid is 0.
+ * Outputs (host pointers; entry r - r0 belongs to row r):
+ *   idx[(r1-r0)*k]     row-major, required
+ *   dist[(r1-r0)*k]    d of each idx entry, bit for bit (may be NULL)
+ *   count[r1-r0]       real entries of the row: min(k, candidates) (may be NULL)
+ *   nvalid[r1-r0]      valid columns of the row, as vsom_bmu_masked_batch (may be NULL)
+ *   blend[(r1-r0)*J]   the record imputed from the k units, weighted as the BMD weights units (may be NULL).  In double,
+ *                      one rounding per operation, nothing contracted: for the real entries j in list order
+ *                      a_j = (double)d_j * (double)d_j; t = the a of the first entry whose distance is not NaN; the row has
+ *                      mass iff that entry exists and its distance is finite; q_j = exp(-(a_j - t) / 2) for a finite d_j and
+ *                      0 for a NaN or +inf one; terms with q_j == 0 are skipped, not multiplied;
+ *                      Q = ((0 + q_0) + q_1) + ..., num_d = ((0 + q_0 * (double)m[0][d]) + q_1 * (double)m[1][d]) + ...
+ *                      A valid column is (double)x of the staged row, by select (a NaN stays, the model does not matter);
+ *                      an invalid one is num_d / Q, and the quiet NaN 0x7FF8000000000000 where the row has no mass.  exp
+ *                      runs on the device (within an ulp of libm's), as vsom_bmd_batch's.  blend reads map only.
+ * Read-only: map, sigmaMap, S, weightMap, bmuHits, lastBMU, sqres and the chunk are untouched; a pending sigmaMap stays
+ * pending.  Refuses (VSOM_ERR_INVALID, nothing enqueued, the context stays usable): a null context, out, out->idx or
+ * valid_host, custom and CLR contexts (the CLR residual runs over column pairs), no chunk, a chunk staged ahead, r0 > r1
+ * or r1 > B, k = 0, k > 64, k > N.  An empty range returns VSOM_OK and enqueues nothing.  Device scratch, in the query
+ * arena: the rows are taken in slices of at most the smallest of vsom_bmu_topk_batch's 64 MiB / (512 k) rows,
+ * vsom_bmu_masked_batch's 64 MiB rule for the validity bytes (VSOM_MASKED_SLICE_ROWS, read at every call, caps it) and,
+ * with blend, 64 MiB / (8 J) rows -- one row where a single row needs more.  Tile and merge are timed under VSOM_T_BMU,
+ * the blend under VSOM_T_FINISH. */
+typedef struct vsom_topk_masked_out {
+    uint64_t *idx;
+    float *dist;
+    uint32_t *count;
+    uint32_t *nvalid;
+    double *blend;
+} vsom_topk_masked_out;
+int vsom_bmu_topk_masked_batch(vsom_ctx *ctx, uint32_t k, uint64_t min_hits, size_t r0, size_t r1,
+                               const uint8_t *valid_host, int one_mask, vsom_topk_masked_out *out);
 /* Som::euclidianWeightedDistRaw(pos, v, ones, ones) (Som.cpp:143-157) for `count` pairs; v is
  * chunk row vrows[i] (from_map = 0) or model vector vrows[i] (from_map = 1, the U-matrix case). */
 int vsom_distances_raw(vsom_ctx *ctx, const uint64_t *nodes_host, const uint64_t *vrows_host,

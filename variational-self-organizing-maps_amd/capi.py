@@ -60,6 +60,7 @@ SYMBOLS = [
     "vsom_bmd_masked_batch", "vsom_generate_masked_batch",
     "vsom_set_column_weights", "vsom_set_chunk_validity", "vsom_find_bmu_valid", "vsom_find_local_bmu_valid",
     "vsom_dist_single_valid", "vsom_train_single_valid",
+    "vsom_bmu_topk_masked_batch",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -91,6 +92,12 @@ class SimilarityMaskedOut(C.Structure):
 class EvaluateMaskedOut(C.Structure):
     """vsom_evaluate_masked_out: vsom_evaluate_out's fields and nvalid; host pointers, each may be NULL"""
     _fields_ = EvaluateOut._fields_ + [("nvalid", C.POINTER(C.c_uint32))]
+
+
+class TopkMaskedOut(C.Structure):
+    """vsom_topk_masked_out: host pointers; idx is required, the others may be NULL"""
+    _fields_ = [("idx", C.POINTER(C.c_uint64)), ("dist", C.POINTER(C.c_float)), ("count", C.POINTER(C.c_uint32)),
+                ("nvalid", C.POINTER(C.c_uint32)), ("blend", C.POINTER(C.c_double))]
 
 
 class GenerateOut(C.Structure):
@@ -308,6 +315,9 @@ def lib():
         L.vsom_find_local_bmu_valid.argtypes = [vp, fp, u8p, C.c_uint64, u64p, fp]
         L.vsom_dist_single_valid.argtypes = [vp, fp, u8p, C.c_uint64, fp]
         L.vsom_train_single_valid.argtypes = [vp, fp, u8p, C.c_double, C.c_double, u64p, C.c_int, fp, fp, u64p]
+    if hasattr(L, "vsom_bmu_topk_masked_batch"):        # (VSOM_LIB may name an older build: tools/topk_masked_bench.py --lib)
+        L.vsom_bmu_topk_masked_batch.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8),
+                                                 C.c_int, C.POINTER(TopkMaskedOut)]
     _lib = L
     return L
 
@@ -817,6 +827,37 @@ class Context:
                 setattr(out, name, res[name].ctypes.data_as(ctype))
         check(lib().vsom_bmu_masked_batch(self._h, int(min_hits), r0, r1, vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one),
                                           C.byref(out)))
+        return res
+
+    def bmu_topk_masked(self, k, valid, r0=0, r1=None, min_hits=0, dist=True, blend=False):
+        """The k best matching units of chunk rows [r0, r1) over their valid columns only (vsom_bmu_topk_masked_batch;
+        Standard / Median): bmu_topk on bmu_masked's distance, over findRestrictedBmu's candidates (node 0, and the nodes
+        with at least min_hits hits).  valid: rows x J (nonzero = valid), or a 1-D column mask of J entries applied to every
+        row.  A dict of arrays: idx (uint64[n, k]; entry 0 is bmu_masked's unit), dist (float32[n, k], None unless dist),
+        count (uint32[n]: the real entries of the row -- a row with fewer than k candidates is padded with idx = NO_UNIT,
+        dist = NaN), nvalid (uint32[n]) and blend (float64[n, J]: x where valid, elsewhere the k units' values weighted as
+        the BMD weights units; None unless blend).  Read-only."""
+        k = int(k)
+        B = self.chunk_size
+        r0 = int(r0)
+        r1 = B if r1 is None else int(r1)
+        if not 1 <= k <= min(64, self.n_nodes):
+            raise ValueError(f"k = {k} is not in [1, min(64, N = {self.n_nodes})]")
+        if int(min_hits) < 0:
+            raise ValueError("min_hits must be >= 0")
+        if r0 < 0 or r0 > r1 or r1 > B:
+            raise ValueError(f"row range [{r0}, {r1}) is not within the chunk's {B} rows")
+        n = r1 - r0
+        vb, one = self._mask_bytes(valid, n)
+        res = {"idx": np.empty((n, k), np.uint64), "dist": np.empty((n, k), np.float32) if dist else None,
+               "count": np.empty(n, np.uint32), "nvalid": np.empty(n, np.uint32),
+               "blend": np.empty((n, self.in_len), np.float64) if blend else None}
+        out = TopkMaskedOut()
+        for name, ctype in TopkMaskedOut._fields_:
+            if res[name] is not None:
+                setattr(out, name, res[name].ctypes.data_as(ctype))
+        check(lib().vsom_bmu_topk_masked_batch(self._h, k, int(min_hits), r0, r1, vb.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                               int(one), C.byref(out)))
         return res
 
     def _mask_bytes(self, valid, n):

@@ -1037,6 +1037,20 @@ int vsom_generate_masked_batch(vsom_ctx *c, uint64_t min_hits, size_t r0, size_t
     return launch_generate_masked(c, min_hits, r0, r1, valid_host, one_mask, draws, keep_observed, u_host, l_host, out);
 }
 
+// Reads the map only: a pending sigmaMap stays pending.
+int vsom_bmu_topk_masked_batch(vsom_ctx *c, uint32_t k, uint64_t min_hits, size_t r0, size_t r1, const uint8_t *valid_host,
+                               int one_mask, vsom_topk_masked_out *out)
+{
+    CHECK_CTX_KEEP(c);
+    if (int rc = vsom_masked_score_gate(c, "vsom_bmu_topk_masked_batch", r0, r1, valid_host, out))
+        return rc;
+    if (!out->idx)
+        return vsom_fail(VSOM_ERR_INVALID, "out->idx is null");
+    if (k == 0 || k > 64 || k > c->N)
+        return vsom_fail(VSOM_ERR_INVALID, "k must be in [1, min(64, N)]");
+    return launch_topk_masked(c, k, min_hits, r0, r1, valid_host, one_mask, out);
+}
+
 int vsom_distances_row(vsom_ctx *c, size_t row, float *dist_out_host)
 {
     CHECK_CTX(c);

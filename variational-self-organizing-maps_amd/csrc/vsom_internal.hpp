@@ -428,6 +428,10 @@ int launch_generate_masked(vsom_ctx *c, u64 min_hits, size_t r0, size_t r1, cons
                            int keep_observed, const double *u_host, const double *l_host, const vsom_generate_out *out);
 // vsom_topk.hip: the k best matching units of chunk rows [r0,r1) (arguments checked by vsom_bmu_topk_batch); synchronises
 int launch_topk(vsom_ctx *c, uint32_t k, size_t r0, size_t r1, uint64_t *idx_out, float *dist_out);
+// the same over the valid columns and findRestrictedBmu's candidates, with the blended imputation (arguments checked by
+// vsom_bmu_topk_masked_batch); synchronises
+int launch_topk_masked(vsom_ctx *c, uint32_t k, u64 min_hits, size_t r0, size_t r1, const uint8_t *valid_host, int one_mask,
+                       const vsom_topk_masked_out *out);
 // vsom_similarity.hip: search + scoring of chunk rows [r0,r1) (arguments checked by vsom_similarity_batch); synchronises
 int launch_similarity(vsom_ctx *c, u64 min_hits, int num_sigmas, int sigma_rule, size_t r0, size_t r1,
                       const uint8_t *valid_host, const vsom_similarity_out *out);

@@ -24,4 +24,5 @@ $CXX $FLAGS "$here/tests/host_accum_masked_test.cpp" -o "$here/host_accum_masked
 $CXX $FLAGS "$here/tests/host_online_masked_test.cpp" -o "$here/host_online_masked_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_masked_score_test.cpp" -o "$here/host_masked_score_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_bmd_masked_test.cpp" -o "$here/host_bmd_masked_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
+$CXX $FLAGS "$here/tests/host_topk_masked_test.cpp" -o "$here/host_topk_masked_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 echo "built $here/libsom_hip.so and host_api_test"

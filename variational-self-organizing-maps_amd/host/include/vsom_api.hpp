@@ -517,6 +517,21 @@ public:
     // (node n at row n / width, column n % width; an error when max(|d row|, |d column|) != 1, no wrap); the count is
     // summed in row order in double and divided by the row count (0 for no rows).  N >= 2.
     double topographicError(const DataSet *data) const;
+    // [MI355X build] extension: findBestMatchingUnits for records with missing fields (the data set's validity flags; one
+    // vsom_bmu_topk_masked_batch call, include/vsom_hip.h): the k best matching units of every row over its VALID columns
+    // only, among node 0 and the nodes with at least minBmuHits hits; entry 0 is findMaskedBmus' unit.  A row with fewer
+    // than k candidates is padded with UINT64_MAX (distance NaN); *count (if given) receives every row's real entries,
+    // *dist their distances.  1 <= k <= min(64, N).  Standard / Median on the device only.
+    std::vector<uint64_t> findBestMatchingUnitsMasked(const DataSet *data, size_t k, size_t minBmuHits,
+                                                      std::vector<float> *dist = nullptr,
+                                                      std::vector<uint32_t> *count = nullptr) const;
+    // [MI355X build] extension: topographicError over the rows of `data` that have a valid column and a second unit
+    // (findBestMatchingUnitsMasked with k = 2); 0 when there are none.  *rowsCounted (if given) receives their number.
+    double topographicErrorMasked(const DataSet *data, size_t minBmuHits, size_t *rowsCounted = nullptr) const;
+    // [MI355X build] extension: rows x sample length, row-major, in double: every row of `data` with its invalid columns
+    // filled from its k findBestMatchingUnitsMasked units, each weighted as the BMD weights it (the same call; NaN at the
+    // invalid columns of a row without mass) -- between impute (one unit) and generateRowsMasked (random).
+    std::vector<double> imputeBlend(const DataSet *data, size_t k, size_t minBmuHits) const;
     // [MI355X build] extension: the per-row report measureSimilarity computes and throws away, for every row of `data`
     // (one vsom_similarity_batch call, include/vsom_hip.h): the row's restricted BMU and its distance, dmax / first (what
     // the reference's running maximum needs), the anomaly score amax = the largest |x - m| / sM / numberOfSigmas over
@@ -702,6 +717,8 @@ private:
                     bool updateUMatrixAfterEpoch, bool resetBmu);
     bool evaluateOnDevice(const DataSet &data, EvaluateRows &r) const;   // false: a validity flag outside {0, 1}
     void maskedRows(const DataSet *data, size_t minBmuHits, uint64_t *bmu, float *dist, float *fill) const;
+    void topkMaskedRows(const char *what, const DataSet *data, size_t k, size_t minBmuHits, uint64_t *idx, float *dist,
+                        uint32_t *count, uint32_t *nvalid, double *blend) const;
     void refreshHost() const;
     void stageOne(const Eigen::VectorXf &v) const;
 };

@@ -2170,6 +2170,73 @@ double Som::topographicError(const DataSet *data) const
     return count / (double)n;
 }
 
+// upload, one vsom_bmu_topk_masked_batch call with the data set's validity flags (a Transformation::Device Som stays off it:
+// the call serves the built-in Standard / Median only)
+void Som::topkMaskedRows(const char *what, const DataSet *data, size_t k, size_t minBmuHits, uint64_t *idx, float *dist,
+                         uint32_t *count, uint32_t *nvalid, double *blend) const
+{
+    requireDevicePath(what);
+    if (transform.kind() == vsom::Custom)
+        throw std::runtime_error(std::string(what) + ": vsom_bmu_topk_masked_batch serves the built-in transformations only");
+    if (k == 0 || k > 64 || k > width * height)
+        throw std::invalid_argument(std::string(what) + ": k must be in [1, min(64, N)]");
+    const size_t n = data->size();
+    if (n == 0)
+        return;
+    const std::vector<uint8_t> valid = validity_bytes(*data, inLen);
+    joinGroup();
+    check(vsom_upload_chunk(ctx, data->contiguous(), n), "vsom_upload_chunk");
+    vsom_topk_masked_out out = {idx, dist, count, nvalid, blend};
+    check(vsom_bmu_topk_masked_batch(ctx, (uint32_t)k, minBmuHits, 0, n, valid.data(), 0, &out), "vsom_bmu_topk_masked_batch");
+}
+
+std::vector<uint64_t> Som::findBestMatchingUnitsMasked(const DataSet *data, size_t k, size_t minBmuHits, std::vector<float> *dist,
+                                                       std::vector<uint32_t> *count) const
+{
+    const size_t n = data->size();
+    std::vector<uint64_t> idx(k <= 64 ? n * k : 0);     // (a k out of range throws below)
+    if (dist)
+        dist->assign(idx.size(), 0.0f);
+    if (count)
+        count->assign(n, 0);
+    topkMaskedRows("findBestMatchingUnitsMasked", data, k, minBmuHits, idx.data(), dist ? dist->data() : nullptr,
+                   count ? count->data() : nullptr, nullptr, nullptr);
+    return idx;
+}
+
+double Som::topographicErrorMasked(const DataSet *data, size_t minBmuHits, size_t *rowsCounted) const
+{
+    if (width * height < 2)
+        throw std::invalid_argument("topographicErrorMasked: the map needs at least 2 nodes");
+    const size_t n = data->size();
+    std::vector<uint64_t> idx(n * 2);
+    std::vector<uint32_t> count(n, 0), nvalid(n, 0);
+    topkMaskedRows("topographicErrorMasked", data, 2, minBmuHits, idx.data(), nullptr, count.data(), nvalid.data(), nullptr);
+    const long long w = (long long)width;
+    double errors = 0.0;
+    size_t rows = 0;
+    for (size_t r = 0; r < n; ++r) {
+        if (nvalid[r] < 1 || count[r] < 2)
+            continue;
+        const long long a = (long long)idx[2 * r], b = (long long)idx[2 * r + 1];
+        const long long dr = std::llabs(a / w - b / w), dc = std::llabs(a % w - b % w);
+        errors += (dr > dc ? dr : dc) != 1 ? 1.0 : 0.0;
+        ++rows;
+    }
+    if (rowsCounted)
+        *rowsCounted = rows;
+    return rows ? errors / (double)rows : 0.0;
+}
+
+std::vector<double> Som::imputeBlend(const DataSet *data, size_t k, size_t minBmuHits) const
+{
+    const size_t n = data->size();
+    std::vector<uint64_t> idx(k <= 64 ? n * k : 0);     // (a k out of range throws below)
+    std::vector<double> blend(n * inLen, 0.0);
+    topkMaskedRows("imputeBlend", data, k, minBmuHits, idx.data(), nullptr, nullptr, nullptr, blend.data());
+    return blend;
+}
+
 Som::GeneratedRows Som::generateRows(const DataSet &data, size_t minBmuHits, const std::vector<double> &u,
                                      const std::vector<double> &l, bool perRow) const
 {

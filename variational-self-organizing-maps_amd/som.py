@@ -635,6 +635,41 @@ class Som:
             raise ValueError("the topographic error needs a map of at least 2 nodes")
         return topographic_error(self.findBestMatchingUnits(data, 2), self.width)
 
+    # ---- the same over the valid columns only (extensions) ---------------------------------------
+    def _topk_masked(self, data, k, minBmuHits, dist, blend):
+        X = self._rows(data)
+        self.ctx.upload_chunk(X)
+        n, k, J = X.shape[0], int(k), self.ctx.in_len
+        if n == 0:
+            return {"idx": np.zeros((0, k), np.uint64), "dist": np.zeros((0, k), np.float32) if dist else None,
+                    "count": np.zeros(0, np.uint32), "nvalid": np.zeros(0, np.uint32),
+                    "blend": np.zeros((0, J), np.float64) if blend else None}
+        return self.ctx.bmu_topk_masked(k, self._validity(data), min_hits=minBmuHits, dist=dist, blend=blend)
+
+    def findBestMatchingUnitsMasked(self, data, k, minBmuHits=0, dist=False):
+        """extension: findBestMatchingUnits for records with missing fields (capi.Context.bmu_topk_masked): the k best
+        matching units of every loaded row of `data` over its valid columns only, among node 0 and the nodes with at least
+        minBmuHits hits.  {"idx": uint64[rows, k] (entry 0 is findBmuMasked's unit; a row with fewer than k candidates is
+        padded with capi.NO_UNIT), "count": uint32[rows] (the real entries), "nvalid": uint32[rows]} and, with dist=True,
+        "dist": float32[rows, k].  Validity as in findBmuMasked."""
+        rep = self._topk_masked(data, k, minBmuHits, dist, False)
+        return {key: rep[key] for key in ("idx", "count", "nvalid") + (("dist",) if dist else ())}
+
+    def topographicErrorMasked(self, data, minBmuHits=0):
+        """extension: topographicError for records with missing fields: (error, rows_counted) -- topographic_error over the
+        rows that have a valid column and a second unit (nvalid >= 1 and count >= 2), 0.0 when there are none"""
+        if self.width * self.height < 2:
+            raise ValueError("the topographic error needs a map of at least 2 nodes")
+        rep = self._topk_masked(data, 2, minBmuHits, False, False)
+        keep = (rep["nvalid"] >= 1) & (rep["count"] >= 2)
+        return topographic_error(rep["idx"][keep], self.width), int(keep.sum())
+
+    def imputeBlend(self, data, k, minBmuHits=0):
+        """extension: float64[rows, J], every loaded row of `data` with its invalid columns filled from its k best matching
+        units over the valid ones, each weighted as the BMD weights it (exp(-d^2 / 2), relative to the best) -- between
+        impute (one unit) and imputeSampled (random).  A row without mass holds NaN at its invalid columns."""
+        return self._topk_masked(data, k, minBmuHits, False, True)["blend"]
+
     # ---- batch training (Som.cpp:716-879) --------------------------------------------------
     def trainBatchSomEpoch(self, dataset, currentSigma, isFirst):
         self._chunkToDevice(dataset)
