@@ -847,6 +847,23 @@ int vsom_get_mse(vsom_ctx *ctx, float *mse_out);
  * no chunk loaded, the next chunk staged ahead over the current chunk's rows (custom contexts included). */
 #define VSOM_SCHEDULE_MAX_EPOCHS 1024
 int vsom_batch_schedule(vsom_ctx *ctx, const double *sigma, size_t epochs, int reset_bmu, float *mse_out /*[epochs]*/);
+/* vsom_batch_schedule over the VALID entries of the chunk only: bit for bit the loop above with
+ *     vsom_batch_epoch_masked(ctx, sigma[ep], ep == 0, valid_host, one_mask, &mse_out[ep])
+ * in place of batch_epoch -- map, sigmaMap, weightMap, bmuHits, lastBMU, sqres, every MSE, the MSE word and the context's
+ * bookkeeping; S is untouched.  The same validity (valid_host / one_mask as in vsom_batch_epoch_masked) applies to every
+ * epoch; it is copied to the device once per call and not read after the call returns.  Where
+ * vsom_masked_tiny_applies(ctx, one_mask) holds and every sigma is finite, one launch of the one-workgroup masked kernel
+ * runs up to VSOM_SCHEDULE_MAX_EPOCHS epochs (longer schedules: successive launches); every other context runs the loop
+ * inside the library.  epochs = 0: nothing is done (VSOM_OK).  The call blocks.  Refuses (VSOM_ERR_INVALID, nothing
+ * enqueued, state untouched, the context stays usable) what vsom_batch_schedule refuses, a null valid_host, and what
+ * vsom_batch_epoch_masked refuses: custom and CLR contexts, an update mode other than VSOM_UPDATE_STRICT. */
+int vsom_batch_schedule_masked(vsom_ctx *ctx, const double *sigma, size_t epochs, int reset_bmu, const uint8_t *valid_host,
+                               int one_mask, float *mse_out /*[epochs]*/);
+/* 1: a masked schedule on the loaded chunk would take the one-workgroup masked kernel (finite sigmas given) -- the chunk
+ * and map are within the one-launch bounds of vsom_batch_epoch (not VSOM_NO_TINY=1), the context is Standard or Median,
+ * not custom, in the strict update mode, and the kernel's LDS need (per-row arrays, the rows when B J <= 10240, the
+ * neighbourhood table, J ceil(B/32) validity words -- J with one_mask) is within 64 KiB.  0 otherwise. */
+int vsom_masked_tiny_applies(const vsom_ctx *ctx, int one_mask);
 
 /* ---- online path -----------------------------------------------------------------------
  * Som::trainSingle (Som.cpp:885-947) on one host vector; residual_out has
@@ -949,6 +966,21 @@ int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_firs
  * or mse_out[k], no chunk loaded, the next chunk staged ahead over its rows. */
 int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma /*[K][epochs[k]]*/, const size_t *epochs /*[K]*/,
                                  int reset_bmu, float *const *mse_out /*[K][epochs[k]]*/);
+/* The two calls above for members whose rows have missing fields.  valid_host[k] is member k's
+ * validity (B_k x J_k bytes, or J_k bytes when one_mask[k] != 0; one_mask NULL: all 0) or NULL for a PLAIN member.  Per
+ * member, bit for bit: vsom_batch_epoch_masked / vsom_batch_schedule_masked with valid_host[k], one_mask[k] for a masked
+ * member, vsom_batch_epoch / vsom_batch_schedule for a plain one (any kind of context).  Masked members for which
+ * vsom_masked_tiny_applies holds (and, in the schedule form, whose sigmas are finite) run as one launch per kind, one
+ * workgroup per member; their validity bytes are gathered into one pinned image and copied to the device once per launch.
+ * Every other member runs its single call in the same call.  valid_host is not read after the call returns.  mse_out of
+ * the epoch form may be NULL; a member with epochs[k] = 0 is not touched.  Refuses (VSOM_ERR_INVALID, naming the member,
+ * before anything is enqueued for any member): what the unmasked forms refuse, a null valid_host array, and for a masked
+ * member a custom or CLR context or an update mode other than VSOM_UPDATE_STRICT. */
+int vsom_ensemble_batch_epoch_masked(vsom_ensemble *e, const double *sigma, int is_first,
+                                     const uint8_t *const *valid_host /*[K]*/, const int *one_mask /*[K], NULL: all 0*/,
+                                     float *mse_out);
+int vsom_ensemble_batch_schedule_masked(vsom_ensemble *e, const double *const *sigma, const size_t *epochs, int reset_bmu,
+                                        const uint8_t *const *valid_host, const int *one_mask, float *const *mse_out);
 /* Every member's chunk from ONE host buffer.  Member k gets B[k] rows of its own row length J_k (the length
  * vsom_upload_chunk reads for that member), contiguous at x_host + offset[k] (offsets in floats).  Several members may
  * name the same rows (equal offsets: a sweep over one data set).  n_floats = the extent of x_host.  Afterwards every call

@@ -61,6 +61,8 @@ SYMBOLS = [
     "vsom_set_column_weights", "vsom_set_chunk_validity", "vsom_find_bmu_valid", "vsom_find_local_bmu_valid",
     "vsom_dist_single_valid", "vsom_train_single_valid",
     "vsom_bmu_topk_masked_batch",
+    "vsom_batch_schedule_masked", "vsom_ensemble_batch_epoch_masked", "vsom_ensemble_batch_schedule_masked",
+    "vsom_masked_tiny_applies",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -287,6 +289,13 @@ def lib():
     if hasattr(L, "vsom_batch_schedule"):
         L.vsom_batch_schedule.argtypes = [vp, dp, C.c_size_t, C.c_int, fp]
         L.vsom_ensemble_batch_schedule.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_size_t), C.c_int, C.POINTER(fp)]
+    if hasattr(L, "vsom_batch_schedule_masked"):        # (VSOM_LIB may name an older build: tools/tiny_masked_bench.py --lib)
+        u8p = C.POINTER(C.c_uint8)
+        L.vsom_batch_schedule_masked.argtypes = [vp, dp, C.c_size_t, C.c_int, u8p, C.c_int, fp]
+        L.vsom_ensemble_batch_epoch_masked.argtypes = [vp, dp, C.c_int, C.POINTER(u8p), C.POINTER(C.c_int), fp]
+        L.vsom_ensemble_batch_schedule_masked.argtypes = [vp, C.POINTER(dp), C.POINTER(C.c_size_t), C.c_int, C.POINTER(u8p),
+                                                          C.POINTER(C.c_int), C.POINTER(fp)]
+        L.vsom_masked_tiny_applies.argtypes = [vp, C.c_int]
     if hasattr(L, "vsom_batch_accum_begin"):    # (VSOM_LIB may name an older build: tools/accum_bench.py --lib)
         L.vsom_batch_accum_begin.argtypes = [vp, C.c_double, C.c_int, C.c_size_t]
         L.vsom_batch_accum_chunk.argtypes = [vp]
@@ -1071,6 +1080,32 @@ class Context:
                                         _f(mse)))
         return mse
 
+    def _validity(self, valid):
+        """valid as contiguous bytes and its one_mask flag; ValueError for a shape that is neither (J,) nor (B, J)"""
+        B = self.chunk_size
+        vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
+        one = vb.ndim == 1
+        if vb.shape != ((self.in_len,) if one else (B, self.in_len)):
+            raise ValueError(f"valid has shape {vb.shape}, neither ({self.in_len},) nor ({B}, {self.in_len})")
+        return vb, one
+
+    def batch_schedule_masked(self, sigmas, valid, reset_bmu=True):
+        """batch_schedule over the valid entries of the chunk only (vsom_batch_schedule_masked): bit for bit the loop of
+        batch_epoch_masked calls with the same validity in every epoch; one launch for a tiny map (masked_tiny_applies).
+        valid: B x J (nonzero = valid), or a 1-D column mask of J entries applied to every row; ValueError for another
+        shape, before any call into the library.  Returns every epoch's MSE [float32 array]."""
+        vb, one = self._validity(valid)
+        sg = _schedule(sigmas)
+        mse = np.zeros(sg.size, np.float32)
+        check(lib().vsom_batch_schedule_masked(self._h, sg.ctypes.data_as(C.POINTER(C.c_double)), sg.size,
+                                               int(bool(reset_bmu)), vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one),
+                                               _f(mse)))
+        return mse
+
+    def masked_tiny_applies(self, one_mask=False):
+        """would batch_schedule_masked on the loaded chunk take the one-workgroup masked kernel (finite sigmas given)?"""
+        return bool(lib().vsom_masked_tiny_applies(self._h, int(bool(one_mask))))
+
     def batch_accum_begin(self, sigma, is_first, total_rows):
         """Open a batch epoch over a data set that loads in several chunks (vsom_batch_accum_begin): total_rows is the sum
         of the rows of the chunks that batch_accum_chunk will be called on.  ValueError for a negative or non-integral
@@ -1094,11 +1129,7 @@ class Context:
         masked distance, and per column the carried chain over the rows valid at that column.  valid: B x J (nonzero =
         valid), or a 1-D column mask of J entries applied to every row; ValueError for another shape, before any call
         into the library.  The array is not read after the call returns (enqueues, does not block)."""
-        B = self.chunk_size
-        vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
-        one = vb.ndim == 1
-        if vb.shape != ((self.in_len,) if one else (B, self.in_len)):
-            raise ValueError(f"valid has shape {vb.shape}, neither ({self.in_len},) nor ({B}, {self.in_len})")
+        vb, one = self._validity(valid)
         check(lib().vsom_batch_accum_chunk_masked(self._h, vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one)))
 
     def batch_accum_end(self):
@@ -1115,11 +1146,7 @@ class Context:
         """One batch epoch over the valid entries of the chunk only (vsom_batch_epoch_masked; Standard / Median, strict
         update mode): the search on the masked distance, and per column the chain over the rows valid at that column.
         valid: B x J (nonzero = valid), or a 1-D column mask of J entries applied to every row.  Returns the MSE."""
-        B = self.chunk_size
-        vb = np.ascontiguousarray(np.asarray(valid) != 0, dtype=np.uint8)
-        one = vb.ndim == 1
-        if vb.shape != ((self.in_len,) if one else (B, self.in_len)):
-            raise ValueError(f"valid has shape {vb.shape}, neither ({self.in_len},) nor ({B}, {self.in_len})")
+        vb, one = self._validity(valid)
         mse = C.c_float()
         check(lib().vsom_batch_epoch_masked(self._h, float(sigma), int(bool(is_first)),
                                             vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one), C.byref(mse)))
@@ -1418,6 +1445,49 @@ class Ensemble:
         out = (C.POINTER(C.c_float) * max(n, 1))(*[_f(m) for m in mses])
         cnt = (C.c_size_t * max(n, 1))(*[sg.size for sg in per])
         check(lib().vsom_ensemble_batch_schedule(self._h, sig, cnt, int(bool(reset_bmu)), out))
+        return mses
+
+    def _validities(self, valid):
+        """valid (one entry per member: None for a plain member, else that member's B x J or 1-D J validity) as the
+        arrays, the pointer array and the one_mask array of the masked calls; ValueError before any call into the library"""
+        n = len(self.members)
+        if isinstance(valid, np.ndarray) or not hasattr(valid, "__len__") or len(valid) != n:
+            raise ValueError(f"valid must be a list of one entry per member ({n}), None for a plain member")
+        keep = [None if v is None else c._validity(v) for c, v in zip(self.members, valid)]
+        u8p = C.POINTER(C.c_uint8)
+        ptrs = (u8p * max(n, 1))(*[u8p() if kv is None else kv[0].ctypes.data_as(u8p) for kv in keep])
+        ones = (C.c_int * max(n, 1))(*[0 if kv is None else int(kv[1]) for kv in keep])
+        return keep, ptrs, ones
+
+    def batch_epoch_masked(self, sigma, is_first, valid):
+        """one batch epoch on every member, over the valid entries only for the members with a validity
+        (vsom_ensemble_batch_epoch_masked).  valid: a list with one entry per member -- None (a plain member: batch_epoch),
+        a B x J array, or a 1-D column mask of J entries.  Returns the MSE per member [float32 array]."""
+        keep, ptrs, ones = self._validities(valid)
+        mse = np.zeros(len(self.members), np.float32)
+        check(lib().vsom_ensemble_batch_epoch_masked(self._h, self._per_member(sigma, C.c_double, float),
+                                                     int(bool(is_first)), ptrs, ones, _f(mse)))
+        del keep
+        return mse
+
+    def batch_schedule_masked(self, sigmas, valid, reset_bmu=True):
+        """batch_schedule with each member's validity (vsom_ensemble_batch_schedule_masked); sigmas as in batch_schedule,
+        valid as in batch_epoch_masked.  Returns each member's per-epoch MSE [list of float32 arrays]."""
+        n = len(self.members)
+        keep, ptrs, ones = self._validities(valid)
+        if _is_nested(sigmas):
+            per = [_schedule(v) for v in sigmas]
+            if len(per) != n:
+                raise ValueError(f"{len(per)} schedules for {n} members")
+        else:
+            per = [_schedule(sigmas)] * n
+        mses = [np.zeros(sg.size, np.float32) for sg in per]
+        dp = C.POINTER(C.c_double)
+        sig = (dp * max(n, 1))(*[sg.ctypes.data_as(dp) for sg in per])
+        out = (C.POINTER(C.c_float) * max(n, 1))(*[_f(m) for m in mses])
+        cnt = (C.c_size_t * max(n, 1))(*[sg.size for sg in per])
+        check(lib().vsom_ensemble_batch_schedule_masked(self._h, sig, cnt, int(bool(reset_bmu)), ptrs, ones, out))
+        del keep
         return mses
 
     def upload_chunks(self, rows):

@@ -29,6 +29,10 @@ struct vsom_ensemble {
     struct Slot {
         PinnedBuf<unsigned char> host;       // descriptors staged here, copied to dev
         DevBuf<unsigned char> dev;
+        // the masked train calls: the launch's tables, table offsets and the launched members' validity bytes, one image
+        // copied once on the launch stream; reused under the same event as the descriptors
+        PinnedBuf<unsigned char> img_host;
+        DevBuf<unsigned char> img_dev;
         hipEvent_t ev = nullptr;
         bool valid = false;
     } slot[2];
@@ -521,6 +525,181 @@ int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma, c
         if (kind[k] >= 0)
             vsom_schedule_results(e->m[k], epochs[k], mse_out[k]);
     return VSOM_OK;
+}
+
+// The masked train calls.  Both forms are one routine: an epoch is a schedule of one epoch whose
+// `first` is the call's is_first.  Masked members on the fast path of vsom_batch_schedule_masked go as rounds of at most
+// VSOM_SCHEDULE_MAX_EPOCHS epochs, one launch per kind and round; per round the tables (one per distinct (shape, sigma)),
+// every member's table offsets and the members' validity bytes form one pinned image in the round's descriptor slot,
+// copied once on the launch stream.  Every other member -- a plain one (valid_host[k] null), a masked one off the fast
+// path -- runs single(k), its single-context call, in the same call.
+template <typename Single>
+static int ens_masked_train(vsom_ensemble *e, const double *const *sigma, const size_t *epochs, int first, int reset_bmu,
+                            const uint8_t *const *valid_host, const int *one_mask, float *const *mse_out, Single single)
+{
+    const size_t n = e->m.size();
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    EnsCall call(e);
+    if (int rc = join_members(e, epochs, true))   // (a member without epochs is not touched)
+        return rc;
+    const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);
+    std::vector<int> kind(n, -1);
+    std::vector<size_t> vbytes(n, 0);
+    size_t longest = 0;
+    bool any = false;
+    for (size_t k = 0; k < n; ++k) {
+        vsom_ctx *c = e->m[k];
+        const int one = one_mask ? one_mask[k] : 0;
+        if (!epochs[k] || !valid_host[k] || !vsom_tiny_masked_schedule_applies(c, one, sigma[k], epochs[k], lds_cap))
+            continue;
+        kind[k] = c->transform;
+        vbytes[k] = (one ? 1 : c->B) * (size_t)c->J;
+        longest = std::max(longest, epochs[k]);
+        any = true;
+    }
+    int rc = VSOM_OK;
+    if (any) {
+        for (size_t k = 0; k < n; ++k)
+            if (kind[k] >= 0)
+                VSOM_ALLOC_CHECK(vsom_grow(e->m[k]->sch_mse, epochs[k], e->m[k]->stream, VSOM_BUF_SYNC));
+        const size_t stride = vsom_tiny_masked_sched_desc_bytes();
+        std::vector<size_t> tab_at(n, 0), v_at(n, 0);
+        std::vector<unsigned> tab;
+        for (size_t e0 = 0; e0 < longest && !rc; e0 += VSOM_SCHEDULE_MAX_EPOCHS) {
+            VsomSchedTables tabs;
+            tab.clear();
+            size_t vtotal = 0;
+            for (size_t k = 0; k < n; ++k) {
+                if (kind[k] < 0 || epochs[k] <= e0)
+                    continue;
+                uint32_t lw, lh;
+                vsom_lut_dims(e->m[k], &lw, &lh);
+                tab_at[k] = tab.size();
+                const size_t cnt = std::min(epochs[k] - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS);
+                for (size_t ep = 0; ep < cnt; ++ep)
+                    tab.push_back((unsigned)tabs.add(lw, lh, sigma[k][e0 + ep]));
+                v_at[k] = vtotal;
+                vtotal += vbytes[k];
+            }
+            if (tabs.floats > 0xFFFFFFFFull) {
+                rc = vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: the tables of one round exceed 2^32 values");
+                break;
+            }
+            // (a member whose schedule has ended stays in the launches with no epochs: every round then has the same
+            //  launch stream, and the rounds stay ordered)
+            ens_scratch(e, stride);
+            for (size_t k = 0; k < n; ++k)
+                if (kind[k] >= 0)
+                    e->grp[k] = kind[k];
+            if (int jrc = call.join(ENS_LAUNCHED))
+                return jrc;
+            // the slot ens_launch is about to take: its last launch has completed, so its image may be rewritten
+            auto &s = e->slot[e->next];
+            if (s.valid)
+                VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
+            const size_t tbytes = (tabs.floats + tab.size()) * sizeof(float), bytes = tbytes + vtotal;
+            VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(s.img_host, bytes), vsom_member(s.img_dev, bytes)}));
+            tabs.tabulate(reinterpret_cast<float *>(s.img_host.p));
+            std::memcpy(s.img_host.p + tabs.floats * sizeof(float), tab.data(), tab.size() * sizeof(unsigned));
+            for (size_t k = 0; k < n; ++k)
+                if (kind[k] >= 0 && epochs[k] > e0)
+                    std::memcpy(s.img_host.p + tbytes + v_at[k], valid_host[k], vbytes[k]);
+            VSOM_HIP_CHECK(hipMemcpyAsync(s.img_dev.p, s.img_host.p, bytes, hipMemcpyHostToDevice, call.ls));
+            const float *lut_dev = reinterpret_cast<const float *>(s.img_dev.p);
+            const unsigned *tab_dev = reinterpret_cast<const unsigned *>(s.img_dev.p + tabs.floats * sizeof(float));
+            for (size_t k = 0; k < n; ++k) {
+                if (kind[k] < 0)
+                    continue;
+                vsom_ctx *c = e->m[k];
+                const size_t cnt = epochs[k] > e0 ? std::min(epochs[k] - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS) : 0;
+                vsom_tiny_masked_sched_fill(c, s.img_dev.p + tbytes + (cnt ? v_at[k] : 0), one_mask ? one_mask[k] : 0, lds_cap,
+                                            lut_dev, tab_dev + (cnt ? tab_at[k] : 0), c->sch_mse.p + (cnt ? e0 : 0), cnt,
+                                            e0 == 0 && first, reset_bmu, e->desc.data() + k * stride, &e->smem[k]);
+            }
+            rc = ens_launch(call, ENS_JOINED, VSOM_TINY_GROUPS, stride, ENS_NO_CAP, ens_always_ready,
+                            [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t st) {
+                                return vsom_tiny_masked_sched_launch_many(g, d, cnt, smem, st);
+                            });
+        }
+    }
+    // the other members through their single calls, while the launches run
+    for (size_t k = 0; k < n && !rc; ++k)
+        if (kind[k] < 0 && epochs[k])
+            rc = single(k);
+    if ((rc = call.end(rc)))
+        return rc;
+    for (size_t k = 0; k < n; ++k)
+        if (kind[k] >= 0)
+            vsom_schedule_results(e->m[k], epochs[k], mse_out[k]);
+    return VSOM_OK;
+}
+
+// what both masked forms refuse for member k (its chunk, and for a masked member its kind), or null
+static const char *ens_masked_refusal(const vsom_ctx *c, const uint8_t *valid)
+{
+    if (const char *why = vsom_schedule_refusal(c))
+        return why;
+    return valid ? vsom_masked_train_refusal(c) : nullptr;
+}
+
+int vsom_ensemble_batch_epoch_masked(vsom_ensemble *e, const double *sigma, int is_first, const uint8_t *const *valid_host,
+                                     const int *one_mask, float *mse_out)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    if (!sigma)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null parameter array");
+    if (!valid_host)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null valid_host array");
+    const size_t n = e->m.size();
+    for (size_t k = 0; k < n; ++k)
+        if (const char *why = ens_masked_refusal(e->m[k], valid_host[k]))
+            return ens_fail(k, why);
+    // every member a schedule of one epoch; the MSEs land in a local array (mse_out may be null)
+    std::vector<const double *> sig(n);
+    std::vector<size_t> epochs(n, 1);
+    std::vector<float> mse(n, 0.f);
+    std::vector<float *> msep(n);
+    for (size_t k = 0; k < n; ++k) {
+        sig[k] = sigma + k;
+        msep[k] = &mse[k];
+    }
+    const int rc = ens_masked_train(e, sig.data(), epochs.data(), is_first ? 1 : 0, 0, valid_host, one_mask, msep.data(),
+                                    [&](size_t k) {
+                                        return valid_host[k] ? vsom_batch_epoch_masked(e->m[k], sigma[k], is_first, valid_host[k],
+                                                                                       one_mask ? one_mask[k] : 0, msep[k])
+                                                             : vsom_batch_epoch(e->m[k], sigma[k], is_first, msep[k]);
+                                    });
+    if (rc)
+        return rc;
+    if (mse_out)
+        std::copy(mse.begin(), mse.end(), mse_out);
+    return VSOM_OK;
+}
+
+int vsom_ensemble_batch_schedule_masked(vsom_ensemble *e, const double *const *sigma, const size_t *epochs, int reset_bmu,
+                                        const uint8_t *const *valid_host, const int *one_mask, float *const *mse_out)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    if (!epochs)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null epochs array");
+    if (!valid_host)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null valid_host array");
+    const size_t n = e->m.size();
+    for (size_t k = 0; k < n; ++k) {
+        if (!epochs[k])
+            continue;                        // not touched
+        if (!sigma || !mse_out || !sigma[k] || !mse_out[k])
+            return ens_fail(k, "null sigma or mse_out with epochs > 0");
+        if (const char *why = ens_masked_refusal(e->m[k], valid_host[k]))
+            return ens_fail(k, why);
+    }
+    return ens_masked_train(e, sigma, epochs, 1, reset_bmu, valid_host, one_mask, mse_out, [&](size_t k) {
+        return valid_host[k] ? vsom_batch_schedule_masked(e->m[k], sigma[k], epochs[k], reset_bmu, valid_host[k],
+                                                          one_mask ? one_mask[k] : 0, mse_out[k])
+                             : vsom_batch_schedule(e->m[k], sigma[k], epochs[k], reset_bmu, mse_out[k]);
+    });
 }
 
 // ================================================================================================================

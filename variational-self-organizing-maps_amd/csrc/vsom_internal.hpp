@@ -594,6 +594,21 @@ int vsom_schedule_loop(vsom_ctx *c, const double *sigma, size_t epochs, int rese
 // after the wait behind the launches: sch_mse[0 .. epochs) into mse_out, the last one into the word vsom_get_mse reads
 void vsom_schedule_results(vsom_ctx *c, size_t epochs, float *mse_out);
 
+// the same over the valid entries only (vsom_batch_schedule_masked, vsom_ensemble_batch_*_masked; vsom_tiny_masked.hip,
+// DESIGN.md section 4t).  A single epoch is a schedule of one epoch whose `first` is the call's is_first.
+// why a masked call refuses this context whatever its chunk (custom, CLR, a non-strict update mode), or null
+const char *vsom_masked_train_refusal(const vsom_ctx *c);
+// the one-workgroup masked kernel applies: vsom_tiny_applies, Standard / Median, not custom, strict, LDS need <= lds_limit
+bool vsom_tiny_masked_applies(const vsom_ctx *c, int one_mask, size_t lds_limit);
+// ... and every sigma is finite
+bool vsom_tiny_masked_schedule_applies(const vsom_ctx *c, int one_mask, const double *sigma, size_t epochs, size_t lds_limit);
+size_t vsom_tiny_masked_sched_desc_bytes();
+// as vsom_tiny_sched_fill; valid_dev: the validity bytes on the device (B x J, or J with one_mask)
+int vsom_tiny_masked_sched_fill(vsom_ctx *c, const unsigned char *valid_dev, int one_mask, size_t lds_limit, const float *lut_dev,
+                                const unsigned *tab_dev, float *mse, size_t epochs, int first, int reset_bmu, void *desc,
+                                size_t *smem);
+int vsom_tiny_masked_sched_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
+
 // custom-transformation contexts (vsom_custom.hip): the entry points that accept one route here, the others refuse it
 #define VSOM_CUSTOM_REFUSE(ctx, what)                                  \
     do {                                                               \

@@ -19,6 +19,7 @@ $CXX $FLAGS "$here/tests/host_evaluate_test.cpp" -o "$here/host_evaluate_test" -
 $CXX $FLAGS "$here/tests/host_generate_test.cpp" -o "$here/host_generate_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_masked_train_test.cpp" -o "$here/host_masked_train_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_schedule_test.cpp" -o "$here/host_schedule_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
+$CXX $FLAGS "$here/tests/host_resident_masked_test.cpp" -o "$here/host_resident_masked_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_accum_test.cpp" -o "$here/host_accum_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_accum_masked_test.cpp" -o "$here/host_accum_masked_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'
 $CXX $FLAGS "$here/tests/host_online_masked_test.cpp" -o "$here/host_online_masked_test" -L"$here" -lsom_hip -L"$here/.." -lvsom_hip -Wl,-rpath,'$ORIGIN' -Wl,-rpath,'$ORIGIN/..'

@@ -457,6 +457,10 @@ public:
     // state, the metrics and the rows' lastBMU are trainBatchSom's bit for bit.  Throws std::invalid_argument before it
     // trains when the first load does not read the whole stream.  One device only.
     void trainBatchSomResident(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay);
+    // [MI355X build] extension: trainBatchSomResident over the VALID entries of the rows only -- one
+    // vsom_batch_schedule_masked call with the chunk's validity flags.  The state, the metrics and the rows' lastBMU are
+    // trainBatchSomMasked's on the same one-chunk data set bit for bit; the same one-chunk rule.  Standard / Median.
+    void trainBatchSomResidentMasked(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay);
     // [MI355X build] extension: trainBatchSom's driver with ONE batch epoch per pass over the stream -- the chunks of a
     // pass accumulate into one epoch over all rows (vsom_batch_accum_begin / _chunk / _end, include/vsom_hip.h), where
     // trainBatchSom runs an epoch per chunk and ends a pass with the batch map of its last chunk alone.  The same sigma
@@ -715,6 +719,7 @@ private:
     void requireDevicePath(const char *what) const;
     void trainWhole(const char *what, bool masked, DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay,
                     bool updateUMatrixAfterEpoch, bool resetBmu);
+    void trainResident(bool masked, const char *name, DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay);
     bool evaluateOnDevice(const DataSet &data, EvaluateRows &r) const;   // false: a validity flag outside {0, 1}
     void maskedRows(const DataSet *data, size_t minBmuHits, uint64_t *bmu, float *dist, float *fill) const;
     void topkMaskedRows(const char *what, const DataSet *data, size_t k, size_t minBmuHits, uint64_t *idx, float *dist,

@@ -1391,10 +1391,21 @@ void Som::trainWhole(const char *what, bool masked, DataSet &data, size_t number
 // epoch (reset_bmu: each epoch's walk starts from unit 0, as after the reference's per-epoch reload, DataSet.cpp:136-137)
 void Som::trainBatchSomResident(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay)
 {
-    requireDevicePath("trainBatchSomResident");
+    trainResident(false, "trainBatchSomResident", data, numberOfEpochs, sigma0, sigmaDecay);
+}
+
+// the same over the valid entries only: one vsom_batch_schedule_masked call with the chunk's validity flags
+void Som::trainBatchSomResidentMasked(DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay)
+{
+    trainResident(true, "trainBatchSomResidentMasked", data, numberOfEpochs, sigma0, sigmaDecay);
+}
+
+void Som::trainResident(bool masked, const char *name, DataSet &data, size_t numberOfEpochs, double sigma0, double sigmaDecay)
+{
+    requireDevicePath(name);
     if (grp)
-        throw std::runtime_error("trainBatchSomResident: a multi-GPU Som has no resident schedule (vsom_batch_schedule "
-                                 "runs on one context)");
+        throw std::runtime_error(std::string(name) + ": a multi-GPU Som has no resident schedule (vsom_batch_schedule "
+                                                     "runs on one context)");
     {
         const std::lock_guard<std::mutex> lock(metricsMutex);   // (the reference resets without it: trainBatchSom)
         metrics = Som::Metrics(numberOfEpochs);
@@ -1411,13 +1422,22 @@ void Som::trainBatchSomResident(DataSet &data, size_t numberOfEpochs, double sig
     data.loadNextDataFromStream();
     if (!data.hasReadWholeDataStream()) {
         data.resetStreamLoadPosition();   // (a caller that falls back to trainBatchSom starts from a clean stream)
-        throw std::invalid_argument("trainBatchSomResident: the data set does not load as one chunk; use trainBatchSom");
+        throw std::invalid_argument(std::string(name) + ": the data set does not load as one chunk; use " +
+                                    (masked ? "trainBatchSomMasked" : "trainBatchSom"));
     }
     const size_t B = data.size();
     std::vector<float> mse(sigmas.size(), 0.f);
     std::vector<uint64_t> lb(B);
     check(vsom_upload_chunk(ctx, data.contiguous(), B), "vsom_upload_chunk");
-    check(vsom_batch_schedule(ctx, sigmas.data(), sigmas.size(), 1, mse.data()), "vsom_batch_schedule");
+    if (masked) {
+        std::vector<uint8_t> valid = validity_bytes(data, inLen);
+        if (valid.empty())
+            valid.assign(1, 0);       // (an empty chunk reads no flag; the call wants a pointer)
+        check(vsom_batch_schedule_masked(ctx, sigmas.data(), sigmas.size(), 1, valid.data(), 0, mse.data()),
+              "vsom_batch_schedule_masked");
+    } else {
+        check(vsom_batch_schedule(ctx, sigmas.data(), sigmas.size(), 1, mse.data()), "vsom_batch_schedule");
+    }
     check(vsom_get_last_bmu(ctx, lb.data()), "vsom_get_last_bmu");
     for (size_t s = 0; s < B; ++s)
         data.getLastBMU(s) = (size_t)lb[s];

@@ -882,6 +882,17 @@ class Som:
         schedule run by one call (capi.Context.batch_schedule) -- the same map, metrics and lastBMU as trainBatchSom,
         which reloads the chunk (lastBMU := 0) and calls the device once per epoch.  Raises ValueError before it trains
         when the first load does not read the whole stream."""
+        self._trainBatchSomResident(False, "trainBatchSomResident", data, numberOfEpochs, sigma0, sigmaDecay)
+
+    def trainBatchSomResidentMasked(self, data, numberOfEpochs, sigma0, sigmaDecay):
+        """extension: trainBatchSomResident over the valid entries of the rows only (capi.Context.batch_schedule_masked)
+        -- the same map, metrics and lastBMU as trainBatchSomMasked on the one-chunk data set.  The validity comes from
+        the data set when it has one (an attribute `validity`, loaded rows x J, nonzero = valid), as in
+        trainBatchSomEpochMasked; without one every column is valid.  The same one-chunk rule: ValueError before it
+        trains when the first load does not read the whole stream."""
+        self._trainBatchSomResident(True, "trainBatchSomResidentMasked", data, numberOfEpochs, sigma0, sigmaDecay)
+
+    def _trainBatchSomResident(self, masked, name, data, numberOfEpochs, sigma0, sigmaDecay):
         self.metrics = Metrics(numberOfEpochs)                    # :719
         sigmas = batch_sigma_schedule(numberOfEpochs, sigma0, sigmaDecay)
         if not sigmas:
@@ -889,9 +900,13 @@ class Som:
         data.loadNextDataFromStream()
         if not data.hasReadWholeDataStream():
             data.resetStreamLoadPosition()      # (a caller that falls back to trainBatchSom starts from a clean stream)
-            raise ValueError("trainBatchSomResident needs a data set that loads as one chunk; use trainBatchSom")
+            raise ValueError(f"{name} needs a data set that loads as one chunk; use "
+                             f"{'trainBatchSomMasked' if masked else 'trainBatchSom'}")
         self.ctx.upload_chunk(data.data)
-        mses = self.ctx.batch_schedule(sigmas, reset_bmu=True)
+        if masked:
+            mses = self.ctx.batch_schedule_masked(sigmas, self._chunkValidity(data), reset_bmu=True)
+        else:
+            mses = self.ctx.batch_schedule(sigmas, reset_bmu=True)
         for i, mse in enumerate(mses):
             self.metrics.MeanSquaredError[i] = np.float32(np.float32(np.float32(0.0) + mse) / np.float32(1))   # :743
         data.lastBMU[...] = self.ctx.get_last_bmu()
