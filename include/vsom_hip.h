@@ -918,13 +918,24 @@ int vsom_train_online_chunk_fetch(vsom_ctx *ctx, double eta, double sigma, int d
  * Refuses (VSOM_ERR_INVALID, nothing enqueued, state untouched, the context stays usable): a null context or valid_host;
  * custom and CLR contexts; a decay_fn other than the two online ones; no chunk loaded; a chunk staged ahead over the
  * current rows; a context that has joined a group or an ensemble.  A pending sigmaMap is materialised first, as for the
- * unmasked chunk calls.  Masked chunks always take the exact scan, for every vsom_set_bmu_mode: neither the image-bounded
- * search nor the one-launch tiny-map chunk is used, and vsom_get_online_search_stats does not count their samples.
+ * unmasked chunk calls.  Two loops give these results, bit for bit the same.  A tiny map, where
+ * vsom_online_masked_tiny_applies holds, takes the one-launch chunk of one workgroup (csrc/vsom_online_tiny_masked.hip,
+ * DESIGN.md section 4u): one H2D copy of the validity bytes and one launch per call, lastBMU and the MSE back through
+ * pinned memory as in vsom_train_online_chunk_fetch.  Every other chunk takes the per-sample loop on the exact scan, for
+ * every vsom_set_bmu_mode; the image-bounded search is never used, and vsom_get_online_search_stats counts the samples of
+ * neither loop.
  * Timed under VSOM_T_STAGE (validity staging) and VSOM_T_ONLINE (the kernels).  Device scratch in the query arena:
- * B (J + chunk pitch) validity bytes, or one row of each with one_mask; VSOM_ERR_NOMEM leaves the state untouched. */
+ * B (J + chunk pitch) validity bytes, or one row of each with one_mask (the one-launch chunk: B J, or J); VSOM_ERR_NOMEM
+ * leaves the state untouched. */
 int vsom_train_online_chunk_masked(vsom_ctx *ctx, double eta, double sigma, int decay_fn, int first_chunk,
                                    const uint8_t *valid_host, int one_mask,
                                    uint64_t *lastbmu_out /*[B], may be NULL*/, float *mse_out /*may be NULL*/);
+/* 1: vsom_train_online_chunk_masked(ctx, ., sigma, ., ., ., one_mask, ., .) would take the one-launch chunk.  That is: a
+ * chunk is loaded; the kind is Standard or Median and not custom; N <= 1024, N D <= 4096, D <= 512, B <= 4096; sigma is no
+ * NaN; the search mode is VSOM_BMU_AUTO (EXACT and SHORTLIST name the per-sample loop); VSOM_NO_TINY=1 was not set when the
+ * context was created; and the kernel's LDS need -- the unmasked one-launch chunk's plus a block of 2048 validity bytes --
+ * is within the 96 KiB its launch sets.  0 otherwise, a null context included.  No side effects. */
+int vsom_online_masked_tiny_applies(const vsom_ctx *ctx, double sigma, int one_mask);
 /* diagnostics of the chunk loop's image-bounded search (csrc/vsom_online_i8.hip; synchronises): out[0] = samples searched
  * through the image since the last reset, out[1] = nodes evaluated exactly for them (the candidates that survived the
  * bound), out[2] = refinement workgroups that had a candidate, out[3] = 0.  All zero while the exact scan is in use. */
@@ -956,6 +967,20 @@ void vsom_ensemble_destroy(vsom_ensemble *e);
 size_t vsom_ensemble_size(const vsom_ensemble *e);
 int vsom_ensemble_train_online_chunk_fetch(vsom_ensemble *e, const double *eta, const double *sigma, const int *decay_fn,
                                            int first_chunk, uint64_t *const *lastbmu_out, float *mse_out);
+/* vsom_ensemble_train_online_chunk_fetch for members whose rows have missing fields.  valid_host[k]
+ * is member k's validity (B_k x J_k bytes, or J_k bytes when one_mask[k] != 0; one_mask NULL: all 0) or NULL for a PLAIN
+ * member, which is trained exactly as vsom_ensemble_train_online_chunk_fetch trains it (any kind of context).  Per masked
+ * member the results are those of vsom_train_online_chunk_masked on a context that is no member, bit for bit.  Masked
+ * members for which vsom_online_masked_tiny_applies holds and whose LDS need fits the device's limit run as one launch per
+ * kernel instantiation, one workgroup per member; their validity bytes are gathered into one pinned image and copied to
+ * the device once per call.  Every other masked member runs the single call's loop inside this call.  valid_host is not
+ * read after the call returns.  Refuses (VSOM_ERR_INVALID, naming the member, before anything is enqueued for any member):
+ * what vsom_ensemble_train_online_chunk_fetch refuses, a null valid_host array, and for a masked member a custom or CLR
+ * context. */
+int vsom_ensemble_train_online_chunk_masked(vsom_ensemble *e, const double *eta, const double *sigma, const int *decay_fn,
+                                            int first_chunk, const uint8_t *const *valid_host /*[K]*/,
+                                            const int *one_mask /*[K], NULL: all 0*/, uint64_t *const *lastbmu_out,
+                                            float *mse_out);
 int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_first, float *mse_out);
 /* vsom_batch_schedule for every member, each with its own schedule: sigma[k] / mse_out[k] hold epochs[k] values.  Per
  * member the result of vsom_batch_schedule(member k, sigma[k], epochs[k], reset_bmu, mse_out[k]).  Members on the fast

@@ -63,6 +63,7 @@ SYMBOLS = [
     "vsom_bmu_topk_masked_batch",
     "vsom_batch_schedule_masked", "vsom_ensemble_batch_epoch_masked", "vsom_ensemble_batch_schedule_masked",
     "vsom_masked_tiny_applies",
+    "vsom_online_masked_tiny_applies", "vsom_ensemble_train_online_chunk_masked",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -304,6 +305,11 @@ def lib():
     if hasattr(L, "vsom_train_online_chunk_masked"):    # (VSOM_LIB may name an older build: tools/online_masked_bench.py --lib)
         L.vsom_train_online_chunk_masked.argtypes = [vp, C.c_double, C.c_double, C.c_int, C.c_int, C.POINTER(C.c_uint8), C.c_int,
                                                      C.POINTER(C.c_uint64), fp]
+    if hasattr(L, "vsom_online_masked_tiny_applies"):   # (VSOM_LIB may name an older build: tools/online_tiny_masked_bench.py --lib)
+        u8p = C.POINTER(C.c_uint8)
+        L.vsom_online_masked_tiny_applies.argtypes = [vp, C.c_double, C.c_int]
+        L.vsom_ensemble_train_online_chunk_masked.argtypes = [vp, dp, dp, C.POINTER(C.c_int), C.c_int, C.POINTER(u8p),
+                                                              C.POINTER(C.c_int), C.POINTER(u64p), fp]
     if hasattr(L, "vsom_batch_accum_chunk_masked"):     # (VSOM_LIB may name an older build: tools/accum_masked_bench.py --lib)
         L.vsom_batch_accum_chunk_masked.argtypes = [vp, C.POINTER(C.c_uint8), C.c_int]
     if hasattr(L, "vsom_similarity_masked_batch"):      # (VSOM_LIB may name an older build: tools/masked_score_bench.py --lib)
@@ -1200,6 +1206,11 @@ class Context:
                                                    vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(one), _u(lb), C.byref(mse)))
         return np.float32(mse.value), lb
 
+    def online_masked_tiny_applies(self, sigma, one_mask=False):
+        """would train_online_chunk_masked on the loaded chunk take the one-launch chunk of one workgroup
+        (vsom_online_masked_tiny_applies)?"""
+        return bool(lib().vsom_online_masked_tiny_applies(self._h, float(sigma), int(bool(one_mask))))
+
     def online_search_stats(self, reset=False):
         """image-bounded search of the online chunk loop: samples searched, nodes evaluated exactly, refinement workgroups
         with work (all zero while the exact scan is in use)"""
@@ -1419,6 +1430,22 @@ class Ensemble:
         check(lib().vsom_ensemble_train_online_chunk_fetch(
             self._h, self._per_member(eta, C.c_double, float), self._per_member(sigma, C.c_double, float),
             self._per_member(decay_fn, C.c_int, int), int(bool(first_chunk)), ptrs, _f(mse)))
+        return mse, lbs
+
+    def train_online_chunk_masked(self, eta, sigma, decay_fn, valid, first_chunk=True):
+        """train_online_chunk_fetch over the valid entries only for the members with a validity
+        (vsom_ensemble_train_online_chunk_masked).  valid: as in batch_epoch_masked -- a list with one entry per member,
+        None (a plain member), a B x J array, or a 1-D column mask of J entries; ValueError before any call into the
+        library.  Returns (running MSE per member [float32 array], lastBMU per member [list of uint64 arrays])."""
+        keep, vptrs, ones = self._validities(valid)
+        n = len(self.members)
+        lbs = [np.zeros(c.chunk_size, np.uint64) for c in self.members]
+        ptrs = (C.POINTER(C.c_uint64) * n)(*[_u(a) for a in lbs])
+        mse = np.zeros(n, np.float32)
+        check(lib().vsom_ensemble_train_online_chunk_masked(
+            self._h, self._per_member(eta, C.c_double, float), self._per_member(sigma, C.c_double, float),
+            self._per_member(decay_fn, C.c_int, int), int(bool(first_chunk)), vptrs, ones, ptrs, _f(mse)))
+        del keep
         return mse, lbs
 
     def batch_epoch(self, sigma, is_first):

@@ -184,6 +184,7 @@ struct EnsCall {
     hipStream_t also = nullptr;              // the schedule's table copies: a launched member's stream
     std::vector<hipStream_t> streams;        // the distinct streams of the last join
     bool onl_slots = false;                  // online training: e->lslot[] of the launched members is released
+    std::vector<std::pair<vsom_ctx *, int>> held;   // ... or, for a call of several ens_launch passes, these table slots
     bool open = true;
     explicit EnsCall(vsom_ensemble *ens) : e(ens) {}
     EnsCall(const EnsCall &) = delete;
@@ -244,6 +245,8 @@ struct EnsCall {
         for (size_t k = 0; k < e->m.size() && onl_slots && ls; ++k)
             if (e->grp[k] >= 0)
                 vsom_onl_tiny_done(e->m[k], e->lslot[k]);
+        for (size_t i = 0; i < held.size() && ls; ++i)
+            vsom_onl_tiny_done(held[i].first, held[i].second);
         return err;
     }
     int end(int rc)
@@ -371,6 +374,144 @@ int vsom_ensemble_train_online_chunk_fetch(vsom_ensemble *e, const double *eta, 
     // results of the launched members: the kernels stored them into each member's pinned words
     for (size_t k = 0; k < n; ++k) {
         if (e->grp[k] < 0)
+            continue;
+        vsom_ctx *c = e->m[k];
+        if (lastbmu_out && lastbmu_out[k])
+            std::memcpy(lastbmu_out[k], c->out_pinned.p, c->B * sizeof(uint64_t));
+        if (mse_out)
+            mse_out[k] = *static_cast<volatile float *>(c->mse.p);
+    }
+    return VSOM_OK;
+}
+
+// The online chunk with validity.  Two ens_launch passes on one launch stream, each with its own
+// descriptor slot: the plain members that take online_tiny_chunk_many_kernel (as vsom_ensemble_train_online_chunk_fetch
+// launches them), then the masked members that take online_tiny_masked_chunk_many_kernel, whose validity bytes form one
+// pinned image in the second pass's slot, copied once.  Every other member runs its single call while the launches run.
+int vsom_ensemble_train_online_chunk_masked(vsom_ensemble *e, const double *eta, const double *sigma, const int *decay_fn,
+                                            int first_chunk, const uint8_t *const *valid_host, const int *one_mask,
+                                            uint64_t *const *lastbmu_out, float *mse_out)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    if (!eta || !sigma || !decay_fn)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null parameter array");
+    if (!valid_host)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null valid_host array");
+    const size_t n = e->m.size();
+    // refusals first: nothing is enqueued for any member unless every member can train
+    for (size_t k = 0; k < n; ++k) {
+        const vsom_ctx *c = e->m[k];
+        if (decay_fn[k] != VSOM_EXPONENTIAL && decay_fn[k] != VSOM_INVERSE_PROPORTIONAL)
+            return ens_fail(k, "online training needs Exponential or InverseProportional");
+        if (valid_host[k] && c->cu)
+            return ens_fail(k, "vsom_train_online_chunk_masked: custom contexts are not supported");
+        if (valid_host[k] && c->transform == VSOM_CLR)
+            return ens_fail(k, "vsom_train_online_chunk_masked: CLR contexts are not supported (residual and step run over column pairs)");
+        if (const char *why = ens_rows_refusal(c))
+            return ens_fail(k, why);
+    }
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    EnsCall call(e);
+    if (int rc = join_members(e, nullptr, true))
+        return rc;
+    // who is launched: 1 = a plain member on the one-launch chunk, 2 = a masked one
+    const size_t pstride = vsom_onl_tiny_desc_bytes(), mstride = vsom_onl_tiny_masked_desc_bytes();
+    std::vector<int> how(n, 0), pgrp(n, -1);
+    std::vector<size_t> psmem(n, 0), v_at(n, 0), vbytes(n, 0);
+    std::vector<unsigned char> pdesc(n * pstride);
+    size_t vtotal = 0;
+    bool any_plain = false, any_masked = false;
+    for (size_t k = 0; k < n; ++k) {
+        vsom_ctx *c = e->m[k];
+        if (c->cu)
+            continue;                        // custom transformation: its own path
+        const bool want_lb = lastbmu_out && lastbmu_out[k];
+        if (!valid_host[k]) {
+            int lslot = 0;
+            if (int rc = vsom_onl_tiny_prepare(c, eta[k], sigma[k], decay_fn[k], first_chunk, want_lb, e->lds_limit,
+                                               pdesc.data() + k * pstride, &pgrp[k], &psmem[k], &lslot))
+                return rc;
+            if (pgrp[k] >= 0) {
+                how[k] = 1;
+                any_plain = true;
+                call.held.emplace_back(c, lslot);
+            }
+        } else if (vsom_onl_tiny_masked_fits(c, sigma[k], e->lds_limit)) {
+            how[k] = 2;
+            any_masked = true;
+            vbytes[k] = ((one_mask && one_mask[k]) ? 1 : c->B) * (size_t)c->J;
+            v_at[k] = vtotal;
+            vtotal += (vbytes[k] + 15) / 16 * 16;
+        }
+    }
+    int rc = VSOM_OK;
+    if (any_plain || any_masked) {
+        // one launch stream behind every launched member's stream, for both passes
+        ens_scratch(e, pstride);
+        for (size_t k = 0; k < n; ++k)
+            e->grp[k] = how[k] ? 0 : -1;
+        if (int jrc = call.join(ENS_LAUNCHED))
+            return jrc;
+    }
+    if (any_plain) {
+        for (size_t k = 0; k < n; ++k) {
+            e->grp[k] = how[k] == 1 ? pgrp[k] : -1;
+            e->smem[k] = psmem[k];
+        }
+        e->desc = pdesc;
+        rc = ens_launch(
+            call, ENS_JOINED, VSOM_ONL_TINY_GROUPS, pstride, ENS_NO_CAP,
+            [&](int g) { return vsom_onl_tiny_ready(g, e->device, e->lds_limit); },
+            [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t s) {
+                return vsom_onl_tiny_launch_many(g, d, cnt, smem, s);
+            });
+    }
+    if (any_masked && !rc) {
+        // the slot ens_launch is about to take: its last launch has completed, so its image may be rewritten
+        auto &s = e->slot[e->next];
+        if (s.valid)
+            VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
+        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(s.img_host, vtotal), vsom_member(s.img_dev, vtotal)}));
+        for (size_t k = 0; k < n; ++k)
+            if (how[k] == 2)
+                std::memcpy(s.img_host.p + v_at[k], valid_host[k], vbytes[k]);
+        VSOM_HIP_CHECK(hipMemcpyAsync(s.img_dev.p, s.img_host.p, vtotal, hipMemcpyHostToDevice, call.ls));
+        ens_scratch(e, mstride);
+        for (size_t k = 0; k < n && !rc; ++k) {
+            if (how[k] != 2)
+                continue;
+            vsom_ctx *c = e->m[k];
+            int lslot = 0;
+            rc = vsom_onl_tiny_masked_prepare(c, eta[k], sigma[k], decay_fn[k], first_chunk, lastbmu_out && lastbmu_out[k],
+                                              s.img_dev.p + v_at[k], one_mask ? one_mask[k] : 0,
+                                              e->desc.data() + k * mstride, &e->grp[k], &e->smem[k], &lslot);
+            if (!rc)
+                call.held.emplace_back(c, lslot);
+        }
+        if (!rc)
+            rc = ens_launch(
+                call, ENS_JOINED, VSOM_ONL_TINY_GROUPS, mstride, ENS_NO_CAP,
+                [&](int g) { return vsom_onl_tiny_masked_ready(g, e->device, e->lds_limit); },
+                [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t st) {
+                    return vsom_onl_tiny_masked_launch_many(g, d, cnt, smem, st);
+                });
+    }
+    // the other members through their single calls, while the launches run
+    for (size_t k = 0; k < n && !rc; ++k) {
+        if (how[k])
+            continue;
+        uint64_t *lb = lastbmu_out ? lastbmu_out[k] : nullptr;
+        float *mse = mse_out ? mse_out + k : nullptr;
+        rc = valid_host[k] ? vsom_online_chunk_masked_member(e->m[k], eta[k], sigma[k], decay_fn[k], first_chunk, valid_host[k],
+                                                             one_mask ? one_mask[k] : 0, lb, mse)
+                           : vsom_train_online_chunk_fetch(e->m[k], eta[k], sigma[k], decay_fn[k], first_chunk, lb, mse);
+    }
+    if ((rc = call.end(rc)))
+        return rc;
+    // results of the launched members: the kernels stored them into each member's pinned words
+    for (size_t k = 0; k < n; ++k) {
+        if (!how[k])
             continue;
         vsom_ctx *c = e->m[k];
         if (lastbmu_out && lastbmu_out[k])

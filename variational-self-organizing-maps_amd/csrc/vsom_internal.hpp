@@ -127,6 +127,7 @@ struct vsom_ctx {
     bool dedupe = true;             // VSOM_NO_DEDUPE=1 switches it off (A/B measurements)
     double dd_min_work = 2.0e10;    // exact searches of at least this many (sample, node, value) triples (vsom_set_row_dedupe)
     bool tiny_lds_attr[12] = {};    // online_tiny_chunk_kernel<kind, local, U>: dynamic LDS limit raised (per context: its device, its kind)
+    bool tiny_masked_lds_attr[6] = {};   // online_tiny_masked_chunk_kernel<kind, local, U>: the same, [local][U]
 
     // MFMA shortlist scratch
     DevBuf<float> sl_G, sl_nrm; DevBuf<unsigned> sl_scal;
@@ -567,6 +568,19 @@ int vsom_onl_tiny_prepare(vsom_ctx *c, double eta, double sigma, int decay_fn, i
 int vsom_onl_tiny_ready(int group, int device, size_t lds_limit);
 int vsom_onl_tiny_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
 void vsom_onl_tiny_done(vsom_ctx *c, int lut_slot);
+// the one-launch chunk over valid entries (vsom_online_tiny_masked.hip): the same groups, a descriptor
+// of its own.  fits: vsom_online_masked_tiny_applies' conditions with the LDS need (+ the static key slots) within lds_limit;
+// prepare (for a member that fits): valid_dev = its validity bytes on the device (B x J, or J with one_mask)
+bool vsom_onl_tiny_masked_fits(const vsom_ctx *c, double sigma, size_t lds_limit);
+size_t vsom_onl_tiny_masked_desc_bytes();
+int vsom_onl_tiny_masked_prepare(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk, bool want_lb,
+                                 const unsigned char *valid_dev, int one_mask, void *desc, int *group, size_t *smem,
+                                 int *lut_slot);
+int vsom_onl_tiny_masked_ready(int group, int device, size_t lds_limit);
+int vsom_onl_tiny_masked_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
+// vsom_train_online_chunk_masked for a member of an ensemble (vsom_online.hip): every refusal but that of the membership
+int vsom_online_chunk_masked_member(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk,
+                                    const uint8_t *valid_host, int one_mask, uint64_t *lastbmu_out, float *mse_out);
 size_t vsom_tiny_desc_bytes();       // (descriptors are packed at exactly this size: the kernels index args[blockIdx.x])
 int vsom_tiny_prepare(vsom_ctx *c, double sigma, int is_first, size_t lds_limit, void *desc, int *group, size_t *smem);
 int vsom_tiny_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);

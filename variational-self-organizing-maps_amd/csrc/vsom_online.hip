@@ -5,12 +5,14 @@
 //                         onl_refine_kernel and their per-chunk passes, enqueue_chunk_i8, vsom_get_online_search_stats
 //   vsom_online_tiny.hip  tiny maps: the whole chunk loop in one launch of one workgroup (online_tiny_chunk_kernel), and
 //                         one workgroup per map for ensembles (vsom_onl_tiny_*)
+//   vsom_online_tiny_masked.hip  the one-launch chunk over the valid entries of the rows only, for the same tiny maps
+//                         (online_tiny_masked_chunk_kernel; vsom_onl_tiny_masked_* for ensembles)
 //   vsom_online_masked.hip the chunk loop over the valid entries of the rows only (Standard / Median): the masked scan,
 //                         window and one-launch step of vsom_train_online_chunk_masked, enqueue_chunk_masked
 //   vsom_single.hip       single-vector queries: vsom_find_bmu, vsom_find_restricted_bmu, vsom_distances_single,
 //                         vsom_dist_single, vsom_find_local_bmu; stage_single
 // Here: the per-sample kernels, the neighbourhood tables (lutd), and the entry points vsom_train_online_chunk* (which pick
-// one of the three chunk loops) and vsom_train_single.
+// one of the four chunk loops) and vsom_train_single.
 //
 // The path is strictly sequential in samples (sample j's BMU search reads the map sample j-1
 // wrote), so one sample = two launches (sigma > 1) or one (sigma <= 1) enqueued back to back on
@@ -480,11 +482,14 @@ extern "C" {
 
 // lb_host != NULL: the caller wants lastBMU back in this call -- *lb_in_pinned = the one-launch kernel has stored it into
 // c->out_pinned.p itself (else the caller fetches it with vsom_get_last_bmu)
-// masked: vsom_train_online_chunk_masked -- the same preamble, then always the exact-scan loop of vsom_online_masked.hip
-// with the validity bytes valid_host (B x J, or J with one_mask) staged into the query arena
+// masked: vsom_train_online_chunk_masked -- the same preamble with the validity bytes valid_host (B x J, or J with one_mask)
+// copied into the query arena, then one of two loops: where vsom_online_masked_tiny_applies holds, the one-launch chunk of
+// vsom_online_tiny_masked.hip, which reads those bytes as they are (one H2D copy and one launch; lastBMU and the MSE come
+// back through pinned memory as in the unmasked call); otherwise the exact-scan loop of vsom_online_masked.hip over their
+// packed copy.  member: the caller is the ensemble the context has joined (vsom_online_chunk_masked_member).
 static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk, float *mse_out,
                                    bool want_lb, bool *lb_in_pinned, bool masked = false, const uint8_t *valid_host = nullptr,
-                                   int one_mask = 0)
+                                   int one_mask = 0, bool member = false)
 {
     if (lb_in_pinned)
         *lb_in_pinned = false;
@@ -493,7 +498,7 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
         VSOM_CUSTOM_REFUSE(c, "vsom_train_online_chunk_masked");
         if (c->transform == VSOM_CLR)
             return vsom_fail(VSOM_ERR_INVALID, "vsom_train_online_chunk_masked: CLR contexts are not supported (residual and step run over column pairs)");
-        if (c->in_group || c->sigma_shared)
+        if (c->in_group || (c->sigma_shared && !member))
             return vsom_fail(VSOM_ERR_INVALID, "vsom_train_online_chunk_masked: the context has joined a group or an ensemble");
         if (!valid_host)
             return vsom_fail(VSOM_ERR_INVALID, "valid_host is null");
@@ -518,7 +523,8 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
     c->rows_free_valid = false;   // (the chunk below reads the staged rows, a later stage-ahead must not take them)
     const double *lutd = nullptr;
     int lutw = (int)c->W, lslot = 0, rc;
-    bool tiny = !masked && online_tiny_applies(c, sigma);
+    const bool tiny_masked = masked && vsom_online_masked_tiny_applies(c, sigma, one_mask);
+    bool tiny = tiny_masked || (!masked && online_tiny_applies(c, sigma));
     if (tiny)                                 // one launch reads the table once, into LDS: straight from the pinned slot
         rc = ensure_lutd_host(c, sigma, &lutd, &lslot);
     else
@@ -526,17 +532,21 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
     if (rc)
         return rc;
     const bool one = one_mask != 0;
-    const unsigned char *packed = nullptr;
-    if (masked && c->B > 0) {     // the validity bytes as given and packed (0xFF / 0x00, xpitch a row), before any kernel
+    const unsigned char *packed = nullptr, *vraw = nullptr;
+    if (masked && c->B > 0) {     // the validity bytes as given and, for the loop, packed (0xFF / 0x00, xpitch a row), before any kernel
         const size_t vrows = one ? 1 : c->B;
         vsom_layout lay;
-        const auto raw = lay.add<unsigned char>(vrows * c->J), pk = lay.add<unsigned char>(vrows * c->xpitch);
+        const auto raw = lay.add<unsigned char>(vrows * c->J);
+        const auto pk = lay.add<unsigned char>(tiny_masked ? 0 : vrows * c->xpitch);   // (the one-launch chunk needs no packed copy)
         VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
         TimerScope ts(c, VSOM_T_STAGE);
         VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(raw), valid_host, vrows * c->J, hipMemcpyHostToDevice, c->stream));
-        vsom_masked_pack_enqueue(c, lay.at(raw), vrows, lay.at(pk));
-        VSOM_HIP_CHECK(hipGetLastError());
-        packed = lay.at(pk);
+        vraw = lay.at(raw);
+        if (!tiny_masked) {
+            vsom_masked_pack_enqueue(c, lay.at(raw), vrows, lay.at(pk));
+            VSOM_HIP_CHECK(hipGetLastError());
+            packed = lay.at(pk);
+        }
     }
     {
         TimerScope ts(c, VSOM_T_ONLINE);
@@ -549,7 +559,9 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
                 VSOM_ALLOC_CHECK(vsom_grow(c->out_pinned, 8192, c->stream));
                 lbh = c->out_pinned.p;
             }
-            if ((rc = enqueue_chunk_tiny(c, eta, sigma, decay_fn, lutd, lutw, first_chunk, lbh)) || (rc = lutd_host_used(c, lslot)))
+            rc = tiny_masked ? enqueue_chunk_tiny_masked(c, eta, sigma, decay_fn, lutd, lutw, first_chunk, lbh, vraw, one)
+                             : enqueue_chunk_tiny(c, eta, sigma, decay_fn, lutd, lutw, first_chunk, lbh);
+            if (rc || (rc = lutd_host_used(c, lslot)))
                 return rc;
             if (lbh && lb_in_pinned)
                 *lb_in_pinned = true;
@@ -626,10 +638,11 @@ int vsom_train_online_chunk_fetch(vsom_ctx *c, double eta, double sigma, int dec
 int vsom_train_online_chunk_masked(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk,
                                    const uint8_t *valid_host, int one_mask, uint64_t *lastbmu_out, float *mse_out)
 {
-    if (int rc = train_online_chunk_impl(c, eta, sigma, decay_fn, first_chunk, nullptr, lastbmu_out != nullptr, nullptr, true,
+    bool in_pinned = false;
+    if (int rc = train_online_chunk_impl(c, eta, sigma, decay_fn, first_chunk, nullptr, lastbmu_out != nullptr, &in_pinned, true,
                                          valid_host, one_mask))
         return rc;
-    return online_chunk_fetch(c, false, lastbmu_out, mse_out);
+    return online_chunk_fetch(c, in_pinned, lastbmu_out, mse_out);
 }
 
 int vsom_train_online_chunk(vsom_ctx *c, double eta, double sigma, int decay_fn, float *mse_out)
@@ -703,3 +716,15 @@ int vsom_train_single(vsom_ctx *c, const float *v_host, double eta, double sigma
 }
 
 }   // extern "C"
+
+// vsom_train_online_chunk_masked for a member of an ensemble (vsom_ensemble_train_online_chunk_masked): the single call with
+// every refusal but that of the membership
+int vsom_online_chunk_masked_member(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk,
+                                    const uint8_t *valid_host, int one_mask, uint64_t *lastbmu_out, float *mse_out)
+{
+    bool in_pinned = false;
+    if (int rc = train_online_chunk_impl(c, eta, sigma, decay_fn, first_chunk, nullptr, lastbmu_out != nullptr, &in_pinned, true,
+                                         valid_host, one_mask, true))
+        return rc;
+    return online_chunk_fetch(c, in_pinned, lastbmu_out, mse_out);
+}

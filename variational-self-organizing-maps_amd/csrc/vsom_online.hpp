@@ -191,6 +191,10 @@ int enqueue_chunk_i8(vsom_ctx *c, double eta, double sigma, int decay_fn, const 
 bool online_tiny_applies(const vsom_ctx *c, double sigma);
 int enqueue_chunk_tiny(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw, int first_chunk,
                        u64 *lastbmu_host);
+// vsom_online_tiny_masked.hip: the one-launch chunk over valid entries (vsom_online_masked_tiny_applies holds), valid_dev:
+// the validity bytes as given (B x J, or J with one)
+int enqueue_chunk_tiny_masked(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw,
+                              int first_chunk, u64 *lastbmu_host, const unsigned char *valid_dev, bool one);
 // vsom_online_masked.hip: the exact-scan chunk loop over valid entries (Standard / Median), vp: the packed validity rows
 int enqueue_chunk_masked(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw,
                          const unsigned char *vp, bool one);

@@ -1,6 +1,6 @@
 // vsom_online_tiny.hip -- tiny maps: the whole chunk loop of Som::trainBasicSom (Som.cpp:1159-1171) in ONE launch of ONE
 // workgroup, and the same body with one workgroup per map for ensembles (vsom_onl_tiny_*, called by vsom_ensemble.hip).
-// One of the three chunk loops vsom_train_online_chunk* picks from (vsom_online.hip, the index of the family).
+// One of the four chunk loops vsom_train_online_chunk* picks from (vsom_online.hip, the index of the family).
 //
 // The reference's own performance scenario trains a 10 x 10 map on 20 nine-dimensional rows (tests/performance/
 // perf_tests.cpp:74-112): two dependent launches per sample were 220-260 us per epoch there against 50 us of one CPU thread.
@@ -21,26 +21,10 @@
 // sigmaMap is written once at the end, from the final S and weight, for the nodes some window touched (the value of the
 // node's last update: onl_sigma_kernel's argument).  Results are bit-identical to the per-sample kernels and the oracle.
 // The kernel is bound by instruction issue (16 wavefronts on 4 SIMDs) and LDS latency: 0.95 us per sample at 10 x 10 x 9.
-#include "vsom_online.hpp"
+#include "vsom_online_tiny.hpp"
 #include <cstring>
 #include <array>
 #include <mutex>
-
-struct OnlTinyArgs {
-    const float *X;          // staged rows
-    int ldx, B, N, W, H, D, pitch;
-    float *map, *Smap, *sigmap, *weight;
-    u64 *hits, *lastbmu;
-    float *fstate;           // [0] distance of the last sample's BMU, [1] MSE running sum (in/out)
-    const double *lutd;
-    int lutw;
-    double eta, sigma;
-    int decay_fn;
-    float fB;
-    int keep_mse;            // 0: first chunk of an epoch, the running MSE starts at 0 (online_init_kernel's argument)
-    float *mse_out;          // vsom_get_mse's value
-    u64 *lastbmu_host;       // pinned host copy of lastBMU (vsom_train_online_chunk_fetch), or NULL
-};
 
 #ifdef VSOM_DEVELOPMENT
 // cycle stamps of one sample of the one-launch chunk (sample 5 of the chunk; s_memtime): [2 w + p] = wavefront w (0: first,
@@ -54,152 +38,6 @@ extern "C" int vsom_dev_tiny_stamps(unsigned long long *out)
 #else
 #define TINY_STAMP(p) ((void)0)
 #endif
-constexpr int TINY_XBLOCK = 2048;      // values of staged rows held in LDS at a time (TINY_XBLOCK / D samples)
-
-// minimum of a u64 over the wavefront, in lane 63: four row shifts, two row broadcasts (DPP moves of both halves; the
-// cross-lane LDS permutes of a shuffle ladder were a third of a tiny-map sample)
-__device__ __forceinline__ u64 onl_wave_min_u64(u64 v)
-{
-#define ONL_DPP_STEP(CTRL, ROWS)                                                                                         \
-    {                                                                                                                    \
-        const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)v, CTRL, ROWS, 0xF, false);         \
-        const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)(unsigned)(v >> 32), CTRL, ROWS, 0xF, false); \
-        const u64 o = (u64)hi << 32 | lo;                                                                                \
-        v = o < v ? o : v;                                                                                               \
-    }
-    ONL_DPP_STEP(0x111, 0xF)   // row_shr:1
-    ONL_DPP_STEP(0x112, 0xF)   // row_shr:2
-    ONL_DPP_STEP(0x114, 0xF)   // row_shr:4
-    ONL_DPP_STEP(0x118, 0xF)   // row_shr:8   (lane 15 of every row: the row's minimum)
-    ONL_DPP_STEP(0x142, 0xA)   // row_bcast:15 into rows 1 and 3
-    ONL_DPP_STEP(0x143, 0xC)   // row_bcast:31 into rows 2 and 3
-#undef ONL_DPP_STEP
-    return v;
-}
-
-// minimum of a u32 over the wavefront, in lane 63 (same ladder, one v_min_u32 with a DPP operand per step)
-__device__ __forceinline__ unsigned onl_wave_min_u32(unsigned v)
-{
-#define ONL_DPP_STEP32(CTRL, ROWS)                                                                  \
-    {                                                                                               \
-        const unsigned o = (unsigned)__builtin_amdgcn_update_dpp(-1, (int)v, CTRL, ROWS, 0xF, false); \
-        v = o < v ? o : v;                                                                          \
-    }
-    ONL_DPP_STEP32(0x111, 0xF)
-    ONL_DPP_STEP32(0x112, 0xF)
-    ONL_DPP_STEP32(0x114, 0xF)
-    ONL_DPP_STEP32(0x118, 0xF)
-    ONL_DPP_STEP32(0x142, 0xA)
-    ONL_DPP_STEP32(0x143, 0xC)
-#undef ONL_DPP_STEP32
-    return v;
-}
-
-struct OnlTinyNode {           // what a thread needs to know about the sample's BMU: its coordinates and window (Som.cpp:899-907)
-    unsigned short bx, by, startX, endX, startY, endY, pad0, pad1;
-};
-
-// Som::findLocalBmu (Som.cpp:335-454) over a table of the sample's distances to every node, by one thread: vsom_local_walk's
-// steps and comparisons in its order (the 8 neighbours of the first try, then 3 nodes ahead while moving in X; the size_t
-// wrap-then-clamp of :362-385 in 32 bits -- a wrapped coordinate is far above width - 1 either way)
-__device__ __forceinline__ int onl_tiny_walk(const float *s_d, const OnlTinyNode *s_win, unsigned W, unsigned H, unsigned start)
-{
-    // (the coordinates of lastMeasured / lastBMU / the running minimum travel in registers: every candidate is built from its
-    //  coordinates, so a step is ONE LDS round trip -- the candidates' distances, requested together, compared in order)
-    unsigned lastBMU = start, minIndex = start, lastMeasured = start;
-    unsigned lmX = s_win[start].bx, lmY = s_win[start].by, lbX = lmX, minX = lmX, minY = lmY;
-    float minDist = s_d[start];
-    for (;;) {
-        if (lastMeasured == lastBMU) {
-            unsigned node[8], cxs[8], cys[8];
-            float di[8];
-#pragma unroll
-            for (int g = 0; g < 8; ++g) {
-                const unsigned fsx = (g == 0 || g >= 6) ? ~0u : ((g == 1 || g == 5) ? 0u : 1u);   // firstSearchX / Y (:341-342)
-                const unsigned fsy = g <= 2 ? 1u : ((g == 3 || g == 7) ? 0u : ~0u);
-                unsigned cx = lmX + fsx, cy = lmY + fsy;
-                cx = cx < W - 1 ? cx : W - 1;
-                cy = cy < H - 1 ? cy : H - 1;
-                cxs[g] = cx;
-                cys[g] = cy;
-                node[g] = cy * W + cx;
-                di[g] = s_d[node[g]];
-            }
-#pragma unroll
-            for (int g = 0; g < 8; ++g)
-                if (di[g] < minDist) {
-                    minDist = di[g];
-                    minIndex = node[g];
-                    minX = cxs[g];
-                    minY = cys[g];
-                }
-            if (minIndex == lastBMU)
-                break;
-            lastMeasured = minIndex;
-            lmX = minX;
-            lmY = minY;
-        } else {
-            if (lmX - lbX) {                                     // moving in X: 3 nodes ahead (:390-403)
-                unsigned cx = lmX + lmX - lbX;
-                cx = cx < W - 1 ? cx : W - 1;
-                unsigned node[3], cys[3];
-                float di[3];
-#pragma unroll
-                for (int i = 0; i < 3; ++i) {
-                    unsigned cy = lmY + (unsigned)(i - 1);
-                    cy = cy < H - 1 ? cy : H - 1;
-                    cys[i] = cy;
-                    node[i] = cy * W + cx;
-                    di[i] = s_d[node[i]];
-                }
-#pragma unroll
-                for (int i = 0; i < 3; ++i)
-                    if (di[i] < minDist) {
-                        minDist = di[i];
-                        minIndex = node[i];
-                        minX = cx;
-                        minY = cys[i];
-                    }
-            }
-            // (moving in Y evaluates nothing: :406-437, vsom_local_walk)
-            if (minIndex == lastMeasured)
-                break;
-            lastBMU = lastMeasured;
-            lbX = lmX;
-            lastMeasured = minIndex;
-            lmX = minX;
-            lmY = minY;
-        }
-    }
-    return (int)minIndex;
-}
-
-// a row of squares added in Eigen's order: the eight accumulator classes, the packet tree, the scalar tail (vsom_group_dist's
-// arithmetic by one thread)
-__device__ __forceinline__ float onl_tiny_row_sum(const float *p, int L8, int rem)
-{
-    float acc[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-    for (int d = 0; d < L8; d += 8) {
-#pragma unroll
-        for (int k = 0; k < 8; ++k)
-            acc[k] = acc[k] + p[d + k];
-    }
-    float q0 = acc[0] + acc[4], q1 = acc[1] + acc[5], q2 = acc[2] + acc[6], q3 = acc[3] + acc[7];
-    int t = 0;
-    if (rem >= 4) {
-        q0 = q0 + p[L8];
-        q1 = q1 + p[L8 + 1];
-        q2 = q2 + p[L8 + 2];
-        q3 = q3 + p[L8 + 3];
-        t = 4;
-    }
-    const float t02 = q0 + q2, t13 = q1 + q3;
-    float res = t02 + t13;
-    for (; t < rem; ++t)
-        res = res + p[L8 + t];
-    return res;
-}
-
 template <int KIND, bool LOCAL, int U>     // U = values per thread (1, 2, 4): N D <= 1024 U
 __global__ __launch_bounds__(1024) void online_tiny_chunk_kernel(OnlTinyArgs a)
 {
@@ -216,7 +54,7 @@ __global__ __launch_bounds__(1024) void online_tiny_chunk_many_kernel(const OnlT
 #include "vsom_tiny_online_body.inc"
 }
 
-static size_t online_tiny_lds_bytes(const vsom_ctx *c)
+size_t online_tiny_lds_bytes(const vsom_ctx *c)
 {
     const size_t N = c->N, D = c->part_len;
     return N * (16 + 8 + 8) + (N * (D | 1) + 2 * ((D + 3) & ~(size_t)3) + TINY_XBLOCK) * sizeof(float) + N * 8 +
@@ -229,8 +67,8 @@ bool online_tiny_applies(const vsom_ctx *c, double sigma)
            (size_t)c->N * c->part_len <= 4096 && c->part_len <= 512 && c->B <= 4096 && c->bmu_mode == VSOM_BMU_AUTO;   // (EXACT / SHORTLIST name the per-sample forms)
 }
 
-static void fill_chunk_tiny_args(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw,
-                                 int first_chunk, u64 *lastbmu_host, OnlTinyArgs &a)
+void fill_chunk_tiny_args(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw,
+                          int first_chunk, u64 *lastbmu_host, OnlTinyArgs &a)
 {
     a.X = c->Xs.p;
     a.ldx = (int)c->xpitch;
@@ -259,7 +97,7 @@ static void fill_chunk_tiny_args(vsom_ctx *c, double eta, double sigma, int deca
 }
 
 // the kernel instantiation a map takes: (Median ? 6 : 0) + (local ? 3 : 0) + (0, 1, 2 for U = 1, 2, 4)
-static int chunk_tiny_group(const vsom_ctx *c, double sigma)
+int chunk_tiny_group(const vsom_ctx *c, double sigma)
 {
     const bool local = !(sigma > 1);                  // SIGMA_SWITCH_TO_LOCAL (SOM.hpp:37, Som.cpp:891)
     const size_t nd = (size_t)c->N * c->part_len;
