@@ -59,6 +59,20 @@ on the first context (run_walk, back_to_back), with nothing between two calls bu
 replayed on the twin and the model, each return held against them: there the third masked chunk does meet a busy stream,
 and the buffers and the arena do grow behind enqueued work.  (Not on clr12 / custom12, where begin is refused, and not on
 the CPU fake, which is sequential by nature.)
+
+A fourth profile, "ensemble" (generate_ensemble, run_ensemble_walk, EnsGpuBackend, at the end of this file), walks the nine
+vsom_ensemble_* calls with the single-context calls on their members between them -- among these vsom_batch_schedule,
+vsom_batch_schedule_masked and vsom_train_online_chunk_masked, which enter the walks here.  Its members (ENS_MEMBERS, beside
+CONFIGS) have row counts at the borders of the path predicates, restated as batch_tiny / masked_batch_tiny / online_tiny;
+two ensemble configurations (ENS_CONFIGS) put them on one stream and on a stream each.  EnsModel keeps one Model per member:
+an accepted ensemble call is the single call on every member in index order, every output compares bit for bit, a refused
+call must name the member the header says and is followed by a comparison of the whole state of every member.  Masks are
+accum_mask's, the rows of a masked member poisoned under every invalid entry; members without validity (valid_host[k] = NULL)
+are in every masked call.  The real backend keeps a twin of every member that never joins and makes the single calls one by
+one, synchronised after each: what an ensemble call returns must equal the twins' returns and the model's.  Where the header
+gives a member another answer than a context that never joined (vsom_train_online_chunk_masked, vsom_batch_accum_begin), the
+model says so: the member must refuse.  The walk's first no-wait run goes to the ensemble back to back before twins and model
+see it; the pinned rows of a wait = 0 upload are overwritten once a call that synchronises every member has returned.
 """
 import copy
 import ctypes as C
@@ -67,6 +81,8 @@ import numpy as np
 
 import gen
 import masked_train_ref
+import online_masked_ref
+import schedule_ref
 from oracle import pyoracle as po
 
 VSOM_ERR_INVALID = -1
@@ -103,6 +119,37 @@ CONFIGS = {
                   chunks=[(320, "u8"), (77, "u8"), (512, "f"), (200, "dense")], weights={"online": 2, "single": 1},
                   accum_chunks=[(40, "u8"), (12, "dense"), (11, "u8")]),
 }
+
+# ---- the ensemble profile: members (never a parametrisation of the other profiles) and ensemble configurations ----
+# Every row count stands at a border of a path predicate (batch_tiny, online_tiny below).  A2 has A's shape and chunks, so
+# chunk_data gives it A's rows: vsom_ensemble_upload_chunks names them by equal offsets.
+ENS_MEMBERS = {
+    "A": dict(W=10, H=10, J=9, tr=po.STANDARD, custom=False,
+              chunks=[(20, "dense"), (160, "dense"), (170, "dense"), (257, "dense")]),
+    "A2": dict(W=10, H=10, J=9, tr=po.STANDARD, custom=False, map_seed=100,
+               chunks=[(20, "dense"), (160, "dense"), (170, "dense"), (257, "dense")]),
+    # (B * N <= 16384 alone would end B's one-launch batch epochs at 151 rows; N * D * B <= 262144 ends them at 121)
+    "B": dict(W=12, H=9, J=20, tr=po.MEDIAN, custom=False,
+              chunks=[(37, "dense"), (151, "dense"), (152, "dense"), (121, "dense"), (122, "dense")]),
+    "C": dict(W=12, H=12, J=6, tr=po.CLR, custom=False, chunks=[(77, "clr"), (128, "clr")]),
+    "D": dict(W=4, H=2, J=512, tr=po.MEDIAN, custom=False, chunks=[(3, "dense"), (64, "dense")]),
+    # (1100 rows with an all-zero column: the chunk gets the column compaction, so vsom_ensemble_upload_chunks stages it by
+    # the single-context path from the raw copy)
+    "E": dict(W=40, H=36, J=24, tr=po.STANDARD, custom=False, zero_col=(2, 5),
+              chunks=[(77, "dense"), (300, "dense"), (1100, "dense")]),
+    "F": dict(CONFIGS["custom12"], chunks=[(64, "dense"), (200, "dense")]),
+    "G": dict(CONFIGS["std48"], chunks=[(77, "u8"), (300, "f")], lazy=True),      # created under VSOM_SIGMA_LAZY
+}
+ENS_CONFIGS = {
+    "ens_shared": dict(members=["A", "A2", "B", "C", "D", "E"], one_stream=True),       # the header's fast form
+    "ens_own": dict(members=["A", "B", "C", "E", "F", "G"], one_stream=False),          # joined through own_stream
+}
+
+
+def config(name):
+    """a configuration of the single-context profiles, or an ensemble member"""
+    return CONFIGS[name] if name in CONFIGS else ENS_MEMBERS[name]
+
 
 # ops that read the staged rows of the current chunk: the ones a pending chunk staged ahead may refuse
 READS_ROWS = {"bmu", "bmu_local", "bmu_restricted", "distances", "distances_row", "p1", "p2", "epoch", "epoch_async",
@@ -151,7 +198,7 @@ def chunk_list(cfg, profile="ingest"):
 
 
 def chunk_data(cfg_name, seed, scale=1, profile="ingest"):
-    cfg = CONFIGS[cfg_name]
+    cfg = config(cfg_name)
     out = []
     for i, (b, kind) in enumerate(chunk_list(cfg, profile)):
         b = max(8, b // scale)
@@ -164,6 +211,9 @@ def chunk_data(cfg_name, seed, scale=1, profile="ingest"):
             x = gen.correlated(b, cfg["J"], seed=s)
         else:
             x = gen.blobs(b, cfg["J"], 5, s, s + 1, sigma=0.4)
+        if cfg.get("zero_col", (None,))[0] == i:      # (ensemble member E: a column the compaction drops)
+            x = np.array(x, np.float32)
+            x[:, cfg["zero_col"][1]] = 0
         out.append(np.ascontiguousarray(x, np.float32))
     return out
 
@@ -261,7 +311,7 @@ def two_quad_launch(cfg):
 
 
 def initial_map(cfg_name, seed):
-    cfg = CONFIGS[cfg_name]
+    cfg = config(cfg_name)
     D = po.length(cfg["tr"], cfg["J"])
     m = gen.random_map(cfg["W"] * cfg["H"], D, seed=seed)
     if cfg["J"] >= 100:                  # in the range of the uint8-valued chunks
@@ -888,7 +938,7 @@ def _rand_state(cfg_name, seed, parts, N, D):
 def materialize(op, model):
     """the concrete arguments of an op in the model's current state (the same for every backend)"""
     name, p = op
-    cfg = CONFIGS[model.cfg_name]
+    cfg = model.cfg
     N, B = model.N, model.B
     if name in ("upload", "prefetch", "stage"):
         return {"X": model.rows(p)}
@@ -897,6 +947,8 @@ def materialize(op, model):
             return {"valid": None}
         X = model.X if model.X is not None else np.zeros((0, cfg["J"]), np.float32)
         return {"valid": np.ascontiguousarray(accum_mask(p["seed"], p["k"], p["form"], p.get("full", False), X), np.uint8)}
+    if name in ("schedule_masked", "online_masked"):
+        return {"valid": ens_mask(p, model.X)}
     if name in MASKED_SCORES:
         rs = np.random.RandomState(p["seed"])
         Xw = model.X[p["r0"]:p["r1"]]
@@ -1011,7 +1063,7 @@ class Model:
     """what the header says the context holds after each call"""
 
     def __init__(self, cfg_name, seed, scale=1, profile="ingest"):
-        cfg = CONFIGS[cfg_name]
+        cfg = config(cfg_name)
         self.cfg_name, self.cfg, self.profile = cfg_name, cfg, profile
         self.som = po.OracleSom(cfg["W"], cfg["H"], cfg["J"], cfg["tr"])
         self.N = cfg["W"] * cfg["H"]
@@ -1245,7 +1297,51 @@ class Model:
             s.set_state(**a)
         elif name == "get_state":
             return self.state()
+        # ---- single-context ops that enter with the ensemble profile ----
+        elif name == "schedule":
+            return {"mses": self._schedule(p["sigmas"], p["reset"], None)}
+        elif name == "schedule_masked":
+            return {"mses": self._schedule(p["sigmas"], p["reset"], a["valid"])}
+        elif name == "online_masked":
+            return self._online_masked(p, a["valid"])
+        elif name == "um":
+            self.um = s.update_umatrix()
+            return {"u": self.um.copy()}
+        elif name == "get_umatrix":
+            return {"u": None if getattr(self, "um", None) is None else self.um.copy()}
         return {}
+
+    def _schedule(self, sigmas, reset, valid):
+        """vsom_batch_schedule as tests/schedule_ref.py, oracle_loop, states it (valid None), vsom_batch_schedule_masked as
+        the same loop over _epoch_masked; a None in sigmas stands for NaN (an op list prints as Python literals)"""
+        sigmas = [float("nan") if v is None else v for v in sigmas]
+        if not sigmas:
+            return np.zeros(0, np.float32)     # "nothing is done"
+        if valid is None:
+            mses, lb = schedule_ref.oracle_loop(self.som, self.X, sigmas, reset)
+            self.lb[...] = lb
+        else:
+            valid = np.broadcast_to(np.asarray(valid) != 0, self.X.shape).copy()
+            mses = np.zeros(len(sigmas), np.float32)
+            for ep, sg in enumerate(sigmas):
+                if ep > 0 and reset:
+                    self.lb[:] = 0
+                mses[ep] = self._epoch_masked({"first": ep == 0, "sigma": sg}, valid)
+        self.mse = mses[-1]
+        self.sqres = None
+        return mses
+
+    def _online_masked(self, p, valid):
+        """tests/online_masked_ref.py, OnlineMasked.train_chunk, on this model's state"""
+        s, cfg = self.som, self.cfg
+        r = online_masked_ref.OnlineMasked(cfg["W"], cfg["H"], cfg["J"], cfg["tr"])
+        r.set_state(map=s.map, sigma=s.sigma, S=s.S, weight=s.weight, hits=s.hits)
+        start = 0.0 if p["first"] else self.run
+        self.run = r.train_chunk(self.X, valid, self.lb, p["eta"], p["sigma"], p["decay"], mse_start=start)
+        s.set_state(map=r.map, sigma=r.sigma, S=r.S, weight=r.weight, hits=r.hits)
+        self.mse = self.run
+        self.sqres = None
+        return {"mse": self.run, "lb": self.lb.copy()}
 
     def state(self):
         s = self.som
@@ -1461,13 +1557,14 @@ class GpuBackend:
         import custom_hooks
         self.capi = capi
         self.L = capi.lib()
-        cfg = CONFIGS[cfg_name]
+        cfg = config(cfg_name)
         if cfg["custom"]:
             depth, rlen = custom_hooks.shape("standard", cfg["J"])
             make = lambda: capi.Context(cfg["W"], cfg["H"], cfg["J"], capi.CUSTOM, source=custom_hooks.STANDARD,
                                         depth=depth, residual_len=rlen)
         else:
             make = lambda: vsom_amd.Context(cfg["W"], cfg["H"], cfg["J"], cfg["tr"])
+        self.make = make                   # (the ensemble profile makes each member's twin with it)
         self.ctx = make()
         # sigma profile: a second context fixed at VSOM_SIGMA_EAGER that receives every call of the walk
         # accum profile: that twin is also the sequential one -- fed from pageable memory, synchronised after every call
@@ -1596,6 +1693,30 @@ class GpuBackend:
             out["mse"] = np.float32(m.value)
         elif name == "accum_abort":
             rc = L.vsom_batch_accum_abort(h)
+        # the single-context ops of the ensemble profile
+        elif name in ("schedule", "schedule_masked"):
+            sg = np.array([np.nan if v is None else v for v in p["sigmas"]], np.float64)
+            mses = np.zeros(sg.size, np.float32)
+            dp = sg.ctypes.data_as(C.POINTER(C.c_double))
+            if name == "schedule":
+                rc = L.vsom_batch_schedule(h, dp, sg.size, int(p["reset"]), f(mses))
+            else:
+                vb = np.ascontiguousarray(a["valid"], np.uint8).copy()
+                rc = L.vsom_batch_schedule_masked(h, dp, sg.size, int(p["reset"]), vb.ctypes.data_as(C.POINTER(C.c_uint8)),
+                                                  int(vb.ndim == 1), f(mses))
+                vb[...] = 0
+            out["mses"] = mses
+        elif name == "online_masked":
+            vb = np.ascontiguousarray(a["valid"], np.uint8).copy()
+            lb, m = np.zeros(B, np.uint64), C.c_float()
+            rc = L.vsom_train_online_chunk_masked(h, p["eta"], p["sigma"], p["decay"], int(p["first"]),
+                                                  vb.ctypes.data_as(C.POINTER(C.c_uint8)), int(vb.ndim == 1), u(lb), C.byref(m))
+            vb[...] = 0
+            out.update(lb=lb, mse=np.float32(m.value))
+        elif name in ("um", "get_umatrix"):
+            um = np.zeros(self.N, np.float64)
+            rc = getattr(L, "vsom_umatrix" if name == "um" else "vsom_get_umatrix")(h, um.ctypes.data_as(C.POINTER(C.c_double)))
+            out["u"] = um
         elif name == "update_mode":
             rc = L.vsom_set_update_mode(h, p["mode"])
         elif name == "similarity_masked":
@@ -1746,4 +1867,1068 @@ class GpuBackend:
 
 def replay(ops):
     """rerun a printed op list against the real library"""
+    if ops[0][1].get("profile") == "ensemble":
+        return run_ensemble_walk(ops, EnsGpuBackend)
     return run_walk(ops, GpuBackend)
+
+
+# ---- the ensemble profile ----------------------------------------------------------------------------------------------
+# The nine calls of include/vsom_hip.h, "ensembles", walked with the single-context calls on their members between them.
+# An op is ("ens_*", params) for an ensemble call -- params["e"] names the ensemble, per-member values are lists in the
+# order given to create --, ("m", {"k": member, "op": (name, params)}) for a single-context call on one member (Model.apply
+# and GpuBackend._call1 serve it), ("ens_create", {"e", "order"}), ("ens_destroy", {"e"}) or ("sigma_stats", {"k", "expect"}).
+# The model (EnsModel) keeps one Model per member: an accepted ensemble call is the single call on every member in index
+# order, a refused one names the member the header says and changes nothing.  generate_ensemble's docstring lists the runs.
+ENS_CALLS = ("ens_upload", "ens_online", "ens_online_masked", "ens_epoch", "ens_epoch_masked", "ens_schedule",
+             "ens_schedule_masked", "ens_bmu", "ens_umatrix")
+ENS_TRAIN = ENS_CALLS[1:7]
+ENS_NEW_OPS = set(ENS_CALLS) | {"ens_create", "ens_destroy", "m", "sigma_stats", "schedule", "schedule_masked",
+                                "online_masked", "um", "get_umatrix"}
+ENS_MASKABLE = ("A", "A2", "B", "D")     # the members the masked calls name (the model's masked searches are pure Python)
+ENS_DRAWS = 10                           # random draws of an ensemble walk, around its runs
+ENS_RUNS = tuple(range(1, 10))
+ENS_REFUSALS = ("null", "no_chunk", "decay", "masked_clr", "non_strict", "offset", "member_online_masked",
+                "member_accum_begin")                              # run 5, every configuration
+ENS_REFUSALS_OWN = ("masked_custom", "umatrix_custom")             # ... those that need the custom member F
+
+
+def batch_tiny(cfg, B):
+    """vsom_tiny_applies (csrc/vsom_tiny.hip:52): the batch epoch of this chunk takes the one-launch kernel --
+    0 < B <= 256, N * part_len <= 4096 (part_len: D, or D / 2 for CLR), B * N <= 16384, N * part_len * B <= 262144; never
+    a custom context."""
+    N, D = cfg["W"] * cfg["H"], po.length(cfg["tr"], cfg["J"])
+    chains = N * (D // 2 if cfg["tr"] == po.CLR else D)
+    return not cfg["custom"] and 0 < B <= 256 and chains <= 4096 and B * N <= 16384 and chains * B <= 262144
+
+
+def masked_batch_tiny(cfg, B, strict=True):
+    """vsom_masked_tiny_applies (csrc/vsom_tiny_masked.hip:114, vsom_tiny_masked_applies): batch_tiny on a Standard / Median
+    context in the strict update mode.  (Its LDS bound, 64 KiB, holds for every member of ENS_MEMBERS: at most 256 rows of
+    24 bytes, a table of at most 23 x 23 floats, J * ceil(B / 32) words, and the rows only when B * J <= 10240.)"""
+    return batch_tiny(cfg, B) and cfg["tr"] != po.CLR and strict
+
+
+def online_tiny(cfg, B, sigma, mode=BMU_AUTO):
+    """vsom_online_masked_tiny_applies as include/vsom_hip.h:933 states it (csrc/vsom_online_tiny_masked.hip:53), which is
+    the unmasked one-launch chunk's rule too: Standard / Median, not custom, N <= 1024, N * D <= 4096, D <= 512,
+    B <= 4096, sigma no NaN, the search mode VSOM_BMU_AUTO.  (The LDS need of every member here is within 96 KiB.)"""
+    N, D = cfg["W"] * cfg["H"], po.length(cfg["tr"], cfg["J"])
+    return cfg["tr"] != po.CLR and not cfg["custom"] and N <= 1024 and N * D <= 4096 and D <= 512 and 0 < B <= 4096 and \
+        sigma == sigma and mode == BMU_AUTO
+
+
+def ens_mask(spec, X):
+    """the validity bytes a masked call gives a member whose rows are X: accum_mask's engineered mask with every late
+    column active -- the border columns, one column valid in no row, spec["full"]: one row without a valid column"""
+    return np.ascontiguousarray(accum_mask(spec["seed"], 2, spec["form"], spec.get("full", False), X), np.uint8)
+
+
+def ens_poisoned(spec, X):
+    """X with NaN / +-inf under every invalid entry of ens_mask(spec, X), and nowhere else"""
+    return poisoned_rows(X, spec["seed"], 2, spec["form"], spec.get("full", False))
+
+
+def _nan(v):
+    return float("nan") if v is None else v
+
+
+class _EnsGen:
+    def __init__(self, cfg_name, seed):
+        self.ec = ENS_CONFIGS[cfg_name]
+        self.all = list(self.ec["members"])
+        self.rs = np.random.RandomState(seed)
+        self.sizes = {n: [b for b, _ in ENS_MEMBERS[n]["chunks"]] for n in self.all}
+        self.B = {n: None for n in self.all}
+        self.chain = {n: False for n in self.all}
+        self.ens = {}
+        self.uid = 0
+        self.ops = []
+
+    def r(self, n):
+        return int(self.rs.randint(n))
+
+    def sigma(self):
+        return float(self.rs.choice([0.7, 1.0, 2.5, 6.0]))
+
+    def emit(self, name, **p):
+        self.ops.append((name, p))
+
+    def m(self, k, name, **p):
+        self.ops.append(("m", {"k": k, "op": (name, p)}))
+        if name == "upload":
+            self.B[k] = self.sizes[k][p["chunk"]]
+        if name == "online":
+            self.chain[k] = True
+        elif name in ("epoch", "epoch_async", "schedule", "schedule_masked", "online_masked") or name in ACCUM_OPS:
+            self.chain[k] = False
+
+    # ---- ensemble calls ----
+    def small(self, n):
+        """a chunk of member n for a random draw: never E's 1100 rows nor G's 300 (the model's dearest: once per walk)"""
+        return self.r(2 if n == "E" else (1 if n == "G" else len(self.sizes[n])))
+
+    def upload(self, e=0, pick=None, wait=1, poison=None, share=None, bad=None):
+        """vsom_ensemble_upload_chunks: pick[n] the chunk of member n (else drawn), poison[n] the masked call its rows are
+        made for, share = (n, rows): A2 names the first `rows` rows of A's range (equal offsets)"""
+        rows = {}
+        for n in self.ens[e]:
+            rows[n] = {"chunk": int((pick or {}).get(n, self.small(n)))}
+        if share and "A" in rows and "A2" in rows:
+            rows["A2"] = {"share": "A", "n": int(min(share, self.sizes["A"][rows["A"]["chunk"]]))}
+        p = dict(e=e, uid=self.uid, wait=int(wait), rows=rows)
+        self.uid += 1
+        if poison:
+            p["poison"] = {n: s for n, s in poison.items() if n in rows}
+        if bad:
+            p["bad"] = bad
+        self.emit("ens_upload", **p)
+        if not bad:
+            for n, s in rows.items():
+                self.B[n] = s["n"] if "share" in s else self.sizes[n][s["chunk"]]
+
+    def specs(self, e, names=None, full=None):
+        """a mask per masked member: both forms, `full` gets the row without a valid column; the others stay plain
+        (valid_host[k] = NULL)"""
+        names = [n for n in self.ens[e] if n in (names or ENS_MASKABLE)]
+        out = {}
+        for i, n in enumerate(names):
+            out[n] = {"seed": self.r(1 << 30), "form": ["rows", "one_mask"][(i + self.r(2)) % 2 if i else 0]}
+            if n == full:
+                out[n]["form"] = "rows"
+                out[n]["full"] = True
+        return out
+
+    def per(self, e, f):
+        return [f() for _ in self.ens[e]]
+
+    def train(self, kind, e=0, masks=None, first=True, sigmas=None, reset=None, bad=None, must_refuse=None):
+        K = len(self.ens[e])
+        p = dict(e=e)
+        if kind in ("ens_epoch", "ens_epoch_masked"):
+            p.update(sigma=self.per(e, self.sigma), first=bool(first))
+        elif kind in ("ens_schedule", "ens_schedule_masked"):
+            p.update(sigmas=sigmas if sigmas is not None else [[self.sigma() for _ in range(1 + self.r(2))] for _ in range(K)],
+                     reset=bool(self.r(2) if reset is None else reset))
+        else:
+            p.update(eta=self.per(e, lambda: float(self.rs.choice([0.05, 0.2]))), sigma=self.per(e, self.sigma),
+                     decay=self.per(e, lambda: self.r(2)), first=bool(first))
+        if kind.endswith("_masked"):
+            p["masks"] = masks if masks is not None else {}
+        if kind == "ens_online_masked":
+            # (the model's masked chunk is pure Python: on more than 40 rows the local walk, sigma <= 1, not the full scan)
+            # (and D's 512 columns on 3 rows only)
+            p["masks"] = {n: s for n, s in p["masks"].items() if n != "D" or (self.B[n] or 0) <= 40}
+            for k, n in enumerate(self.ens[e]):
+                if n in p["masks"]:          # (the full scan, sigma > 1, with a window of a few nodes)
+                    p["sigma"][k] = [0.7, 1.0 if (self.B[n] or 0) > 40 else 1.5][self.r(2)]
+        if bad:
+            p["bad"] = bad
+        if must_refuse:
+            p["must_refuse"] = must_refuse
+        self.emit(kind, **p)
+        if bad or must_refuse:
+            return
+        for n in self.ens[e]:
+            if kind in ("ens_schedule", "ens_schedule_masked") and not p["sigmas"][self.ens[e].index(n)]:
+                continue
+            self.chain[n] = kind in ("ens_online", "ens_online_masked")
+
+    def can_chain(self, e):
+        return all(self.chain[n] for n in self.ens[e])
+
+    def masked_block(self, kinds, e=0, pick=None, names=None, full=None, first=True, wait=1):
+        """rows poisoned for the masked members' masks, the masked calls, clean rows again"""
+        masks = self.specs(e, names, full)
+        self.upload(e, pick, wait=wait, poison=masks)
+        for kind in kinds:
+            self.train(kind, e, masks=masks, first=first)
+        return masks
+
+    # ---- random draws ----
+    def member_op(self):
+        n = self.all[self.r(len(self.all))]
+        cfg = ENS_MEMBERS[n]
+        plain = not cfg["custom"] and cfg["tr"] != po.CLR
+        what = ["upload", "prefetch", "set_state", "get_state", "set_last_bmu", "get_last_bmu", "get_sqres", "get_mse",
+                "epoch", "online", "bmu", "bmu_masked", "um", "bmu_mode", "schedule", "schedule_masked"][self.r(16)]
+        if what == "upload":
+            self.m(n, "upload", chunk=self.small(n), asynchronous=bool(self.r(2)))
+        elif what == "prefetch":
+            c = self.small(n)
+            self.m(n, "prefetch", chunk=c, src=["pinned", "pageable"][self.r(2)])
+            self.m(n, "commit")
+            self.B[n] = self.sizes[n][c]
+        elif what == "set_state":
+            self.m(n, "set_state", seed=self.r(1 << 30), parts=["map_only", "weight_only", "msw"][self.r(3)])
+        elif what == "epoch":
+            self.m(n, "epoch", sigma=self.sigma(), first=bool(self.r(2)))
+        elif what == "online":
+            first = True if not self.chain[n] else bool(self.r(2))
+            self.m(n, "online", eta=0.1, sigma=self.sigma(), decay=self.r(2), first=first, mode=["mse", "fetch", "null"][self.r(3)])
+        elif what == "set_last_bmu":
+            self.m(n, "set_last_bmu", seed=self.r(1 << 30))
+        elif what == "bmu_masked":
+            if plain and n in ENS_MASKABLE:
+                k = 1 + self.r(min(32, self.B[n]))
+                r0 = self.r(self.B[n] - k + 1)
+                self.m(n, "bmu_masked", min_hits=self.r(2), rule=self.r(2), seed=self.r(1 << 30), r0=r0, r1=r0 + k)
+        elif what == "um":
+            if not cfg["custom"]:
+                self.m(n, "um")
+                self.m(n, "get_umatrix")
+        elif what == "bmu_mode":
+            if not cfg["custom"]:
+                self.m(n, "bmu_mode", mode=self.r(3))
+                self.m(n, "online", eta=0.1, sigma=2.5, decay=0, first=True, mode="mse")
+                self.m(n, "bmu_mode", mode=BMU_AUTO)
+        elif what == "schedule":
+            if n not in ("E", "G"):
+                self.m(n, "schedule", sigmas=[self.sigma() for _ in range(self.r(3))], reset=bool(self.r(2)))
+        elif what == "schedule_masked":
+            if n in ENS_MASKABLE:
+                self.m(n, "schedule_masked", sigmas=[self.sigma()], reset=True, seed=self.r(1 << 30),
+                       form=["rows", "one_mask"][self.r(2)])
+        else:
+            self.m(n, what)
+
+    def random_op(self, e=0):
+        what = ["epoch", "schedule", "online", "bmu", "umatrix", "upload", "masked", "member", "member", "member"][self.r(10)]
+        if what == "epoch":
+            self.train("ens_epoch", e, first=bool(self.r(2)))
+        elif what == "schedule":
+            self.train("ens_schedule", e)
+        elif what == "online":
+            self.train("ens_online", e, first=True if not self.can_chain(e) else bool(self.r(2)))
+        elif what == "bmu":
+            self.emit("ens_bmu", e=e)
+        elif what == "umatrix":
+            if "F" not in self.ens[e]:
+                self.emit("ens_umatrix", e=e)
+                n = self.ens[e][self.r(len(self.ens[e]))]
+                self.m(n, "get_umatrix")
+        elif what == "upload":
+            self.upload(e, wait=self.r(2), share=[None, 20, 160][self.r(3)])
+        elif what == "masked":
+            kind = ["ens_epoch_masked", "ens_schedule_masked", "ens_online_masked"][self.r(3)]
+            two = [n for n in self.ens[e] if n in ENS_MASKABLE]
+            self.rs.shuffle(two)
+            self.masked_block([kind], e, names=two[:2], pick={n: 0 for n in two}, first=True)
+            self.upload(e)
+        else:
+            self.member_op()
+
+    # ---- the runs ----
+    def run(self, run):
+        own = not self.ec["one_stream"]
+        e = 0
+        self.upload(e, wait=1)               # (every run starts from clean rows)
+        self.emit("run", id=run)
+        if run == 1:
+            pick = {"A": 1, "A2": 0, "B": 1, "C": 0, "D": 1, "E": 0, "F": 0, "G": 0}
+            masks = self.specs(e, full="A")
+            self.upload(e, pick, wait=0, poison=masks)
+            self.train("ens_epoch_masked", e, masks=masks, first=True)
+            self.emit("ens_bmu", e=e)
+            if not own:
+                self.emit("ens_umatrix", e=e)
+            self.train("ens_schedule_masked", e, masks=masks,       # (one masked epoch of the model on the long chunks)
+                       sigmas=[[self.sigma()] * (1 if n in ("A", "B") else 2) for n in self.ens[e]])
+            self.train("ens_online_masked", e, masks=masks, first=True)
+            big = {"A": 3, "A2": 3, "B": 2, "C": 1, "D": 1, "E": 2, "F": 1, "G": 1}
+            self.upload(e, big, wait=0)      # more floats than the first: the raw buffer grows behind the stagings
+            self.train("ens_epoch", e, first=True)
+        elif run == 2:
+            self.train("ens_online", e, first=True)
+            x, y = "A", "B"
+            self.m(x, "upload", chunk=self.r(2), asynchronous=False)
+            self.m(y, "upload", chunk=0, asynchronous=bool(self.r(2)))
+            self.m(x, "online", eta=0.1, sigma=self.sigma(), decay=self.r(2), first=False, mode="mse")
+            self.train("ens_online_masked", e, masks=self.specs(e, names=(x, y, "D")), first=False)
+            for n in self.ens[e]:
+                self.m(n, "get_mse")
+        elif run == 3:
+            steps = [{"A": 1, "B": 1}, {"A": 2, "B": 2}, {"A": 1, "B": 3}]
+            for i, pick in enumerate([{"A": 1, "B": 3}, {"A": 2, "B": 4}, {"A": 1, "B": 3}]):
+                pick = dict(pick, A2=0, D=1, E=0, G=0)
+                masks = self.specs(e, names=("A", "B"))
+                self.upload(e, pick, poison=masks)
+                self.train("ens_epoch_masked", e, masks=masks, first=i == 0)
+                if i < 2:
+                    self.train("ens_schedule_masked", e, masks=masks, reset=False,
+                               sigmas=[[self.sigma()] if n != "E" or i else [2.5, None] for n in self.ens[e]])
+                    if i == 0:               # (a plain member's NaN sigma: its map is NaN now)
+                        self.m("E", "get_state")
+                        self.m("E", "set_state", seed=self.r(1 << 30), parts="all")
+                self.train("ens_online_masked", e, masks=masks, first=True)
+            for i, pick in enumerate(steps):
+                self.upload(e, dict(pick, E=0, G=0), share=[160, None, 20][i])
+                self.train("ens_epoch", e, first=i == 0)
+                idle = self.ens[e][self.r(len(self.ens[e]))]
+                sig = [[self.sigma() for _ in range(1 + self.r(2))] if n != idle else [] for n in self.ens[e]]
+                if i == 1 and idle != "A":
+                    sig[self.ens[e].index("A")] = [2.5, None]
+                self.train("ens_schedule", e, sigmas=sig, reset=bool(i % 2))
+                for what in ("get_last_bmu", "get_sqres", "get_mse"):    # epochs[k] = 0: not touched
+                    self.m(idle, what)
+                if i == 1 and idle != "A":
+                    self.m("A", "get_state")
+                    self.m("A", "set_state", seed=self.r(1 << 30), parts="all")
+                self.train("ens_online", e, first=True)
+            self.m("A", "bmu_mode", mode=BMU_EXACT)
+            self.train("ens_online", e, first=False)
+            self.train("ens_online_masked", e, masks=self.specs(e, names=("A", "B")), first=True)
+            self.m("A", "bmu_mode", mode=BMU_AUTO)
+            self.train("ens_online", e, first=True)
+        elif run == 4:
+            k = "G" if own else "E"
+            ahead = k if stages_ahead(ENS_MEMBERS[k]) else None
+            self.m(k, "upload", chunk=0, asynchronous=False)
+            self.m(k, "epoch_async", sigma=self.sigma(), first=True)
+            self.m(k, "prefetch", chunk=0, src="pinned")
+            if ahead:                        # every row-reading call MUST be refused, naming the member
+                for kind in ENS_TRAIN:
+                    self.train(kind, e, masks={}, must_refuse=ahead)
+                self.emit("ens_bmu", e=e, must_refuse=ahead)
+            else:                            # (nothing is staged ahead: the calls take the old chunk)
+                self.emit("ens_bmu", e=e)
+            self.upload(e, {k: 0})           # accepted, as the header says
+            self.m(k, "commit")
+            self.train("ens_epoch", e, first=True)
+            self.emit("ens_bmu", e=e)
+        elif run == 5:
+            K = len(self.ens[e])
+            self.train("ens_epoch", e, bad="null")
+            self.train("ens_online_masked", e, bad="null_valid")
+            self.train("ens_schedule", e, bad="null_epochs")
+            self.train("ens_schedule", e, bad="null_sigma", sigmas=[[1.0]] * K)
+            self.upload(e, bad="null")
+            self.upload(e, bad="offset")
+            self.train("ens_online", e, bad="decay")
+            c = {"C": {"seed": 5, "form": "rows"}}
+            self.train("ens_epoch_masked", e, masks=c)
+            self.train("ens_schedule_masked", e, masks=dict(c, A={"seed": 6, "form": "one_mask"}))
+            self.train("ens_online_masked", e, masks=c)
+            if own:
+                f = {"F": {"seed": 5, "form": "rows"}}
+                self.train("ens_epoch_masked", e, masks=f)
+                self.train("ens_online_masked", e, masks=f)
+                self.emit("ens_umatrix", e=e)
+            a = {"A": {"seed": 7, "form": "rows"}}
+            self.m("A", "update_mode", mode=UPDATE_FMA)
+            self.train("ens_epoch_masked", e, masks=a)
+            self.train("ens_schedule_masked", e, masks=a)
+            self.m("A", "update_mode", mode=UPDATE_STRICT)
+            self.m("B", "online_masked", eta=0.1, sigma=2.5, decay=0, first=True, seed=3, form="rows")
+            self.m("A", "accum_begin", sigma=2.5, first=True, total=self.B["A"])
+        elif run == 6:
+            self.m("A", "set_state", seed=self.r(1 << 30), parts="map_only")
+            self.m("B", "set_state", seed=self.r(1 << 30), parts="weight_only")
+            self.m("E", "set_last_bmu", seed=self.r(1 << 30))
+            self.m("A", "set_last_bmu", seed=self.r(1 << 30))
+            self.train("ens_epoch", e, first=False)
+            self.m("B", "set_last_bmu", seed=self.r(1 << 30))
+            self.train("ens_schedule_masked", e, masks=self.specs(e, names=("B",)), reset=False,
+                       sigmas=[[self.sigma(), self.sigma()] for _ in self.ens[e]])
+            self.m("B", "get_last_bmu")
+        elif run == 7:
+            old = list(self.ens[0])
+            self.emit("ens_destroy", e=0)
+            del self.ens[0]
+            for n in old[:3]:
+                self.m(n, "epoch", sigma=self.sigma(), first=True)
+            if own:                          # a former member stays eager: the deferred count does not move
+                self.m("G", "epoch_async", sigma=self.sigma(), first=True)
+                self.emit("sigma_stats", k="G", expect=[1, 0, 1, 0])
+            sub = [n for n in old if n != ("F" if own else "C")]
+            sub = [sub[i] for i in self.rs.permutation(len(sub))]
+            self.emit("ens_create", e=0, order=sub)
+            self.ens[0] = sub
+            self.emit("ens_umatrix", e=0)
+            self.m(sub[0], "get_umatrix")
+            self.ens[1] = [sub[2], sub[0], old[-1] if old[-1] not in (sub[0], sub[2]) else sub[1]]
+            self.emit("ens_create", e=1, order=self.ens[1])
+            for _ in range(2):
+                self.train("ens_epoch", 0, first=bool(self.r(2)))
+                self.train("ens_online", 1, first=True)
+                self.emit("ens_bmu", e=0)
+                self.train("ens_schedule", 1)
+            self.upload(1)
+            self.train("ens_epoch", 1, first=True)
+            self.emit("ens_destroy", e=1)
+            del self.ens[1]
+            self.train("ens_epoch", 0, first=False)
+            self.emit("ens_umatrix", e=0)
+            self.m(sub[1], "get_umatrix")
+        self.emit("run_end", id=run)
+        self.m(self.all[self.r(len(self.all))], "get_state")
+
+
+def generate_ensemble(cfg_name, seed, n_ops=ENS_DRAWS):
+    """The ensemble profile: n_ops random draws (ensemble calls, masked blocks, single-context calls on members) around
+    these runs, each between ("run", id) / ("run_end", id) markers.  Runs 8, 9 and the refusal for a member without a chunk
+    open the walk (they need contexts that have not joined yet); runs 1-6 follow in a drawn order, run 7 ends the walk.
+      1  back to back: upload_chunks(wait = 0) of poisoned rows from pinned memory, batch_epoch_masked, bmu_batch, umatrix
+         (ens_shared), batch_schedule_masked, train_online_chunk_masked; a second, larger upload_chunks(wait = 0) -- the raw
+         buffer grows behind the stagings --, batch_epoch.  Six descriptor sizes through two slots.
+      2  the running MSE: ensemble online (first_chunk = 1), new rows for A and B by their own uploads, a single online chunk
+         with first = 0 on A, the ensemble masked online with first_chunk = 0; every member's vsom_get_mse
+      3  path borders between two calls of each kind: A 160 -> 170 -> 160 rows, B 121 -> 122 -> 121 (masked calls) and
+         151 -> 152 -> 121 (plain calls); A's search mode EXACT, then AUTO; one schedule with a NaN sigma; a member with
+         epochs[k] = 0, whose lastBMU, sqres and MSE word are read
+      4  the stage-ahead: an asynchronous epoch and a prefetch on G (ens_own; E on ens_shared, where nothing stages ahead);
+         where stages_ahead holds every row-reading ensemble call MUST be refused naming the member; upload_chunks is
+         accepted; after the commit the calls are accepted
+      5  every refusal the header lists, and vsom_train_online_chunk_masked / vsom_batch_accum_begin on a member
+      6  vsom_set_state(map) on A, (weight) on B, vsom_set_last_bmu on A and E, batch_epoch(is_first = 0); vsom_set_last_bmu
+         on B, batch_schedule_masked(reset_bmu = 0)
+      7  destroy, single epochs on the former members, create over a permuted subset (ens_own without F: umatrix is now
+         accepted), a second ensemble over an overlapping subset, calls alternating between the two
+      8  G (ens_own): a whole-map epoch under VSOM_SIGMA_LAZY leaves its sigmaMap pending before the first create, which
+         must materialise it; vsom_sigma_stats' deferred count never moves again
+      9  an accumulated epoch opened on A before it joins: begin, chunk, create, an ensemble batch_epoch, chunk, end"""
+    g = _EnsGen(cfg_name, seed)
+    g.ops.append(("config", {"name": cfg_name, "seed": seed, "profile": "ensemble"}))
+    own = "G" in g.all
+    for n in g.all:
+        g.m(n, "set_state", seed=seed + ENS_MEMBERS[n].get("map_seed", 0), parts="init")
+    if own:
+        g.emit("run", id=8)
+        g.m("G", "sigma_mode", mode="lazy")
+        g.m("G", "upload", chunk=0, asynchronous=False)
+        g.m("G", "epoch", sigma=g.sigma(), first=True)
+        g.emit("sigma_stats", k="G", expect=[1, 0, 0, 1])
+    for n in g.all:
+        if n not in ("C", "G"):
+            g.m(n, "upload", chunk=0, asynchronous=False)
+    # (no member yet: the masked online chunk is accepted, on the member's context and on its twin)
+    g.m("B", "online_masked", eta=0.1, sigma=1.5, decay=1, first=True, seed=g.r(1 << 30), form="rows")
+    g.emit("run", id=9)
+    g.m("A", "accum_begin", sigma=g.sigma(), first=True, total=2 * g.sizes["A"][0])
+    g.m("A", "accum_chunk")
+    g.emit("ens_create", e=0, order=list(g.all))
+    g.ens[0] = list(g.all)
+    if own:
+        g.emit("sigma_stats", k="G", expect=[1, 0, 1, 0])
+        g.m("G", "get_state")
+        g.emit("run_end", id=8)
+    g.train("ens_epoch", 0)                  # C has no chunk: refused
+    g.emit("ens_bmu", e=0)
+    g.upload(0, {n: 0 for n in g.all})
+    g.train("ens_epoch", 0, first=True)
+    g.m("A", "accum_chunk")
+    g.m("A", "accum_end")
+    g.emit("run_end", id=9)
+    g.m("A", "get_state")
+    slots = sorted(g.rs.choice(np.arange(0, n_ops), 6, replace=False)) if n_ops >= 6 else [0] * 6
+    runs = [int(r) for r in g.rs.permutation(6) + 1]
+    for k in range(n_ops):
+        while slots and k >= slots[0]:
+            slots.pop(0)
+            g.run(runs.pop(0))
+        g.random_op()
+    while runs:
+        g.run(runs.pop(0))
+    g.run(7)
+    if own:
+        g.m("G", "epoch", sigma=g.sigma(), first=True)
+        g.emit("sigma_stats", k="G", expect=[1, 0, 1, 0])
+    for n in g.all:
+        g.m(n, "get_state")
+    return g.ops
+
+
+class EnsModel:
+    """one Model per member, the ensembles' member orders, and who has ever joined one"""
+
+    def __init__(self, cfg_name, seed):
+        self.cfg_name = cfg_name
+        self.names = list(ENS_CONFIGS[cfg_name]["members"])
+        self.m = {n: Model(n, seed, 1, "ensemble") for n in self.names}
+        for mod in self.m.values():
+            mod.bmu_mode = BMU_AUTO
+            mod.um = None
+        self.ens = {}
+        self.joined = set()
+
+    def close(self):
+        for mod in self.m.values():
+            mod.close()
+
+    def layout(self, p):
+        """vsom_ensemble_upload_chunks' arguments: each member's rows, the host buffer (a gap of 3 floats between two
+        ranges), offsets and row counts in member order"""
+        order = self.ens[p["e"]]
+        X, off, parts, at = {}, {}, [], 0
+        for n in order:
+            s = p["rows"][n]
+            if "share" in s:
+                continue
+            x = self.m[n].chunks[s["chunk"]]
+            if n in p.get("poison", {}):
+                x = ens_poisoned(p["poison"][n], x)
+            X[n], off[n] = x, at
+            parts.append(x.reshape(-1))
+            parts.append(np.full(3, -7.0, np.float32))
+            at += x.size + 3
+        for n in order:
+            s = p["rows"][n]
+            if "share" in s:
+                X[n], off[n] = X[s["share"]][:s["n"]], off[s["share"]]
+        buf = np.ascontiguousarray(np.concatenate(parts), np.float32)
+        n_floats = buf.size - (4 if p.get("bad") == "offset" else 0)
+        return {"X": X, "buf": buf, "n_floats": n_floats, "off": [off[n] for n in order],
+                "B": [X[n].shape[0] for n in order]}
+
+    def materialize(self, op):
+        name, p = op
+        if name == "m":
+            return materialize(p["op"], self.m[p["k"]])
+        if name == "ens_upload":
+            return self.layout(p)
+        if "masks" in p:
+            return {"valid": {n: (ens_mask(p["masks"][n], self.m[n].X) if n in p["masks"] and self.m[n].X is not None
+                                  else (np.ones(1, np.uint8) if n in p["masks"] else None)) for n in self.ens[p["e"]]}}
+        return {}
+
+    def path(self, op, n, k):
+        """whether member n (index k) of an accepted train call takes its one-launch kernel, by the restated predicates"""
+        name, p = op
+        mod = self.m[n]
+        cfg, B = mod.cfg, mod.B
+        masked = n in p.get("masks", {})
+        if name in ("ens_epoch", "ens_epoch_masked"):
+            return masked_batch_tiny(cfg, B, mod.update_mode == UPDATE_STRICT) if masked else batch_tiny(cfg, B)
+        if name in ("ens_schedule", "ens_schedule_masked"):
+            sg = [_nan(v) for v in p["sigmas"][k]]
+            if not sg or not all(np.isfinite(sg)):
+                return False
+            return masked_batch_tiny(cfg, B, mod.update_mode == UPDATE_STRICT) if masked else batch_tiny(cfg, B)
+        return online_tiny(cfg, B, p["sigma"][k], mod.bmu_mode)
+
+    def ens_refusal(self, op, a):
+        """None where the header accepts the ensemble call, else (member index or None, words of the message, the entry of
+        run 5's list), in the order csrc/vsom_ensemble.hip checks; a chunk staged ahead is the backend's to know"""
+        name, p = op
+        bad = p.get("bad")
+        order = self.ens[p["e"]]
+        if bad in ("null", "null_epochs", "null_valid"):
+            return None, {"null": "null", "null_epochs": "null epochs array", "null_valid": "null valid_host array"}[bad], "null"
+        for k, n in enumerate(order):
+            mod = self.m[n]
+            cfg = mod.cfg
+            masked = n in p.get("masks", {})
+            if name == "ens_upload":
+                if a["off"][k] + a["B"][k] * cfg["J"] > a["n_floats"]:
+                    return k, "rows beyond n_floats", "offset"
+                continue
+            if name == "ens_umatrix":
+                if cfg["custom"]:
+                    return k, "custom-transformation context", "umatrix_custom"
+                continue
+            if name in ("ens_schedule", "ens_schedule_masked"):
+                if not p["sigmas"][k]:
+                    continue                 # not touched
+                if bad == "null_sigma" and k == len(order) - 1:
+                    return k, "null sigma or mse_out", "null"
+            if name in ("ens_online", "ens_online_masked"):
+                if bad == "decay" and k == 1:
+                    return k, "Exponential or InverseProportional", "decay"
+                if masked and cfg["custom"]:
+                    return k, "custom contexts are not supported", "masked_custom"
+                if masked and cfg["tr"] == po.CLR:
+                    return k, "CLR contexts are not supported", "masked_clr"
+            if mod.X is None:
+                return k, "no chunk loaded", "no_chunk"
+            if name in ("ens_epoch_masked", "ens_schedule_masked") and masked:
+                if cfg["custom"]:
+                    return k, "custom context", "masked_custom"
+                if cfg["tr"] == po.CLR:
+                    return k, "CLR contexts are not supported", "masked_clr"
+                if mod.update_mode != UPDATE_STRICT:
+                    return k, "strict update mode", "non_strict"
+        return None
+
+    def member_refusal(self, n, op):
+        """what a single-context call on member n must be refused for: (rc, words, label) or None"""
+        name, p = op
+        mod = self.m[n]
+        cfg = mod.cfg
+        if cfg["custom"] and (name in CUSTOM_REFUSED or name in ("schedule_masked", "online_masked", "um", "update_mode")):
+            return VSOM_ERR_INVALID, "", None
+        if cfg["tr"] == po.CLR and (name in CLR_REFUSED or name in ("schedule_masked", "online_masked")):
+            return VSOM_ERR_INVALID, "CLR", None
+        if name == "online_masked" and n in self.joined:
+            return VSOM_ERR_INVALID, "joined a group or an ensemble", "member_online_masked"
+        if name in ACCUM_OPS:
+            why = mod.accum_refusal(op)
+            if name == "accum_begin" and n in self.joined and why in (None, "already open"):
+                return VSOM_ERR_INVALID, "joined a group or an ensemble", "member_accum_begin"
+            if why is not None:
+                return VSOM_ERR_INVALID, why, None
+        return None
+
+    def apply_member(self, n, op, a):
+        mod = self.m[n]
+        if op[0] == "bmu_mode":
+            mod.bmu_mode = op[1]["mode"]
+        return mod.apply(op, a)
+
+    def apply(self, op, a):
+        """an accepted ensemble call: the single call on every member in index order; outputs keyed "<member>.<name>" """
+        name, p = op
+        out = {}
+        if name == "ens_create":
+            self.ens[p["e"]] = list(p["order"])
+            self.joined |= set(p["order"])
+            return out
+        if name == "ens_destroy":
+            del self.ens[p["e"]]
+            return out
+        for k, n in enumerate(self.ens[p["e"]]):
+            mod = self.m[n]
+            valid = a.get("valid", {}).get(n)
+            if name == "ens_upload":
+                single, arg = ("upload", {}), {"X": a["X"][n]}
+            elif name in ("ens_epoch", "ens_epoch_masked"):
+                q = {"sigma": p["sigma"][k], "first": p["first"]}
+                single, arg = ("epoch", q) if valid is None else ("epoch_masked", q), {"valid": valid}
+                if valid is not None:
+                    arg = {"valid": np.broadcast_to(valid, mod.X.shape).copy()}
+            elif name in ("ens_schedule", "ens_schedule_masked"):
+                q = {"sigmas": p["sigmas"][k], "reset": p["reset"]}
+                single, arg = ("schedule", q) if valid is None else ("schedule_masked", q), {"valid": valid}
+                if not q["sigmas"]:
+                    continue                 # "a member with epochs[k] = 0 is not touched"
+            elif name in ("ens_online", "ens_online_masked"):
+                q = {"eta": p["eta"][k], "sigma": p["sigma"][k], "decay": p["decay"][k], "first": p["first"], "mode": "fetch"}
+                single, arg = ("online", q) if valid is None else ("online_masked", q), {"valid": valid}
+            elif name == "ens_bmu":
+                single, arg = ("bmu", {}), {}
+            else:
+                single, arg = ("um", {}), {}
+            for key, v in mod.apply(single, arg).items():
+                out[f"{n}.{key}"] = v
+        return out
+
+
+def ens_conditions(cfg_name, stats, gpu=False):
+    """what a walk of the ensemble profile must have met, from run_ensemble_walk's counts, so that it cannot pass vacuously"""
+    own = not ENS_CONFIGS[cfg_name]["one_stream"]
+    assert stats["ops"] >= 100, stats
+    assert all(stats["accepted"][c] >= 2 for c in ENS_CALLS), stats["accepted"]
+    # in each kind of train call: one call at least with two launched members and one on its ordinary path
+    assert all(stats["mixed"][c] >= 1 for c in ENS_TRAIN), stats["mixed"]
+    for label in ENS_REFUSALS + (ENS_REFUSALS_OWN if own else ()):
+        assert stats["refusals"].get(label, 0) >= 1, (label, stats["refusals"])
+    # run 4: G's chunk is staged ahead (ens_own): the six train calls and bmu_batch were refused, naming it
+    assert stats["staged"] == (7 if own else 0), stats
+    if gpu:
+        assert stats["nowait"] >= 2 and stats["applies"] >= 10, stats
+
+
+def ens_difference(got, exp):
+    """first_difference on the values' own width: the U-matrix is a double"""
+    if exp is not None and np.asarray(exp).dtype == np.float64 and np.asarray(exp).ndim:
+        return first_difference_exact(np.asarray(got, np.float64), np.asarray(exp))
+    return first_difference(got, exp)
+
+
+def run_ensemble_walk(ops, make_backend):
+    """run_walk for the ensemble profile: the backend make_backend(cfg_name, model) holds the members (the real one: also a
+    twin of each that never joins) and the ensembles.  Returns counts: accepted calls per ensemble call, per kind of train
+    call the calls with at least two launched members and one on its ordinary path, the refusals of run 5 by entry, the
+    stage-ahead refusals, the wait = 0 uploads followed by a call with no host wait between."""
+    name0, cfg = ops[0]
+    assert name0 == "config" and cfg["profile"] == "ensemble", ops[0]
+    em = EnsModel(cfg["name"], cfg["seed"])
+    em.ops = ops
+    be = make_backend(cfg["name"], em)
+    stats = {"ops": 0, "accepted": {c: 0 for c in ENS_CALLS}, "mixed": {c: 0 for c in ENS_TRAIN}, "refusals": {},
+             "staged": 0, "nowait": 0, "applies": 0}
+    done = [ops[0]]
+
+    def fail(msg):
+        raise WalkFailure(f"call-sequence walk {cfg['name']} seed {cfg['seed']}: {msg}\n"
+                          f"replay(ops) with ops = {done!r}")
+
+    def check_outputs(what, got, exp):
+        for k, e in exp.items():
+            d = ens_difference(got.get(k), e)
+            if d:
+                fail(f"{what}: output {k!r} differs from the oracle at {d}")
+
+    def check_all(what, observe=None):
+        for n in em.names:
+            mod = em.m[n]
+            exp = mod.state()
+            exp.update(lb=mod.lb, mse=mod.mse)
+            check_outputs(f"{what} (full state of member {n})", (observe or be.observe)(n), exp)
+
+    def refusal(what, rc, msg, k, words, label):
+        if rc != VSOM_ERR_INVALID or words not in msg or (k is not None and f"member {k}:" not in msg):
+            fail(f"{what} returned {rc} {msg!r}: the header refuses it ({words}" +
+                 (f", naming member {k})" if k is not None else ")"))
+        if label:
+            stats["refusals"][label] = stats["refusals"].get(label, 0) + 1
+        check_all(f"{what} refused ({words})")       # a refused call changes nothing in any member
+
+    def check(op, a, rc, msg, out):
+        name, p = op
+        stats["ops"] += 1
+        if out.get("twin_diff"):
+            fail(f"{name}: {out['twin_diff']}")
+        if name == "sigma_stats":
+            if rc != 0 or [int(v) for v in out["stats"]] != list(p["expect"]):
+                fail(f"vsom_sigma_stats of member {p['k']} = {out.get('stats')}, the header's contract gives {p['expect']} "
+                     f"(deferred, dropped, materialised, pending)")
+            return
+        if name == "m":
+            n, inner = p["k"], p["op"]
+            why = em.member_refusal(n, inner)
+            if why is not None:
+                if rc != why[0] or why[1] not in msg:
+                    fail(f"{inner[0]} on member {n} returned {rc} {msg!r}: the header refuses it ({why[1]})")
+                if why[2]:
+                    refusal(f"{inner[0]} on member {n}", rc, msg, None, why[1], why[2])
+                return
+            if rc != 0:
+                fail(f"{inner[0]} on member {n} failed: {rc} {msg}")
+            check_outputs(f"{inner[0]} on member {n}", out, em.apply_member(n, inner, a))
+            if inner[0] == "get_state":
+                check_all("get_state")
+            return
+        if name in ("ens_create", "ens_destroy"):
+            if rc != 0:
+                fail(f"{name} failed: {rc} {msg}")
+            em.apply(op, a)
+            return
+        why = em.ens_refusal(op, a)
+        if why is not None:
+            return refusal(name, rc, msg, *why)
+        if "must_refuse" in p:
+            k = em.ens[p["e"]].index(p["must_refuse"])
+            stats["staged"] += 1
+            return refusal(f"{name} behind epoch_async, prefetch on member {k}", rc, msg, k, "vsom_commit_chunk first", None)
+        if rc != 0:
+            fail(f"{name} failed: {rc} {msg}")
+        for n, v in out.pop("applies", {}).items():       # the library's own predicate for every masked member
+            k = em.ens[p["e"]].index(n)
+            stats["applies"] += 1
+            if bool(v) != em.path(op, n, k):
+                fail(f"{name}: member {k} ({n}, {em.m[n].B} rows): the library's *_tiny_applies says {v}, the restated "
+                     f"predicate {em.path(op, n, k)}")
+        if name in ENS_TRAIN:
+            order = em.ens[p["e"]]
+            touched = [k for k in range(len(order)) if "sigmas" not in p or p["sigmas"][k]]
+            fast = sum(em.path(op, order[k], k) for k in touched)
+            stats["mixed"][name] += fast >= 2 and len(touched) - fast >= 1
+        stats["accepted"][name] += 1
+        check_outputs(name, out, em.apply(op, a))
+
+    def back_to_back(batch):
+        """run 1 on a backend that can separate the ensemble from the twins (call_first / call_twin): every call goes to
+        the ensemble before a twin or the model sees one; the arguments come from a shadow that follows the uploads alone"""
+        shadow = copy.copy(em)
+        shadow.m = {n: copy.copy(mod) for n, mod in em.m.items()}
+        made = []
+        for op in batch:
+            a = shadow.materialize(op)
+            made.append((op, a) + tuple(be.call_first(op, a)))
+            if made[-1][2] == 0 and op[0] == "ens_upload":
+                for n in shadow.ens[op[1]["e"]]:
+                    shadow.m[n].X = a["X"][n]
+            if len(made) > 1 and made[-2][0][0] == "ens_upload" and made[-2][0][1]["wait"] == 0 and made[-1][2] == 0:
+                stats["nowait"] += 1
+        for op, a, rc, msg, out in made:
+            done.append(op)
+            be.call_twin(op, a, rc, msg, out)
+            check(op, a, rc, msg, out)
+
+    try:
+        todo = list(ops[1:])
+        while todo:
+            op = todo.pop(0)
+            done.append(op)
+            if op[0] in ("run", "run_end"):
+                if op == ("run", {"id": 1}) and hasattr(be, "call_first"):
+                    n = [o[0] for o in todo].index("run_end")
+                    back_to_back(todo[:n])
+                    del todo[:n]
+                continue
+            a = em.materialize(op)
+            rc, msg, out = be.call(op, a)
+            check(op, a, rc, msg, out)
+        check_all("end of walk")
+        if hasattr(be, "observe_twin"):
+            check_all("end of walk, the twins", be.observe_twin)
+    finally:
+        be.close()
+        em.close()
+    return stats
+
+
+class EnsGpuBackend:
+    """The members of an ensemble configuration and one twin of each that never joins, on the C ABI.  A member is a
+    GpuBackend (its context, pinned and device copies of its chunks); its twin comes from the same constructor, gets the
+    same settings, and makes every call as a single call, fed from pageable memory and synchronised after each.  What an
+    ensemble call returns must equal, bit for bit, what the twins' single calls return in member order."""
+
+    def __init__(self, cfg_name, em):
+        self.em = em
+        ec = ENS_CONFIGS[cfg_name]
+        self.gb = {n: GpuBackend(n, em.m[n]) for n in em.names}
+        self.capi, self.L, self.hip = self.gb[em.names[0]].capi, self.gb[em.names[0]].L, self.gb[em.names[0]].hip
+        self.twin = {n: self.gb[n].make() for n in em.names}
+        self.streams = []
+        for i, n in enumerate(em.names):
+            if ENS_MEMBERS[n].get("lazy"):             # (the twin too: it never joins, and may go on deferring)
+                self.gb[n].ctx.set_sigma_mode(SIGMA_LAZY)
+                self.twin[n].set_sigma_mode(SIGMA_LAZY)
+            if not ec["one_stream"] or i == 0:
+                s = C.c_void_p()
+                assert self.hip.hipStreamCreate(C.byref(s)) == 0
+                self.streams.append(s)
+            self.capi.check(self.L.vsom_set_stream(self.gb[n].ctx._h, self.streams[-1]))
+        self.ens = {}
+        # the pinned buffer of every wait = 0 upload, made and filled up front (an allocation inside the walk would
+        # synchronise the device); junk goes in once a synchronising call on the members has returned
+        self.pinned, self.in_flight = {}, []
+        shadow = copy.copy(em)
+        shadow.ens = {}
+        for name, p in em.ops[1:]:
+            if name == "ens_create":
+                shadow.ens[p["e"]] = list(p["order"])
+            elif name == "ens_destroy":
+                del shadow.ens[p["e"]]
+            elif name == "ens_upload" and p["wait"] == 0:
+                lay = shadow.layout(p)
+                pb = self.capi.PinnedBuffer((lay["buf"].size,))
+                pb.array[...] = lay["buf"]
+                self.pinned[p["uid"]] = pb
+
+    def close(self):
+        for n, gb in self.gb.items():
+            self.L.vsom_synchronize(gb.ctx._h)
+        for e in list(self.ens.values()):
+            self.L.vsom_ensemble_destroy(e)
+        for n, gb in self.gb.items():
+            self.twin[n].close()
+            gb.close()
+        for pb in self.pinned.values():
+            pb.free()
+        for s in self.streams:
+            self.hip.hipStreamDestroy(s)
+
+    def call(self, op, a):
+        rc, msg, out = self.call_first(op, a)
+        self.call_twin(op, a, rc, msg, out)
+        return rc, msg, out
+
+    def _err(self, rc):
+        return "" if rc == 0 else self.L.vsom_last_error().decode(errors="replace")
+
+    # ---- the members and the ensembles ----
+    def call_first(self, op, a):
+        name, p = op
+        L = self.L
+        if name == "m":
+            gb = self.gb[p["k"]]
+            return gb._call(gb.ctx, p["op"], a)
+        if name == "sigma_stats":
+            st = self.gb[p["k"]].ctx.sigma_stats()
+            return 0, "", {"stats": tuple(st[k] for k in ("deferred", "dropped", "materialised", "pending"))}
+        if name == "ens_create":
+            K = len(p["order"])
+            arr = (C.c_void_p * K)(*[self.gb[n].ctx._h.value for n in p["order"]])
+            h = C.c_void_p()
+            rc = L.vsom_ensemble_create(C.byref(h), arr, K)
+            if rc == 0:
+                self.ens[p["e"]] = h
+            return rc, self._err(rc), {}
+        if name == "ens_destroy":
+            L.vsom_ensemble_destroy(self.ens.pop(p["e"]))
+            return 0, "", {}
+        rc, out = self._ensemble(self.ens[p["e"]], self.em.ens[p["e"]], op, a)
+        msg = self._err(rc)
+        if rc == 0 and name in ENS_TRAIN + ("ens_bmu",) and self.in_flight and \
+                not any("sigmas" in p and not s for s in p.get("sigmas", [])):
+            # every member's stream has been waited for: the pinned rows of earlier wait = 0 uploads may change
+            for pb in self.in_flight:
+                pb.array[...] = np.float32(np.nan)
+            self.in_flight = []
+        return rc, msg, out
+
+    def _ensemble(self, eh, order, op, a):
+        name, p = op
+        L, K = self.L, len(order)
+        f, u = self.capi._f, self.capi._u
+        dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        bad = p.get("bad")
+        B = [int(L.vsom_chunk_size(self.gb[n].ctx._h)) for n in order]
+        out, keep = {}, []
+        if "masks" in p and bad != "null_valid":
+            valid = [a["valid"][n] for n in order]
+            keep = [None if v is None else v.copy() for v in valid]
+            vptr = (u8p * K)(*[u8p() if v is None else v.ctypes.data_as(u8p) for v in keep])
+            ones = (C.c_int * K)(*[0 if v is None else int(v.ndim == 1) for v in keep])
+            masked = [n for n, v in zip(order, valid) if v is not None]
+        if name == "ens_upload":
+            buf = self.pinned[p["uid"]].array if p["wait"] == 0 else a["buf"]
+            off, bs = (C.c_size_t * K)(*a["off"]), (C.c_size_t * K)(*a["B"])
+            rc = L.vsom_ensemble_upload_chunks(eh, f(buf), a["n_floats"], None if bad == "null" else off, bs, p["wait"])
+            if rc == 0 and p["wait"] == 0:
+                self.in_flight.append(self.pinned[p["uid"]])
+        elif name in ("ens_epoch", "ens_epoch_masked"):
+            sig, mse = (C.c_double * K)(*p["sigma"]), np.zeros(K, np.float32)
+            if name == "ens_epoch":
+                rc = L.vsom_ensemble_batch_epoch(eh, None if bad == "null" else sig, int(p["first"]), f(mse))
+            else:
+                if bad != "null_valid":
+                    out["applies"] = {n: L.vsom_masked_tiny_applies(self.gb[n].ctx._h, int(a["valid"][n].ndim == 1))
+                                      for n in masked if self.em.m[n].X is not None}
+                rc = L.vsom_ensemble_batch_epoch_masked(eh, sig, int(p["first"]), vptr, ones, f(mse))
+            out.update({f"{n}.mse": mse[k] for k, n in enumerate(order)})
+        elif name in ("ens_schedule", "ens_schedule_masked"):
+            sgs = [np.array([_nan(v) for v in s], np.float64) for s in p["sigmas"]]
+            mses = [np.zeros(s.size, np.float32) for s in sgs]
+            sig = (dp * K)(*[s.ctypes.data_as(dp) for s in sgs])
+            if bad == "null_sigma":
+                sig[K - 1] = dp()
+            mo = (C.POINTER(C.c_float) * K)(*[f(m) for m in mses])
+            cnt = (C.c_size_t * K)(*[s.size for s in sgs])
+            if name == "ens_schedule":
+                rc = L.vsom_ensemble_batch_schedule(eh, sig, None if bad == "null_epochs" else cnt, int(p["reset"]), mo)
+            else:
+                out["applies"] = {n: L.vsom_masked_tiny_applies(self.gb[n].ctx._h, int(a["valid"][n].ndim == 1))
+                                  for k, n in enumerate(order) if n in masked and self.em.m[n].X is not None and
+                                  sgs[k].size and np.isfinite(sgs[k]).all()}
+                rc = L.vsom_ensemble_batch_schedule_masked(eh, sig, cnt, int(p["reset"]), vptr, ones, mo)
+            out.update({f"{n}.mses": mses[k] for k, n in enumerate(order) if sgs[k].size})
+        elif name in ("ens_online", "ens_online_masked"):
+            decay = list(p["decay"])
+            if bad == "decay":
+                decay[1] = 7
+            eta, sig, dec = (C.c_double * K)(*p["eta"]), (C.c_double * K)(*p["sigma"]), (C.c_int * K)(*decay)
+            lbs = [np.zeros(b, np.uint64) for b in B]
+            lp = (C.POINTER(C.c_uint64) * K)(*[u(x) for x in lbs])
+            mse = np.zeros(K, np.float32)
+            if name == "ens_online":
+                rc = L.vsom_ensemble_train_online_chunk_fetch(eh, eta, sig, dec, int(p["first"]), lp, f(mse))
+            elif bad == "null_valid":
+                rc = L.vsom_ensemble_train_online_chunk_masked(eh, eta, sig, dec, int(p["first"]), None, None, lp, f(mse))
+            else:
+                out["applies"] = {n: L.vsom_online_masked_tiny_applies(self.gb[n].ctx._h, p["sigma"][order.index(n)],
+                                                                       int(a["valid"][n].ndim == 1))
+                                  for n in masked if self.em.m[n].X is not None}
+                rc = L.vsom_ensemble_train_online_chunk_masked(eh, eta, sig, dec, int(p["first"]), vptr, ones, lp, f(mse))
+            for k, n in enumerate(order):
+                out[f"{n}.mse"], out[f"{n}.lb"] = mse[k], lbs[k]
+        elif name == "ens_bmu":
+            idx, dist = [np.zeros(b, np.uint64) for b in B], [np.zeros(b, np.float32) for b in B]
+            rc = L.vsom_ensemble_bmu_batch(eh, (C.POINTER(C.c_uint64) * K)(*[u(x) for x in idx]),
+                                           (C.POINTER(C.c_float) * K)(*[f(x) for x in dist]))
+            for k, n in enumerate(order):
+                out[f"{n}.idx"], out[f"{n}.dist"] = idx[k], dist[k]
+        else:
+            um = [np.zeros(self.gb[n].N, np.float64) for n in order]
+            rc = L.vsom_ensemble_umatrix(eh, (dp * K)(*[x.ctypes.data_as(dp) for x in um]))
+            out.update({f"{n}.u": um[k] for k, n in enumerate(order)})
+        for v in keep:                         # "valid_host is not read after the call returns"
+            if v is not None:
+                v[...] = 0
+        return rc, out
+
+    # ---- the twins ----
+    def call_twin(self, op, a, rc, msg, out):
+        name, p = op
+        if rc != 0 and name != "m":
+            return                             # (a refused ensemble call: nothing to replay)
+        if name in ("ens_create", "ens_destroy", "sigma_stats"):
+            return
+        if name == "m":
+            n, inner = p["k"], p["op"]
+            gb, t = self.gb[n], self.twin[n]
+            joined = n in self.em.joined
+            if inner[0] == "online_masked" and joined and not self.em.m[n].cfg["custom"] and self.em.m[n].cfg["tr"] != po.CLR:
+                return                         # the member must refuse it; the twin would accept and train
+            trc, _, tout = gb._call(t, inner, a, twin=True)
+            if inner[0] == "accum_begin" and joined and rc != 0 and trc == 0:
+                # the header gives the twin, which never joined, another answer: it accepts -- and is put back
+                self.capi.check(self.L.vsom_batch_accum_abort(t._h))
+                return
+            if trc != rc:
+                out["twin_diff"] = f"{inner[0]} on member {n} returned {rc}, its twin {trc}"
+                return
+            if rc == 0 and inner[0] != "get_state":
+                self._diff(out, tout, f"member {n}'s twin")
+            return
+        order = self.em.ens[p["e"]]
+        tout = {}
+        for k, n in enumerate(order):
+            for key, v in self._single(self.twin[n], n, k, op, a).items():
+                tout[f"{n}.{key}"] = v
+            self.capi.check(self.L.vsom_synchronize(self.twin[n]._h))
+        self._diff(out, tout, "the twins' single calls")
+
+    def _diff(self, out, tout, who):
+        for key, v in tout.items():
+            d = first_difference_exact(np.asarray(out.get(key)), np.asarray(v))
+            if d:
+                out["twin_diff"] = f"output {key!r} differs from {who} at {d}"
+                return
+
+    def _single(self, t, n, k, op, a):
+        """member k's share of an accepted ensemble call as the single call on its twin"""
+        name, p = op
+        L, h = self.L, t._h
+        f, u = self.capi._f, self.capi._u
+        dp, u8p = C.POINTER(C.c_double), C.POINTER(C.c_uint8)
+        valid = a.get("valid", {}).get(n)
+        vb = None if valid is None else valid.copy()
+        vp, one = (None, 0) if vb is None else (vb.ctypes.data_as(u8p), int(vb.ndim == 1))
+        m = C.c_float()
+        out = {}
+        if name == "ens_upload":
+            X = np.ascontiguousarray(a["X"][n], np.float32)
+            rc = L.vsom_upload_chunk(h, f(X), X.shape[0])
+        elif name in ("ens_epoch", "ens_epoch_masked"):
+            if vb is None:
+                rc = L.vsom_batch_epoch(h, p["sigma"][k], int(p["first"]), C.byref(m))
+            else:
+                rc = L.vsom_batch_epoch_masked(h, p["sigma"][k], int(p["first"]), vp, one, C.byref(m))
+            out["mse"] = np.float32(m.value)
+        elif name in ("ens_schedule", "ens_schedule_masked"):
+            sg = np.array([_nan(v) for v in p["sigmas"][k]], np.float64)
+            if not sg.size:
+                return out
+            mses = np.zeros(sg.size, np.float32)
+            if vb is None:
+                rc = L.vsom_batch_schedule(h, sg.ctypes.data_as(dp), sg.size, int(p["reset"]), f(mses))
+            else:
+                rc = L.vsom_batch_schedule_masked(h, sg.ctypes.data_as(dp), sg.size, int(p["reset"]), vp, one, f(mses))
+            out["mses"] = mses
+        elif name in ("ens_online", "ens_online_masked"):
+            lb = np.zeros(int(L.vsom_chunk_size(h)), np.uint64)
+            args = (h, p["eta"][k], p["sigma"][k], p["decay"][k], int(p["first"]))
+            if vb is None:
+                rc = L.vsom_train_online_chunk_fetch(*args, u(lb), C.byref(m))
+            else:
+                rc = L.vsom_train_online_chunk_masked(*args, vp, one, u(lb), C.byref(m))
+            out.update(mse=np.float32(m.value), lb=lb)
+        elif name == "ens_bmu":
+            B = int(L.vsom_chunk_size(h))
+            idx, dist = np.zeros(B, np.uint64), np.zeros(B, np.float32)
+            rc = L.vsom_bmu_batch(h, u(idx), f(dist))
+            out.update(idx=idx, dist=dist)
+        else:
+            um = np.zeros(self.gb[n].N, np.float64)
+            rc = L.vsom_umatrix(h, um.ctypes.data_as(dp))
+            out["u"] = um
+        self.capi.check(rc)
+        return out
+
+    def observe(self, n):
+        return self.gb[n].observe(self.gb[n].ctx)
+
+    def observe_twin(self, n):
+        return self.gb[n].observe(self.twin[n])

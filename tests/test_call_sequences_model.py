@@ -12,7 +12,12 @@ would.  The ingest walks themselves are pinned by digest: the generator's new op
 The accum profile's walks (the accumulated batch epoch) run against the same fake, which keeps what the model keeps -- the
 open epoch's rows, validity and lastBMU -- on its own oracle.  Mutants l-r break it the ways hand-kept host state can be
 wrong between calls that do not block.  The sigma walks are pinned by digest too, and what the GPU test asserts of its
-walks' counts is checked here as a condition on the inputs."""
+walks' counts is checked here as a condition on the inputs.
+
+The ensemble profile's walks (callseq.generate_ensemble) run against FakeEnsemble, the members and ensembles on a second set
+of oracles.  The faithful fake passes the walks the GPU test runs and meets the conditions it asserts
+(callseq.ens_conditions); the walks are pinned by digest; each of the eight mutants -- the ways an ensemble call can differ
+from the single calls on its members in turn -- is caught by one of them."""
 import ast
 import copy
 import functools
@@ -979,5 +984,295 @@ def test_accum_mutants_are_caught(mutant):
             _run_accum(cfg, mode, seed, mutant)
         except cs.WalkFailure as e:
             caught.append((cfg, mode, seed, str(e).splitlines()[0]))
+            break
+    assert caught, f"mutant {mutant} was not caught by any walk"
+
+
+# ---- the ensemble profile ----------------------------------------------------------------------------------------------
+class FakeEnsemble:
+    """The members and the ensembles as the header describes them, on a second set of oracles (callseq.EnsModel).  A
+    prefetch right behind an asynchronous epoch is staged ahead where callseq.stages_ahead holds, and every row-reading
+    ensemble call is then refused naming the member; vsom_sigma_stats follows callseq.SigmaRecord until the member joins,
+    which materialises a pending record and ends the deferring.  `mutant` breaks it:
+      mse       an ensemble online call with first_chunk = 0 restarts member 1's running MSE
+      trained   a refused call has already trained the members before the refusing one
+      idle_lb   a member with epochs[k] = 0 gets its lastBMU reset
+      lb        a non-first ensemble epoch or a schedule ignores a lastBMU written by vsom_set_last_bmu
+      share     members with equal offsets get the first one's B
+      null_mask a NULL-validity member is treated as masked, so a masked call refuses C
+      begin     a former member accepts vsom_batch_accum_begin
+      um        vsom_ensemble_umatrix leaves the per-member buffer unwritten: vsom_get_umatrix is stale"""
+
+    def __init__(self, cfg_name, em, mutant=None):
+        self.f = cs.EnsModel(cfg_name, 0)
+        for n in em.names:
+            self.f.m[n].chunks = em.m[n].chunks
+        self.mutant = mutant
+        self.ahead = {n: False for n in em.names}
+        self.last = {n: None for n in em.names}
+        self.stale = {}
+        self.rec = {n: cs.SigmaRecord(cs.ENS_MEMBERS[n]) for n in em.names}
+
+    def close(self):
+        self.f.close()
+
+    def observe(self, n):
+        mod = self.f.m[n]
+        st = mod.state()
+        st.update(lb=mod.lb.copy(), mse=mod.mse)
+        return st
+
+    def _member(self, n, inner, a):
+        f, mod = self.f, self.f.m[n]
+        why = f.member_refusal(n, inner)
+        if why is not None and not (self.mutant == "begin" and why[2] == "member_accum_begin"):
+            return why[0], f"{inner[0]}: {why[1]}", {}
+        name = inner[0]
+        if name == "prefetch" and self.last[n] == "epoch_async" and cs.stages_ahead(mod.cfg):
+            self.ahead[n] = True
+        elif name in ("commit", "upload"):
+            self.ahead[n] = False
+        if name in ("commit", "upload"):
+            self.stale.pop(n, None)
+        if name == "set_last_bmu" and self.mutant == "lb":
+            self.stale[n] = mod.lb.copy()
+        self.rec[n].accepted(inner, mod.B, mod.N)
+        self.last[n] = name
+        out = f.apply_member(n, inner, a)
+        return 0, "", {k: v for k, v in out.items() if v is not None}
+
+    def call(self, op, a):
+        name, p = op
+        f = self.f
+        if name == "m":
+            return self._member(p["k"], p["op"], a)
+        if name == "sigma_stats":
+            return 0, "", {"stats": self.rec[p["k"]].stats()}
+        if name == "ens_create":
+            for n in p["order"]:
+                self.rec[n].read()           # create materialises a pending record; a member never defers again
+                self.rec[n].can_defer = False
+        if name in ("ens_create", "ens_destroy"):
+            f.apply(op, a)
+            return 0, "", {}
+        order = f.ens[p["e"]]
+        why = f.ens_refusal(op, a)
+        if why is None and self.mutant == "null_mask" and p.get("masks"):
+            for k, n in enumerate(order):
+                if f.m[n].cfg["custom"] or f.m[n].cfg["tr"] == po.CLR:
+                    why = (k, "CLR contexts are not supported", None)
+                    break
+        if why is None and name not in ("ens_upload", "ens_umatrix"):
+            for k, n in enumerate(order):
+                if self.ahead[n] and ("sigmas" not in p or p["sigmas"][k]):
+                    why = (k, "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first", None)
+                    break
+        if why is not None:
+            if self.mutant == "trained" and why[0]:
+                for n in order[:why[0]]:
+                    if f.m[n].X is not None:
+                        f.m[n].som.train_single(f.m[n].X[0], 0.1, 1.0, 0, 0)
+            who = "" if why[0] is None else f"member {why[0]}: "
+            return cs.VSOM_ERR_INVALID, f"vsom_ensemble: {who}{why[1]}", {}
+        if name == "ens_upload":
+            for n in order:
+                self.ahead[n] = False
+                self.stale.pop(n, None)
+            if self.mutant == "share":
+                X = dict(a["X"])
+                for n in order:
+                    if "share" in p["rows"][n]:
+                        X[n] = X[p["rows"][n]["share"]]
+                a = dict(a, X=X)
+        if name in ("ens_online", "ens_online_masked") and not p["first"] and self.mutant == "mse":
+            f.m[order[1]].run = np.float32(0)
+        if name in ("ens_epoch", "ens_schedule", "ens_schedule_masked", "ens_epoch_masked"):
+            for n in order:
+                if n in self.stale:
+                    f.m[n].lb[:] = self.stale.pop(n)
+        before = {n: f.m[n].um for n in order}
+        out = f.apply(op, a)
+        if name == "ens_umatrix" and self.mutant == "um":
+            for n in order:
+                f.m[n].um = np.zeros(f.m[n].N) if before[n] is None else before[n]
+        if "sigmas" in p and self.mutant == "idle_lb":
+            for k, n in enumerate(order):
+                if not p["sigmas"][k]:
+                    f.m[n].lb[:] = 0
+        for n in order:
+            self.last[n] = name
+            self.rec[n].read()
+        return 0, "", {k: v for k, v in out.items() if v is not None}
+
+
+ENS_SEEDS = (1, 2)   # tests/test_gpu_call_sequences.py, test_ensemble_walk_matches_oracle
+
+
+def _ens_walks():
+    return [(c, s) for c in cs.ENS_CONFIGS for s in ENS_SEEDS]
+
+
+def _run_ens(cfg, seed, mutant=None):
+    return cs.run_ensemble_walk(cs.generate_ensemble(cfg, seed), lambda name, em: FakeEnsemble(name, em, mutant))
+
+
+@functools.lru_cache(maxsize=None)
+def _faithful_ens(cfg, seed):
+    return _run_ens(cfg, seed)
+
+
+def test_ensemble_ops_stay_out_of_the_other_walks():
+    assert not set(cs.ENS_MEMBERS) & set(cs.CONFIGS)
+    for cfg in cs.CONFIGS:
+        for seed in SEEDS:
+            walks = [cs.generate(cfg, seed, scale=SCALE)]
+            walks += [cs.generate(cfg, seed, scale=SCALE, profile="sigma", mode=mode) for mode in MODES]
+            walks += [_accum_ops(cfg, mode, seed) for mode in MODES]
+            for ops in walks:
+                assert not cs.ENS_NEW_OPS & {op[0] for op in ops}
+
+
+def test_ensemble_predicates_stand_at_their_borders():
+    """every row count of callseq.ENS_MEMBERS is at a border of a restated path predicate"""
+    M = cs.ENS_MEMBERS
+    assert [cs.batch_tiny(M["A"], b) for b in (20, 160, 163, 164, 170, 257)] == [True, True, True, False, False, False]
+    assert [cs.batch_tiny(M["B"], b) for b in (37, 121, 122, 151, 152)] == [True, True, False, False, False]
+    assert 151 * 108 <= 16384 < 152 * 108 and 121 * 108 * 20 <= 262144 < 122 * 108 * 20
+    assert [cs.batch_tiny(M["C"], b) for b in (77, 128)] == [True, False] and not cs.masked_batch_tiny(M["C"], 77)
+    assert cs.batch_tiny(M["D"], 64) and not cs.batch_tiny(M["D"], 65)         # N D B = 262144 exactly
+    assert cs.online_tiny(M["D"], 64, 2.5) and M["D"]["W"] * M["D"]["H"] * 512 == 4096
+    assert all(cs.online_tiny(M["A"], b, 0.7) for b in (20, 160, 170, 257))
+    assert not cs.online_tiny(M["A"], 20, 2.5, cs.BMU_EXACT) and not cs.online_tiny(M["A"], 20, float("nan"))
+    assert not cs.online_tiny(M["C"], 77, 2.5) and not cs.online_tiny(M["F"], 64, 2.5)
+    for n in ("E", "F", "G"):
+        assert not any(cs.batch_tiny(M[n], b) or cs.online_tiny(M[n], b, 2.5) for b, _ in M[n]["chunks"])
+    assert cs.stages_ahead(M["G"]) and cs.defers(M["G"]) and not cs.stages_ahead(M["E"])
+    assert cs.masked_batch_tiny(M["A"], 20) and not cs.masked_batch_tiny(M["A"], 20, strict=False)
+
+
+def test_ensemble_masks_are_engineered():
+    """NaN / inf under every invalid entry and nowhere else, a column valid in no row, the row without a valid column"""
+    for n in cs.ENS_MASKABLE:
+        for X in cs.chunk_data(n, 1, 1, "ensemble"):
+            for form in ("rows", "one_mask"):
+                spec = {"seed": 77, "form": form, "full": form == "rows"}
+                v = np.broadcast_to(cs.ens_mask(spec, X) != 0, X.shape)
+                P = cs.ens_poisoned(spec, X)
+                assert (np.isfinite(P) == v).all() and (P[v] == X[v]).all()
+                assert (np.broadcast_to(cs.ens_mask(spec, P) != 0, X.shape) == v).all()
+                assert (~v.any(axis=0)).sum() >= 1
+                if form == "rows":
+                    assert (~v.any(axis=1)).sum() == 1
+    X = cs.chunk_data("E", 1, 1, "ensemble")[2]
+    assert X.shape[0] == 1100 and not X[:, 5].any() and X[:, 4].any()
+    a, a2 = cs.chunk_data("A", 1, 1, "ensemble"), cs.chunk_data("A2", 1, 1, "ensemble")
+    assert all((x == y).all() for x, y in zip(a, a2))
+
+
+def _ens_runs(ops):
+    """the ops between each run's markers (runs 8 and 9, which open the walk, overlap)"""
+    runs, inside = {}, []
+    for op in ops[1:]:
+        if op[0] == "run":
+            inside.append(op[1]["id"])
+        elif op[0] == "run_end":
+            inside.remove(op[1]["id"])
+        for run in inside:
+            if op[0] != "run":
+                runs.setdefault(run, []).append(op)
+    return runs
+
+
+def test_ensemble_walks_hold_the_required_runs():
+    for cfg, seed in _ens_walks():
+        own = cfg == "ens_own"
+        ops = cs.generate_ensemble(cfg, seed)
+        assert ast.literal_eval(repr(ops)) == ops        # a printed walk can be replayed
+        runs = _ens_runs(ops)
+        assert set(runs) == set(cs.ENS_RUNS) - (set() if own else {8}), (cfg, seed, sorted(runs))
+        names = {r: [o[1]["op"][0] if o[0] == "m" else o[0] for o in runs[r]] for r in runs}
+        # 1: nothing but ensemble calls; two wait = 0 uploads, the second larger, each followed by a train call
+        assert names[1] == ["ens_upload", "ens_epoch_masked", "ens_bmu"] + ([] if own else ["ens_umatrix"]) + \
+            ["ens_schedule_masked", "ens_online_masked", "ens_upload", "ens_epoch"], names[1]
+        ups = [o[1] for o in runs[1] if o[0] == "ens_upload"]
+        assert all(u["wait"] == 0 for u in ups) and ups[0]["poison"] and "poison" not in ups[1]
+        assert any(s.get("full") for s in ups[0]["poison"].values())
+        size = lambda u: sum(cs.ENS_MEMBERS[n]["chunks"][s["chunk"]][0] * cs.ENS_MEMBERS[n]["J"] for n, s in u["rows"].items())
+        assert size(ups[1]) > size(ups[0])
+        assert any(v is None for v in [runs[1][1][1]["masks"].get(n) for n in ups[0]["rows"]])       # NULL-validity members
+        # 2: first_chunk = 1, own uploads, a single online chunk with first = 0, the masked call with first_chunk = 0
+        assert names[2][:5] == ["ens_online", "upload", "upload", "online", "ens_online_masked"], names[2]
+        assert runs[2][0][1]["first"] and not runs[2][3][1]["op"][1]["first"] and not runs[2][4][1]["first"]
+        # 3: A at 160, 170, 160 rows and B at 121, 122, 121 / 151, 152, 121 in front of each kind of call; EXACT and AUTO; a
+        # NaN; epochs 0
+        sizes = [(cs.ENS_MEMBERS["A"]["chunks"][o[1]["rows"]["A"]["chunk"]][0],
+                  cs.ENS_MEMBERS["B"]["chunks"][o[1]["rows"]["B"]["chunk"]][0]) for o in runs[3] if o[0] == "ens_upload"]
+        assert sizes == [(160, 121), (170, 122), (160, 121), (160, 151), (170, 152), (160, 121)], sizes
+        for kind in cs.ENS_TRAIN:
+            assert names[3].count(kind) >= 2, (kind, names[3])
+        modes = [o[1]["op"][1]["mode"] for o in runs[3] if o[0] == "m" and o[1]["op"][0] == "bmu_mode"]
+        assert modes == [cs.BMU_EXACT, cs.BMU_AUTO]
+        sched = [o[1]["sigmas"] for o in runs[3] if o[0] in ("ens_schedule", "ens_schedule_masked")]
+        assert any(None in s for sg in sched for s in sg) and any(s == [] for sg in sched for s in sg)
+        # 4: the stage-ahead
+        k = "G" if own else "E"
+        assert names[4][:3] == ["upload", "epoch_async", "prefetch"] and runs[4][1][1]["k"] == k
+        refused = [o for o in runs[4] if "must_refuse" in o[1]]
+        assert [o[0] for o in refused] == (list(cs.ENS_TRAIN) + ["ens_bmu"] if own else [])
+        rest = names[4][names[4].index("ens_upload"):]
+        assert rest == ["ens_upload", "commit", "ens_epoch", "ens_bmu"], rest
+        # 6: state rewritten between ensemble calls
+        assert names[6] == ["set_state", "set_state", "set_last_bmu", "set_last_bmu", "ens_epoch", "set_last_bmu",
+                            "ens_schedule_masked", "get_last_bmu"], names[6]
+        assert not runs[6][4][1]["first"] and not runs[6][6][1]["reset"]
+        # 7: lifetime
+        assert names[7][0] == "ens_destroy" and names[7].count("ens_create") == 2 and "ens_umatrix" in names[7]
+        created = [o[1]["order"] for o in runs[7] if o[0] == "ens_create"]
+        assert "F" not in created[0] and set(created[1]) & set(created[0])
+        es = [o[1]["e"] for o in runs[7] if o[0] in cs.ENS_CALLS]
+        assert any(x != y for x, y in zip(es, es[1:]))
+        # 8, 9: before the first create
+        first = [o[0] for o in ops].index("ens_create")
+        if own:
+            assert ops[first - 1] != ops[first] and ("sigma_stats", {"k": "G", "expect": [1, 0, 0, 1]}) in ops[:first]
+            assert ops[first + 1] == ("sigma_stats", {"k": "G", "expect": [1, 0, 1, 0]})
+        # (the first ensemble epoch is the one refused for C, which has no chunk yet)
+        assert [n for n in names[9] if n in ("accum_begin", "accum_chunk", "ens_create", "ens_epoch", "accum_end")] == \
+            ["accum_begin", "accum_chunk", "ens_create", "ens_epoch", "ens_epoch", "accum_chunk", "accum_end"], names[9]
+
+
+@pytest.mark.parametrize("cfg,seed", _ens_walks())
+def test_faithful_fake_passes_ensemble_walks(cfg, seed):
+    """... and the walks the GPU test runs meet the conditions it asserts (callseq.ens_conditions)"""
+    cs.ens_conditions(cfg, _faithful_ens(cfg, seed))
+
+
+# sha256(repr(generate_ensemble(cfg, seed)))
+ENS_DIGESTS = {
+    ("ens_shared", 1): "e7e68cd3eb80eb062226cdfa914adac94f070ec2c05f7126dff782a4ad386aef",
+    ("ens_shared", 2): "0e4207a8364dea50c2ff26f2fe5e50ff826ec982a2819a158f471bf21c40c9e4",
+    ("ens_own", 1): "2f4dacc5fbdd06a73f159177002cedc9635d4bdec383617c585338133cc3aba8",
+    ("ens_own", 2): "06ea491e869f80c28c0331a1f68f3d9a1fb386533084403a3f32067c856d702b",
+}
+
+
+@pytest.mark.parametrize("key", [(c, s) for c in cs.ENS_CONFIGS for s in ENS_SEEDS], ids=lambda k: "-".join(str(v) for v in k))
+def test_ensemble_walks_are_unchanged(key):
+    ops = cs.generate_ensemble(*key)
+    assert hashlib.sha256(repr(ops).encode()).hexdigest() == ENS_DIGESTS[key]
+
+
+@pytest.mark.parametrize("mutant", ["mse", "trained", "idle_lb", "lb", "share", "null_mask", "begin", "um"])
+def test_ensemble_mutants_are_caught(mutant):
+    caught = []
+    for cfg, seed in _ens_walks():
+        try:
+            _run_ens(cfg, seed, mutant)
+        except cs.WalkFailure as e:
+            text = str(e)
+            assert f"seed {seed}" in text and "replay(ops) with ops = [('config'" in text
+            # the first differing element, or the return code where it is the call's acceptance that differs
+            assert "element" in text or "returned" in text or "failed: -1" in text, text.splitlines()[0]
+            caught.append((cfg, seed, text.splitlines()[0]))
             break
     assert caught, f"mutant {mutant} was not caught by any walk"

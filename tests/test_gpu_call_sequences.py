@@ -55,7 +55,36 @@ std12 1.8, 1.5 / 1.8, 2.0; clr12, custom12 at most 0.1.  On an MI355X the tests 
 them, on chunks of the accum profile alone that are short enough (callseq.CONFIGS, "accum_chunks"; callseq.maskable caps
 rows x nodes at callseq.MASK_DISTANCES, 8 times that for the local walk), and a walk makes 12 random draws around its runs
 (callseq.ACCUM_DRAWS; with 24 the large maps measured 9 to 17 s); the rest is the phase 2 at end -- run 2 ends on the
-configuration's largest chunk by design, and every dirty column costs one single-column oracle run."""
+configuration's largest chunk by design, and every dirty column costs one single-column oracle run.
+
+The ensemble walks (callseq.generate_ensemble) do the same for the nine vsom_ensemble_* calls (include/vsom_hip.h,
+"ensembles"), the object of the C ABI that keeps the most state between calls and shares it between contexts: two descriptor
+slots behind events, which also carry the masked calls' tables and validity image, the grow-only raw upload buffer read by
+stagings on several streams, the members' neighbourhood-table slots, schedule tables shared between members, and the flag that
+changes what the single-context calls do on a member, past or present.  The members (callseq.ENS_MEMBERS) have row counts at
+the borders of the path predicates -- a 10 x 10 x 9 map takes the one-launch batch kernel at 160 rows and not at 170, a
+12 x 9 x 20 map at 121 and not at 122 -- restated in callseq.batch_tiny / masked_batch_tiny / online_tiny; at every masked call
+the walk asks vsom_masked_tiny_applies / vsom_online_masked_tiny_applies for every masked member and fails where a restated
+predicate disagrees.  ens_shared puts A, A2 (A's rows by equal offsets), B, C, D, E on one stream, ens_own gives A, B, C, E, F
+(custom), G (48 x 48, created under VSOM_SIGMA_LAZY) a stream each.  A walk makes callseq.ENS_DRAWS random draws -- ensemble
+calls, masked blocks on poisoned rows, single-context calls on members (uploads, prefetch and commit, partial vsom_set_state,
+lastBMU writes, epochs, online chunks, searches, U-matrices, search modes, vsom_batch_schedule and its masked form) -- around
+the runs of generate_ensemble's docstring: the no-wait run (six descriptor sizes through two slots, the raw buffer rewritten
+behind stagings; sent to the ensemble back to back before the twins and the model see it), the running MSE across ensemble
+and single calls, members crossing path borders between two calls of each kind (rows, search mode, a NaN sigma, epochs[k] = 0),
+the stage-ahead refusal naming G, every refusal the header lists, state rewritten between ensemble calls, destroy / create
+over a permuted subset / two overlapping ensembles, G's pending sigmaMap meeting create, and an accumulated epoch open on A
+when it joins.  Every output equals the oracle's (one callseq.Model per member, the single call on every member in index
+order) and the return of a twin of each member that never joins and makes the single calls one by one; every refusal names
+the member the header says and is followed by a comparison of the whole state, lastBMU and MSE word of every member; where
+the header gives a member another answer than its twin (vsom_train_online_chunk_masked, vsom_batch_accum_begin) the member
+must refuse.  callseq.ens_conditions asserts from the walk's counts that it did not pass vacuously.
+
+Cost of an ensemble walk, measured the same way (against the CPU fake; the model's share is about half), seeds 1 and 2, in
+seconds: ens_shared 6.2, 7.2; ens_own 7.5, 7.0.  On an MI355X the tests themselves took 1.7 to 2.2 s (ens_shared) and
+2.8 to 4.3 s (ens_own).  The dearest ops are the model's masked calls (tests/masked_train_ref.py and
+tests/online_masked_ref.py, pure Python): they name A, A2, B and D only, the masked online chunk takes the local walk
+(sigma <= 1) on more than 40 rows and D's 512 columns on 3 rows, and E's 1100 and G's 300 rows are loaded once per walk."""
 import pytest
 
 import callseq as cs
@@ -111,3 +140,13 @@ def test_accum_walk_matches_oracle(cfg, mode, seed):
         assert not any(a.values()), stats            # vsom_batch_accum_begin is refused, and so every call behind it
     if cfg not in DEFERRING:
         assert stats["sigma"][:3] == (0, 0, 0), stats
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+@pytest.mark.parametrize("cfg", list(cs.ENS_CONFIGS))
+def test_ensemble_walk_matches_oracle(cfg, seed):
+    # (run_ensemble_walk itself fails a walk in which an ensemble call is refused where the header accepts it, accepted
+    # where it refuses it, names another member, or where a restated path predicate disagrees with the library's)
+    stats = cs.run_ensemble_walk(cs.generate_ensemble(cfg, seed), cs.EnsGpuBackend)
+    # (tests/test_call_sequences_model.py, test_faithful_fake_passes_ensemble_walks: these walks meet them)
+    cs.ens_conditions(cfg, stats, gpu=True)
