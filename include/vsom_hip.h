@@ -919,7 +919,7 @@ int vsom_train_online_chunk_fetch(vsom_ctx *ctx, double eta, double sigma, int d
  * custom and CLR contexts; a decay_fn other than the two online ones; no chunk loaded; a chunk staged ahead over the
  * current rows; a context that has joined a group or an ensemble.  A pending sigmaMap is materialised first, as for the
  * unmasked chunk calls.  Two loops give these results, bit for bit the same.  A tiny map, where
- * vsom_online_masked_tiny_applies holds, takes the one-launch chunk of one workgroup (csrc/vsom_online_tiny_masked.hip,
+ * vsom_online_masked_tiny_applies holds, takes the one-launch chunk of one workgroup (csrc/vsom_online_tiny.hip,
  * DESIGN.md section 4u): one H2D copy of the validity bytes and one launch per call, lastBMU and the MSE back through
  * pinned memory as in vsom_train_online_chunk_fetch.  Every other chunk takes the per-sample loop on the exact scan, for
  * every vsom_set_bmu_mode; the image-bounded search is never used, and vsom_get_online_search_stats counts the samples of

@@ -1909,7 +1909,7 @@ def masked_batch_tiny(cfg, B, strict=True):
 
 
 def online_tiny(cfg, B, sigma, mode=BMU_AUTO):
-    """vsom_online_masked_tiny_applies as include/vsom_hip.h:933 states it (csrc/vsom_online_tiny_masked.hip:53), which is
+    """vsom_online_masked_tiny_applies as include/vsom_hip.h:933 states it (vsom_onl_tiny_fits, csrc/vsom_online_tiny.hip), which is
     the unmasked one-launch chunk's rule too: Standard / Median, not custom, N <= 1024, N * D <= 4096, D <= 512,
     B <= 4096, sigma no NaN, the search mode VSOM_BMU_AUTO.  (The LDS need of every member here is within 96 KiB.)"""
     N, D = cfg["W"] * cfg["H"], po.length(cfg["tr"], cfg["J"])

@@ -21,8 +21,10 @@ for tree in "$1" "$2"; do
   ls "$csrc"/*.hip | xargs -P "${JOBS:-8}" -I{} sh -c \
     "$HIPCC $flags -I$work/stub -fuse-cuid=none --cuda-device-only --no-gpu-bundle-output -c {} -o $work/$side/\$(basename {} .hip).o"
   for o in "$work/$side"/*.o; do
-    # "<address> <name>:" opens a function; "\tinsn // address: encoding" is one instruction
+    # "<address> <name>:" opens a function; "\tinsn // address: encoding" is one instruction; "\t\t..." is the zero padding up
+    # to the next function's alignment, which only a function that is not the last of its object has: no instruction
     "$LLVM/llvm-objdump" -d -C "$o" | awk '/^[0-9a-f]+ <.*>:$/ { sub(/^[0-9a-f]+ </, ""); sub(/>:$/, ""); k = $0; next }
+      /^\t+\.\.\.$/ { next }
       /^\t/ && k != "" { sub(/\/\/ [0-9A-F]+:/, "//"); print k "\t" $0 }'
   done > "$work/$side.txt"
   side=b

@@ -21,7 +21,7 @@ PY
   rm -f "$here/vsom_update.o"
 fi
 objs=()
-for f in vsom_capi vsom_bmu vsom_shortlist vsom_update vsom_online vsom_online_i8 vsom_online_tiny vsom_online_tiny_masked vsom_online_masked vsom_single vsom_tiny vsom_tiny_masked vsom_group vsom_compact vsom_xq vsom_sl_i8 vsom_custom vsom_ensemble vsom_bmd vsom_topk vsom_umatrix vsom_similarity vsom_masked vsom_masked_train vsom_accum vsom_accum_masked vsom_evaluate vsom_generate; do
+for f in vsom_capi vsom_bmu vsom_shortlist vsom_update vsom_online vsom_online_i8 vsom_online_tiny vsom_online_masked vsom_single vsom_tiny vsom_tiny_masked vsom_group vsom_compact vsom_xq vsom_sl_i8 vsom_custom vsom_ensemble vsom_bmd vsom_topk vsom_umatrix vsom_similarity vsom_masked vsom_masked_train vsom_accum vsom_accum_masked vsom_evaluate vsom_generate; do
   o="$here/$f.o"
   stale=0
   for d in "$here/$f.hip" "$here"/*.hpp "$here"/*.inc "$here/../../include/vsom_hip.h"; do   # any header may reach any object

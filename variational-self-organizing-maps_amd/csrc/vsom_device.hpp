@@ -254,3 +254,42 @@ __device__ __forceinline__ void vsom_somindex(u64 idx, u64 W, u64 H, int &x, int
     x = (int)xm;
     y = (int)((idx - xm) / H);
 }
+
+// Transformation::Stepper's sign (Transformation.cpp:49-50) as the one-launch batch epochs take it: +-1; a zero or a NaN
+// comes back as it is.  (The online kernels keep onl_sign, vsom_online.hpp, whose zero is +0 whatever the argument's sign:
+// the two forms are pinned bit for bit by their own tests and are not interchangeable.)
+__device__ __forceinline__ float tiny_sign(float a)
+{
+    const float one = __builtin_copysignf(1.f, a);
+    return (a < 0.f || a > 0.f) ? one : a;
+}
+
+// A schedule of one-launch batch epochs, plain (Args = TinyArgs, vsom_tiny.hip) or masked (TinyMaskedArgs,
+// vsom_tiny_masked.hip): the epoch's descriptor and where the launch's epochs find their tables
+template <class Args>
+struct TinySched {
+    Args t;                      // lut: the first table of the launch's table buffer; mse: slot 0 of this launch
+    const unsigned *tab;         // [epochs] each epoch's table, in floats from t.lut
+    int epochs;                  // of this launch (0: nothing to do)
+    int first;                   // this launch starts the schedule: its epoch 0 is the exact search
+    int reset_bmu;               // lastBMU := 0 before every epoch but an exact search
+    int pad;
+};
+
+// epoch ep of the launch: the barrier behind the previous epoch, the lastBMU reset, and the epoch's descriptor
+template <class Args>
+__device__ __forceinline__ Args tiny_schedule_epoch(const TinySched<Args> &s, int ep)
+{
+    Args a = s.t;
+    a.is_first = (s.first && ep == 0) ? 1 : 0;
+    a.lut = s.t.lut + s.tab[ep];
+    a.mse = s.t.mse + ep;
+    if (ep > 0)
+        __syncthreads();                     // the previous epoch's phase 2: map rows stored, LDS free
+    if (!a.is_first && s.reset_bmu) {
+        for (int i = threadIdx.x; i < a.B; i += 256)
+            a.lastbmu[i] = 0ull;             // DataSet.cpp:136-137
+        __syncthreads();
+    }
+    return a;
+}

@@ -29,8 +29,8 @@ struct vsom_ensemble {
     struct Slot {
         PinnedBuf<unsigned char> host;       // descriptors staged here, copied to dev
         DevBuf<unsigned char> dev;
-        // the masked train calls: the launch's tables, table offsets and the launched members' validity bytes, one image
-        // copied once on the launch stream; reused under the same event as the descriptors
+        // what the launch reads besides the descriptors -- a schedule round's image (vsom_sched_round.hpp), the online
+        // chunk's validity bytes -- copied once on the launch stream; reused under the same event as the descriptors
         PinnedBuf<unsigned char> img_host;
         DevBuf<unsigned char> img_dev;
         hipEvent_t ev = nullptr;
@@ -39,7 +39,7 @@ struct vsom_ensemble {
     int next = 0;
     // per call scratch
     std::vector<unsigned char> desc;         // one descriptor per member, packed at the kind's own descriptor size
-    std::vector<int> grp, lslot;
+    std::vector<int> grp;
     std::vector<size_t> smem;
     std::vector<unsigned> ext;               // the grid's other dimension: 16-row blocks (staging), 64-row tiles (scoring)
     // upload: the members' rows as one copy of the host range (grow-only); ev_raw is recorded behind the call's last
@@ -52,9 +52,6 @@ struct vsom_ensemble {
     PinnedBuf<float> sc_dist;
     // U-matrices of the launched members, stored by the kernel (pinned host memory, grow-only)
     PinnedBuf<double> um_out;
-    // schedules: every launched member's tables (shared where shape and sigma agree) and per-epoch table offsets
-    PinnedBuf<unsigned char> sch_host;
-    DevBuf<unsigned char> sch_dev;
 };
 
 static int ens_fail(size_t k, const char *what)
@@ -164,7 +161,6 @@ static void ens_scratch(vsom_ensemble *e, size_t stride)
     const size_t n = e->m.size();
     e->desc.resize(n * stride);
     e->grp.assign(n, -1);
-    e->lslot.assign(n, 0);
     e->smem.assign(n, 0);
     e->ext.assign(n, 0);
 }
@@ -181,10 +177,8 @@ enum EnsSet { ENS_LAUNCHED, ENS_PLAIN, ENS_JOINED };
 struct EnsCall {
     vsom_ensemble *e;
     hipStream_t ls = nullptr;                // the launch stream (null: nothing joined or launched yet)
-    hipStream_t also = nullptr;              // the schedule's table copies: a launched member's stream
     std::vector<hipStream_t> streams;        // the distinct streams of the last join
-    bool onl_slots = false;                  // online training: e->lslot[] of the launched members is released
-    std::vector<std::pair<vsom_ctx *, int>> held;   // ... or, for a call of several ens_launch passes, these table slots
+    std::vector<std::pair<vsom_ctx *, int>> held;   // online training: the launched members' table slots, released by wait()
     bool open = true;
     explicit EnsCall(vsom_ensemble *ens) : e(ens) {}
     EnsCall(const EnsCall &) = delete;
@@ -236,15 +230,11 @@ struct EnsCall {
             if (err == hipSuccess)
                 err = x;
         };
-        sync(also);
         if (failed)
             for (hipStream_t s : streams)
                 sync(s);
         sync(ls);
         // (also on an error: a launched member's table slot is released only once its reader has completed)
-        for (size_t k = 0; k < e->m.size() && onl_slots && ls; ++k)
-            if (e->grp[k] >= 0)
-                vsom_onl_tiny_done(e->m[k], e->lslot[k]);
         for (size_t i = 0; i < held.size() && ls; ++i)
             vsom_onl_tiny_done(held[i].first, held[i].second);
         return err;
@@ -326,6 +316,126 @@ static int ens_launch(EnsCall &call, EnsSet set, int ngroups, size_t stride, uns
     return VSOM_OK;
 }
 
+// The online chunk of every member, plain or with validity (DESIGN.md sections 4c, 4u); valid_host null: no member has
+// validity bytes.  Up to two ens_launch passes on one launch stream, each with its own descriptor slot: the plain members
+// that take online_tiny_chunk_many_kernel, then the masked members that take online_tiny_masked_chunk_many_kernel, whose
+// validity bytes form one pinned image in the second pass's slot, copied once.  Every other member runs its single call
+// while the launches run.  The callers have made their argument checks.
+static int ens_online_chunk(vsom_ensemble *e, const double *eta, const double *sigma, const int *decay_fn, int first_chunk,
+                            const uint8_t *const *valid_host, const int *one_mask, uint64_t *const *lastbmu_out,
+                            float *mse_out)
+{
+    const size_t n = e->m.size();
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    EnsCall call(e);
+    if (int rc = join_members(e, nullptr, true))
+        return rc;
+    // who is launched: 1 = a plain member on the one-launch chunk (prepared here), 2 = a masked one
+    const size_t pstride = vsom_onl_tiny_desc_bytes(false), mstride = vsom_onl_tiny_desc_bytes(true);
+    std::vector<int> how(n, 0);
+    std::vector<size_t> v_at(n, 0), vbytes(n, 0);
+    size_t vtotal = 0;
+    bool any_plain = false, any_masked = false;
+    ens_scratch(e, pstride);
+    for (size_t k = 0; k < n; ++k) {
+        vsom_ctx *c = e->m[k];
+        const bool masked = valid_host && valid_host[k];
+        if (!vsom_onl_tiny_fits(c, sigma[k], masked, e->lds_limit))
+            continue;                        // (a custom transformation among them): its own path
+        if (!masked) {
+            int lslot = 0;
+            if (int rc = vsom_onl_tiny_prepare(c, eta[k], sigma[k], decay_fn[k], first_chunk, lastbmu_out && lastbmu_out[k],
+                                               nullptr, 0, e->desc.data() + k * pstride, &e->grp[k], &e->smem[k], &lslot))
+                return rc;
+            how[k] = 1;
+            any_plain = true;
+            call.held.emplace_back(c, lslot);
+        } else {
+            how[k] = 2;
+            any_masked = true;
+            vbytes[k] = ((one_mask && one_mask[k]) ? 1 : c->B) * (size_t)c->J;
+            v_at[k] = vtotal;
+            vtotal += (vbytes[k] + 15) / 16 * 16;
+        }
+    }
+    int rc = VSOM_OK;
+    if (any_plain || any_masked) {
+        // one launch stream behind every launched member's stream, for both passes
+        std::vector<int> pgrp;
+        if (any_masked) {
+            pgrp = e->grp;
+            for (size_t k = 0; k < n; ++k)
+                if (how[k] == 2)
+                    e->grp[k] = 0;
+        }
+        if (int jrc = call.join(ENS_LAUNCHED))
+            return jrc;
+        if (any_masked)
+            e->grp = pgrp;
+    }
+    if (any_plain)
+        rc = ens_launch(
+            call, ENS_JOINED, VSOM_ONL_TINY_GROUPS, pstride, ENS_NO_CAP,
+            [&](int g) { return vsom_onl_tiny_ready(false, g, e->device, e->lds_limit); },
+            [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t s) {
+                return vsom_onl_tiny_launch_many(false, g, d, cnt, smem, s);
+            });
+    if (any_masked && !rc) {
+        // the slot ens_launch is about to take: its last launch has completed, so its image may be rewritten
+        auto &s = e->slot[e->next];
+        if (s.valid)
+            VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
+        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(s.img_host, vtotal), vsom_member(s.img_dev, vtotal)}));
+        for (size_t k = 0; k < n; ++k)
+            if (how[k] == 2)
+                std::memcpy(s.img_host.p + v_at[k], valid_host[k], vbytes[k]);
+        VSOM_HIP_CHECK(hipMemcpyAsync(s.img_dev.p, s.img_host.p, vtotal, hipMemcpyHostToDevice, call.ls));
+        ens_scratch(e, mstride);
+        for (size_t k = 0; k < n && !rc; ++k) {
+            if (how[k] != 2)
+                continue;
+            vsom_ctx *c = e->m[k];
+            int lslot = 0;
+            rc = vsom_onl_tiny_prepare(c, eta[k], sigma[k], decay_fn[k], first_chunk, lastbmu_out && lastbmu_out[k],
+                                       s.img_dev.p + v_at[k], one_mask ? one_mask[k] : 0, e->desc.data() + k * mstride,
+                                       &e->grp[k], &e->smem[k], &lslot);
+            if (!rc)
+                call.held.emplace_back(c, lslot);
+        }
+        if (!rc)
+            rc = ens_launch(
+                call, ENS_JOINED, VSOM_ONL_TINY_GROUPS, mstride, ENS_NO_CAP,
+                [&](int g) { return vsom_onl_tiny_ready(true, g, e->device, e->lds_limit); },
+                [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t st) {
+                    return vsom_onl_tiny_launch_many(true, g, d, cnt, smem, st);
+                });
+    }
+    // the other members through their single calls, while the launches run
+    for (size_t k = 0; k < n && !rc; ++k) {
+        if (how[k])
+            continue;
+        uint64_t *lb = lastbmu_out ? lastbmu_out[k] : nullptr;
+        float *mse = mse_out ? mse_out + k : nullptr;
+        rc = valid_host && valid_host[k]
+                 ? vsom_online_chunk_masked_member(e->m[k], eta[k], sigma[k], decay_fn[k], first_chunk, valid_host[k],
+                                                   one_mask ? one_mask[k] : 0, lb, mse)
+                 : vsom_train_online_chunk_fetch(e->m[k], eta[k], sigma[k], decay_fn[k], first_chunk, lb, mse);
+    }
+    if ((rc = call.end(rc)))
+        return rc;
+    // results of the launched members: the kernels stored them into each member's pinned words
+    for (size_t k = 0; k < n; ++k) {
+        if (!how[k])
+            continue;
+        vsom_ctx *c = e->m[k];
+        if (lastbmu_out && lastbmu_out[k])
+            std::memcpy(lastbmu_out[k], c->out_pinned.p, c->B * sizeof(uint64_t));
+        if (mse_out)
+            mse_out[k] = *static_cast<volatile float *>(c->mse.p);
+    }
+    return VSOM_OK;
+}
+
 int vsom_ensemble_train_online_chunk_fetch(vsom_ensemble *e, const double *eta, const double *sigma, const int *decay_fn,
                                            int first_chunk, uint64_t *const *lastbmu_out, float *mse_out)
 {
@@ -342,52 +452,9 @@ int vsom_ensemble_train_online_chunk_fetch(vsom_ensemble *e, const double *eta, 
         if (const char *why = ens_rows_refusal(c))
             return ens_fail(k, why);
     }
-    VSOM_HIP_CHECK(hipSetDevice(e->device));
-    EnsCall call(e);
-    call.onl_slots = true;
-    if (int rc = join_members(e, nullptr, true))
-        return rc;
-    const size_t stride = vsom_onl_tiny_desc_bytes();
-    ens_scratch(e, stride);
-    for (size_t k = 0; k < n; ++k) {
-        vsom_ctx *c = e->m[k];
-        if (c->cu)
-            continue;                        // custom transformation: its own path
-        const bool want_lb = lastbmu_out && lastbmu_out[k];
-        if (int rc = vsom_onl_tiny_prepare(c, eta[k], sigma[k], decay_fn[k], first_chunk, want_lb, e->lds_limit,
-                                           e->desc.data() + k * stride, &e->grp[k], &e->smem[k], &e->lslot[k]))
-            return rc;
-    }
-    int rc = ens_launch(
-        call, ENS_LAUNCHED, VSOM_ONL_TINY_GROUPS, stride, ENS_NO_CAP,
-        [&](int g) { return vsom_onl_tiny_ready(g, e->device, e->lds_limit); },
-        [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t s) {
-            return vsom_onl_tiny_launch_many(g, d, cnt, smem, s);
-        });
-    // the other members through their ordinary path, while the launches run
-    for (size_t k = 0; k < n && !rc; ++k)
-        if (e->grp[k] < 0)
-            rc = vsom_train_online_chunk_fetch(e->m[k], eta[k], sigma[k], decay_fn[k], first_chunk,
-                                               lastbmu_out ? lastbmu_out[k] : nullptr, mse_out ? mse_out + k : nullptr);
-    if ((rc = call.end(rc)))
-        return rc;
-    // results of the launched members: the kernels stored them into each member's pinned words
-    for (size_t k = 0; k < n; ++k) {
-        if (e->grp[k] < 0)
-            continue;
-        vsom_ctx *c = e->m[k];
-        if (lastbmu_out && lastbmu_out[k])
-            std::memcpy(lastbmu_out[k], c->out_pinned.p, c->B * sizeof(uint64_t));
-        if (mse_out)
-            mse_out[k] = *static_cast<volatile float *>(c->mse.p);
-    }
-    return VSOM_OK;
+    return ens_online_chunk(e, eta, sigma, decay_fn, first_chunk, nullptr, nullptr, lastbmu_out, mse_out);
 }
 
-// The online chunk with validity.  Two ens_launch passes on one launch stream, each with its own
-// descriptor slot: the plain members that take online_tiny_chunk_many_kernel (as vsom_ensemble_train_online_chunk_fetch
-// launches them), then the masked members that take online_tiny_masked_chunk_many_kernel, whose validity bytes form one
-// pinned image in the second pass's slot, copied once.  Every other member runs its single call while the launches run.
 int vsom_ensemble_train_online_chunk_masked(vsom_ensemble *e, const double *eta, const double *sigma, const int *decay_fn,
                                             int first_chunk, const uint8_t *const *valid_host, const int *one_mask,
                                             uint64_t *const *lastbmu_out, float *mse_out)
@@ -411,115 +478,7 @@ int vsom_ensemble_train_online_chunk_masked(vsom_ensemble *e, const double *eta,
         if (const char *why = ens_rows_refusal(c))
             return ens_fail(k, why);
     }
-    VSOM_HIP_CHECK(hipSetDevice(e->device));
-    EnsCall call(e);
-    if (int rc = join_members(e, nullptr, true))
-        return rc;
-    // who is launched: 1 = a plain member on the one-launch chunk, 2 = a masked one
-    const size_t pstride = vsom_onl_tiny_desc_bytes(), mstride = vsom_onl_tiny_masked_desc_bytes();
-    std::vector<int> how(n, 0), pgrp(n, -1);
-    std::vector<size_t> psmem(n, 0), v_at(n, 0), vbytes(n, 0);
-    std::vector<unsigned char> pdesc(n * pstride);
-    size_t vtotal = 0;
-    bool any_plain = false, any_masked = false;
-    for (size_t k = 0; k < n; ++k) {
-        vsom_ctx *c = e->m[k];
-        if (c->cu)
-            continue;                        // custom transformation: its own path
-        const bool want_lb = lastbmu_out && lastbmu_out[k];
-        if (!valid_host[k]) {
-            int lslot = 0;
-            if (int rc = vsom_onl_tiny_prepare(c, eta[k], sigma[k], decay_fn[k], first_chunk, want_lb, e->lds_limit,
-                                               pdesc.data() + k * pstride, &pgrp[k], &psmem[k], &lslot))
-                return rc;
-            if (pgrp[k] >= 0) {
-                how[k] = 1;
-                any_plain = true;
-                call.held.emplace_back(c, lslot);
-            }
-        } else if (vsom_onl_tiny_masked_fits(c, sigma[k], e->lds_limit)) {
-            how[k] = 2;
-            any_masked = true;
-            vbytes[k] = ((one_mask && one_mask[k]) ? 1 : c->B) * (size_t)c->J;
-            v_at[k] = vtotal;
-            vtotal += (vbytes[k] + 15) / 16 * 16;
-        }
-    }
-    int rc = VSOM_OK;
-    if (any_plain || any_masked) {
-        // one launch stream behind every launched member's stream, for both passes
-        ens_scratch(e, pstride);
-        for (size_t k = 0; k < n; ++k)
-            e->grp[k] = how[k] ? 0 : -1;
-        if (int jrc = call.join(ENS_LAUNCHED))
-            return jrc;
-    }
-    if (any_plain) {
-        for (size_t k = 0; k < n; ++k) {
-            e->grp[k] = how[k] == 1 ? pgrp[k] : -1;
-            e->smem[k] = psmem[k];
-        }
-        e->desc = pdesc;
-        rc = ens_launch(
-            call, ENS_JOINED, VSOM_ONL_TINY_GROUPS, pstride, ENS_NO_CAP,
-            [&](int g) { return vsom_onl_tiny_ready(g, e->device, e->lds_limit); },
-            [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t s) {
-                return vsom_onl_tiny_launch_many(g, d, cnt, smem, s);
-            });
-    }
-    if (any_masked && !rc) {
-        // the slot ens_launch is about to take: its last launch has completed, so its image may be rewritten
-        auto &s = e->slot[e->next];
-        if (s.valid)
-            VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
-        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(s.img_host, vtotal), vsom_member(s.img_dev, vtotal)}));
-        for (size_t k = 0; k < n; ++k)
-            if (how[k] == 2)
-                std::memcpy(s.img_host.p + v_at[k], valid_host[k], vbytes[k]);
-        VSOM_HIP_CHECK(hipMemcpyAsync(s.img_dev.p, s.img_host.p, vtotal, hipMemcpyHostToDevice, call.ls));
-        ens_scratch(e, mstride);
-        for (size_t k = 0; k < n && !rc; ++k) {
-            if (how[k] != 2)
-                continue;
-            vsom_ctx *c = e->m[k];
-            int lslot = 0;
-            rc = vsom_onl_tiny_masked_prepare(c, eta[k], sigma[k], decay_fn[k], first_chunk, lastbmu_out && lastbmu_out[k],
-                                              s.img_dev.p + v_at[k], one_mask ? one_mask[k] : 0,
-                                              e->desc.data() + k * mstride, &e->grp[k], &e->smem[k], &lslot);
-            if (!rc)
-                call.held.emplace_back(c, lslot);
-        }
-        if (!rc)
-            rc = ens_launch(
-                call, ENS_JOINED, VSOM_ONL_TINY_GROUPS, mstride, ENS_NO_CAP,
-                [&](int g) { return vsom_onl_tiny_masked_ready(g, e->device, e->lds_limit); },
-                [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t st) {
-                    return vsom_onl_tiny_masked_launch_many(g, d, cnt, smem, st);
-                });
-    }
-    // the other members through their single calls, while the launches run
-    for (size_t k = 0; k < n && !rc; ++k) {
-        if (how[k])
-            continue;
-        uint64_t *lb = lastbmu_out ? lastbmu_out[k] : nullptr;
-        float *mse = mse_out ? mse_out + k : nullptr;
-        rc = valid_host[k] ? vsom_online_chunk_masked_member(e->m[k], eta[k], sigma[k], decay_fn[k], first_chunk, valid_host[k],
-                                                             one_mask ? one_mask[k] : 0, lb, mse)
-                           : vsom_train_online_chunk_fetch(e->m[k], eta[k], sigma[k], decay_fn[k], first_chunk, lb, mse);
-    }
-    if ((rc = call.end(rc)))
-        return rc;
-    // results of the launched members: the kernels stored them into each member's pinned words
-    for (size_t k = 0; k < n; ++k) {
-        if (!how[k])
-            continue;
-        vsom_ctx *c = e->m[k];
-        if (lastbmu_out && lastbmu_out[k])
-            std::memcpy(lastbmu_out[k], c->out_pinned.p, c->B * sizeof(uint64_t));
-        if (mse_out)
-            mse_out[k] = *static_cast<volatile float *>(c->mse.p);
-    }
-    return VSOM_OK;
+    return ens_online_chunk(e, eta, sigma, decay_fn, first_chunk, valid_host, one_mask, lastbmu_out, mse_out);
 }
 
 int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_first, float *mse_out)
@@ -562,9 +521,117 @@ int vsom_ensemble_batch_epoch(vsom_ensemble *e, const double *sigma, int is_firs
     return VSOM_OK;
 }
 
-// vsom_batch_schedule for every member.  The members on the fast path of that call go as rounds of
-// at most VSOM_SCHEDULE_MAX_EPOCHS epochs: per round one table copy and one launch per kind, each workgroup looping its own
-// count.  A call within the cap is one round and one wait; a further round waits for the one before it.
+// The schedule calls (DESIGN.md sections 4m, 4t), one routine over the flavour of the launched members: plain
+// (vsom_ensemble_batch_schedule: the members on the fast path of vsom_batch_schedule) or masked (the masked train calls:
+// the members with validity bytes on the fast path of vsom_batch_schedule_masked; an epoch is a schedule of one epoch whose
+// `first` is the call's is_first).  They go as rounds of at most VSOM_SCHEDULE_MAX_EPOCHS epochs, one launch per kind and
+// round, each workgroup looping its own count; the round's image (vsom_sched_round.hpp: tables, every member's table
+// offsets, the masked members' validity bytes) is pinned in the round's descriptor slot and copied once on the launch
+// stream, so a round is ordered behind the one two before it by the slot's event and nothing else waits between rounds.
+// Every other member -- off the fast path, or a plain one in a masked call (valid_host[k] null) -- runs single(k), its
+// single-context call, in the same call.  `what`: the entry point, for the refusal's text.
+template <typename Single>
+static int ens_schedule_train(vsom_ensemble *e, bool masked, const char *what, const double *const *sigma,
+                              const size_t *epochs, int first, int reset_bmu, const uint8_t *const *valid_host,
+                              const int *one_mask, float *const *mse_out, Single single)
+{
+    const size_t n = e->m.size();
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    EnsCall call(e);
+    if (int rc = join_members(e, epochs, true))   // (a member without epochs is not touched)
+        return rc;
+    // who is launched
+    const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);   // (no attribute is raised for the batch kernels)
+    std::vector<int> kind(n, -1);
+    std::vector<VsomSchedMember> mem(n);
+    size_t longest = 0;
+    bool any = false;
+    for (size_t k = 0; k < n; ++k) {
+        vsom_ctx *c = e->m[k];
+        const int one = masked && one_mask ? one_mask[k] : 0;
+        mem[k] = VsomSchedMember{0, 0, nullptr, 0, nullptr, 0};
+        if (!epochs[k])
+            continue;
+        if (masked ? !valid_host[k] || !vsom_tiny_masked_schedule_applies(c, one, sigma[k], epochs[k], lds_cap)
+                   : !vsom_tiny_schedule_applies(c, sigma[k], epochs[k], lds_cap))
+            continue;
+        kind[k] = c->transform;
+        vsom_lut_dims(c, &mem[k].lw, &mem[k].lh);
+        if (masked) {
+            mem[k].valid = valid_host[k];
+            mem[k].vbytes = (one ? 1 : c->B) * (size_t)c->J;
+        }
+        longest = std::max(longest, epochs[k]);
+        any = true;
+    }
+    int rc = VSOM_OK;
+    if (any) {
+        for (size_t k = 0; k < n; ++k)
+            if (kind[k] >= 0)
+                VSOM_ALLOC_CHECK(vsom_grow(e->m[k]->sch_mse, epochs[k], e->m[k]->stream, VSOM_BUF_SYNC));
+        const size_t stride = masked ? vsom_tiny_masked_sched_desc_bytes() : vsom_tiny_sched_desc_bytes();
+        VsomSchedRound round;
+        for (size_t e0 = 0; e0 < longest && !rc; e0 += VSOM_SCHEDULE_MAX_EPOCHS) {
+            for (size_t k = 0; k < n; ++k)
+                if (kind[k] >= 0) {
+                    mem[k].sigma = sigma[k] + std::min(e0, epochs[k]);
+                    mem[k].epochs = epochs[k] > e0 ? std::min(epochs[k] - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS) : 0;
+                }
+            if (!round.plan(mem.data(), n)) {
+                rc = vsom_fail(VSOM_ERR_INVALID, std::string(what) + ": the tables of one round exceed 2^32 values");
+                break;
+            }
+            // (a member whose schedule has ended stays in the launches with no epochs: every round then has the same
+            //  launch stream, and the rounds stay ordered)
+            ens_scratch(e, stride);
+            for (size_t k = 0; k < n; ++k)
+                e->grp[k] = kind[k];
+            if (int jrc = call.join(ENS_LAUNCHED))
+                return jrc;
+            // the slot ens_launch is about to take: its last launch has completed, so its image may be rewritten
+            auto &s = e->slot[e->next];
+            if (s.valid)
+                VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
+            const size_t bytes = round.bytes();
+            VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(s.img_host, bytes), vsom_member(s.img_dev, bytes)}));
+            round.write(s.img_host.p, mem.data());
+            VSOM_HIP_CHECK(hipMemcpyAsync(s.img_dev.p, s.img_host.p, bytes, hipMemcpyHostToDevice, call.ls));
+            const float *lut_dev = reinterpret_cast<const float *>(s.img_dev.p);
+            const unsigned *tab_dev = reinterpret_cast<const unsigned *>(s.img_dev.p + round.table_bytes());
+            const unsigned char *v_dev = s.img_dev.p + round.table_bytes() + round.offset_bytes();
+            for (size_t k = 0; k < n; ++k) {
+                if (kind[k] < 0)
+                    continue;
+                vsom_ctx *c = e->m[k];
+                const size_t cnt = mem[k].epochs;
+                const unsigned *tab_k = tab_dev + (cnt ? round.tab_at[k] : 0);
+                float *mse_k = c->sch_mse.p + (cnt ? e0 : 0);
+                void *desc = e->desc.data() + k * stride;
+                if (masked)
+                    vsom_tiny_masked_sched_fill(c, v_dev + (cnt ? round.v_at[k] : 0), one_mask ? one_mask[k] : 0, lds_cap,
+                                                lut_dev, tab_k, mse_k, cnt, e0 == 0 && first, reset_bmu, desc, &e->smem[k]);
+                else
+                    vsom_tiny_sched_fill(c, lut_dev, tab_k, mse_k, cnt, e0 == 0 && first, reset_bmu, desc, &e->smem[k]);
+            }
+            rc = ens_launch(call, ENS_JOINED, VSOM_TINY_GROUPS, stride, ENS_NO_CAP, ens_always_ready,
+                            [masked](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t st) {
+                                return masked ? vsom_tiny_masked_sched_launch_many(g, d, cnt, smem, st)
+                                              : vsom_tiny_sched_launch_many(g, d, cnt, smem, st);
+                            });
+        }
+    }
+    // the other members through their single calls, while the launches run
+    for (size_t k = 0; k < n && !rc; ++k)
+        if (kind[k] < 0 && epochs[k])
+            rc = single(k);
+    if ((rc = call.end(rc)))
+        return rc;
+    for (size_t k = 0; k < n; ++k)
+        if (kind[k] >= 0)
+            vsom_schedule_results(e->m[k], epochs[k], mse_out[k]);
+    return VSOM_OK;
+}
+
 int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma, const size_t *epochs, int reset_bmu,
                                  float *const *mse_out)
 {
@@ -581,198 +648,13 @@ int vsom_ensemble_batch_schedule(vsom_ensemble *e, const double *const *sigma, c
         if (const char *why = vsom_schedule_refusal(e->m[k]))
             return ens_fail(k, why);
     }
-    VSOM_HIP_CHECK(hipSetDevice(e->device));
-    EnsCall call(e);
-    if (int rc = join_members(e, epochs, true))   // (a member without epochs is not touched)
-        return rc;
-    // who is launched
-    const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);
-    std::vector<int> kind(n, -1);
-    size_t longest = 0;
-    vsom_ctx *first_launched = nullptr;
-    for (size_t k = 0; k < n; ++k) {
-        vsom_ctx *c = e->m[k];
-        if (!epochs[k] || !vsom_tiny_schedule_applies(c, sigma[k], epochs[k], lds_cap))
-            continue;
-        kind[k] = c->transform;
-        longest = std::max(longest, epochs[k]);
-        if (!first_launched)
-            first_launched = c;
-    }
-    int rc = VSOM_OK;
-    if (first_launched) {
-        for (size_t k = 0; k < n; ++k)
-            if (kind[k] >= 0)
-                VSOM_ALLOC_CHECK(vsom_grow(e->m[k]->sch_mse, epochs[k], e->m[k]->stream, VSOM_BUF_SYNC));
-        call.also = first_launched->stream;  // the table copies below
-        const size_t stride = vsom_tiny_sched_desc_bytes();
-        std::vector<size_t> tab_at(n, 0);    // the member's first offset word of the round
-        std::vector<unsigned> tab;
-        for (size_t e0 = 0; e0 < longest && !rc; e0 += VSOM_SCHEDULE_MAX_EPOCHS) {
-            // the round's tables: one per distinct (shape, sigma) over all launched members
-            VsomSchedTables tabs;
-            tab.clear();
-            for (size_t k = 0; k < n; ++k) {
-                if (kind[k] < 0 || epochs[k] <= e0)
-                    continue;
-                uint32_t lw, lh;
-                vsom_lut_dims(e->m[k], &lw, &lh);
-                tab_at[k] = tab.size();
-                const size_t cnt = std::min(epochs[k] - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS);
-                for (size_t ep = 0; ep < cnt; ++ep)
-                    tab.push_back((unsigned)tabs.add(lw, lh, sigma[k][e0 + ep]));
-            }
-            if (tabs.floats > 0xFFFFFFFFull) {
-                rc = vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble_batch_schedule: the tables of one round exceed 2^32 values");
-                break;
-            }
-            if (e0) {                        // the previous round has read the image and the device buffer
-                VSOM_HIP_CHECK(hipStreamSynchronize(first_launched->stream));
-                VSOM_HIP_CHECK(hipStreamSynchronize(call.ls));
-            }
-            // (no kernel of an earlier call or round is running now)
-            const size_t bytes = (tabs.floats + tab.size()) * sizeof(float);
-            VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(e->sch_host, bytes), vsom_member(e->sch_dev, bytes)}));
-            tabs.tabulate(reinterpret_cast<float *>(e->sch_host.p));
-            std::memcpy(e->sch_host.p + tabs.floats * sizeof(float), tab.data(), tab.size() * sizeof(unsigned));
-            // on a launched member's stream: the launch stream is that stream, or waits for an event recorded behind this copy
-            VSOM_HIP_CHECK(hipMemcpyAsync(e->sch_dev.p, e->sch_host.p, bytes, hipMemcpyHostToDevice, first_launched->stream));
-            const float *lut_dev = reinterpret_cast<const float *>(e->sch_dev.p);
-            const unsigned *tab_dev = reinterpret_cast<const unsigned *>(e->sch_dev.p + tabs.floats * sizeof(float));
-            ens_scratch(e, stride);
-            for (size_t k = 0; k < n; ++k) {
-                if (kind[k] < 0)
-                    continue;
-                // (a member whose schedule has ended stays in the launches with no epochs: every round then has the
-                //  same launch stream, and the rounds stay ordered)
-                vsom_ctx *c = e->m[k];
-                const size_t cnt = epochs[k] > e0 ? std::min(epochs[k] - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS) : 0;
-                e->grp[k] = vsom_tiny_sched_fill(c, lut_dev, tab_dev + (cnt ? tab_at[k] : 0), c->sch_mse.p + (cnt ? e0 : 0), cnt,
-                                                 e0 == 0, reset_bmu, e->desc.data() + k * stride, &e->smem[k]);
-            }
-            rc = ens_launch(call, ENS_LAUNCHED, VSOM_TINY_GROUPS, stride, ENS_NO_CAP, ens_always_ready,
-                            [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t s) {
-                                return vsom_tiny_sched_launch_many(g, d, cnt, smem, s);
-                            });
-        }
-    }
-    // the other members through the sequence of single epochs, while the launches run
-    for (size_t k = 0; k < n && !rc; ++k)
-        if (kind[k] < 0 && epochs[k])
-            rc = vsom_schedule_loop(e->m[k], sigma[k], epochs[k], reset_bmu, mse_out[k]);
-    if ((rc = call.end(rc)))
-        return rc;
-    for (size_t k = 0; k < n; ++k)
-        if (kind[k] >= 0)
-            vsom_schedule_results(e->m[k], epochs[k], mse_out[k]);
-    return VSOM_OK;
-}
-
-// The masked train calls.  Both forms are one routine: an epoch is a schedule of one epoch whose
-// `first` is the call's is_first.  Masked members on the fast path of vsom_batch_schedule_masked go as rounds of at most
-// VSOM_SCHEDULE_MAX_EPOCHS epochs, one launch per kind and round; per round the tables (one per distinct (shape, sigma)),
-// every member's table offsets and the members' validity bytes form one pinned image in the round's descriptor slot,
-// copied once on the launch stream.  Every other member -- a plain one (valid_host[k] null), a masked one off the fast
-// path -- runs single(k), its single-context call, in the same call.
-template <typename Single>
-static int ens_masked_train(vsom_ensemble *e, const double *const *sigma, const size_t *epochs, int first, int reset_bmu,
-                            const uint8_t *const *valid_host, const int *one_mask, float *const *mse_out, Single single)
-{
-    const size_t n = e->m.size();
-    VSOM_HIP_CHECK(hipSetDevice(e->device));
-    EnsCall call(e);
-    if (int rc = join_members(e, epochs, true))   // (a member without epochs is not touched)
-        return rc;
-    const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);
-    std::vector<int> kind(n, -1);
-    std::vector<size_t> vbytes(n, 0);
-    size_t longest = 0;
-    bool any = false;
-    for (size_t k = 0; k < n; ++k) {
-        vsom_ctx *c = e->m[k];
-        const int one = one_mask ? one_mask[k] : 0;
-        if (!epochs[k] || !valid_host[k] || !vsom_tiny_masked_schedule_applies(c, one, sigma[k], epochs[k], lds_cap))
-            continue;
-        kind[k] = c->transform;
-        vbytes[k] = (one ? 1 : c->B) * (size_t)c->J;
-        longest = std::max(longest, epochs[k]);
-        any = true;
-    }
-    int rc = VSOM_OK;
-    if (any) {
-        for (size_t k = 0; k < n; ++k)
-            if (kind[k] >= 0)
-                VSOM_ALLOC_CHECK(vsom_grow(e->m[k]->sch_mse, epochs[k], e->m[k]->stream, VSOM_BUF_SYNC));
-        const size_t stride = vsom_tiny_masked_sched_desc_bytes();
-        std::vector<size_t> tab_at(n, 0), v_at(n, 0);
-        std::vector<unsigned> tab;
-        for (size_t e0 = 0; e0 < longest && !rc; e0 += VSOM_SCHEDULE_MAX_EPOCHS) {
-            VsomSchedTables tabs;
-            tab.clear();
-            size_t vtotal = 0;
-            for (size_t k = 0; k < n; ++k) {
-                if (kind[k] < 0 || epochs[k] <= e0)
-                    continue;
-                uint32_t lw, lh;
-                vsom_lut_dims(e->m[k], &lw, &lh);
-                tab_at[k] = tab.size();
-                const size_t cnt = std::min(epochs[k] - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS);
-                for (size_t ep = 0; ep < cnt; ++ep)
-                    tab.push_back((unsigned)tabs.add(lw, lh, sigma[k][e0 + ep]));
-                v_at[k] = vtotal;
-                vtotal += vbytes[k];
-            }
-            if (tabs.floats > 0xFFFFFFFFull) {
-                rc = vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: the tables of one round exceed 2^32 values");
-                break;
-            }
-            // (a member whose schedule has ended stays in the launches with no epochs: every round then has the same
-            //  launch stream, and the rounds stay ordered)
-            ens_scratch(e, stride);
-            for (size_t k = 0; k < n; ++k)
-                if (kind[k] >= 0)
-                    e->grp[k] = kind[k];
-            if (int jrc = call.join(ENS_LAUNCHED))
-                return jrc;
-            // the slot ens_launch is about to take: its last launch has completed, so its image may be rewritten
-            auto &s = e->slot[e->next];
-            if (s.valid)
-                VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
-            const size_t tbytes = (tabs.floats + tab.size()) * sizeof(float), bytes = tbytes + vtotal;
-            VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(s.img_host, bytes), vsom_member(s.img_dev, bytes)}));
-            tabs.tabulate(reinterpret_cast<float *>(s.img_host.p));
-            std::memcpy(s.img_host.p + tabs.floats * sizeof(float), tab.data(), tab.size() * sizeof(unsigned));
-            for (size_t k = 0; k < n; ++k)
-                if (kind[k] >= 0 && epochs[k] > e0)
-                    std::memcpy(s.img_host.p + tbytes + v_at[k], valid_host[k], vbytes[k]);
-            VSOM_HIP_CHECK(hipMemcpyAsync(s.img_dev.p, s.img_host.p, bytes, hipMemcpyHostToDevice, call.ls));
-            const float *lut_dev = reinterpret_cast<const float *>(s.img_dev.p);
-            const unsigned *tab_dev = reinterpret_cast<const unsigned *>(s.img_dev.p + tabs.floats * sizeof(float));
-            for (size_t k = 0; k < n; ++k) {
-                if (kind[k] < 0)
-                    continue;
-                vsom_ctx *c = e->m[k];
-                const size_t cnt = epochs[k] > e0 ? std::min(epochs[k] - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS) : 0;
-                vsom_tiny_masked_sched_fill(c, s.img_dev.p + tbytes + (cnt ? v_at[k] : 0), one_mask ? one_mask[k] : 0, lds_cap,
-                                            lut_dev, tab_dev + (cnt ? tab_at[k] : 0), c->sch_mse.p + (cnt ? e0 : 0), cnt,
-                                            e0 == 0 && first, reset_bmu, e->desc.data() + k * stride, &e->smem[k]);
-            }
-            rc = ens_launch(call, ENS_JOINED, VSOM_TINY_GROUPS, stride, ENS_NO_CAP, ens_always_ready,
-                            [](int g, const void *d, unsigned cnt, size_t smem, unsigned, hipStream_t st) {
-                                return vsom_tiny_masked_sched_launch_many(g, d, cnt, smem, st);
-                            });
-        }
-    }
-    // the other members through their single calls, while the launches run
-    for (size_t k = 0; k < n && !rc; ++k)
-        if (kind[k] < 0 && epochs[k])
-            rc = single(k);
-    if ((rc = call.end(rc)))
-        return rc;
-    for (size_t k = 0; k < n; ++k)
-        if (kind[k] >= 0)
-            vsom_schedule_results(e->m[k], epochs[k], mse_out[k]);
-    return VSOM_OK;
+    // the members off the fast path through the sequence of single epochs
+    return ens_schedule_train(e, false, "vsom_ensemble_batch_schedule", sigma, epochs, 1, reset_bmu, nullptr, nullptr, mse_out,
+                              [&](size_t k) {
+                                  return vsom_schedule_loop(e->m[k], epochs[k], reset_bmu, [&](size_t ep) {
+                                      return vsom_batch_epoch(e->m[k], sigma[k][ep], ep == 0, &mse_out[k][ep]);
+                                  });
+                              });
 }
 
 // what both masked forms refuse for member k (its chunk, and for a masked member its kind), or null
@@ -805,12 +687,12 @@ int vsom_ensemble_batch_epoch_masked(vsom_ensemble *e, const double *sigma, int 
         sig[k] = sigma + k;
         msep[k] = &mse[k];
     }
-    const int rc = ens_masked_train(e, sig.data(), epochs.data(), is_first ? 1 : 0, 0, valid_host, one_mask, msep.data(),
-                                    [&](size_t k) {
-                                        return valid_host[k] ? vsom_batch_epoch_masked(e->m[k], sigma[k], is_first, valid_host[k],
-                                                                                       one_mask ? one_mask[k] : 0, msep[k])
-                                                             : vsom_batch_epoch(e->m[k], sigma[k], is_first, msep[k]);
-                                    });
+    const int rc = ens_schedule_train(e, true, "vsom_ensemble", sig.data(), epochs.data(), is_first ? 1 : 0, 0, valid_host,
+                                      one_mask, msep.data(), [&](size_t k) {
+                                          return valid_host[k] ? vsom_batch_epoch_masked(e->m[k], sigma[k], is_first, valid_host[k],
+                                                                                         one_mask ? one_mask[k] : 0, msep[k])
+                                                               : vsom_batch_epoch(e->m[k], sigma[k], is_first, msep[k]);
+                                      });
     if (rc)
         return rc;
     if (mse_out)
@@ -836,7 +718,7 @@ int vsom_ensemble_batch_schedule_masked(vsom_ensemble *e, const double *const *s
         if (const char *why = ens_masked_refusal(e->m[k], valid_host[k]))
             return ens_fail(k, why);
     }
-    return ens_masked_train(e, sigma, epochs, 1, reset_bmu, valid_host, one_mask, mse_out, [&](size_t k) {
+    return ens_schedule_train(e, true, "vsom_ensemble", sigma, epochs, 1, reset_bmu, valid_host, one_mask, mse_out, [&](size_t k) {
         return valid_host[k] ? vsom_batch_schedule_masked(e->m[k], sigma[k], epochs[k], reset_bmu, valid_host[k],
                                                           one_mask ? one_mask[k] : 0, mse_out[k])
                              : vsom_batch_schedule(e->m[k], sigma[k], epochs[k], reset_bmu, mse_out[k]);

@@ -23,6 +23,7 @@
 
 #include "../../include/vsom_hip.h"
 #include "vsom_buf.hpp"
+#include "vsom_sched_round.hpp"
 
 typedef unsigned long long u64;
 
@@ -126,8 +127,6 @@ struct vsom_ctx {
     DevBuf<u64> dd_hash; DevBuf<int> dd_rep, dd_list;
     bool dedupe = true;             // VSOM_NO_DEDUPE=1 switches it off (A/B measurements)
     double dd_min_work = 2.0e10;    // exact searches of at least this many (sample, node, value) triples (vsom_set_row_dedupe)
-    bool tiny_lds_attr[12] = {};    // online_tiny_chunk_kernel<kind, local, U>: dynamic LDS limit raised (per context: its device, its kind)
-    bool tiny_masked_lds_attr[6] = {};   // online_tiny_masked_chunk_kernel<kind, local, U>: the same, [local][U]
 
     // MFMA shortlist scratch
     DevBuf<float> sl_G, sl_nrm; DevBuf<unsigned> sl_scal;
@@ -561,23 +560,19 @@ int launch_tiny_epoch(vsom_ctx *c, double sigma, int is_first);   // whole batch
 // `desc` and its kernel instantiation into *group, or *group = -1 when the member's single call would not take the
 // one-launch kernel or its LDS need exceeds lds_limit (the member takes its ordinary path)
 constexpr int VSOM_ONL_TINY_GROUPS = 12, VSOM_TINY_GROUPS = 3;
-size_t vsom_onl_tiny_desc_bytes();  // (descriptors are packed at exactly this size: the kernels index args[blockIdx.x])
+// The one-launch online chunk (vsom_online_tiny.hip), plain or over valid entries (`masked`): the same
+// 12 groups, a descriptor size per flavour.  fits: the member is loaded, not custom, its single call would take the
+// one-launch kernel and its LDS need (+ the static key slots) is within lds_limit -- vsom_online_masked_tiny_applies'
+// conditions for the masked flavour.  prepare, for a member that fits: valid_dev = its validity bytes on the device
+// (B x J, or J with one_mask), or null for the plain chunk.
+bool vsom_onl_tiny_fits(const vsom_ctx *c, double sigma, bool masked, size_t lds_limit);
+size_t vsom_onl_tiny_desc_bytes(bool masked);  // (descriptors are packed at exactly this size: the kernels index args[blockIdx.x])
 int vsom_onl_tiny_prepare(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk, bool want_lb,
-                          size_t lds_limit, void *desc, int *group, size_t *smem, int *lut_slot);
-// before any launch of the call: the instantiation's dynamic LDS limit (process-wide, raised only; vsom_online_tiny.hip)
-int vsom_onl_tiny_ready(int group, int device, size_t lds_limit);
-int vsom_onl_tiny_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
+                          const unsigned char *valid_dev, int one_mask, void *desc, int *group, size_t *smem, int *lut_slot);
+// before any launch of the call: the kernel's dynamic LDS limit (process-wide per device and kernel, raised only)
+int vsom_onl_tiny_ready(bool masked, int group, int device, size_t lds_limit);
+int vsom_onl_tiny_launch_many(bool masked, int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
 void vsom_onl_tiny_done(vsom_ctx *c, int lut_slot);
-// the one-launch chunk over valid entries (vsom_online_tiny_masked.hip): the same groups, a descriptor
-// of its own.  fits: vsom_online_masked_tiny_applies' conditions with the LDS need (+ the static key slots) within lds_limit;
-// prepare (for a member that fits): valid_dev = its validity bytes on the device (B x J, or J with one_mask)
-bool vsom_onl_tiny_masked_fits(const vsom_ctx *c, double sigma, size_t lds_limit);
-size_t vsom_onl_tiny_masked_desc_bytes();
-int vsom_onl_tiny_masked_prepare(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk, bool want_lb,
-                                 const unsigned char *valid_dev, int one_mask, void *desc, int *group, size_t *smem,
-                                 int *lut_slot);
-int vsom_onl_tiny_masked_ready(int group, int device, size_t lds_limit);
-int vsom_onl_tiny_masked_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
 // vsom_train_online_chunk_masked for a member of an ensemble (vsom_online.hip): every refusal but that of the membership
 int vsom_online_chunk_masked_member(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk,
                                     const uint8_t *valid_host, int one_mask, uint64_t *lastbmu_out, float *mse_out);
@@ -587,13 +582,7 @@ int vsom_tiny_launch_many(int group, const void *desc_dev, unsigned count, size_
 
 // whole schedules in one launch (vsom_batch_schedule, vsom_ensemble_batch_schedule; vsom_tiny.hip)
 void vsom_lut_dims(const vsom_ctx *c, uint32_t *lw, uint32_t *lh);   // the shape of the context's neighbourhood table
-// the tables of a call: one per distinct (lut_w, lut_h, sigma), packed in the order of first use
-struct VsomSchedTables {
-    std::map<std::tuple<uint32_t, uint32_t, uint64_t>, size_t> at;   // (shape, sigma's bits) -> the table's first float
-    size_t floats = 0;
-    size_t add(uint32_t w, uint32_t h, double sigma);                // the table's first float
-    void tabulate(float *host) const;                                // every table, as ensure_lut fills one
-};
+// (the round image -- tables, table offsets, validity bytes -- is vsom_sched_round.hpp's)
 const char *vsom_schedule_refusal(const vsom_ctx *c);                // why a schedule call refuses this context, or null
 // the fast path applies: the single epoch would take the one-launch kernel within lds_limit, and every sigma is finite
 bool vsom_tiny_schedule_applies(const vsom_ctx *c, const double *sigma, size_t epochs, size_t lds_limit);
@@ -603,8 +592,29 @@ size_t vsom_tiny_sched_desc_bytes();
 int vsom_tiny_sched_fill(vsom_ctx *c, const float *lut_dev, const unsigned *tab_dev, float *mse, size_t epochs, int first,
                          int reset_bmu, void *desc, size_t *smem);
 int vsom_tiny_sched_launch_many(int group, const void *desc_dev, unsigned count, size_t smem, hipStream_t s);
-// the schedule as the sequence of single epochs (contexts off the fast path)
-int vsom_schedule_loop(vsom_ctx *c, const double *sigma, size_t epochs, int reset_bmu, float *mse_out);
+// the contract itself, what every context off the fast path runs: the schedule as the sequence of single epochs,
+// epoch(ep) = the flavour's single-epoch call
+template <typename Epoch>
+int vsom_schedule_loop(vsom_ctx *c, size_t epochs, int reset_bmu, Epoch epoch)
+{
+    for (size_t ep = 0; ep < epochs; ++ep) {
+        if (ep > 0 && reset_bmu && c->B) {
+            VSOM_HIP_CHECK(hipSetDevice(c->device));
+            VSOM_HIP_CHECK(hipMemsetAsync(c->lastbmu.p, 0, c->B * sizeof(uint64_t), c->stream));
+        }
+        if (int rc = epoch(ep))
+            return rc;
+    }
+    return VSOM_OK;
+}
+// The fast path of a single context's schedule, plain or masked: rounds of at most VSOM_SCHEDULE_MAX_EPOCHS epochs, per
+// round one image (vsom_sched_round.hpp) copied once and launch(...) = the flavour's descriptor and its kernel on
+// c->stream; then the wait and the results.  valid_host non-null: the validity bytes are copied to the device once, before
+// the rounds, and handed to every launch as valid_dev.
+typedef int (*VsomSchedLaunch)(vsom_ctx *c, const unsigned char *valid_dev, int one_mask, const float *lut_dev,
+                               const unsigned *tab_dev, float *mse, size_t epochs, int first, int reset_bmu);
+int vsom_schedule_rounds(vsom_ctx *c, const double *sigma, size_t epochs, int reset_bmu, const uint8_t *valid_host,
+                         int one_mask, float *mse_out, VsomSchedLaunch launch);
 // after the wait behind the launches: sch_mse[0 .. epochs) into mse_out, the last one into the word vsom_get_mse reads
 void vsom_schedule_results(vsom_ctx *c, size_t epochs, float *mse_out);
 

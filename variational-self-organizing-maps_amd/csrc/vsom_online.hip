@@ -3,10 +3,9 @@
 //   vsom_online.hpp       what the files share: the onl_state layout, OnlineArgs, the window update of one node
 //   vsom_online_i8.hip    the image-bounded search of the chunk loop (sigma > 1, Standard / Median): onl_fused_kernel,
 //                         onl_refine_kernel and their per-chunk passes, enqueue_chunk_i8, vsom_get_online_search_stats
-//   vsom_online_tiny.hip  tiny maps: the whole chunk loop in one launch of one workgroup (online_tiny_chunk_kernel), and
-//                         one workgroup per map for ensembles (vsom_onl_tiny_*)
-//   vsom_online_tiny_masked.hip  the one-launch chunk over the valid entries of the rows only, for the same tiny maps
-//                         (online_tiny_masked_chunk_kernel; vsom_onl_tiny_masked_* for ensembles)
+//   vsom_online_tiny.hip  tiny maps: the whole chunk loop in one launch of one workgroup, plain (online_tiny_chunk_kernel)
+//                         and over the valid entries of the rows only (online_tiny_masked_chunk_kernel), and one
+//                         workgroup per map for ensembles (vsom_onl_tiny_*)
 //   vsom_online_masked.hip the chunk loop over the valid entries of the rows only (Standard / Median): the masked scan,
 //                         window and one-launch step of vsom_train_online_chunk_masked, enqueue_chunk_masked
 //   vsom_single.hip       single-vector queries: vsom_find_bmu, vsom_find_restricted_bmu, vsom_distances_single,
@@ -484,7 +483,7 @@ extern "C" {
 // c->out_pinned.p itself (else the caller fetches it with vsom_get_last_bmu)
 // masked: vsom_train_online_chunk_masked -- the same preamble with the validity bytes valid_host (B x J, or J with one_mask)
 // copied into the query arena, then one of two loops: where vsom_online_masked_tiny_applies holds, the one-launch chunk of
-// vsom_online_tiny_masked.hip, which reads those bytes as they are (one H2D copy and one launch; lastBMU and the MSE come
+// vsom_online_tiny.hip, which reads those bytes as they are (one H2D copy and one launch; lastBMU and the MSE come
 // back through pinned memory as in the unmasked call); otherwise the exact-scan loop of vsom_online_masked.hip over their
 // packed copy.  member: the caller is the ensemble the context has joined (vsom_online_chunk_masked_member).
 static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int decay_fn, int first_chunk, float *mse_out,
@@ -559,8 +558,7 @@ static int train_online_chunk_impl(vsom_ctx *c, double eta, double sigma, int de
                 VSOM_ALLOC_CHECK(vsom_grow(c->out_pinned, 8192, c->stream));
                 lbh = c->out_pinned.p;
             }
-            rc = tiny_masked ? enqueue_chunk_tiny_masked(c, eta, sigma, decay_fn, lutd, lutw, first_chunk, lbh, vraw, one)
-                             : enqueue_chunk_tiny(c, eta, sigma, decay_fn, lutd, lutw, first_chunk, lbh);
+            rc = enqueue_chunk_tiny(c, eta, sigma, decay_fn, lutd, lutw, first_chunk, lbh, tiny_masked ? vraw : nullptr, one);
             if (rc || (rc = lutd_host_used(c, lslot)))
                 return rc;
             if (lbh && lb_in_pinned)

@@ -187,14 +187,12 @@ int ensure_lutd_host(vsom_ctx *c, double sigma, const double **out, int *slot_ou
 // vsom_online_i8.hip: does the chunk loop of this context search through the image, and that loop
 bool onl_i8_applies(const vsom_ctx *c, double sigma);
 int enqueue_chunk_i8(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw);
-// vsom_online_tiny.hip: does the chunk take the one-launch kernel, and that launch
+// vsom_online_tiny.hip: does the chunk take the one-launch kernel, and that launch.  valid_dev null: the plain chunk;
+// otherwise the chunk over valid entries (vsom_online_masked_tiny_applies holds) and the validity bytes as given (B x J, or
+// J with one)
 bool online_tiny_applies(const vsom_ctx *c, double sigma);
 int enqueue_chunk_tiny(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw, int first_chunk,
-                       u64 *lastbmu_host);
-// vsom_online_tiny_masked.hip: the one-launch chunk over valid entries (vsom_online_masked_tiny_applies holds), valid_dev:
-// the validity bytes as given (B x J, or J with one)
-int enqueue_chunk_tiny_masked(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw,
-                              int first_chunk, u64 *lastbmu_host, const unsigned char *valid_dev, bool one);
+                       u64 *lastbmu_host, const unsigned char *valid_dev, bool one);
 // vsom_online_masked.hip: the exact-scan chunk loop over valid entries (Standard / Median), vp: the packed validity rows
 int enqueue_chunk_masked(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw,
                          const unsigned char *vp, bool one);

@@ -1,5 +1,5 @@
-// vsom_online_tiny.hpp -- the device helpers the one-workgroup online chunks share: the plain chunk (vsom_online_tiny.hip,
-// vsom_tiny_online_body.inc) and the chunk over valid entries (vsom_online_tiny_masked.hip, vsom_tiny_online_masked_body.inc).
+// vsom_online_tiny.hpp -- the descriptors and device helpers of the one-workgroup online chunk, plain and over valid entries
+// (vsom_online_tiny.hip, vsom_tiny_online_body.inc).
 #pragma once
 #include "vsom_online.hpp"
 
@@ -19,12 +19,20 @@ struct OnlTinyArgs {
     u64 *lastbmu_host;       // pinned host copy of lastBMU (vsom_train_online_chunk_fetch), or NULL
 };
 
-// vsom_online_tiny.hip: the chunk's LDS need, its descriptor from the context, and the kernel instantiation a map takes:
-// (Median ? 6 : 0) + (local ? 3 : 0) + (0, 1, 2 for U = 1, 2, 4)
-size_t online_tiny_lds_bytes(const vsom_ctx *c);
-void fill_chunk_tiny_args(vsom_ctx *c, double eta, double sigma, int decay_fn, const double *lutd, int lutw, int first_chunk,
-                          u64 *lastbmu_host, OnlTinyArgs &a);
-int chunk_tiny_group(const vsom_ctx *c, double sigma);
+// OnlTinyArgs and the validity bytes (a descriptor of its own: the stride of OnlTinyArgs stays)
+struct OnlTinyMaskedArgs : OnlTinyArgs {
+    const unsigned char *V;  // validity bytes on the device: B rows of ldv bytes, or one row (one != 0)
+    int ldv, one;
+};
+
+// the validity fields as the chunk body reads them: the masked descriptor's own, constants for the plain one (which the
+// body never reads: every use is behind its compile-time MASKED)
+struct OnlNoValid {
+    static constexpr const unsigned char *V = nullptr;
+    static constexpr int ldv = 0, one = 1;
+};
+__device__ __forceinline__ OnlNoValid onl_valid(const OnlTinyArgs &) { return {}; }
+__device__ __forceinline__ const OnlTinyMaskedArgs &onl_valid(const OnlTinyMaskedArgs &a) { return a; }
 
 constexpr int TINY_XBLOCK = 2048;      // values of staged rows held in LDS at a time (TINY_XBLOCK / D samples)
 

@@ -8,7 +8,10 @@
 //   phase 2  one thread per (node, dim) chain [CLR: per (node, pair)]: the neighbourhood weight from
 //            the host table, the fp32 prefix W, c = w/W, and the mean / sigma^2 recurrences, every
 //            operation rounded separately like the general kernels
-// so the results are bit-identical to those kernels and to the oracle.
+// so the results are bit-identical to those kernels and to the oracle.  Also here: whole schedules of such epochs in one
+// launch (tiny_batch_schedule_kernel), and vsom_schedule_rounds, the host routine that runs a single context's schedule
+// round by round for this flavour and for the masked one (vsom_tiny_masked.hip); the round's image is
+// vsom_sched_round.hpp's.
 #include "vsom_device.hpp"
 #include <cmath>
 #include <cstring>
@@ -24,12 +27,6 @@ struct TinyArgs {
     int stage_x;                                    // samples fit into LDS
     int luth;                                       // table rows (the table is copied into LDS)
 };
-
-__device__ __forceinline__ float tiny_sign(float a)   // Transformation::Stepper's sign (Transformation.cpp:49-50):
-{                                                     // +-1; a zero or a NaN comes back as it is
-    const float one = __builtin_copysignf(1.f, a);
-    return (a < 0.f || a > 0.f) ? one : a;
-}
 
 template <int KIND>
 __global__ __launch_bounds__(256) void tiny_batch_epoch_kernel(TinyArgs a)
@@ -152,31 +149,9 @@ int vsom_tiny_launch_many(int group, const void *desc_dev, unsigned count, size_
 // this workgroup, and the LDS arrays (keys, sq, bxy, the staged rows, the table) are written again.  All of a map's
 // traffic is vector loads and stores of one CU, which one L1 serves; the map pointers stay plain (no __restrict__, no
 // __ldg) so that no load of them goes through the scalar cache, which vector stores do not update.
-struct TinySchedArgs {
-    TinyArgs t;                  // lut: the first table of the schedule's table buffer; mse: slot 0 of this launch
-    const unsigned *tab;         // [epochs] each epoch's table, in floats from t.lut
-    int epochs;                  // of this launch (0: nothing to do)
-    int first;                   // this launch starts the schedule: its epoch 0 is the exact search
-    int reset_bmu;               // lastBMU := 0 before every epoch but the schedule's first
-    int pad;
-};
-
-// epoch ep of the launch: the barrier behind the previous epoch, the lastBMU reset, and the epoch's descriptor
-__device__ __forceinline__ TinyArgs tiny_schedule_epoch(const TinySchedArgs &s, int ep)
-{
-    TinyArgs a = s.t;
-    a.is_first = (s.first && ep == 0) ? 1 : 0;
-    a.lut = s.t.lut + s.tab[ep];
-    a.mse = s.t.mse + ep;
-    if (ep > 0)
-        __syncthreads();                     // the previous epoch's phase 2: map rows stored, LDS free
-    if (!a.is_first && s.reset_bmu) {
-        for (int i = threadIdx.x; i < a.B; i += 256)
-            a.lastbmu[i] = 0ull;             // DataSet.cpp:136-137
-        __syncthreads();
-    }
-    return a;
-}
+// (TinySched and tiny_schedule_epoch: vsom_device.hpp.  A struct of its own rather than an alias, so that the kernels'
+// parameter type keeps its name)
+struct TinySchedArgs : TinySched<TinyArgs> {};
 
 template <int KIND>
 __global__ __launch_bounds__(256) void tiny_batch_schedule_kernel(TinySchedArgs s)
@@ -202,29 +177,6 @@ void vsom_lut_dims(const vsom_ctx *c, uint32_t *lw, uint32_t *lh)   // as ensure
     const uint32_t ymax = c->N ? (c->N - c->W) / c->H : 0;
     *lh = ymax + 1;
     *lw = c->W;
-}
-
-size_t VsomSchedTables::add(uint32_t w, uint32_t h, double sigma)
-{
-    uint64_t bits;
-    std::memcpy(&bits, &sigma, sizeof(bits));
-    const auto r = at.emplace(std::make_tuple(w, h, bits), floats);
-    if (r.second)
-        floats += (size_t)w * h;
-    return r.first->second;
-}
-
-void VsomSchedTables::tabulate(float *host) const
-{
-    for (const auto &kv : at) {
-        const uint32_t w = std::get<0>(kv.first), h = std::get<1>(kv.first);
-        double sigma;
-        std::memcpy(&sigma, &std::get<2>(kv.first), sizeof(sigma));
-        float *t = host + kv.second;
-        for (uint32_t dy = 0; dy < h; ++dy)
-            for (uint32_t dx = 0; dx < w; ++dx)
-                t[(size_t)dy * w + dx] = (float)vsom_neighbourhood_weight(dx, dy, 0, 0, sigma);
-    }
 }
 
 bool vsom_tiny_schedule_applies(const vsom_ctx *c, const double *sigma, size_t epochs, size_t lds_limit)
@@ -272,20 +224,6 @@ int vsom_tiny_sched_launch_many(int group, const void *desc_dev, unsigned count,
     return VSOM_OK;
 }
 
-// the contract itself: what every context off the fast path runs
-int vsom_schedule_loop(vsom_ctx *c, const double *sigma, size_t epochs, int reset_bmu, float *mse_out)
-{
-    for (size_t ep = 0; ep < epochs; ++ep) {
-        if (ep > 0 && reset_bmu && c->B) {
-            VSOM_HIP_CHECK(hipSetDevice(c->device));
-            VSOM_HIP_CHECK(hipMemsetAsync(c->lastbmu.p, 0, c->B * sizeof(u64), c->stream));
-        }
-        if (int rc = vsom_batch_epoch(c, sigma[ep], ep == 0, &mse_out[ep]))
-            return rc;
-    }
-    return VSOM_OK;
-}
-
 const char *vsom_schedule_refusal(const vsom_ctx *c)
 {
     if (!c->chunk_loaded)        // (custom contexts keep chunk_loaded and ahead_rows like every other)
@@ -306,45 +244,68 @@ int vsom_batch_schedule(vsom_ctx *c, const double *sigma, size_t epochs, int res
     if (const char *why = vsom_schedule_refusal(c))
         return vsom_fail(VSOM_ERR_INVALID, why);
     if (!vsom_tiny_schedule_applies(c, sigma, epochs, (size_t)64 << 10))
-        return vsom_schedule_loop(c, sigma, epochs, reset_bmu, mse_out);
+        return vsom_schedule_loop(c, epochs, reset_bmu,
+                                  [&](size_t ep) { return vsom_batch_epoch(c, sigma[ep], ep == 0, &mse_out[ep]); });
+    return vsom_schedule_rounds(c, sigma, epochs, reset_bmu, nullptr, 0, mse_out,
+                                [](vsom_ctx *ctx, const unsigned char *, int, const float *lut_dev, const unsigned *tab_dev,
+                                   float *mse, size_t cnt, int first, int reset) {
+                                    TinySchedArgs s;
+                                    size_t smem = 0;
+                                    vsom_tiny_sched_fill(ctx, lut_dev, tab_dev, mse, cnt, first, reset, &s, &smem);
+                                    if (ctx->transform == VSOM_CLR)
+                                        hipLaunchKernelGGL(tiny_batch_schedule_kernel<VSOM_CLR>, dim3(1), dim3(256), smem, ctx->stream, s);
+                                    else if (ctx->transform == VSOM_MEDIAN)
+                                        hipLaunchKernelGGL(tiny_batch_schedule_kernel<VSOM_MEDIAN>, dim3(1), dim3(256), smem, ctx->stream, s);
+                                    else
+                                        hipLaunchKernelGGL(tiny_batch_schedule_kernel<VSOM_STANDARD>, dim3(1), dim3(256), smem, ctx->stream, s);
+                                    VSOM_HIP_CHECK(hipGetLastError());
+                                    return (int)VSOM_OK;
+                                });
+}
 
+int vsom_schedule_rounds(vsom_ctx *c, const double *sigma, size_t epochs, int reset_bmu, const uint8_t *valid_host,
+                         int one_mask, float *mse_out, VsomSchedLaunch launch)
+{
     VSOM_HIP_CHECK(hipSetDevice(c->device));
     if (int rc = vsom_join_aux(c))
         return rc;
     c->rows_free_valid = false;   // (as every entry point that reads the staged rows)
+    // the validity bytes: one copy per call into the query arena, read by every epoch of every launch
+    const unsigned char *valid_dev = nullptr;
+    if (valid_host) {
+        const size_t vbytes = (one_mask ? 1 : c->B) * (size_t)c->J;
+        vsom_layout lay;
+        const auto vraw = lay.add<unsigned char>(vbytes);
+        VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
+        TimerScope ts(c, VSOM_T_STAGE);
+        VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(vraw), valid_host, vbytes, hipMemcpyHostToDevice, c->stream));
+        valid_dev = lay.at(vraw);
+    }
     // Launch by launch (no launch runs more than VSOM_SCHEDULE_MAX_EPOCHS epochs, and the tables of one launch are at most
-    // 1024 x 16 KB): the launch's tables, one per distinct sigma, then each epoch's offset -- one pinned image, one copy.
-    // A schedule within the cap is one copy, one launch and one wait; a longer one waits before it rewrites the image.
-    uint32_t lw, lh;
-    vsom_lut_dims(c, &lw, &lh);
+    // 1024 x 16 KB, below 2^32 values): the round's image -- its tables, one per distinct sigma, then each epoch's offset --
+    // pinned, one copy.  A schedule within the cap is one copy, one launch and one wait; a longer one waits before it
+    // rewrites the image.
+    VsomSchedMember m;
+    vsom_lut_dims(c, &m.lw, &m.lh);
+    m.valid = nullptr;
+    m.vbytes = 0;
     VSOM_ALLOC_CHECK(vsom_grow(c->sch_mse, epochs, c->stream, VSOM_BUF_SYNC));
-    std::vector<unsigned> tab;
+    VsomSchedRound round;
     for (size_t e0 = 0; e0 < epochs; e0 += VSOM_SCHEDULE_MAX_EPOCHS) {
-        const size_t cnt = std::min(epochs - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS);
+        m.sigma = sigma + e0;
+        m.epochs = std::min(epochs - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS);
         if (e0)
             VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));   // the previous launch's copy has left the pinned image
-        VsomSchedTables tabs;
-        tab.resize(cnt);
-        for (size_t ep = 0; ep < cnt; ++ep)
-            tab[ep] = (unsigned)tabs.add(lw, lh, sigma[e0 + ep]);   // (below 1024 * 4096 floats)
-        const size_t bytes = (tabs.floats + cnt) * sizeof(float);
+        round.plan(&m, 1);
+        const size_t bytes = round.bytes();
         VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_SYNC, {vsom_member(c->sch_host, bytes), vsom_member(c->sch_dev, bytes)}));
-        tabs.tabulate(reinterpret_cast<float *>(c->sch_host.p));
-        std::memcpy(c->sch_host.p + tabs.floats * sizeof(float), tab.data(), cnt * sizeof(unsigned));
+        round.write(c->sch_host.p, &m);
         VSOM_HIP_CHECK(hipMemcpyAsync(c->sch_dev.p, c->sch_host.p, bytes, hipMemcpyHostToDevice, c->stream));
         const float *lut_dev = reinterpret_cast<const float *>(c->sch_dev.p);
-        const unsigned *tab_dev = reinterpret_cast<const unsigned *>(c->sch_dev.p + tabs.floats * sizeof(float));
+        const unsigned *tab_dev = reinterpret_cast<const unsigned *>(c->sch_dev.p + round.table_bytes());
         TimerScope ts(c, VSOM_T_UPDATE);
-        TinySchedArgs s;
-        size_t smem = 0;
-        vsom_tiny_sched_fill(c, lut_dev, tab_dev, c->sch_mse.p + e0, cnt, e0 == 0, reset_bmu, &s, &smem);
-        if (c->transform == VSOM_CLR)
-            hipLaunchKernelGGL(tiny_batch_schedule_kernel<VSOM_CLR>, dim3(1), dim3(256), smem, c->stream, s);
-        else if (c->transform == VSOM_MEDIAN)
-            hipLaunchKernelGGL(tiny_batch_schedule_kernel<VSOM_MEDIAN>, dim3(1), dim3(256), smem, c->stream, s);
-        else
-            hipLaunchKernelGGL(tiny_batch_schedule_kernel<VSOM_STANDARD>, dim3(1), dim3(256), smem, c->stream, s);
-        VSOM_HIP_CHECK(hipGetLastError());
+        if (int rc = launch(c, valid_dev, one_mask, lut_dev, tab_dev, c->sch_mse.p + e0, m.epochs, e0 == 0, reset_bmu))
+            return rc;
     }
     VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
     vsom_schedule_results(c, epochs, mse_out);

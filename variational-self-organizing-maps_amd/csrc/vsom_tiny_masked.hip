@@ -1,6 +1,8 @@
-// vsom_tiny_masked.hip -- vsom_batch_epoch_masked (vsom_masked_train.hip) for maps so small that its dozen launches cost
-// more than the work: ONE workgroup runs whole masked epochs in one launch, as vsom_tiny.hip does for the unmasked epoch
-// (gfx950; Standard / Median, strict arithmetic: this translation unit is built with the strict flags).
+// vsom_tiny_masked.hip -- the masked flavour of the one-workgroup batch epochs (vsom_tiny.hip is the plain one): for maps
+// so small that the dozen launches of vsom_batch_epoch_masked (vsom_masked_train.hip) cost more than the work, ONE workgroup
+// runs whole masked epochs in one launch (gfx950; Standard / Median, strict arithmetic: this translation unit is built with
+// the strict flags).  The two flavours share the schedule descriptor and its epoch step (TinySched, tiny_schedule_epoch:
+// vsom_device.hpp), the round image (vsom_sched_round.hpp) and the host's round loop (vsom_schedule_rounds, vsom_tiny.hip).
 //   phase 1  every (sample, node) masked distance by 8-lane groups (masked_group_dist: r_d = valid ? m_d - x_d : +0), the
 //            argmin through an LDS atomicMin on the (distance, index) key -- or findLocalBmu's walk on the same distance,
 //            one wavefront per sample;  bmuHits;  MSE summed in sample order
@@ -30,47 +32,19 @@ struct TinyMaskedArgs {
     int nw;                      // validity words per column in LDS: ceil(B / 32), or 1 with `one`
 };
 
-__device__ __forceinline__ float tinym_sign(float a)   // Transformation::Stepper's sign (Transformation.cpp:49-50):
-{                                                      // +-1; a zero or a NaN comes back as it is
-    const float one = __builtin_copysignf(1.f, a);
-    return (a < 0.f || a > 0.f) ? one : a;
-}
-
 // The loop over the epochs is in the kernel, as in tiny_batch_schedule_kernel (vsom_tiny.hip): between two epochs one
 // barrier -- phase 2 stored map rows (a.map) that the next phase 1 reads (a.d.ma) from other threads of this workgroup, and
 // the LDS arrays are written again.  The map pointers stay plain (no __restrict__, no __ldg): no load of them may go
 // through the scalar cache, which vector stores do not update.
-struct TinyMaskedSchedArgs {
-    TinyMaskedArgs t;            // lut: the first table of the launch's table buffer; mse: slot 0 of this launch
-    const unsigned *tab;         // [epochs] each epoch's table, in floats from t.lut
-    int epochs;                  // of this launch (0: nothing to do)
-    int first;                   // epoch 0 of this launch is the exact search
-    int reset_bmu;               // lastBMU := 0 before every epoch but an exact search
-    int pad;
-};
-
-// epoch ep of the launch: the barrier behind the previous epoch, the lastBMU reset, and the epoch's descriptor
-__device__ __forceinline__ TinyMaskedArgs tinym_schedule_epoch(const TinyMaskedSchedArgs &s, int ep)
-{
-    TinyMaskedArgs a = s.t;
-    a.is_first = (s.first && ep == 0) ? 1 : 0;
-    a.lut = s.t.lut + s.tab[ep];
-    a.mse = s.t.mse + ep;
-    if (ep > 0)
-        __syncthreads();                     // the previous epoch's phase 2: map rows stored, LDS free
-    if (!a.is_first && s.reset_bmu) {
-        for (int i = threadIdx.x; i < a.B; i += 256)
-            a.lastbmu[i] = 0ull;             // DataSet.cpp:136-137
-        __syncthreads();
-    }
-    return a;
-}
+// (TinySched and tiny_schedule_epoch: vsom_device.hpp.  A struct of its own rather than an alias, so that the kernels'
+// parameter type keeps its name)
+struct TinyMaskedSchedArgs : TinySched<TinyMaskedArgs> {};
 
 template <int KIND>
 __global__ __launch_bounds__(256) void tiny_masked_schedule_kernel(TinyMaskedSchedArgs s)
 {
     for (int ep = 0; ep < s.epochs; ++ep) {
-        const TinyMaskedArgs a = tinym_schedule_epoch(s, ep);
+        const TinyMaskedArgs a = tiny_schedule_epoch(s, ep);
 #include "vsom_tiny_masked_body.inc"
     }
 }
@@ -81,7 +55,7 @@ __global__ __launch_bounds__(256) void tiny_masked_schedule_many_kernel(const Ti
 {
     const TinyMaskedSchedArgs s = args[blockIdx.x];
     for (int ep = 0; ep < s.epochs; ++ep) {
-        const TinyMaskedArgs a = tinym_schedule_epoch(s, ep);
+        const TinyMaskedArgs a = tiny_schedule_epoch(s, ep);
 #include "vsom_tiny_masked_body.inc"
     }
 }
@@ -190,21 +164,6 @@ int vsom_masked_tiny_applies(const vsom_ctx *c, int one_mask)
     return c && c->chunk_loaded && vsom_tiny_masked_applies(c, one_mask, (size_t)64 << 10) ? 1 : 0;
 }
 
-// the contract itself: what every context off the fast path runs
-static int masked_schedule_loop(vsom_ctx *c, const double *sigma, size_t epochs, int reset_bmu, const uint8_t *valid_host,
-                                int one_mask, float *mse_out)
-{
-    for (size_t ep = 0; ep < epochs; ++ep) {
-        if (ep > 0 && reset_bmu && c->B) {
-            VSOM_HIP_CHECK(hipSetDevice(c->device));
-            VSOM_HIP_CHECK(hipMemsetAsync(c->lastbmu.p, 0, c->B * sizeof(u64), c->stream));
-        }
-        if (int rc = vsom_batch_epoch_masked(c, sigma[ep], ep == 0, valid_host, one_mask, &mse_out[ep]))
-            return rc;
-    }
-    return VSOM_OK;
-}
-
 int vsom_batch_schedule_masked(vsom_ctx *c, const double *sigma, size_t epochs, int reset_bmu, const uint8_t *valid_host,
                                int one_mask, float *mse_out)
 {
@@ -222,54 +181,21 @@ int vsom_batch_schedule_masked(vsom_ctx *c, const double *sigma, size_t epochs, 
         return vsom_fail(VSOM_ERR_INVALID, why);
     const size_t lds_cap = (size_t)64 << 10;     // (no attribute is raised for the batch kernels)
     if (!vsom_tiny_masked_schedule_applies(c, one_mask, sigma, epochs, lds_cap))
-        return masked_schedule_loop(c, sigma, epochs, reset_bmu, valid_host, one_mask, mse_out);
-
-    VSOM_HIP_CHECK(hipSetDevice(c->device));
-    if (int rc = vsom_join_aux(c))
-        return rc;
-    c->rows_free_valid = false;   // (as every entry point that reads the staged rows)
-    // the validity bytes: one copy per call into the query arena, read by every epoch of every launch
-    vsom_layout lay;
-    const auto vraw = lay.add<unsigned char>((one_mask ? 1 : c->B) * (size_t)c->J);
-    VSOM_ALLOC_CHECK(vsom_arena_ensure(c->q_scratch, lay, c->stream));
-    {
-        TimerScope ts(c, VSOM_T_STAGE);
-        VSOM_HIP_CHECK(hipMemcpyAsync(lay.at(vraw), valid_host, (one_mask ? 1 : c->B) * (size_t)c->J, hipMemcpyHostToDevice,
-                                      c->stream));
-    }
-    // launch by launch as vsom_batch_schedule: the launch's tables, one per distinct sigma, then each epoch's offset -- one
-    // pinned image, one copy; a schedule longer than the cap waits before it rewrites the image
-    uint32_t lw, lh;
-    vsom_lut_dims(c, &lw, &lh);
-    VSOM_ALLOC_CHECK(vsom_grow(c->sch_mse, epochs, c->stream, VSOM_BUF_SYNC));
-    std::vector<unsigned> tab;
-    for (size_t e0 = 0; e0 < epochs; e0 += VSOM_SCHEDULE_MAX_EPOCHS) {
-        const size_t cnt = std::min(epochs - e0, (size_t)VSOM_SCHEDULE_MAX_EPOCHS);
-        if (e0)
-            VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));   // the previous launch's copy has left the pinned image
-        VsomSchedTables tabs;
-        tab.resize(cnt);
-        for (size_t ep = 0; ep < cnt; ++ep)
-            tab[ep] = (unsigned)tabs.add(lw, lh, sigma[e0 + ep]);   // (below 1024 * 4096 floats)
-        const size_t bytes = (tabs.floats + cnt) * sizeof(float);
-        VSOM_ALLOC_CHECK(vsom_grow_set(c->stream, VSOM_BUF_SYNC, {vsom_member(c->sch_host, bytes), vsom_member(c->sch_dev, bytes)}));
-        tabs.tabulate(reinterpret_cast<float *>(c->sch_host.p));
-        std::memcpy(c->sch_host.p + tabs.floats * sizeof(float), tab.data(), cnt * sizeof(unsigned));
-        VSOM_HIP_CHECK(hipMemcpyAsync(c->sch_dev.p, c->sch_host.p, bytes, hipMemcpyHostToDevice, c->stream));
-        const float *lut_dev = reinterpret_cast<const float *>(c->sch_dev.p);
-        const unsigned *tab_dev = reinterpret_cast<const unsigned *>(c->sch_dev.p + tabs.floats * sizeof(float));
-        TimerScope ts(c, VSOM_T_UPDATE);
-        TinyMaskedSchedArgs s;
-        size_t smem = 0;
-        vsom_tiny_masked_sched_fill(c, lay.at(vraw), one_mask, lds_cap, lut_dev, tab_dev, c->sch_mse.p + e0, cnt, e0 == 0,
-                                    reset_bmu, &s, &smem);
-        if (c->transform == VSOM_MEDIAN)
-            hipLaunchKernelGGL(tiny_masked_schedule_kernel<VSOM_MEDIAN>, dim3(1), dim3(256), smem, c->stream, s);
-        else
-            hipLaunchKernelGGL(tiny_masked_schedule_kernel<VSOM_STANDARD>, dim3(1), dim3(256), smem, c->stream, s);
-        VSOM_HIP_CHECK(hipGetLastError());
-    }
-    VSOM_HIP_CHECK(hipStreamSynchronize(c->stream));
-    vsom_schedule_results(c, epochs, mse_out);
-    return VSOM_OK;
+        return vsom_schedule_loop(c, epochs, reset_bmu, [&](size_t ep) {
+            return vsom_batch_epoch_masked(c, sigma[ep], ep == 0, valid_host, one_mask, &mse_out[ep]);
+        });
+    return vsom_schedule_rounds(c, sigma, epochs, reset_bmu, valid_host, one_mask, mse_out,
+                                [](vsom_ctx *ctx, const unsigned char *valid_dev, int one, const float *lut_dev,
+                                   const unsigned *tab_dev, float *mse, size_t cnt, int first, int reset) {
+                                    TinyMaskedSchedArgs s;
+                                    size_t smem = 0;
+                                    vsom_tiny_masked_sched_fill(ctx, valid_dev, one, (size_t)64 << 10, lut_dev, tab_dev, mse, cnt,
+                                                                first, reset, &s, &smem);
+                                    if (ctx->transform == VSOM_MEDIAN)
+                                        hipLaunchKernelGGL(tiny_masked_schedule_kernel<VSOM_MEDIAN>, dim3(1), dim3(256), smem, ctx->stream, s);
+                                    else
+                                        hipLaunchKernelGGL(tiny_masked_schedule_kernel<VSOM_STANDARD>, dim3(1), dim3(256), smem, ctx->stream, s);
+                                    VSOM_HIP_CHECK(hipGetLastError());
+                                    return (int)VSOM_OK;
+                                });
 }

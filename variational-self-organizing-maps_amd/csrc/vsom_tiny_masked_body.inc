@@ -122,7 +122,7 @@
             const float cc = w / Wd;                         // :864 (0/0 -> NaN, SURVEY Q7)
             float dl = xsrc[(size_t)s * xld + e] - M;        // Stepper (Transformation.cpp:12 / :50)
             if (KIND == VSOM_MEDIAN)
-                dl = tinym_sign(dl);
+                dl = tiny_sign(dl);
             const float t = cc * dl;
             M = M + t;                                       // :864
             float u;

@@ -1,7 +1,9 @@
-// vsom_tiny_online_body.inc -- the body of the one-workgroup online chunk (vsom_online.hip): included inside
-// online_tiny_chunk_kernel<KIND, LOCAL, U> (its kernarg `a`) and online_tiny_chunk_many_kernel<KIND, LOCAL, U> (`a` = its
-// workgroup's descriptor).  Every piece of the map's state is in LDS, registers and `a`: no blockIdx, gridDim or global
-// atomics on shared words.
+// vsom_tiny_online_body.inc -- the body of the one-workgroup online chunk (vsom_online_tiny.hip): included as text inside
+// the four kernel templates online_tiny[_masked]_chunk[_many]_kernel<KIND, LOCAL, U>, each of which defines `a` (its kernarg,
+// or its workgroup's descriptor) and `constexpr bool MASKED` first.  MASKED: the chunk runs over the VALID entries of the
+// rows only -- a validity byte beside every staged value (onl_valid(a): the descriptor's V, ldv, one; constants for the
+// plain descriptor, which has none).  Every `if (MASKED)` folds at compile time.  Every piece of the map's state is in LDS,
+// registers and `a`: no blockIdx, gridDim or global atomics on shared words.
     extern __shared__ __attribute__((aligned(16))) unsigned char tiny_onl_smem[];
     const int N = a.N, D = a.D, ND = N * D, tid = threadIdx.x, Dp = D | 1;      // (odd row pitch: phase B's rows hit distinct banks)
     // LDS: per-BMU window table, the neighbourhood table (double for :933's division; its two float images for :924-925),
@@ -12,7 +14,9 @@
     float *s_p = reinterpret_cast<float *>(s_lf + N);                           // [N Dp] squares of the sample against every node
     float *s_p2 = s_p + N * Dp;                                                 // [2][D]  squares of the BMU's row after its update
     float *s_x = s_p2 + 2 * ((D + 3) & ~3);                                     // [TINY_XBLOCK] staged rows of this block
-    unsigned *s_hits = reinterpret_cast<unsigned *>(s_x + TINY_XBLOCK);         // [N]  addBmu counts of this chunk
+    unsigned char *s_v = reinterpret_cast<unsigned char *>(s_x + TINY_XBLOCK);  // [TINY_XBLOCK] MASKED only: their validity bytes as
+                                                                                //      the caller gave them (one: ONE row of D)
+    unsigned *s_hits = reinterpret_cast<unsigned *>(s_v + (MASKED ? TINY_XBLOCK : 0));   // [N]  addBmu counts of this chunk
     float *s_d = reinterpret_cast<float *>(s_hits + N);                         // [N]  LOCAL: the sample's distances
     unsigned short *s_last = reinterpret_cast<unsigned short *>(s_d + N);       // [B]  lastBMU of every sample (a global store
                                                                                 //      per sample made its wavefront wait for it)
@@ -38,10 +42,17 @@
         t.pad0 = t.pad1 = 0;
         s_win[i] = t;
     }
-    // this thread's values: flattened (node, dim) indices tid + 1024 u
-    float m[U], sv[U], w[U];
+    const auto va = onl_valid(a);
+    if (MASKED && va.one)                                    // one validity row for the whole chunk, staged once
+        for (int i = tid; i < D; i += 1024)
+            s_v[i] = va.V[i];
+    const int vstep = va.one ? 0 : D;                        // a sample's validity row within the block
+    // this thread's values: flattened (node, dim) indices tid + 1024 u.  stepped = some step of this chunk moved the value.
+    // MASKED: wl = the node's weight at the value's last VALID step (online_node_update_masked writes sigmaMap[d] with the twf
+    // of the step that stepped column d; later visits with d invalid raise the weight and leave sigmaMap[d])
+    float m[U], sv[U], w[U], wl[U];
     int node[U], dim[U], nx[U], ny[U];
-    bool own[U], touched[U];
+    bool own[U], stepped[U];
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         const int e = tid + 1024 * u;
@@ -53,7 +64,8 @@
         m[u] = own[u] ? a.map[(size_t)node[u] * a.pitch + dim[u]] : 0.f;
         sv[u] = own[u] ? a.Smap[(size_t)node[u] * a.pitch + dim[u]] : 0.f;
         w[u] = own[u] ? a.weight[node[u]] : 0.f;
-        touched[u] = false;
+        wl[u] = 0.f;
+        stepped[u] = false;
     }
     float mse = a.keep_mse ? a.fstate[1] : 0.f, lastdist = 0.f;
     if (tid < 2)
@@ -61,7 +73,8 @@
     const int L8 = D & ~7, rem = D - L8, KB = TINY_XBLOCK / D;
     int pj = -1, pbmu = 0;                                   // the sample whose post step is owed, and its BMU
     // post step of a sample (one thread): the distance of its BMU after the update (:946) from the squares the BMU's threads
-    // left in that sample's parity, the MSE running sum (:1167), addBmu (:1165), lastBMU (:895); re-arms the parity's key
+    // left in that sample's parity (MASKED: +0 at the invalid columns), the MSE running sum (:1167), addBmu (:1165), lastBMU
+    // (:895); re-arms the parity's key
     auto post = [&](int sj, int sbmu) {
         const int ppar = sj & 1;
         const float res = onl_tiny_row_sum(s_p2 + ppar * ((D + 3) & ~3), L8, rem);
@@ -77,18 +90,35 @@
         const int kb = min(KB, a.B - j0);
         if (j0 == 0)
             __syncthreads();                                 // the tables (later blocks: the sample loop's last barrier -- nobody reads the old rows)
-        for (int i = tid; i < kb * D; i += 1024)
-            s_x[i] = a.X[(size_t)(j0 + i / D) * a.ldx + (i % D)];
+        for (int i = tid; i < kb * D; i += 1024) {
+            // (row and column of the value in the spelling each flavour's kernels were compiled from: either spelling gives
+            //  the other flavour the same values through another instruction schedule)
+            if (MASKED) {
+                const int r = i / D, d = i - r * D;
+                s_x[i] = a.X[(size_t)(j0 + r) * a.ldx + d];
+                if (!va.one)                                 // the block's validity bytes, B x J as given
+                    s_v[i] = va.V[(size_t)(j0 + r) * va.ldv + d];
+            } else {
+                s_x[i] = a.X[(size_t)(j0 + i / D) * a.ldx + (i % D)];
+            }
+        }
         __syncthreads();
-        // A (first sample of the block): squares of the sample against every node
+        // A (first sample of the block): squares of the sample against every node.  MASKED: a select, never a product -- x at an
+        // invalid position may be NaN or +-inf
         float x[U];
+        bool vd[U];
 #pragma unroll
-        for (int u = 0; u < U; ++u)
+        for (int u = 0; u < U; ++u) {
+            vd[u] = false;
             if (own[u]) {
                 x[u] = s_x[dim[u]];
                 const float r = m[u] - x[u];
-                s_p[node[u] * Dp + dim[u]] = r * r;
+                const float rr = r * r;
+                if (MASKED)
+                    vd[u] = s_v[dim[u]] != 0;
+                s_p[node[u] * Dp + dim[u]] = (!MASKED || vd[u]) ? rr : 0.f;
             }
+        }
         __syncthreads();
         for (int jj = 0; jj < kb; ++jj) {
             const int j = j0 + jj, par = j & 1;
@@ -142,6 +172,8 @@
                 dx = dx < 0 ? -dx : dx;
                 dy = dy < 0 ? -dy : dy;
                 const int at = dy * a.W + dx;                    // calculateNeighbourhoodWeight(i,j,bx,by,sigma) :915
+                // (MASKED: the node's weight and the step's scalars are the unmasked step's whatever the column's validity
+                //  -- the weight counts the sample ...)
                 const float wold = w[u];
                 const float2 lf = s_lf[at];
                 const float hf = lf.y;
@@ -154,6 +186,9 @@
                     const double tw = wnew == 0 ? 1.0 : s_lut[at] / (double)wnew;   // :933
                     scM = (float)tw;
                 }
+                w[u] = wnew;
+                if (MASKED && !vd[u])
+                    continue;                                    // ... and an invalid column is not stepped: m, sv, wl keep their bits
                 float dl = x[u] - m[u];                          // Stepper :912
                 if (KIND == VSOM_MEDIAN)
                     dl = onl_sign(dl);
@@ -166,8 +201,8 @@
                 const float uu = hf * pr;
                 sv[u] = sv[u] + uu;                              // :941
                 m[u] = mn;
-                w[u] = wnew;
-                touched[u] = true;
+                wl[u] = wnew;
+                stepped[u] = true;
             }
             TINY_STAMP(6);
             // D: distance of the BMU after the update (:946), MSE (:1167), addBmu (:1165), lastBMU (:895)
@@ -176,7 +211,8 @@
             for (int u = 0; u < U; ++u)
                 if (own[u] && node[u] == bmu) {
                     const float r = m[u] - x[u];
-                    p2[dim[u]] = r * r;
+                    const float rr = r * r;
+                    p2[dim[u]] = (!MASKED || vd[u]) ? rr : 0.f;
                 }
             TINY_STAMP(7);
             // A of the NEXT sample before the same barrier (its squares go where phase B of this sample, long done, read)
@@ -185,8 +221,11 @@
                 for (int u = 0; u < U; ++u)
                     if (own[u]) {
                         x[u] = s_x[(jj + 1) * D + dim[u]];
+                        if (MASKED)
+                            vd[u] = s_v[(jj + 1) * vstep + dim[u]] != 0;
                         const float r = m[u] - x[u];
-                        s_p[node[u] * Dp + dim[u]] = r * r;
+                        const float rr = r * r;
+                        s_p[node[u] * Dp + dim[u]] = (!MASKED || vd[u]) ? rr : 0.f;
                     }
             }
             TINY_STAMP(8);
@@ -200,17 +239,22 @@
     if (tid == 1023 && pj >= 0)                               // the chunk's last sample
         post(pj, pbmu);
     __syncthreads();
-    // state back: M and S of every value, weight by the node's first value, sigmaMap = sqrt(|S / w|) (:939-942) where a
-    // window touched the node during this chunk
+    // state back: M and S of every value, sigmaMap = sqrt(|S / w|) (:939-942) with the final weight where a window touched
+    // the node during this chunk; the weight by the node's first value.  MASKED: M, S and sigmaMap only of the values some
+    // valid step touched -- the others are not written, so their bits stay (NaN payloads included) -- and sigmaMap with the
+    // weight of that last valid step, not the final one
 #pragma unroll
     for (int u = 0; u < U; ++u) {
         if (!own[u])
             continue;
         const size_t at = (size_t)node[u] * a.pitch + dim[u];
-        a.map[at] = m[u];
-        a.Smap[at] = sv[u];
-        if (touched[u]) {
-            const double tw2 = w[u] == 0 ? 0.000001 : (double)w[u];   // :939
+        if (!MASKED || stepped[u]) {
+            a.map[at] = m[u];
+            a.Smap[at] = sv[u];
+        }
+        if (stepped[u]) {
+            const float wlast = MASKED ? wl[u] : w[u];
+            const double tw2 = wlast == 0 ? 0.000001 : (double)wlast;   // :939
             const float twf = (float)tw2;
             a.sigmap[at] = sqrtf(fabsf(sv[u] / twf));                 // :942
         }
