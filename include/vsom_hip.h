@@ -1027,6 +1027,42 @@ int vsom_ensemble_upload_chunks(vsom_ensemble *e, const float *x_host, size_t n_
  * call.  idx_out / dist_out: NULL, or one pointer per member (NULL or room for that member's B values).  Refuses like
  * the train calls: a member without a chunk, a member whose next chunk is staged ahead over its rows. */
 int vsom_ensemble_bmu_batch(vsom_ensemble *e, uint64_t *const *idx_out, float *const *dist_out);
+/* The two queries of a map trained on records with missing fields, for every member in one call:
+ * which unit matches a row's observed columns and what does it say about the others (vsom_bmu_masked_batch: bmu, dist,
+ * nvalid, fill), and how far is the row from that unit in units of its sigma and which column is to blame
+ * (vsom_similarity_masked_batch: the similarity words, nvalid, the dense delta).  valid_host[k] is member k's validity
+ * (B_k x J_k bytes, row-major, or J_k bytes when one_mask[k] != 0; one_mask NULL: all 0; a non-zero byte means valid) or
+ * NULL: that member is SKIPPED -- nothing is enqueued for it and out[k] is neither read nor written.  min_hits NULL: all 0;
+ * num_sigmas holds one value per member, sigma_rule applies to all.  out[k] holds host pointers, each may be NULL.
+ * Per member with a validity every output is, bit for bit, that of
+ *   vsom_bmu_masked_batch(member k, min_hits[k], 0, B_k, valid_host[k], one_mask[k], &out[k])
+ *   vsom_similarity_masked_batch(member k, min_hits[k], num_sigmas[k], sigma_rule, 0, B_k, valid_host[k], one_mask[k], &out[k])
+ * made on a context that is no member -- the arithmetic, the argmin rule and the edge cases stated at those calls hold
+ * word for word: node 0 seeds the search whatever its hits, strict `<` over the nodes with bmuHits >= min_hits, NaN never
+ * wins, a NaN d_0 pins node 0 and stores 0x7FC00000, a row without a valid column reports node 0, distance +0, nvalid 0 and
+ * the similarity defaults given there; what x, map and sigmaMap hold at an invalid position reaches no output but `fill`,
+ * which copies the map by definition.  A member with B_k = 0 writes nothing.
+ * Members with a validity, B_k > 0, N * D <= 4096 and an LDS need (768 bytes + 4 N D) within the device's limit run as one
+ * launch per kind (Standard, Median), one workgroup per (member, 64 rows), whatever their search settings: the search of
+ * vsom_ensemble_bmu_batch on the masked distance and, in the same workgroup, the per-row epilogue (nvalid, fill, the
+ * similarity words by the code vsom_similarity_masked_batch runs).  Their validity bytes are gathered into one pinned
+ * image and copied to the device once per call, and their results return through pinned buffers of the ensemble (grow-only,
+ * one set for both calls; B_k x J_k floats of fill / delta only for the members that ask for them).  Every other member
+ * with a validity runs its single call inside this call, while the launches are in flight.  Each call ends in one wait
+ * for the launches; valid_host is not read after the call returns.
+ * Read-only: every member's lastBMU, sqres, map, sigmaMap, S, weightMap, bmuHits and chunk are untouched.  A member has
+ * no pending sigmaMap to materialise: vsom_ensemble_create materialises one and a member's epochs are eager from then on
+ * (vsom_set_sigma_mode), so sigmaMap is current when these calls read it; the entry gate that would materialise one is
+ * the single calls' all the same.
+ * Refuses (VSOM_ERR_INVALID, naming the member, before anything is enqueued for any member; a refused call changes nothing):
+ * a null ensemble, valid_host array or out array; similarity: a null num_sigmas, an unknown sigma_rule; for a member with
+ * a validity: a custom or CLR context, no chunk, the next chunk staged ahead over its rows. */
+int vsom_ensemble_bmu_masked_batch(vsom_ensemble *e, const uint64_t *min_hits /*[K], NULL: all 0*/,
+                                   const uint8_t *const *valid_host /*[K]*/, const int *one_mask /*[K], NULL: all 0*/,
+                                   const vsom_masked_out *out /*[K]*/);
+int vsom_ensemble_similarity_masked_batch(vsom_ensemble *e, const uint64_t *min_hits, const int *num_sigmas /*[K]*/,
+                                          int sigma_rule, const uint8_t *const *valid_host, const int *one_mask,
+                                          const vsom_similarity_masked_out *out /*[K]*/);
 /* Som::updateUMatrix of every member: per member exactly what vsom_umatrix gives (also in the member's VSOM_BUF_UMATRIX
  * buffer: a later vsom_get_umatrix of the member returns it).  u_out: NULL, or one pointer per member (NULL entries
  * skipped, else room for that member's N doubles).  Members whose map has N * part_len <= 4096 are computed by one launch

@@ -64,6 +64,7 @@ SYMBOLS = [
     "vsom_batch_schedule_masked", "vsom_ensemble_batch_epoch_masked", "vsom_ensemble_batch_schedule_masked",
     "vsom_masked_tiny_applies",
     "vsom_online_masked_tiny_applies", "vsom_ensemble_train_online_chunk_masked",
+    "vsom_ensemble_bmu_masked_batch", "vsom_ensemble_similarity_masked_batch",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -333,6 +334,11 @@ def lib():
     if hasattr(L, "vsom_bmu_topk_masked_batch"):        # (VSOM_LIB may name an older build: tools/topk_masked_bench.py --lib)
         L.vsom_bmu_topk_masked_batch.argtypes = [vp, C.c_uint32, C.c_uint64, C.c_size_t, C.c_size_t, C.POINTER(C.c_uint8),
                                                  C.c_int, C.POINTER(TopkMaskedOut)]
+    if hasattr(L, "vsom_ensemble_bmu_masked_batch"):    # (VSOM_LIB may name an older build: tools/ensemble_masked_query_bench.py --lib)
+        u8p = C.POINTER(C.c_uint8)
+        L.vsom_ensemble_bmu_masked_batch.argtypes = [vp, u64p, C.POINTER(u8p), C.POINTER(C.c_int), C.POINTER(MaskedOut)]
+        L.vsom_ensemble_similarity_masked_batch.argtypes = [vp, u64p, C.POINTER(C.c_int), C.c_int, C.POINTER(u8p),
+                                                            C.POINTER(C.c_int), C.POINTER(SimilarityMaskedOut)]
     _lib = L
     return L
 
@@ -1474,12 +1480,13 @@ class Ensemble:
         check(lib().vsom_ensemble_batch_schedule(self._h, sig, cnt, int(bool(reset_bmu)), out))
         return mses
 
-    def _validities(self, valid):
-        """valid (one entry per member: None for a plain member, else that member's B x J or 1-D J validity) as the
-        arrays, the pointer array and the one_mask array of the masked calls; ValueError before any call into the library"""
+    def _validities(self, valid, none="a plain member"):
+        """valid (one entry per member: None for a plain member -- in the masked queries a skipped one, `none` words the
+        message -- else that member's B x J or 1-D J validity) as the arrays, the pointer array and the one_mask array of
+        the masked calls; ValueError before any call into the library"""
         n = len(self.members)
         if isinstance(valid, np.ndarray) or not hasattr(valid, "__len__") or len(valid) != n:
-            raise ValueError(f"valid must be a list of one entry per member ({n}), None for a plain member")
+            raise ValueError(f"valid must be a list of one entry per member ({n}), None for {none}")
         keep = [None if v is None else c._validity(v) for c, v in zip(self.members, valid)]
         u8p = C.POINTER(C.c_uint8)
         ptrs = (u8p * max(n, 1))(*[u8p() if kv is None else kv[0].ctypes.data_as(u8p) for kv in keep])
@@ -1573,6 +1580,81 @@ class Ensemble:
         dp = (C.POINTER(C.c_float) * n)(*[_f(a) for a in dist])
         check(lib().vsom_ensemble_bmu_batch(self._h, ip, dp))
         return idx, dist
+
+    def _min_hits(self, min_hits):
+        """min_hits (a scalar or one value per member) as the uint64 array of the masked queries; ValueError for a
+        negative value or a wrong count"""
+        n = len(self.members)
+        vals = [int(v) for v in min_hits] if np.ndim(min_hits) else [int(min_hits)] * n
+        if len(vals) != n:
+            raise ValueError(f"{len(vals)} values of min_hits for {n} members")
+        if any(v < 0 for v in vals):
+            raise ValueError("min_hits must be >= 0")
+        return (C.c_uint64 * max(n, 1))(*vals)
+
+    def bmu_masked(self, valid, min_hits=0, fill=False):
+        """Context.bmu_masked of every member's whole chunk in one call (vsom_ensemble_bmu_masked_batch).  valid: a list with
+        one entry per member -- None (the member is skipped), a B x J array (nonzero = valid), or a 1-D column mask of J
+        entries; min_hits: a scalar or one value per member.  A list with one entry per member: the dict Context.bmu_masked
+        returns (bmu, dist, nvalid, and fill unless fill=False), or None for a skipped member.  ValueError before any call
+        into the library.  Read-only."""
+        keep, vptrs, ones = self._validities(valid, none="a skipped member")
+        mh = self._min_hits(min_hits)
+        n = len(self.members)
+        res, outs = [], (MaskedOut * max(n, 1))()
+        for k, (c, kv) in enumerate(zip(self.members, keep)):
+            if kv is None:
+                res.append(None)
+                continue
+            B, J = c.chunk_size, c.in_len
+            r = {"bmu": np.empty(B, np.uint64), "dist": np.empty(B, np.float32), "nvalid": np.empty(B, np.uint32),
+                 "fill": np.empty((B, J), np.float32) if fill else None}
+            for name, ctype in MaskedOut._fields_:
+                if r[name] is not None:
+                    setattr(outs[k], name, r[name].ctypes.data_as(ctype))
+            res.append(r)
+        check(lib().vsom_ensemble_bmu_masked_batch(self._h, mh, vptrs, ones, outs))
+        del keep
+        return res
+
+    def impute(self, valid, min_hits=0):
+        """every member's rows with the missing fields taken from the row's masked BMU (bmu_masked's fill): a list of
+        float32[B, J] arrays, None for a skipped member"""
+        return [None if r is None else r["fill"] for r in self.bmu_masked(valid, min_hits=min_hits, fill=True)]
+
+    def similarity_masked(self, valid, min_hits, num_sigmas, sigma_rule=SIGMA_FLOOR, delta=False):
+        """Context.similarity_masked of every member's whole chunk in one call (vsom_ensemble_similarity_masked_batch).
+        valid and min_hits as in bmu_masked; num_sigmas: a scalar or one value per member; sigma_rule applies to every
+        member.  A list with one entry per member: the dict Context.similarity_masked returns, or None for a skipped
+        member.  ValueError before any call into the library.  Read-only."""
+        if int(sigma_rule) not in (SIGMA_AS_WRITTEN, SIGMA_FLOOR):
+            raise ValueError(f"sigma_rule = {sigma_rule} is neither SIGMA_AS_WRITTEN nor SIGMA_FLOOR")
+        keep, vptrs, ones = self._validities(valid, none="a skipped member")
+        mh = self._min_hits(min_hits)
+        n = len(self.members)
+        ns = [int(v) for v in num_sigmas] if np.ndim(num_sigmas) else [int(num_sigmas)] * n
+        if len(ns) != n:
+            raise ValueError(f"{len(ns)} values of num_sigmas for {n} members")
+        if any(not -2 ** 31 <= v < 2 ** 31 for v in ns):
+            raise ValueError("num_sigmas must fit an int")
+        res, outs = [], (SimilarityMaskedOut * max(n, 1))()
+        for k, (c, kv) in enumerate(zip(self.members, keep)):
+            if kv is None:
+                res.append(None)
+                continue
+            B, J = c.chunk_size, c.in_len
+            r = {"bmu": np.empty(B, np.uint64), "dist": np.empty(B, np.float32), "dmax": np.empty(B, np.float32),
+                 "dmax_col": np.empty(B, np.uint32), "first": np.empty(B, np.float32), "amax": np.empty(B, np.float32),
+                 "amax_col": np.empty(B, np.uint32), "outside": np.empty(B, np.uint32),
+                 "delta": np.empty((B, J), np.float32) if delta else None, "nvalid": np.empty(B, np.uint32)}
+            for name, ctype in SimilarityMaskedOut._fields_:
+                if r[name] is not None:
+                    setattr(outs[k], name, r[name].ctypes.data_as(ctype))
+            res.append(r)
+        check(lib().vsom_ensemble_similarity_masked_batch(self._h, mh, (C.c_int * max(n, 1))(*ns), int(sigma_rule), vptrs,
+                                                          ones, outs))
+        del keep
+        return res
 
     def umatrix(self):
         """Som::updateUMatrix of every member (vsom_ensemble_umatrix): a list of float64 arrays, one per member, each

@@ -16,7 +16,11 @@
 // upload.  vsom_ensemble_bmu_batch scores every tiny member with one launch of ensemble_bmu_many_kernel<kind> per kind
 // (one workgroup per (member, 64 rows)): the exact search of the one-launch batch epoch's phase 1, whose results the
 // kernel also stores into one pinned buffer for all members; every other member runs vsom_bmu_batch in the same call.
-#include "vsom_device.hpp"
+// vsom_ensemble_bmu_masked_batch and vsom_ensemble_similarity_masked_batch are the same shape over the valid columns only
+// (DESIGN.md section 4v): one launch of ensemble_masked_many_kernel<kind, score> per kind, the search of that kernel on the
+// masked distance followed in the same workgroup by a per-row epilogue (nvalid, the imputed row, the similarity words).
+#include "vsom_masked_dist.hpp"
+#include "vsom_sim_row.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -52,6 +56,11 @@ struct vsom_ensemble {
     PinnedBuf<float> sc_dist;
     // U-matrices of the launched members, stored by the kernel (pinned host memory, grow-only)
     PinnedBuf<double> um_out;
+    // the masked queries: the per-row words of every launched member (arrays of B entries, vsom_similarity.hip's order) and
+    // the dense rows (fill / delta, B x J) of those that asked for them, stored by the kernel (pinned, grow-only; one set
+    // for both calls)
+    PinnedBuf<unsigned> mq_rows;
+    PinnedBuf<float> mq_dense;
 };
 
 static int ens_fail(size_t k, const char *what)
@@ -1027,6 +1036,327 @@ int vsom_ensemble_bmu_batch(vsom_ensemble *e, uint64_t *const *idx_out, float *c
             std::memcpy(dist_out[k], e->sc_dist.p + at[k], b * sizeof(float));
     }
     return VSOM_OK;
+}
+
+// ================================================================================================================
+// the masked queries: search over the valid columns, imputation, similarity
+// ================================================================================================================
+struct EnsMaskedDesc {
+    const float *x;              // the member's staged rows (Xs), pitch ldx
+    const float *map, *sigma;    // model rows, pitch ldm (sigma: SCORE only)
+    const u64 *hits;
+    u64 min_hits;
+    const unsigned char *valid;  // the member's validity bytes in the call's image, vstride bytes per row (0: one row for all)
+    unsigned *rows;              // the member's per-row words in the pinned results: arrays of B entries -- bmu (2 words),
+                                 // dist, then nvalid (search) or dmax, dmax_col, first, amax, amax_col, outside, nvalid (SCORE)
+    unsigned *dense;             // B x J words in the pinned results -- fill (search) or delta (SCORE) -- or null
+    int ldx, ldm, vstride, B, N, J;
+    float k;                     // SCORE: (float)num_sigmas, and the sigma rule
+    int floor_rule;
+};
+
+constexpr int ENS_MQ_WORDS = 4, ENS_MQ_SCORE_WORDS = 10;   // per row: the search's words, the similarity's
+
+// vsom_bmu_masked_batch (SCORE: vsom_similarity_masked_batch) for rows [64x, 64x + 64) of member y.  The search is
+// ensemble_bmu_many_kernel's on the masked distance: the model rows in LDS (N * J <= 4096 values), every (row, node)
+// distance by an 8-lane group (masked_group_dist: the residual +0 at an invalid column, the exact search's order), nodes
+// n > 0 with bmuHits[n] < min_hits left out (node 0 seeds whatever its hits), the argmin as an LDS atomicMin on the
+// (distance, index) key (strict <, lowest index, NaN never wins), a NaN at node 0 pins the unit to 0 with distance NaN.
+// Then, behind one barrier, one wavefront per row (16 rows each): the count of valid columns, the imputed row (the bits
+// of x where valid, of the unit's LDS row where not) when asked for, and under SCORE the row body of similarity_kernel
+// (vsom_sim_row.hpp, vsom_sim_reduce.inc: one column per lane and step) on x, the unit's LDS row and its sigmaMap row.
+// Validity bytes are read as given (non-zero = valid); Standard / Median only.  KIND is only a launch-group label, as in
+// ensemble_bmu_many_kernel (one launch per kind): the body never reads it, so the two instantiations of a SCORE are the
+// same machine code.
+template <int KIND, bool SCORE>
+__global__ __launch_bounds__(256) void ensemble_masked_many_kernel(const EnsMaskedDesc *__restrict__ descs)
+{
+    static_assert(KIND == VSOM_STANDARD || KIND == VSOM_MEDIAN, "the masked residual does not run over CLR's column pairs");
+    const EnsMaskedDesc a = descs[blockIdx.y];
+    const int s0 = blockIdx.x * ENS_SCORE_ROWS;
+    if (s0 >= a.B)
+        return;                                          // (workgroup-uniform)
+    const int T = a.B - s0 < ENS_SCORE_ROWS ? a.B - s0 : ENS_SCORE_ROWS, N = a.N, L = a.J;
+    extern __shared__ __attribute__((aligned(16))) unsigned char ens_mq_smem[];
+    u64 *keys = reinterpret_cast<u64 *>(ens_mq_smem);            // [64]
+    int *nan0 = reinterpret_cast<int *>(keys + ENS_SCORE_ROWS);   // [64]
+    float *ml = reinterpret_cast<float *>(nan0 + ENS_SCORE_ROWS); // N rows of L values
+    const int tid = threadIdx.x;
+    for (int i = tid; i < N * L; i += 256) {
+        const int n = i / L, e = i - n * L;
+        ml[i] = a.map[(size_t)n * a.ldm + e];
+    }
+    for (int s = tid; s < T; s += 256) {
+        keys[s] = ~0ull;
+        nan0[s] = 0;
+    }
+    __syncthreads();
+    const int grp = tid >> 3, k = tid & 7;
+    for (int p = grp; p < T * N; p += 32) {
+        const int s = p / N, n = p - s * N;
+        // findRestrictedBmu (Som.cpp:316-322): node 0 seeds unconditionally, the others need the hits (group-uniform)
+        if (n > 0 && a.min_hits && a.hits[n] < a.min_hits)
+            continue;
+        const float dd = masked_group_dist(a.x + (size_t)(s0 + s) * a.ldx, a.valid + (size_t)(s0 + s) * a.vstride,
+                                           ml + (size_t)n * L, L, k);
+        if (k == 0) {
+            if (n == 0 && dd != dd)
+                nan0[s] = 1;
+            atomicMin(&keys[s], vsom_key(dd, (uint32_t)n));
+        }
+    }
+    __syncthreads();
+    // the rows' epilogue: wavefront w takes rows w, w + 4, ...
+    const int lane = tid & 63;
+    const size_t R = (size_t)a.B;
+    SimArgs sa{};                                        // (sim_column reads k and floor_rule)
+    sa.k = a.k;
+    sa.floor_rule = a.floor_rule;
+    for (int s = tid >> 6; s < T; s += 4) {
+        const u64 key = keys[s];
+        const u64 idx = nan0[s] ? 0ull : (key & 0xFFFFFFFFull);
+        const float sq = nan0[s] ? __uint_as_float(0x7FC00000u) : __uint_as_float((uint32_t)(key >> 32));
+        const size_t i = (size_t)(s0 + s);
+        const unsigned *xr = reinterpret_cast<const unsigned *>(a.x) + i * a.ldx;
+        const unsigned *mr = reinterpret_cast<const unsigned *>(ml) + (size_t)idx * L;
+        const float *sr = a.sigma + (size_t)idx * a.ldm;
+        const unsigned char *vr = a.valid + i * (size_t)a.vstride;
+        unsigned *dr = a.dense ? a.dense + i * L : nullptr;
+        unsigned nv = 0;
+        SimLane l;
+        sim_lane_init(l);
+        for (int d = lane; d < L; d += 64) {
+            const bool valid = vr[d] != 0;
+            const unsigned xb = xr[d], mb = mr[d];
+            nv += valid ? 1u : 0u;
+            if constexpr (SCORE) {
+                const float out = sim_column<true>(l, sa, (uint32_t)d, __uint_as_float(xb), __uint_as_float(mb), sr[d], valid);
+                if (dr)
+                    dr[d] = __float_as_uint(out);
+            } else if (dr) {
+                dr[d] = valid ? xb : mb;
+            }
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1)
+            nv += __shfl_xor(nv, m);
+        if constexpr (SCORE) {
+            constexpr int W = 1;                         // one column per lane and step
+#include "vsom_sim_reduce.inc"
+            if (lane == 0) {
+                a.rows[3 * R + i] = __float_as_uint(dmax);
+                a.rows[4 * R + i] = dc;
+                a.rows[5 * R + i] = __float_as_uint(first);
+                a.rows[6 * R + i] = __float_as_uint(amax);
+                a.rows[7 * R + i] = ac;
+                a.rows[8 * R + i] = cnt;
+            }
+        }
+        if (lane == 0) {
+            reinterpret_cast<u64 *>(a.rows)[i] = idx;
+            a.rows[2 * R + i] = __float_as_uint(sq);
+            a.rows[(SCORE ? 9 : 3) * R + i] = nv;
+        }
+    }
+}
+
+// what both masked queries refuse for member k with a validity, or null
+static const char *ens_masked_query_refusal(const vsom_ctx *c, const char *what, std::string &buf)
+{
+    if (c->cu) {
+        buf = std::string(what) + ": custom contexts are not supported";
+        return buf.c_str();
+    }
+    if (c->transform == VSOM_CLR) {
+        buf = std::string(what) + ": CLR contexts are not supported (the residual runs over column pairs)";
+        return buf.c_str();
+    }
+    return ens_rows_refusal(c);
+}
+
+// a launched member's row words from the pinned results into the caller's arrays (null: not wanted): array 0 is bmu, two
+// words per row, every later one a word per row, in the order the kernel stores them
+static void ens_mq_copy_out(const unsigned *p, size_t b, std::initializer_list<void *> dst)
+{
+    size_t i = 0;
+    for (void *d : dst) {
+        if (d)
+            std::memcpy(d, p + (i == 0 ? 0 : (i + 1) * b), (i == 0 ? 2 * b : b) * 4);
+        ++i;
+    }
+}
+
+// what both entry points check: the arrays every form takes, and -- last, behind the call's own arguments -- every member
+// with a validity (`what`: the single call, for the refusal's text).  Nothing is enqueued for any member unless every
+// member with a validity can be searched.
+static int ens_masked_query_arrays(const vsom_ensemble *e, const uint8_t *const *valid_host, const void *out)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    if (!valid_host)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null valid_host array");
+    if (!out)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null out array");
+    return VSOM_OK;
+}
+
+static int ens_masked_query_members(const vsom_ensemble *e, const char *what, const uint8_t *const *valid_host)
+{
+    std::string buf;
+    for (size_t k = 0; k < e->m.size(); ++k)
+        if (valid_host[k])
+            if (const char *why = ens_masked_query_refusal(e->m[k], what, buf))
+                return ens_fail(k, why);
+    return VSOM_OK;
+}
+
+// Both masked queries (the callers have made their argument checks): bout (the search, vsom_bmu_masked_batch per member) or
+// sout (the similarity, vsom_similarity_masked_batch per member) is non-null.  The members with a validity and rows whose
+// map fits the kernel's LDS rows go as one launch per kind, their validity bytes as one pinned image in the launch's
+// descriptor slot, copied once; every other member with a validity runs its single call while the launches run.
+static int ens_masked_query(vsom_ensemble *e, const uint64_t *min_hits, const int *num_sigmas, int sigma_rule,
+                            const uint8_t *const *valid_host, const int *one_mask, const vsom_masked_out *bout,
+                            const vsom_similarity_masked_out *sout)
+{
+    const bool score = sout != nullptr;
+    const size_t n = e->m.size();
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    EnsCall call(e);
+    std::vector<size_t> asked(n);
+    for (size_t k = 0; k < n; ++k)
+        asked[k] = valid_host[k] != nullptr;             // (a member without a validity is not touched)
+    if (int rc = join_members(e, asked.data(), true))    // (a pending sigmaMap is materialised here)
+        return rc;
+    const size_t lds_cap = std::min(e->lds_limit, (size_t)64 << 10);
+    const size_t words = score ? ENS_MQ_SCORE_WORDS : ENS_MQ_WORDS;
+    ens_scratch(e, sizeof(EnsMaskedDesc));
+    std::vector<size_t> v_at(n, 0), vbytes(n, 0), w_at(n, 0), d_at(n, 0);
+    std::vector<float *> dense(n, nullptr);              // the caller's fill / delta
+    size_t vtotal = 0, wtotal = 0, dtotal = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const vsom_ctx *c = e->m[k];
+        if (!asked[k] || c->B == 0)
+            continue;
+        dense[k] = score ? sout[k].delta : bout[k].fill;
+        const size_t smem = ENS_SCORE_ROWS * (sizeof(u64) + sizeof(int)) + (size_t)c->N * c->J * sizeof(float);
+        if ((size_t)c->N * c->part_len > 4096 || smem > lds_cap)
+            continue;
+        e->grp[k] = c->transform;
+        e->smem[k] = smem;
+        e->ext[k] = (unsigned)((c->B + ENS_SCORE_ROWS - 1) / ENS_SCORE_ROWS);
+        vbytes[k] = ((one_mask && one_mask[k]) ? 1 : c->B) * (size_t)c->J;
+        v_at[k] = vtotal;
+        vtotal += (vbytes[k] + 15) / 16 * 16;
+        w_at[k] = wtotal;
+        wtotal += (c->B * words + 3) / 4 * 4;            // (16-byte steps: the 8-byte units lead each member's words)
+        if (dense[k]) {
+            d_at[k] = dtotal;
+            dtotal += c->B * (size_t)c->J;
+        }
+    }
+    int rc = VSOM_OK;
+    if (wtotal) {
+        if (int jrc = call.join(ENS_LAUNCHED))
+            return jrc;
+        // the slot ens_launch is about to take: its last launch has completed, so its image may be rewritten
+        auto &s = e->slot[e->next];
+        if (s.valid)
+            VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
+        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(s.img_host, vtotal), vsom_member(s.img_dev, vtotal)}));
+        // (no kernel of an earlier call is running: every call ends in a wait)
+        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(e->mq_rows, wtotal), vsom_member(e->mq_dense, std::max<size_t>(dtotal, 1))}));
+        for (size_t k = 0; k < n; ++k)
+            if (e->grp[k] >= 0)
+                std::memcpy(s.img_host.p + v_at[k], valid_host[k], vbytes[k]);
+        VSOM_HIP_CHECK(hipMemcpyAsync(s.img_dev.p, s.img_host.p, vtotal, hipMemcpyHostToDevice, call.ls));
+        for (size_t k = 0; k < n; ++k) {
+            if (e->grp[k] < 0)
+                continue;
+            const vsom_ctx *c = e->m[k];
+            EnsMaskedDesc a;
+            a.x = c->Xs.p;
+            a.map = c->map.p;
+            a.sigma = c->sigma.p;
+            a.hits = c->hits.p;
+            a.min_hits = min_hits ? min_hits[k] : 0;
+            a.valid = s.img_dev.p + v_at[k];
+            a.rows = e->mq_rows.p + w_at[k];
+            a.dense = dense[k] ? reinterpret_cast<unsigned *>(e->mq_dense.p + d_at[k]) : nullptr;
+            a.ldx = (int)c->xpitch;
+            a.ldm = (int)c->pitch;
+            a.vstride = (one_mask && one_mask[k]) ? 0 : (int)c->J;
+            a.B = (int)c->B;
+            a.N = (int)c->N;
+            a.J = (int)c->J;
+            a.k = score ? (float)num_sigmas[k] : 0.f;
+            a.floor_rule = sigma_rule == VSOM_SIGMA_FLOOR;
+            std::memcpy(e->desc.data() + k * sizeof(a), &a, sizeof(a));
+        }
+        static void (*const kernel[2][2])(const EnsMaskedDesc *) = {
+            {ensemble_masked_many_kernel<VSOM_STANDARD, false>, ensemble_masked_many_kernel<VSOM_MEDIAN, false>},
+            {ensemble_masked_many_kernel<VSOM_STANDARD, true>, ensemble_masked_many_kernel<VSOM_MEDIAN, true>}};
+        rc = ens_launch(call, ENS_JOINED, 2, sizeof(EnsMaskedDesc), ENS_MAX_Y, ens_always_ready,
+                        [score](int kind, const void *d, unsigned cnt, size_t smem, unsigned tiles, hipStream_t st) -> int {
+                            hipLaunchKernelGGL(kernel[score][kind], dim3(tiles, cnt), dim3(256), smem, st,
+                                               static_cast<const EnsMaskedDesc *>(d));
+                            VSOM_HIP_CHECK_AS(hipGetLastError(), "ensemble_masked_many_kernel");
+                            return VSOM_OK;
+                        });
+    }
+    // the other members through their single calls, while the launches run
+    for (size_t k = 0; k < n && !rc; ++k) {
+        vsom_ctx *c = e->m[k];
+        if (!asked[k] || c->B == 0 || e->grp[k] >= 0)
+            continue;
+        const int one = one_mask ? one_mask[k] : 0;
+        const u64 mh = min_hits ? min_hits[k] : 0;
+        rc = score ? launch_similarity_masked(c, mh, num_sigmas[k], sigma_rule, 0, c->B, valid_host[k], one, &sout[k])
+                   : launch_masked(c, mh, 0, c->B, valid_host[k], one, &bout[k]);
+    }
+    if ((rc = call.end(rc)))
+        return rc;
+    // results of the launched members: the kernel stored them into the pinned buffers
+    for (size_t k = 0; k < n; ++k) {
+        if (e->grp[k] < 0)
+            continue;
+        const size_t b = e->m[k]->B;
+        const unsigned *p = e->mq_rows.p + w_at[k];
+        if (score) {
+            const vsom_similarity_masked_out &o = sout[k];
+            ens_mq_copy_out(p, b, {o.bmu, o.dist, o.dmax, o.dmax_col, o.first, o.amax, o.amax_col, o.outside, o.nvalid});
+        } else {
+            const vsom_masked_out &o = bout[k];
+            ens_mq_copy_out(p, b, {o.bmu, o.dist, o.nvalid});
+        }
+        if (dense[k])
+            std::memcpy(dense[k], e->mq_dense.p + d_at[k], b * (size_t)e->m[k]->J * sizeof(float));
+    }
+    return VSOM_OK;
+}
+
+int vsom_ensemble_bmu_masked_batch(vsom_ensemble *e, const uint64_t *min_hits, const uint8_t *const *valid_host,
+                                   const int *one_mask, const vsom_masked_out *out)
+{
+    if (int rc = ens_masked_query_arrays(e, valid_host, out))
+        return rc;
+    if (int rc = ens_masked_query_members(e, "vsom_bmu_masked_batch", valid_host))
+        return rc;
+    return ens_masked_query(e, min_hits, nullptr, VSOM_SIGMA_FLOOR, valid_host, one_mask, out, nullptr);
+}
+
+int vsom_ensemble_similarity_masked_batch(vsom_ensemble *e, const uint64_t *min_hits, const int *num_sigmas, int sigma_rule,
+                                          const uint8_t *const *valid_host, const int *one_mask,
+                                          const vsom_similarity_masked_out *out)
+{
+    if (int rc = ens_masked_query_arrays(e, valid_host, out))
+        return rc;
+    if (!num_sigmas)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null num_sigmas array");
+    if (sigma_rule != VSOM_SIGMA_AS_WRITTEN && sigma_rule != VSOM_SIGMA_FLOOR)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: unknown sigma_rule");
+    if (int rc = ens_masked_query_members(e, "vsom_similarity_masked_batch", valid_host))
+        return rc;
+    return ens_masked_query(e, min_hits, num_sigmas, sigma_rule, valid_host, one_mask, nullptr, out);
 }
 
 // Som::updateUMatrix of every member (vsom_umatrix.hip): members whose model and sigma rows fit LDS in one launch per kind

@@ -20,83 +20,16 @@
 //                      row), and delta of an invalid column is the quiet NaN by select before anything is reduced: such a
 //                      column can be neither dmax nor first nor amax, is not counted outside, and stores 0 in the dense
 //                      report, whatever x, map and sigmaMap hold there.  Lane 0 stores a tenth word, the row's nvalid.
-#include "vsom_device.hpp"
+#include "vsom_sim_row.hpp"
 #include <algorithm>
 #include <cstring>
 
-#define SIM_NONE 0xFFFFFFFFu
 #define SIM_ROWS_PER_WG 4
 #define SIM_ROW_WORDS 9     // bmu (2), dist, dmax, dmax_col, first, amax, amax_col, outside
 #define SIM_MROW_WORDS 10   // ... and nvalid (vsom_similarity_masked_batch)
 
-struct SimArgs {
-    const float *x;             // staged rows (Xs), pitch ldx
-    const float *map, *sigma;   // model rows, pitch ldm
-    const u64 *lastbmu;         // per chunk row; MASKED: the slice's search results, entry r - s0 for row r
-    const float *sqres;
-    const unsigned *nvalid;     // MASKED only: the slice's counts of valid columns
-    const unsigned char *valid; // rows [r0, r1) x J, or null: every column valid; MASKED: the slice's packed rows, vstride
-                                // bytes apart (0: the one row every sample shares)
-    float *delta;               // the slice's dense report, rows x C, or null
-    unsigned *rows;             // per-row results of [r0, r1): SIM_ROW_WORDS arrays of R entries
-    int ldx, ldm, part_len, part_pitch;
-    int J, C, N, R, vstride;
-    float k;
-    int floor_rule;
-};
-
-// order-preserving image of a float that is not NaN (-0 taken as +0: the two compare equal)
-__device__ __forceinline__ uint32_t sim_ord(float v)
-{
-    const uint32_t u = __float_as_uint(v == 0.f ? 0.f : v);
-    return (u >> 31) ? ~u : (u | 0x80000000u);
-}
-
-__device__ __forceinline__ u64 sim_wave_max(u64 v)
-{
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const u64 o = __shfl_xor(v, m);
-        v = o > v ? o : v;
-    }
-    return v;
-}
-
-struct SimLane {
-    float dmax_v, first_v, amax_v;
-    uint32_t dmax_c, first_c, amax_c, outside;
-};
-
-template <bool MASKED>
-__device__ __forceinline__ float sim_column(SimLane &l, const SimArgs &a, uint32_t d, float x, float m, float s, bool valid)
-{
-    const float eps = 0.00001f;
-    const float sM = a.floor_rule ? (s > eps ? s : eps) : (s > eps ? eps : s);
-    const float t = x - m;
-    const float q = t / sM;
-    float delta = q / a.k;
-    if constexpr (MASKED)
-        delta = valid ? delta : __uint_as_float(0x7FC00000u);
-    const float sk = sM * a.k;
-    const float lo = m - sk, hi = m + sk;
-    if (delta == delta && (l.dmax_c == SIM_NONE || delta > l.dmax_v)) {
-        l.dmax_v = delta;
-        l.dmax_c = d;
-    }
-    if (l.first_c == SIM_NONE && delta > -99999999.f) {
-        l.first_v = delta;
-        l.first_c = d;
-    }
-    const float ad = fabsf(delta);
-    const bool finite = ad < __builtin_inff();     // (false for NaN)
-    if (valid && finite && (l.amax_c == SIM_NONE || ad > l.amax_v)) {
-        l.amax_v = ad;
-        l.amax_c = d;
-    }
-    if (valid && (x < lo || x > hi))
-        ++l.outside;
-    return finite ? delta : 0.f;
-}
+// (SimArgs, the column arithmetic sim_column and the wave reductions: vsom_sim_row.hpp and vsom_sim_reduce.inc, shared
+//  with the ensemble's masked query kernel)
 
 // VEC: the model row is one part and lanes take four consecutive columns per step (pitches are multiples of 32 floats and
 // C <= J, D: a 16-byte load of a row's last, partial quad stays inside the padded row).  Otherwise one column per lane and
@@ -125,11 +58,7 @@ __global__ __launch_bounds__(64 * SIM_ROWS_PER_WG) void similarity_kernel(SimArg
     const bool quad_store = VEC && (C & 3) == 0;
 
     SimLane l;
-    l.dmax_v = -__builtin_inff();
-    l.first_v = __uint_as_float(0x7FC00000u);
-    l.amax_v = 0.f;
-    l.dmax_c = l.first_c = l.amax_c = SIM_NONE;
-    l.outside = 0;
+    sim_lane_init(l);
 
     for (int g0 = lane; g0 * W < C; g0 += 64 * U) {
         float xv[U][W], mv[U][W], sv[U][W];
@@ -189,19 +118,7 @@ __global__ __launch_bounds__(64 * SIM_ROWS_PER_WG) void similarity_kernel(SimArg
     }
 
     // the row's results over the 64 lanes; the lane that owns column c is (c / W) % 64
-    const u64 kd = sim_wave_max(l.dmax_c == SIM_NONE ? 0ull : ((u64)sim_ord(l.dmax_v) << 32) | (u64)(~l.dmax_c));
-    const u64 ka = sim_wave_max(l.amax_c == SIM_NONE ? 0ull : ((u64)sim_ord(l.amax_v) << 32) | (u64)(~l.amax_c));
-    uint32_t fc = l.first_c, cnt = l.outside;
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) {
-        const uint32_t o = __shfl_xor(fc, m);
-        fc = o < fc ? o : fc;
-        cnt += __shfl_xor(cnt, m);
-    }
-    const uint32_t dc = kd ? ~(uint32_t)kd : SIM_NONE, ac = ka ? ~(uint32_t)ka : SIM_NONE;
-    const float dmax = __shfl(l.dmax_v, dc == SIM_NONE ? 0 : (int)((dc / W) & 63));     // (no column: every lane holds -inf)
-    const float amax = __shfl(l.amax_v, ac == SIM_NONE ? 0 : (int)((ac / W) & 63));     // (... 0)
-    const float first = __shfl(l.first_v, fc == SIM_NONE ? 0 : (int)((fc / W) & 63));   // (... NaN)
+#include "vsom_sim_reduce.inc"
     if (lane == 0) {
         const size_t i = (size_t)(r - r0), R = (size_t)a.R;
         reinterpret_cast<u64 *>(a.rows)[i] = a.lastbmu[ri];
