@@ -1063,6 +1063,57 @@ int vsom_ensemble_bmu_masked_batch(vsom_ensemble *e, const uint64_t *min_hits /*
 int vsom_ensemble_similarity_masked_batch(vsom_ensemble *e, const uint64_t *min_hits, const int *num_sigmas /*[K]*/,
                                           int sigma_rule, const uint8_t *const *valid_host, const int *one_mask,
                                           const vsom_similarity_masked_out *out /*[K]*/);
+/* The k best matching units of every row of every member in one call, over all columns (vsom_bmu_topk_batch per member) or
+ * over the valid columns only (vsom_bmu_topk_masked_batch per member): the runner-up that the topographic error of every
+ * map of a sweep needs.  k holds one value per member; out[m] holds member m's host pointers
+ * (idx[B_m * k_m] row-major, required for a covered member; dist[B_m * k_m], count[B_m], nvalid[B_m] may be NULL; the
+ * plain call ignores count and nvalid).  blend is out of scope for the ensemble calls -- the struct has no such field:
+ * vsom_bmu_topk_masked_batch on the member gives it.
+ * Plain call: covers every member with out[m].idx != NULL; a member with a NULL idx is SKIPPED -- nothing is enqueued for
+ * it and out[m] is not written.  Standard, Median and CLR members are taken, as in vsom_ensemble_bmu_batch.  Per covered
+ * member idx and dist are, bit for bit, those of
+ *   vsom_bmu_topk_batch(member m, k[m], 0, B_m, idx, dist)
+ * made on a context that is no member, and what is stated at that call holds word for word: nodes ordered by the key
+ * (d_i, i) with NaN after +inf, every node a candidate, entry 0 findBmu's BMU -- node 0 with 0x7FC00000 when d_0 is NaN,
+ * the others behind it in key order -- and a NaN distance stored as 0x7FC00000.
+ * Masked call: covers every member with valid_host[m] != NULL (B_m x J_m bytes, row-major, or J_m bytes when
+ * one_mask[m] != 0; one_mask NULL: all 0; a non-zero byte means valid); NULL: SKIPPED, as in
+ * vsom_ensemble_bmu_masked_batch.  min_hits NULL: all 0.  Per covered member idx, dist, count and nvalid are, bit for
+ * bit, those of
+ *   vsom_bmu_topk_masked_batch(member m, k[m], min_hits[m], 0, B_m, valid_host[m], one_mask[m], ...)
+ * and that call's contract holds unchanged: the candidates are node 0 and the nodes with bmuHits >= min_hits; a row with
+ * fewer than k candidates has count < k and idx = UINT64_MAX, dist = 0x7FC00000 from entry count on; a row without a
+ * valid column gets that call's list (the first count candidates in index order, every distance +0, nvalid 0); what x
+ * and the map hold at an invalid position reaches no output.
+ * Both: a member with B_m = 0 writes nothing.  Read-only: every member's lastBMU, sqres, map, sigmaMap, S, weightMap,
+ * bmuHits and chunk are untouched.  valid_host is not read after the call returns.  Each call ends in one wait.
+ * The fast path: a covered member that is not custom, with B_m > 0, k <= N, N * part_len <= 4096 (part_len: D, or D / 2
+ * for CLR) and an LDS need of 512 + 512 (k | 1) + 4 N D bytes within min(the device's limit per workgroup, 64 KiB) runs
+ * in one launch per kind of ensemble_topk_many_kernel, one workgroup per (member, 64 rows): the model rows in LDS, every
+ * (row, node) distance by the 8-lane routine of vsom_ensemble_bmu_batch (masked: of vsom_ensemble_bmu_masked_batch),
+ * each row's k smallest keys kept as a sorted list in LDS.  vsom_ensemble_topk_applies reports it.  The validity bytes of
+ * those members travel as one pinned image, copied once per call, and their results return through the pinned buffers
+ * of the masked queries.  Every other covered member runs its single call inside the same call, while the launches are
+ * in flight.
+ * Refuses (VSOM_ERR_INVALID, naming the member, before anything is enqueued for any member; a refused call changes
+ * nothing): a null ensemble, k array or out array; masked: a null valid_host array; for a covered member: a null idx
+ * (masked call), k = 0, k > 64, k > N, a custom context, no chunk, the next chunk staged ahead over its rows; masked: a
+ * CLR context (the residual runs over column pairs). */
+typedef struct vsom_ensemble_topk_out {   /* host pointers of ONE member; idx required, the others may be NULL */
+    uint64_t *idx;      /* [B_k * k_k] row-major */
+    float    *dist;     /* [B_k * k_k] */
+    uint32_t *count;    /* [B_k]  masked call only; the plain call ignores it */
+    uint32_t *nvalid;   /* [B_k]  masked call only; the plain call ignores it */
+} vsom_ensemble_topk_out;
+int vsom_ensemble_bmu_topk_batch(vsom_ensemble *e, const uint32_t *k /*[K]*/, const vsom_ensemble_topk_out *out /*[K]*/);
+int vsom_ensemble_bmu_topk_masked_batch(vsom_ensemble *e, const uint32_t *k /*[K]*/,
+                                        const uint64_t *min_hits /*[K], NULL: all 0*/,
+                                        const uint8_t *const *valid_host /*[K]*/, const int *one_mask /*[K], NULL: all 0*/,
+                                        const vsom_ensemble_topk_out *out /*[K]*/);
+/* 1 when member `member` with that k would run in ensemble_topk_many_kernel (the fast path above, on its loaded chunk),
+ * 0 when it would run its single call inside the ensemble call (or be refused); VSOM_ERR_INVALID for a null ensemble or
+ * a member index out of range.  masked != 0: the masked call, which takes no CLR member. */
+int vsom_ensemble_topk_applies(const vsom_ensemble *e, size_t member, uint32_t k, int masked);
 /* Som::updateUMatrix of every member: per member exactly what vsom_umatrix gives (also in the member's VSOM_BUF_UMATRIX
  * buffer: a later vsom_get_umatrix of the member returns it).  u_out: NULL, or one pointer per member (NULL entries
  * skipped, else room for that member's N doubles).  Members whose map has N * part_len <= 4096 are computed by one launch

@@ -65,6 +65,7 @@ SYMBOLS = [
     "vsom_masked_tiny_applies",
     "vsom_online_masked_tiny_applies", "vsom_ensemble_train_online_chunk_masked",
     "vsom_ensemble_bmu_masked_batch", "vsom_ensemble_similarity_masked_batch",
+    "vsom_ensemble_bmu_topk_batch", "vsom_ensemble_bmu_topk_masked_batch", "vsom_ensemble_topk_applies",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -102,6 +103,11 @@ class TopkMaskedOut(C.Structure):
     """vsom_topk_masked_out: host pointers; idx is required, the others may be NULL"""
     _fields_ = [("idx", C.POINTER(C.c_uint64)), ("dist", C.POINTER(C.c_float)), ("count", C.POINTER(C.c_uint32)),
                 ("nvalid", C.POINTER(C.c_uint32)), ("blend", C.POINTER(C.c_double))]
+
+
+class EnsembleTopkOut(C.Structure):
+    """vsom_ensemble_topk_out: one member's host pointers; idx is required for a covered member, the others may be NULL"""
+    _fields_ = TopkMaskedOut._fields_[:4]
 
 
 class GenerateOut(C.Structure):
@@ -339,6 +345,12 @@ def lib():
         L.vsom_ensemble_bmu_masked_batch.argtypes = [vp, u64p, C.POINTER(u8p), C.POINTER(C.c_int), C.POINTER(MaskedOut)]
         L.vsom_ensemble_similarity_masked_batch.argtypes = [vp, u64p, C.POINTER(C.c_int), C.c_int, C.POINTER(u8p),
                                                             C.POINTER(C.c_int), C.POINTER(SimilarityMaskedOut)]
+    if hasattr(L, "vsom_ensemble_bmu_topk_batch"):      # (VSOM_LIB may name an older build: tools/ensemble_topk_bench.py --lib)
+        u8p, u32p = C.POINTER(C.c_uint8), C.POINTER(C.c_uint32)
+        L.vsom_ensemble_bmu_topk_batch.argtypes = [vp, u32p, C.POINTER(EnsembleTopkOut)]
+        L.vsom_ensemble_bmu_topk_masked_batch.argtypes = [vp, u32p, u64p, C.POINTER(u8p), C.POINTER(C.c_int),
+                                                          C.POINTER(EnsembleTopkOut)]
+        L.vsom_ensemble_topk_applies.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_int]
     _lib = L
     return L
 
@@ -1655,6 +1667,112 @@ class Ensemble:
                                                           ones, outs))
         del keep
         return res
+
+    def _ks(self, k):
+        """k (an int or one value per member) as the uint32 array of the top-k calls and as a list; ValueError for a
+        wrong count or a value outside [1, 64]"""
+        n = len(self.members)
+        vals = [int(v) for v in k] if np.ndim(k) else [int(k)] * n
+        if len(vals) != n:
+            raise ValueError(f"{len(vals)} values of k for {n} members")
+        if any(not 1 <= v <= 64 for v in vals):
+            raise ValueError("k must be in [1, 64]")
+        return (C.c_uint32 * max(n, 1))(*vals), vals
+
+    def _topk_outputs(self, ks, covered, dist, masked):
+        """the result dicts (None for a member that is not covered) and the vsom_ensemble_topk_out array over them"""
+        n = len(self.members)
+        res, outs = [], (EnsembleTopkOut * max(n, 1))()
+        for m, c in enumerate(self.members):
+            if not covered[m]:
+                res.append(None)
+                continue
+            B = c.chunk_size
+            r = {"idx": np.empty((B, ks[m]), np.uint64), "dist": np.empty((B, ks[m]), np.float32) if dist else None}
+            if masked:
+                r.update(count=np.empty(B, np.uint32), nvalid=np.empty(B, np.uint32))
+            for name, ctype in EnsembleTopkOut._fields_:
+                if r.get(name) is not None:
+                    setattr(outs[m], name, r[name].ctypes.data_as(ctype))
+            res.append(r)
+        return res, outs
+
+    def bmu_topk(self, k, dist=True, members=None):
+        """Context.bmu_topk of every member's whole chunk in one call (vsom_ensemble_bmu_topk_batch).  k: an int or one
+        value per member; members: None (every member) or the indices of the members to cover, the others are skipped.
+        A list with one entry per member: {"idx": uint64[B, k], "dist": float32[B, k] or None}, or None for a skipped
+        member.  ValueError before any call into the library.  Read-only."""
+        n = len(self.members)
+        kp, ks = self._ks(k)
+        covered = [True] * n
+        if members is not None:
+            chosen = [int(m) for m in members]
+            if any(not 0 <= m < n for m in chosen):
+                raise ValueError(f"members must be indices in [0, {n})")
+            covered = [m in chosen for m in range(n)]
+        res, outs = self._topk_outputs(ks, covered, dist, False)
+        check(lib().vsom_ensemble_bmu_topk_batch(self._h, kp, outs))
+        return res
+
+    def bmu_topk_masked(self, k, valid, min_hits=0, dist=True):
+        """Context.bmu_topk_masked (without blend) of every member's whole chunk in one call
+        (vsom_ensemble_bmu_topk_masked_batch).  k: an int or one value per member; valid and min_hits as in bmu_masked.
+        A list with one entry per member: {"idx": uint64[B, k], "dist": float32[B, k] or None, "count": uint32[B],
+        "nvalid": uint32[B]}, or None for a skipped member.  ValueError before any call into the library.  Read-only."""
+        kp, ks = self._ks(k)
+        keep, vptrs, ones = self._validities(valid, none="a skipped member")
+        mh = self._min_hits(min_hits)
+        res, outs = self._topk_outputs(ks, [kv is not None for kv in keep], dist, True)
+        check(lib().vsom_ensemble_bmu_topk_masked_batch(self._h, kp, mh, vptrs, ones, outs))
+        del keep
+        return res
+
+    def topk_applies(self, member, k, masked=False):
+        """would that member with that k run in the one-launch kernel of bmu_topk / bmu_topk_masked
+        (vsom_ensemble_topk_applies)?"""
+        rc = lib().vsom_ensemble_topk_applies(self._h, int(member), int(k), int(bool(masked)))
+        if rc < 0:
+            check(rc)
+        return bool(rc)
+
+    def _rankable(self):
+        """the members a topographic error exists for: at least 2 nodes and a chunk with rows"""
+        return [c.n_nodes >= 2 and c.chunk_size > 0 for c in self.members]
+
+    def topographic_error(self):
+        """the topographic error of every member on its chunk, from one bmu_topk call with k = 2: a float64 array, member
+        m's value som.topographic_error(idx2, width) on its lists; NaN for a member with fewer than 2 nodes or no rows"""
+        from .som import topographic_error
+        ok = self._rankable()
+        te = np.full(len(self.members), np.nan, np.float64)
+        if any(ok):
+            got = self.bmu_topk(2, dist=False, members=[m for m, v in enumerate(ok) if v])
+            for m, c in enumerate(self.members):
+                if ok[m]:
+                    te[m] = topographic_error(got[m]["idx"], c.width)
+        return te
+
+    def topographic_error_masked(self, valid, min_hits=0):
+        """the topographic error of every member over the valid columns, from one bmu_topk_masked call with k = 2:
+        (errors float64[K], rows_counted int64[K]).  A member's rows count when they have a valid column and a second unit
+        (nvalid >= 1 and count >= 2, the rule of Som.topographicErrorMasked); its error is som.topographic_error over
+        them.  NaN and 0 for a member with fewer than 2 nodes, no rows or no validity (None)."""
+        from .som import topographic_error
+        n = len(self.members)
+        if isinstance(valid, np.ndarray) or not hasattr(valid, "__len__") or len(valid) != n:
+            raise ValueError(f"valid must be a list of one entry per member ({n}), None for a skipped member")
+        ok = self._rankable()
+        te = np.full(n, np.nan, np.float64)
+        counted = np.zeros(n, np.int64)
+        use = [v if ok[m] else None for m, v in enumerate(valid)]
+        if any(v is not None for v in use):
+            got = self.bmu_topk_masked(2, use, min_hits=min_hits, dist=False)
+            for m, c in enumerate(self.members):
+                if got[m] is not None:
+                    keep = (got[m]["nvalid"] >= 1) & (got[m]["count"] >= 2)
+                    te[m] = topographic_error(got[m]["idx"][keep], c.width)
+                    counted[m] = int(keep.sum())
+        return te, counted
 
     def umatrix(self):
         """Som::updateUMatrix of every member (vsom_ensemble_umatrix): a list of float64 arrays, one per member, each

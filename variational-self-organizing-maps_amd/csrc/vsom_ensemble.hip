@@ -19,6 +19,8 @@
 // vsom_ensemble_bmu_masked_batch and vsom_ensemble_similarity_masked_batch are the same shape over the valid columns only
 // (DESIGN.md section 4v): one launch of ensemble_masked_many_kernel<kind, score> per kind, the search of that kernel on the
 // masked distance followed in the same workgroup by a per-row epilogue (nvalid, the imputed row, the similarity words).
+// vsom_ensemble_bmu_topk_batch and vsom_ensemble_bmu_topk_masked_batch keep, in the same workgroup
+// shape, each row's k smallest keys as a sorted list in LDS: one launch of ensemble_topk_many_kernel<kind, masked> per kind.
 #include "vsom_masked_dist.hpp"
 #include "vsom_sim_row.hpp"
 #include <algorithm>
@@ -1357,6 +1359,348 @@ int vsom_ensemble_similarity_masked_batch(vsom_ensemble *e, const uint64_t *min_
     if (int rc = ens_masked_query_members(e, "vsom_similarity_masked_batch", valid_host))
         return rc;
     return ens_masked_query(e, min_hits, num_sigmas, sigma_rule, valid_host, one_mask, nullptr, out);
+}
+
+// ================================================================================================================
+// the k best matching units of every row of every member, plain and over the valid columns
+// ================================================================================================================
+struct EnsTopkDesc {
+    DistArgs d;                  // plain: ensemble_bmu_many_kernel's operands; masked: xa = the staged rows (Xs), ma = the map
+    const u64 *hits;             // masked: the candidates are node 0 and the nodes with hits >= min_hits
+    u64 min_hits;
+    const unsigned char *valid;  // masked: the member's validity bytes in the call's image, vstride bytes per row (0: one row)
+    unsigned *out;               // the member's words in the pinned results: idx (B x k, two words each), dist (B x k),
+                                 // count (B), nvalid (B)
+    int vstride, B, N, k;
+};
+
+// words of one member in the pinned results (a multiple of 4: the 8-byte indices lead each member's words)
+static size_t ens_topk_words(size_t B, size_t k) { return (B * (3 * k + 2) + 3) / 4 * 4; }
+
+// the row stride of the LDS lists in keys: odd, so that the lists of the eight rows whose groups share a wavefront start
+// on eight different bank pairs (the groups' lanes 0 insert at the same time, at about the same place of their lists)
+__host__ __device__ constexpr int ens_topk_stride(int k) { return k | 1; }
+
+// vsom_bmu_topk_batch (MASKED: vsom_bmu_topk_masked_batch without blend) for rows [64x, 64x + 64) of member y.  The model
+// rows in LDS as in ensemble_bmu_many_kernel; the 32 eight-lane groups each own rows g and g + 32 of the tile and walk
+// that row's nodes in index order: every (row, node) distance by vsom_group_dist<CLR> (MASKED: masked_group_dist, nodes
+// n > 0 with bmuHits[n] < min_hits left out), and lane 0 of the group keeps the row's sorted list of its k smallest keys
+// vsom_key(d, n) in LDS -- a key that beats the list's last (or finds the list short) is inserted by shifting.  One lane
+// owns a list from start to end, keys are unique and arrive in index order: no atomics, no second pass, one result.  The
+// node-0 rule (Som.cpp:291-309): a NaN d_0 is recorded and kept out of the list, which then holds k - 1 keys; the
+// epilogue puts node 0 with 0x7FC00000 in front.  The epilogue, behind one barrier, is one wavefront per row (16 rows
+// each): lane j stores entry j (idx, dist; UINT64_MAX / 0x7FC00000 behind the row's last real entry) and, MASKED, the
+// wavefront counts the row's valid columns as ensemble_masked_many_kernel does and stores count and nvalid.
+// LDS: 64 lists of (k | 1) keys, 64 counts, 64 flags, the model rows -- independent of N but for the model rows.
+template <int KIND, bool MASKED>
+__global__ __launch_bounds__(256) void ensemble_topk_many_kernel(const EnsTopkDesc *__restrict__ descs)
+{
+    constexpr bool CLR = KIND == VSOM_CLR;
+    static_assert(!(CLR && MASKED), "the masked residual does not run over CLR's column pairs");
+    const EnsTopkDesc a = descs[blockIdx.y];
+    const int s0 = blockIdx.x * ENS_SCORE_ROWS;
+    if (s0 >= a.B)
+        return;                                          // (workgroup-uniform)
+    const int T = a.B - s0 < ENS_SCORE_ROWS ? a.B - s0 : ENS_SCORE_ROWS, N = a.N, L = a.d.L, K = a.k;
+    const int LS = ens_topk_stride(K);
+    extern __shared__ __attribute__((aligned(16))) unsigned char ens_tk_smem[];
+    u64 *lists = reinterpret_cast<u64 *>(ens_tk_smem);            // [64][LS]
+    int *cnts = reinterpret_cast<int *>(lists + ENS_SCORE_ROWS * LS);   // [64] keys in the row's list
+    int *nan0 = cnts + ENS_SCORE_ROWS;                            // [64]
+    float *ml = reinterpret_cast<float *>(nan0 + ENS_SCORE_ROWS); // N rows of L values (CLR: A part, then B part)
+    const int tid = threadIdx.x;
+    const int rl = CLR ? 2 * L : L;
+    for (int i = tid; i < N * rl; i += 256) {
+        const int n = i / rl, e = i - n * rl;
+        ml[i] = e < L ? a.d.ma[(size_t)n * a.d.ldm + e] : a.d.mb[(size_t)n * a.d.ldm + e - L];
+    }
+    __syncthreads();
+    const float *ma = ml, *mb = CLR ? ml + L : ml;
+    const int grp = tid >> 3, k = tid & 7;
+    for (int s = grp; s < T; s += 32) {                  // (group-uniform)
+        u64 *list = lists + s * LS;
+        const size_t row = (size_t)(s0 + s) * a.d.ldx;
+        // lane 0's record of the list: its length, its capacity (k, or k - 1 behind a NaN node 0), its last key once full
+        int cnt = 0, cap = K, first_nan = 0;
+        u64 last = 0;
+        for (int n = 0; n < N; ++n) {
+            float dd;
+            if constexpr (MASKED) {
+                // findRestrictedBmu (Som.cpp:316-322): node 0 seeds unconditionally, the others need the hits
+                if (n > 0 && a.min_hits && a.hits[n] < a.min_hits)
+                    continue;
+                dd = masked_group_dist(a.d.xa + row, a.valid + (size_t)(s0 + s) * a.vstride, ml + (size_t)n * L, L, k);
+            } else {
+                dd = vsom_group_dist<CLR>(a.d.xa + row, a.d.xb + row, ma + (size_t)n * rl, mb + (size_t)n * rl, L, k);
+            }
+            if (k != 0)
+                continue;
+            if (n == 0 && dd != dd) {
+                first_nan = 1;
+                cap = K - 1;
+                continue;
+            }
+            const u64 key = vsom_key(dd, (uint32_t)n);
+            int j;                                       // the place that opens: behind a short list, or its last key's
+            if (cnt < cap)
+                j = cnt++;
+            else if (cap > 0 && key < last)
+                j = cap - 1;
+            else
+                continue;
+            for (; j > 0; --j) {
+                const u64 prev = list[j - 1];
+                if (prev < key)
+                    break;
+                list[j] = prev;
+            }
+            list[j] = key;
+            if (cnt == cap)
+                last = list[cap - 1];
+        }
+        if (k == 0) {
+            cnts[s] = cnt;
+            nan0[s] = first_nan;
+        }
+    }
+    __syncthreads();
+    // the rows' epilogue: wavefront w takes rows w, w + 4, ...; lane j stores entry j
+    const int lane = tid & 63;
+    const size_t R = (size_t)a.B;
+    u64 *oidx = reinterpret_cast<u64 *>(a.out);
+    unsigned *odist = a.out + 2 * R * K, *ocount = odist + R * K, *onvalid = ocount + R;
+    for (int s = tid >> 6; s < T; s += 4) {
+        const size_t i = (size_t)(s0 + s);
+        const int pinned = nan0[s], cnt = cnts[s];
+        if (lane < K) {
+            u64 idx = ~0ull;
+            unsigned bits = 0x7FC00000u;
+            const int e = lane - pinned;
+            if (e < 0) {
+                idx = 0ull;                              // node 0 with the quiet NaN
+            } else if (e < cnt) {
+                const u64 key = lists[s * LS + e];
+                idx = key & 0xFFFFFFFFull;
+                const unsigned b = (unsigned)(key >> 32);
+                bits = b == 0xFFFFFFFFu ? 0x7FC00000u : b;
+            }
+            oidx[i * K + lane] = idx;
+            odist[i * K + lane] = bits;
+        }
+        if constexpr (MASKED) {
+            const unsigned char *vr = a.valid + i * (size_t)a.vstride;
+            unsigned nv = 0;
+            for (int d = lane; d < L; d += 64)
+                nv += vr[d] != 0 ? 1u : 0u;
+#pragma unroll
+            for (int m = 32; m >= 1; m >>= 1)
+                nv += __shfl_xor(nv, m);
+            if (lane == 0) {
+                ocount[i] = (unsigned)(pinned + cnt);
+                onvalid[i] = nv;
+            }
+        }
+    }
+}
+
+// the LDS need of a member in ensemble_topk_many_kernel
+static size_t ens_topk_smem(const vsom_ctx *c, uint32_t k)
+{
+    const size_t rl = c->transform == VSOM_CLR ? 2 * c->part_len : c->part_len;
+    return ENS_SCORE_ROWS * ((size_t)ens_topk_stride((int)k) * sizeof(u64) + 2 * sizeof(int)) + (size_t)c->N * rl * sizeof(float);
+}
+
+// the fast-path rule (include/vsom_hip.h): would this member with this k run in ensemble_topk_many_kernel?
+static bool ens_topk_fast(const vsom_ensemble *e, const vsom_ctx *c, uint32_t k, bool masked)
+{
+    if (c->cu || (masked && c->transform == VSOM_CLR) || !c->chunk_loaded || c->B == 0)
+        return false;
+    if (k == 0 || k > 64 || k > c->N || (size_t)c->N * c->part_len > 4096)
+        return false;
+    return ens_topk_smem(c, k) <= std::min(e->lds_limit, (size_t)64 << 10);   // (no attribute is raised)
+}
+
+int vsom_ensemble_topk_applies(const vsom_ensemble *e, size_t member, uint32_t k, int masked)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    if (member >= e->m.size())
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: member index out of range");
+    return ens_topk_fast(e, e->m[member], k, masked != 0) ? 1 : 0;
+}
+
+// Both top-k calls (the callers have made their argument checks); valid_host null: the plain call, whose covered members
+// are those with an idx.  The covered members on the fast path go as one launch per kind, the masked ones' validity bytes
+// as one pinned image in the launch's descriptor slot, copied once; every other covered member with rows runs its single
+// call while the launches run.
+static int ens_topk(vsom_ensemble *e, const uint32_t *k, const uint64_t *min_hits, const uint8_t *const *valid_host,
+                    const int *one_mask, const vsom_ensemble_topk_out *out)
+{
+    const bool masked = valid_host != nullptr;
+    const size_t n = e->m.size();
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    EnsCall call(e);
+    std::vector<size_t> asked(n);
+    for (size_t m = 0; m < n; ++m)
+        asked[m] = masked ? valid_host[m] != nullptr : out[m].idx != nullptr;   // (a skipped member is not touched)
+    if (int rc = join_members(e, asked.data(), true))
+        return rc;
+    ens_scratch(e, sizeof(EnsTopkDesc));
+    std::vector<size_t> v_at(n, 0), vbytes(n, 0), w_at(n, 0);
+    size_t vtotal = 0, wtotal = 0;
+    for (size_t m = 0; m < n; ++m) {
+        const vsom_ctx *c = e->m[m];
+        if (!asked[m] || !ens_topk_fast(e, c, k[m], masked))
+            continue;
+        e->grp[m] = c->transform;
+        e->smem[m] = ens_topk_smem(c, k[m]);
+        e->ext[m] = (unsigned)((c->B + ENS_SCORE_ROWS - 1) / ENS_SCORE_ROWS);
+        if (masked) {
+            vbytes[m] = ((one_mask && one_mask[m]) ? 1 : c->B) * (size_t)c->J;
+            v_at[m] = vtotal;
+            vtotal += (vbytes[m] + 15) / 16 * 16;
+        }
+        w_at[m] = wtotal;
+        wtotal += ens_topk_words(c->B, k[m]);
+    }
+    int rc = VSOM_OK;
+    if (wtotal) {
+        if (int jrc = call.join(ENS_LAUNCHED))
+            return jrc;
+        // the slot ens_launch is about to take: its last launch has completed, so its image may be rewritten
+        auto &s = e->slot[e->next];
+        if (s.valid)
+            VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
+        if (masked)
+            VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(s.img_host, vtotal), vsom_member(s.img_dev, vtotal)}));
+        // (no kernel of an earlier call is running: every call ends in a wait)
+        VSOM_ALLOC_CHECK(vsom_grow(e->mq_rows, wtotal, nullptr));
+        if (masked) {
+            for (size_t m = 0; m < n; ++m)
+                if (e->grp[m] >= 0)
+                    std::memcpy(s.img_host.p + v_at[m], valid_host[m], vbytes[m]);
+            VSOM_HIP_CHECK(hipMemcpyAsync(s.img_dev.p, s.img_host.p, vtotal, hipMemcpyHostToDevice, call.ls));
+        }
+        for (size_t m = 0; m < n; ++m) {
+            if (e->grp[m] < 0)
+                continue;
+            const vsom_ctx *c = e->m[m];
+            const bool clr = c->transform == VSOM_CLR;
+            EnsTopkDesc a;
+            a.d.xa = clr ? c->XP.p : c->Xs.p;
+            a.d.xb = clr ? c->YP.p : c->Xs.p;
+            a.d.ldx = (int)(clr ? c->part_pitch : c->xpitch);
+            a.d.ma = c->map.p;
+            a.d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
+            a.d.ldm = (int)c->pitch;
+            a.d.L = (int)c->part_len;
+            a.hits = c->hits.p;
+            a.min_hits = masked && min_hits ? min_hits[m] : 0;
+            a.valid = masked ? s.img_dev.p + v_at[m] : nullptr;
+            a.out = e->mq_rows.p + w_at[m];
+            a.vstride = (one_mask && one_mask[m]) ? 0 : (int)c->J;
+            a.B = (int)c->B;
+            a.N = (int)c->N;
+            a.k = (int)k[m];
+            std::memcpy(e->desc.data() + m * sizeof(a), &a, sizeof(a));
+        }
+        static void (*const kernel[2][3])(const EnsTopkDesc *) = {
+            {ensemble_topk_many_kernel<VSOM_STANDARD, false>, ensemble_topk_many_kernel<VSOM_MEDIAN, false>,
+             ensemble_topk_many_kernel<VSOM_CLR, false>},
+            {ensemble_topk_many_kernel<VSOM_STANDARD, true>, ensemble_topk_many_kernel<VSOM_MEDIAN, true>, nullptr}};
+        rc = ens_launch(call, ENS_JOINED, 3, sizeof(EnsTopkDesc), ENS_MAX_Y, ens_always_ready,
+                        [masked](int kind, const void *d, unsigned cnt, size_t smem, unsigned tiles, hipStream_t st) -> int {
+                            hipLaunchKernelGGL(kernel[masked][kind], dim3(tiles, cnt), dim3(256), smem, st,
+                                               static_cast<const EnsTopkDesc *>(d));
+                            VSOM_HIP_CHECK_AS(hipGetLastError(), "ensemble_topk_many_kernel");
+                            return VSOM_OK;
+                        });
+    }
+    // the other members through their single calls, while the launches run
+    for (size_t m = 0; m < n && !rc; ++m) {
+        vsom_ctx *c = e->m[m];
+        if (!asked[m] || c->B == 0 || e->grp[m] >= 0)
+            continue;
+        if (masked) {
+            const vsom_topk_masked_out o = {out[m].idx, out[m].dist, out[m].count, out[m].nvalid, nullptr};
+            rc = launch_topk_masked(c, k[m], min_hits ? min_hits[m] : 0, 0, c->B, valid_host[m], one_mask ? one_mask[m] : 0, &o);
+        } else {
+            rc = launch_topk(c, k[m], 0, c->B, out[m].idx, out[m].dist);
+        }
+    }
+    if ((rc = call.end(rc)))
+        return rc;
+    // results of the launched members: the kernel stored them into the pinned buffer
+    for (size_t m = 0; m < n; ++m) {
+        if (e->grp[m] < 0)
+            continue;
+        const size_t b = e->m[m]->B, bk = b * k[m];
+        const unsigned *p = e->mq_rows.p + w_at[m];
+        std::memcpy(out[m].idx, p, bk * sizeof(uint64_t));
+        if (out[m].dist)
+            std::memcpy(out[m].dist, p + 2 * bk, bk * sizeof(float));
+        if (masked && out[m].count)
+            std::memcpy(out[m].count, p + 3 * bk, b * sizeof(uint32_t));
+        if (masked && out[m].nvalid)
+            std::memcpy(out[m].nvalid, p + 3 * bk + b, b * sizeof(uint32_t));
+    }
+    return VSOM_OK;
+}
+
+// what both top-k calls check for a covered member, behind the call's own arrays: the member, then its k
+static int ens_topk_member(const vsom_ensemble *e, size_t m, const char *what, bool masked, uint32_t k, std::string &buf)
+{
+    const vsom_ctx *c = e->m[m];
+    if (masked) {
+        if (const char *why = ens_masked_query_refusal(c, what, buf))
+            return ens_fail(m, why);
+    } else {
+        if (c->cu) {
+            buf = std::string(what) + ": custom contexts are not supported";
+            return ens_fail(m, buf.c_str());
+        }
+        if (const char *why = ens_rows_refusal(c))
+            return ens_fail(m, why);
+    }
+    if (k == 0 || k > 64 || k > c->N)
+        return ens_fail(m, "k must be in [1, min(64, N)]");
+    return VSOM_OK;
+}
+
+int vsom_ensemble_bmu_topk_batch(vsom_ensemble *e, const uint32_t *k, const vsom_ensemble_topk_out *out)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    if (!k)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null k array");
+    if (!out)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null out array");
+    std::string buf;
+    for (size_t m = 0; m < e->m.size(); ++m)
+        if (out[m].idx)
+            if (int rc = ens_topk_member(e, m, "vsom_bmu_topk_batch", false, k[m], buf))
+                return rc;
+    return ens_topk(e, k, nullptr, nullptr, nullptr, out);
+}
+
+int vsom_ensemble_bmu_topk_masked_batch(vsom_ensemble *e, const uint32_t *k, const uint64_t *min_hits,
+                                        const uint8_t *const *valid_host, const int *one_mask,
+                                        const vsom_ensemble_topk_out *out)
+{
+    if (int rc = ens_masked_query_arrays(e, valid_host, out))
+        return rc;
+    if (!k)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null k array");
+    std::string buf;
+    for (size_t m = 0; m < e->m.size(); ++m) {
+        if (!valid_host[m])
+            continue;
+        if (int rc = ens_topk_member(e, m, "vsom_bmu_topk_masked_batch", true, k[m], buf))
+            return rc;
+        if (!out[m].idx)
+            return ens_fail(m, "out->idx is null");
+    }
+    return ens_topk(e, k, min_hits, valid_host, one_mask, out);
 }
 
 // Som::updateUMatrix of every member (vsom_umatrix.hip): members whose model and sigma rows fit LDS in one launch per kind
