@@ -73,6 +73,17 @@ one, synchronised after each: what an ensemble call returns must equal the twins
 gives a member another answer than a context that never joined (vsom_train_online_chunk_masked, vsom_batch_accum_begin), the
 model says so: the member must refuse.  The walk's first no-wait run goes to the ensemble back to back before twins and model
 see it; the pinned rows of a wait = 0 upload are overwritten once a call that synchronises every member has returned.
+
+A fifth profile, "ensemble_query" (generate_ensemble_query, the last section of this file), walks the four ensemble calls
+that return results through state shared across calls -- vsom_ensemble_bmu_masked_batch, _similarity_masked_batch,
+_bmu_topk_batch, _bmu_topk_masked_batch, with vsom_ensemble_topk_applies -- between the ensemble profile's calls, and adds
+the single-context vsom_similarity_masked_batch, vsom_bmu_topk_batch, vsom_bmu_topk_masked_batch, vsom_bmd_masked_batch and
+vsom_generate_masked_batch on members.  Its members and configurations stand beside the ensemble profile's (ENSQ_MEMBERS,
+ENSQ_CONFIGS), its path predicates beside batch_tiny (masked_query_fast, topk_fast).  run_ensemble_walk serves it: a query
+changes nothing, so the model has nothing to apply; EnsModel.query computes what every covered member must return from the
+member's oracle state and the plain references (masked_score_ref, topk_masked_ref), every row of the small members and a
+seeded sample of the large ones; the real backend gives every output array a canary and a guard and holds every row to the
+member's twin.  ensq_conditions asserts that a walk was not vacuous.
 """
 import copy
 import ctypes as C
@@ -146,9 +157,31 @@ ENS_CONFIGS = {
 }
 
 
+# ---- the ensemble_query profile: two more members and two configurations of their own (generate_ensemble_query) ----
+ENSQ_MEMBERS = {
+    # (the many-member query kernels take one workgroup per (member, 64 rows): every row count is at a tile border;
+    # exact_rows: chunk_data gives these members the rows they name, a chunk of one row included)
+    "Q": dict(W=10, H=10, J=9, tr=po.STANDARD, custom=False, map_seed=200, exact_rows=True,
+              chunks=[(1, "dense"), (63, "dense"), (64, "dense"), (65, "dense"), (128, "dense"), (129, "dense")]),
+    # (N * D = 4104: the first size beyond the fast path's N * D <= 4096, beside D's 4096)
+    "D2": dict(W=4, H=2, J=513, tr=po.MEDIAN, custom=False, exact_rows=True, chunks=[(3, "dense"), (64, "dense")]),
+}
+ENSQ_CONFIGS = {
+    "ensq_shared": dict(members=["A", "A2", "B", "C", "D", "D2", "Q", "E"], one_stream=True),
+    "ensq_own": dict(members=["A", "B", "C", "D", "D2", "Q", "F", "G"], one_stream=False),
+}
+
+
 def config(name):
     """a configuration of the single-context profiles, or an ensemble member"""
-    return CONFIGS[name] if name in CONFIGS else ENS_MEMBERS[name]
+    if name in CONFIGS:
+        return CONFIGS[name]
+    return ENS_MEMBERS[name] if name in ENS_MEMBERS else ENSQ_MEMBERS[name]
+
+
+def ens_config(name):
+    """an ensemble configuration of the ensemble or the ensemble_query profile"""
+    return ENS_CONFIGS[name] if name in ENS_CONFIGS else ENSQ_CONFIGS[name]
 
 
 # ops that read the staged rows of the current chunk: the ones a pending chunk staged ahead may refuse
@@ -201,7 +234,7 @@ def chunk_data(cfg_name, seed, scale=1, profile="ingest"):
     cfg = config(cfg_name)
     out = []
     for i, (b, kind) in enumerate(chunk_list(cfg, profile)):
-        b = max(8, b // scale)
+        b = b if cfg.get("exact_rows") else max(8, b // scale)
         s = 1000 * seed + 17 * i + 3
         if kind == "u8":
             x = gen.mnist_like(b, seed=s, dim=cfg["J"])
@@ -920,6 +953,8 @@ class Refused(Exception):
 
 def _rand_state(cfg_name, seed, parts, N, D):
     rs = np.random.RandomState(seed)
+    if parts == "hits0":                   # (the ensemble_query profile: only node 0 is a candidate under min_hits >= 1)
+        return {"hits": np.zeros(N, np.uint64)}
     if parts == "weight_only":
         return {"weight": (rs.rand(N) * 10 + 0.5).astype(np.float32)}
     st = {"map": initial_map(cfg_name, seed)}      # ("map", "map_only": the map alone)
@@ -958,6 +993,12 @@ def materialize(op, model):
             valid = (rs.rand(*Xw.shape) < 0.8) & np.isfinite(Xw)
         binary = (rs.rand(cfg["J"]) < 0.3).astype(np.float32)
         return {"valid": valid.astype(np.uint8), "binary": binary, "continuous": (1 - binary).astype(np.float32)}
+    if name in ("topk_masked", "bmd_masked", "generate_masked"):       # (the ensemble_query profile's member ops)
+        rs = np.random.RandomState(p["seed"])
+        n, J, draws = p["r1"] - p["r0"], cfg["J"], p.get("draws", 1)
+        valid = (rs.rand(J) < 0.7) if p["form"] == "one_mask" else (rs.rand(n, J) < 0.8)
+        return {"valid": valid.astype(np.uint8), "u": rs.rand(n) if name == "bmd_masked" else rs.rand(n, draws),
+                "l": 0.05 + 0.9 * rs.rand(n, draws, J)}
     if name == "single":
         rs = np.random.RandomState(p["seed"])
         X = model.chunks[rs.randint(len(model.chunks))]
@@ -1668,7 +1709,8 @@ class GpuBackend:
         name, p = op
         out = {}
         B = int(L.vsom_chunk_size(h))
-        if name in ("similarity", "generate", "evaluate", "topk", "bmd", "bmu_masked") or name in MASKED_SCORES:
+        if name in ("similarity", "generate", "evaluate", "topk", "bmd", "bmu_masked", "topk_masked", "bmd_masked",
+                    "generate_masked") or name in MASKED_SCORES:
             w = dict(r0=p["r0"], r1=p["r1"])
         if "poisoned" in p:                    # (one entry, under the chunk's index)
             pinned = {p["chunk"]: self.pinned_poisoned[self._key(p)]}
@@ -1752,6 +1794,12 @@ class GpuBackend:
             rc, out = self._wrapped(ctx.restricted_bmd, p["min_hits"], u=a["u"], **w)
         elif name == "bmu_masked":
             rc, out = self._wrapped(ctx.bmu_masked, a["valid"], min_hits=p["min_hits"], fill=True, **w)
+        elif name == "topk_masked":
+            rc, out = self._wrapped(ctx.bmu_topk_masked, p["k"], a["valid"], min_hits=p["min_hits"], blend=p["blend"], **w)
+        elif name == "bmd_masked":
+            rc, out = self._wrapped(ctx.restricted_bmd_masked, a["valid"], p["min_hits"], u=a["u"], probs=True, **w)
+        elif name == "generate_masked":
+            rc, out = self._wrapped(ctx.generate_masked, a["valid"], p["min_hits"], a["u"], a["l"], draws=p["draws"], **w)
         elif name == "upload":
             X = a["X"]
             if p["asynchronous"] and not twin:
@@ -1867,7 +1915,7 @@ class GpuBackend:
 
 def replay(ops):
     """rerun a printed op list against the real library"""
-    if ops[0][1].get("profile") == "ensemble":
+    if ops[0][1].get("profile") in ("ensemble", "ensemble_query"):
         return run_ensemble_walk(ops, EnsGpuBackend)
     return run_walk(ops, GpuBackend)
 
@@ -1934,10 +1982,10 @@ def _nan(v):
 
 class _EnsGen:
     def __init__(self, cfg_name, seed):
-        self.ec = ENS_CONFIGS[cfg_name]
+        self.ec = ens_config(cfg_name)
         self.all = list(self.ec["members"])
         self.rs = np.random.RandomState(seed)
-        self.sizes = {n: [b for b, _ in ENS_MEMBERS[n]["chunks"]] for n in self.all}
+        self.sizes = {n: [b for b, _ in config(n)["chunks"]] for n in self.all}
         self.B = {n: None for n in self.all}
         self.chain = {n: False for n in self.all}
         self.ens = {}
@@ -2047,7 +2095,7 @@ class _EnsGen:
     # ---- random draws ----
     def member_op(self):
         n = self.all[self.r(len(self.all))]
-        cfg = ENS_MEMBERS[n]
+        cfg = config(n)
         plain = not cfg["custom"] and cfg["tr"] != po.CLR
         what = ["upload", "prefetch", "set_state", "get_state", "set_last_bmu", "get_last_bmu", "get_sqres", "get_mse",
                 "epoch", "online", "bmu", "bmu_masked", "um", "bmu_mode", "schedule", "schedule_masked"][self.r(16)]
@@ -2342,7 +2390,7 @@ class EnsModel:
 
     def __init__(self, cfg_name, seed):
         self.cfg_name = cfg_name
-        self.names = list(ENS_CONFIGS[cfg_name]["members"])
+        self.names = list(ens_config(cfg_name)["members"])
         self.m = {n: Model(n, seed, 1, "ensemble") for n in self.names}
         for mod in self.m.values():
             mod.bmu_mode = BMU_AUTO
@@ -2364,6 +2412,8 @@ class EnsModel:
             if "share" in s:
                 continue
             x = self.m[n].chunks[s["chunk"]]
+            if "head" in s:                  # (the ensemble_query profile: the chunk's first rows, none of them: B = 0)
+                x = x[:s["head"]]
             if n in p.get("poison", {}):
                 x = ens_poisoned(p["poison"][n], x)
             X[n], off[n] = x, at
@@ -2396,6 +2446,8 @@ class EnsModel:
         mod = self.m[n]
         cfg, B = mod.cfg, mod.B
         masked = n in p.get("masks", {})
+        if name in ("ens_topk", "ens_topk_masked"):
+            return topk_fast(cfg, B, p["k"][k], name == "ens_topk_masked")
         if name in ("ens_epoch", "ens_epoch_masked"):
             return masked_batch_tiny(cfg, B, mod.update_mode == UPDATE_STRICT) if masked else batch_tiny(cfg, B)
         if name in ("ens_schedule", "ens_schedule_masked"):
@@ -2471,7 +2523,62 @@ class EnsModel:
         mod = self.m[n]
         if op[0] == "bmu_mode":
             mod.bmu_mode = op[1]["mode"]
+        if op[0] in MEMBER_QUERIES and mod.profile == "ensemble":    # read-only: the window's rows from the plain references
+            return member_query(mod, op, a)
         return mod.apply(op, a)
+
+    # ---- the four query calls of the ensemble_query profile (read-only: apply() has nothing to do for them) ----
+    def ensq_refusal(self, op):
+        """None where the header accepts the query call, else (member index or None, words of the message, the entry of
+        ENSQ_REFUSALS), in the order csrc/vsom_ensemble.hip checks: the call's arrays, then member by member the context,
+        its chunk, its k, its idx pointer.  A chunk staged ahead is the backend's to know (must_refuse)."""
+        name, p = op
+        bad = p.get("bad")
+        order = self.ens[p["e"]]
+        masked = name != "ens_topk"
+        arrays = (["null_valid", "null_out"] if masked else ["null_k", "null_out"]) + \
+            {"ens_similarity_masked": ["null_num_sigmas", "bad_rule"], "ens_topk_masked": ["null_k"]}.get(name, [])
+        words = {"null_valid": "null valid_host array", "null_out": "null out array", "null_k": "null k array",
+                 "null_num_sigmas": "null num_sigmas array", "bad_rule": "unknown sigma_rule"}
+        if bad in arrays:
+            return None, words[bad], bad
+        cov = covered(op, order)
+        for k, n in enumerate(order):
+            if n not in cov:
+                continue
+            mod = self.m[n]
+            if mod.cfg["custom"]:
+                return k, "custom contexts are not supported", "custom"
+            if masked and mod.cfg["tr"] == po.CLR:
+                return k, "CLR contexts are not supported", "clr"
+            if mod.X is None:
+                return k, "no chunk loaded", "no_chunk"
+            if "k" in p and not 1 <= p["k"][k] <= min(64, mod.N):
+                return k, "k must be in [1, min(64, N)]", f"k{p['k'][k]}"
+            if bad == "null_idx" and n == p["null_idx"]:
+                return k, "out->idx is null", "null_idx"
+        return None
+
+    def query_fast(self, op, n, k):
+        """whether member n (index k) of an accepted query call runs in the many-member kernel, by the restated predicates"""
+        if op[0] in ("ens_topk", "ens_topk_masked"):
+            return self.path(op, n, k)
+        return masked_query_fast(self.m[n].cfg, self.m[n].B)
+
+    def query(self, op, a, hits=None, sigma=None):
+        """{member: (rows, {output: expected values of those rows})} of an accepted query call, every covered member with
+        rows; hits / sigma: {member: array} taken for the member's own (the CPU fake's mutants)"""
+        name, p = op
+        order = self.ens[p["e"]]
+        res = {}
+        for n in covered(op, order):
+            mod, k = self.m[n], order.index(n)
+            if mod.B == 0:
+                continue
+            valid = a.get("valid", {}).get(n)
+            rows = model_rows(mod, valid, p, k)
+            res[n] = (rows, query_member(mod, name, p, k, valid, rows, (hits or {}).get(n), (sigma or {}).get(n)))
+        return res
 
     def apply(self, op, a):
         """an accepted ensemble call: the single call on every member in index order; outputs keyed "<member>.<name>" """
@@ -2526,8 +2633,46 @@ def ens_conditions(cfg_name, stats, gpu=False):
         assert stats["nowait"] >= 2 and stats["applies"] >= 10, stats
 
 
+class Within:
+    """An expected array of a member op whose arithmetic is not restated bit for bit (the device's double exp and log): `ref`
+    and a bound per element -- 0: the element bit for bit (NaN equal to NaN), inf: not compared (a draw within
+    bmd_masked_ref.NEAR of a cumulative boundary, and what hangs on it), else |got - ref| <= bound."""
+
+    def __init__(self, ref, bound):
+        self.ref = np.asarray(ref)
+        self.bound = np.broadcast_to(np.asarray(bound, np.float64), self.ref.shape)
+
+    def difference(self, got):
+        if got is None:
+            return "got nothing"
+        g, e, b = np.asarray(got), self.ref, self.bound
+        if g.shape != e.shape or g.dtype != e.dtype:
+            return f"shape / type {g.shape} {g.dtype} != {e.shape} {e.dtype}"
+        exact = b == 0
+        if e.dtype.kind == "f":
+            with np.errstate(all="ignore"):
+                exact = exact | ~np.isfinite(e)          # (an infinite or NaN reference value: the same value)
+                near = (np.abs(g - e) <= b) | (g == e)   # (a NaN bound -- a NaN in the row's units -- asks for the same value)
+            same = np.where(exact, (g == e) & (np.signbit(g) == np.signbit(e)) | (np.isnan(g) & np.isnan(e)), near)
+        else:
+            same = g == e
+        same = same | np.isinf(b)
+        if same.all():
+            return None
+        at = np.unravel_index(int(np.argmin(same.reshape(-1))), same.shape)
+        return (f"element {tuple(int(i) for i in at)}: got {g[at]!r}, expected {e[at]!r} within {b[at]!r} "
+                f"({int((~same).sum())} differ)")
+
+
+def plain(out):
+    """a model's outputs as a library would return them: the reference values of the bounded ones"""
+    return {k: (v.ref.copy() if isinstance(v, Within) else v) for k, v in out.items()}
+
+
 def ens_difference(got, exp):
     """first_difference on the values' own width: the U-matrix is a double"""
+    if isinstance(exp, Within):
+        return exp.difference(got)
     if exp is not None and np.asarray(exp).dtype == np.float64 and np.asarray(exp).ndim:
         return first_difference_exact(np.asarray(got, np.float64), np.asarray(exp))
     return first_difference(got, exp)
@@ -2539,12 +2684,12 @@ def run_ensemble_walk(ops, make_backend):
     call the calls with at least two launched members and one on its ordinary path, the refusals of run 5 by entry, the
     stage-ahead refusals, the wait = 0 uploads followed by a call with no host wait between."""
     name0, cfg = ops[0]
-    assert name0 == "config" and cfg["profile"] == "ensemble", ops[0]
+    assert name0 == "config" and cfg["profile"] in ("ensemble", "ensemble_query"), ops[0]
     em = EnsModel(cfg["name"], cfg["seed"])
     em.ops = ops
     be = make_backend(cfg["name"], em)
     stats = {"ops": 0, "accepted": {c: 0 for c in ENS_CALLS}, "mixed": {c: 0 for c in ENS_TRAIN}, "refusals": {},
-             "staged": 0, "nowait": 0, "applies": 0}
+             "staged": 0, "nowait": 0, "applies": 0, "q": ensq_stats()}
     done = [ops[0]]
 
     def fail(msg):
@@ -2577,6 +2722,8 @@ def run_ensemble_walk(ops, make_backend):
         stats["ops"] += 1
         if out.get("twin_diff"):
             fail(f"{name}: {out['twin_diff']}")
+        if name in ENSQ_CALLS:
+            return check_query(op, a, rc, msg, out)
         if name == "sigma_stats":
             if rc != 0 or [int(v) for v in out["stats"]] != list(p["expect"]):
                 fail(f"vsom_sigma_stats of member {p['k']} = {out.get('stats')}, the header's contract gives {p['expect']} "
@@ -2624,6 +2771,62 @@ def run_ensemble_walk(ops, make_backend):
             stats["mixed"][name] += fast >= 2 and len(touched) - fast >= 1
         stats["accepted"][name] += 1
         check_outputs(name, out, em.apply(op, a))
+
+    def check_query(op, a, rc, msg, out):
+        """one of the four query calls of the ensemble_query profile: the library's fast-path predicate, the refusal the
+        header lists, the arrays that must stay as they were, every covered member's outputs against the model"""
+        name, p = op
+        q = stats["q"]
+        order = em.ens[p["e"]]
+        cov = covered(op, order)
+        for n, v in out.pop("applies", {}).items():
+            k = order.index(n)
+            q["applies"] += 1
+            if int(v) != int(em.path(op, n, k)):
+                fail(f"{name}: member {k} ({n}, {em.m[n].B} rows, k = {p['k'][k]}): vsom_ensemble_topk_applies says {v}, the "
+                     f"restated predicate topk_fast {em.path(op, n, k)}")
+        rows_of = {n: em.m[n].B for n in order}
+        why = em.ensq_refusal(op)
+        if why is None and "must_refuse" in p:
+            why = (order.index(p["must_refuse"]), "vsom_commit_chunk first", "staged")
+        if why is not None:
+            wrote = sorted(k for k in out if "." in k)
+            if wrote:
+                fail(f"{name} returned {rc} and wrote {wrote}: the header refuses it ({why[1]}), and a refused call writes nothing")
+            return refusal(name, rc, msg, why[0], why[1], "q_" + why[2])
+        if rc != 0:
+            fail(f"{name} failed: {rc} {msg}")
+        for key in sorted(out):
+            n = key.split(".")[0]
+            if "." in key and (n not in cov or rows_of[n] == 0):
+                fail(f"{name}: output {key!r} of member {order.index(n)} was written (element 0: "
+                     f"{np.asarray(out[key]).reshape(-1)[:1].tolist()}): the member is "
+                     f"{'skipped' if n not in cov else 'without rows'} and its arrays must keep what they held")
+        fast = [n for n in cov if rows_of[n] and em.query_fast(op, n, order.index(n))]
+        slow = [n for n in cov if rows_of[n] and n not in fast]
+        q["accepted"][name] += 1
+        q["mixed"][name] += len(fast) >= 2 and len(slow) >= 1 and len(cov) < len(order)
+        q["b0"] += sum(rows_of[n] == 0 for n in cov)
+        q["ahead_skipped"] += bool(p.get("ahead_skipped"))
+        for label in p.get("labels", ()):
+            q["met"][label] = q["met"].get(label, 0) + 1
+        for n, (rows, exp) in em.query(op, a).items():
+            q["covered_rows"][n] = q["covered_rows"].get(n, 0) + rows_of[n]
+            q["model_rows"][n] = q["model_rows"].get(n, 0) + len(rows)
+            if "count" in exp:
+                q["padded"] += int((exp["count"] < p["k"][order.index(n)]).sum())
+            q["novalid"] += int((exp["nvalid"] == 0).sum()) if "nvalid" in exp else 0
+            for key, e in exp.items():
+                got = out.get(f"{n}.{key}")
+                if got is None:
+                    continue                   # (a NULL output pointer)
+                got = np.asarray(got)
+                if got.shape[:1] != (rows_of[n],):
+                    fail(f"{name}: output {n}.{key} returned {got.shape} values for {rows_of[n]} rows")
+                d = query_difference(got[rows], e, key)
+                if d:
+                    fail(f"{name}: output {n}.{key} (member {order.index(n)}, rows {rows[:8].tolist()}...) differs from "
+                         f"the model at {d}")
 
     def back_to_back(batch):
         """run 1 on a backend that can separate the ensemble from the twins (call_first / call_twin): every call goes to
@@ -2675,15 +2878,16 @@ class EnsGpuBackend:
 
     def __init__(self, cfg_name, em):
         self.em = em
-        ec = ENS_CONFIGS[cfg_name]
+        ec = ens_config(cfg_name)
         self.gb = {n: GpuBackend(n, em.m[n]) for n in em.names}
         self.capi, self.L, self.hip = self.gb[em.names[0]].capi, self.gb[em.names[0]].L, self.gb[em.names[0]].hip
         self.twin = {n: self.gb[n].make() for n in em.names}
         self.streams = []
+        self.queries = cfg_name in ENSQ_CONFIGS    # the ensemble_query profile: every twin is fixed at VSOM_SIGMA_EAGER
         for i, n in enumerate(em.names):
-            if ENS_MEMBERS[n].get("lazy"):             # (the twin too: it never joins, and may go on deferring)
+            if config(n).get("lazy"):             # (the twin too: it never joins, and may go on deferring)
                 self.gb[n].ctx.set_sigma_mode(SIGMA_LAZY)
-                self.twin[n].set_sigma_mode(SIGMA_LAZY)
+                self.twin[n].set_sigma_mode(SIGMA_EAGER if self.queries else SIGMA_LAZY)
             if not ec["one_stream"] or i == 0:
                 s = C.c_void_p()
                 assert self.hip.hipStreamCreate(C.byref(s)) == 0
@@ -2748,6 +2952,11 @@ class EnsGpuBackend:
         if name == "ens_destroy":
             L.vsom_ensemble_destroy(self.ens.pop(p["e"]))
             return 0, "", {}
+        if name in ENSQ_CALLS:
+            # (a query that skips a member has not synchronised it: the pinned rows of a wait = 0 upload stay as they are
+            # until a call that covers every member has returned, below)
+            rc, out = self._query(self.ens[p["e"]], self.em.ens[p["e"]], op, a)
+            return rc, self._err(rc), out
         rc, out = self._ensemble(self.ens[p["e"]], self.em.ens[p["e"]], op, a)
         msg = self._err(rc)
         if rc == 0 and name in ENS_TRAIN + ("ens_bmu",) and self.in_flight and \
@@ -2838,6 +3047,120 @@ class EnsGpuBackend:
                 v[...] = 0
         return rc, out
 
+    # ---- the four query calls: the C ABI directly, every array behind a canary ----
+    QUERY_ARRAYS = {
+        "ens_bmu_masked": (("bmu", np.uint64, "B"), ("dist", np.float32, "B"), ("nvalid", np.uint32, "B"),
+                           ("fill", np.float32, "BJ")),
+        "ens_similarity_masked": (("bmu", np.uint64, "B"), ("dist", np.float32, "B"), ("dmax", np.float32, "B"),
+                                  ("dmax_col", np.uint32, "B"), ("first", np.float32, "B"), ("amax", np.float32, "B"),
+                                  ("amax_col", np.uint32, "B"), ("outside", np.uint32, "B"), ("delta", np.float32, "BJ"),
+                                  ("nvalid", np.uint32, "B")),
+        "ens_topk": (("idx", np.uint64, "Bk"), ("dist", np.float32, "Bk"), ("count", np.uint32, "B"),
+                     ("nvalid", np.uint32, "B")),
+    }
+    GUARD = 8                                  # elements behind every array that must keep the canary too
+
+    def _query(self, eh, order, op, a):
+        """One query call.  Every output array of every member -- covered, skipped, asked for or not -- is filled with the
+        byte 0xA5 first and has GUARD elements more than its size.  After the call: an array the call was given for a
+        covered member with rows must be overwritten (no element of an index / count array still the canary) and is
+        returned as "<member>.<output>"; every other array, every array of a refused call and every guard must still hold
+        the canary -- one that does not is returned like an output, and the walk reports the write."""
+        name, p = op
+        L, K, bad = self.L, len(order), p.get("bad")
+        u8p = C.POINTER(C.c_uint8)
+        masked = name != "ens_topk"
+        cov = covered(op, order)
+        B = [int(L.vsom_chunk_size(self.gb[n].ctx._h)) for n in order]
+        out = {}
+        ks = p.get("k", [1] * K)
+        if "k" in p and bad != "null_k":       # the library's own predicate for every covered member, and an index past the end
+            out["applies"] = {n: L.vsom_ensemble_topk_applies(eh, order.index(n), ks[order.index(n)], int(masked)) for n in cov}
+            if L.vsom_ensemble_topk_applies(eh, K, 1, int(masked)) != VSOM_ERR_INVALID:
+                out["twin_diff"] = f"vsom_ensemble_topk_applies accepted the member index {K} of {K} members"
+        spec = self.QUERY_ARRAYS["ens_topk" if "k" in p else name]
+        struct = {"ens_bmu_masked": self.capi.MaskedOut, "ens_similarity_masked": self.capi.SimilarityMaskedOut}.get(
+            name, self.capi.EnsembleTopkOut)
+        outs = (struct * K)()
+        arrays = {}
+        for k, n in enumerate(order):
+            J = config(n)["J"]
+            for key, dtype, shape in spec:
+                count = B[k] * {"B": 1, "BJ": J, "Bk": ks[k]}[shape]
+                arr = np.empty(count + self.GUARD, dtype)
+                arr.view(np.uint8)[...] = 0xA5
+                asked = p[key][k] if key in p and isinstance(p[key], list) and key != "k" else True
+                if key in ("count", "nvalid") and name == "ens_topk":
+                    asked = True               # (the plain call ignores them: they must stay as they are)
+                if key == "idx" and ((not masked and n not in cov) or (bad == "null_idx" and n == p["null_idx"])):
+                    asked = False              # (the plain call: a NULL idx is what skips a member)
+                if asked:
+                    setattr(outs[k], key, arr.ctypes.data_as(dict(struct._fields_)[key]))
+                arrays[n, key] = (arr, count, asked, shape)
+        keep = [a["valid"][n].copy() if masked and a["valid"].get(n) is not None else None for n in order]
+        vptr = (u8p * K)(*[u8p() if v is None else v.ctypes.data_as(u8p) for v in keep])
+        ones = (C.c_int * K)(*[0 if v is None else int(v.ndim == 1) for v in keep])
+        mh = (C.c_uint64 * K)(*p.get("min_hits", [0] * K))
+        kp = (C.c_uint32 * K)(*ks)
+        vp = None if bad == "null_valid" else vptr
+        op_ = None if bad == "null_out" else outs
+        if name == "ens_bmu_masked":
+            rc = L.vsom_ensemble_bmu_masked_batch(eh, mh, vp, ones, op_)
+        elif name == "ens_similarity_masked":
+            ns = (C.c_int * K)(*p["num_sigmas"])
+            rc = L.vsom_ensemble_similarity_masked_batch(eh, mh, None if bad == "null_num_sigmas" else ns,
+                                                         7 if bad == "bad_rule" else p["rule"], vp, ones, op_)
+        elif name == "ens_topk":
+            rc = L.vsom_ensemble_bmu_topk_batch(eh, None if bad == "null_k" else kp, op_)
+        else:
+            rc = L.vsom_ensemble_bmu_topk_masked_batch(eh, None if bad == "null_k" else kp, mh, vp, ones, op_)
+        for v in keep:                         # "valid_host is not read after the call returns"
+            if v is not None:
+                v[...] = 0
+        for (n, key), (arr, count, asked, shape) in arrays.items():
+            k = order.index(n)
+            body, guard = arr[:count], arr[count:]
+            clean = lambda x: bool((x.view(np.uint8) == 0xA5).all())
+            if not clean(guard):
+                out["twin_diff"] = f"the {self.GUARD} elements behind output {key!r} of member {k} ({n}) were written"
+            written = rc == 0 and asked and n in cov and B[k] > 0 and not (name == "ens_topk" and key in ("count", "nvalid"))
+            if not written:
+                if not clean(body):
+                    out[f"{n}.{key}"] = body.copy()
+                continue
+            if body.dtype.kind == "u" and (body.view(np.uint8).reshape(count, -1) == 0xA5).all(axis=1).any():
+                out["twin_diff"] = f"output {key!r} of member {k} ({n}) still holds the canary: not every element was written"
+            cols = {"B": (), "BJ": (config(n)["J"],), "Bk": (ks[k],)}[shape]
+            out[f"{n}.{key}"] = body.reshape((B[k],) + cols).copy()
+        return rc, out
+
+    def _query_twins(self, order, op, a, out):
+        """every covered member's share as the single call over [0, B) on its twin, from pageable memory; every row compared
+        on the words (NaN payloads and signs included)"""
+        name, p = op
+        for n in covered(op, order):
+            k, t = order.index(n), self.twin[n]
+            if int(self.L.vsom_chunk_size(t._h)) == 0:
+                continue                       # (the single calls refuse a chunk without rows)
+            valid = a.get("valid", {}).get(n)
+            if name == "ens_bmu_masked":
+                tout = t.bmu_masked(valid, min_hits=p["min_hits"][k], fill=p["fill"][k])
+            elif name == "ens_similarity_masked":
+                tout = t.similarity_masked(valid, p["min_hits"][k], p["num_sigmas"][k], p["rule"], delta=p["delta"][k])
+            elif name == "ens_topk":
+                tout = dict(zip(("idx", "dist"), t.bmu_topk(p["k"][k], dist=p["dist"][k])))
+            else:
+                tout = t.bmu_topk_masked(p["k"][k], valid, min_hits=p["min_hits"][k], dist=p["dist"][k])
+            self.capi.check(self.L.vsom_synchronize(t._h))
+            for key, v in tout.items():
+                got = out.get(f"{n}.{key}")
+                if v is None or got is None:
+                    continue
+                d = first_difference_exact(words(got), words(v))
+                if d:
+                    out["twin_diff"] = f"output {key!r} of member {k} ({n}) differs from its twin's single call at {d}"
+                    return
+
     # ---- the twins ----
     def call_twin(self, op, a, rc, msg, out):
         name, p = op
@@ -2852,6 +3175,8 @@ class EnsGpuBackend:
             if inner[0] == "online_masked" and joined and not self.em.m[n].cfg["custom"] and self.em.m[n].cfg["tr"] != po.CLR:
                 return                         # the member must refuse it; the twin would accept and train
             trc, _, tout = gb._call(t, inner, a, twin=True)
+            if inner[0] == "sigma_mode" and self.queries:
+                t.set_sigma_mode(SIGMA_EAGER)
             if inner[0] == "accum_begin" and joined and rc != 0 and trc == 0:
                 # the header gives the twin, which never joined, another answer: it accepts -- and is put back
                 self.capi.check(self.L.vsom_batch_accum_abort(t._h))
@@ -2859,10 +3184,12 @@ class EnsGpuBackend:
             if trc != rc:
                 out["twin_diff"] = f"{inner[0]} on member {n} returned {rc}, its twin {trc}"
                 return
-            if rc == 0 and inner[0] != "get_state":
-                self._diff(out, tout, f"member {n}'s twin")
+            if rc == 0 and inner[0] != "get_state":      # (the same single call on both: on the words where it is a query)
+                self._diff(out, tout, f"member {n}'s twin", on_words=inner[0] in MEMBER_QUERIES or inner[0] == "bmu_masked")
             return
         order = self.em.ens[p["e"]]
+        if name in ENSQ_CALLS:
+            return self._query_twins(order, op, a, out)
         tout = {}
         for k, n in enumerate(order):
             for key, v in self._single(self.twin[n], n, k, op, a).items():
@@ -2870,9 +3197,12 @@ class EnsGpuBackend:
             self.capi.check(self.L.vsom_synchronize(self.twin[n]._h))
         self._diff(out, tout, "the twins' single calls")
 
-    def _diff(self, out, tout, who):
+    def _diff(self, out, tout, who, on_words=False):
         for key, v in tout.items():
-            d = first_difference_exact(np.asarray(out.get(key)), np.asarray(v))
+            g, v = np.asarray(out.get(key)), np.asarray(v)
+            if on_words and g.dtype == v.dtype and v.dtype.kind == "f":
+                g, v = words(g), words(v)      # (NaN payloads too: a record that is NaN throughout, a padded list)
+            d = first_difference_exact(g, v)
             if d:
                 out["twin_diff"] = f"output {key!r} differs from {who} at {d}"
                 return
@@ -2932,3 +3262,573 @@ class EnsGpuBackend:
 
     def observe_twin(self, n):
         return self.gb[n].observe(self.twin[n])
+
+
+# ---- the ensemble_query profile ----------------------------------------------------------------------------------------
+# The four query calls of include/vsom_hip.h, "ensembles" -- vsom_ensemble_bmu_masked_batch, _similarity_masked_batch,
+# _bmu_topk_batch, _bmu_topk_masked_batch (with vsom_ensemble_topk_applies) -- walked with the ensemble profile's calls
+# between them.  Ops: ("ens_bmu_masked", {e, masks, min_hits[], fill[]}), ("ens_similarity_masked", {e, masks, min_hits[],
+# num_sigmas[], rule, delta[]}), ("ens_topk", {e, cover[], k[], dist[]}), ("ens_topk_masked", {e, masks, k[], min_hits[],
+# dist[], count[], nvalid[]}); masks names the covered members (ens_mask specs), every other member is skipped; the boolean
+# lists say which optional output pointers are non-NULL.  generate_ensemble_query's docstring lists the runs.
+ENSQ_CALLS = ("ens_bmu_masked", "ens_similarity_masked", "ens_topk", "ens_topk_masked")
+ENSQ_MASKED = ("ens_bmu_masked", "ens_similarity_masked", "ens_topk_masked")
+ENSQ_NEW_OPS = set(ENSQ_CALLS) | {"similarity_masked", "topk_masked", "bmd_masked", "generate_masked"}
+ENSQ_MASKABLE = ("A", "A2", "B", "D", "D2", "Q")      # the model checks every row of these (B * N <= ENSQ_ALL_ROWS)
+ENSQ_DRAWS = 6                       # random draws of an ensemble_query walk, around its runs
+ENSQ_RUNS = tuple(range(1, 9))
+ENSQ_K = (1, 2, 8, 64)
+ENSQ_ALL_ROWS = 32768                # B * N up to which the model checks every row of a covered member
+ENSQ_SAMPLE = 8                      # ... beyond it: this many rows (row 0, the last, the row without a valid column)
+ENSQ_REFUSALS = ("null_valid", "null_out", "null_k", "null_num_sigmas", "bad_rule", "clr", "no_chunk", "k0", "k65", "k9",
+                 "null_idx")                                       # run 6, every configuration
+ENSQ_REFUSALS_OWN = ("custom",)                                    # ... the one that needs the custom member F
+QNAN32 = np.uint32(0x7FC00000)
+
+
+def masked_query_fast(cfg, B):
+    """include/vsom_hip.h, vsom_ensemble_bmu_masked_batch: the member runs in ensemble_masked_many_kernel -- Standard /
+    Median, not custom, B > 0, N * D <= 4096.  (The LDS term 768 + 4 N D is at most 17152 bytes there: it never binds.)"""
+    N, D = cfg["W"] * cfg["H"], po.length(cfg["tr"], cfg["J"])
+    return not cfg["custom"] and cfg["tr"] != po.CLR and B > 0 and N * D <= 4096
+
+
+def topk_fast(cfg, B, k, masked):
+    """vsom_ensemble_topk_applies as include/vsom_hip.h states it: not custom, B > 0, 1 <= k <= min(64, N),
+    N * part_len <= 4096 (part_len: D, or D / 2 for CLR), no CLR member in the masked call.  (The LDS term
+    512 + 512 (k | 1) + 4 N D is at most 512 + 512 * 65 + 4 * 2 * 4096 = 66560 bytes only for a CLR map at k = 64 with
+    N * part_len = 4096; for the members here it is at most 50176: it never binds.)"""
+    N, D = cfg["W"] * cfg["H"], po.length(cfg["tr"], cfg["J"])
+    part = D // 2 if cfg["tr"] == po.CLR else D
+    return not cfg["custom"] and B > 0 and 1 <= k <= min(64, N) and N * part <= 4096 and \
+        not (masked and cfg["tr"] == po.CLR)
+
+
+def covered(op, order):
+    """the members a query call covers, in member order"""
+    name, p = op
+    if name == "ens_topk":
+        return [n for n, c in zip(order, p["cover"]) if c]
+    return [n for n in order if n in p["masks"]]
+
+
+def ensq_stats():
+    return {"accepted": {c: 0 for c in ENSQ_CALLS}, "mixed": {c: 0 for c in ENSQ_CALLS}, "applies": 0, "padded": 0,
+            "novalid": 0, "b0": 0, "ahead_skipped": 0, "met": {}, "covered_rows": {}, "model_rows": {}}
+
+
+# -- the model's distances: pure Python (about 12 us a distance), cached by content, so that the calls of one block and the
+# CPU fake (tests/test_call_sequences_model.py), which states the same function of ITS state, share them
+_DIST_CACHE = {}
+
+
+def _digest(*arrays):
+    import hashlib
+    h = hashlib.sha1()
+    for a in arrays:
+        a = np.ascontiguousarray(a)
+        h.update(str((a.shape, a.dtype)).encode())
+        h.update(a.tobytes())
+    return h.digest()
+
+
+def _cached(key, make):
+    if key not in _DIST_CACHE:
+        if len(_DIST_CACHE) > 256:
+            _DIST_CACHE.clear()
+        _DIST_CACHE[key] = make()
+    return _DIST_CACHE[key]
+
+
+def masked_distances(mod, X, V):
+    """masked_score_ref.masked_dists of the rows X under the validity V to every node of the member's map: rows x N"""
+    import masked_score_ref as msr
+    M = mod.som.map
+    def make():
+        with np.errstate(all="ignore"):
+            return np.array([msr.masked_dists(mod.cfg["tr"], x, M, v) for x, v in zip(X, V)], np.float32).reshape(len(X), mod.N)
+    return _cached(("masked", mod.cfg["tr"], _digest(M, X, V)), make)
+
+
+def plain_distances(mod, rows):
+    """the oracle's own distance (Model._dist) of the chunk's rows `rows` to every node: rows x N"""
+    def make():
+        with np.errstate(all="ignore"):
+            return np.array([mod._dist(np.arange(mod.N), np.full(mod.N, r)) for r in rows], np.float32).reshape(len(rows), mod.N)
+    return _cached(("plain", mod.cfg["tr"], mod.cfg["J"], _digest(mod.som.map, mod.X[rows])), make)
+
+
+def model_rows(mod, valid, p, k):
+    """The rows of a covered member the model checks: all of them where B * N <= ENSQ_ALL_ROWS; on the larger members a
+    seeded sample of ENSQ_SAMPLE rows with row 0, the last row and the row without a valid column, if the mask has one"""
+    B = mod.B
+    if B * mod.N <= ENSQ_ALL_ROWS:
+        return np.arange(B)
+    rows = {0, B - 1}
+    if valid is not None and np.ndim(valid) == 2:
+        rows |= set(np.flatnonzero(~(np.asarray(valid) != 0).any(axis=1))[:1].tolist())
+    rs = np.random.RandomState([B, k, mod.N])
+    for r in rs.permutation(B):
+        if len(rows) >= ENSQ_SAMPLE:
+            break
+        rows.add(int(r))
+    return np.array(sorted(rows))
+
+
+def _searched(d, hits, min_hits):
+    """masked_score_ref.argmin_rule per row of distances; a NaN distance is 0x7FC00000"""
+    import masked_score_ref as msr
+    with np.errstate(all="ignore"):
+        got = [msr.argmin_rule(row, hits, min_hits) for row in d]
+    bmu = np.array([b for b, _ in got], np.uint64)
+    dist = np.array([v for _, v in got], np.float32)
+    dist[np.isnan(dist)] = QNAN32.view(np.float32)
+    return bmu, dist
+
+
+def query_member(mod, name, p, k, valid, rows, hits=None, sigma=None):
+    """what one covered member's share of a query call returns for the chunk's rows `rows`, from the plain references:
+    masked_score_ref (masked_dists, argmin_rule, similarity), topk_masked_ref (lists, nvalid, keys' order over the
+    oracle's own distances for the plain call); fill is x at valid columns and the unit's map row elsewhere"""
+    import masked_score_ref as msr
+    import topk_masked_ref as tmr
+    s = mod.som
+    hits = s.hits if hits is None else hits
+    if name == "ens_topk":
+        idx, dist, _ = tmr.lists(plain_distances(mod, rows), hits, 0, p["k"][k])
+        return {"idx": idx, "dist": dist}
+    X = mod.X[rows]
+    V = np.broadcast_to(np.asarray(valid) != 0, mod.X.shape)[rows]
+    d = masked_distances(mod, X, V)
+    nvalid = V.sum(axis=1).astype(np.uint32)
+    mh = p["min_hits"][k]
+    if name == "ens_topk_masked":
+        idx, dist, count = tmr.lists(d, hits, mh, p["k"][k])
+        return {"idx": idx, "dist": dist, "count": count, "nvalid": nvalid}
+    bmu, dist = _searched(d, hits, mh)
+    b = bmu.astype(np.int64)
+    if name == "ens_bmu_masked":
+        return {"bmu": bmu, "dist": dist, "nvalid": nvalid, "fill": np.where(V, X, s.map[b]).astype(np.float32)}
+    with np.errstate(all="ignore"):
+        out = msr.similarity(X, s.map[b], (s.sigma if sigma is None else sigma)[b], p["num_sigmas"][k], p["rule"] == 1, V)
+    out.update(bmu=bmu, dist=dist, nvalid=nvalid)
+    return out
+
+
+MEMBER_QUERIES = ("topk", "topk_masked", "similarity_masked", "bmd_masked", "generate_masked")
+BMD_RTOL = 1e-15                     # norm and prob against the float64 restatement: tests/test_gpu_bmd_masked.py's RTOL
+
+
+def member_query(mod, op, a):
+    """The single-context queries this profile draws on a member, for its rows [r0, r1), from the plain references:
+    topk_masked_ref (lists, nvalid, blend within blend_bound), masked_score_ref.similarity, bmd_masked_ref (distribution,
+    draws, records within generate_ref.bound).  What depends on the device's exp or log is a Within; a draw within
+    bmd_masked_ref.NEAR of a cumulative boundary is not compared, nor is the record around it."""
+    import bmd_masked_ref as bmr
+    import generate_ref as gr
+    import masked_score_ref as msr
+    import topk_masked_ref as tmr
+    name, p = op
+    s = mod.som
+    rows = np.arange(p["r0"], p["r1"])
+    if name == "topk":
+        idx, dist, _ = tmr.lists(plain_distances(mod, rows), s.hits, 0, p["k"])
+        return {"r0": idx, "r1": dist}
+    X = mod.X[rows]
+    V = np.broadcast_to(a["valid"] != 0, X.shape)
+    d = masked_distances(mod, X, V)
+    nvalid = V.sum(axis=1).astype(np.uint32)
+    if name == "topk_masked":
+        idx, dist, count = tmr.lists(d, s.hits, p["min_hits"], p["k"])
+        out = {"idx": idx, "dist": dist, "count": count, "nvalid": nvalid}
+        if p["blend"]:
+            want, mass = tmr.blend(X, V, s.map, idx, dist, count)
+            bound = np.where(V | ~mass[:, None], 0.0, tmr.blend_bound(s.map, idx, count, p["k"]))
+            out["blend"] = Within(want, bound)
+        return out
+    if name == "similarity_masked":
+        bmu, dist = _searched(d, s.hits, p["min_hits"])
+        b = bmu.astype(np.int64)
+        with np.errstate(all="ignore"):      # (GpuBackend._call1: two sigmas, with delta)
+            out = msr.similarity(X, s.map[b], s.sigma[b], 2, p["rule"] == 1, V)
+        out.update(bmu=bmu, dist=dist, nvalid=nvalid)
+        return out
+    P, norm, prob = bmr.distribution(d, s.hits, p["min_hits"])
+    unit, near = bmr.draws(P, a["u"])
+    clear = near > bmr.NEAR
+    if name == "bmd_masked":
+        with np.errstate(all="ignore"):
+            return {"norm": Within(norm, BMD_RTOL * np.abs(norm)), "prob": Within(prob, BMD_RTOL * np.abs(prob)),
+                    "draw": Within(unit, np.where(clear, 0.0, np.inf))}
+    rec, zs, kept = bmr.records(s.map, s.sigma, unit, a["l"], X, V, True)
+    with np.errstate(all="ignore"):
+        bound = np.where(kept, 0.0, gr.bound(rec, zs))
+    return {"unit": Within(unit, np.where(clear, 0.0, np.inf)),
+            "record": Within(rec, np.where(clear[:, :, None], bound, np.inf))}
+
+
+def words(a):
+    """an array as its words: floats as unsigned integers of their width, so that NaN payloads and signs compare"""
+    a = np.ascontiguousarray(a)
+    return a.view({4: np.uint32, 8: np.uint64}[a.dtype.itemsize]) if a.dtype.kind == "f" else a
+
+
+# outputs whose NaN is computed, not defined: the similarity words, and fill, which copies the map at invalid columns -- a
+# NaN there was computed by an earlier epoch (x is finite wherever it is valid), on the host with the host's payload
+ARITHMETIC_NAN = ("dmax", "first", "amax", "delta", "fill")
+
+
+def query_difference(got, exp, key=None):
+    """A query output against the model, on the words: every bit, NaN payloads included -- the header fixes every NaN these
+    calls store by definition (0x7FC00000 for a NaN distance and for the padding of a short list, UINT64_MAX for its
+    units).  Only the outputs of ARITHMETIC_NAN, where a NaN is the result of the CPU's own arithmetic (a NaN in the map or
+    the sigmaMap), compare as values with NaN equal to NaN; every other bit of them, the sign of a zero included, counts."""
+    got, exp = np.asarray(got), np.asarray(exp)
+    if got.shape != exp.shape or got.dtype != exp.dtype:
+        return f"a shape / type: returned {got.shape} {got.dtype} values, expected {exp.shape} {exp.dtype}"
+    if key in ARITHMETIC_NAN:
+        return first_difference_exact(got, exp)
+    d = first_difference_exact(words(got), words(exp))
+    if d and exp.dtype.kind == "f":
+        at = np.unravel_index(int(np.argmax(words(got).reshape(-1) != words(exp).reshape(-1))), exp.shape)
+        d += f"; as values: got {got[at]!r}, expected {exp[at]!r}"
+    return d
+
+
+class _EnsqGen(_EnsGen):
+    """the ensemble profile's generator and the four query calls"""
+
+    def slow(self):
+        return "G" if "G" in self.all else "E"
+
+    def kfor(self, n, k=None):
+        """a k of ENSQ_K for member n: k = N = 8 on D and D2 instead of 8 and 64"""
+        k = ENSQ_K[self.r(len(ENSQ_K))] if k is None else k
+        N = config(n)["W"] * config(n)["H"]
+        return min(k, N) if k in ENSQ_K else k       # (a refusal's k -- 0, 65, 9 -- stays as it is)
+
+    def train(self, kind, e=0, masks=None, **kw):
+        if kind == "ens_online_masked" and masks:      # (D2's 513 columns as D's 512: on 3 rows only)
+            masks = {n: s for n, s in masks.items() if n != "D2" or (self.B[n] or 0) <= 40}
+        return super().train(kind, e, masks=masks, **kw)
+
+    def q(self, kind, e=0, cover=(), masks=None, k=None, min_hits=None, flags=None, full=None, **tags):
+        """One query call.  cover: the covered members' names (every other member is skipped); masks: specs to reuse (the
+        rows are poisoned for them), a covered member without one gets a fresh spec; k / min_hits: one value, a dict per
+        member, or drawn; flags[output]: True / False / a set of member names with a non-NULL pointer, else drawn"""
+        order = self.ens[e]
+        cover = [n for n in order if n in cover]
+        K = len(order)
+        p = dict(e=e)
+
+        def per(v, draw):
+            return [int(v[n]) if isinstance(v, dict) and n in v else (draw(n) if v is None or isinstance(v, dict) else int(v))
+                    for n in order]
+
+        def flag(key):
+            v = (flags or {}).get(key)
+            if v is None:
+                return [bool(self.r(2)) for _ in range(K)]
+            return [v] * K if isinstance(v, bool) else [n in v for n in order]
+
+        if kind == "ens_topk":
+            p["cover"] = [n in cover for n in order]
+        else:
+            new = [n for n in cover if n not in (masks or {})]
+            fresh = self.specs(e, names=new, full=full) if new else {}
+            p["masks"] = {n: dict((masks or {}).get(n) or fresh[n]) for n in cover}
+        if kind in ("ens_topk", "ens_topk_masked"):
+            p["k"] = per(k, lambda n: self.kfor(n))
+            p["k"] = [self.kfor(n, v) for n, v in zip(order, p["k"])]
+        if kind != "ens_topk":
+            p["min_hits"] = per(min_hits, lambda n: self.r(3))
+        if kind == "ens_bmu_masked":
+            p["fill"] = flag("fill")
+        elif kind == "ens_similarity_masked":
+            p.update(num_sigmas=[1 + self.r(3) for _ in range(K)], rule=self.r(2), delta=flag("delta"))
+        elif kind == "ens_topk":
+            p["dist"] = flag("dist")
+        else:
+            p.update(dist=flag("dist"), count=flag("count"), nvalid=flag("nvalid"))
+        p.update(tags)
+        self.emit(kind, **p)
+
+    def four(self, e=0, cover=(), masks=None, **kw):
+        """the four calls over one cover, the three masked ones under the same masks (the model's distances are shared)"""
+        names = [n for n in self.ens[e] if n in cover and n not in (masks or {}) and n != "C"]
+        masks = dict(masks or {}, **(self.specs(e, names=names) if names else {}))
+        for kind in ENSQ_CALLS:
+            self.q(kind, e, cover=[n for n in cover if n != "C" or kind == "ens_topk"], masks=masks, **kw)
+
+    def maskable(self, e=0):
+        return [n for n in self.ens[e] if n in ENSQ_MASKABLE]
+
+    def some(self, e=0, slow=None):
+        """a cover for a drawn query: two or more of the small members but not all of them, the slow member in half"""
+        names = self.maskable(e)
+        self.rs.shuffle(names)
+        names = names[:max(2, 1 + self.r(len(names) - 1))] if len(names) > 2 else names
+        if (self.r(2) if slow is None else slow) and self.slow() in self.ens[e]:
+            names = names + [self.slow()]
+        return names
+
+    def member_query(self):
+        """a single-context query on a small member: the ones this profile adds beside bmu_masked"""
+        n = self.maskable()[self.r(len(self.maskable()))]
+        B = self.B[n] or 0
+        if B == 0:
+            return
+        k = 1 + self.r(min(32, B))
+        r0 = self.r(B - k + 1)
+        w = dict(r0=r0, r1=r0 + k, seed=self.r(1 << 30))
+        N = config(n)["W"] * config(n)["H"]
+        form = ["rows", "one_mask"][self.r(2)]
+        what = ["similarity_masked", "topk", "topk_masked", "bmd_masked", "generate_masked"][self.r(5)]
+        if what == "similarity_masked":
+            self.m(n, what, min_hits=self.r(2), rule=self.r(2), form=form, **w)
+        elif what == "topk":
+            self.ops.append(("m", {"k": n, "op": (what, dict(k=min(N, ENSQ_K[self.r(4)]), r0=w["r0"], r1=w["r1"]))}))
+        elif what == "topk_masked":
+            self.ops.append(("m", {"k": n, "op": (what, dict(k=min(N, ENSQ_K[self.r(4)]), min_hits=self.r(3),
+                                                           blend=bool(self.r(2)), form=form, **w))}))
+        elif what == "bmd_masked":
+            self.m(n, what, min_hits=self.r(2), form=form, **w)
+        else:
+            self.m(n, what, min_hits=self.r(2), draws=[1, 3][self.r(2)], form=form, **w)
+
+    def random_op(self, e=0):
+        what = self.r(10)
+        if what < 4:
+            self.q(ENSQ_CALLS[what], e, cover=self.some(e) + (["C"] if what == 2 and "C" in self.ens[e] and self.r(2) else []))
+        elif what == 4:
+            self.member_query()
+        else:
+            super().random_op(e)
+
+    # ---- the runs ----
+    def qrun(self, run):
+        own = not self.ec["one_stream"]
+        e, S = 0, self.slow()
+        small = self.maskable(e)
+        # (every run starts from clean rows; short chunks: the model's masked distance is pure Python)
+        self.upload(e, {"A": 0, "A2": 0, "B": 0, "Q": 1}, wait=1)
+        self.emit("run", id=run)
+        if run == 1:
+            pick = {"A": 0, "A2": 0, "B": 0, "C": 0, "D": 1, "D2": 1, "Q": 3, "E": 0, "F": 0, "G": 0}
+            tm = self.specs(e, names=[n for n in small if n != "D2"], full="A")
+            skip = [n for n in small if n not in ("A", "Q")]
+            cov = lambda i: [n for n in small if n != skip[i % len(skip)]] + [S]
+            self.upload(e, pick, wait=0, poison=tm)
+            self.train("ens_epoch_masked", e, masks=tm, first=True)
+            self.q("ens_bmu_masked", e, cover=cov(0), masks=tm, flags={"fill": True})
+            self.train("ens_schedule_masked", e, masks=tm, sigmas=[[self.sigma()] for _ in self.ens[e]])
+            self.q("ens_topk_masked", e, cover=cov(1), masks=tm)
+            self.train("ens_online_masked", e, masks=tm, first=True)
+            self.q("ens_similarity_masked", e, cover=cov(2), masks=tm, flags={"delta": True})
+            big = {"A": 3, "A2": 3, "B": 2, "C": 1, "D": 1, "D2": 1, "Q": 5, "E": 2, "F": 1, "G": 1}
+            self.upload(e, big, wait=0)      # more floats than the first: the raw buffer grows behind the stagings
+            self.q("ens_topk", e, cover=[n for n in self.ens[e] if n not in ("F", skip[0])])
+            self.train("ens_epoch", e, first=True)         # covers every member: the pinned rows may change behind it
+        elif run == 2:
+            self.upload(e, {"A": 0, "A2": 0, "B": 0, "D": 1, "D2": 1, "Q": 3, "E": 0, "G": 0})
+            tm = self.specs(e, names=small + [S], full="Q")
+            wide = [n for n in self.ens[e] if n != "F"]
+            self.q("ens_similarity_masked", e, cover=small + [S], masks=tm, flags={"delta": True})
+            self.q("ens_topk", e, cover=wide[:-1] if S == wide[-1] and not own else wide[1:], k=64, flags={"dist": True})
+            self.q("ens_bmu_masked", e, cover=["A", "Q"], masks=tm, flags={"fill": False})
+            self.q("ens_topk", e, cover=wide[1:], k=1)
+            self.q("ens_topk_masked", e, cover=small[1:] + [S], masks=tm, k={"A": 2, "B": 8, "Q": 64, "D": 8, "D2": 1, S: 2},
+                   flags={"dist": set(small[1:-1]), "count": set(small[2:]) | {S}, "nvalid": set(small[1:3]) | {S}})
+            self.q("ens_bmu_masked", e, cover=small[:-1] + [S], masks=tm, flags={"fill": {"B"}})
+        elif run == 3:
+            self.upload(e, {"A": 0, "A2": 0, "B": 0, "D": 0, "D2": 0, "Q": 1, "E": 0, "G": 0})
+            self.m("A", "set_last_bmu", seed=self.r(1 << 30))
+            self.m("Q", "set_last_bmu", seed=self.r(1 << 30))
+            tm = self.specs(e, names=small + [S])
+            self.four(e, cover=[n for n in self.ens[e] if n in tm or n == "C"], masks=tm)
+            for n in self.ens[e]:
+                for what in ("get_last_bmu", "get_sqres", "get_mse"):
+                    self.m(n, what)
+            self.train("ens_epoch", e, first=False)
+            self.m("B", "set_state", seed=self.r(1 << 30), parts="hits0")
+            self.m("A", "set_state", seed=self.r(1 << 30), parts="all")
+            for again in range(2):
+                self.q("ens_bmu_masked", e, cover=small[:-1], masks=tm, min_hits=1)
+                self.q("ens_similarity_masked", e, cover=small[1:] + [S], masks=tm, min_hits=2, flags={"delta": True})
+                self.q("ens_topk_masked", e, cover=small, masks=tm, min_hits={"A": 2, "B": 1, "Q": 2}, k={"A": 8, "B": 8, "Q": 2},
+                       flags={"dist": True, "count": True, "nvalid": True})
+                if not again:
+                    self.train("ens_online", e, first=True)
+        elif run == 4:
+            for i, c in enumerate((1, 2, 3, 5, 0)):          # Q at 63, 64, 65, 129 rows and at 1
+                self.upload(e, {"Q": c, "D": i % 2, "D2": i % 2, "A": 0, "A2": 0, "B": 0, "E": 0, "G": 0})
+                if i == 1:
+                    self.m("A", "bmu_mode", mode=BMU_EXACT)
+                    self.m("A", "update_mode", mode=UPDATE_FMA)
+                self.four(e, cover=["A", "D", "D2", "Q"] + ([S] if i in (1, 4) else []) + (["B"] if i == 2 else []))
+                if i == 1:
+                    self.m("A", "update_mode", mode=UPDATE_STRICT)
+                    self.m("A", "bmu_mode", mode=BMU_AUTO)
+            if "E" in self.ens[e]:           # a NaN sigma: E's map is NaN when the queries read it
+                self.train("ens_schedule", e, sigmas=[[2.5, None] if n == "E" else [] for n in self.ens[e]], reset=False)
+                self.four(e, cover=["A", "Q", "E"], labels=["nan_map"])
+                self.m("E", "get_state")
+                self.m("E", "set_state", seed=self.r(1 << 30), parts="all")
+        elif run == 5:
+            ahead = S if stages_ahead(config(S)) else None
+            self.m(S, "upload", chunk=0, asynchronous=False)
+            self.m(S, "epoch_async", sigma=self.sigma(), first=True)
+            self.m(S, "prefetch", chunk=0, src="pinned")
+            tm = self.specs(e, names=["A", "Q", S])
+            for kind in ENSQ_CALLS:          # covered: MUST be refused where the chunk is staged ahead, naming the member
+                self.q(kind, e, cover=["A", "Q", S], masks=tm, **({"must_refuse": ahead} if ahead else {}))
+            for kind in ENSQ_CALLS:          # skipped: accepted
+                self.q(kind, e, cover=["A", "Q"], masks=tm, **({"ahead_skipped": ahead} if ahead else {}))
+            self.m(S, "commit")
+            for kind in ENSQ_CALLS:
+                self.q(kind, e, cover=["A", "Q", S], masks=tm)
+        elif run == 6:
+            tm = self.specs(e, names=["A", "D", "Q"])
+            for kind in ENSQ_MASKED:
+                self.q(kind, e, cover=["A", "D", "Q"], masks=tm, bad="null_valid")
+            for kind in ENSQ_CALLS:
+                self.q(kind, e, cover=["A", "D", "Q"], masks=tm, bad="null_out")
+            for kind in ("ens_topk", "ens_topk_masked"):
+                self.q(kind, e, cover=["A", "D", "Q"], masks=tm, bad="null_k")
+            self.q("ens_similarity_masked", e, cover=["A", "Q"], masks=tm, bad="null_num_sigmas")
+            self.q("ens_similarity_masked", e, cover=["A", "Q"], masks=tm, bad="bad_rule")
+            if own:
+                for kind in ENSQ_CALLS:
+                    self.q(kind, e, cover=["A", "Q", "F"], masks=tm)
+            for kind in ENSQ_MASKED:
+                self.q(kind, e, cover=["A", "C", "Q"], masks=tm)
+            self.q("ens_topk", e, cover=["A", "C", "Q"], labels=["topk_clr"])       # accepted
+            for kind in ("ens_topk", "ens_topk_masked"):
+                self.q(kind, e, cover=["A", "D", "Q"], masks=tm, k={"A": 0, "D": 8, "Q": 2})
+                self.q(kind, e, cover=["A", "D", "Q"], masks=tm, k={"A": 65, "D": 8, "Q": 2})
+                self.q(kind, e, cover=["A", "D", "Q"], masks=tm, k={"A": 2, "D": 9, "Q": 2})
+                self.q(kind, e, cover=["A", "Q"], masks=tm, k={"A": 2, "D": 9, "Q": 2}, labels=["k_of_a_skipped_member"])
+            self.q("ens_topk_masked", e, cover=["A", "D", "Q"], masks=tm, bad="null_idx", null_idx="D")
+        elif run == 7:
+            old = list(self.ens[0])
+            self.emit("ens_destroy", e=0)
+            del self.ens[0]
+            self.ens[0] = old                # (member_query draws among the former members)
+            for _ in range(6):
+                self.member_query()
+            del self.ens[0]
+            sub = [n for n in old if n != ("F" if own else "C")]
+            sub = [sub[i] for i in self.rs.permutation(len(sub))]
+            self.emit("ens_create", e=0, order=sub)
+            self.ens[0] = sub
+            self.ens[1] = [n for n in reversed(sub) if n in ENSQ_MASKABLE][:3]
+            self.emit("ens_create", e=1, order=self.ens[1])
+            for i in range(4):
+                self.q(ENSQ_CALLS[i], 0, cover=self.some(0, slow=i % 2))
+                self.q(ENSQ_CALLS[(i + 1) % 4], 1, cover=self.ens[1][:2] if i % 2 else self.ens[1])
+            empty = self.ens[1][1]
+            self.upload(1, {"A": 0, "A2": 0, "B": 0, "Q": 2})
+            self.ops[-1][1]["rows"][empty] = {"chunk": 0, "head": 0}      # B = 0: that member writes nothing
+            self.B[empty] = 0
+            self.four(1, cover=self.ens[1], labels=["b0"])
+            self.four(0, cover=[n for n in self.maskable(0)[:3]] + [empty])
+            self.upload(1)
+            self.emit("ens_destroy", e=1)
+            del self.ens[1]
+            self.four(0, cover=self.some(0, slow=1))
+            self.emit("ens_destroy", e=0)
+            del self.ens[0]
+        self.emit("run_end", id=run)
+        self.m(self.all[self.r(len(self.all))], "get_state")
+
+
+def generate_ensemble_query(cfg_name, seed, n_ops=ENSQ_DRAWS):
+    """The ensemble_query profile: n_ops random draws -- the four query calls and single-context queries on members mixed
+    into the ensemble profile's draws (training calls, masked blocks, uploads, member ops) -- around these runs, each
+    between ("run", id) / ("run_end", id) markers.  Run 8 and the refusals of run 6 that need a member without a chunk open
+    the walk; runs 1-6 follow in a drawn order, run 7 ends the walk.
+      1  back to back, no wait: upload_chunks(wait = 0) of rows poisoned for the masks from pinned memory, batch_epoch_masked,
+         bmu_masked (fill), batch_schedule_masked, bmu_topk_masked, train_online_chunk_masked, similarity_masked (delta) --
+         six images of different sizes through the two descriptor slots, training tables and query images in turn --; a
+         second, larger upload_chunks(wait = 0) of clean rows and bmu_topk at once behind it; a batch epoch, which covers
+         every member, ends the run.  Every query covers the slow member (E / G) and skips one
+      2  the result buffers shrink and change their layout, on one set of rows: similarity_masked with delta for every small
+         member, bmu_topk with k = 64 where N allows, bmu_masked without fill over two members, bmu_topk with k = 1,
+         bmu_topk_masked with mixed k and dist / count / nvalid each NULL for some member, bmu_masked with fill for one
+      3  read-only, and the live state: vsom_set_last_bmu on A and Q, the four queries, every member's lastBMU / sqres / MSE,
+         batch_epoch(is_first = 0); bmuHits all zero on B and mixed on A, the masked queries with min_hits 1 and 2, an
+         ensemble online chunk, the same queries again
+      4  path borders: Q at 63, 64, 65, 129 and 1 rows between two calls of each kind, D and D2 in the same calls; A's search
+         mode EXACT and its update mode non-strict around one block; E (ensq_shared) queried with a NaN map
+      5  the stage-ahead: an asynchronous epoch and a prefetch on G (ensq_own; E on ensq_shared, where nothing stages ahead):
+         the four calls covering it MUST be refused naming it, with it skipped they are accepted; after the commit accepted
+      6  every refusal the header lists for the four calls; bmu_topk accepts the CLR member; a skipped member may hold any k
+      7  destroy, single-context queries on former members, create over a permuted subset and a second ensemble over an
+         overlapping subset in another order, queries alternating between the two, an upload that leaves a member B = 0
+      8  G (ensq_own): an epoch under VSOM_SIGMA_LAZY before the first create, create, a batch epoch, similarity_masked
+         covering G on its single-call path"""
+    g = _EnsqGen(cfg_name, seed)
+    g.ops.append(("config", {"name": cfg_name, "seed": seed, "profile": "ensemble_query"}))
+    own = "G" in g.all
+    for n in g.all:
+        g.m(n, "set_state", seed=seed + config(n).get("map_seed", 0), parts="init")
+    if own:
+        g.emit("run", id=8)
+        g.m("G", "sigma_mode", mode="lazy")
+        g.m("G", "upload", chunk=0, asynchronous=False)
+        g.m("G", "epoch", sigma=g.sigma(), first=True)
+        g.emit("sigma_stats", k="G", expect=[1, 0, 0, 1])
+    for n in g.all:
+        if n not in ("C", "G", "Q"):
+            g.m(n, "upload", chunk=0, asynchronous=False)
+    g.emit("ens_create", e=0, order=list(g.all))
+    g.ens[0] = list(g.all)
+    if own:
+        g.emit("sigma_stats", k="G", expect=[1, 0, 1, 0])
+    # C and Q have no chunk yet: refused where covered, accepted where skipped
+    g.emit("run", id=6)
+    g.q("ens_topk", 0, cover=["A", "C"])
+    for kind in ENSQ_MASKED:
+        g.q(kind, 0, cover=["A", "Q"])
+    g.four(0, cover=["A", "D", "D2"], labels=["no_chunk_skipped"])
+    g.emit("run_end", id=6)
+    g.upload(0, {n: 0 for n in g.all})
+    if own:
+        g.train("ens_epoch", 0, first=True)
+        g.q("ens_similarity_masked", 0, cover=["A", "Q", "G"], flags={"delta": True}, labels=["lazy_sigma"])
+        g.m("G", "get_state")
+        g.emit("run_end", id=8)
+    slots = sorted(g.rs.choice(np.arange(0, n_ops), 6, replace=False)) if n_ops >= 6 else [0] * 6
+    runs = [int(r) for r in g.rs.permutation(6) + 1]
+    for k in range(n_ops):
+        while slots and k >= slots[0]:
+            slots.pop(0)
+            g.qrun(runs.pop(0))
+        g.random_op()
+    while runs:
+        g.qrun(runs.pop(0))
+    g.qrun(7)
+    for n in g.all:
+        g.m(n, "get_state")
+    return g.ops
+
+
+def ensq_conditions(cfg_name, stats, gpu=False):
+    """what a walk of the ensemble_query profile must have met, from run_ensemble_walk's counts: it cannot pass vacuously"""
+    own = not ENSQ_CONFIGS[cfg_name]["one_stream"]
+    q = stats["q"]
+    assert all(q["accepted"][c] >= 4 for c in ENSQ_CALLS), q["accepted"]
+    # each call: two or more members in the many-member kernel, one on its single call and one skipped, together
+    assert all(q["mixed"][c] >= 1 for c in ENSQ_CALLS), q["mixed"]
+    for label in ENSQ_REFUSALS + (ENSQ_REFUSALS_OWN if own else ()):
+        assert stats["refusals"].get("q_" + label, 0) >= 1, (label, stats["refusals"])
+    for label in ("no_chunk_skipped", "topk_clr", "k_of_a_skipped_member", "b0"):
+        assert q["met"].get(label, 0) >= 1, (label, q["met"])
+    assert stats["refusals"].get("q_staged", 0) == (4 if own else 0) and q["ahead_skipped"] == (4 if own else 0), (stats, q)
+    assert q["padded"] >= 1 and q["novalid"] >= 1 and q["b0"] >= 1, q
+    assert q["applies"] >= 20, q
+    for n in ENSQ_MASKABLE:                  # the sample rule of the large members is the only place the model leaves rows out
+        assert q["covered_rows"].get(n, 0) == q["model_rows"].get(n, 0), (n, q["covered_rows"], q["model_rows"])
+        assert n not in ens_config(cfg_name)["members"] or q["covered_rows"].get(n, 0) > 0, n
+    if gpu:
+        assert stats["nowait"] >= 2, stats

@@ -1001,7 +1001,21 @@ class FakeEnsemble:
       share     members with equal offsets get the first one's B
       null_mask a NULL-validity member is treated as masked, so a masked call refuses C
       begin     a former member accepts vsom_batch_accum_begin
-      um        vsom_ensemble_umatrix leaves the per-member buffer unwritten: vsom_get_umatrix is stale"""
+      um        vsom_ensemble_umatrix leaves the per-member buffer unwritten: vsom_get_umatrix is stale
+    and, in the four query calls of the ensemble_query profile (_query):
+      q_lb          a query overwrites the covered members' lastBMU / sqres with its own search
+      q_skip        a skipped member's output arrays are written
+      q_skip_refuse a skipped member that has no chunk, or a chunk staged ahead, makes the call refuse
+      q_ahead       a covered member with a chunk staged ahead is accepted
+      q_hits        min_hits is applied to the bmuHits as they were at vsom_ensemble_create
+      q_sigma       the similarity words come from the sigmaMap before the last training call
+      q_k           every member gets k[0]
+      q_order       in an ensemble created over another order, per-member arguments are matched by the member's index
+                    in the first ensemble
+      q_one_mask    one_mask[k] is read as one_mask[0]
+      q_pad         a row with fewer than k candidates repeats its last candidate instead of the padding
+      q_stale       a call behind a larger one returns, for its last covered member, what the larger call left
+      q_b0          a member with B = 0 gets its arrays zeroed"""
 
     def __init__(self, cfg_name, em, mutant=None):
         self.f = cs.EnsModel(cfg_name, 0)
@@ -1011,7 +1025,8 @@ class FakeEnsemble:
         self.ahead = {n: False for n in em.names}
         self.last = {n: None for n in em.names}
         self.stale = {}
-        self.rec = {n: cs.SigmaRecord(cs.ENS_MEMBERS[n]) for n in em.names}
+        self.rec = {n: cs.SigmaRecord(cs.config(n)) for n in em.names}
+        self.first_order, self.hits_at_create, self.prev_sigma, self.prev_out = None, {}, {}, None
 
     def close(self):
         self.f.close()
@@ -1038,7 +1053,7 @@ class FakeEnsemble:
             self.stale[n] = mod.lb.copy()
         self.rec[n].accepted(inner, mod.B, mod.N)
         self.last[n] = name
-        out = f.apply_member(n, inner, a)
+        out = cs.plain(f.apply_member(n, inner, a))
         return 0, "", {k: v for k, v in out.items() if v is not None}
 
     def call(self, op, a):
@@ -1052,10 +1067,15 @@ class FakeEnsemble:
             for n in p["order"]:
                 self.rec[n].read()           # create materialises a pending record; a member never defers again
                 self.rec[n].can_defer = False
+        if name == "ens_create":
+            self.first_order = self.first_order or list(p["order"])
+            self.hits_at_create.update({n: f.m[n].som.hits.copy() for n in p["order"]})
         if name in ("ens_create", "ens_destroy"):
             f.apply(op, a)
             return 0, "", {}
         order = f.ens[p["e"]]
+        if name in cs.ENSQ_CALLS:
+            return self._query(op, a)
         why = f.ens_refusal(op, a)
         if why is None and self.mutant == "null_mask" and p.get("masks"):
             for k, n in enumerate(order):
@@ -1091,6 +1111,8 @@ class FakeEnsemble:
                 if n in self.stale:
                     f.m[n].lb[:] = self.stale.pop(n)
         before = {n: f.m[n].um for n in order}
+        if name in cs.ENS_TRAIN and self.mutant == "q_sigma":
+            self.prev_sigma = {n: f.m[n].som.sigma.copy() for n in order}
         out = f.apply(op, a)
         if name == "ens_umatrix" and self.mutant == "um":
             for n in order:
@@ -1103,6 +1125,94 @@ class FakeEnsemble:
             self.last[n] = name
             self.rec[n].read()
         return 0, "", {k: v for k, v in out.items() if v is not None}
+
+    # ---- the four query calls ----
+    @staticmethod
+    def _asked(name, p, key, k):
+        """whether the call's struct holds a pointer for this output of member k"""
+        if key in ("fill", "delta") or (key in ("dist", "count", "nvalid") and name in ("ens_topk", "ens_topk_masked")):
+            return p[key][k]
+        return True
+
+    def _query(self, op, a):
+        name, p = op
+        f, mu = self.f, self.mutant
+        order = f.ens[p["e"]]
+        K = len(order)
+        cov = cs.covered(op, order)
+        asks = {}
+        if "k" in p and p.get("bad") != "null_k":     # vsom_ensemble_topk_applies, asked before every top-k call
+            asks = {"applies": {n: int(cs.topk_fast(f.m[n].cfg, f.m[n].B, p["k"][order.index(n)], name == "ens_topk_masked"))
+                                for n in cov}}
+        why = f.ensq_refusal(op)
+        if why is None:
+            ahead = "the next chunk is staged ahead over the current chunk's rows: vsom_commit_chunk first"
+            for k, n in enumerate(order):
+                if self.ahead[n] and ((n in cov and mu != "q_ahead") or (n not in cov and mu == "q_skip_refuse")):
+                    why = (k, ahead, None)
+                elif n not in cov and mu == "q_skip_refuse" and f.m[n].X is None:
+                    why = (k, "no chunk loaded", None)
+                if why:
+                    break
+        if why is not None:
+            who = "" if why[0] is None else f"member {why[0]}: "
+            return cs.VSOM_ERR_INVALID, f"vsom_ensemble: {who}{why[1]}", asks
+        q, valid = dict(p), dict(a.get("valid", {}))
+        per_member = [key for key in ("k", "min_hits", "num_sigmas") if key in p]
+        if mu == "q_k" and "k" in p:
+            q["k"] = [p["k"][0]] * K
+        if mu == "q_order" and order != self.first_order[:K]:
+            at = [self.first_order.index(n) % K for n in order]
+            for key in per_member:
+                q[key] = [p[key][i] for i in at]
+        if mu == "q_one_mask" and name != "ens_topk":
+            one0 = valid.get(order[0]) is not None and valid[order[0]].ndim == 1
+            for n in cov:
+                v = valid[n]
+                if f.m[n].B and (v.ndim == 1) != one0:
+                    if one0:
+                        valid[n] = np.ascontiguousarray(v[0])
+                    else:                    # (B x J bytes read from a mask of J: what lies behind it is not valid)
+                        valid[n] = np.zeros((f.m[n].B, v.size), np.uint8)
+                        valid[n][0] = v
+        hits = self.hits_at_create if mu == "q_hits" else None
+        sigma = self.prev_sigma if mu == "q_sigma" else None
+        out, size, last = dict(asks), 0, None
+        for n, (rows, exp) in f.query((name, q), dict(a, valid=valid), hits=hits, sigma=sigma).items():
+            k, B = order.index(n), f.m[n].B
+            if mu == "q_pad" and "count" in exp:
+                for r, c in enumerate(exp["count"]):
+                    exp["idx"][r, c:] = exp["idx"][r, c - 1]
+                    exp["dist"][r, c:] = exp["dist"][r, c - 1]
+            if mu == "q_lb" and "bmu" in exp:
+                f.m[n].lb[rows] = exp["bmu"]
+                f.m[n].sqres = np.zeros(B, np.float32) if f.m[n].sqres is None else f.m[n].sqres
+                f.m[n].sqres[rows] = exp["dist"]
+            for key, v in exp.items():
+                if self._asked(name, p, key, k):
+                    full = np.zeros((B,) + v.shape[1:], v.dtype)
+                    full[rows] = v
+                    out[f"{n}.{key}"] = full
+                    size += full.size
+            last = f"{n}.{'bmu' if 'bmu' in exp else 'idx'}"
+        if mu == "q_skip":
+            for n in order:
+                if n not in cov and f.m[n].B:
+                    out[f"{n}.idx"] = np.zeros(f.m[n].B, np.uint64)
+                    break
+        if mu == "q_b0":
+            for n in cov:
+                if f.m[n].X is not None and f.m[n].B == 0:
+                    out[f"{n}.idx"] = np.zeros(1, np.uint64)
+        if last is not None:
+            kept = out[last].copy()
+            if mu == "q_stale" and self.prev_out is not None and size < self.prev_out[0]:
+                out[last] = np.resize(self.prev_out[1], out[last].shape).astype(out[last].dtype)
+            self.prev_out = (size, kept)
+        for n in cov:
+            self.last[n] = name
+            self.rec[n].read()
+        return 0, "", out
 
 
 ENS_SEEDS = (1, 2)   # tests/test_gpu_call_sequences.py, test_ensemble_walk_matches_oracle
@@ -1268,6 +1378,189 @@ def test_ensemble_mutants_are_caught(mutant):
     for cfg, seed in _ens_walks():
         try:
             _run_ens(cfg, seed, mutant)
+        except cs.WalkFailure as e:
+            text = str(e)
+            assert f"seed {seed}" in text and "replay(ops) with ops = [('config'" in text
+            # the first differing element, or the return code where it is the call's acceptance that differs
+            assert "element" in text or "returned" in text or "failed: -1" in text, text.splitlines()[0]
+            caught.append((cfg, seed, text.splitlines()[0]))
+            break
+    assert caught, f"mutant {mutant} was not caught by any walk"
+
+
+# ---- the ensemble_query profile ------------------------------------------------------------------------------------------
+def _ensq_walks():
+    return [(c, s) for c in cs.ENSQ_CONFIGS for s in ENS_SEEDS]     # tests/test_gpu_call_sequences.py runs these four
+
+
+def _run_ensq(cfg, seed, mutant=None):
+    return cs.run_ensemble_walk(cs.generate_ensemble_query(cfg, seed), lambda name, em: FakeEnsemble(name, em, mutant))
+
+
+@functools.lru_cache(maxsize=None)
+def _faithful_ensq(cfg, seed):
+    return _run_ensq(cfg, seed)
+
+
+@pytest.mark.parametrize("cfg,seed", _ensq_walks())
+def test_faithful_fake_passes_ensemble_query_walks(cfg, seed):
+    """... and the walks the GPU test runs meet the conditions it asserts (callseq.ensq_conditions)"""
+    cs.ensq_conditions(cfg, _faithful_ensq(cfg, seed))
+
+
+# sha256(repr(generate_ensemble_query(cfg, seed)))
+ENSQ_DIGESTS = {
+    ("ensq_shared", 1): "8d9fad2f87c2c7438270b8703d4d5154e5d6b66151b72a644601f82bbf86bf20",
+    ("ensq_shared", 2): "f438b6bf52400ecb69bc6a952b9d70110b4aab61dd648448226c5994abfe3fdc",
+    ("ensq_own", 1): "4fee7816e3a8733451844a919754cbb0b1af925390cf54169aa1acfc36cb7dde",
+    ("ensq_own", 2): "79e70bf208deea422cf5a3c27456ce547ce38737924afd73087c76a8b2073975",
+}
+
+
+@pytest.mark.parametrize("key", _ensq_walks(), ids=lambda k: "-".join(str(v) for v in k))
+def test_ensemble_query_walks_are_unchanged(key):
+    ops = cs.generate_ensemble_query(*key)
+    assert hashlib.sha256(repr(ops).encode()).hexdigest() == ENSQ_DIGESTS[key]
+
+
+def test_ensemble_query_ops_stay_out_of_the_other_walks():
+    assert not (set(cs.ENSQ_MEMBERS) & (set(cs.CONFIGS) | set(cs.ENS_MEMBERS))) and not set(cs.ENSQ_CONFIGS) & set(cs.ENS_CONFIGS)
+    assert not set(cs.ENSQ_CALLS) & set(cs.ENS_CALLS) and not cs.ENSQ_NEW_OPS & cs.ENS_NEW_OPS
+    walks = [cs.generate_ensemble(cfg, seed) for cfg, seed in _ens_walks()]
+    for cfg in cs.CONFIGS:
+        for seed in SEEDS:
+            walks.append(cs.generate(cfg, seed, scale=SCALE))
+            walks += [cs.generate(cfg, seed, scale=SCALE, profile="sigma", mode=mode) for mode in MODES]
+            walks += [_accum_ops(cfg, mode, seed) for mode in MODES]
+    for ops in walks:
+        names = {op[0] for op in ops} | {op[1]["op"][0] for op in ops if op[0] == "m"}
+        assert not (cs.ENSQ_NEW_OPS - set(cs.MASKED_SCORES)) & names
+        assert not {op[1]["k"] for op in ops if op[0] == "m"} & set(cs.ENSQ_MEMBERS)
+    # (similarity_masked is the accum profile's too: there it is a row-window query of one context)
+    for cfg, seed in _ens_walks():
+        assert "similarity_masked" not in {op[1]["op"][0] for op in cs.generate_ensemble(cfg, seed) if op[0] == "m"}
+
+
+def test_ensemble_query_predicates_stand_at_their_borders():
+    """callseq.masked_query_fast / topk_fast at N * D = 4096 and beyond, at k = 0, 1, min(64, N) and above, for CLR, custom
+    and empty chunks; the LDS terms the header names never bind for a member of these walks"""
+    M = dict(cs.ENS_MEMBERS, **cs.ENSQ_MEMBERS)
+    N = lambda n: M[n]["W"] * M[n]["H"]
+    assert N("D") * 512 == 4096 and N("D2") * 513 == 4104
+    assert cs.masked_query_fast(M["D"], 3) and not cs.masked_query_fast(M["D2"], 3)
+    assert not cs.masked_query_fast(M["D"], 0) and cs.masked_query_fast(M["Q"], 1) and cs.masked_query_fast(M["B"], 152)
+    assert not cs.masked_query_fast(M["C"], 77) and not cs.masked_query_fast(M["F"], 64)
+    assert not any(cs.masked_query_fast(M[n], 77) for n in ("E", "G"))
+    for masked in (False, True):
+        assert [cs.topk_fast(M["D"], 3, k, masked) for k in (0, 1, 8, 9)] == [False, True, True, False]
+        assert not any(cs.topk_fast(M["D2"], 3, k, masked) for k in (1, 8))
+        assert [cs.topk_fast(M["Q"], 1, k, masked) for k in (0, 1, 64, 65)] == [False, True, True, False]
+        assert not cs.topk_fast(M["Q"], 0, 2, masked) and not cs.topk_fast(M["F"], 64, 2, masked)
+        assert not any(cs.topk_fast(M[n], 77, 2, masked) for n in ("E", "G"))
+    assert cs.topk_fast(M["C"], 77, 64, False) and not cs.topk_fast(M["C"], 77, 64, True)
+    assert N("C") * (cs.po.length(cs.po.CLR, 6) // 2) <= 4096
+    # the LDS terms: within 64 KiB wherever N * part_len <= 4096 lets a member of these walks onto the fast path
+    for n, cfg in M.items():
+        D = cs.po.length(cfg["tr"], cfg["J"])
+        part = D // 2 if cfg["tr"] == cs.po.CLR else D
+        if N(n) * part <= 4096:
+            assert 512 + 512 * (min(64, N(n)) | 1) + 4 * N(n) * D <= 65536, n
+            assert cfg["tr"] == cs.po.CLR or 768 + 4 * N(n) * D <= 65536, n
+    # every row count of Q is at a border of the 64-row tile
+    assert [b for b, _ in M["Q"]["chunks"]] == [1, 63, 64, 65, 128, 129]
+    assert [x.shape[0] for x in cs.chunk_data("Q", 1, 1, "ensemble")] == [1, 63, 64, 65, 128, 129]
+    assert [x.shape for x in cs.chunk_data("D2", 1, 1, "ensemble")] == [(3, 513), (64, 513)]
+
+
+def test_ensemble_query_walks_hold_the_required_runs():
+    for cfg, seed in _ensq_walks():
+        own = cfg == "ensq_own"
+        S = "G" if own else "E"
+        ops = cs.generate_ensemble_query(cfg, seed)
+        assert ast.literal_eval(repr(ops)) == ops        # a printed walk can be replayed
+        runs = _ens_runs(ops)
+        assert set(runs) == set(cs.ENSQ_RUNS) - (set() if own else {8}), (cfg, seed, sorted(runs))
+        names = {r: [o[1]["op"][0] if o[0] == "m" else o[0] for o in runs[r]] for r in runs}
+        members = cs.ENSQ_CONFIGS[cfg]["members"]
+        cov = lambda o: cs.covered(o, members)
+        # 1: two wait = 0 uploads, training tables and query images in turn, every query covers the slow member and skips one
+        assert names[1] == ["ens_upload", "ens_epoch_masked", "ens_bmu_masked", "ens_schedule_masked", "ens_topk_masked",
+                            "ens_online_masked", "ens_similarity_masked", "ens_upload", "ens_topk", "ens_epoch"], names[1]
+        ups = [o[1] for o in runs[1] if o[0] == "ens_upload"]
+        assert all(u["wait"] == 0 for u in ups) and ups[0]["poison"] and "poison" not in ups[1]
+        size = lambda u: sum(cs.config(n)["chunks"][s["chunk"]][0] * cs.config(n)["J"] for n, s in u["rows"].items())
+        assert size(ups[1]) > size(ups[0])
+        for o in runs[1]:
+            if o[0] in cs.ENSQ_CALLS:
+                assert S in cov(o) and len(cov(o)) < len(members), o
+        assert all(runs[1][2][1]["fill"]) and all(runs[1][6][1]["delta"])
+        # 2: the layouts in the issue's order
+        assert names[2] == ["ens_upload", "ens_similarity_masked", "ens_topk", "ens_bmu_masked", "ens_topk", "ens_topk_masked",
+                            "ens_bmu_masked"], names[2]
+        r2 = [o[1] for o in runs[2]]
+        assert all(r2[1]["delta"]) and set(cs.ENSQ_MASKABLE) & set(members) <= set(r2[1]["masks"])
+        assert max(r2[2]["k"]) == 64 and set(r2[4]["k"]) == {1} and len(r2[3]["masks"]) == 2 and not any(r2[3]["fill"])
+        c5 = cov(runs[2][5])
+        for key in ("dist", "count", "nvalid"):
+            flags = [v for n, v in zip(members, r2[5][key]) if n in c5]
+            assert not all(flags) and any(flags), (key, flags)
+        assert len({k for n, k in zip(members, r2[5]["k"]) if n in c5}) >= 3
+        assert sum(v for n, v in zip(members, r2[6]["fill"]) if n in cov(runs[2][6])) == 1
+        # 3: lastBMU written, the four queries, the observers, a non-first epoch; hits rewritten; queries, training, queries
+        assert names[3][:7] == ["ens_upload", "set_last_bmu", "set_last_bmu"] + list(cs.ENSQ_CALLS), names[3]
+        at = names[3].index("ens_epoch")
+        assert set(names[3][7:at]) == {"get_last_bmu", "get_sqres", "get_mse"} and not runs[3][at][1]["first"]
+        assert names[3][at + 1:] == ["set_state", "set_state", "ens_bmu_masked", "ens_similarity_masked", "ens_topk_masked",
+                                     "ens_online", "ens_bmu_masked", "ens_similarity_masked", "ens_topk_masked"]
+        assert runs[3][at + 1][1]["op"][1]["parts"] == "hits0" and runs[3][at + 1][1]["k"] == "B"
+        assert max(runs[3][at + 3][1]["min_hits"]) == 1 and max(runs[3][at + 4][1]["min_hits"]) == 2
+        # 4: Q's row counts, D and D2 in the same calls
+        rows = [cs.config("Q")["chunks"][o[1]["rows"]["Q"]["chunk"]][0] for o in runs[4] if o[0] == "ens_upload"]
+        assert rows == [63, 64, 65, 129, 1], rows
+        assert all({"D", "D2", "Q"} <= set(cov(o)) for o in runs[4] if o[0] in cs.ENSQ_CALLS and "labels" not in o[1])
+        modes = [o[1]["op"][1]["mode"] for o in runs[4] if o[0] == "m" and o[1]["op"][0] in ("bmu_mode", "update_mode")]
+        assert modes == [cs.BMU_EXACT, cs.UPDATE_FMA, cs.UPDATE_STRICT, cs.BMU_AUTO]
+        if not own:
+            assert any(None in s for o in runs[4] if o[0] == "ens_schedule" for s in o[1]["sigmas"])
+        # 5: covered (refused where staged ahead), skipped, committed
+        assert names[5] == ["upload", "epoch_async", "prefetch"] + list(cs.ENSQ_CALLS) * 2 + ["commit"] + list(cs.ENSQ_CALLS)
+        five = [o for o in runs[5] if o[0] in cs.ENSQ_CALLS]
+        assert [("must_refuse" in o[1], S in cov(o)) for o in five] == [(own, True)] * 4 + [(False, False)] * 4 + [(False, True)] * 4
+        # 6: the refusals, in the generator's order
+        bad = [(o[0], o[1].get("bad")) for o in runs[6] if o[0] in cs.ENSQ_CALLS and o[1].get("bad")]
+        assert bad == [(c, "null_valid") for c in cs.ENSQ_MASKED] + [(c, "null_out") for c in cs.ENSQ_CALLS] + \
+            [("ens_topk", "null_k"), ("ens_topk_masked", "null_k"), ("ens_similarity_masked", "null_num_sigmas"),
+             ("ens_similarity_masked", "bad_rule"), ("ens_topk_masked", "null_idx")], bad
+        ks = [o[1]["k"][0] for o in runs[6] if "k" in o[1] and o[1]["k"][0] in (0, 65)]
+        assert ks == [0, 65, 0, 65] and sum(9 in o[1].get("k", ()) for o in runs[6]) == 4
+        assert sum("C" in cov(o) for o in runs[6] if o[0] in cs.ENSQ_CALLS) == 5
+        assert sum("F" in cov(o) for o in runs[6] if o[0] in cs.ENSQ_CALLS) == (4 if own else 0)
+        # 7: lifetime
+        assert names[7][0] == "ens_destroy" and names[7].count("ens_create") == 2 and names[7].count("ens_destroy") == 3 and names[7][-1] == "ens_destroy"
+        created = [o[1]["order"] for o in runs[7] if o[0] == "ens_create"]
+        assert set(created[1]) <= set(created[0]) and created[1] != [n for n in created[0] if n in created[1]]
+        es = [o[1]["e"] for o in runs[7] if o[0] in cs.ENSQ_CALLS]
+        assert sum(x != y for x, y in zip(es, es[1:])) >= 7
+        assert any("head" in s for o in runs[7] if o[0] == "ens_upload" for s in o[1]["rows"].values())
+        singles = {o[1]["op"][0] for o in runs[7] if o[0] == "m"}
+        assert singles & (cs.ENSQ_NEW_OPS | {"topk"})
+        if own:
+            first = [o[0] for o in ops].index("ens_create")
+            assert ("sigma_stats", {"k": "G", "expect": [1, 0, 0, 1]}) in ops[:first]
+            assert [n for n in names[8] if n.startswith("ens_")][-2:] == ["ens_epoch", "ens_similarity_masked"]
+            assert "G" in cov(runs[8][-2])
+
+
+QUERY_MUTANTS = ["q_lb", "q_skip", "q_skip_refuse", "q_ahead", "q_hits", "q_sigma", "q_k", "q_order", "q_one_mask", "q_pad",
+                 "q_stale", "q_b0"]
+
+
+@pytest.mark.parametrize("mutant", QUERY_MUTANTS)
+def test_ensemble_query_mutants_are_caught(mutant):
+    caught = []
+    for cfg, seed in [("ensq_own", 1), ("ensq_own", 2), ("ensq_shared", 1), ("ensq_shared", 2)]:
+        try:
+            _run_ensq(cfg, seed, mutant)
         except cs.WalkFailure as e:
             text = str(e)
             assert f"seed {seed}" in text and "replay(ops) with ops = [('config'" in text

@@ -84,7 +84,51 @@ Cost of an ensemble walk, measured the same way (against the CPU fake; the model
 seconds: ens_shared 6.2, 7.2; ens_own 7.5, 7.0.  On an MI355X the tests themselves took 1.7 to 2.2 s (ens_shared) and
 2.8 to 4.3 s (ens_own).  The dearest ops are the model's masked calls (tests/masked_train_ref.py and
 tests/online_masked_ref.py, pure Python): they name A, A2, B and D only, the masked online chunk takes the local walk
-(sigma <= 1) on more than 40 rows and D's 512 columns on 3 rows, and E's 1100 and G's 300 rows are loaded once per walk."""
+(sigma <= 1) on more than 40 rows and D's 512 columns on 3 rows, and E's 1100 and G's 300 rows are loaded once per walk.
+
+The ensemble query walks (callseq.generate_ensemble_query) add the four calls that return through state shared with the rest
+of the ensemble: vsom_ensemble_bmu_masked_batch, vsom_ensemble_similarity_masked_batch, vsom_ensemble_bmu_topk_batch and
+vsom_ensemble_bmu_topk_masked_batch (with vsom_ensemble_topk_applies).  They take the descriptor slot the masked training
+calls use for their tables and grow its validity image in place; all four return through one grow-only pinned pair whose
+word layout depends on the call, on each member's k and on who asked for fill / delta; they join the covered members' streams
+only, so a query right behind vsom_ensemble_upload_chunks(wait = 0) or a member's own asynchronous epoch is ordered by that
+join alone; a skipped member must be untouched and must not make the call refuse; and they promise to leave lastBMU, sqres
+and the state alone while reading the live bmuHits, map and sigmaMap.  Two members join the ensemble profile's
+(callseq.ENSQ_MEMBERS): Q, 10 x 10 x 9 with chunks of 1, 63, 64, 65, 128 and 129 rows -- the many-member kernels take one
+workgroup per (member, 64 rows) --, and D2, 4 x 2 x 513, whose N * D = 4104 is the first size beyond the fast path's 4096,
+beside D's 4096.  ensq_shared puts A, A2, B, C, D, D2, Q, E on one stream, ensq_own gives A, B, C, D, D2, Q, F, G a stream
+each.  Around callseq.ENSQ_DRAWS random draws (the four queries and single-context queries on members mixed into the
+ensemble profile's draws) a walk holds the runs of generate_ensemble_query's docstring: the no-wait run (six images of
+different sizes through the two slots, training tables and query images in turn, then bmu_topk at once behind a second,
+larger wait = 0 upload; sent to the ensemble back to back -- the pinned rows are overwritten with NaN only once a call that
+covers every member has returned), result buffers that shrink and change layout, the read-only promise and the live state
+(a written lastBMU must survive four queries and feed batch_epoch(is_first = 0); bmuHits all zero make rows with count < k),
+path borders between two calls of each kind, the stage-ahead (covered: refused naming G; skipped: accepted), every refusal
+the header lists, two ensembles over overlapping subsets in different orders with a member of B = 0, and G's sigmaMap behind
+a lazy epoch, create and an ensemble epoch.  Before every top-k call the walk asks vsom_ensemble_topk_applies for every
+covered member, and with an index past the end, and fails where the library and callseq.topk_fast disagree.  The calls go to
+the C ABI with every output array of every member -- covered, skipped, asked for or not -- filled with a canary and followed
+by a guard: what the call was given for a covered member must be overwritten, everything else, every array of a refused call
+and every guard must stay.  Every output is held twice: on the words (NaN payloads included) to the member's twin, which makes
+the single call over [0, B) from pageable memory, every row; and to the model, which computes it from the member's oracle
+state
+with tests/masked_score_ref.py and tests/topk_masked_ref.py, on the words as well wherever the header defines the word
+(the units, 0x7FC00000 for a NaN distance and for a short list's padding, the counts); NaN equals NaN only in dmax, first,
+amax, delta and fill, where a NaN was computed from a NaN in the map or sigmaMap and carries the host's payload -- every
+row where B * N <= 32768, on E and G a seeded sample of 8 rows with row 0, the last row and the row
+without a valid column.  callseq.ensq_conditions asserts that the walk was not vacuous and that on A, A2, B, D, D2 and Q the
+model checked every covered row.  The single-context queries drawn on members (callseq.member_query) are held to the twin
+on the words and to the model too: the lists and the similarity words bit for bit, blend within topk_masked_ref.blend_bound,
+the BMD's norm and prob within the relative 1e-15 of tests/test_gpu_bmd_masked.py, the records within generate_ref.bound, a
+draw exactly unless it lies within bmd_masked_ref.NEAR of a cumulative boundary.
+
+Cost of an ensemble query walk, seeds 1 and 2, in seconds, against the CPU fake: ensq_shared 11.4, 10.2; ensq_own 15.2, 14.7;
+the ensemble walks, measured beside them: ens_shared 7.5, 8.2; ens_own 10.8, 8.8.  On an MI355X the tests themselves took
+5.4, 4.6 (ensq_shared) and 7.6, 8.0 (ensq_own), the ensemble walks beside them 2.2, 2.0 (ens_shared) and 4.3, 4.1
+(ens_own): within twice the slowest of those, with little to spare on ensq_own.  The model's masked distance is pure Python
+(about 12 us a distance, twice that with its call overhead) and is most of the cost: the runs load the members' shortest
+chunks wherever a run is not about the row count, the calls of one block share their masks and, through a cache keyed by the
+bytes of the map, the rows and the mask, their distances, and a walk makes 6 random draws."""
 import pytest
 
 import callseq as cs
@@ -150,3 +194,10 @@ def test_ensemble_walk_matches_oracle(cfg, seed):
     stats = cs.run_ensemble_walk(cs.generate_ensemble(cfg, seed), cs.EnsGpuBackend)
     # (tests/test_call_sequences_model.py, test_faithful_fake_passes_ensemble_walks: these walks meet them)
     cs.ens_conditions(cfg, stats, gpu=True)
+
+
+@pytest.mark.parametrize("seed", [1, 2])
+@pytest.mark.parametrize("cfg_name", list(cs.ENSQ_CONFIGS))
+def test_ensemble_query_walk_matches_oracle(cfg_name, seed):
+    stats = cs.run_ensemble_walk(cs.generate_ensemble_query(cfg_name, seed), cs.EnsGpuBackend)
+    cs.ensq_conditions(cfg_name, stats, gpu=True)

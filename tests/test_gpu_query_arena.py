@@ -9,9 +9,17 @@ Standard, and one CLR context (J = 8, 20 x 20) for the queries that accept CLR.
 
 Orders: ORDER is large layouts first (the restricted BMD with probabilities), then smaller ones, the largest top-k, and
 small ones again.  ASCENDING starts with the smallest layouts, so that on the 20 x 20 Standard map the arena regrows before
-almost every call: 10 pairs and one row of distances (4 KiB), evaluate (~9 KiB), similarity with its dense report
-(~33 KiB), the masked search with imputation (48 KiB), top-k with k = 5 (~51 KiB) and k = 64 (~640 KiB), the BMD with
-probabilities (~1 MiB).
+almost every call: 10 pairs and one row of distances (4 KiB), evaluate (~9 KiB), the masked evaluate (~29 KiB: the masked
+search's pieces and ~15 KiB of validity bytes, raw and packed), similarity with its dense report (~33 KiB), the masked
+search with imputation (48 KiB), top-k with k = 5 (~51 KiB), the masked top-k with k = 5 (~66 KiB), generate (~568 KiB: the
+BMD's 152 x 400 doubles, logits and records), top-k with k = 64 (~640 KiB), the masked top-k with k = 64 and blend
+(~697 KiB), the masked generate with 3 draws (~763 KiB), the BMD with probabilities (~950 KiB) and the masked BMD with
+probabilities (~965 KiB).  The figures are the sums of the pieces each call adds to its vsom_layout (the lay.add lines of
+csrc/vsom_topk.hip, vsom_bmd.hip, vsom_generate.hip, vsom_evaluate.hip, vsom_masked.hip) at N = 400, J = 37, B = 150 in one
+slice: seven node groups, a BMD pitch of 152 rows in two node chunks, validity bytes raw (150 x 37) and packed (150 x 64).
+
+The queries added since the arena -- the masked top-k with and without blend, the masked BMD, generate and its masked form
+with several draws, the masked evaluate -- are steps like the others; the masked ones refuse CLR and are left out there.
 
 vsom_bmu_topk_batch refuses a row range beyond the staged chunk before it allocates anything, and a slice's layout is
 bounded by the slice budget whatever the range, so no argument makes the arena's allocation fail on a context that holds
@@ -52,6 +60,8 @@ def inputs(tr, W, H, J):
          "continuous": (rng.random(J) < 0.85).astype(np.float32),
          "nodes": rng.integers(0, N, 10).astype(np.uint64),
          "rows": rng.integers(0, B, 10).astype(np.uint64)}
+    # (drawn behind the older arrays, which keep their values: uniforms and logits of generate and of 3 masked draws)
+    d.update(u3=rng.random((B, 3)), l=0.05 + 0.9 * rng.random((B, min(J, D))), l3=0.05 + 0.9 * rng.random((B, 3, J)))
     d["hits"][:3] = (5, 0, 2)
     d["valid"][:, 0] = 1                                                  # (every row keeps a valid column)
     d["mask"][0] = 1
@@ -81,14 +91,24 @@ STEPS = {
     "masked_one": lambda c, d: c.bmu_masked(d["mask"]),
     "bmd_range": lambda c, d: c.restricted_bmd(2, r0=7, r1=23),
     "similarity": lambda c, d: c.similarity(0, 3),
+    "topk_masked5": lambda c, d: c.bmu_topk_masked(5, d["valid"], min_hits=2),
+    "topk_masked_max_blend": lambda c, d: c.bmu_topk_masked(min(64, c.n_nodes), d["mask"], min_hits=2, blend=True),
+    "bmd_masked_probs": lambda c, d: c.restricted_bmd_masked(d["valid"], 2, u=d["u"], probs=True),
+    "generate": lambda c, d: c.generate(2, d["u"], d["l"]),
+    "generate_masked3": lambda c, d: c.generate_masked(d["valid"], 2, d["u3"], d["l3"], draws=3),
+    "evaluate_masked": lambda c, d: c.evaluate_masked(d["valid"], d["binary"], d["continuous"], min_hits=2),
 }
 ORDER = tuple(STEPS)
-ASCENDING = ("distances", "distances_row", "evaluate", "similarity_delta", "masked_fill", "topk5", "topk_max", "bmd_probs",
-             "masked_one", "bmd_range", "similarity")
+ASCENDING = ("distances", "distances_row", "evaluate", "evaluate_masked", "similarity_delta", "masked_fill", "topk5",
+             "topk_masked5", "generate", "topk_max", "topk_masked_max_blend", "generate_masked3", "bmd_probs",
+             "bmd_masked_probs", "masked_one", "bmd_range", "similarity")
+# the steps that refuse a CLR context: the masked search and every query built on the masked distance
+NO_CLR = ("masked_fill", "masked_one", "topk_masked5", "topk_masked_max_blend", "bmd_masked_probs", "generate_masked3",
+          "evaluate_masked")
 
 
 def steps_of(case, order):
-    return [s for s in order if not (case[0] == po.CLR and s.startswith("masked"))]   # (the masked search refuses CLR)
+    return [s for s in order if not (case[0] == po.CLR and s in NO_CLR)]
 
 
 def flat(res):
