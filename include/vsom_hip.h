@@ -1114,6 +1114,54 @@ int vsom_ensemble_bmu_topk_masked_batch(vsom_ensemble *e, const uint32_t *k /*[K
  * 0 when it would run its single call inside the ensemble call (or be refused); VSOM_ERR_INVALID for a null ensemble or
  * a member index out of range.  masked != 0: the masked call, which takes no CLR member. */
 int vsom_ensemble_topk_applies(const vsom_ensemble *e, size_t member, uint32_t k, int masked);
+/* Som::evaluate (Som.cpp:490-523), the validation loss, of every member on its own chunk in one call, over all columns
+ * (vsom_evaluate_batch per member) or over the valid columns only (vsom_evaluate_masked_batch per member): the number a
+ * sweep is ranked by.  binary_host[k] / continuous_host[k] hold member k's J_k column factors;
+ * out[k] holds member k's host pointers, each of which may be NULL.
+ * Plain call: covers every member with binary_host[k] != NULL -- every field of vsom_evaluate_out is optional, so the
+ * column array is what names a covered member; a member with a NULL binary_host[k] is SKIPPED: nothing is enqueued for it
+ * and out[k] is neither read nor written.  valid_host: NULL (every column of every member valid), or one entry per member:
+ * NULL or B_k x J_k bytes.  Standard, Median and CLR members are taken.  Per covered member every output is, bit for bit,
+ * that of
+ *   vsom_evaluate_batch(member k, 0, B_k, binary_host[k], continuous_host[k], valid_host ? valid_host[k] : NULL, &out[k])
+ * made on a context that is no member.  The call IS vsom_ensemble_bmu_batch's search for the covered members, as
+ * vsom_evaluate_batch is vsom_bmu_batch: their lastBMU / sqres are left as that call leaves them.
+ * Masked call: covers every member with valid_host[k] != NULL (B_k x J_k bytes, row-major, or J_k bytes when
+ * one_mask[k] != 0; one_mask NULL: all 0; a non-zero byte means valid); NULL: SKIPPED, as in
+ * vsom_ensemble_bmu_masked_batch.  min_hits NULL: all 0.  Per covered member every output is, bit for bit, that of
+ *   vsom_evaluate_masked_batch(member k, min_hits[k], 0, B_k, binary_host[k], continuous_host[k], valid_host[k],
+ *                              one_mask[k], &out[k])
+ * Read-only: every member's lastBMU, sqres, map, sigmaMap, S, weightMap, bmuHits and chunk are untouched.
+ * Both: what is stated at the two single calls holds word for word -- the search, the node-0 rule, the NaN rules, the
+ * select at invalid columns, the -99999 replacement, bsum's packet order, the accuracy statement for log; bsum is the
+ * same bits as the single call's because both kernels run one row body on the same logf.  *error is the running mean in
+ * row order, evaluated on the host.  A member with B_k = 0 writes *error = 0 and nothing else.  The host arrays are not
+ * read after the call returns.  Each call ends in one wait.
+ * The fast path: the covered members with B_k > 0 that vsom_ensemble_bmu_batch (masked: vsom_ensemble_bmu_masked_batch)
+ * searches in its one launch -- not custom, N * part_len <= 4096 (part_len: D, or D / 2 for CLR; masked: Standard / Median,
+ * N * D <= 4096) and an LDS need of 768 + 4 N D bytes within min(the device's limit per workgroup, 64 KiB) -- run in one
+ * launch per kind of ensemble_evaluate_many_kernel, one workgroup per (member, 64 rows): that search, and behind one
+ * barrier the row scoring of vsom_evaluate_batch's kernel, eight lanes per row, against the unit's row in LDS.
+ * vsom_ensemble_evaluate_applies reports it.  The column arrays (2 J_k floats) and the validity bytes of those members
+ * travel as one pinned image, copied once per call; their results (5 words per row, masked 6) return through the pinned
+ * buffers of the masked queries.  Every other covered member runs its single call inside the same call, while the
+ * launches are in flight.
+ * Refuses (VSOM_ERR_INVALID, naming the member, before anything is enqueued for any member; a refused call changes
+ * nothing): a null ensemble, binary_host, continuous_host or out array; masked: a null valid_host array; for a covered
+ * member: a null continuous_host[k] (masked: or binary_host[k]), a custom context, no chunk, the next chunk staged ahead
+ * over its rows; masked: a CLR context (the residual runs over column pairs). */
+int vsom_ensemble_evaluate_batch(vsom_ensemble *e, const float *const *binary_host /*[K][J_k]*/,
+                                 const float *const *continuous_host /*[K][J_k]*/,
+                                 const uint8_t *const *valid_host /*NULL, or [K]: NULL or B_k x J_k bytes*/,
+                                 const vsom_evaluate_out *out /*[K]*/);
+int vsom_ensemble_evaluate_masked_batch(vsom_ensemble *e, const uint64_t *min_hits /*[K], NULL: all 0*/,
+                                        const float *const *binary_host, const float *const *continuous_host,
+                                        const uint8_t *const *valid_host /*[K]*/, const int *one_mask /*[K], NULL: all 0*/,
+                                        const vsom_evaluate_masked_out *out /*[K]*/);
+/* 1 when member `member` would run in ensemble_evaluate_many_kernel (the fast path above, on its loaded chunk), 0 when it
+ * would run its single call inside the ensemble call (or be refused); VSOM_ERR_INVALID for a null ensemble or a member
+ * index out of range.  masked != 0: the masked call, which takes no CLR member. */
+int vsom_ensemble_evaluate_applies(const vsom_ensemble *e, size_t member, int masked);
 /* Som::updateUMatrix of every member: per member exactly what vsom_umatrix gives (also in the member's VSOM_BUF_UMATRIX
  * buffer: a later vsom_get_umatrix of the member returns it).  u_out: NULL, or one pointer per member (NULL entries
  * skipped, else room for that member's N doubles).  Members whose map has N * part_len <= 4096 are computed by one launch

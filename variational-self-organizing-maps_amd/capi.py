@@ -66,6 +66,7 @@ SYMBOLS = [
     "vsom_online_masked_tiny_applies", "vsom_ensemble_train_online_chunk_masked",
     "vsom_ensemble_bmu_masked_batch", "vsom_ensemble_similarity_masked_batch",
     "vsom_ensemble_bmu_topk_batch", "vsom_ensemble_bmu_topk_masked_batch", "vsom_ensemble_topk_applies",
+    "vsom_ensemble_evaluate_batch", "vsom_ensemble_evaluate_masked_batch", "vsom_ensemble_evaluate_applies",
 ]
 SCHEDULE_MAX_EPOCHS = 1024     # VSOM_SCHEDULE_MAX_EPOCHS: the epochs of one launch of a schedule call
 
@@ -351,6 +352,12 @@ def lib():
         L.vsom_ensemble_bmu_topk_masked_batch.argtypes = [vp, u32p, u64p, C.POINTER(u8p), C.POINTER(C.c_int),
                                                           C.POINTER(EnsembleTopkOut)]
         L.vsom_ensemble_topk_applies.argtypes = [vp, C.c_size_t, C.c_uint32, C.c_int]
+    if hasattr(L, "vsom_ensemble_evaluate_batch"):      # (VSOM_LIB may name an older build: tools/ensemble_evaluate_bench.py --lib)
+        u8p = C.POINTER(C.c_uint8)
+        L.vsom_ensemble_evaluate_batch.argtypes = [vp, C.POINTER(fp), C.POINTER(fp), C.POINTER(u8p), C.POINTER(EvaluateOut)]
+        L.vsom_ensemble_evaluate_masked_batch.argtypes = [vp, u64p, C.POINTER(fp), C.POINTER(fp), C.POINTER(u8p),
+                                                          C.POINTER(C.c_int), C.POINTER(EvaluateMaskedOut)]
+        L.vsom_ensemble_evaluate_applies.argtypes = [vp, C.c_size_t, C.c_int]
     _lib = L
     return L
 
@@ -1734,6 +1741,126 @@ class Ensemble:
         if rc < 0:
             check(rc)
         return bool(rc)
+
+    def _columns(self, name, a, covered):
+        """the column factors `name` (one array of J entries for all members, when every covered J agrees, or a list with
+        one array per member; an entry of a member that is not covered may be None) as the float32 arrays (None: not
+        covered) and the pointer array of the evaluate calls; ValueError before any call into the library"""
+        n = len(self.members)
+        if isinstance(a, (list, tuple)) and (len(a) == 0 or a[0] is None or np.ndim(a[0]) > 0):
+            if len(a) != n:
+                raise ValueError(f"{name}: {len(a)} arrays for {n} members")
+            per = list(a)
+        else:
+            per = [a] * n
+        fp = C.POINTER(C.c_float)
+        keep = []
+        for m, c in enumerate(self.members):
+            if not covered[m]:
+                keep.append(None)
+                continue
+            if per[m] is None:
+                raise ValueError(f"{name}: member {m} is covered and has no array")
+            v = np.ascontiguousarray(per[m], dtype=np.float32)
+            if v.shape != (c.in_len,):
+                raise ValueError(f"{name}: member {m}: shape {v.shape}, not ({c.in_len},)")
+            keep.append(v)
+        return keep, (fp * max(n, 1))(*[fp() if v is None else _f(v) for v in keep])
+
+    def _evaluate_outputs(self, covered, struct):
+        """the result dicts (None for a member that is not covered) and the array of `struct` over them"""
+        n = len(self.members)
+        res, outs = [], (struct * max(n, 1))()
+        for m, c in enumerate(self.members):
+            if not covered[m]:
+                res.append(None)
+                continue
+            B = c.chunk_size
+            r = {"bmu": np.empty(B, np.uint64), "dist": np.empty(B, np.float32), "bsum": np.empty(B, np.float32),
+                 "nrepl": np.empty(B, np.uint32), "error": np.zeros(1, np.float64)}
+            if struct is EvaluateMaskedOut:
+                r["nvalid"] = np.empty(B, np.uint32)
+            for name, ctype in struct._fields_:
+                setattr(outs[m], name, r[name].ctypes.data_as(ctype))
+            res.append(r)
+        return res, outs
+
+    def evaluate(self, binary, continuous, valid=None, members=None):
+        """Context.evaluate of every member's whole chunk in one call (vsom_ensemble_evaluate_batch): the validation loss a
+        sweep is ranked by.  binary, continuous: one array of J column factors for all members (every covered J must
+        agree) or a list with one array per member; valid: None, or a list with one entry per member -- None or that
+        member's B x J validity (nonzero = valid); members: None (every member) or the indices of the members to cover,
+        the others are skipped.  A list with one entry per member: the dict Context.evaluate returns (bmu, dist, bsum,
+        nrepl, error), or None for a skipped member.  ValueError before any call into the library.  Overwrites the
+        covered members' lastBMU / sqres like bmu_batch."""
+        n = len(self.members)
+        covered = [True] * n
+        if members is not None:
+            chosen = [int(m) for m in members]
+            if any(not 0 <= m < n for m in chosen):
+                raise ValueError(f"members must be indices in [0, {n})")
+            covered = [m in chosen for m in range(n)]
+        bkeep, bptrs = self._columns("binary", binary, covered)
+        ckeep, cptrs = self._columns("continuous", continuous, covered)
+        vkeep, vptrs = None, None
+        if valid is not None:
+            if isinstance(valid, np.ndarray) or not hasattr(valid, "__len__") or len(valid) != n:
+                raise ValueError(f"valid must be None or a list of one entry per member ({n}), None for a member without one")
+            u8p = C.POINTER(C.c_uint8)
+            vkeep = []
+            for m, (c, v) in enumerate(zip(self.members, valid)):
+                if v is None or not covered[m]:
+                    vkeep.append(None)
+                    continue
+                vb = np.ascontiguousarray(np.asarray(v) != 0, dtype=np.uint8)
+                if vb.shape != (c.chunk_size, c.in_len):
+                    raise ValueError(f"valid: member {m}: shape {vb.shape}, not ({c.chunk_size}, {c.in_len})")
+                vkeep.append(vb)
+            vptrs = (u8p * max(n, 1))(*[u8p() if v is None else v.ctypes.data_as(u8p) for v in vkeep])
+        res, outs = self._evaluate_outputs(covered, EvaluateOut)
+        check(lib().vsom_ensemble_evaluate_batch(self._h, bptrs, cptrs, vptrs, outs))
+        del bkeep, ckeep, vkeep
+        for r in res:
+            if r is not None:
+                r["error"] = float(r["error"][0])
+        return res
+
+    def evaluate_masked(self, valid, binary, continuous, min_hits=0):
+        """Context.evaluate_masked of every member's whole chunk in one call (vsom_ensemble_evaluate_masked_batch).  valid
+        and min_hits as in bmu_masked (a None entry skips the member); binary, continuous as in evaluate.  A list with one
+        entry per member: evaluate's dict with nvalid added, or None for a skipped member.  ValueError before any call
+        into the library.  Read-only."""
+        keep, vptrs, ones = self._validities(valid, none="a skipped member")
+        mh = self._min_hits(min_hits)
+        covered = [kv is not None for kv in keep]
+        bkeep, bptrs = self._columns("binary", binary, covered)
+        ckeep, cptrs = self._columns("continuous", continuous, covered)
+        res, outs = self._evaluate_outputs(covered, EvaluateMaskedOut)
+        check(lib().vsom_ensemble_evaluate_masked_batch(self._h, mh, bptrs, cptrs, vptrs, ones, outs))
+        del keep, bkeep, ckeep
+        for r in res:
+            if r is not None:
+                r["error"] = float(r["error"][0])
+        return res
+
+    def evaluate_applies(self, member, masked=False):
+        """would that member run in the one-launch kernel of evaluate / evaluate_masked (vsom_ensemble_evaluate_applies)?"""
+        rc = lib().vsom_ensemble_evaluate_applies(self._h, int(member), int(bool(masked)))
+        if rc < 0:
+            check(rc)
+        return bool(rc)
+
+    def validation_errors(self, binary, continuous, valid=None, members=None, masked=False, min_hits=0):
+        """the validation loss of every member on its chunk as one float64 array, NaN for a skipped member: what a sweep
+        sorts by.  masked=False: evaluate(binary, continuous, valid, members); masked=True: evaluate_masked(valid, binary,
+        continuous, min_hits), whose None entries of valid are the skipped members."""
+        if masked:
+            if members is not None:
+                raise ValueError("masked=True: the members are chosen by the None entries of valid")
+            got = self.evaluate_masked(valid, binary, continuous, min_hits=min_hits)
+        else:
+            got = self.evaluate(binary, continuous, valid=valid, members=members)
+        return np.array([np.nan if r is None else r["error"] for r in got], np.float64)
 
     def _rankable(self):
         """the members a topographic error exists for: at least 2 nodes and a chunk with rows"""

@@ -21,8 +21,11 @@
 // masked distance followed in the same workgroup by a per-row epilogue (nvalid, the imputed row, the similarity words).
 // vsom_ensemble_bmu_topk_batch and vsom_ensemble_bmu_topk_masked_batch keep, in the same workgroup
 // shape, each row's k smallest keys as a sorted list in LDS: one launch of ensemble_topk_many_kernel<kind, masked> per kind.
+// vsom_ensemble_evaluate_batch and vsom_ensemble_evaluate_masked_batch run the search and, in the same
+// workgroup, evaluate_kernel's row scoring against the unit's row in LDS: ensemble_evaluate_many_kernel<kind, masked>.
 #include "vsom_masked_dist.hpp"
 #include "vsom_sim_row.hpp"
+#include "vsom_eval_row.hpp"
 #include <algorithm>
 #include <cstring>
 
@@ -1701,6 +1704,344 @@ int vsom_ensemble_bmu_topk_masked_batch(vsom_ensemble *e, const uint32_t *k, con
             return ens_fail(m, "out->idx is null");
     }
     return ens_topk(e, k, min_hits, valid_host, one_mask, out);
+}
+
+// ================================================================================================================
+// the validation loss of every member, plain and over the valid columns
+// ================================================================================================================
+struct EnsEvalDesc {
+    DistArgs d;                  // plain: ensemble_bmu_many_kernel's operands; masked: xa = the staged rows (Xs), ma = the map
+    const float *x;              // the staged rows the scoring reads (Xs), pitch ldxs
+    const u64 *hits;             // masked: the candidates are node 0 and the nodes with hits >= min_hits
+    u64 min_hits;
+    const unsigned char *valid;  // the member's validity bytes in the call's image, vstride bytes per row (masked, 0: one row
+                                 // for all); plain: null when every column is valid
+    const float *binary, *continuous;   // [J] in the call's image
+    u64 *lastbmu;                // plain: the member's lastBMU / sqres, stored as ensemble_bmu_many_kernel stores them
+    float *sqres;
+    unsigned *rows;              // the member's per-row words in the pinned results: arrays of B entries -- bmu (2 words),
+                                 // dist, bsum, nrepl, and nvalid (masked)
+    int ldxs, vstride, B, N, C;
+};
+
+// vsom_evaluate_batch (MASKED: vsom_evaluate_masked_batch) for rows [64x, 64x + 64) of member y.
+// Phase 1 is the sibling's search: ensemble_bmu_many_kernel's (MASKED: ensemble_masked_many_kernel's) -- the model rows in
+// LDS, every (row, node) distance by an 8-lane group, the argmin as an LDS atomicMin on the (distance, index) key, a NaN at
+// node 0 pins the unit to 0 with distance NaN.
+// Phase 2, behind one barrier, is evaluate_kernel's row scoring in its geometry: eight lanes per row, so the 256 threads
+// take 32 rows per pass and two passes cover the tile.  The row body is the one evaluate_kernel runs (vsom_eval_row.inc: the
+// same operations in the same order on the same logf, hence the same bits), on x and the unit's row IN LDS -- the layout of
+// phase 1 keeps a CLR row's two parts side by side, so logical column d is element d of the row and nothing is gathered from
+// global memory behind the search's result.  Lane 0 of the eight stores the row's words; the plain form also stores the
+// member's lastBMU / sqres.  No LDS beyond the search's, no atomics in phase 2.  The two passes are one rolled loop: the
+// row body's registers are live once.  Residency in workgroups per CU, bound by the registers, is the sibling search's: the
+// plain forms reach it unasked (8 as ensemble_bmu_many_kernel, CLR 5); the masked form is held to
+// ensemble_masked_many_kernel's 7 by the second launch bound (it would take 74 registers, two past the step; nothing spills).
+template <int KIND, bool MASKED>
+__global__ __launch_bounds__(256, MASKED ? 7 : 1) void ensemble_evaluate_many_kernel(const EnsEvalDesc *__restrict__ descs)
+{
+    constexpr bool CLR = KIND == VSOM_CLR;
+    static_assert(!(CLR && MASKED), "the masked residual does not run over CLR's column pairs");
+    const EnsEvalDesc a = descs[blockIdx.y];
+    const int s0 = blockIdx.x * ENS_SCORE_ROWS;
+    if (s0 >= a.B)
+        return;                                          // (workgroup-uniform)
+    const int T = a.B - s0 < ENS_SCORE_ROWS ? a.B - s0 : ENS_SCORE_ROWS, N = a.N, L = a.d.L;
+    extern __shared__ __attribute__((aligned(16))) unsigned char ens_ev_smem[];
+    u64 *keys = reinterpret_cast<u64 *>(ens_ev_smem);             // [64]
+    int *nan0 = reinterpret_cast<int *>(keys + ENS_SCORE_ROWS);   // [64]
+    float *ml = reinterpret_cast<float *>(nan0 + ENS_SCORE_ROWS); // N rows of L values (CLR: A part, then B part)
+    const int tid = threadIdx.x;
+    const int rl = CLR ? 2 * L : L;
+    for (int i = tid; i < N * rl; i += 256) {
+        const int n = i / rl, e = i - n * rl;
+        ml[i] = e < L ? a.d.ma[(size_t)n * a.d.ldm + e] : a.d.mb[(size_t)n * a.d.ldm + e - L];
+    }
+    for (int s = tid; s < T; s += 256) {
+        keys[s] = ~0ull;
+        nan0[s] = 0;
+    }
+    __syncthreads();
+    {
+        const float *ma = ml, *mb = CLR ? ml + L : ml;
+        const int grp = tid >> 3, k = tid & 7;
+        for (int p = grp; p < T * N; p += 32) {
+            const int s = p / N, n = p - s * N;
+            const size_t row = (size_t)(s0 + s) * a.d.ldx;
+            float dd;
+            if constexpr (MASKED) {
+                // findRestrictedBmu (Som.cpp:316-322): node 0 seeds unconditionally, the others need the hits (group-uniform)
+                if (n > 0 && a.min_hits && a.hits[n] < a.min_hits)
+                    continue;
+                dd = masked_group_dist(a.d.xa + row, a.valid + (size_t)(s0 + s) * a.vstride, ml + (size_t)n * L, L, k);
+            } else {
+                dd = vsom_group_dist<CLR>(a.d.xa + row, a.d.xb + row, ma + (size_t)n * rl, mb + (size_t)n * rl, L, k);
+            }
+            if (k == 0) {
+                if (n == 0 && dd != dd)
+                    nan0[s] = 1;
+                atomicMin(&keys[s], vsom_key(dd, (uint32_t)n));
+            }
+        }
+    }
+    __syncthreads();
+    // the rows' scoring: eight tid >> 3 takes rows tid >> 3 and 32 + (tid >> 3)
+    const int c = tid & (EV_LANES - 1);
+    const size_t R = (size_t)a.B;
+#pragma unroll 1
+    for (int h = 0; h < T; h += EV_ROWS_PER_WG) {        // (workgroup-uniform)
+        const int sl = h + (tid >> 3);
+        const bool live = sl < T;
+        const int sr = live ? sl : T - 1;                // (a dead eight repeats the last row and stores nothing)
+        const u64 key = keys[sr];
+        const u64 idx = nan0[sr] ? 0ull : (key & 0xFFFFFFFFull);
+        const float sq = nan0[sr] ? __uint_as_float(0x7FC00000u) : __uint_as_float((uint32_t)(key >> 32));
+        const size_t i = (size_t)(s0 + sr);
+        const float *xr = a.x + i * a.ldxs;
+        const float *mr = ml + (size_t)idx * rl;
+        const unsigned char *vr = (MASKED || a.valid) ? a.valid + i * (size_t)a.vstride : nullptr;
+        auto model = [&](int d) -> float { return mr[d]; };
+#include "vsom_eval_row.inc"
+        unsigned nv = 0;
+        if constexpr (MASKED) {
+            for (int d = c; d < L; d += EV_LANES)
+                nv += vr[d] != 0 ? 1u : 0u;
+#pragma unroll
+            for (int m = 4; m >= 1; m >>= 1)
+                nv += __shfl_xor(nv, m);
+        }
+        if (live && c == 0) {
+            if constexpr (!MASKED) {
+                a.lastbmu[i] = idx;
+                a.sqres[i] = sq;
+            }
+            reinterpret_cast<u64 *>(a.rows)[i] = idx;
+            a.rows[2 * R + i] = __float_as_uint(sq);
+            a.rows[3 * R + i] = __float_as_uint(s);
+            a.rows[4 * R + i] = nrepl;
+            if constexpr (MASKED)
+                a.rows[5 * R + i] = nv;
+        }
+    }
+}
+
+// the LDS need of a member in ensemble_evaluate_many_kernel: that of the sibling search
+static size_t ens_eval_smem(const vsom_ctx *c)
+{
+    const size_t rl = c->transform == VSOM_CLR ? 2 * c->part_len : c->part_len;
+    return ENS_SCORE_ROWS * (sizeof(u64) + sizeof(int)) + (size_t)c->N * rl * sizeof(float);
+}
+
+// the fast-path rule (include/vsom_hip.h): would this member run in ensemble_evaluate_many_kernel?  The members that
+// vsom_ensemble_bmu_batch (masked: vsom_ensemble_bmu_masked_batch) searches in its one launch, with rows.
+static bool ens_eval_fast(const vsom_ensemble *e, const vsom_ctx *c, bool masked)
+{
+    if (c->cu || (masked && c->transform == VSOM_CLR) || !c->chunk_loaded || c->B == 0)
+        return false;
+    if ((size_t)c->N * c->part_len > 4096)
+        return false;
+    return ens_eval_smem(c) <= std::min(e->lds_limit, (size_t)64 << 10);      // (no attribute is raised)
+}
+
+int vsom_ensemble_evaluate_applies(const vsom_ensemble *e, size_t member, int masked)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    if (member >= e->m.size())
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: member index out of range");
+    return ens_eval_fast(e, e->m[member], masked != 0) ? 1 : 0;
+}
+
+// Both evaluate calls (the callers have made their argument checks): pout (vsom_evaluate_batch per member, covered: a
+// binary_host[k]) or mout (vsom_evaluate_masked_batch per member, covered: a valid_host[k]) is non-null.  The covered members
+// on the fast path go as one launch per kind; their column arrays and validity bytes form one pinned image in the launch's
+// descriptor slot, copied once.  Every other covered member with rows runs its single call while the launches run.
+static int ens_evaluate(vsom_ensemble *e, const uint64_t *min_hits, const float *const *binary_host,
+                        const float *const *continuous_host, const uint8_t *const *valid_host, const int *one_mask,
+                        const vsom_evaluate_out *pout, const vsom_evaluate_masked_out *mout)
+{
+    const bool masked = mout != nullptr;
+    const size_t n = e->m.size();
+    VSOM_HIP_CHECK(hipSetDevice(e->device));
+    EnsCall call(e);
+    std::vector<size_t> asked(n);
+    for (size_t k = 0; k < n; ++k)
+        asked[k] = masked ? valid_host[k] != nullptr : binary_host[k] != nullptr;   // (a skipped member is not touched)
+    if (int rc = join_members(e, asked.data(), true))
+        return rc;
+    const size_t words = masked ? EV_MROW_WORDS : EV_ROW_WORDS;
+    ens_scratch(e, sizeof(EnsEvalDesc));
+    std::vector<size_t> c_at(n, 0), v_at(n, 0), vbytes(n, 0), w_at(n, 0);
+    std::vector<const uint8_t *> vh(n, nullptr);         // the member's validity bytes, or null (plain: every column valid)
+    size_t itotal = 0, wtotal = 0;
+    for (size_t k = 0; k < n; ++k) {
+        const vsom_ctx *c = e->m[k];
+        if (!asked[k])
+            continue;
+        vh[k] = valid_host ? valid_host[k] : nullptr;
+        if (!ens_eval_fast(e, c, masked))
+            continue;
+        e->grp[k] = c->transform;
+        e->smem[k] = ens_eval_smem(c);
+        e->ext[k] = (unsigned)((c->B + ENS_SCORE_ROWS - 1) / ENS_SCORE_ROWS);
+        c_at[k] = itotal;
+        itotal += (2 * c->J * sizeof(float) + 15) / 16 * 16;
+        if (vh[k]) {
+            vbytes[k] = ((masked && one_mask && one_mask[k]) ? 1 : c->B) * (size_t)c->J;
+            v_at[k] = itotal;
+            itotal += (vbytes[k] + 15) / 16 * 16;
+        }
+        w_at[k] = wtotal;
+        wtotal += (c->B * words + 3) / 4 * 4;            // (16-byte steps: the 8-byte units lead each member's words)
+    }
+    int rc = VSOM_OK;
+    if (wtotal) {
+        if (int jrc = call.join(ENS_LAUNCHED))
+            return jrc;
+        // the slot ens_launch is about to take: its last launch has completed, so its image may be rewritten
+        auto &s = e->slot[e->next];
+        if (s.valid)
+            VSOM_HIP_CHECK(hipEventSynchronize(s.ev));
+        VSOM_ALLOC_CHECK(vsom_grow_set(nullptr, 0, {vsom_member(s.img_host, std::max<size_t>(itotal, 1)),
+                                                    vsom_member(s.img_dev, std::max<size_t>(itotal, 1))}));
+        // (no kernel of an earlier call is running: every call ends in a wait)
+        VSOM_ALLOC_CHECK(vsom_grow(e->mq_rows, wtotal, nullptr));
+        for (size_t k = 0; k < n; ++k) {
+            if (e->grp[k] < 0)
+                continue;
+            const size_t J = e->m[k]->J;
+            float *cols = reinterpret_cast<float *>(s.img_host.p + c_at[k]);
+            std::memcpy(cols, binary_host[k], J * sizeof(float));
+            std::memcpy(cols + J, continuous_host[k], J * sizeof(float));
+            if (vh[k])
+                std::memcpy(s.img_host.p + v_at[k], vh[k], vbytes[k]);
+        }
+        if (itotal)
+            VSOM_HIP_CHECK(hipMemcpyAsync(s.img_dev.p, s.img_host.p, itotal, hipMemcpyHostToDevice, call.ls));
+        for (size_t k = 0; k < n; ++k) {
+            if (e->grp[k] < 0)
+                continue;
+            const vsom_ctx *c = e->m[k];
+            const bool clr = c->transform == VSOM_CLR;
+            EnsEvalDesc a;
+            a.d.xa = clr ? c->XP.p : c->Xs.p;
+            a.d.xb = clr ? c->YP.p : c->Xs.p;
+            a.d.ldx = (int)(clr ? c->part_pitch : c->xpitch);
+            a.d.ma = c->map.p;
+            a.d.mb = clr ? c->map.p + c->part_pitch : c->map.p;
+            a.d.ldm = (int)c->pitch;
+            a.d.L = (int)c->part_len;
+            a.x = c->Xs.p;
+            a.hits = c->hits.p;
+            a.min_hits = masked && min_hits ? min_hits[k] : 0;
+            a.valid = vh[k] ? s.img_dev.p + v_at[k] : nullptr;
+            a.binary = reinterpret_cast<const float *>(s.img_dev.p + c_at[k]);
+            a.continuous = a.binary + c->J;
+            a.lastbmu = c->lastbmu.p;
+            a.sqres = c->sqres.p;
+            a.rows = e->mq_rows.p + w_at[k];
+            a.ldxs = (int)c->xpitch;
+            a.vstride = (masked && one_mask && one_mask[k]) ? 0 : (int)c->J;
+            a.B = (int)c->B;
+            a.N = (int)c->N;
+            a.C = (int)std::min<size_t>(c->J, c->D);
+            std::memcpy(e->desc.data() + k * sizeof(a), &a, sizeof(a));
+        }
+        static void (*const kernel[2][3])(const EnsEvalDesc *) = {
+            {ensemble_evaluate_many_kernel<VSOM_STANDARD, false>, ensemble_evaluate_many_kernel<VSOM_MEDIAN, false>,
+             ensemble_evaluate_many_kernel<VSOM_CLR, false>},
+            {ensemble_evaluate_many_kernel<VSOM_STANDARD, true>, ensemble_evaluate_many_kernel<VSOM_MEDIAN, true>, nullptr}};
+        rc = ens_launch(call, ENS_JOINED, 3, sizeof(EnsEvalDesc), ENS_MAX_Y, ens_always_ready,
+                        [masked](int kind, const void *d, unsigned cnt, size_t smem, unsigned tiles, hipStream_t st) -> int {
+                            hipLaunchKernelGGL(kernel[masked][kind], dim3(tiles, cnt), dim3(256), smem, st,
+                                               static_cast<const EnsEvalDesc *>(d));
+                            VSOM_HIP_CHECK_AS(hipGetLastError(), "ensemble_evaluate_many_kernel");
+                            return VSOM_OK;
+                        });
+    }
+    // the other members through their single calls, while the launches run (no rows: *error = 0 and nothing else)
+    for (size_t k = 0; k < n && !rc; ++k) {
+        vsom_ctx *c = e->m[k];
+        if (!asked[k] || e->grp[k] >= 0)
+            continue;
+        rc = masked ? launch_evaluate_masked(c, min_hits ? min_hits[k] : 0, 0, c->B, binary_host[k], continuous_host[k],
+                                             valid_host[k], one_mask ? one_mask[k] : 0, &mout[k])
+                    : launch_evaluate(c, 0, c->B, binary_host[k], continuous_host[k], vh[k], &pout[k]);
+    }
+    if ((rc = call.end(rc)))
+        return rc;
+    // results of the launched members: the kernel stored them into the pinned buffer
+    for (size_t k = 0; k < n; ++k) {
+        if (e->grp[k] < 0)
+            continue;
+        const size_t b = e->m[k]->B;
+        const unsigned *p = e->mq_rows.p + w_at[k];
+        double *error;
+        if (masked) {
+            const vsom_evaluate_masked_out &o = mout[k];
+            ens_mq_copy_out(p, b, {o.bmu, o.dist, o.bsum, o.nrepl, o.nvalid});
+            error = o.error;
+        } else {
+            const vsom_evaluate_out &o = pout[k];
+            ens_mq_copy_out(p, b, {o.bmu, o.dist, o.bsum, o.nrepl});
+            error = o.error;
+        }
+        if (error)
+            *error = ev_running_mean(reinterpret_cast<const float *>(p + 2 * b), reinterpret_cast<const float *>(p + 3 * b), b);
+    }
+    return VSOM_OK;
+}
+
+// what both evaluate calls check for a covered member: its column arrays, its kind, its chunk
+static int ens_evaluate_member(const vsom_ensemble *e, size_t k, bool masked, const float *binary, const float *continuous,
+                               std::string &buf)
+{
+    const vsom_ctx *c = e->m[k];
+    if (!binary || !continuous)
+        return ens_fail(k, "binary_host or continuous_host is null");
+    if (masked) {
+        if (const char *why = ens_masked_query_refusal(c, "vsom_evaluate_masked_batch", buf))
+            return ens_fail(k, why);
+        return VSOM_OK;
+    }
+    if (c->cu)
+        return ens_fail(k, "vsom_evaluate_batch: custom contexts are not supported");
+    if (const char *why = ens_rows_refusal(c))
+        return ens_fail(k, why);
+    return VSOM_OK;
+}
+
+int vsom_ensemble_evaluate_batch(vsom_ensemble *e, const float *const *binary_host, const float *const *continuous_host,
+                                 const uint8_t *const *valid_host, const vsom_evaluate_out *out)
+{
+    if (!e)
+        return vsom_fail(VSOM_ERR_INVALID, "null ensemble");
+    if (!binary_host || !continuous_host)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null binary_host or continuous_host array");
+    if (!out)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null out array");
+    std::string buf;
+    for (size_t k = 0; k < e->m.size(); ++k)
+        if (binary_host[k])
+            if (int rc = ens_evaluate_member(e, k, false, binary_host[k], continuous_host[k], buf))
+                return rc;
+    return ens_evaluate(e, nullptr, binary_host, continuous_host, valid_host, nullptr, out, nullptr);
+}
+
+int vsom_ensemble_evaluate_masked_batch(vsom_ensemble *e, const uint64_t *min_hits, const float *const *binary_host,
+                                        const float *const *continuous_host, const uint8_t *const *valid_host,
+                                        const int *one_mask, const vsom_evaluate_masked_out *out)
+{
+    if (int rc = ens_masked_query_arrays(e, valid_host, out))
+        return rc;
+    if (!binary_host || !continuous_host)
+        return vsom_fail(VSOM_ERR_INVALID, "vsom_ensemble: null binary_host or continuous_host array");
+    std::string buf;
+    for (size_t k = 0; k < e->m.size(); ++k)
+        if (valid_host[k])
+            if (int rc = ens_evaluate_member(e, k, true, binary_host[k], continuous_host[k], buf))
+                return rc;
+    return ens_evaluate(e, min_hits, binary_host, continuous_host, valid_host, one_mask, nullptr, out);
 }
 
 // Som::updateUMatrix of every member (vsom_umatrix.hip): members whose model and sigma rows fit LDS in one launch per kind

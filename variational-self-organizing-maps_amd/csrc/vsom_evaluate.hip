@@ -13,6 +13,8 @@
 //                    (p0[1] + p0[3]), and the at most three scalar-tail columns added one by one.  Accumulators start at +0:
 //                    +0 + p = p exactly for a square p, so every branch of Eigen's redux (C < 4, 4 <= C < 8, C >= 8) is this
 //                    one sequence.  No LDS, no atomics; lane 0 of the eight stores the row's five words.
+//                    (The row body -- ev_zero, ev_square, the column rule, the walk, the tail, the reduction -- lives in
+//                    vsom_eval_row.hpp / .inc, which ensemble_evaluate_many_kernel of vsom_ensemble.hip includes too.)
 //                    A column whose factor is an exact zero -- binary[d] == 0 with a finite val, or val == 0 with a finite
 //                    binary[d] -- has t = +-0 whatever m and x hold (be is finite after :512), and adding its +0 changes no
 //                    accumulator: such a column is skipped before anything of the row is gathered.  With the usual few
@@ -31,16 +33,9 @@
 // vsom_bmd_batch.  The tolerance of include/vsom_hip.h therefore takes L = 1 AS AN ASSUMPTION.
 // Against the host loop this call replaces in the C++ mirror (libm logf, a sequential sum) the value of a data set with
 // binary columns moves within that tolerance; with no binary column every t is +-0, bsum is 0 and the value is the same bits.
-#include "vsom_device.hpp"
+#include "vsom_eval_row.hpp"
 #include <algorithm>
-#include <cmath>
 #include <cstring>
-
-#define EV_LANES 8          // lanes per row: one per element of the two Packet4f accumulators
-#define EV_ROWS_PER_WG 32   // four wavefronts of eight rows
-#define EV_ROW_WORDS 5      // bmu (2), dist, bsum, nrepl
-#define EV_MROW_WORDS 6     // ... and nvalid (vsom_evaluate_masked_batch)
-#define EV_STEPS 4          // steps whose loads are in flight together
 
 struct EvArgs {
     const float *x;             // staged rows (Xs), pitch ldx
@@ -56,31 +51,6 @@ struct EvArgs {
     int J, C, N, R, vstride;
     int out0;                   // MASKED: the slice's first row in the call's results (r0 of the slice - r0 of the call)
 };
-
-// the factor of a column is an exact zero: t = +-0 for every finite be
-__device__ __forceinline__ bool ev_zero(float fb, float val)
-{
-    const float inf = __builtin_inff();
-    return (fb == 0.f && fabsf(val) < inf) || (val == 0.f && fabsf(fb) < inf);
-}
-
-// t * t of one column; counts a replaced term whose factor is non-zero
-__device__ __forceinline__ float ev_square(float x, float m, float fb, float val, uint32_t &nrepl)
-{
-    const float lm = logf(m);
-    const float om = 1.0f - m;
-    const float l1 = logf(om);
-    const float ox = 1.0f - x;
-    const float a = lm * x;
-    const float b = l1 * ox;
-    float be = a + b;
-    const bool repl = !(fabsf(be) < __builtin_inff());      // NaN or +-inf
-    be = repl ? -99999.0f : be;
-    const float tb = be * fb;
-    const float t = tb * val;
-    nrepl += (repl && fb != 0.f && val != 0.f) ? 1u : 0u;
-    return t * t;
-}
 
 // CLR: the model row has two parts, logical column d at (d / part_len) * part_pitch + d % part_len (as similarity_kernel<false>)
 // MASKED: [r0, r1) is one slice of the call; the search results and the packed validity rows are the slice's own.
@@ -98,19 +68,6 @@ __global__ __launch_bounds__(EV_LANES * EV_ROWS_PER_WG) void evaluate_kernel(EvA
     const float *mr = a.map + (size_t)b * a.ldm;
     const unsigned char *vr = MASKED ? a.valid + ri * (size_t)a.vstride
                                      : (a.valid ? a.valid + (size_t)(r - r0) * a.J : nullptr);
-    const int C = a.C, a2 = C / 8 * 8;
-
-    auto factor = [&](int d, float &fb, float &val) -> bool {      // false: the column adds +0
-        fb = a.binary[d];
-        const float fc = a.continuous[d];
-        if constexpr (MASKED) {
-            val = fc;
-            return vr[d] != 0 && !ev_zero(fb, val);
-        } else {
-            val = (vr && vr[d] == 0) ? 0.0f : fc;
-            return !ev_zero(fb, val);
-        }
-    };
     auto model = [&](int d) -> float {
         if constexpr (CLR) {
             const int part = d / a.part_len;
@@ -119,56 +76,7 @@ __global__ __launch_bounds__(EV_LANES * EV_ROWS_PER_WG) void evaluate_kernel(EvA
             return mr[d];
         }
     };
-
-    float acc = 0.f;
-    uint32_t nrepl = 0;
-    for (int d0 = c; d0 < a2; d0 += 8 * EV_STEPS) {
-        float fb[EV_STEPS], val[EV_STEPS], xv[EV_STEPS], mv[EV_STEPS];
-        bool on[EV_STEPS];
-#pragma unroll
-        for (int u = 0; u < EV_STEPS; ++u) {
-            const int d = d0 + 8 * u;
-            on[u] = d < a2 && factor(d, fb[u], val[u]);
-        }
-#pragma unroll
-        for (int u = 0; u < EV_STEPS; ++u) {
-            const int d = d0 + 8 * u;
-            if (on[u]) {
-                xv[u] = xr[d];
-                mv[u] = model(d);
-            }
-        }
-#pragma unroll
-        for (int u = 0; u < EV_STEPS; ++u)
-            if (on[u])
-                acc += ev_square(xv[u], mv[u], fb[u], val[u], nrepl);
-    }
-    // the one column behind the multiples of 8 that this lane owns: packet tail (C - a2 >= 4: lanes 0..3) or scalar tail
-    float q = 0.f;
-    {
-        const int d = a2 + c;
-        float fb, val;
-        if (d < C && factor(d, fb, val))
-            q = ev_square(xr[d], model(d), fb, val, nrepl);
-    }
-    const int rest = C - a2;                        // 0..7
-    const bool ptail = rest >= 4;
-    float s = acc + __shfl_xor(acc, 4);             // p0 += p1 (lanes 0..3)
-    if (ptail)
-        s += q;                                     // p0 += the packet tail (lanes 0..3)
-    s = s + __shfl_xor(s, 2);                       // lane 0: p0[0] + p0[2], lane 1: p0[1] + p0[3]
-    s = s + __shfl_xor(s, 1);                       // lane 0: (p0[0] + p0[2]) + (p0[1] + p0[3])
-    const int t0 = ptail ? 4 : 0, nt = rest - t0;   // the scalar tail: lanes t0 .. t0 + nt - 1, nt <= 3
-    const int base = (int)(threadIdx.x & 63) & ~(EV_LANES - 1);
-#pragma unroll
-    for (int j = 0; j < 3; ++j) {
-        const float qj = __shfl(q, base + t0 + j);
-        if (j < nt)
-            s += qj;
-    }
-#pragma unroll
-    for (int m = 4; m >= 1; m >>= 1)
-        nrepl += __shfl_xor(nrepl, m);
+#include "vsom_eval_row.inc"
     if (live && c == 0) {
         const size_t i = (size_t)(r - r0) + (MASKED ? (size_t)a.out0 : 0), R = (size_t)a.R;
         reinterpret_cast<u64 *>(a.rows)[i] = a.lastbmu[ri];
@@ -197,15 +105,6 @@ static EvArgs ev_args(const vsom_ctx *c, size_t C, size_t rows, const float *col
     a.N = (int)c->N;
     a.R = (int)rows;
     return a;
-}
-
-// Som.cpp:519, the running mean in row order
-static double ev_running_mean(const float *dist, const float *bsum, size_t rows)
-{
-    double error = 0;
-    for (size_t i = 0; i < rows; ++i)
-        error += 1.0 / ((double)i + 1.0) * ((double)dist[i] + std::sqrt((double)bsum[i]) - error);
-    return error;
 }
 
 int launch_evaluate(vsom_ctx *c, size_t r0, size_t r1, const float *binary_host, const float *continuous_host,
